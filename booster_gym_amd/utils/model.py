@@ -3,10 +3,12 @@
 Same architecture and `state_dict` key names as reference `utils/model.py:5-36` (so checkpoints and the exported
 TorchScript actor interoperate): `critic.{0,2,4,6}`, `actor.{0,2,4,6}`, `logstd`; actor 47-256-128-128-12,
 critic (47+14)-256-256-128-1, ELU, state-independent log-std initialised to -2.
-GEMMs run through PyTorch-ROCm (hipBLASLt / rocBLAS, fp32 MFMA); the rollout-time inference + sampling is one
-fused HIP launch (`sample_actions` -> bg_actor_sample).
+The PPO update's GEMMs run on hand-written HIP kernels (MLPTrainer: the chained hidden layers, the grouped weight
+gradients), in the form its NetPlan names; the rollout-time inference + sampling is one fused HIP launch
+(`sample_actions` -> bg_actor_sample).
 """
 import ctypes
+from typing import NamedTuple
 
 import torch
 
@@ -50,6 +52,33 @@ def plan_wgrad_slices(shapes, rows, workgroups=256, share_rows=True):
     return s, tw
 
 
+class NetPlan(NamedTuple):
+    """The kernels one network's passes run in an update (plan_network); every branch of MLPTrainer reads it (MLPTrainer.plan)."""
+    fwd: str         # hidden layers: "chain_split" / "chain" (one launch: bf16 splits / fp32 MFMA), "layer_split" / "layer" (one launch per layer), "library"
+    bwd: str         # backward-data of the hidden layers: "chain_split" (one launch), "layer_split" / "layer" (one launch per layer), "library"
+    alternate: bool  # odd slabs of the chained split kernels accumulate the negated sums (MLPTrainer.CHAIN_ALTERNATE)
+    terms: int       # products of the per-layer split kernels ("layer_split": MLPTrainer.SPLIT)
+    grouped: tuple   # per layer: its weight gradient runs in the grouped launch (GroupedWeightGrad); False: library GEMMs
+
+    @property
+    def chained(self):
+        return self.fwd in ("chain", "chain_split")
+
+
+def plan_network(widths, kin, rows, split, fused, chain, chain_split, chain_split_bwd, alternate, fused_wgrad):
+    """NetPlan of an MLP of layer widths `widths` (input, hidden..., output) whose input is zero-padded to `kin` columns and whose backward pass
+    differentiates `rows` rows, under MLPTrainer's switches (SPLIT, FUSED, CHAIN, CHAIN_SPLIT, CHAIN_SPLIT_BWD, CHAIN_ALTERNATE, FUSED_WGRAD).  Pure: no
+    tensors, no device.  The chained kernels take the reference's widths on a zero-padded 64-column input."""
+    chainable = chain and fused and not split and kin == 64 != widths[0] and tuple(widths[1:-1]) in ((256, 128, 128), (256, 256, 128))
+    per_layer = ("layer_split" if split else "layer") if fused else "library"
+    fwd = ("chain_split" if chain_split else "chain") if chainable else per_layer
+    bwd = "chain_split" if fwd == "chain_split" and chain_split_bwd else per_layer
+    # the grouped kernel's shapes: output widths a multiple of 128, input widths 64 or a multiple of 128, an even batch of 64 rows or more
+    grouped = tuple(bool(fused_wgrad and fused) and co % 128 == 0 and (ci == 64 or ci % 128 == 0) and rows % 2 == 0 and rows >= 64
+                    for ci, co in zip((kin,) + tuple(widths[1:-1]), widths[1:]))
+    return NetPlan(fwd, bwd, bool(alternate), int(split) if fused else 0, grouped)
+
+
 class GroupedWeightGrad:
     """All deferred weight gradients of several MLPTrainers in one launch pair (bg_mlp_weight_grad_group)."""
 
@@ -61,21 +90,19 @@ class GroupedWeightGrad:
         self._key, self._arr, self._scratch = None, None, None
         self.timed_events = None
 
-    def run(self, trainers, finish=True):
-        """finish = False: the main kernel only (bg_mlp_weight_grad_group_partial); returns (descriptor array, count) for bg_update_tail, which sums the
-        slices inside the mini-epoch's last launch -- or None where that form does not apply (split mode, no supported layer) and the finished
-        gradients have been written as usual."""
+    def run(self, trainers, split, partial):
+        """The launch of every pending weight gradient in the form the UpdatePlan names: split = 0 the fp32-MFMA kernel (bg_wgrad.hip), 6 / 9 the
+        bf16-split kernel with that many products (bg_wgrad_split.hip: the waves of a workgroup share their rows through LDS, all tiles of a layer in one
+        workgroup).  partial: the main kernel only (..._partial); returns (descriptor array, count) for bg_update_tail, which sums the slices inside
+        the mini-epoch's last launch.  Otherwise the finished gradients are written and None is returned."""
         probs = [p for tr in trainers for p in tr.pending_wgrad_problems()]
         if not probs:
             return None
-        key = (MLPTrainer.SPLIT, MLPTrainer.WGRAD_SPLIT) + tuple((g.data_ptr(), a.data_ptr(), dw.data_ptr(), g.shape[0], co, ci, cr) for g, a, dw, co, ci, cr in probs)
-        if key != self._key:  # buffers are static: built once
+        key = (split,) + tuple((g.data_ptr(), a.data_ptr(), dw.data_ptr(), g.shape[0], co, ci, cr) for g, a, dw, co, ci, cr in probs)
+        if key != self._key:  # buffers are static: built once per form
             rows = probs[0][0].shape[0]
-            # split mode (bg_mlp_weight_grad_group_split): the waves of a workgroup share their rows through LDS, all tiles of a layer in one workgroup
-            # (MLPTrainer.WGRAD_SPLIT: the split launch behind the chained kernels, its finish inside bg_update_tail like the fp32 launch's)
-            chained = all(tr._chain_split_bwd() for tr in trainers)
-            self.split = (MLPTrainer.SPLIT or (MLPTrainer.WGRAD_SPLIT if chained else 0)) if rows % 32 == 0 and rows >= 128 and all((co, ci) in ((256, 256), (128, 256), (128, 128), (256, 64)) for _, _, _, co, ci, _ in probs) else 0
-            slices, tw = plan_wgrad_slices([(co, ci) for _, _, _, co, ci, _ in probs], rows, self.workgroups, share_rows=self.share_rows or bool(self.split))
+            self.split = split
+            slices, tw = plan_wgrad_slices([(co, ci) for _, _, _, co, ci, _ in probs], rows, self.workgroups, share_rows=self.share_rows or bool(split))
             self._scratch = [torch.empty(sl * co * ci, dtype=torch.float32, device=probs[0][0].device) for sl, (_, _, _, co, ci, _) in zip(slices, probs)]
             arr = (_lib.WgradProblem * len(probs))()
             for k, ((g, a, dw, co, ci, cr), sl) in enumerate(zip(probs, slices)):
@@ -86,15 +113,8 @@ class GroupedWeightGrad:
         if ev is not None:  # bench.py: HIP events on the launch stream around the launch pair
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-        partial = not finish and (not self.split or not MLPTrainer.SPLIT)
-        if self.split and partial:
-            _lib.check(_lib.load().bg_mlp_weight_grad_group_split_partial(self._arr, len(probs), self.split, _lib.current_stream_ptr()), "bg_mlp_weight_grad_group_split_partial")
-        elif self.split:
-            _lib.check(_lib.load().bg_mlp_weight_grad_group_split(self._arr, len(probs), self.split, _lib.current_stream_ptr()), "bg_mlp_weight_grad_group_split")
-        elif partial:
-            _lib.check(_lib.load().bg_mlp_weight_grad_group_partial(self._arr, len(probs), _lib.current_stream_ptr()), "bg_mlp_weight_grad_group_partial")
-        else:
-            _lib.check(_lib.load().bg_mlp_weight_grad_group(self._arr, len(probs), _lib.current_stream_ptr()), "bg_mlp_weight_grad_group")
+        name = "bg_mlp_weight_grad_group" + ("_split" if split else "") + ("_partial" if partial else "")
+        _lib.check(getattr(_lib.load(), name)(self._arr, len(probs), *((split,) if split else ()), _lib.current_stream_ptr()), name)
         if ev is not None:
             e1.record()
             # algorithmic flops: the REAL input columns (47 / 61 of the zero-padded 64 of the first layers)
@@ -104,12 +124,14 @@ class GroupedWeightGrad:
 
 class MLPTrainer:
     """Hand-scheduled forward / backward of one of the two ELU MLPs for the full-batch PPO update (replaces autograd for
-    reference utils/runner.py:132,147,163).  Same arithmetic as torch's Linear/ELU autograd, different schedule:
-      * forward: addmm (bias in the GEMM epilogue) + in-place ELU, activations kept for the backward;
-      * backward per layer: one fused pass `g <- g * elu'(a)` + bias gradient (bg_elu_backward_colsum), the weight gradient as a
-        split-K batched GEMM (`bmm` over S slices of the batch, then a sum) -- hipBLASLt's single GEMM with K = 98,304 runs at
-        8-45 TF/s, the split form at 60-110 TF/s on MI355X -- and dX = g @ W;
+    reference utils/runner.py:132,147,163).  Same arithmetic as torch's Linear/ELU autograd, different schedule, in the form `plan` names (a NetPlan,
+    set by the runner once per rollout / update; the class attributes below are its switches):
+      * forward: the three hidden layers as ONE launch, activations handed on in registers and kept for the backward (bg_mlp_chain_split.hip, the
+        default; bg_mlp_chain.hip on the fp32 matrix pipe), or one fused Linear + bias + ELU launch per layer (bg_mlp.hip / bg_mlp_split.hip);
+      * backward-data: dX = g W, ELU' and the bias gradients of the hidden layers as one launch (bg_mlp_chain_split_bwd.hip) or one per layer;
+      * weight gradients: deferred, all hidden layers of both networks in one grouped launch (GroupedWeightGrad);
       * gradients are WRITTEN into the parameters' `.grad` views of the flat Adam buffer (no AccumulateGrad adds, no zero_grad).
+    The "library" forms (torch GEMMs + bg_elu_backward_colsum, split-K bmm weight gradients) serve other widths and the tests that compare forms.
     """
 
     # Hidden layers with K in {64, 128, 256} and N % 128 == 0 run on the hand-written fused fp32-MFMA layer (bg_mlp.hip: bias + ELU in the GEMM
@@ -124,12 +146,18 @@ class MLPTrainer:
     # The grouped weight-gradient launch on the bf16 matrix pipe as well (bg_wgrad_split.hip: exact 3-way splits, all 9 products, the sub-ranges of the
     # batch alternating the sign of the accumulation; its error against float64 is 0.84-0.89 of the fp32-MFMA launch's and it is 0.4 ms per iteration
     # faster in the loop: profiles/r06_wgrad_split_*).  BG_WGRAD_SPLIT=0: the fp32-MFMA launch (bg_wgrad.hip).  Applies behind the chained split kernels
-    # only (GroupedWeightGrad.run); shapes outside the split kernel's four take the fp32 launch.
+    # only (UpdatePlan.wgrad); shapes outside the split kernel's four take the fp32 launch.
     WGRAD_SPLIT = int(__import__("os").environ.get("BG_WGRAD_SPLIT", "9"))
 
-    @classmethod
-    def _fusable(cls, k_in, n_out):
-        return cls.FUSED and k_in in (64, 128, 256) and n_out % 128 == 0
+    @staticmethod
+    def _fusable(k_in, n_out):
+        """Shapes of the per-layer forward kernels (bg_mlp.hip, bg_mlp_split.hip)."""
+        return k_in in (64, 128, 256) and n_out % 128 == 0
+
+    @staticmethod
+    def bwd_fusable(c_out, c_in):
+        """Shapes of the per-layer backward-data kernels (bg_mlp_layer_backward*); other layers take torch.mm + bg_elu_backward_colsum."""
+        return c_out in (128, 256) and c_in % 128 == 0
 
     # The forward pass of the three hidden layers as one launch (bg_mlp_chain_forward) where the widths are the reference's (CHAIN = False: one launch
     # per layer)
@@ -148,7 +176,7 @@ class MLPTrainer:
     CHAIN_ALTERNATE = __import__("os").environ.get("BG_CHAIN_ALTERNATE", "1") == "1"
 
     def _chain_split(self):
-        return self.CHAIN_SPLIT and self._chainable()
+        return self.plan.fwd == "chain_split"
 
     def _fresh_planes(self):
         """The bf16 planes of the three hidden layers' weights (what the chained split kernel reads): created on first use; rewritten from the
@@ -166,7 +194,7 @@ class MLPTrainer:
 
     def _chain_split_bwd(self):
         """Does backward_hidden run as ONE launch on the bf16 matrix pipe (bg_mlp_chain_split_bwd.hip)?  Same widths as the chained forward."""
-        return self.CHAIN_SPLIT_BWD and self._chain_split()
+        return self.plan.bwd == "chain_split"
 
     def _fresh_planes_t(self):
         """The bf16 planes of the transposed weights of hidden layers 2 and 1 (what the chained backward kernel reads), as _fresh_planes."""
@@ -187,25 +215,11 @@ class MLPTrainer:
         PT = self._fresh_planes_t()
         n1, n2, n3 = ls[0].weight.shape[0], ls[1].weight.shape[0], ls[2].weight.shape[0]
         slabs = (B + 127) // 128
-        wg = self.chain_bwd_workgroups if 0 < self.chain_bwd_workgroups < slabs else slabs
         if self.chain_colsum is None or self.chain_colsum.numel() < slabs * 4 * (n1 + n2):  # one record of column sums per (slab, wave)
             self.chain_colsum = torch.empty(slabs * 4 * (n1 + n2), dtype=torch.float32, device=g.device)
         self._pending_wgrad = [(2, g), (1, self.gin[2]), (0, self.gin[1])]
-        return _lib.MlpChainSplitBwd(B, n1, n2, n3, int(self.chain_bwd_workgroups), int(self.CHAIN_ALTERNATE), p(g), p(PT[2]), p(PT[1]), p(self.acts[1]), p(self.acts[0]), p(self.gin[2]),
+        return _lib.MlpChainSplitBwd(B, n1, n2, n3, int(self.chain_bwd_workgroups), int(self.plan.alternate), p(g), p(PT[2]), p(PT[1]), p(self.acts[1]), p(self.acts[0]), p(self.gin[2]),
                                      p(self.gin[1]), p(self.chain_colsum), p(ls[1].bias.grad), p(ls[0].bias.grad))
-
-    def _chainable(self):
-        ls = self.layers
-        return (self.CHAIN and self.FUSED and not self.SPLIT and len(ls) == 4 and self._kin == 64 and self.w0pad is not None
-                and tuple(l.weight.shape[0] for l in ls[:3]) in ((256, 128, 128), (256, 256, 128))
-                and ls[1].weight.shape[1] == ls[0].weight.shape[0] and ls[2].weight.shape[1] == ls[1].weight.shape[0])
-
-    def chainable_for(self, x, train_rows=None):
-        """Will forward_hidden(x, train_rows) run the chained kernel (and with it a `value_head`)?"""
-        B = x.shape[0] if train_rows is None else train_rows
-        if self._B != B or self._rows != x.shape[0] or self._kin != x.shape[1]:
-            self._alloc(x.shape[0], B, x.device, x.shape[1])
-        return self._chainable()
 
     def _chain_descriptor(self):
         """bg_mlp_chain of this network's hidden layers on the input of the forward pass in progress (self.x)."""
@@ -217,7 +231,7 @@ class MLPTrainer:
         if self._chain_split():
             P = self._fresh_planes()
             return _lib.MlpChainSplit(self.x.shape[0], self._kin, ls[0].weight.shape[0], ls[1].weight.shape[0], ls[2].weight.shape[0], int(self.chain_workgroups),
-                                      int(self.CHAIN_ALTERNATE), 0, p(self.x), p(P[0]), p(P[1]), p(P[2]), p(ls[0].bias), p(ls[1].bias), p(ls[2].bias), p(self.acts[0]), p(self.acts[1]),
+                                      int(self.plan.alternate), 0, p(self.x), p(P[0]), p(P[1]), p(P[2]), p(ls[0].bias), p(ls[1].bias), p(ls[2].bias), p(self.acts[0]), p(self.acts[1]),
                                       p(self.acts[2]), p(vw), p(vb), p(vo))
         if not self.mirror_fresh:
             self.w0pad[:, : ls[0].weight.shape[1]].copy_(ls[0].weight)
@@ -265,12 +279,6 @@ class MLPTrainer:
         if d.v_out:
             d.v_out = d.v_out + 4 * row0
         return d
-
-    @staticmethod
-    def forward_rows_group(jobs):
-        """jobs = [(trainer, row0, nrows), ...]: the chained forward of those rows of every trainer's prepared pass in ONE launch (at most 4)."""
-        descs = [tr.chain_rows_descriptor(r0, nr) for tr, r0, nr in jobs]
-        MLPTrainer.launch_chain(descs)
 
     @staticmethod
     def forward_hidden_group(jobs):
@@ -337,6 +345,7 @@ class MLPTrainer:
         self.chain_bwd_workgroups = 0  # ... of the chained backward launch
         # (weight [N3], bias [1], out [rows]): a scalar output layer evaluated by the chained forward kernel itself (the critic's values); None: not
         self.value_head = None
+        self.plan = None  # the NetPlan this network's passes follow: set by the runner before each rollout / update
 
     def _split(self, B):
         s = self.max_split
@@ -355,10 +364,7 @@ class MLPTrainer:
         B_pad = (B + 127) // 128 * 128  # (whole 128-row slabs: the chained backward kernel stores every slab in full)
         self.gin = [None] + [torch.empty(B_pad, l.weight.shape[1], dtype=torch.float32, device=dev)[:B] for l in self.layers[1:]]
         self.cs = [torch.empty(((B + 127) // 128) * l.weight.shape[0], dtype=torch.float32, device=dev) for l in self.layers]
-        # weight gradients: hand-written split-over-the-batch MFMA kernel (bg_mlp_weight_grad) where the shape allows, scratch = slices x dW
-        self.wg_slices = [self._wgrad_slices(B, l.weight.shape[0], k_in if i == 0 else l.weight.shape[1]) for i, l in enumerate(self.layers)]
-        self.dw = [torch.empty(self.wg_slices[i] or self._S, l.weight.shape[0], k_in if i == 0 else l.weight.shape[1], dtype=torch.float32, device=dev)
-                   for i, l in enumerate(self.layers)]
+        self.dw = [None] * len(self.layers)  # slices x dW of the library weight gradients (_weight_grad), created on first use
         self.wt = [None] * len(self.layers)  # transposed weights for the fused backward kernel
         # True while w0pad and wt ARE the current weights: the optimiser launch keeps them current (mirror_descriptors); False makes forward /
         # backward copy them first.  The owner of the optimiser sets it (utils/runner.py) and clears it wherever weights change by other means.
@@ -380,18 +386,6 @@ class MLPTrainer:
     FUSED_WGRAD = True
     WGRAD_WORKGROUPS = 256  # one 4-wave workgroup per CU
 
-    @classmethod
-    def _wgrad_slices(cls, B, c_out, c_in):
-        """Number of batch slices for bg_mlp_weight_grad (0 = shape not supported: library GEMM).  One workgroup per (128 x 128 output tile,
-        slice); slices a multiple of 8 (same-slice tiles share an XCD); runs of 16 row pairs per wave keep the MFMA loop free of idle trips."""
-        if not (cls.FUSED_WGRAD and cls.FUSED) or c_out % 128 or (c_in != 64 and c_in % 128) or B % 2 or B < 64:
-            return 0
-        ntiles = (c_out // 128) * max(1, c_in // 128)
-        s = max(8, cls.WGRAD_WORKGROUPS // ntiles // 8 * 8)
-        while s > 8 and s * 4 > (B // 2) // 16:  # 4 waves per slice, each at least one run of 16 row pairs where the batch allows it
-            s -= 8
-        return s
-
     def forward_hidden(self, x, train_rows=None):
         """All layers but the output layer: returns the activations of the last hidden (ELU) layer [rows, width].  The output layer then runs
         fused with the loss (bg_actor_head / bg_critic_head_*), and `backward_hidden` takes over from the gradient those kernels produce."""
@@ -399,14 +393,12 @@ class MLPTrainer:
 
     def forward(self, x, train_rows=None, _stop_before_output=False):
         """x [rows, in (possibly zero-padded)].  The first `train_rows` rows (default: all) are the batch the backward pass differentiates."""
-        B = x.shape[0] if train_rows is None else train_rows
-        if self._B != B or self._rows != x.shape[0] or self._kin != x.shape[1]:
-            self._alloc(x.shape[0], B, x.device, x.shape[1])
-        self.x, h = x, x
+        self.prepare(x, train_rows)
+        h = x
         last = len(self.layers) - 1
         lib, stream = _lib.load(), _lib.current_stream_ptr()
         first = 0
-        if self._chainable():
+        if self.plan.chained:
             # the three hidden layers in ONE launch, activations handed on in registers (bg_mlp_chain.hip); bit-identical to the per-layer launches
             timed = self.timed_layer is not None
             if timed:  # bench.py: HIP events on the launch stream around this one kernel
@@ -416,29 +408,26 @@ class MLPTrainer:
             self.launch_chain([d])
             if timed:
                 e1.record()
-                self.timed_events.append((e0, e1, x.shape[0], self._kin, tuple(l.weight.shape[0] for l in self.layers[:3]), "chain_split" if self._chain_split() else "chain"))
+                self.timed_events.append((e0, e1, x.shape[0], self._kin, tuple(l.weight.shape[0] for l in self.layers[:3]), self.plan.fwd))
             first, h = 3, self.acts[2]
-        for i, l in enumerate(self.layers):
-            if i < first:
-                continue
-            if i == last and _stop_before_output:
-                break
+        for i in range(first, last if _stop_before_output else last + 1):
+            l = self.layers[i]
             n_out, k_in = l.weight.shape
             w = l.weight
-            if self.SPLIT and i < last and self._fusable(self._kin if i == 0 else k_in, n_out):
+            if self.plan.fwd == "layer_split" and i < last and self._fusable(self._kin if i == 0 else k_in, n_out):
                 kp = self._kin if i == 0 else k_in
                 if self.planes[i] is None:
                     self.planes[i] = torch.empty(n_out * kp * 3, dtype=torch.int16, device=h.device)
                 _lib.check(lib.bg_mlp_split_weights(n_out, kp, _lib.ptr(l.weight), k_in, n_out, k_in, 0, _lib.ptr(self.planes[i]), stream), "bg_mlp_split_weights")
                 _lib.check(lib.bg_mlp_layer_forward_split(h.shape[0], kp, n_out, _lib.ptr(h), _lib.ptr(self.planes[i]), _lib.ptr(l.bias), _lib.ptr(self.acts[i]),
-                                                          1, self.SPLIT, stream), "bg_mlp_layer_forward_split")
+                                                          1, self.plan.terms, stream), "bg_mlp_layer_forward_split")
                 h = self.acts[i]
                 continue
             if i == 0 and self.w0pad is not None:
                 if not self.mirror_fresh:
                     self.w0pad[:, :k_in].copy_(l.weight)  # weights change every optimiser step; 16k floats
                 w, k_in = self.w0pad, self._kin
-            if i < last and self._fusable(k_in, n_out):
+            if i < last and self.plan.fwd != "library" and self._fusable(k_in, n_out):
                 # hand-written fp32-MFMA layer with bias + ELU in the epilogue (bg_mlp.hip)
                 timed = self.timed_layer is not None and (i == self.timed_layer or (isinstance(self.timed_layer, (tuple, list, set)) and i in self.timed_layer))
                 if timed:  # bench.py: HIP events on the launch stream around this one kernel
@@ -505,7 +494,7 @@ class MLPTrainer:
         """(G, A, dW, C_out, C_in (padded), C_in_real) of every deferred weight gradient, and clears the list (for the grouped launch)."""
         out = []
         for i, g in self._pending_wgrad:
-            if not self.wg_slices[i]:  # shape outside the kernel's range: the library path, now
+            if not self.plan.grouped[i]:  # shape outside the kernel's range: the library path, now
                 self._weight_grad(i, g)
                 continue
             l = self.layers[i]
@@ -515,16 +504,14 @@ class MLPTrainer:
         return out
 
     def _weight_grad(self, i, g):
-        lib, stream = _lib.load(), _lib.current_stream_ptr()
+        """Library path of one layer's weight gradient: a split-K batched GEMM over S slices of the batch, then a sum."""
         B, S = self._B, self._S
         l = self.layers[i]
         a_in = (self.acts[i - 1] if i > 0 else self.x)[:B]
         C_out, C_in = l.weight.shape
-        if self.wg_slices[i]:
-            # dW = G^T A in one hand-written launch pair, written straight into the flat gradient buffer (padded input columns dropped)
-            _lib.check(lib.bg_mlp_weight_grad(B, C_out, a_in.shape[1], C_in, _lib.ptr(g), _lib.ptr(a_in), _lib.ptr(l.weight.grad), _lib.ptr(self.dw[i]),
-                                              self.wg_slices[i], stream), "bg_mlp_weight_grad")
-        elif i == 0 and self.w0pad is not None:  # padded input columns: their gradient columns are dropped
+        if self.dw[i] is None:
+            self.dw[i] = torch.empty(S, C_out, a_in.shape[1], dtype=torch.float32, device=g.device)
+        if i == 0 and self.w0pad is not None:  # padded input columns: their gradient columns are dropped
             torch.bmm(g.view(S, B // S, C_out).transpose(1, 2), a_in.view(S, B // S, self._kin), out=self.dw[0])
             torch.sum(self.dw[0], dim=0, out=self.dw0sum)
             l.weight.grad.copy_(self.dw0sum[:, :C_in])
@@ -537,7 +524,7 @@ class MLPTrainer:
         or the zero-padded first layer of the fp32 chain; the transposed hidden layers of the backward kernels): handed to bg_optimizer_step, which then writes them together with the parameters.  `flat`: the optimiser's flat
         parameter buffer (the weights are views of it).  Only buffers that exist are listed (they are created by the first forward / backward)."""
         out = []
-        if self.SPLIT or not self.FUSED:
+        if self.plan.fwd in ("layer_split", "library"):
             return out
         split = self._chain_split() and self.cplanes[0] is not None
         for i, l in enumerate(self.layers):
@@ -566,15 +553,16 @@ class MLPTrainer:
             self._pending_wgrad.append((i, g))
             if i > 0:
                 below = self.layers[i - 1]
-                if self.SPLIT and self.FUSED and C_out in (128, 256) and C_in % 128 == 0:
+                fusable = self.bwd_fusable(C_out, C_in)
+                if fusable and self.plan.bwd == "layer_split":
                     if self.planes_t[i] is None:
                         self.planes_t[i] = torch.empty(C_in * C_out * 3, dtype=torch.int16, device=g.device)
                     _lib.check(lib.bg_mlp_split_weights(C_in, C_out, _lib.ptr(l.weight), C_in, C_out, C_in, 1, _lib.ptr(self.planes_t[i]), stream),
                                "bg_mlp_split_weights")
                     _lib.check(lib.bg_mlp_layer_backward_split(B, C_out, C_in, _lib.ptr(g), _lib.ptr(self.planes_t[i]), _lib.ptr(a_in), _lib.ptr(self.gin[i]),
-                                                               _lib.ptr(below.bias.grad), _lib.ptr(self.cs[i - 1]), self.SPLIT, stream),
+                                                               _lib.ptr(below.bias.grad), _lib.ptr(self.cs[i - 1]), self.plan.terms, stream),
                                "bg_mlp_layer_backward_split")
-                elif self.FUSED and C_out in (128, 256) and C_in % 128 == 0:
+                elif fusable and self.plan.bwd == "layer":
                     if self.wt[i] is None:
                         self.wt[i] = torch.empty(C_in, C_out, dtype=torch.float32, device=g.device)
                         self.wt[i].copy_(l.weight.t())

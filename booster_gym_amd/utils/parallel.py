@@ -16,7 +16,7 @@ that enqueue the same communicator's collectives in different orders dead-lock o
   * the OWN communicator (utils/rccl.py): tag "moments" (the advantage moments, once per mini-epoch) and tag "bucket" (the grouped gradient /
     statistics / log-std exchange, once per mini-epoch, inside Runner._epoch_gradients_and_step).  In the default one-stream mini-epoch
     (Runner._epoch_on_one_stream) both are enqueued on the MAIN stream: one communicator, one stream.  With BG_ONE_STREAM=0 "moments" is enqueued on
-    the side stream (Runner._epoch_critic_forward_and_gae) and "bucket" on the main stream: one communicator driven from two streams of a rank;
+    the side stream (Runner._epoch_on_two_streams) and "bucket" on the main stream: one communicator driven from two streams of a rank;
   * the PROCESS GROUP's communicator for everything outside the mini-epochs (seed, initial weights, curriculum grid, barriers).
 The host enqueues strictly in program order -- moments(e), bucket(e), moments(e + 1), ... -- on every rank, whatever the streams do on the device, and
 nothing else touches the own communicator; the process group's collectives are issued only between iterations.  Any change that makes the ORDER OF

@@ -37,6 +37,7 @@ import random
 import time
 
 import types
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -45,7 +46,7 @@ from .. import _lib
 from ..envs import TASKS
 from .buffer import ExperienceBuffer
 from .config import load_cfg
-from .model import ActorCritic, GroupedWeightGrad, MLPTrainer
+from .model import ActorCritic, GroupedWeightGrad, MLPTrainer, NetPlan, plan_network
 from .parallel import DataParallel
 from .recorder import Recorder
 from .utils import (actor_head_forward, actor_head_loss_backward, critic_head_backward, critic_head_forward, critic_values_gae, gae, gaussian_logp, head_scratch, reduce_group,
@@ -64,6 +65,44 @@ def plan_chain_split(slabs_c, slabs_a, cost_c, cost_a, cus, xcds=8):
     best = min(range(step, cus, step), key=lambda a: (max(-(-slabs_c // a) * cost_c, -(-slabs_a // (cus - a)) * cost_a),
                                                        abs(a - cus * slabs_c * cost_c / (slabs_c * cost_c + slabs_a * cost_a))))
     return best, cus - best
+
+
+class UpdatePlan(NamedTuple):
+    """The kernels of one Runner.update() and of the rollout's forward-ahead (plan_update): resolved once per call, read by every branch."""
+    critic: NetPlan
+    actor: NetPlan
+    wgrad: int          # products of the grouped weight-gradient launch: 0 = fp32 MFMA (bg_wgrad.hip), 6 / 9 = bf16 splits (bg_wgrad_split.hip)
+    fused_head: bool    # output layers fused with the loss (bg_head.hip); False: library GEMMs + bg_ppo_loss
+    fused_gae: bool     # critic output layer + GAE in one launch (bg_critic_values_gae)
+    chain_values: bool  # ... with the values from the critic's chained forward launch
+    one_stream: bool    # each of the forward and backward-data passes of both networks as ONE launch, the mini-epoch on the main stream
+    defer: bool         # the small reductions behind heads and backward layers as one launch in front of the weight gradients
+    fused_opt: bool     # clip + Adam + KL rule + statistics bookkeeping in one launch (bg_optimizer_step)
+    one_tail: bool      # ... together with the deferred sums and the weight gradients' finish (bg_update_tail; the weight gradients partial)
+    ahead: bool         # the rollout runs the first mini-epoch's forward passes
+    ranks: bool         # several ranks: the exchanges run
+
+
+def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_split_bwd, chain_alternate, fused_wgrad, wgrad_split, one_stream,
+                defer_finish, one_launch_tail, fused_opt, fused_head, fused_gae, chain_values, rollout_forward, dp_active):
+    """UpdatePlan from the switches (MLPTrainer.SPLIT ... WGRAD_SPLIT and Runner._one_stream ... _rollout_forward, by the same names in lower case;
+    dp.active) and the shapes: critic / actor = (layer widths, padded input width), rows = the batch.  Pure: no tensors, no device."""
+    nets = [plan_network(w, kin, rows, split, fused, chain, chain_split, chain_split_bwd and fused_head, chain_alternate, fused_wgrad) for w, kin in (critic, actor)]
+    bwd_chained = all(n.bwd == "chain_split" for n in nets)
+    grouped = [(co, ci) for (w, kin), n in zip((critic, actor), nets) for ci, co, g in zip((kin,) + tuple(w[1:-1]), w[1:], n.grouped) if g]
+    wgrad = ((split or (wgrad_split if bwd_chained else 0)) if rows % 32 == 0 and rows >= 128
+             and all(s in ((256, 256), (128, 256), (128, 128), (256, 64)) for s in grouped) else 0)
+    chain_values = fused_head and fused_gae and chain_values and nets[0].chained
+    defer = fused_head and defer_finish and not split
+    # bg_update_tail takes the gradient's norm from its own sums, so every gradient element must come out of them: all hidden layers' weight gradients
+    # from the grouped launch, every hidden layer's bias gradient from a deferred finish (of the chained backward launch, or of a partial per-layer
+    # backward launch of every layer), at most 8 finish descriptors in all
+    fins = [1 if n.bwd == "chain_split" else len(w) - 3 for (w, _), n in zip((critic, actor), nets)]
+    finishing = all(n.bwd == "chain_split" or n.bwd == "layer" and all(MLPTrainer.bwd_fusable(co, ci) for ci, co in zip(w[1:-2], w[2:-1]))
+                    for (w, _), n in zip((critic, actor), nets))
+    one_tail = fused_opt and one_launch_tail and defer and finishing and all(all(n.grouped[:-1]) for n in nets) and sum(fins) + 2 <= 8
+    return UpdatePlan(nets[0], nets[1], wgrad, fused_head, fused_gae, chain_values, one_stream and chain_values and defer and bwd_chained, defer, fused_opt,
+                      one_tail, rollout_forward and chain_values and nets[1].chained, dp_active)
 
 
 class FlatAdam:
@@ -91,6 +130,8 @@ class FlatAdam:
         self.betas, self.eps, self.max_grad_norm = betas, eps, max_grad_norm
         self.step_count = 0
         self._gnorm = torch.zeros(1, dtype=torch.float64, device=dev)
+        self._tail_sync = torch.zeros(4, dtype=torch.int32, device=dev)  # bg_update_tail's ticket and squared-norm pieces
+        self._tail_norm = torch.zeros(8192, dtype=torch.float64, device=dev)
 
     def zero_grad(self):
         self.grad.zero_()
@@ -118,11 +159,8 @@ class FlatAdam:
     def step_tail(self, wgrad, reductions, stats, stats_acc, stats_last, kl_index, count, desired_kl, grad_logstd=None, ls_off=0, lr_min=1e-5, lr_max=1e-2,
                   mirrors=None):
         """`step_fused` together with the sums in front of it (bg_update_tail: two launches for four): wgrad = (descriptor array, count) of a weight-gradient
-        launch made without its finish (GroupedWeightGrad.run(..., finish=False)) or None, reductions = the deferred _lib.ReduceProblem descriptors."""
+        launch made without its finish (GroupedWeightGrad.run(..., partial=True)) or None, reductions = the deferred _lib.ReduceProblem descriptors."""
         self.step_count += 1
-        if not hasattr(self, "_tail_sync"):
-            self._tail_sync = torch.zeros(4, dtype=torch.int32, device=self.flat.device)
-            self._tail_norm = torch.zeros(8192, dtype=torch.float64, device=self.flat.device)
         warr, wn = wgrad if wgrad is not None else (None, 0)
         rarr = (_lib.ReduceProblem * len(reductions))(*reductions) if reductions else None
         _lib.check(_lib.load().bg_update_tail(warr, wn, rarr, len(reductions) if reductions else 0, self.flat.numel(), _lib.ptr(self.flat), _lib.ptr(self.grad),
@@ -135,9 +173,6 @@ class FlatAdam:
 
     def tail_sums(self, wgrad, reductions):
         """Launch (1) of `step_tail` alone (bg_update_tail_sums): the ranks of a multi-GPU job average the gradient between the sums and `step_fused`."""
-        if not hasattr(self, "_tail_sync"):
-            self._tail_sync = torch.zeros(4, dtype=torch.int32, device=self.flat.device)
-            self._tail_norm = torch.zeros(8192, dtype=torch.float64, device=self.flat.device)
         warr, wn = wgrad if wgrad is not None else (None, 0)
         rarr = (_lib.ReduceProblem * len(reductions))(*reductions) if reductions else None
         _lib.check(_lib.load().bg_update_tail_sums(warr, wn, rarr, len(reductions) if reductions else 0, _lib.ptr(self._tail_norm), _lib.current_stream_ptr()),
@@ -250,10 +285,9 @@ class Runner:
         # The small fixed-order reductions behind the head / backward-layer kernels run as ONE launch in front of the weight gradients instead of
         # inside the chains, where each of them waits 20-45 us for a workgroup slot between the other network's resident GEMM workgroups (see
         # update()).  Measured in the loop (tools/ab_env.sh, 4 alternating runs of 20 iterations each): update 21.68-21.91 ms with the one launch in
-        # front of the weight gradients (BG_DEFER_FINISH=1, the default), 21.85-21.97 ms with it on the side stream BESIDE them (=2: it delays the
-        # one-workgroup-per-CU launch), 21.99-22.04 ms with the finishes inside the chains (=0).
-        self._defer_finish = os.environ.get("BG_DEFER_FINISH", "1") in ("1", "2")
-        self._defer_serial = os.environ.get("BG_DEFER_FINISH", "1") != "2"
+        # front of the weight gradients (BG_DEFER_FINISH=1, the default), 21.99-22.04 ms with the finishes inside the chains (=0).  (On the side stream
+        # beside the weight gradients it was 21.85-21.97 ms: it delays the one-workgroup-per-CU launch.)
+        self._defer_finish = {"0": False, "1": True}[os.environ.get("BG_DEFER_FINISH", "1")]  # (KeyError for 2: the side-stream form is gone)
         # critic output layer + GAE in one launch (bg_critic_values_gae: horizons up to 32 steps); otherwise bg_critic_head_forward, a fill and bg_gae
         self._fused_gae = self.cfg["runner"]["horizon_length"] <= 32
         self._chain_values = True  # ... with the values from the chained forward kernel's value head (False: from the stored activations)
@@ -281,7 +315,7 @@ class Runner:
         # the env step leaves idle and slow it down (110 against 102.5 us).  Same box, 20 iterations each, ms per iteration: off 24.78-24.92, one step
         # per group 24.46-24.49, two 24.39-24.41, three 24.42-24.47, four 24.55-24.66, eight 24.58-24.65 (profiles/r04_rollout_forward_ab.txt).
         self._rollout_group = max(1, int(os.environ.get("BG_ROLLOUT_FORWARD_GROUP", "2")))
-        self._fwd_ready = False  # rollout() has left the activations / values / old mu of the whole batch in the trainers' buffers
+        self._fwd_plan = None  # the UpdatePlan under which rollout() has left the activations / values / old mu of the whole batch in the trainers' buffers
         self.timers = {"rollout": 0.0, "update": 0.0}
 
     # ------------------------------------------------------------------ config / seed / checkpoint (runner.py:44-97)
@@ -348,7 +382,7 @@ class Runner:
         rollout() may leave the first mini-epoch's forward passes (activations, values, old mu, old log-probabilities of every row) in the trainers'
         buffers and the weight copies that the layer kernels read current, and update() then trusts both without looking; this forgets them, so the
         next update() recomputes everything from the parameters and the buffers as they are."""
-        self._fwd_ready = False
+        self._fwd_plan = None
         for tr in (getattr(self, "_actor_tr", None), getattr(self, "_critic_tr", None)):
             if tr is not None:
                 tr.mirror_fresh = False
@@ -357,6 +391,20 @@ class Runner:
         return {"model": self.model.state_dict(), "optimizer": self.optimizer.state_dict(), "curriculum": self.env.curriculum_prob}
 
     # ------------------------------------------------------------------ one PPO iteration
+    def _resolve_plan(self):
+        """The UpdatePlan of the switches and shapes as they are now, handed to the trainers (MLPTrainer.plan) with the critic's value head."""
+        ct, at = self._critic_tr, self._actor_tr
+        sw = {k.lower(): getattr(MLPTrainer, k) for k in ("SPLIT", "FUSED", "CHAIN", "CHAIN_SPLIT", "CHAIN_SPLIT_BWD", "CHAIN_ALTERNATE", "FUSED_WGRAD", "WGRAD_SPLIT")}
+        sw.update((k[1:], getattr(self, k)) for k in ("_one_stream", "_defer_finish", "_one_launch_tail", "_fused_opt", "_fused_head", "_fused_gae", "_chain_values",
+                                                      "_rollout_forward"))
+        widths = lambda tr: (tr.layers[0].in_features,) + tuple(l.out_features for l in tr.layers)
+        kin_a = self._actor_in.shape[-1] if self._actor_in is not None else self.env.num_obs
+        plan = plan_update((widths(ct), self._critic_in.shape[-1]), (widths(at), kin_a), self._old_logp.numel(), dp_active=self.dp.active, **sw)
+        ct.plan, at.plan = plan.critic, plan.actor
+        c_out = ct.layers[-1]
+        ct.value_head = (c_out.weight.reshape(-1), c_out.bias, self._values_all) if plan.chain_values else None
+        return plan
+
     def rollout(self):
         """runner.py:106-121: horizon_length env steps with sampled actions, outputs written in place.
 
@@ -369,33 +417,24 @@ class Runner:
         buf, T = self.buffer, self.cfg["runner"]["horizon_length"]
         obses, priv = buf["obses"], buf["privileged_obses"]
         seed = int(self.cfg["basic"]["seed"]) + 1000003 * (self.rank + 1)
-        ahead = (self._rollout_forward and self._fused_head and self._fused_gae and self._chain_values and not MLPTrainer.SPLIT
-                 and self._prepare_rollout_forward())
+        plan = self._resolve_plan()
+        if plan.ahead:
+            N = self.env.num_envs
+            self._critic_tr.prepare(self._critic_in.reshape((T + 1) * N, -1), train_rows=T * N)
+            self._actor_tr.prepare(self._actor_in.reshape(T * N, -1))
         main = torch.cuda.current_stream()
         g, start = self._rollout_group, 0
         with torch.no_grad():
             for n in range(T):
-                if ahead and n + 1 - start >= g:
+                if plan.ahead and n + 1 - start >= g:
                     self._forward_rows(start, n, main)  # rows of steps start .. n: on the side stream, beside this step's launches
                     start = n + 1
                 self.model.sample_actions(obses[n], buf["actions"][n], seed, self._act_counter)
                 self._act_counter += 1
                 self.env.step_to(buf["actions"][n], obses[n + 1], priv[n + 1], buf["rewards"][n], buf["dones"][n], buf["time_outs"][n])
-            if ahead:
+            if plan.ahead:
                 self._forward_rows(start, T, main)  # ... and the observation after the last step: the critic's last_values rows
-                self._fwd_ready = True
-
-    def _prepare_rollout_forward(self):
-        T, N = self.cfg["runner"]["horizon_length"], self.env.num_envs
-        ct, at = self._critic_tr, self._actor_tr
-        ct.prepare(self._critic_in.reshape((T + 1) * N, -1), train_rows=T * N)
-        at.prepare(self._actor_in.reshape(T * N, -1))
-        if not (ct._chainable() and at._chainable()):
-            return False
-        c_out = ct.layers[-1]
-        ct.value_head = (c_out.weight.reshape(-1), c_out.bias, self._values_all)
-        at.value_head = None
-        return True
+        self._fwd_plan = plan if plan.ahead else None
 
     def _forward_rows(self, a, b, main):
         """Side stream: pad the observation rows of steps a .. b (b = T: the observation after the last step, critic only) into the network inputs
@@ -423,7 +462,7 @@ class Runner:
             if a <= ba:
                 self._actor_in[a : ba + 1, :, :no].copy_(buf["obses"][a : ba + 1])
                 jobs.append((at, a * N, (ba + 1 - a) * N))
-            MLPTrainer.forward_rows_group(jobs)
+            MLPTrainer.launch_chain([tr.chain_rows_descriptor(r0, nr) for tr, r0, nr in jobs])  # ONE launch (at most 4 jobs)
             if a <= ba:
                 a_out = at.layers[-1]
                 actor_head_forward(at.acts[2][a * N : (ba + 1) * N], a_out.weight, a_out.bias, self._old_mu[a * N : (ba + 1) * N])
@@ -435,23 +474,22 @@ class Runner:
     def update(self):
         """runner.py:123-189: old log-probs, then mini_epochs full-batch optimiser steps.
 
-        Contract with rollout(): when rollout() has run the first mini-epoch's forward passes (`_fwd_ready`), this method starts from them and from the
-        weight copies the last optimiser launch wrote -- parameters and rollout buffers must not have been changed in between except through
-        `invalidate()` (which `_load` and the initial broadcast call)."""
-        u = self._update_begin()
+        Contract with rollout(): when rollout() has run the first mini-epoch's forward passes under the plan this update resolves (`_fwd_plan`), this
+        method starts from them and from the weight copies the last optimiser launch wrote -- parameters and rollout buffers must not have been changed
+        in between except through `invalidate()` (which `_load` and the initial broadcast call)."""
+        u = self._update_begin(self._resolve_plan())
         with torch.no_grad():
             for epoch in range(self.cfg["runner"]["mini_epochs"]):
                 # this mini-epoch's hidden activations and values may be the rollout's: same kernels, same weights
                 have_fwd = u.ahead and epoch == 0
-                if u.one_stream:
+                if u.plan.one_stream:
                     self._epoch_on_one_stream(u, have_fwd)
                 else:
-                    self._epoch_critic_forward_and_gae(u, have_fwd)
-                    self._epoch_losses_and_backward(u, have_fwd)
+                    self._epoch_on_two_streams(u, have_fwd)
                 self._epoch_gradients_and_step(u)
         return self._stats_acc
 
-    def _update_begin(self):
+    def _update_begin(self, plan):
         """What update() does once per call: inputs of both networks, old mu / log-std / log-probabilities (runner.py:123-129) unless rollout() left them,
         zeroed accumulators, the CU split of the forward launches.  Returns the namespace the three phases of a mini-epoch share."""
         cfg, buf = self.cfg, self.buffer
@@ -460,9 +498,11 @@ class Runner:
         alg = cfg["algorithm"]
         act_flat = buf["actions"].reshape(B, A)
         no, npv = self.env.num_obs, self.env.num_privileged_obs
-        # rollout() may have run the first mini-epoch's forward passes already (activations, values and old mu of every row are in place)
-        ahead, self._fwd_ready = self._fwd_ready, False
+        # rollout() may have run the first mini-epoch's forward passes already (activations, values and old mu of every row are in place); they
+        # serve only the plan they were computed under
+        ahead, self._fwd_plan = self._fwd_plan == plan, None
         if not ahead:
+            torch.cuda.current_stream().wait_stream(self._side_stream)  # a forward-ahead being discarded may still write these buffers
             self._actor_tr.mirror_fresh = self._critic_tr.mirror_fresh = False  # weights may have changed outside the loop below (checkpoint, broadcast)
             self._critic_in[:, :, :no].copy_(buf["obses"])
             self._critic_in[:, :, no : no + npv].copy_(buf["privileged_obses"])
@@ -470,14 +510,13 @@ class Runner:
                 self._actor_in[:, :, :no].copy_(buf["obses"][:T])
         obs_flat = self._actor_in.reshape(B, -1) if self._actor_in is not None else buf["obses"][:T].reshape(B, -1)
         critic_all = self._critic_in.reshape((T + 1) * N, -1)  # rows [B, B+N) = the observation after the last step (last_values)
-        fused_head = self._fused_head
         logstd_flat = self.model.logstd.reshape(-1)
         a_out, c_out = self._actor_tr.layers[-1], self._critic_tr.layers[-1]
         with torch.no_grad():
             # old mu through the same kernels as the mini-epochs: the first ratio is exactly 1
             if ahead:
                 old_mu = self._old_mu
-            elif fused_head:
+            elif plan.fused_head:
                 old_mu = actor_head_forward(self._actor_tr.forward_hidden(obs_flat), a_out.weight, a_out.bias, self._old_mu)
             else:
                 old_mu = self._actor_tr.forward(obs_flat).clone()
@@ -487,64 +526,50 @@ class Runner:
         self._stats_acc.zero_()
         self._stats.zero_()
         self._grad_logstd.zero_()
-        self._plan_chain_split(critic_all.shape[0], B)
-        # Two HIP streams: the actor and the critic are independent networks, so the HBM-bound elementwise kernels of one overlap
-        # the MFMA-bound GEMMs of the other.  side stream = critic forward -> GAE ... critic backward; main stream = actor.
-        main = torch.cuda.current_stream()
-        side = self._side_stream
-        ct, at = self._critic_tr, self._actor_tr
-        one_stream = (self._one_stream and fused_head and self._fused_gae and self._chain_values and self._defer_finish and self._defer_serial
-                      and not MLPTrainer.SPLIT and ct.chainable_for(critic_all, B) and at.chainable_for(obs_flat) and ct._chain_split_bwd() and at._chain_split_bwd())
+        self._plan_chain_split(critic_all, obs_flat, plan)
+        # (two streams, plan.one_stream = False: side stream = critic forward -> GAE ... critic backward; main stream = actor)
         return types.SimpleNamespace(cfg=cfg, buf=buf, T=T, N=N, B=B, A=A, alg=alg, act_flat=act_flat, ahead=ahead, obs_flat=obs_flat, critic_all=critic_all,
-                                     fused_head=fused_head, logstd_flat=logstd_flat, a_out=a_out, c_out=c_out, old_mu=old_mu, old_logstd=old_logstd, main=main, side=side,
-                                     mirrors=None, one_stream=one_stream)
+                                     plan=plan, logstd_flat=logstd_flat, a_out=a_out, c_out=c_out, old_mu=old_mu, old_logstd=old_logstd,
+                                     main=torch.cuda.current_stream(), side=self._side_stream, mirrors=None)
 
-    def _epoch_critic_forward_and_gae(self, u, have_fwd):
+    def _epoch_on_two_streams(self, u, have_fwd):
         """Side stream: the critic's forward pass (unless the rollout ran it), values, time-out bootstrap, GAE, returns, advantage moments and their
-        exchange (runner.py:132-145).  Leaves hc / values / gae_done in u."""
-        cfg, buf, T, N, B, alg, critic_all, fused_head, c_out, main, side = u.cfg, u.buf, u.T, u.N, u.B, u.alg, u.critic_all, u.fused_head, u.c_out, u.main, u.side
+        exchange (runner.py:132-145).  Main stream: the actor's forward pass; then both output layers fused with the loss, both backward-data chains
+        on their streams (runner.py:147-163).  Leaves fins / fin_c / fin_a in u."""
+        buf, T, N, B, alg, act_flat, obs_flat, critic_all, logstd_flat, a_out, c_out, old_mu, old_logstd, main, side, plan = (
+            u.buf, u.T, u.N, u.B, u.alg, u.act_flat, u.obs_flat, u.critic_all, u.logstd_flat, u.a_out, u.c_out, u.old_mu, u.old_logstd, u.main, u.side, u.plan)
         # parameters updated by the previous optimiser step; the loss accumulators (_stats, _grad_logstd) were zeroed by it (before the loop
         # for the first mini-epoch): both heads add into them
-        # the chained forward kernel also evaluates the value head, from the registers that hold the last activations: the launch between the
-        # critic's forward and the actor's loss then has 400 KB to read instead of 52 MB
-        chain_values = fused_head and self._fused_gae and self._chain_values and self._critic_tr.chainable_for(critic_all, B)
-        self._critic_tr.value_head = (c_out.weight.reshape(-1), c_out.bias, self._values_all) if chain_values else None
+        # (plan.chain_values: the chained forward kernel also evaluates the value head, from the registers that hold the last activations: the launch
+        # between the critic's forward and the actor's loss then has 400 KB to read instead of 52 MB)
         side.wait_stream(main)
         with torch.cuda.stream(side):
-            if fused_head:
+            if plan.fused_head:
                 if have_fwd:
                     hc = self._critic_tr.acts[2]
                 else:
                     hc = self._critic_tr.forward_hidden(critic_all, train_rows=B)
-                if self._fused_gae:
+                if plan.fused_gae:
                     # output layer + timeout bootstrap + GAE + returns + advantage moments in ONE launch in front of the actor's loss
-                    v_all = critic_values_gae(None if chain_values else hc, c_out.weight, c_out.bias, buf["rewards"], buf["dones"], buf["time_outs"],
+                    v_all = critic_values_gae(None if plan.chain_values else hc, c_out.weight, c_out.bias, buf["rewards"], buf["dones"], buf["time_outs"],
                                               alg["gamma"], alg["lam"], self._values_all, self._adv, self._ret, self._adv_sums, self._gae_scratch)
                 else:
                     v_all = critic_head_forward(hc, c_out.weight, c_out.bias, self._values_all)
             else:
                 v_all = self._critic_tr.forward(critic_all, train_rows=B).squeeze(-1)
             values, last_values = v_all[:B], v_all[B:]
-            if not (fused_head and self._fused_gae):
+            if not (plan.fused_head and plan.fused_gae):
                 gae(buf["rewards"], buf["dones"], buf["time_outs"], values.view(T, N), last_values, alg["gamma"], alg["lam"],
                     advantages=self._adv, returns=self._ret, sums=self._adv_sums)
             self.dp.sum_(self._adv_sums, tag="moments")  # exchange (1), on the side stream: hidden under the actor forward
             gae_done = side.record_event()
-        u.hc, u.values, u.gae_done = (hc if fused_head else None), values, gae_done
-
-    def _epoch_losses_and_backward(self, u, have_fwd):
-        """The actor's forward pass (main stream), both output layers fused with the loss, both backward-data chains on their streams
-        (runner.py:147-163).  Leaves defer / fins / fin_c / fin_a in u."""
-        buf, B, alg, act_flat, obs_flat, fused_head, logstd_flat, a_out, c_out, old_mu, old_logstd, main, side = u.buf, u.B, u.alg, u.act_flat, u.obs_flat, u.fused_head, u.logstd_flat, u.a_out, u.c_out, u.old_mu, u.old_logstd, u.main, u.side
-        hc, values, gae_done = u.hc, u.values, u.gae_done
-        fins = fin_c = fin_a = None
-        if fused_head:
+        defer, fins, fin_c, fin_a = plan.defer, None, None, None
+        if plan.fused_head:
             # Output layers fused with the loss (bg_head.hip): per network ONE pass over the [B][128] hidden activations gives the
             # output, the loss terms, dL/dz of the hidden layer and the output layer's gradients.  Both heads add into _stats.
             # defer (the default, see __init__): the small fixed-order reductions behind the head kernels and behind every backward layer
-            # (output-layer and bias gradients, loss statistics: nothing a chain needs) run as ONE launch on the side stream beside the
-            # weight-gradient launch (bg_reduce_group) instead of inside the chains.
-            defer = self._defer_finish and not MLPTrainer.SPLIT
+            # (output-layer and bias gradients, loss statistics: nothing a chain needs) run as ONE launch in front of the weight-gradient launch
+            # (bg_reduce_group, or inside bg_update_tail) instead of inside the chains.
             fins = [] if defer else None
             fin_c, fin_a = (_lib.ReduceProblem(), _lib.ReduceProblem()) if defer else (None, None)
             ha = self._actor_tr.acts[2] if have_fwd else self._actor_tr.forward_hidden(obs_flat)
@@ -557,13 +582,12 @@ class Runner:
                                      self._adv.view(B), self._adv_sums, 0.2, alg["bound_coef"], alg["entropy_coef"],
                                      self._actor_tr.hidden_grad, a_out.weight.grad, a_out.bias.grad, self._actor_tr.layers[-2].bias.grad,
                                      self._grad_logstd, self._stats, self._head_scratch_a, finish=fin_a)
-            if self.dp.active and not defer:
+            if plan.ranks and not defer:
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
                     self._exchange_sums()  # exchange (3): loss / KL sums, hidden under the backward passes
             self._actor_tr.backward_hidden(finishes=fins)
         else:
-            defer = False
             mu = self._actor_tr.forward(obs_flat)
             main.wait_stream(side)
             ppo_loss_fused(mu, logstd_flat, act_flat, old_mu, old_logstd, self._old_logp, self._adv.view(B), self._adv_sums,
@@ -574,16 +598,15 @@ class Runner:
                 self._exchange_sums()  # exchange (3): loss / KL sums, hidden under the backward passes
                 self._critic_tr.backward(self._grad_val.view(B, 1))
             self._actor_tr.backward(self._grad_mu)
-        u.defer, u.fins, u.fin_c, u.fin_a = defer, fins, fin_c, fin_a
+        u.fins, u.fin_c, u.fin_a = fins, fin_c, fin_a
 
     def _epoch_on_one_stream(self, u, have_fwd):
-        """What _epoch_critic_forward_and_gae + _epoch_losses_and_backward do, as one sequence of launches on the main stream: both forward chains in
+        """What _epoch_on_two_streams does, as one sequence of launches on the main stream: both forward chains in
         one launch (unless the rollout ran them), values + GAE + moments (+ their exchange), the two output layers fused with the loss, both
         backward-data chains in one launch (runner.py:132-163).  Same kernels on the same slabs with the same reduction order as the two-stream form:
-        bit-identical results (tests/test_gpu_ppo.py).  Leaves defer / fins / fin_c / fin_a in u."""
+        bit-identical results (tests/test_gpu_ppo.py).  Leaves fins / fin_c / fin_a in u."""
         buf, B, alg, act_flat, obs_flat, critic_all, logstd_flat, a_out, c_out, old_mu, old_logstd = u.buf, u.B, u.alg, u.act_flat, u.obs_flat, u.critic_all, u.logstd_flat, u.a_out, u.c_out, u.old_mu, u.old_logstd
         ct, at = self._critic_tr, self._actor_tr
-        ct.value_head = (c_out.weight.reshape(-1), c_out.bias, self._values_all)
         if have_fwd:
             u.main.wait_stream(u.side)  # the rollout ran the forward passes on the side stream
             hc, ha = ct.acts[2], at.acts[2]
@@ -600,44 +623,28 @@ class Runner:
                                  alg["bound_coef"], alg["entropy_coef"], at.hidden_grad, a_out.weight.grad, a_out.bias.grad, at.layers[-2].bias.grad,
                                  self._grad_logstd, self._stats, self._head_scratch_a, finish=fin_a)
         MLPTrainer.backward_hidden_group([ct, at], fins)
-        u.hc, u.values, u.gae_done = hc, values, None
-        u.defer, u.fins, u.fin_c, u.fin_a = True, fins, fin_c, fin_a
+        u.fins, u.fin_c, u.fin_a = fins, fin_c, fin_a
 
     def _epoch_gradients_and_step(self, u):
         """Deferred reductions, all weight gradients, the exchange of the gradient over the ranks, clip + Adam + KL rule (runner.py:162-180)."""
-        cfg, B, alg, main, side = u.cfg, u.B, u.alg, u.main, u.side
-        defer, fins, fin_c, fin_a, mirrors = u.defer, u.fins, u.fin_c, u.fin_a, u.mirrors
-        fused_tail = self._fused_opt and not self._lr_restart
-        # the sums of the tail as one launch behind the main weight-gradient kernel + a lean optimiser launch (single process, see __init__)
-        # (its norm is assembled from the sums' own pieces: every gradient element must come out of that launch -- all hidden-layer weight
-        # gradients from the grouped kernel, everything else from the deferred reductions)
-        # (that is: every hidden layer's backward went through the partial kernel, whose finish carries the bias gradient of the layer below --
-        # a layer that fell to the library path wrote its bias gradient outside both lists and the norm would miss it)
-        one_tail = (fused_tail and self._one_launch_tail and defer and self._defer_serial and len(fins) + 2 <= 8
-                    and all(all(tr.wg_slices[:-1]) for tr in (self._critic_tr, self._actor_tr))
-                    and len(fins) == sum(1 if tr._chain_split_bwd() else len(tr.layers) - 2 for tr in (self._critic_tr, self._actor_tr)))
-        if not u.one_stream:
+        cfg, B, alg, main, side, plan = u.cfg, u.B, u.alg, u.main, u.side, u.plan
+        fins, fin_c, fin_a, mirrors = u.fins, u.fin_c, u.fin_a, u.mirrors
+        # (the first optimiser step after a checkpoint restore runs the separate launches: see __init__)
+        fused_tail, one_tail = plan.fused_opt and not self._lr_restart, plan.one_tail and not self._lr_restart
+        if not plan.one_stream:
             main.wait_stream(side)
-        if one_tail:
-            pass  # the deferred reductions run inside bg_update_tail
-        elif defer and self._defer_serial:  # the deferred reductions as one launch in FRONT of the weight gradients (the default)
+        if plan.defer and not one_tail:  # the deferred reductions as one launch in FRONT of the weight gradients (one_tail: inside bg_update_tail)
             reduce_group([fin_c, fin_a] + fins)
-            if self.dp.active:
+            if plan.ranks:
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
                     self._exchange_sums()  # exchange (3), beside the weight gradients
-        elif defer:  # BG_DEFER_FINISH=2: ... (+ what depends on them) on the side stream, beside the weight gradients on the main stream
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                reduce_group([fin_c, fin_a] + fins)
-                if self.dp.active:
-                    self._exchange_sums()  # exchange (3)
         # all weight gradients after both backward chains, alone on the GPU: one launch pair for the six hidden layers (shapes outside the
-        # kernel's range, or MLPTrainer.FUSED_WGRAD = False: library GEMMs, layer by layer)
-        wg_partial = self._wgrad_group.run((self._critic_tr, self._actor_tr), finish=not one_tail)
-        if defer and (self.dp.active or not self._defer_serial):
+        # kernel's range, or MLPTrainer.FUSED_WGRAD = False: library GEMMs, layer by layer); one_tail: their finish inside bg_update_tail
+        wg_partial = self._wgrad_group.run((self._critic_tr, self._actor_tr), plan.wgrad, one_tail)
+        if plan.defer and plan.ranks:
             main.wait_stream(side)
-        if one_tail and self.dp.active:
+        if one_tail and plan.ranks:
             # ranks: the sums, then ONE collective launch on this stream (gradient bucket: mean; loss / KL sums: sum; log-std gradient: mean -- exchanges
             # (2) and (3) of SURVEY 8(e)), then the optimiser launch, which takes the norm of the averaged gradient
             self.optimizer.tail_sums(wg_partial, [fin_c, fin_a] + fins)
@@ -651,7 +658,7 @@ class Runner:
             if mirrors is None:
                 ms = self._critic_tr.mirror_descriptors(self.optimizer.flat) + self._actor_tr.mirror_descriptors(self.optimizer.flat)
                 mirrors = (_lib.ParamMirror * len(ms))(*ms) if 0 < len(ms) <= 16 else None
-            if one_tail and not self.dp.active:
+            if one_tail and not plan.ranks:
                 self.optimizer.step_tail(wg_partial, [fin_c, fin_a] + fins, self._stats, self._stats_acc, self._stats_last, 4, B, alg["desired_kl"],
                                          grad_logstd=self._grad_logstd, ls_off=self._logstd_off, mirrors=mirrors)
             else:
@@ -672,27 +679,28 @@ class Runner:
             self._grad_logstd.zero_()
         u.mirrors = mirrors
 
-    def _plan_chain_split(self, rows_c, rows_a):
-        """The two networks' chains of a mini-epoch run side by side -- inside one grid (the default) or as two launches on two streams -- one workgroup
+    def _plan_chain_split(self, x_c, x_a, plan):
+        """x_c / x_a: the critic's / the actor's input of the full-batch forward pass (their widths, not the trainers': a trainer is allocated by its
+        first pass, which may come after this).  The two networks' chains of a mini-epoch run side by side -- inside one grid (the default) or as two launches on two streams -- one workgroup
         per CU (all of its LDS).  Left to the dispatcher, equal-sized slabs of unequal cost run in lockstep rounds and the last 32 slabs run alone (370 us
         for 325 us of work per CU); here each network gets a share of the CUs whose workgroups walk its slabs (bg_mlp_chain_split::workgroups): the
         split that minimises the longer of the two, slab cost ~ flops.  Which workgroup walks which slab changes no bit of the results."""
         ct, at = self._critic_tr, self._actor_tr
         ct.chain_workgroups = at.chain_workgroups = 0
-        if not (self._split_chain_cus and ct._chainable() and at._chainable()):
+        if not (self._split_chain_cus and plan.critic.chained and plan.actor.chained):
             return
         cus = torch.cuda.get_device_properties(self.device).multi_processor_count
-        sc, sa = (rows_c + 127) // 128, (rows_a + 127) // 128
+        sc, sa = (x_c.shape[0] + 127) // 128, (x_a.shape[0] + 127) // 128
         if sc + sa <= cus:
             return
-        cost = lambda tr: sum(l.weight.shape[0] * (tr._kin if i == 0 else l.weight.shape[1]) for i, l in enumerate(tr.layers[:3]))
-        ct.chain_workgroups, at.chain_workgroups = plan_chain_split(sc, sa, cost(ct), cost(at), cus)
+        cost = lambda tr, x: sum(l.weight.shape[0] * (x.shape[1] if i == 0 else l.weight.shape[1]) for i, l in enumerate(tr.layers[:3]))
+        ct.chain_workgroups, at.chain_workgroups = plan_chain_split(sc, sa, cost(ct, x_c), cost(at, x_a), cus)
         fixed = os.environ.get("BG_FWD_CHAIN_CUS")  # "critic,actor": a fixed split (A/B runs)
         if fixed:
             ct.chain_workgroups, at.chain_workgroups = (int(v) for v in fixed.split(","))
-        # the chained backward launches likewise (both networks differentiate the same rows_a rows; slab cost ~ flops of the two backward layers)
+        # the chained backward launches likewise (both networks differentiate the actor's rows; slab cost ~ flops of the two backward layers)
         ct.chain_bwd_workgroups = at.chain_bwd_workgroups = 0
-        if self._split_bwd_chain_cus and ct._chain_split_bwd() and at._chain_split_bwd():
+        if self._split_bwd_chain_cus and plan.critic.bwd == plan.actor.bwd == "chain_split":
             bcost = lambda tr: sum(l.weight.shape[0] * l.weight.shape[1] for l in tr.layers[1:3])
             ct.chain_bwd_workgroups, at.chain_bwd_workgroups = plan_chain_split(sa, sa, bcost(ct), bcost(at), cus)
             fixed = os.environ.get("BG_BWD_CHAIN_CUS")  # "critic,actor": a fixed split (A/B runs)
@@ -707,10 +715,9 @@ class Runner:
             self._grad_logstd.mul_(1.0 / self.world_size)
 
     def iteration(self):
-        buf, T = self.buffer, self.cfg["runner"]["horizon_length"]
         self.rollout()
         stats = self.update()
-        buf.roll()  # carry the last observation into row 0 of the next rollout
+        self.buffer.roll()  # carry the last observation into row 0 of the next rollout
         return stats
 
     def _sync_curriculum(self):

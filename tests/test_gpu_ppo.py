@@ -349,7 +349,7 @@ SWITCHES = {
     # name: (runner attributes, MLPTrainer class attributes) -- every branch of Runner.update() / MLPTrainer that a switch or a shape can select
     "default": ({}, {}),
     # (environment switches and the attributes they set: BG_ONE_LAUNCH_TAIL -> _one_launch_tail, BG_SPLIT_CHAIN_CUS -> _split_chain_cus,
-    #  BG_ONE_STREAM -> _one_stream, BG_ROLLOUT_FORWARD -> _rollout_forward, BG_ROLLOUT_FORWARD_GROUP -> _rollout_group, BG_DEFER_FINISH -> _defer_finish / _defer_serial (own test below),
+    #  BG_ONE_STREAM -> _one_stream, BG_ROLLOUT_FORWARD -> _rollout_forward, BG_ROLLOUT_FORWARD_GROUP -> _rollout_group, BG_DEFER_FINISH -> _defer_finish (own test below),
     #  BG_CHAIN_SPLIT / BG_CHAIN_SPLIT_BWD / BG_CHAIN_ALTERNATE / BG_WGRAD_SPLIT -> MLPTrainer.CHAIN_SPLIT / CHAIN_SPLIT_BWD / CHAIN_ALTERNATE / WGRAD_SPLIT; BG_OWN_RCCL = 0 and 1: tests/test_gpu_rccl.py; BG_FWD_CHAIN_CUS / BG_BWD_CHAIN_CUS: test_cu_shares_of_the_chains_change_no_bit below)
     "tail_as_three_launches": ({"_one_launch_tail": False}, {}),                  # reduce_group, weight gradients + finish, optimizer_step (what ranks of a job run)
     "separate_optimizer_tail": ({"_fused_opt": False}, {}),                      # bg_adam_step + bg_adapt_lr + torch adds (first step after a restore)
@@ -395,7 +395,7 @@ def _update_under(switch):
         first = (r.optimizer.flat.clone(), acc, r._summarize(acc))
         acc2 = r.iteration().clone()  # a second iteration: its rollout reads the weight copies the optimiser launch wrote
         torch.cuda.synchronize()
-        return start, first, (r.optimizer.flat.clone(), acc2, r.buffer["actions"].clone())
+        return start, first, (r.optimizer.flat.clone(), acc2, r.buffer["actions"].clone()), r._resolve_plan()
     finally:
         for k, v in saved.items():
             setattr(MLPTrainer, k, v)
@@ -411,9 +411,12 @@ def test_update_through_every_switch_matches_the_default(switch, default_update)
     """Every branch of the update path that an attribute, a class switch or a shape can select (the library-GEMM fallbacks included) runs a whole
     PPO iteration from the same seed and lands where the default path lands: parameters within 2 % of the distance they moved (different kernels
     round differently, and Adam turns a rounding-size gradient difference into a fraction of a step), loss statistics to 1e-3, the same learning
-    rate.  The rollout-forward variants run the same kernels on the same numbers: identical bits, also after a second iteration."""
-    start, (p0, a0, s0), (q0, b0, act0) = default_update
-    _, (p1, a1, s1), (q1, b1, act1) = _update_under(switch)
+    rate.  The rollout-forward variants run the same kernels on the same numbers: identical bits, also after a second iteration.  Every switch that
+    selects a kernel form resolves to a plan of its own (none is silently ignored); only the scheduling switches leave the plan as it is."""
+    start, (p0, a0, s0), (q0, b0, act0), plan0 = default_update
+    _, (p1, a1, s1), (q1, b1, act1), plan1 = _update_under(switch)
+    scheduling = switch.startswith("rollout_forward_") and switch != "rollout_forward_off" or switch.endswith("_one_workgroup_per_slab")
+    assert (plan1 == plan0) == scheduling, (switch, plan1, plan0)
     if switch.startswith("rollout_forward") or switch in ("chain_one_workgroup_per_slab", "backward_chain_one_workgroup_per_slab", "two_launches_on_two_streams"):
         assert torch.equal(p1, p0) and torch.equal(a1, a0) and torch.equal(q1, q0) and torch.equal(b1, b0) and torch.equal(act1, act0)
         return
@@ -458,18 +461,43 @@ def test_cu_shares_of_the_chains_change_no_bit(monkeypatch):
             assert s1 == (0, 0, 0, 0)
 
 
+def test_switching_a_live_runner_to_the_fp32_chains_takes_the_fp32_weight_gradients():
+    """What bench.py does between its loops: the class switches flipped on a runner that has already run (with runner.invalidate()).  The next
+    update resolves its plan afresh, and the grouped weight gradients follow it: the fp32 chains take the fp32-MFMA launch, not the split launch
+    the default path left behind (its descriptors are cached on the same buffers)."""
+    from booster_gym_amd.utils.config import load_cfg
+    from booster_gym_amd.utils.model import MLPTrainer
+    from booster_gym_amd.utils.runner import Runner
+
+    r = Runner(cfg=load_cfg("T1", {"env.num_envs": 256, "terrain.type": "plane", "runner.mini_epochs": 2, "basic.seed": 3}))
+    obs, infos = r.env.reset()
+    r.buffer["obses"][0].copy_(obs); r.buffer["privileged_obses"][0].copy_(infos["privileged_obs"])
+    r.iteration()
+    assert r._wgrad_group.split == MLPTrainer.WGRAD_SPLIT != 0
+    keep = MLPTrainer.CHAIN_SPLIT
+    try:
+        MLPTrainer.CHAIN_SPLIT = False
+        r.invalidate()
+        r.iteration()
+        torch.cuda.synchronize()
+        assert r._wgrad_group.split == 0
+        assert torch.isfinite(r.optimizer.flat).all()
+    finally:
+        MLPTrainer.CHAIN_SPLIT = keep
+
+
 def test_update_with_deferred_reductions_equals_update_with_immediate_ones():
-    """Runner.update() with the small reductions deferred to one launch in front of the weight gradients (the default), to one launch on the side
-    stream beside them (BG_DEFER_FINISH=2) and with every finish inside its chain (=0), from identical weights and rollout data: same parameters
-    after 3 mini-epochs up to the summation order of the hidden layers' bias gradients, same loss statistics."""
+    """Runner.update() with the small reductions deferred to one launch in front of the weight gradients (the default) and with every finish inside
+    its chain (BG_DEFER_FINISH=0), from identical weights and rollout data: same parameters after 3 mini-epochs up to the summation order of the
+    hidden layers' bias gradients, same loss statistics."""
     from booster_gym_amd.utils.config import load_cfg
     from booster_gym_amd.utils.runner import Runner
 
     res = []
-    for defer, serial in ((True, True), (True, False), (False, True)):
+    for defer in (True, False):
         cfg = load_cfg("T1", {"env.num_envs": 128, "terrain.type": "plane", "runner.mini_epochs": 3})
         r = Runner(cfg=cfg)
-        r._defer_finish, r._defer_serial = defer, serial
+        r._defer_finish = defer
         obs, infos = r.env.reset()
         r.buffer["obses"][0].copy_(obs); r.buffer["privileged_obses"][0].copy_(infos["privileged_obs"])
         r.rollout()
@@ -477,12 +505,10 @@ def test_update_with_deferred_reductions_equals_update_with_immediate_ones():
         torch.cuda.synchronize()
         res.append((r.optimizer.flat.clone(), acc, r._summarize(acc)))
         del r
-    p0, a0, s0 = res[2]
-    for p1, a1, s1 in res[:2]:
-        assert torch.allclose(p1, p0, rtol=1e-5, atol=1e-7), (p1 - p0).abs().max().item()
-        assert torch.allclose(a1, a0, rtol=1e-4)
-        assert abs(s1["lr"] - s0["lr"]) < 1e-12
-    assert torch.equal(res[0][0], res[1][0])  # the two deferred forms run the same launches: identical bits
+    (p1, a1, s1), (p0, a0, s0) = res
+    assert torch.allclose(p1, p0, rtol=1e-5, atol=1e-7), (p1 - p0).abs().max().item()
+    assert torch.allclose(a1, a0, rtol=1e-4)
+    assert abs(s1["lr"] - s0["lr"]) < 1e-12
 
 
 @pytest.mark.parametrize("B,C,with_act", [(98304, 256, True), (98304, 128, True), (3000, 256, True), (1000, 128, True), (777, 12, False), (98304, 1, False),

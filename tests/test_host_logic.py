@@ -982,3 +982,81 @@ def test_chain_split_gives_each_xcd_whole_workgroups():
         assert cost(c) <= 1.03 * min(cost(x) for x in range(1, 256)), (envs, c, cost(c))
     assert plan_chain_split(800, 768, fc, fa, 256) == (160, 96)  # the bench shape
     assert sum(plan_chain_split(800, 768, fc, fa, 250)) == 250   # a part whose CU count is no multiple of 8: any split
+
+
+def test_update_plan_names_the_form_every_switch_selects():
+    """plan_update (host only): the default switches give the default path -- both networks' chains on the bf16 matrix pipe, the split weight
+    gradients, one stream, the one-launch tail, the rollout's forward-ahead -- and every entry of tests/test_gpu_ppo.py's SWITCHES gives the form it
+    names; only the scheduling entries (rollout group sizes, one workgroup per slab) leave the plan as it is."""
+    from booster_gym_amd.utils.model import NetPlan
+    from booster_gym_amd.utils.runner import plan_update
+    from test_gpu_ppo import SWITCHES
+
+    inputs = dict(split=0, fused=True, chain=True, chain_split=True, chain_split_bwd=True, chain_alternate=True, fused_wgrad=True, wgrad_split=9,
+                  one_stream=True, defer_finish=True, one_launch_tail=True, fused_opt=True, fused_head=True, fused_gae=True, chain_values=True,
+                  rollout_forward=True, dp_active=False)
+
+    def plan(**sw):
+        return plan_update(((61, 256, 256, 128, 1), 64), ((47, 256, 128, 128, 12), 64), 24 * 4096, **dict(inputs, **sw))
+
+    d = plan()
+    assert d.critic == d.actor == NetPlan("chain_split", "chain_split", True, 0, (True, True, True, False))
+    assert d.wgrad == 9 and d.one_stream and d.defer and d.one_tail and d.ahead and d.chain_values and d.fused_opt and not d.ranks
+    nets = lambda **kw: dict(critic=d.critic._replace(**kw), actor=d.actor._replace(**kw))
+    fp32_bwd = dict(wgrad=0, one_stream=False)
+    want = {
+        "default": d,
+        "tail_as_three_launches": d._replace(one_tail=False),
+        "separate_optimizer_tail": d._replace(fused_opt=False, one_tail=False),
+        "gae_as_three_launches": d._replace(fused_gae=False, chain_values=False, one_stream=False, ahead=False),
+        "values_from_stored_activations": d._replace(chain_values=False, one_stream=False, ahead=False),
+        "output_layers_as_library_gemms": d._replace(fused_head=False, chain_values=False, defer=False, one_tail=False, ahead=False, **nets(bwd="layer"), **fp32_bwd),
+        "hidden_layers_one_launch_each": d._replace(chain_values=False, ahead=False, **nets(fwd="layer", bwd="layer"), **fp32_bwd),
+        "hidden_layers_as_library_gemms": d._replace(chain_values=False, ahead=False, one_tail=False, **nets(fwd="library", bwd="library", grouped=(False,) * 4), **fp32_bwd),
+        "weight_gradients_as_library_gemms": d._replace(one_tail=False, **nets(grouped=(False,) * 4)),
+        "fp32_mfma_chains": d._replace(**nets(fwd="chain", bwd="layer"), **fp32_bwd),          # the fp32 weight-gradient launch too
+        "split_forward_fp32_mfma_backward": d._replace(**nets(bwd="layer"), **fp32_bwd),        # ... here as well
+        "fp32_mfma_weight_gradients": d._replace(wgrad=0),
+        "plain_accumulation": d._replace(**nets(alternate=False)),
+        "two_launches_on_two_streams": d._replace(one_stream=False),
+        "rollout_forward_off": d._replace(ahead=False),
+    }
+    for switch, (attrs, cls_attrs) in SWITCHES.items():
+        sw = {k.strip("_").lower(): v for k, v in {**attrs, **cls_attrs}.items()}
+        scheduling = {k: v for k, v in sw.items() if k not in inputs}  # CU shares and rollout groups: not part of the plan
+        got = plan(**{k: v for k, v in sw.items() if k in inputs})
+        assert got == want.get(switch, d), (switch, got)
+        assert (got == d) == (switch == "default" or bool(scheduling)), switch
+    # per-layer split GEMMs (BG_GEMM_SPLIT): the split kernels everywhere, reductions inside the chains
+    s = plan(split=6)
+    assert s.critic.fwd == s.actor.bwd == "layer_split" and s.critic.terms == 6 and s.wgrad == 6 and not (s.defer or s.one_tail or s.ahead)
+    # a batch the grouped split kernel cannot take (rows % 32): the fp32 launch; ranks: the exchanges
+    assert plan_update(((61, 256, 256, 128, 1), 64), ((47, 256, 128, 128, 12), 64), 24 * 4099, **dict(inputs, dp_active=True)).wgrad == 0
+    assert plan(dp_active=True).ranks
+
+
+def test_cu_shares_are_planned_before_the_trainers_have_run(monkeypatch):
+    """Runner._plan_chain_split at the bench shape (4,096 envs, horizon 24: 800 + 768 slabs on 256 CUs) with trainers that no pass has allocated yet --
+    the first update() when no forward-ahead ran in the rollout (BG_ROLLOUT_FORWARD=0, horizons beyond 32, ...): the slab costs come from the inputs'
+    padded width, and the shares are the bench's."""
+    import types
+
+    from booster_gym_amd.utils.model import ActorCritic, MLPTrainer
+    from booster_gym_amd.utils.runner import Runner, plan_chain_split, plan_update
+
+    for k in ("BG_FWD_CHAIN_CUS", "BG_BWD_CHAIN_CUS"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(torch.cuda, "get_device_properties", lambda dev: types.SimpleNamespace(multi_processor_count=256))
+    m = ActorCritic(12, 47, 14)
+    r = Runner.__new__(Runner)
+    r._critic_tr, r._actor_tr, r.device = MLPTrainer(m.critic), MLPTrainer(m.actor), "cpu"
+    r._split_chain_cus = r._split_bwd_chain_cus = True
+    plan = plan_update(((61, 256, 256, 128, 1), 64), ((47, 256, 128, 128, 12), 64), 24 * 4096, split=0, fused=True, chain=True, chain_split=True,
+                       chain_split_bwd=True, chain_alternate=True, fused_wgrad=True, wgrad_split=9, one_stream=True, defer_finish=True, one_launch_tail=True,
+                       fused_opt=True, fused_head=True, fused_gae=True, chain_values=True, rollout_forward=False, dp_active=False)
+    assert r._critic_tr._kin is None and r._actor_tr._kin is None
+    r._plan_chain_split(torch.empty(25 * 4096, 64, device="meta"), torch.empty(24 * 4096, 64, device="meta"), plan)
+    fc, fa = 64 * 256 + 256 * 256 + 256 * 128, 64 * 256 + 256 * 128 + 128 * 128
+    bc, ba = 256 * 256 + 128 * 256, 128 * 256 + 128 * 128
+    assert (r._critic_tr.chain_workgroups, r._actor_tr.chain_workgroups) == plan_chain_split(800, 768, fc, fa, 256) == (160, 96)
+    assert (r._critic_tr.chain_bwd_workgroups, r._actor_tr.chain_bwd_workgroups) == plan_chain_split(768, 768, bc, ba, 256)
