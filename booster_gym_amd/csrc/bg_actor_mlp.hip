@@ -1,0 +1,183 @@
+// Fused actor MLP + Gaussian sample for the rollout at any supported architecture (reference utils/model.py:8-25 with the widths a user sets,
+// utils/runner.py:109-111: dist = model.act(obs); act = dist.sample()), fp32 MFMA, gfx950 only.  bg_actor_sample (bg_ppo.hip) keeps the
+// reference's widths built into its kernel; this one reads them from descriptors: 47 inputs, 2 to 4 hidden ELU layers of widths a multiple of 128
+// up to 512, 12 outputs.
+//
+// One workgroup (4 waves) = 16 observation rows.  The activations ping-pong between two LDS tiles [16][MAXW + 4]; each wave owns the 16-neuron
+// output tiles wave, wave + 4, ... of a layer and accumulates them with v_mfma_f32_16x16x4_f32 (exact fp32, D = A*B + C), operands as in
+// bg_actor_sample:
+//     A[i = lane & 15][k = lane >> 4] = X[row i][k]          (from LDS, one ds_read_b128 feeds 4 MFMAs)
+//     B[k = lane >> 4][j = lane & 15] = W[neuron j][k]       (straight from global memory / L2: torch layout [out][in], one 16-byte load feeds 4 MFMAs)
+//     C/D: neuron j = lane & 15, row i = (lane >> 4) * 4 + reg
+// A wave walks its (tile, 128-wide k-chunk) steps in one flat loop and fetches the 8 weight vectors (+ the bias) of step s + 1 before it runs the
+// 32 MFMAs of step s, so the L2 latency hides under them whatever the widths.  Two accumulators per tile (even / odd k groups) keep the MFMA chain
+// from waiting on its own 40-cycle dependent latency.
+// LDS: 2 x 16 x 516 floats = 66 kB at MAXW = 512 (two workgroups per CU), 33 kB at MAXW = 256; 16 rows per workgroup: 256 workgroups at 4,096 rows.
+// The noise is bg_actor_sample's: the same bg::rand4(seed, row, counter, RS_ACTOR + g) draw per (row, group of 4 actions), the same expression.
+#include <hip/hip_runtime.h>
+
+#include "../../include/booster_gym_amd.h"
+#include "bg_rng.h"
+
+extern int bg_set_error(int code, const char* msg);
+#define HIP_OK(expr)                                                                        \
+    do {                                                                                    \
+        hipError_t _e = (expr);                                                             \
+        if (_e != hipSuccess) return bg_set_error(-2, hipGetErrorString(_e));               \
+    } while (0)
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+constexpr int MR = 16;         // rows per workgroup
+constexpr int MAX_LAYERS = 5;  // 4 hidden + the output layer
+constexpr int KIN = 48;        // the 47 observations padded with a zero column
+
+struct ActorNet {
+    const float* W[MAX_LAYERS];
+    const float* b[MAX_LAYERS];
+    int in[MAX_LAYERS], out[MAX_LAYERS];
+    int n;
+};
+
+__device__ __forceinline__ float elu(float x) { return x > 0.f ? x : expm1f(x); }  // = bg_ppo.hip's
+
+// first layer: K = 47 (rows not 16-byte aligned): scalar weight loads, k padded to 48 with zeros; OUT a multiple of 16.  One step per tile.
+template <int LDA>
+__device__ __forceinline__ void first_layer(const float* __restrict__ W, const float* __restrict__ bv, int OUT, const float* in, float* out, int wave,
+                                            int lane) {
+    constexpr int STEPS = KIN / 4;
+    const int r = lane & 15, kg = lane >> 4, tiles = OUT / 16;
+    if (wave >= tiles) return;
+    float cur[STEPS], nxt[STEPS] = {}, bc, bn = 0.f;
+    auto fetch = [&](float (&w)[STEPS], float& bias, int tile) {
+        const int n = tile * 16 + r;
+#pragma unroll
+        for (int s2 = 0; s2 < STEPS; s2++) { const int k = 4 * s2 + kg; w[s2] = k < BG_NUM_OBS ? W[(size_t)n * BG_NUM_OBS + k] : 0.f; }
+        bias = bv[n];
+    };
+    fetch(cur, bc, wave);
+    for (int tile = wave; tile < tiles; tile += 4) {
+        if (tile + 4 < tiles) fetch(nxt, bn, tile + 4);
+        f32x4 acc = {bc, bc, bc, bc};
+#pragma unroll
+        for (int s2 = 0; s2 < STEPS; s2++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(in[r * LDA + 4 * s2 + kg], cur[s2], acc, 0, 0, 0);
+#pragma unroll
+        for (int q = 0; q < 4; q++) out[(kg * 4 + q) * LDA + tile * 16 + r] = elu(acc[q]);
+#pragma unroll
+        for (int s2 = 0; s2 < STEPS; s2++) cur[s2] = nxt[s2];
+        bc = bn;
+    }
+}
+
+// a layer of K inputs (a multiple of 128) and OUT outputs; neurons >= OUT (the 12-wide output layer's last tile) compute zeros that nobody reads
+template <int LDA>
+__device__ __forceinline__ void layer(const float* __restrict__ W, const float* __restrict__ bv, int K, int OUT, bool act, const float* in, float* out,
+                                      int wave, int lane) {
+    const int r = lane & 15, kg = lane >> 4, tiles = (OUT + 15) / 16, cpt = K >> 7;
+    if (wave >= tiles) return;
+    const int steps = (tiles - wave + 3) / 4 * cpt;
+    f32x4 cur[8], nxt[8] = {};
+    float bc = 0.f, bn = 0.f;
+    auto fetch = [&](f32x4 (&w)[8], float& bias, int s) {
+        const int tile = wave + 4 * (s / cpt), c = s % cpt, n = tile * 16 + r;
+        const bool nv = n < OUT;
+        const float* wrow = W + (size_t)(nv ? n : 0) * K + c * 128 + 4 * kg;
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            w[u] = *reinterpret_cast<const f32x4*>(wrow + 16 * u);
+            if (!nv) w[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        if (c == 0) bias = nv ? bv[n] : 0.f;
+    };
+    fetch(cur, bc, 0);
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
+    for (int s = 0; s < steps; s++) {
+        if (s + 1 < steps) fetch(nxt, bn, s + 1);
+        const int tile = wave + 4 * (s / cpt), c = s % cpt;
+        if (c == 0) { acc0 = f32x4{bc, bc, bc, bc}; acc1 = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        const float* arow = in + r * LDA + c * 128 + 4 * kg;
+#pragma unroll
+        for (int u = 0; u < 8; u += 2) {
+            const f32x4 a0 = *reinterpret_cast<const f32x4*>(arow + 16 * u), a1 = *reinterpret_cast<const f32x4*>(arow + 16 * (u + 1));
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, cur[u].x, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, cur[u + 1].x, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, cur[u].y, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, cur[u + 1].y, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, cur[u].z, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, cur[u + 1].z, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, cur[u].w, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, cur[u + 1].w, acc1, 0, 0, 0);
+        }
+        if (c == cpt - 1) {
+            const f32x4 v = acc0 + acc1;
+#pragma unroll
+            for (int q = 0; q < 4; q++) out[(kg * 4 + q) * LDA + tile * 16 + r] = act ? elu(v[q]) : v[q];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; u++) cur[u] = nxt[u];
+        if (c + 1 == cpt) bc = bn;
+    }
+}
+
+template <int MAXW>
+__global__ __launch_bounds__(256) void actor_mlp_sample_kernel(int N, const float* __restrict__ obs, ActorNet net, const float* __restrict__ logstd,
+                                                               uint64_t seed, uint32_t counter, float* __restrict__ mu_out, float* __restrict__ act_out) {
+    constexpr int LDA = MAXW + 4;  // row stride (floats): = 4 mod 64 banks, as bg_actor_sample's 260
+    __shared__ __attribute__((aligned(16))) float buf[2][MR * LDA];
+    const int r0 = blockIdx.x * MR, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int k = threadIdx.x; k < MR * KIN; k += blockDim.x) {  // obs tile, k padded 47 -> 48 with zeros
+        const int r = k / KIN, c = k % KIN;
+        buf[0][r * LDA + c] = (r0 + r < N && c < BG_NUM_OBS) ? obs[(size_t)(r0 + r) * BG_NUM_OBS + c] : 0.f;
+    }
+    __syncthreads();
+    first_layer<LDA>(net.W[0], net.b[0], net.out[0], buf[0], buf[1], wave, lane);
+    __syncthreads();
+    int cur = 1;
+    for (int l = 1; l < net.n; l++) {
+        layer<LDA>(net.W[l], net.b[l], net.in[l], net.out[l], l + 1 < net.n, buf[cur], buf[cur ^ 1], wave, lane);
+        __syncthreads();
+        cur ^= 1;
+    }
+    // sample: one thread per (row, group of 4 actions), as bg_actor_sample
+    if (threadIdx.x < MR * 3) {
+        const int r = threadIdx.x / 3, g = threadIdx.x % 3, row = r0 + r;
+        if (row < N) {
+            bg::Rand4 rn = bg::rand4(seed, (uint32_t)row, counter, bg::RS_ACTOR + g);
+            for (int k = 0; k < 4; k++) {
+                const int a = g * 4 + k;
+                const float m = buf[cur][r * LDA + a];
+                if (mu_out) mu_out[(size_t)row * BG_NUM_DOFS + a] = m;
+                act_out[(size_t)row * BG_NUM_DOFS + a] = m + expf(logstd[a]) * rn.n[k];
+            }
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int bg_actor_sample_mlp(int32_t N, const float* obs, int32_t n_layers, const bg_mlp_layer_desc* layers, const float* logstd, uint64_t seed,
+                                   uint64_t counter, float* mu, float* actions, void* stream) {
+    if (N <= 0 || !obs || !layers || !logstd || !actions) return bg_set_error(-1, "bg_actor_sample_mlp: bad argument");
+    if (n_layers < 3 || n_layers > MAX_LAYERS) return bg_set_error(-4, "bg_actor_sample_mlp: 2 to 4 hidden layers (n_layers 3 to 5)");
+    ActorNet net{};
+    net.n = n_layers;
+    int maxw = 0;
+    for (int l = 0; l < n_layers; l++) {
+        const bg_mlp_layer_desc& d = layers[l];
+        if (!d.W || !d.b) return bg_set_error(-1, "bg_actor_sample_mlp: bad argument (layer weights)");
+        const bool last = l + 1 == n_layers;
+        if (d.in != (l == 0 ? BG_NUM_OBS : layers[l - 1].out)) return bg_set_error(-4, "bg_actor_sample_mlp: layer widths do not chain (first layer: 47 inputs)");
+        if (last ? d.out != BG_NUM_DOFS : (d.out % 128 != 0 || d.out < 128 || d.out > 512))
+            return bg_set_error(-4, "bg_actor_sample_mlp: unsupported widths (hidden: multiples of 128 up to 512; output: 12)");
+        if (l > 0 && ((uintptr_t)d.W & 15)) return bg_set_error(-1, "bg_actor_sample_mlp: weight matrices after the first must be 16-byte aligned");
+        net.W[l] = d.W; net.b[l] = d.b; net.in[l] = d.in; net.out[l] = d.out;
+        if (!last && d.out > maxw) maxw = d.out;
+    }
+    const dim3 grid((N + MR - 1) / MR), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (maxw <= 256) hipLaunchKernelGGL(actor_mlp_sample_kernel<256>, grid, block, 0, st, N, obs, net, logstd, seed, (uint32_t)counter, mu, actions);
+    else hipLaunchKernelGGL(actor_mlp_sample_kernel<512>, grid, block, 0, st, N, obs, net, logstd, seed, (uint32_t)counter, mu, actions);
+    HIP_OK(hipGetLastError());
+    return 0;
+}

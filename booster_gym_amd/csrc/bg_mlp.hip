@@ -1,5 +1,6 @@
 // Hand-written fp32-MFMA layer kernels for the PPO update's MLPs (reference utils/model.py:9-26 Linear+ELU stacks, runner.py:132,147,163),
-// gfx950 only.  Shapes are tall and skinny (M = 98,304 rows, K and N in {128, 256}), so one workgroup owns a 128-row slab and ALL N columns:
+// gfx950 only.  Shapes are tall and skinny (M = 98,304 rows, K and N in {128, 256}; up to 512 for configured wider networks), so one workgroup owns
+// a 128-row slab and ALL N columns:
 //   * the A operand (activations) is read once from HBM straight into registers (16-byte loads, k permuted identically for A and B so that
 //     one load feeds four v_mfma_f32_32x32x2_f32) and reused across the N/32 column tiles;
 //   * the B operand (weights, <= 256 kB, L2 resident) is staged per 32-wide k-chunk in LDS and shared by the 4 waves;
@@ -173,8 +174,9 @@ extern "C" int bg_mlp_layer_forward(int32_t M, int32_t K, int32_t N, const float
     BG_FWD(256)
     BG_FWD(128)
     BG_FWD(64)
+    BG_FWD(512)
 #undef BG_FWD
-    return bg_set_error(-4, "bg_mlp_layer_forward: unsupported K (64, 128, 256)");
+    return bg_set_error(-4, "bg_mlp_layer_forward: unsupported K (64, 128, 256, 512)");
 }
 
 extern "C" int bg_mlp_layer_backward(int32_t M, int32_t K, int32_t N, const float* G, const float* Wt, const float* act_below, float* Gout,
@@ -197,8 +199,9 @@ extern "C" int bg_mlp_layer_backward(int32_t M, int32_t K, int32_t N, const floa
     }
     BG_BWD(256)
     BG_BWD(128)
+    BG_BWD(512)
 #undef BG_BWD
-    return bg_set_error(-4, "bg_mlp_layer_backward: unsupported K (128, 256)");
+    return bg_set_error(-4, "bg_mlp_layer_backward: unsupported K (128, 256, 512)");
 }
 
 // bg_mlp_layer_backward without the column-sum finish: the descriptor of that reduction instead (bg_reduce_group runs it later)
@@ -208,7 +211,7 @@ extern "C" int bg_mlp_layer_backward_partial(int32_t M, int32_t K, int32_t N, co
     if ((((uintptr_t)G | (uintptr_t)Wt | (uintptr_t)Gout | (uintptr_t)act_below) & 15) != 0)
         return bg_set_error(-1, "bg_mlp_layer_backward_partial: pointers must be 16-byte aligned");
     if (N % 128 != 0 || N > 1024) return bg_set_error(-4, "bg_mlp_layer_backward_partial: unsupported N (multiples of 128 up to 1024)");
-    if (K != 256 && K != 128) return bg_set_error(-4, "bg_mlp_layer_backward_partial: unsupported K (128, 256)");
+    if (K != 256 && K != 128 && K != 512) return bg_set_error(-4, "bg_mlp_layer_backward_partial: unsupported K (128, 256, 512)");
     const int nb = (M + FW_BM - 1) / FW_BM;
     dim3 grid(((nb + 7) / 8) * 8 * (N / 128)), block(256);
     hipStream_t st = (hipStream_t)stream;
@@ -220,6 +223,7 @@ extern "C" int bg_mlp_layer_backward_partial(int32_t M, int32_t K, int32_t N, co
     }
     BG_BWDP(256)
     BG_BWDP(128)
+    BG_BWDP(512)
 #undef BG_BWDP
     HIP_OK(hipGetLastError());
     memset(finish, 0, sizeof(*finish));

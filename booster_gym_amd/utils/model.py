@@ -2,10 +2,12 @@
 
 Same architecture and `state_dict` key names as reference `utils/model.py:5-36` (so checkpoints and the exported
 TorchScript actor interoperate): `critic.{0,2,4,6}`, `actor.{0,2,4,6}`, `logstd`; actor 47-256-128-128-12,
-critic (47+14)-256-256-128-1, ELU, state-independent log-std initialised to -2.
+critic (47+14)-256-256-128-1, ELU, state-independent log-std initialised to -2.  The hidden widths are configurable
+(`algorithm.actor_hidden` / `algorithm.critic_hidden`, checked by `check_hidden`): 2 to 4 hidden layers of 128, 256 or 512, the last 128 wide;
+the keys keep the `Sequential` numbering (`actor.{0,2,4,6,8}` for four hidden layers).
 The PPO update's GEMMs run on hand-written HIP kernels (MLPTrainer: the chained hidden layers, the grouped weight
 gradients), in the form its NetPlan names; the rollout-time inference + sampling is one fused HIP launch
-(`sample_actions` -> bg_actor_sample).
+(`sample_actions` -> bg_actor_sample at the reference's widths, bg_actor_sample_mlp at any other supported widths).
 """
 import ctypes
 from typing import NamedTuple
@@ -16,6 +18,38 @@ from .. import _lib
 
 ACTOR_HIDDEN = (256, 128, 128)
 CRITIC_HIDDEN = (256, 256, 128)
+# The architectures every kernel of the rollout and the update takes: 2 to 4 hidden layers, each of these widths, the last one HEAD_WIDTH wide (the
+# fused output layers of bg_head.hip).  The reference's widths run the chained kernels; every other supported architecture the per-layer ones.
+HIDDEN_WIDTHS = (128, 256, 512)
+HIDDEN_LAYERS = (2, 4)
+HEAD_WIDTH = 128
+SPLIT_K = (64, 128, 256)  # layer inputs of the split-bf16 per-layer kernels (bg_mlp_split.hip)
+
+
+def check_hidden(actor_hidden=ACTOR_HIDDEN, critic_hidden=CRITIC_HIDDEN, split=0):
+    """The two width lists as tuples, or ValueError naming the supported set.  split: the products of the split-bf16 GEMMs in use
+    (parallel.gemm_split / BG_GEMM_SPLIT; 0 = off), whose per-layer kernels take layer inputs of SPLIT_K columns only."""
+    supported = (f"supported: {HIDDEN_LAYERS[0]} to {HIDDEN_LAYERS[1]} hidden layers, each of width {', '.join(map(str, HIDDEN_WIDTHS))}, "
+                 f"the last one {HEAD_WIDTH} (the fused output layers)")
+    out = []
+    for name, h in (("algorithm.actor_hidden", actor_hidden), ("algorithm.critic_hidden", critic_hidden)):
+        ok = (isinstance(h, (list, tuple)) and HIDDEN_LAYERS[0] <= len(h) <= HIDDEN_LAYERS[1]
+              and all(isinstance(w, int) and not isinstance(w, bool) and w in HIDDEN_WIDTHS for w in h) and h[-1] == HEAD_WIDTH)
+        if not ok:
+            raise ValueError(f"{name} = {h!r} is not a supported architecture; {supported}")
+        out.append(tuple(h))
+    if split:
+        for name, h in zip(("algorithm.actor_hidden", "algorithm.critic_hidden"), out):
+            if any(w not in SPLIT_K for w in h[:-1]):
+                raise ValueError(f"parallel.gemm_split / BG_GEMM_SPLIT = {split} runs split-bf16 layer kernels that take layer inputs of "
+                                 f"{', '.join(map(str, SPLIT_K))} columns only; {name} = {list(h)} has a wider layer (use gemm_split 0)")
+    return out[0], out[1]
+
+
+def hidden_of(state_dict, net):
+    """Hidden widths of network `net` ("actor" / "critic") of an ActorCritic state_dict: the output widths of its Linear layers but the last."""
+    idx = sorted(int(k.split(".")[1]) for k in state_dict if k.startswith(net + ".") and k.endswith(".weight"))
+    return tuple(int(state_dict[f"{net}.{i}.weight"].shape[0]) for i in idx[:-1])
 
 
 def _mlp(n_in, hidden, n_out):
@@ -134,7 +168,7 @@ class MLPTrainer:
     The "library" forms (torch GEMMs + bg_elu_backward_colsum, split-K bmm weight gradients) serve other widths and the tests that compare forms.
     """
 
-    # Hidden layers with K in {64, 128, 256} and N % 128 == 0 run on the hand-written fused fp32-MFMA layer (bg_mlp.hip: bias + ELU in the GEMM
+    # Hidden layers with K in {64, 128, 256, 512} and N % 128 == 0 run on the hand-written fused fp32-MFMA layer (bg_mlp.hip: bias + ELU in the GEMM
     # epilogue).  Measured on MI355X at M = 98,304 (tools/mlp_probe.py): 131.8 vs 151.3 us (256x256), 63.9 vs 76.3 us (256x128), 37.5 vs 55.8 us
     # (128x128) against hipBLASLt addmm + elu_.  Other shapes, or FUSED = False (a class attribute, for the tests that compare the two forms): the
     # library GEMM + elementwise ELU.
@@ -152,12 +186,12 @@ class MLPTrainer:
     @staticmethod
     def _fusable(k_in, n_out):
         """Shapes of the per-layer forward kernels (bg_mlp.hip, bg_mlp_split.hip)."""
-        return k_in in (64, 128, 256) and n_out % 128 == 0
+        return k_in in (64, 128, 256, 512) and n_out % 128 == 0
 
     @staticmethod
     def bwd_fusable(c_out, c_in):
         """Shapes of the per-layer backward-data kernels (bg_mlp_layer_backward*); other layers take torch.mm + bg_elu_backward_colsum."""
-        return c_out in (128, 256) and c_in % 128 == 0
+        return c_out in (128, 256, 512) and c_in % 128 == 0
 
     # The forward pass of the three hidden layers as one launch (bg_mlp_chain_forward) where the widths are the reference's (CHAIN = False: one launch
     # per layer)
@@ -585,11 +619,13 @@ class MLPTrainer:
 
 
 class ActorCritic(torch.nn.Module):
-    def __init__(self, num_act, num_obs, num_privileged_obs):
+    def __init__(self, num_act, num_obs, num_privileged_obs, actor_hidden=ACTOR_HIDDEN, critic_hidden=CRITIC_HIDDEN):
         super().__init__()
-        self.critic = _mlp(num_obs + num_privileged_obs, CRITIC_HIDDEN, 1)
-        self.actor = _mlp(num_obs, ACTOR_HIDDEN, num_act)
+        self.actor_hidden, self.critic_hidden = tuple(actor_hidden), tuple(critic_hidden)
+        self.critic = _mlp(num_obs + num_privileged_obs, self.critic_hidden, 1)
+        self.actor = _mlp(num_obs, self.actor_hidden, num_act)
         self.logstd = torch.nn.parameter.Parameter(torch.full((1, num_act), fill_value=-2.0), requires_grad=True)
+        self._sample_key, self._sample_layers = None, None
 
     def act(self, obs):
         mean = self.actor(obs)
@@ -600,13 +636,25 @@ class ActorCritic(torch.nn.Module):
 
     # ---- fused rollout inference (reference runner.py:109-111: dist = model.act(obs); act = dist.sample())
     def sample_actions(self, obs, actions_out, seed, counter, mu_out=None):
+        """One launch: the actor's mean and a Gaussian sample around it.  The reference's widths run bg_actor_sample (its widths built into the
+        kernel), every other architecture bg_actor_sample_mlp (widths from descriptors); both draw the same noise for the same seed and counter."""
         if not obs.is_cuda:
             raise RuntimeError("sample_actions runs the fused HIP actor kernel and needs CUDA tensors")
         a = self.actor
-        w = [a[0].weight, a[0].bias, a[2].weight, a[2].bias, a[4].weight, a[4].bias, a[6].weight, a[6].bias, self.logstd]
+        lin = [m for m in a if isinstance(m, torch.nn.Linear)]
+        w = [t for l in lin for t in (l.weight, l.bias)] + [self.logstd]
         for t in w + [obs, actions_out]:
             if not t.is_contiguous():
                 raise RuntimeError("sample_actions needs contiguous tensors")
-        _lib.check(_lib.load().bg_actor_sample(obs.shape[0], _lib.ptr(obs), *[_lib.ptr(t) for t in w], int(seed), int(counter), _lib.ptr(mu_out),
-                                               _lib.ptr(actions_out), _lib.current_stream_ptr()), "bg_actor_sample")
+        if self.actor_hidden == ACTOR_HIDDEN:
+            _lib.check(_lib.load().bg_actor_sample(obs.shape[0], _lib.ptr(obs), *[_lib.ptr(t) for t in w], int(seed), int(counter), _lib.ptr(mu_out),
+                                                   _lib.ptr(actions_out), _lib.current_stream_ptr()), "bg_actor_sample")
+            return actions_out
+        key = tuple(t.data_ptr() for t in w)
+        if key != self._sample_key:  # descriptors of the current parameter storage (the optimiser moves it into its flat buffer once)
+            self._sample_layers = (_lib.MlpLayerDesc * len(lin))(*[_lib.MlpLayerDesc(l.weight.data_ptr(), l.bias.data_ptr(), l.in_features, l.out_features)
+                                                                   for l in lin])
+            self._sample_key = key
+        _lib.check(_lib.load().bg_actor_sample_mlp(obs.shape[0], _lib.ptr(obs), len(lin), self._sample_layers, _lib.ptr(self.logstd), int(seed), int(counter),
+                                                   _lib.ptr(mu_out), _lib.ptr(actions_out), _lib.current_stream_ptr()), "bg_actor_sample_mlp")
         return actions_out

@@ -46,7 +46,7 @@ from .. import _lib
 from ..envs import TASKS
 from .buffer import ExperienceBuffer
 from .config import load_cfg
-from .model import ActorCritic, GroupedWeightGrad, MLPTrainer, NetPlan, plan_network
+from .model import ACTOR_HIDDEN, CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, MLPTrainer, NetPlan, check_hidden, hidden_of, plan_network
 from .parallel import DataParallel
 from .recorder import Recorder
 from .utils import (actor_head_forward, actor_head_loss_backward, critic_head_backward, critic_head_forward, critic_values_gae, gae, gaussian_logp, head_scratch, reduce_group,
@@ -67,6 +67,14 @@ def plan_chain_split(slabs_c, slabs_a, cost_c, cost_a, cus, xcds=8):
     return best, cus - best
 
 
+def hidden_widths(cfg):
+    """(actor, critic) hidden widths of a config: algorithm.actor_hidden / algorithm.critic_hidden (default: the reference's), checked against the
+    supported set and against the split-bf16 GEMMs if parallel.gemm_split or BG_GEMM_SPLIT selects them (model.check_hidden: ValueError)."""
+    alg = cfg.get("algorithm", {}) or {}
+    split = int((cfg.get("parallel", {}) or {}).get("gemm_split", 0) or 0) or MLPTrainer.SPLIT
+    return check_hidden(alg.get("actor_hidden", ACTOR_HIDDEN), alg.get("critic_hidden", CRITIC_HIDDEN), split)
+
+
 class UpdatePlan(NamedTuple):
     """The kernels of one Runner.update() and of the rollout's forward-ahead (plan_update): resolved once per call, read by every branch."""
     critic: NetPlan
@@ -81,6 +89,9 @@ class UpdatePlan(NamedTuple):
     one_tail: bool      # ... together with the deferred sums and the weight gradients' finish (bg_update_tail; the weight gradients partial)
     ahead: bool         # the rollout runs the first mini-epoch's forward passes
     ranks: bool         # several ranks: the exchanges run
+
+
+TAIL_MAX_ITEMS = 8192  # blocks of sums of one bg_update_tail launch (bg_tail.hip)
 
 
 def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_split_bwd, chain_alternate, fused_wgrad, wgrad_split, one_stream,
@@ -100,7 +111,13 @@ def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_
     fins = [1 if n.bwd == "chain_split" else len(w) - 3 for (w, _), n in zip((critic, actor), nets)]
     finishing = all(n.bwd == "chain_split" or n.bwd == "layer" and all(MLPTrainer.bwd_fusable(co, ci) for ci, co in zip(w[1:-2], w[2:-1]))
                     for (w, _), n in zip((critic, actor), nets))
-    one_tail = fused_opt and one_launch_tail and defer and finishing and all(all(n.grouped[:-1]) for n in nets) and sum(fins) + 2 <= 8
+    # ... and at most TAIL_MAX_ITEMS blocks of sums in that launch (bg_tail.hip): the weight gradients' finish (64 elements per block: 4,096 for a
+    # 512 x 512 layer) and the deferred reductions (the heads' gradients and statistics, the per-layer bias gradients: 16 per block).  Beyond it
+    # (two 512 x 512 layers) the sums run as their own launches in front of bg_optimizer_step.
+    sums = sum((co * ci // 4 + 15) // 16 for co, ci in grouped) + sum((w[-2] * w[-1] + w[-2] + w[-1] + 15) // 16 + 32 + sum((ci + 15) // 16 for ci in w[1:-2])
+                                                                       for w, _ in (critic, actor))
+    one_tail = (fused_opt and one_launch_tail and defer and finishing and all(all(n.grouped[:-1]) for n in nets) and sum(fins) + 2 <= 8
+                and sums <= TAIL_MAX_ITEMS)
     return UpdatePlan(nets[0], nets[1], wgrad, fused_head, fused_gae, chain_values, one_stream and chain_values and defer and bwd_chained, defer, fused_opt,
                       one_tail, rollout_forward and chain_values and nets[1].chained, dp_active)
 
@@ -213,6 +230,7 @@ class Runner:
             self.cfg = cfg
             self.cfg["basic"].setdefault("task", "T1")
         self.cfg["basic"]["rank"] = self.rank
+        self.actor_hidden, self.critic_hidden = hidden_widths(self.cfg)  # (before anything is built: a width outside the supported set is a ValueError)
         if self.world_size > 1:  # one process per GPU: each rank simulates and learns on its own device
             self.cfg["basic"]["sim_device"] = self.cfg["basic"]["rl_device"] = f"cuda:{self.dp.device_index}"
         self._set_seed()
@@ -225,7 +243,7 @@ class Runner:
         if torch.device(self.device) != torch.device(self.env.device):
             raise ValueError("rl_device must equal sim_device: the rollout writes simulator outputs straight into the PPO buffers")
         self.learning_rate = self.cfg["algorithm"]["learning_rate"]
-        self.model = ActorCritic(self.env.num_actions, self.env.num_obs, self.env.num_privileged_obs).to(self.device)
+        self.model = ActorCritic(self.env.num_actions, self.env.num_obs, self.env.num_privileged_obs, self.actor_hidden, self.critic_hidden).to(self.device)
         self.dp.broadcast_parameters(self.model)  # identical initial weights on every rank
         self.invalidate()
         self.optimizer = FlatAdam(self.model.parameters(), lr=self.learning_rate)
@@ -365,6 +383,11 @@ class Runner:
             self.cfg["basic"]["checkpoint"] = ck
         print("Loading model from {}".format(ck))
         model_dict = torch.load(ck, map_location=self.device, weights_only=True)
+        ck_a, ck_c = hidden_of(model_dict["model"], "actor"), hidden_of(model_dict["model"], "critic")
+        if (ck_a, ck_c) != (self.actor_hidden, self.critic_hidden):
+            raise ValueError(f"checkpoint {ck} has actor hidden widths {list(ck_a)} and critic hidden widths {list(ck_c)}, the config "
+                             f"algorithm.actor_hidden = {list(self.actor_hidden)} and algorithm.critic_hidden = {list(self.critic_hidden)}: set these to the "
+                             "checkpoint's widths")
         self.model.load_state_dict(model_dict["model"], strict=False)
         self.invalidate()
         try:

@@ -1,5 +1,6 @@
 """python export_model.py --task=T1 [--checkpoint path|-1]: TorchScript export of the actor (reference export_model.py:8-30) so that
-the reference's deployment code (deploy/utils/policy.py:9) can load what this framework trains."""
+the reference's deployment code (deploy/utils/policy.py:9) can load what this framework trains.  The actor's widths are read from the checkpoint's tensors (any supported architecture exports without editing
+the YAML); the TorchScript module is still a plain Sequential."""
 import argparse
 import glob
 import os
@@ -7,7 +8,7 @@ import os
 import torch
 
 from booster_gym_amd.utils.config import load_cfg
-from booster_gym_amd.utils.model import ActorCritic
+from booster_gym_amd.utils.model import ActorCritic, hidden_of
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
@@ -19,8 +20,10 @@ if __name__ == "__main__":
     if ck in ("-1", None):
         ck = sorted(glob.glob(os.path.join("logs", "**/*.pth"), recursive=True), key=os.path.getmtime)[-1]
     print("Loading model from {}".format(ck))
-    model = ActorCritic(cfg["env"]["num_actions"], cfg["env"]["num_observations"], cfg["env"]["num_privileged_obs"])
-    model.load_state_dict(torch.load(ck, map_location="cpu", weights_only=True)["model"])
+    sd = torch.load(ck, map_location="cpu", weights_only=True)["model"]
+    model = ActorCritic(cfg["env"]["num_actions"], cfg["env"]["num_observations"], cfg["env"]["num_privileged_obs"], actor_hidden=hidden_of(sd, "actor"),
+                        critic_hidden=hidden_of(sd, "critic"))
+    model.load_state_dict(sd)
     os.makedirs("deploy/models", exist_ok=True)
     out = os.path.join("deploy", "models", f"{args.task}.pt")
     torch.jit.script(model.actor).save(out)

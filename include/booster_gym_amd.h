@@ -259,6 +259,18 @@ int bg_gaussian_logp(int32_t B, int32_t A, const float* mu, const float* logstd,
 int bg_actor_sample(int32_t N, const float* obs, const float* w0, const float* b0, const float* w1, const float* b1, const float* w2,
                     const float* b2, const float* w3, const float* b3, const float* logstd, uint64_t seed, uint64_t counter,
                     float* mu, float* actions, void* stream);
+/* One Linear layer of an MLP for bg_actor_sample_mlp: W [out][in] row-major (torch layout), b [out]. */
+typedef struct bg_mlp_layer_desc {
+    const float* W;
+    const float* b;
+    int32_t in, out;
+} bg_mlp_layer_desc;
+/* bg_actor_sample at any supported actor architecture (utils/model.py:8-25 with configured widths + dist.sample(), runner.py:109-111), one
+ * launch: layers [n_layers] = 2 to 4 hidden ELU layers (47 inputs; widths multiples of 128 up to 512) and the 12-wide output layer; weight
+ * matrices after the first 16-byte aligned.  Same noise as bg_actor_sample: Philox(seed, row, counter, RS_ACTOR + group of 4 actions).
+ * mu [N][12] may be NULL. */
+int bg_actor_sample_mlp(int32_t N, const float* obs, int32_t n_layers, const bg_mlp_layer_desc* layers, const float* logstd, uint64_t seed,
+                        uint64_t counter, float* mu, float* actions, void* stream);
 /* Fused global-norm clip + Adam over one flat parameter buffer (runner.py:162-165); lr is read from device memory
  * so the KL-adaptive schedule (runner.py:174-180) needs no host sync.  gnorm_scratch [1] device float64. */
 int bg_adam_step(int32_t n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const float* lr_device, int32_t step,
