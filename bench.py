@@ -1,11 +1,17 @@
 """Headline benchmark: env-steps/sec of the full PPO training loop (rollout + update), T1, 4096 envs per GPU.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one PPO iteration on synthetic (randomly initialised) policy weights: 24 env-steps x 4096 envs per GPU through the
 HIP simulator + 20 full-batch optimiser steps (BASELINE.json configs[1], flat terrain).  Rank 0 prints
 ONE JSON line.  `value` = world * N * T * K / wall (max over ranks).
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: the figures it carries besides `value` come
+from HIP events inside the timed steps and from the committed profiles.  `--full` adds what takes runs of its own after the timed
+steps: the stand-alone kernel timings (`roofline.alone_on_the_gpu`) and, on one GPU, the A/B loops (`fp32_mfma_loop` and its
+neighbours, `opt_in_split_bf16_layers`), `gemm_errors_vs_float64`, `other_configs`, `roofline_aba` and `cpu_baseline`; with --full,
+--no-extra drops all but the last and --no-cpu-baseline the last.
 
 `roofline` = both networks' chained forward pass, one launch (bg_mlp_chain_split.hip: fp32 operands as exact three-way bf16 splits, all 9 products on the
 bf16 matrix pipe, fp32 accumulation), priced against the 9-product equivalent of the bf16 pipe's peak AND against the fp32 matrix pipe's;
@@ -360,9 +366,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--num_envs", type=int, default=4096)
     ap.add_argument("--terrain", type=str, default="plane")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the measurements after the timed region (kernel alone on the GPU, ABA roofline): "
-                    "used under rocprofv3 so that the per-kernel averages of the summary are those of the timed region")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run the measurements that take runs of their own: stand-alone "
+                    "kernels and, on one GPU, A/B loops, GEMM errors, other configurations, ABA roofline, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the GPU measurements after the timed region (everything --full "
+                    "adds but the CPU baseline)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (rank 0: policy parameters, logged "
                     "scalars, experience streams) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     args = ap.parse_args()
@@ -558,7 +566,7 @@ def main():
                      "frac_of_fp32_mfma_peak": fl_c / (c_loop_us * 1e-6) / 1e12 / MFMA_F32_PEAK_TF,
                      "traffic": tr_c[0], "traffic_source": PMC_SOURCE, "avg_launch_us": c_loop_us, "algorithmic_flops_per_launch": fl_c,
                      "note": "timed inside the loop, where the actor's launch runs beside it on the second stream"}
-        if not args.no_extra:
+        if args.full and not args.no_extra:
             # the same launches with nothing beside them (hidden layers only: the critic's value head is left out of the stand-alone launch)
             from booster_gym_amd.utils.model import MLPTrainer as _MLPT
             alone = {}
@@ -670,7 +678,7 @@ def main():
             out["multi_rank"] = {"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"), "own_rccl": runner.dp.comm is not None,
                                  "backend": runner.dp.backend, "exchange_ms_per_mini_epoch": ex_ms or None, "phase_ms_slowest_rank": slow_phase,
                                  "note": "exchange times are rank 0's (collective + waiting for the slowest rank); phase_ms_slowest_rank: the largest rollout / update time over the ranks"}
-        if world == 1 and not args.no_extra:
+        if world == 1 and args.full and not args.no_extra:
             try:
                 # The same loop, same run, same timing with BOTH chains on the fp32 matrix pipe (last round's headline path: bg_mlp_chain.hip forward,
                 # bg_mlp_layer_backward per layer): what a reader who does not accept the 9-product arithmetic as fp32 falls back on.  NOT part of `value`.
@@ -778,7 +786,7 @@ def main():
                 out["roofline_aba"] = aba_roofline()
             except Exception as ex:
                 out["roofline_aba"] = {"error": repr(ex)}
-        if not args.no_cpu_baseline and world == 1:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 log("cpu baseline ...")
                 out["cpu_baseline"] = cpu_baseline(N)

@@ -45,3 +45,20 @@ def test_bench_gpus_2_prints_one_line():
     assert out["n_gpus"] == 2 and out["config"]["parallelism"] == "dp2" and out["scaling"] == "weak"
     assert out["value"] > 0 and abs(out["value"] - 2 * 256 * 24 * 2 / (out["ms_per_step"] * 2e-3)) < 1e-6 * out["value"]
     assert out["phase_ms"]["all_reduce_ms"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_leaves_the_extras_to_full():
+    """A plain one-GPU run prints the headline and nothing that takes runs of its own: those belong to `--full`."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--num_envs", "256"],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["unit"] == "env-steps/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["value"] > 0 and abs(out["value"] - 256 * 24 * 2 / (out["ms_per_step"] * 2e-3)) < 1e-6 * out["value"]
+    assert "alone_on_the_gpu" not in out["roofline"]
+    full_only = {"fp32_mfma_loop", "split_forward_only_loop", "fp32_mfma_weight_gradients_loop", "two_launches_on_two_streams_loop", "headline_loop_again",
+                 "gemm_errors_vs_float64", "opt_in_split_bf16_layers", "other_configs", "roofline_aba", "cpu_baseline"}
+    assert not full_only & set(out), sorted(full_only & set(out))
