@@ -132,6 +132,7 @@ SYMBOLS = [
     "bg_sim_refresh_body_state", "bg_sim_write_root_state", "bg_sim_write_dof_state", "bg_gae", "bg_ppo_loss", "bg_gaussian_logp", "bg_actor_sample", "bg_actor_sample_mlp", "bg_adam_step", "bg_adapt_lr", "bg_optimizer_step", "bg_elu_backward_colsum", "bg_mlp_layer_forward", "bg_mlp_chain_forward", "bg_critic_values_gae", "bg_mlp_chain_forward_group", "bg_mlp_chain_forward_split", "bg_mlp_chain_backward_split", "bg_mlp_split_weights_pm", "bg_mlp_layer_backward", "bg_mlp_split_weights", "bg_mlp_layer_forward_split", "bg_mlp_layer_backward_split", "bg_mlp_weight_grad", "bg_mlp_weight_grad_group", "bg_mlp_weight_grad_group_partial", "bg_update_tail", "bg_update_tail_sums", "bg_mlp_weight_grad_group_split", "bg_mlp_weight_grad_group_split_partial",
     "bg_critic_head_forward", "bg_actor_head", "bg_critic_head_backward",
     "bg_reduce_group", "bg_actor_head_partial", "bg_critic_head_backward_partial", "bg_mlp_layer_backward_partial",
+    "bg_actor_head_sym", "bg_actor_head_sym_partial", "bg_mirror_rows",
     "bg_last_error", "bg_version",
 ]
 
@@ -219,6 +220,9 @@ def load():
         "bg_actor_head_partial": (i32, [i32] + [vp] * 10 + [f32, f32, f32] + [vp] * 8 + [C.POINTER(ReduceProblem), vp]),
         "bg_critic_head_backward_partial": (i32, [i32] + [vp] * 10 + [C.POINTER(ReduceProblem), vp]),
         "bg_mlp_layer_backward_partial": (i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(ReduceProblem), vp]),
+        "bg_actor_head_sym": (i32, [i32] + [vp] * 10 + [f32] * 4 + [vp] * 11),
+        "bg_actor_head_sym_partial": (i32, [i32] + [vp] * 10 + [f32] * 4 + [vp] * 10 + [C.POINTER(ReduceProblem), vp]),
+        "bg_mirror_rows": (i32, [i32, i32, vp, vp, vp, vp, vp]),
         "bg_last_error": (C.c_char_p, []),
         "bg_version": (C.c_char_p, []),
     }

@@ -8,6 +8,8 @@
 //                           hidden layer, log-std gradient and the loss statistics
 //   bg_critic_head_forward  values = h w + b for every row (the GAE scan between forward and backward needs all of them first)
 //   bg_critic_head_backward value loss (runner.py:148) backward through the output layer into the last hidden layer
+//   bg_actor_head_sym       bg_actor_head on a batch of 2B rows (the rollout's, then their mirror images) plus the mirror-symmetry loss
+//                           (algorithm.symmetry_loss); bg_mirror_rows writes the mirrored network inputs
 // Arithmetic is plain fp32 FMA on the vector ALU: 4.6 kflop per row against 1 KB of traffic is under the HBM ridge, so nothing here is
 // reshaped into an MFMA GEMM.  Reductions over rows are deterministic: every workgroup writes its partial sums, a second kernel adds them
 // in a fixed order (the loss statistics and the log-std gradient keep the float64 atomics of bg_ppo_loss).
@@ -538,6 +540,196 @@ __global__ __launch_bounds__(256) void critic_values_gae_kernel(int T, int N, co
     }
 }
 
+// ---- mirror-symmetry loss (bg_actor_head_sym): the actor's batch is 2B rows, rows [B, 2B) the mirror images of rows [0, B).  A tile holds HTS
+// original rows in LDS rows [0, HTS) and their mirror images in LDS rows [HTS, 2 HTS), so that the pair's means meet in LDS.  Per pair, with
+// d = mu(M_o x) - M_a mu(x) and c = sym_scale = 2 coef / (B A):  dL/dmu of the mirrored row += c d,  of the original row += -c M_a d  (M_a a
+// symmetric involution: (M_a d)[a] = sign[a] d[src[a]]), on top of the PPO, bound and entropy terms of the original row; statistic A + 5 = sum d^2.
+constexpr int HTS = HT / 2;
+constexpr int HEAD_NSTAT_SYM = HEAD_NSTAT + 1;
+struct ActionMirror { int src[HA]; float sign[HA]; };
+
+__global__ __launch_bounds__(256) void actor_head_sym_kernel(int B, int tiles, const float* __restrict__ h, const float* __restrict__ W,
+                                                             const float* __restrict__ bias, const float* __restrict__ logstd,
+                                                             const float* __restrict__ actions, const float* __restrict__ old_mu,
+                                                             const float* __restrict__ old_logstd, const float* __restrict__ old_logp,
+                                                             const float* __restrict__ adv, const double* __restrict__ adv_stats, float e_clip,
+                                                             float bound_coef, float sym_scale, ActionMirror am, float* __restrict__ mu_out,
+                                                             float* __restrict__ g_hidden, float* __restrict__ partial) {
+    constexpr int A = HA;
+    __shared__ __attribute__((aligned(16))) float s_h[HT * HLD];
+    __shared__ __attribute__((aligned(16))) float s_w[A * HLD];
+    __shared__ __attribute__((aligned(16))) float s_g[HT * A];
+    __shared__ float s_mu[HT * A];
+    __shared__ int s_src[A];
+    __shared__ float s_sign[A];
+    const int t = threadIdx.x;
+    for (int i = t; i < A * HK; i += 256) s_w[(i >> 7) * HLD + (i & (HK - 1))] = W[i];
+    if (t < A) { s_src[t] = am.src[t]; s_sign[t] = am.sign[t]; }
+    const int fr = t >> 2, fq = t & 3, pr = fr & (HTS - 1);
+    const bool mirror = fr >= HTS;
+    float fb[3];
+    for (int i = 0; i < 3; i++) fb[i] = bias[3 * fq + i];
+    const int kc = t & (HK - 1), half = t >> 7;  // backward: half 0 = the original rows, half 1 = their mirror images
+    float wcol[A], dW[A], cs = 0.f;
+    for (int j = 0; j < A; j++) { wcol[j] = W[j * HK + kc]; dW[j] = 0.f; }
+    float ls[3], ols[3], isig2[3], osig2[3], dbias[3] = {0.f, 0.f, 0.f};
+    double acc_ls[3] = {0.0, 0.0, 0.0}, acc_st[4] = {0.0, 0.0, 0.0, 0.0}, acc_sym = 0.0;
+    bg::ActorLossConsts<A> c;
+    bg::actor_loss_consts<A>(c, B, logstd, old_logstd, adv_stats, e_clip, bound_coef);
+    for (int i = 0; i < 3; i++) { ls[i] = logstd[3 * fq + i]; ols[i] = old_logstd[3 * fq + i]; }
+    for (int i = 0; i < 3; i++) { const float sg = expf(ls[i]), os = expf(ols[i]); isig2[i] = 1.0f / (sg * sg); osig2[i] = os * os; }
+    const float ent = c.ent, mean = c.mean, inv_std = c.inv_std, invB = c.invB, bscale = c.bscale;
+    __syncthreads();
+    int src[3];
+    float sgn[3];
+    for (int i = 0; i < 3; i++) { src[i] = s_src[3 * fq + i]; sgn[i] = s_sign[3 * fq + i]; }
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int row0 = tile * HTS;
+#pragma unroll
+        for (int i = 0; i < HTV; i++) {
+            const int idx = t + 256 * i, r = idx >> 5, c4 = idx & 31, o = row0 + (r & (HTS - 1));
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (o < B) v = *reinterpret_cast<const float4*>(h + (size_t)(r < HTS ? o : B + o) * HK + c4 * 4);
+            *reinterpret_cast<float4*>(s_h + r * HLD + c4 * 4) = v;
+        }
+        __syncthreads();
+        const int b = row0 + pr;
+        const bool live = b < B;
+        float m[3];
+        {   // mu = h W^T + b (bg_actor_head's arithmetic)
+            float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+            const float4* hr = reinterpret_cast<const float4*>(s_h + fr * HLD);
+            const float4* w0 = reinterpret_cast<const float4*>(s_w + (3 * fq) * HLD);
+            const float4* w1 = reinterpret_cast<const float4*>(s_w + (3 * fq + 1) * HLD);
+            const float4* w2 = reinterpret_cast<const float4*>(s_w + (3 * fq + 2) * HLD);
+#pragma unroll 2
+            for (int k4 = 0; k4 < HK / 4; k4++) {
+                const float4 x = hr[k4], u = w0[k4], v = w1[k4], w = w2[k4];
+                a0 = fmaf(x.x, u.x, a0); a0 = fmaf(x.y, u.y, a0); a0 = fmaf(x.z, u.z, a0); a0 = fmaf(x.w, u.w, a0);
+                a1 = fmaf(x.x, v.x, a1); a1 = fmaf(x.y, v.y, a1); a1 = fmaf(x.z, v.z, a1); a1 = fmaf(x.w, v.w, a1);
+                a2 = fmaf(x.x, w.x, a2); a2 = fmaf(x.y, w.y, a2); a2 = fmaf(x.z, w.z, a2); a2 = fmaf(x.w, w.w, a2);
+            }
+            m[0] = a0 + fb[0]; m[1] = a1 + fb[1]; m[2] = a2 + fb[2];
+        }
+        for (int i = 0; i < 3; i++) s_mu[fr * A + 3 * fq + i] = m[i];
+        if (mu_out && live) for (int i = 0; i < 3; i++) mu_out[(size_t)(mirror ? B + b : b) * A + 3 * fq + i] = m[i];
+        __syncthreads();
+        float gm[3] = {0.f, 0.f, 0.f};
+        {   // symmetry term of the pair (pr, HTS + pr)
+            const float* mo = s_mu + pr * A;
+            const float* mm = s_mu + (HTS + pr) * A;
+            for (int i = 0; i < 3; i++) {
+                const int a = 3 * fq + i;
+                if (mirror) {
+                    const float d = mm[a] - sgn[i] * mo[src[i]];
+                    if (live) { gm[i] = sym_scale * d; acc_sym += (double)(d * d); }
+                } else {
+                    const float d = mm[src[i]] - sgn[i] * mo[a];  // d[src[a]] (sign[src[a]] = sign[a])
+                    if (live) gm[i] = -sym_scale * sgn[i] * d;
+                }
+            }
+        }
+        if (!mirror) {  // PPO actor loss of the original row (bg_actor_head MODE 1)
+            const size_t o = (size_t)(live ? b : B - 1) * A + 3 * fq;
+            float d[3], hl[3], lp = 0.f, kl = 0.f, bound = 0.f;
+            for (int i = 0; i < 3; i++) {
+                d[i] = actions[o + i] - m[i];
+                lp += -0.5f * d[i] * d[i] * isig2[i] - ls[i] - bg::kHalfLog2Pi;
+                const float dm = m[i] - old_mu[o + i];
+                kl += ls[i] - ols[i] + 0.5f * (osig2[i] + dm * dm) * isig2[i] - 0.5f;
+                const float hi = fmaxf(m[i] - 1.0f, 0.f), lo = fminf(m[i] + 1.0f, 0.f);
+                bound += hi * hi + lo * lo;
+                hl[i] = hi + lo;
+            }
+            // (a wave holds 16 rows, all of them original or all mirrored: `mirror` is uniform per wave, and the DPP moves run in whole waves)
+            lp = quad_sum(lp); kl = quad_sum(kl); bound = quad_sum(bound);
+            const float An = (adv[live ? b : B - 1] - mean) * inv_std;
+            const float ratio = expf(lp - old_logp[live ? b : B - 1]);
+            const float rc = fminf(fmaxf(ratio, 1.0f - e_clip), 1.0f + e_clip);
+            const float s1 = -An * ratio, s2 = -An * rc;
+            const bool inside = ratio >= 1.0f - e_clip && ratio <= 1.0f + e_clip;
+            const float dlogp = (live && (inside || s1 > s2)) ? -An * ratio * invB : 0.f;
+            for (int i = 0; i < 3; i++) {
+                if (live) gm[i] += dlogp * d[i] * isig2[i] + bscale * hl[i];
+                acc_ls[i] += (double)(dlogp * (d[i] * d[i] * isig2[i] - 1.0f));
+            }
+            if (live && fq == 0) {
+                acc_st[0] += (double)fmaxf(s1, s2); acc_st[1] += (double)bound; acc_st[2] += (double)ent; acc_st[3] += (double)kl;
+            }
+        }
+        for (int i = 0; i < 3; i++) { s_g[fr * A + 3 * fq + i] = gm[i]; dbias[i] += gm[i]; }
+        __syncthreads();
+        // g_hidden = (dL/dmu W) * elu'(h), dW += dL/dmu^T h, hidden bias gradient = column sums of g_hidden: over all 2B rows
+        for (int rr = 0; rr < HTS; rr++) {
+            const int r = half * HTS + rr;
+            const float hv = s_h[r * HLD + kc];
+            const float4* gp = reinterpret_cast<const float4*>(s_g + r * A);
+            const float4 g0 = gp[0], g1 = gp[1], g2 = gp[2];
+            const float g[A] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w, g2.x, g2.y, g2.z, g2.w};
+            float sa = 0.f, sb = 0.f;
+#pragma unroll
+            for (int j = 0; j < A; j += 2) {
+                sa = fmaf(g[j], wcol[j], sa); sb = fmaf(g[j + 1], wcol[j + 1], sb);
+                dW[j] = fmaf(g[j], hv, dW[j]); dW[j + 1] = fmaf(g[j + 1], hv, dW[j + 1]);
+            }
+            const float gz = (sa + sb) * elu_grad_from_output(hv);
+            cs += gz;
+            if (row0 + rr < B) g_hidden[(size_t)(half ? B + row0 + rr : row0 + rr) * HK + kc] = gz;
+        }
+        __syncthreads();
+    }
+    // ---- this workgroup's partial sums (bg_actor_head's record layout; one float64 statistic more)
+    float* red = s_h;  // [2][A + 1][HK]
+    for (int j = 0; j < A; j++) red[(half * (A + 1) + j) * HK + kc] = dW[j];
+    red[(half * (A + 1) + A) * HK + kc] = cs;
+    __syncthreads();
+    float* rec = partial + (size_t)blockIdx.x * head_record<A>();
+    for (int i = t; i < (A + 1) * HK; i += 256) rec[i] = red[i] + red[(A + 1) * HK + i];
+    const int wave = t >> 6, lane = t & 63;
+    constexpr int SL = 20;  // slots per wave: 0..11 per action, 12..15 loss terms, 16 symmetry
+    __syncthreads();
+    float* redf = s_h;                                    // [4 waves][16]
+    double* redd = reinterpret_cast<double*>(s_h + 64);  // [4 waves][SL]
+    for (int i = 0; i < 3; i++) {
+        const float v = quadcol_sum(dbias[i]);
+        const double w = quadcol_sum(acc_ls[i]);
+        if (lane < 4) { redf[wave * 16 + 3 * lane + i] = v; redd[wave * SL + 3 * lane + i] = w; }
+    }
+    for (int i = 0; i < 4; i++) {
+        const double w = quadcol_sum(acc_st[i]);
+        if (lane == 0) redd[wave * SL + 12 + i] = w;
+    }
+    {
+        const double w = wave_sum_d(acc_sym);
+        if (lane == 0) redd[wave * SL + 16] = w;
+    }
+    __syncthreads();
+    if (t < 17) {
+        double* srec = reinterpret_cast<double*>(partial + head_stat_base<A>());
+        const double w = redd[t] + redd[SL + t] + redd[2 * SL + t] + redd[3 * SL + t];
+        // statistic index: [0, A) dL/dlogstd, A unused (the critic head's), A+1.. = surrogate, bound, entropy, kl, symmetry
+        const int k = t < A ? t : t + 1;
+        srec[(size_t)k * gridDim.x + blockIdx.x] = w;
+        if (t < A) rec[(A + 1) * HK + t] = redf[t] + redf[16 + t] + redf[32 + t] + redf[48 + t];
+    }
+}
+
+// y[r][c] = sign[c] x[r][src[c]] (src[c] < 0: 0) for rows x cols elements: exact, only signs change
+struct ColumnMirror { int src[64]; float sign[64]; };
+__global__ __launch_bounds__(256) void mirror_rows_kernel(int rows, int cols, ColumnMirror cm, const float* __restrict__ x, float* __restrict__ y) {
+    __shared__ int s_src[64];
+    __shared__ float s_sign[64];
+    if ((int)threadIdx.x < 64) { s_src[threadIdx.x] = cm.src[threadIdx.x]; s_sign[threadIdx.x] = cm.sign[threadIdx.x]; }
+    __syncthreads();
+    const size_t n = (size_t)rows * cols;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const size_t r = i / cols;
+        const int col = (int)(i - r * cols), s = s_src[col];
+        const float v = s < 0 ? 0.f : x[r * cols + s];
+        y[i] = s_sign[col] < 0.f ? -v : v;
+    }
+}
+
 int head_grid(int tiles) { return tiles < HEAD_MAX_GRID ? tiles : HEAD_MAX_GRID; }
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
@@ -643,6 +835,86 @@ extern "C" int bg_critic_head_backward(int32_t B, const float* h, const float* w
     constexpr int n_out = HK + HK + 1;
     hipLaunchKernelGGL(head_finish_kernel, dim3((n_out + 15) / 16 + 1), dim3(256), 0, st, grid, head_record<1>(), n_out, scratch, grad_w, HK, grad_b_hidden,
                        grad_b, head_stat_base<1>(), 1, 0, 0u, 0.0, (double*)nullptr, stats);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ---- mirror-symmetry loss
+static int action_mirror(ActionMirror* am, const int32_t* act_src, const float* act_sign) {
+    if (!act_src || !act_sign) return -1;
+    for (int a = 0; a < HA; a++) {
+        const int s = act_src[a];
+        // a symmetric signed-permutation involution: src[src[a]] = a, sign[src[a]] = sign[a], sign +-1
+        if (s < 0 || s >= HA || act_src[s] != a || !(act_sign[a] == 1.f || act_sign[a] == -1.f) || act_sign[s] != act_sign[a]) return -1;
+        am->src[a] = s; am->sign[a] = act_sign[a];
+    }
+    return 0;
+}
+static int actor_head_sym_launch(int32_t B, const float* h, const float* W, const float* bias, const float* logstd, const float* actions,
+                                 const float* old_mu, const float* old_logstd, const float* old_logp, const float* adv, const double* adv_stats, float e_clip,
+                                 float bound_coef, float sym_coef, const int32_t* act_src, const float* act_sign, float* mu_out, float* g_hidden, float* scratch,
+                                 int* grid_out, hipStream_t st) {
+    ActionMirror am;
+    if (action_mirror(&am, act_src, act_sign)) return bg_set_error(-1, "bg_actor_head_sym: act_src / act_sign must be a symmetric signed permutation of the 12 actions that is its own inverse");
+    if (!aligned16(h)) return bg_set_error(-1, "bg_actor_head_sym: h must be 16-byte aligned");
+    const int tiles = (B + HTS - 1) / HTS, grid = head_grid(tiles);
+    const float sym_scale = (float)(2.0 * (double)sym_coef / ((double)B * HA));
+    hipLaunchKernelGGL(actor_head_sym_kernel, dim3(grid), dim3(256), 0, st, B, tiles, h, W, bias, logstd, actions, old_mu, old_logstd, old_logp, adv, adv_stats,
+                       e_clip, bound_coef, sym_scale, am, mu_out, g_hidden, scratch);
+    *grid_out = grid;
+    return 0;
+}
+
+extern "C" int bg_actor_head_sym(int32_t B, const float* h, const float* W, const float* bias, const float* logstd, const float* actions, const float* old_mu,
+                                 const float* old_logstd, const float* old_logp, const float* adv, const double* adv_stats, float e_clip, float bound_coef,
+                                 float entropy_coef, float sym_coef, const int32_t* act_src, const float* act_sign, float* mu_out, float* g_hidden, float* grad_W,
+                                 float* grad_b, float* grad_b_hidden, double* grad_logstd, double* stats, float* scratch, void* stream) {
+    if (B <= 0 || !h || !W || !bias || !logstd || !actions || !old_mu || !old_logstd || !old_logp || !adv || !adv_stats || !g_hidden || !grad_W || !grad_b ||
+        !grad_b_hidden || !grad_logstd || !stats || !scratch)
+        return bg_set_error(-1, "bg_actor_head_sym: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    int grid = 0;
+    const int rc = actor_head_sym_launch(B, h, W, bias, logstd, actions, old_mu, old_logstd, old_logp, adv, adv_stats, e_clip, bound_coef,
+                                         sym_coef, act_src, act_sign, mu_out, g_hidden, scratch, &grid, st);
+    if (rc) return rc;
+    constexpr int n_out = HA * HK + HK + HA;
+    hipLaunchKernelGGL(head_finish_kernel, dim3((n_out + 15) / 16 + HEAD_NSTAT_SYM), dim3(256), 0, st, grid, head_record<HA>(), n_out, scratch, grad_W, HA * HK,
+                       grad_b_hidden, grad_b, head_stat_base<HA>(), HEAD_NSTAT_SYM, HA, 1u << HA, (double)entropy_coef, grad_logstd, stats);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int bg_actor_head_sym_partial(int32_t B, const float* h, const float* W, const float* bias, const float* logstd, const float* actions,
+                                         const float* old_mu, const float* old_logstd, const float* old_logp, const float* adv, const double* adv_stats,
+                                         float e_clip, float bound_coef, float entropy_coef, float sym_coef, const int32_t* act_src, const float* act_sign,
+                                         float* mu_out, float* g_hidden, float* grad_W, float* grad_b, float* grad_b_hidden, double* grad_logstd, double* stats,
+                                         float* scratch, bg_reduce_problem* finish, void* stream) {
+    if (B <= 0 || !h || !W || !bias || !logstd || !actions || !old_mu || !old_logstd || !old_logp || !adv || !adv_stats || !g_hidden || !grad_W || !grad_b ||
+        !grad_b_hidden || !grad_logstd || !stats || !scratch || !finish)
+        return bg_set_error(-1, "bg_actor_head_sym_partial: bad argument");
+    int grid = 0;
+    const int rc = actor_head_sym_launch(B, h, W, bias, logstd, actions, old_mu, old_logstd, old_logp, adv, adv_stats, e_clip,
+                                         bound_coef, sym_coef, act_src, act_sign, mu_out, g_hidden, scratch, &grid, (hipStream_t)stream);
+    if (rc) return rc;
+    HIP_OK(hipGetLastError());
+    head_finish_desc(finish, scratch, grid, head_record<HA>(), grad_W, HA * HK, grad_b_hidden, grad_b, HA, head_stat_base<HA>(), HEAD_NSTAT_SYM, HA, 1u << HA,
+                     (double)entropy_coef, grad_logstd, stats);
+    return 0;
+}
+
+extern "C" int bg_mirror_rows(int32_t rows, int32_t cols, const int32_t* src, const float* sign, const float* x, float* y, void* stream) {
+    if (rows <= 0 || cols <= 0 || cols > 64 || !src || !sign || !x || !y) return bg_set_error(-1, "bg_mirror_rows: bad argument (1 to 64 columns)");
+    ColumnMirror cm;
+    for (int c = 0; c < 64; c++) { cm.src[c] = -1; cm.sign[c] = 1.f; }
+    for (int c = 0; c < cols; c++) {
+        if (src[c] < -1 || src[c] >= cols || !(sign[c] == 1.f || sign[c] == -1.f)) return bg_set_error(-1, "bg_mirror_rows: src in [-1, cols), sign +-1");
+        cm.src[c] = src[c]; cm.sign[c] = sign[c];
+    }
+    const float *xe = x + (size_t)rows * cols, *ye = y + (size_t)rows * cols;
+    if (x < ye && y < xe) return bg_set_error(-1, "bg_mirror_rows: x and y overlap");
+    size_t blocks = ((size_t)rows * cols + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(mirror_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rows, cols, cm, x, y);
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -21,6 +21,7 @@ from .. import _lib
 from ..utils.urdf import load_model
 from ..utils.utils import rand_spec
 from .base_task import BaseTask
+from .mirror import mirror_maps
 
 
 def _draw(rng, shape, params):
@@ -388,6 +389,12 @@ class T1(BaseTask):
         return self._actions_scratch
 
     # ------------------------------------------------------------------ state access (what the reference exposes as tensor attributes)
+    def mirror_maps(self):
+        """(obs_src, obs_sign, act_src, act_sign): the left-right mirror maps of the observations and actions (envs/mirror.py), from the model's joint
+        names and axes; ValueError if the model has no left / right pairing or its default pose is not mirror-invariant."""
+        axes = [int(a) for a in self.model.joint_axis if int(a) != 0]  # (bodies depth-first: body j + 1 is moved by DoF j)
+        return mirror_maps(self.dof_names, axes, self.default_dof_pos[0].cpu().numpy(), self.num_obs)
+
     def get_field(self, name):
         comps, is_int = C.c_int32(), C.c_int32()
         _lib.check(self._lib.bg_env_field_info(self._env, name.encode(), C.byref(comps), C.byref(is_int)), "bg_env_field_info")

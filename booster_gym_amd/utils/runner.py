@@ -49,8 +49,8 @@ from .config import load_cfg
 from .model import ACTOR_HIDDEN, CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, MLPTrainer, NetPlan, check_hidden, hidden_of, plan_network
 from .parallel import DataParallel
 from .recorder import Recorder
-from .utils import (actor_head_forward, actor_head_loss_backward, critic_head_backward, critic_head_forward, critic_values_gae, gae, gaussian_logp, head_scratch, reduce_group,
-                    ppo_loss_fused)
+from .utils import (actor_head_forward, actor_head_loss_backward, actor_head_sym_loss_backward, critic_head_backward, critic_head_forward, critic_values_gae, gae,
+                    gaussian_logp, head_scratch, mirror_rows, reduce_group, ppo_loss_fused)
 
 
 def plan_chain_split(slabs_c, slabs_a, cost_c, cost_a, cus, xcds=8):
@@ -75,6 +75,23 @@ def hidden_widths(cfg):
     return check_hidden(alg.get("actor_hidden", ACTOR_HIDDEN), alg.get("critic_hidden", CRITIC_HIDDEN), split)
 
 
+def symmetry_loss(cfg):
+    """(on, coefficient) of the mirror-symmetry loss: algorithm.symmetry_loss (an addition of this build; absent = false) and the reference's
+    algorithm.symmetric_coef, which the loss reads only when it is on."""
+    alg = cfg.get("algorithm", {}) or {}
+    on = alg.get("symmetry_loss", False)
+    if on is None:
+        on = False
+    if not isinstance(on, bool):
+        raise ValueError(f"algorithm.symmetry_loss must be true or false, got {on!r}")
+    if not on:
+        return False, 0.0
+    coef = alg.get("symmetric_coef", 0.0)
+    if isinstance(coef, bool) or not isinstance(coef, (int, float)) or not np.isfinite(coef) or coef < 0:
+        raise ValueError(f"algorithm.symmetric_coef must be a finite number >= 0 when algorithm.symmetry_loss is on, got {coef!r}")
+    return True, float(coef)
+
+
 class UpdatePlan(NamedTuple):
     """The kernels of one Runner.update() and of the rollout's forward-ahead (plan_update): resolved once per call, read by every branch."""
     critic: NetPlan
@@ -89,16 +106,24 @@ class UpdatePlan(NamedTuple):
     one_tail: bool      # ... together with the deferred sums and the weight gradients' finish (bg_update_tail; the weight gradients partial)
     ahead: bool         # the rollout runs the first mini-epoch's forward passes
     ranks: bool         # several ranks: the exchanges run
+    symmetry: bool = False  # the mirror-symmetry loss: the actor trains on 2B rows (the batch, then its mirror images) through bg_actor_head_sym
 
 
 TAIL_MAX_ITEMS = 8192  # blocks of sums of one bg_update_tail launch (bg_tail.hip)
 
 
 def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_split_bwd, chain_alternate, fused_wgrad, wgrad_split, one_stream,
-                defer_finish, one_launch_tail, fused_opt, fused_head, fused_gae, chain_values, rollout_forward, dp_active):
+                defer_finish, one_launch_tail, fused_opt, fused_head, fused_gae, chain_values, rollout_forward, dp_active, symmetry=False):
     """UpdatePlan from the switches (MLPTrainer.SPLIT ... WGRAD_SPLIT and Runner._one_stream ... _rollout_forward, by the same names in lower case;
-    dp.active) and the shapes: critic / actor = (layer widths, padded input width), rows = the batch.  Pure: no tensors, no device."""
-    nets = [plan_network(w, kin, rows, split, fused, chain, chain_split, chain_split_bwd and fused_head, chain_alternate, fused_wgrad) for w, kin in (critic, actor)]
+    dp.active; symmetry = algorithm.symmetry_loss) and the shapes: critic / actor = (layer widths, padded input width), rows = the batch.  Pure: no
+    tensors, no device.  symmetry: the actor's passes differentiate 2 x rows rows (the batch and its mirror images) and the rollout runs no
+    forward passes for the update (ahead = False: update() mirrors the batch and runs the first mini-epoch's passes itself); a plan whose output
+    layers are not the fused head kernels is a ValueError (bg_actor_head_sym is the only form of the loss)."""
+    if symmetry and not fused_head:
+        raise ValueError("algorithm.symmetry_loss needs the fused output layers of bg_head.hip (bg_actor_head_sym: an actor whose last hidden layer is "
+                         "128 wide with 12 actions); this plan runs the output layers as library GEMMs")
+    nets = [plan_network(w, kin, r, split, fused, chain, chain_split, chain_split_bwd and fused_head, chain_alternate, fused_wgrad)
+            for (w, kin), r in ((critic, rows), (actor, 2 * rows if symmetry else rows))]
     bwd_chained = all(n.bwd == "chain_split" for n in nets)
     grouped = [(co, ci) for (w, kin), n in zip((critic, actor), nets) for ci, co, g in zip((kin,) + tuple(w[1:-1]), w[1:], n.grouped) if g]
     wgrad = ((split or (wgrad_split if bwd_chained else 0)) if rows % 32 == 0 and rows >= 128
@@ -119,7 +144,7 @@ def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_
     one_tail = (fused_opt and one_launch_tail and defer and finishing and all(all(n.grouped[:-1]) for n in nets) and sum(fins) + 2 <= 8
                 and sums <= TAIL_MAX_ITEMS)
     return UpdatePlan(nets[0], nets[1], wgrad, fused_head, fused_gae, chain_values, one_stream and chain_values and defer and bwd_chained, defer, fused_opt,
-                      one_tail, rollout_forward and chain_values and nets[1].chained, dp_active)
+                      one_tail, rollout_forward and chain_values and nets[1].chained and not symmetry, dp_active, bool(symmetry))
 
 
 class FlatAdam:
@@ -243,6 +268,10 @@ class Runner:
         if torch.device(self.device) != torch.device(self.env.device):
             raise ValueError("rl_device must equal sim_device: the rollout writes simulator outputs straight into the PPO buffers")
         self.learning_rate = self.cfg["algorithm"]["learning_rate"]
+        self._symmetry, self._symmetric_coef = symmetry_loss(self.cfg)
+        if self._symmetry:  # (ValueError for a model without a left / right pairing or with an asymmetric default pose)
+            obs_src, obs_sign, act_src, act_sign = self.env.mirror_maps()
+            self._act_mirror = (act_src.tolist(), act_sign.tolist())
         self.model = ActorCritic(self.env.num_actions, self.env.num_obs, self.env.num_privileged_obs, self.actor_hidden, self.critic_hidden).to(self.device)
         self.dp.broadcast_parameters(self.model)  # identical initial weights on every rank
         self.invalidate()
@@ -269,6 +298,11 @@ class Runner:
         self._pad_in = 64 if MLPTrainer.FUSED else None
         self._critic_in = torch.zeros(T + 1, N, self._pad_in or (self.env.num_obs + self.env.num_privileged_obs), device=dev)
         self._actor_in = torch.zeros(T, N, self._pad_in, device=dev) if self._pad_in else None
+        if self._symmetry:
+            # the actor's input of 2B rows: the batch, then its mirror images (bg_mirror_rows in update(); the padded columns stay zero)
+            kin = self._pad_in or self.env.num_obs
+            self._actor_in = torch.zeros(2 * T, N, kin, device=dev)
+            self._obs_mirror = (obs_src.tolist() + [-1] * (kin - len(obs_src)), obs_sign.tolist() + [1.0] * (kin - len(obs_sign)))
         self._adv = torch.zeros(T, N, device=dev)
         self._ret = torch.zeros(T, N, device=dev)
         self._adv_sums = torch.zeros(3, dtype=torch.float64, device=dev)
@@ -276,10 +310,12 @@ class Runner:
         self._grad_val = torch.zeros(B, device=dev)
         # the float64 sums of a mini-epoch that every rank needs in full: loss / KL statistics [5] and the log-std gradient [A], contiguous so that ONE
         # collective carries both (exchange (3); the log-std gradient then enters the optimiser launch in float64 and not through the fp32 bucket)
-        self._sums = torch.zeros(5 + A, dtype=torch.float64, device=dev)
-        self._stats, self._grad_logstd = self._sums[:5], self._sums[5:]
-        self._stats_acc = torch.zeros(5, dtype=torch.float64, device=dev)
-        self._stats_last = torch.zeros(5, dtype=torch.float64, device=dev)  # the last mini-epoch's sums (kl_mean of the log, runner.py:199)
+        # (with the symmetry loss a sixth statistic: the sum of squared mean asymmetries; without it the layout, and what the ranks exchange, stays five)
+        S = self._n_stats = 6 if self._symmetry else 5
+        self._sums = torch.zeros(S + A, dtype=torch.float64, device=dev)
+        self._stats, self._grad_logstd = self._sums[:S], self._sums[S:]
+        self._stats_acc = torch.zeros(S, dtype=torch.float64, device=dev)
+        self._stats_last = torch.zeros(S, dtype=torch.float64, device=dev)  # the last mini-epoch's sums (kl_mean of the log, runner.py:199)
         # False: the mini-epoch tail as separate launches (bg_adam_step, bg_adapt_lr, torch adds / fills): what the first optimiser step after a
         # checkpoint restore runs (see update()); as an attribute for the tests that compare the two forms
         self._fused_opt = True
@@ -322,6 +358,8 @@ class Runner:
         # fused output layers + loss (bg_head.hip): both networks end in a 128-wide ELU layer, 12 actions / 1 value (utils/model.py); a model of
         # other widths runs the output layers as library GEMMs + bg_ppo_loss (as an attribute for the test that compares the two forms)
         self._fused_head = A == 12 and self.model.actor[-1].in_features == 128 and self.model.critic[-1].in_features == 128
+        if self._symmetry and not self._fused_head:
+            raise ValueError("algorithm.symmetry_loss needs the fused output layers of bg_head.hip: an actor whose last hidden layer is 128 wide with 12 actions")
         self._old_mu = torch.zeros(B, A, device=dev)
         self._values_all = torch.zeros(B + N, device=dev)
         self._head_scratch_a, self._head_scratch_c = head_scratch(dev), head_scratch(dev)
@@ -335,6 +373,8 @@ class Runner:
         self._rollout_group = max(1, int(os.environ.get("BG_ROLLOUT_FORWARD_GROUP", "2")))
         self._fwd_plan = None  # the UpdatePlan under which rollout() has left the activations / values / old mu of the whole batch in the trainers' buffers
         self.timers = {"rollout": 0.0, "update": 0.0}
+        if self._symmetry:
+            self._resolve_plan()  # (a plan the symmetric head cannot serve is a ValueError here, not at the first update)
 
     # ------------------------------------------------------------------ config / seed / checkpoint (runner.py:44-97)
     def _get_args(self, args=None):
@@ -422,7 +462,7 @@ class Runner:
                                                       "_rollout_forward"))
         widths = lambda tr: (tr.layers[0].in_features,) + tuple(l.out_features for l in tr.layers)
         kin_a = self._actor_in.shape[-1] if self._actor_in is not None else self.env.num_obs
-        plan = plan_update((widths(ct), self._critic_in.shape[-1]), (widths(at), kin_a), self._old_logp.numel(), dp_active=self.dp.active, **sw)
+        plan = plan_update((widths(ct), self._critic_in.shape[-1]), (widths(at), kin_a), self._old_logp.numel(), dp_active=self.dp.active, symmetry=self._symmetry, **sw)
         ct.plan, at.plan = plan.critic, plan.actor
         c_out = ct.layers[-1]
         ct.value_head = (c_out.weight.reshape(-1), c_out.bias, self._values_all) if plan.chain_values else None
@@ -530,8 +570,10 @@ class Runner:
             self._critic_in[:, :, :no].copy_(buf["obses"])
             self._critic_in[:, :, no : no + npv].copy_(buf["privileged_obses"])
             if self._actor_in is not None:
-                self._actor_in[:, :, :no].copy_(buf["obses"][:T])
-        obs_flat = self._actor_in.reshape(B, -1) if self._actor_in is not None else buf["obses"][:T].reshape(B, -1)
+                self._actor_in[:T, :, :no].copy_(buf["obses"][:T])
+            if plan.symmetry:  # rows [B, 2B): the mirror images M_o x of the batch
+                mirror_rows(self._actor_in[:T].reshape(B, -1), self._actor_in[T:].reshape(B, -1), *self._obs_mirror)
+        obs_flat = self._actor_in.reshape(-1, self._actor_in.shape[-1]) if self._actor_in is not None else buf["obses"][:T].reshape(B, -1)
         critic_all = self._critic_in.reshape((T + 1) * N, -1)  # rows [B, B+N) = the observation after the last step (last_values)
         logstd_flat = self.model.logstd.reshape(-1)
         a_out, c_out = self._actor_tr.layers[-1], self._critic_tr.layers[-1]
@@ -540,7 +582,7 @@ class Runner:
             if ahead:
                 old_mu = self._old_mu
             elif plan.fused_head:
-                old_mu = actor_head_forward(self._actor_tr.forward_hidden(obs_flat), a_out.weight, a_out.bias, self._old_mu)
+                old_mu = actor_head_forward(self._actor_tr.forward_hidden(obs_flat)[:B], a_out.weight, a_out.bias, self._old_mu)
             else:
                 old_mu = self._actor_tr.forward(obs_flat).clone()
             old_logstd = self.model.logstd.detach().reshape(-1).clone()
@@ -601,10 +643,7 @@ class Runner:
                                      c_out.bias.grad, self._critic_tr.layers[-2].bias.grad, self._stats, self._head_scratch_c, finish=fin_c)
                 self._critic_tr.backward_hidden(finishes=fins)
             main.wait_event(gae_done)  # advantages and their moments
-            actor_head_loss_backward(ha, a_out.weight, a_out.bias, logstd_flat, act_flat, old_mu, old_logstd, self._old_logp,
-                                     self._adv.view(B), self._adv_sums, 0.2, alg["bound_coef"], alg["entropy_coef"],
-                                     self._actor_tr.hidden_grad, a_out.weight.grad, a_out.bias.grad, self._actor_tr.layers[-2].bias.grad,
-                                     self._grad_logstd, self._stats, self._head_scratch_a, finish=fin_a)
+            self._actor_loss_head(u, ha, fin_a)
             if plan.ranks and not defer:
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
@@ -642,11 +681,21 @@ class Runner:
         fins, fin_c, fin_a = [], _lib.ReduceProblem(), _lib.ReduceProblem()
         critic_head_backward(hc[:B], c_out.weight, values, self._ret.view(B), ct.hidden_grad, c_out.weight.grad, c_out.bias.grad, ct.layers[-2].bias.grad,
                              self._stats, self._head_scratch_c, finish=fin_c)
-        actor_head_loss_backward(ha, a_out.weight, a_out.bias, logstd_flat, act_flat, old_mu, old_logstd, self._old_logp, self._adv.view(B), self._adv_sums, 0.2,
-                                 alg["bound_coef"], alg["entropy_coef"], at.hidden_grad, a_out.weight.grad, a_out.bias.grad, at.layers[-2].bias.grad,
-                                 self._grad_logstd, self._stats, self._head_scratch_a, finish=fin_a)
+        self._actor_loss_head(u, ha, fin_a)
         MLPTrainer.backward_hidden_group([ct, at], fins)
         u.fins, u.fin_c, u.fin_a = fins, fin_c, fin_a
+
+    def _actor_loss_head(self, u, ha, finish):
+        """The actor's output layer fused with its loss and backward (runner.py:145-161) on the last hidden activations ha: bg_actor_head, or with the
+        mirror-symmetry loss bg_actor_head_sym on the 2B rows of ha (the batch, then its mirror images)."""
+        at, a_out, alg = self._actor_tr, u.a_out, u.alg
+        args = (ha, a_out.weight, a_out.bias, u.logstd_flat, u.act_flat, u.old_mu, u.old_logstd, self._old_logp, self._adv.view(u.B), self._adv_sums, 0.2,
+                alg["bound_coef"], alg["entropy_coef"])
+        outs = (at.hidden_grad, a_out.weight.grad, a_out.bias.grad, at.layers[-2].bias.grad, self._grad_logstd, self._stats, self._head_scratch_a)
+        if u.plan.symmetry:
+            actor_head_sym_loss_backward(*args, self._symmetric_coef, self._act_mirror, *outs, finish=finish)
+        else:
+            actor_head_loss_backward(*args, *outs, finish=finish)
 
     def _epoch_gradients_and_step(self, u):
         """Deferred reductions, all weight gradients, the exchange of the gradient over the ranks, clip + Adam + KL rule (runner.py:162-180)."""
@@ -721,11 +770,13 @@ class Runner:
         fixed = os.environ.get("BG_FWD_CHAIN_CUS")  # "critic,actor": a fixed split (A/B runs)
         if fixed:
             ct.chain_workgroups, at.chain_workgroups = (int(v) for v in fixed.split(","))
-        # the chained backward launches likewise (both networks differentiate the actor's rows; slab cost ~ flops of the two backward layers)
+        # the chained backward launches likewise (slab cost ~ flops of the two backward layers)
         ct.chain_bwd_workgroups = at.chain_bwd_workgroups = 0
         if self._split_bwd_chain_cus and plan.critic.bwd == plan.actor.bwd == "chain_split":
             bcost = lambda tr: sum(l.weight.shape[0] * l.weight.shape[1] for l in tr.layers[1:3])
-            ct.chain_bwd_workgroups, at.chain_bwd_workgroups = plan_chain_split(sa, sa, bcost(ct), bcost(at), cus)
+            # the critic's backward differentiates the batch, the actor's the batch (and, with the symmetry loss, its mirror images: x_a's 2B rows)
+            sb = (x_a.shape[0] // (2 if plan.symmetry else 1) + 127) // 128
+            ct.chain_bwd_workgroups, at.chain_bwd_workgroups = plan_chain_split(sb, sa, bcost(ct), bcost(at), cus)
             fixed = os.environ.get("BG_BWD_CHAIN_CUS")  # "critic,actor": a fixed split (A/B runs)
             if fixed:
                 ct.chain_bwd_workgroups, at.chain_bwd_workgroups = (int(v) for v in fixed.split(","))
@@ -758,10 +809,13 @@ class Runner:
 
     def _summary_from(self, s):
         T, N = self.cfg["runner"]["horizon_length"], self.env.num_envs
-        B, A, E = T * N * self.world_size, self.env.num_actions, self.cfg["runner"]["mini_epochs"]
-        self.learning_rate = s[10]
-        return {"value_loss": s[0] / (B * E), "actor_loss": s[1] / (B * E), "bound_loss": s[2] / (B * A * E), "entropy": s[3] / (B * E),
-                "kl_mean": s[9] / B, "lr": s[10]}
+        B, A, E, S = T * N * self.world_size, self.env.num_actions, self.cfg["runner"]["mini_epochs"], self._n_stats
+        self.learning_rate = s[2 * S]
+        out = {"value_loss": s[0] / (B * E), "actor_loss": s[1] / (B * E), "bound_loss": s[2] / (B * A * E), "entropy": s[3] / (B * E),
+               "kl_mean": s[S + 4] / B, "lr": s[2 * S]}
+        if S > 5:  # mean squared asymmetry of the actor's mean, before symmetric_coef (like bound_loss before bound_coef)
+            out["symmetry_loss"] = s[5] / (B * A * E)
+        return out
 
     # ------------------------------------------------------------------ entry points
     # The reference's loop reads several scalars per mini-epoch with .item() (runner.py:175,182-184) and so stalls the GPU twenty times per
@@ -774,7 +828,7 @@ class Runner:
         obs, infos = self.env.reset()
         self.buffer["obses"][0].copy_(obs)
         self.buffer["privileged_obses"][0].copy_(infos["privileged_obs"])
-        n = 11 + 4 + _lib.NUM_REWARD_TERMS + 4
+        n = 2 * self._n_stats + 1 + 4 + _lib.NUM_REWARD_TERMS + 4
         self._log_dev = torch.zeros(n, dtype=torch.float64, device=self.device)
         self._log_host = [torch.zeros(n, dtype=torch.float64).pin_memory() for _ in range(2)]
         self._log_event = [torch.cuda.Event() for _ in range(2)]
@@ -788,11 +842,12 @@ class Runner:
         self._log_event[slot].synchronize()  # recorded one iteration ago: already complete unless the host ran a whole iteration ahead
         s = self._log_host[slot].tolist()
         self._log_pending = None
-        summary = self._summary_from(s[:11])
+        h = 2 * self._n_stats + 1  # loss sums, the last mini-epoch's sums, learning rate
+        summary = self._summary_from(s[:h])
         ne = 4 + _lib.NUM_REWARD_TERMS
-        self.recorder.record_episode_statistics(self.env, self.env.reward_names, it, stats=s[11 : 11 + ne])
-        self.nonfinite_resets_total += s[11 + ne - 1]
-        lv = s[11 + ne :]
+        self.recorder.record_episode_statistics(self.env, self.env.reward_names, it, stats=s[h : h + ne])
+        self.nonfinite_resets_total += s[h + ne - 1]
+        lv = s[h + ne :]
         if self.cfg["commands"].get("curriculum", False):
             self.env.mean_lin_vel_level, self.env.mean_ang_vel_level, self.env.max_lin_vel_level, self.env.max_ang_vel_level = lv
         summary.update({"curriculum/mean_lin_vel_level": self.env.mean_lin_vel_level, "curriculum/mean_ang_vel_level": self.env.mean_ang_vel_level,
@@ -802,15 +857,16 @@ class Runner:
     def train_iteration(self, it):
         """One pass of the reference's training loop body (runner.py:103-213): rollout, update, statistics, curriculum exchange, checkpoint."""
         stats = self.iteration()
-        d = self._log_dev
-        d[0:5].copy_(stats); d[5:10].copy_(self._stats_last); d[10:11].copy_(self.optimizer.lr)
+        d, S = self._log_dev, self._n_stats
+        h = 2 * S + 1
+        d[0:S].copy_(stats); d[S : 2 * S].copy_(self._stats_last); d[2 * S : h].copy_(self.optimizer.lr)
         ne = 4 + _lib.NUM_REWARD_TERMS
-        d[11 : 11 + ne].copy_(self.env.episode_stats(reset=True))
+        d[h : h + ne].copy_(self.env.episode_stats(reset=True))
         self._sync_curriculum()
         if self.cfg["commands"].get("curriculum", False):
             lin = self.env.get_field("env_curriculum_level_lin").abs().double()
             ang = self.env.get_field("env_curriculum_level_ang").abs().double()
-            d[11 + ne :].copy_(torch.stack((lin.mean(), ang.mean(), lin.max(), ang.max())))
+            d[h + ne :].copy_(torch.stack((lin.mean(), ang.mean(), lin.max(), ang.max())))
         self._flush_log()  # the previous iteration's scalars: their copy finished long ago
         slot = it & 1
         self._log_host[slot].copy_(d, non_blocking=True)

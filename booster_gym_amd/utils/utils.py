@@ -169,6 +169,42 @@ def actor_head_loss_backward(h, weight, bias, logstd, actions, old_mu, old_logst
                                          _lib.current_stream_ptr()), "bg_actor_head")
 
 
+def actor_head_sym_loss_backward(h, weight, bias, logstd, actions, old_mu, old_logstd, old_logp, adv, adv_stats, e_clip, bound_coef, entropy_coef,
+                                 sym_coef, act_mirror, g_hidden, grad_weight, grad_bias, grad_bias_hidden, grad_logstd, stats, scratch, mu_out=None,
+                                 finish=None):
+    """actor_head_loss_backward plus the mirror-symmetry loss (bg_actor_head_sym): h [2B, 128] holds the batch's rows and then their mirror images,
+    g_hidden [2B, 128] (and mu_out [2B, 12]) likewise; act_mirror = (src, sign) of M_a (int32 / float32 sequences of 12: (M_a v)[a] = sign[a]
+    v[src[a]]).  stats float64[6]: entries 1..4 as actor_head_loss_backward, entry 5 += sum_r |mu(M_o x_r) - M_a mu(x_r)|^2.  The PPO terms see rows
+    [0, B) only; the output-layer and bias gradients cover all 2B rows.  finish: as for actor_head_loss_backward."""
+    _need_cuda(h, weight, bias, logstd, actions, old_mu, old_logstd, old_logp, adv, adv_stats, g_hidden, grad_weight, grad_bias, grad_bias_hidden,
+               grad_logstd, stats, scratch)
+    if h.shape[0] % 2 or g_hidden.shape[0] != h.shape[0] or stats.numel() < 6 or (mu_out is not None and mu_out.shape[0] != h.shape[0]):
+        raise ValueError("actor_head_sym_loss_backward: h, g_hidden (and mu_out) of 2B rows, stats of 6 entries")
+    B = h.shape[0] // 2
+    if actions.shape[0] != B or old_mu.shape[0] != B or old_logp.shape[0] != B or adv.shape[0] != B:
+        raise ValueError("actor_head_sym_loss_backward: actions, old_mu, old_logp and adv of B rows")
+    src, sign = (C.c_int32 * 12)(*[int(v) for v in act_mirror[0]]), (C.c_float * 12)(*[float(v) for v in act_mirror[1]])
+    args = [h.shape[0] // 2] + [_lib.ptr(t) for t in (h, weight, bias, logstd, actions, old_mu, old_logstd, old_logp, adv, adv_stats)]
+    args += [e_clip, bound_coef, entropy_coef, sym_coef, src, sign]
+    args += [_lib.ptr(t) for t in (mu_out, g_hidden, grad_weight, grad_bias, grad_bias_hidden, grad_logstd, stats, scratch)]
+    if finish is not None:
+        _lib.check(_lib.load().bg_actor_head_sym_partial(*args, finish, _lib.current_stream_ptr()), "bg_actor_head_sym_partial")
+    else:
+        _lib.check(_lib.load().bg_actor_head_sym(*args, _lib.current_stream_ptr()), "bg_actor_head_sym")
+
+
+def mirror_rows(x, y, src, sign):
+    """y[r, c] = sign[c] * x[r, src[c]] (src[c] = -1: 0) on [rows, cols <= 64] row-major tensors (bg_mirror_rows): the mirror images of a batch of
+    network inputs.  src / sign: sequences of cols, sign +-1."""
+    _need_cuda(x, y)
+    rows, cols = x.shape
+    if y.shape != x.shape or len(src) != cols or len(sign) != cols:
+        raise ValueError("mirror_rows: x and y of one shape, src / sign of its width")
+    _lib.check(_lib.load().bg_mirror_rows(rows, cols, (C.c_int32 * cols)(*[int(v) for v in src]), (C.c_float * cols)(*[float(v) for v in sign]),
+                                          _lib.ptr(x), _lib.ptr(y), _lib.current_stream_ptr()), "bg_mirror_rows")
+    return y
+
+
 def critic_head_backward(h, weight, values, returns, g_hidden, grad_weight, grad_bias, grad_bias_hidden, stats, scratch, finish=None):
     """Backward of mean((values - returns)^2) (runner.py:148) through the 128 -> 1 output layer; stats[0] += sum of squared errors.
     finish: as for actor_head_loss_backward."""

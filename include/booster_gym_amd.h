@@ -445,6 +445,20 @@ int bg_actor_head(int32_t B, int32_t mode, const float* h, const float* W, const
 int bg_critic_head_backward(int32_t B, const float* h, const float* w, const float* values, const float* returns, float* g_hidden, float* grad_w,
                             float* grad_b, float* grad_b_hidden, double* stats, float* scratch, void* stream);
 
+/* Mirror-symmetry loss (algorithm.symmetry_loss): the actor's batch is 2B rows, rows [B, 2B) of h / g_hidden / mu_out the mirror images of rows [0, B)
+ * (their observations M_o x, written by bg_mirror_rows).  bg_actor_head mode 1 on the original rows plus, with d_r = mu(M_o x_r) - M_a mu(x_r), the term
+ * sym_coef / (B 12) sum_r |d_r|^2, differentiated through both means: g_hidden [2B][128], grad_W / grad_b / grad_b_hidden over all 2B rows,
+ * grad_logstd as bg_actor_head, stats[1..4] as bg_actor_head and stats[5] = sum_r |d_r|^2 (float64).  M_a: act_src / act_sign (host arrays of 12),
+ * (M_a v)[a] = act_sign[a] v[act_src[a]], a symmetric involution (act_src[act_src[a]] = a, act_sign[act_src[a]] = act_sign[a]; -1 otherwise).
+ * Fixed-order sums as bg_actor_head; mu_out [2B][12] may be NULL. */
+int bg_actor_head_sym(int32_t B, const float* h, const float* W, const float* bias, const float* logstd, const float* actions, const float* old_mu,
+                      const float* old_logstd, const float* old_logp, const float* adv, const double* adv_stats, float e_clip, float bound_coef,
+                      float entropy_coef, float sym_coef, const int32_t* act_src, const float* act_sign, float* mu_out, float* g_hidden, float* grad_W,
+                      float* grad_b, float* grad_b_hidden, double* grad_logstd, double* stats, float* scratch, void* stream);
+/* y [rows][cols] = the rows of x [rows][cols] mirrored: y[r][c] = sign[c] x[r][src[c]] (src[c] = -1: 0), cols <= 64, src / sign host arrays of cols,
+ * sign +-1; x and y must not overlap.  Exact. */
+int bg_mirror_rows(int32_t rows, int32_t cols, const int32_t* src, const float* sign, const float* x, float* y, void* stream);
+
 /* ---- deferred fixed-order reductions.  The head kernels and the backward layer kernel leave per-workgroup partial sums that a small second
  * kernel adds up (head: output-layer weight / bias gradients, last hidden layer's bias gradient, float64 loss statistics; backward layer: the
  * bias gradient of the layer below).  None of these sums is needed before the optimiser step (utils/runner.py:162-165), so instead of one small
@@ -461,6 +475,11 @@ typedef struct {
     uint64_t stat_base; int32_t n_stat, n_ls; uint32_t stat_skip; double entropy_coef; double* grad_logstd; double* stats;
 } bg_reduce_problem;
 int bg_reduce_group(const bg_reduce_problem* problems, int32_t count, void* stream); /* count <= 8 */
+/* bg_actor_head_sym without its finishing launch (as bg_actor_head_partial). */
+int bg_actor_head_sym_partial(int32_t B, const float* h, const float* W, const float* bias, const float* logstd, const float* actions, const float* old_mu,
+                              const float* old_logstd, const float* old_logp, const float* adv, const double* adv_stats, float e_clip, float bound_coef,
+                              float entropy_coef, float sym_coef, const int32_t* act_src, const float* act_sign, float* mu_out, float* g_hidden, float* grad_W,
+                              float* grad_b, float* grad_b_hidden, double* grad_logstd, double* stats, float* scratch, bg_reduce_problem* finish, void* stream);
 /* The backward-data chain of one network in ONE launch on the bf16 matrix pipe with fp32 semantics (bg_mlp_chain_split_bwd.hip; the dX part of
  * `loss.backward()`, utils/runner.py:163, through utils/model.py:9-26's hidden layers):  G2 [M][N2] = (G3 [M][N3] . W3 [N3][N2]) * elu'(A2),
  * G1 [M][N1] = (G2 . W2 [N2][N1]) * elu'(A1), and the column sums of G2 / G1 (the bias gradients of layers 2 / 1: bg_mlp_layer_backward twice).
