@@ -118,6 +118,8 @@ class EnvCfg(C.Structure):
         ("body_gate_height", C.c_float), ("penalized_body_mask", C.c_int32), ("terminate_body_mask", C.c_int32),
         ("exact_still_count", C.c_int32), ("same_step_curriculum", C.c_int32),
         ("self_collisions", C.c_int32), ("self_k", C.c_float), ("self_d", C.c_float), ("self_mu", C.c_float), ("self_visc", C.c_float),
+        ("terrain_curriculum", C.c_int32), ("terrain_num_levels", C.c_int32), ("terrain_tile_width", C.c_float), ("terrain_tile_length", C.c_float),
+        ("terrain_down_time", C.c_float),
     ]
 
 
@@ -128,6 +130,7 @@ SYMBOLS = [
     "bg_model_create", "bg_model_get", "bg_model_destroy", "bg_model_load_urdf", "bg_model_body_name", "bg_model_dof_name", "bg_model_find_body", "bg_env_create", "bg_env_destroy", "bg_env_set_heightfield",
     "bg_env_set_params", "bg_env_bind_outputs", "bg_env_reset", "bg_env_step", "bg_env_step_to", "bg_env_get_state",
     "bg_env_set_state", "bg_env_get_field", "bg_env_set_field", "bg_env_field_info", "bg_env_get_curriculum", "bg_env_set_curriculum", "bg_env_step_count", "bg_env_set_step_count",
+    "bg_env_get_terrain_level_sum", "bg_env_set_terrain_level_sum",
     "bg_env_forward_dynamics", "bg_env_forward_dynamics_packed", "bg_sim_bind_state", "bg_sim_set_actuation", "bg_sim_apply_body_wrench_local", "bg_sim_simulate",
     "bg_sim_refresh_body_state", "bg_sim_write_root_state", "bg_sim_write_dof_state", "bg_gae", "bg_ppo_loss", "bg_gaussian_logp", "bg_actor_sample", "bg_actor_sample_mlp", "bg_adam_step", "bg_adapt_lr", "bg_optimizer_step", "bg_elu_backward_colsum", "bg_mlp_layer_forward", "bg_mlp_chain_forward", "bg_critic_values_gae", "bg_mlp_chain_forward_group", "bg_mlp_chain_forward_split", "bg_mlp_chain_backward_split", "bg_mlp_split_weights_pm", "bg_mlp_layer_backward", "bg_mlp_split_weights", "bg_mlp_layer_forward_split", "bg_mlp_layer_backward_split", "bg_mlp_weight_grad", "bg_mlp_weight_grad_group", "bg_mlp_weight_grad_group_partial", "bg_update_tail", "bg_update_tail_sums", "bg_mlp_weight_grad_group_split", "bg_mlp_weight_grad_group_split_partial",
     "bg_critic_head_forward", "bg_actor_head", "bg_critic_head_backward",
@@ -174,6 +177,8 @@ def load():
         "bg_env_field_info": (i32, [vp, C.c_char_p, C.POINTER(i32), C.POINTER(i32)]),
         "bg_env_get_curriculum": (i32, [vp, vp, vp]),
         "bg_env_set_curriculum": (i32, [vp, vp, vp]),
+        "bg_env_get_terrain_level_sum": (i32, [vp, vp, vp]),
+        "bg_env_set_terrain_level_sum": (i32, [vp, vp, vp]),
         "bg_env_step_count": (i64, [vp]),
         "bg_env_set_step_count": (i32, [vp, i64]),
         "bg_env_forward_dynamics": (i32, [vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -80,6 +80,7 @@ struct EnvDev {
     TerrainDev terrain;
     bg_env_cfg cfg;
     int n;
+    int32_t* tcur;  // terrain curriculum (cfg.terrain_curriculum), else null: [n] levels, [n] columns, [1] sum of the levels
 };
 
 struct StepOut {
@@ -211,7 +212,8 @@ BG_HD FieldRef<H16> field_ref(float* F, bg_half_bits* H, int idx, int n, int e) 
 }
 
 // BODY: this env step evaluates the non-foot body contacts (decided by the caller from the trunk height at the START of the env step)
-template <class X, class Sink, bool H16, bool BODY>
+// TC: the terrain curriculum (cfg.terrain_curriculum) -- a compile-time switch, so that the instantiations without it compile exactly as before
+template <class X, class Sink, bool H16, bool BODY, bool TC = false>
 BG_HD void env_step_lane(const EnvDev& E, X& x, Sink& sink, int e, int leg, bool valid, const float* act, uint32_t step, int mode,
                          const StepOut& out) {
     const bg_env_cfg& C = E.cfg;
@@ -508,6 +510,40 @@ BG_HD void env_step_lane(const EnvDev& E, X& x, Sink& sink, int e, int leg, bool
 #undef BG_ACC
         }
     }
+    // ------------------------------------------------------------ terrain curriculum update (legged_gym's _update_terrain_curriculum), pre-reset
+    // values: root position, origin and command of the ending episode.  Both lanes of the env compute the same level and origin (the spawn below
+    // reads them from registers); the leg-0 lane stores them.
+    float org_x = 0.f, org_y = 0.f;
+    if constexpr (TC) {
+        org_x = FLD(F_ORIGIN, 0); org_y = FLD(F_ORIGIN, 1);
+        if (reset_flag && mode == 0 && valid && bad == 0.f) {
+            int32_t* const TL = E.tcur;
+            const int lvl = TL[e], col = TL[(size_t)n + e];
+            const float dx = bs.pos.e[0] - org_x, dy = bs.pos.e[1] - org_y;
+            const float d = sqrtf(dx * dx + dy * dy);
+            const bool up = d > 0.5f * C.terrain_tile_length;
+            const bool down = !up && d < sqrtf(cmd[0] * cmd[0] + cmd[1] * cmd[1]) * C.terrain_down_time;
+            int nl = lvl + (up ? 1 : 0) - (down ? 1 : 0);
+            nl = nl < 0 ? 0 : nl;
+            if (nl >= C.terrain_num_levels) {  // past the top: a uniform random level (the same draw on both lanes)
+                nl = (int)(rand4(C.seed, (uint32_t)e, step, RS_TLEVEL).u[0] * (float)C.terrain_num_levels);
+                nl = nl < C.terrain_num_levels ? nl : C.terrain_num_levels - 1;
+            }
+            org_x = ((float)col + 0.5f) * C.terrain_tile_width;
+            org_y = ((float)nl + 0.5f) * C.terrain_tile_length;
+            if (leg == 0) {
+                TL[e] = nl;
+                FLD(F_ORIGIN, 0) = org_x; FLD(F_ORIGIN, 1) = org_y; FLD(F_ORIGIN, 2) = terrain_height(E.terrain, org_x, org_y);
+                if (nl != lvl) {
+#if defined(__HIP_DEVICE_COMPILE__)
+                    atomicAdd(&TL[2 * (size_t)n], nl - lvl);
+#else
+                    TL[2 * (size_t)n] += nl - lvl;
+#endif
+                }
+            }
+        }
+    }
     if (reset_flag) {
         uint32_t noise_env = C.shared_reset_noise ? 0xFFFFFFFFu : (uint32_t)e;
         Rand4 d0 = rand4(C.seed, noise_env, step, so + RS_RESETDOF + leg * 2), d1 = rand4(C.seed, noise_env, step, so + RS_RESETDOF + leg * 2 + 1);
@@ -518,8 +554,9 @@ BG_HD void env_step_lane(const EnvDev& E, X& x, Sink& sink, int e, int leg, bool
             last_tgt[i] = ls.q[i];
         }
         Rand4 r0 = rand4(C.seed, (uint32_t)e, step, so + RS_RESET0), r1 = rand4(C.seed, (uint32_t)e, step, so + RS_RESET1);
-        float px = apply_rand(C.base_init_state[0] + FLD(F_ORIGIN, 0), C.init_base_pos_xy, r0.u[0], r0.n[0]);
-        float py = apply_rand(C.base_init_state[1] + FLD(F_ORIGIN, 1), C.init_base_pos_xy, r0.u[1], r0.n[1]);
+        // (the curriculum's origin from registers: the one just updated; the expression otherwise exactly the one without it)
+        float px = apply_rand(C.base_init_state[0] + (TC ? org_x : (float)FLD(F_ORIGIN, 0)), C.init_base_pos_xy, r0.u[0], r0.n[0]);
+        float py = apply_rand(C.base_init_state[1] + (TC ? org_y : (float)FLD(F_ORIGIN, 1)), C.init_base_pos_xy, r0.u[1], r0.n[1]);
         bs.pos = v3(px, py, C.base_init_state[2] + terrain_height(E.terrain, px, py));
         float yw = r0.u[2] * 6.28318530717959f, sy, cy;
         bg_sincos(0.5f * yw, &sy, &cy);

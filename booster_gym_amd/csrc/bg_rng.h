@@ -56,6 +56,7 @@ enum {
     RS_CMD0 = 24,     // vx vy yaw gait_frequency
     RS_CMD1 = 25,     // still, resample time
     RS_CURR = 26,     // curriculum: grid cell, cmd x / y / yaw jitter
+    RS_TLEVEL = 27,   // terrain curriculum: the level of an env that passed the top one
     RS_ACTOR = 32     // + k : action noise (bg_actor_sample)
 };
 

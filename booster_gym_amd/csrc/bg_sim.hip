@@ -41,6 +41,7 @@ struct bg_env {
     float* curr = nullptr;
     float* curr_read = nullptr;
     int curr_cells = 0;
+    int32_t* tcur = nullptr;  // terrain curriculum: [n] levels, [n] columns, [1] level sum (cfg.terrain_curriculum only)
     ModelDev* model_dev = nullptr;
     PairModel* pair_dev = nullptr;  // the leg constants with the two legs side by side (packed ABA kernel)
     int16_t* hf = nullptr;
@@ -96,7 +97,8 @@ __device__ __forceinline__ void copy_out_rows(const StepOut& out, int e0, int ro
     }
 }
 
-template <bool H16, bool GATED>
+// TC: with the terrain curriculum's level update at resets (separate instantiations: the default ones compile without a trace of it)
+template <bool H16, bool GATED, bool TC = false>
 __global__ __launch_bounds__(64) void env_step_kernel(EnvDev E, const float* __restrict__ act, uint32_t step, int mode, StepOut out,
                                                       unsigned* __restrict__ lowmask) {
     __shared__ float s_obs[ENVS_PER_BLOCK * BG_NUM_OBS];
@@ -116,7 +118,7 @@ __global__ __launch_bounds__(64) void env_step_kernel(EnvDev E, const float* __r
     const V3 p0 = v3(E.f[(size_t)(F_ROOT + 0) * E.n + e], E.f[(size_t)(F_ROOT + 1) * E.n + e], E.f[(size_t)(F_ROOT + 2) * E.n + e]);
     const bool low = GATED && mode == 0 && body_contacts_active(make_phys(E.cfg), E.terrain, *E.model, p0);
     if (low) { if (valid && !(lane & 1)) atomicOr(&s_low, 1u << (lane >> 1)); }
-    else env_step_lane<DppSwap, LdsSink, H16, false>(E, x, sink, e, lane & 1, valid, act, step, mode, out);
+    else env_step_lane<DppSwap, LdsSink, H16, false, TC>(E, x, sink, e, lane & 1, valid, act, step, mode, out);
     __syncthreads();
     const int rows = min(ENVS_PER_BLOCK, E.n - e0);
     const unsigned lowm = s_low;
@@ -133,7 +135,7 @@ __global__ __launch_bounds__(64) void env_step_kernel(EnvDev E, const float* __r
 }
 
 // kernel B: the envs kernel A left out (trunk low at the start of the step), with the non-foot body contacts
-template <bool H16>
+template <bool H16, bool TC = false>
 __global__ __launch_bounds__(64) void env_step_body_kernel(EnvDev E, const float* __restrict__ act, uint32_t step, StepOut out,
                                                            const unsigned* __restrict__ lowmask, int nblocks) {
     __shared__ float s_obs[ENVS_PER_BLOCK * BG_NUM_OBS];
@@ -149,7 +151,7 @@ __global__ __launch_bounds__(64) void env_step_body_kernel(EnvDev E, const float
         if (!valid) e = E.n - 1;
         DppSwap x;
         LdsSink sink{s_obs, s_priv, lane >> 1, (lds_f32*)s_self, lane};
-        if ((lowm >> (lane >> 1)) & 1u) env_step_lane<DppSwap, LdsSink, H16, true>(E, x, sink, e, lane & 1, valid, act, step, 0, out);
+        if ((lowm >> (lane >> 1)) & 1u) env_step_lane<DppSwap, LdsSink, H16, true, TC>(E, x, sink, e, lane & 1, valid, act, step, 0, out);
         __syncthreads();
         copy_out_rows(out, e0, min(ENVS_PER_BLOCK, E.n - e0), lowm, s_obs, s_priv);
         __syncthreads();
@@ -628,7 +630,7 @@ __global__ void set_state_kernel(EnvDev E, const float* root, const float* dof) 
 static EnvDev env_dev(const bg_env* e) {
     EnvDev E;
     E.zmask = e->zmask;
-    E.f = e->f; E.h = e->h; E.i = e->i; E.stats = e->stats; E.curr = e->curr; E.curr_read = e->curr_read; E.model = e->model_dev; E.terrain = e->terrain; E.cfg = e->cfg; E.n = e->n;
+    E.f = e->f; E.h = e->h; E.i = e->i; E.stats = e->stats; E.curr = e->curr; E.curr_read = e->curr_read; E.tcur = e->tcur; E.model = e->model_dev; E.terrain = e->terrain; E.cfg = e->cfg; E.n = e->n;
     return E;
 }
 
@@ -657,6 +659,10 @@ static int env_create_fill(bg_env* e, const bg_env_cfg* cfg, const bg_model* mod
     HIP_OK(hipMemset(e->f, 0, sizeof(float) * n * F_COUNT));
     HIP_OK(hipMemset(e->i, 0, sizeof(int32_t) * n * I_COUNT));
     HIP_OK(hipMemset(e->stats, 0, sizeof(float) * STATS_COUNT));
+    if (cfg->terrain_curriculum) {  // levels / columns / sum all zero until the caller sets them (fields terrain_level, terrain_type)
+        HIP_OK(hipMalloc(&e->tcur, sizeof(int32_t) * (2 * n + 1)));
+        HIP_OK(hipMemset(e->tcur, 0, sizeof(int32_t) * (2 * n + 1)));
+    }
     ModelDev md;
     memset(&md, 0, sizeof(md));
     for (int b = 0; b < BG_NUM_BODIES; b++) {
@@ -741,6 +747,8 @@ extern "C" int bg_env_create(const bg_env_cfg* cfg, const bg_model* model, bg_en
     if (cfg->decimation <= 0 || !(cfg->sim_dt > 0.f)) return fail(-1, "bg_env_create: bad sim dt / decimation");
     if (cfg->lin_vel_levels < 0 || cfg->ang_vel_levels < 0 || cfg->lin_vel_levels > 64 || cfg->ang_vel_levels > 64)
         return fail(-1, "bg_env_create: curriculum levels out of range");
+    if (cfg->terrain_curriculum && (cfg->terrain_type == 0 || cfg->terrain_num_levels < 1 || !(cfg->terrain_tile_width > 0.f) || !(cfg->terrain_tile_length > 0.f)))
+        return fail(-1, "bg_env_create: the terrain curriculum needs a height field of at least one level and positive tile sizes");
     int ndev = 0;
     hipError_t de = hipGetDeviceCount(&ndev);
     if (de != hipSuccess || ndev == 0) return fail(-3, "bg_env_create: no HIP device available (this library has no CPU path)");
@@ -759,7 +767,7 @@ extern "C" int bg_env_create(const bg_env_cfg* cfg, const bg_model* model, bg_en
 extern "C" void bg_env_destroy(bg_env* e) {
     if (!e) return;
     (void)hipFree(e->sim_tau); (void)hipFree(e->sim_bforce); (void)hipFree(e->sim_btorque);
-    (void)hipFree(e->f); (void)hipFree(e->h); (void)hipFree(e->lowmask); (void)hipFree(e->fd_mask); (void)hipFree(e->fd_list); (void)hipFree(e->fd_count); (void)hipFree(e->rs_counts); (void)hipFree(e->i); (void)hipFree(e->stats); (void)hipFree(e->model_dev); (void)hipFree(e->pair_dev); (void)hipFree(e->hf); (void)hipFree(e->curr); (void)hipFree(e->curr_read);
+    (void)hipFree(e->f); (void)hipFree(e->h); (void)hipFree(e->lowmask); (void)hipFree(e->fd_mask); (void)hipFree(e->fd_list); (void)hipFree(e->fd_count); (void)hipFree(e->rs_counts); (void)hipFree(e->i); (void)hipFree(e->stats); (void)hipFree(e->model_dev); (void)hipFree(e->pair_dev); (void)hipFree(e->hf); (void)hipFree(e->curr); (void)hipFree(e->curr_read); (void)hipFree(e->tcur);
     delete e;
 }
 
@@ -810,7 +818,15 @@ static int launch_step(bg_env* e, const float* actions, int mode, const StepOut&
     dim3 grid((e->n + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK), block(64);
     hipStream_t st = (hipStream_t)stream;
     const uint32_t cnt = (uint32_t)e->step_count;
-    if (e->body_two_kernel) {
+    if (e->tcur) {  // terrain curriculum: the same launches, instantiated with the level update
+        if (e->body_two_kernel) {
+            if (e->h) hipLaunchKernelGGL((env_step_kernel<true, true, true>), grid, block, 0, st, env_dev(e), actions, cnt, mode, out, e->lowmask);
+            else hipLaunchKernelGGL((env_step_kernel<false, true, true>), grid, block, 0, st, env_dev(e), actions, cnt, mode, out, e->lowmask);
+        } else {
+            if (e->h) hipLaunchKernelGGL((env_step_kernel<true, false, true>), grid, block, 0, st, env_dev(e), actions, cnt, mode, out, (unsigned*)nullptr);
+            else hipLaunchKernelGGL((env_step_kernel<false, false, true>), grid, block, 0, st, env_dev(e), actions, cnt, mode, out, (unsigned*)nullptr);
+        }
+    } else if (e->body_two_kernel) {
         if (e->h) hipLaunchKernelGGL((env_step_kernel<true, true>), grid, block, 0, st, env_dev(e), actions, cnt, mode, out, e->lowmask);
         else hipLaunchKernelGGL((env_step_kernel<false, true>), grid, block, 0, st, env_dev(e), actions, cnt, mode, out, e->lowmask);
     } else {
@@ -820,7 +836,10 @@ static int launch_step(bg_env* e, const float* actions, int mode, const StepOut&
     if (e->body_two_kernel && mode == 0) {  // kernel B: the envs whose trunk was low at the start of the step (usually none)
         const int nb = (int)grid.x;
         dim3 gb(nb < BODY_GRID ? nb : BODY_GRID);
-        if (e->h) hipLaunchKernelGGL(env_step_body_kernel<true>, gb, block, 0, st, env_dev(e), actions, cnt, out, (const unsigned*)e->lowmask, nb);
+        if (e->tcur) {
+            if (e->h) hipLaunchKernelGGL((env_step_body_kernel<true, true>), gb, block, 0, st, env_dev(e), actions, cnt, out, (const unsigned*)e->lowmask, nb);
+            else hipLaunchKernelGGL((env_step_body_kernel<false, true>), gb, block, 0, st, env_dev(e), actions, cnt, out, (const unsigned*)e->lowmask, nb);
+        } else if (e->h) hipLaunchKernelGGL(env_step_body_kernel<true>, gb, block, 0, st, env_dev(e), actions, cnt, out, (const unsigned*)e->lowmask, nb);
         else hipLaunchKernelGGL(env_step_body_kernel<false>, gb, block, 0, st, env_dev(e), actions, cnt, out, (const unsigned*)e->lowmask, nb);
     }
     if (e->rs_counts) {  // reference-exact resampling: the cross-env part of _resample_commands (see resample_apply_kernel)
@@ -885,8 +904,20 @@ static const FieldInfo* find_field(const char* name) {
     for (const auto& f : kFields) if (strcmp(f.name, name) == 0) return &f;
     return nullptr;
 }
+// the terrain curriculum's per-env int arrays (allocated only with cfg.terrain_curriculum): offset into bg_env::tcur, or -1
+static int terrain_field(const char* name) {
+    if (!name) return -1;
+    if (strcmp(name, "terrain_level") == 0) return 0;
+    if (strcmp(name, "terrain_type") == 0) return 1;
+    return -1;
+}
 extern "C" int bg_env_field_info(bg_env* e, const char* name, int32_t* comps, int32_t* is_int) {
-    (void)e;
+    if (terrain_field(name) >= 0) {
+        if (!e || !e->tcur) return fail(-1, std::string("field ") + name + " exists only with the terrain curriculum (terrain.curriculum: true)");
+        if (comps) *comps = 1;
+        if (is_int) *is_int = 1;
+        return 0;
+    }
     const FieldInfo* f = name ? find_field(name) : nullptr;
     if (!f) return fail(-1, std::string("unknown field: ") + (name ? name : "(null)"));
     if (comps) *comps = f->comps;
@@ -897,6 +928,11 @@ extern "C" int bg_env_get_field(bg_env* e, const char* name, void* dst, void* st
     if (!e || !dst) return fail(-1, "bg_env_get_field: null argument");
     if (name && strcmp(name, "episode_stats") == 0) {  // global accumulator, STATS_COUNT floats
         HIP_OK(hipMemcpyAsync(dst, e->stats, sizeof(float) * STATS_COUNT, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return 0;
+    }
+    if (const int tf = terrain_field(name); tf >= 0) {
+        if (!e->tcur) return fail(-1, std::string("field ") + name + " exists only with the terrain curriculum (terrain.curriculum: true)");
+        HIP_OK(hipMemcpyAsync(dst, e->tcur + (size_t)tf * e->n, sizeof(int32_t) * e->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
         return 0;
     }
     const FieldInfo* f = name ? find_field(name) : nullptr;
@@ -910,6 +946,11 @@ extern "C" int bg_env_set_field(bg_env* e, const char* name, const void* src, vo
     if (!e || !src) return fail(-1, "bg_env_set_field: null argument");
     if (name && strcmp(name, "episode_stats") == 0) {
         HIP_OK(hipMemcpyAsync(e->stats, src, sizeof(float) * STATS_COUNT, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return 0;
+    }
+    if (const int tf = terrain_field(name); tf >= 0) {  // (the level sum is NOT updated: bg_env_set_terrain_level_sum)
+        if (!e->tcur) return fail(-1, std::string("field ") + name + " exists only with the terrain curriculum (terrain.curriculum: true)");
+        HIP_OK(hipMemcpyAsync(e->tcur + (size_t)tf * e->n, src, sizeof(int32_t) * e->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
         return 0;
     }
     const FieldInfo* f = name ? find_field(name) : nullptr;
@@ -933,6 +974,18 @@ extern "C" int bg_env_set_curriculum(bg_env* e, const float* prob, void* stream)
     if (!e || !prob) return fail(-1, "bg_env_set_curriculum: null argument");
     HIP_OK(hipMemcpyAsync(e->curr, prob, sizeof(float) * e->curr_cells, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     HIP_OK(hipMemcpyAsync(e->curr_read, prob, sizeof(float) * e->curr_cells, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+extern "C" int bg_env_get_terrain_level_sum(bg_env* e, int32_t* sum, void* stream) {
+    if (!e || !sum) return fail(-1, "bg_env_get_terrain_level_sum: null argument");
+    if (!e->tcur) return fail(-1, "bg_env_get_terrain_level_sum: the env has no terrain curriculum");
+    HIP_OK(hipMemcpyAsync(sum, e->tcur + 2 * (size_t)e->n, sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+extern "C" int bg_env_set_terrain_level_sum(bg_env* e, const int32_t* sum, void* stream) {
+    if (!e || !sum) return fail(-1, "bg_env_set_terrain_level_sum: null argument");
+    if (!e->tcur) return fail(-1, "bg_env_set_terrain_level_sum: the env has no terrain curriculum");
+    HIP_OK(hipMemcpyAsync(e->tcur + 2 * (size_t)e->n, sum, sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 extern "C" int64_t bg_env_step_count(const bg_env* e) { return e ? e->step_count : -1; }

@@ -24,6 +24,10 @@ from .base_task import BaseTask
 from .mirror import mirror_maps
 
 
+# third entropy word of the initial terrain-level generator (seeded with basic.seed and basic.rank)
+TERRAIN_LEVEL_STREAM = 0x7E44A1
+
+
 def _draw(rng, shape, params):
     """Set-up time randomisation on numpy arrays: returns (noise_value, raw_draw) or (None, None) when disabled."""
     if params is None:
@@ -132,6 +136,14 @@ class T1(BaseTask):
             spacing = self.cfg["env"]["env_spacing"]
             origins[:, 0] = spacing * xx.flatten()[:N]
             origins[:, 1] = spacing * yy.flatten()[:N]
+        elif self.terrain.curriculum:
+            # legged_gym's _get_env_origins: env i on column floor(i / (N / num_terrains)), on a level uniform in [0, max_init_level] drawn from a
+            # generator of its own (no draw of self._rng moves), at the centre of its tile
+            t = self.terrain
+            cols = np.minimum(np.floor(np.arange(N) / (N / self.cfg["terrain"]["num_terrains"])), self.cfg["terrain"]["num_terrains"] - 1)
+            lrng = np.random.default_rng([int(self.cfg["basic"].get("seed", 0)), int(self.cfg["basic"].get("rank", 0)), TERRAIN_LEVEL_STREAM])
+            self._terrain_init = (lrng.integers(0, t.max_init_level + 1, size=N).astype(np.int32), cols.astype(np.int32))
+            origins = t.tile_centres(*self._terrain_init)
         else:
             t = self.terrain
             num_cols = max(1.0, np.floor(np.sqrt(N * t.env_length / t.env_width)))
@@ -254,6 +266,10 @@ class T1(BaseTask):
         else:
             c.terrain_type = 1
             c.terrain_env_width, c.terrain_env_length, c.terrain_border = self.terrain.env_width, self.terrain.env_length, self.terrain.border_size
+            if self.terrain.curriculum:
+                c.terrain_curriculum, c.terrain_num_levels = 1, self.terrain.num_levels
+                c.terrain_tile_width, c.terrain_tile_length = self.terrain.terrain_width, self.terrain.terrain_length
+                c.terrain_down_time = 0.5 * float(rw["episode_length_s"])
         sd = str(cfg["sim"].get("state_dtype", "fp32")).lower()
         if sd not in ("fp32", "float32", "fp16", "float16", "half"):
             raise ValueError(f"sim.state_dtype must be fp32 or fp16, got {sd!r}")
@@ -328,6 +344,10 @@ class T1(BaseTask):
         _lib.check(lib.bg_env_bind_outputs(eh, _lib.ptr(self.obs_buf), _lib.ptr(self.privileged_obs_buf), _lib.ptr(self.rew_buf),
                                            _lib.ptr(self.reset_buf), _lib.ptr(self.time_out_buf), _lib.ptr(self._rew_terms)),
                    "bg_env_bind_outputs")
+        if self.terrain.curriculum:
+            self._tlevel_sum = torch.zeros(1, dtype=torch.int32, device=self.device)  # where terrain_level_sum() leaves the device's running sum
+            self.set_field("terrain_type", torch.from_numpy(self._terrain_init[1]))
+            self.terrain_levels = torch.from_numpy(self._terrain_init[0])
         self.extras["privileged_obs"] = self.privileged_obs_buf
         self.extras["time_outs"] = self.time_out_buf
         for name in self.reward_names:
@@ -452,6 +472,47 @@ class T1(BaseTask):
         ang = self.get_field("env_curriculum_level_ang").abs().float()
         self.mean_lin_vel_level, self.mean_ang_vel_level = float(lin.mean()), float(ang.mean())
         self.max_lin_vel_level, self.max_ang_vel_level = float(lin.max()), float(ang.max())
+
+    # ---- terrain curriculum state (legged_gym's terrain_levels / terrain_types / max_terrain_level; terrain.curriculum: true only)
+    @property
+    def max_terrain_level(self):
+        return self.terrain.num_levels
+
+    @property
+    def terrain_types(self):
+        return self.get_field("terrain_type").squeeze(-1)
+
+    @property
+    def terrain_levels(self):
+        return self.get_field("terrain_level").squeeze(-1)
+
+    @terrain_levels.setter
+    def terrain_levels(self, value):
+        """Set every env's level; its origin becomes the centre of its new tile and the running level sum is recomputed (a restore, a test)."""
+        lv = torch.as_tensor(value).to(torch.int64).reshape(self.num_envs).cpu().numpy()
+        if lv.min() < 0 or lv.max() >= self.terrain.num_levels:
+            raise ValueError(f"terrain levels must lie in [0, {self.terrain.num_levels - 1}]")
+        self.set_field("terrain_level", torch.from_numpy(lv.astype(np.int32)))
+        self.set_field("env_origins", torch.from_numpy(self.terrain.tile_centres(lv, self.terrain_types.cpu().numpy())).float())
+        s = torch.tensor([int(lv.sum())], dtype=torch.int32, device=self.device)
+        _lib.check(self._lib.bg_env_set_terrain_level_sum(self._env, _lib.ptr(s), _lib.current_stream_ptr()), "bg_env_set_terrain_level_sum")
+        torch.cuda.current_stream().synchronize()
+
+    def terrain_level_sum(self):
+        """int32 [1] device tensor: the sum of all envs' levels as the env steps keep it (enqueued copy, no host sync); overwritten by the next call."""
+        _lib.check(self._lib.bg_env_get_terrain_level_sum(self._env, _lib.ptr(self._tlevel_sum), _lib.current_stream_ptr()), "bg_env_get_terrain_level_sum")
+        return self._tlevel_sum
+
+    @property
+    def env_origins(self):
+        """[N][3] origins; with the terrain curriculum the device's (they move with the levels), otherwise the set-up tensor."""
+        if self._env is not None and self.terrain.curriculum:
+            return self.get_field("env_origins")
+        return self._env_origins
+
+    @env_origins.setter
+    def env_origins(self, value):
+        self._env_origins = value
 
     @property
     def root_states(self):

@@ -434,6 +434,14 @@ class Runner:
             self.env.curriculum_prob = model_dict["curriculum"]
         except Exception as e:
             print(f"Failed to load curriculum: {e}")
+        if self.env.terrain.curriculum:  # the levels (their origins and sum follow); a checkpoint without them, or of another env count, keeps the initial draw
+            try:
+                lv = model_dict["terrain_levels"]
+                if tuple(lv.shape) != (self.env.num_envs,):
+                    raise ValueError(f"shape {tuple(lv.shape)}, the env has {self.env.num_envs} envs")
+                self.env.terrain_levels = lv
+            except Exception as e:
+                print(f"Failed to load terrain levels: {e!r}")
         try:
             self.optimizer.load_state_dict(model_dict["optimizer"])
         except Exception as e:
@@ -451,7 +459,10 @@ class Runner:
                 tr.mirror_fresh = False
 
     def checkpoint_dict(self):
-        return {"model": self.model.state_dict(), "optimizer": self.optimizer.state_dict(), "curriculum": self.env.curriculum_prob}
+        d = {"model": self.model.state_dict(), "optimizer": self.optimizer.state_dict(), "curriculum": self.env.curriculum_prob}
+        if self.env.terrain.curriculum:
+            d["terrain_levels"] = self.env.terrain_levels
+        return d
 
     # ------------------------------------------------------------------ one PPO iteration
     def _resolve_plan(self):
@@ -828,7 +839,8 @@ class Runner:
         obs, infos = self.env.reset()
         self.buffer["obses"][0].copy_(obs)
         self.buffer["privileged_obses"][0].copy_(infos["privileged_obs"])
-        n = 2 * self._n_stats + 1 + 4 + _lib.NUM_REWARD_TERMS + 4
+        # (+1 with the terrain curriculum: the sum of this rank's terrain levels)
+        n = 2 * self._n_stats + 1 + 4 + _lib.NUM_REWARD_TERMS + 4 + (1 if self.env.terrain.curriculum else 0)
         self._log_dev = torch.zeros(n, dtype=torch.float64, device=self.device)
         self._log_host = [torch.zeros(n, dtype=torch.float64).pin_memory() for _ in range(2)]
         self._log_event = [torch.cuda.Event() for _ in range(2)]
@@ -847,11 +859,13 @@ class Runner:
         ne = 4 + _lib.NUM_REWARD_TERMS
         self.recorder.record_episode_statistics(self.env, self.env.reward_names, it, stats=s[h : h + ne])
         self.nonfinite_resets_total += s[h + ne - 1]
-        lv = s[h + ne :]
+        lv = s[h + ne : h + ne + 4]
         if self.cfg["commands"].get("curriculum", False):
             self.env.mean_lin_vel_level, self.env.mean_ang_vel_level, self.env.max_lin_vel_level, self.env.max_ang_vel_level = lv
         summary.update({"curriculum/mean_lin_vel_level": self.env.mean_lin_vel_level, "curriculum/mean_ang_vel_level": self.env.mean_ang_vel_level,
                         "curriculum/max_lin_vel_level": self.env.max_lin_vel_level, "curriculum/max_ang_vel_level": self.env.max_ang_vel_level})
+        if self.env.terrain.curriculum:  # this rank's envs only under data parallelism
+            summary["terrain/mean_level"] = s[h + ne + 4] / self.env.num_envs
         self.recorder.record_statistics(summary, it)
 
     def train_iteration(self, it):
@@ -866,7 +880,9 @@ class Runner:
         if self.cfg["commands"].get("curriculum", False):
             lin = self.env.get_field("env_curriculum_level_lin").abs().double()
             ang = self.env.get_field("env_curriculum_level_ang").abs().double()
-            d[h + ne :].copy_(torch.stack((lin.mean(), ang.mean(), lin.max(), ang.max())))
+            d[h + ne : h + ne + 4].copy_(torch.stack((lin.mean(), ang.mean(), lin.max(), ang.max())))
+        if self.env.terrain.curriculum:
+            d[h + ne + 4 :].copy_(self.env.terrain_level_sum())
         self._flush_log()  # the previous iteration's scalars: their copy finished long ago
         slot = it & 1
         self._log_host[slot].copy_(d, non_blocking=True)

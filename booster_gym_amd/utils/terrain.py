@@ -58,11 +58,29 @@ def _pyramid_slope(width, length, hscale, vscale, slope, platform_size):
     return np.clip(hf, min(ref, 0), max(ref, 0)).astype(np.int16)
 
 
+def terrain_curriculum(terrain_cfg):
+    """(on, num_levels, max_init_level) of the terrain curriculum (terrain.curriculum / num_levels / max_init_level, additions of this build);
+    ValueError naming the offending key.  Off: one level, and the field is the one built without the keys."""
+    on = bool(terrain_cfg.get("curriculum", False))
+    if not on:
+        return False, 1, 0
+    if terrain_cfg["type"] == "plane":
+        raise ValueError('terrain.curriculum: true needs a height field, terrain.type is "plane"')
+    levels = int(terrain_cfg.get("num_levels", 10))
+    if levels < 1:
+        raise ValueError(f"terrain.num_levels must be at least 1, got {levels}")
+    init = int(terrain_cfg.get("max_init_level", 4))
+    if not 0 <= init <= levels - 1:
+        raise ValueError(f"terrain.max_init_level must lie in [0, num_levels - 1] = [0, {levels - 1}], got {init}")
+    return True, levels, init
+
+
 class Terrain:
     def __init__(self, device, terrain_cfg, seed=0):
         self.terrain_cfg = terrain_cfg
         self.device = device
         self.type = terrain_cfg["type"]
+        self.curriculum, self.num_levels, self.max_init_level = terrain_curriculum(terrain_cfg)
         if self.type == "plane":
             self.height_field_raw = None
         elif self.type == "trimesh":
@@ -71,31 +89,46 @@ class Terrain:
             raise ValueError(f"Invalid terrain type: {self.type}")
 
     def _create_heightfield(self, seed):
+        """Columns of `num_terrains` types along x; with the curriculum `num_levels` rows along y, tile (level l, column c) at the amplitudes
+        scaled by (l + 1) / num_levels (the top row is the field without the curriculum), generated level-major from the one seeded generator."""
         c = self.terrain_cfg
+        L = self.num_levels
+        self.terrain_width, self.terrain_length = c["terrain_width"], c["terrain_length"]
         self.env_width = c["num_terrains"] * c["terrain_width"]
-        self.env_length = c["terrain_length"]
+        self.env_length = L * c["terrain_length"]
         self.border_size = c["border_size"]
         self.horizontal_scale = c["horizontal_scale"]
         self.vertical_scale = c["vertical_scale"]
         self.border_pixels = int(self.border_size / self.horizontal_scale)
         wpx, lpx = int(c["terrain_width"] / self.horizontal_scale), int(c["terrain_length"] / self.horizontal_scale)
-        hf = np.zeros((c["num_terrains"] * wpx + 2 * self.border_pixels, lpx + 2 * self.border_pixels), dtype=np.int16)
+        hf = np.zeros((c["num_terrains"] * wpx + 2 * self.border_pixels, L * lpx + 2 * self.border_pixels), dtype=np.int16)
         props = np.asarray(c["terrain_proportions"], dtype=np.float64)
         bounds = c["num_terrains"] * np.cumsum(props) / np.sum(props)
         rng = np.random.default_rng(seed)
-        for i in range(c["num_terrains"]):
-            if i < bounds[0]:
-                sub = np.zeros((wpx, lpx), dtype=np.int16)
-            elif i < bounds[1]:
-                sub = _pyramid_slope(wpx, lpx, self.horizontal_scale, self.vertical_scale, c["slope"], 3.0)
-            elif i < bounds[2]:
-                sub = _random_uniform(rng, wpx, lpx, self.horizontal_scale, self.vertical_scale, -0.5 * c["random_height"],
-                                      0.5 * c["random_height"], 0.005, 0.2)
-            else:
-                sub = _discrete_obstacles(rng, wpx, lpx, self.horizontal_scale, self.vertical_scale, c["discrete_height"], 1.0, 2.0, 20, 3.0)
-            x0 = self.border_pixels + i * wpx
-            hf[x0 : x0 + wpx, self.border_pixels : self.border_pixels + lpx] = sub
+        for lv in range(L):
+            k = (lv + 1) / L  # 1.0 exactly on the top level (and without the curriculum)
+            for i in range(c["num_terrains"]):
+                if i < bounds[0]:
+                    sub = np.zeros((wpx, lpx), dtype=np.int16)
+                elif i < bounds[1]:
+                    sub = _pyramid_slope(wpx, lpx, self.horizontal_scale, self.vertical_scale, c["slope"] * k, 3.0)
+                elif i < bounds[2]:
+                    sub = _random_uniform(rng, wpx, lpx, self.horizontal_scale, self.vertical_scale, -0.5 * c["random_height"] * k,
+                                          0.5 * c["random_height"] * k, 0.005, 0.2)
+                else:
+                    sub = _discrete_obstacles(rng, wpx, lpx, self.horizontal_scale, self.vertical_scale, c["discrete_height"] * k, 1.0, 2.0, 20, 3.0)
+                x0, y0 = self.border_pixels + i * wpx, self.border_pixels + lv * lpx
+                hf[x0 : x0 + wpx, y0 : y0 + lpx] = sub
         self.height_field_raw = hf
+
+    def tile_centres(self, levels, columns):
+        """World (x, y, z) of the centres of tiles (level, column): the origins of the terrain curriculum."""
+        levels, columns = np.asarray(levels), np.asarray(columns)
+        out = np.zeros((len(levels), 3))
+        out[:, 0] = (columns + 0.5) * self.terrain_width
+        out[:, 1] = (levels + 0.5) * self.terrain_length
+        out[:, 2] = self.terrain_heights(out).cpu().numpy()
+        return out
 
     def terrain_heights(self, base_pos):
         """Bilinear height under world (x, y) -- reference terrain.py:101-121, indices clamped to the field."""

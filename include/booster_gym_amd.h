@@ -132,6 +132,14 @@ typedef struct {
      * normal stiffness [N/m] and damping [N s/m], Coulomb coefficient, and the viscous cap [N s/m] of the regularised friction. */
     int32_t self_collisions;
     float self_k, self_d, self_mu, self_visc;
+    /* Terrain curriculum (T1.yaml terrain.curriculum; an addition of this build, legged_gym's rule).  0 = off: nothing below is read and no
+     * per-env level is kept.  1 = the height field holds terrain_num_levels rows of terrain_tile_length along y (difficulty (l + 1) / levels)
+     * by the type columns of terrain_tile_width along x; every env has a level and a fixed column, and at each reset of an env step (not
+     * bg_env_reset) its level moves up when the robot walked farther than terrain_tile_length / 2 from its origin, down when it walked less than
+     * |command xy| * terrain_down_time (rewards.episode_length_s / 2), wraps to a random level past the top, and the origin becomes the centre
+     * of the env's new tile.  Levels / columns: fields "terrain_level" / "terrain_type"; their running sum: bg_env_get/set_terrain_level_sum. */
+    int32_t terrain_curriculum, terrain_num_levels;
+    float terrain_tile_width, terrain_tile_length, terrain_down_time;
 } bg_env_cfg;
 
 /* ---- model (replaces gym.load_asset and the asset queries, t1.py:54-108) */
@@ -193,6 +201,10 @@ int bg_env_field_info(bg_env* env, const char* name, int32_t* components, int32_
  * get returns min(sum, 1). */
 int bg_env_get_curriculum(bg_env* env, float* prob_device, void* stream);
 int bg_env_set_curriculum(bg_env* env, const float* prob_device, void* stream);
+/* terrain curriculum (cfg.terrain_curriculum = 1 only, else -1): the sum of all envs' levels, one int32 at a device pointer, kept by the env
+ * step's resets with one atomic add per change (no reduction launch).  The setter is for restores that write "terrain_level" directly. */
+int bg_env_get_terrain_level_sum(bg_env* env, int32_t* sum_device, void* stream);
+int bg_env_set_terrain_level_sum(bg_env* env, const int32_t* sum_device, void* stream);
 int64_t bg_env_step_count(const bg_env* env);
 int bg_env_set_step_count(bg_env* env, int64_t count);
 

@@ -53,6 +53,8 @@ for it in range(iters):
                         "grid_cells_positive": int((g > 0).sum()), "grid_sum": round(float(g.sum()), 2),
                         "episodes_ended": ended, "share_long_enough_for_success": round(long_enough / max(ended, 1), 4)})
             ended = long_enough = 0
+        if r.env.terrain.curriculum:  # terrain.curriculum=true: where the envs stand on the levels
+            row["terrain/mean_level"] = round(float(r.env.terrain_levels.double().mean()), 3)
         hist.append(row); print(json.dumps(row), flush=True)
 os.makedirs("gpurun_out", exist_ok=True)
 torch.save(r.checkpoint_dict(), "gpurun_out/train_probe.pth")
