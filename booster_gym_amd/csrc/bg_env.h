@@ -85,11 +85,12 @@ struct EnvDev {
 
 struct StepOut {
     float* obs;      // [N][47]
-    float* priv;     // [N][14]
+    float* priv;     // [N][priv_stride]: columns 0..13 from the env step; 14.. the height scan (bg_height_scan), when there is one
     float* rew;      // [N]
     uint8_t* done;   // [N]
     uint8_t* tout;   // [N]
     float* terms;    // [26][N] or null
+    int priv_stride; // floats per privileged row: 14 + cfg.height_scan_points
 };
 
 BG_HD float apply_rand(float x, const bg_rand& r, float u, float nrm) {

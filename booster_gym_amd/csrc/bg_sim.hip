@@ -42,6 +42,7 @@ struct bg_env {
     float* curr_read = nullptr;
     int curr_cells = 0;
     int32_t* tcur = nullptr;  // terrain curriculum: [n] levels, [n] columns, [1] level sum (cfg.terrain_curriculum only)
+    float* scan_xy = nullptr; // height scan: [P][2] points in the robot's yaw frame (cfg.height_scan_points > 0 only)
     ModelDev* model_dev = nullptr;
     PairModel* pair_dev = nullptr;  // the leg constants with the two legs side by side (packed ABA kernel)
     int16_t* hf = nullptr;
@@ -93,7 +94,7 @@ __device__ __forceinline__ void copy_out_rows(const StepOut& out, int e0, int ro
     for (int r = 0; r < rows; r++) {
         if (!((mask >> r) & 1u)) continue;
         if (lane < BG_NUM_OBS) out.obs[(size_t)(e0 + r) * BG_NUM_OBS + lane] = s_obs[r * BG_NUM_OBS + lane];
-        if (lane < BG_NUM_PRIV) out.priv[(size_t)(e0 + r) * BG_NUM_PRIV + lane] = s_priv[r * BG_NUM_PRIV + lane];
+        if (lane < BG_NUM_PRIV) out.priv[(size_t)(e0 + r) * out.priv_stride + lane] = s_priv[r * BG_NUM_PRIV + lane];
     }
 }
 
@@ -123,11 +124,15 @@ __global__ __launch_bounds__(64) void env_step_kernel(EnvDev E, const float* __r
     const int rows = min(ENVS_PER_BLOCK, E.n - e0);
     const unsigned lowm = s_low;
     if (lowm == 0u) {
-        // coalesced copy-out of the block's 32 observation rows (contiguous in the [N][47] / [N][14] outputs)
+        // coalesced copy-out of the block's 32 observation rows (contiguous in the [N][47] output; in the privileged output [N][priv_stride] the
+        // first 14 columns of each row, contiguous without the height scan)
         float* go = out.obs + (size_t)e0 * BG_NUM_OBS;
         for (int k = lane; k < rows * BG_NUM_OBS; k += 64) go[k] = s_obs[k];
-        float* gp = out.priv + (size_t)e0 * BG_NUM_PRIV;
-        for (int k = lane; k < rows * BG_NUM_PRIV; k += 64) gp[k] = s_priv[k];
+        float* gp = out.priv + (size_t)e0 * out.priv_stride;
+        for (int k = lane; k < rows * BG_NUM_PRIV; k += 64) {
+            const int r = k / BG_NUM_PRIV;
+            gp[(size_t)r * out.priv_stride + (k - r * BG_NUM_PRIV)] = s_priv[k];
+        }
     } else {
         copy_out_rows(out, e0, rows, ~lowm, s_obs, s_priv);
     }
@@ -156,6 +161,30 @@ __global__ __launch_bounds__(64) void env_step_body_kernel(EnvDev E, const float
         copy_out_rows(out, e0, min(ENVS_PER_BLOCK, E.n - e0), lowm, s_obs, s_priv);
         __syncthreads();
     }
+}
+
+// ------------------------------------------------------------------ terrain height scan of the critic (cfg.height_scan_points > 0)
+// legged_gym's measured heights: one thread per (env, point), the points of a row on consecutive lanes, so that the launch stores every privileged
+// row's scan columns [14, 14 + P) as runs of whole lines.  Reads the stored base position (fp32) and orientation (fp16 slab with state_fp16) after the
+// env step; the height field (int16, ~2 MB with the terrain curriculum) stays in L2 / MALL.  A launch of its own: inside the latency-bound env-step
+// kernel the P values per env would need LDS staging and cost its occupancy.
+constexpr int SCAN_BLOCK = 256;
+template <bool H16>
+__global__ __launch_bounds__(SCAN_BLOCK) void bg_height_scan(EnvDev E, const float2* __restrict__ pts, int P, float* __restrict__ priv, int stride) {
+    const unsigned t = blockIdx.x * SCAN_BLOCK + threadIdx.x;  // (n P < 2^31: bg_env_create)
+    if (t >= (unsigned)E.n * (unsigned)P) return;
+    const int e = (int)(t / (unsigned)P), p = (int)(t - (unsigned)e * (unsigned)P);
+    const int n = E.n;
+#define SFLD(off) field_ref<H16>(E.f, E.h, (off), n, e)
+    const float bx = SFLD(F_ROOT + 0), by = SFLD(F_ROOT + 1), bz = SFLD(F_ROOT + 2);
+    const float q[4] = {SFLD(F_ROOT + 3), SFLD(F_ROOT + 4), SFLD(F_ROOT + 5), SFLD(F_ROOT + 6)};
+#undef SFLD
+    float s, c;
+    bg_sincos(quat_yaw(q), &s, &c);
+    const float2 pt = pts[p];
+    const float h = terrain_height(E.terrain, bx + c * pt.x - s * pt.y, by + s * pt.x + c * pt.y);
+    const float v = fminf(fmaxf(bz - h - E.cfg.base_height_target, -1.f), 1.f);
+    priv[(size_t)e * stride + BG_NUM_PRIV + p] = v * E.cfg.height_scan_scale;
 }
 
 // ------------------------------------------------------------------ reference-exact command resampling (cfg.exact_still_count / same_step_curriculum)
@@ -709,6 +738,12 @@ static int env_create_fill(bg_env* e, const bg_env_cfg* cfg, const bg_model* mod
     HIP_OK(hipMemcpy(e->pair_dev, &pmh, sizeof(pmh), hipMemcpyHostToDevice));
     e->terrain.type = 0; e->terrain.rows = e->terrain.cols = e->terrain.border_px = 0; e->terrain.inv_hscale = 1.f; e->terrain.vscale = 0.f; e->terrain.hf = nullptr;
     memset(&e->bound, 0, sizeof(e->bound));
+    e->bound.priv_stride = BG_NUM_PRIV + cfg->height_scan_points;
+    e->cfg.height_scan_xy = nullptr;  // (the caller's host array: read here, never kept)
+    if (cfg->height_scan_points > 0) {
+        HIP_OK(hipMalloc(&e->scan_xy, sizeof(float) * 2 * cfg->height_scan_points));
+        HIP_OK(hipMemcpy(e->scan_xy, cfg->height_scan_xy, sizeof(float) * 2 * cfg->height_scan_points, hipMemcpyHostToDevice));
+    }
     // defaults: unit mass scale / compliance, identity orientation, nominal friction
     std::vector<float> host(n * F_COUNT, 0.f);
     for (size_t k = 0; k < n; k++) {
@@ -749,6 +784,8 @@ extern "C" int bg_env_create(const bg_env_cfg* cfg, const bg_model* model, bg_en
         return fail(-1, "bg_env_create: curriculum levels out of range");
     if (cfg->terrain_curriculum && (cfg->terrain_type == 0 || cfg->terrain_num_levels < 1 || !(cfg->terrain_tile_width > 0.f) || !(cfg->terrain_tile_length > 0.f)))
         return fail(-1, "bg_env_create: the terrain curriculum needs a height field of at least one level and positive tile sizes");
+    if (cfg->height_scan_points < 0 || cfg->height_scan_points > BG_MAX_HEIGHT_SCAN_POINTS || (cfg->height_scan_points > 0 && (cfg->terrain_type == 0 || !cfg->height_scan_xy || (int64_t)cfg->num_envs * cfg->height_scan_points >= (int64_t)1 << 31)))
+        return fail(-1, "bg_env_create: the height scan needs a height field and 1 .. BG_MAX_HEIGHT_SCAN_POINTS points");
     int ndev = 0;
     hipError_t de = hipGetDeviceCount(&ndev);
     if (de != hipSuccess || ndev == 0) return fail(-3, "bg_env_create: no HIP device available (this library has no CPU path)");
@@ -767,7 +804,7 @@ extern "C" int bg_env_create(const bg_env_cfg* cfg, const bg_model* model, bg_en
 extern "C" void bg_env_destroy(bg_env* e) {
     if (!e) return;
     (void)hipFree(e->sim_tau); (void)hipFree(e->sim_bforce); (void)hipFree(e->sim_btorque);
-    (void)hipFree(e->f); (void)hipFree(e->h); (void)hipFree(e->lowmask); (void)hipFree(e->fd_mask); (void)hipFree(e->fd_list); (void)hipFree(e->fd_count); (void)hipFree(e->rs_counts); (void)hipFree(e->i); (void)hipFree(e->stats); (void)hipFree(e->model_dev); (void)hipFree(e->pair_dev); (void)hipFree(e->hf); (void)hipFree(e->curr); (void)hipFree(e->curr_read); (void)hipFree(e->tcur);
+    (void)hipFree(e->f); (void)hipFree(e->h); (void)hipFree(e->lowmask); (void)hipFree(e->fd_mask); (void)hipFree(e->fd_list); (void)hipFree(e->fd_count); (void)hipFree(e->rs_counts); (void)hipFree(e->i); (void)hipFree(e->stats); (void)hipFree(e->model_dev); (void)hipFree(e->pair_dev); (void)hipFree(e->hf); (void)hipFree(e->curr); (void)hipFree(e->curr_read); (void)hipFree(e->tcur); (void)hipFree(e->scan_xy);
     delete e;
 }
 
@@ -847,6 +884,12 @@ static int launch_step(bg_env* e, const float* actions, int mode, const StepOut&
         hipLaunchKernelGGL(resample_count_kernel, dim3(nb), dim3(RS_BLOCK), 0, st, env_dev(e), e->rs_counts);
         hipLaunchKernelGGL(resample_offsets_kernel, dim3(1), dim3(RS_BLOCK), 0, st, e->rs_counts, nb);
         hipLaunchKernelGGL(resample_apply_kernel, dim3(nb), dim3(RS_BLOCK), 0, st, env_dev(e), (const int*)e->rs_counts, nb, cnt, mode, out.obs);
+    }
+    if (e->scan_xy) {  // the critic's height scan from the state this launch sequence has just stored (bg_height_scan)
+        const int P = e->cfg.height_scan_points;
+        dim3 gs((unsigned)(((int64_t)e->n * P + SCAN_BLOCK - 1) / SCAN_BLOCK));
+        if (e->h) hipLaunchKernelGGL(bg_height_scan<true>, gs, dim3(SCAN_BLOCK), 0, st, env_dev(e), (const float2*)e->scan_xy, P, out.priv, out.priv_stride);
+        else hipLaunchKernelGGL(bg_height_scan<false>, gs, dim3(SCAN_BLOCK), 0, st, env_dev(e), (const float2*)e->scan_xy, P, out.priv, out.priv_stride);
     }
     HIP_OK(hipGetLastError());
     if (e->cfg.curriculum && mode == 0)  // publish this step's curriculum increments to the next step's samplers

@@ -26,6 +26,23 @@ from .mirror import mirror_maps
 
 # third entropy word of the initial terrain-level generator (seeded with basic.seed and basic.rank)
 TERRAIN_LEVEL_STREAM = 0x7E44A1
+# observations + privileged observations + height scan the critic may take: its first layer's padded input on the per-layer kernels (bg_mlp.hip)
+MAX_CRITIC_INPUT = 512
+
+
+def check_env_sizes(cfg, num_height_points):
+    """ValueError unless env.num_observations / num_privileged_obs / num_actions are what this build computes: 47, 14 (+ P with the terrain height scan's
+    P points: legged_gym requires num_observations to match what the env computes) and 12; and 47 + 14 + P within MAX_CRITIC_INPUT."""
+    env, P = cfg["env"], num_height_points
+    no, npv, na = env["num_observations"], env["num_privileged_obs"], env["num_actions"]
+    if P and no + _lib.NUM_PRIV + P > MAX_CRITIC_INPUT:
+        raise ValueError(f"terrain.measured_points_x x terrain.measured_points_y = {P} points: the critic's input {no} + {_lib.NUM_PRIV} + {P} "
+                         f"exceeds {MAX_CRITIC_INPUT} (the widest first layer of the kernels)")
+    if P and npv != _lib.NUM_PRIV + P:
+        raise ValueError(f"env.num_privileged_obs = {npv}, but terrain.measure_heights with {P} points computes {_lib.NUM_PRIV} + {P} = "
+                         f"{_lib.NUM_PRIV + P} privileged observations: set env.num_privileged_obs to {_lib.NUM_PRIV + P}")
+    if (no, npv - P, na) != (_lib.NUM_OBS, _lib.NUM_PRIV, _lib.NUM_DOFS):
+        raise ValueError("this build computes 47 observations, 14 privileged observations and 12 actions (envs/T1.yaml env.*)")
 
 
 def _draw(rng, shape, params):
@@ -49,6 +66,7 @@ def _apply(x, params, rng, return_raw=False):
 class T1(BaseTask):
     def __init__(self, cfg):
         super().__init__(cfg)
+        check_env_sizes(cfg, len(self.terrain.height_points))  # (before anything touches the device)
         self._lib = _lib.load()
         self._model = None
         self._env = None
@@ -160,8 +178,9 @@ class T1(BaseTask):
         self.num_obs = cfg["env"]["num_observations"]
         self.num_privileged_obs = cfg["env"]["num_privileged_obs"]
         self.num_actions = cfg["env"]["num_actions"]
-        if (self.num_obs, self.num_privileged_obs, self.num_actions) != (_lib.NUM_OBS, _lib.NUM_PRIV, _lib.NUM_DOFS):
-            raise ValueError("this build computes 47 observations, 14 privileged observations and 12 actions (envs/T1.yaml env.*)")
+        # the critic's terrain height scan (terrain.measure_heights): P more privileged columns after the 14 (checked in __init__)
+        P = self.num_height_points = len(self.terrain.height_points)
+        self.height_points = torch.tensor(self.terrain.height_points, dtype=torch.float, device=self.device).reshape(P, 2)
         self.dt = cfg["control"]["decimation"] * cfg["sim"]["dt"]
         N, dev = self.num_envs, self.device
         self.obs_buf = torch.zeros(N, self.num_obs, dtype=torch.float, device=dev)
@@ -270,6 +289,10 @@ class T1(BaseTask):
                 c.terrain_curriculum, c.terrain_num_levels = 1, self.terrain.num_levels
                 c.terrain_tile_width, c.terrain_tile_length = self.terrain.terrain_width, self.terrain.terrain_length
                 c.terrain_down_time = 0.5 * float(rw["episode_length_s"])
+            if self.num_height_points:  # (bg_env_create copies the points; the array need not outlive the call)
+                self._scan_xy = np.ascontiguousarray(self.terrain.height_points, dtype=np.float32)
+                c.height_scan_points, c.height_scan_xy = self.num_height_points, self._scan_xy.ctypes.data
+                c.height_scan_scale = float(nz.get("height_measurements", 5.0))
         sd = str(cfg["sim"].get("state_dtype", "fp32")).lower()
         if sd not in ("fp32", "float32", "fp16", "float16", "half"):
             raise ValueError(f"sim.state_dtype must be fp32 or fp16, got {sd!r}")
@@ -395,6 +418,8 @@ class T1(BaseTask):
         for t in (obs, privileged_obs, rew, done, time_outs):
             if not (t.is_cuda and t.is_contiguous()):
                 raise RuntimeError("step_to needs contiguous CUDA output tensors")
+        if privileged_obs.numel() < self.num_envs * self.num_privileged_obs:  # (rows of 14 + P with the height scan)
+            raise RuntimeError(f"step_to needs privileged_obs of {self.num_envs} x {self.num_privileged_obs} floats")
         _lib.check(self._lib.bg_env_step_to(self._env, _lib.ptr(a), _lib.ptr(obs), _lib.ptr(privileged_obs), _lib.ptr(rew), _lib.ptr(done),
                                             _lib.ptr(time_outs), _lib.current_stream_ptr()), "bg_env_step_to")
         if self._stale_tout:

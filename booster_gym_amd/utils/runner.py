@@ -75,6 +75,18 @@ def hidden_widths(cfg):
     return check_hidden(alg.get("actor_hidden", ACTOR_HIDDEN), alg.get("critic_hidden", CRITIC_HIDDEN), split)
 
 
+INPUT_PADS = (64, 128, 256, 512)  # first-layer inputs of the per-layer fused kernels (bg_mlp.hip); the chained kernels take 64 only
+
+
+def pad_input(width):
+    """The zero-padded input width of a network whose input has `width` features: the next of 64, 128, 256, 512 (actor 47 -> 64; critic 61 -> 64,
+    61 + 187 = 248 -> 256 with the default height scan); ValueError beyond 512."""
+    for p in INPUT_PADS:
+        if width <= p:
+            return p
+    raise ValueError(f"a network input of {width} features exceeds the widest first layer of the kernels ({INPUT_PADS[-1]})")
+
+
 def symmetry_loss(cfg):
     """(on, coefficient) of the mirror-symmetry loss: algorithm.symmetry_loss (an addition of this build; absent = false) and the reference's
     algorithm.symmetric_coef, which the loss reads only when it is on."""
@@ -294,13 +306,19 @@ class Runner:
         self.buffer.add_buffer("time_outs", (), dtype=torch.bool)
         B, A = T * N, self.env.num_actions
         dev = self.device
-        # network inputs with the feature dimension zero-padded to 64 (47 -> 64, 61 -> 64) so that the first layers run on the fused MFMA kernel
-        self._pad_in = 64 if MLPTrainer.FUSED else None
-        self._critic_in = torch.zeros(T + 1, N, self._pad_in or (self.env.num_obs + self.env.num_privileged_obs), device=dev)
-        self._actor_in = torch.zeros(T, N, self._pad_in, device=dev) if self._pad_in else None
+        # network inputs with the feature dimension zero-padded, each network on its own (pad_input: actor 47 -> 64, critic 61 -> 64, or 61 + P -> 128 /
+        # 256 / 512 with the terrain height scan) so that the first layers run on the fused MFMA kernels
+        no, npv = self.env.num_obs, self.env.num_privileged_obs
+        self._pad_actor = pad_input(no) if MLPTrainer.FUSED else None
+        self._pad_critic = pad_input(no + npv) if MLPTrainer.FUSED else None
+        if self._pad_critic and self._pad_critic > 256 and (int((self.cfg.get("parallel", {}) or {}).get("gemm_split", 0) or 0) or MLPTrainer.SPLIT):
+            raise ValueError(f"parallel.gemm_split / BG_GEMM_SPLIT runs split-bf16 layer kernels that take layer inputs of 64, 128 or 256 columns only; the "
+                             f"critic's input {no} + {npv} pads to {self._pad_critic} (fewer terrain.measured_points_x / _y points, or gemm_split 0)")
+        self._critic_in = torch.zeros(T + 1, N, self._pad_critic or (no + npv), device=dev)
+        self._actor_in = torch.zeros(T, N, self._pad_actor, device=dev) if self._pad_actor else None
         if self._symmetry:
             # the actor's input of 2B rows: the batch, then its mirror images (bg_mirror_rows in update(); the padded columns stay zero)
-            kin = self._pad_in or self.env.num_obs
+            kin = self._pad_actor or self.env.num_obs
             self._actor_in = torch.zeros(2 * T, N, kin, device=dev)
             self._obs_mirror = (obs_src.tolist() + [-1] * (kin - len(obs_src)), obs_sign.tolist() + [1.0] * (kin - len(obs_sign)))
         self._adv = torch.zeros(T, N, device=dev)
@@ -365,7 +383,7 @@ class Runner:
         self._head_scratch_a, self._head_scratch_c = head_scratch(dev), head_scratch(dev)
         self._act_counter = 0
         # The forward passes of the first mini-epoch run DURING the rollout (see rollout()): 1 = on (default where the chained kernels apply), 0 = off
-        self._rollout_forward = os.environ.get("BG_ROLLOUT_FORWARD", "1") == "1" and self._pad_in is not None and N % 128 == 0
+        self._rollout_forward = os.environ.get("BG_ROLLOUT_FORWARD", "1") == "1" and self._pad_actor is not None and N % 128 == 0
         # ... the rows of this many consecutive steps per group of side-stream launches.  Every group costs the main stream one event record (2.9 us, 5.7
         # with a waiter on another queue: tools/event_cost_probe.py), and from four steps per group on the chained launches need more than the 128 CUs
         # the env step leaves idle and slow it down (110 against 102.5 us).  Same box, 20 iterations each, ms per iteration: off 24.78-24.92, one step
@@ -423,6 +441,11 @@ class Runner:
             self.cfg["basic"]["checkpoint"] = ck
         print("Loading model from {}".format(ck))
         model_dict = torch.load(ck, map_location=self.device, weights_only=True)
+        ck_in, c_in = int(model_dict["model"]["critic.0.weight"].shape[1]), self.model.critic[0].in_features
+        if ck_in != c_in:  # (the critic's input: observations + privileged observations, with the terrain height scan 14 + P of the latter)
+            raise ValueError(f"checkpoint {ck} has a critic of {ck_in} inputs, the config's critic takes {c_in} (env.num_observations + "
+                             f"env.num_privileged_obs): terrain.measure_heights and its measured_points_x / measured_points_y must be as in the run "
+                             "that saved the checkpoint")
         ck_a, ck_c = hidden_of(model_dict["model"], "actor"), hidden_of(model_dict["model"], "critic")
         if (ck_a, ck_c) != (self.actor_hidden, self.critic_hidden):
             raise ValueError(f"checkpoint {ck} has actor hidden widths {list(ck_a)} and critic hidden widths {list(ck_c)}, the config "

@@ -75,12 +75,36 @@ def terrain_curriculum(terrain_cfg):
     return True, levels, init
 
 
+# legged_gym's measured_points_x / measured_points_y: the default grid of the height scan, metres in the robot's yaw frame (17 x 11 = 187 points)
+MEASURED_POINTS_X = [round(-0.8 + 0.1 * i, 1) for i in range(17)]
+MEASURED_POINTS_Y = [round(-0.5 + 0.1 * j, 1) for j in range(11)]
+
+
+def height_scan_points(terrain_cfg):
+    """(on, points) of the critic's terrain height scan (terrain.measure_heights / measured_points_x / measured_points_y, legged_gym's names):
+    points float32 [P][2] in the robot's yaw frame, point p = i * len(y) + j at (x_i, y_j) (meshgrid "ij", flattened); [0][2] when off.
+    ValueError naming the offending key."""
+    if not bool(terrain_cfg.get("measure_heights", False)):
+        return False, np.zeros((0, 2), dtype=np.float32)
+    if terrain_cfg["type"] == "plane":
+        raise ValueError('terrain.measure_heights: true needs a height field, terrain.type is "plane"')
+    axes = []
+    for key, default in (("measured_points_x", MEASURED_POINTS_X), ("measured_points_y", MEASURED_POINTS_Y)):
+        v = np.asarray(terrain_cfg.get(key, default), dtype=np.float64).reshape(-1)
+        if v.size == 0:
+            raise ValueError(f"terrain.{key} is empty: terrain.measure_heights needs at least one point along each axis")
+        axes.append(v)
+    gx, gy = np.meshgrid(axes[0], axes[1], indexing="ij")
+    return True, np.stack([gx.reshape(-1), gy.reshape(-1)], axis=1).astype(np.float32)
+
+
 class Terrain:
     def __init__(self, device, terrain_cfg, seed=0):
         self.terrain_cfg = terrain_cfg
         self.device = device
         self.type = terrain_cfg["type"]
         self.curriculum, self.num_levels, self.max_init_level = terrain_curriculum(terrain_cfg)
+        self.measure_heights, self.height_points = height_scan_points(terrain_cfg)
         if self.type == "plane":
             self.height_field_raw = None
         elif self.type == "trimesh":

@@ -26,6 +26,7 @@ extern "C" {
 #define BG_NUM_PRIV 14
 #define BG_NUM_REWARD_TERMS 26
 #define BG_MAX_BODY_SPHERES 16
+#define BG_MAX_HEIGHT_SCAN_POINTS 1024 /* bg_env_cfg.height_scan_points */
 
 typedef struct bg_model bg_model;
 typedef struct bg_env bg_env;
@@ -140,6 +141,14 @@ typedef struct {
      * of the env's new tile.  Levels / columns: fields "terrain_level" / "terrain_type"; their running sum: bg_env_get/set_terrain_level_sum. */
     int32_t terrain_curriculum, terrain_num_levels;
     float terrain_tile_width, terrain_tile_length, terrain_down_time;
+    /* Terrain height scan of the critic (T1.yaml terrain.measure_heights; an addition of this build, legged_gym's measured heights).  0 points =
+     * off: nothing below is read and the privileged row is the 14 values.  P > 0 (a height field only): after every env step and reset-all, one
+     * more launch (bg_height_scan) writes columns 14 .. 14 + P of each privileged row [N][14 + P]:
+     *   clip(base z - h(base xy + Rz(yaw) (x_p, y_p)) - base_height_target, -1, 1) * height_scan_scale
+     * with h the bilinear ground height, yaw that of the stored base quaternion, no noise. */
+    int32_t height_scan_points;       /* P: points of the scan (0 = off) */
+    const float* height_scan_xy;      /* host float [P][2]: (x, y) of each point in the robot's yaw frame [m]; copied by bg_env_create */
+    float height_scan_scale;          /* normalization.height_measurements */
 } bg_env_cfg;
 
 /* ---- model (replaces gym.load_asset and the asset queries, t1.py:54-108) */
@@ -176,8 +185,8 @@ int bg_env_set_heightfield(bg_env* env, const int16_t* hf_host, int32_t rows, in
  * restitution), base_mass_scaled [N][4] (raw draws shown to the critic, t1.py:141-152), env_origins [N][3] (t1.py:169-185) */
 int bg_env_set_params(bg_env* env, const float* kp, const float* kd, const float* friction, const float* mass_scale, const float* com_offset,
                       const float* foot_material, const float* base_mass_scaled, const float* env_origins);
-/* outputs of reset/step, device pointers owned by the caller (torch tensors): obs [N][47], privileged [N][14],
- * rew [N], done uint8 [N], time_outs uint8 [N], rew_terms [26][N] (rows of dropped terms stay 0) */
+/* outputs of reset/step, device pointers owned by the caller (torch tensors): obs [N][47], privileged [N][14 + P] (P = cfg.height_scan_points,
+ * 0 without the height scan: [N][14]), rew [N], done uint8 [N], time_outs uint8 [N], rew_terms [26][N] (rows of dropped terms stay 0) */
 int bg_env_bind_outputs(bg_env* env, float* obs, float* privileged_obs, float* rew, uint8_t* done, uint8_t* time_outs, float* rew_terms);
 /* T1.reset(): t1.py:294-299 */
 int bg_env_reset(bg_env* env, void* stream);
