@@ -121,6 +121,7 @@ class EnvCfg(C.Structure):
         ("terrain_curriculum", C.c_int32), ("terrain_num_levels", C.c_int32), ("terrain_tile_width", C.c_float), ("terrain_tile_length", C.c_float),
         ("terrain_down_time", C.c_float),
         ("height_scan_points", C.c_int32), ("height_scan_xy", C.c_void_p), ("height_scan_scale", C.c_float),
+        ("frame_stack", C.c_int32),
     ]
 
 

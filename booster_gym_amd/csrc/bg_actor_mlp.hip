@@ -1,7 +1,7 @@
 // Fused actor MLP + Gaussian sample for the rollout at any supported architecture (reference utils/model.py:8-25 with the widths a user sets,
 // utils/runner.py:109-111: dist = model.act(obs); act = dist.sample()), fp32 MFMA, gfx950 only.  bg_actor_sample (bg_ppo.hip) keeps the
-// reference's widths built into its kernel; this one reads them from descriptors: 47 inputs, 2 to 4 hidden ELU layers of widths a multiple of 128
-// up to 512, 12 outputs.
+// reference's widths built into its kernel; this one reads them from descriptors: 47 H inputs (H = 1 .. 10 observation frames, env.frame_stack),
+// 2 to 4 hidden ELU layers of widths a multiple of 128 up to 512, 12 outputs.
 //
 // One workgroup (4 waves) = 16 observation rows.  The activations ping-pong between two LDS tiles [16][MAXW + 4]; each wave owns the 16-neuron
 // output tiles wave, wave + 4, ... of a layer and accumulates them with v_mfma_f32_16x16x4_f32 (exact fp32, D = A*B + C), operands as in
@@ -12,7 +12,10 @@
 // A wave walks its (tile, 128-wide k-chunk) steps in one flat loop and fetches the 8 weight vectors (+ the bias) of step s + 1 before it runs the
 // 32 MFMAs of step s, so the L2 latency hides under them whatever the widths.  Two accumulators per tile (even / odd k groups) keep the MFMA chain
 // from waiting on its own 40-cycle dependent latency.
+// The first layer reads the torch-layout rows [out][47 H] (16-byte aligned only when H % 4 == 0) with scalar loads, straight from the parameters
+// (no padded copy that could go stale), in k-chunks of 48 columns = 12 MFMAs, prefetched the same way; the input tile is zero beyond column 47 H.
 // LDS: 2 x 16 x 516 floats = 66 kB at MAXW = 512 (two workgroups per CU), 33 kB at MAXW = 256; 16 rows per workgroup: 256 workgroups at 4,096 rows.
+// The input tile [16][48 H] lives in the first activation tile, so 6 frames and more (288 columns and up) take the MAXW = 512 form.
 // The noise is bg_actor_sample's: the same bg::rand4(seed, row, counter, RS_ACTOR + g) draw per (row, group of 4 actions), the same expression.
 #include <hip/hip_runtime.h>
 
@@ -31,7 +34,7 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int MR = 16;         // rows per workgroup
 constexpr int MAX_LAYERS = 5;  // 4 hidden + the output layer
-constexpr int KIN = 48;        // the 47 observations padded with a zero column
+constexpr int KC = 48;         // k-chunk of the first layer: one frame's 47 observations and a column more (47 H <= 48 H: H chunks cover H frames)
 
 struct ActorNet {
     const float* W[MAX_LAYERS];
@@ -42,31 +45,39 @@ struct ActorNet {
 
 __device__ __forceinline__ float elu(float x) { return x > 0.f ? x : expm1f(x); }  // = bg_ppo.hip's
 
-// first layer: K = 47 (rows not 16-byte aligned): scalar weight loads, k padded to 48 with zeros; OUT a multiple of 16.  One step per tile.
+// first layer: K = 47 H inputs (rows not 16-byte aligned): scalar weight loads, k padded to a multiple of KC with zeros; OUT a multiple of 16.  A wave
+// walks its (tile, k-chunk) steps in one flat loop, the weights of step s + 1 in flight under the 12 MFMAs of step s; with H = 1 one step per tile.
 template <int LDA>
-__device__ __forceinline__ void first_layer(const float* __restrict__ W, const float* __restrict__ bv, int OUT, const float* in, float* out, int wave,
-                                            int lane) {
-    constexpr int STEPS = KIN / 4;
-    const int r = lane & 15, kg = lane >> 4, tiles = OUT / 16;
+__device__ __forceinline__ void first_layer(const float* __restrict__ W, const float* __restrict__ bv, int K, int OUT, const float* in, float* out,
+                                            int wave, int lane) {
+    constexpr int STEPS = KC / 4;
+    const int r = lane & 15, kg = lane >> 4, tiles = OUT / 16, cpt = (K + KC - 1) / KC;
     if (wave >= tiles) return;
-    float cur[STEPS], nxt[STEPS] = {}, bc, bn = 0.f;
-    auto fetch = [&](float (&w)[STEPS], float& bias, int tile) {
-        const int n = tile * 16 + r;
+    const int steps = (tiles - wave + 3) / 4 * cpt;
+    float cur[STEPS], nxt[STEPS] = {}, bc = 0.f, bn = 0.f;
+    auto fetch = [&](float (&w)[STEPS], float& bias, int s) {
+        const int tile = wave + 4 * (s / cpt), c = s % cpt, n = tile * 16 + r;
+        const float* wrow = W + (size_t)n * K;
 #pragma unroll
-        for (int s2 = 0; s2 < STEPS; s2++) { const int k = 4 * s2 + kg; w[s2] = k < BG_NUM_OBS ? W[(size_t)n * BG_NUM_OBS + k] : 0.f; }
-        bias = bv[n];
+        for (int s2 = 0; s2 < STEPS; s2++) { const int k = c * KC + 4 * s2 + kg; w[s2] = k < K ? wrow[k] : 0.f; }
+        if (c == 0) bias = bv[n];
     };
-    fetch(cur, bc, wave);
-    for (int tile = wave; tile < tiles; tile += 4) {
-        if (tile + 4 < tiles) fetch(nxt, bn, tile + 4);
-        f32x4 acc = {bc, bc, bc, bc};
+    fetch(cur, bc, 0);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < steps; s++) {
+        if (s + 1 < steps) fetch(nxt, bn, s + 1);
+        const int tile = wave + 4 * (s / cpt), c = s % cpt;
+        if (c == 0) acc = f32x4{bc, bc, bc, bc};
+        const float* arow = in + r * LDA + c * KC + kg;
 #pragma unroll
-        for (int s2 = 0; s2 < STEPS; s2++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(in[r * LDA + 4 * s2 + kg], cur[s2], acc, 0, 0, 0);
+        for (int s2 = 0; s2 < STEPS; s2++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[4 * s2], cur[s2], acc, 0, 0, 0);
+        if (c == cpt - 1) {
 #pragma unroll
-        for (int q = 0; q < 4; q++) out[(kg * 4 + q) * LDA + tile * 16 + r] = elu(acc[q]);
+            for (int q = 0; q < 4; q++) out[(kg * 4 + q) * LDA + tile * 16 + r] = elu(acc[q]);
+        }
 #pragma unroll
         for (int s2 = 0; s2 < STEPS; s2++) cur[s2] = nxt[s2];
-        bc = bn;
+        if (c + 1 == cpt) bc = bn;
     }
 }
 
@@ -126,12 +137,13 @@ __global__ __launch_bounds__(256) void actor_mlp_sample_kernel(int N, const floa
     constexpr int LDA = MAXW + 4;  // row stride (floats): = 4 mod 64 banks, as bg_actor_sample's 260
     __shared__ __attribute__((aligned(16))) float buf[2][MR * LDA];
     const int r0 = blockIdx.x * MR, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int k = threadIdx.x; k < MR * KIN; k += blockDim.x) {  // obs tile, k padded 47 -> 48 with zeros
-        const int r = k / KIN, c = k % KIN;
-        buf[0][r * LDA + c] = (r0 + r < N && c < BG_NUM_OBS) ? obs[(size_t)(r0 + r) * BG_NUM_OBS + c] : 0.f;
+    const int K = net.in[0], KP = (K + KC - 1) / KC * KC;  // obs row stride 47 H; the tile's columns padded to whole k-chunks with zeros (KP <= LDA: host)
+    for (int k = threadIdx.x; k < MR * KP; k += blockDim.x) {
+        const int r = k / KP, c = k - r * KP;
+        buf[0][r * LDA + c] = (r0 + r < N && c < K) ? obs[(size_t)(r0 + r) * K + c] : 0.f;
     }
     __syncthreads();
-    first_layer<LDA>(net.W[0], net.b[0], net.out[0], buf[0], buf[1], wave, lane);
+    first_layer<LDA>(net.W[0], net.b[0], K, net.out[0], buf[0], buf[1], wave, lane);
     __syncthreads();
     int cur = 1;
     for (int l = 1; l < net.n; l++) {
@@ -167,7 +179,8 @@ extern "C" int bg_actor_sample_mlp(int32_t N, const float* obs, int32_t n_layers
         const bg_mlp_layer_desc& d = layers[l];
         if (!d.W || !d.b) return bg_set_error(-1, "bg_actor_sample_mlp: bad argument (layer weights)");
         const bool last = l + 1 == n_layers;
-        if (d.in != (l == 0 ? BG_NUM_OBS : layers[l - 1].out)) return bg_set_error(-4, "bg_actor_sample_mlp: layer widths do not chain (first layer: 47 inputs)");
+        if (l == 0 ? (d.in < BG_NUM_OBS || d.in > BG_NUM_OBS * BG_MAX_FRAME_STACK || d.in % BG_NUM_OBS != 0) : d.in != layers[l - 1].out)
+            return bg_set_error(-4, "bg_actor_sample_mlp: layer widths do not chain (first layer: 47 H inputs, H = 1 .. 10 observation frames)");
         if (last ? d.out != BG_NUM_DOFS : (d.out % 128 != 0 || d.out < 128 || d.out > 512))
             return bg_set_error(-4, "bg_actor_sample_mlp: unsupported widths (hidden: multiples of 128 up to 512; output: 12)");
         if (l > 0 && ((uintptr_t)d.W & 15)) return bg_set_error(-1, "bg_actor_sample_mlp: weight matrices after the first must be 16-byte aligned");
@@ -176,7 +189,8 @@ extern "C" int bg_actor_sample_mlp(int32_t N, const float* obs, int32_t n_layers
     }
     const dim3 grid((N + MR - 1) / MR), block(256);
     hipStream_t st = (hipStream_t)stream;
-    if (maxw <= 256) hipLaunchKernelGGL(actor_mlp_sample_kernel<256>, grid, block, 0, st, N, obs, net, logstd, seed, (uint32_t)counter, mu, actions);
+    const int kp = (layers[0].in + KC - 1) / KC * KC;  // the input tile's columns: within the 256-wide form's LDS tile up to 5 frames (240)
+    if (maxw <= 256 && kp <= 256) hipLaunchKernelGGL(actor_mlp_sample_kernel<256>, grid, block, 0, st, N, obs, net, logstd, seed, (uint32_t)counter, mu, actions);
     else hipLaunchKernelGGL(actor_mlp_sample_kernel<512>, grid, block, 0, st, N, obs, net, logstd, seed, (uint32_t)counter, mu, actions);
     HIP_OK(hipGetLastError());
     return 0;

@@ -84,7 +84,7 @@ struct EnvDev {
 };
 
 struct StepOut {
-    float* obs;      // [N][47]
+    float* obs;      // [N][47]: the caller's output, or with cfg.frame_stack > 1 a plane of the env's observation ring (bg_obs_stack, bg_sim.hip)
     float* priv;     // [N][priv_stride]: columns 0..13 from the env step; 14.. the height scan (bg_height_scan), when there is one
     float* rew;      // [N]
     uint8_t* done;   // [N]

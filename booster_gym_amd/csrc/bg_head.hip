@@ -714,19 +714,22 @@ __global__ __launch_bounds__(256) void actor_head_sym_kernel(int B, int tiles, c
     }
 }
 
-// y[r][c] = sign[c] x[r][src[c]] (src[c] < 0: 0) for rows x cols elements: exact, only signs change
-struct ColumnMirror { int src[64]; float sign[64]; };
+// y[r][c] = sign[c] x[r][src[c]] (src[c] < 0: 0) for rows x cols elements: exact, only signs change.  Up to MIRROR_MAX_COLS columns (the widest
+// network input: a frame stack's 47 H observations padded to 512); the map travels as a kernel argument, one 16-bit code per column: -1 for a zero
+// column, else src with MIRROR_NEG set where the sign is -1.
+constexpr int MIRROR_MAX_COLS = 512;
+constexpr int MIRROR_NEG = 0x4000;
+struct ColumnMirror { int16_t code[MIRROR_MAX_COLS]; };
 __global__ __launch_bounds__(256) void mirror_rows_kernel(int rows, int cols, ColumnMirror cm, const float* __restrict__ x, float* __restrict__ y) {
-    __shared__ int s_src[64];
-    __shared__ float s_sign[64];
-    if ((int)threadIdx.x < 64) { s_src[threadIdx.x] = cm.src[threadIdx.x]; s_sign[threadIdx.x] = cm.sign[threadIdx.x]; }
+    __shared__ int16_t s_code[MIRROR_MAX_COLS];
+    for (int c = threadIdx.x; c < cols; c += 256) s_code[c] = cm.code[c];
     __syncthreads();
     const size_t n = (size_t)rows * cols;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         const size_t r = i / cols;
-        const int col = (int)(i - r * cols), s = s_src[col];
-        const float v = s < 0 ? 0.f : x[r * cols + s];
-        y[i] = s_sign[col] < 0.f ? -v : v;
+        const int col = (int)(i - r * cols), code = s_code[col];
+        const float v = code < 0 ? 0.f : x[r * cols + (code & (MIRROR_NEG - 1))];
+        y[i] = (code & MIRROR_NEG) ? -v : v;
     }
 }
 
@@ -903,12 +906,12 @@ extern "C" int bg_actor_head_sym_partial(int32_t B, const float* h, const float*
 }
 
 extern "C" int bg_mirror_rows(int32_t rows, int32_t cols, const int32_t* src, const float* sign, const float* x, float* y, void* stream) {
-    if (rows <= 0 || cols <= 0 || cols > 64 || !src || !sign || !x || !y) return bg_set_error(-1, "bg_mirror_rows: bad argument (1 to 64 columns)");
+    if (rows <= 0 || cols <= 0 || cols > MIRROR_MAX_COLS || !src || !sign || !x || !y) return bg_set_error(-1, "bg_mirror_rows: bad argument (1 to 512 columns)");
     ColumnMirror cm;
-    for (int c = 0; c < 64; c++) { cm.src[c] = -1; cm.sign[c] = 1.f; }
+    for (int c = 0; c < MIRROR_MAX_COLS; c++) cm.code[c] = -1;
     for (int c = 0; c < cols; c++) {
         if (src[c] < -1 || src[c] >= cols || !(sign[c] == 1.f || sign[c] == -1.f)) return bg_set_error(-1, "bg_mirror_rows: src in [-1, cols), sign +-1");
-        cm.src[c] = src[c]; cm.sign[c] = sign[c];
+        cm.code[c] = (int16_t)(src[c] < 0 ? -1 : (src[c] | (sign[c] < 0.f ? MIRROR_NEG : 0)));
     }
     const float *xe = x + (size_t)rows * cols, *ye = y + (size_t)rows * cols;
     if (x < ye && y < xe) return bg_set_error(-1, "bg_mirror_rows: x and y overlap");

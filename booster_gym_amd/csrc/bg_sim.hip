@@ -43,6 +43,8 @@ struct bg_env {
     int curr_cells = 0;
     int32_t* tcur = nullptr;  // terrain curriculum: [n] levels, [n] columns, [1] level sum (cfg.terrain_curriculum only)
     float* scan_xy = nullptr; // height scan: [P][2] points in the robot's yaw frame (cfg.height_scan_points > 0 only)
+    float* hist = nullptr;    // observation history: ring [H][n][47] of the last H single observations (cfg.frame_stack = H > 1 only)
+    int hist_head = 0;        // ... the plane of the newest one: the env-step kernels of a launch sequence write their observations there
     ModelDev* model_dev = nullptr;
     PairModel* pair_dev = nullptr;  // the leg constants with the two legs side by side (packed ABA kernel)
     int16_t* hf = nullptr;
@@ -185,6 +187,30 @@ __global__ __launch_bounds__(SCAN_BLOCK) void bg_height_scan(EnvDev E, const flo
     const float h = terrain_height(E.terrain, bx + c * pt.x - s * pt.y, by + s * pt.x + c * pt.y);
     const float v = fminf(fmaxf(bz - h - E.cfg.base_height_target, -1.f), 1.f);
     priv[(size_t)e * stride + BG_NUM_PRIV + p] = v * E.cfg.height_scan_scale;
+}
+
+// ------------------------------------------------------------------ observation history of the actor's input (cfg.frame_stack = H > 1)
+// humanoid-gym's frame stack: the row [47 H] of an env is its last H single observations, oldest first, newest last.  The env keeps them as a
+// ring of H planes [n][47]; the env-step kernels (and resample_apply_kernel's patch) of a launch sequence write their 47-wide rows into plane
+// `head`, and this launch, the last of the sequence, copies the planes head + 1, ..., head + H (mod H) into the destination's columns, which is
+// a different tensor at every step of a rollout (bg_env_step_to), so nothing of the history can live there.  One thread per destination element,
+// a row's elements on consecutive lanes: the destination goes out in whole lines, the ring is read in runs of 47 floats.  An env that was reset
+// in this step (every env at reset-all, which writes no done flags) reads zeros for its H - 1 older frames and zeroes them in the ring; a thread
+// writes only the ring element it alone reads, and nobody writes plane `head` here, so no element is read after another thread has changed it.
+constexpr int STACK_BLOCK = 256;
+__global__ __launch_bounds__(STACK_BLOCK) void bg_obs_stack(int n, int H, int head, int all_reset, float* ring, const uint8_t* __restrict__ done,
+                                                            float* __restrict__ dst) {
+    const unsigned W = (unsigned)(BG_NUM_OBS * H);
+    const unsigned t = blockIdx.x * STACK_BLOCK + threadIdx.x;  // (n 47 H < 2^31: bg_env_create)
+    if (t >= (unsigned)n * W) return;
+    const unsigned e = t / W, col = t - e * W, k = col / BG_NUM_OBS, c = col - k * BG_NUM_OBS;
+    unsigned slot = (unsigned)head + 1u + k;  // frame k = the observation of H - 1 - k steps ago
+    if (slot >= (unsigned)H) slot -= (unsigned)H;
+    float* src = ring + ((size_t)slot * n + e) * BG_NUM_OBS + c;
+    float v = 0.f;
+    if (k + 1u == (unsigned)H || !(all_reset || done[e])) v = *src;
+    else *src = 0.f;
+    dst[t] = v;
 }
 
 // ------------------------------------------------------------------ reference-exact command resampling (cfg.exact_still_count / same_step_curriculum)
@@ -744,6 +770,11 @@ static int env_create_fill(bg_env* e, const bg_env_cfg* cfg, const bg_model* mod
         HIP_OK(hipMalloc(&e->scan_xy, sizeof(float) * 2 * cfg->height_scan_points));
         HIP_OK(hipMemcpy(e->scan_xy, cfg->height_scan_xy, sizeof(float) * 2 * cfg->height_scan_points, hipMemcpyHostToDevice));
     }
+    if (cfg->frame_stack > 1) {  // the ring of single observations, all zeros: an env that has never been reset has an empty history
+        const size_t hb = sizeof(float) * (size_t)cfg->frame_stack * n * BG_NUM_OBS;
+        HIP_OK(hipMalloc(&e->hist, hb));
+        HIP_OK(hipMemset(e->hist, 0, hb));
+    }
     // defaults: unit mass scale / compliance, identity orientation, nominal friction
     std::vector<float> host(n * F_COUNT, 0.f);
     for (size_t k = 0; k < n; k++) {
@@ -786,6 +817,8 @@ extern "C" int bg_env_create(const bg_env_cfg* cfg, const bg_model* model, bg_en
         return fail(-1, "bg_env_create: the terrain curriculum needs a height field of at least one level and positive tile sizes");
     if (cfg->height_scan_points < 0 || cfg->height_scan_points > BG_MAX_HEIGHT_SCAN_POINTS || (cfg->height_scan_points > 0 && (cfg->terrain_type == 0 || !cfg->height_scan_xy || (int64_t)cfg->num_envs * cfg->height_scan_points >= (int64_t)1 << 31)))
         return fail(-1, "bg_env_create: the height scan needs a height field and 1 .. BG_MAX_HEIGHT_SCAN_POINTS points");
+    if (cfg->frame_stack < 0 || cfg->frame_stack > BG_MAX_FRAME_STACK || (int64_t)cfg->num_envs * BG_NUM_OBS * cfg->frame_stack >= (int64_t)1 << 31)
+        return fail(-1, "bg_env_create: frame_stack must be 1 .. BG_MAX_FRAME_STACK (0 = 1: no history) with num_envs x 47 x frame_stack below 2^31");
     int ndev = 0;
     hipError_t de = hipGetDeviceCount(&ndev);
     if (de != hipSuccess || ndev == 0) return fail(-3, "bg_env_create: no HIP device available (this library has no CPU path)");
@@ -804,7 +837,7 @@ extern "C" int bg_env_create(const bg_env_cfg* cfg, const bg_model* model, bg_en
 extern "C" void bg_env_destroy(bg_env* e) {
     if (!e) return;
     (void)hipFree(e->sim_tau); (void)hipFree(e->sim_bforce); (void)hipFree(e->sim_btorque);
-    (void)hipFree(e->f); (void)hipFree(e->h); (void)hipFree(e->lowmask); (void)hipFree(e->fd_mask); (void)hipFree(e->fd_list); (void)hipFree(e->fd_count); (void)hipFree(e->rs_counts); (void)hipFree(e->i); (void)hipFree(e->stats); (void)hipFree(e->model_dev); (void)hipFree(e->pair_dev); (void)hipFree(e->hf); (void)hipFree(e->curr); (void)hipFree(e->curr_read); (void)hipFree(e->tcur); (void)hipFree(e->scan_xy);
+    (void)hipFree(e->f); (void)hipFree(e->h); (void)hipFree(e->lowmask); (void)hipFree(e->fd_mask); (void)hipFree(e->fd_list); (void)hipFree(e->fd_count); (void)hipFree(e->rs_counts); (void)hipFree(e->i); (void)hipFree(e->stats); (void)hipFree(e->model_dev); (void)hipFree(e->pair_dev); (void)hipFree(e->hf); (void)hipFree(e->curr); (void)hipFree(e->curr_read); (void)hipFree(e->tcur); (void)hipFree(e->scan_xy); (void)hipFree(e->hist);
     delete e;
 }
 
@@ -850,8 +883,13 @@ extern "C" int bg_env_bind_outputs(bg_env* e, float* obs, float* priv, float* re
     return 0;
 }
 
-static int launch_step(bg_env* e, const float* actions, int mode, const StepOut& out, void* stream) {
-    if (!out.obs || !out.priv || !out.rew || !out.done || !out.tout) return fail(-1, "bg_env_step: outputs are not bound");
+static int launch_step(bg_env* e, const float* actions, int mode, const StepOut& dst, void* stream) {
+    if (!dst.obs || !dst.priv || !dst.rew || !dst.done || !dst.tout) return fail(-1, "bg_env_step: outputs are not bound");
+    StepOut out = dst;
+    if (e->hist) {  // observation history: this sequence's 47-wide observation rows go to the next plane of the ring, bg_obs_stack writes dst.obs
+        e->hist_head = (e->hist_head + 1) % e->cfg.frame_stack;
+        out.obs = e->hist + (size_t)e->hist_head * e->n * BG_NUM_OBS;
+    }
     dim3 grid((e->n + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK), block(64);
     hipStream_t st = (hipStream_t)stream;
     const uint32_t cnt = (uint32_t)e->step_count;
@@ -890,6 +928,11 @@ static int launch_step(bg_env* e, const float* actions, int mode, const StepOut&
         dim3 gs((unsigned)(((int64_t)e->n * P + SCAN_BLOCK - 1) / SCAN_BLOCK));
         if (e->h) hipLaunchKernelGGL(bg_height_scan<true>, gs, dim3(SCAN_BLOCK), 0, st, env_dev(e), (const float2*)e->scan_xy, P, out.priv, out.priv_stride);
         else hipLaunchKernelGGL(bg_height_scan<false>, gs, dim3(SCAN_BLOCK), 0, st, env_dev(e), (const float2*)e->scan_xy, P, out.priv, out.priv_stride);
+    }
+    if (e->hist) {  // last: every launch that writes the single observation (kernel B and resample_apply_kernel included) is in front of it
+        const int H = e->cfg.frame_stack;
+        dim3 gs((unsigned)(((int64_t)e->n * BG_NUM_OBS * H + STACK_BLOCK - 1) / STACK_BLOCK));
+        hipLaunchKernelGGL(bg_obs_stack, gs, dim3(STACK_BLOCK), 0, st, e->n, H, e->hist_head, mode, e->hist, (const uint8_t*)out.done, dst.obs);
     }
     HIP_OK(hipGetLastError());
     if (e->cfg.curriculum && mode == 0)  // publish this step's curriculum increments to the next step's samplers

@@ -45,14 +45,18 @@ def joint_mirror(dof_names, dof_axes):
     return np.array(src, dtype=np.int32), np.array(sign, dtype=np.float32)
 
 
-def mirror_maps(dof_names, dof_axes, default_dof_pos, num_obs):
+def mirror_maps(dof_names, dof_axes, default_dof_pos, num_obs, frame_stack=1):
     """(obs_src, obs_sign, act_src, act_sign): the maps M_o of the observations and M_a of the actions.  ValueError if the model has no left /
     right pairing, the observation width is not T1's layout for these joints, or the default pose is not its own mirror image (dof_pos - default
-    then would not mirror as a signed permutation)."""
+    then would not mirror as a signed permutation).  frame_stack = H > 1 (env.frame_stack): num_obs is H single observations side by side and M_o
+    the single observation's map tiled over them, frame k's source indices offset by k times the single width."""
     act_src, act_sign = joint_mirror(dof_names, dof_axes)
     nd = len(act_src)
-    if num_obs != OBS_JOINTS + 3 * nd:
-        raise ValueError(f"symmetry loss: {num_obs} observations are not T1's layout for {nd} joints ({OBS_JOINTS + 3 * nd})")
+    H, total = int(frame_stack), num_obs
+    if H < 1 or num_obs != H * (OBS_JOINTS + 3 * nd):
+        raise ValueError(f"symmetry loss: {num_obs} observations are not T1's layout for {nd} joints ({OBS_JOINTS + 3 * nd}"
+                         + (f" x {H} frames)" if H > 1 else ")"))
+    num_obs = total // H
     q0 = np.asarray(default_dof_pos, dtype=np.float64).reshape(-1)
     if not np.array_equal(act_sign * q0[act_src], q0):
         raise ValueError(f"symmetry loss: the default joint pose {q0.tolist()} is not its own mirror image")
@@ -63,6 +67,9 @@ def mirror_maps(dof_names, dof_axes, default_dof_pos, num_obs):
         blk = OBS_JOINTS + k * nd
         obs_src[blk : blk + nd] = blk + act_src
         obs_sign[blk : blk + nd] = act_sign
+    if H > 1:
+        obs_src = np.concatenate([obs_src + k * num_obs for k in range(H)]).astype(np.int32)
+        obs_sign = np.tile(obs_sign, H)
     return obs_src, obs_sign, act_src, act_sign
 
 

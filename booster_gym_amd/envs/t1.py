@@ -30,19 +30,42 @@ TERRAIN_LEVEL_STREAM = 0x7E44A1
 MAX_CRITIC_INPUT = 512
 
 
+MAX_FRAME_STACK = 10  # env.frame_stack: 47 x 10 = 470 actor inputs, within the widest first layer of the kernels (512)
+
+
+def frame_stack_of(cfg):
+    """env.frame_stack (an addition of this build, humanoid-gym's name; absent = 1): the number H of single observations in the actor's input.
+    ValueError unless it is an integer in 1 .. MAX_FRAME_STACK."""
+    H = cfg["env"].get("frame_stack", 1)
+    if isinstance(H, bool) or not isinstance(H, int) or not 1 <= H <= MAX_FRAME_STACK:
+        raise ValueError(f"env.frame_stack = {H!r} must be an integer from 1 to {MAX_FRAME_STACK}: {_lib.NUM_OBS} x env.frame_stack observations are the "
+                         f"actor's input, and {_lib.NUM_OBS} x {MAX_FRAME_STACK} = {_lib.NUM_OBS * MAX_FRAME_STACK} is the most within the widest first layer "
+                         f"of the kernels ({MAX_CRITIC_INPUT})")
+    return H
+
+
 def check_env_sizes(cfg, num_height_points):
-    """ValueError unless env.num_observations / num_privileged_obs / num_actions are what this build computes: 47, 14 (+ P with the terrain height scan's
-    P points: legged_gym requires num_observations to match what the env computes) and 12; and 47 + 14 + P within MAX_CRITIC_INPUT."""
-    env, P = cfg["env"], num_height_points
+    """ValueError unless env.num_observations / num_privileged_obs / num_actions are what this build computes: 47 H (H = env.frame_stack single
+    observations, 47 without the key), 14 (+ P with the terrain height scan's P points: legged_gym requires num_observations to match what the env
+    computes) and 12; and 47 H + 14 + P within MAX_CRITIC_INPUT."""
+    env, P, H = cfg["env"], num_height_points, frame_stack_of(cfg)
     no, npv, na = env["num_observations"], env["num_privileged_obs"], env["num_actions"]
+    if H > 1 and no != _lib.NUM_OBS * H:
+        raise ValueError(f"env.num_observations = {no}, but env.frame_stack = {H} computes {_lib.NUM_OBS} x {H} = {_lib.NUM_OBS * H} observations: set "
+                         f"env.num_observations to {_lib.NUM_OBS * H}")
+    if H > 1 and no + _lib.NUM_PRIV + P > MAX_CRITIC_INPUT:
+        scan = f" + {P} (terrain.measured_points_x x terrain.measured_points_y)" if P else ""
+        raise ValueError(f"env.frame_stack = {H}: the critic's input {no} + {_lib.NUM_PRIV}{scan} = {no + _lib.NUM_PRIV + P} exceeds {MAX_CRITIC_INPUT} "
+                         f"(the widest first layer of the kernels): a smaller env.frame_stack" + (", or fewer points of the height scan" if P else ""))
     if P and no + _lib.NUM_PRIV + P > MAX_CRITIC_INPUT:
         raise ValueError(f"terrain.measured_points_x x terrain.measured_points_y = {P} points: the critic's input {no} + {_lib.NUM_PRIV} + {P} "
                          f"exceeds {MAX_CRITIC_INPUT} (the widest first layer of the kernels)")
     if P and npv != _lib.NUM_PRIV + P:
         raise ValueError(f"env.num_privileged_obs = {npv}, but terrain.measure_heights with {P} points computes {_lib.NUM_PRIV} + {P} = "
                          f"{_lib.NUM_PRIV + P} privileged observations: set env.num_privileged_obs to {_lib.NUM_PRIV + P}")
-    if (no, npv - P, na) != (_lib.NUM_OBS, _lib.NUM_PRIV, _lib.NUM_DOFS):
-        raise ValueError("this build computes 47 observations, 14 privileged observations and 12 actions (envs/T1.yaml env.*)")
+    if (no, npv - P, na) != (_lib.NUM_OBS * H, _lib.NUM_PRIV, _lib.NUM_DOFS):
+        raise ValueError("this build computes 47 observations (47 x env.frame_stack with a frame stack), 14 privileged observations and 12 actions "
+                         "(envs/T1.yaml env.*)")
 
 
 def _draw(rng, shape, params):
@@ -175,6 +198,8 @@ class T1(BaseTask):
 
     def _init_buffers(self):
         cfg = self.cfg
+        # the actor's observation history (env.frame_stack): H single observations of 47 floats per row, oldest first (checked in __init__)
+        self.num_single_obs, self.frame_stack = _lib.NUM_OBS, frame_stack_of(cfg)
         self.num_obs = cfg["env"]["num_observations"]
         self.num_privileged_obs = cfg["env"]["num_privileged_obs"]
         self.num_actions = cfg["env"]["num_actions"]
@@ -293,6 +318,7 @@ class T1(BaseTask):
                 self._scan_xy = np.ascontiguousarray(self.terrain.height_points, dtype=np.float32)
                 c.height_scan_points, c.height_scan_xy = self.num_height_points, self._scan_xy.ctypes.data
                 c.height_scan_scale = float(nz.get("height_measurements", 5.0))
+        c.frame_stack = self.frame_stack
         sd = str(cfg["sim"].get("state_dtype", "fp32")).lower()
         if sd not in ("fp32", "float32", "fp16", "float16", "half"):
             raise ValueError(f"sim.state_dtype must be fp32 or fp16, got {sd!r}")
@@ -420,6 +446,8 @@ class T1(BaseTask):
                 raise RuntimeError("step_to needs contiguous CUDA output tensors")
         if privileged_obs.numel() < self.num_envs * self.num_privileged_obs:  # (rows of 14 + P with the height scan)
             raise RuntimeError(f"step_to needs privileged_obs of {self.num_envs} x {self.num_privileged_obs} floats")
+        if self.frame_stack > 1 and obs.numel() < self.num_envs * self.num_obs:  # (rows of 47 H with a frame stack)
+            raise RuntimeError(f"step_to needs obs of {self.num_envs} x {self.num_obs} floats")
         _lib.check(self._lib.bg_env_step_to(self._env, _lib.ptr(a), _lib.ptr(obs), _lib.ptr(privileged_obs), _lib.ptr(rew), _lib.ptr(done),
                                             _lib.ptr(time_outs), _lib.current_stream_ptr()), "bg_env_step_to")
         if self._stale_tout:
@@ -438,7 +466,7 @@ class T1(BaseTask):
         """(obs_src, obs_sign, act_src, act_sign): the left-right mirror maps of the observations and actions (envs/mirror.py), from the model's joint
         names and axes; ValueError if the model has no left / right pairing or its default pose is not mirror-invariant."""
         axes = [int(a) for a in self.model.joint_axis if int(a) != 0]  # (bodies depth-first: body j + 1 is moved by DoF j)
-        return mirror_maps(self.dof_names, axes, self.default_dof_pos[0].cpu().numpy(), self.num_obs)
+        return mirror_maps(self.dof_names, axes, self.default_dof_pos[0].cpu().numpy(), self.num_obs, self.frame_stack)
 
     def get_field(self, name):
         comps, is_int = C.c_int32(), C.c_int32()

@@ -7,7 +7,8 @@ critic (47+14)-256-256-128-1, ELU, state-independent log-std initialised to -2. 
 the keys keep the `Sequential` numbering (`actor.{0,2,4,6,8}` for four hidden layers).
 The PPO update's GEMMs run on hand-written HIP kernels (MLPTrainer: the chained hidden layers, the grouped weight
 gradients), in the form its NetPlan names; the rollout-time inference + sampling is one fused HIP launch
-(`sample_actions` -> bg_actor_sample at the reference's widths, bg_actor_sample_mlp at any other supported widths).
+(`sample_actions` -> bg_actor_sample at the reference's widths on 47 inputs, bg_actor_sample_mlp at any other supported widths and on a
+frame stack of 47 H inputs).
 """
 import ctypes
 from typing import NamedTuple
@@ -636,8 +637,9 @@ class ActorCritic(torch.nn.Module):
 
     # ---- fused rollout inference (reference runner.py:109-111: dist = model.act(obs); act = dist.sample())
     def sample_actions(self, obs, actions_out, seed, counter, mu_out=None):
-        """One launch: the actor's mean and a Gaussian sample around it.  The reference's widths run bg_actor_sample (its widths built into the
-        kernel), every other architecture bg_actor_sample_mlp (widths from descriptors); both draw the same noise for the same seed and counter."""
+        """One launch: the actor's mean and a Gaussian sample around it.  The reference's widths on 47 inputs run bg_actor_sample (its widths built
+        into the kernel), every other architecture, and every actor on a frame stack (47 H inputs, env.frame_stack), bg_actor_sample_mlp (widths from
+        descriptors, the weights read from the parameters themselves); both draw the same noise for the same seed and counter."""
         if not obs.is_cuda:
             raise RuntimeError("sample_actions runs the fused HIP actor kernel and needs CUDA tensors")
         a = self.actor
@@ -646,10 +648,12 @@ class ActorCritic(torch.nn.Module):
         for t in w + [obs, actions_out]:
             if not t.is_contiguous():
                 raise RuntimeError("sample_actions needs contiguous tensors")
-        if self.actor_hidden == ACTOR_HIDDEN:
+        if self.actor_hidden == ACTOR_HIDDEN and lin[0].in_features == _lib.NUM_OBS:
             _lib.check(_lib.load().bg_actor_sample(obs.shape[0], _lib.ptr(obs), *[_lib.ptr(t) for t in w], int(seed), int(counter), _lib.ptr(mu_out),
                                                    _lib.ptr(actions_out), _lib.current_stream_ptr()), "bg_actor_sample")
             return actions_out
+        if obs.shape[-1] != lin[0].in_features:  # (the kernel takes the row stride from the first layer's descriptor)
+            raise ValueError(f"sample_actions: observations of {obs.shape[-1]} columns, the actor takes {lin[0].in_features}")
         key = tuple(t.data_ptr() for t in w)
         if key != self._sample_key:  # descriptors of the current parameter storage (the optimiser moves it into its flat buffer once)
             self._sample_layers = (_lib.MlpLayerDesc * len(lin))(*[_lib.MlpLayerDesc(l.weight.data_ptr(), l.bias.data_ptr(), l.in_features, l.out_features)

@@ -307,10 +307,14 @@ class Runner:
         B, A = T * N, self.env.num_actions
         dev = self.device
         # network inputs with the feature dimension zero-padded, each network on its own (pad_input: actor 47 -> 64, critic 61 -> 64, or 61 + P -> 128 /
-        # 256 / 512 with the terrain height scan) so that the first layers run on the fused MFMA kernels
+        # 256 / 512 with the terrain height scan; with env.frame_stack = H the actor's 47 H and the critic's 47 H + 14 + P likewise) so that the first
+        # layers run on the fused MFMA kernels
         no, npv = self.env.num_obs, self.env.num_privileged_obs
         self._pad_actor = pad_input(no) if MLPTrainer.FUSED else None
         self._pad_critic = pad_input(no + npv) if MLPTrainer.FUSED else None
+        if self._pad_actor and self._pad_actor > 256 and (int((self.cfg.get("parallel", {}) or {}).get("gemm_split", 0) or 0) or MLPTrainer.SPLIT):
+            raise ValueError(f"parallel.gemm_split / BG_GEMM_SPLIT runs split-bf16 layer kernels that take layer inputs of 64, 128 or 256 columns only; the "
+                             f"actor's input of {no} observations pads to {self._pad_actor} (env.frame_stack 5 or less, or gemm_split 0)")
         if self._pad_critic and self._pad_critic > 256 and (int((self.cfg.get("parallel", {}) or {}).get("gemm_split", 0) or 0) or MLPTrainer.SPLIT):
             raise ValueError(f"parallel.gemm_split / BG_GEMM_SPLIT runs split-bf16 layer kernels that take layer inputs of 64, 128 or 256 columns only; the "
                              f"critic's input {no} + {npv} pads to {self._pad_critic} (fewer terrain.measured_points_x / _y points, or gemm_split 0)")
@@ -441,6 +445,11 @@ class Runner:
             self.cfg["basic"]["checkpoint"] = ck
         print("Loading model from {}".format(ck))
         model_dict = torch.load(ck, map_location=self.device, weights_only=True)
+        ck_ain, a_in = int(model_dict["model"]["actor.0.weight"].shape[1]), self.model.actor[0].in_features
+        if ck_ain != a_in:  # (the actor's input: env.frame_stack single observations of 47)
+            raise ValueError(f"checkpoint {ck} has an actor of {ck_ain} inputs, the config's actor takes {a_in} (env.num_observations = "
+                             f"{self.env.num_single_obs} x env.frame_stack): env.frame_stack must be as in the run that saved the checkpoint "
+                             f"({ck_ain // self.env.num_single_obs if ck_ain % self.env.num_single_obs == 0 else '?'})")
         ck_in, c_in = int(model_dict["model"]["critic.0.weight"].shape[1]), self.model.critic[0].in_features
         if ck_in != c_in:  # (the critic's input: observations + privileged observations, with the terrain height scan 14 + P of the latter)
             raise ValueError(f"checkpoint {ck} has a critic of {ck_in} inputs, the config's critic takes {c_in} (env.num_observations + "

@@ -1,6 +1,6 @@
 """python export_model.py --task=T1 [--checkpoint path|-1]: TorchScript export of the actor (reference export_model.py:8-30) so that
 the reference's deployment code (deploy/utils/policy.py:9) can load what this framework trains.  The actor's widths are read from the checkpoint's tensors (any supported architecture, with or without the terrain height
-scan, exports without editing the YAML); the TorchScript module is still a plain Sequential."""
+scan or a frame stack, exports without editing the YAML); the TorchScript module is still a plain Sequential."""
 import argparse
 import glob
 import os
@@ -21,9 +21,11 @@ if __name__ == "__main__":
         ck = sorted(glob.glob(os.path.join("logs", "**/*.pth"), recursive=True), key=os.path.getmtime)[-1]
     print("Loading model from {}".format(ck))
     sd = torch.load(ck, map_location="cpu", weights_only=True)["model"]
-    # the critic's privileged inputs from the checkpoint too (14, or 14 + P with terrain.measure_heights); only the actor is exported
-    num_priv = int(sd["critic.0.weight"].shape[1]) - cfg["env"]["num_observations"]
-    model = ActorCritic(cfg["env"]["num_actions"], cfg["env"]["num_observations"], num_priv, actor_hidden=hidden_of(sd, "actor"),
+    # the actor's input from the checkpoint (47, or 47 H with env.frame_stack), and the critic's privileged inputs too (14, or 14 + P with
+    # terrain.measure_heights); only the actor is exported
+    num_obs = int(sd["actor.0.weight"].shape[1])
+    num_priv = int(sd["critic.0.weight"].shape[1]) - num_obs
+    model = ActorCritic(cfg["env"]["num_actions"], num_obs, num_priv, actor_hidden=hidden_of(sd, "actor"),
                         critic_hidden=hidden_of(sd, "critic"))
     model.load_state_dict(sd)
     os.makedirs("deploy/models", exist_ok=True)

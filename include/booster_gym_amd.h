@@ -27,6 +27,7 @@ extern "C" {
 #define BG_NUM_REWARD_TERMS 26
 #define BG_MAX_BODY_SPHERES 16
 #define BG_MAX_HEIGHT_SCAN_POINTS 1024 /* bg_env_cfg.height_scan_points */
+#define BG_MAX_FRAME_STACK 10 /* bg_env_cfg.frame_stack: 47 x 10 = 470 observation columns, within the 512 of the widest first layer */
 
 typedef struct bg_model bg_model;
 typedef struct bg_env bg_env;
@@ -149,6 +150,13 @@ typedef struct {
     int32_t height_scan_points;       /* P: points of the scan (0 = off) */
     const float* height_scan_xy;      /* host float [P][2]: (x, y) of each point in the robot's yaw frame [m]; copied by bg_env_create */
     float height_scan_scale;          /* normalization.height_measurements */
+    /* Observation history of the actor's input (T1.yaml env.frame_stack; an addition of this build, humanoid-gym's frame_stack).  H = 1, or 0 (a
+     * zero-initialised struct: every caller older than the field), is no history: the observation output is [N][47] and no launch is added.
+     * H in 2 .. BG_MAX_FRAME_STACK: the observation output (bound or passed to bg_env_step_to) is [N][47 H], the last H single observations of
+     * each env oldest first, newest last; the env keeps the history itself and one more launch (bg_obs_stack) behind every env step and
+     * reset-all writes the row.  An env that was reset in the step (every env, for bg_env_reset) gets H - 1 zero frames and its new observation.
+     * Negative or above BG_MAX_FRAME_STACK: bg_env_create fails. */
+    int32_t frame_stack;
 } bg_env_cfg;
 
 /* ---- model (replaces gym.load_asset and the asset queries, t1.py:54-108) */
@@ -185,8 +193,8 @@ int bg_env_set_heightfield(bg_env* env, const int16_t* hf_host, int32_t rows, in
  * restitution), base_mass_scaled [N][4] (raw draws shown to the critic, t1.py:141-152), env_origins [N][3] (t1.py:169-185) */
 int bg_env_set_params(bg_env* env, const float* kp, const float* kd, const float* friction, const float* mass_scale, const float* com_offset,
                       const float* foot_material, const float* base_mass_scaled, const float* env_origins);
-/* outputs of reset/step, device pointers owned by the caller (torch tensors): obs [N][47], privileged [N][14 + P] (P = cfg.height_scan_points,
- * 0 without the height scan: [N][14]), rew [N], done uint8 [N], time_outs uint8 [N], rew_terms [26][N] (rows of dropped terms stay 0) */
+/* outputs of reset/step, device pointers owned by the caller (torch tensors): obs [N][47 H] (H = cfg.frame_stack, [N][47] without a
+ * history), privileged [N][14 + P] (P = cfg.height_scan_points, 0 without the height scan: [N][14]), rew [N], done uint8 [N], time_outs uint8 [N], rew_terms [26][N] (rows of dropped terms stay 0) */
 int bg_env_bind_outputs(bg_env* env, float* obs, float* privileged_obs, float* rew, uint8_t* done, uint8_t* time_outs, float* rew_terms);
 /* T1.reset(): t1.py:294-299 */
 int bg_env_reset(bg_env* env, void* stream);
@@ -287,8 +295,8 @@ typedef struct bg_mlp_layer_desc {
     int32_t in, out;
 } bg_mlp_layer_desc;
 /* bg_actor_sample at any supported actor architecture (utils/model.py:8-25 with configured widths + dist.sample(), runner.py:109-111), one
- * launch: layers [n_layers] = 2 to 4 hidden ELU layers (47 inputs; widths multiples of 128 up to 512) and the 12-wide output layer; weight
- * matrices after the first 16-byte aligned.  Same noise as bg_actor_sample: Philox(seed, row, counter, RS_ACTOR + group of 4 actions).
+ * launch: layers [n_layers] = 2 to 4 hidden ELU layers (widths multiples of 128 up to 512) and the 12-wide output layer; the first layer's
+ * `in` is the row stride of obs: 47 H, H = 1 .. 10 observation frames (bg_env_cfg.frame_stack).  Weight matrices after the first 16-byte aligned.  Same noise as bg_actor_sample: Philox(seed, row, counter, RS_ACTOR + group of 4 actions).
  * mu [N][12] may be NULL. */
 int bg_actor_sample_mlp(int32_t N, const float* obs, int32_t n_layers, const bg_mlp_layer_desc* layers, const float* logstd, uint64_t seed,
                         uint64_t counter, float* mu, float* actions, void* stream);
@@ -476,7 +484,7 @@ int bg_actor_head_sym(int32_t B, const float* h, const float* W, const float* bi
                       const float* old_logstd, const float* old_logp, const float* adv, const double* adv_stats, float e_clip, float bound_coef,
                       float entropy_coef, float sym_coef, const int32_t* act_src, const float* act_sign, float* mu_out, float* g_hidden, float* grad_W,
                       float* grad_b, float* grad_b_hidden, double* grad_logstd, double* stats, float* scratch, void* stream);
-/* y [rows][cols] = the rows of x [rows][cols] mirrored: y[r][c] = sign[c] x[r][src[c]] (src[c] = -1: 0), cols <= 64, src / sign host arrays of cols,
+/* y [rows][cols] = the rows of x [rows][cols] mirrored: y[r][c] = sign[c] x[r][src[c]] (src[c] = -1: 0), cols <= 512, src / sign host arrays of cols,
  * sign +-1; x and y must not overlap.  Exact. */
 int bg_mirror_rows(int32_t rows, int32_t cols, const int32_t* src, const float* sign, const float* x, float* y, void* stream);
 

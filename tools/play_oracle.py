@@ -23,6 +23,31 @@ def load_actor(path):
     return [(sd[f"actor.{i}.weight"].numpy(), sd[f"actor.{i}.bias"].numpy()) for i in (0, 2, 4, 6)]
 
 
+class FrameStack:
+    """The deploy side of env.frame_stack (humanoid-gym's sim2sim deque): the last H single observations side by side, oldest first, newest last,
+    all zeros before the first push and after reset()."""
+
+    def __init__(self, frames, width=47):
+        self.frames, self.width = int(frames), int(width)
+        self.reset()
+
+    def reset(self):
+        self.row = np.zeros(self.frames * self.width)
+
+    def push(self, obs):
+        """Append the newest single observation, drop the oldest; returns the stacked row [frames * width] (a view: copy it to keep it)."""
+        self.row = np.concatenate([self.row[self.width :], np.asarray(obs, dtype=np.float64).reshape(self.width)])
+        return self.row
+
+
+def actor_frames(layers, width=47):
+    """Frames H of an actor whose first layer takes H * width inputs (ValueError otherwise)."""
+    k = int(layers[0][0].shape[1])
+    if k < width or k % width:
+        raise ValueError(f"the actor takes {k} inputs, not a multiple of the {width} single observations (env.frame_stack)")
+    return k // width
+
+
 def gait_frequency(cmd, cfg_commands, max_lin=1.0, max_ang=1.0):
     """play_mujoco.py:692-714: stand still below 0.1 of command magnitude, else scale the frequency with the command."""
     mag = float(np.sqrt(np.sum(np.square(cmd))))
@@ -51,6 +76,7 @@ def rollout(layers, cmd, seconds, cfg=None, dyn=None, model=None):
     gf, gp = gait_frequency(cmd, cfg["commands"]), 0.0
     actions, targets = np.zeros(12), default.copy()
     dec, dt = cfg["control"]["decimation"], cfg["sim"]["dt"]
+    stack = FrameStack(actor_frames(layers))  # (H = 1: the single observation itself)
     traj = []
     for it in range(int(round(seconds / dt))):
         if it % dec == 0:  # play_mujoco.py:733-748
@@ -60,7 +86,7 @@ def rollout(layers, cmd, seconds, cfg=None, dyn=None, model=None):
             o[6], o[7], o[8] = cmd[0] * nz["lin_vel"], cmd[1] * nz["lin_vel"], cmd[2] * nz["ang_vel"]
             o[9], o[10] = np.cos(2 * np.pi * gp) * (gf > 1e-8), np.sin(2 * np.pi * gp) * (gf > 1e-8)
             o[11:23], o[23:35], o[35:47] = (q - default) * nz["dof_pos"], qd * nz["dof_vel"], actions
-            x = o
+            x = stack.push(o)
             for k, (w, b) in enumerate(layers):
                 x = w @ x + b
                 if k < 3:
