@@ -127,6 +127,7 @@ class EnvCfg(C.Structure):
 
 # every symbol include/booster_gym_amd.h declares (tests check that the .so exports all of them)
 HEAD_SCRATCH_FLOATS = 768 * 1720  # BG_HEAD_SCRATCH_FLOATS
+OBS_MOMENTS_MAX_GROUPS = 1024  # BG_OBS_MOMENTS_MAX_GROUPS
 
 SYMBOLS = [
     "bg_model_create", "bg_model_get", "bg_model_destroy", "bg_model_load_urdf", "bg_model_body_name", "bg_model_dof_name", "bg_model_find_body", "bg_env_create", "bg_env_destroy", "bg_env_set_heightfield",
@@ -138,6 +139,7 @@ SYMBOLS = [
     "bg_critic_head_forward", "bg_actor_head", "bg_critic_head_backward",
     "bg_reduce_group", "bg_actor_head_partial", "bg_critic_head_backward_partial", "bg_mlp_layer_backward_partial",
     "bg_actor_head_sym", "bg_actor_head_sym_partial", "bg_mirror_rows",
+    "bg_obs_moments", "bg_obs_normalize",
     "bg_last_error", "bg_version",
 ]
 
@@ -230,6 +232,8 @@ def load():
         "bg_actor_head_sym": (i32, [i32] + [vp] * 10 + [f32] * 4 + [vp] * 11),
         "bg_actor_head_sym_partial": (i32, [i32] + [vp] * 10 + [f32] * 4 + [vp] * 10 + [C.POINTER(ReduceProblem), vp]),
         "bg_mirror_rows": (i32, [i32, i32, vp, vp, vp, vp, vp]),
+        "bg_obs_moments": (i32, [i32, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp]),
+        "bg_obs_normalize": (i32, [i32, i32, vp, i32, vp, i32, i32, vp, vp, i32, vp]),
         "bg_last_error": (C.c_char_p, []),
         "bg_version": (C.c_char_p, []),
     }

@@ -17,8 +17,11 @@ that enqueue the same communicator's collectives in different orders dead-lock o
     statistics / log-std exchange, once per mini-epoch, inside Runner._epoch_gradients_and_step).  In the default one-stream mini-epoch
     (Runner._epoch_on_one_stream) both are enqueued on the MAIN stream: one communicator, one stream.  With BG_ONE_STREAM=0 "moments" is enqueued on
     the side stream (Runner._epoch_on_two_streams) and "bucket" on the main stream: one communicator driven from two streams of a rank;
+    with algorithm.empirical_normalization (and only then) tag "obs_norm": ONE float64 vector [column sums, column sums of squares, row count] of
+    the iteration's observation rows, once per ITERATION, enqueued on the main stream behind the last mini-epoch's "bucket" (Runner.update ->
+    ObsNormalizer.update_from), after which every rank merges the same totals into identical statistics;
   * the PROCESS GROUP's communicator for everything outside the mini-epochs (seed, initial weights, curriculum grid, barriers).
-The host enqueues strictly in program order -- moments(e), bucket(e), moments(e + 1), ... -- on every rank, whatever the streams do on the device, and
+The host enqueues strictly in program order -- moments(e), bucket(e), moments(e + 1), ..., bucket(last), [obs_norm] -- on every rank, whatever the streams do on the device, and
 nothing else touches the own communicator; the process group's collectives are issued only between iterations.  Any change that makes the ORDER OF
 HOST CALLS depend on rank-local data (an early exit, a rank-dependent branch around an exchange) breaks the contract.  `BG_DP_LOG_ORDER=1` records the
 sequence of (tag, stream) per rank (DataParallel.order_log); tests/test_host_logic.py compares it across the ranks of a two-process job.

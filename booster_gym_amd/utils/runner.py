@@ -46,6 +46,7 @@ from .. import _lib
 from ..envs import TASKS
 from .buffer import ExperienceBuffer
 from .config import load_cfg
+from .obs_norm import ObsNormalizer, check_checkpoint, normalization_cfg
 from .model import ACTOR_HIDDEN, CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, MLPTrainer, NetPlan, check_hidden, hidden_of, plan_network
 from .parallel import DataParallel
 from .recorder import Recorder
@@ -281,11 +282,15 @@ class Runner:
             raise ValueError("rl_device must equal sim_device: the rollout writes simulator outputs straight into the PPO buffers")
         self.learning_rate = self.cfg["algorithm"]["learning_rate"]
         self._symmetry, self._symmetric_coef = symmetry_loss(self.cfg)
+        obs_norm_on, obs_norm_eps = normalization_cfg(self.cfg)  # (ValueError for normalization_eps <= 0)
         if self._symmetry:  # (ValueError for a model without a left / right pairing or with an asymmetric default pose)
             obs_src, obs_sign, act_src, act_sign = self.env.mirror_maps()
             self._act_mirror = (act_src.tolist(), act_sign.tolist())
         self.model = ActorCritic(self.env.num_actions, self.env.num_obs, self.env.num_privileged_obs, self.actor_hidden, self.critic_hidden).to(self.device)
         self.dp.broadcast_parameters(self.model)  # identical initial weights on every rank
+        # algorithm.empirical_normalization: running mean / variance of the critic's input columns (the actor's are its first num_obs), applied where rows
+        # enter a network and updated at the end of update(); None = off, the one switch every branch below reads
+        self.obs_norm = ObsNormalizer(self.env.num_obs + self.env.num_privileged_obs, obs_norm_eps, self.device) if obs_norm_on else None
         self.invalidate()
         self.optimizer = FlatAdam(self.model.parameters(), lr=self.learning_rate)
         self._load()
@@ -325,6 +330,11 @@ class Runner:
             kin = self._pad_actor or self.env.num_obs
             self._actor_in = torch.zeros(2 * T, N, kin, device=dev)
             self._obs_mirror = (obs_src.tolist() + [-1] * (kin - len(obs_src)), obs_sign.tolist() + [1.0] * (kin - len(obs_sign)))
+        if self.obs_norm is not None:
+            self._obs_normed = torch.zeros(N, no, device=dev)  # one step's normalised rows: what the sampling kernel reads in rollout()
+            if self._symmetry:  # the mirror images of the raw batch, normalised into rows [B, 2B) of the actor's input
+                self._mirror_raw = torch.zeros(B, no, device=dev)
+                self._obs_mirror_raw = (obs_src.tolist(), obs_sign.tolist())
         self._adv = torch.zeros(T, N, device=dev)
         self._ret = torch.zeros(T, N, device=dev)
         self._adv_sums = torch.zeros(3, dtype=torch.float64, device=dev)
@@ -460,6 +470,7 @@ class Runner:
             raise ValueError(f"checkpoint {ck} has actor hidden widths {list(ck_a)} and critic hidden widths {list(ck_c)}, the config "
                              f"algorithm.actor_hidden = {list(self.actor_hidden)} and algorithm.critic_hidden = {list(self.critic_hidden)}: set these to the "
                              "checkpoint's widths")
+        check_checkpoint(ck, model_dict.get("obs_normalizer"), self.obs_norm)  # (ValueError naming algorithm.empirical_normalization)
         self.model.load_state_dict(model_dict["model"], strict=False)
         self.invalidate()
         try:
@@ -494,6 +505,8 @@ class Runner:
         d = {"model": self.model.state_dict(), "optimizer": self.optimizer.state_dict(), "curriculum": self.env.curriculum_prob}
         if self.env.terrain.curriculum:
             d["terrain_levels"] = self.env.terrain_levels
+        if self.obs_norm is not None:
+            d["obs_normalizer"] = self.obs_norm.state_dict()
         return d
 
     # ------------------------------------------------------------------ one PPO iteration
@@ -530,12 +543,16 @@ class Runner:
             self._actor_tr.prepare(self._actor_in.reshape(T * N, -1))
         main = torch.cuda.current_stream()
         g, start = self._rollout_group, 0
+        norm = self.obs_norm
         with torch.no_grad():
             for n in range(T):
                 if plan.ahead and n + 1 - start >= g:
                     self._forward_rows(start, n, main)  # rows of steps start .. n: on the side stream, beside this step's launches
                     start = n + 1
-                self.model.sample_actions(obses[n], buf["actions"][n], seed, self._act_counter)
+                if norm is None:
+                    self.model.sample_actions(obses[n], buf["actions"][n], seed, self._act_counter)
+                else:  # the buffer keeps the raw rows; the actor samples from their normalised copy (one more launch per step: bg_obs_normalize)
+                    self.model.sample_actions(norm.normalize_into(obses[n], self._obs_normed), buf["actions"][n], seed, self._act_counter)
                 self._act_counter += 1
                 self.env.step_to(buf["actions"][n], obses[n + 1], priv[n + 1], buf["rewards"][n], buf["dones"][n], buf["time_outs"][n])
             if plan.ahead:
@@ -562,11 +579,15 @@ class Runner:
                 r0, r1 = self._logp_done * N, a * N
                 gaussian_logp(self._old_mu[r0:r1], logstd, buf["actions"][self._logp_done : a].reshape(-1, self.env.num_actions), out=self._old_logp[r0:r1])
                 self._logp_done = a
-            self._critic_in[a : b + 1, :, :no].copy_(buf["obses"][a : b + 1])
-            self._critic_in[a : b + 1, :, no : no + npv].copy_(buf["privileged_obses"][a : b + 1])
+            if self.obs_norm is not None:  # (valid ahead of the update: the statistics change only at its end)
+                self._normalize_inputs(a, b + 1, ba + 1)
+            else:
+                self._critic_in[a : b + 1, :, :no].copy_(buf["obses"][a : b + 1])
+                self._critic_in[a : b + 1, :, no : no + npv].copy_(buf["privileged_obses"][a : b + 1])
             jobs = [(ct, a * N, (b + 1 - a) * N)]
             if a <= ba:
-                self._actor_in[a : ba + 1, :, :no].copy_(buf["obses"][a : ba + 1])
+                if self.obs_norm is None:
+                    self._actor_in[a : ba + 1, :, :no].copy_(buf["obses"][a : ba + 1])
                 jobs.append((at, a * N, (ba + 1 - a) * N))
             MLPTrainer.launch_chain([tr.chain_rows_descriptor(r0, nr) for tr, r0, nr in jobs])  # ONE launch (at most 4 jobs)
             if a <= ba:
@@ -576,6 +597,17 @@ class Runner:
                 r0 = self._logp_done * N
                 gaussian_logp(self._old_mu[r0:], logstd, buf["actions"][self._logp_done :].reshape(-1, self.env.num_actions), out=self._old_logp[r0:])
                 self._logp_done = T
+
+    def _normalize_inputs(self, a, b, b_actor):
+        """algorithm.empirical_normalization: the padded network inputs of steps [a, b) (critic: observation and privileged block) and [a, b_actor)
+        (actor) from the raw rows of the experience buffer through bg_obs_normalize, on the current stream, in place of the copies; with the
+        statistics as they are (they change only at the end of update()); the padded columns stay zero."""
+        buf, no, norm = self.buffer, self.env.num_obs, self.obs_norm
+        ci, ai = self._critic_in, self._actor_in
+        norm.normalize_into(buf["obses"][a:b], ci[a:b, :, :no])
+        norm.normalize_into(buf["privileged_obses"][a:b], ci[a:b, :, no:], col0=no, dst_cols=ci.shape[-1] - no)
+        if ai is not None and a < b_actor:
+            norm.normalize_into(buf["obses"][a:b_actor], ai[a:b_actor], dst_cols=ai.shape[-1])
 
     def update(self):
         """runner.py:123-189: old log-probs, then mini_epochs full-batch optimiser steps.
@@ -593,6 +625,10 @@ class Runner:
                 else:
                     self._epoch_on_two_streams(u, have_fwd)
                 self._epoch_gradients_and_step(u)
+            if self.obs_norm is not None:
+                # behind the last optimiser step: this iteration's T x N rows enter the statistics (row T is the next iteration's row 0), under data
+                # parallelism all ranks' rows through ONE float64 exchange (tag "obs_norm", main stream, behind the last "bucket": utils/parallel.py)
+                self.obs_norm.update_from(u.buf["obses"][: u.T], u.buf["privileged_obses"][: u.T], self.dp)
         return self._stats_acc
 
     def _update_begin(self, plan):
@@ -610,13 +646,24 @@ class Runner:
         if not ahead:
             torch.cuda.current_stream().wait_stream(self._side_stream)  # a forward-ahead being discarded may still write these buffers
             self._actor_tr.mirror_fresh = self._critic_tr.mirror_fresh = False  # weights may have changed outside the loop below (checkpoint, broadcast)
-            self._critic_in[:, :, :no].copy_(buf["obses"])
-            self._critic_in[:, :, no : no + npv].copy_(buf["privileged_obses"])
-            if self._actor_in is not None:
-                self._actor_in[:T, :, :no].copy_(buf["obses"][:T])
-            if plan.symmetry:  # rows [B, 2B): the mirror images M_o x of the batch
+            if self.obs_norm is not None:
+                self._normalize_inputs(0, T + 1, T)
+            else:
+                self._critic_in[:, :, :no].copy_(buf["obses"])
+                self._critic_in[:, :, no : no + npv].copy_(buf["privileged_obses"])
+                if self._actor_in is not None:
+                    self._actor_in[:T, :, :no].copy_(buf["obses"][:T])
+            if plan.symmetry and self.obs_norm is not None:  # rows [B, 2B): normalise(M_o x), what the policy computes on the mirrored raw observation
+                mirror_rows(buf["obses"][:T].reshape(B, -1), self._mirror_raw, *self._obs_mirror_raw)
+                self.obs_norm.normalize_into(self._mirror_raw, self._actor_in[T:].reshape(B, -1), dst_cols=self._actor_in.shape[-1])
+            elif plan.symmetry:  # rows [B, 2B): the mirror images M_o x of the batch
                 mirror_rows(self._actor_in[:T].reshape(B, -1), self._actor_in[T:].reshape(B, -1), *self._obs_mirror)
-        obs_flat = self._actor_in.reshape(-1, self._actor_in.shape[-1]) if self._actor_in is not None else buf["obses"][:T].reshape(B, -1)
+        if self._actor_in is not None:
+            obs_flat = self._actor_in.reshape(-1, self._actor_in.shape[-1])
+        elif self.obs_norm is not None:  # (no padded input: the per-layer library path reads the normalised rows from a copy of its own)
+            obs_flat = self.obs_norm.normalize_into(buf["obses"][:T].reshape(B, -1), torch.empty(B, no, device=self.device))
+        else:
+            obs_flat = buf["obses"][:T].reshape(B, -1)
         critic_all = self._critic_in.reshape((T + 1) * N, -1)  # rows [B, B+N) = the observation after the last step (last_values)
         logstd_flat = self.model.logstd.reshape(-1)
         a_out, c_out = self._actor_tr.layers[-1], self._critic_tr.layers[-1]
@@ -877,6 +924,7 @@ class Runner:
         self._log_host = [torch.zeros(n, dtype=torch.float64).pin_memory() for _ in range(2)]
         self._log_event = [torch.cuda.Event() for _ in range(2)]
         self._log_pending = None
+        self._log_obs_norm = [None, None]
         self.nonfinite_resets_total = 0.0  # over the whole run (the per-iteration accumulator is reset when it is read)
 
     def _flush_log(self):
@@ -898,6 +946,8 @@ class Runner:
                         "curriculum/max_lin_vel_level": self.env.max_lin_vel_level, "curriculum/max_ang_vel_level": self.env.max_ang_vel_level})
         if self.env.terrain.curriculum:  # this rank's envs only under data parallelism
             summary["terrain/mean_level"] = s[h + ne + 4] / self.env.num_envs
+        if self.obs_norm is not None:
+            summary.update(self._log_obs_norm[slot])
         self.recorder.record_statistics(summary, it)
 
     def train_iteration(self, it):
@@ -920,6 +970,8 @@ class Runner:
         self._log_host[slot].copy_(d, non_blocking=True)
         self._log_event[slot].record()
         self._log_pending = (slot, it)
+        if self.obs_norm is not None:  # (host values already: written with this iteration's scalars, one iteration later)
+            self._log_obs_norm[slot] = self.obs_norm.scalars()
         if (it + 1) % self.cfg["runner"]["save_interval"] == 0:
             self.recorder.save(self.checkpoint_dict(), it + 1)
 
@@ -940,6 +992,8 @@ class Runner:
         try:
             while max_steps is None or step < max_steps:
                 with torch.no_grad():
+                    if self.obs_norm is not None:
+                        obs = self.obs_norm.normalize_into(obs, torch.empty_like(obs))
                     act = self.model.actor(obs)
                     obs, rew, done, infos = self.env.step(act)
                 if record_path is not None:

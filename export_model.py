@@ -1,6 +1,7 @@
 """python export_model.py --task=T1 [--checkpoint path|-1]: TorchScript export of the actor (reference export_model.py:8-30) so that
 the reference's deployment code (deploy/utils/policy.py:9) can load what this framework trains.  The actor's widths are read from the checkpoint's tensors (any supported architecture, with or without the terrain height
-scan or a frame stack, exports without editing the YAML); the TorchScript module is still a plain Sequential."""
+scan or a frame stack, exports without editing the YAML); the TorchScript module is still a plain Sequential.  A checkpoint trained with
+algorithm.empirical_normalization carries its observation statistics: they are folded into the actor's first layer, so the exported module takes raw observations."""
 import argparse
 import glob
 import os
@@ -20,7 +21,8 @@ if __name__ == "__main__":
     if ck in ("-1", None):
         ck = sorted(glob.glob(os.path.join("logs", "**/*.pth"), recursive=True), key=os.path.getmtime)[-1]
     print("Loading model from {}".format(ck))
-    sd = torch.load(ck, map_location="cpu", weights_only=True)["model"]
+    ckpt = torch.load(ck, map_location="cpu", weights_only=True)
+    sd = ckpt["model"]
     # the actor's input from the checkpoint (47, or 47 H with env.frame_stack), and the critic's privileged inputs too (14, or 14 + P with
     # terrain.measure_heights); only the actor is exported
     num_obs = int(sd["actor.0.weight"].shape[1])
@@ -28,6 +30,19 @@ if __name__ == "__main__":
     model = ActorCritic(cfg["env"]["num_actions"], num_obs, num_priv, actor_hidden=hidden_of(sd, "actor"),
                         critic_hidden=hidden_of(sd, "critic"))
     model.load_state_dict(sd)
+    if ckpt.get("obs_normalizer") is not None:
+        # algorithm.empirical_normalization: the statistics go into the first Linear layer (W' = W diag(inv_std), b' = b - W' mean), so the exported
+        # module still takes the raw observation deploy/utils/policy.py builds
+        from booster_gym_amd.utils.obs_norm import ObsNormalizer
+
+        st = ckpt["obs_normalizer"]
+        norm = ObsNormalizer(int(st["mean"].numel()), float(st["eps"]))
+        norm.load_state_dict(st)
+        w, b = norm.fold_into_first_layer(model.actor[0].weight, model.actor[0].bias)
+        with torch.no_grad():
+            model.actor[0].weight.copy_(w)
+            model.actor[0].bias.copy_(b)
+        print("Folded the observation normaliser ({} columns, count {:.0f}) into the actor's first layer".format(norm.cols, norm.count))
     os.makedirs("deploy/models", exist_ok=True)
     out = os.path.join("deploy", "models", f"{args.task}.pt")
     torch.jit.script(model.actor).save(out)

@@ -560,6 +560,25 @@ int bg_critic_head_backward_partial(int32_t B, const float* h, const float* w, c
 int bg_mlp_layer_backward_partial(int32_t M, int32_t K, int32_t N, const float* G, const float* Wt, const float* act_below, float* Gout,
                                   float* bias_grad_below, float* scratch, bg_reduce_problem* finish, void* stream);
 
+/* ---- empirical observation normalisation (algorithm.empirical_normalization; bg_obs_norm.hip).  Two launches of their own beside the hot path:
+ * nothing of them runs when the key is false.
+ *
+ * bg_obs_moments: sum[c] = sum over r of x[r][c] and sumsq[c] = sum over r of x[r][c]^2 in float64 for the row-major fp32 matrix x [rows][cols_a +
+ * cols_b] given as two column blocks with their own row strides in floats (a: columns [0, cols_a), 1 to 512; b: the cols_b columns behind them,
+ * 0 to 201, b may be NULL when cols_b is 0): the observation and the privileged block of an experience buffer, without a concatenated copy.
+ * Fixed summation order, no floating-point atomics: every workgroup leaves one record [2][cols_a + cols_b] in `scratch` (float64, at least
+ * BG_OBS_MOMENTS_MAX_GROUPS * 2 * (cols_a + cols_b) values) and a second small launch adds the records in a fixed order; the grid depends on `rows`
+ * alone, so the same input gives the same bits on every device.  sum / sumsq: float64 [cols_a + cols_b], overwritten. */
+#define BG_OBS_MOMENTS_MAX_GROUPS 1024
+int bg_obs_moments(int32_t rows, const float* a, int32_t cols_a, int32_t stride_a, const float* b, int32_t cols_b, int32_t stride_b, double* sum,
+                   double* sumsq, double* scratch, void* stream);
+/* dst[r][c] = (src[r][c] - mean[col0 + c]) * inv_std[col0 + c] for c < cols and 0 for cols <= c < dst_cols, r < rows: the fp32 subtract rounded,
+ * then the fp32 multiply rounded (never contracted), so every call gives the same bits for the same row.  src_stride / dst_stride: row strides in
+ * floats (cols <= src_stride, cols <= dst_cols <= dst_stride); dst_cols - cols = the zero padding of a network input behind the block (dst_cols at
+ * most 512); col0 + cols at most 713.  src is not written; src and dst must not overlap. */
+int bg_obs_normalize(int32_t rows, int32_t cols, const float* src, int32_t src_stride, float* dst, int32_t dst_cols, int32_t dst_stride,
+                     const float* mean, const float* inv_std, int32_t col0, void* stream);
+
 const char* bg_last_error(void);
 const char* bg_version(void);
 

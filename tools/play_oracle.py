@@ -19,8 +19,24 @@ def load_actor(path):
         return [(W[f"{i}.weight"], W[f"{i}.bias"]) for i in (0, 2, 4, 6)]
     import torch
 
-    sd = torch.load(path, map_location="cpu", weights_only=True)["model"]
-    return [(sd[f"actor.{i}.weight"].numpy(), sd[f"actor.{i}.bias"].numpy()) for i in (0, 2, 4, 6)]
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    sd = ck["model"]
+    layers = [(sd[f"actor.{i}.weight"].numpy(), sd[f"actor.{i}.bias"].numpy()) for i in (0, 2, 4, 6)]
+    if ck.get("obs_normalizer") is not None:
+        # algorithm.empirical_normalization: the actor was trained on (x - mean) / (sqrt(var) + eps); the first layer takes the statistics in, so the
+        # loop below feeds raw observations as the deployed policy does (export_model.py folds the same way)
+        layers[0] = tuple(t.numpy() for t in normalizer_of(ck).fold_into_first_layer(*layers[0]))
+    return layers
+
+
+def normalizer_of(ck):
+    """The ObsNormalizer (host only) a checkpoint carries under "obs_normalizer"."""
+    from booster_gym_amd.utils.obs_norm import ObsNormalizer
+
+    st = ck["obs_normalizer"]
+    norm = ObsNormalizer(int(st["mean"].numel()), float(st["eps"]))
+    norm.load_state_dict(st)
+    return norm
 
 
 class FrameStack:
