@@ -84,6 +84,11 @@ class MlpLayerDesc(C.Structure):
     _fields_ = [("W", C.c_void_p), ("b", C.c_void_p), ("in_", C.c_int32), ("out", C.c_int32)]
 
 
+class GatherStream(C.Structure):
+    """bg_gather_stream: one row-major fp32 stream of bg_gather_rows (include/booster_gym_amd.h)."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("width", C.c_int32), ("pad", C.c_int32)]
+
+
 class Rand(C.Structure):
     _fields_ = [("mode", C.c_int32), ("a", C.c_float), ("b", C.c_float)]
 
@@ -128,6 +133,7 @@ class EnvCfg(C.Structure):
 # every symbol include/booster_gym_amd.h declares (tests check that the .so exports all of them)
 HEAD_SCRATCH_FLOATS = 768 * 1720  # BG_HEAD_SCRATCH_FLOATS
 OBS_MOMENTS_MAX_GROUPS = 1024  # BG_OBS_MOMENTS_MAX_GROUPS
+GATHER_MAX_STREAMS = 8  # BG_GATHER_MAX_STREAMS
 
 SYMBOLS = [
     "bg_model_create", "bg_model_get", "bg_model_destroy", "bg_model_load_urdf", "bg_model_body_name", "bg_model_dof_name", "bg_model_find_body", "bg_env_create", "bg_env_destroy", "bg_env_set_heightfield",
@@ -140,6 +146,7 @@ SYMBOLS = [
     "bg_reduce_group", "bg_actor_head_partial", "bg_critic_head_backward_partial", "bg_mlp_layer_backward_partial",
     "bg_actor_head_sym", "bg_actor_head_sym_partial", "bg_mirror_rows",
     "bg_obs_moments", "bg_obs_normalize",
+    "bg_perm_fill", "bg_gather_rows",
     "bg_last_error", "bg_version",
 ]
 
@@ -234,6 +241,8 @@ def load():
         "bg_mirror_rows": (i32, [i32, i32, vp, vp, vp, vp, vp]),
         "bg_obs_moments": (i32, [i32, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp]),
         "bg_obs_normalize": (i32, [i32, i32, vp, i32, vp, i32, i32, vp, vp, i32, vp]),
+        "bg_perm_fill": (i32, [i32, u64, C.c_uint32, C.c_uint32, vp, vp]),
+        "bg_gather_rows": (i32, [i32, i32, vp, C.POINTER(GatherStream), i32, vp]),
         "bg_last_error": (C.c_char_p, []),
         "bg_version": (C.c_char_p, []),
     }

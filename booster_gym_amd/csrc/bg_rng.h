@@ -57,6 +57,7 @@ enum {
     RS_CMD1 = 25,     // still, resample time
     RS_CURR = 26,     // curriculum: grid cell, cmd x / y / yaw jitter
     RS_TLEVEL = 27,   // terrain curriculum: the level of an env that passed the top one
+    RS_PERM = 28,     // mini-batch shuffle: the Feistel round functions of bg_perm.h (counter words: half, round | mini-epoch << 8, this, update)
     RS_ACTOR = 32     // + k : action noise (bg_actor_sample)
 };
 

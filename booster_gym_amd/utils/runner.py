@@ -105,6 +105,31 @@ def symmetry_loss(cfg):
     return True, float(coef)
 
 
+def mini_batches(cfg):
+    """(on, K) of runner.num_mini_batches (an addition of this build, rsl_rl's name; absent or 1 = off: (False, 1)): every mini-epoch takes K optimiser
+    steps on disjoint shuffled K-ths of the batch of B = runner.horizon_length x env.num_envs rows (per rank) instead of one step on all of it.
+    ValueError unless K is an integer >= 1 that divides B into whole 128-row slabs (the chained kernels store every slab in full; the grouped
+    weight gradients need rows % 32 == 0 and >= 128); and, for now, with algorithm.symmetry_loss."""
+    K = (cfg.get("runner", {}) or {}).get("num_mini_batches", 1)
+    if K is None:
+        K = 1
+    if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+        raise ValueError(f"runner.num_mini_batches must be an integer >= 1, got {K!r}")
+    if K == 1:
+        return False, 1
+    T, N = int(cfg["runner"]["horizon_length"]), int(cfg["env"]["num_envs"])
+    B = T * N
+    if B % K:
+        raise ValueError(f"runner.num_mini_batches = {K} does not divide the batch of runner.horizon_length x env.num_envs = {T} x {N} = {B} rows")
+    if (B // K) % 128:
+        raise ValueError(f"runner.num_mini_batches = {K} gives mini-batches of {B} / {K} = {B // K} rows, which is not a multiple of 128 (the kernels work "
+                         "on whole 128-row slabs)")
+    if symmetry_loss(cfg)[0]:
+        raise ValueError(f"runner.num_mini_batches = {K} together with algorithm.symmetry_loss is not supported: set runner.num_mini_batches to 1 or "
+                         "algorithm.symmetry_loss to false")
+    return True, K
+
+
 class UpdatePlan(NamedTuple):
     """The kernels of one Runner.update() and of the rollout's forward-ahead (plan_update): resolved once per call, read by every branch."""
     critic: NetPlan
@@ -271,6 +296,7 @@ class Runner:
         self.actor_hidden, self.critic_hidden = hidden_widths(self.cfg)  # (before anything is built: a width outside the supported set is a ValueError)
         if self.world_size > 1:  # one process per GPU: each rank simulates and learns on its own device
             self.cfg["basic"]["sim_device"] = self.cfg["basic"]["rl_device"] = f"cuda:{self.dp.device_index}"
+        self._mini_batches = mini_batches(self.cfg)[1]  # (ValueError before anything is built; 1 = off: the one switch every branch below reads)
         self._set_seed()
         task = self.cfg["basic"]["task"]
         if task not in TASKS:
@@ -405,6 +431,8 @@ class Runner:
         self._rollout_group = max(1, int(os.environ.get("BG_ROLLOUT_FORWARD_GROUP", "2")))
         self._fwd_plan = None  # the UpdatePlan under which rollout() has left the activations / values / old mu of the whole batch in the trainers' buffers
         self.timers = {"rollout": 0.0, "update": 0.0}
+        if self._mini_batches > 1:
+            self._init_mini_batches()
         if self._symmetry:
             self._resolve_plan()  # (a plan the symmetric head cannot serve is a ValueError here, not at the first update)
 
@@ -497,7 +525,7 @@ class Runner:
         buffers and the weight copies that the layer kernels read current, and update() then trusts both without looking; this forgets them, so the
         next update() recomputes everything from the parameters and the buffers as they are."""
         self._fwd_plan = None
-        for tr in (getattr(self, "_actor_tr", None), getattr(self, "_critic_tr", None)):
+        for tr in (getattr(self, "_actor_tr", None), getattr(self, "_critic_tr", None), getattr(self, "_actor_mb", None), getattr(self, "_critic_mb", None)):
             if tr is not None:
                 tr.mirror_fresh = False
 
@@ -522,7 +550,122 @@ class Runner:
         ct.plan, at.plan = plan.critic, plan.actor
         c_out = ct.layers[-1]
         ct.value_head = (c_out.weight.reshape(-1), c_out.bias, self._values_all) if plan.chain_values else None
+        if self._mini_batches > 1:
+            # runner.num_mini_batches: the plan above serves the whole-batch passes (forward-ahead, old mu, values + GAE); the K optimiser steps of a
+            # mini-epoch run a plan of their own for b = B / K rows on the second pair of trainers
+            mp = self._mb_plan = plan_update((widths(ct), self._critic_in.shape[-1]), (widths(at), kin_a), self._mb_rows, dp_active=self.dp.active, **sw)
+            self._critic_mb.plan, self._actor_mb.plan = mp.critic, mp.actor
+            self._critic_mb.value_head = (c_out.weight.reshape(-1), c_out.bias, self._mb_values) if mp.chain_values else None
         return plan
+
+    # ------------------------------------------------------------------ runner.num_mini_batches > 1
+    def _init_mini_batches(self):
+        """What K = runner.num_mini_batches > 1 adds to the runner: a second pair of trainers over the same Linear modules, sized for b = B / K rows (they
+        share the parameters and the .grad views of the flat Adam buffer; a trainer reallocates its workspaces and weight planes when its row count
+        changes, so the whole-batch pair is never flipped to b rows), the permutation and the gathered copies of every per-row stream the steps read."""
+        K, B, A, dev = self._mini_batches, self._old_logp.numel(), self.env.num_actions, self.device
+        b = self._mb_rows = B // K
+        self._actor_mb, self._critic_mb = MLPTrainer(self.model.actor), MLPTrainer(self.model.critic)
+        # the grouped weight-gradient launch keeps its descriptors per input buffer: one per mini-batch position (static after the first mini-epoch)
+        self._mb_wgrad = [GroupedWeightGrad() for _ in range(K)]
+        self._perm = torch.zeros(B, dtype=torch.int32, device=dev)
+        ka = self._actor_in.shape[-1] if self._actor_in is not None else self.env.num_obs
+        f = lambda *shape: torch.zeros(*shape, device=dev)
+        self._mb = types.SimpleNamespace(critic_in=f(B, self._critic_in.shape[-1]), actor_in=f(B, ka), actions=f(B, A), old_mu=f(B, A), old_logp=f(B), adv=f(B), ret=f(B))
+        self._mb_values = f(b)
+        self._mb_updates = 0  # the update counter of the permutation's key
+
+    def permutation(self, update, epoch, out=None):
+        """The permutation of [0, B) that mini-epoch `epoch` of this rank's update number `update` shuffles its rows with (bg_perm_fill), as an int32
+        device tensor: keyed by (basic.seed with the rank folded in as in the rollout's action noise, update, epoch)."""
+        out = torch.empty_like(self._perm) if out is None else out
+        seed = (int(self.cfg["basic"]["seed"]) + 1000003 * (self.rank + 1)) & 0xFFFFFFFFFFFFFFFF
+        _lib.check(_lib.load().bg_perm_fill(out.numel(), seed, int(update) & 0xFFFFFFFF, int(epoch), _lib.ptr(out), _lib.current_stream_ptr()), "bg_perm_fill")
+        return out
+
+    def _mini_batch_begin(self, u):
+        """Once per update(): the optimiser steps run on the mini-batch trainers under their own plan; the CU shares of their launches are sized for
+        b-row slabs; the descriptors of the gather."""
+        m, b = self._mb, self._mb_rows
+        u.ct, u.at, u.step_plan, u.rows = self._critic_mb, self._actor_mb, self._mb_plan, b
+        self._plan_chain_split(m.critic_in[:b], m.actor_in[:b], u.step_plan, u.ct, u.at)
+        # the whole-batch passes of this update run one network at a time (old mu; the critic's values): one workgroup per slab, no CU share
+        self._critic_tr.chain_workgroups = self._actor_tr.chain_workgroups = 0
+        B = u.B
+        pairs = [(u.critic_all[:B], m.critic_in), (u.obs_flat[:B], m.actor_in), (u.act_flat, m.actions), (u.old_mu, m.old_mu), (self._old_logp, m.old_logp),
+                 (self._adv.view(B), m.adv), (self._ret.view(B), m.ret)]
+        for src, dst in pairs:
+            if not (src.is_contiguous() and src.dtype == torch.float32 and src.shape == dst.shape):
+                raise RuntimeError(f"mini-batch gather: a stream of shape {tuple(src.shape)} does not match its buffer {tuple(dst.shape)}")
+        u.gather = (_lib.GatherStream * len(pairs))(*[_lib.GatherStream(src.data_ptr(), dst.data_ptr(), src.numel() // B, 0) for src, dst in pairs])
+        u.gather_keep = pairs
+
+    def _whole_batch_values(self, u, have_fwd):
+        """The whole-batch pass of a mini-epoch, exactly as with one step per mini-epoch (runner.py:132-145): the critic on all (T + 1) N rows with
+        the current weights (in mini-epoch 0 the rollout's forward-ahead where the plan has it), time-out bootstrap, GAE, returns, advantage moments
+        and their exchange.  On the main stream."""
+        buf, T, N, B, alg, c_out, plan, ct = u.buf, u.T, u.N, u.B, u.alg, u.c_out, u.plan, self._critic_tr
+        if have_fwd:
+            u.main.wait_stream(u.side)  # the rollout ran the forward passes on the side stream
+        else:
+            ct.mirror_fresh = False  # the optimiser launch keeps the mini-batch trainers' weight copies current, not this trainer's
+        if plan.fused_head:
+            hc = ct.acts[2] if have_fwd else ct.forward_hidden(u.critic_all, train_rows=B)
+            if plan.fused_gae:
+                v_all = critic_values_gae(None if plan.chain_values else hc, c_out.weight, c_out.bias, buf["rewards"], buf["dones"], buf["time_outs"],
+                                          alg["gamma"], alg["lam"], self._values_all, self._adv, self._ret, self._adv_sums, self._gae_scratch)
+            else:
+                v_all = critic_head_forward(hc, c_out.weight, c_out.bias, self._values_all)
+        else:
+            v_all = ct.forward(u.critic_all, train_rows=B).squeeze(-1)
+        if not (plan.fused_head and plan.fused_gae):
+            gae(buf["rewards"], buf["dones"], buf["time_outs"], v_all[:B].view(T, N), v_all[B:], alg["gamma"], alg["lam"],
+                advantages=self._adv, returns=self._ret, sums=self._adv_sums)
+        self.dp.sum_(self._adv_sums, tag="moments")  # exchange (1)
+
+    def _shuffle(self, u, epoch):
+        """A fresh permutation of the batch's rows and ONE gather of every per-row stream the K steps read, mini-batch after mini-batch."""
+        self.permutation(self._mb_updates, epoch, out=self._perm)
+        _lib.check(_lib.load().bg_gather_rows(u.B, u.B, _lib.ptr(self._perm), u.gather, len(u.gather), _lib.current_stream_ptr()), "bg_gather_rows")
+
+    def _mini_batch_step(self, u, k):
+        """Optimiser step k of a mini-epoch up to its backward-data passes, on rows [k b, (k + 1) b) of the gathered buffers: today's launch
+        sequence on the main stream -- both forward passes, the critic's values on those rows, both output layers fused with the loss, both
+        backward-data passes.  Advantages and returns are the whole-batch pass's; the advantages are normalised with its moments.  Leaves fins /
+        fin_c / fin_a in u for _epoch_gradients_and_step."""
+        m, b, plan, ct, at, alg, a_out, c_out = self._mb, self._mb_rows, u.step_plan, u.ct, u.at, u.alg, u.a_out, u.c_out
+        r = slice(k * b, (k + 1) * b)
+        x_c, x_a = m.critic_in[r], m.actor_in[r]
+        u.wgrad_group = self._mb_wgrad[k]
+        fins = fin_c = fin_a = None
+        if plan.fused_head:
+            if plan.one_stream:
+                hc, ha = MLPTrainer.forward_hidden_group([(ct, x_c, None), (at, x_a, None)])
+            else:
+                hc, ha = ct.forward_hidden(x_c), at.forward_hidden(x_a)
+            values = self._mb_values if plan.chain_values else critic_head_forward(hc, c_out.weight, c_out.bias, self._mb_values)
+            if plan.defer:
+                fins, fin_c, fin_a = [], _lib.ReduceProblem(), _lib.ReduceProblem()
+            critic_head_backward(hc, c_out.weight, values, m.ret[r], ct.hidden_grad, c_out.weight.grad, c_out.bias.grad, ct.layers[-2].bias.grad, self._stats,
+                                 self._head_scratch_c, finish=fin_c)
+            actor_head_loss_backward(ha, a_out.weight, a_out.bias, u.logstd_flat, m.actions[r], m.old_mu[r], u.old_logstd, m.old_logp[r], m.adv[r], self._adv_sums,
+                                     0.2, alg["bound_coef"], alg["entropy_coef"], at.hidden_grad, a_out.weight.grad, a_out.bias.grad, at.layers[-2].bias.grad,
+                                     self._grad_logstd, self._stats, self._head_scratch_a, finish=fin_a)
+            if plan.ranks and not plan.defer:
+                self._exchange_sums()  # exchange (3)
+            if plan.one_stream:
+                MLPTrainer.backward_hidden_group([ct, at], fins)
+            else:
+                ct.backward_hidden(finishes=fins)
+                at.backward_hidden(finishes=fins)
+        else:
+            mu, values = at.forward(x_a), ct.forward(x_c).squeeze(-1)
+            ppo_loss_fused(mu, u.logstd_flat, m.actions[r], m.old_mu[r], u.old_logstd, m.old_logp[r], m.adv[r], self._adv_sums, values, m.ret[r], 0.2,
+                           alg["bound_coef"], alg["entropy_coef"], self._grad_mu[:b], self._grad_val[:b], self._grad_logstd, self._stats)
+            self._exchange_sums()  # exchange (3)
+            ct.backward(self._grad_val[:b].view(b, 1))
+            at.backward(self._grad_mu[:b])
+        u.fins, u.fin_c, u.fin_a = fins, fin_c, fin_a
 
     def rollout(self):
         """runner.py:106-121: horizon_length env steps with sampled actions, outputs written in place.
@@ -616,10 +759,22 @@ class Runner:
         method starts from them and from the weight copies the last optimiser launch wrote -- parameters and rollout buffers must not have been changed
         in between except through `invalidate()` (which `_load` and the initial broadcast call)."""
         u = self._update_begin(self._resolve_plan())
+        K = self._mini_batches
+        if K > 1:
+            self._mini_batch_begin(u)
         with torch.no_grad():
             for epoch in range(self.cfg["runner"]["mini_epochs"]):
                 # this mini-epoch's hidden activations and values may be the rollout's: same kernels, same weights
                 have_fwd = u.ahead and epoch == 0
+                if K > 1:
+                    # runner.num_mini_batches: the whole-batch pass once, then K optimiser steps on disjoint shuffled K-ths of the batch; returns and
+                    # advantages stay fixed for the K steps, the KL rule moves the learning rate after every one of them
+                    self._whole_batch_values(u, have_fwd)
+                    self._shuffle(u, epoch)
+                    for k in range(K):
+                        self._mini_batch_step(u, k)
+                        self._epoch_gradients_and_step(u)
+                    continue
                 if u.plan.one_stream:
                     self._epoch_on_one_stream(u, have_fwd)
                 else:
@@ -629,6 +784,9 @@ class Runner:
                 # behind the last optimiser step: this iteration's T x N rows enter the statistics (row T is the next iteration's row 0), under data
                 # parallelism all ranks' rows through ONE float64 exchange (tag "obs_norm", main stream, behind the last "bucket": utils/parallel.py)
                 self.obs_norm.update_from(u.buf["obses"][: u.T], u.buf["privileged_obses"][: u.T], self.dp)
+        if K > 1:
+            self._mb_updates += 1
+            self._actor_tr.mirror_fresh = self._critic_tr.mirror_fresh = False  # (the optimiser launches wrote the mini-batch trainers' copies)
         return self._stats_acc
 
     def _update_begin(self, plan):
@@ -685,7 +843,9 @@ class Runner:
         # (two streams, plan.one_stream = False: side stream = critic forward -> GAE ... critic backward; main stream = actor)
         return types.SimpleNamespace(cfg=cfg, buf=buf, T=T, N=N, B=B, A=A, alg=alg, act_flat=act_flat, ahead=ahead, obs_flat=obs_flat, critic_all=critic_all,
                                      plan=plan, logstd_flat=logstd_flat, a_out=a_out, c_out=c_out, old_mu=old_mu, old_logstd=old_logstd,
-                                     main=torch.cuda.current_stream(), side=self._side_stream, mirrors=None)
+                                     main=torch.cuda.current_stream(), side=self._side_stream, mirrors=None,
+                                     # what an optimiser step runs on: the trainers, their plan, their rows (runner.num_mini_batches > 1: the mini-batch pair)
+                                     ct=self._critic_tr, at=self._actor_tr, step_plan=plan, rows=B, wgrad_group=self._wgrad_group)
 
     def _epoch_on_two_streams(self, u, have_fwd):
         """Side stream: the critic's forward pass (unless the rollout ran it), values, time-out bootstrap, GAE, returns, advantage moments and their
@@ -789,7 +949,7 @@ class Runner:
 
     def _epoch_gradients_and_step(self, u):
         """Deferred reductions, all weight gradients, the exchange of the gradient over the ranks, clip + Adam + KL rule (runner.py:162-180)."""
-        cfg, B, alg, main, side, plan = u.cfg, u.B, u.alg, u.main, u.side, u.plan
+        cfg, B, alg, main, side, plan = u.cfg, u.rows, u.alg, u.main, u.side, u.step_plan
         fins, fin_c, fin_a, mirrors = u.fins, u.fin_c, u.fin_a, u.mirrors
         # (the first optimiser step after a checkpoint restore runs the separate launches: see __init__)
         fused_tail, one_tail = plan.fused_opt and not self._lr_restart, plan.one_tail and not self._lr_restart
@@ -803,7 +963,7 @@ class Runner:
                     self._exchange_sums()  # exchange (3), beside the weight gradients
         # all weight gradients after both backward chains, alone on the GPU: one launch pair for the six hidden layers (shapes outside the
         # kernel's range, or MLPTrainer.FUSED_WGRAD = False: library GEMMs, layer by layer); one_tail: their finish inside bg_update_tail
-        wg_partial = self._wgrad_group.run((self._critic_tr, self._actor_tr), plan.wgrad, one_tail)
+        wg_partial = u.wgrad_group.run((u.ct, u.at), plan.wgrad, one_tail)
         if plan.defer and plan.ranks:
             main.wait_stream(side)
         if one_tail and plan.ranks:
@@ -818,7 +978,7 @@ class Runner:
             # ... and the copies of the weights that the layer kernels read (zero-padded first layers, transposed hidden layers): written by the
             # same launch instead of six strided torch copies inside the chains of the next mini-epoch
             if mirrors is None:
-                ms = self._critic_tr.mirror_descriptors(self.optimizer.flat) + self._actor_tr.mirror_descriptors(self.optimizer.flat)
+                ms = u.ct.mirror_descriptors(self.optimizer.flat) + u.at.mirror_descriptors(self.optimizer.flat)
                 mirrors = (_lib.ParamMirror * len(ms))(*ms) if 0 < len(ms) <= 16 else None
             if one_tail and not plan.ranks:
                 self.optimizer.step_tail(wg_partial, [fin_c, fin_a] + fins, self._stats, self._stats_acc, self._stats_last, 4, B, alg["desired_kl"],
@@ -826,11 +986,11 @@ class Runner:
             else:
                 self.optimizer.step_fused(self._stats, self._stats_acc, self._stats_last, 4, B * self.world_size, alg["desired_kl"],
                                           grad_logstd=self._grad_logstd, ls_off=self._logstd_off, mirrors=mirrors)
-            self._actor_tr.mirror_fresh = self._critic_tr.mirror_fresh = mirrors is not None
+            u.at.mirror_fresh = u.ct.mirror_fresh = mirrors is not None
         else:
             self._logstd_grad_view.copy_(self._grad_logstd)  # (behind the bucket's all-reduce, which carries a stale value in this slot)
             self.optimizer.step()
-            self._actor_tr.mirror_fresh = self._critic_tr.mirror_fresh = False  # this launch does not write the weight copies: the next pass copies them
+            u.at.mirror_fresh = u.ct.mirror_fresh = False  # this launch does not write the weight copies: the next pass copies them
             if self._lr_restart:  # first step after a checkpoint load: see __init__
                 self.optimizer.lr.fill_(float(cfg["algorithm"]["learning_rate"]))
                 self._lr_restart = False
@@ -841,13 +1001,14 @@ class Runner:
             self._grad_logstd.zero_()
         u.mirrors = mirrors
 
-    def _plan_chain_split(self, x_c, x_a, plan):
-        """x_c / x_a: the critic's / the actor's input of the full-batch forward pass (their widths, not the trainers': a trainer is allocated by its
+    def _plan_chain_split(self, x_c, x_a, plan, ct=None, at=None):
+        """ct / at: the pair of trainers whose launches are planned (default: the whole-batch pair; runner.num_mini_batches > 1: the mini-batch pair, with
+        x_c / x_a one mini-batch's b rows, so that the shares are sized for b-row slabs).  x_c / x_a: the critic's / the actor's input of the full-batch forward pass (their widths, not the trainers': a trainer is allocated by its
         first pass, which may come after this).  The two networks' chains of a mini-epoch run side by side -- inside one grid (the default) or as two launches on two streams -- one workgroup
         per CU (all of its LDS).  Left to the dispatcher, equal-sized slabs of unequal cost run in lockstep rounds and the last 32 slabs run alone (370 us
         for 325 us of work per CU); here each network gets a share of the CUs whose workgroups walk its slabs (bg_mlp_chain_split::workgroups): the
         split that minimises the longer of the two, slab cost ~ flops.  Which workgroup walks which slab changes no bit of the results."""
-        ct, at = self._critic_tr, self._actor_tr
+        ct, at = ct or self._critic_tr, at or self._actor_tr
         ct.chain_workgroups = at.chain_workgroups = 0
         if not (self._split_chain_cus and plan.critic.chained and plan.actor.chained):
             return
@@ -902,7 +1063,7 @@ class Runner:
         B, A, E, S = T * N * self.world_size, self.env.num_actions, self.cfg["runner"]["mini_epochs"], self._n_stats
         self.learning_rate = s[2 * S]
         out = {"value_loss": s[0] / (B * E), "actor_loss": s[1] / (B * E), "bound_loss": s[2] / (B * A * E), "entropy": s[3] / (B * E),
-               "kl_mean": s[S + 4] / B, "lr": s[2 * S]}
+               "kl_mean": s[S + 4] / (B // self._mini_batches), "lr": s[2 * S]}  # (the last optimiser step's KL sum: over its b = B / K rows of every rank)
         if S > 5:  # mean squared asymmetry of the actor's mean, before symmetric_coef (like bound_loss before bound_coef)
             out["symmetry_loss"] = s[5] / (B * A * E)
         return out

@@ -579,6 +579,27 @@ int bg_obs_moments(int32_t rows, const float* a, int32_t cols_a, int32_t stride_
 int bg_obs_normalize(int32_t rows, int32_t cols, const float* src, int32_t src_stride, float* dst, int32_t dst_cols, int32_t dst_stride,
                      const float* mean, const float* inv_std, int32_t col0, void* stream);
 
+/* ---- shuffled mini-batches of the PPO update (runner.num_mini_batches > 1; bg_minibatch.hip).  Two launches of their own per mini-epoch: nothing of
+ * them runs when the key is absent or 1.
+ *
+ * bg_perm_fill: perm[i] = pi(i), i < n, for the permutation pi of [0, n) that the key (seed, update, epoch) names: a balanced Feistel network on
+ * ceil(log2 n) bits (rounded up to an even number) whose round functions are philox4x32_10 draws, with cycle walking for images at or beyond n
+ * (csrc/bg_perm.h, which also compiles for the host).  Evaluated per index: no sort, no generator state, the same numbers on every device.
+ * seed: basic.seed with the rank folded in by the caller; update: the caller's update counter; epoch: the mini-epoch (below 2^24).  perm: int32 [n]. */
+int bg_perm_fill(int32_t n, uint64_t seed, uint32_t update, uint32_t epoch, int32_t* perm, void* stream);
+/* One row-major fp32 stream of bg_gather_rows: dst [rows][width] = rows of src [src_rows][width]. */
+typedef struct {
+    const float* src;
+    float* dst;
+    int32_t width; /* floats per row, 1 to 4096; a multiple of 4 with 16-byte aligned buffers moves 16 bytes per thread */
+    int32_t pad;
+} bg_gather_stream;
+#define BG_GATHER_MAX_STREAMS 8
+/* dst_s[i][:] = src_s[perm[i]][:] for i < rows and every stream s < n_streams (1 to BG_GATHER_MAX_STREAMS), all in ONE launch: bit copies, no
+ * arithmetic.  perm: int32 [rows] with values in [0, src_rows); a value outside leaves its destination row as it was (never read out of bounds).
+ * A stream's src and dst must not overlap. */
+int bg_gather_rows(int32_t rows, int32_t src_rows, const int32_t* perm, const bg_gather_stream* streams, int32_t n_streams, void* stream);
+
 const char* bg_last_error(void);
 const char* bg_version(void);
 

@@ -1,0 +1,372 @@
+"""runner.num_mini_batches on the GPU: the device permutation against the host harness, bg_gather_rows against torch.index_select, Runner.update()
+with K steps per mini-epoch against a torch restatement of the reference loop with the K-step inner loop (fed the device's permutations), off is
+off, reproducibility, the refusal of the symmetry loss and a short training run."""
+import numpy as np
+import pytest
+import torch
+
+from test_mini_batches import KEYS, host_perm, perm_lib  # noqa: F401  (perm_lib: the fixture that compiles csrc/bg_perm.h for the host)
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+P = 187
+KEY = "runner.num_mini_batches"
+
+
+def _runner(n, **over):
+    from booster_gym_amd.utils.config import load_cfg
+    from booster_gym_amd.utils.runner import Runner
+
+    ov = {"env.num_envs": n, "basic.sim_device": DEV, "basic.rl_device": DEV, "terrain.type": "plane"}
+    ov.update(over)
+    return Runner(cfg=load_cfg("T1", ov))
+
+
+def _start(r):
+    obs, infos = r.env.reset()
+    r.buffer["obses"][0].copy_(obs); r.buffer["privileged_obses"][0].copy_(infos["privileged_obs"])
+
+
+# ------------------------------------------------------------------ bg_perm_fill
+def _device_perm(n, seed, update, epoch):
+    from booster_gym_amd import _lib
+
+    out = torch.full((n + 64,), -7, dtype=torch.int32, device=DEV)  # (64 guard words behind the permutation: must stay untouched)
+    _lib.check(_lib.load().bg_perm_fill(n, seed, update, epoch, _lib.ptr(out), _lib.current_stream_ptr()), "bg_perm_fill")
+    torch.cuda.synchronize()
+    assert bool((out[n:] == -7).all())
+    return out[:n].cpu().numpy()
+
+
+@pytest.mark.parametrize("B", [128, 3072, 6144, 98304, 100 * 24, 786432])
+def test_device_permutation_equals_the_host_harness(perm_lib, B):  # noqa: F811
+    for seed, update, epoch in KEYS:
+        d = _device_perm(B, seed, update, epoch)
+        assert np.array_equal(d, host_perm(perm_lib, B, seed, update, epoch)), (B, seed, update, epoch)
+
+
+def test_perm_fill_refuses_bad_arguments():
+    from booster_gym_amd import _lib
+
+    lib, out = _lib.load(), torch.zeros(16, dtype=torch.int32, device=DEV)
+    assert lib.bg_perm_fill(0, 1, 0, 0, _lib.ptr(out), None) != 0
+    assert lib.bg_perm_fill(16, 1, 0, 0, None, None) != 0
+    assert lib.bg_perm_fill(16, 1, 0, 1 << 24, _lib.ptr(out), None) != 0 and b"epoch" in lib.bg_last_error()
+
+
+# ------------------------------------------------------------------ bg_gather_rows
+def _gather(perm, srcs, rows=None):
+    from booster_gym_amd import _lib
+
+    rows = perm.numel() if rows is None else rows
+    dsts = [torch.full((rows + 1,) + tuple(s.shape[1:]), float("nan"), device=DEV) for s in srcs]  # (one guard row behind every destination)
+    arr = (_lib.GatherStream * len(srcs))(*[_lib.GatherStream(s.data_ptr(), d.data_ptr(), s[0].numel(), 0) for s, d in zip(srcs, dsts)])
+    _lib.check(_lib.load().bg_gather_rows(rows, srcs[0].shape[0], _lib.ptr(perm), arr, len(srcs), _lib.current_stream_ptr()), "bg_gather_rows")
+    torch.cuda.synchronize()
+    for d in dsts:
+        assert bool(torch.isnan(d[rows:]).all())  # nothing written behind the last row
+    return [d[:rows] for d in dsts]
+
+
+def test_gather_rows_equals_index_select_in_one_launch_over_mixed_streams(monkeypatch):
+    from booster_gym_amd import _lib
+
+    g = torch.Generator(device=DEV).manual_seed(11)
+    lib, calls = _lib.load(), [0]
+
+    def counted(*a, _fn=lib.bg_gather_rows):
+        calls[0] += 1
+        return _fn(*a)
+
+    monkeypatch.setattr(lib, "bg_gather_rows", counted)
+    for B in (128, 3072, 98304):
+        perm = torch.randperm(B, device=DEV, generator=g).to(torch.int32)
+        # every input width, actions and old mu, and two scalar streams: eight streams, one launch
+        srcs = [torch.randn(B, w, device=DEV, generator=g) for w in (64, 128, 256, 512, 12, 12)] + [torch.randn(B, device=DEV, generator=g) for _ in range(2)]
+        calls[0] = 0
+        outs = _gather(perm, srcs)
+        assert calls[0] == 1
+        for s, o in zip(srcs, outs):
+            assert torch.equal(o, torch.index_select(s, 0, perm.long())), (B, tuple(s.shape))
+    # a width that is no multiple of 4 floats and a buffer off the 16-byte grid take the 4-byte path: the same bits
+    B = 1000
+    perm = torch.randperm(B, device=DEV, generator=g).to(torch.int32)
+    a, base = torch.randn(B, 47, device=DEV, generator=g), torch.randn(B * 12 + 1, device=DEV, generator=g)
+    off = base[1:].view(B, 12)
+    assert off.data_ptr() % 16 == 4
+    for s, o in zip((a, off), _gather(perm, [a, off])):
+        assert torch.equal(o, torch.index_select(s, 0, perm.long()))
+    # fewer destination rows than source rows (a prefix of a permutation), and an index outside the source leaves its row as it was
+    sub = _gather(perm[:256].contiguous(), [a], rows=256)[0]
+    assert torch.equal(sub, a[perm[:256].long()])
+    bad = perm.clone(); bad[5] = B; bad[9] = -1
+    out = _gather(bad, [a])[0]
+    keep = torch.ones(B, dtype=torch.bool, device=DEV); keep[5] = keep[9] = False
+    assert torch.equal(out[keep], a[perm.long()][keep]) and bool(torch.isnan(out[~keep]).all())
+
+
+def test_gather_rows_refuses_bad_arguments():
+    from booster_gym_amd import _lib
+
+    lib = _lib.load()
+    x, y, perm = torch.zeros(8, 4, device=DEV), torch.zeros(8, 4, device=DEV), torch.arange(8, dtype=torch.int32, device=DEV)
+    one = lambda s, d, w: (_lib.GatherStream * 1)(_lib.GatherStream(s, d, w, 0))
+    assert lib.bg_gather_rows(0, 8, _lib.ptr(perm), one(x.data_ptr(), y.data_ptr(), 4), 1, None) != 0
+    assert lib.bg_gather_rows(8, 8, None, one(x.data_ptr(), y.data_ptr(), 4), 1, None) != 0
+    assert lib.bg_gather_rows(8, 8, _lib.ptr(perm), one(x.data_ptr(), y.data_ptr(), 4), 9, None) != 0 and b"streams" in lib.bg_last_error()
+    assert lib.bg_gather_rows(8, 8, _lib.ptr(perm), one(x.data_ptr(), y.data_ptr(), 0), 1, None) != 0 and b"width" in lib.bg_last_error()
+    assert lib.bg_gather_rows(8, 8, _lib.ptr(perm), one(None, y.data_ptr(), 4), 1, None) != 0
+    assert lib.bg_gather_rows(8, 8, _lib.ptr(perm), one(x.data_ptr(), x.data_ptr() + 16, 4), 1, None) != 0 and b"overlap" in lib.bg_last_error()
+
+
+# ------------------------------------------------------------------ the update against the reference loop with the K-step inner loop
+def reference_update_with_mini_batches(model, optimizer, obses, privileged_obses, actions, rewards, dones, time_outs, last_obs, last_privileged_obs, batches,
+                                       gamma=0.995, lam=0.95, bound_coef=1.0, entropy_coef=-0.01, desired_kl=0.01, learning_rate=1e-5, max_grad_norm=1.0):
+    """oracle/ppo_ref.ppo_update_reference (the reference's utils/runner.py:123-189 op by op) with the one optimiser step of a mini-epoch replaced by
+    one step per entry of batches[epoch], each a tensor of row numbers of the time-major flattened batch.  Per mini-epoch, once and without
+    gradients: values of the whole batch from the current weights, the time-out overwrite, GAE, returns, advantages normalised with the
+    whole-batch moments.  Per step: values, distribution, the four loss terms as means over the step's rows, clip, Adam, the KL rule.
+    Returns (means of the loss terms over all steps, the last step's kl_mean), final learning rate."""
+    import torch.nn.functional as F
+
+    from oracle.ppo_ref import discount_values, surrogate_loss
+
+    T, N = rewards.shape
+    B = T * N
+    fl = lambda x: x.reshape(B, *x.shape[2:])
+    obs_f, priv_f, act_f = fl(obses), fl(privileged_obses), fl(actions)
+    with torch.no_grad():
+        old_dist = model.act(obs_f)
+        old_logp = old_dist.log_prob(act_f).sum(dim=-1)
+    sums, steps, kl_mean = np.zeros(4), 0, torch.tensor(0.0)
+    for epoch_batches in batches:
+        with torch.no_grad():
+            values = model.est_value(obses, privileged_obses)
+            last_values = model.est_value(last_obs, last_privileged_obs)
+            rewards[time_outs] = values[time_outs]
+            advantages = discount_values(rewards, dones | time_outs, values, last_values, gamma, lam)
+            returns = fl(values + advantages)
+            advantages = fl((advantages - advantages.mean()) / (advantages.std() + 1e-8))
+        for idx in epoch_batches:
+            v = model.est_value(obs_f[idx], priv_f[idx])
+            value_loss = F.mse_loss(v, returns[idx])
+            dist = model.act(obs_f[idx])
+            actor_loss = surrogate_loss(old_logp[idx], dist.log_prob(act_f[idx]).sum(dim=-1), advantages[idx])
+            bound_loss = torch.clip(dist.loc - 1.0, min=0.0).square().mean() + torch.clip(dist.loc + 1.0, max=0.0).square().mean()
+            entropy = dist.entropy().sum(dim=-1)
+            loss = value_loss + actor_loss + bound_coef * bound_loss + entropy_coef * entropy.mean()
+            optimizer.zero_grad()
+            loss.backward()
+            torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)
+            optimizer.step()
+            with torch.no_grad():
+                o_loc, o_scale = old_dist.loc[idx], old_dist.scale[idx]
+                kl = torch.sum(torch.log(dist.scale / o_scale) + 0.5 * (torch.square(o_scale) + torch.square(dist.loc - o_loc)) / torch.square(dist.scale) - 0.5, axis=-1)
+                kl_mean = torch.mean(kl)
+                if kl_mean > desired_kl * 2:
+                    learning_rate = max(1e-5, learning_rate / 1.5)
+                elif kl_mean < desired_kl / 2:
+                    learning_rate = min(1e-2, learning_rate * 1.5)
+                for group in optimizer.param_groups:
+                    group["lr"] = learning_rate
+            sums += [value_loss.item(), actor_loss.item(), bound_loss.item(), entropy.mean().item()]
+            steps += 1
+    m = sums / steps
+    return {"value_loss": m[0], "actor_loss": m[1], "bound_loss": m[2], "entropy": m[3], "kl_mean": float(kl_mean)}, learning_rate
+
+
+def assert_same_adam_steps(name, p, q, start):
+    """tests/test_gpu_ppo.py's bound: all but 0.5 % of the elements within 2 % of the distance the tensor's parameters moved, none beyond twice it."""
+    moved = (q - start).abs().max().item()
+    d = (p - q).abs()
+    off = (d > 0.02 * moved + 2e-6).float().mean().item()
+    print(f"{name}: max |p - q| {d.max().item():.3e}, moved {moved:.3e}, outside 2 %: {off:.5f}")
+    assert off <= 0.005 and d.max().item() <= 2.0 * moved + 2e-6, (name, off, d.max().item(), moved)
+
+
+def compare_with_reference(r, ref_model, stats_ref, lr_ref, p_start, acc):
+    summ = r._summarize(acc)
+    for (k, p), (k2, q) in zip(r.model.named_parameters(), ref_model.named_parameters()):
+        assert k == k2
+        assert_same_adam_steps(k, p, q, p_start[k])
+    for k in ("value_loss", "actor_loss", "bound_loss", "entropy", "kl_mean"):
+        print(f"{k}: {summ[k]!r} against {stats_ref[k]!r}")
+        assert abs(summ[k] - stats_ref[k]) <= 2e-4 * max(1.0, abs(stats_ref[k])), (k, summ[k], stats_ref[k])
+    print(f"lr: {summ['lr']!r} against {lr_ref!r}")
+    assert abs(summ["lr"] - lr_ref) < 1e-9
+
+
+def device_batches(r, E, K):
+    """The row numbers of every step of the update the runner is about to make: its permutations read back from the device, cut into K-ths."""
+    b = r._old_logp.numel() // K
+    perms = [r.permutation(r._mb_updates, e).long() for e in range(E)]
+    for p in perms:
+        assert torch.equal(torch.sort(p).values, torch.arange(p.numel(), device=p.device))
+    return [[p[k * b : (k + 1) * b] for k in range(K)] for p in perms]
+
+
+@pytest.mark.parametrize("n,T,E,K", [(128, 24, 3, 2), (256, 24, 3, 3), (4096, 24, 5, 4)])
+def test_update_with_mini_batches_matches_the_reference_loop(n, T, E, K):
+    from booster_gym_amd.utils.model import ActorCritic
+
+    r = _runner(n, **{"runner.mini_epochs": E, "runner.horizon_length": T, KEY: K})
+    assert r._mini_batches == K and r._mb_rows == T * n // K
+    _start(r)
+    r.rollout()
+    assert r._fwd_plan is not None and r._mb_plan.critic.fwd == "chain_split" and r._mb_plan.one_tail  # the default kernels, on b rows
+    ref_model = ActorCritic(12, 47, 14).to(DEV)
+    ref_model.load_state_dict(r.model.state_dict())
+    b = r.buffer
+    batches = device_batches(r, E, K)
+    stats_ref, lr_ref = reference_update_with_mini_batches(ref_model, torch.optim.Adam(ref_model.parameters(), lr=1e-5), b["obses"][:T].clone(),
+                                                           b["privileged_obses"][:T].clone(), b["actions"].clone(), b["rewards"].clone(), b["dones"].clone(),
+                                                           b["time_outs"].clone(), b["obses"][T].clone(), b["privileged_obses"][T].clone(), batches)
+    p_start = {k: p.detach().clone() for k, p in r.model.named_parameters()}
+    acc = r.update()
+    torch.cuda.synchronize()
+    assert r.optimizer.step_count == E * K and r._mb_updates == 1
+    assert torch.equal(r._perm.long(), torch.cat(batches[-1]))  # the last mini-epoch's permutation is the one the restatement was fed
+    compare_with_reference(r, ref_model, stats_ref, lr_ref, p_start, acc)
+
+
+def test_mini_batches_with_frame_stack_height_scan_and_normalisation_through_the_per_layer_kernels():
+    """env.frame_stack 3 + terrain.measure_heights + algorithm.empirical_normalization with K = 2: inputs of 256 and 512 columns, so both networks run
+    the per-layer kernels.  Iteration 2 against the restatement on host-normalised inputs, as tests/test_gpu_obs_norm.py compares (the Adam state of
+    iteration 1 cleared, so that the restatement's fresh torch.optim.Adam starts where the runner does)."""
+    from booster_gym_amd.utils.model import ActorCritic
+
+    E, T, n, K, H = 3, 24, 256, 2, 3
+    r = _runner(n, **{"runner.mini_epochs": E, KEY: K, "env.frame_stack": H, "env.num_observations": 47 * H, "terrain.type": "trimesh",
+                      "terrain.measure_heights": True, "env.num_privileged_obs": 14 + P, "algorithm.empirical_normalization": True})
+    no, npv = r.env.num_obs, r.env.num_privileged_obs
+    assert (no, npv) == (47 * H, 14 + P)
+    _start(r)
+    r.iteration()
+    assert r._mb_plan.critic.fwd == r._mb_plan.actor.fwd == "layer" and r._mb_updates == 1
+    norm, opt = r.obs_norm, r.optimizer
+    opt.exp_avg.zero_(); opt.exp_avg_sq.zero_(); opt.step_count = 0; opt.lr.fill_(1e-5)
+    r.invalidate()
+    r.rollout()
+    ref_model = ActorCritic(12, no, npv).to(DEV)
+    ref_model.load_state_dict(r.model.state_dict())
+    b = r.buffer
+    hn = lambda x: (x - norm.mean_dev[:no]) * norm.inv_std_dev[:no]
+    hp = lambda x: (x - norm.mean_dev[no : no + npv]) * norm.inv_std_dev[no : no + npv]
+    batches = device_batches(r, E, K)
+    stats_ref, lr_ref = reference_update_with_mini_batches(ref_model, torch.optim.Adam(ref_model.parameters(), lr=1e-5), hn(b["obses"][:T]), hp(b["privileged_obses"][:T]),
+                                                           b["actions"].clone(), b["rewards"].clone(), b["dones"].clone(), b["time_outs"].clone(), hn(b["obses"][T]),
+                                                           hp(b["privileged_obses"][T]), batches)
+    p_start = {k: p.detach().clone() for k, p in r.model.named_parameters()}
+    acc = r.update()
+    torch.cuda.synchronize()
+    assert norm.count == 2 * T * n
+    compare_with_reference(r, ref_model, stats_ref, lr_ref, p_start, acc)
+
+
+# ------------------------------------------------------------------ the runner
+class _Rec:
+    def __init__(self, *a, **k):
+        self.stats = {}
+
+    def record_episode_statistics(self, env, names, it, stats=None):
+        pass
+
+    def record_statistics(self, summary, it):
+        self.stats[it] = dict(summary)
+
+    def save(self, d, it):
+        return None
+
+
+def _train(r, iters):
+    r.begin_training(recorder=_Rec())
+    for it in range(iters):
+        r.train_iteration(it)
+    r._flush_log()
+    torch.cuda.synchronize()
+    return r.recorder
+
+
+def _count_calls(monkeypatch):
+    from booster_gym_amd import _lib
+
+    lib, counts = _lib.load(), {"bg_perm_fill": 0, "bg_gather_rows": 0}
+    for name in counts:
+        def wrap(*a, _fn=getattr(lib, name), _name=name):
+            counts[_name] += 1
+            return _fn(*a)
+        monkeypatch.setattr(lib, name, wrap)
+    return counts
+
+
+def _state(r, rec):
+    o = r.optimizer
+    return [o.flat.clone(), o.exp_avg.clone(), o.exp_avg_sq.clone(), o.lr.clone(), r._stats_acc.clone(), r._stats_last.clone(), r._old_logp.clone(),
+            r.buffer["actions"].clone(), r.buffer["rewards"].clone()], rec.stats
+
+
+def test_off_is_off(monkeypatch):
+    """Key absent and K = 1: the same bits in the parameters, the Adam moments, _stats_acc and every log scalar after two iterations, and neither new
+    entry point is called."""
+    from booster_gym_amd.utils.config import load_cfg
+    from booster_gym_amd.utils.runner import Runner
+
+    counts = _count_calls(monkeypatch)
+    res = []
+    for absent in (True, False):
+        cfg = load_cfg("T1", {"env.num_envs": 256, "basic.sim_device": DEV, "basic.rl_device": DEV, "terrain.type": "plane", "runner.mini_epochs": 3, "basic.seed": 5})
+        if absent:
+            del cfg["runner"]["num_mini_batches"]
+        else:
+            assert cfg["runner"]["num_mini_batches"] == 1
+        r = Runner(cfg=cfg)
+        assert r._mini_batches == 1 and not hasattr(r, "_perm") and not hasattr(r, "_critic_mb")
+        res.append(_state(r, _train(r, 2)))
+        assert sorted(r.checkpoint_dict()) == ["curriculum", "model", "optimizer"]
+        del r
+    for k, (a, b) in enumerate(zip(res[0][0], res[1][0])):
+        assert torch.equal(a, b), k
+    assert res[0][1] == res[1][1] and len(res[0][1]) == 2
+    assert counts == {"bg_perm_fill": 0, "bg_gather_rows": 0}
+
+
+def test_two_runs_with_one_seed_are_bitwise_equal_and_another_seed_shuffles_differently(monkeypatch):
+    counts = _count_calls(monkeypatch)
+    res, E, K = [], 3, 4
+    for seed in (5, 5, 6):
+        r = _runner(256, **{"runner.mini_epochs": E, KEY: K, "basic.seed": seed})
+        rec = _train(r, 2)
+        res.append((_state(r, rec), r._perm.clone(), r.permutation(0, 0).clone()))
+        assert r._mb_updates == 2 and r.optimizer.step_count == 2 * E * K
+        del r
+    assert counts == {"bg_perm_fill": 2 * E * 3 + 3, "bg_gather_rows": 2 * E * 3}  # one of each per mini-epoch (+ the three read-backs above)
+    for k, (a, b) in enumerate(zip(res[0][0][0], res[1][0][0])):
+        assert torch.equal(a, b), k
+    assert res[0][0][1] == res[1][0][1] and torch.equal(res[0][1], res[1][1])
+    assert not torch.equal(res[0][2], res[2][2]) and not torch.equal(res[0][1], res[2][1])
+
+
+def test_symmetry_loss_with_mini_batches_is_refused_at_construction():
+    with pytest.raises(ValueError, match=r"runner\.num_mini_batches = 2 together with algorithm\.symmetry_loss"):
+        _runner(128, **{KEY: 2, "algorithm.symmetry_loss": True})
+
+
+def test_training_runs_and_logs_todays_names(monkeypatch):
+    from booster_gym_amd.utils import runner as runner_mod
+
+    monkeypatch.setattr(runner_mod, "Recorder", _Rec)
+    names = []
+    for K in (1, 2):
+        r = _runner(128, **{KEY: K, "runner.mini_epochs": 2, "basic.max_iterations": 3})
+        r.train()
+        torch.cuda.synchronize()
+        stats = r.recorder.stats
+        assert sorted(stats) == [0, 1, 2]
+        for it, s in stats.items():
+            for k, v in s.items():
+                assert np.isfinite(v), (K, it, k, v)
+        assert torch.isfinite(r.optimizer.flat).all()
+        names.append(sorted(stats[2]))
+        assert sorted(r.checkpoint_dict()) == ["curriculum", "model", "optimizer"]
+        del r
+    assert names[0] == names[1] and "kl_mean" in names[0] and "lr" in names[0]
