@@ -45,7 +45,6 @@ __device__ __forceinline__ float elu_f(float x) { return x > 0.f ? x : __expf(x)
 struct SplitTmp { unsigned m0, m1, n0, n1; float r0, r1, s0; };
 template <int PH>
 __device__ __forceinline__ void split_phase(float x0, float x1, SplitTmp& s, unsigned& hp, unsigned& mp, unsigned& lp) {
-#ifndef BG_ABL_NOSPLIT
     if constexpr (PH == 0) {
         const unsigned u0 = __float_as_uint(x0), u1 = __float_as_uint(x1);
         hp = __builtin_amdgcn_perm(u1, u0, 0x07060302u); s.m0 = u0 & 0xffff0000u; s.m1 = u1 & 0xffff0000u;
@@ -56,22 +55,11 @@ __device__ __forceinline__ void split_phase(float x0, float x1, SplitTmp& s, uns
     }
     if constexpr (PH == 2) { s.n0 = __float_as_uint(s.r0) & 0xffff0000u; s.n1 = __float_as_uint(s.r1) & 0xffff0000u; s.s0 = s.r0 - __uint_as_float(s.n0); }
     if constexpr (PH == 3) { const float s1 = s.r1 - __uint_as_float(s.n1); lp = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s.s0), 0x07060302u); }
-#endif
 }
 // ELU of an accumulator element in two pieces (3 + 1 issue slots: the exponential counts double; then 3)
 struct FinTmp { float v, e; };
-__device__ __forceinline__ void fin_a(FinTmp& f, float x) {
-#ifndef BG_ABL_NOFIN
-    f.v = x; f.e = __expf(x);
-#endif
-}
-__device__ __forceinline__ float fin_b(const FinTmp& f, float x) {
-#ifndef BG_ABL_NOFIN
-    return f.v > 0.f ? f.v : f.e - 1.0f;
-#else
-    return x;
-#endif
-}
+__device__ __forceinline__ void fin_a(FinTmp& f, float x) { f.v = x; f.e = __expf(x); }
+__device__ __forceinline__ float fin_b(const FinTmp& f) { return f.v > 0.f ? f.v : f.e - 1.0f; }
 
 // One tile's nine products (small terms first); fill(gap) runs behind MFMA number gap, pinned there.
 template <class F>
@@ -102,9 +90,7 @@ __device__ __forceinline__ void dma_piece(const unsigned* __restrict__ P, int CH
     const unsigned lofs = rowpart[m] * (unsigned)CH + piecepart[m];
     // inline asm: the copies' bookkeeping is explicit (wait_vm), the compiler must not drain vmcnt for them; M0 cannot be named as a clobber
     // (reserved), the backend never keeps a value of its own live in M0 across an inline asm (see bg_mlp_chain.hip)
-#ifndef BG_ABL_NODMA
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(lofs), "s"(base), "s"(lds) : "memory");
-#endif
 }
 
 // The same for the tile-major stream of the backward chain: the chunk is ONE 32-row tile of a layer's planes over ALL its CH k-chunks (a contiguous
@@ -118,9 +104,7 @@ __device__ __forceinline__ void dma_tile_piece(const unsigned* __restrict__ P, i
     const unsigned* base = P + ((size_t)(32 * tile + 16 * (G & 1)) * CH + (G >> 1)) * SP_ROW;
     const unsigned lds = lds_chunk_bytes + (unsigned)((G * 192 + m * 64) * 16);
     const unsigned lofs = rowpart[m] * (unsigned)CH + piecepart[m];
-#ifndef BG_ABL_NODMA
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(lofs), "s"(base), "s"(lds) : "memory");
-#endif
 }
 
 // mfma9 for the first k-step of a tile: the accumulator starts from zero (C = 0 in the first product: no register initialisation)

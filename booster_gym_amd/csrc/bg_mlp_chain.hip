@@ -23,13 +23,8 @@
 
 extern int bg_set_error(int code, const char* msg);
 
-#ifdef BG_CHAIN_PROBE_STAMPS  // tools/mlp_chain_stamps.py: shader-clock stamp of every wave behind every chunk barrier (never defined in the product build)
-__device__ long long bg_chain_stamp_buf[2048 * 4 * 24];
-extern "C" int bg_probe_read_chain_stamps(void* dst, size_t bytes) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(bg_chain_stamp_buf), bytes); }
-#define BG_CHAIN_STAMP(K) stamps[K] = clock64()
-#else
-#define BG_CHAIN_STAMP(K) do { } while (0)
-#endif
+#include "bg_stamps.h"
+BG_STAMP_BUFFER(bg_chain_stamp_buf, bg_probe_read_chain_stamps, 2048, 24)  // tools/mlp_chain_stamps.py: [workgroup][wave][stamp], a stamp behind every chunk barrier
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -110,10 +105,8 @@ __device__ __forceinline__ void chain_slab(const bg_mlp_chain& a, int slab, floa
         else if (cc < C0 + C1) dma_rows<N1, N2>(W2, cc - C0, dst, wave, lo2);
         else if (cc < C) dma_rows<N2, N3>(W3, cc - C0 - C1, dst, wave, lo3);
     };
-#ifdef BG_CHAIN_PROBE_STAMPS
-    long long stamps[24];
-#endif
-    BG_CHAIN_STAMP(0);
+    BG_STAMP_LOCALS(24);
+    BG_STAMP(0);
     dma(0);
     dma(1);
     dma(2);
@@ -145,7 +138,7 @@ __device__ __forceinline__ void chain_slab(const bg_mlp_chain& a, int slab, floa
             wait_vm<S::behind(c)>();
             if (c == 0) __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the bias values written to sB above
             asm volatile("s_barrier" ::: "memory");  // no fence: a workgroup fence would drain vmcnt (stores and younger copies included)
-            BG_CHAIN_STAMP(c + 1);
+            BG_STAMP(c + 1);
             __builtin_amdgcn_sched_barrier(0);
             dma(c + AHEAD);
             __builtin_amdgcn_sched_barrier(0);
@@ -209,11 +202,8 @@ __device__ __forceinline__ void chain_slab(const bg_mlp_chain& a, int slab, floa
         part += __shfl_xor(part, 32);
         if (h == 0 && row < a.M) a.v_out[row] = part + a.v_b[0];
     }
-#ifdef BG_CHAIN_PROBE_STAMPS
-    stamps[C + 1] = clock64();
-    if (lane == 0 && blockIdx.x < 2048)
-        for (int k = 0; k < 24; k++) bg_chain_stamp_buf[((size_t)blockIdx.x * 4 + wave) * 24 + k] = k <= C + 1 ? stamps[k] : 0;
-#endif
+    BG_STAMP(C + 1);
+    BG_STAMP_FLUSH(bg_chain_stamp_buf, 24, blockIdx.x < 2048, blockIdx.x);
 }
 
 // TAG: 1 / 2 = one network with N2 = 128 / 256 (the layer shape gets its own kernel symbol: a profiler's per-kernel average is then the average of

@@ -26,15 +26,9 @@
 
 extern int bg_set_error(int code, const char* msg);
 
-#ifdef BG_CHAIN_PROBE_STAMPS  // tools/chain_split_stamps.py: shader-clock stamps of every wave around every chunk barrier (never defined in the product build)
-__device__ long long bg_split_stamp_buf[2 * 256 * 4 * 64];  // [N2 == 256][workgroup][wave][stamp]
-extern "C" int bg_probe_read_split_stamps(void* dst, size_t bytes) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(bg_split_stamp_buf), bytes); }
-#define BG_STAMP(K) stamps[K] = clock64()
-#else
-#define BG_STAMP(K) do { } while (0)
-#endif
-
 #include "bg_chain_split.h"
+#include "bg_stamps.h"
+BG_STAMP_BUFFER(bg_split_stamp_buf, bg_probe_read_split_stamps, 2 * 256, 64)  // tools/chain_split_stamps.py: [N2 == 256][workgroup][wave][stamp], stamps around every chunk barrier
 
 namespace {
 
@@ -109,9 +103,7 @@ __device__ __forceinline__ void split_net(const bg_mlp_chain_split& a, int first
             else dma_piece<q>(P3 + (neg ? (size_t)N3 * N2 * 3 / 2 : 0), C2, c - C0 - C1, dst, wave, rowpart, piecepart);
         }
     };
-#ifdef BG_CHAIN_PROBE_STAMPS
-    long long stamps[64];
-#endif
+    BG_STAMP_LOCALS(64);
     const int sx = (i >> 2) & 3;                                 // this lane's slot swizzle (rows 32 t + i: the tile offset does not change it)
     const int s0 = ((0 + h) ^ sx) * 4, s1 = ((2 + h) ^ sx) * 4;  // step 0 / step 1 of a chunk
     const unsigned* swl = sW + i * SP_ROW;                       // + buffer, + tile * 32 rows, + slot
@@ -136,13 +128,11 @@ __device__ __forceinline__ void split_net(const bg_mlp_chain_split& a, int first
     };
     // ELU of element r of tile t in place, in two pieces (fin_a / fin_b)
     auto fa = [&](FinTmp& f, auto& A, auto t_, auto r_, float sg) { fin_a(f, A[decltype(t_)::value][decltype(r_)::value] * sg); };
-    auto fb = [&](const FinTmp& f, auto& A, auto t_, auto r_) { constexpr int t = decltype(t_)::value, r = decltype(r_)::value; A[t][r] = fin_b(f, A[t][r]); };
+    auto fb = [&](const FinTmp& f, auto& A, auto t_, auto r_) { constexpr int t = decltype(t_)::value, r = decltype(r_)::value; A[t][r] = fin_b(f); };
     auto store4 = [&](auto& A, float* __restrict__ Y, int r, auto N_, auto t_, auto g_) {
-#ifndef BG_ABL_NOSTORE
         constexpr int N = decltype(N_)::value, t = decltype(t_)::value, g = decltype(g_)::value;
         const f32x4 v = {A[t][4 * g + 0], A[t][4 * g + 1], A[t][4 * g + 2], A[t][4 * g + 3]};
         *reinterpret_cast<f32x4*>(Y + (size_t)r * N + 32 * t + 8 * g + 4 * h) = v;
-#endif
     };
     auto vw4 = [&](auto G_) { constexpr int G = decltype(G_)::value; wv[G % 3] = *reinterpret_cast<const f32x4*>(&sB[N1 + N2 + N3 + 32 * (G / 4) + 8 * (G % 4) + 4 * h]); };
     // element e of layer 3 (tile e / 16, register e % 16): ELU in place (two pieces) + its term of the value head; the weights of group e / 4 + 1 are
@@ -187,9 +177,7 @@ __device__ __forceinline__ void split_net(const bg_mlp_chain_split& a, int first
     negc = a.alternate && (slab & 1);
     sgn = sgnp = negc ? -1.0f : 1.0f;
     BG_STAMP(0);
-#ifdef BG_CHAIN_PROBE_STAMPS
-    stamps[62] = wall_clock64();
-#endif
+    BG_STAMP_WALL(62);
     static_for<K0 / 8>([&](auto j_) { loadx(row, j_); });
     BG_PIN();
     static_for<S::ndma(0)>([&](auto q_) { dma(IC<0>{}, q_); });
@@ -375,12 +363,9 @@ __device__ __forceinline__ void split_net(const bg_mlp_chain_split& a, int first
     part += __shfl_xor(part, 32);
     if (a.v_out && h == 0 && rowp < a.M) a.v_out[rowp] = part + vbias;
     wait_vm<0>();  // the copies issued for a slab that does not exist must have landed before the workgroup's LDS is handed on
-#ifdef BG_CHAIN_PROBE_STAMPS
-    stamps[1 + 2 * C] = clock64();
-    stamps[63] = wall_clock64();
-    if (lane == 0 && blockIdx.x < 256)
-        for (int k = 0; k < 64; k++) bg_split_stamp_buf[(((size_t)(N2 == 256) * 256 + blockIdx.x) * 4 + wave) * 64 + k] = (k <= 1 + 2 * C || k >= 62) ? stamps[k] : 0;
-#endif
+    BG_STAMP(1 + 2 * C);
+    BG_STAMP_WALL(63);
+    BG_STAMP_FLUSH(bg_split_stamp_buf, 64, blockIdx.x < 256, (N2 == 256) * 256 + blockIdx.x);
 }
 
 // TAG: 1 / 2 = one network with N2 = 128 / 256 (one kernel symbol per shape: a profiler's per-kernel average is the average of ONE shape),

@@ -27,14 +27,8 @@
 extern int bg_set_error(int code, const char* msg);
 
 #include "bg_chain_split.h"
-
-#ifdef BG_CHAIN_PROBE_STAMPS  // tools/chain_split_bwd_stamps.py: shader-clock stamps of every wave around every chunk barrier (never defined in the product build)
-__device__ long long bg_bwd_stamp_buf[2 * 256 * 4 * 64];  // [N2 == 256][workgroup][wave][stamp]
-extern "C" int bg_probe_read_bwd_stamps(void* dst, size_t bytes) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(bg_bwd_stamp_buf), bytes); }
-#define BG_STAMP(K) stamps[K] = clock64()
-#else
-#define BG_STAMP(K) do { } while (0)
-#endif
+#include "bg_stamps.h"
+BG_STAMP_BUFFER(bg_bwd_stamp_buf, bg_probe_read_bwd_stamps, 2 * 256, 64)  // tools/chain_split_bwd_stamps.py: [N2 == 256][workgroup][wave][stamp], stamps around every chunk barrier
 
 namespace {
 
@@ -203,9 +197,7 @@ __device__ __forceinline__ void bwd_net(const bg_mlp_chain_split_bwd& a, int fir
     f32x4 xin[2][2] = {};  // two 16-byte pieces of the next slab's input row on their way into gp: loaded in one chunk, split in the next
     Frag fr[2];
     unsigned pn[3][4] = {}, pn2[3][4] = {};
-#ifdef BG_CHAIN_PROBE_STAMPS
-    long long stamps[64] = {};
-#endif
+    BG_STAMP_LOCALS(64);
     // input rows: 16-byte piece j of the lane = floats 8 j + 4 h .. + 3; rows >= M are ZERO (then so is everything computed from them: G2, G1 rows and
     // their share of the column sums)
     // Prologue loads of the first slab's input rows (plain loads: the compiler's waits are fine there).  (The select for rows >= M is applied where
@@ -222,18 +214,14 @@ __device__ __forceinline__ void bwd_net(const bg_mlp_chain_split_bwd& a, int fir
     // the activations under tile `tile` of rows row0 .. row0 + 31 (this wave's) -> this wave's LDS corner: four pieces of eight full 128-byte rows
     auto aux_dma = [&](const float* __restrict__ A, int ld, unsigned lofs, int row0, int tile, auto k_) {
         constexpr int k = decltype(k_)::value;
-#ifndef BG_ABL_NOAUX
         const float* base = A + (size_t)(row0 + 8 * k) * ld + 32 * tile;
         const unsigned lds = sTw + 1024u * k;
         asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(lofs), "s"(base), "s"(lds) : "memory");
-#endif
     };
     auto store4 = [&](const f32x16& A, float* __restrict__ Y, int ld, int r, int tile, auto g_) {
-#ifndef BG_ABL_NOSTORE
         constexpr int g = decltype(g_)::value;
         const f32x4 v = {A[4 * g + 0], A[4 * g + 1], A[4 * g + 2], A[4 * g + 3]};
         *reinterpret_cast<f32x4*>(Y + (size_t)r * ld + 32 * tile + 8 * g + 4 * h) = v;
-#endif
     };
     auto chunk_top = [&](auto cc_) {
         constexpr int cc = decltype(cc_)::value;
@@ -254,9 +242,7 @@ __device__ __forceinline__ void bwd_net(const bg_mlp_chain_split_bwd& a, int fir
         BG_PIN();
     };
 
-#ifdef BG_CHAIN_PROBE_STAMPS
-    stamps[62] = wall_clock64();
-#endif
+    BG_STAMP_WALL(62);
     BG_STAMP(0);
     // ---- prologue of the first slab: its input rows, split; the first two chunks' copies
     int slab = first;
@@ -381,10 +367,9 @@ __device__ __forceinline__ void bwd_net(const bg_mlp_chain_split_bwd& a, int fir
                     });
                 }
             };
-#ifdef BG_CHAIN_PROBE_STAMPS   // one chunk of each layer k-step by k-step: stamps 40 .. (layer A, chunk 1), 48 .. (layer B, chunk TA + 2)
+            // one chunk of each layer k-step by k-step: stamps 40 .. (layer A, chunk 1), 48 .. (layer B, chunk TA + 2)
             if constexpr (c == 1) BG_STAMP(40 + J);
             if constexpr (c == TA + 2 && J < 14) BG_STAMP(48 + J);
-#endif
             const u32x4 (&xpl)[3] = [&]() -> const u32x4 (&)[3] { if constexpr (A) return gp[J]; else return hp[J]; }();
             mfma9_asm<!A, J == 0>(cur, fr[J & 1].p, xpl, fill);
         });
@@ -427,12 +412,9 @@ __device__ __forceinline__ void bwd_net(const bg_mlp_chain_split_bwd& a, int fir
         if ((i & 1) == 0) a.colsum_partial[((size_t)(slabp * 4 + wave)) * (N2 + N1) + N2 + 32 * (TB - 1) + csofs] = bf.w;
     }
     wait_vm<0>();  // the copies issued for a slab that does not exist must have landed before the workgroup's LDS is handed on
-#ifdef BG_CHAIN_PROBE_STAMPS
-    stamps[1 + 3 * C] = clock64();
-    stamps[63] = wall_clock64();
-    if (lane == 0 && blockIdx.x < 256)
-        for (int k = 0; k < 64; k++) bg_bwd_stamp_buf[(((size_t)(N2 == 256) * 256 + blockIdx.x) * 4 + wave) * 64 + k] = stamps[k];
-#endif
+    BG_STAMP(1 + 3 * C);
+    BG_STAMP_WALL(63);
+    BG_STAMP_FLUSH(bg_bwd_stamp_buf, 64, blockIdx.x < 256, (N2 == 256) * 256 + blockIdx.x);
 }
 
 template <int TAG>

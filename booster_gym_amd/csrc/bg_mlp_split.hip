@@ -260,9 +260,7 @@ extern "C" int bg_mlp_layer_forward_split(int32_t M, int32_t K, int32_t N, const
     if (M <= 0 || !X || !planes || !bias || !Y) return bg_set_error(-1, "bg_mlp_layer_forward_split: bad argument");
     if ((((uintptr_t)X | (uintptr_t)planes | (uintptr_t)Y) & 15) != 0) return bg_set_error(-1, "bg_mlp_layer_forward_split: pointers must be 16-byte aligned");
     if (N % 128 != 0 || N > 1024) return bg_set_error(-4, "bg_mlp_layer_forward_split: unsupported N (multiples of 128 up to 1024)");
-#ifndef BG_PROBE_TERMS
     if (terms != 9 && terms != 6) return bg_set_error(-4, "bg_mlp_layer_forward_split: terms must be 9 or 6");
-#endif
     dim3 grid((((M + FW_BM - 1) / FW_BM + 7) / 8) * 8 * (N / 128)), block(256);
     hipStream_t st = (hipStream_t)stream;
     const unsigned* P = reinterpret_cast<const unsigned*>(planes);
@@ -274,9 +272,6 @@ extern "C" int bg_mlp_layer_forward_split(int32_t M, int32_t K, int32_t N, const
         return 0;                                                                                                                 \
     }
     BG_FWD(256, 9) BG_FWD(128, 9) BG_FWD(64, 9) BG_FWD(256, 6) BG_FWD(128, 6) BG_FWD(64, 6)
-#ifdef BG_PROBE_TERMS
-    BG_FWD(256, 1) BG_FWD(128, 1) BG_FWD(64, 1)
-#endif
 #undef BG_FWD
     return bg_set_error(-4, "bg_mlp_layer_forward_split: unsupported K (64, 128, 256)");
 }

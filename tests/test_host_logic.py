@@ -760,6 +760,41 @@ def test_inline_asm_mfmas_of_the_backward_chain_keep_their_wait_states():
     assert sum(len(h) for _, h, _, _ in bad.values()) > 0
 
 
+CSRC = os.path.join(ROOT, "booster_gym_amd", "csrc")
+
+
+def test_kernel_sources_hold_no_probe_conditionals_but_the_stamps():
+    """The shipped kernels contain shipped code: the only preprocessor conditionals under csrc/ whose condition names a probe, an ablation or a stamp are
+    those of bg_stamps.h (the clock stamps of the chained kernels, one definition) and the BG_ABL_NOPIN block of the backward chain (which the hazard-scan
+    test above compiles to prove that the scan sees a hazard)."""
+    found = []
+    for name in sorted(os.listdir(CSRC)):
+        if not name.endswith((".hip", ".h", ".cpp", ".hpp")) or name == "bg_stamps.h":
+            continue
+        text = open(os.path.join(CSRC, name)).read().replace("\\\n", " ")
+        for m in re.finditer(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b([^\n]*)", text, re.M):
+            cond = m.group(1).split("//")[0].strip()
+            if re.search(r"PROBE|ABL|STAMP", cond):
+                found.append((name, cond))
+    assert found == [("bg_mlp_chain_split_bwd.hip", "BG_ABL_NOPIN")], found
+    assert "BG_CHAIN_PROBE_STAMPS" in open(os.path.join(CSRC, "bg_stamps.h")).read()
+
+
+def test_chain_kernels_compile_with_their_stamps(tmp_path):
+    """The probe build that no product build exercises: each chained kernel compiled for gfx950 with the clock stamps of bg_stamps.h, by the Makefile's own
+    rule (its flags), the three side by side; each object must define the reader its decoder under tools/ calls."""
+    readers = {"bg_mlp_chain": "bg_probe_read_chain_stamps", "bg_mlp_chain_split": "bg_probe_read_split_stamps", "bg_mlp_chain_split_bwd": "bg_probe_read_bwd_stamps"}
+    objs = {k: str(tmp_path / f"{k}.o") for k in readers}
+    p = subprocess.run(["make", "-C", CSRC, "-j3", f"STAMPS_OBJ={tmp_path}"] + list(objs.values()), capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert p.stdout.count("-DBG_CHAIN_PROBE_STAMPS") == 3, p.stdout
+    for k, sym in readers.items():
+        defined = subprocess.check_output(["nm", "--defined-only", objs[k]], text=True)
+        assert re.search(rf"\bT {sym}$", defined, re.M), (k, sym)
+        decoder = {"bg_mlp_chain": "mlp_chain_stamps.py", "bg_mlp_chain_split": "chain_split_stamps.py", "bg_mlp_chain_split_bwd": "chain_split_bwd_stamps.py"}[k]
+        assert f"lib.{sym}(" in open(os.path.join(ROOT, "tools", decoder)).read(), (decoder, sym)
+
+
 def _synthetic_urdf(flat_model, path):
     """A URDF of the T1 topology written from the flat model, with the things the loader must fold: the trunk split into a root link plus two
     links behind FIXED joints (one of them rotated, one a chain of two), an inertial frame given with rpy, and a fixed sensor link on a shank."""

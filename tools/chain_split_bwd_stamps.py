@@ -1,5 +1,5 @@
 """Where a slab of the chained split-bf16 backward kernel spends its time: shader-clock stamps of every wave around every chunk barrier (probe build
-tools/build_chain_split_bwd_stamps.sh; BG_LIB=tools/probe/libbg_bwd_stamps.so python tools/chain_split_bwd_stamps.py [critic_wgs actor_wgs]).  Per network, the median
+tools/build_stamps.sh bg_mlp_chain_split_bwd; BG_LIB=tools/probe/bg_mlp_chain_split_bwd_stamps.so python tools/chain_split_bwd_stamps.py [critic_wgs actor_wgs]).  Per network, the median
 over all waves of the LAST slab of every workgroup: cycles waiting at the top of each chunk (counted wait + barrier), cycles in the compiler's own wait for the
 chunk's loads, cycles of the chunk's body next to its MFMA cycles (k-steps x 9 x 32), and the shader clock."""
 import ctypes as C, os, sys

@@ -1,5 +1,5 @@
 """Where a slab of the chained split-bf16 forward kernel spends its time: shader-clock stamps of every wave around every chunk barrier (probe build
-tools/build_chain_split_stamps.sh; BG_LIB=tools/probe/libbg_split_stamps.so python tools/chain_split_stamps.py [critic_wgs actor_wgs]).  Per network, the
+tools/build_stamps.sh bg_mlp_chain_split; BG_LIB=tools/probe/bg_mlp_chain_split_stamps.so python tools/chain_split_stamps.py [critic_wgs actor_wgs]).  Per network, the
 median over all waves of: cycles waiting at the top of each chunk (wait + barrier), cycles issuing the copies, cycles of the chunk's body, next to the MFMA
 cycles of the chunk (tiles x 2 k-steps x 9 x 32), and the shader clock (cycles / 100 MHz wall ticks).  `pair`: both networks side by side on two streams."""
 import ctypes as C, os, sys
