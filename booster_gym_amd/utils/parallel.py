@@ -14,9 +14,10 @@ calls of this file (tests/test_gpu_rccl.py).
 Enqueue-order contract (two communicators, two streams).  A communicator executes its collectives in the order they were ENQUEUED, per rank; ranks
 that enqueue the same communicator's collectives in different orders dead-lock or mix up buffers.  This build drives
   * the OWN communicator (utils/rccl.py): tag "moments" (the advantage moments, once per mini-epoch) and tag "bucket" (the grouped gradient /
-    statistics / log-std exchange, once per mini-epoch, inside Runner._epoch_gradients_and_step).  In the default one-stream mini-epoch
-    (Runner._epoch_on_one_stream) both are enqueued on the MAIN stream: one communicator, one stream.  With BG_ONE_STREAM=0 "moments" is enqueued on
-    the side stream (Runner._epoch_on_two_streams) and "bucket" on the main stream: one communicator driven from two streams of a rank;
+    statistics / log-std exchange, once per optimiser step, inside Runner._epoch_gradients_and_step).  "moments" is enqueued by
+    Runner._whole_batch_values: in the default one-stream mini-epoch (Runner.update calls it, then Runner._step) on the MAIN stream like "bucket": one
+    communicator, one stream.  With BG_ONE_STREAM=0 Runner._epoch_on_two_streams calls it under the side stream, and "bucket" stays on the main
+    stream: one communicator driven from two streams of a rank;
     with algorithm.empirical_normalization (and only then) tag "obs_norm": ONE float64 vector [column sums, column sums of squares, row count] of
     the iteration's observation rows, once per ITERATION, enqueued on the main stream behind the last mini-epoch's "bucket" (Runner.update ->
     ObsNormalizer.update_from), after which every rank merges the same totals into identical statistics;

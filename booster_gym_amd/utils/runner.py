@@ -22,6 +22,8 @@ Same surface: `Runner(test=False)` parses the reference's 8 CLI flags (runner.py
                              (bg_mlp_weight_grad_group_split_partial; BG_WGRAD_SPLIT=0: the fp32-MFMA launch bg_mlp_weight_grad_group_partial);
               tail           two launches (bg_update_tail): the deferred fixed-order sums + the squared-norm pieces, then clip + Adam + KL learning-rate
                              rule + statistics bookkeeping + the copies of the weights the layer kernels read (bf16 planes of W, -W, W^T, -W^T).
+            The sequence is written once, on the rows of a StepRows (the whole batch, or one of runner.num_mini_batches' K-ths of it): Runner.update ->
+            _whole_batch_values, then per optimiser step _step and _epoch_gradients_and_step; _epoch_on_two_streams places the same pieces on two streams.
   multi-GPU one process per GPU (torchrun), environments sharded; per mini-epoch one float64 moments all-reduce on the side stream and ONE grouped RCCL
             launch on the main stream (gradient bucket mean, loss / KL sums, log-std gradient mean) through an own communicator (utils/rccl.py) --
             SURVEY section 8e; the enqueue-order contract of the two communicators is written in utils/parallel.py.
@@ -37,7 +39,7 @@ import random
 import time
 
 import types
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -145,6 +147,25 @@ class UpdatePlan(NamedTuple):
     ahead: bool         # the rollout runs the first mini-epoch's forward passes
     ranks: bool         # several ranks: the exchanges run
     symmetry: bool = False  # the mirror-symmetry loss: the actor trains on 2B rows (the batch, then its mirror images) through bg_actor_head_sym
+
+
+class StepRows(NamedTuple):
+    """What one optimiser step of Runner.update() reads and writes, built once per update(): the whole batch (Runner._update_begin), or one of the K
+    mini-batches of runner.num_mini_batches (Runner._mini_batch_begin: rows [k b, (k + 1) b) of the gathered buffers)."""
+    ct: MLPTrainer                # the critic's and the actor's trainer
+    at: MLPTrainer
+    plan: UpdatePlan              # ... and the plan they run under
+    rows: int                     # the rows the loss is a mean over
+    wgrad: GroupedWeightGrad      # the grouped weight-gradient launch (its descriptors are static per input buffer)
+    x_c: torch.Tensor             # the critic's input; the step trains on its first train_rows rows (None: all; the whole batch carries last_values' N rows behind them)
+    train_rows: Optional[int]
+    x_a: torch.Tensor             # the actor's input (with the symmetry loss 2 x rows: the batch, then its mirror images)
+    actions: torch.Tensor
+    old_mu: torch.Tensor
+    old_logp: torch.Tensor
+    adv: torch.Tensor
+    ret: torch.Tensor
+    values: torch.Tensor          # where the value head of the fused kernels writes the values of x_c's rows
 
 
 TAIL_MAX_ITEMS = 8192  # blocks of sums of one bg_update_tail launch (bg_tail.hip)
@@ -584,88 +605,27 @@ class Runner:
         return out
 
     def _mini_batch_begin(self, u):
-        """Once per update(): the optimiser steps run on the mini-batch trainers under their own plan; the CU shares of their launches are sized for
-        b-row slabs; the descriptors of the gather."""
-        m, b = self._mb, self._mb_rows
-        u.ct, u.at, u.step_plan, u.rows = self._critic_mb, self._actor_mb, self._mb_plan, b
-        self._plan_chain_split(m.critic_in[:b], m.actor_in[:b], u.step_plan, u.ct, u.at)
+        """Once per update(): the K optimiser steps of a mini-epoch run on the mini-batch trainers under their own plan, step k on rows [k b, (k + 1) b)
+        of the gathered buffers; the CU shares of their launches are sized for b-row slabs; the descriptors of the gather."""
+        m, b, w = self._mb, self._mb_rows, u.whole
+        u.steps = [StepRows(self._critic_mb, self._actor_mb, self._mb_plan, b, self._mb_wgrad[k], m.critic_in[r], None, m.actor_in[r], m.actions[r], m.old_mu[r],
+                            m.old_logp[r], m.adv[r], m.ret[r], self._mb_values) for k, r in enumerate(slice(k * b, (k + 1) * b) for k in range(self._mini_batches))]
+        self._plan_chain_split(u.steps[0].x_c, u.steps[0].x_a, self._mb_plan, self._critic_mb, self._actor_mb)
         # the whole-batch passes of this update run one network at a time (old mu; the critic's values): one workgroup per slab, no CU share
         self._critic_tr.chain_workgroups = self._actor_tr.chain_workgroups = 0
         B = u.B
-        pairs = [(u.critic_all[:B], m.critic_in), (u.obs_flat[:B], m.actor_in), (u.act_flat, m.actions), (u.old_mu, m.old_mu), (self._old_logp, m.old_logp),
-                 (self._adv.view(B), m.adv), (self._ret.view(B), m.ret)]
+        pairs = [(w.x_c[:B], m.critic_in), (w.x_a[:B], m.actor_in), (w.actions, m.actions), (w.old_mu, m.old_mu), (w.old_logp, m.old_logp), (w.adv, m.adv),
+                 (w.ret, m.ret)]
         for src, dst in pairs:
             if not (src.is_contiguous() and src.dtype == torch.float32 and src.shape == dst.shape):
                 raise RuntimeError(f"mini-batch gather: a stream of shape {tuple(src.shape)} does not match its buffer {tuple(dst.shape)}")
         u.gather = (_lib.GatherStream * len(pairs))(*[_lib.GatherStream(src.data_ptr(), dst.data_ptr(), src.numel() // B, 0) for src, dst in pairs])
         u.gather_keep = pairs
 
-    def _whole_batch_values(self, u, have_fwd):
-        """The whole-batch pass of a mini-epoch, exactly as with one step per mini-epoch (runner.py:132-145): the critic on all (T + 1) N rows with
-        the current weights (in mini-epoch 0 the rollout's forward-ahead where the plan has it), time-out bootstrap, GAE, returns, advantage moments
-        and their exchange.  On the main stream."""
-        buf, T, N, B, alg, c_out, plan, ct = u.buf, u.T, u.N, u.B, u.alg, u.c_out, u.plan, self._critic_tr
-        if have_fwd:
-            u.main.wait_stream(u.side)  # the rollout ran the forward passes on the side stream
-        else:
-            ct.mirror_fresh = False  # the optimiser launch keeps the mini-batch trainers' weight copies current, not this trainer's
-        if plan.fused_head:
-            hc = ct.acts[2] if have_fwd else ct.forward_hidden(u.critic_all, train_rows=B)
-            if plan.fused_gae:
-                v_all = critic_values_gae(None if plan.chain_values else hc, c_out.weight, c_out.bias, buf["rewards"], buf["dones"], buf["time_outs"],
-                                          alg["gamma"], alg["lam"], self._values_all, self._adv, self._ret, self._adv_sums, self._gae_scratch)
-            else:
-                v_all = critic_head_forward(hc, c_out.weight, c_out.bias, self._values_all)
-        else:
-            v_all = ct.forward(u.critic_all, train_rows=B).squeeze(-1)
-        if not (plan.fused_head and plan.fused_gae):
-            gae(buf["rewards"], buf["dones"], buf["time_outs"], v_all[:B].view(T, N), v_all[B:], alg["gamma"], alg["lam"],
-                advantages=self._adv, returns=self._ret, sums=self._adv_sums)
-        self.dp.sum_(self._adv_sums, tag="moments")  # exchange (1)
-
     def _shuffle(self, u, epoch):
         """A fresh permutation of the batch's rows and ONE gather of every per-row stream the K steps read, mini-batch after mini-batch."""
         self.permutation(self._mb_updates, epoch, out=self._perm)
         _lib.check(_lib.load().bg_gather_rows(u.B, u.B, _lib.ptr(self._perm), u.gather, len(u.gather), _lib.current_stream_ptr()), "bg_gather_rows")
-
-    def _mini_batch_step(self, u, k):
-        """Optimiser step k of a mini-epoch up to its backward-data passes, on rows [k b, (k + 1) b) of the gathered buffers: today's launch
-        sequence on the main stream -- both forward passes, the critic's values on those rows, both output layers fused with the loss, both
-        backward-data passes.  Advantages and returns are the whole-batch pass's; the advantages are normalised with its moments.  Leaves fins /
-        fin_c / fin_a in u for _epoch_gradients_and_step."""
-        m, b, plan, ct, at, alg, a_out, c_out = self._mb, self._mb_rows, u.step_plan, u.ct, u.at, u.alg, u.a_out, u.c_out
-        r = slice(k * b, (k + 1) * b)
-        x_c, x_a = m.critic_in[r], m.actor_in[r]
-        u.wgrad_group = self._mb_wgrad[k]
-        fins = fin_c = fin_a = None
-        if plan.fused_head:
-            if plan.one_stream:
-                hc, ha = MLPTrainer.forward_hidden_group([(ct, x_c, None), (at, x_a, None)])
-            else:
-                hc, ha = ct.forward_hidden(x_c), at.forward_hidden(x_a)
-            values = self._mb_values if plan.chain_values else critic_head_forward(hc, c_out.weight, c_out.bias, self._mb_values)
-            if plan.defer:
-                fins, fin_c, fin_a = [], _lib.ReduceProblem(), _lib.ReduceProblem()
-            critic_head_backward(hc, c_out.weight, values, m.ret[r], ct.hidden_grad, c_out.weight.grad, c_out.bias.grad, ct.layers[-2].bias.grad, self._stats,
-                                 self._head_scratch_c, finish=fin_c)
-            actor_head_loss_backward(ha, a_out.weight, a_out.bias, u.logstd_flat, m.actions[r], m.old_mu[r], u.old_logstd, m.old_logp[r], m.adv[r], self._adv_sums,
-                                     0.2, alg["bound_coef"], alg["entropy_coef"], at.hidden_grad, a_out.weight.grad, a_out.bias.grad, at.layers[-2].bias.grad,
-                                     self._grad_logstd, self._stats, self._head_scratch_a, finish=fin_a)
-            if plan.ranks and not plan.defer:
-                self._exchange_sums()  # exchange (3)
-            if plan.one_stream:
-                MLPTrainer.backward_hidden_group([ct, at], fins)
-            else:
-                ct.backward_hidden(finishes=fins)
-                at.backward_hidden(finishes=fins)
-        else:
-            mu, values = at.forward(x_a), ct.forward(x_c).squeeze(-1)
-            ppo_loss_fused(mu, u.logstd_flat, m.actions[r], m.old_mu[r], u.old_logstd, m.old_logp[r], m.adv[r], self._adv_sums, values, m.ret[r], 0.2,
-                           alg["bound_coef"], alg["entropy_coef"], self._grad_mu[:b], self._grad_val[:b], self._grad_logstd, self._stats)
-            self._exchange_sums()  # exchange (3)
-            ct.backward(self._grad_val[:b].view(b, 1))
-            at.backward(self._grad_mu[:b])
-        u.fins, u.fin_c, u.fin_a = fins, fin_c, fin_a
 
     def rollout(self):
         """runner.py:106-121: horizon_length env steps with sampled actions, outputs written in place.
@@ -759,27 +719,34 @@ class Runner:
         method starts from them and from the weight copies the last optimiser launch wrote -- parameters and rollout buffers must not have been changed
         in between except through `invalidate()` (which `_load` and the initial broadcast call)."""
         u = self._update_begin(self._resolve_plan())
-        K = self._mini_batches
+        K, w = self._mini_batches, u.whole
         if K > 1:
             self._mini_batch_begin(u)
         with torch.no_grad():
             for epoch in range(self.cfg["runner"]["mini_epochs"]):
                 # this mini-epoch's hidden activations and values may be the rollout's: same kernels, same weights
                 have_fwd = u.ahead and epoch == 0
-                if K > 1:
-                    # runner.num_mini_batches: the whole-batch pass once, then K optimiser steps on disjoint shuffled K-ths of the batch; returns and
-                    # advantages stay fixed for the K steps, the KL rule moves the learning rate after every one of them
-                    self._whole_batch_values(u, have_fwd)
-                    self._shuffle(u, epoch)
-                    for k in range(K):
-                        self._mini_batch_step(u, k)
-                        self._epoch_gradients_and_step(u)
+                if K == 1 and not u.plan.one_stream:
+                    self._epoch_on_two_streams(u, have_fwd)  # the same pieces, the critic's on the side stream beside the actor's
+                    self._epoch_gradients_and_step(u, w)
                     continue
-                if u.plan.one_stream:
-                    self._epoch_on_one_stream(u, have_fwd)
+                # Per mini-epoch: the whole-batch values, returns and advantages from the current critic; then the optimiser steps, each on its rows (K = 1:
+                # one step on the whole batch; runner.num_mini_batches = K: on disjoint shuffled K-ths of it -- returns and advantages stay fixed for the
+                # K steps, the KL rule moves the learning rate after every one of them).  Every launch on the main stream.
+                hc = ha = None
+                if have_fwd:
+                    u.main.wait_stream(u.side)  # the rollout ran the forward passes on the side stream
+                    hc, ha = w.ct.acts[2], w.at.acts[2]
+                elif K == 1:
+                    hc, ha = self._forward_hidden(w)  # the one step's rows are the values pass's: both networks' forward passes as its grouped launch
                 else:
-                    self._epoch_on_two_streams(u, have_fwd)
-                self._epoch_gradients_and_step(u)
+                    w.ct.mirror_fresh = False  # the optimiser launch keeps the mini-batch trainers' weight copies current, not this trainer's
+                hc, v_all = self._whole_batch_values(u, hc)
+                if K > 1:
+                    self._shuffle(u, epoch)
+                for v in u.steps:
+                    self._step(u, v, (hc, ha, v_all[: u.B]) if K == 1 else None)
+                    self._epoch_gradients_and_step(u, v)
             if self.obs_norm is not None:
                 # behind the last optimiser step: this iteration's T x N rows enter the statistics (row T is the next iteration's row 0), under data
                 # parallelism all ranks' rows through ONE float64 exchange (tag "obs_norm", main stream, behind the last "bucket": utils/parallel.py)
@@ -840,116 +807,152 @@ class Runner:
         self._stats.zero_()
         self._grad_logstd.zero_()
         self._plan_chain_split(critic_all, obs_flat, plan)
-        # (two streams, plan.one_stream = False: side stream = critic forward -> GAE ... critic backward; main stream = actor)
-        return types.SimpleNamespace(cfg=cfg, buf=buf, T=T, N=N, B=B, A=A, alg=alg, act_flat=act_flat, ahead=ahead, obs_flat=obs_flat, critic_all=critic_all,
-                                     plan=plan, logstd_flat=logstd_flat, a_out=a_out, c_out=c_out, old_mu=old_mu, old_logstd=old_logstd,
-                                     main=torch.cuda.current_stream(), side=self._side_stream, mirrors=None,
-                                     # what an optimiser step runs on: the trainers, their plan, their rows (runner.num_mini_batches > 1: the mini-batch pair)
-                                     ct=self._critic_tr, at=self._actor_tr, step_plan=plan, rows=B, wgrad_group=self._wgrad_group)
+        whole = StepRows(self._critic_tr, self._actor_tr, plan, B, self._wgrad_group, critic_all, B, obs_flat, act_flat, old_mu, self._old_logp, self._adv.view(B),
+                         self._ret.view(B), self._values_all)
+        # whole: the batch as the rows of one optimiser step; steps: what the steps of a mini-epoch run on (runner.num_mini_batches > 1: _mini_batch_begin)
+        return types.SimpleNamespace(cfg=cfg, buf=buf, T=T, N=N, B=B, alg=alg, ahead=ahead, plan=plan, logstd_flat=logstd_flat, old_logstd=old_logstd,
+                                     main=torch.cuda.current_stream(), side=self._side_stream, mirrors=None, whole=whole, steps=[whole])
 
-    def _epoch_on_two_streams(self, u, have_fwd):
-        """Side stream: the critic's forward pass (unless the rollout ran it), values, time-out bootstrap, GAE, returns, advantage moments and their
-        exchange (runner.py:132-145).  Main stream: the actor's forward pass; then both output layers fused with the loss, both backward-data chains
-        on their streams (runner.py:147-163).  Leaves fins / fin_c / fin_a in u."""
-        buf, T, N, B, alg, act_flat, obs_flat, critic_all, logstd_flat, a_out, c_out, old_mu, old_logstd, main, side, plan = (
-            u.buf, u.T, u.N, u.B, u.alg, u.act_flat, u.obs_flat, u.critic_all, u.logstd_flat, u.a_out, u.c_out, u.old_mu, u.old_logstd, u.main, u.side, u.plan)
-        # parameters updated by the previous optimiser step; the loss accumulators (_stats, _grad_logstd) were zeroed by it (before the loop
-        # for the first mini-epoch): both heads add into them
-        # (plan.chain_values: the chained forward kernel also evaluates the value head, from the registers that hold the last activations: the launch
-        # between the critic's forward and the actor's loss then has 400 KB to read instead of 52 MB)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            if plan.fused_head:
-                if have_fwd:
-                    hc = self._critic_tr.acts[2]
-                else:
-                    hc = self._critic_tr.forward_hidden(critic_all, train_rows=B)
-                if plan.fused_gae:
-                    # output layer + timeout bootstrap + GAE + returns + advantage moments in ONE launch in front of the actor's loss
-                    v_all = critic_values_gae(None if plan.chain_values else hc, c_out.weight, c_out.bias, buf["rewards"], buf["dones"], buf["time_outs"],
-                                              alg["gamma"], alg["lam"], self._values_all, self._adv, self._ret, self._adv_sums, self._gae_scratch)
-                else:
-                    v_all = critic_head_forward(hc, c_out.weight, c_out.bias, self._values_all)
-            else:
-                v_all = self._critic_tr.forward(critic_all, train_rows=B).squeeze(-1)
-            values, last_values = v_all[:B], v_all[B:]
-            if not (plan.fused_head and plan.fused_gae):
-                gae(buf["rewards"], buf["dones"], buf["time_outs"], values.view(T, N), last_values, alg["gamma"], alg["lam"],
-                    advantages=self._adv, returns=self._ret, sums=self._adv_sums)
-            self.dp.sum_(self._adv_sums, tag="moments")  # exchange (1), on the side stream: hidden under the actor forward
-            gae_done = side.record_event()
-        defer, fins, fin_c, fin_a = plan.defer, None, None, None
-        if plan.fused_head:
-            # Output layers fused with the loss (bg_head.hip): per network ONE pass over the [B][128] hidden activations gives the
-            # output, the loss terms, dL/dz of the hidden layer and the output layer's gradients.  Both heads add into _stats.
-            # defer (the default, see __init__): the small fixed-order reductions behind the head kernels and behind every backward layer
-            # (output-layer and bias gradients, loss statistics: nothing a chain needs) run as ONE launch in front of the weight-gradient launch
-            # (bg_reduce_group, or inside bg_update_tail) instead of inside the chains.
-            fins = [] if defer else None
-            fin_c, fin_a = (_lib.ReduceProblem(), _lib.ReduceProblem()) if defer else (None, None)
-            ha = self._actor_tr.acts[2] if have_fwd else self._actor_tr.forward_hidden(obs_flat)
-            with torch.cuda.stream(side):
-                critic_head_backward(hc[:B], c_out.weight, values, self._ret.view(B), self._critic_tr.hidden_grad, c_out.weight.grad,
-                                     c_out.bias.grad, self._critic_tr.layers[-2].bias.grad, self._stats, self._head_scratch_c, finish=fin_c)
-                self._critic_tr.backward_hidden(finishes=fins)
-            main.wait_event(gae_done)  # advantages and their moments
-            self._actor_loss_head(u, ha, fin_a)
-            if plan.ranks and not defer:
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    self._exchange_sums()  # exchange (3): loss / KL sums, hidden under the backward passes
-            self._actor_tr.backward_hidden(finishes=fins)
-        else:
-            mu = self._actor_tr.forward(obs_flat)
-            main.wait_stream(side)
-            ppo_loss_fused(mu, logstd_flat, act_flat, old_mu, old_logstd, self._old_logp, self._adv.view(B), self._adv_sums,
-                           values, self._ret.view(B), 0.2, alg["bound_coef"], alg["entropy_coef"], self._grad_mu, self._grad_val,
-                           self._grad_logstd, self._stats)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                self._exchange_sums()  # exchange (3): loss / KL sums, hidden under the backward passes
-                self._critic_tr.backward(self._grad_val.view(B, 1))
-            self._actor_tr.backward(self._grad_mu)
-        u.fins, u.fin_c, u.fin_a = fins, fin_c, fin_a
+    # ------------------------------------------------------------------ the pieces of a mini-epoch, each on the rows of a StepRows, on the current stream
+    def _forward_hidden(self, v):
+        """The hidden layers of both networks on v's rows: one grouped launch, or one pass per network.  Returns their last hidden activations."""
+        if v.plan.one_stream:
+            return MLPTrainer.forward_hidden_group([(v.ct, v.x_c, v.train_rows), (v.at, v.x_a, None)])
+        return v.ct.forward_hidden(v.x_c, train_rows=v.train_rows), v.at.forward_hidden(v.x_a)
 
-    def _epoch_on_one_stream(self, u, have_fwd):
-        """What _epoch_on_two_streams does, as one sequence of launches on the main stream: both forward chains in
-        one launch (unless the rollout ran them), values + GAE + moments (+ their exchange), the two output layers fused with the loss, both
-        backward-data chains in one launch (runner.py:132-163).  Same kernels on the same slabs with the same reduction order as the two-stream form:
-        bit-identical results (tests/test_gpu_ppo.py).  Leaves fins / fin_c / fin_a in u."""
-        buf, B, alg, act_flat, obs_flat, critic_all, logstd_flat, a_out, c_out, old_mu, old_logstd = u.buf, u.B, u.alg, u.act_flat, u.obs_flat, u.critic_all, u.logstd_flat, u.a_out, u.c_out, u.old_mu, u.old_logstd
-        ct, at = self._critic_tr, self._actor_tr
-        if have_fwd:
-            u.main.wait_stream(u.side)  # the rollout ran the forward passes on the side stream
-            hc, ha = ct.acts[2], at.acts[2]
+    def _head_values(self, v, hc):
+        """The critic's values of v.x_c's rows in v.values: left there by the chained forward launch's value head (plan.chain_values: from the registers
+        that hold the last activations, so that the launch between the critic's forward and the actor's loss has 400 KB to read instead of 52 MB), or
+        the output layer on the stored activations hc."""
+        c_out = v.ct.layers[-1]
+        return v.values if v.plan.chain_values else critic_head_forward(hc, c_out.weight, c_out.bias, v.values)
+
+    def _whole_batch_values(self, u, hc):
+        """The whole-batch pass of a mini-epoch (runner.py:132-145): the critic on all (T + 1) N rows with the current weights, time-out bootstrap, GAE,
+        returns, advantage moments and their exchange.  hc: the critic's last hidden activations where a forward pass has left them (the rollout's
+        forward-ahead in mini-epoch 0, the grouped launch of both networks), None: the pass runs here.  Returns hc and the values of all rows."""
+        v, plan, buf, alg, T, N, B = u.whole, u.plan, u.buf, u.alg, u.T, u.N, u.B
+        if plan.fused_head and hc is None:
+            hc = v.ct.forward_hidden(v.x_c, train_rows=v.train_rows)
+        if plan.fused_head and plan.fused_gae:
+            # output layer + timeout bootstrap + GAE + returns + advantage moments in ONE launch in front of the actor's loss
+            c_out = v.ct.layers[-1]
+            v_all = critic_values_gae(None if plan.chain_values else hc, c_out.weight, c_out.bias, buf["rewards"], buf["dones"], buf["time_outs"], alg["gamma"],
+                                      alg["lam"], v.values, self._adv, self._ret, self._adv_sums, self._gae_scratch)
         else:
-            hc, ha = MLPTrainer.forward_hidden_group([(ct, critic_all, B), (at, obs_flat, None)])
-        v_all = critic_values_gae(None, c_out.weight, c_out.bias, buf["rewards"], buf["dones"], buf["time_outs"], alg["gamma"], alg["lam"], self._values_all,
-                                  self._adv, self._ret, self._adv_sums, self._gae_scratch)
-        values = v_all[:B]
+            v_all = self._head_values(v, hc) if plan.fused_head else v.ct.forward(v.x_c, train_rows=v.train_rows).squeeze(-1)
+            gae(buf["rewards"], buf["dones"], buf["time_outs"], v_all[:B].view(T, N), v_all[B:], alg["gamma"], alg["lam"], advantages=self._adv,
+                returns=self._ret, sums=self._adv_sums)
         self.dp.sum_(self._adv_sums, tag="moments")  # exchange (1)
-        fins, fin_c, fin_a = [], _lib.ReduceProblem(), _lib.ReduceProblem()
-        critic_head_backward(hc[:B], c_out.weight, values, self._ret.view(B), ct.hidden_grad, c_out.weight.grad, c_out.bias.grad, ct.layers[-2].bias.grad,
-                             self._stats, self._head_scratch_c, finish=fin_c)
-        self._actor_loss_head(u, ha, fin_a)
-        MLPTrainer.backward_hidden_group([ct, at], fins)
-        u.fins, u.fin_c, u.fin_a = fins, fin_c, fin_a
+        return hc, v_all
 
-    def _actor_loss_head(self, u, ha, finish):
+    # Output layers fused with the loss (bg_head.hip): per network ONE pass over the [rows][128] hidden activations gives the output, the loss terms,
+    # dL/dz of the hidden layer and the output layer's gradients.  Both heads add into _stats, which the previous optimiser step zeroed (before the
+    # loop for the first).  plan.defer (the default, see __init__): the small fixed-order reductions behind the head kernels and behind every backward
+    # layer (output-layer and bias gradients, loss statistics: nothing a chain needs) are left as descriptors and run as ONE launch in front of the
+    # weight-gradient launch (bg_reduce_group, or inside bg_update_tail) instead of inside the chains.
+    @staticmethod
+    def _deferred_finishes(plan):
+        """(fins, fin_c, fin_a): the list the backward passes append their descriptors to and those of the critic's and the actor's head."""
+        return ([], _lib.ReduceProblem(), _lib.ReduceProblem()) if plan.defer else (None, None, None)
+
+    def _critic_loss_head(self, v, hc, values, finish):
+        """The critic's output layer fused with the value loss and its backward (runner.py:148) on the last hidden activations hc."""
+        ct, c_out = v.ct, v.ct.layers[-1]
+        critic_head_backward(hc[: v.rows], c_out.weight, values, v.ret, ct.hidden_grad, c_out.weight.grad, c_out.bias.grad, ct.layers[-2].bias.grad, self._stats,
+                             self._head_scratch_c, finish=finish)
+
+    def _actor_loss_head(self, u, v, ha, finish):
         """The actor's output layer fused with its loss and backward (runner.py:145-161) on the last hidden activations ha: bg_actor_head, or with the
-        mirror-symmetry loss bg_actor_head_sym on the 2B rows of ha (the batch, then its mirror images)."""
-        at, a_out, alg = self._actor_tr, u.a_out, u.alg
-        args = (ha, a_out.weight, a_out.bias, u.logstd_flat, u.act_flat, u.old_mu, u.old_logstd, self._old_logp, self._adv.view(u.B), self._adv_sums, 0.2,
-                alg["bound_coef"], alg["entropy_coef"])
+        mirror-symmetry loss bg_actor_head_sym on the 2B rows of ha (the batch, then its mirror images).  The advantages are normalised with the
+        whole batch's moments."""
+        at, a_out, alg = v.at, v.at.layers[-1], u.alg
+        args = (ha, a_out.weight, a_out.bias, u.logstd_flat, v.actions, v.old_mu, u.old_logstd, v.old_logp, v.adv, self._adv_sums, 0.2, alg["bound_coef"],
+                alg["entropy_coef"])
         outs = (at.hidden_grad, a_out.weight.grad, a_out.bias.grad, at.layers[-2].bias.grad, self._grad_logstd, self._stats, self._head_scratch_a)
-        if u.plan.symmetry:
+        if v.plan.symmetry:
             actor_head_sym_loss_backward(*args, self._symmetric_coef, self._act_mirror, *outs, finish=finish)
         else:
             actor_head_loss_backward(*args, *outs, finish=finish)
 
-    def _epoch_gradients_and_step(self, u):
-        """Deferred reductions, all weight gradients, the exchange of the gradient over the ranks, clip + Adam + KL rule (runner.py:162-180)."""
-        cfg, B, alg, main, side, plan = u.cfg, u.rows, u.alg, u.main, u.side, u.step_plan
+    def _library_loss(self, u, v, mu, values):
+        """Output layers as library GEMMs (plan.fused_head = False): the PPO loss of both networks' outputs and its gradients in one launch (bg_ppo_loss).
+        Returns dL/d values [rows, 1] and dL/d mu, what the two backward passes start from."""
+        alg, g_mu, g_val = u.alg, self._grad_mu[: v.rows], self._grad_val[: v.rows]
+        ppo_loss_fused(mu, u.logstd_flat, v.actions, v.old_mu, u.old_logstd, v.old_logp, v.adv, self._adv_sums, values, v.ret, 0.2, alg["bound_coef"],
+                       alg["entropy_coef"], g_mu, g_val, self._grad_logstd, self._stats)
+        return g_val.view(v.rows, 1), g_mu
+
+    def _step(self, u, v, fwd=None):
+        """One optimiser step up to its backward-data passes on the rows of v, as one sequence of launches on the current stream (runner.py:147-163):
+        both forward passes and the critic's values on those rows, both output layers fused with the loss, both backward-data passes -- with
+        plan.one_stream each pair of passes as ONE launch.  fwd = (hc, ha, values): the last hidden activations and the critic's values where earlier
+        launches have left them (K = 1: the step's rows are the values pass's).  Leaves fins / fin_c / fin_a in u for _epoch_gradients_and_step."""
+        plan, ct, at = v.plan, v.ct, v.at
+        fins = fin_c = fin_a = None
+        if plan.fused_head:
+            if fwd is None:
+                hc, ha = self._forward_hidden(v)
+                values = self._head_values(v, hc)
+            else:
+                hc, ha, values = fwd
+            fins, fin_c, fin_a = self._deferred_finishes(plan)
+            self._critic_loss_head(v, hc, values, fin_c)
+            self._actor_loss_head(u, v, ha, fin_a)
+            if plan.ranks and not plan.defer:
+                self._exchange_sums()  # exchange (3)
+            if plan.one_stream:
+                MLPTrainer.backward_hidden_group([ct, at], fins)
+            else:
+                ct.backward_hidden(finishes=fins)
+                at.backward_hidden(finishes=fins)
+        else:
+            g_val, g_mu = self._library_loss(u, v, at.forward(v.x_a), ct.forward(v.x_c, train_rows=v.train_rows).squeeze(-1)[: v.rows])
+            self._exchange_sums()  # exchange (3)
+            ct.backward(g_val)
+            at.backward(g_mu)
+        u.fins, u.fin_c, u.fin_a = fins, fin_c, fin_a
+
+    def _epoch_on_two_streams(self, u, have_fwd):
+        """One step on the whole batch with the critic on the side stream (plan.one_stream = False at K = 1).  Side stream: the whole-batch values pass,
+        the critic's loss head and backward-data pass.  Main stream: the actor's forward pass, its loss head once the advantages are there, its
+        backward-data pass.  The pieces are _step's; the hand-overs between the streams are this function's.  Leaves fins / fin_c / fin_a in u."""
+        v, plan, main, side = u.whole, u.plan, u.main, u.side
+        ct, at = v.ct, v.at
+        side.wait_stream(main)  # parameters updated by the previous optimiser step
+        with torch.cuda.stream(side):
+            hc, v_all = self._whole_batch_values(u, ct.acts[2] if have_fwd else None)  # (exchange (1) on the side stream: hidden under the actor forward)
+            gae_done = side.record_event()
+        values = v_all[: u.B]
+        fins = fin_c = fin_a = None
+        if plan.fused_head:
+            fins, fin_c, fin_a = self._deferred_finishes(plan)
+            ha = at.acts[2] if have_fwd else at.forward_hidden(v.x_a)
+            with torch.cuda.stream(side):
+                self._critic_loss_head(v, hc, values, fin_c)
+                ct.backward_hidden(finishes=fins)
+            main.wait_event(gae_done)  # advantages and their moments
+            self._actor_loss_head(u, v, ha, fin_a)
+            if plan.ranks and not plan.defer:
+                side.wait_stream(main)
+                with torch.cuda.stream(side):
+                    self._exchange_sums()  # exchange (3): loss / KL sums, hidden under the backward passes
+            at.backward_hidden(finishes=fins)
+        else:
+            mu = at.forward(v.x_a)
+            main.wait_stream(side)
+            g_val, g_mu = self._library_loss(u, v, mu, values)
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                self._exchange_sums()  # exchange (3): loss / KL sums, hidden under the backward passes
+                ct.backward(g_val)
+            at.backward(g_mu)
+        u.fins, u.fin_c, u.fin_a = fins, fin_c, fin_a
+
+    def _epoch_gradients_and_step(self, u, v):
+        """Deferred reductions, all weight gradients, the exchange of the gradient over the ranks, clip + Adam + KL rule (runner.py:162-180) of the step
+        on the rows of v."""
+        cfg, B, alg, main, side, plan = u.cfg, v.rows, u.alg, u.main, u.side, v.plan
         fins, fin_c, fin_a, mirrors = u.fins, u.fin_c, u.fin_a, u.mirrors
         # (the first optimiser step after a checkpoint restore runs the separate launches: see __init__)
         fused_tail, one_tail = plan.fused_opt and not self._lr_restart, plan.one_tail and not self._lr_restart
@@ -963,7 +966,7 @@ class Runner:
                     self._exchange_sums()  # exchange (3), beside the weight gradients
         # all weight gradients after both backward chains, alone on the GPU: one launch pair for the six hidden layers (shapes outside the
         # kernel's range, or MLPTrainer.FUSED_WGRAD = False: library GEMMs, layer by layer); one_tail: their finish inside bg_update_tail
-        wg_partial = u.wgrad_group.run((u.ct, u.at), plan.wgrad, one_tail)
+        wg_partial = v.wgrad.run((v.ct, v.at), plan.wgrad, one_tail)
         if plan.defer and plan.ranks:
             main.wait_stream(side)
         if one_tail and plan.ranks:
@@ -978,7 +981,7 @@ class Runner:
             # ... and the copies of the weights that the layer kernels read (zero-padded first layers, transposed hidden layers): written by the
             # same launch instead of six strided torch copies inside the chains of the next mini-epoch
             if mirrors is None:
-                ms = u.ct.mirror_descriptors(self.optimizer.flat) + u.at.mirror_descriptors(self.optimizer.flat)
+                ms = v.ct.mirror_descriptors(self.optimizer.flat) + v.at.mirror_descriptors(self.optimizer.flat)
                 mirrors = (_lib.ParamMirror * len(ms))(*ms) if 0 < len(ms) <= 16 else None
             if one_tail and not plan.ranks:
                 self.optimizer.step_tail(wg_partial, [fin_c, fin_a] + fins, self._stats, self._stats_acc, self._stats_last, 4, B, alg["desired_kl"],
@@ -986,11 +989,11 @@ class Runner:
             else:
                 self.optimizer.step_fused(self._stats, self._stats_acc, self._stats_last, 4, B * self.world_size, alg["desired_kl"],
                                           grad_logstd=self._grad_logstd, ls_off=self._logstd_off, mirrors=mirrors)
-            u.at.mirror_fresh = u.ct.mirror_fresh = mirrors is not None
+            v.at.mirror_fresh = v.ct.mirror_fresh = mirrors is not None
         else:
             self._logstd_grad_view.copy_(self._grad_logstd)  # (behind the bucket's all-reduce, which carries a stale value in this slot)
             self.optimizer.step()
-            u.at.mirror_fresh = u.ct.mirror_fresh = False  # this launch does not write the weight copies: the next pass copies them
+            v.at.mirror_fresh = v.ct.mirror_fresh = False  # this launch does not write the weight copies: the next pass copies them
             if self._lr_restart:  # first step after a checkpoint load: see __init__
                 self.optimizer.lr.fill_(float(cfg["algorithm"]["learning_rate"]))
                 self._lr_restart = False

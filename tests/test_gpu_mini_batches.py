@@ -1,6 +1,7 @@
 """runner.num_mini_batches on the GPU: the device permutation against the host harness, bg_gather_rows against torch.index_select, Runner.update()
 with K steps per mini-epoch against a torch restatement of the reference loop with the K-step inner loop (fed the device's permutations), off is
-off, reproducibility, the refusal of the symmetry loss and a short training run."""
+off, every switch that selects another branch inside a step or its tail against the default at K = 2, reproducibility, the refusal of the symmetry loss
+and a short training run."""
 import numpy as np
 import pytest
 import torch
@@ -261,6 +262,66 @@ def test_mini_batches_with_frame_stack_height_scan_and_normalisation_through_the
     torch.cuda.synchronize()
     assert norm.count == 2 * T * n
     compare_with_reference(r, ref_model, stats_ref, lr_ref, p_start, acc)
+
+
+# ------------------------------------------------------------------ every branch inside a step or its tail, at K = 2
+# the entries of tests/test_gpu_ppo.py::SWITCHES that select another branch inside an optimiser step or its tail, and BG_DEFER_FINISH = 0
+STEP_SWITCHES = ("two_launches_on_two_streams", "tail_as_three_launches", "separate_optimizer_tail", "values_from_stored_activations",
+                 "output_layers_as_library_gemms", "hidden_layers_one_launch_each", "hidden_layers_as_library_gemms", "immediate_reductions")
+
+
+def _update_with_two_mini_batches_under(switch):
+    from test_gpu_ppo import SWITCHES
+
+    from booster_gym_amd.utils.model import MLPTrainer
+
+    attrs, cls_attrs = ({"_defer_finish": False}, {}) if switch == "immediate_reductions" else SWITCHES[switch]
+    saved = {k: getattr(MLPTrainer, k) for k in cls_attrs}
+    try:
+        for k, v in cls_attrs.items():
+            setattr(MLPTrainer, k, v)
+        r = _runner(128, **{"runner.mini_epochs": 3, "runner.horizon_length": 24, KEY: 2, "basic.seed": 11})
+        for k, v in attrs.items():
+            assert hasattr(r, k)
+            setattr(r, k, v)
+        _start(r)
+        start = r.optimizer.flat.clone()
+        r.rollout()
+        acc = r.update().clone()
+        torch.cuda.synchronize()
+        assert r.optimizer.step_count == 3 * 2 and r._mb_updates == 1
+        return start, r.optimizer.flat.clone(), acc, r._summarize(acc), r._mb_plan
+    finally:
+        for k, v in saved.items():
+            setattr(MLPTrainer, k, v)
+
+
+@pytest.fixture(scope="module")
+def default_update_with_two_mini_batches():
+    return _update_with_two_mini_batches_under("default")
+
+
+@pytest.mark.parametrize("switch", STEP_SWITCHES)
+def test_update_with_mini_batches_through_every_step_switch_matches_the_default(switch, default_update_with_two_mini_batches):
+    """What tests/test_gpu_ppo.py::test_update_through_every_switch_matches_the_default states at one step per mini-epoch, at K = 2 (128 envs, horizon 24,
+    3 mini-epochs: six optimiser steps on 1,536 rows each, one update() after one rollout()), under the same rule: parameters within 2 % of the
+    distance they moved, loss statistics to 1e-3, the same learning rate.  Every switch gives the steps a plan of its own.  BG_ONE_STREAM = 0 only
+    schedules: at K > 1 it runs the default's kernels as separate launches on the main stream, so the parameters and the loss sums keep their bits."""
+    from test_gpu_ppo import _assert_same_adam_steps
+
+    start, p0, a0, s0, plan0 = default_update_with_two_mini_batches
+    _, p1, a1, s1, plan1 = _update_with_two_mini_batches_under(switch)
+    assert plan1 != plan0, (switch, plan1)
+    for k in ("value_loss", "actor_loss", "bound_loss", "entropy", "kl_mean"):
+        print(f"{switch} {k}: {s1[k]!r} against {s0[k]!r}")
+    print(f"{switch} lr: {s1['lr']!r} against {s0['lr']!r}; max |p1 - p0| {(p1 - p0).abs().max().item():.3e}, moved {(p0 - start).abs().max().item():.3e}")
+    if switch == "two_launches_on_two_streams":
+        assert torch.equal(p1, p0) and torch.equal(a1, a0)
+        return
+    _assert_same_adam_steps(switch, p1, p0, start)
+    for k in ("value_loss", "actor_loss", "bound_loss", "entropy", "kl_mean"):
+        assert abs(s1[k] - s0[k]) <= 1e-3 * max(1.0, abs(s0[k])), (k, s1[k], s0[k])
+    assert abs(s1["lr"] - s0["lr"]) < 1e-9
 
 
 # ------------------------------------------------------------------ the runner
