@@ -1,6 +1,7 @@
 // Fused actor MLP + Gaussian sample for the rollout at any supported architecture (reference utils/model.py:8-25 with the widths a user sets,
 // utils/runner.py:109-111: dist = model.act(obs); act = dist.sample()), fp32 MFMA, gfx950 only.  bg_actor_sample (bg_ppo.hip) keeps the
-// reference's widths built into its kernel; this one reads them from descriptors: 47 H inputs (H = 1 .. 10 observation frames, env.frame_stack),
+// reference's widths built into its kernel; this one reads them from descriptors: 47 H inputs (H = 1 .. 10 observation frames, env.frame_stack)
+// and with terrain.actor_heights P more, the height scan (K = 47 H + P up to 480 = BG_ACTOR_MAX_INPUT: whole k-chunks within the 516-column LDS tile),
 // 2 to 4 hidden ELU layers of widths a multiple of 128 up to 512, 12 outputs.
 //
 // One workgroup (4 waves) = 16 observation rows.  The activations ping-pong between two LDS tiles [16][MAXW + 4]; each wave owns the 16-neuron
@@ -45,7 +46,7 @@ struct ActorNet {
 
 __device__ __forceinline__ float elu(float x) { return x > 0.f ? x : expm1f(x); }  // = bg_ppo.hip's
 
-// first layer: K = 47 H inputs (rows not 16-byte aligned): scalar weight loads, k padded to a multiple of KC with zeros; OUT a multiple of 16.  A wave
+// first layer: K = 47 H (+ P) inputs (rows not 16-byte aligned): scalar weight loads, k padded to a multiple of KC with zeros; OUT a multiple of 16.  A wave
 // walks its (tile, k-chunk) steps in one flat loop, the weights of step s + 1 in flight under the 12 MFMAs of step s; with H = 1 one step per tile.
 template <int LDA>
 __device__ __forceinline__ void first_layer(const float* __restrict__ W, const float* __restrict__ bv, int K, int OUT, const float* in, float* out,
@@ -137,7 +138,7 @@ __global__ __launch_bounds__(256) void actor_mlp_sample_kernel(int N, const floa
     constexpr int LDA = MAXW + 4;  // row stride (floats): = 4 mod 64 banks, as bg_actor_sample's 260
     __shared__ __attribute__((aligned(16))) float buf[2][MR * LDA];
     const int r0 = blockIdx.x * MR, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int K = net.in[0], KP = (K + KC - 1) / KC * KC;  // obs row stride 47 H; the tile's columns padded to whole k-chunks with zeros (KP <= LDA: host)
+    const int K = net.in[0], KP = (K + KC - 1) / KC * KC;  // obs row stride 47 H (+ P); the tile's columns padded to whole k-chunks with zeros (KP <= LDA: host)
     for (int k = threadIdx.x; k < MR * KP; k += blockDim.x) {
         const int r = k / KP, c = k - r * KP;
         buf[0][r * LDA + c] = (r0 + r < N && c < K) ? obs[(size_t)(r0 + r) * K + c] : 0.f;
@@ -168,8 +169,9 @@ __global__ __launch_bounds__(256) void actor_mlp_sample_kernel(int N, const floa
 
 }  // namespace
 
-extern "C" int bg_actor_sample_mlp(int32_t N, const float* obs, int32_t n_layers, const bg_mlp_layer_desc* layers, const float* logstd, uint64_t seed,
-                                   uint64_t counter, float* mu, float* actions, void* stream) {
+// scan: the height-scan values behind the 47 H observations of a row (bg_env_cfg.actor_heights), 0 without them
+static int sample_mlp(int32_t N, const float* obs, int32_t n_layers, const bg_mlp_layer_desc* layers, int32_t scan, const float* logstd, uint64_t seed,
+                      uint64_t counter, float* mu, float* actions, void* stream) {
     if (N <= 0 || !obs || !layers || !logstd || !actions) return bg_set_error(-1, "bg_actor_sample_mlp: bad argument");
     if (n_layers < 3 || n_layers > MAX_LAYERS) return bg_set_error(-4, "bg_actor_sample_mlp: 2 to 4 hidden layers (n_layers 3 to 5)");
     ActorNet net{};
@@ -179,8 +181,10 @@ extern "C" int bg_actor_sample_mlp(int32_t N, const float* obs, int32_t n_layers
         const bg_mlp_layer_desc& d = layers[l];
         if (!d.W || !d.b) return bg_set_error(-1, "bg_actor_sample_mlp: bad argument (layer weights)");
         const bool last = l + 1 == n_layers;
-        if (l == 0 ? (d.in < BG_NUM_OBS || d.in > BG_NUM_OBS * BG_MAX_FRAME_STACK || d.in % BG_NUM_OBS != 0) : d.in != layers[l - 1].out)
-            return bg_set_error(-4, "bg_actor_sample_mlp: layer widths do not chain (first layer: 47 H inputs, H = 1 .. 10 observation frames)");
+        if (l == 0 ? (d.in - scan < BG_NUM_OBS || d.in - scan > BG_NUM_OBS * BG_MAX_FRAME_STACK || (d.in - scan) % BG_NUM_OBS != 0 || d.in > BG_ACTOR_MAX_INPUT)
+                   : d.in != layers[l - 1].out)
+            return bg_set_error(-4, "bg_actor_sample_mlp: layer widths do not chain (first layer: 47 H inputs, H = 1 .. 10 observation frames, and the "
+                                    "height scan's points behind them, BG_ACTOR_MAX_INPUT at most)");
         if (last ? d.out != BG_NUM_DOFS : (d.out % 128 != 0 || d.out < 128 || d.out > 512))
             return bg_set_error(-4, "bg_actor_sample_mlp: unsupported widths (hidden: multiples of 128 up to 512; output: 12)");
         if (l > 0 && ((uintptr_t)d.W & 15)) return bg_set_error(-1, "bg_actor_sample_mlp: weight matrices after the first must be 16-byte aligned");
@@ -194,4 +198,15 @@ extern "C" int bg_actor_sample_mlp(int32_t N, const float* obs, int32_t n_layers
     else hipLaunchKernelGGL(actor_mlp_sample_kernel<512>, grid, block, 0, st, N, obs, net, logstd, seed, (uint32_t)counter, mu, actions);
     HIP_OK(hipGetLastError());
     return 0;
+}
+
+extern "C" int bg_actor_sample_mlp(int32_t N, const float* obs, int32_t n_layers, const bg_mlp_layer_desc* layers, const float* logstd, uint64_t seed,
+                                   uint64_t counter, float* mu, float* actions, void* stream) {
+    return sample_mlp(N, obs, n_layers, layers, 0, logstd, seed, counter, mu, actions, stream);
+}
+
+extern "C" int bg_actor_sample_mlp_scan(int32_t N, const float* obs, int32_t n_layers, const bg_mlp_layer_desc* layers, int32_t scan_points,
+                                        const float* logstd, uint64_t seed, uint64_t counter, float* mu, float* actions, void* stream) {
+    if (scan_points < 0 || scan_points > BG_MAX_HEIGHT_SCAN_POINTS) return bg_set_error(-1, "bg_actor_sample_mlp_scan: bad argument (scan_points)");
+    return sample_mlp(N, obs, n_layers, layers, scan_points, logstd, seed, counter, mu, actions, stream);
 }

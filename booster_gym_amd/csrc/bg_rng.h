@@ -39,6 +39,13 @@ BG_HD Rand4 rand4(uint64_t seed, uint32_t env, uint32_t step, uint32_t stream) {
     return r;
 }
 
+// the 4 uniforms of rand4 alone (the same bits), for a caller that has no use for the normals' logarithms and sines
+BG_HD void rand4_uniform(uint64_t seed, uint32_t env, uint32_t step, uint32_t stream, float u[4]) {
+    uint32_t o[4];
+    philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), env, step, stream, 0u, o);
+    for (int i = 0; i < 4; i++) u[i] = u32_to_unit(o[i]);
+}
+
 // RNG stream ids (third counter word).  Mirrored in oracle/task_ref.py.
 enum {
     RS_OBS0 = 0,      // gravity xyz, ang_vel x
@@ -58,7 +65,10 @@ enum {
     RS_CURR = 26,     // curriculum: grid cell, cmd x / y / yaw jitter
     RS_TLEVEL = 27,   // terrain curriculum: the level of an env that passed the top one
     RS_PERM = 28,     // mini-batch shuffle: the Feistel round functions of bg_perm.h (counter words: half, round | mini-epoch << 8, this, update)
-    RS_ACTOR = 32     // + k : action noise (bg_actor_sample)
+    RS_ACTOR = 32,    // + k : action noise (bg_actor_sample)
+    // (the env-step kernels and resample_apply_kernel add 64 to their ids at reset-all: 64 .. 64 + RS_TLEVEL are in use as well)
+    RS_SCAN = 128,       // + (p >> 2), p < 1024 : noise of the actor's height scan, point p at entry p & 3 (bg_obs_assemble): 128 .. 383
+    RS_SCAN_RESET = 384  // + (p >> 2) : the same at reset-all, which shares its step counter with the step that follows it: 384 .. 639
 };
 
 }  // namespace bg

@@ -43,7 +43,7 @@ struct bg_env {
     int curr_cells = 0;
     int32_t* tcur = nullptr;  // terrain curriculum: [n] levels, [n] columns, [1] level sum (cfg.terrain_curriculum only)
     float* scan_xy = nullptr; // height scan: [P][2] points in the robot's yaw frame (cfg.height_scan_points > 0 only)
-    float* hist = nullptr;    // observation history: ring [H][n][47] of the last H single observations (cfg.frame_stack = H > 1 only)
+    float* hist = nullptr;    // observation history: ring [H][n][47] of the last H single observations (cfg.frame_stack = H > 1, or cfg.actor_heights at any H)
     int hist_head = 0;        // ... the plane of the newest one: the env-step kernels of a launch sequence write their observations there
     ModelDev* model_dev = nullptr;
     PairModel* pair_dev = nullptr;  // the leg constants with the two legs side by side (packed ABA kernel)
@@ -211,6 +211,80 @@ __global__ __launch_bounds__(STACK_BLOCK) void bg_obs_stack(int n, int H, int he
     if (k + 1u == (unsigned)H || !(all_reset || done[e])) v = *src;
     else *src = 0.f;
     dst[t] = v;
+}
+
+// ------------------------------------------------------------------ the actor's row with the terrain height scan (cfg.actor_heights)
+// legged_gym's perceptive policy: the row [47 H + P] of an env is its H single observations (bg_obs_stack's layout and reset rule, H = 1 included)
+// and then, once, the newest height scan with noise; the critic's columns [14, 14 + P) get the same scan without it.  One launch in place of
+// bg_height_scan + bg_obs_stack: a block owns ASM_ENVS envs, whose rows are contiguous in the destination.  Before the barrier ASM_ENVS threads read
+// each env's base pose (seven state fields, once per env) and leave position, sin / cos of the yaw and the reset flag in LDS, and the block draws
+// the noise: one thread per (env, group of 4 points) runs the Philox of rand4(seed, env, step, base + group) once and leaves S n_p of its 4 points
+// in LDS (the normals' logarithms and sines only for a gaussian spec).  After it, one thread per destination element, consecutive lanes on
+// consecutive addresses over the block's rows, so the destination leaves in whole lines.  A frame element is copied from the ring as in
+// bg_obs_stack (a thread writes only the ring element it alone reads); a scan element computes its ground height once, stores v S to the
+// privileged row and v S + S n_p to the actor's.  Dynamic LDS: ASM_ENVS x P floats with a noise spec, none without.
+constexpr int ASM_BLOCK = 256, ASM_ENVS = 4;
+template <bool H16>
+__global__ __launch_bounds__(ASM_BLOCK) void bg_obs_assemble(EnvDev E, const float2* __restrict__ pts, int P, int H, int head, int all_reset, uint32_t step,
+                                                             uint32_t stream0, float* ring, const uint8_t* __restrict__ done, float* __restrict__ dst,
+                                                             float* __restrict__ priv, int stride) {
+    __shared__ float s_pose[ASM_ENVS][6];  // base x, y, z, sin yaw, cos yaw, reset in this step
+    extern __shared__ float s_noise[];     // [ASM_ENVS][P]: S n_p
+    const int n = E.n, e0 = blockIdx.x * ASM_ENVS, rows = min(ASM_ENVS, n - e0);
+    const float S = E.cfg.height_scan_scale;
+    const bg_rand spec = E.cfg.noise_height_measurements;
+    if ((int)threadIdx.x < rows) {
+        const int e = e0 + (int)threadIdx.x;
+#define SFLD(off) field_ref<H16>(E.f, E.h, (off), n, e)
+        const float q[4] = {SFLD(F_ROOT + 3), SFLD(F_ROOT + 4), SFLD(F_ROOT + 5), SFLD(F_ROOT + 6)};
+        float* sp = s_pose[threadIdx.x];
+        sp[0] = SFLD(F_ROOT + 0); sp[1] = SFLD(F_ROOT + 1); sp[2] = SFLD(F_ROOT + 2);
+#undef SFLD
+        bg_sincos(quat_yaw(q), &sp[3], &sp[4]);
+        sp[5] = (all_reset || done[e]) ? 1.f : 0.f;
+    }
+    if (spec.mode != 0) {
+        const int G = (P + 3) >> 2;
+        for (int t = threadIdx.x; t < rows * G; t += ASM_BLOCK) {
+            const int el = t / G, g = t - el * G;
+            float u[4], nr[4] = {0.f, 0.f, 0.f, 0.f};
+            if (spec.mode <= 2) {
+                const Rand4 r = rand4(E.cfg.seed, (uint32_t)(e0 + el), step, stream0 + (uint32_t)g);
+#pragma unroll
+                for (int i = 0; i < 4; i++) { u[i] = r.u[i]; nr[i] = r.n[i]; }
+            } else {
+                rand4_uniform(E.cfg.seed, (uint32_t)(e0 + el), step, stream0 + (uint32_t)g, u);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                if (4 * g + i < P) s_noise[el * P + 4 * g + i] = S * apply_rand(0.f, spec, u[i], nr[i]);
+        }
+    }
+    __syncthreads();
+    const unsigned F = (unsigned)(BG_NUM_OBS * H), W = F + (unsigned)P;  // (n W < 2^31: bg_env_create)
+    for (unsigned t = threadIdx.x; t < (unsigned)rows * W; t += ASM_BLOCK) {
+        const unsigned el = t / W, col = t - el * W, e = (unsigned)e0 + el;
+        const float* sp = s_pose[el];
+        float v;
+        if (col < F) {
+            const unsigned k = col / BG_NUM_OBS, c = col - k * BG_NUM_OBS;
+            unsigned slot = (unsigned)head + 1u + k;  // frame k = the observation of H - 1 - k steps ago
+            if (slot >= (unsigned)H) slot -= (unsigned)H;
+            float* src = ring + ((size_t)slot * n + e) * BG_NUM_OBS + c;
+            v = 0.f;
+            if (k + 1u == (unsigned)H || sp[5] == 0.f) v = *src;
+            else *src = 0.f;
+        } else {
+            const unsigned p = col - F;
+            const float2 pt = pts[p];
+            const float s = sp[3], c = sp[4];
+            const float h = terrain_height(E.terrain, sp[0] + c * pt.x - s * pt.y, sp[1] + s * pt.x + c * pt.y);
+            const float clean = fminf(fmaxf(sp[2] - h - E.cfg.base_height_target, -1.f), 1.f) * S;
+            priv[(size_t)e * stride + BG_NUM_PRIV + p] = clean;
+            v = spec.mode != 0 ? clean + s_noise[el * (unsigned)P + p] : clean;
+        }
+        dst[(size_t)e0 * W + t] = v;
+    }
 }
 
 // ------------------------------------------------------------------ reference-exact command resampling (cfg.exact_still_count / same_step_curriculum)
@@ -770,8 +844,9 @@ static int env_create_fill(bg_env* e, const bg_env_cfg* cfg, const bg_model* mod
         HIP_OK(hipMalloc(&e->scan_xy, sizeof(float) * 2 * cfg->height_scan_points));
         HIP_OK(hipMemcpy(e->scan_xy, cfg->height_scan_xy, sizeof(float) * 2 * cfg->height_scan_points, hipMemcpyHostToDevice));
     }
-    if (cfg->frame_stack > 1) {  // the ring of single observations, all zeros: an env that has never been reset has an empty history
-        const size_t hb = sizeof(float) * (size_t)cfg->frame_stack * n * BG_NUM_OBS;
+    if (cfg->actor_heights && cfg->frame_stack == 0) e->cfg.frame_stack = 1;  // (a ring of one plane; without the key the field stays as passed)
+    if (cfg->frame_stack > 1 || cfg->actor_heights) {  // the ring of single observations, all zeros: an env that has never been reset has an empty history
+        const size_t hb = sizeof(float) * (size_t)e->cfg.frame_stack * n * BG_NUM_OBS;
         HIP_OK(hipMalloc(&e->hist, hb));
         HIP_OK(hipMemset(e->hist, 0, hb));
     }
@@ -819,6 +894,8 @@ extern "C" int bg_env_create(const bg_env_cfg* cfg, const bg_model* model, bg_en
         return fail(-1, "bg_env_create: the height scan needs a height field and 1 .. BG_MAX_HEIGHT_SCAN_POINTS points");
     if (cfg->frame_stack < 0 || cfg->frame_stack > BG_MAX_FRAME_STACK || (int64_t)cfg->num_envs * BG_NUM_OBS * cfg->frame_stack >= (int64_t)1 << 31)
         return fail(-1, "bg_env_create: frame_stack must be 1 .. BG_MAX_FRAME_STACK (0 = 1: no history) with num_envs x 47 x frame_stack below 2^31");
+    if (cfg->actor_heights && (cfg->height_scan_points <= 0 || (int64_t)cfg->num_envs * (BG_NUM_OBS * (cfg->frame_stack > 1 ? cfg->frame_stack : 1) + cfg->height_scan_points) >= (int64_t)1 << 31))
+        return fail(-1, "bg_env_create: actor_heights needs the height scan's points (height_scan_points > 0) with num_envs x (47 x frame_stack + points) below 2^31");
     int ndev = 0;
     hipError_t de = hipGetDeviceCount(&ndev);
     if (de != hipSuccess || ndev == 0) return fail(-3, "bg_env_create: no HIP device available (this library has no CPU path)");
@@ -886,7 +963,7 @@ extern "C" int bg_env_bind_outputs(bg_env* e, float* obs, float* priv, float* re
 static int launch_step(bg_env* e, const float* actions, int mode, const StepOut& dst, void* stream) {
     if (!dst.obs || !dst.priv || !dst.rew || !dst.done || !dst.tout) return fail(-1, "bg_env_step: outputs are not bound");
     StepOut out = dst;
-    if (e->hist) {  // observation history: this sequence's 47-wide observation rows go to the next plane of the ring, bg_obs_stack writes dst.obs
+    if (e->hist) {  // observation history: this sequence's 47-wide observation rows go to the next plane of the ring, bg_obs_stack / bg_obs_assemble writes dst.obs
         e->hist_head = (e->hist_head + 1) % e->cfg.frame_stack;
         out.obs = e->hist + (size_t)e->hist_head * e->n * BG_NUM_OBS;
     }
@@ -923,13 +1000,20 @@ static int launch_step(bg_env* e, const float* actions, int mode, const StepOut&
         hipLaunchKernelGGL(resample_offsets_kernel, dim3(1), dim3(RS_BLOCK), 0, st, e->rs_counts, nb);
         hipLaunchKernelGGL(resample_apply_kernel, dim3(nb), dim3(RS_BLOCK), 0, st, env_dev(e), (const int*)e->rs_counts, nb, cnt, mode, out.obs);
     }
-    if (e->scan_xy) {  // the critic's height scan from the state this launch sequence has just stored (bg_height_scan)
+    if (e->cfg.actor_heights) {  // last, in place of the two launches below: the actor's row [47 H + P] and the critic's clean scan (bg_obs_assemble)
+        const int P = e->cfg.height_scan_points, H = e->cfg.frame_stack;
+        dim3 gs((unsigned)((e->n + ASM_ENVS - 1) / ASM_ENVS));
+        const uint32_t base = mode ? (uint32_t)bg::RS_SCAN_RESET : (uint32_t)bg::RS_SCAN;
+        const size_t lds = e->cfg.noise_height_measurements.mode != 0 ? sizeof(float) * ASM_ENVS * P : 0;  // (at most 16 kB: P <= 1024)
+        if (e->h) hipLaunchKernelGGL(bg_obs_assemble<true>, gs, dim3(ASM_BLOCK), lds, st, env_dev(e), (const float2*)e->scan_xy, P, H, e->hist_head, mode, cnt, base, e->hist, (const uint8_t*)out.done, dst.obs, out.priv, out.priv_stride);
+        else hipLaunchKernelGGL(bg_obs_assemble<false>, gs, dim3(ASM_BLOCK), lds, st, env_dev(e), (const float2*)e->scan_xy, P, H, e->hist_head, mode, cnt, base, e->hist, (const uint8_t*)out.done, dst.obs, out.priv, out.priv_stride);
+    } else if (e->scan_xy) {  // the critic's height scan from the state this launch sequence has just stored (bg_height_scan)
         const int P = e->cfg.height_scan_points;
         dim3 gs((unsigned)(((int64_t)e->n * P + SCAN_BLOCK - 1) / SCAN_BLOCK));
         if (e->h) hipLaunchKernelGGL(bg_height_scan<true>, gs, dim3(SCAN_BLOCK), 0, st, env_dev(e), (const float2*)e->scan_xy, P, out.priv, out.priv_stride);
         else hipLaunchKernelGGL(bg_height_scan<false>, gs, dim3(SCAN_BLOCK), 0, st, env_dev(e), (const float2*)e->scan_xy, P, out.priv, out.priv_stride);
     }
-    if (e->hist) {  // last: every launch that writes the single observation (kernel B and resample_apply_kernel included) is in front of it
+    if (e->hist && !e->cfg.actor_heights) {  // last: every launch that writes the single observation (kernel B and resample_apply_kernel included) is in front of it
         const int H = e->cfg.frame_stack;
         dim3 gs((unsigned)(((int64_t)e->n * BG_NUM_OBS * H + STACK_BLOCK - 1) / STACK_BLOCK));
         hipLaunchKernelGGL(bg_obs_stack, gs, dim3(STACK_BLOCK), 0, st, e->n, H, e->hist_head, mode, e->hist, (const uint8_t*)out.done, dst.obs);

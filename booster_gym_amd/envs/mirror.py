@@ -45,13 +45,28 @@ def joint_mirror(dof_names, dof_axes):
     return np.array(src, dtype=np.int32), np.array(sign, dtype=np.float32)
 
 
-def mirror_maps(dof_names, dof_axes, default_dof_pos, num_obs, frame_stack=1):
+def scan_mirror(height_points):
+    """src of the height scan's mirror map (every sign is +1, a height does not change under y -> -y): src[p] = the point at (x_p, -y_p).
+    ValueError naming terrain.measured_points_y if the grid is not symmetric under y -> -y."""
+    pts = np.asarray(height_points, dtype=np.float64).reshape(-1, 2)
+    index = {(float(x), float(y)): p for p, (x, y) in enumerate(pts)}
+    src = [index.get((float(x), float(-y)), -1) for x, y in pts]
+    if min(src, default=0) < 0:
+        raise ValueError("algorithm.symmetry_loss with terrain.actor_heights needs a height scan that is its own mirror image: "
+                         "terrain.measured_points_y must be symmetric under negation (for every y also -y)")
+    return np.array(src, dtype=np.int32)
+
+
+def mirror_maps(dof_names, dof_axes, default_dof_pos, num_obs, frame_stack=1, height_points=None):
     """(obs_src, obs_sign, act_src, act_sign): the maps M_o of the observations and M_a of the actions.  ValueError if the model has no left /
     right pairing, the observation width is not T1's layout for these joints, or the default pose is not its own mirror image (dof_pos - default
     then would not mirror as a signed permutation).  frame_stack = H > 1 (env.frame_stack): num_obs is H single observations side by side and M_o
-    the single observation's map tiled over them, frame k's source indices offset by k times the single width."""
+    the single observation's map tiled over them, frame k's source indices offset by k times the single width.  height_points ([P][2], terrain.actor_heights)
+    : the row ends with the P values of the height scan, and M_o with their block: point (x_i, y_j) takes the value of (x_i, -y_j), sign +1."""
     act_src, act_sign = joint_mirror(dof_names, dof_axes)
     nd = len(act_src)
+    scan_src = scan_mirror(height_points) if height_points is not None and len(height_points) else np.zeros(0, dtype=np.int32)
+    num_obs = num_obs - len(scan_src)
     H, total = int(frame_stack), num_obs
     if H < 1 or num_obs != H * (OBS_JOINTS + 3 * nd):
         raise ValueError(f"symmetry loss: {num_obs} observations are not T1's layout for {nd} joints ({OBS_JOINTS + 3 * nd}"
@@ -70,6 +85,9 @@ def mirror_maps(dof_names, dof_axes, default_dof_pos, num_obs, frame_stack=1):
     if H > 1:
         obs_src = np.concatenate([obs_src + k * num_obs for k in range(H)]).astype(np.int32)
         obs_sign = np.tile(obs_sign, H)
+    if len(scan_src):
+        obs_src = np.concatenate([obs_src, total + scan_src]).astype(np.int32)
+        obs_sign = np.concatenate([obs_sign, np.ones(len(scan_src), dtype=np.float32)])
     return obs_src, obs_sign, act_src, act_sign
 
 

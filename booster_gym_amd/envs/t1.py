@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..utils.terrain import actor_heights_of
 from ..utils.urdf import load_model
 from ..utils.utils import rand_spec
 from .base_task import BaseTask
@@ -30,6 +31,7 @@ TERRAIN_LEVEL_STREAM = 0x7E44A1
 MAX_CRITIC_INPUT = 512
 
 
+MAX_ACTOR_INPUT = 480  # BG_ACTOR_MAX_INPUT: the widest first layer of the rollout's sampling kernel (bg_actor_sample_mlp)
 MAX_FRAME_STACK = 10  # env.frame_stack: 47 x 10 = 470 actor inputs, within the widest first layer of the kernels (512)
 
 
@@ -46,10 +48,30 @@ def frame_stack_of(cfg):
 
 def check_env_sizes(cfg, num_height_points):
     """ValueError unless env.num_observations / num_privileged_obs / num_actions are what this build computes: 47 H (H = env.frame_stack single
-    observations, 47 without the key), 14 (+ P with the terrain height scan's P points: legged_gym requires num_observations to match what the env
-    computes) and 12; and 47 H + 14 + P within MAX_CRITIC_INPUT."""
+    observations, 47 without the key; 47 H + P with terrain.actor_heights), 14 (+ P with the terrain height scan's P points: legged_gym requires
+    num_observations to match what the env computes) and 12; and the critic's input, observations + privileged observations, within MAX_CRITIC_INPUT."""
     env, P, H = cfg["env"], num_height_points, frame_stack_of(cfg)
     no, npv, na = env["num_observations"], env["num_privileged_obs"], env["num_actions"]
+    if actor_heights_of(cfg["terrain"]):
+        want = _lib.NUM_OBS * H + P
+        if no != want:
+            raise ValueError(f"env.num_observations = {no}, but terrain.actor_heights with env.frame_stack = {H} and {P} points computes "
+                             f"{_lib.NUM_OBS} x {H} + {P} = {want} observations: set env.num_observations to {want}")
+        if want > MAX_ACTOR_INPUT:
+            raise ValueError(f"terrain.actor_heights: the actor's input {_lib.NUM_OBS} x {H} (env.frame_stack) + {P} (terrain.measured_points_x x "
+                             f"terrain.measured_points_y) = {want} exceeds {MAX_ACTOR_INPUT} (the widest first layer of the rollout's sampling kernel): a "
+                             f"smaller env.frame_stack, or fewer points of the height scan")
+        if want + _lib.NUM_PRIV + P > MAX_CRITIC_INPUT:
+            raise ValueError(f"terrain.actor_heights: the critic's input {_lib.NUM_OBS} x {H} (env.frame_stack) + {P} + {_lib.NUM_PRIV} + {P} "
+                             f"(terrain.measured_points_x x terrain.measured_points_y, in the actor's row and in the privileged one) = "
+                             f"{want + _lib.NUM_PRIV + P} exceeds {MAX_CRITIC_INPUT} (the widest first layer of the kernels): a smaller env.frame_stack, "
+                             f"or fewer points of the height scan")
+        if npv != _lib.NUM_PRIV + P:
+            raise ValueError(f"env.num_privileged_obs = {npv}, but terrain.measure_heights with {P} points computes {_lib.NUM_PRIV} + {P} = "
+                             f"{_lib.NUM_PRIV + P} privileged observations: set env.num_privileged_obs to {_lib.NUM_PRIV + P}")
+        if na != _lib.NUM_DOFS:
+            raise ValueError("this build computes 12 actions (envs/T1.yaml env.num_actions)")
+        return
     if H > 1 and no != _lib.NUM_OBS * H:
         raise ValueError(f"env.num_observations = {no}, but env.frame_stack = {H} computes {_lib.NUM_OBS} x {H} = {_lib.NUM_OBS * H} observations: set "
                          f"env.num_observations to {_lib.NUM_OBS * H}")
@@ -206,6 +228,10 @@ class T1(BaseTask):
         # the critic's terrain height scan (terrain.measure_heights): P more privileged columns after the 14 (checked in __init__)
         P = self.num_height_points = len(self.terrain.height_points)
         self.height_points = torch.tensor(self.terrain.height_points, dtype=torch.float, device=self.device).reshape(P, 2)
+        # the actor's height scan (terrain.actor_heights): the row is [47 H single observations | P scan values], the newest scan only, with noise
+        self.actor_heights = self.terrain.actor_heights
+        self.num_scan_obs, self.scan_obs_offset = (P if self.actor_heights else 0), self.num_single_obs * self.frame_stack
+        self._wide_obs = self.frame_stack > 1 or self.actor_heights  # (step_to checks the destination's size then only: one attribute on the default path)
         self.dt = cfg["control"]["decimation"] * cfg["sim"]["dt"]
         N, dev = self.num_envs, self.device
         self.obs_buf = torch.zeros(N, self.num_obs, dtype=torch.float, device=dev)
@@ -318,6 +344,9 @@ class T1(BaseTask):
                 self._scan_xy = np.ascontiguousarray(self.terrain.height_points, dtype=np.float32)
                 c.height_scan_points, c.height_scan_xy = self.num_height_points, self._scan_xy.ctypes.data
                 c.height_scan_scale = float(nz.get("height_measurements", 5.0))
+                if self.actor_heights:  # (noise.height_measurements is read with the key on only)
+                    c.actor_heights = 1
+                    setr(c.noise_height_measurements, nc.get("height_measurements"))
         c.frame_stack = self.frame_stack
         sd = str(cfg["sim"].get("state_dtype", "fp32")).lower()
         if sd not in ("fp32", "float32", "fp16", "float16", "half"):
@@ -446,7 +475,7 @@ class T1(BaseTask):
                 raise RuntimeError("step_to needs contiguous CUDA output tensors")
         if privileged_obs.numel() < self.num_envs * self.num_privileged_obs:  # (rows of 14 + P with the height scan)
             raise RuntimeError(f"step_to needs privileged_obs of {self.num_envs} x {self.num_privileged_obs} floats")
-        if self.frame_stack > 1 and obs.numel() < self.num_envs * self.num_obs:  # (rows of 47 H with a frame stack)
+        if self._wide_obs and obs.numel() < self.num_envs * self.num_obs:  # (rows of 47 H with a frame stack, + P with the actor's scan)
             raise RuntimeError(f"step_to needs obs of {self.num_envs} x {self.num_obs} floats")
         _lib.check(self._lib.bg_env_step_to(self._env, _lib.ptr(a), _lib.ptr(obs), _lib.ptr(privileged_obs), _lib.ptr(rew), _lib.ptr(done),
                                             _lib.ptr(time_outs), _lib.current_stream_ptr()), "bg_env_step_to")
@@ -466,7 +495,8 @@ class T1(BaseTask):
         """(obs_src, obs_sign, act_src, act_sign): the left-right mirror maps of the observations and actions (envs/mirror.py), from the model's joint
         names and axes; ValueError if the model has no left / right pairing or its default pose is not mirror-invariant."""
         axes = [int(a) for a in self.model.joint_axis if int(a) != 0]  # (bodies depth-first: body j + 1 is moved by DoF j)
-        return mirror_maps(self.dof_names, axes, self.default_dof_pos[0].cpu().numpy(), self.num_obs, self.frame_stack)
+        return mirror_maps(self.dof_names, axes, self.default_dof_pos[0].cpu().numpy(), self.num_obs, self.frame_stack,
+                           self.terrain.height_points if self.actor_heights else None)
 
     def get_field(self, name):
         comps, is_int = C.c_int32(), C.c_int32()

@@ -636,10 +636,11 @@ class ActorCritic(torch.nn.Module):
         return self.critic(torch.cat((obs, privileged_obs), dim=-1)).squeeze(-1)
 
     # ---- fused rollout inference (reference runner.py:109-111: dist = model.act(obs); act = dist.sample())
-    def sample_actions(self, obs, actions_out, seed, counter, mu_out=None):
+    def sample_actions(self, obs, actions_out, seed, counter, mu_out=None, scan=0):
         """One launch: the actor's mean and a Gaussian sample around it.  The reference's widths on 47 inputs run bg_actor_sample (its widths built
         into the kernel), every other architecture, and every actor on a frame stack (47 H inputs, env.frame_stack), bg_actor_sample_mlp (widths from
-        descriptors, the weights read from the parameters themselves); both draw the same noise for the same seed and counter."""
+        descriptors, the weights read from the parameters themselves); both draw the same noise for the same seed and counter.  scan = P
+        (terrain.actor_heights): the rows end with the height scan's P values behind the 47 H observations (bg_actor_sample_mlp_scan, the same kernel)."""
         if not obs.is_cuda:
             raise RuntimeError("sample_actions runs the fused HIP actor kernel and needs CUDA tensors")
         a = self.actor
@@ -659,6 +660,11 @@ class ActorCritic(torch.nn.Module):
             self._sample_layers = (_lib.MlpLayerDesc * len(lin))(*[_lib.MlpLayerDesc(l.weight.data_ptr(), l.bias.data_ptr(), l.in_features, l.out_features)
                                                                    for l in lin])
             self._sample_key = key
+        if scan:
+            _lib.check(_lib.load().bg_actor_sample_mlp_scan(obs.shape[0], _lib.ptr(obs), len(lin), self._sample_layers, int(scan), _lib.ptr(self.logstd), int(seed),
+                                                            int(counter), _lib.ptr(mu_out), _lib.ptr(actions_out), _lib.current_stream_ptr()),
+                       "bg_actor_sample_mlp_scan")
+            return actions_out
         _lib.check(_lib.load().bg_actor_sample_mlp(obs.shape[0], _lib.ptr(obs), len(lin), self._sample_layers, _lib.ptr(self.logstd), int(seed), int(counter),
                                                    _lib.ptr(mu_out), _lib.ptr(actions_out), _lib.current_stream_ptr()), "bg_actor_sample_mlp")
         return actions_out

@@ -366,7 +366,7 @@ class Runner:
         self._pad_critic = pad_input(no + npv) if MLPTrainer.FUSED else None
         if self._pad_actor and self._pad_actor > 256 and (int((self.cfg.get("parallel", {}) or {}).get("gemm_split", 0) or 0) or MLPTrainer.SPLIT):
             raise ValueError(f"parallel.gemm_split / BG_GEMM_SPLIT runs split-bf16 layer kernels that take layer inputs of 64, 128 or 256 columns only; the "
-                             f"actor's input of {no} observations pads to {self._pad_actor} (env.frame_stack 5 or less, or gemm_split 0)")
+                             f"actor's input of {no} observations pads to {self._pad_actor} (env.frame_stack 5 or less, without terrain.actor_heights or with fewer points of its scan, or gemm_split 0)")
         if self._pad_critic and self._pad_critic > 256 and (int((self.cfg.get("parallel", {}) or {}).get("gemm_split", 0) or 0) or MLPTrainer.SPLIT):
             raise ValueError(f"parallel.gemm_split / BG_GEMM_SPLIT runs split-bf16 layer kernels that take layer inputs of 64, 128 or 256 columns only; the "
                              f"critic's input {no} + {npv} pads to {self._pad_critic} (fewer terrain.measured_points_x / _y points, or gemm_split 0)")
@@ -505,6 +505,11 @@ class Runner:
         print("Loading model from {}".format(ck))
         model_dict = torch.load(ck, map_location=self.device, weights_only=True)
         ck_ain, a_in = int(model_dict["model"]["actor.0.weight"].shape[1]), self.model.actor[0].in_features
+        scan_ck, scan_cfg = (int(model_dict["height_points"].shape[0]) if "height_points" in model_dict else 0), getattr(self.env, "num_scan_obs", 0)
+        if ck_ain != a_in and ck_ain - scan_ck == a_in - scan_cfg:  # (the widths differ by the height scan in the actor's row)
+            raise ValueError(f"checkpoint {ck} has an actor of {ck_ain} inputs, {scan_ck} of them the terrain height scan, the config's actor takes {a_in} "
+                             f"with {scan_cfg}: terrain.actor_heights (and terrain.measured_points_x / measured_points_y, env.num_observations) must be "
+                             "as in the run that saved the checkpoint")
         if ck_ain != a_in:  # (the actor's input: env.frame_stack single observations of 47)
             raise ValueError(f"checkpoint {ck} has an actor of {ck_ain} inputs, the config's actor takes {a_in} (env.num_observations = "
                              f"{self.env.num_single_obs} x env.frame_stack): env.frame_stack must be as in the run that saved the checkpoint "
@@ -556,6 +561,8 @@ class Runner:
             d["terrain_levels"] = self.env.terrain_levels
         if self.obs_norm is not None:
             d["obs_normalizer"] = self.obs_norm.state_dict()
+        if getattr(self.env, "num_scan_obs", 0):  # terrain.actor_heights: the grid of the scan at the end of the actor's row, for whoever deploys the actor
+            d["height_points"] = self.env.height_points.clone()
         return d
 
     # ------------------------------------------------------------------ one PPO iteration
@@ -647,15 +654,16 @@ class Runner:
         main = torch.cuda.current_stream()
         g, start = self._rollout_group, 0
         norm = self.obs_norm
+        scan = getattr(self.env, "num_scan_obs", 0)  # terrain.actor_heights: the rows end with the height scan
         with torch.no_grad():
             for n in range(T):
                 if plan.ahead and n + 1 - start >= g:
                     self._forward_rows(start, n, main)  # rows of steps start .. n: on the side stream, beside this step's launches
                     start = n + 1
                 if norm is None:
-                    self.model.sample_actions(obses[n], buf["actions"][n], seed, self._act_counter)
+                    self.model.sample_actions(obses[n], buf["actions"][n], seed, self._act_counter, scan=scan)
                 else:  # the buffer keeps the raw rows; the actor samples from their normalised copy (one more launch per step: bg_obs_normalize)
-                    self.model.sample_actions(norm.normalize_into(obses[n], self._obs_normed), buf["actions"][n], seed, self._act_counter)
+                    self.model.sample_actions(norm.normalize_into(obses[n], self._obs_normed), buf["actions"][n], seed, self._act_counter, scan=scan)
                 self._act_counter += 1
                 self.env.step_to(buf["actions"][n], obses[n + 1], priv[n + 1], buf["rewards"][n], buf["dones"][n], buf["time_outs"][n])
             if plan.ahead:

@@ -98,6 +98,16 @@ def height_scan_points(terrain_cfg):
     return True, np.stack([gx.reshape(-1), gy.reshape(-1)], axis=1).astype(np.float32)
 
 
+def actor_heights_of(terrain_cfg):
+    """terrain.actor_heights (an addition of this build, legged_gym's perceptive policy; absent = false): the actor's input ends with the height scan's
+    P values.  It is the scan the critic already gets, so ValueError unless terrain.measure_heights is on as well."""
+    on = bool(terrain_cfg.get("actor_heights", False))
+    if on and not bool(terrain_cfg.get("measure_heights", False)):
+        raise ValueError("terrain.actor_heights: true needs terrain.measure_heights: true (the actor gets the scan of terrain.measured_points_x x "
+                         "terrain.measured_points_y that the critic's privileged observation already holds)")
+    return on
+
+
 class Terrain:
     def __init__(self, device, terrain_cfg, seed=0):
         self.terrain_cfg = terrain_cfg
@@ -105,6 +115,7 @@ class Terrain:
         self.type = terrain_cfg["type"]
         self.curriculum, self.num_levels, self.max_init_level = terrain_curriculum(terrain_cfg)
         self.measure_heights, self.height_points = height_scan_points(terrain_cfg)
+        self.actor_heights = actor_heights_of(terrain_cfg)
         if self.type == "plane":
             self.height_field_raw = None
         elif self.type == "trimesh":

@@ -1,6 +1,6 @@
 """python export_model.py --task=T1 [--checkpoint path|-1]: TorchScript export of the actor (reference export_model.py:8-30) so that
 the reference's deployment code (deploy/utils/policy.py:9) can load what this framework trains.  The actor's widths are read from the checkpoint's tensors (any supported architecture, with or without the terrain height
-scan or a frame stack, exports without editing the YAML); the TorchScript module is still a plain Sequential.  A checkpoint trained with
+scan, a frame stack or the actor's own height scan, exports without editing the YAML); the TorchScript module is still a plain Sequential.  A checkpoint trained with
 algorithm.empirical_normalization carries its observation statistics: they are folded into the actor's first layer, so the exported module takes raw observations."""
 import argparse
 import glob
@@ -27,6 +27,16 @@ if __name__ == "__main__":
     # terrain.measure_heights); only the actor is exported
     num_obs = int(sd["actor.0.weight"].shape[1])
     num_priv = int(sd["critic.0.weight"].shape[1]) - num_obs
+    if num_obs % 47:
+        # terrain.actor_heights: the actor's row ends with the height scan, whose grid the checkpoint carries
+        pts = ckpt.get("height_points")
+        P = int(pts.shape[0]) if pts is not None else 0
+        if P == 0 or (num_obs - P) % 47 or num_obs <= P:
+            raise ValueError(f"the checkpoint's actor takes {num_obs} inputs: neither 47 x env.frame_stack nor that plus the points of its "
+                             f"\"height_points\" entry ({P}; terrain.actor_heights)")
+        xs, ys = sorted(set(pts[:, 0].tolist())), sorted(set(pts[:, 1].tolist()))
+        print("Actor input of {} columns: 47 x {} observations, then {} heights, grid x {:.3g} .. {:.3g} ({}) by y {:.3g} .. {:.3g} ({}), point p = i * {} + j "
+              "at (x_i, y_j) in the robot's yaw frame".format(num_obs, (num_obs - P) // 47, P, xs[0], xs[-1], len(xs), ys[0], ys[-1], len(ys), len(ys)))
     model = ActorCritic(cfg["env"]["num_actions"], num_obs, num_priv, actor_hidden=hidden_of(sd, "actor"),
                         critic_hidden=hidden_of(sd, "critic"))
     model.load_state_dict(sd)

@@ -27,6 +27,7 @@ extern "C" {
 #define BG_NUM_REWARD_TERMS 26
 #define BG_MAX_BODY_SPHERES 16
 #define BG_MAX_HEIGHT_SCAN_POINTS 1024 /* bg_env_cfg.height_scan_points */
+#define BG_ACTOR_MAX_INPUT 480 /* bg_actor_sample_mlp: the widest first layer (47 H observations + P height-scan values), ten 48-column k-chunks */
 #define BG_MAX_FRAME_STACK 10 /* bg_env_cfg.frame_stack: 47 x 10 = 470 observation columns, within the 512 of the widest first layer */
 
 typedef struct bg_model bg_model;
@@ -157,6 +158,17 @@ typedef struct {
      * reset-all writes the row.  An env that was reset in the step (every env, for bg_env_reset) gets H - 1 zero frames and its new observation.
      * Negative or above BG_MAX_FRAME_STACK: bg_env_create fails. */
     int32_t frame_stack;
+    /* Terrain height scan in the actor's input (T1.yaml terrain.actor_heights; an addition of this build, legged_gym's perceptive policy).  0 = off:
+     * nothing below is read and every launch is as without the field.  1 (height_scan_points = P > 0 only, else bg_env_create fails): the observation
+     * output (bound or passed to bg_env_step_to) is [N][47 H + P]: the H single observations as with frame_stack (H = 1 included), then once, not
+     * stacked, the newest scan with noise:
+     *   clip(base z - h_p - base_height_target, -1, 1) * height_scan_scale + height_scan_scale * n_p,
+     * n_p [m] = apply_rand(0, noise_height_measurements, u, n) on entry p & 3 of Philox(seed, env, step count, RS_SCAN + (p >> 2)) (RS_SCAN_RESET at
+     * bg_env_reset; csrc/bg_rng.h).  The privileged columns 14 .. 14 + P keep the clean scan, bit for bit the first term.  One launch
+     * (bg_obs_assemble), the last of every env step and reset-all, writes both and takes the place of bg_height_scan and bg_obs_stack; the env keeps
+     * its ring of H observation planes also at H = 1.  num_envs x (47 H + P) must stay below 2^31. */
+    int32_t actor_heights;
+    bg_rand noise_height_measurements; /* noise.height_measurements [m]; read with actor_heights only */
 } bg_env_cfg;
 
 /* ---- model (replaces gym.load_asset and the asset queries, t1.py:54-108) */
@@ -194,7 +206,7 @@ int bg_env_set_heightfield(bg_env* env, const int16_t* hf_host, int32_t rows, in
 int bg_env_set_params(bg_env* env, const float* kp, const float* kd, const float* friction, const float* mass_scale, const float* com_offset,
                       const float* foot_material, const float* base_mass_scaled, const float* env_origins);
 /* outputs of reset/step, device pointers owned by the caller (torch tensors): obs [N][47 H] (H = cfg.frame_stack, [N][47] without a
- * history), privileged [N][14 + P] (P = cfg.height_scan_points, 0 without the height scan: [N][14]), rew [N], done uint8 [N], time_outs uint8 [N], rew_terms [26][N] (rows of dropped terms stay 0) */
+ * history; [N][47 H + P] with cfg.actor_heights), privileged [N][14 + P] (P = cfg.height_scan_points, 0 without the height scan: [N][14]), rew [N], done uint8 [N], time_outs uint8 [N], rew_terms [26][N] (rows of dropped terms stay 0) */
 int bg_env_bind_outputs(bg_env* env, float* obs, float* privileged_obs, float* rew, uint8_t* done, uint8_t* time_outs, float* rew_terms);
 /* T1.reset(): t1.py:294-299 */
 int bg_env_reset(bg_env* env, void* stream);
@@ -300,6 +312,11 @@ typedef struct bg_mlp_layer_desc {
  * mu [N][12] may be NULL. */
 int bg_actor_sample_mlp(int32_t N, const float* obs, int32_t n_layers, const bg_mlp_layer_desc* layers, const float* logstd, uint64_t seed,
                         uint64_t counter, float* mu, float* actions, void* stream);
+/* The same launch on the rows of a perceptive actor (bg_env_cfg.actor_heights): the first layer's `in` is 47 H + scan_points, the height scan behind
+ * the H observation frames, BG_ACTOR_MAX_INPUT at most (the first layer's k-chunks of 48 columns run over the frames' boundaries; columns past
+ * `in` read as zeros).  scan_points = 0 is bg_actor_sample_mlp. */
+int bg_actor_sample_mlp_scan(int32_t N, const float* obs, int32_t n_layers, const bg_mlp_layer_desc* layers, int32_t scan_points, const float* logstd,
+                             uint64_t seed, uint64_t counter, float* mu, float* actions, void* stream);
 /* Fused global-norm clip + Adam over one flat parameter buffer (runner.py:162-165); lr is read from device memory
  * so the KL-adaptive schedule (runner.py:174-180) needs no host sync.  gnorm_scratch [1] device float64. */
 int bg_adam_step(int32_t n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const float* lr_device, int32_t step,

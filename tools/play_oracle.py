@@ -56,12 +56,36 @@ class FrameStack:
         return self.row
 
 
-def actor_frames(layers, width=47):
-    """Frames H of an actor whose first layer takes H * width inputs (ValueError otherwise)."""
-    k = int(layers[0][0].shape[1])
+def load_height_points(path):
+    """[P][2] grid of the actor's height scan (terrain.actor_heights: the checkpoint's "height_points"), or None."""
+    if path.endswith(".npz"):
+        W = np.load(path)
+        return W["height_points"] if "height_points" in W.files else None
+    import torch
+
+    pts = torch.load(path, map_location="cpu", weights_only=True).get("height_points")
+    return None if pts is None else pts.numpy()
+
+
+def actor_frames(layers, width=47, scan=0):
+    """Frames H of an actor whose first layer takes H * width inputs and then `scan` height-scan values (ValueError otherwise)."""
+    k = int(layers[0][0].shape[1]) - int(scan)
     if k < width or k % width:
-        raise ValueError(f"the actor takes {k} inputs, not a multiple of the {width} single observations (env.frame_stack)")
+        raise ValueError(f"the actor takes {k + int(scan)} inputs, not a multiple of the {width} single observations (env.frame_stack)"
+                         + (f" plus the {scan} points of the height scan (terrain.actor_heights)" if scan else ""))
     return k // width
+
+
+def height_scan(root, height_points, cfg, terrain_height=None):
+    """The noiseless actor scan the env computes (terrain.actor_heights): clip(base z - h_p - base_height_target, -1, 1) * S at the grid points turned
+    by the base yaw.  terrain_height(x, y) -> h; None = the oracle's plane, h = 0."""
+    pts = np.asarray(height_points, dtype=np.float64).reshape(-1, 2)
+    x, y, z, w = root[3:7]
+    yaw = np.arctan2(2.0 * (w * z + x * y), w * w + x * x - y * y - z * z)
+    c, s = np.cos(yaw), np.sin(yaw)
+    wx, wy = root[0] + c * pts[:, 0] - s * pts[:, 1], root[1] + s * pts[:, 0] + c * pts[:, 1]
+    h = np.zeros(len(pts)) if terrain_height is None else np.array([terrain_height(a, b) for a, b in zip(wx, wy)])
+    return np.clip(root[2] - h - cfg["rewards"]["base_height_target"], -1.0, 1.0) * cfg["normalization"].get("height_measurements", 5.0)
 
 
 def gait_frequency(cmd, cfg_commands, max_lin=1.0, max_ang=1.0):
@@ -73,7 +97,7 @@ def gait_frequency(cmd, cfg_commands, max_lin=1.0, max_ang=1.0):
     return lo + min(1.0, mag / max(max_lin, max_ang)) * (hi - lo)
 
 
-def rollout(layers, cmd, seconds, cfg=None, dyn=None, model=None):
+def rollout(layers, cmd, seconds, cfg=None, dyn=None, model=None, height_points=None):
     from booster_gym_amd.utils.config import load_cfg
     from booster_gym_amd.utils.urdf import load_model
     from oracle import task_ref as tr
@@ -92,7 +116,8 @@ def rollout(layers, cmd, seconds, cfg=None, dyn=None, model=None):
     gf, gp = gait_frequency(cmd, cfg["commands"]), 0.0
     actions, targets = np.zeros(12), default.copy()
     dec, dt = cfg["control"]["decimation"], cfg["sim"]["dt"]
-    stack = FrameStack(actor_frames(layers))  # (H = 1: the single observation itself)
+    P = 0 if height_points is None else len(height_points)  # terrain.actor_heights: the row ends with the newest scan, not stacked
+    stack = FrameStack(actor_frames(layers, scan=P))  # (H = 1: the single observation itself)
     traj = []
     for it in range(int(round(seconds / dt))):
         if it % dec == 0:  # play_mujoco.py:733-748
@@ -103,6 +128,8 @@ def rollout(layers, cmd, seconds, cfg=None, dyn=None, model=None):
             o[9], o[10] = np.cos(2 * np.pi * gp) * (gf > 1e-8), np.sin(2 * np.pi * gp) * (gf > 1e-8)
             o[11:23], o[23:35], o[35:47] = (q - default) * nz["dof_pos"], qd * nz["dof_vel"], actions
             x = stack.push(o)
+            if P:
+                x = np.concatenate([x, height_scan(root, height_points, cfg)])
             for k, (w, b) in enumerate(layers):
                 x = w @ x + b
                 if k < 3:
@@ -121,6 +148,6 @@ if __name__ == "__main__":
     ap.add_argument("--cmd", type=float, nargs=3, default=[0.5, 0.0, 0.0])
     ap.add_argument("--seconds", type=float, default=8.0)
     a = ap.parse_args()
-    tr_ = rollout(load_actor(a.policy), a.cmd, a.seconds)
+    tr_ = rollout(load_actor(a.policy), a.cmd, a.seconds, height_points=load_height_points(a.policy))
     up = 1 - 2 * (tr_[-1, 3] ** 2 + tr_[-1, 4] ** 2)
     print(f"cmd {a.cmd}: final pos {np.round(tr_[-1, :3], 3)}, mean velocity {np.round((tr_[-1, :2] - tr_[0, :2]) / a.seconds, 3)}, min height {tr_[:, 2].min():.3f}, upright {up:.3f}")
