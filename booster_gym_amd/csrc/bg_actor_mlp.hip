@@ -18,7 +18,13 @@
 // LDS: 2 x 16 x 516 floats = 66 kB at MAXW = 512 (two workgroups per CU), 33 kB at MAXW = 256; 16 rows per workgroup: 256 workgroups at 4,096 rows.
 // The input tile [16][48 H] lives in the first activation tile, so 6 frames and more (288 columns and up) take the MAXW = 512 form.
 // The noise is bg_actor_sample's: the same bg::rand4(seed, row, counter, RS_ACTOR + g) draw per (row, group of 4 actions), the same expression.
+//
+// bg_distill_act (teacher-student distillation, utils/distill.py) runs TWO such networks on the same rows in one launch: the grid is split, workgroups
+// [0, nb) evaluate the teacher on all 47 H + P columns of their 16 rows and write its mean, workgroups [nb, 2 nb) the student on the first 47 H
+// columns and sample.  Both kernels are one body, actor_rows, so a half computes what the stand-alone kernel does on the same operands, bit for bit.
 #include <hip/hip_runtime.h>
+
+#include <string>
 
 #include "../../include/booster_gym_amd.h"
 #include "bg_rng.h"
@@ -132,16 +138,18 @@ __device__ __forceinline__ void layer(const float* __restrict__ W, const float* 
     }
 }
 
+// One workgroup's 16 rows [r0, r0 + 16) through one network: the body of both kernels below.  The rows are `stride` floats apart and the network reads
+// its own first net.in[0] columns of them.  act_out == nullptr: the mean alone goes to mu_out and no noise is drawn (bg_distill_act's teacher).
 template <int MAXW>
-__global__ __launch_bounds__(256) void actor_mlp_sample_kernel(int N, const float* __restrict__ obs, ActorNet net, const float* __restrict__ logstd,
-                                                               uint64_t seed, uint32_t counter, float* __restrict__ mu_out, float* __restrict__ act_out) {
+__device__ __forceinline__ void actor_rows(int N, int r0, const float* __restrict__ obs, int stride, const ActorNet& net, const float* __restrict__ logstd,
+                                           uint64_t seed, uint32_t counter, float* __restrict__ mu_out, float* __restrict__ act_out) {
     constexpr int LDA = MAXW + 4;  // row stride (floats): = 4 mod 64 banks, as bg_actor_sample's 260
     __shared__ __attribute__((aligned(16))) float buf[2][MR * LDA];
-    const int r0 = blockIdx.x * MR, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int K = net.in[0], KP = (K + KC - 1) / KC * KC;  // obs row stride 47 H (+ P); the tile's columns padded to whole k-chunks with zeros (KP <= LDA: host)
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int K = net.in[0], KP = (K + KC - 1) / KC * KC;  // 47 H (+ P) columns; the tile's columns padded to whole k-chunks with zeros (KP <= LDA: host)
     for (int k = threadIdx.x; k < MR * KP; k += blockDim.x) {
         const int r = k / KP, c = k - r * KP;
-        buf[0][r * LDA + c] = (r0 + r < N && c < K) ? obs[(size_t)(r0 + r) * K + c] : 0.f;
+        buf[0][r * LDA + c] = (r0 + r < N && c < K) ? obs[(size_t)(r0 + r) * stride + c] : 0.f;
     }
     __syncthreads();
     first_layer<LDA>(net.W[0], net.b[0], K, net.out[0], buf[0], buf[1], wave, lane);
@@ -156,41 +164,72 @@ __global__ __launch_bounds__(256) void actor_mlp_sample_kernel(int N, const floa
     if (threadIdx.x < MR * 3) {
         const int r = threadIdx.x / 3, g = threadIdx.x % 3, row = r0 + r;
         if (row < N) {
-            bg::Rand4 rn = bg::rand4(seed, (uint32_t)row, counter, bg::RS_ACTOR + g);
-            for (int k = 0; k < 4; k++) {
-                const int a = g * 4 + k;
-                const float m = buf[cur][r * LDA + a];
-                if (mu_out) mu_out[(size_t)row * BG_NUM_DOFS + a] = m;
-                act_out[(size_t)row * BG_NUM_DOFS + a] = m + expf(logstd[a]) * rn.n[k];
+            if (!act_out) {
+                for (int k = 0; k < 4; k++) mu_out[(size_t)row * BG_NUM_DOFS + g * 4 + k] = buf[cur][r * LDA + g * 4 + k];
+            } else {
+                bg::Rand4 rn = bg::rand4(seed, (uint32_t)row, counter, bg::RS_ACTOR + g);
+                for (int k = 0; k < 4; k++) {
+                    const int a = g * 4 + k;
+                    const float m = buf[cur][r * LDA + a];
+                    if (mu_out) mu_out[(size_t)row * BG_NUM_DOFS + a] = m;
+                    act_out[(size_t)row * BG_NUM_DOFS + a] = m + expf(logstd[a]) * rn.n[k];
+                }
             }
         }
     }
 }
 
+template <int MAXW>
+__global__ __launch_bounds__(256) void actor_mlp_sample_kernel(int N, const float* __restrict__ obs, ActorNet net, const float* __restrict__ logstd,
+                                                               uint64_t seed, uint32_t counter, float* __restrict__ mu_out, float* __restrict__ act_out) {
+    actor_rows<MAXW>(N, blockIdx.x * MR, obs, net.in[0], net, logstd, seed, counter, mu_out, act_out);  // contiguous rows; act_out != nullptr: host
+}
+
+// bg_distill_act: nets.n[0] = the teacher (workgroups [0, nb): the longer network first), nets.n[1] = the student (workgroups [nb, 2 nb)).  Both read
+// rows of `stride` floats (the student's 47 H columns are a prefix of the teacher's 47 H + P); the teacher writes its mean, the student samples.
+struct DistillNets { ActorNet n[2]; };
+template <int MAXW>
+__global__ __launch_bounds__(256) void distill_act_kernel(int N, int nb, const float* __restrict__ obs, int stride, DistillNets nets,
+                                                          const float* __restrict__ logstd, uint64_t seed, uint32_t counter, float* __restrict__ student_mu,
+                                                          float* __restrict__ act_out, float* __restrict__ teacher_mu) {
+    const bool teacher = (int)blockIdx.x < nb;
+    const int r0 = (teacher ? blockIdx.x : blockIdx.x - nb) * MR;
+    actor_rows<MAXW>(N, r0, obs, stride, nets.n[teacher ? 0 : 1], logstd, seed, counter, teacher ? teacher_mu : student_mu, teacher ? nullptr : act_out);
+}
+
 }  // namespace
 
-// scan: the height-scan values behind the 47 H observations of a row (bg_env_cfg.actor_heights), 0 without them
-static int sample_mlp(int32_t N, const float* obs, int32_t n_layers, const bg_mlp_layer_desc* layers, int32_t scan, const float* logstd, uint64_t seed,
-                      uint64_t counter, float* mu, float* actions, void* stream) {
-    if (N <= 0 || !obs || !layers || !logstd || !actions) return bg_set_error(-1, "bg_actor_sample_mlp: bad argument");
-    if (n_layers < 3 || n_layers > MAX_LAYERS) return bg_set_error(-4, "bg_actor_sample_mlp: 2 to 4 hidden layers (n_layers 3 to 5)");
-    ActorNet net{};
+// The descriptors of one network -> ActorNet, with the width rules of the kernel; scan: the height-scan values behind the 47 H observations of a row
+// (bg_env_cfg.actor_heights), 0 without them.  maxw: the widest hidden layer.  `who` heads the error messages.
+static int fill_net(const char* who, int32_t n_layers, const bg_mlp_layer_desc* layers, int32_t scan, ActorNet& net, int& maxw) {
+    const std::string w(who);
+    if (n_layers < 3 || n_layers > MAX_LAYERS) return bg_set_error(-4, (w + ": 2 to 4 hidden layers (n_layers 3 to 5)").c_str());
+    net = ActorNet{};
     net.n = n_layers;
-    int maxw = 0;
+    maxw = 0;
     for (int l = 0; l < n_layers; l++) {
         const bg_mlp_layer_desc& d = layers[l];
-        if (!d.W || !d.b) return bg_set_error(-1, "bg_actor_sample_mlp: bad argument (layer weights)");
+        if (!d.W || !d.b) return bg_set_error(-1, (w + ": bad argument (layer weights)").c_str());
         const bool last = l + 1 == n_layers;
         if (l == 0 ? (d.in - scan < BG_NUM_OBS || d.in - scan > BG_NUM_OBS * BG_MAX_FRAME_STACK || (d.in - scan) % BG_NUM_OBS != 0 || d.in > BG_ACTOR_MAX_INPUT)
                    : d.in != layers[l - 1].out)
-            return bg_set_error(-4, "bg_actor_sample_mlp: layer widths do not chain (first layer: 47 H inputs, H = 1 .. 10 observation frames, and the "
-                                    "height scan's points behind them, BG_ACTOR_MAX_INPUT at most)");
+            return bg_set_error(-4, (w + ": layer widths do not chain (first layer: 47 H inputs, H = 1 .. 10 observation frames, and the "
+                                         "height scan's points behind them, BG_ACTOR_MAX_INPUT at most)").c_str());
         if (last ? d.out != BG_NUM_DOFS : (d.out % 128 != 0 || d.out < 128 || d.out > 512))
-            return bg_set_error(-4, "bg_actor_sample_mlp: unsupported widths (hidden: multiples of 128 up to 512; output: 12)");
-        if (l > 0 && ((uintptr_t)d.W & 15)) return bg_set_error(-1, "bg_actor_sample_mlp: weight matrices after the first must be 16-byte aligned");
+            return bg_set_error(-4, (w + ": unsupported widths (hidden: multiples of 128 up to 512; output: 12)").c_str());
+        if (l > 0 && ((uintptr_t)d.W & 15)) return bg_set_error(-1, (w + ": weight matrices after the first must be 16-byte aligned").c_str());
         net.W[l] = d.W; net.b[l] = d.b; net.in[l] = d.in; net.out[l] = d.out;
         if (!last && d.out > maxw) maxw = d.out;
     }
+    return 0;
+}
+
+static int sample_mlp(int32_t N, const float* obs, int32_t n_layers, const bg_mlp_layer_desc* layers, int32_t scan, const float* logstd, uint64_t seed,
+                      uint64_t counter, float* mu, float* actions, void* stream) {
+    if (N <= 0 || !obs || !layers || !logstd || !actions) return bg_set_error(-1, "bg_actor_sample_mlp: bad argument");
+    ActorNet net;
+    int maxw = 0;
+    if (const int rc = fill_net("bg_actor_sample_mlp", n_layers, layers, scan, net, maxw)) return rc;
     const dim3 grid((N + MR - 1) / MR), block(256);
     hipStream_t st = (hipStream_t)stream;
     const int kp = (layers[0].in + KC - 1) / KC * KC;  // the input tile's columns: within the 256-wide form's LDS tile up to 5 frames (240)
@@ -209,4 +248,29 @@ extern "C" int bg_actor_sample_mlp_scan(int32_t N, const float* obs, int32_t n_l
                                         const float* logstd, uint64_t seed, uint64_t counter, float* mu, float* actions, void* stream) {
     if (scan_points < 0 || scan_points > BG_MAX_HEIGHT_SCAN_POINTS) return bg_set_error(-1, "bg_actor_sample_mlp_scan: bad argument (scan_points)");
     return sample_mlp(N, obs, n_layers, layers, scan_points, logstd, seed, counter, mu, actions, stream);
+}
+
+extern "C" int bg_distill_act(int32_t N, const float* obs, int32_t obs_stride, int32_t n_student, const bg_mlp_layer_desc* student, int32_t n_teacher,
+                              const bg_mlp_layer_desc* teacher, int32_t scan_points, const float* student_logstd, uint64_t seed, uint64_t counter,
+                              float* student_mu, float* actions, float* teacher_mu, void* stream) {
+    if (N <= 0 || !obs || !student || !teacher || !student_logstd || !actions || !teacher_mu) return bg_set_error(-1, "bg_distill_act: bad argument");
+    if (scan_points < 0 || scan_points > BG_MAX_HEIGHT_SCAN_POINTS) return bg_set_error(-1, "bg_distill_act: bad argument (scan_points)");
+    DistillNets nets;
+    int maxw_t = 0, maxw_s = 0;
+    if (const int rc = fill_net("bg_distill_act (teacher)", n_teacher, teacher, scan_points, nets.n[0], maxw_t)) return rc;
+    if (const int rc = fill_net("bg_distill_act (student)", n_student, student, 0, nets.n[1], maxw_s)) return rc;
+    if (obs_stride != teacher[0].in)
+        return bg_set_error(-4, "bg_distill_act: obs_stride must equal the teacher's first-layer input (47 H + scan_points columns per row)");
+    if (student[0].in != teacher[0].in - scan_points)
+        return bg_set_error(-4, "bg_distill_act: the student's first layer takes the 47 H observation columns in front of the teacher's scan_points");
+    const int nb = (N + MR - 1) / MR;
+    const dim3 grid(2 * nb), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    const int kp = (teacher[0].in + KC - 1) / KC * KC, maxw = maxw_t > maxw_s ? maxw_t : maxw_s;  // one LDS form for both halves: the wider one's
+    if (maxw <= 256 && kp <= 256)
+        hipLaunchKernelGGL(distill_act_kernel<256>, grid, block, 0, st, N, nb, obs, obs_stride, nets, student_logstd, seed, (uint32_t)counter, student_mu, actions, teacher_mu);
+    else
+        hipLaunchKernelGGL(distill_act_kernel<512>, grid, block, 0, st, N, nb, obs, obs_stride, nets, student_logstd, seed, (uint32_t)counter, student_mu, actions, teacher_mu);
+    HIP_OK(hipGetLastError());
+    return 0;
 }

@@ -8,12 +8,16 @@
 //                           hidden layer, log-std gradient and the loss statistics
 //   bg_critic_head_forward  values = h w + b for every row (the GAE scan between forward and backward needs all of them first)
 //   bg_critic_head_backward value loss (runner.py:148) backward through the output layer into the last hidden layer
+//   bg_distill_head         mu = h W^T + b -> behaviour-cloning loss mean((mu - target)^2) and its backward (teacher-student distillation,
+//                           utils/distill.py): bg_actor_head's forward and backward mappings around bg_critic_head_backward's form of loss
 //   bg_actor_head_sym       bg_actor_head on a batch of 2B rows (the rollout's, then their mirror images) plus the mirror-symmetry loss
 //                           (algorithm.symmetry_loss); bg_mirror_rows writes the mirrored network inputs
 // Arithmetic is plain fp32 FMA on the vector ALU: 4.6 kflop per row against 1 KB of traffic is under the HBM ridge, so nothing here is
 // reshaped into an MFMA GEMM.  Reductions over rows are deterministic: every workgroup writes its partial sums, a second kernel adds them
 // in a fixed order (the loss statistics and the log-std gradient keep the float64 atomics of bg_ppo_loss).
 #include <hip/hip_runtime.h>
+
+#include <string>
 
 #include "../../include/booster_gym_amd.h"
 #include "bg_ppo_math.h"
@@ -540,6 +544,100 @@ __global__ __launch_bounds__(256) void critic_values_gae_kernel(int T, int N, co
     }
 }
 
+// Behaviour-cloning head (bg_distill_head): L = 1 / (A B) sum_r |mu_r - target_r|^2, dL/dmu = 2 (mu - target) / (A B).  actor_head_kernel's thread
+// mappings, tile walk and record layout (the forward sums are its sums: the same mu bits), one float64 statistic per workgroup: the squared errors.
+__global__ __launch_bounds__(256) void distill_head_kernel(int B, int tiles, const float* __restrict__ h, const float* __restrict__ W,
+                                                           const float* __restrict__ bias, const float* __restrict__ target, float* __restrict__ mu_out,
+                                                           float* __restrict__ g_hidden, float* __restrict__ partial) {
+    constexpr int A = HA;
+    __shared__ __attribute__((aligned(16))) float s_h[HT * HLD];
+    __shared__ __attribute__((aligned(16))) float s_w[A * HLD];
+    __shared__ __attribute__((aligned(16))) float s_g[HT * A];
+    const int t = threadIdx.x;
+    for (int i = t; i < A * HK; i += 256) s_w[(i >> 7) * HLD + (i & (HK - 1))] = W[i];
+    const int fr = t >> 2, fq = t & 3;
+    float fb[3];
+    for (int i = 0; i < 3; i++) fb[i] = bias[3 * fq + i];
+    const int kc = t & (HK - 1), half = t >> 7;
+    float wcol[A], dW[A], cs = 0.f, dbias[3] = {0.f, 0.f, 0.f};
+    for (int j = 0; j < A; j++) { wcol[j] = W[j * HK + kc]; dW[j] = 0.f; }
+    const float gscale = 2.0f / ((float)A * (float)B);
+    double sse = 0.0;
+    __syncthreads();
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int row0 = tile * HT;
+        load_tile(h, row0, B, s_h);
+        __syncthreads();
+        {   // mu = h W^T + b (bg_actor_head's arithmetic)
+            float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+            const float4* hr = reinterpret_cast<const float4*>(s_h + fr * HLD);
+            const float4* w0 = reinterpret_cast<const float4*>(s_w + (3 * fq) * HLD);
+            const float4* w1 = reinterpret_cast<const float4*>(s_w + (3 * fq + 1) * HLD);
+            const float4* w2 = reinterpret_cast<const float4*>(s_w + (3 * fq + 2) * HLD);
+#pragma unroll 2
+            for (int k4 = 0; k4 < HK / 4; k4++) {
+                const float4 x = hr[k4], u = w0[k4], v = w1[k4], w = w2[k4];
+                a0 = fmaf(x.x, u.x, a0); a0 = fmaf(x.y, u.y, a0); a0 = fmaf(x.z, u.z, a0); a0 = fmaf(x.w, u.w, a0);
+                a1 = fmaf(x.x, v.x, a1); a1 = fmaf(x.y, v.y, a1); a1 = fmaf(x.z, v.z, a1); a1 = fmaf(x.w, v.w, a1);
+                a2 = fmaf(x.x, w.x, a2); a2 = fmaf(x.y, w.y, a2); a2 = fmaf(x.z, w.z, a2); a2 = fmaf(x.w, w.w, a2);
+            }
+            const float m[3] = {a0 + fb[0], a1 + fb[1], a2 + fb[2]};
+            const int b = row0 + fr;
+            const bool live = b < B;
+            const size_t o = (size_t)(live ? b : B - 1) * A + 3 * fq;
+            if (mu_out && live) for (int i = 0; i < 3; i++) mu_out[o + i] = m[i];
+            for (int i = 0; i < 3; i++) {
+                const float e = m[i] - target[o + i];
+                const float gm = live ? gscale * e : 0.f;
+                s_g[fr * A + 3 * fq + i] = gm;
+                dbias[i] += gm;
+                if (live) sse += (double)(e * e);
+            }
+        }
+        __syncthreads();
+        // g_hidden = (dL/dmu W) * elu'(h), dW += dL/dmu^T h, hidden bias gradient = column sums of g_hidden (as actor_head_kernel)
+        for (int rr = 0; rr < HT / 2; rr++) {
+            const int r = half * (HT / 2) + rr;
+            const float hv = s_h[r * HLD + kc];
+            const float4* gp = reinterpret_cast<const float4*>(s_g + r * A);
+            const float4 g0 = gp[0], g1 = gp[1], g2 = gp[2];
+            const float g[A] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w, g2.x, g2.y, g2.z, g2.w};
+            float sa = 0.f, sb = 0.f;
+#pragma unroll
+            for (int j = 0; j < A; j += 2) {
+                sa = fmaf(g[j], wcol[j], sa); sb = fmaf(g[j + 1], wcol[j + 1], sb);
+                dW[j] = fmaf(g[j], hv, dW[j]); dW[j + 1] = fmaf(g[j + 1], hv, dW[j + 1]);
+            }
+            const float gz = (sa + sb) * elu_grad_from_output(hv);
+            cs += gz;
+            if (row0 + r < B) g_hidden[(size_t)(row0 + r) * HK + kc] = gz;
+        }
+        __syncthreads();
+    }
+    // ---- this workgroup's partial sums (bg_actor_head's record layout; ONE float64 statistic)
+    float* red = s_h;  // [2][A + 1][HK]
+    for (int j = 0; j < A; j++) red[(half * (A + 1) + j) * HK + kc] = dW[j];
+    red[(half * (A + 1) + A) * HK + kc] = cs;
+    __syncthreads();
+    float* rec = partial + (size_t)blockIdx.x * head_record<A>();
+    for (int i = t; i < (A + 1) * HK; i += 256) rec[i] = red[i] + red[(A + 1) * HK + i];
+    const int wave = t >> 6, lane = t & 63;
+    __syncthreads();
+    float* redf = s_h;                                    // [4 waves][16]
+    double* redd = reinterpret_cast<double*>(s_h + 64);  // [4 waves]
+    for (int i = 0; i < 3; i++) {
+        const float v = quadcol_sum(dbias[i]);
+        if (lane < 4) redf[wave * 16 + 3 * lane + i] = v;
+    }
+    {
+        const double w = wave_sum_d(sse);
+        if (lane == 0) redd[wave] = w;
+    }
+    __syncthreads();
+    if (t < A) rec[(A + 1) * HK + t] = redf[t] + redf[16 + t] + redf[32 + t] + redf[48 + t];
+    if (t == 0) reinterpret_cast<double*>(partial + head_stat_base<A>())[blockIdx.x] = redd[0] + redd[1] + redd[2] + redd[3];
+}
+
 // ---- mirror-symmetry loss (bg_actor_head_sym): the actor's batch is 2B rows, rows [B, 2B) the mirror images of rows [0, B).  A tile holds HTS
 // original rows in LDS rows [0, HTS) and their mirror images in LDS rows [HTS, 2 HTS), so that the pair's means meet in LDS.  Per pair, with
 // d = mu(M_o x) - M_a mu(x) and c = sym_scale = 2 coef / (B A):  dL/dmu of the mirrored row += c d,  of the original row += -c M_a d  (M_a a
@@ -839,6 +937,42 @@ extern "C" int bg_critic_head_backward(int32_t B, const float* h, const float* w
     hipLaunchKernelGGL(head_finish_kernel, dim3((n_out + 15) / 16 + 1), dim3(256), 0, st, grid, head_record<1>(), n_out, scratch, grad_w, HK, grad_b_hidden,
                        grad_b, head_stat_base<1>(), 1, 0, 0u, 0.0, (double*)nullptr, stats);
     HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ---- behaviour-cloning head (teacher-student distillation)
+static int distill_head_launch(const char* who, int32_t B, const float* h, const float* W, const float* bias, const float* target, float* mu_out, float* g_hidden,
+                               float* grad_W, float* grad_b, float* grad_b_hidden, double* stats, float* scratch, int* grid_out, hipStream_t st) {
+    if (B <= 0 || !h || !W || !bias || !target || !g_hidden || !grad_W || !grad_b || !grad_b_hidden || !stats || !scratch)
+        return bg_set_error(-1, (std::string(who) + ": bad argument").c_str());
+    if (!aligned16(h)) return bg_set_error(-1, (std::string(who) + ": h must be 16-byte aligned").c_str());
+    const int tiles = (B + HT - 1) / HT, grid = head_grid(tiles);
+    hipLaunchKernelGGL(distill_head_kernel, dim3(grid), dim3(256), 0, st, B, tiles, h, W, bias, target, mu_out, g_hidden, scratch);
+    *grid_out = grid;
+    return 0;
+}
+
+extern "C" int bg_distill_head(int32_t B, const float* h, const float* W, const float* bias, const float* target, float* mu_out, float* g_hidden, float* grad_W,
+                               float* grad_b, float* grad_b_hidden, double* stats, float* scratch, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    int grid = 0;
+    if (const int rc = distill_head_launch("bg_distill_head", B, h, W, bias, target, mu_out, g_hidden, grad_W, grad_b, grad_b_hidden, stats, scratch, &grid, st)) return rc;
+    constexpr int n_out = HA * HK + HK + HA;
+    hipLaunchKernelGGL(head_finish_kernel, dim3((n_out + 15) / 16 + 1), dim3(256), 0, st, grid, head_record<HA>(), n_out, scratch, grad_W, HA * HK, grad_b_hidden,
+                       grad_b, head_stat_base<HA>(), 1, 0, 0u, 0.0, (double*)nullptr, stats);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int bg_distill_head_partial(int32_t B, const float* h, const float* W, const float* bias, const float* target, float* mu_out, float* g_hidden,
+                                       float* grad_W, float* grad_b, float* grad_b_hidden, double* stats, float* scratch, bg_reduce_problem* finish, void* stream) {
+    if (!finish) return bg_set_error(-1, "bg_distill_head_partial: bad argument");
+    int grid = 0;
+    if (const int rc = distill_head_launch("bg_distill_head_partial", B, h, W, bias, target, mu_out, g_hidden, grad_W, grad_b, grad_b_hidden, stats, scratch, &grid,
+                                           (hipStream_t)stream))
+        return rc;
+    HIP_OK(hipGetLastError());
+    head_finish_desc(finish, scratch, grid, head_record<HA>(), grad_W, HA * HK, grad_b_hidden, grad_b, HA, head_stat_base<HA>(), 1, 0, 0u, 0.0, nullptr, stats);
     return 0;
 }
 

@@ -1,0 +1,309 @@
+"""Teacher-student distillation of a perceptive actor into a blind one (rsl_rl's `Distillation`, DAgger): a mode beside PPO.
+
+The teacher is an actor trained with terrain.actor_heights: its row is [47 H observations | P height-scan values].  The robot has no height sensor,
+so the deployed policy must act on the first 47 H columns alone.  Here the STUDENT acts in the teacher's env (noise, randomisation and curriculum as
+in training), the teacher labels every visited row with its mean action, and the student regresses onto the labels:
+
+  rollout   per env step ONE launch for both networks (bg_distill_act: the student samples from columns [0, 47 H), the teacher's mean from all
+            47 H + P) and ONE env launch (bg_env_step_to), outputs written in place as in Runner.rollout();
+  update    the prefix columns of the B = T N rows once into the student's zero-padded input, then num_epochs full-batch steps: MLPTrainer's
+            hidden layers forward, bg_distill_head (output layer + mean squared error + its backward), backward_hidden, the grouped weight
+            gradients, the fixed-order finishes, FlatAdam.step (global-norm clip + Adam) over the student's actor parameters at a constant rate.
+
+The student checkpoint is what Runner, play.py, export_model.py and tools/play_oracle.py load under the config with terrain.actor_heights: false and
+env.num_observations: 47 H: `actor.*`, `logstd` (fixed at log(student_noise_std)) and an UNTRAINED `critic.*` of that config's shape.
+"""
+import argparse
+import math
+import os
+import random
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from .. import _lib
+from ..envs import TASKS
+from .buffer import ExperienceBuffer
+from .config import load_cfg
+from .model import CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, MLPTrainer, check_hidden, hidden_of, plan_network
+from .recorder import Recorder
+from .runner import FlatAdam, hidden_widths, pad_input, wgrad_products
+from .terrain import actor_heights_of
+from .utils import head_scratch, reduce_group
+
+DEFAULTS = {"teacher_checkpoint": None, "student_hidden": [256, 128, 128], "num_epochs": 5, "learning_rate": 1.0e-3, "max_grad_norm": 1.0,
+            "student_noise_std": 0.1}
+
+
+class DistillCfg(NamedTuple):
+    teacher_checkpoint: Optional[str]
+    student_hidden: tuple
+    num_epochs: int
+    learning_rate: float
+    max_grad_norm: float
+    student_noise_std: float
+
+
+def distillation_cfg(cfg, world_size=1):
+    """The `distillation:` section of a config as a DistillCfg (absent keys: DEFAULTS), or ValueError naming the key.  Pure: no tensors, no device.
+    The mode needs a perceptive teacher's env (terrain.actor_heights), runs without observation normalisation and on one rank."""
+    sec = cfg.get("distillation")
+    if sec is None:
+        raise ValueError("the config has no `distillation` section: the distillation mode is unavailable (envs/T1.yaml ships one)")
+    if not isinstance(sec, dict):
+        raise ValueError(f"distillation must be a mapping of its keys ({', '.join(DEFAULTS)}), got {sec!r}")
+    unknown = sorted(set(sec) - set(DEFAULTS))
+    if unknown:
+        raise ValueError(f"distillation.{unknown[0]} is not a key of the section ({', '.join(DEFAULTS)})")
+    if not actor_heights_of(cfg["terrain"]):
+        raise ValueError("distillation needs terrain.actor_heights: true (with terrain.measure_heights: the config the teacher was trained under): "
+                         "without the height scan in the actor's row there is nothing to distil from")
+    if (cfg.get("algorithm", {}) or {}).get("empirical_normalization", False):
+        raise ValueError("algorithm.empirical_normalization: true is not supported with distillation for now (a teacher trained with it carries "
+                         "statistics of its own row, the student's would be others)")
+    if int(world_size) != 1:
+        raise ValueError(f"distillation runs on one rank (WORLD_SIZE = {world_size}): data parallelism is out of scope")
+    v = dict(DEFAULTS, **sec)
+    ck = v["teacher_checkpoint"]
+    if ck is not None and not isinstance(ck, str):
+        raise ValueError(f"distillation.teacher_checkpoint must be a path or null, got {ck!r}")
+    try:
+        hidden, _ = check_hidden(v["student_hidden"], CRITIC_HIDDEN)
+    except ValueError as e:
+        raise ValueError(str(e).replace("algorithm.actor_hidden", "distillation.student_hidden")) from None
+    n = v["num_epochs"]
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"distillation.num_epochs must be an integer >= 1, got {n!r}")
+    for key in ("learning_rate", "max_grad_norm", "student_noise_std"):
+        x = v[key]
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or x <= 0:
+            raise ValueError(f"distillation.{key} must be a finite number > 0, got {x!r}")
+    return DistillCfg(ck, hidden, n, float(v["learning_rate"]), float(v["max_grad_norm"]), float(v["student_noise_std"]))
+
+
+def student_cfg_overrides(cfg):
+    """The overrides under which the student checkpoint re-enters Runner / play.py / export_model.py: the teacher's config without the actor's scan."""
+    H = int(cfg["env"].get("frame_stack", 1) or 1)
+    return {"terrain.actor_heights": False, "env.num_observations": _lib.NUM_OBS * H}
+
+
+class Distiller:
+    def __init__(self, cfg=None, args=None):
+        if cfg is None:
+            self._get_args(args)
+            cfg = load_cfg(self.args.task)
+            for arg in ("num_envs",):
+                if getattr(self.args, arg) is not None:
+                    cfg["env"][arg] = getattr(self.args, arg)
+            for arg in ("seed", "max_iterations", "sim_device", "rl_device"):
+                if getattr(self.args, arg) is not None:
+                    cfg["basic"][arg] = getattr(self.args, arg)
+            if self.args.teacher is not None:
+                cfg.setdefault("distillation", {})
+                if isinstance(cfg["distillation"], dict):
+                    cfg["distillation"]["teacher_checkpoint"] = self.args.teacher
+        self.cfg = cfg
+        cfg["basic"].setdefault("task", "T1")
+        cfg["basic"]["rank"] = self.rank = 0
+        self.dcfg = distillation_cfg(cfg, int(os.environ.get("WORLD_SIZE", "1")))  # (ValueError before anything is built)
+        if not self.dcfg.teacher_checkpoint:
+            raise ValueError("distillation.teacher_checkpoint is not set: the path of a checkpoint trained with terrain.actor_heights (distill.py --teacher=PATH)")
+        critic_hidden = hidden_widths(cfg)[1]
+        self._set_seed()
+        task = cfg["basic"]["task"]
+        if task not in TASKS:
+            raise NameError(f"name {task!r} is not defined")
+        self.env = env = TASKS[task](cfg)  # the teacher's env, exactly as Runner builds it
+        self.device = dev = cfg["basic"]["rl_device"]
+        if torch.device(dev) != torch.device(env.device):
+            raise ValueError("rl_device must equal sim_device: the rollout writes simulator outputs straight into the distillation buffers")
+        self.student_obs, self.scan = env.scan_obs_offset, env.num_scan_obs  # 47 H columns, then P
+        self.teacher = self._load_teacher(self.dcfg.teacher_checkpoint)
+        A = env.num_actions
+        self.student = ActorCritic(A, self.student_obs, env.num_privileged_obs, self.dcfg.student_hidden, critic_hidden).to(dev)
+        with torch.no_grad():
+            self.student.logstd.fill_(math.log(self.dcfg.student_noise_std))
+        self.student.logstd.requires_grad_(False)  # fixed exploration noise of the data-collecting student; not trained
+        # only the student's actor is trained: the critic and logstd keep their storage outside the flat Adam buffer
+        self.optimizer = FlatAdam(self.student.actor.parameters(), lr=self.dcfg.learning_rate, max_grad_norm=self.dcfg.max_grad_norm)
+
+        T, N = int(cfg["runner"]["horizon_length"]), env.num_envs
+        self.T, self.N, self.B = T, N, T * N
+        self.buffer = buf = ExperienceBuffer(T, N, dev)
+        buf.add_buffer("actions", (A,))
+        buf.add_buffer("teacher_mu", (A,))
+        buf.add_buffer("obses", (env.num_obs,), extra_rows=1)
+        buf.add_buffer("privileged_obses", (env.num_privileged_obs,), extra_rows=1)
+        buf.add_buffer("rewards", ())
+        buf.add_buffer("dones", (), dtype=torch.bool)
+        buf.add_buffer("time_outs", (), dtype=torch.bool)
+        kin = pad_input(self.student_obs)
+        self._student_in = torch.zeros(self.B, kin, device=dev)  # (the padded columns stay zero)
+        self._trainer = tr = MLPTrainer(self.student.actor)
+        widths = (tr.layers[0].in_features,) + tuple(l.out_features for l in tr.layers)
+        sw = MLPTrainer
+        tr.plan = plan = plan_network(widths, kin, self.B, sw.SPLIT, sw.FUSED, sw.CHAIN, sw.CHAIN_SPLIT, sw.CHAIN_SPLIT_BWD, sw.CHAIN_ALTERNATE, sw.FUSED_WGRAD)
+        if "library" in (plan.fwd, plan.bwd) or not all(plan.grouped[:-1]):
+            raise ValueError(f"distillation: a batch of runner.horizon_length x env.num_envs = {T} x {N} = {self.B} rows is outside the range of the layer "
+                             "kernels (an even number of 64 rows or more)")
+        shapes = [(co, ci) for ci, co in zip((kin,) + widths[1:-2], widths[1:-1])]
+        # the products of the grouped weight-gradient launch, by runner.plan_update's rule: the bf16 splits behind the chained split backward only
+        self._wgrad_terms = wgrad_products(self.B, shapes, plan.bwd == "chain_split", sw.SPLIT, sw.WGRAD_SPLIT)
+        self._wgrad = GroupedWeightGrad()
+        self._head_scratch = head_scratch(dev)
+        self._stats = torch.zeros(1, dtype=torch.float64, device=dev)
+        self._losses = torch.zeros(self.dcfg.num_epochs, dtype=torch.float64, device=dev)
+        self._act_counter = 0
+        self._descs = (None, None, None)
+        self.iteration_count = 0
+        self.last_loss = float("nan")
+
+    # ------------------------------------------------------------------ config / seed / teacher
+    def _get_args(self, args=None):
+        parser = argparse.ArgumentParser()
+        parser.add_argument("--task", required=True, type=str, help="Name of the task to run.")
+        parser.add_argument("--teacher", type=str, help="Path of the perceptive teacher's checkpoint. Overrides distillation.teacher_checkpoint.")
+        parser.add_argument("--max_iterations", type=int, help="Number of distillation iterations. Overrides config file if provided.")
+        parser.add_argument("--num_envs", type=int, help="Number of environments to create. Overrides config file if provided.")
+        parser.add_argument("--sim_device", type=str, help="Device for physics simulation. Overrides config file if provided.")
+        parser.add_argument("--rl_device", type=str, help="Device for the networks. Overrides config file if provided.")
+        parser.add_argument("--seed", type=int, help="Random seed. Overrides config file if provided.")
+        self.args = parser.parse_args(args)
+
+    def _set_seed(self):
+        if self.cfg["basic"]["seed"] == -1:
+            self.cfg["basic"]["seed"] = int(np.random.randint(0, 10000))
+        seed = self.cfg["basic"]["seed"]
+        print("Setting seed: {}".format(seed))
+        random.seed(seed)
+        np.random.seed(seed)
+        torch.manual_seed(seed)
+        os.environ["PYTHONHASHSEED"] = str(seed)
+        torch.cuda.manual_seed_all(seed)
+
+    def _load_teacher(self, ck):
+        env = self.env
+        print("Loading teacher from {}".format(ck))
+        d = torch.load(ck, map_location=self.device, weights_only=True)
+        sd = d["model"]
+        if d.get("obs_normalizer") is not None:
+            raise ValueError(f"teacher checkpoint {ck} was trained with algorithm.empirical_normalization (it has an \"obs_normalizer\"): not supported "
+                             "with distillation for now")
+        a_in = int(sd["actor.0.weight"].shape[1])
+        if a_in != env.num_obs:
+            raise ValueError(f"teacher checkpoint {ck} has an actor of {a_in} inputs, the env's row has {env.num_obs} (env.num_observations = 47 x "
+                             "env.frame_stack + the points of terrain.measured_points_x / measured_points_y): the config must be the teacher's")
+        pts = d.get("height_points")
+        if pts is None or tuple(pts.shape) != tuple(env.height_points.shape) or not torch.equal(pts.to(env.height_points.device), env.height_points):
+            raise ValueError(f"teacher checkpoint {ck} " + ("has no \"height_points\" (it was not trained with terrain.actor_heights)" if pts is None else
+                                                            "has other \"height_points\" than the env's terrain.measured_points_x / measured_points_y"))
+        teacher = ActorCritic(env.num_actions, a_in, int(sd["critic.0.weight"].shape[1]) - a_in, hidden_of(sd, "actor"), hidden_of(sd, "critic")).to(self.device)
+        teacher.load_state_dict(sd)
+        teacher.requires_grad_(False)
+        if "curriculum" in d:
+            try:
+                env.curriculum_prob = d["curriculum"]
+            except Exception as e:
+                print(f"Failed to load curriculum: {e}")
+        if env.terrain.curriculum and "terrain_levels" in d:
+            try:
+                lv = d["terrain_levels"]
+                if tuple(lv.shape) != (env.num_envs,):
+                    raise ValueError(f"shape {tuple(lv.shape)}, the env has {env.num_envs} envs")
+                env.terrain_levels = lv
+            except Exception as e:
+                print(f"Failed to load terrain levels: {e!r}")
+        return teacher
+
+    def checkpoint_dict(self):
+        """The student as a checkpoint of the config with terrain.actor_heights: false and env.num_observations: 47 H (student_cfg_overrides): no
+        "height_points", no "optimizer"; the critic is the untrained one built here."""
+        d = {"model": self.student.state_dict(), "curriculum": self.env.curriculum_prob,
+             "distillation": {"teacher": str(self.dcfg.teacher_checkpoint), "iteration": int(self.iteration_count), "loss": float(self.last_loss)}}
+        if self.env.terrain.curriculum:
+            d["terrain_levels"] = self.env.terrain_levels
+        return d
+
+    # ------------------------------------------------------------------ one iteration
+    def _descriptors(self):
+        """bg_mlp_layer_desc arrays of the student's and the teacher's actor on their current parameter storage."""
+        lins = [[m for m in net.actor if isinstance(m, torch.nn.Linear)] for net in (self.student, self.teacher)]
+        key = tuple(t.data_ptr() for lin in lins for l in lin for t in (l.weight, l.bias))
+        if key != self._descs[0]:
+            arrs = [(_lib.MlpLayerDesc * len(lin))(*[_lib.MlpLayerDesc(l.weight.data_ptr(), l.bias.data_ptr(), l.in_features, l.out_features) for l in lin])
+                    for lin in lins]
+            self._descs = (key, arrs[0], arrs[1])
+        return self._descs[1], self._descs[2]
+
+    def rollout(self):
+        """T env steps with the student's sampled actions; every visited row and the teacher's mean action on it are kept."""
+        buf, T, N = self.buffer, self.T, self.N
+        obses, priv, actions, labels = buf["obses"], buf["privileged_obses"], buf["actions"], buf["teacher_mu"]
+        seed = int(self.cfg["basic"]["seed"]) + 1000003  # (Runner's rollout seed of rank 0)
+        sd, td = self._descriptors()
+        lib, logstd = _lib.load(), self.student.logstd
+        with torch.no_grad():
+            for n in range(T):
+                _lib.check(lib.bg_distill_act(N, _lib.ptr(obses[n]), obses.shape[-1], len(sd), sd, len(td), td, self.scan, _lib.ptr(logstd), seed, self._act_counter,
+                                              None, _lib.ptr(actions[n]), _lib.ptr(labels[n]), _lib.current_stream_ptr()), "bg_distill_act")
+                self._act_counter += 1
+                self.env.step_to(actions[n], obses[n + 1], priv[n + 1], buf["rewards"][n], buf["dones"][n], buf["time_outs"][n])
+
+    def update(self):
+        """num_epochs full-batch behaviour-cloning steps on the rollout's rows.  Returns the per-epoch mean losses (float64 device tensor: the loss
+        each step's gradient was taken of)."""
+        tr, B, A = self._trainer, self.B, self.env.num_actions
+        out, hid = tr.layers[-1], tr.layers[-2]
+        target = self.buffer["teacher_mu"].reshape(B, A)
+        with torch.no_grad():
+            self._student_in[:, : self.student_obs].copy_(self.buffer["obses"][: self.T].reshape(B, -1)[:, : self.student_obs])
+            for e in range(self.dcfg.num_epochs):
+                tr.mirror_fresh = False  # FlatAdam.step does not write the copies of the weights that the layer kernels read
+                h = tr.forward_hidden(self._student_in)
+                self._stats.zero_()
+                fin, fins = _lib.ReduceProblem(), []
+                _lib.check(_lib.load().bg_distill_head_partial(B, _lib.ptr(h), _lib.ptr(out.weight), _lib.ptr(out.bias), _lib.ptr(target), None,
+                                                               _lib.ptr(tr.hidden_grad), _lib.ptr(out.weight.grad), _lib.ptr(out.bias.grad), _lib.ptr(hid.bias.grad),
+                                                               _lib.ptr(self._stats), _lib.ptr(self._head_scratch), fin, _lib.current_stream_ptr()),
+                           "bg_distill_head_partial")
+                tr.backward_hidden(finishes=fins)
+                self._wgrad.run((tr,), self._wgrad_terms, False)
+                reduce_group([fin] + fins)
+                self.optimizer.step()
+                self._losses[e : e + 1].copy_(self._stats)
+        return self._losses / float(A * B)
+
+    def iteration(self):
+        self.rollout()
+        losses = self.update()
+        self.buffer.roll()
+        self.iteration_count += 1
+        return losses
+
+    # ------------------------------------------------------------------ entry point
+    def begin(self, recorder=None):
+        self.recorder = recorder if recorder is not None else Recorder(self.cfg, rank=0)
+        obs, infos = self.env.reset()
+        self.buffer["obses"][0].copy_(obs)
+        self.buffer["privileged_obses"][0].copy_(infos["privileged_obs"])
+
+    def train_iteration(self, it):
+        losses = self.iteration()
+        self.last_loss = float(losses[-1].item())  # (one host read per iteration)
+        self.recorder.record_episode_statistics(self.env, self.env.reward_names, it)
+        stats = {"distill/behaviour_loss": self.last_loss}
+        if self.env.terrain.curriculum:
+            stats["terrain/mean_level"] = float(self.env.terrain_level_sum().item()) / self.env.num_envs
+        self.recorder.record_statistics(stats, it)
+        if (it + 1) % self.cfg["runner"]["save_interval"] == 0:
+            self.recorder.save(self.checkpoint_dict(), it + 1)
+
+    def train(self):
+        self.begin()
+        max_it = self.cfg["basic"]["max_iterations"]
+        for it in range(max_it):
+            self.train_iteration(it)
+            print("distillation: {}/{}  behaviour loss {:.6f}".format(it + 1, max_it, self.last_loss))
+        if max_it % self.cfg["runner"]["save_interval"]:
+            self.recorder.save(self.checkpoint_dict(), max_it)

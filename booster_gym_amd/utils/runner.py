@@ -171,6 +171,18 @@ class StepRows(NamedTuple):
 TAIL_MAX_ITEMS = 8192  # blocks of sums of one bg_update_tail launch (bg_tail.hip)
 
 
+WGRAD_SPLIT_SHAPES = ((256, 256), (128, 256), (128, 128), (256, 64))  # (C_out, C_in padded) that bg_wgrad_split.hip has kernels for
+
+
+def wgrad_products(rows, grouped, bwd_chained, split, wgrad_split):
+    """Products of the grouped weight-gradient launch over the layers `grouped` = [(C_out, C_in padded)]: 0 = fp32 MFMA (bg_wgrad.hip), 6 / 9 = bf16
+    splits (bg_wgrad_split.hip: its shapes, rows a multiple of 32 from 128 up; `split` everywhere, `wgrad_split` behind the chained split backward of
+    every network only).  The one rule of plan_update and of utils/distill.py."""
+    if rows % 32 != 0 or rows < 128 or not all(s in WGRAD_SPLIT_SHAPES for s in grouped):
+        return 0
+    return split or (wgrad_split if bwd_chained else 0)
+
+
 def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_split_bwd, chain_alternate, fused_wgrad, wgrad_split, one_stream,
                 defer_finish, one_launch_tail, fused_opt, fused_head, fused_gae, chain_values, rollout_forward, dp_active, symmetry=False):
     """UpdatePlan from the switches (MLPTrainer.SPLIT ... WGRAD_SPLIT and Runner._one_stream ... _rollout_forward, by the same names in lower case;
@@ -185,8 +197,7 @@ def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_
             for (w, kin), r in ((critic, rows), (actor, 2 * rows if symmetry else rows))]
     bwd_chained = all(n.bwd == "chain_split" for n in nets)
     grouped = [(co, ci) for (w, kin), n in zip((critic, actor), nets) for ci, co, g in zip((kin,) + tuple(w[1:-1]), w[1:], n.grouped) if g]
-    wgrad = ((split or (wgrad_split if bwd_chained else 0)) if rows % 32 == 0 and rows >= 128
-             and all(s in ((256, 256), (128, 256), (128, 128), (256, 64)) for s in grouped) else 0)
+    wgrad = wgrad_products(rows, grouped, bwd_chained, split, wgrad_split)
     chain_values = fused_head and fused_gae and chain_values and nets[0].chained
     defer = fused_head and defer_finish and not split
     # bg_update_tail takes the gradient's norm from its own sums, so every gradient element must come out of them: all hidden layers' weight gradients

@@ -317,6 +317,17 @@ int bg_actor_sample_mlp(int32_t N, const float* obs, int32_t n_layers, const bg_
  * `in` read as zeros).  scan_points = 0 is bg_actor_sample_mlp. */
 int bg_actor_sample_mlp_scan(int32_t N, const float* obs, int32_t n_layers, const bg_mlp_layer_desc* layers, int32_t scan_points, const float* logstd,
                              uint64_t seed, uint64_t counter, float* mu, float* actions, void* stream);
+/* Teacher-student distillation (utils/distill.py), the rollout's launch: TWO networks of bg_actor_sample_mlp's kind on the same rows.  obs [N] rows of
+ * obs_stride floats = the perceptive teacher's row [47 H observations | scan_points height-scan values]; obs_stride must equal the teacher's first-layer
+ * `in` (47 H + scan_points <= BG_ACTOR_MAX_INPUT) and the student's first-layer `in` must be 47 H: the student reads columns [0, 47 H) of each row and
+ * samples actions [N][12] = mu_s + exp(student_logstd) n with bg_actor_sample_mlp's noise (Philox(seed, row, counter, RS_ACTOR + group of 4 actions)),
+ * student_mu [N][12] may be NULL; the teacher reads all columns and writes its mean teacher_mu [N][12] only.  Width rules per network as
+ * bg_actor_sample_mlp; depths and widths may differ.  The grid is split between the networks (16 rows per workgroup each), every half running the
+ * stand-alone kernel's layer code: teacher_mu equals bg_actor_sample_mlp_scan's mu and student_mu / actions equal bg_actor_sample_mlp's on a
+ * contiguous copy of the prefix columns, bit for bit. */
+int bg_distill_act(int32_t N, const float* obs, int32_t obs_stride, int32_t n_student, const bg_mlp_layer_desc* student, int32_t n_teacher,
+                   const bg_mlp_layer_desc* teacher, int32_t scan_points, const float* student_logstd, uint64_t seed, uint64_t counter, float* student_mu,
+                   float* actions, float* teacher_mu, void* stream);
 /* Fused global-norm clip + Adam over one flat parameter buffer (runner.py:162-165); lr is read from device memory
  * so the KL-adaptive schedule (runner.py:174-180) needs no host sync.  gnorm_scratch [1] device float64. */
 int bg_adam_step(int32_t n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const float* lr_device, int32_t step,
@@ -490,6 +501,12 @@ int bg_actor_head(int32_t B, int32_t mode, const float* h, const float* W, const
  * stats[0] += sum of squared value errors (float64, atomic) */
 int bg_critic_head_backward(int32_t B, const float* h, const float* w, const float* values, const float* returns, float* g_hidden, float* grad_w,
                             float* grad_b, float* grad_b_hidden, double* stats, float* scratch, void* stream);
+/* Behaviour-cloning head of the distillation's student: mu = h W^T + b (W [12][128], b [12]; bg_actor_head's sums: the same bits as its mode 0), the
+ * loss L = 1 / (12 B) sum (mu - target)^2 against target [B][12] (the teacher's means) and its backward: g_hidden [B][128] = dL/dz of the last hidden
+ * layer (ELU derivative from h applied), grad_W [12][128], grad_b [12], grad_b_hidden [128], stats[0] += the sum of squared errors (float64, one
+ * atomic; the caller zeroes).  mu_out [B][12] may be NULL.  Per-workgroup records in scratch, added in a fixed order: deterministic. */
+int bg_distill_head(int32_t B, const float* h, const float* W, const float* bias, const float* target, float* mu_out, float* g_hidden, float* grad_W,
+                    float* grad_b, float* grad_b_hidden, double* stats, float* scratch, void* stream);
 
 /* Mirror-symmetry loss (algorithm.symmetry_loss): the actor's batch is 2B rows, rows [B, 2B) of h / g_hidden / mu_out the mirror images of rows [0, B)
  * (their observations M_o x, written by bg_mirror_rows).  bg_actor_head mode 1 on the original rows plus, with d_r = mu(M_o x_r) - M_a mu(x_r), the term
@@ -576,6 +593,9 @@ int bg_critic_head_backward_partial(int32_t B, const float* h, const float* w, c
                                     void* stream);
 int bg_mlp_layer_backward_partial(int32_t M, int32_t K, int32_t N, const float* G, const float* Wt, const float* act_below, float* Gout,
                                   float* bias_grad_below, float* scratch, bg_reduce_problem* finish, void* stream);
+/* bg_distill_head without its finishing launch (as bg_actor_head_partial). */
+int bg_distill_head_partial(int32_t B, const float* h, const float* W, const float* bias, const float* target, float* mu_out, float* g_hidden, float* grad_W,
+                            float* grad_b, float* grad_b_hidden, double* stats, float* scratch, bg_reduce_problem* finish, void* stream);
 
 /* ---- empirical observation normalisation (algorithm.empirical_normalization; bg_obs_norm.hip).  Two launches of their own beside the hot path:
  * nothing of them runs when the key is false.

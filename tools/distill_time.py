@@ -1,0 +1,169 @@
+"""Timing of the teacher-student distillation (README "Distillation"); writes profiles/distill_time.txt.
+
+  python tools/distill_time.py [K=20] [W=5] [pairs=3] [num_envs=4096] [out=profiles/distill_time.txt]
+      (1) the rollout's launch, bg_distill_act, against the sum of its stand-alone launches on the same rows (bg_actor_sample_mlp_scan on the whole
+          row, bg_actor_sample_mlp on a contiguous copy of the prefix columns, and that copy), HIP events around 200 back-to-back calls, best of 5,
+          alternating, at H = 1 / P = 187 and at H = 3 / P = 45: us per env step's inference, both networks 256-128-128;
+      (2) bg_distill_head against bg_actor_head mode 1 at B = 98,304 rows, the same way: us per launch pair (kernel + fixed-order finish);
+      (3) the distillation loop (rollout of 24 steps + 5 epochs, no instrumentation) at H = 1 / P = 187 with a seeded teacher: W warm-up iterations,
+          then runs of K iterations: ms per iteration, iterations per second.
+  The outputs of (1) are compared bit for bit before they are timed.  The committed profile carries two more sections that this tool does not
+  write: the figures tests/test_gpu_distill.py prints under -s, and bench.py of this tree against a checkout of its parent commit."""
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch
+
+DEV = "cuda:0"
+GRID_9x5 = {"terrain.measured_points_x": [round(-0.4 + 0.1 * i, 1) for i in range(9)], "terrain.measured_points_y": [-0.2, -0.1, 0.0, 0.1, 0.2]}
+LINES = []
+
+
+def say(s):
+    print(s, flush=True)
+    LINES.append(s)
+
+
+def _best(fn, reps, rounds=5):
+    b = 1e9
+    for _ in range(rounds):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for k in range(reps):
+            fn(k)
+        e1.record(); torch.cuda.synchronize()
+        b = min(b, e0.elapsed_time(e1) / reps * 1e3)
+    return b
+
+
+def _orders(p, keys):
+    return keys if p % 2 == 0 else tuple(reversed(keys))
+
+
+def _descs(model):
+    from booster_gym_amd import _lib
+
+    lin = [m for m in model.actor if isinstance(m, torch.nn.Linear)]
+    return (_lib.MlpLayerDesc * len(lin))(*[_lib.MlpLayerDesc(l.weight.data_ptr(), l.bias.data_ptr(), l.in_features, l.out_features) for l in lin]), len(lin)
+
+
+def act(pairs=3, N=4096):
+    from booster_gym_amd import _lib
+    from booster_gym_amd.utils.model import ActorCritic
+
+    lib, p = _lib.load(), _lib.ptr
+    for H, P in ((1, 187), (3, 45)):
+        torch.manual_seed(H)
+        F = 47 * H
+        teacher, student = ActorCritic(12, F + P, 14 + P).to(DEV), ActorCritic(12, F, 14 + P).to(DEV)
+        obs, prefix = torch.randn(N, F + P, device=DEV), torch.empty(N, F, device=DEV)
+        (sd, ns), (td, nt) = _descs(student), _descs(teacher)
+        a1, t1, a2, t2, tmp = (torch.empty(N, 12, device=DEV) for _ in range(5))
+        st = _lib.current_stream_ptr()
+
+        def fused(k):
+            _lib.check(lib.bg_distill_act(N, p(obs), F + P, ns, sd, nt, td, P, p(student.logstd), 1, k, None, p(a1), p(t1), st), "bg_distill_act")
+
+        def separate(k):
+            _lib.check(lib.bg_actor_sample_mlp_scan(N, p(obs), nt, td, P, p(teacher.logstd), 1, k, p(t2), p(tmp), st), "bg_actor_sample_mlp_scan")
+            prefix.copy_(obs[:, :F])
+            _lib.check(lib.bg_actor_sample_mlp(N, p(prefix), ns, sd, p(student.logstd), 1, k, None, p(a2), st), "bg_actor_sample_mlp")
+
+        fused(7); separate(7); torch.cuda.synchronize()
+        assert torch.equal(a1, a2) and torch.equal(t1, t2), "bg_distill_act differs from its stand-alone launches"
+        for q in range(pairs):
+            us = {m: _best(f, 200) for m, f in _orders(q, (("fused", fused), ("separate", separate)))}
+            say(f"rollout inference, {N} rows, H = {H}, P = {P}, both 256-128-128: bg_distill_act {us['fused']:.2f} us, bg_actor_sample_mlp_scan + prefix copy + "
+                f"bg_actor_sample_mlp {us['separate']:.2f} us, fused / separate = {us['fused'] / us['separate']:.4f}")
+
+
+def head(pairs=3, B=98304):
+    from booster_gym_amd import _lib
+    from booster_gym_amd.utils.utils import actor_head_loss_backward, head_scratch
+
+    g = torch.Generator(device="cpu").manual_seed(0)
+    A = 12
+    h = torch.nn.functional.elu(torch.randn(B, 128, generator=g)).to(DEV)
+    W, b = (torch.randn(A, 128, generator=g) * 0.1).to(DEV), (torch.randn(A, generator=g) * 0.1).to(DEV)
+    target = torch.randn(B, A, generator=g).to(DEV)
+    logstd = torch.full((A,), -2.0, device=DEV)
+    old_mu = h @ W.t() + b + 0.02 * torch.randn(B, A, generator=g).to(DEV)
+    actions = old_mu + 0.135 * torch.randn(B, A, generator=g).to(DEV)
+    old_logp = (-0.5 * ((actions - old_mu) / logstd.exp()) ** 2 - logstd - 0.9189385332046727).sum(-1)
+    adv = torch.randn(B, generator=g).to(DEV)
+    adv_stats = torch.stack([adv.double().sum(), (adv.double() ** 2).sum(), torch.tensor(float(B), dtype=torch.float64, device=DEV)])
+    gh, dW, db, dbh = torch.empty(B, 128, device=DEV), torch.empty(A, 128, device=DEV), torch.empty(A, device=DEV), torch.empty(128, device=DEV)
+    gls, st5, st1, scr = torch.zeros(A, dtype=torch.float64, device=DEV), torch.zeros(5, dtype=torch.float64, device=DEV), torch.zeros(1, dtype=torch.float64, device=DEV), head_scratch(DEV)
+    lib, p = _lib.load(), _lib.ptr
+
+    def distill(k):
+        _lib.check(lib.bg_distill_head(B, p(h), p(W), p(b), p(target), None, p(gh), p(dW), p(db), p(dbh), p(st1), p(scr), _lib.current_stream_ptr()), "bg_distill_head")
+
+    def actor(k):
+        actor_head_loss_backward(h, W, b, logstd, actions, old_mu, logstd, old_logp, adv, adv_stats, 0.2, 1.0, -0.01, gh, dW, db, dbh, gls, st5, scr)
+
+    for q in range(pairs):
+        us = {m: _best(f, 100) for m, f in _orders(q, (("distill", distill), ("actor", actor)))}
+        # the kernel reads h [B][128] and target [B][12] and writes g_hidden [B][128]
+        gbs = B * (128 * 2 + 12) * 4 / (us["distill"] * 1e-6) / 1e9
+        say(f"loss head, B = {B}: bg_distill_head {us['distill']:.2f} us ({gbs:.0f} GB/s of h + target read, g_hidden written, finish launch included), bg_actor_head mode 1 "
+            f"{us['actor']:.2f} us, distill / actor = {us['distill'] / us['actor']:.4f}")
+
+
+def loop(K=20, W=5, pairs=3, N=4096):
+    from booster_gym_amd.utils.config import load_cfg
+    from booster_gym_amd.utils.distill import Distiller
+    from booster_gym_amd.utils.model import ActorCritic
+    from booster_gym_amd.utils.recorder import Recorder
+    from booster_gym_amd.utils.terrain import height_scan_points
+
+    tmp = tempfile.mkdtemp(prefix="bg_distill_")
+    cfg = load_cfg("T1", {"env.num_envs": N, "terrain.measure_heights": True, "terrain.actor_heights": True, "env.num_observations": 234, "env.num_privileged_obs": 201})
+    cfg["runner"]["save_interval"] = 10 ** 9  # no checkpoint inside the timed region
+    torch.manual_seed(0)
+    ck = os.path.join(tmp, "teacher.pth")
+    torch.save({"model": ActorCritic(12, 234, 201).state_dict(), "height_points": torch.tensor(height_scan_points(cfg["terrain"])[1], dtype=torch.float).reshape(-1, 2)}, ck)
+    cfg["distillation"]["teacher_checkpoint"] = ck
+    d = Distiller(cfg=cfg)
+    d.begin(Recorder(cfg, root=tmp, rank=0))
+    it = 0
+
+    def run(n):
+        nonlocal it
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        for _ in range(n):
+            d.train_iteration(it); it += 1
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3
+
+    run(W)
+    T, E = cfg["runner"]["horizon_length"], d.dcfg.num_epochs
+    for q in range(pairs):
+        ms = run(K)
+        say(f"distillation loop, {N} envs, H = 1, P = 187, horizon {T}, {E} epochs, student 256-128-128 (plan {d._trainer.plan.fwd} / {d._trainer.plan.bwd}, weight "
+            f"gradients {d._wgrad_terms or 'fp32'}): {ms:.3f} ms per iteration = {1e3 / ms:.2f} iterations/s = {N * T / ms / 1e3:.3f} M env-steps/s; last loss "
+            f"{d.last_loss:.6f}")
+    for ph, fn in (("rollout", d.rollout), ("update", d.update)):
+        best = 1e9
+        for _ in range(3):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            best = min(best, (time.perf_counter() - t0) * 1e3)
+        say(f"  {ph} alone: {best:.3f} ms (best of 3)")
+
+
+if __name__ == "__main__":
+    a = sys.argv[1:]
+    K, W, pairs, N = (int(a[i]) if len(a) > i else v for i, v in enumerate((20, 5, 3, 4096)))
+    out = a[4] if len(a) > 4 else os.path.join(ROOT, "profiles", "distill_time.txt")
+    say(f"tools/distill_time.py {K} {W} {pairs} {N} on {torch.cuda.get_device_name(0)}")
+    act(pairs, N)
+    head(pairs)
+    loop(K, W, pairs, N)
+    with open(out, "w") as f:
+        f.write("\n".join(LINES) + "\n")
