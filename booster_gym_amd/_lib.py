@@ -135,6 +135,7 @@ class EnvCfg(C.Structure):
 HEAD_SCRATCH_FLOATS = 768 * 1720  # BG_HEAD_SCRATCH_FLOATS
 OBS_MOMENTS_MAX_GROUPS = 1024  # BG_OBS_MOMENTS_MAX_GROUPS
 GATHER_MAX_STREAMS = 8  # BG_GATHER_MAX_STREAMS
+ACTOR_PACKED_FLOATS = 65616  # BG_ACTOR_PACKED_FLOATS
 
 SYMBOLS = [
     "bg_model_create", "bg_model_get", "bg_model_destroy", "bg_model_load_urdf", "bg_model_body_name", "bg_model_dof_name", "bg_model_find_body", "bg_env_create", "bg_env_destroy", "bg_env_set_heightfield",
@@ -142,7 +143,7 @@ SYMBOLS = [
     "bg_env_set_state", "bg_env_get_field", "bg_env_set_field", "bg_env_field_info", "bg_env_get_curriculum", "bg_env_set_curriculum", "bg_env_step_count", "bg_env_set_step_count",
     "bg_env_get_terrain_level_sum", "bg_env_set_terrain_level_sum",
     "bg_env_forward_dynamics", "bg_env_forward_dynamics_packed", "bg_sim_bind_state", "bg_sim_set_actuation", "bg_sim_apply_body_wrench_local", "bg_sim_simulate",
-    "bg_sim_refresh_body_state", "bg_sim_write_root_state", "bg_sim_write_dof_state", "bg_gae", "bg_ppo_loss", "bg_gaussian_logp", "bg_actor_sample", "bg_actor_sample_mlp", "bg_actor_sample_mlp_scan", "bg_distill_act", "bg_adam_step", "bg_adapt_lr", "bg_optimizer_step", "bg_elu_backward_colsum", "bg_mlp_layer_forward", "bg_mlp_chain_forward", "bg_critic_values_gae", "bg_mlp_chain_forward_group", "bg_mlp_chain_forward_split", "bg_mlp_chain_backward_split", "bg_mlp_split_weights_pm", "bg_mlp_layer_backward", "bg_mlp_split_weights", "bg_mlp_layer_forward_split", "bg_mlp_layer_backward_split", "bg_mlp_weight_grad", "bg_mlp_weight_grad_group", "bg_mlp_weight_grad_group_partial", "bg_update_tail", "bg_update_tail_sums", "bg_mlp_weight_grad_group_split", "bg_mlp_weight_grad_group_split_partial",
+    "bg_sim_refresh_body_state", "bg_sim_write_root_state", "bg_sim_write_dof_state", "bg_gae", "bg_ppo_loss", "bg_gaussian_logp", "bg_actor_pack", "bg_actor_sample", "bg_actor_sample_mlp", "bg_actor_sample_mlp_scan", "bg_distill_act", "bg_adam_step", "bg_adapt_lr", "bg_optimizer_step", "bg_elu_backward_colsum", "bg_mlp_layer_forward", "bg_mlp_chain_forward", "bg_critic_values_gae", "bg_mlp_chain_forward_group", "bg_mlp_chain_forward_split", "bg_mlp_chain_backward_split", "bg_mlp_split_weights_pm", "bg_mlp_layer_backward", "bg_mlp_split_weights", "bg_mlp_layer_forward_split", "bg_mlp_layer_backward_split", "bg_mlp_weight_grad", "bg_mlp_weight_grad_group", "bg_mlp_weight_grad_group_partial", "bg_update_tail", "bg_update_tail_sums", "bg_mlp_weight_grad_group_split", "bg_mlp_weight_grad_group_split_partial",
     "bg_critic_head_forward", "bg_actor_head", "bg_critic_head_backward",
     "bg_reduce_group", "bg_actor_head_partial", "bg_critic_head_backward_partial", "bg_mlp_layer_backward_partial",
     "bg_actor_head_sym", "bg_actor_head_sym_partial", "bg_mirror_rows",
@@ -206,7 +207,8 @@ def load():
         "bg_gae": (i32, [i32, i32, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp]),
         "bg_ppo_loss": (i32, [i32, i32] + [vp] * 10 + [f32, f32, f32] + [vp] * 5),
         "bg_gaussian_logp": (i32, [i32, i32, vp, vp, vp, vp, vp]),
-        "bg_actor_sample": (i32, [i32] + [vp] * 10 + [u64, u64, vp, vp, vp]),
+        "bg_actor_pack": (i32, [vp] * 11),
+        "bg_actor_sample": (i32, [i32, vp, vp, u64, u64, vp, vp, vp]),
         "bg_actor_sample_mlp": (i32, [i32, vp, i32, C.POINTER(MlpLayerDesc), vp, u64, u64, vp, vp, vp]),
         "bg_actor_sample_mlp_scan": (i32, [i32, vp, i32, C.POINTER(MlpLayerDesc), i32, vp, u64, u64, vp, vp, vp]),
         "bg_distill_act": (i32, [i32, vp, i32, i32, C.POINTER(MlpLayerDesc), i32, C.POINTER(MlpLayerDesc), i32, vp, u64, u64, vp, vp, vp, vp]),

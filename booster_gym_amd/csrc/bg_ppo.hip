@@ -13,6 +13,7 @@
 #include "bg_mirror.h"
 #include "bg_ppo_math.h"
 #include "bg_rng.h"
+#include "bg_stamps.h"
 
 extern int bg_set_error(int code, const char* msg);
 #define HIP_OK(expr)                                                                        \
@@ -169,139 +170,226 @@ __global__ void gaussian_logp_kernel(int B, const float* __restrict__ mu, const 
 // One workgroup (4 waves) = 16 observation rows; activations ping-pong between two LDS tiles; every wave owns output-neuron
 // tiles of 16 and accumulates them with v_mfma_f32_16x16x4_f32 (exact fp32, D = A*B + C):
 //     A[i = lane & 15][k = lane >> 4] = X[row i][k]          (from LDS, one ds_read_b128 feeds 4 MFMAs)
-//     B[k = lane >> 4][j = lane & 15] = W[neuron j][k]       (straight from L2: torch layout [out][in], one 16-byte load feeds 4 MFMAs)
+//     B[k = lane >> 4][j = lane & 15] = W[neuron j][k]       (from the packed copy below, one 16-byte load feeds 4 MFMAs)
 //     C/D: neuron j = lane & 15, row i = (lane >> 4) * 4 + reg
 // The k index inside a group of 16 is permuted identically for A and B (k = 16 t + 4 (lane >> 4) + step), which a sum over k allows.
-// 63,244 weights = 253 kB stay L2-resident; 992 MFMAs per workgroup.
+// 992 MFMAs per workgroup.
+//
+// The weights come from a PACKED copy (bg_actor_pack, once per rollout; BG_ACTOR_PACKED_FLOATS floats), laid out in the order the lanes consume them, so
+// that every weight load of a wave is one 16-byte load per lane at consecutive addresses (1 kB per instruction).  As torch keeps them ([out][in]) the same
+// operands are 16-byte pieces 64 to 1,024 bytes apart, and the 47-column first layer 48 single dwords per lane: 16 cache lines touched per load instruction,
+// by every workgroup of every launch.  Layout, `wave` and tile slot j as in the kernel (tile = wave + 4 j), neuron n = 16 tile + (lane & 15):
+//     layer 0   float4 [4 waves][4 j][3 q][64 lanes]: component c = W0[n][4 (4 q + c) + (lane >> 4)], column 47 (q = 2, c = 3, lanes 48 .. 63) zero
+//     layer L   float4 [waves][NT j][K / 16 t][64 lanes]: component c = WL[n][16 t + 4 (lane >> 4) + c]; zero where n is no neuron (the 12-neuron output
+//               layer: lanes with lane & 15 >= 12); the output layer keeps wave 0 only, the only wave with a tile of it
+//     biases    float [waves][NT j][64 lanes] = b[n] behind every layer's weights; logstd [12] (+ 4 zeros) at the end
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int AROWS = 16;
 constexpr int ALD = 260;  // LDS row stride (floats)
 __device__ __forceinline__ float elu(float x) { return x > 0.f ? x : expm1f(x); }
 
-// A layer = its weight fetch (straight from L2 into registers, nothing of it depends on the activations) and its MFMAs.  The two are separate calls so that
-// the kernel can issue layer L + 1's fetch BEFORE it computes layer L: with fetch and MFMAs back to back per tile (the first form of this kernel) a
-// workgroup spent ~1 us of exposed L2 latency per tile, 9 tiles per wave, in a launch of 15 us that the rollout waits for 24 times per iteration.
-// K % 16 == 0, weight rows 16-byte aligned; tiles of 16 neurons, tile = wave + 4 j.
-template <int K, int OUT>
+// A layer = its weight fetch (from the packed copy in L2 into registers, nothing of it depends on the activations) and its MFMAs.  The two are separate
+// calls so that the kernel can issue layer L + 1's fetch BEFORE it computes layer L: with fetch and MFMAs back to back per tile (the first form of this
+// kernel) a workgroup spent ~1 us of exposed L2 latency per tile, 9 tiles per wave.  K % 16 == 0; tiles of 16 neurons, tile = wave + 4 j.
+template <int K, int OUT, int WAVES = 4>
 struct LayerW {
     static constexpr int TILES = (OUT + 15) / 16, NT = (TILES + 3) / 4, G = K / 16;
+    static constexpr int W_FLOATS = WAVES * NT * G * 256, FLOATS = W_FLOATS + WAVES * NT * 64;  // packed: weights, then biases
     float4 b[NT][G];
     float bias[NT];
-    __device__ __forceinline__ void fetch(const float* __restrict__ W, const float* __restrict__ bv, int wave, int lane) {
-        const int r = lane & 15, kg = lane >> 4;
+    __device__ __forceinline__ void fetch(const float* __restrict__ pk, int wave, int lane) {
 #pragma unroll
         for (int j = 0; j < NT; j++) {
-            const int n = (wave + 4 * j) * 16 + r;
-            const bool nv = wave + 4 * j < TILES && n < OUT;
-            const float* wrow = W + (size_t)(nv ? n : 0) * K + 4 * kg;
 #pragma unroll
-            for (int t = 0; t < G; t++) {
-                b[j][t] = *reinterpret_cast<const float4*>(wrow + 16 * t);
-                if (!nv) b[j][t] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            bias[j] = nv ? bv[n] : 0.f;
+            for (int t = 0; t < G; t++) b[j][t] = reinterpret_cast<const float4*>(pk)[((wave * NT + j) * G + t) * 64 + lane];
+            bias[j] = pk[W_FLOATS + (wave * NT + j) * 64 + lane];
         }
     }
+    // packed element e of this layer, from the torch layout
+    static __device__ __forceinline__ float packed(int e, const float* __restrict__ W, const float* __restrict__ bv) {
+        const bool is_w = e < W_FLOATS;
+        if (!is_w) e -= W_FLOATS;
+        const int c = e & 3, lane = is_w ? (e >> 2) & 63 : e & 63, rest = is_w ? e >> 8 : e >> 6;
+        const int t = is_w ? rest % G : 0, wj = is_w ? rest / G : rest, j = wj % NT, wave = wj / NT;
+        const int tile = wave + 4 * j, n = tile * 16 + (lane & 15);
+        if (tile >= TILES || n >= OUT) return 0.f;
+        return is_w ? W[(size_t)n * K + 16 * t + 4 * (lane >> 4) + c] : bv[n];
+    }
+    // tile j of the wave: its MFMAs (bias + the sum over k in the order t, then x y z w of the float4) ...
+    __device__ __forceinline__ f32x4 mfma(const float* in /*LDS [16][ALD]*/, int j, int lane) const {
+        const int r = lane & 15, kg = lane >> 4;
+        f32x4 acc = {bias[j], bias[j], bias[j], bias[j]};
+#pragma unroll
+        for (int t = 0; t < G; t++) {
+            const float4 a = *reinterpret_cast<const float4*>(in + r * ALD + 16 * t + 4 * kg);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b[j][t].x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b[j][t].y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b[j][t].z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b[j][t].w, acc, 0, 0, 0);
+        }
+        return acc;
+    }
+    // ... and its epilogue: the activation and the transposing store into the next layer's input tile
     template <bool ACT>
-    __device__ __forceinline__ void run(const float* in /*LDS [16][ALD]*/, float* out /*LDS [16][ALD]*/, int wave, int lane) const {
+    __device__ __forceinline__ void store(float* out /*LDS [16][ALD]*/, int tile, int lane, f32x4 acc) const {
         const int r = lane & 15, kg = lane >> 4;
 #pragma unroll
-        for (int j = 0; j < NT; j++) {
-            const int tile = wave + 4 * j;
-            if (tile >= TILES) break;
-            f32x4 acc = {bias[j], bias[j], bias[j], bias[j]};
-#pragma unroll
-            for (int t = 0; t < G; t++) {
-                const float4 a = *reinterpret_cast<const float4*>(in + r * ALD + 16 * t + 4 * kg);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b[j][t].x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b[j][t].y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b[j][t].z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b[j][t].w, acc, 0, 0, 0);
-            }
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const float v = ACT ? elu(acc[q]) : acc[q];
-                out[(kg * 4 + q) * ALD + tile * 16 + r] = v;
-            }
-        }
+        for (int q = 0; q < 4; q++) out[(kg * 4 + q) * ALD + tile * 16 + r] = ACT ? elu(acc[q]) : acc[q];
     }
 };
 
-// first layer: K = 47 (rows not 16-byte aligned, K not a multiple of 4): scalar operand loads, k padded to 48 with zeros
+// first layer: K = 47, padded to 48 with a zero column in the packed copy; MFMA step s2 takes column 4 s2 + (lane >> 4)
 template <int K, int OUT>
 struct FirstLayerW {
-    static constexpr int TILES = OUT / 16, NT = TILES / 4, STEPS = (K + 3) / 4;
+    static constexpr int TILES = OUT / 16, NT = TILES / 4, STEPS = (K + 3) / 4, Q = STEPS / 4;
+    static constexpr int W_FLOATS = 4 * NT * Q * 256, FLOATS = W_FLOATS + 4 * NT * 64;
+    static_assert(STEPS % 4 == 0, "the packed first layer holds whole float4s of MFMA steps");
     float b[NT][STEPS];
     float bias[NT];
-    __device__ __forceinline__ void fetch(const float* __restrict__ W, const float* __restrict__ bv, int wave, int lane) {
-        const int r = lane & 15, kg = lane >> 4;
+    __device__ __forceinline__ void fetch(const float* __restrict__ pk, int wave, int lane) {
 #pragma unroll
         for (int j = 0; j < NT; j++) {
-            const int n = (wave + 4 * j) * 16 + r;
 #pragma unroll
-            for (int s2 = 0; s2 < STEPS; s2++) { const int k = 4 * s2 + kg; b[j][s2] = k < K ? W[(size_t)n * K + k] : 0.f; }
-            bias[j] = bv[n];
+            for (int q = 0; q < Q; q++) {
+                const float4 v = reinterpret_cast<const float4*>(pk)[((wave * NT + j) * Q + q) * 64 + lane];
+                b[j][4 * q] = v.x; b[j][4 * q + 1] = v.y; b[j][4 * q + 2] = v.z; b[j][4 * q + 3] = v.w;
+            }
+            bias[j] = pk[W_FLOATS + (wave * NT + j) * 64 + lane];
         }
     }
-    __device__ __forceinline__ void run(const float* in, float* out, int wave, int lane) const {
+    static __device__ __forceinline__ float packed(int e, const float* __restrict__ W, const float* __restrict__ bv) {
+        const bool is_w = e < W_FLOATS;
+        if (!is_w) e -= W_FLOATS;
+        const int c = e & 3, lane = is_w ? (e >> 2) & 63 : e & 63, rest = is_w ? e >> 8 : e >> 6;
+        const int q = is_w ? rest % Q : 0, wj = is_w ? rest / Q : rest, j = wj % NT, wave = wj / NT;
+        const int n = (wave + 4 * j) * 16 + (lane & 15), k = 4 * (4 * q + c) + (lane >> 4);
+        return is_w ? (k < K ? W[(size_t)n * K + k] : 0.f) : bv[n];
+    }
+    __device__ __forceinline__ f32x4 mfma(const float* in, int j, int lane) const {
+        const int r = lane & 15, kg = lane >> 4;
+        f32x4 acc = {bias[j], bias[j], bias[j], bias[j]};
+#pragma unroll
+        for (int s2 = 0; s2 < STEPS; s2++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(in[r * ALD + 4 * s2 + kg], b[j][s2], acc, 0, 0, 0);
+        return acc;
+    }
+    template <bool ACT>
+    __device__ __forceinline__ void store(float* out, int tile, int lane, f32x4 acc) const {
         const int r = lane & 15, kg = lane >> 4;
 #pragma unroll
-        for (int j = 0; j < NT; j++) {
-            const int tile = wave + 4 * j;
-            f32x4 acc = {bias[j], bias[j], bias[j], bias[j]};
-#pragma unroll
-            for (int s2 = 0; s2 < STEPS; s2++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(in[r * ALD + 4 * s2 + kg], b[j][s2], acc, 0, 0, 0);
-#pragma unroll
-            for (int q = 0; q < 4; q++) out[(kg * 4 + q) * ALD + tile * 16 + r] = elu(acc[q]);
-        }
+        for (int q = 0; q < 4; q++) out[(kg * 4 + q) * ALD + tile * 16 + r] = ACT ? elu(acc[q]) : acc[q];
     }
 };
 
-__global__ __launch_bounds__(256) void actor_sample_kernel(int N, const float* __restrict__ obs, const float* __restrict__ w0,
-                                                           const float* __restrict__ b0, const float* __restrict__ w1,
-                                                           const float* __restrict__ b1, const float* __restrict__ w2,
-                                                           const float* __restrict__ b2, const float* __restrict__ w3,
-                                                           const float* __restrict__ b3, const float* __restrict__ logstd, uint64_t seed,
+using ActorL0 = FirstLayerW<BG_NUM_OBS, 256>;
+using ActorL1 = LayerW<256, 128>;
+using ActorL2 = LayerW<128, 128>;
+using ActorL3 = LayerW<128, BG_NUM_DOFS, 1>;  // one tile: wave 0's
+constexpr int PK_L0 = 0, PK_L1 = PK_L0 + ActorL0::FLOATS, PK_L2 = PK_L1 + ActorL1::FLOATS, PK_L3 = PK_L2 + ActorL2::FLOATS, PK_LOGSTD = PK_L3 + ActorL3::FLOATS;
+static_assert(PK_LOGSTD + 16 == BG_ACTOR_PACKED_FLOATS, "BG_ACTOR_PACKED_FLOATS (booster_gym_amd.h) is the packed layout's size");
+
+__global__ __launch_bounds__(256) void actor_pack_kernel(const float* __restrict__ w0, const float* __restrict__ b0, const float* __restrict__ w1,
+                                                         const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2,
+                                                         const float* __restrict__ w3, const float* __restrict__ b3, const float* __restrict__ logstd,
+                                                         float* __restrict__ packed) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= BG_ACTOR_PACKED_FLOATS) return;
+    float v;
+    if (e < PK_L1) v = ActorL0::packed(e - PK_L0, w0, b0);
+    else if (e < PK_L2) v = ActorL1::packed(e - PK_L1, w1, b1);
+    else if (e < PK_L3) v = ActorL2::packed(e - PK_L2, w2, b2);
+    else if (e < PK_LOGSTD) v = ActorL3::packed(e - PK_L3, w3, b3);
+    else v = e - PK_LOGSTD < BG_NUM_DOFS ? logstd[e - PK_LOGSTD] : 0.f;
+    packed[e] = v;
+}
+
+// clock stamps of actor_sample_kernel, [workgroup][wave][stamp]: tools/actor_sample_stamps.py names the slots
+BG_STAMP_BUFFER(bg_actor_stamp_buf, bg_probe_read_actor_stamps, 256, 32)
+// one layer: the wave's tiles wave, wave + 4, ...; stamp S + 2 j behind tile j's MFMAs, S + 2 j + 1 behind its epilogue
+#define ACTOR_LAYER(L, ACT, IN, OUT, S)                                  \
+    _Pragma("unroll") for (int j = 0; j < L.NT; j++) {                   \
+        if (wave + 4 * j >= L.TILES) break;                              \
+        const f32x4 acc = L.mfma(IN, j, lane);                           \
+        BG_STAMP_FENCED((S) + 2 * j);                                    \
+        L.template store<ACT>(OUT, wave + 4 * j, lane, acc);             \
+        BG_STAMP_FENCED((S) + 2 * j + 1);                                \
+    }
+
+__global__ __launch_bounds__(256) void actor_sample_kernel(int N, const float* __restrict__ obs, const float* __restrict__ packed, uint64_t seed,
                                                            uint32_t counter, float* __restrict__ mu_out, float* __restrict__ act_out) {
     __shared__ __attribute__((aligned(16))) float bufA[AROWS * ALD];
     __shared__ __attribute__((aligned(16))) float bufB[AROWS * ALD];
     const int r0 = blockIdx.x * AROWS, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    FirstLayerW<BG_NUM_OBS, 256> l0;
-    l0.fetch(w0, b0, wave, lane);
-    LayerW<256, 128> l1;
-    l1.fetch(w1, b1, wave, lane);
-    for (int k = threadIdx.x; k < AROWS * 48; k += blockDim.x) {  // obs tile, k padded 47 -> 48 with zeros
-        const int r = k / 48, c = k % 48;
-        bufA[r * ALD + c] = (r0 + r < N && c < BG_NUM_OBS) ? obs[(size_t)(r0 + r) * BG_NUM_OBS + c] : 0.f;
+    BG_STAMP_LOCALS(32);
+    BG_STAMP_WALL(30);
+    BG_STAMP_FENCED(0);
+    // every global load that does not depend on the network goes out first, in the order it is needed (the waits count loads oldest first): the sampling
+    // threads' log-stds (one thread per (row, group of 4 actions)), the observation tile (k padded 47 -> 48 with zeros; rows from N on are never read),
+    // then the weights of the first two layers
+    const int sr = threadIdx.x / 3, sg = threadIdx.x % 3, srow = r0 + sr;
+    const bool sampler = threadIdx.x < AROWS * 3 && srow < N;
+    const float4 ls = reinterpret_cast<const float4*>(packed + PK_LOGSTD)[sg];  // (every thread: sg < 3, no branch in front of the loads below)
+    constexpr int OBS_PER_THREAD = AROWS * 48 / 256;
+    float ov[OBS_PER_THREAD];
+#pragma unroll
+    for (int i = 0; i < OBS_PER_THREAD; i++) {
+        const int k = threadIdx.x + 256 * i, r = k / 48, c = k % 48;
+        ov[i] = (r0 + r < N && c < BG_NUM_OBS) ? obs[(size_t)(r0 + r) * BG_NUM_OBS + c] : 0.f;
     }
+    ActorL0 l0;
+    l0.fetch(packed + PK_L0, wave, lane);
+    ActorL1 l1;
+    l1.fetch(packed + PK_L1, wave, lane);
+    __builtin_amdgcn_sched_barrier(0);  // (the scheduler would otherwise put the exponentials, and with them a wait for the log-stds, in front of the loads)
+    BG_STAMP_FENCED(1);
+    // the sample's noise and standard deviations, under the latency of those loads, held until the tail
+    bg::Rand4 rn = {};
+    float sigma[4] = {};
+    if (sampler) {
+        rn = bg::rand4(seed, (uint32_t)srow, counter, bg::RS_ACTOR + sg);
+        sigma[0] = expf(ls.x); sigma[1] = expf(ls.y); sigma[2] = expf(ls.z); sigma[3] = expf(ls.w);
+    }
+#pragma unroll
+    for (int i = 0; i < OBS_PER_THREAD; i++) {
+        const int k = threadIdx.x + 256 * i;
+        bufA[(k / 48) * ALD + k % 48] = ov[i];
+    }
+    BG_STAMP_FENCED(2);
     __syncthreads();
+    BG_STAMP_FENCED(3);
     // same arithmetic and order as one fetch + MFMA pass per layer; only WHEN the weights are fetched differs: a layer ahead
-    l0.run(bufA, bufB, wave, lane);
-    LayerW<128, 128> l2;
-    l2.fetch(w2, b2, wave, lane);
+    ACTOR_LAYER(l0, true, bufA, bufB, 4)
+    ActorL2 l2;
+    l2.fetch(packed + PK_L2, wave, lane);
+    BG_STAMP_FENCED(12);
     __syncthreads();
-    l1.template run<true>(bufB, bufA, wave, lane);
-    LayerW<128, BG_NUM_DOFS> l3;
-    l3.fetch(w3, b3, wave, lane);
+    BG_STAMP_FENCED(13);
+    ACTOR_LAYER(l1, true, bufB, bufA, 14)
+    ActorL3 l3;
+    if (wave == 0) l3.fetch(packed + PK_L3, 0, lane);
+    BG_STAMP_FENCED(18);
     __syncthreads();
-    l2.template run<true>(bufA, bufB, wave, lane);
+    BG_STAMP_FENCED(19);
+    ACTOR_LAYER(l2, true, bufA, bufB, 20)
+    BG_STAMP_FENCED(24);
     __syncthreads();
-    l3.template run<false>(bufB, bufA, wave, lane);
+    BG_STAMP_FENCED(25);
+    ACTOR_LAYER(l3, false, bufB, bufA, 26)
     __syncthreads();
-    // sample: one thread per (row, group of 4 actions)
-    if (threadIdx.x < AROWS * 3) {
-        const int r = threadIdx.x / 3, g = threadIdx.x % 3, row = r0 + r;
-        if (row < N) {
-            bg::Rand4 rn = bg::rand4(seed, (uint32_t)row, counter, bg::RS_ACTOR + g);
-            for (int k = 0; k < 4; k++) {
-                const int a = g * 4 + k;
-                const float m = bufA[r * ALD + a];
-                if (mu_out) mu_out[(size_t)row * BG_NUM_DOFS + a] = m;
-                act_out[(size_t)row * BG_NUM_DOFS + a] = m + expf(logstd[a]) * rn.n[k];
-            }
+    BG_STAMP_FENCED(28);
+    // sample: the mean from the output tile, one add and the stores
+    if (sampler) {
+        for (int k = 0; k < 4; k++) {
+            const int a = sg * 4 + k;
+            const float m = bufA[sr * ALD + a];
+            if (mu_out) mu_out[(size_t)srow * BG_NUM_DOFS + a] = m;
+            act_out[(size_t)srow * BG_NUM_DOFS + a] = m + sigma[k] * rn.n[k];
         }
     }
+    BG_STAMP_FENCED(29);
+    BG_STAMP_WALL(31);
+    BG_STAMP_FLUSH(bg_actor_stamp_buf, 32, blockIdx.x < 256, blockIdx.x);
 }
+#undef ACTOR_LAYER
 
 // ------------------------------------------------------------------ clip_grad_norm_ + Adam on a flat buffer
 __global__ __launch_bounds__(256) void sqnorm_kernel(int n, const float* __restrict__ g, double* __restrict__ out) {
@@ -542,14 +630,22 @@ extern "C" int bg_gaussian_logp(int32_t B, int32_t A, const float* mu, const flo
     return 0;
 }
 
-extern "C" int bg_actor_sample(int32_t N, const float* obs, const float* w0, const float* b0, const float* w1, const float* b1, const float* w2,
-                               const float* b2, const float* w3, const float* b3, const float* logstd, uint64_t seed, uint64_t counter, float* mu,
-                               float* actions, void* stream) {
-    if (N <= 0 || !obs || !w0 || !b0 || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !logstd || !actions)
-        return bg_set_error(-1, "bg_actor_sample: bad argument");
-    if (((uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)w3) & 15) return bg_set_error(-1, "bg_actor_sample: weight matrices must be 16-byte aligned");
-    hipLaunchKernelGGL(actor_sample_kernel, dim3((N + AROWS - 1) / AROWS), dim3(256), 0, (hipStream_t)stream, N, obs, w0, b0, w1, b1, w2, b2, w3, b3,
-                       logstd, seed, (uint32_t)counter, mu, actions);
+extern "C" int bg_actor_pack(const float* w0, const float* b0, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
+                             const float* b3, const float* logstd, float* packed, void* stream) {
+    if (!w0 || !b0 || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !logstd || !packed) return bg_set_error(-1, "bg_actor_pack: bad argument");
+    if ((uintptr_t)packed & 15) return bg_set_error(-1, "bg_actor_pack: the packed buffer must be 16-byte aligned");
+    hipLaunchKernelGGL(actor_pack_kernel, dim3((BG_ACTOR_PACKED_FLOATS + 255) / 256), dim3(256), 0, (hipStream_t)stream, w0, b0, w1, b1, w2, b2, w3, b3,
+                       logstd, packed);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int bg_actor_sample(int32_t N, const float* obs, const float* packed, uint64_t seed, uint64_t counter, float* mu, float* actions,
+                               void* stream) {
+    if (N <= 0 || !obs || !packed || !actions) return bg_set_error(-1, "bg_actor_sample: bad argument");
+    if ((uintptr_t)packed & 15) return bg_set_error(-1, "bg_actor_sample: the packed weights must be 16-byte aligned");
+    hipLaunchKernelGGL(actor_sample_kernel, dim3((N + AROWS - 1) / AROWS), dim3(256), 0, (hipStream_t)stream, N, obs, packed, seed, (uint32_t)counter, mu,
+                       actions);
     HIP_OK(hipGetLastError());
     return 0;
 }

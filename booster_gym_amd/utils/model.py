@@ -627,6 +627,7 @@ class ActorCritic(torch.nn.Module):
         self.actor = _mlp(num_obs, self.actor_hidden, num_act)
         self.logstd = torch.nn.parameter.Parameter(torch.full((1, num_act), fill_value=-2.0), requires_grad=True)
         self._sample_key, self._sample_layers = None, None
+        self._packed = None  # pack_actor()
 
     def act(self, obs):
         mean = self.actor(obs)
@@ -636,21 +637,44 @@ class ActorCritic(torch.nn.Module):
         return self.critic(torch.cat((obs, privileged_obs), dim=-1)).squeeze(-1)
 
     # ---- fused rollout inference (reference runner.py:109-111: dist = model.act(obs); act = dist.sample())
-    def sample_actions(self, obs, actions_out, seed, counter, mu_out=None, scan=0):
+    def _sample_params(self):
+        lin = [m for m in self.actor if isinstance(m, torch.nn.Linear)]
+        return lin, [t for l in lin for t in (l.weight, l.bias)] + [self.logstd]
+
+    def pack_actor(self):
+        """The actor's parameters as bg_actor_sample reads them (bg_actor_pack: one small launch on the current stream into a buffer this model keeps),
+        or None where the architecture samples through bg_actor_sample_mlp, which reads the parameters themselves.  The packed copy is a snapshot:
+        whoever passes it to sample_actions packs again after anything that may have changed a parameter (the rollout: at its start, every iteration)."""
+        lin, w = self._sample_params()
+        if self.actor_hidden != ACTOR_HIDDEN or lin[0].in_features != _lib.NUM_OBS:
+            return None
+        if not w[0].is_cuda:
+            raise RuntimeError("pack_actor runs a HIP kernel and needs CUDA parameters")
+        for t in w:
+            if not t.is_contiguous():
+                raise RuntimeError("pack_actor needs contiguous parameters")
+        if self._packed is None or self._packed.device != w[0].device:
+            self._packed = torch.empty(_lib.ACTOR_PACKED_FLOATS, dtype=torch.float32, device=w[0].device)
+        _lib.check(_lib.load().bg_actor_pack(*[_lib.ptr(t) for t in w], _lib.ptr(self._packed), _lib.current_stream_ptr()), "bg_actor_pack")
+        return self._packed
+
+    def sample_actions(self, obs, actions_out, seed, counter, mu_out=None, scan=0, packed=None):
         """One launch: the actor's mean and a Gaussian sample around it.  The reference's widths on 47 inputs run bg_actor_sample (its widths built
-        into the kernel), every other architecture, and every actor on a frame stack (47 H inputs, env.frame_stack), bg_actor_sample_mlp (widths from
-        descriptors, the weights read from the parameters themselves); both draw the same noise for the same seed and counter.  scan = P
-        (terrain.actor_heights): the rows end with the height scan's P values behind the 47 H observations (bg_actor_sample_mlp_scan, the same kernel)."""
+        into the kernel) on a packed copy of the parameters: `packed` from pack_actor() where the caller knows that no parameter has changed since
+        (the rollout packs once for its 24 steps), else packed here, one more small launch.  Every other architecture, and every actor on a frame stack
+        (47 H inputs, env.frame_stack), runs bg_actor_sample_mlp (widths from descriptors, the weights read from the parameters themselves); both draw
+        the same noise for the same seed and counter.  scan = P (terrain.actor_heights): the rows end with the height scan's P values behind the 47 H
+        observations (bg_actor_sample_mlp_scan, the same kernel)."""
         if not obs.is_cuda:
             raise RuntimeError("sample_actions runs the fused HIP actor kernel and needs CUDA tensors")
-        a = self.actor
-        lin = [m for m in a if isinstance(m, torch.nn.Linear)]
-        w = [t for l in lin for t in (l.weight, l.bias)] + [self.logstd]
+        lin, w = self._sample_params()
         for t in w + [obs, actions_out]:
             if not t.is_contiguous():
                 raise RuntimeError("sample_actions needs contiguous tensors")
         if self.actor_hidden == ACTOR_HIDDEN and lin[0].in_features == _lib.NUM_OBS:
-            _lib.check(_lib.load().bg_actor_sample(obs.shape[0], _lib.ptr(obs), *[_lib.ptr(t) for t in w], int(seed), int(counter), _lib.ptr(mu_out),
+            if packed is None:
+                packed = self.pack_actor()
+            _lib.check(_lib.load().bg_actor_sample(obs.shape[0], _lib.ptr(obs), _lib.ptr(packed), int(seed), int(counter), _lib.ptr(mu_out),
                                                    _lib.ptr(actions_out), _lib.current_stream_ptr()), "bg_actor_sample")
             return actions_out
         if obs.shape[-1] != lin[0].in_features:  # (the kernel takes the row stride from the first layer's descriptor)

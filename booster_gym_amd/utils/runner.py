@@ -667,14 +667,18 @@ class Runner:
         norm = self.obs_norm
         scan = getattr(self.env, "num_scan_obs", 0)  # terrain.actor_heights: the rows end with the height scan
         with torch.no_grad():
+            # the default actor samples from a packed copy of its parameters: laid out here, once for the T steps and in every rollout (whatever changed
+            # the parameters since the last one -- optimiser, checkpoint, broadcast -- is behind this launch on the stream); None for other architectures
+            packed = self.model.pack_actor()
             for n in range(T):
                 if plan.ahead and n + 1 - start >= g:
                     self._forward_rows(start, n, main)  # rows of steps start .. n: on the side stream, beside this step's launches
                     start = n + 1
                 if norm is None:
-                    self.model.sample_actions(obses[n], buf["actions"][n], seed, self._act_counter, scan=scan)
+                    self.model.sample_actions(obses[n], buf["actions"][n], seed, self._act_counter, scan=scan, packed=packed)
                 else:  # the buffer keeps the raw rows; the actor samples from their normalised copy (one more launch per step: bg_obs_normalize)
-                    self.model.sample_actions(norm.normalize_into(obses[n], self._obs_normed), buf["actions"][n], seed, self._act_counter, scan=scan)
+                    self.model.sample_actions(norm.normalize_into(obses[n], self._obs_normed), buf["actions"][n], seed, self._act_counter, scan=scan,
+                                              packed=packed)
                 self._act_counter += 1
                 self.env.step_to(buf["actions"][n], obses[n + 1], priv[n + 1], buf["rewards"][n], buf["dones"][n], buf["time_outs"][n])
             if plan.ahead:

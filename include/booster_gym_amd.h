@@ -294,12 +294,16 @@ int bg_ppo_loss(int32_t B, int32_t A, const float* mu, const float* logstd, cons
                 double* grad_logstd, double* stats, void* stream);
 /* log-prob of actions under N(mu, exp(logstd)) summed over A (runner.py:123-125) */
 int bg_gaussian_logp(int32_t B, int32_t A, const float* mu, const float* logstd, const float* actions, float* logp, void* stream);
-/* Fused actor inference for the rollout (utils/model.py:29-32 + dist.sample(), runner.py:109-111):
- * 47->256->128->128->12 ELU MLP + Gaussian sample.  weights: w0[256][47] b0[256] w1[128][256] b1 w2[128][128] b2 w3[12][128] b3,
- * logstd[12]; obs [N][47]; out: mu [N][12] (may be NULL), actions [N][12].  Noise from Philox(seed, counter). */
-int bg_actor_sample(int32_t N, const float* obs, const float* w0, const float* b0, const float* w1, const float* b1, const float* w2,
-                    const float* b2, const float* w3, const float* b3, const float* logstd, uint64_t seed, uint64_t counter,
-                    float* mu, float* actions, void* stream);
+/* Fused actor inference for the rollout (utils/model.py:29-32 + dist.sample(), runner.py:109-111): 47->256->128->128->12 ELU MLP + Gaussian sample, in
+ * two entry points.  bg_actor_pack copies the parameters (torch layout: w0[256][47] b0[256] w1[128][256] b1 w2[128][128] b2 w3[12][128] b3, logstd[12])
+ * into `packed`, BG_ACTOR_PACKED_FLOATS floats, 16-byte aligned, in the order the sampling kernel's lanes consume them (layout: csrc/bg_ppo.hip; the
+ * first layer zero-padded from 47 to 48 columns): one small launch.  bg_actor_sample reads ONLY the packed copy: obs [N][47]; out: mu [N][12] (may be
+ * NULL), actions [N][12] = mu + exp(logstd) n, noise from Philox(seed, row, counter, RS_ACTOR + group of 4 actions).  A packed copy is a snapshot: it
+ * does not follow later changes of the parameters; the caller packs again (the rollout does at its start, every iteration). */
+#define BG_ACTOR_PACKED_FLOATS 65616
+int bg_actor_pack(const float* w0, const float* b0, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
+                  const float* logstd, float* packed, void* stream);
+int bg_actor_sample(int32_t N, const float* obs, const float* packed, uint64_t seed, uint64_t counter, float* mu, float* actions, void* stream);
 /* One Linear layer of an MLP for bg_actor_sample_mlp: W [out][in] row-major (torch layout), b [out]. */
 typedef struct bg_mlp_layer_desc {
     const float* W;
