@@ -8,7 +8,8 @@ in training), the teacher labels every visited row with its mean action, and the
             47 H + P) and ONE env launch (bg_env_step_to), outputs written in place as in Runner.rollout();
   update    the prefix columns of the B = T N rows once into the student's zero-padded input, then num_epochs full-batch steps: MLPTrainer's
             hidden layers forward, bg_distill_head (output layer + mean squared error + its backward), backward_hidden, the grouped weight
-            gradients, the fixed-order finishes, FlatAdam.step (global-norm clip + Adam) over the student's actor parameters at a constant rate.
+            gradients, the fixed-order finishes, FlatAdam.step (global-norm clip + Adam) over the student's actor parameters at a constant rate; the step
+            writes none of the trainer's weight copies, so the WeightClock ticks behind it and the next pass rewrites them (model.WeightCopies).
 
 The student checkpoint is what Runner, play.py, export_model.py and tools/play_oracle.py load under the config with terrain.actor_heights: false and
 env.num_observations: 47 H: `actor.*`, `logstd` (fixed at log(student_noise_std)) and an UNTRAINED `critic.*` of that config's shape.
@@ -26,7 +27,7 @@ from .. import _lib
 from ..envs import TASKS
 from .buffer import ExperienceBuffer
 from .config import load_cfg
-from .model import CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, MLPTrainer, check_hidden, hidden_of, plan_network
+from .model import CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, MLPTrainer, WeightClock, check_hidden, hidden_of, plan_network
 from .recorder import Recorder
 from .runner import FlatAdam, hidden_widths, pad_input, wgrad_products
 from .terrain import actor_heights_of
@@ -140,7 +141,8 @@ class Distiller:
         buf.add_buffer("time_outs", (), dtype=torch.bool)
         kin = pad_input(self.student_obs)
         self._student_in = torch.zeros(self.B, kin, device=dev)  # (the padded columns stay zero)
-        self._trainer = tr = MLPTrainer(self.student.actor)
+        self._clock = WeightClock()  # (of the student's actor parameters; one trainer reads it)
+        self._trainer = tr = MLPTrainer(self.student.actor, clock=self._clock)
         widths = (tr.layers[0].in_features,) + tuple(l.out_features for l in tr.layers)
         sw = MLPTrainer
         tr.plan = plan = plan_network(widths, kin, self.B, sw.SPLIT, sw.FUSED, sw.CHAIN, sw.CHAIN_SPLIT, sw.CHAIN_SPLIT_BWD, sw.CHAIN_ALTERNATE, sw.FUSED_WGRAD)
@@ -259,7 +261,6 @@ class Distiller:
         with torch.no_grad():
             self._student_in[:, : self.student_obs].copy_(self.buffer["obses"][: self.T].reshape(B, -1)[:, : self.student_obs])
             for e in range(self.dcfg.num_epochs):
-                tr.mirror_fresh = False  # FlatAdam.step does not write the copies of the weights that the layer kernels read
                 h = tr.forward_hidden(self._student_in)
                 self._stats.zero_()
                 fin, fins = _lib.ReduceProblem(), []
@@ -271,6 +272,7 @@ class Distiller:
                 self._wgrad.run((tr,), self._wgrad_terms, False)
                 reduce_group([fin] + fins)
                 self.optimizer.step()
+                self._clock.tick()
                 self._losses[e : e + 1].copy_(self._stats)
         return self._losses / float(A * B)
 

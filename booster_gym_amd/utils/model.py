@@ -6,12 +6,16 @@ critic (47+14)-256-256-128-1, ELU, state-independent log-std initialised to -2. 
 (`algorithm.actor_hidden` / `algorithm.critic_hidden`, checked by `check_hidden`): 2 to 4 hidden layers of 128, 256 or 512, the last 128 wide;
 the keys keep the `Sequential` numbering (`actor.{0,2,4,6,8}` for four hidden layers).
 The PPO update's GEMMs run on hand-written HIP kernels (MLPTrainer: the chained hidden layers, the grouped weight
-gradients), in the form its NetPlan names; the rollout-time inference + sampling is one fused HIP launch
+gradients), in the form its NetPlan names, on copies of the weights that one object per trainer owns (WeightCopies: padded, transposed, bf16 planes;
+each current exactly when written or stamped at the present value of the parameters' WeightClock); the rollout-time inference + sampling is one fused HIP launch
 (`sample_actions` -> bg_actor_sample at the reference's widths on 47 inputs, bg_actor_sample_mlp at any other supported widths and on a
 frame stack of 47 H inputs).
 """
 import ctypes
-from typing import NamedTuple
+import os
+from contextlib import contextmanager
+from functools import partial
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -157,6 +161,126 @@ class GroupedWeightGrad:
         return (self._arr, len(probs)) if partial else None
 
 
+class WeightClock:
+    """The version of one set of parameters: one integer, shared by every trainer over those parameters (a Runner's whole-batch and mini-batch pairs, a
+    Distiller's trainer) and ticked by whoever changes them -- every optimiser step, Runner.invalidate(), an update() that does not start from the
+    rollout's forward passes.  A weight copy is current exactly when it was written or stamped at the clock's present value (WeightCopies)."""
+    now = 0
+
+    def tick(self):
+        self.now += 1
+
+
+def _write_planes(name, transpose, w, kp, out):
+    """The bf16 planes of w [rows, cols] (its columns zero-padded to kp) or of its transpose into `out`, through the library's writer `name`."""
+    rows, cols = w.shape
+    n, k = (cols, rows) if transpose else (rows, kp)
+    _lib.check(getattr(_lib.load(), name)(n, k, _lib.ptr(w), cols, rows, cols, transpose, _lib.ptr(out), _lib.current_stream_ptr()), name)
+
+
+class CopyKind(NamedTuple):
+    """One kind of copy of a weight matrix W [rows, cols] whose input is zero-padded to kp columns (kp = cols for every layer but the first)."""
+    shape: Callable    # (rows, cols, kp) -> shape of the copy
+    dtype: torch.dtype
+    write: Callable    # (w, kp, out): rewrite `out` from the parameter, on the current stream
+    mirror: Optional[Callable]  # (rows, cols, kp) -> (transpose, ld, pad) of its bg_param_mirror entry; None: the optimiser launch cannot write it
+    read_by: tuple     # (NetPlan field, values): the plans whose kernels read it from an optimiser launch's entry
+
+
+# Every copy of a weight matrix that a layer kernel reads, in the order the bg_param_mirror entries of one layer are listed; the layouts appear here only.
+#   cplanes / cplanes_t  the chained split kernels': the three bf16 planes of W (of W^T), then those of -W (bg_param_mirror.pad: where the second set starts)
+#   w0pad / wt           the fp32 kernels': the zero-padded first layer (the padded columns stay zero) / the transposed hidden layers of the backward
+#   planes / planes_t    the per-layer split kernels': the planes of W / of W^T (bg_mlp_split.hip)
+COPY_KINDS = {
+    "cplanes": CopyKind(lambda r, c, kp: (2 * r * kp * 3,), torch.int16, partial(_write_planes, "bg_mlp_split_weights_pm", 0),
+                        lambda r, c, kp: (2, kp, r * kp * 3), ("fwd", ("chain_split",))),
+    "w0pad": CopyKind(lambda r, c, kp: (r, kp), torch.float32, lambda w, kp, out: out[:, : w.shape[1]].copy_(w),
+                      lambda r, c, kp: (0, kp, 0), ("fwd", ("chain", "layer"))),
+    "cplanes_t": CopyKind(lambda r, c, kp: (2 * c * r * 3,), torch.int16, partial(_write_planes, "bg_mlp_split_weights_pm", 1),
+                          lambda r, c, kp: (3, r, r * c * 3), ("bwd", ("chain_split",))),
+    "wt": CopyKind(lambda r, c, kp: (c, r), torch.float32, lambda w, kp, out: out.copy_(w.t()), lambda r, c, kp: (1, r, 0), ("bwd", ("layer",))),
+    "planes": CopyKind(lambda r, c, kp: (r * kp * 3,), torch.int16, partial(_write_planes, "bg_mlp_split_weights", 0), None, ()),
+    "planes_t": CopyKind(lambda r, c, kp: (c * r * 3,), torch.int16, partial(_write_planes, "bg_mlp_split_weights", 1), None, ()),
+}
+
+
+class WeightCopies:
+    """Every copy of one trainer's weights that its layer kernels read (COPY_KINDS), each with the clock value at which it was last written from the
+    parameter or stamped as written by the optimiser launch.  `tensors`: {(kind, layer): tensor} of the copies that exist.  Without a clock nothing is
+    ever current: every `get` rewrites (a stand-alone trainer)."""
+
+    def __init__(self, layers, clock=None, kin=None):
+        self.layers, self.clock = layers, clock
+        self.reset(kin)
+
+    def reset(self, kin):
+        """Forget every copy; kin: the zero-padded input width of the first layer."""
+        self.kin, self.tensors, self._at, self.listed = kin, {}, {}, []
+
+    def kp(self, i):
+        return self.kin if i == 0 else self.layers[i].weight.shape[1]
+
+    def current(self, kind, i):
+        return self.clock is not None and self._at.get((kind, i)) == self.clock.now
+
+    def _write(self, kind, i):
+        COPY_KINDS[kind].write(self.layers[i].weight, self.kp(i), self.tensors[kind, i])
+        self._at[kind, i] = self.clock and self.clock.now
+
+    def get(self, kind, i):
+        """The copy `kind` of layer i's weight: created (zeroed) on first use, rewritten from the parameter if and only if it is not current."""
+        if (kind, i) not in self.tensors:
+            w, k = self.layers[i].weight, COPY_KINDS[kind]
+            self.tensors[kind, i] = torch.zeros(k.shape(*w.shape, self.kp(i)), dtype=k.dtype, device=w.device)
+        if not self.current(kind, i):
+            self._write(kind, i)
+        return self.tensors[kind, i]
+
+    def rewrite_all(self):
+        """Rewrite every copy that exists from the parameters, current or not, on the current stream."""
+        for kind, i in self.tensors:
+            self._write(kind, i)
+
+    def descriptors(self, flat, plan):
+        """bg_param_mirror entries of the existing copies that the kernels of `plan` read, for the optimiser launch (bg_optimizer_step / bg_update_tail),
+        which then writes them together with the parameters; `stamp()` afterwards.  flat: the optimiser's flat parameter buffer (the weights are views
+        of it).  Remembers what it listed (`listed`); nothing for the "layer_split" and "library" plans, whose kernels read no copy the launch can write."""
+        out, self.listed = [], []
+        for i, l in enumerate(self.layers):
+            off, (rows, cols) = (l.weight.data_ptr() - flat.data_ptr()) // 4, l.weight.shape
+            for kind, k in COPY_KINDS.items():
+                if (kind, i) in self.tensors and k.mirror is not None and getattr(plan, k.read_by[0]) in k.read_by[1]:
+                    out.append(_lib.ParamMirror(off, rows, cols, *k.mirror(rows, cols, self.kp(i)), _lib.ptr(self.tensors[kind, i])))
+                    self.listed.append((kind, i))
+        return out
+
+    def stamp(self):
+        """The optimiser launch has just written the copies `descriptors` listed: they are the parameters of the clock's present value."""
+        self._at.update((key, self.clock and self.clock.now) for key in self.listed)
+
+
+@contextmanager
+def timed(trainers, note, layer=None):
+    """bench.py's probe: where a trainer's `timed_layer` asks for it (any value: the chained launches; `layer`: a per-layer launch it selects), a HIP
+    event pair on the launch stream around the body, appended as (e0, e1) + note(trainer) to `timed_events` of every trainer given -- the same pair
+    on every network of a grouped launch."""
+    sel = lambda t: t is not None and (layer is None or layer == t or (isinstance(t, (tuple, list, set)) and layer in t))
+    if not any(sel(tr.timed_layer) for tr in trainers):
+        yield
+        return
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    yield
+    e1.record()
+    for tr in trainers:
+        tr.timed_events.append((e0, e1) + note(tr))
+
+
+def _backward_note(tr):
+    """`timed`'s note of a backward-data pass: dX = G W of every hidden layer but the first (whose input gradient nobody needs), 2 B C_out C_in flops each."""
+    return (tr._B, 2.0 * tr._B * sum(l.weight.shape[0] * l.weight.shape[1] for l in tr.layers[1:-1]), None, "backward")
+
+
 class MLPTrainer:
     """Hand-scheduled forward / backward of one of the two ELU MLPs for the full-batch PPO update (replaces autograd for
     reference utils/runner.py:132,147,163).  Same arithmetic as torch's Linear/ELU autograd, different schedule, in the form `plan` names (a NetPlan,
@@ -167,6 +291,7 @@ class MLPTrainer:
       * weight gradients: deferred, all hidden layers of both networks in one grouped launch (GroupedWeightGrad);
       * gradients are WRITTEN into the parameters' `.grad` views of the flat Adam buffer (no AccumulateGrad adds, no zero_grad).
     The "library" forms (torch GEMMs + bg_elu_backward_colsum, split-K bmm weight gradients) serve other widths and the tests that compare forms.
+    The kernels read copies of the weights (`copies`, a WeightCopies): every pass takes them through `copies.get`, which rewrites the stale ones.
     """
 
     # Hidden layers with K in {64, 128, 256, 512} and N % 128 == 0 run on the hand-written fused fp32-MFMA layer (bg_mlp.hip: bias + ELU in the GEMM
@@ -177,12 +302,36 @@ class MLPTrainer:
 
     # Opt-in (BG_GEMM_SPLIT=9 or 6): the same layers on the bf16 matrix pipe, every fp32 operand split exactly into three bf16 numbers and all 9
     # (or the 6 largest) cross products accumulated in fp32 (bg_mlp_split.hip).  0 = the fp32 MFMA kernels.
-    SPLIT = int(__import__("os").environ.get("BG_GEMM_SPLIT", "0"))
+    SPLIT = int(os.environ.get("BG_GEMM_SPLIT", "0"))
     # The grouped weight-gradient launch on the bf16 matrix pipe as well (bg_wgrad_split.hip: exact 3-way splits, all 9 products, the sub-ranges of the
     # batch alternating the sign of the accumulation; its error against float64 is 0.84-0.89 of the fp32-MFMA launch's and it is 0.4 ms per iteration
     # faster in the loop: profiles/r06_wgrad_split_*).  BG_WGRAD_SPLIT=0: the fp32-MFMA launch (bg_wgrad.hip).  Applies behind the chained split kernels
     # only (UpdatePlan.wgrad); shapes outside the split kernel's four take the fp32 launch.
-    WGRAD_SPLIT = int(__import__("os").environ.get("BG_WGRAD_SPLIT", "9"))
+    WGRAD_SPLIT = int(os.environ.get("BG_WGRAD_SPLIT", "9"))
+
+    # The forward pass of the three hidden layers as one launch (bg_mlp_chain_forward) where the widths are the reference's (CHAIN = False: one launch
+    # per layer)
+    CHAIN = True
+
+    # ... and that launch on the bf16 matrix pipe with fp32 semantics (bg_mlp_chain_split.hip: every fp32 operand the exact sum of three bf16 numbers, all
+    # 9 cross products accumulated in fp32 -- 9 x 32 cycles per 32 x 32 x 16 block against 8 x 64 on the fp32 pipe, error against float64 at or below the
+    # fp32-MFMA chain's).  The default; BG_CHAIN_SPLIT=0 (or CHAIN_SPLIT = False) runs the fp32-MFMA chain (bg_mlp_chain.hip).
+    CHAIN_SPLIT = os.environ.get("BG_CHAIN_SPLIT", "1") == "1"
+    # ... and the backward-data pass of the hidden layers as one launch of the same arithmetic (bg_mlp_chain_split_bwd.hip); BG_CHAIN_SPLIT_BWD=0: one
+    # fp32-MFMA launch per layer (bg_mlp_layer_backward)
+    CHAIN_SPLIT_BWD = os.environ.get("BG_CHAIN_SPLIT_BWD", "1") == "1"
+    # Odd 128-row slabs of the chained split kernels accumulate the NEGATED sums (planes of -W beside the planes of W) and put the sign back where a tile
+    # is finished: the bf16 MFMA's accumulator does not round to nearest, every accumulated element carries a small bias of one sign, and what is summed
+    # over the rows downstream (bias gradients, weight gradients) would collect it; alternating makes it cancel.  BG_CHAIN_ALTERNATE=0: off.
+    CHAIN_ALTERNATE = os.environ.get("BG_CHAIN_ALTERNATE", "1") == "1"
+
+    # Weight gradients (the dW part of loss.backward(), runner.py:163): hand-written fp32-MFMA kernel, ALL hidden layers of both networks in one
+    # launch pair after both backward chains (bg_mlp_weight_grad_group, GroupedWeightGrad).  Measured on MI355X, round 2
+    # (tools/archive/ab_defer.sh, update phase per iteration): library split-K bmm + sum inside the chains 24.13 ms; the hand-written kernel one layer at a
+    # time inside the chains 26.46 ms (its 512-register, 128 KB-LDS workgroups cannot share a CU with the other stream's kernels); the library
+    # path deferred 24.39 ms; the grouped hand-written launch 23.01 ms = 3.77 M env-steps/s against 3.61 M.  FUSED_WGRAD = False selects the library path.
+    FUSED_WGRAD = True
+    WGRAD_WORKGROUPS = 256  # one 4-wave workgroup per CU
 
     @staticmethod
     def _fusable(k_in, n_out):
@@ -194,182 +343,8 @@ class MLPTrainer:
         """Shapes of the per-layer backward-data kernels (bg_mlp_layer_backward*); other layers take torch.mm + bg_elu_backward_colsum."""
         return c_out in (128, 256, 512) and c_in % 128 == 0
 
-    # The forward pass of the three hidden layers as one launch (bg_mlp_chain_forward) where the widths are the reference's (CHAIN = False: one launch
-    # per layer)
-    CHAIN = True
-
-    # ... and that launch on the bf16 matrix pipe with fp32 semantics (bg_mlp_chain_split.hip: every fp32 operand the exact sum of three bf16 numbers, all
-    # 9 cross products accumulated in fp32 -- 9 x 32 cycles per 32 x 32 x 16 block against 8 x 64 on the fp32 pipe, error against float64 at or below the
-    # fp32-MFMA chain's).  The default; BG_CHAIN_SPLIT=0 (or CHAIN_SPLIT = False) runs the fp32-MFMA chain (bg_mlp_chain.hip).
-    CHAIN_SPLIT = __import__("os").environ.get("BG_CHAIN_SPLIT", "1") == "1"
-    # ... and the backward-data pass of the hidden layers as one launch of the same arithmetic (bg_mlp_chain_split_bwd.hip); BG_CHAIN_SPLIT_BWD=0: one
-    # fp32-MFMA launch per layer (bg_mlp_layer_backward)
-    CHAIN_SPLIT_BWD = __import__("os").environ.get("BG_CHAIN_SPLIT_BWD", "1") == "1"
-    # Odd 128-row slabs of the chained split kernels accumulate the NEGATED sums (planes of -W beside the planes of W) and put the sign back where a tile
-    # is finished: the bf16 MFMA's accumulator does not round to nearest, every accumulated element carries a small bias of one sign, and what is summed
-    # over the rows downstream (bias gradients, weight gradients) would collect it; alternating makes it cancel.  BG_CHAIN_ALTERNATE=0: off.
-    CHAIN_ALTERNATE = __import__("os").environ.get("BG_CHAIN_ALTERNATE", "1") == "1"
-
-    def _chain_split(self):
-        return self.plan.fwd == "chain_split"
-
-    def _fresh_planes(self):
-        """The bf16 planes of the three hidden layers' weights (what the chained split kernel reads): created on first use; rewritten from the
-        parameters unless the optimiser launch keeps them current (mirror_fresh)."""
-        ls, lib, stream = self.layers, _lib.load(), _lib.current_stream_ptr()
-        new = self.cplanes[0] is None
-        for i in range(3):
-            n_out, k_in = ls[i].weight.shape
-            kp = self._kin if i == 0 else k_in
-            if new:  # (the planes of W, then the planes of -W)
-                self.cplanes[i] = torch.zeros(2 * n_out * kp * 3, dtype=torch.int16, device=ls[i].weight.device)
-            if new or not self.mirror_fresh:
-                _lib.check(lib.bg_mlp_split_weights_pm(n_out, kp, _lib.ptr(ls[i].weight), k_in, n_out, k_in, 0, _lib.ptr(self.cplanes[i]), stream), "bg_mlp_split_weights_pm")
-        return self.cplanes
-
-    def _chain_split_bwd(self):
-        """Does backward_hidden run as ONE launch on the bf16 matrix pipe (bg_mlp_chain_split_bwd.hip)?  Same widths as the chained forward."""
-        return self.plan.bwd == "chain_split"
-
-    def _fresh_planes_t(self):
-        """The bf16 planes of the transposed weights of hidden layers 2 and 1 (what the chained backward kernel reads), as _fresh_planes."""
-        ls, lib, stream = self.layers, _lib.load(), _lib.current_stream_ptr()
-        new = self.cplanes_t[1] is None
-        for i in (1, 2):
-            c_out, c_in = ls[i].weight.shape
-            if new:
-                self.cplanes_t[i] = torch.zeros(2 * c_in * c_out * 3, dtype=torch.int16, device=ls[i].weight.device)
-            if new or not self.mirror_fresh:
-                _lib.check(lib.bg_mlp_split_weights_pm(c_in, c_out, _lib.ptr(ls[i].weight), c_in, c_out, c_in, 1, _lib.ptr(self.cplanes_t[i]), stream), "bg_mlp_split_weights_pm")
-        return self.cplanes_t
-
-    def chain_backward_descriptor(self, g=None):
-        """bg_mlp_chain_split_bwd of this network's backward-data pass from g = dL/dz of the last hidden layer (default: hidden_grad)."""
-        ls, B, p = self.layers, self._B, _lib.ptr
-        g = self.hidden_grad if g is None else g
-        PT = self._fresh_planes_t()
-        n1, n2, n3 = ls[0].weight.shape[0], ls[1].weight.shape[0], ls[2].weight.shape[0]
-        slabs = (B + 127) // 128
-        if self.chain_colsum is None or self.chain_colsum.numel() < slabs * 4 * (n1 + n2):  # one record of column sums per (slab, wave)
-            self.chain_colsum = torch.empty(slabs * 4 * (n1 + n2), dtype=torch.float32, device=g.device)
-        self._pending_wgrad = [(2, g), (1, self.gin[2]), (0, self.gin[1])]
-        return _lib.MlpChainSplitBwd(B, n1, n2, n3, int(self.chain_bwd_workgroups), int(self.plan.alternate), p(g), p(PT[2]), p(PT[1]), p(self.acts[1]), p(self.acts[0]), p(self.gin[2]),
-                                     p(self.gin[1]), p(self.chain_colsum), p(ls[1].bias.grad), p(ls[0].bias.grad))
-
-    def _chain_descriptor(self):
-        """bg_mlp_chain of this network's hidden layers on the input of the forward pass in progress (self.x)."""
-        ls = self.layers
-        p = _lib.ptr
-        vw, vb, vo = self.value_head if self.value_head is not None else (None, None, None)
-        if vo is not None and (vo.numel() < self.x.shape[0] or vw.numel() != ls[2].weight.shape[0]):
-            raise ValueError("value_head: weight [width of the last hidden layer], bias [1], output [rows]")
-        if self._chain_split():
-            P = self._fresh_planes()
-            return _lib.MlpChainSplit(self.x.shape[0], self._kin, ls[0].weight.shape[0], ls[1].weight.shape[0], ls[2].weight.shape[0], int(self.chain_workgroups),
-                                      int(self.plan.alternate), 0, p(self.x), p(P[0]), p(P[1]), p(P[2]), p(ls[0].bias), p(ls[1].bias), p(ls[2].bias), p(self.acts[0]), p(self.acts[1]),
-                                      p(self.acts[2]), p(vw), p(vb), p(vo))
-        if not self.mirror_fresh:
-            self.w0pad[:, : ls[0].weight.shape[1]].copy_(ls[0].weight)
-        return _lib.MlpChain(self.x.shape[0], self._kin, ls[0].weight.shape[0], ls[1].weight.shape[0], ls[2].weight.shape[0], int(self.chain_workgroups), p(self.x),
-                             p(self.w0pad),
-                             p(ls[0].bias), p(ls[1].weight), p(ls[1].bias), p(ls[2].weight), p(ls[2].bias), p(self.acts[0]), p(self.acts[1]), p(self.acts[2]),
-                             p(vw), p(vb), p(vo))
-
-    def prepare(self, x, train_rows=None):
-        """Workspaces for a forward pass on x (first `train_rows` rows = the batch the backward pass differentiates) without running it."""
-        B = x.shape[0] if train_rows is None else train_rows
-        if self._B != B or self._rows != x.shape[0] or self._kin != x.shape[1]:
-            self._alloc(x.shape[0], B, x.device, x.shape[1])
-        self.x = x
-
-    def refresh_mirrors(self):
-        """Rewrite the copies of the weights that the layer kernels read (zero-padded first layer, transposed hidden layers) from the parameters, on
-        the current stream.  The optimiser launch keeps them current; this covers weights changed by other means (checkpoint, broadcast, a test)."""
-        ls = self.layers
-        if self.w0pad is not None:
-            self.w0pad[:, : ls[0].weight.shape[1]].copy_(ls[0].weight)
-        for i, w in enumerate(self.wt):
-            if w is not None:
-                w.copy_(ls[i].weight.t())
-        if self.cplanes[0] is not None or self.cplanes_t[1] is not None:
-            self.mirror_fresh = False
-            if self.cplanes[0] is not None:
-                self._fresh_planes()
-            if self.cplanes_t[1] is not None:
-                self._fresh_planes_t()
-        self.mirror_fresh = True
-
-    def chain_rows_descriptor(self, row0, nrows):
-        """bg_mlp_chain of rows [row0, row0 + nrows) of the pass prepared by `prepare` (whole 128-row slabs: the kernel stores every slab in full):
-        the same launch the full-batch forward makes, restricted to these slabs -- bit-identical outputs in the same places of the activation buffers
-        (and of the value head's output).  Used by the rollout, which evaluates each step's rows as soon as the simulator has produced them."""
-        if row0 % 128 or nrows % 128 or row0 + nrows > self.x.shape[0]:
-            raise ValueError("chain_rows_descriptor: row0 and nrows must be multiples of 128 inside the prepared batch")
-        d = self._chain_descriptor()
-        d.M = nrows
-        d.workgroups = 0  # (a few slabs during the rollout: one workgroup each)
-        d.X = d.X + 4 * row0 * self._kin
-        ls = self.layers
-        d.Y1, d.Y2, d.Y3 = (y + 4 * row0 * l.weight.shape[0] for y, l in zip((d.Y1, d.Y2, d.Y3), ls[:3]))
-        if d.v_out:
-            d.v_out = d.v_out + 4 * row0
-        return d
-
-    @staticmethod
-    def forward_hidden_group(jobs):
-        """jobs = [(trainer, x, train_rows), ...] (at most 4, all on the chained split kernel): `forward_hidden` of every job in ONE launch -- the
-        networks share the chip by their `chain_workgroups` inside one grid instead of as launches on several streams.  Same kernel code per network,
-        same slabs, same order of the sums: bit-identical to the separate launches.  Returns the last hidden activations of every job."""
-        descs = []
-        for tr, x, train_rows in jobs:
-            tr.prepare(x, train_rows)
-            if not tr._chain_split():
-                raise ValueError("forward_hidden_group: every network must run the chained split kernel")
-            descs.append(tr._chain_descriptor())
-        timed = any(tr.timed_layer is not None for tr, _, _ in jobs)
-        if timed:  # bench.py: HIP events on the launch stream around this one kernel (the same pair is noted for every network of the launch)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        MLPTrainer.launch_chain(descs)
-        if timed:
-            e1.record()
-            for tr, x, _ in jobs:
-                tr.timed_events.append((e0, e1, x.shape[0], tr._kin, tuple(l.weight.shape[0] for l in tr.layers[:3]), "chain_split"))
-        return [tr.acts[2] for tr, _, _ in jobs]
-
-    @staticmethod
-    def backward_hidden_group(trainers, finishes):
-        """`backward_hidden(finishes=finishes)` of every trainer (at most 4, all on the chained split backward kernel) in ONE launch; appends one
-        reduction descriptor per trainer, in the order given."""
-        if not all(tr._chain_split_bwd() for tr in trainers):
-            raise ValueError("backward_hidden_group: every network must run the chained split backward kernel")
-        timed = any(tr.timed_layer is not None for tr in trainers)
-        if timed:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        ds = [tr.chain_backward_descriptor() for tr in trainers]
-        arr = (_lib.MlpChainSplitBwd * len(ds))(*ds)
-        fins = (_lib.ReduceProblem * len(ds))()
-        _lib.check(_lib.load().bg_mlp_chain_backward_split(ctypes.addressof(arr), len(ds), fins, _lib.current_stream_ptr()), "bg_mlp_chain_backward_split")
-        finishes.extend(fins[k] for k in range(len(ds)))
-        if timed:
-            e1.record()
-            for tr in trainers:
-                fl = 2.0 * tr._B * sum(l.weight.shape[0] * l.weight.shape[1] for l in tr.layers[1:-1])
-                tr.timed_events.append((e0, e1, tr._B, fl, None, "backward"))
-
-    @staticmethod
-    def launch_chain(descs):
-        """One launch for a list of chain descriptors of one kind (all bg_mlp_chain or all bg_mlp_chain_split); a mixed list runs as two launches."""
-        lib, st = _lib.load(), _lib.current_stream_ptr()
-        for kind, fn, name in ((_lib.MlpChainSplit, lib.bg_mlp_chain_forward_split, "bg_mlp_chain_forward_split"),
-                               (_lib.MlpChain, lib.bg_mlp_chain_forward_group, "bg_mlp_chain_forward_group")):
-            sel = [d for d in descs if isinstance(d, kind)]
-            if sel:
-                arr = (kind * len(sel))(*sel)
-                _lib.check(fn(ctypes.addressof(arr), len(sel), st), name)
-
-    def __init__(self, seq, max_split=32):
+    # ------------------------------------------------------------------ construction and workspaces
+    def __init__(self, seq, max_split=32, clock=None):
         self.layers = [m for m in seq if isinstance(m, torch.nn.Linear)]
         self.max_split = max_split
         self.x = None
@@ -381,6 +356,8 @@ class MLPTrainer:
         # (weight [N3], bias [1], out [rows]): a scalar output layer evaluated by the chained forward kernel itself (the critic's values); None: not
         self.value_head = None
         self.plan = None  # the NetPlan this network's passes follow: set by the runner before each rollout / update
+        # the copies of the weights that the layer kernels read; clock: the WeightClock of whoever steps the optimiser (None: rewritten on every pass)
+        self.copies = WeightCopies(self.layers, clock)
 
     def _split(self, B):
         s = self.max_split
@@ -400,26 +377,100 @@ class MLPTrainer:
         self.gin = [None] + [torch.empty(B_pad, l.weight.shape[1], dtype=torch.float32, device=dev)[:B] for l in self.layers[1:]]
         self.cs = [torch.empty(((B + 127) // 128) * l.weight.shape[0], dtype=torch.float32, device=dev) for l in self.layers]
         self.dw = [None] * len(self.layers)  # slices x dW of the library weight gradients (_weight_grad), created on first use
-        self.wt = [None] * len(self.layers)  # transposed weights for the fused backward kernel
-        # True while w0pad and wt ARE the current weights: the optimiser launch keeps them current (mirror_descriptors); False makes forward /
-        # backward copy them first.  The owner of the optimiser sets it (utils/runner.py) and clears it wherever weights change by other means.
-        self.mirror_fresh = False
-        self.cplanes = [None] * 3  # CHAIN_SPLIT: bf16 planes of the three hidden layers' weights for the chained forward kernel
-        self.cplanes_t = [None] * 3  # ... and of the transposed weights of layers 1 and 2 for the chained backward kernel
-        self.chain_colsum = None     # ... whose waves leave one record of column sums per slab here
-        self.planes = [None] * len(self.layers)  # SPLIT: bf16 planes of the weights (forward) ...
-        self.planes_t = [None] * len(self.layers)  # ... and of the transposed weights (backward)
-        l0 = self.layers[0]
-        self.w0pad = torch.zeros(l0.weight.shape[0], k_in, dtype=torch.float32, device=dev) if k_in != l0.weight.shape[1] else None
-        self.dw0sum = torch.empty(l0.weight.shape[0], k_in, dtype=torch.float32, device=dev) if self.w0pad is not None else None
+        self.copies.reset(k_in)
+        self.chain_colsum = None  # the chained backward kernel's waves leave one record of column sums per slab here
+        l0 = self.layers[0]  # (padded input columns: the library weight gradient of the first layer is summed at the padded width)
+        self.dw0sum = torch.empty(l0.weight.shape[0], k_in, dtype=torch.float32, device=dev) if k_in != l0.weight.shape[1] else None
 
-    # Weight gradients (the dW part of loss.backward(), runner.py:163): hand-written fp32-MFMA kernel, ALL hidden layers of both networks in one
-    # launch pair after both backward chains (bg_mlp_weight_grad_group, GroupedWeightGrad).  Measured on MI355X, round 2
-    # (tools/archive/ab_defer.sh, update phase per iteration): library split-K bmm + sum inside the chains 24.13 ms; the hand-written kernel one layer at a
-    # time inside the chains 26.46 ms (its 512-register, 128 KB-LDS workgroups cannot share a CU with the other stream's kernels); the library
-    # path deferred 24.39 ms; the grouped hand-written launch 23.01 ms = 3.77 M env-steps/s against 3.61 M.  FUSED_WGRAD = False selects the library path.
-    FUSED_WGRAD = True
-    WGRAD_WORKGROUPS = 256  # one 4-wave workgroup per CU
+    def prepare(self, x, train_rows=None):
+        """Workspaces for a forward pass on x (first `train_rows` rows = the batch the backward pass differentiates) without running it."""
+        B = x.shape[0] if train_rows is None else train_rows
+        if self._B != B or self._rows != x.shape[0] or self._kin != x.shape[1]:
+            self._alloc(x.shape[0], B, x.device, x.shape[1])
+        self.x = x
+
+    # ------------------------------------------------------------------ descriptors of the chained launches
+    def _chain_split(self):
+        return self.plan.fwd == "chain_split"
+
+    def _chain_split_bwd(self):
+        """Does backward_hidden run as ONE launch on the bf16 matrix pipe (bg_mlp_chain_split_bwd.hip)?  Same widths as the chained forward."""
+        return self.plan.bwd == "chain_split"
+
+    def _chain_descriptor(self):
+        """bg_mlp_chain of this network's hidden layers on the input of the forward pass in progress (self.x)."""
+        ls, p = self.layers, _lib.ptr
+        vw, vb, vo = self.value_head if self.value_head is not None else (None, None, None)
+        if vo is not None and (vo.numel() < self.x.shape[0] or vw.numel() != ls[2].weight.shape[0]):
+            raise ValueError("value_head: weight [width of the last hidden layer], bias [1], output [rows]")
+        if self._chain_split():
+            P = [self.copies.get("cplanes", i) for i in range(3)]
+            return _lib.MlpChainSplit(self.x.shape[0], self._kin, ls[0].weight.shape[0], ls[1].weight.shape[0], ls[2].weight.shape[0], int(self.chain_workgroups),
+                                      int(self.plan.alternate), 0, p(self.x), p(P[0]), p(P[1]), p(P[2]), p(ls[0].bias), p(ls[1].bias), p(ls[2].bias), p(self.acts[0]), p(self.acts[1]),
+                                      p(self.acts[2]), p(vw), p(vb), p(vo))
+        return _lib.MlpChain(self.x.shape[0], self._kin, ls[0].weight.shape[0], ls[1].weight.shape[0], ls[2].weight.shape[0], int(self.chain_workgroups), p(self.x),
+                             p(self.copies.get("w0pad", 0)), p(ls[0].bias), p(ls[1].weight), p(ls[1].bias), p(ls[2].weight), p(ls[2].bias), p(self.acts[0]),
+                             p(self.acts[1]), p(self.acts[2]), p(vw), p(vb), p(vo))
+
+    def chain_rows_descriptor(self, row0, nrows):
+        """bg_mlp_chain of rows [row0, row0 + nrows) of the pass prepared by `prepare` (whole 128-row slabs: the kernel stores every slab in full):
+        the same launch the full-batch forward makes, restricted to these slabs -- bit-identical outputs in the same places of the activation buffers
+        (and of the value head's output).  Used by the rollout, which evaluates each step's rows as soon as the simulator has produced them."""
+        if row0 % 128 or nrows % 128 or row0 + nrows > self.x.shape[0]:
+            raise ValueError("chain_rows_descriptor: row0 and nrows must be multiples of 128 inside the prepared batch")
+        d = self._chain_descriptor()
+        d.M = nrows
+        d.workgroups = 0  # (a few slabs during the rollout: one workgroup each)
+        d.X = d.X + 4 * row0 * self._kin
+        d.Y1, d.Y2, d.Y3 = (y + 4 * row0 * l.weight.shape[0] for y, l in zip((d.Y1, d.Y2, d.Y3), self.layers[:3]))
+        if d.v_out:
+            d.v_out = d.v_out + 4 * row0
+        return d
+
+    def chain_backward_descriptor(self, g=None):
+        """bg_mlp_chain_split_bwd of this network's backward-data pass from g = dL/dz of the last hidden layer (default: hidden_grad)."""
+        ls, B, p = self.layers, self._B, _lib.ptr
+        g = self.hidden_grad if g is None else g
+        PT1, PT2 = self.copies.get("cplanes_t", 1), self.copies.get("cplanes_t", 2)
+        n1, n2, n3 = ls[0].weight.shape[0], ls[1].weight.shape[0], ls[2].weight.shape[0]
+        slabs = (B + 127) // 128
+        if self.chain_colsum is None or self.chain_colsum.numel() < slabs * 4 * (n1 + n2):  # one record of column sums per (slab, wave)
+            self.chain_colsum = torch.empty(slabs * 4 * (n1 + n2), dtype=torch.float32, device=g.device)
+        self._pending_wgrad = [(2, g), (1, self.gin[2]), (0, self.gin[1])]
+        return _lib.MlpChainSplitBwd(B, n1, n2, n3, int(self.chain_bwd_workgroups), int(self.plan.alternate), p(g), p(PT2), p(PT1), p(self.acts[1]), p(self.acts[0]), p(self.gin[2]),
+                                     p(self.gin[1]), p(self.chain_colsum), p(ls[1].bias.grad), p(ls[0].bias.grad))
+
+    @staticmethod
+    def launch_chain(descs):
+        """One launch for a list of chain descriptors of one kind (all bg_mlp_chain or all bg_mlp_chain_split); a mixed list runs as two launches."""
+        lib, st = _lib.load(), _lib.current_stream_ptr()
+        for kind, fn, name in ((_lib.MlpChainSplit, lib.bg_mlp_chain_forward_split, "bg_mlp_chain_forward_split"),
+                               (_lib.MlpChain, lib.bg_mlp_chain_forward_group, "bg_mlp_chain_forward_group")):
+            sel = [d for d in descs if isinstance(d, kind)]
+            if sel:
+                arr = (kind * len(sel))(*sel)
+                _lib.check(fn(ctypes.addressof(arr), len(sel), st), name)
+
+    # ------------------------------------------------------------------ forward
+    @staticmethod
+    def _chained_forward(trainers):
+        """The chained hidden layers of every (prepared) trainer in ONE launch (bg_mlp_chain.hip / bg_mlp_chain_split.hip: activations handed on in
+        registers, bit-identical to the per-layer launches).  Returns their last hidden activations."""
+        descs = [tr._chain_descriptor() for tr in trainers]
+        with timed(trainers, lambda tr: (tr.x.shape[0], tr._kin, tuple(l.weight.shape[0] for l in tr.layers[:3]), tr.plan.fwd)):
+            MLPTrainer.launch_chain(descs)
+        return [tr.acts[2] for tr in trainers]
+
+    @staticmethod
+    def forward_hidden_group(jobs):
+        """jobs = [(trainer, x, train_rows), ...] (at most 4, all on the chained split kernel): `forward_hidden` of every job in ONE launch -- the
+        networks share the chip by their `chain_workgroups` inside one grid instead of as launches on several streams.  Same kernel code per network,
+        same slabs, same order of the sums: bit-identical to the separate launches.  Returns the last hidden activations of every job."""
+        for tr, x, train_rows in jobs:
+            if not tr._chain_split():
+                raise ValueError("forward_hidden_group: every network must run the chained split kernel")
+            tr.prepare(x, train_rows)
+        return MLPTrainer._chained_forward([tr for tr, _, _ in jobs])
 
     def forward_hidden(self, x, train_rows=None):
         """All layers but the output layer: returns the activations of the last hidden (ELU) layer [rows, width].  The output layer then runs
@@ -429,50 +480,25 @@ class MLPTrainer:
     def forward(self, x, train_rows=None, _stop_before_output=False):
         """x [rows, in (possibly zero-padded)].  The first `train_rows` rows (default: all) are the batch the backward pass differentiates."""
         self.prepare(x, train_rows)
-        h = x
-        last = len(self.layers) - 1
+        h, first, last = x, 0, len(self.layers) - 1
         lib, stream = _lib.load(), _lib.current_stream_ptr()
-        first = 0
-        if self.plan.chained:
-            # the three hidden layers in ONE launch, activations handed on in registers (bg_mlp_chain.hip); bit-identical to the per-layer launches
-            timed = self.timed_layer is not None
-            if timed:  # bench.py: HIP events on the launch stream around this one kernel
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            d = self._chain_descriptor()
-            self.launch_chain([d])
-            if timed:
-                e1.record()
-                self.timed_events.append((e0, e1, x.shape[0], self._kin, tuple(l.weight.shape[0] for l in self.layers[:3]), self.plan.fwd))
-            first, h = 3, self.acts[2]
+        if self.plan.chained:  # the three hidden layers: the grouped launch of one network
+            first, h = 3, self._chained_forward([self])[0]
         for i in range(first, last if _stop_before_output else last + 1):
             l = self.layers[i]
             n_out, k_in = l.weight.shape
-            w = l.weight
-            if self.plan.fwd == "layer_split" and i < last and self._fusable(self._kin if i == 0 else k_in, n_out):
-                kp = self._kin if i == 0 else k_in
-                if self.planes[i] is None:
-                    self.planes[i] = torch.empty(n_out * kp * 3, dtype=torch.int16, device=h.device)
-                _lib.check(lib.bg_mlp_split_weights(n_out, kp, _lib.ptr(l.weight), k_in, n_out, k_in, 0, _lib.ptr(self.planes[i]), stream), "bg_mlp_split_weights")
-                _lib.check(lib.bg_mlp_layer_forward_split(h.shape[0], kp, n_out, _lib.ptr(h), _lib.ptr(self.planes[i]), _lib.ptr(l.bias), _lib.ptr(self.acts[i]),
-                                                          1, self.plan.terms, stream), "bg_mlp_layer_forward_split")
+            kp = self._kin if i == 0 else k_in
+            if self.plan.fwd == "layer_split" and i < last and self._fusable(kp, n_out):
+                _lib.check(lib.bg_mlp_layer_forward_split(h.shape[0], kp, n_out, _lib.ptr(h), _lib.ptr(self.copies.get("planes", i)), _lib.ptr(l.bias),
+                                                          _lib.ptr(self.acts[i]), 1, self.plan.terms, stream), "bg_mlp_layer_forward_split")
                 h = self.acts[i]
                 continue
-            if i == 0 and self.w0pad is not None:
-                if not self.mirror_fresh:
-                    self.w0pad[:, :k_in].copy_(l.weight)  # weights change every optimiser step; 16k floats
-                w, k_in = self.w0pad, self._kin
-            if i < last and self.plan.fwd != "library" and self._fusable(k_in, n_out):
+            w = l.weight if kp == k_in else self.copies.get("w0pad", 0)  # (padded input columns: the zero-padded first layer)
+            if i < last and self.plan.fwd != "library" and self._fusable(kp, n_out):
                 # hand-written fp32-MFMA layer with bias + ELU in the epilogue (bg_mlp.hip)
-                timed = self.timed_layer is not None and (i == self.timed_layer or (isinstance(self.timed_layer, (tuple, list, set)) and i in self.timed_layer))
-                if timed:  # bench.py: HIP events on the launch stream around this one kernel
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                _lib.check(lib.bg_mlp_layer_forward(h.shape[0], k_in, n_out, _lib.ptr(h), _lib.ptr(w), _lib.ptr(l.bias), _lib.ptr(self.acts[i]), 1,
-                                                    stream), "bg_mlp_layer_forward")
-                if timed:
-                    e1.record()
-                    self.timed_events.append((e0, e1, h.shape[0], k_in, n_out, i))
+                with timed([self], lambda tr: (h.shape[0], kp, n_out, i), layer=i):
+                    _lib.check(lib.bg_mlp_layer_forward(h.shape[0], kp, n_out, _lib.ptr(h), _lib.ptr(w), _lib.ptr(l.bias), _lib.ptr(self.acts[i]), 1,
+                                                        stream), "bg_mlp_layer_forward")
                 h = self.acts[i]
                 continue
             torch.addmm(l.bias, h, w.t(), out=self.acts[i])
@@ -481,6 +507,7 @@ class MLPTrainer:
                 torch.nn.functional.elu_(h)
         return h
 
+    # ------------------------------------------------------------------ backward
     def backward(self, grad_out):
         """grad_out [B, out] is consumed (modified in place).  Fills weight.grad / bias.grad of every layer.
 
@@ -496,32 +523,67 @@ class MLPTrainer:
         """[B, width] buffer the fused head kernels write dL/dz of the last hidden layer into (input of `backward_hidden`)."""
         return self.gin[len(self.layers) - 1]
 
+    @staticmethod
+    def backward_hidden_group(trainers, finishes, g=None):
+        """`backward_hidden(finishes=finishes)` of every trainer (at most 4, all on the chained split backward kernel) in ONE launch; appends one
+        reduction descriptor per trainer, in the order given.  g: dL/dz of the last hidden layer of a single trainer (default: each `hidden_grad`)."""
+        if not all(tr._chain_split_bwd() for tr in trainers):
+            raise ValueError("backward_hidden_group: every network must run the chained split backward kernel")
+        with timed(trainers, _backward_note):
+            ds = [tr.chain_backward_descriptor(g) for tr in trainers]
+            arr = (_lib.MlpChainSplitBwd * len(ds))(*ds)
+            fins = (_lib.ReduceProblem * len(ds))()
+            _lib.check(_lib.load().bg_mlp_chain_backward_split(ctypes.addressof(arr), len(ds), fins, _lib.current_stream_ptr()), "bg_mlp_chain_backward_split")
+            finishes.extend(fins[k] for k in range(len(ds)))
+
     def backward_hidden(self, g=None, finishes=None):
         """Backward from the last hidden layer down.  g = dL/dz of that layer (default: `hidden_grad`); its bias gradient and the output
         layer's weight / bias gradients have already been written by the fused head kernel.  finishes (a list): the fused backward layers run
         without their column-sum finish and append its descriptor (_lib.ReduceProblem) instead; the caller runs them later with
         utils.reduce_group (the bias gradients are not needed before the optimiser step)."""
-        timed = self.timed_layer is not None
-        if timed:  # bench.py: HIP events on the launch stream around this network's backward-data chain
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        if self._chain_split_bwd():
-            d = self.chain_backward_descriptor(g)
-            fin = _lib.ReduceProblem()
-            _lib.check(_lib.load().bg_mlp_chain_backward_split(ctypes.addressof(d), 1, fin, _lib.current_stream_ptr()), "bg_mlp_chain_backward_split")
-            if finishes is not None:
-                finishes.append(fin)
-            else:
-                from .utils import reduce_group
-                reduce_group([fin])
-        else:
-            self._backward_from(len(self.layers) - 2, self.hidden_grad if g is None else g, finishes)
-        if timed:
-            e1.record()
-            # dX = G W of every hidden layer but the first (whose input gradient nobody needs): 2 B C_out C_in each
-            fl = 2.0 * self._B * sum(l.weight.shape[0] * l.weight.shape[1] for l in self.layers[1:-1])
-            self.timed_events.append((e0, e1, self._B, fl, None, "backward"))
+        if not self._chain_split_bwd():
+            with timed([self], _backward_note):
+                self._backward_from(len(self.layers) - 2, self.hidden_grad if g is None else g, finishes)
+            return
+        fins = [] if finishes is None else finishes
+        self.backward_hidden_group([self], fins, g)  # the grouped launch of one network
+        if finishes is None:
+            from .utils import reduce_group
+            reduce_group(fins)
 
+    def _backward_from(self, start, g, finishes=None):
+        lib, B, stream = _lib.load(), self._B, _lib.current_stream_ptr()
+        self._pending_wgrad = []
+        for i in range(start, -1, -1):
+            l = self.layers[i]
+            a_in = (self.acts[i - 1] if i > 0 else self.x)[:B]
+            C_out, C_in = l.weight.shape
+            self._pending_wgrad.append((i, g))
+            if i > 0:
+                below = self.layers[i - 1]
+                fusable = self.bwd_fusable(C_out, C_in)
+                if fusable and self.plan.bwd == "layer_split":
+                    _lib.check(lib.bg_mlp_layer_backward_split(B, C_out, C_in, _lib.ptr(g), _lib.ptr(self.copies.get("planes_t", i)), _lib.ptr(a_in), _lib.ptr(self.gin[i]),
+                                                               _lib.ptr(below.bias.grad), _lib.ptr(self.cs[i - 1]), self.plan.terms, stream),
+                               "bg_mlp_layer_backward_split")
+                elif fusable and self.plan.bwd == "layer":
+                    wt = self.copies.get("wt", i)
+                    if finishes is not None:
+                        fin = _lib.ReduceProblem()
+                        _lib.check(lib.bg_mlp_layer_backward_partial(B, C_out, C_in, _lib.ptr(g), _lib.ptr(wt), _lib.ptr(a_in), _lib.ptr(self.gin[i]),
+                                                                     _lib.ptr(below.bias.grad), _lib.ptr(self.cs[i - 1]), fin, stream),
+                                   "bg_mlp_layer_backward_partial")
+                        finishes.append(fin)
+                    else:
+                        _lib.check(lib.bg_mlp_layer_backward(B, C_out, C_in, _lib.ptr(g), _lib.ptr(wt), _lib.ptr(a_in), _lib.ptr(self.gin[i]),
+                                                             _lib.ptr(below.bias.grad), _lib.ptr(self.cs[i - 1]), stream), "bg_mlp_layer_backward")
+                else:
+                    torch.mm(g, l.weight, out=self.gin[i])
+                    _lib.check(lib.bg_elu_backward_colsum(B, C_in, _lib.ptr(self.gin[i]), _lib.ptr(a_in), _lib.ptr(below.bias.grad), _lib.ptr(self.cs[i - 1]),
+                                                          stream), "bg_elu_backward_colsum")
+                g = self.gin[i]
+
+    # ------------------------------------------------------------------ weight gradients
     # The backward chain computes only dL/dz; the weight gradients of all layers run afterwards, when both networks' chains are done and nothing
     # else competes for the GPU: the grouped launch (GroupedWeightGrad.run); shapes outside its range run as library GEMMs there.
 
@@ -546,77 +608,13 @@ class MLPTrainer:
         C_out, C_in = l.weight.shape
         if self.dw[i] is None:
             self.dw[i] = torch.empty(S, C_out, a_in.shape[1], dtype=torch.float32, device=g.device)
-        if i == 0 and self.w0pad is not None:  # padded input columns: their gradient columns are dropped
+        if i == 0 and self.dw0sum is not None:  # padded input columns: their gradient columns are dropped
             torch.bmm(g.view(S, B // S, C_out).transpose(1, 2), a_in.view(S, B // S, self._kin), out=self.dw[0])
             torch.sum(self.dw[0], dim=0, out=self.dw0sum)
             l.weight.grad.copy_(self.dw0sum[:, :C_in])
         else:
             torch.bmm(g.view(S, B // S, C_out).transpose(1, 2), a_in.view(S, B // S, C_in), out=self.dw[i])
             torch.sum(self.dw[i], dim=0, out=l.weight.grad)
-
-    def mirror_descriptors(self, flat):
-        """bg_param_mirror entries for the copies of this network's weights that the layer kernels read (the bf16 planes of the chained split forward
-        or the zero-padded first layer of the fp32 chain; the transposed hidden layers of the backward kernels): handed to bg_optimizer_step, which then writes them together with the parameters.  `flat`: the optimiser's flat
-        parameter buffer (the weights are views of it).  Only buffers that exist are listed (they are created by the first forward / backward)."""
-        out = []
-        if self.plan.fwd in ("layer_split", "library"):
-            return out
-        split = self._chain_split() and self.cplanes[0] is not None
-        for i, l in enumerate(self.layers):
-            off = (l.weight.data_ptr() - flat.data_ptr()) // 4
-            rows, cols = l.weight.shape
-            if split and i < 3:  # the chained split kernel's planes (the padded input columns of the first layer stay zero)
-                kp = self._kin if i == 0 else cols
-                out.append(_lib.ParamMirror(off, rows, cols, 2, kp, rows * kp * 3, _lib.ptr(self.cplanes[i])))  # (pad: the planes of -W behind)
-            if i == 0 and self.w0pad is not None and not split:
-                out.append(_lib.ParamMirror(off, rows, cols, 0, self.w0pad.shape[1], 0, _lib.ptr(self.w0pad)))
-            if i in (1, 2) and self.cplanes_t[i] is not None:  # the chained backward kernel's planes of W^T
-                out.append(_lib.ParamMirror(off, rows, cols, 3, rows, rows * cols * 3, _lib.ptr(self.cplanes_t[i])))
-            if self.wt[i] is not None:
-                out.append(_lib.ParamMirror(off, rows, cols, 1, rows, 0, _lib.ptr(self.wt[i])))
-        return out
-
-    def _backward_from(self, start, g, finishes=None):
-        lib = _lib.load()
-        B = self._B
-        stream = _lib.current_stream_ptr()
-        self._pending_wgrad = []
-        for i in range(start, -1, -1):
-            l = self.layers[i]
-            a_in = (self.acts[i - 1] if i > 0 else self.x)[:B]
-            C_out, C_in = l.weight.shape
-            self._pending_wgrad.append((i, g))
-            if i > 0:
-                below = self.layers[i - 1]
-                fusable = self.bwd_fusable(C_out, C_in)
-                if fusable and self.plan.bwd == "layer_split":
-                    if self.planes_t[i] is None:
-                        self.planes_t[i] = torch.empty(C_in * C_out * 3, dtype=torch.int16, device=g.device)
-                    _lib.check(lib.bg_mlp_split_weights(C_in, C_out, _lib.ptr(l.weight), C_in, C_out, C_in, 1, _lib.ptr(self.planes_t[i]), stream),
-                               "bg_mlp_split_weights")
-                    _lib.check(lib.bg_mlp_layer_backward_split(B, C_out, C_in, _lib.ptr(g), _lib.ptr(self.planes_t[i]), _lib.ptr(a_in), _lib.ptr(self.gin[i]),
-                                                               _lib.ptr(below.bias.grad), _lib.ptr(self.cs[i - 1]), self.plan.terms, stream),
-                               "bg_mlp_layer_backward_split")
-                elif fusable and self.plan.bwd == "layer":
-                    if self.wt[i] is None:
-                        self.wt[i] = torch.empty(C_in, C_out, dtype=torch.float32, device=g.device)
-                        self.wt[i].copy_(l.weight.t())
-                    elif not self.mirror_fresh:
-                        self.wt[i].copy_(l.weight.t())
-                    if finishes is not None:
-                        fin = _lib.ReduceProblem()
-                        _lib.check(lib.bg_mlp_layer_backward_partial(B, C_out, C_in, _lib.ptr(g), _lib.ptr(self.wt[i]), _lib.ptr(a_in), _lib.ptr(self.gin[i]),
-                                                                     _lib.ptr(below.bias.grad), _lib.ptr(self.cs[i - 1]), fin, stream),
-                                   "bg_mlp_layer_backward_partial")
-                        finishes.append(fin)
-                    else:
-                        _lib.check(lib.bg_mlp_layer_backward(B, C_out, C_in, _lib.ptr(g), _lib.ptr(self.wt[i]), _lib.ptr(a_in), _lib.ptr(self.gin[i]),
-                                                             _lib.ptr(below.bias.grad), _lib.ptr(self.cs[i - 1]), stream), "bg_mlp_layer_backward")
-                else:
-                    torch.mm(g, l.weight, out=self.gin[i])
-                    _lib.check(lib.bg_elu_backward_colsum(B, C_in, _lib.ptr(self.gin[i]), _lib.ptr(a_in), _lib.ptr(below.bias.grad), _lib.ptr(self.cs[i - 1]),
-                                                          stream), "bg_elu_backward_colsum")
-                g = self.gin[i]
 
 
 class ActorCritic(torch.nn.Module):

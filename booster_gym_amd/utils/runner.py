@@ -22,6 +22,8 @@ Same surface: `Runner(test=False)` parses the reference's 8 CLI flags (runner.py
                              (bg_mlp_weight_grad_group_split_partial; BG_WGRAD_SPLIT=0: the fp32-MFMA launch bg_mlp_weight_grad_group_partial);
               tail           two launches (bg_update_tail): the deferred fixed-order sums + the squared-norm pieces, then clip + Adam + KL learning-rate
                              rule + statistics bookkeeping + the copies of the weights the layer kernels read (bf16 planes of W, -W, W^T, -W^T).
+            Whether a weight copy is current is the trainers' own record (model.WeightCopies) against ONE clock of the parameters that this runner ticks at
+            every optimiser step, in invalidate() and at the start of an update() that does not start from the rollout's passes; the tail stamps what it wrote.
             The sequence is written once, on the rows of a StepRows (the whole batch, or one of runner.num_mini_batches' K-ths of it): Runner.update ->
             _whole_batch_values, then per optimiser step _step and _epoch_gradients_and_step; _epoch_on_two_streams places the same pieces on two streams.
   multi-GPU one process per GPU (torchrun), environments sharded; per mini-epoch one float64 moments all-reduce on the side stream and ONE grouped RCCL
@@ -49,7 +51,7 @@ from ..envs import TASKS
 from .buffer import ExperienceBuffer
 from .config import load_cfg
 from .obs_norm import ObsNormalizer, check_checkpoint, normalization_cfg
-from .model import ACTOR_HIDDEN, CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, MLPTrainer, NetPlan, check_hidden, hidden_of, plan_network
+from .model import ACTOR_HIDDEN, CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, MLPTrainer, NetPlan, WeightClock, check_hidden, hidden_of, plan_network
 from .parallel import DataParallel
 from .recorder import Recorder
 from .utils import (actor_head_forward, actor_head_loss_backward, actor_head_sym_loss_backward, critic_head_backward, critic_head_forward, critic_values_gae, gae,
@@ -349,6 +351,7 @@ class Runner:
         # algorithm.empirical_normalization: running mean / variance of the critic's input columns (the actor's are its first num_obs), applied where rows
         # enter a network and updated at the end of update(); None = off, the one switch every branch below reads
         self.obs_norm = ObsNormalizer(self.env.num_obs + self.env.num_privileged_obs, obs_norm_eps, self.device) if obs_norm_on else None
+        self._clock = WeightClock()  # the version of the parameters, shared by every trainer over them: see invalidate()
         self.invalidate()
         self.optimizer = FlatAdam(self.model.parameters(), lr=self.learning_rate)
         self._load()
@@ -416,7 +419,7 @@ class Runner:
         self._old_logp = torch.zeros(B, device=dev)
         self._logstd_grad_view = self.model.logstd.grad.view(-1)
         self._logstd_off = (self._logstd_grad_view.data_ptr() - self.optimizer.grad.data_ptr()) // 4  # position of logstd in the flat buffers
-        self._actor_tr, self._critic_tr = MLPTrainer(self.model.actor), MLPTrainer(self.model.critic)
+        self._actor_tr, self._critic_tr = MLPTrainer(self.model.actor, clock=self._clock), MLPTrainer(self.model.critic, clock=self._clock)
         gs = (self.cfg.get("parallel", {}) or {}).get("gemm_split", 0)
         if gs:  # yaml switch for the split-bf16 GEMMs (process-wide, like the environment variable)
             if int(gs) not in (6, 9):
@@ -559,12 +562,11 @@ class Runner:
         """Call after changing the model's parameters or the rollout buffers by any means other than this runner's own rollout() / update() (a
         checkpoint or test that loads weights, a tool that edits buffer["obses"] / buffer["actions"]).  The contract between the two phases:
         rollout() may leave the first mini-epoch's forward passes (activations, values, old mu, old log-probabilities of every row) in the trainers'
-        buffers and the weight copies that the layer kernels read current, and update() then trusts both without looking; this forgets them, so the
-        next update() recomputes everything from the parameters and the buffers as they are."""
+        buffers and the weight copies that the layer kernels read current, and update() then trusts both without looking; this forgets them (the
+        clock of the parameters ticks: every copy of every trainer is stale), so the next update() recomputes everything from the parameters and the
+        buffers as they are."""
         self._fwd_plan = None
-        for tr in (getattr(self, "_actor_tr", None), getattr(self, "_critic_tr", None), getattr(self, "_actor_mb", None), getattr(self, "_critic_mb", None)):
-            if tr is not None:
-                tr.mirror_fresh = False
+        self._clock.tick()
 
     def checkpoint_dict(self):
         d = {"model": self.model.state_dict(), "optimizer": self.optimizer.state_dict(), "curriculum": self.env.curriculum_prob}
@@ -604,7 +606,7 @@ class Runner:
         changes, so the whole-batch pair is never flipped to b rows), the permutation and the gathered copies of every per-row stream the steps read."""
         K, B, A, dev = self._mini_batches, self._old_logp.numel(), self.env.num_actions, self.device
         b = self._mb_rows = B // K
-        self._actor_mb, self._critic_mb = MLPTrainer(self.model.actor), MLPTrainer(self.model.critic)
+        self._actor_mb, self._critic_mb = MLPTrainer(self.model.actor, clock=self._clock), MLPTrainer(self.model.critic, clock=self._clock)
         # the grouped weight-gradient launch keeps its descriptors per input buffer: one per mini-batch position (static after the first mini-epoch)
         self._mb_wgrad = [GroupedWeightGrad() for _ in range(K)]
         self._perm = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -699,7 +701,7 @@ class Runner:
         with torch.cuda.stream(side), torch.no_grad():
             logstd = self.model.logstd.reshape(-1)
             if a == 0:  # weights may have changed since the last optimiser step by other means (checkpoint, broadcast): six small copies, off the critical path
-                ct.refresh_mirrors(); at.refresh_mirrors()
+                ct.copies.rewrite_all(); at.copies.rewrite_all()
                 self._logp_done = 0
             if self._logp_done < a:  # steps of earlier calls: their actions were sampled on the main stream after their rows were enqueued here
                 r0, r1 = self._logp_done * N, a * N
@@ -762,8 +764,6 @@ class Runner:
                     hc, ha = w.ct.acts[2], w.at.acts[2]
                 elif K == 1:
                     hc, ha = self._forward_hidden(w)  # the one step's rows are the values pass's: both networks' forward passes as its grouped launch
-                else:
-                    w.ct.mirror_fresh = False  # the optimiser launch keeps the mini-batch trainers' weight copies current, not this trainer's
                 hc, v_all = self._whole_batch_values(u, hc)
                 if K > 1:
                     self._shuffle(u, epoch)
@@ -776,7 +776,6 @@ class Runner:
                 self.obs_norm.update_from(u.buf["obses"][: u.T], u.buf["privileged_obses"][: u.T], self.dp)
         if K > 1:
             self._mb_updates += 1
-            self._actor_tr.mirror_fresh = self._critic_tr.mirror_fresh = False  # (the optimiser launches wrote the mini-batch trainers' copies)
         return self._stats_acc
 
     def _update_begin(self, plan):
@@ -793,7 +792,7 @@ class Runner:
         ahead, self._fwd_plan = self._fwd_plan == plan, None
         if not ahead:
             torch.cuda.current_stream().wait_stream(self._side_stream)  # a forward-ahead being discarded may still write these buffers
-            self._actor_tr.mirror_fresh = self._critic_tr.mirror_fresh = False  # weights may have changed outside the loop below (checkpoint, broadcast)
+            self._clock.tick()  # weights may have changed outside the loop below (checkpoint, broadcast): every weight copy is stale
             if self.obs_norm is not None:
                 self._normalize_inputs(0, T + 1, T)
             else:
@@ -1004,7 +1003,7 @@ class Runner:
             # ... and the copies of the weights that the layer kernels read (zero-padded first layers, transposed hidden layers): written by the
             # same launch instead of six strided torch copies inside the chains of the next mini-epoch
             if mirrors is None:
-                ms = v.ct.mirror_descriptors(self.optimizer.flat) + v.at.mirror_descriptors(self.optimizer.flat)
+                ms = v.ct.copies.descriptors(self.optimizer.flat, v.ct.plan) + v.at.copies.descriptors(self.optimizer.flat, v.at.plan)
                 mirrors = (_lib.ParamMirror * len(ms))(*ms) if 0 < len(ms) <= 16 else None
             if one_tail and not plan.ranks:
                 self.optimizer.step_tail(wg_partial, [fin_c, fin_a] + fins, self._stats, self._stats_acc, self._stats_last, 4, B, alg["desired_kl"],
@@ -1012,11 +1011,9 @@ class Runner:
             else:
                 self.optimizer.step_fused(self._stats, self._stats_acc, self._stats_last, 4, B * self.world_size, alg["desired_kl"],
                                           grad_logstd=self._grad_logstd, ls_off=self._logstd_off, mirrors=mirrors)
-            v.at.mirror_fresh = v.ct.mirror_fresh = mirrors is not None
         else:
             self._logstd_grad_view.copy_(self._grad_logstd)  # (behind the bucket's all-reduce, which carries a stale value in this slot)
             self.optimizer.step()
-            v.at.mirror_fresh = v.ct.mirror_fresh = False  # this launch does not write the weight copies: the next pass copies them
             if self._lr_restart:  # first step after a checkpoint load: see __init__
                 self.optimizer.lr.fill_(float(cfg["algorithm"]["learning_rate"]))
                 self._lr_restart = False
@@ -1025,6 +1022,9 @@ class Runner:
             self._stats_last.copy_(self._stats)
             self._stats.zero_()
             self._grad_logstd.zero_()
+        self._clock.tick()  # the parameters have changed: every weight copy of every trainer over them is stale, but those this launch listed and wrote
+        if fused_tail and mirrors is not None:
+            v.ct.copies.stamp(); v.at.copies.stamp()
         u.mirrors = mirrors
 
     def _plan_chain_split(self, x_c, x_a, plan, ct=None, at=None):

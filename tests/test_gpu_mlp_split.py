@@ -135,7 +135,7 @@ def test_full_update_in_split_mode_matches_reference_loop(terms):
                                                  b["time_outs"].clone(), b["obses"][T].clone(), b["privileged_obses"][T].clone(), mini_epochs=E,
                                                  learning_rate=1e-5)
         summ = r._summarize(r.update())
-        assert r._actor_tr.planes[0] is not None and r._critic_tr.planes_t[1] is not None  # the split kernels did run
+        assert ("planes", 0) in r._actor_tr.copies.tensors and ("planes_t", 1) in r._critic_tr.copies.tensors  # the split kernels did run
         for (k, p), (k2, q) in zip(r.model.named_parameters(), ref_model.named_parameters()):
             assert k == k2 and torch.allclose(p, q, rtol=1e-3, atol=2e-6), (k, (p - q).abs().max().item())
         for k in ("value_loss", "actor_loss", "bound_loss", "entropy", "kl_mean"):

@@ -167,8 +167,10 @@ def test_update_of_other_widths_matches_reference_loop_without_library_gemms(mon
         assert abs(summ[k] - stats_ref[k]) <= 2e-4 * max(1.0, abs(stats_ref[k])), (k, summ[k], stats_ref[k])
     assert abs(summ["lr"] - lr_ref) < 1e-9
     # the optimiser launch kept every weight copy the layer kernels read current (zero-padded first layers, transposed hidden layers)
-    ms = r._critic_tr.mirror_descriptors(r.optimizer.flat) + r._actor_tr.mirror_descriptors(r.optimizer.flat)
-    assert len(ms) == len(actor_hidden) + len(critic_hidden) <= 16 and r._actor_tr.mirror_fresh and r._critic_tr.mirror_fresh
+    trs = (r._critic_tr, r._actor_tr)
+    ms = [m for tr in trs for m in tr.copies.descriptors(r.optimizer.flat, tr.plan)]
+    current = [tr.copies.current(*key) for tr in trs for key in tr.copies.listed]
+    assert len(ms) == len(actor_hidden) + len(critic_hidden) <= 16 and len(current) == len(ms) and all(current)
 
 
 def test_train_save_reload_play_and_checkpoint_width_mismatch(tmp_path):

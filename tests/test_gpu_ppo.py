@@ -486,6 +486,60 @@ def test_switching_a_live_runner_to_the_fp32_chains_takes_the_fp32_weight_gradie
         MLPTrainer.CHAIN_SPLIT = keep
 
 
+COPIES_CASES = {
+    # name: (config overrides, MLPTrainer class attributes, the copies of each stepping trainer: {kind: layers})
+    "default": ({}, {}, {"cplanes": (0, 1, 2), "cplanes_t": (1, 2)}),
+    "fp32_mfma_chains": ({}, {"CHAIN_SPLIT": False}, {"w0pad": (0,), "wt": (1, 2)}),
+    "hidden_layers_one_launch_each": ({}, {"CHAIN": False}, {"w0pad": (0,), "wt": (1, 2)}),
+    "two_mini_batches": ({"runner.num_mini_batches": 2}, {}, {"cplanes": (0, 1, 2), "cplanes_t": (1, 2)}),
+}
+
+
+@pytest.mark.parametrize("case", list(COPIES_CASES))
+def test_every_weight_copy_is_the_parameters_or_knows_that_it_is_not(case):
+    """After two whole iterations (the second rollout has read the copies the optimiser launch wrote) at the smallest shapes that use every copy (128 envs
+    x 4 steps = 512 rows; two mini-batches of 256): every copy that exists on every trainer of the runner and reports itself current is, bit for bit, a fresh
+    rewrite from the parameters into a zeroed buffer; one that reports itself stale is that after one get.  The trainers the optimiser launch listed
+    have their listed copies current; with runner.num_mini_batches = 2 those are the mini-batch pair, and the whole-batch pair over the same parameters
+    is stale right after update()."""
+    from booster_gym_amd.utils.config import load_cfg
+    from booster_gym_amd.utils.model import COPY_KINDS, MLPTrainer
+    from booster_gym_amd.utils.runner import Runner
+
+    over, cls_attrs, expected = COPIES_CASES[case]
+    saved = {k: getattr(MLPTrainer, k) for k in cls_attrs}
+    try:
+        for k, v in cls_attrs.items():
+            setattr(MLPTrainer, k, v)
+        r = Runner(cfg=load_cfg("T1", dict({"env.num_envs": 128, "runner.horizon_length": 4, "runner.mini_epochs": 2, "terrain.type": "plane", "basic.seed": 7}, **over)))
+        obs, infos = r.env.reset()
+        r.buffer["obses"][0].copy_(obs); r.buffer["privileged_obses"][0].copy_(infos["privileged_obs"])
+        r.iteration()
+        r.rollout()
+        r.update()
+        torch.cuda.synchronize()
+        whole, K = [r._critic_tr, r._actor_tr], r._mini_batches
+        stepping = [r._critic_mb, r._actor_mb] if K > 1 else whole
+        assert K == (2 if case == "two_mini_batches" else 1) and r._old_logp.numel() == 512 and all(tr._B == 512 // K for tr in stepping)
+        for tr in stepping:
+            keys = [(kind, i) for kind, layers in expected.items() for i in layers]
+            assert sorted(tr.copies.tensors) == sorted(keys) == sorted(tr.copies.listed) and all(tr.copies.current(*key) for key in keys), (case, list(tr.copies.tensors))
+        if K > 1:  # what two hand-written lines of update() used to say
+            for tr in whole:
+                assert ("cplanes", 0) in tr.copies.tensors and not any(tr.copies.current(*key) for key in tr.copies.tensors)
+        for tr in whole + (stepping if K > 1 else []):
+            for (kind, i), t in tr.copies.tensors.items():
+                fresh = torch.zeros_like(t)
+                COPY_KINDS[kind].write(tr.layers[i].weight, tr.copies.kp(i), fresh)
+                if not tr.copies.current(kind, i):
+                    assert tr.copies.get(kind, i) is t and tr.copies.current(kind, i)
+                assert torch.equal(t, fresh), (case, kind, i)
+        torch.cuda.synchronize()
+    finally:
+        for k, v in saved.items():
+            setattr(MLPTrainer, k, v)
+
+
 def test_update_with_deferred_reductions_equals_update_with_immediate_ones():
     """Runner.update() with the small reductions deferred to one launch in front of the weight gradients (the default) and with every finish inside
     its chain (BG_DEFER_FINISH=0), from identical weights and rollout data: same parameters after 3 mini-epochs up to the summation order of the
