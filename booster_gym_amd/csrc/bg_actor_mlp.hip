@@ -26,19 +26,11 @@
 
 #include <string>
 
-#include "../../include/booster_gym_amd.h"
+#include "bg_common.h"
 #include "bg_rng.h"
-
-extern int bg_set_error(int code, const char* msg);
-#define HIP_OK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) return bg_set_error(-2, hipGetErrorString(_e));               \
-    } while (0)
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int MR = 16;         // rows per workgroup
 constexpr int MAX_LAYERS = 5;  // 4 hidden + the output layer
 constexpr int KC = 48;         // k-chunk of the first layer: one frame's 47 observations and a column more (47 H <= 48 H: H chunks cover H frames)

@@ -2,17 +2,9 @@
 // backward-data): the exact three-way split of an fp32 operand in MFMA-gap-sized pieces, the nine products of a tile, the weight planes' copy into LDS
 // and their fragment reads.  gfx950 only.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <type_traits>
-#include <utility>
+#include "bg_common.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SP_ROW = 48;              // dwords per weight row and 32-deep chunk: 3 planes x 2 steps x 2 lane halves x 16 bytes
 constexpr int NMAX = 256;               // widest layer
@@ -21,24 +13,9 @@ constexpr int NBUF = 3, AHEAD = 2;
 constexpr int CHAIN_MAX = 4;
 
 template <int V> using IC = std::integral_constant<int, V>;
-template <int... I, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) { (f(IC<I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl(std::make_integer_sequence<int, N>{}, f); }
 
 #define BG_PIN() __builtin_amdgcn_sched_barrier(0)
 #define BG_MFMA(ACC, A, B) ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A), __builtin_bit_cast(bf16x8, B), ACC, 0, 0, 0)
-
-// s_waitcnt vmcnt(n) only (gfx9 encoding: vmcnt = bits 3:0 and 15:14, expcnt 6:4, lgkmcnt 11:8)
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0, "");
-    constexpr int n = N > 63 ? 63 : N;
-    __builtin_amdgcn_s_waitcnt((n & 15) | ((n >> 4) << 14) | 0x0F70);
-}
-
-// ELU through v_exp_f32 (as bg_mlp_tile.h)
-__device__ __forceinline__ float elu_f(float x) { return x > 0.f ? x : __expf(x) - 1.0f; }
 
 // The split of one pair of fp32 values into the three planes' packed bf16 pairs (low half = x0), in four pieces that ride behind four MFMAs:
 // 3 + 3 + 3 + 2 VALU instructions (an MFMA gap takes four for free).

@@ -17,17 +17,8 @@
 // in a fixed order (the loss statistics and the log-std gradient keep the float64 atomics of bg_ppo_loss).
 #include <hip/hip_runtime.h>
 
-#include <string>
-
-#include "../../include/booster_gym_amd.h"
 #include "bg_ppo_math.h"
-
-extern int bg_set_error(int code, const char* msg);
-#define HIP_OK(expr)                                                          \
-    do {                                                                      \
-        hipError_t _e = (expr);                                               \
-        if (_e != hipSuccess) return bg_set_error(-2, hipGetErrorString(_e)); \
-    } while (0)
+#include "bg_reduce.h"
 
 namespace {
 
@@ -37,10 +28,6 @@ constexpr int HLD = 132;   // LDS row stride of the activation tile: 16-byte ali
 constexpr int HA = BG_NUM_DOFS;
 constexpr int HEAD_MAX_GRID = 768;
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 __device__ __forceinline__ float elu_grad_from_output(float a) { return a > 0.f ? 1.0f : a + 1.0f; }
 
 // coalesced load of a [HT][HK] activation tile into LDS (rows past B read as zero), in two halves so that a persistent workgroup can have the
@@ -67,7 +54,7 @@ __device__ __forceinline__ void load_tile(const float* __restrict__ h, int row0,
     tile_put(v, s_h);
 }
 
-// Per-workgroup partial sums, added in a fixed order by head_finish_kernel.  scratch = [HEAD_MAX_GRID records of head_record<NO>() floats:
+// Per-workgroup partial sums, added in a fixed order by reduce_group_kernel.  scratch = [HEAD_MAX_GRID records of head_record<NO>() floats:
 // [NO][HK] output-layer weight gradient, [HK] hidden bias gradient, [NO] output bias gradient] followed by the float64 loss statistics,
 // statistic-major [HEAD_NSTAT][groups].  (Float64 atomics from every workgroup on the 17 shared addresses cost 45-60 us per launch.)
 constexpr int HEAD_NSTAT = HA + 5;
@@ -287,109 +274,12 @@ __global__ __launch_bounds__(256) void critic_head_backward_kernel(int B, int ti
     }
 }
 
-// One float64 statistic (row k of the stat-major [n_stat][groups] block) added up by one workgroup in a fixed order, then ONE atomic: k < n_ls goes to
-// grad_logstd[k] (+ entropy_coef: d(entropy.mean())/dlogstd = 1), the rest to stats[k - n_ls]; a statistic whose stat_skip bit is set is skipped.
-// (One workgroup PER statistic: a single workgroup walking the 17 statistics of the actor head one after the other -- a load, a butterfly and two
-// barriers each -- was a 66 us launch on the actor's chain of every mini-epoch.)
-__device__ __forceinline__ void finish_statistic(const double* __restrict__ sp, int groups, int k, int n_ls, unsigned stat_skip, double entropy_coef,
-                                                 double* __restrict__ grad_logstd, double* __restrict__ stats) {
-    if ((stat_skip >> k) & 1u) return;
-    __shared__ double sd[4];
-    double s = 0.0;
-#pragma unroll 4
-    for (int g = threadIdx.x; g < groups; g += 256) s += sp[(size_t)k * groups + g];
-    s = wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) sd[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double v = sd[0] + sd[1] + sd[2] + sd[3];
-        if (k < n_ls) atomicAdd(&grad_logstd[k], v + entropy_coef);
-        else atomicAdd(&stats[k - n_ls], v);
-    }
-}
-
-// fixed-order sum of the workgroups' records: out[i] = sum_g partial[g][i]; 16 outputs x 16 record slices per workgroup.  The n_stat workgroups
-// behind those add up the float64 statistics (stat-major [n_stat][groups] at stat_base), one each (finish_statistic).
-__global__ __launch_bounds__(256) void head_finish_kernel(int groups, int record, int n_out, const float* __restrict__ partial, float* __restrict__ grad_w,
-                                                          int n_w, float* __restrict__ grad_b_hidden, float* __restrict__ grad_b, size_t stat_base,
-                                                          int n_stat, int n_ls, unsigned stat_skip, double entropy_coef,
-                                                          double* __restrict__ grad_logstd, double* __restrict__ stats) {
-    const int nsum = (n_out + 15) / 16;
-    if ((int)blockIdx.x >= nsum) {
-        finish_statistic(reinterpret_cast<const double*>(partial + stat_base), groups, blockIdx.x - nsum, n_ls, stat_skip, entropy_coef, grad_logstd, stats);
-        return;
-    }
-    __shared__ float sm[16][17];
-    const int o = threadIdx.x & 15, gs = threadIdx.x >> 4, i = blockIdx.x * 16 + o;
-    float s = 0.f;
-    if (i < n_out) {
-#pragma unroll 8  // 8 loads in flight: the 48 dependent adds of a thread were a chain of 48 L2 round trips
-        for (int g = gs; g < groups; g += 16) s += partial[(size_t)g * record + i];
-    }
-    sm[gs][o] = s;
-    __syncthreads();
-    if (threadIdx.x < 16 && i < n_out) {
-        float v = 0.f;
-        for (int k = 0; k < 16; k++) v += sm[k][o];
-        if (i < n_w) grad_w[i] = v;
-        else if (i < n_w + HK) grad_b_hidden[i - n_w] = v;
-        else grad_b[i - n_w - HK] = v;
-    }
-}
-
-// ---- deferred reductions (include/booster_gym_amd.h: bg_reduce_problem / bg_reduce_group): the work of head_finish_kernel (and of the backward
-// layer's column-sum finish) for up to 8 descriptors in one launch.  Workgroups [begin_k, begin_k + nblk_k) serve descriptor k: 16 outputs x 16
-// slices of the groups each, followed by one workgroup per float64 statistic of the descriptor (finish_statistic).
-constexpr int RG_MAX = 8;
-struct ReduceGroup { int np; int begin[RG_MAX]; bg_reduce_problem p[RG_MAX]; };
+// ---- the fixed-order sums over the workgroups' records (bg_reduce.h: reduce_block), for up to 8 descriptors in one launch: the deferred reductions of
+// bg_reduce_group, and the finish of a head's immediate form on the one descriptor of that head (head_finish)
 __global__ __launch_bounds__(256) void reduce_group_kernel(ReduceGroup grp) {
-    int k = 0;
-#pragma unroll
-    for (int j = 1; j < RG_MAX; j++)
-        if (j < grp.np && (int)blockIdx.x >= grp.begin[j]) k = j;
-    const bg_reduce_problem& pr = grp.p[k];
-    const int b = blockIdx.x - grp.begin[k], nsum = (pr.n_out + 15) / 16;
-    if (b >= nsum) {  // one of the statistics blocks of this descriptor
-        finish_statistic(reinterpret_cast<const double*>(pr.partial + pr.stat_base), pr.groups, b - nsum, pr.n_ls, pr.stat_skip, pr.entropy_coef, pr.grad_logstd,
-                         pr.stats);
-        return;
-    }
     __shared__ float sm[16][17];
-    const int o = threadIdx.x & 15, gs = threadIdx.x >> 4, i = b * 16 + o;
-    float s = 0.f;
-    if (i < pr.n_out) {
-#pragma unroll 8
-        for (int g = gs; g < pr.groups; g += 16) s += pr.partial[(size_t)g * pr.record + i];
-    }
-    sm[gs][o] = s;
-    __syncthreads();
-    if (threadIdx.x < 16 && i < pr.n_out) {
-        float v = 0.f;
-        for (int j = 0; j < 16; j++) v += sm[j][o];
-        if (i < pr.n[0]) pr.out[0][i] = v;
-        else if (i < pr.n[0] + pr.n[1]) pr.out[1][i - pr.n[0]] = v;
-        else pr.out[2][i - pr.n[0] - pr.n[1]] = v;
-    }
-}
-extern "C" int bg_reduce_group(const bg_reduce_problem* problems, int32_t count, void* stream) {
-    if (!problems || count <= 0 || count > RG_MAX) return bg_set_error(-1, "bg_reduce_group: 1 to 8 descriptors");
-    ReduceGroup grp;
-    grp.np = count;
-    int blocks = 0;
-    for (int k = 0; k < count; k++) {
-        const bg_reduce_problem& q = problems[k];
-        if (!q.partial || q.groups <= 0 || q.record <= 0 || q.n_out <= 0 || q.n_out > q.record || !q.out[0] || q.n[0] <= 0 ||
-            q.n[0] + q.n[1] + q.n[2] != q.n_out || (q.n[1] > 0 && !q.out[1]) || (q.n[2] > 0 && !q.out[2]))
-            return bg_set_error(-1, "bg_reduce_group: bad descriptor");
-        if (q.n_stat < 0 || q.n_stat > 32 || (q.n_stat > 0 && (!q.stats || (q.n_ls > 0 && !q.grad_logstd) || (q.stat_base & 1))))
-            return bg_set_error(-1, "bg_reduce_group: bad statistics descriptor");
-        grp.begin[k] = blocks;
-        grp.p[k] = q;
-        blocks += (q.n_out + 15) / 16 + q.n_stat;
-    }
-    hipLaunchKernelGGL(reduce_group_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, grp);
-    HIP_OK(hipGetLastError());
-    return 0;
+    __shared__ double sd[4];
+    (void)reduce_block(grp, blockIdx.x, sm, sd);  // (the squares of what it wrote are the tail's business: tail_sums_kernel, bg_tail.hip)
 }
 
 // values = h w + b: half a wave per row (32 lanes x 16 bytes = one 512-byte row), 4 rows in flight per half-wave
@@ -832,9 +722,18 @@ __global__ __launch_bounds__(256) void mirror_rows_kernel(int rows, int cols, Co
 }
 
 int head_grid(int tiles) { return tiles < HEAD_MAX_GRID ? tiles : HEAD_MAX_GRID; }
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
+
+// the deferred reductions of up to 8 descriptors in one launch
+extern "C" int bg_reduce_group(const bg_reduce_problem* problems, int32_t count, void* stream) {
+    ReduceGroup grp;
+    int blocks = 0;
+    if (const int rc = reduce_group_fill(problems, count, 1, grp, blocks, "bg_reduce_group")) return rc;
+    hipLaunchKernelGGL(reduce_group_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, grp);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
 
 extern "C" int bg_critic_head_forward(int32_t rows, const float* h, const float* w, const float* b, float* values, void* stream) {
     if (rows <= 0 || !h || !w || !b || !values) return bg_set_error(-1, "bg_critic_head_forward: bad argument");
@@ -862,118 +761,105 @@ extern "C" int bg_critic_values_gae(int32_t T, int32_t N, const float* h, const 
     return 0;
 }
 
-extern "C" int bg_actor_head(int32_t B, int32_t mode, const float* h, const float* W, const float* bias, const float* logstd, const float* actions,
-                             const float* old_mu, const float* old_logstd, const float* old_logp, const float* adv, const double* adv_stats,
-                             float e_clip, float bound_coef, float entropy_coef, float* mu_out, float* g_hidden, float* grad_W, float* grad_b,
-                             float* grad_b_hidden, double* grad_logstd, double* stats, float* scratch, void* stream) {
-    if (B <= 0 || !h || !W || !bias) return bg_set_error(-1, "bg_actor_head: bad argument");
-    if (!aligned16(h)) return bg_set_error(-1, "bg_actor_head: h must be 16-byte aligned");
-    const int tiles = (B + HT - 1) / HT, grid = head_grid(tiles);
-    hipStream_t st = (hipStream_t)stream;
-    if (mode == 0) {
-        if (!mu_out) return bg_set_error(-1, "bg_actor_head: mode 0 needs mu_out");
-        hipLaunchKernelGGL(actor_head_kernel<0>, dim3(grid), dim3(256), 0, st, B, tiles, h, W, bias, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, 0.f, 0.f, mu_out, nullptr, nullptr);
-        HIP_OK(hipGetLastError());
-        return 0;
-    }
-    if (mode != 1) return bg_set_error(-1, "bg_actor_head: mode must be 0 (forward) or 1 (forward + loss + backward)");
-    if (!logstd || !actions || !old_mu || !old_logstd || !old_logp || !adv || !adv_stats || !g_hidden || !grad_W || !grad_b || !grad_b_hidden ||
-        !grad_logstd || !stats || !scratch)
-        return bg_set_error(-1, "bg_actor_head: bad argument");
-    hipLaunchKernelGGL(actor_head_kernel<1>, dim3(grid), dim3(256), 0, st, B, tiles, h, W, bias, logstd, actions, old_mu, old_logstd, old_logp, adv,
-                       adv_stats, e_clip, bound_coef, mu_out, g_hidden, scratch);
-    constexpr int n_out = HA * HK + HK + HA;
-    hipLaunchKernelGGL(head_finish_kernel, dim3((n_out + 15) / 16 + HEAD_NSTAT), dim3(256), 0, st, grid, head_record<HA>(), n_out, scratch, grad_W, HA * HK,
-                       grad_b_hidden, grad_b, head_stat_base<HA>(), HEAD_NSTAT, HA, 1u << HA, (double)entropy_coef, grad_logstd, stats);
+// ---- the heads with a loss.  Each is ONE function for its immediate and its deferred entry point: the main kernel, then the sums over its workgroups'
+// records -- handed to the caller as a descriptor (`finish`: bg_reduce_group or bg_update_tail runs it later), or, without one, run now as a launch of
+// reduce_group_kernel on that descriptor.  `who` prefixes the error messages.
+static int head_finish(bg_reduce_problem* finish, const float* scratch, int grid, int record, float* grad_w, int n_w, float* grad_b_hidden, float* grad_b, int n_b,
+                       size_t stat_base, int n_stat, int n_ls, unsigned skip, double entropy_coef, double* grad_logstd, double* stats, hipStream_t st) {
+    HIP_OK(hipGetLastError());  // the main kernel's launch: a descriptor is filled only behind a launch that was taken
+    bg_reduce_problem now;
+    bg_reduce_problem* f = finish ? finish : &now;
+    f->partial = scratch; f->groups = grid; f->record = record; f->n_out = n_w + HK + n_b;
+    f->out[0] = grad_w; f->n[0] = n_w; f->out[1] = grad_b_hidden; f->n[1] = HK; f->out[2] = grad_b; f->n[2] = n_b;
+    f->stat_base = stat_base; f->n_stat = n_stat; f->n_ls = n_ls; f->stat_skip = skip; f->entropy_coef = entropy_coef; f->grad_logstd = grad_logstd; f->stats = stats;
+    if (finish) return 0;
+    ReduceGroup grp;  // (n_out + 15) / 16 + n_stat workgroups
+    int blocks = 0;
+    if (const int rc = reduce_group_fill(f, 1, 1, grp, blocks, "head finish")) return rc;
+    hipLaunchKernelGGL(reduce_group_kernel, dim3(blocks), dim3(256), 0, st, grp);
     HIP_OK(hipGetLastError());
     return 0;
 }
 
-static void head_finish_desc(bg_reduce_problem* f, const float* scratch, int grid, int record, float* grad_w, int n_w, float* grad_b_hidden, float* grad_b, int n_b,
-                             size_t stat_base, int n_stat, int n_ls, unsigned skip, double entropy_coef, double* grad_logstd, double* stats) {
-    f->partial = scratch; f->groups = grid; f->record = record; f->n_out = n_w + HK + n_b;
-    f->out[0] = grad_w; f->n[0] = n_w; f->out[1] = grad_b_hidden; f->n[1] = HK; f->out[2] = grad_b; f->n[2] = n_b;
-    f->stat_base = stat_base; f->n_stat = n_stat; f->n_ls = n_ls; f->stat_skip = skip; f->entropy_coef = entropy_coef; f->grad_logstd = grad_logstd; f->stats = stats;
+static int actor_head_loss(const char* who, int32_t B, const float* h, const float* W, const float* bias, const float* logstd, const float* actions,
+                           const float* old_mu, const float* old_logstd, const float* old_logp, const float* adv, const double* adv_stats, float e_clip,
+                           float bound_coef, float entropy_coef, float* mu_out, float* g_hidden, float* grad_W, float* grad_b, float* grad_b_hidden,
+                           double* grad_logstd, double* stats, float* scratch, bg_reduce_problem* finish, hipStream_t st) {
+    if (B <= 0 || !h || !W || !bias || !logstd || !actions || !old_mu || !old_logstd || !old_logp || !adv || !adv_stats || !g_hidden || !grad_W || !grad_b ||
+        !grad_b_hidden || !grad_logstd || !stats || !scratch)
+        return bg_fail(who, -1, "bad argument");
+    if (!aligned16(h)) return bg_fail(who, -1, "h must be 16-byte aligned");
+    const int tiles = (B + HT - 1) / HT, grid = head_grid(tiles);
+    hipLaunchKernelGGL(actor_head_kernel<1>, dim3(grid), dim3(256), 0, st, B, tiles, h, W, bias, logstd, actions, old_mu, old_logstd, old_logp, adv, adv_stats,
+                       e_clip, bound_coef, mu_out, g_hidden, scratch);
+    return head_finish(finish, scratch, grid, head_record<HA>(), grad_W, HA * HK, grad_b_hidden, grad_b, HA, head_stat_base<HA>(), HEAD_NSTAT, HA, 1u << HA,
+                       (double)entropy_coef, grad_logstd, stats, st);
+}
+extern "C" int bg_actor_head(int32_t B, int32_t mode, const float* h, const float* W, const float* bias, const float* logstd, const float* actions,
+                             const float* old_mu, const float* old_logstd, const float* old_logp, const float* adv, const double* adv_stats,
+                             float e_clip, float bound_coef, float entropy_coef, float* mu_out, float* g_hidden, float* grad_W, float* grad_b,
+                             float* grad_b_hidden, double* grad_logstd, double* stats, float* scratch, void* stream) {
+    if (mode == 1)
+        return actor_head_loss("bg_actor_head", B, h, W, bias, logstd, actions, old_mu, old_logstd, old_logp, adv, adv_stats, e_clip, bound_coef, entropy_coef, mu_out,
+                               g_hidden, grad_W, grad_b, grad_b_hidden, grad_logstd, stats, scratch, nullptr, (hipStream_t)stream);
+    if (B <= 0 || !h || !W || !bias) return bg_set_error(-1, "bg_actor_head: bad argument");
+    if (!aligned16(h)) return bg_set_error(-1, "bg_actor_head: h must be 16-byte aligned");
+    if (mode != 0) return bg_set_error(-1, "bg_actor_head: mode must be 0 (forward) or 1 (forward + loss + backward)");
+    if (!mu_out) return bg_set_error(-1, "bg_actor_head: mode 0 needs mu_out");
+    const int tiles = (B + HT - 1) / HT;
+    hipLaunchKernelGGL(actor_head_kernel<0>, dim3(head_grid(tiles)), dim3(256), 0, (hipStream_t)stream, B, tiles, h, W, bias, nullptr, nullptr, nullptr, nullptr,
+                       nullptr, nullptr, nullptr, 0.f, 0.f, mu_out, nullptr, nullptr);
+    HIP_OK(hipGetLastError());
+    return 0;
 }
 extern "C" int bg_actor_head_partial(int32_t B, const float* h, const float* W, const float* bias, const float* logstd, const float* actions,
                                      const float* old_mu, const float* old_logstd, const float* old_logp, const float* adv, const double* adv_stats,
                                      float e_clip, float bound_coef, float entropy_coef, float* mu_out, float* g_hidden, float* grad_W, float* grad_b,
                                      float* grad_b_hidden, double* grad_logstd, double* stats, float* scratch, bg_reduce_problem* finish, void* stream) {
-    if (B <= 0 || !h || !W || !bias || !logstd || !actions || !old_mu || !old_logstd || !old_logp || !adv || !adv_stats || !g_hidden || !grad_W || !grad_b ||
-        !grad_b_hidden || !grad_logstd || !stats || !scratch || !finish)
-        return bg_set_error(-1, "bg_actor_head_partial: bad argument");
-    if (!aligned16(h)) return bg_set_error(-1, "bg_actor_head_partial: h must be 16-byte aligned");
+    if (!finish) return bg_set_error(-1, "bg_actor_head_partial: bad argument");
+    return actor_head_loss("bg_actor_head_partial", B, h, W, bias, logstd, actions, old_mu, old_logstd, old_logp, adv, adv_stats, e_clip, bound_coef, entropy_coef,
+                           mu_out, g_hidden, grad_W, grad_b, grad_b_hidden, grad_logstd, stats, scratch, finish, (hipStream_t)stream);
+}
+
+static int critic_head_backward(const char* who, int32_t B, const float* h, const float* w, const float* values, const float* returns, float* g_hidden,
+                                float* grad_w, float* grad_b, float* grad_b_hidden, double* stats, float* scratch, bg_reduce_problem* finish, hipStream_t st) {
+    if (B <= 0 || !h || !w || !values || !returns || !g_hidden || !grad_w || !grad_b || !grad_b_hidden || !stats || !scratch) return bg_fail(who, -1, "bad argument");
+    if (!aligned16(h)) return bg_fail(who, -1, "h must be 16-byte aligned");
     const int tiles = (B + HT - 1) / HT, grid = head_grid(tiles);
-    hipLaunchKernelGGL(actor_head_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, B, tiles, h, W, bias, logstd, actions, old_mu, old_logstd, old_logp,
-                       adv, adv_stats, e_clip, bound_coef, mu_out, g_hidden, scratch);
-    HIP_OK(hipGetLastError());
-    head_finish_desc(finish, scratch, grid, head_record<HA>(), grad_W, HA * HK, grad_b_hidden, grad_b, HA, head_stat_base<HA>(), HEAD_NSTAT, HA, 1u << HA,
-                     (double)entropy_coef, grad_logstd, stats);
-    return 0;
+    hipLaunchKernelGGL(critic_head_backward_kernel, dim3(grid), dim3(256), 0, st, B, tiles, h, w, values, returns, g_hidden, scratch);
+    return head_finish(finish, scratch, grid, head_record<1>(), grad_w, HK, grad_b_hidden, grad_b, 1, head_stat_base<1>(), 1, 0, 0u, 0.0, nullptr, stats, st);
+}
+extern "C" int bg_critic_head_backward(int32_t B, const float* h, const float* w, const float* values, const float* returns, float* g_hidden,
+                                       float* grad_w, float* grad_b, float* grad_b_hidden, double* stats, float* scratch, void* stream) {
+    return critic_head_backward("bg_critic_head_backward", B, h, w, values, returns, g_hidden, grad_w, grad_b, grad_b_hidden, stats, scratch, nullptr,
+                                (hipStream_t)stream);
 }
 extern "C" int bg_critic_head_backward_partial(int32_t B, const float* h, const float* w, const float* values, const float* returns, float* g_hidden,
                                                float* grad_w, float* grad_b, float* grad_b_hidden, double* stats, float* scratch, bg_reduce_problem* finish,
                                                void* stream) {
-    if (B <= 0 || !h || !w || !values || !returns || !g_hidden || !grad_w || !grad_b || !grad_b_hidden || !stats || !scratch || !finish)
-        return bg_set_error(-1, "bg_critic_head_backward_partial: bad argument");
-    if (!aligned16(h)) return bg_set_error(-1, "bg_critic_head_backward_partial: h must be 16-byte aligned");
-    const int tiles = (B + HT - 1) / HT, grid = head_grid(tiles);
-    hipLaunchKernelGGL(critic_head_backward_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, B, tiles, h, w, values, returns, g_hidden, scratch);
-    HIP_OK(hipGetLastError());
-    head_finish_desc(finish, scratch, grid, head_record<1>(), grad_w, HK, grad_b_hidden, grad_b, 1, head_stat_base<1>(), 1, 0, 0u, 0.0, nullptr, stats);
-    return 0;
-}
-
-extern "C" int bg_critic_head_backward(int32_t B, const float* h, const float* w, const float* values, const float* returns, float* g_hidden,
-                                       float* grad_w, float* grad_b, float* grad_b_hidden, double* stats, float* scratch, void* stream) {
-    if (B <= 0 || !h || !w || !values || !returns || !g_hidden || !grad_w || !grad_b || !grad_b_hidden || !stats || !scratch)
-        return bg_set_error(-1, "bg_critic_head_backward: bad argument");
-    if (!aligned16(h)) return bg_set_error(-1, "bg_critic_head_backward: h must be 16-byte aligned");
-    const int tiles = (B + HT - 1) / HT, grid = head_grid(tiles);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(critic_head_backward_kernel, dim3(grid), dim3(256), 0, st, B, tiles, h, w, values, returns, g_hidden, scratch);
-    constexpr int n_out = HK + HK + 1;
-    hipLaunchKernelGGL(head_finish_kernel, dim3((n_out + 15) / 16 + 1), dim3(256), 0, st, grid, head_record<1>(), n_out, scratch, grad_w, HK, grad_b_hidden,
-                       grad_b, head_stat_base<1>(), 1, 0, 0u, 0.0, (double*)nullptr, stats);
-    HIP_OK(hipGetLastError());
-    return 0;
+    if (!finish) return bg_set_error(-1, "bg_critic_head_backward_partial: bad argument");
+    return critic_head_backward("bg_critic_head_backward_partial", B, h, w, values, returns, g_hidden, grad_w, grad_b, grad_b_hidden, stats, scratch, finish,
+                                (hipStream_t)stream);
 }
 
 // ---- behaviour-cloning head (teacher-student distillation)
-static int distill_head_launch(const char* who, int32_t B, const float* h, const float* W, const float* bias, const float* target, float* mu_out, float* g_hidden,
-                               float* grad_W, float* grad_b, float* grad_b_hidden, double* stats, float* scratch, int* grid_out, hipStream_t st) {
-    if (B <= 0 || !h || !W || !bias || !target || !g_hidden || !grad_W || !grad_b || !grad_b_hidden || !stats || !scratch)
-        return bg_set_error(-1, (std::string(who) + ": bad argument").c_str());
-    if (!aligned16(h)) return bg_set_error(-1, (std::string(who) + ": h must be 16-byte aligned").c_str());
+static int distill_head(const char* who, int32_t B, const float* h, const float* W, const float* bias, const float* target, float* mu_out, float* g_hidden,
+                        float* grad_W, float* grad_b, float* grad_b_hidden, double* stats, float* scratch, bg_reduce_problem* finish, hipStream_t st) {
+    if (B <= 0 || !h || !W || !bias || !target || !g_hidden || !grad_W || !grad_b || !grad_b_hidden || !stats || !scratch) return bg_fail(who, -1, "bad argument");
+    if (!aligned16(h)) return bg_fail(who, -1, "h must be 16-byte aligned");
     const int tiles = (B + HT - 1) / HT, grid = head_grid(tiles);
     hipLaunchKernelGGL(distill_head_kernel, dim3(grid), dim3(256), 0, st, B, tiles, h, W, bias, target, mu_out, g_hidden, scratch);
-    *grid_out = grid;
-    return 0;
+    return head_finish(finish, scratch, grid, head_record<HA>(), grad_W, HA * HK, grad_b_hidden, grad_b, HA, head_stat_base<HA>(), 1, 0, 0u, 0.0, nullptr, stats, st);
 }
-
 extern "C" int bg_distill_head(int32_t B, const float* h, const float* W, const float* bias, const float* target, float* mu_out, float* g_hidden, float* grad_W,
                                float* grad_b, float* grad_b_hidden, double* stats, float* scratch, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    int grid = 0;
-    if (const int rc = distill_head_launch("bg_distill_head", B, h, W, bias, target, mu_out, g_hidden, grad_W, grad_b, grad_b_hidden, stats, scratch, &grid, st)) return rc;
-    constexpr int n_out = HA * HK + HK + HA;
-    hipLaunchKernelGGL(head_finish_kernel, dim3((n_out + 15) / 16 + 1), dim3(256), 0, st, grid, head_record<HA>(), n_out, scratch, grad_W, HA * HK, grad_b_hidden,
-                       grad_b, head_stat_base<HA>(), 1, 0, 0u, 0.0, (double*)nullptr, stats);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return distill_head("bg_distill_head", B, h, W, bias, target, mu_out, g_hidden, grad_W, grad_b, grad_b_hidden, stats, scratch, nullptr, (hipStream_t)stream);
 }
-
 extern "C" int bg_distill_head_partial(int32_t B, const float* h, const float* W, const float* bias, const float* target, float* mu_out, float* g_hidden,
                                        float* grad_W, float* grad_b, float* grad_b_hidden, double* stats, float* scratch, bg_reduce_problem* finish, void* stream) {
     if (!finish) return bg_set_error(-1, "bg_distill_head_partial: bad argument");
-    int grid = 0;
-    if (const int rc = distill_head_launch("bg_distill_head_partial", B, h, W, bias, target, mu_out, g_hidden, grad_W, grad_b, grad_b_hidden, stats, scratch, &grid,
-                                           (hipStream_t)stream))
-        return rc;
-    HIP_OK(hipGetLastError());
-    head_finish_desc(finish, scratch, grid, head_record<HA>(), grad_W, HA * HK, grad_b_hidden, grad_b, HA, head_stat_base<HA>(), 1, 0, 0u, 0.0, nullptr, stats);
-    return 0;
+    return distill_head("bg_distill_head_partial", B, h, W, bias, target, mu_out, g_hidden, grad_W, grad_b, grad_b_hidden, stats, scratch, finish,
+                        (hipStream_t)stream);
 }
 
 // ---- mirror-symmetry loss
@@ -987,56 +873,40 @@ static int action_mirror(ActionMirror* am, const int32_t* act_src, const float* 
     }
     return 0;
 }
-static int actor_head_sym_launch(int32_t B, const float* h, const float* W, const float* bias, const float* logstd, const float* actions,
-                                 const float* old_mu, const float* old_logstd, const float* old_logp, const float* adv, const double* adv_stats, float e_clip,
-                                 float bound_coef, float sym_coef, const int32_t* act_src, const float* act_sign, float* mu_out, float* g_hidden, float* scratch,
-                                 int* grid_out, hipStream_t st) {
+static int actor_head_sym(const char* who, int32_t B, const float* h, const float* W, const float* bias, const float* logstd, const float* actions,
+                          const float* old_mu, const float* old_logstd, const float* old_logp, const float* adv, const double* adv_stats, float e_clip,
+                          float bound_coef, float entropy_coef, float sym_coef, const int32_t* act_src, const float* act_sign, float* mu_out, float* g_hidden,
+                          float* grad_W, float* grad_b, float* grad_b_hidden, double* grad_logstd, double* stats, float* scratch, bg_reduce_problem* finish,
+                          hipStream_t st) {
+    if (B <= 0 || !h || !W || !bias || !logstd || !actions || !old_mu || !old_logstd || !old_logp || !adv || !adv_stats || !g_hidden || !grad_W || !grad_b ||
+        !grad_b_hidden || !grad_logstd || !stats || !scratch)
+        return bg_fail(who, -1, "bad argument");
     ActionMirror am;
-    if (action_mirror(&am, act_src, act_sign)) return bg_set_error(-1, "bg_actor_head_sym: act_src / act_sign must be a symmetric signed permutation of the 12 actions that is its own inverse");
-    if (!aligned16(h)) return bg_set_error(-1, "bg_actor_head_sym: h must be 16-byte aligned");
+    if (action_mirror(&am, act_src, act_sign))
+        return bg_fail(who, -1, "act_src / act_sign must be a symmetric signed permutation of the 12 actions that is its own inverse");
+    if (!aligned16(h)) return bg_fail(who, -1, "h must be 16-byte aligned");
     const int tiles = (B + HTS - 1) / HTS, grid = head_grid(tiles);
     const float sym_scale = (float)(2.0 * (double)sym_coef / ((double)B * HA));
     hipLaunchKernelGGL(actor_head_sym_kernel, dim3(grid), dim3(256), 0, st, B, tiles, h, W, bias, logstd, actions, old_mu, old_logstd, old_logp, adv, adv_stats,
                        e_clip, bound_coef, sym_scale, am, mu_out, g_hidden, scratch);
-    *grid_out = grid;
-    return 0;
+    return head_finish(finish, scratch, grid, head_record<HA>(), grad_W, HA * HK, grad_b_hidden, grad_b, HA, head_stat_base<HA>(), HEAD_NSTAT_SYM, HA, 1u << HA,
+                       (double)entropy_coef, grad_logstd, stats, st);
 }
-
 extern "C" int bg_actor_head_sym(int32_t B, const float* h, const float* W, const float* bias, const float* logstd, const float* actions, const float* old_mu,
                                  const float* old_logstd, const float* old_logp, const float* adv, const double* adv_stats, float e_clip, float bound_coef,
                                  float entropy_coef, float sym_coef, const int32_t* act_src, const float* act_sign, float* mu_out, float* g_hidden, float* grad_W,
                                  float* grad_b, float* grad_b_hidden, double* grad_logstd, double* stats, float* scratch, void* stream) {
-    if (B <= 0 || !h || !W || !bias || !logstd || !actions || !old_mu || !old_logstd || !old_logp || !adv || !adv_stats || !g_hidden || !grad_W || !grad_b ||
-        !grad_b_hidden || !grad_logstd || !stats || !scratch)
-        return bg_set_error(-1, "bg_actor_head_sym: bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    int grid = 0;
-    const int rc = actor_head_sym_launch(B, h, W, bias, logstd, actions, old_mu, old_logstd, old_logp, adv, adv_stats, e_clip, bound_coef,
-                                         sym_coef, act_src, act_sign, mu_out, g_hidden, scratch, &grid, st);
-    if (rc) return rc;
-    constexpr int n_out = HA * HK + HK + HA;
-    hipLaunchKernelGGL(head_finish_kernel, dim3((n_out + 15) / 16 + HEAD_NSTAT_SYM), dim3(256), 0, st, grid, head_record<HA>(), n_out, scratch, grad_W, HA * HK,
-                       grad_b_hidden, grad_b, head_stat_base<HA>(), HEAD_NSTAT_SYM, HA, 1u << HA, (double)entropy_coef, grad_logstd, stats);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return actor_head_sym("bg_actor_head_sym", B, h, W, bias, logstd, actions, old_mu, old_logstd, old_logp, adv, adv_stats, e_clip, bound_coef, entropy_coef, sym_coef,
+                          act_src, act_sign, mu_out, g_hidden, grad_W, grad_b, grad_b_hidden, grad_logstd, stats, scratch, nullptr, (hipStream_t)stream);
 }
-
 extern "C" int bg_actor_head_sym_partial(int32_t B, const float* h, const float* W, const float* bias, const float* logstd, const float* actions,
                                          const float* old_mu, const float* old_logstd, const float* old_logp, const float* adv, const double* adv_stats,
                                          float e_clip, float bound_coef, float entropy_coef, float sym_coef, const int32_t* act_src, const float* act_sign,
                                          float* mu_out, float* g_hidden, float* grad_W, float* grad_b, float* grad_b_hidden, double* grad_logstd, double* stats,
                                          float* scratch, bg_reduce_problem* finish, void* stream) {
-    if (B <= 0 || !h || !W || !bias || !logstd || !actions || !old_mu || !old_logstd || !old_logp || !adv || !adv_stats || !g_hidden || !grad_W || !grad_b ||
-        !grad_b_hidden || !grad_logstd || !stats || !scratch || !finish)
-        return bg_set_error(-1, "bg_actor_head_sym_partial: bad argument");
-    int grid = 0;
-    const int rc = actor_head_sym_launch(B, h, W, bias, logstd, actions, old_mu, old_logstd, old_logp, adv, adv_stats, e_clip,
-                                         bound_coef, sym_coef, act_src, act_sign, mu_out, g_hidden, scratch, &grid, (hipStream_t)stream);
-    if (rc) return rc;
-    HIP_OK(hipGetLastError());
-    head_finish_desc(finish, scratch, grid, head_record<HA>(), grad_W, HA * HK, grad_b_hidden, grad_b, HA, head_stat_base<HA>(), HEAD_NSTAT_SYM, HA, 1u << HA,
-                     (double)entropy_coef, grad_logstd, stats);
-    return 0;
+    if (!finish) return bg_set_error(-1, "bg_actor_head_sym_partial: bad argument");
+    return actor_head_sym("bg_actor_head_sym_partial", B, h, W, bias, logstd, actions, old_mu, old_logstd, old_logp, adv, adv_stats, e_clip, bound_coef, entropy_coef,
+                          sym_coef, act_src, act_sign, mu_out, g_hidden, grad_W, grad_b, grad_b_hidden, grad_logstd, stats, scratch, finish, (hipStream_t)stream);
 }
 
 extern "C" int bg_mirror_rows(int32_t rows, int32_t cols, const int32_t* src, const float* sign, const float* x, float* y, void* stream) {

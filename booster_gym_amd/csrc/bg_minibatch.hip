@@ -10,19 +10,9 @@
 // whole 64- or 128-byte pieces of lines (a 64-float row is 256 bytes = two 128-byte lines) -- and writes 1 KiB of consecutive destination bytes.  The
 // other streams (the per-row scalars) move 4 bytes per thread: random 4-byte reads, consecutive 4-byte writes; they are 3 of 155 floats per row at
 // the default shape.  pi is read once per thread (the threads of a row read the same word: one request per wave and row).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 
-#include "../../include/booster_gym_amd.h"
+#include "bg_common.h"
 #include "bg_perm.h"
-
-extern int bg_set_error(int code, const char* msg);
-
-#define HIP_OK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) return bg_set_error(-2, hipGetErrorString(_e));               \
-    } while (0)
 
 constexpr int MB_BLOCK = 256;
 

@@ -9,15 +9,6 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 
-#include "../../include/booster_gym_amd.h"
-
-extern int bg_set_error(int code, const char* msg);
-#define HIP_OK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) return bg_set_error(-2, hipGetErrorString(_e));               \
-    } while (0)
-
 #include "bg_mlp_tile.h"
 
 // one k-chunk (32 k-values) of MFMAs for this wave: 4 sub-steps x NT column tiles x 4 MFMAs
@@ -159,57 +150,47 @@ extern "C" int bg_mlp_layer_forward(int32_t M, int32_t K, int32_t N, const float
     return bg_set_error(-4, "bg_mlp_layer_forward: unsupported K (64, 128, 256, 512)");
 }
 
-extern "C" int bg_mlp_layer_backward(int32_t M, int32_t K, int32_t N, const float* G, const float* Wt, const float* act_below, float* Gout,
-                                     float* bias_grad_below, float* scratch, void* stream) {
-    if (M <= 0 || !G || !Wt || !act_below || !Gout || !bias_grad_below || !scratch) return bg_set_error(-1, "bg_mlp_layer_backward: bad argument");
-    if ((((uintptr_t)G | (uintptr_t)Wt | (uintptr_t)Gout | (uintptr_t)act_below) & 15) != 0)
-        return bg_set_error(-1, "bg_mlp_layer_backward: pointers must be 16-byte aligned");
-    if (N % 128 != 0 || N > 1024) return bg_set_error(-4, "bg_mlp_layer_backward: unsupported N (multiples of 128 up to 1024)");
+// The backward layer behind both of its entry points: the main kernel (EPI 2), then the column sums over its row slabs' records -- left to the caller
+// as a descriptor (`finish`: bg_reduce_group or bg_update_tail runs it later), or, without one, added now by mlp_colsum_finish_kernel.
+// The two finishes stay two kernels: mlp_colsum_finish_kernel adds a column with a 256-thread tree, the reduce block (bg_reduce.h) with 16 slices x 16
+// terms -- another order of the same terms, so folding one into the other would change the bias-gradient bits of the per-layer path (the tests compare
+// the two forms to 1e-5, not bit for bit).
+static int layer_backward(const char* who, int32_t M, int32_t K, int32_t N, const float* G, const float* Wt, const float* act_below, float* Gout,
+                          float* bias_grad_below, float* scratch, bg_reduce_problem* finish, hipStream_t st) {
+    if (M <= 0 || !G || !Wt || !act_below || !Gout || !bias_grad_below || !scratch) return bg_fail(who, -1, "bad argument");
+    if ((((uintptr_t)G | (uintptr_t)Wt | (uintptr_t)Gout | (uintptr_t)act_below) & 15) != 0) return bg_fail(who, -1, "pointers must be 16-byte aligned");
+    if (N % 128 != 0 || N > 1024) return bg_fail(who, -4, "unsupported N (multiples of 128 up to 1024)");
     const int nb = (M + FW_BM - 1) / FW_BM;
     dim3 grid(((nb + 7) / 8) * 8 * (N / 128)), block(256);
-    hipStream_t st = (hipStream_t)stream;
 #define BG_BWD(KK)                                                                                                                \
     if (K == KK) {                                                                                                                \
         if (N == 128) hipLaunchKernelGGL((mlp_fwd_kernel<KK, 2, 1>), grid, block, 0, st, M, N, G, Wt, nullptr, Gout, act_below, scratch);      \
         else if (N == 256) hipLaunchKernelGGL((mlp_fwd_kernel<KK, 2, 2>), grid, block, 0, st, M, N, G, Wt, nullptr, Gout, act_below, scratch); \
         else hipLaunchKernelGGL((mlp_fwd_kernel<KK, 2, 0>), grid, block, 0, st, M, N, G, Wt, nullptr, Gout, act_below, scratch);               \
-        hipLaunchKernelGGL(mlp_colsum_finish_kernel, dim3(N), dim3(256), 0, st, nb, N, scratch, bias_grad_below);                  \
-        HIP_OK(hipGetLastError());                                                                                                \
-        return 0;                                                                                                                 \
     }
     BG_BWD(256)
-    BG_BWD(128)
-    BG_BWD(512)
+    else BG_BWD(128)
+    else BG_BWD(512)
+    else return bg_fail(who, -4, "unsupported K (128, 256, 512)");
 #undef BG_BWD
-    return bg_set_error(-4, "bg_mlp_layer_backward: unsupported K (128, 256, 512)");
+    if (!finish) hipLaunchKernelGGL(mlp_colsum_finish_kernel, dim3(N), dim3(256), 0, st, nb, N, scratch, bias_grad_below);
+    HIP_OK(hipGetLastError());
+    if (finish) {
+        memset(finish, 0, sizeof(*finish));
+        finish->partial = scratch; finish->groups = nb; finish->record = N; finish->n_out = N;
+        finish->out[0] = bias_grad_below; finish->n[0] = N;
+    }
+    return 0;
 }
-
-// bg_mlp_layer_backward without the column-sum finish: the descriptor of that reduction instead (bg_reduce_group runs it later)
+extern "C" int bg_mlp_layer_backward(int32_t M, int32_t K, int32_t N, const float* G, const float* Wt, const float* act_below, float* Gout,
+                                     float* bias_grad_below, float* scratch, void* stream) {
+    return layer_backward("bg_mlp_layer_backward", M, K, N, G, Wt, act_below, Gout, bias_grad_below, scratch, nullptr, (hipStream_t)stream);
+}
+// bg_mlp_layer_backward without the column-sum finish: the descriptor of that reduction instead
 extern "C" int bg_mlp_layer_backward_partial(int32_t M, int32_t K, int32_t N, const float* G, const float* Wt, const float* act_below, float* Gout,
                                              float* bias_grad_below, float* scratch, bg_reduce_problem* finish, void* stream) {
-    if (M <= 0 || !G || !Wt || !act_below || !Gout || !bias_grad_below || !scratch || !finish) return bg_set_error(-1, "bg_mlp_layer_backward_partial: bad argument");
-    if ((((uintptr_t)G | (uintptr_t)Wt | (uintptr_t)Gout | (uintptr_t)act_below) & 15) != 0)
-        return bg_set_error(-1, "bg_mlp_layer_backward_partial: pointers must be 16-byte aligned");
-    if (N % 128 != 0 || N > 1024) return bg_set_error(-4, "bg_mlp_layer_backward_partial: unsupported N (multiples of 128 up to 1024)");
-    if (K != 256 && K != 128 && K != 512) return bg_set_error(-4, "bg_mlp_layer_backward_partial: unsupported K (128, 256, 512)");
-    const int nb = (M + FW_BM - 1) / FW_BM;
-    dim3 grid(((nb + 7) / 8) * 8 * (N / 128)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-#define BG_BWDP(KK)                                                                                                               \
-    if (K == KK) {                                                                                                                \
-        if (N == 128) hipLaunchKernelGGL((mlp_fwd_kernel<KK, 2, 1>), grid, block, 0, st, M, N, G, Wt, nullptr, Gout, act_below, scratch);      \
-        else if (N == 256) hipLaunchKernelGGL((mlp_fwd_kernel<KK, 2, 2>), grid, block, 0, st, M, N, G, Wt, nullptr, Gout, act_below, scratch); \
-        else hipLaunchKernelGGL((mlp_fwd_kernel<KK, 2, 0>), grid, block, 0, st, M, N, G, Wt, nullptr, Gout, act_below, scratch);               \
-    }
-    BG_BWDP(256)
-    BG_BWDP(128)
-    BG_BWDP(512)
-#undef BG_BWDP
-    HIP_OK(hipGetLastError());
-    memset(finish, 0, sizeof(*finish));
-    finish->partial = scratch; finish->groups = nb; finish->record = N; finish->n_out = N;
-    finish->out[0] = bias_grad_below; finish->n[0] = N;
-    return 0;
+    if (!finish) return bg_set_error(-1, "bg_mlp_layer_backward_partial: bad argument");
+    return layer_backward("bg_mlp_layer_backward_partial", M, K, N, G, Wt, act_below, Gout, bias_grad_below, scratch, finish, (hipStream_t)stream);
 }
 
 // launch of the fixed-order column-sum finish for bg_mlp_split.hip's backward layer

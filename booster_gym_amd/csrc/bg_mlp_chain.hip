@@ -19,15 +19,10 @@
 #include <stdint.h>
 #include <type_traits>
 
-#include "../../include/booster_gym_amd.h"
-
-extern int bg_set_error(int code, const char* msg);
+#include "bg_common.h"
 
 #include "bg_stamps.h"
 BG_STAMP_BUFFER(bg_chain_stamp_buf, bg_probe_read_chain_stamps, 2048, 24)  // tools/mlp_chain_stamps.py: [workgroup][wave][stamp], a stamp behind every chunk barrier
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int KC = 32;    // k-chunk staged in LDS (one row of a chunk = 128 bytes = 8 units of 16 bytes)
 constexpr int NMAX = 256;
@@ -35,21 +30,6 @@ constexpr int BUF = NMAX * KC;  // floats per LDS buffer
 constexpr int NBUF = 4, AHEAD = 3;
 constexpr int CHAIN_MAX = 4;
 struct ChainGroup { int n; int begin[CHAIN_MAX + 1]; bg_mlp_chain net[CHAIN_MAX]; };
-
-template <int... I, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl(std::make_integer_sequence<int, N>{}, f); }
-
-__device__ __forceinline__ float elu_f(float x) { return x > 0.f ? x : __expf(x) - 1.0f; }
-
-// s_waitcnt vmcnt(n) only (gfx9 encoding: vmcnt = bits 3:0 and 15:14, expcnt 6:4, lgkmcnt 11:8)
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0, "");
-    constexpr int n = N > 63 ? 63 : N;
-    __builtin_amdgcn_s_waitcnt((n & 15) | ((n >> 4) << 14) | 0x0F70);
-}
 
 // One k-chunk (32 columns) of W [N][K] global -> LDS with no register stop (global_load_lds_dwordx4: the LDS side of one wave-instruction is 64
 // consecutive 16-byte units = 8 rows of the chunk, the global side is per lane).  Unit u of row n is kept at unit u ^ ((n >> 1) & 7) of its row: the

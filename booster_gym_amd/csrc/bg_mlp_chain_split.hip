@@ -22,10 +22,6 @@
 #include <type_traits>
 #include <utility>
 
-#include "../../include/booster_gym_amd.h"
-
-extern int bg_set_error(int code, const char* msg);
-
 #include "bg_chain_split.h"
 #include "bg_stamps.h"
 BG_STAMP_BUFFER(bg_split_stamp_buf, bg_probe_read_split_stamps, 2 * 256, 64)  // tools/chain_split_stamps.py: [N2 == 256][workgroup][wave][stamp], stamps around every chunk barrier

@@ -2,16 +2,7 @@
 // unit: the default scheduler keeps it at three waves per SIMD without spills, max-ilp does not.
 #include <hip/hip_runtime.h>
 
-#include "../../include/booster_gym_amd.h"
 #include "bg_mlp_tile.h"
-
-extern int bg_set_error(int code, const char* msg);
-extern int bg_colsum_finish_launch(int nb, int C, const float* partial, float* out, hipStream_t st);
-#define HIP_OK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) return bg_set_error(-2, hipGetErrorString(_e));               \
-    } while (0)
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // Split form of the same layer (opt-in, `terms` = 9 or 6): fp32 x fp32 products on the bf16 matrix pipe, which on gfx950 is 16 x the fp32 one.
@@ -24,8 +15,6 @@ extern int bg_colsum_finish_launch(int nb, int C, const float* partial, float* o
 //     the A side produces (below), staged per chunk in LDS (3 planes x 64 B per column, row stride 208 B);
 //   * activations: fp32 from HBM exactly as in the fp32 kernel (16-byte loads, lane (i, h) takes floats s * 8 + 4 h + 0..3 of its row), split in
 //     registers (5.5 VALU per element, hidden in the MFMA shadow: an MFMA holds the issue port 8 of its 32 cycles).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int SP_ROW = 48;  // dwords per weight column and k-chunk in LDS: 3 planes x 4 slots of 16 bytes (slot = MFMA step j x lane half h)
 
 // (x0, x1) -> packed bf16 pairs (low half = x0) of the three planes

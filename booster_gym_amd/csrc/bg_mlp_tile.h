@@ -1,13 +1,7 @@
 // Pieces shared by the layer kernels of bg_mlp.hip (fp32 MFMA) and bg_mlp_split.hip (split bf16 MFMA): tile constants, the A-operand load and
 // the epilogues.  gfx950 only.
 #pragma once
-#include <hip/hip_runtime.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));  // native vector: stays in registers (HIP's float4 struct blocked SROA here)
-
-// exp(x) - 1 through v_exp_f32: absolute error ~1e-7 on (-1, 0], far below fp32 activation noise; expm1f costs ~20 VALU per element
-__device__ __forceinline__ float elu_f(float x) { return x > 0.f ? x : __expf(x) - 1.0f; }
+#include "bg_common.h"
 
 constexpr int FW_BM = 128;   // rows per workgroup (4 waves x 32 rows)
 constexpr int FW_KC = 32;    // k-chunk staged in LDS

@@ -10,18 +10,8 @@
 // This file is compiled without the value-changing FP relaxations of the other translation units and with -ffp-contract=off (Makefile): the
 // normalised value is the fp32 subtract rounded, then the fp32 multiply rounded, in every call site, so the rollout and the update produce the
 // same bits for the same row.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 
-#include "../../include/booster_gym_amd.h"
-
-extern int bg_set_error(int code, const char* msg);
-
-#define HIP_OK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) return bg_set_error(-2, hipGetErrorString(_e));               \
-    } while (0)
+#include "bg_common.h"
 
 // ------------------------------------------------------------------ moments
 // The matrix is [rows][cols_a + cols_b], given as two column blocks with their own row strides (the observation block and the privileged block of

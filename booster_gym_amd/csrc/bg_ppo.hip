@@ -9,29 +9,18 @@
 #include <hip/hip_runtime.h>
 #include <string>
 
-#include "../../include/booster_gym_amd.h"
 #include "bg_mirror.h"
 #include "bg_ppo_math.h"
+#include "bg_reduce.h"
 #include "bg_rng.h"
 #include "bg_stamps.h"
 
-extern int bg_set_error(int code, const char* msg);
-#define HIP_OK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) return bg_set_error(-2, hipGetErrorString(_e));               \
-    } while (0)
-
-// ------------------------------------------------------------------ block reduction helper (wave64)
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
+// ------------------------------------------------------------------ block reduction helper (wave64; wave_sum_d: bg_reduce.h)
 template <int NV>
 __device__ __forceinline__ void block_atomic_add(double (&v)[NV], double* dst, double* smem /*[NV * waves]*/) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = (blockDim.x + 63) >> 6;
     for (int k = 0; k < NV; k++) {
-        double s = wave_sum(v[k]);
+        double s = wave_sum_d(v[k]);
         if (lane == 0) smem[k * waves + wave] = s;
     }
     __syncthreads();
@@ -139,7 +128,7 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(int B, const float* __res
     // reduce: grad_logstd[A] and stats[5]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = (blockDim.x + 63) >> 6;
     for (int k = 0; k < A + 5; k++) {
-        double s = wave_sum(acc[k]);
+        double s = wave_sum_d(acc[k]);
         if (lane == 0) sm[k * waves + wave] = s;
     }
     __syncthreads();
@@ -183,7 +172,6 @@ __global__ void gaussian_logp_kernel(int B, const float* __restrict__ mu, const 
 //     layer L   float4 [waves][NT j][K / 16 t][64 lanes]: component c = WL[n][16 t + 4 (lane >> 4) + c]; zero where n is no neuron (the 12-neuron output
 //               layer: lanes with lane & 15 >= 12); the output layer keeps wave 0 only, the only wave with a tile of it
 //     biases    float [waves][NT j][64 lanes] = b[n] behind every layer's weights; logstd [12] (+ 4 zeros) at the end
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int AROWS = 16;
 constexpr int ALD = 260;  // LDS row stride (floats)
 __device__ __forceinline__ float elu(float x) { return x > 0.f ? x : expm1f(x); }
@@ -458,7 +446,7 @@ __global__ __launch_bounds__(OPT_THREADS) void optimizer_step_kernel(int n, floa
         acc += (double)x.x * (double)x.x + (double)x.y * (double)x.y + (double)x.z * (double)x.z + (double)x.w * (double)x.w;
     }
     for (int i = (n4 << 2) + t; i < n; i += OPT_THREADS) acc += (double)g[i] * (double)g[i];
-    acc = wave_sum(acc);
+    acc = wave_sum_d(acc);
     if ((t & 63) == 0) s_part[t >> 6] = acc;
     __syncthreads();
     if (t == 0) {

@@ -16,6 +16,7 @@ using namespace bg;
 
 // ------------------------------------------------------------------ error plumbing
 static int fail(int code, const std::string& msg) { return bg_set_error(code, msg.c_str()); }  // (the message lives in bg_model.cpp, host-only code)
+// (its own HIP_OK, not bg_common.h's: the message also names the call that failed)
 #define HIP_OK(expr)                                                                                 \
     do {                                                                                             \
         hipError_t _e = (expr);                                                                      \

@@ -4,8 +4,8 @@
 // launch-to-launch gaps of 7-8 us on the critical path of every mini-epoch (tools/timeline.py on the round-3 trace).
 //
 //   tail_sums_kernel   one workgroup per block of either kernel's work -- the weight gradients' fixed-order sums over their slices and the deferred
-//                      reductions (head / bias gradients, float64 loss statistics), the arithmetic and the order of the two kernels named above,
-//                      statement for statement: the gradients are the same bits -- and, while the finished values are in registers, the block's sum
+//                      reductions (head / bias gradients, float64 loss statistics), through the block functions the two kernels named above run
+//                      themselves (bg_wgrad.h, bg_reduce.h): the gradients are the same bits -- and, while the finished values are in registers, the block's sum
 //                      of their squares (float64) into one slot of norm_partial.  Every element of the flat gradient except the log-std's is
 //                      written by exactly one block, so the slots add up to the squared global norm;
 //   tail_adam_kernel   every workgroup adds the slots in slot order (+ the log-std's squares): the same total everywhere, deterministic, no
@@ -18,106 +18,22 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../include/booster_gym_amd.h"
 #include "bg_mirror.h"
+#include "bg_reduce.h"
 #include "bg_wgrad.h"
 
-extern int bg_set_error(int code, const char* msg);
-extern int bg_wgrad_group_fill(const bg_wgrad_problem* problems, int32_t count, WgradGroup& grp, int& wg, int& fin, const char* who);
-
 namespace {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 // ADAM_GRID: one workgroup per CU.  Every workgroup adds the ~2,900 norm slots itself (23 KB out of L2, the same order everywhere: the same total), so
 // the count changes no bit; with the weight copies the launch writes since round 6 (bf16 planes of W, -W, W^T, -W^T: up to 12 two-byte stores per
 // parameter, the transposed ones a cache line each) 256 workgroups instead of 64 are worth 0.1 ms per iteration (21.82-21.90 against 21.95-22.00 ms).
-constexpr int ADAM_GRID = 256, TAIL_THREADS = 256, RG_MAX = 8, TAIL_MAX_ITEMS = 8192;
-struct ReduceGroup { int np; int begin[RG_MAX]; bg_reduce_problem p[RG_MAX]; };
+constexpr int ADAM_GRID = 256, TAIL_THREADS = 256, TAIL_MAX_ITEMS = 8192;
 struct OptArgs {
     int n; float *p, *g, *m, *v, *lr_dev; float bc1, bc2_sqrt, beta1, beta2, eps, max_norm;
     double* grad_logstd; int ls_off, ls_n;
     double *stats, *stats_acc, *stats_last; int n_stats, kl_index; float kl_count, desired_kl, lr_min, lr_max;
 };
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-// one block of mlp_wgrad_group_finish_kernel (bg_wgrad.hip): dW element group e4 = sum over the slices, 16 slice groups x 16 float4 per workgroup
-// returns (threads 0..15: the others 0) the squares of the values this thread wrote
-__device__ __forceinline__ double wgrad_finish_block(const WgradGroup& grp, int b, f32x4 (*sm)[16]) {
-    int k = 0;
-#pragma unroll
-    for (int j = 1; j < WG_MAX_PROBLEMS; j++)
-        if (j < grp.np && b >= grp.p[j].fin_begin) k = j;
-    const WgradProblem& pr = grp.p[k];
-    const int c = threadIdx.x & 15, sg = threadIdx.x >> 4, e4 = (b - pr.fin_begin) * 16 + c, n4 = pr.n4, S = pr.slices, Cin = pr.Cin, Cin_real = pr.Cin_real;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (e4 < n4)
-        for (int s = sg; s < S; s += 16) acc += *reinterpret_cast<const f32x4*>(pr.P + ((size_t)s * n4 + e4) * 4);
-    sm[sg][c] = acc;
-    __syncthreads();
-    if (sg == 0 && e4 < n4) {
-        f32x4 v = sm[0][c];
-#pragma unroll
-        for (int j = 1; j < 16; j++) v += sm[j][c];
-        const int row = (e4 * 4) / Cin, col = (e4 * 4) % Cin;
-        double q = 0.0;
-        if (Cin_real == Cin) {
-            *reinterpret_cast<f32x4*>(pr.dW + (size_t)row * Cin + col) = v;
-            q = (double)v[0] * (double)v[0] + (double)v[1] * (double)v[1] + (double)v[2] * (double)v[2] + (double)v[3] * (double)v[3];
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                if (col + j < Cin_real) { pr.dW[(size_t)row * Cin_real + col + j] = v[j]; q += (double)v[j] * (double)v[j]; }
-        }
-        return q;
-    }
-    return 0.0;
-}
-// one block of reduce_group_kernel (bg_head.hip): 16 outputs x 16 record slices, or one float64 statistic
-__device__ __forceinline__ double reduce_block(const ReduceGroup& grp, int blk, float (*sm)[17], double* sd) {
-    int k = 0;
-#pragma unroll
-    for (int j = 1; j < RG_MAX; j++)
-        if (j < grp.np && blk >= grp.begin[j]) k = j;
-    const bg_reduce_problem& pr = grp.p[k];
-    const int b = blk - grp.begin[k], nsum = (pr.n_out + 15) / 16;
-    if (b >= nsum) {
-        const int ks = b - nsum;
-        if ((pr.stat_skip >> ks) & 1u) return 0.0;
-        const double* sp = reinterpret_cast<const double*>(pr.partial + pr.stat_base);
-        double s = 0.0;
-#pragma unroll 4
-        for (int g = threadIdx.x; g < pr.groups; g += 256) s += sp[(size_t)ks * pr.groups + g];
-        s = wave_sum_d(s);
-        if ((threadIdx.x & 63) == 0) sd[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const double v = sd[0] + sd[1] + sd[2] + sd[3];
-            if (ks < pr.n_ls) atomicAdd(&pr.grad_logstd[ks], v + pr.entropy_coef);
-            else atomicAdd(&pr.stats[ks - pr.n_ls], v);
-        }
-        return 0.0;  // (statistics are not gradients; the log-std's gradient is squared by tail_adam_kernel, once every statistic has been added)
-    }
-    const int o = threadIdx.x & 15, gs = threadIdx.x >> 4, i = b * 16 + o;
-    float s = 0.f;
-    if (i < pr.n_out) {
-#pragma unroll 8
-        for (int g = gs; g < pr.groups; g += 16) s += pr.partial[(size_t)g * pr.record + i];
-    }
-    sm[gs][o] = s;
-    __syncthreads();
-    if (threadIdx.x < 16 && i < pr.n_out) {
-        float v = 0.f;
-        for (int j = 0; j < 16; j++) v += sm[j][o];
-        if (i < pr.n[0]) pr.out[0][i] = v;
-        else if (i < pr.n[0] + pr.n[1]) pr.out[1][i - pr.n[0]] = v;
-        else pr.out[2][i - pr.n[0] - pr.n[1]] = v;
-        return (double)v * (double)v;
-    }
-    return 0.0;
-}
-
+// one workgroup per block of the weight gradients' finish (wgrad_finish_block, bg_wgrad.h) or of the deferred reductions (reduce_block, bg_reduce.h)
 __global__ __launch_bounds__(TAIL_THREADS) void tail_sums_kernel(WgradGroup wg, ReduceGroup rg, int rg_blocks, double* __restrict__ norm_partial) {
     __shared__ f32x4 sm4[16][16];
     __shared__ float smf[16][17];
@@ -204,7 +120,6 @@ __global__ __launch_bounds__(1024) void tail_adam_kernel(OptArgs o, ParamMirrors
 // the work list of tail_sums_kernel from the two descriptor lists (shared by bg_update_tail and bg_update_tail_sums)
 static int tail_sums_fill(const bg_wgrad_problem* wgrad, int32_t n_wgrad, const bg_reduce_problem* reduce, int32_t n_reduce, WgradGroup& wg, ReduceGroup& rg,
                           int& blocks, int& fin, const char* who) {
-    if (n_reduce < 0 || n_reduce > RG_MAX || (n_reduce > 0 && !reduce)) return bg_set_error(-1, "bg_update_tail: at most 8 reductions");
     wg.np = 0;
     int wgs = 0;
     fin = 0;
@@ -212,20 +127,7 @@ static int tail_sums_fill(const bg_wgrad_problem* wgrad, int32_t n_wgrad, const 
         const int rc = bg_wgrad_group_fill(wgrad, n_wgrad, wg, wgs, fin, who);
         if (rc) return rc;
     }
-    rg.np = n_reduce;
-    blocks = 0;
-    for (int k = 0; k < n_reduce; k++) {
-        const bg_reduce_problem& q = reduce[k];
-        if (!q.partial || q.groups <= 0 || q.record <= 0 || q.n_out <= 0 || q.n_out > q.record || !q.out[0] || q.n[0] <= 0 ||
-            q.n[0] + q.n[1] + q.n[2] != q.n_out || (q.n[1] > 0 && !q.out[1]) || (q.n[2] > 0 && !q.out[2]))
-            return bg_set_error(-1, "bg_update_tail: bad reduction descriptor");
-        if (q.n_stat < 0 || q.n_stat > 32 || (q.n_stat > 0 && (!q.stats || (q.n_ls > 0 && !q.grad_logstd) || (q.stat_base & 1))))
-            return bg_set_error(-1, "bg_update_tail: bad statistics descriptor");
-        rg.begin[k] = blocks;
-        rg.p[k] = q;
-        blocks += (q.n_out + 15) / 16 + q.n_stat;
-    }
-    for (int k = n_reduce; k < RG_MAX; k++) rg.begin[k] = blocks;
+    if (const int rc = reduce_group_fill(reduce, n_reduce, 0, rg, blocks, who)) return rc;
     if (blocks + fin > TAIL_MAX_ITEMS) return bg_set_error(-4, "bg_update_tail: more than 8192 blocks of sums (norm_scratch holds one slot per block)");
     return 0;
 }

@@ -2,20 +2,8 @@
 // Own translation unit: built with the default machine scheduler (Makefile) -- under -amdgpu-sched-strategy=max-ilp, which the lane-per-env
 // simulator kernels need, the 256-accumulator MFMA loop below was spilled to scratch.
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 
-#include "../../include/booster_gym_amd.h"
 #include "bg_wgrad.h"
-
-extern int bg_set_error(int code, const char* msg);
-#define HIP_OK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) return bg_set_error(-2, hipGetErrorString(_e));               \
-    } while (0)
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));  // native vector: stays in registers (HIP's float4 struct blocked SROA here)
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // Weight gradient dW[C_out][C_in] = G^T A over the batch (reference utils/runner.py:163 `loss.backward()` through model.py:9-26's Linear
@@ -209,53 +197,27 @@ extern "C" int bg_mlp_weight_grad(int32_t M, int32_t C_out, int32_t C_in, int32_
     return 0;
 }
 
-
+// the finish of a grouped launch: one workgroup per block of wgrad_finish_block (bg_wgrad.h), the block tail_sums_kernel (bg_tail.hip) runs as well
 __global__ __launch_bounds__(256) void mlp_wgrad_group_finish_kernel(WgradGroup grp) {
     __shared__ f32x4 sm[16][16];
-    const int b = blockIdx.x;
-    int k = 0;
-#pragma unroll
-    for (int j = 1; j < WG_MAX_PROBLEMS; j++)
-        if (j < grp.np && b >= grp.p[j].fin_begin) k = j;
-    const WgradProblem& pr = grp.p[k];
-    const int c = threadIdx.x & 15, sg = threadIdx.x >> 4, e4 = (b - pr.fin_begin) * 16 + c, n4 = pr.n4, S = pr.slices, Cin = pr.Cin, Cin_real = pr.Cin_real;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (e4 < n4)
-        for (int s = sg; s < S; s += 16) acc += *reinterpret_cast<const f32x4*>(pr.P + ((size_t)s * n4 + e4) * 4);
-    sm[sg][c] = acc;
-    __syncthreads();
-    if (sg == 0 && e4 < n4) {
-        f32x4 v = sm[0][c];
-#pragma unroll
-        for (int j = 1; j < 16; j++) v += sm[j][c];
-        const int row = (e4 * 4) / Cin, col = (e4 * 4) % Cin;
-        if (Cin_real == Cin) {
-            *reinterpret_cast<f32x4*>(pr.dW + (size_t)row * Cin + col) = v;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                if (col + j < Cin_real) pr.dW[(size_t)row * Cin_real + col + j] = v[j];
-        }
-    }
+    (void)wgrad_finish_block(grp, blockIdx.x, sm);  // (the squares of what it wrote are the tail's business)
 }
 
 // validation + descriptor build shared with bg_wgrad_split.hip; `who` prefixes the error messages
 int bg_wgrad_group_fill(const bg_wgrad_problem* problems, int32_t count, WgradGroup& grp, int& wg, int& fin, const char* who) {
-    static thread_local char msg[160];
-    auto fail = [&](int code, const char* what) { snprintf(msg, sizeof msg, "%s: %s", who, what); return bg_set_error(code, msg); };
-    if (!problems || count <= 0 || count > WG_MAX_PROBLEMS) return fail(-1, "1 to 8 problems");
+    if (!problems || count <= 0 || count > WG_MAX_PROBLEMS) return bg_fail(who, -1, "1 to 8 problems");
     grp.np = count;
     wg = 0; fin = 0;
     for (int k = 0; k < count; k++) {
         const bg_wgrad_problem& q = problems[k];
-        if (q.M <= 0 || !q.G || !q.A || !q.dW || !q.scratch) return fail(-1, "bad argument");
-        if ((((uintptr_t)q.G | (uintptr_t)q.A | (uintptr_t)q.scratch) & 15) != 0) return fail(-1, "G, A, scratch must be 16-byte aligned");
-        if (q.C_in_real == q.C_in && (((uintptr_t)q.dW) & 15) != 0) return fail(-1, "dW must be 16-byte aligned");
-        if (q.C_out % 128 != 0 || q.C_out > 1024) return fail(-4, "unsupported C_out (multiples of 128 up to 1024)");
-        if (q.C_in != 64 && (q.C_in % 128 != 0 || q.C_in > 1024)) return fail(-4, "unsupported C_in (64, or multiples of 128 up to 1024)");
-        if (q.C_in_real <= 0 || q.C_in_real > q.C_in) return fail(-1, "C_in_real must be in [1, C_in]");
-        if (q.M % 2 != 0) return fail(-4, "M must be even (rows are consumed in pairs)");
-        if (q.slices <= 0 || (long)q.slices * 8 > q.M) return fail(-4, "slices must be in [1, M / 8]");
+        if (q.M <= 0 || !q.G || !q.A || !q.dW || !q.scratch) return bg_fail(who, -1, "bad argument");
+        if ((((uintptr_t)q.G | (uintptr_t)q.A | (uintptr_t)q.scratch) & 15) != 0) return bg_fail(who, -1, "G, A, scratch must be 16-byte aligned");
+        if (q.C_in_real == q.C_in && (((uintptr_t)q.dW) & 15) != 0) return bg_fail(who, -1, "dW must be 16-byte aligned");
+        if (q.C_out % 128 != 0 || q.C_out > 1024) return bg_fail(who, -4, "unsupported C_out (multiples of 128 up to 1024)");
+        if (q.C_in != 64 && (q.C_in % 128 != 0 || q.C_in > 1024)) return bg_fail(who, -4, "unsupported C_in (64, or multiples of 128 up to 1024)");
+        if (q.C_in_real <= 0 || q.C_in_real > q.C_in) return bg_fail(who, -1, "C_in_real must be in [1, C_in]");
+        if (q.M % 2 != 0) return bg_fail(who, -4, "M must be even (rows are consumed in pairs)");
+        if (q.slices <= 0 || (long)q.slices * 8 > q.M) return bg_fail(who, -4, "slices must be in [1, M / 8]");
         WgradProblem& p = grp.p[k];
         p.G = q.G; p.A = q.A; p.P = q.scratch; p.dW = q.dW;
         p.M = q.M; p.Cout = q.C_out; p.Cin = q.C_in; p.Cin_real = q.C_in_real; p.tci = q.C_in == 64 ? 2 : 4;
@@ -263,8 +225,8 @@ int bg_wgrad_group_fill(const bg_wgrad_problem* problems, int32_t count, WgradGr
         p.ntiles = (q.C_out / 128) * p.ntile_ci;
         p.tw = q.tiles_per_workgroup <= 0 ? 1 : q.tiles_per_workgroup;
         if ((p.tw != 1 && p.tw != 2 && p.tw != 4) || p.ntiles % p.tw != 0)
-            return fail(-4, "tiles_per_workgroup must be 1, 2 or 4 and divide the layer's tile count");
-        if ((long)q.slices * (4 / p.tw) * 2 > q.M) return fail(-4, "too many slices for M");
+            return bg_fail(who, -4, "tiles_per_workgroup must be 1, 2 or 4 and divide the layer's tile count");
+        if ((long)q.slices * (4 / p.tw) * 2 > q.M) return bg_fail(who, -4, "too many slices for M");
         p.slices = q.slices;
         p.wg_begin = wg; wg += (p.ntiles / p.tw) * p.slices;
         p.n4 = q.C_out * q.C_in / 4;

@@ -244,6 +244,7 @@ class FlatAdam:
         self.betas, self.eps, self.max_grad_norm = betas, eps, max_grad_norm
         self.step_count = 0
         self._gnorm = torch.zeros(1, dtype=torch.float64, device=dev)
+        self._ticket = torch.zeros(1, dtype=torch.int32, device=dev)  # bg_optimizer_step's ticket
         self._tail_sync = torch.zeros(4, dtype=torch.int32, device=dev)  # bg_update_tail's ticket and squared-norm pieces
         self._tail_norm = torch.zeros(8192, dtype=torch.float64, device=dev)
 
@@ -256,40 +257,40 @@ class FlatAdam:
                                             _lib.ptr(self.exp_avg_sq), _lib.ptr(self.lr), self.step_count, self.betas[0], self.betas[1], self.eps,
                                             self.max_grad_norm, _lib.ptr(self._gnorm), _lib.current_stream_ptr()), "bg_adam_step")
 
+    def _opt_args(self, stats, stats_acc, stats_last, kl_index, count, desired_kl, grad_logstd, ls_off, lr_min, lr_max):
+        """The arguments bg_optimizer_step and bg_update_tail share, from `n` to `lr_max` (the step is counted by the caller)."""
+        return [self.flat.numel(), _lib.ptr(self.flat), _lib.ptr(self.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(self.lr), self.step_count,
+                self.betas[0], self.betas[1], self.eps, self.max_grad_norm, _lib.ptr(grad_logstd), int(ls_off), 0 if grad_logstd is None else grad_logstd.numel(),
+                _lib.ptr(stats), _lib.ptr(stats_acc), _lib.ptr(stats_last), stats.numel(), int(kl_index), float(count), desired_kl, lr_min, lr_max]
+
+    @staticmethod
+    def _sums_args(wgrad, reductions):
+        """The two descriptor lists of bg_update_tail / bg_update_tail_sums: wgrad = (descriptor array, count) of a weight-gradient launch made without its
+        finish (GroupedWeightGrad.run(..., partial=True)) or None, reductions = the deferred _lib.ReduceProblem descriptors."""
+        warr, wn = wgrad if wgrad is not None else (None, 0)
+        rarr = (_lib.ReduceProblem * len(reductions))(*reductions) if reductions else None
+        return [warr, wn, rarr, len(reductions) if reductions else 0]
+
     def step_fused(self, stats, stats_acc, stats_last, kl_index, count, desired_kl, grad_logstd=None, ls_off=0, lr_min=1e-5, lr_max=1e-2, mirrors=None):
         """clip + Adam + KL learning-rate rule + statistics bookkeeping in one launch (bg_optimizer_step): what `step()`, `adapt_lr()` and the
         runner's `stats_acc += stats` / zero fills do as seven dependent launches."""
         self.step_count += 1
-        if not hasattr(self, "_ticket"):
-            self._ticket = torch.zeros(1, dtype=torch.int32, device=self.flat.device)
-        _lib.check(_lib.load().bg_optimizer_step(self.flat.numel(), _lib.ptr(self.flat), _lib.ptr(self.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
-                                                 _lib.ptr(self.lr), self.step_count, self.betas[0], self.betas[1], self.eps, self.max_grad_norm,
-                                                 _lib.ptr(grad_logstd), int(ls_off), 0 if grad_logstd is None else grad_logstd.numel(), _lib.ptr(stats),
-                                                 _lib.ptr(stats_acc), _lib.ptr(stats_last), stats.numel(), int(kl_index), float(count), desired_kl, lr_min,
-                                                 lr_max, _lib.ptr(self._ticket), None if mirrors is None else ctypes.addressof(mirrors),
-                                                 0 if mirrors is None else len(mirrors), _lib.current_stream_ptr()),
-                   "bg_optimizer_step")
+        args = self._opt_args(stats, stats_acc, stats_last, kl_index, count, desired_kl, grad_logstd, ls_off, lr_min, lr_max)
+        _lib.check(_lib.load().bg_optimizer_step(*args, _lib.ptr(self._ticket), None if mirrors is None else ctypes.addressof(mirrors),
+                                                 0 if mirrors is None else len(mirrors), _lib.current_stream_ptr()), "bg_optimizer_step")
 
     def step_tail(self, wgrad, reductions, stats, stats_acc, stats_last, kl_index, count, desired_kl, grad_logstd=None, ls_off=0, lr_min=1e-5, lr_max=1e-2,
                   mirrors=None):
-        """`step_fused` together with the sums in front of it (bg_update_tail: two launches for four): wgrad = (descriptor array, count) of a weight-gradient
-        launch made without its finish (GroupedWeightGrad.run(..., partial=True)) or None, reductions = the deferred _lib.ReduceProblem descriptors."""
+        """`step_fused` together with the sums in front of it (bg_update_tail: two launches for four); wgrad, reductions: see _sums_args."""
         self.step_count += 1
-        warr, wn = wgrad if wgrad is not None else (None, 0)
-        rarr = (_lib.ReduceProblem * len(reductions))(*reductions) if reductions else None
-        _lib.check(_lib.load().bg_update_tail(warr, wn, rarr, len(reductions) if reductions else 0, self.flat.numel(), _lib.ptr(self.flat), _lib.ptr(self.grad),
-                                              _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(self.lr), self.step_count, self.betas[0], self.betas[1],
-                                              self.eps, self.max_grad_norm, _lib.ptr(grad_logstd), int(ls_off), 0 if grad_logstd is None else grad_logstd.numel(),
-                                              _lib.ptr(stats), _lib.ptr(stats_acc), _lib.ptr(stats_last), stats.numel(), int(kl_index), float(count), desired_kl,
-                                              lr_min, lr_max, _lib.ptr(self._tail_sync), _lib.ptr(self._tail_norm),
+        args = self._opt_args(stats, stats_acc, stats_last, kl_index, count, desired_kl, grad_logstd, ls_off, lr_min, lr_max)
+        _lib.check(_lib.load().bg_update_tail(*self._sums_args(wgrad, reductions), *args, _lib.ptr(self._tail_sync), _lib.ptr(self._tail_norm),
                                               None if mirrors is None else ctypes.addressof(mirrors), 0 if mirrors is None else len(mirrors),
                                               _lib.current_stream_ptr()), "bg_update_tail")
 
     def tail_sums(self, wgrad, reductions):
         """Launch (1) of `step_tail` alone (bg_update_tail_sums): the ranks of a multi-GPU job average the gradient between the sums and `step_fused`."""
-        warr, wn = wgrad if wgrad is not None else (None, 0)
-        rarr = (_lib.ReduceProblem * len(reductions))(*reductions) if reductions else None
-        _lib.check(_lib.load().bg_update_tail_sums(warr, wn, rarr, len(reductions) if reductions else 0, _lib.ptr(self._tail_norm), _lib.current_stream_ptr()),
+        _lib.check(_lib.load().bg_update_tail_sums(*self._sums_args(wgrad, reductions), _lib.ptr(self._tail_norm), _lib.current_stream_ptr()),
                    "bg_update_tail_sums")
 
     def adapt_lr(self, kl_sum, count, desired_kl, lr_min=1e-5, lr_max=1e-2):

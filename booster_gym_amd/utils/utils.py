@@ -155,18 +155,12 @@ def actor_head_loss_backward(h, weight, bias, logstd, actions, old_mu, old_logst
     stats) are left to a later bg_reduce_group call on the descriptor written into `finish`; g_hidden is complete either way."""
     _need_cuda(h, weight, bias, logstd, actions, old_mu, old_logstd, old_logp, adv, adv_stats, g_hidden, grad_weight, grad_bias, grad_bias_hidden,
                grad_logstd, stats, scratch)
+    args = [_lib.ptr(t) for t in (h, weight, bias, logstd, actions, old_mu, old_logstd, old_logp, adv, adv_stats)] + [e_clip, bound_coef, entropy_coef]
+    args += [_lib.ptr(t) for t in (mu_out, g_hidden, grad_weight, grad_bias, grad_bias_hidden, grad_logstd, stats, scratch)]
     if finish is not None:
-        _lib.check(_lib.load().bg_actor_head_partial(h.shape[0], _lib.ptr(h), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(logstd), _lib.ptr(actions),
-                                                     _lib.ptr(old_mu), _lib.ptr(old_logstd), _lib.ptr(old_logp), _lib.ptr(adv), _lib.ptr(adv_stats), e_clip,
-                                                     bound_coef, entropy_coef, _lib.ptr(mu_out), _lib.ptr(g_hidden), _lib.ptr(grad_weight), _lib.ptr(grad_bias),
-                                                     _lib.ptr(grad_bias_hidden), _lib.ptr(grad_logstd), _lib.ptr(stats), _lib.ptr(scratch), finish,
-                                                     _lib.current_stream_ptr()), "bg_actor_head_partial")
-        return
-    _lib.check(_lib.load().bg_actor_head(h.shape[0], 1, _lib.ptr(h), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(logstd), _lib.ptr(actions),
-                                         _lib.ptr(old_mu), _lib.ptr(old_logstd), _lib.ptr(old_logp), _lib.ptr(adv), _lib.ptr(adv_stats), e_clip,
-                                         bound_coef, entropy_coef, _lib.ptr(mu_out), _lib.ptr(g_hidden), _lib.ptr(grad_weight), _lib.ptr(grad_bias),
-                                         _lib.ptr(grad_bias_hidden), _lib.ptr(grad_logstd), _lib.ptr(stats), _lib.ptr(scratch),
-                                         _lib.current_stream_ptr()), "bg_actor_head")
+        _lib.check(_lib.load().bg_actor_head_partial(h.shape[0], *args, finish, _lib.current_stream_ptr()), "bg_actor_head_partial")
+    else:
+        _lib.check(_lib.load().bg_actor_head(h.shape[0], 1, *args, _lib.current_stream_ptr()), "bg_actor_head")
 
 
 def actor_head_sym_loss_backward(h, weight, bias, logstd, actions, old_mu, old_logstd, old_logp, adv, adv_stats, e_clip, bound_coef, entropy_coef,
@@ -209,14 +203,11 @@ def critic_head_backward(h, weight, values, returns, g_hidden, grad_weight, grad
     """Backward of mean((values - returns)^2) (runner.py:148) through the 128 -> 1 output layer; stats[0] += sum of squared errors.
     finish: as for actor_head_loss_backward."""
     _need_cuda(h, weight, values, returns, g_hidden, grad_weight, grad_bias, grad_bias_hidden, stats, scratch)
+    args = [h.shape[0]] + [_lib.ptr(t) for t in (h, weight, values, returns, g_hidden, grad_weight, grad_bias, grad_bias_hidden, stats, scratch)]
     if finish is not None:
-        _lib.check(_lib.load().bg_critic_head_backward_partial(h.shape[0], _lib.ptr(h), _lib.ptr(weight), _lib.ptr(values), _lib.ptr(returns), _lib.ptr(g_hidden),
-                                                               _lib.ptr(grad_weight), _lib.ptr(grad_bias), _lib.ptr(grad_bias_hidden), _lib.ptr(stats),
-                                                               _lib.ptr(scratch), finish, _lib.current_stream_ptr()), "bg_critic_head_backward_partial")
-        return
-    _lib.check(_lib.load().bg_critic_head_backward(h.shape[0], _lib.ptr(h), _lib.ptr(weight), _lib.ptr(values), _lib.ptr(returns), _lib.ptr(g_hidden),
-                                                   _lib.ptr(grad_weight), _lib.ptr(grad_bias), _lib.ptr(grad_bias_hidden), _lib.ptr(stats),
-                                                   _lib.ptr(scratch), _lib.current_stream_ptr()), "bg_critic_head_backward")
+        _lib.check(_lib.load().bg_critic_head_backward_partial(*args, finish, _lib.current_stream_ptr()), "bg_critic_head_backward_partial")
+    else:
+        _lib.check(_lib.load().bg_critic_head_backward(*args, _lib.current_stream_ptr()), "bg_critic_head_backward")
 
 
 def reduce_group(problems):

@@ -212,3 +212,90 @@ def test_critic_values_and_gae_in_one_launch_equal_the_separate_launches(T, N):
         with pytest.raises(RuntimeError, match="horizon"):
             critic_values_gae(torch.zeros(34 * N, 128, device=dev), w, b, big, big.bool(), big.bool(), 0.99, 0.95, torch.zeros(34 * N, device=dev), big.clone(),
                               big.clone(), s1, scratch)
+
+
+def test_tail_sums_equal_the_separate_launches_bit_for_bit():
+    """bg_update_tail_sums (one launch: the default plan) against bg_reduce_group + the grouped weight gradients' own finish (the ranks of a multi-GPU
+    job, BG_ONE_LAUNCH_TAIL=0) on copies of the same partial sums: every gradient and every statistic bit for bit.  Head partials of B = 1,000 rows
+    (not a multiple of the 64-row tile); weight-gradient partials of two layers at M = 256: 3 slices of a zero-padded first layer (47 of 64 input
+    columns) and 17 slices (the 16 slice groups' strided loop takes a second turn).  The slots of norm_scratch add up to the squares of what was
+    written: float64 sums of ~50,000 float64 squares in two orders, 1e-12 relative."""
+    import ctypes as C
+
+    from booster_gym_amd import _lib
+    from booster_gym_amd.utils.utils import actor_head_loss_backward, critic_head_backward, head_scratch, reduce_group
+
+    lib = _lib.load()
+    B, A, M = 1000, 12, 256
+    g, dev, h, W, b = _data(B, 5)
+    logstd = torch.full((A,), -2.0, device=dev) + 0.1 * torch.randn(A, generator=g).to(dev)
+    old_logstd = torch.full((A,), -2.0, device=dev)
+    old_mu = h @ W.t() + b + 0.02 * torch.randn(B, A, generator=g).to(dev)
+    actions = old_mu + 0.135 * torch.randn(B, A, generator=g).to(dev)
+    old_logp = (-0.5 * ((actions - old_mu) / old_logstd.exp()) ** 2 - old_logstd - 0.9189385332046727).sum(-1)
+    adv = torch.randn(B, generator=g).to(dev)
+    adv_stats = torch.stack([adv.double().sum(), (adv.double() ** 2).sum(), torch.tensor(float(B), dtype=torch.float64, device=dev)])
+    values, returns = torch.randn(B, generator=g).to(dev), torch.randn(B, generator=g).to(dev)
+    layers = [(128, 64, 47, 3), (256, 128, 128, 17)]  # (C_out, C_in, C_in_real, slices)
+    Gs = [torch.randn(M, co, generator=g).to(dev) for co, _, _, _ in layers]
+    As = [torch.randn(M, ci, generator=g).to(dev) for _, ci, _, _ in layers]
+
+    def outputs():
+        nan = lambda *s: torch.full(s, float("nan"), device=dev)
+        return dict(dW=nan(A, 128), db=nan(A), dbh=nan(128), dw=nan(1, 128), dbc=nan(1), dbhc=nan(128), gls=torch.zeros(A, dtype=torch.float64, device=dev),
+                    st=torch.zeros(5, dtype=torch.float64, device=dev), wg=[nan(co, cr) for co, _, cr, _ in layers])
+
+    def wgrad_problems(out, scratch):
+        arr = (_lib.WgradProblem * len(layers))()
+        for q, (co, ci, cr, s), G, Ain, dW, P in zip(arr, layers, Gs, As, out["wg"], scratch):
+            q.G, q.A, q.dW, q.scratch, q.M, q.C_out, q.C_in, q.C_in_real, q.slices, q.tiles_per_workgroup = _lib.ptr(G), _lib.ptr(Ain), _lib.ptr(dW), _lib.ptr(P), M, co, ci, cr, s, 1
+        return arr
+
+    # the partial sums, once: both heads without their finish, the grouped weight gradients without theirs
+    one, two = outputs(), outputs()
+    fa, fc = _lib.ReduceProblem(), _lib.ReduceProblem()
+    sa, sc = head_scratch(dev).zero_(), head_scratch(dev).zero_()
+    gh = torch.empty(B, 128, device=dev)
+    critic_head_backward(h, W[:1].contiguous(), values, returns, gh, one["dw"], one["dbc"], one["dbhc"], one["st"], sc, finish=fc)
+    actor_head_loss_backward(h, W, b, logstd, actions, old_mu, old_logstd, old_logp, adv, adv_stats, 0.2, 1.0, -0.01, gh, one["dW"], one["db"], one["dbh"],
+                             one["gls"], one["st"], sa, finish=fa)
+    P1 = [torch.zeros(s * co * ci, device=dev) for co, ci, _, s in layers]
+    w1 = wgrad_problems(one, P1)
+    _lib.check(lib.bg_mlp_weight_grad_group_partial(w1, len(layers), _lib.current_stream_ptr()), "bg_mlp_weight_grad_group_partial")
+    torch.cuda.synchronize()
+    assert all(torch.isnan(t).all() for t in (one["dW"], one["dw"], *one["wg"])) and (one["st"] == 0).all()  # nothing summed yet
+    # their copies, and the descriptors of the second form on them
+    sa2, sc2, P2 = sa.clone(), sc.clone(), [p.clone() for p in P1]
+
+    def moved(f, scratch, outs, gls, st):
+        f2 = _lib.ReduceProblem()
+        C.memmove(C.addressof(f2), C.addressof(f), C.sizeof(f))
+        f2.partial = _lib.ptr(scratch)
+        for k, t in enumerate(outs):
+            f2.out[k] = _lib.ptr(t)
+        f2.grad_logstd, f2.stats = _lib.ptr(gls), _lib.ptr(st)
+        return f2
+
+    fc2 = moved(fc, sc2, (two["dw"], two["dbhc"], two["dbc"]), None, two["st"])
+    fa2 = moved(fa, sa2, (two["dW"], two["dbh"], two["db"]), two["gls"], two["st"])
+    # (1) the separate launches: bg_reduce_group, and the grouped launch with its own finish (its main kernel writes the partials again: the same bits)
+    reduce_group([fc, fa])
+    _lib.check(lib.bg_mlp_weight_grad_group(w1, len(layers), _lib.current_stream_ptr()), "bg_mlp_weight_grad_group")
+    # (2) one launch on the copies
+    norm = torch.zeros(8192, dtype=torch.float64, device=dev)
+    _lib.check(lib.bg_update_tail_sums(wgrad_problems(two, P2), len(layers), (_lib.ReduceProblem * 2)(fc2, fa2), 2, _lib.ptr(norm), _lib.current_stream_ptr()),
+               "bg_update_tail_sums")
+    torch.cuda.synchronize()
+    for p1, p2 in zip(P1, P2):
+        assert torch.equal(p1, p2)
+    written = []
+    for k in ("dW", "db", "dbh", "dw", "dbc", "dbhc", "gls", "st"):
+        assert torch.isfinite(two[k]).all() and torch.equal(one[k], two[k]), k
+        written += [two[k]] if k not in ("gls", "st") else []
+    for k, (x, y) in enumerate(zip(one["wg"], two["wg"])):
+        assert torch.isfinite(y).all() and torch.equal(x, y), k
+        written.append(y)
+    assert one["st"][0] > 0 and one["st"][4] > 0 and (one["gls"] != 0).all()  # (value error, KL, dL/dlogstd: the statistics blocks ran)
+    sq = sum((t.double() ** 2).sum() for t in written)
+    print(f"norm slots {norm.sum().item():.17g}, squares of the written gradients {sq.item():.17g}")
+    assert abs(norm.sum().item() - sq.item()) <= 1e-12 * sq.item()

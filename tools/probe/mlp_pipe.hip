@@ -27,14 +27,7 @@
 // global_load_lds) + 18 KB wave-private transposition blocks (they can no longer alias the staging buffer: the next item is already using it).
 #include <hip/hip_runtime.h>
 
-#include "../../include/booster_gym_amd.h"  // (built by tools/mlp_pipe_probe.py from tools/probe/)
-
-static int bg_set_error(int code, const char*) { return code; }
-#define HIP_OK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) return bg_set_error(-2, hipGetErrorString(_e));               \
-    } while (0)
+static int bg_set_error(int code, const char*) { return code; }  // (built by tools/mlp_pipe_probe.py from tools/probe/, outside the library)
 #include "../../booster_gym_amd/csrc/bg_mlp_tile.h"
 
 namespace {
