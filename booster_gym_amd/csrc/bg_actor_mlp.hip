@@ -179,14 +179,16 @@ __global__ __launch_bounds__(256) void actor_mlp_sample_kernel(int N, const floa
 
 // bg_distill_act: nets.n[0] = the teacher (workgroups [0, nb): the longer network first), nets.n[1] = the student (workgroups [nb, 2 nb)).  Both read
 // rows of `stride` floats (the student's 47 H columns are a prefix of the teacher's 47 H + P); the teacher writes its mean, the student samples.
+// bg_distill_act_hist: the student half reads its own rows `sobs` of `sstride` floats (its longer history [47 Hs]); bg_distill_act passes the teacher's.
 struct DistillNets { ActorNet n[2]; };
 template <int MAXW>
-__global__ __launch_bounds__(256) void distill_act_kernel(int N, int nb, const float* __restrict__ obs, int stride, DistillNets nets,
-                                                          const float* __restrict__ logstd, uint64_t seed, uint32_t counter, float* __restrict__ student_mu,
+__global__ __launch_bounds__(256) void distill_act_kernel(int N, int nb, const float* __restrict__ obs, int stride, const float* __restrict__ sobs, int sstride,
+                                                          DistillNets nets, const float* __restrict__ logstd, uint64_t seed, uint32_t counter, float* __restrict__ student_mu,
                                                           float* __restrict__ act_out, float* __restrict__ teacher_mu) {
     const bool teacher = (int)blockIdx.x < nb;
     const int r0 = (teacher ? blockIdx.x : blockIdx.x - nb) * MR;
-    actor_rows<MAXW>(N, r0, obs, stride, nets.n[teacher ? 0 : 1], logstd, seed, counter, teacher ? teacher_mu : student_mu, teacher ? nullptr : act_out);
+    actor_rows<MAXW>(N, r0, teacher ? obs : sobs, teacher ? stride : sstride, nets.n[teacher ? 0 : 1], logstd, seed, counter, teacher ? teacher_mu : student_mu,
+                     teacher ? nullptr : act_out);
 }
 
 }  // namespace
@@ -242,27 +244,57 @@ extern "C" int bg_actor_sample_mlp_scan(int32_t N, const float* obs, int32_t n_l
     return sample_mlp(N, obs, n_layers, layers, scan_points, logstd, seed, counter, mu, actions, stream);
 }
 
-extern "C" int bg_distill_act(int32_t N, const float* obs, int32_t obs_stride, int32_t n_student, const bg_mlp_layer_desc* student, int32_t n_teacher,
-                              const bg_mlp_layer_desc* teacher, int32_t scan_points, const float* student_logstd, uint64_t seed, uint64_t counter,
-                              float* student_mu, float* actions, float* teacher_mu, void* stream) {
-    if (N <= 0 || !obs || !student || !teacher || !student_logstd || !actions || !teacher_mu) return bg_set_error(-1, "bg_distill_act: bad argument");
-    if (scan_points < 0 || scan_points > BG_MAX_HEIGHT_SCAN_POINTS) return bg_set_error(-1, "bg_distill_act: bad argument (scan_points)");
+// Both distillation entry points: hist = bg_distill_act_hist (the student's own buffer), else bg_distill_act (sobs = obs, sstride = stride).
+static int distill_act(bool hist, int32_t N, const float* obs, int32_t stride, const float* sobs, int32_t sstride, int32_t n_student, const bg_mlp_layer_desc* student,
+                       int32_t n_teacher, const bg_mlp_layer_desc* teacher, int32_t scan_points, const float* student_logstd, uint64_t seed, uint64_t counter,
+                       float* student_mu, float* actions, float* teacher_mu, void* stream) {
+    const std::string who(hist ? "bg_distill_act_hist" : "bg_distill_act");
+    if (N <= 0 || !obs || !sobs || !student || !teacher || !student_logstd || !actions || !teacher_mu) return bg_set_error(-1, (who + ": bad argument").c_str());
+    if (scan_points < 0 || scan_points > BG_MAX_HEIGHT_SCAN_POINTS) return bg_set_error(-1, (who + ": bad argument (scan_points)").c_str());
     DistillNets nets;
     int maxw_t = 0, maxw_s = 0;
-    if (const int rc = fill_net("bg_distill_act (teacher)", n_teacher, teacher, scan_points, nets.n[0], maxw_t)) return rc;
-    if (const int rc = fill_net("bg_distill_act (student)", n_student, student, 0, nets.n[1], maxw_s)) return rc;
-    if (obs_stride != teacher[0].in)
-        return bg_set_error(-4, "bg_distill_act: obs_stride must equal the teacher's first-layer input (47 H + scan_points columns per row)");
-    if (student[0].in != teacher[0].in - scan_points)
-        return bg_set_error(-4, "bg_distill_act: the student's first layer takes the 47 H observation columns in front of the teacher's scan_points");
+    if (const int rc = fill_net((who + " (teacher)").c_str(), n_teacher, teacher, scan_points, nets.n[0], maxw_t)) return rc;
+    if (const int rc = fill_net((who + " (student)").c_str(), n_student, student, 0, nets.n[1], maxw_s)) return rc;
+    if (!hist) {
+        if (stride != teacher[0].in)
+            return bg_set_error(-4, "bg_distill_act: obs_stride must equal the teacher's first-layer input (47 H + scan_points columns per row)");
+        if (student[0].in != teacher[0].in - scan_points)
+            return bg_set_error(-4, "bg_distill_act: the student's first layer takes the 47 H observation columns in front of the teacher's scan_points");
+    } else {
+        if (stride != teacher[0].in)
+            return bg_set_error(-4, "bg_distill_act_hist: teacher_stride must equal the teacher's first-layer input (47 H + scan_points columns per row)");
+        // (the student on the teacher's own rows, same buffer and same stride: bg_distill_act's case, its prefix rule)
+        if (sobs == obs && sstride == stride ? student[0].in != teacher[0].in - scan_points : sstride != student[0].in)
+            return bg_set_error(-4, "bg_distill_act_hist: student_stride must equal the student's first-layer input (47 Hs columns per row; or, on the teacher's "
+                                    "buffer at the teacher's stride, the student's first layer takes the teacher's 47 H columns)");
+        if (student[0].in < teacher[0].in - scan_points)
+            return bg_set_error(-4, "bg_distill_act_hist: the student's first layer (47 Hs) must take at least the teacher's 47 H observation columns");
+    }
     const int nb = (N + MR - 1) / MR;
     const dim3 grid(2 * nb), block(256);
     hipStream_t st = (hipStream_t)stream;
-    const int kp = (teacher[0].in + KC - 1) / KC * KC, maxw = maxw_t > maxw_s ? maxw_t : maxw_s;  // one LDS form for both halves: the wider one's
+    // one LDS form for both halves: the wider input tile of the two (the student's with a longer history) and the wider hidden layer of the two
+    const int kin = teacher[0].in > student[0].in ? teacher[0].in : student[0].in;
+    const int kp = (kin + KC - 1) / KC * KC, maxw = maxw_t > maxw_s ? maxw_t : maxw_s;
     if (maxw <= 256 && kp <= 256)
-        hipLaunchKernelGGL(distill_act_kernel<256>, grid, block, 0, st, N, nb, obs, obs_stride, nets, student_logstd, seed, (uint32_t)counter, student_mu, actions, teacher_mu);
+        hipLaunchKernelGGL(distill_act_kernel<256>, grid, block, 0, st, N, nb, obs, stride, sobs, sstride, nets, student_logstd, seed, (uint32_t)counter, student_mu, actions, teacher_mu);
     else
-        hipLaunchKernelGGL(distill_act_kernel<512>, grid, block, 0, st, N, nb, obs, obs_stride, nets, student_logstd, seed, (uint32_t)counter, student_mu, actions, teacher_mu);
+        hipLaunchKernelGGL(distill_act_kernel<512>, grid, block, 0, st, N, nb, obs, stride, sobs, sstride, nets, student_logstd, seed, (uint32_t)counter, student_mu, actions, teacher_mu);
     HIP_OK(hipGetLastError());
     return 0;
+}
+
+extern "C" int bg_distill_act(int32_t N, const float* obs, int32_t obs_stride, int32_t n_student, const bg_mlp_layer_desc* student, int32_t n_teacher,
+                              const bg_mlp_layer_desc* teacher, int32_t scan_points, const float* student_logstd, uint64_t seed, uint64_t counter,
+                              float* student_mu, float* actions, float* teacher_mu, void* stream) {
+    return distill_act(false, N, obs, obs_stride, obs, obs_stride, n_student, student, n_teacher, teacher, scan_points, student_logstd, seed, counter, student_mu,
+                       actions, teacher_mu, stream);
+}
+
+extern "C" int bg_distill_act_hist(int32_t N, const float* teacher_obs, int32_t teacher_stride, const float* student_obs, int32_t student_stride, int32_t n_student,
+                                   const bg_mlp_layer_desc* student, int32_t n_teacher, const bg_mlp_layer_desc* teacher, int32_t scan_points,
+                                   const float* student_logstd, uint64_t seed, uint64_t counter, float* student_mu, float* actions, float* teacher_mu,
+                                   void* stream) {
+    return distill_act(true, N, teacher_obs, teacher_stride, student_obs, student_stride, n_student, student, n_teacher, teacher, scan_points, student_logstd, seed,
+                       counter, student_mu, actions, teacher_mu, stream);
 }

@@ -46,6 +46,8 @@ struct bg_env {
     float* scan_xy = nullptr; // height scan: [P][2] points in the robot's yaw frame (cfg.height_scan_points > 0 only)
     float* hist = nullptr;    // observation history: ring [H][n][47] of the last H single observations (cfg.frame_stack = H > 1, or cfg.actor_heights at any H)
     int hist_head = 0;        // ... the plane of the newest one: the env-step kernels of a launch sequence write their observations there
+    int hist_planes = 0;      // R, the planes of the ring: cfg.frame_stack, or cfg.student_frame_stack = Hs when that is on
+    float* student_bound = nullptr;  // [n][47 Hs]: the student's row of bg_env_reset / bg_env_step (bg_env_bind_student_obs), the caller's
     ModelDev* model_dev = nullptr;
     PairModel* pair_dev = nullptr;  // the leg constants with the two legs side by side (packed ABA kernel)
     int16_t* hf = nullptr;
@@ -224,11 +226,25 @@ __global__ __launch_bounds__(STACK_BLOCK) void bg_obs_stack(int n, int H, int he
 // consecutive addresses over the block's rows, so the destination leaves in whole lines.  A frame element is copied from the ring as in
 // bg_obs_stack (a thread writes only the ring element it alone reads); a scan element computes its ground height once, stores v S to the
 // privileged row and v S + S n_p to the actor's.  Dynamic LDS: ASM_ENVS x P floats with a noise spec, none without.
+//
+// STUDENT (cfg.student_frame_stack = Hs, distillation's longer history): the ring has R = Hs >= H planes and the launch writes a third output, the
+// student's row [47 R] of each env = all R planes oldest first, bg_obs_stack's layout and reset rule at R frames.  The block's ASM_ENVS student rows are
+// contiguous in `sdst` as its actor rows are in `dst`, so a second loop of the same shape (one thread per destination element, consecutive lanes on
+// consecutive addresses) sends them out in whole lines; the reset flags are the ones already in LDS.  The actor's frame k of H is then plane
+// head - (H - 1 - k) (mod R), which is head + 1 + k (mod H) only at R = H.  Two rows now map to one ring element, so "a thread writes only the ring
+// element it alone reads" no longer holds by itself.  The invariant with STUDENT, by construction:
+//   - nobody writes plane `head` here (both rows read it), and nobody writes any plane of an env that was not reset: those are read-only in this launch;
+//   - for a reset env NO thread reads an older plane: both rows take the constant 0 for their older frames;
+//   - the student-row threads of a reset env, one per element of its R - 1 older planes (the student's row covers every plane), store the zeros, each
+//     thread one element that no other thread of the launch touches;
+//   - the actor-row threads of a reset env neither read nor write the older planes (their H - 1 older frames lie among the R - 1 the student row zeroes).
+// So no ring element is read after another thread has changed it, and none is written twice.  STUDENT is a template parameter, not a uniform branch:
+// the instantiations without it keep today's code (head + 1 + k mod H, the single loop) and today's registers, and the extra arguments are unused there.
 constexpr int ASM_BLOCK = 256, ASM_ENVS = 4;
-template <bool H16>
+template <bool H16, bool STUDENT = false>
 __global__ __launch_bounds__(ASM_BLOCK) void bg_obs_assemble(EnvDev E, const float2* __restrict__ pts, int P, int H, int head, int all_reset, uint32_t step,
                                                              uint32_t stream0, float* ring, const uint8_t* __restrict__ done, float* __restrict__ dst,
-                                                             float* __restrict__ priv, int stride) {
+                                                             float* __restrict__ priv, int stride, int R, float* __restrict__ sdst) {
     __shared__ float s_pose[ASM_ENVS][6];  // base x, y, z, sin yaw, cos yaw, reset in this step
     extern __shared__ float s_noise[];     // [ASM_ENVS][P]: S n_p
     const int n = E.n, e0 = blockIdx.x * ASM_ENVS, rows = min(ASM_ENVS, n - e0);
@@ -269,12 +285,18 @@ __global__ __launch_bounds__(ASM_BLOCK) void bg_obs_assemble(EnvDev E, const flo
         float v;
         if (col < F) {
             const unsigned k = col / BG_NUM_OBS, c = col - k * BG_NUM_OBS;
-            unsigned slot = (unsigned)head + 1u + k;  // frame k = the observation of H - 1 - k steps ago
-            if (slot >= (unsigned)H) slot -= (unsigned)H;
-            float* src = ring + ((size_t)slot * n + e) * BG_NUM_OBS + c;
-            v = 0.f;
-            if (k + 1u == (unsigned)H || sp[5] == 0.f) v = *src;
-            else *src = 0.f;
+            if (STUDENT) {  // frame k = the observation of H - 1 - k steps ago = plane head - (H - 1 - k) mod R; read only (the invariant above)
+                unsigned slot = (unsigned)head + (unsigned)R - ((unsigned)H - 1u - k);
+                if (slot >= (unsigned)R) slot -= (unsigned)R;
+                v = (k + 1u == (unsigned)H || sp[5] == 0.f) ? ring[((size_t)slot * n + e) * BG_NUM_OBS + c] : 0.f;
+            } else {
+                unsigned slot = (unsigned)head + 1u + k;  // frame k = the observation of H - 1 - k steps ago
+                if (slot >= (unsigned)H) slot -= (unsigned)H;
+                float* src = ring + ((size_t)slot * n + e) * BG_NUM_OBS + c;
+                v = 0.f;
+                if (k + 1u == (unsigned)H || sp[5] == 0.f) v = *src;
+                else *src = 0.f;
+            }
         } else {
             const unsigned p = col - F;
             const float2 pt = pts[p];
@@ -285,6 +307,20 @@ __global__ __launch_bounds__(ASM_BLOCK) void bg_obs_assemble(EnvDev E, const flo
             v = spec.mode != 0 ? clean + s_noise[el * (unsigned)P + p] : clean;
         }
         dst[(size_t)e0 * W + t] = v;
+    }
+    if (STUDENT) {  // the student's rows [47 R]: every plane, oldest first; the only threads that zero a reset env's older planes
+        const unsigned Ws = (unsigned)(BG_NUM_OBS * R);  // (n Ws < 2^31: bg_env_create)
+        for (unsigned t = threadIdx.x; t < (unsigned)rows * Ws; t += ASM_BLOCK) {
+            const unsigned el = t / Ws, col = t - el * Ws, e = (unsigned)e0 + el;
+            const unsigned k = col / BG_NUM_OBS, c = col - k * BG_NUM_OBS;
+            unsigned slot = (unsigned)head + 1u + k;  // frame k = the observation of R - 1 - k steps ago
+            if (slot >= (unsigned)R) slot -= (unsigned)R;
+            float* src = ring + ((size_t)slot * n + e) * BG_NUM_OBS + c;
+            float v = 0.f;
+            if (k + 1u == (unsigned)R || s_pose[el][5] == 0.f) v = *src;
+            else *src = 0.f;
+            sdst[(size_t)e0 * Ws + t] = v;
+        }
     }
 }
 
@@ -847,7 +883,8 @@ static int env_create_fill(bg_env* e, const bg_env_cfg* cfg, const bg_model* mod
     }
     if (cfg->actor_heights && cfg->frame_stack == 0) e->cfg.frame_stack = 1;  // (a ring of one plane; without the key the field stays as passed)
     if (cfg->frame_stack > 1 || cfg->actor_heights) {  // the ring of single observations, all zeros: an env that has never been reset has an empty history
-        const size_t hb = sizeof(float) * (size_t)e->cfg.frame_stack * n * BG_NUM_OBS;
+        e->hist_planes = cfg->student_frame_stack ? cfg->student_frame_stack : e->cfg.frame_stack;  // (the student's longer history: R = Hs planes)
+        const size_t hb = sizeof(float) * (size_t)e->hist_planes * n * BG_NUM_OBS;
         HIP_OK(hipMalloc(&e->hist, hb));
         HIP_OK(hipMemset(e->hist, 0, hb));
     }
@@ -897,6 +934,9 @@ extern "C" int bg_env_create(const bg_env_cfg* cfg, const bg_model* model, bg_en
         return fail(-1, "bg_env_create: frame_stack must be 1 .. BG_MAX_FRAME_STACK (0 = 1: no history) with num_envs x 47 x frame_stack below 2^31");
     if (cfg->actor_heights && (cfg->height_scan_points <= 0 || (int64_t)cfg->num_envs * (BG_NUM_OBS * (cfg->frame_stack > 1 ? cfg->frame_stack : 1) + cfg->height_scan_points) >= (int64_t)1 << 31))
         return fail(-1, "bg_env_create: actor_heights needs the height scan's points (height_scan_points > 0) with num_envs x (47 x frame_stack + points) below 2^31");
+    if (cfg->student_frame_stack != 0 && (!cfg->actor_heights || cfg->student_frame_stack < (cfg->frame_stack > 1 ? cfg->frame_stack : 1) || cfg->student_frame_stack > BG_MAX_FRAME_STACK ||
+                                          (int64_t)cfg->num_envs * BG_NUM_OBS * cfg->student_frame_stack >= (int64_t)1 << 31))
+        return fail(-1, "bg_env_create: student_frame_stack needs actor_heights and a value in frame_stack .. BG_MAX_FRAME_STACK (0 = off) with num_envs x 47 x student_frame_stack below 2^31");
     int ndev = 0;
     hipError_t de = hipGetDeviceCount(&ndev);
     if (de != hipSuccess || ndev == 0) return fail(-3, "bg_env_create: no HIP device available (this library has no CPU path)");
@@ -961,11 +1001,21 @@ extern "C" int bg_env_bind_outputs(bg_env* e, float* obs, float* priv, float* re
     return 0;
 }
 
-static int launch_step(bg_env* e, const float* actions, int mode, const StepOut& dst, void* stream) {
+extern "C" int bg_env_bind_student_obs(bg_env* e, float* student_obs) {
+    if (!e || !student_obs) return fail(-1, "bg_env_bind_student_obs: null argument");
+    if (!e->cfg.student_frame_stack) return fail(-1, "bg_env_bind_student_obs: the env has no student row (bg_env_cfg.student_frame_stack is 0)");
+    e->student_bound = student_obs;
+    return 0;
+}
+
+// student: the destination of the student's row [n][47 Hs] (cfg.student_frame_stack), required exactly when the field is on
+static int launch_step(bg_env* e, const float* actions, int mode, const StepOut& dst, float* student, void* stream) {
     if (!dst.obs || !dst.priv || !dst.rew || !dst.done || !dst.tout) return fail(-1, "bg_env_step: outputs are not bound");
+    if (e->cfg.student_frame_stack && !student)
+        return fail(-1, "bg_env_step: student_frame_stack is on and the student's row has no destination (bg_env_bind_student_obs, bg_env_step_to_student)");
     StepOut out = dst;
     if (e->hist) {  // observation history: this sequence's 47-wide observation rows go to the next plane of the ring, bg_obs_stack / bg_obs_assemble writes dst.obs
-        e->hist_head = (e->hist_head + 1) % e->cfg.frame_stack;
+        e->hist_head = (e->hist_head + 1) % e->hist_planes;
         out.obs = e->hist + (size_t)e->hist_head * e->n * BG_NUM_OBS;
     }
     dim3 grid((e->n + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK), block(64);
@@ -1006,8 +1056,12 @@ static int launch_step(bg_env* e, const float* actions, int mode, const StepOut&
         dim3 gs((unsigned)((e->n + ASM_ENVS - 1) / ASM_ENVS));
         const uint32_t base = mode ? (uint32_t)bg::RS_SCAN_RESET : (uint32_t)bg::RS_SCAN;
         const size_t lds = e->cfg.noise_height_measurements.mode != 0 ? sizeof(float) * ASM_ENVS * P : 0;  // (at most 16 kB: P <= 1024)
-        if (e->h) hipLaunchKernelGGL(bg_obs_assemble<true>, gs, dim3(ASM_BLOCK), lds, st, env_dev(e), (const float2*)e->scan_xy, P, H, e->hist_head, mode, cnt, base, e->hist, (const uint8_t*)out.done, dst.obs, out.priv, out.priv_stride);
-        else hipLaunchKernelGGL(bg_obs_assemble<false>, gs, dim3(ASM_BLOCK), lds, st, env_dev(e), (const float2*)e->scan_xy, P, H, e->hist_head, mode, cnt, base, e->hist, (const uint8_t*)out.done, dst.obs, out.priv, out.priv_stride);
+        const int R = e->hist_planes;
+        if (e->cfg.student_frame_stack) {  // the same one launch, with the student's row as its third output
+            if (e->h) hipLaunchKernelGGL((bg_obs_assemble<true, true>), gs, dim3(ASM_BLOCK), lds, st, env_dev(e), (const float2*)e->scan_xy, P, H, e->hist_head, mode, cnt, base, e->hist, (const uint8_t*)out.done, dst.obs, out.priv, out.priv_stride, R, student);
+            else hipLaunchKernelGGL((bg_obs_assemble<false, true>), gs, dim3(ASM_BLOCK), lds, st, env_dev(e), (const float2*)e->scan_xy, P, H, e->hist_head, mode, cnt, base, e->hist, (const uint8_t*)out.done, dst.obs, out.priv, out.priv_stride, R, student);
+        } else if (e->h) hipLaunchKernelGGL((bg_obs_assemble<true, false>), gs, dim3(ASM_BLOCK), lds, st, env_dev(e), (const float2*)e->scan_xy, P, H, e->hist_head, mode, cnt, base, e->hist, (const uint8_t*)out.done, dst.obs, out.priv, out.priv_stride, R, student);
+        else hipLaunchKernelGGL((bg_obs_assemble<false, false>), gs, dim3(ASM_BLOCK), lds, st, env_dev(e), (const float2*)e->scan_xy, P, H, e->hist_head, mode, cnt, base, e->hist, (const uint8_t*)out.done, dst.obs, out.priv, out.priv_stride, R, student);
     } else if (e->scan_xy) {  // the critic's height scan from the state this launch sequence has just stored (bg_height_scan)
         const int P = e->cfg.height_scan_points;
         dim3 gs((unsigned)(((int64_t)e->n * P + SCAN_BLOCK - 1) / SCAN_BLOCK));
@@ -1027,11 +1081,11 @@ static int launch_step(bg_env* e, const float* actions, int mode, const StepOut&
 
 extern "C" int bg_env_reset(bg_env* e, void* stream) {
     if (!e) return fail(-1, "bg_env_reset: null env");
-    return launch_step(e, nullptr, 1, e->bound, stream);
+    return launch_step(e, nullptr, 1, e->bound, e->student_bound, stream);
 }
 extern "C" int bg_env_step(bg_env* e, const float* actions, void* stream) {
     if (!e || !actions) return fail(-1, "bg_env_step: null argument");
-    int r = launch_step(e, actions, 0, e->bound, stream);
+    int r = launch_step(e, actions, 0, e->bound, e->student_bound, stream);
     if (r == 0) e->step_count++;
     return r;
 }
@@ -1039,7 +1093,17 @@ extern "C" int bg_env_step_to(bg_env* e, const float* actions, float* obs, float
     if (!e || !actions) return fail(-1, "bg_env_step_to: null argument");
     StepOut o = e->bound;
     o.obs = obs; o.priv = priv; o.rew = rew; o.done = done; o.tout = tout;
-    int r = launch_step(e, actions, 0, o, stream);
+    int r = launch_step(e, actions, 0, o, nullptr, stream);  // (with cfg.student_frame_stack: an error, this call names no destination for that row)
+    if (r == 0) e->step_count++;
+    return r;
+}
+extern "C" int bg_env_step_to_student(bg_env* e, const float* actions, float* obs, float* priv, float* rew, uint8_t* done, uint8_t* tout, float* student_obs,
+                                      void* stream) {
+    if (!e || !actions) return fail(-1, "bg_env_step_to_student: null argument");
+    if (!e->cfg.student_frame_stack) return fail(-1, "bg_env_step_to_student: the env has no student row (bg_env_cfg.student_frame_stack is 0)");
+    StepOut o = e->bound;
+    o.obs = obs; o.priv = priv; o.rew = rew; o.done = done; o.tout = tout;
+    int r = launch_step(e, actions, 0, o, student_obs, stream);
     if (r == 0) e->step_count++;
     return r;
 }

@@ -46,6 +46,24 @@ def frame_stack_of(cfg):
     return H
 
 
+def student_frame_stack_of(cfg):
+    """env.student_frame_stack (set by utils/distill.py's Distiller from distillation.student_frame_stack, never shipped in a yaml's env: section;
+    absent or None = 0 = off): the number Hs of single observations in the student's row, a second output of the env beside the actor's
+    [47 H | P].  ValueError naming distillation.student_frame_stack unless it is an integer in env.frame_stack .. MAX_FRAME_STACK with
+    terrain.actor_heights on."""
+    Hs = cfg["env"].get("student_frame_stack")
+    if Hs is None:
+        return 0
+    H = frame_stack_of(cfg)
+    if isinstance(Hs, bool) or not isinstance(Hs, int) or not H <= Hs <= MAX_FRAME_STACK:
+        raise ValueError(f"distillation.student_frame_stack = {Hs!r} must be an integer from env.frame_stack = {H} to {MAX_FRAME_STACK}: the student's "
+                         f"row is the env's last {_lib.NUM_OBS} x student_frame_stack observations, the teacher's {_lib.NUM_OBS} x {H} its newest")
+    if not actor_heights_of(cfg["terrain"]):
+        raise ValueError("distillation.student_frame_stack needs terrain.actor_heights: true: the student's row is an output of the perceptive "
+                         "teacher's env (bg_obs_assemble) only")
+    return Hs
+
+
 def check_env_sizes(cfg, num_height_points):
     """ValueError unless env.num_observations / num_privileged_obs / num_actions are what this build computes: 47 H (H = env.frame_stack single
     observations, 47 without the key; 47 H + P with terrain.actor_heights), 14 (+ P with the terrain height scan's P points: legged_gym requires
@@ -112,6 +130,7 @@ class T1(BaseTask):
     def __init__(self, cfg):
         super().__init__(cfg)
         check_env_sizes(cfg, len(self.terrain.height_points))  # (before anything touches the device)
+        student_frame_stack_of(cfg)
         self._lib = _lib.load()
         self._model = None
         self._env = None
@@ -232,10 +251,14 @@ class T1(BaseTask):
         self.actor_heights = self.terrain.actor_heights
         self.num_scan_obs, self.scan_obs_offset = (P if self.actor_heights else 0), self.num_single_obs * self.frame_stack
         self._wide_obs = self.frame_stack > 1 or self.actor_heights  # (step_to checks the destination's size then only: one attribute on the default path)
+        # the student's longer history (distillation.student_frame_stack through env.student_frame_stack): a second row [47 Hs] per env; 0 = off
+        self.student_frame_stack = student_frame_stack_of(cfg)
+        self.num_student_obs = self.num_single_obs * self.student_frame_stack
         self.dt = cfg["control"]["decimation"] * cfg["sim"]["dt"]
         N, dev = self.num_envs, self.device
         self.obs_buf = torch.zeros(N, self.num_obs, dtype=torch.float, device=dev)
         self.privileged_obs_buf = torch.zeros(N, self.num_privileged_obs, dtype=torch.float, device=dev)
+        self.student_obs_buf = torch.zeros(N, self.num_student_obs, dtype=torch.float, device=dev) if self.student_frame_stack else None
         self.rew_buf = torch.zeros(N, dtype=torch.float, device=dev)
         self.reset_buf = torch.ones(N, dtype=torch.bool, device=dev)
         self.time_out_buf = torch.zeros(N, dtype=torch.bool, device=dev)
@@ -348,6 +371,7 @@ class T1(BaseTask):
                     c.actor_heights = 1
                     setr(c.noise_height_measurements, nc.get("height_measurements"))
         c.frame_stack = self.frame_stack
+        c.student_frame_stack = self.student_frame_stack
         sd = str(cfg["sim"].get("state_dtype", "fp32")).lower()
         if sd not in ("fp32", "float32", "fp16", "float16", "half"):
             raise ValueError(f"sim.state_dtype must be fp32 or fp16, got {sd!r}")
@@ -422,6 +446,9 @@ class T1(BaseTask):
         _lib.check(lib.bg_env_bind_outputs(eh, _lib.ptr(self.obs_buf), _lib.ptr(self.privileged_obs_buf), _lib.ptr(self.rew_buf),
                                            _lib.ptr(self.reset_buf), _lib.ptr(self.time_out_buf), _lib.ptr(self._rew_terms)),
                    "bg_env_bind_outputs")
+        if self.student_frame_stack:
+            _lib.check(lib.bg_env_bind_student_obs(eh, _lib.ptr(self.student_obs_buf)), "bg_env_bind_student_obs")
+            self.extras["student_obs"] = self.student_obs_buf
         if self.terrain.curriculum:
             self._tlevel_sum = torch.zeros(1, dtype=torch.int32, device=self.device)  # where terrain_level_sum() leaves the device's running sum
             self.set_field("terrain_type", torch.from_numpy(self._terrain_init[1]))
@@ -467,18 +494,25 @@ class T1(BaseTask):
             self._stale_time_outs(self.reset_buf, self.time_out_buf)
         return self.obs_buf, self.rew_buf, self.reset_buf, self.extras
 
-    def step_to(self, actions, obs, privileged_obs, rew, done, time_outs):
-        """`step` that writes its per-step outputs straight into rows of the caller's rollout buffers."""
+    def step_to(self, actions, obs, privileged_obs, rew, done, time_outs, student_obs=None):
+        """`step` that writes its per-step outputs straight into rows of the caller's rollout buffers.  student_obs: the destination of the student's
+        row [N][47 Hs], required with env.student_frame_stack and an error without it."""
         a = self._as_actions(actions)
-        for t in (obs, privileged_obs, rew, done, time_outs):
+        for t in (obs, privileged_obs, rew, done, time_outs) + (() if student_obs is None else (student_obs,)):
             if not (t.is_cuda and t.is_contiguous()):
                 raise RuntimeError("step_to needs contiguous CUDA output tensors")
         if privileged_obs.numel() < self.num_envs * self.num_privileged_obs:  # (rows of 14 + P with the height scan)
             raise RuntimeError(f"step_to needs privileged_obs of {self.num_envs} x {self.num_privileged_obs} floats")
         if self._wide_obs and obs.numel() < self.num_envs * self.num_obs:  # (rows of 47 H with a frame stack, + P with the actor's scan)
             raise RuntimeError(f"step_to needs obs of {self.num_envs} x {self.num_obs} floats")
-        _lib.check(self._lib.bg_env_step_to(self._env, _lib.ptr(a), _lib.ptr(obs), _lib.ptr(privileged_obs), _lib.ptr(rew), _lib.ptr(done),
-                                            _lib.ptr(time_outs), _lib.current_stream_ptr()), "bg_env_step_to")
+        if student_obs is not None:  # (the library refuses the call on an env without the row)
+            if student_obs.numel() < self.num_envs * self.num_student_obs:
+                raise RuntimeError(f"step_to needs student_obs of {self.num_envs} x {self.num_student_obs} floats")
+            _lib.check(self._lib.bg_env_step_to_student(self._env, _lib.ptr(a), _lib.ptr(obs), _lib.ptr(privileged_obs), _lib.ptr(rew), _lib.ptr(done),
+                                                        _lib.ptr(time_outs), _lib.ptr(student_obs), _lib.current_stream_ptr()), "bg_env_step_to_student")
+        else:
+            _lib.check(self._lib.bg_env_step_to(self._env, _lib.ptr(a), _lib.ptr(obs), _lib.ptr(privileged_obs), _lib.ptr(rew), _lib.ptr(done),
+                                                _lib.ptr(time_outs), _lib.current_stream_ptr()), "bg_env_step_to")
         if self._stale_tout:
             self._stale_time_outs(done, time_outs)
 

@@ -13,6 +13,12 @@ in training), the teacher labels every visited row with its mean action, and the
 
 The student checkpoint is what Runner, play.py, export_model.py and tools/play_oracle.py load under the config with terrain.actor_heights: false and
 env.num_observations: 47 H: `actor.*`, `logstd` (fixed at log(student_noise_std)) and an UNTRAINED `critic.*` of that config's shape.
+
+distillation.student_frame_stack: Hs > H gives the student a longer history than its teacher has: a blind policy learns about the ground only from
+what its joints and IMU did over the last steps, a perceptive teacher does not need (and with 187 points cannot afford) that history.  The env then
+writes a second row per step, the student's [47 Hs] (env.student_frame_stack; the last 47 H columns are the teacher's first 47 H, noise included), the
+rollout's launch is bg_distill_act_hist (the student half on its own buffer), the update regresses on buffer["student_obses"], and the checkpoint
+re-enters under env.frame_stack: Hs, env.num_observations: 47 Hs.  Absent, null or equal to H: every call is the one described above.
 """
 import argparse
 import math
@@ -25,16 +31,17 @@ import torch
 
 from .. import _lib
 from ..envs import TASKS
+from ..envs.t1 import MAX_CRITIC_INPUT, MAX_FRAME_STACK, frame_stack_of
 from .buffer import ExperienceBuffer
 from .config import load_cfg
 from .model import CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, MLPTrainer, WeightClock, check_hidden, hidden_of, plan_network
 from .recorder import Recorder
 from .runner import FlatAdam, hidden_widths, pad_input, wgrad_products
-from .terrain import actor_heights_of
+from .terrain import actor_heights_of, height_scan_points
 from .utils import head_scratch, reduce_group
 
 DEFAULTS = {"teacher_checkpoint": None, "student_hidden": [256, 128, 128], "num_epochs": 5, "learning_rate": 1.0e-3, "max_grad_norm": 1.0,
-            "student_noise_std": 0.1}
+            "student_noise_std": 0.1, "student_frame_stack": None}
 
 
 class DistillCfg(NamedTuple):
@@ -83,10 +90,37 @@ def distillation_cfg(cfg, world_size=1):
     return DistillCfg(ck, hidden, n, float(v["learning_rate"]), float(v["max_grad_norm"]), float(v["student_noise_std"]))
 
 
+def student_frame_stack_of(cfg):
+    """distillation.student_frame_stack as the number Hs of single observations in the student's row: null or absent = the teacher's env.frame_stack = H.
+    Pure.  ValueError naming the key unless it is an integer in H .. MAX_FRAME_STACK whose student config passes the env's own size check: the
+    student's critic takes 47 Hs + 14 + P columns (P points of terrain.measured_points_x x measured_points_y), MAX_CRITIC_INPUT at most."""
+    H = frame_stack_of(cfg)
+    sec = cfg.get("distillation")
+    Hs = sec.get("student_frame_stack") if isinstance(sec, dict) else None
+    if Hs is None:
+        return H
+    if isinstance(Hs, bool) or not isinstance(Hs, int) or not H <= Hs <= MAX_FRAME_STACK:
+        raise ValueError(f"distillation.student_frame_stack = {Hs!r} must be null or an integer from env.frame_stack = {H} (the teacher's) to "
+                         f"{MAX_FRAME_STACK}: the student sees the env's last student_frame_stack observations, the teacher's {H} among them")
+    P = len(height_scan_points(cfg["terrain"])[1])
+    if _lib.NUM_OBS * Hs + _lib.NUM_PRIV + P > MAX_CRITIC_INPUT:
+        raise ValueError(f"distillation.student_frame_stack = {Hs}: the student's config (env.frame_stack: {Hs}, terrain.actor_heights: false) has a critic of "
+                         f"{_lib.NUM_OBS} x {Hs} + {_lib.NUM_PRIV} + {P} (terrain.measured_points_x x terrain.measured_points_y) = "
+                         f"{_lib.NUM_OBS * Hs + _lib.NUM_PRIV + P} inputs, above {MAX_CRITIC_INPUT} (the widest first layer of the kernels): a smaller "
+                         f"distillation.student_frame_stack, or fewer points of the height scan")
+    return Hs
+
+
 def student_cfg_overrides(cfg):
-    """The overrides under which the student checkpoint re-enters Runner / play.py / export_model.py: the teacher's config without the actor's scan."""
+    """The overrides under which the student checkpoint re-enters Runner / play.py / export_model.py: the teacher's config without the actor's scan,
+    and with distillation.student_frame_stack = Hs > H the student's own history."""
     H = int(cfg["env"].get("frame_stack", 1) or 1)
-    return {"terrain.actor_heights": False, "env.num_observations": _lib.NUM_OBS * H}
+    over = {"terrain.actor_heights": False, "env.num_observations": _lib.NUM_OBS * H}
+    if isinstance(cfg.get("distillation"), dict) and cfg["distillation"].get("student_frame_stack") is not None:
+        Hs = student_frame_stack_of(cfg)
+        if Hs > H:
+            over = {"terrain.actor_heights": False, "env.frame_stack": Hs, "env.num_observations": _lib.NUM_OBS * Hs}
+    return over
 
 
 class Distiller:
@@ -104,12 +138,20 @@ class Distiller:
                 cfg.setdefault("distillation", {})
                 if isinstance(cfg["distillation"], dict):
                     cfg["distillation"]["teacher_checkpoint"] = self.args.teacher
+            if self.args.student_frame_stack is not None:
+                cfg.setdefault("distillation", {})
+                if isinstance(cfg["distillation"], dict):
+                    cfg["distillation"]["student_frame_stack"] = self.args.student_frame_stack
         self.cfg = cfg
         cfg["basic"].setdefault("task", "T1")
         cfg["basic"]["rank"] = self.rank = 0
         self.dcfg = distillation_cfg(cfg, int(os.environ.get("WORLD_SIZE", "1")))  # (ValueError before anything is built)
         if not self.dcfg.teacher_checkpoint:
             raise ValueError("distillation.teacher_checkpoint is not set: the path of a checkpoint trained with terrain.actor_heights (distill.py --teacher=PATH)")
+        Hs, H = student_frame_stack_of(cfg), frame_stack_of(cfg)
+        self.history = Hs > H  # the student's own, longer history: a second row of the env, bg_distill_act_hist
+        if self.history:
+            cfg["env"]["student_frame_stack"] = Hs  # (the env's name of it; T1 builds the ring of Hs planes and the third output of its last launch)
         critic_hidden = hidden_widths(cfg)[1]
         self._set_seed()
         task = cfg["basic"]["task"]
@@ -120,6 +162,8 @@ class Distiller:
         if torch.device(dev) != torch.device(env.device):
             raise ValueError("rl_device must equal sim_device: the rollout writes simulator outputs straight into the distillation buffers")
         self.student_obs, self.scan = env.scan_obs_offset, env.num_scan_obs  # 47 H columns, then P
+        if self.history:
+            self.student_obs = env.num_student_obs  # 47 Hs columns of a row of their own
         self.teacher = self._load_teacher(self.dcfg.teacher_checkpoint)
         A = env.num_actions
         self.student = ActorCritic(A, self.student_obs, env.num_privileged_obs, self.dcfg.student_hidden, critic_hidden).to(dev)
@@ -135,6 +179,8 @@ class Distiller:
         buf.add_buffer("actions", (A,))
         buf.add_buffer("teacher_mu", (A,))
         buf.add_buffer("obses", (env.num_obs,), extra_rows=1)
+        if self.history:
+            buf.add_buffer("student_obses", (self.student_obs,), extra_rows=1)
         buf.add_buffer("privileged_obses", (env.num_privileged_obs,), extra_rows=1)
         buf.add_buffer("rewards", ())
         buf.add_buffer("dones", (), dtype=torch.bool)
@@ -166,6 +212,8 @@ class Distiller:
         parser = argparse.ArgumentParser()
         parser.add_argument("--task", required=True, type=str, help="Name of the task to run.")
         parser.add_argument("--teacher", type=str, help="Path of the perceptive teacher's checkpoint. Overrides distillation.teacher_checkpoint.")
+        parser.add_argument("--student_frame_stack", type=int, help="Observation frames of the student's input (at least the teacher's env.frame_stack). "
+                            "Overrides distillation.student_frame_stack.")
         parser.add_argument("--max_iterations", type=int, help="Number of distillation iterations. Overrides config file if provided.")
         parser.add_argument("--num_envs", type=int, help="Number of environments to create. Overrides config file if provided.")
         parser.add_argument("--sim_device", type=str, help="Device for physics simulation. Overrides config file if provided.")
@@ -223,6 +271,8 @@ class Distiller:
         "height_points", no "optimizer"; the critic is the untrained one built here."""
         d = {"model": self.student.state_dict(), "curriculum": self.env.curriculum_prob,
              "distillation": {"teacher": str(self.dcfg.teacher_checkpoint), "iteration": int(self.iteration_count), "loss": float(self.last_loss)}}
+        if self.history:
+            d["distillation"]["student_frame_stack"] = self.env.student_frame_stack
         if self.env.terrain.curriculum:
             d["terrain_levels"] = self.env.terrain_levels
         return d
@@ -245,6 +295,16 @@ class Distiller:
         seed = int(self.cfg["basic"]["seed"]) + 1000003  # (Runner's rollout seed of rank 0)
         sd, td = self._descriptors()
         lib, logstd = _lib.load(), self.student.logstd
+        if self.history:
+            sobs = buf["student_obses"]
+            with torch.no_grad():
+                for n in range(T):
+                    _lib.check(lib.bg_distill_act_hist(N, _lib.ptr(obses[n]), obses.shape[-1], _lib.ptr(sobs[n]), sobs.shape[-1], len(sd), sd, len(td), td, self.scan,
+                                                       _lib.ptr(logstd), seed, self._act_counter, None, _lib.ptr(actions[n]), _lib.ptr(labels[n]),
+                                                       _lib.current_stream_ptr()), "bg_distill_act_hist")
+                    self._act_counter += 1
+                    self.env.step_to(actions[n], obses[n + 1], priv[n + 1], buf["rewards"][n], buf["dones"][n], buf["time_outs"][n], student_obs=sobs[n + 1])
+            return
         with torch.no_grad():
             for n in range(T):
                 _lib.check(lib.bg_distill_act(N, _lib.ptr(obses[n]), obses.shape[-1], len(sd), sd, len(td), td, self.scan, _lib.ptr(logstd), seed, self._act_counter,
@@ -259,7 +319,8 @@ class Distiller:
         out, hid = tr.layers[-1], tr.layers[-2]
         target = self.buffer["teacher_mu"].reshape(B, A)
         with torch.no_grad():
-            self._student_in[:, : self.student_obs].copy_(self.buffer["obses"][: self.T].reshape(B, -1)[:, : self.student_obs])
+            rows = self.buffer["student_obses" if self.history else "obses"][: self.T].reshape(B, -1)
+            self._student_in[:, : self.student_obs].copy_(rows[:, : self.student_obs])
             for e in range(self.dcfg.num_epochs):
                 h = tr.forward_hidden(self._student_in)
                 self._stats.zero_()
@@ -289,6 +350,8 @@ class Distiller:
         obs, infos = self.env.reset()
         self.buffer["obses"][0].copy_(obs)
         self.buffer["privileged_obses"][0].copy_(infos["privileged_obs"])
+        if self.history:
+            self.buffer["student_obses"][0].copy_(infos["student_obs"])
 
     def train_iteration(self, it):
         losses = self.iteration()

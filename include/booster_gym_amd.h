@@ -169,6 +169,14 @@ typedef struct {
      * its ring of H observation planes also at H = 1.  num_envs x (47 H + P) must stay below 2^31. */
     int32_t actor_heights;
     bg_rand noise_height_measurements; /* noise.height_measurements [m]; read with actor_heights only */
+    /* A longer observation history for the student of a distillation (T1.yaml distillation.student_frame_stack; utils/distill.py).  0 = off: nothing
+     * changes (a zero-initialised struct: every caller older than the field).  Hs in frame_stack .. BG_MAX_FRAME_STACK, with actor_heights only (else
+     * bg_env_create fails): the env's ring has Hs planes and bg_obs_assemble, still the one and last launch of every env step and reset-all, writes a
+     * third output, the student's row [N][47 Hs]: the env's last Hs single observations oldest first, newest last, frames from before the env's last
+     * reset zero (frame_stack's rule at Hs frames).  Its last 47 H columns are the first 47 H columns of the actor's row [47 H + P], noise included.
+     * The destination comes from bg_env_bind_student_obs (bg_env_reset, bg_env_step) or bg_env_step_to_student; a reset or step without one is an
+     * error, and so is bg_env_step_to.  num_envs x 47 Hs must stay below 2^31. */
+    int32_t student_frame_stack;
 } bg_env_cfg;
 
 /* ---- model (replaces gym.load_asset and the asset queries, t1.py:54-108) */
@@ -208,6 +216,9 @@ int bg_env_set_params(bg_env* env, const float* kp, const float* kd, const float
 /* outputs of reset/step, device pointers owned by the caller (torch tensors): obs [N][47 H] (H = cfg.frame_stack, [N][47] without a
  * history; [N][47 H + P] with cfg.actor_heights), privileged [N][14 + P] (P = cfg.height_scan_points, 0 without the height scan: [N][14]), rew [N], done uint8 [N], time_outs uint8 [N], rew_terms [26][N] (rows of dropped terms stay 0) */
 int bg_env_bind_outputs(bg_env* env, float* obs, float* privileged_obs, float* rew, uint8_t* done, uint8_t* time_outs, float* rew_terms);
+/* The student's row of bg_env_reset / bg_env_step (bg_env_cfg.student_frame_stack = Hs): device float [N][47 Hs], owned by the caller.  An error
+ * naming the field when it is 0. */
+int bg_env_bind_student_obs(bg_env* env, float* student_obs);
 /* T1.reset(): t1.py:294-299 */
 int bg_env_reset(bg_env* env, void* stream);
 /* T1.step(actions): t1.py:437-497.  actions: device float [N][12] */
@@ -216,6 +227,9 @@ int bg_env_step(bg_env* env, const float* actions, void* stream);
  * the bound ones (lets the rollout loop write straight into rows of the experience buffer, runner.py:107-118) */
 int bg_env_step_to(bg_env* env, const float* actions, float* obs, float* privileged_obs, float* rew, uint8_t* done, uint8_t* time_outs,
                    void* stream);
+/* bg_env_step_to with the student's row [N][47 Hs] of this step (bg_env_cfg.student_frame_stack; an error naming the field when it is 0) */
+int bg_env_step_to_student(bg_env* env, const float* actions, float* obs, float* privileged_obs, float* rew, uint8_t* done, uint8_t* time_outs,
+                           float* student_obs, void* stream);
 /* Isaac-Gym-layout views of the simulator state for inspection / tests (device pointers, may be NULL):
  * root [N][13] (pos, quat xyzw, lin vel, ang vel: t1.py:215), dof [N][12][2] (pos, vel: t1.py:216-218),
  * contact [N][13][3] net contact force per body, world frame (t1.py:219) */
@@ -332,6 +346,17 @@ int bg_actor_sample_mlp_scan(int32_t N, const float* obs, int32_t n_layers, cons
 int bg_distill_act(int32_t N, const float* obs, int32_t obs_stride, int32_t n_student, const bg_mlp_layer_desc* student, int32_t n_teacher,
                    const bg_mlp_layer_desc* teacher, int32_t scan_points, const float* student_logstd, uint64_t seed, uint64_t counter, float* student_mu,
                    float* actions, float* teacher_mu, void* stream);
+/* bg_distill_act for a student with a longer history than its teacher (bg_env_cfg.student_frame_stack): the same split grid and layer code, the student
+ * half reading its own buffer.  teacher_obs [N] rows of teacher_stride floats = [47 H | scan_points], teacher_stride = the teacher's first-layer `in`;
+ * student_obs [N] rows of student_stride floats = [47 Hs], student_stride = the student's first-layer `in` = 47 Hs, 1 <= Hs <= BG_MAX_FRAME_STACK and
+ * 47 Hs >= 47 H (each violation -4, the message naming the side).  One LDS form for both halves: the wider input tile and the wider hidden layer of
+ * the two decide (a student of 6 frames or more pads to 288 columns and takes the 512-wide form at any widths).  teacher_mu equals
+ * bg_actor_sample_mlp_scan's mu on teacher_obs, student_mu / actions equal bg_actor_sample_mlp's on student_obs, bit for bit; bg_distill_act is this
+ * call with student_obs = teacher_obs and student_stride = teacher_stride, the one case in which student_stride is not the student's `in` (which
+ * must then be the teacher's 47 H). */
+int bg_distill_act_hist(int32_t N, const float* teacher_obs, int32_t teacher_stride, const float* student_obs, int32_t student_stride, int32_t n_student,
+                        const bg_mlp_layer_desc* student, int32_t n_teacher, const bg_mlp_layer_desc* teacher, int32_t scan_points,
+                        const float* student_logstd, uint64_t seed, uint64_t counter, float* student_mu, float* actions, float* teacher_mu, void* stream);
 /* Fused global-norm clip + Adam over one flat parameter buffer (runner.py:162-165); lr is read from device memory
  * so the KL-adaptive schedule (runner.py:174-180) needs no host sync.  gnorm_scratch [1] device float64. */
 int bg_adam_step(int32_t n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const float* lr_device, int32_t step,

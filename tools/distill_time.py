@@ -1,12 +1,19 @@
 """Timing of the teacher-student distillation (README "Distillation"); writes profiles/distill_time.txt.
 
-  python tools/distill_time.py [K=20] [W=5] [pairs=3] [num_envs=4096] [out=profiles/distill_time.txt]
+  python tools/distill_time.py [K=20] [W=5] [pairs=3] [num_envs=4096] [out=profiles/distill_time.txt] [Hs] [only]
       (1) the rollout's launch, bg_distill_act, against the sum of its stand-alone launches on the same rows (bg_actor_sample_mlp_scan on the whole
           row, bg_actor_sample_mlp on a contiguous copy of the prefix columns, and that copy), HIP events around 200 back-to-back calls, best of 5,
           alternating, at H = 1 / P = 187 and at H = 3 / P = 45: us per env step's inference, both networks 256-128-128;
       (2) bg_distill_head against bg_actor_head mode 1 at B = 98,304 rows, the same way: us per launch pair (kernel + fixed-order finish);
       (3) the distillation loop (rollout of 24 steps + 5 epochs, no instrumentation) at H = 1 / P = 187 with a seeded teacher: W warm-up iterations,
           then runs of K iterations: ms per iteration, iterations per second.
+  With Hs (distillation.student_frame_stack; out "-" = profiles/distill_history_time.txt) the sections are those of the longer history instead, all at
+  H = 1 / P = 187:
+      (4) the env step (bg_env_step_to, whose last launch is bg_obs_assemble) with the student's row [47 Hs] against the same env without it, HIP
+          events around 200 back-to-back steps, best of 5, alternating, and the bytes bg_obs_assemble writes in each; `only` = "assemble" stops
+          here (the run under a kernel trace, which gives the launch's own time);
+      (5) bg_distill_act_hist on a buffer of the student's own against bg_distill_act at Hs = H (same networks, expected equal), and at Hs;
+      (6) the loop of (3) with the key absent and with it, one Distiller after the other, `pairs` times each.
   The outputs of (1) are compared bit for bit before they are timed.  The committed profile carries two more sections that this tool does not
   write: the figures tests/test_gpu_distill.py prints under -s, and bench.py of this tree against a checkout of its parent commit."""
 import os
@@ -114,7 +121,70 @@ def head(pairs=3, B=98304):
             f"{us['actor']:.2f} us, distill / actor = {us['distill'] / us['actor']:.4f}")
 
 
-def loop(K=20, W=5, pairs=3, N=4096):
+def assemble(pairs=3, N=4096, Hs=5, P=187):
+    from booster_gym_amd.envs import T1
+    from booster_gym_amd.utils.config import load_cfg
+
+    ov = {"env.num_envs": N, "terrain.measure_heights": True, "terrain.actor_heights": True, "env.num_observations": 47 + P, "env.num_privileged_obs": 14 + P}
+    envs = {"with": T1(load_cfg("T1", dict(ov, **{"env.student_frame_stack": Hs}))), "without": T1(load_cfg("T1", ov))}
+    g = torch.Generator(device="cpu").manual_seed(0)
+    a = ((torch.rand(N, 12, generator=g) * 2 - 1) * 0.3).to(DEV)
+    obs, priv, sob = torch.empty(N, 47 + P, device=DEV), torch.empty(N, 14 + P, device=DEV), torch.empty(N, 47 * Hs, device=DEV)
+    rew, done, tout = torch.empty(N, device=DEV), torch.empty(N, dtype=torch.bool, device=DEV), torch.empty(N, dtype=torch.bool, device=DEV)
+    for e in envs.values():
+        e.reset()
+    fns = {"with": lambda k: envs["with"].step_to(a, obs, priv, rew, done, tout, student_obs=sob),
+           "without": lambda k: envs["without"].step_to(a, obs, priv, rew, done, tout)}
+    for f in fns.values():
+        for k in range(20):
+            f(k)
+    torch.cuda.synchronize()
+    # what bg_obs_assemble writes: the actor's row [47 H + P] and the critic's P clean scan columns; with the key the student's row [47 Hs] as well
+    w0 = N * (47 + P + P) * 4
+    w1 = w0 + N * 47 * Hs * 4
+    say(f"bg_obs_assemble, {N} envs, H = 1, P = {P}: writes {w0 / 1e6:.3f} MB without the student's row, {w1 / 1e6:.3f} MB with Hs = {Hs} "
+        f"(+{(w1 - w0) / 1e6:.3f} MB, x{w1 / w0:.3f}); ring reads {N * 47 * 4 / 1e6:.3f} MB against {N * 47 * (Hs + 1) * 4 / 1e6:.3f} MB")
+    for q in range(pairs):
+        us = {m: _best(fns[m], 200) for m in _orders(q, ("with", "without"))}
+        say(f"env step (bg_env_step_to, all launches), {N} envs: with the student's row {us['with']:.2f} us, without {us['without']:.2f} us, "
+            f"difference {us['with'] - us['without']:+.2f} us, with / without = {us['with'] / us['without']:.4f}")
+
+
+def act_hist(pairs=3, N=4096, Hs=5, P=187):
+    from booster_gym_amd import _lib
+    from booster_gym_amd.utils.model import ActorCritic
+
+    lib, p = _lib.load(), _lib.ptr
+    torch.manual_seed(1)
+    teacher = ActorCritic(12, 47 + P, 14 + P).to(DEV)
+    obs = torch.randn(N, 47 + P, device=DEV)
+    (td, nt), st = _descs(teacher), _lib.current_stream_ptr()
+    for hs in (1, Hs):
+        student = ActorCritic(12, 47 * hs, 14 + P).to(DEV)
+        sobs = torch.randn(N, 47 * hs, device=DEV)
+        sobs[:, -47:] = obs[:, :47]
+        (sd, ns) = _descs(student)
+        a1, t1, a2, t2 = (torch.empty(N, 12, device=DEV) for _ in range(4))
+
+        def hist(k):
+            _lib.check(lib.bg_distill_act_hist(N, p(obs), 47 + P, p(sobs), 47 * hs, ns, sd, nt, td, P, p(student.logstd), 1, k, None, p(a1), p(t1), st), "bg_distill_act_hist")
+
+        def plain(k):
+            _lib.check(lib.bg_distill_act(N, p(obs), 47 + P, ns, sd, nt, td, P, p(student.logstd), 1, k, None, p(a2), p(t2), st), "bg_distill_act")
+
+        if hs == 1:
+            hist(7); plain(7); torch.cuda.synchronize()
+            assert torch.equal(a1, a2) and torch.equal(t1, t2), "bg_distill_act_hist differs from bg_distill_act at Hs = H"
+        for q in range(pairs):
+            if hs == 1:
+                us = {m: _best(f, 200) for m, f in _orders(q, (("hist", hist), ("plain", plain)))}
+                say(f"rollout inference, {N} rows, H = 1, P = {P}, both 256-128-128, Hs = H: bg_distill_act_hist (student on its own [47] buffer) {us['hist']:.2f} us, "
+                    f"bg_distill_act {us['plain']:.2f} us, hist / plain = {us['hist'] / us['plain']:.4f}")
+            else:
+                say(f"rollout inference, {N} rows, H = 1, P = {P}, both 256-128-128, Hs = {hs} ({47 * hs} student columns): bg_distill_act_hist {_best(hist, 200):.2f} us")
+
+
+def loop(K=20, W=5, pairs=3, N=4096, Hs=None):
     from booster_gym_amd.utils.config import load_cfg
     from booster_gym_amd.utils.distill import Distiller
     from booster_gym_amd.utils.model import ActorCritic
@@ -128,6 +198,8 @@ def loop(K=20, W=5, pairs=3, N=4096):
     ck = os.path.join(tmp, "teacher.pth")
     torch.save({"model": ActorCritic(12, 234, 201).state_dict(), "height_points": torch.tensor(height_scan_points(cfg["terrain"])[1], dtype=torch.float).reshape(-1, 2)}, ck)
     cfg["distillation"]["teacher_checkpoint"] = ck
+    if Hs:
+        cfg["distillation"]["student_frame_stack"] = Hs
     d = Distiller(cfg=cfg)
     d.begin(Recorder(cfg, root=tmp, rank=0))
     it = 0
@@ -144,7 +216,7 @@ def loop(K=20, W=5, pairs=3, N=4096):
     T, E = cfg["runner"]["horizon_length"], d.dcfg.num_epochs
     for q in range(pairs):
         ms = run(K)
-        say(f"distillation loop, {N} envs, H = 1, P = 187, horizon {T}, {E} epochs, student 256-128-128 (plan {d._trainer.plan.fwd} / {d._trainer.plan.bwd}, weight "
+        say(f"distillation loop, {N} envs, H = 1, P = 187, student_frame_stack {Hs or 'absent'} ({d.student_obs} student columns padded to {d._student_in.shape[1]}), horizon {T}, {E} epochs, student 256-128-128 (plan {d._trainer.plan.fwd} / {d._trainer.plan.bwd}, weight "
             f"gradients {d._wgrad_terms or 'fp32'}): {ms:.3f} ms per iteration = {1e3 / ms:.2f} iterations/s = {N * T / ms / 1e3:.3f} M env-steps/s; last loss "
             f"{d.last_loss:.6f}")
     for ph, fn in (("rollout", d.rollout), ("update", d.update)):
@@ -160,10 +232,19 @@ def loop(K=20, W=5, pairs=3, N=4096):
 if __name__ == "__main__":
     a = sys.argv[1:]
     K, W, pairs, N = (int(a[i]) if len(a) > i else v for i, v in enumerate((20, 5, 3, 4096)))
-    out = a[4] if len(a) > 4 else os.path.join(ROOT, "profiles", "distill_time.txt")
-    say(f"tools/distill_time.py {K} {W} {pairs} {N} on {torch.cuda.get_device_name(0)}")
-    act(pairs, N)
-    head(pairs)
-    loop(K, W, pairs, N)
+    Hs, only = (int(a[5]) if len(a) > 5 else 0), (a[6] if len(a) > 6 else "")
+    out = a[4] if len(a) > 4 and a[4] != "-" else os.path.join(ROOT, "profiles", "distill_history_time.txt" if Hs else "distill_time.txt")
+    say(f"tools/distill_time.py {' '.join(a) or f'{K} {W} {pairs} {N}'} on {torch.cuda.get_device_name(0)}")
+    if Hs:
+        assemble(pairs, N, Hs)
+        if only != "assemble":
+            act_hist(pairs, N, Hs)
+            for q in range(pairs):  # (a Distiller each: the env and the buffers are per configuration)
+                for hs in _orders(q, (None, Hs)):
+                    loop(K, W, 1, N, hs)
+    else:
+        act(pairs, N)
+        head(pairs)
+        loop(K, W, pairs, N)
     with open(out, "w") as f:
         f.write("\n".join(LINES) + "\n")
