@@ -137,12 +137,24 @@ HEAD_SCRATCH_FLOATS = 768 * 1720  # BG_HEAD_SCRATCH_FLOATS
 OBS_MOMENTS_MAX_GROUPS = 1024  # BG_OBS_MOMENTS_MAX_GROUPS
 GATHER_MAX_STREAMS = 8  # BG_GATHER_MAX_STREAMS
 ACTOR_PACKED_FLOATS = 65616  # BG_ACTOR_PACKED_FLOATS
+# planes of the evaluation record [EVAL_PLANES][N] (bg_env_eval_begin / bg_env_eval_step): the one place that names them, for the kernel's callers
+# and for the report (utils/evaluate.py).  Command class c = 0 still, 1 slow (max |cmd| <= 0.5), 2 fast.
+EVAL_PLANES = 23  # BG_EVAL_PLANES
+(EVAL_STATE, EVAL_LEN, EVAL_REW, EVAL_LEVEL, EVAL_TYPE, EVAL_X0, EVAL_Y0, EVAL_X1, EVAL_Y1, EVAL_CLASS, EVAL_POWER, EVAL_TRACK) = range(12)
+EVAL_CLASSES, EVAL_CLASS_NAMES, EVAL_AXES = 3, ("still", "slow", "fast"), ("lin_vel_x", "lin_vel_y", "ang_vel_yaw")
+EVAL_RUNNING, EVAL_TIMED_OUT, EVAL_FELL = 0, 1, 2  # values of the STATE plane
+
+
+def eval_track_plane(c, k):
+    """Plane of command class c's CNT (k = 0) or SQ of axis k - 1 (k = 1, 2, 3)."""
+    return EVAL_TRACK + 4 * c + k
+
 
 SYMBOLS = [
     "bg_model_create", "bg_model_get", "bg_model_destroy", "bg_model_load_urdf", "bg_model_body_name", "bg_model_dof_name", "bg_model_find_body", "bg_env_create", "bg_env_destroy", "bg_env_set_heightfield",
     "bg_env_set_params", "bg_env_bind_outputs", "bg_env_reset", "bg_env_step", "bg_env_step_to", "bg_env_bind_student_obs", "bg_env_step_to_student", "bg_env_get_state",
     "bg_env_set_state", "bg_env_get_field", "bg_env_set_field", "bg_env_field_info", "bg_env_get_curriculum", "bg_env_set_curriculum", "bg_env_step_count", "bg_env_set_step_count",
-    "bg_env_get_terrain_level_sum", "bg_env_set_terrain_level_sum",
+    "bg_env_get_terrain_level_sum", "bg_env_set_terrain_level_sum", "bg_env_eval_begin", "bg_env_eval_step",
     "bg_env_forward_dynamics", "bg_env_forward_dynamics_packed", "bg_sim_bind_state", "bg_sim_set_actuation", "bg_sim_apply_body_wrench_local", "bg_sim_simulate",
     "bg_sim_refresh_body_state", "bg_sim_write_root_state", "bg_sim_write_dof_state", "bg_gae", "bg_ppo_loss", "bg_gaussian_logp", "bg_actor_pack", "bg_actor_sample", "bg_actor_sample_mlp", "bg_actor_sample_mlp_scan", "bg_distill_act", "bg_distill_act_hist", "bg_adam_step", "bg_adapt_lr", "bg_optimizer_step", "bg_elu_backward_colsum", "bg_mlp_layer_forward", "bg_mlp_chain_forward", "bg_critic_values_gae", "bg_mlp_chain_forward_group", "bg_mlp_chain_forward_split", "bg_mlp_chain_backward_split", "bg_mlp_split_weights_pm", "bg_mlp_layer_backward", "bg_mlp_split_weights", "bg_mlp_layer_forward_split", "bg_mlp_layer_backward_split", "bg_mlp_weight_grad", "bg_mlp_weight_grad_group", "bg_mlp_weight_grad_group_partial", "bg_update_tail", "bg_update_tail_sums", "bg_mlp_weight_grad_group_split", "bg_mlp_weight_grad_group_split_partial",
     "bg_critic_head_forward", "bg_actor_head", "bg_critic_head_backward",
@@ -196,6 +208,8 @@ def load():
         "bg_env_set_curriculum": (i32, [vp, vp, vp]),
         "bg_env_get_terrain_level_sum": (i32, [vp, vp, vp]),
         "bg_env_set_terrain_level_sum": (i32, [vp, vp, vp]),
+        "bg_env_eval_begin": (i32, [vp, vp, vp]),
+        "bg_env_eval_step": (i32, [vp, vp, vp, vp, i32, vp, vp]),
         "bg_env_step_count": (i64, [vp]),
         "bg_env_set_step_count": (i32, [vp, i64]),
         "bg_env_forward_dynamics": (i32, [vp, vp, vp, vp, vp, vp, vp, vp]),

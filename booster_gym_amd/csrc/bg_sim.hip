@@ -192,6 +192,71 @@ __global__ __launch_bounds__(SCAN_BLOCK) void bg_height_scan(EnvDev E, const flo
     priv[(size_t)e * stride + BG_NUM_PRIV + p] = v * E.cfg.height_scan_scale;
 }
 
+// ------------------------------------------------------------------ evaluation record (bg_env_eval_begin / bg_env_eval_step; evaluate.py)
+// Per-robot metrics of every env's FIRST episode in the caller's record [BG_EVAL_PLANES][n], plane-major: one thread per env, so a wave loads and
+// stores 64 consecutive floats of a plane.  No atomics, no LDS, nothing across envs: the report (utils/evaluate.py) reduces on the host, once.  A
+// launch of its own after the env step's sequence, never part of it: a training run launches none of this.  Like bg_height_scan it reads the state
+// the step has stored (fp16 slab with state_fp16), so a host restatement reading the same fields through bg_env_get_field sees the same values.
+//
+// The rule, per env e (the README's evaluation paragraph holds the other copy):
+//   begin (after bg_env_reset): every plane 0; LEVEL / TYPE = the env's terrain level and column (0 / 0 without the terrain curriculum);
+//       X0 = X1 and Y0 = Y1 = the stored root x, y.
+//   step (after an env step that wrote rew, done, time_outs):
+//       STATE != 0: return without writing any plane of e -- a finished record is frozen.
+//       LEN += 1, REW += rew[e].
+//       done[e]: STATE = time_outs[e] ? 1 : 2 and return -- the env's fields already belong to the next episode, this step gives no sample.
+//       else, from the stored command cmd[3], v = (filtered_lin_vel.x, filtered_lin_vel.y, filtered_ang_vel.z), root x, y, torques[12] (the
+//       substep mean) and dof_vel[12]:
+//           command class c = 0 if every |cmd_a| <= 1e-6, else 1 if max |cmd_a| <= 0.5, else 2;
+//           CLASS = c; X1, Y1 = x, y; POWER += sum_j |torques_j dof_vel_j|;
+//           if LEN > settle_steps: CNT[c] += 1, SQ[c][a] += (cmd_a - v_a)^2.
+enum { EV_STATE = 0, EV_LEN = 1, EV_REW = 2, EV_LEVEL = 3, EV_TYPE = 4, EV_X0 = 5, EV_Y0 = 6, EV_X1 = 7, EV_Y1 = 8, EV_CLASS = 9, EV_POWER = 10,
+       EV_TRACK = 11 };  // EV_TRACK + 4 c + {0: CNT, 1: SQ_vx, 2: SQ_vy, 3: SQ_yaw}
+static_assert(EV_TRACK + 4 * 3 == BG_EVAL_PLANES, "three command classes of four planes after the eleven scalar planes");
+constexpr int EVAL_BLOCK = 256;
+template <bool H16>
+__global__ __launch_bounds__(EVAL_BLOCK) void bg_eval_begin(EnvDev E, float* __restrict__ rec) {
+    const int e = blockIdx.x * EVAL_BLOCK + threadIdx.x, n = E.n;
+    if (e >= n) return;
+    const float x = field_ref<H16>(E.f, E.h, F_ROOT + 0, n, e), y = field_ref<H16>(E.f, E.h, F_ROOT + 1, n, e);
+    for (int p = 0; p < BG_EVAL_PLANES; p++) rec[(size_t)p * n + e] = 0.f;
+    if (E.tcur) { rec[(size_t)EV_LEVEL * n + e] = (float)E.tcur[e]; rec[(size_t)EV_TYPE * n + e] = (float)E.tcur[(size_t)n + e]; }
+    rec[(size_t)EV_X0 * n + e] = x; rec[(size_t)EV_X1 * n + e] = x;
+    rec[(size_t)EV_Y0 * n + e] = y; rec[(size_t)EV_Y1 * n + e] = y;
+}
+template <bool H16>
+__global__ __launch_bounds__(EVAL_BLOCK) void bg_eval_step(EnvDev E, const float* __restrict__ rew, const uint8_t* __restrict__ done,
+                                                           const uint8_t* __restrict__ tout, int settle_steps, float* __restrict__ rec) {
+    const int e = blockIdx.x * EVAL_BLOCK + threadIdx.x, n = E.n;
+    if (e >= n) return;
+#define REC(p) rec[(size_t)(p) * n + e]
+#define SFLD(off) field_ref<H16>(E.f, E.h, (off), n, e)
+    if (REC(EV_STATE) != 0.f) return;
+    const float len = REC(EV_LEN) + 1.f;
+    REC(EV_LEN) = len;
+    REC(EV_REW) += rew[e];
+    if (done[e]) { REC(EV_STATE) = tout[e] ? 1.f : 2.f; return; }
+    const float cmd[3] = {SFLD(F_CMD + 0), SFLD(F_CMD + 1), SFLD(F_CMD + 2)};
+    const float v[3] = {SFLD(F_FILT_LIN + 0), SFLD(F_FILT_LIN + 1), SFLD(F_FILT_ANG + 2)};
+    const float m = fmaxf(fmaxf(fabsf(cmd[0]), fabsf(cmd[1])), fabsf(cmd[2]));
+    const int c = m <= 1e-6f ? 0 : (m <= 0.5f ? 1 : 2);
+    REC(EV_CLASS) = (float)c;
+    REC(EV_X1) = SFLD(F_ROOT + 0);
+    REC(EV_Y1) = SFLD(F_ROOT + 1);
+    float pw = 0.f;
+#pragma unroll
+    for (int j = 0; j < BG_NUM_DOFS; j++) pw += fabsf(SFLD(F_TORQUES + j) * SFLD(F_QD + j));
+    REC(EV_POWER) += pw;
+    if (len > (float)settle_steps) {
+        const int t = EV_TRACK + 4 * c;
+        REC(t) += 1.f;
+#pragma unroll
+        for (int a = 0; a < 3; a++) { const float d = cmd[a] - v[a]; REC(t + 1 + a) += d * d; }
+    }
+#undef SFLD
+#undef REC
+}
+
 // ------------------------------------------------------------------ observation history of the actor's input (cfg.frame_stack = H > 1)
 // humanoid-gym's frame stack: the row [47 H] of an env is its last H single observations, oldest first, newest last.  The env keeps them as a
 // ring of H planes [n][47]; the env-step kernels (and resample_apply_kernel's patch) of a launch sequence write their 47-wide rows into plane
@@ -1106,6 +1171,31 @@ extern "C" int bg_env_step_to_student(bg_env* e, const float* actions, float* ob
     int r = launch_step(e, actions, 0, o, student_obs, stream);
     if (r == 0) e->step_count++;
     return r;
+}
+
+// evaluation record: one launch each, on the caller's buffer (the env keeps nothing of it)
+extern "C" int bg_env_eval_begin(bg_env* e, float* record, void* stream) {
+    if (!e) return fail(-1, "bg_env_eval_begin: null env");
+    if (!record) return fail(-1, "bg_env_eval_begin: null record");
+    const dim3 grid((e->n + EVAL_BLOCK - 1) / EVAL_BLOCK), block(EVAL_BLOCK);
+    if (e->h) hipLaunchKernelGGL(bg_eval_begin<true>, grid, block, 0, (hipStream_t)stream, env_dev(e), record);
+    else hipLaunchKernelGGL(bg_eval_begin<false>, grid, block, 0, (hipStream_t)stream, env_dev(e), record);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+extern "C" int bg_env_eval_step(bg_env* e, const float* rew, const uint8_t* done, const uint8_t* time_outs, int32_t settle_steps, float* record,
+                                void* stream) {
+    if (!e) return fail(-1, "bg_env_eval_step: null env");
+    if (!rew) return fail(-1, "bg_env_eval_step: null rew");
+    if (!done) return fail(-1, "bg_env_eval_step: null done");
+    if (!time_outs) return fail(-1, "bg_env_eval_step: null time_outs");
+    if (settle_steps < 0) return fail(-1, "bg_env_eval_step: settle_steps = " + std::to_string(settle_steps) + " is negative");
+    if (!record) return fail(-1, "bg_env_eval_step: null record");
+    const dim3 grid((e->n + EVAL_BLOCK - 1) / EVAL_BLOCK), block(EVAL_BLOCK);
+    if (e->h) hipLaunchKernelGGL(bg_eval_step<true>, grid, block, 0, (hipStream_t)stream, env_dev(e), rew, done, time_outs, (int)settle_steps, record);
+    else hipLaunchKernelGGL(bg_eval_step<false>, grid, block, 0, (hipStream_t)stream, env_dev(e), rew, done, time_outs, (int)settle_steps, record);
+    HIP_OK(hipGetLastError());
+    return 0;
 }
 
 extern "C" int bg_env_get_state(bg_env* e, float* root, float* dof, float* contact, void* stream) {

@@ -516,6 +516,28 @@ class T1(BaseTask):
         if self._stale_tout:
             self._stale_time_outs(done, time_outs)
 
+    # ------------------------------------------------------------------ evaluation record (bg_env_eval_begin / bg_env_eval_step; utils/evaluate.py)
+    def eval_begin(self, record=None):
+        """Start the per-robot record of every env's first episode, after reset(): float [_lib.EVAL_PLANES][N] (the planes are named in _lib), the
+        caller's tensor or a new one.  One launch, no host sync."""
+        if self._stale_tout:
+            raise ValueError("parallel.stale_time_outs: true is not supported by eval_begin: its time-out flags are those of the last step that reset "
+                             "an env, not this step's, and the record tells a time-out from a fall by them")
+        shape = (_lib.EVAL_PLANES, self.num_envs)
+        if record is None:
+            record = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif tuple(record.shape) != shape or record.dtype != torch.float32 or not (record.is_cuda and record.is_contiguous()):
+            raise ValueError(f"eval_begin needs a contiguous float32 CUDA record of shape {shape}, got {tuple(record.shape)} {record.dtype}")
+        _lib.check(self._lib.bg_env_eval_begin(self._env, _lib.ptr(record), _lib.current_stream_ptr()), "bg_env_eval_begin")
+        return record
+
+    def eval_step(self, record, settle_steps):
+        """Add the last step() to the record, from its rew_buf / reset_buf / time_out_buf.  One launch, no host sync."""
+        if tuple(record.shape) != (_lib.EVAL_PLANES, self.num_envs) or record.dtype != torch.float32 or not (record.is_cuda and record.is_contiguous()):
+            raise ValueError(f"eval_step needs the record of eval_begin, float32 {(_lib.EVAL_PLANES, self.num_envs)}")
+        _lib.check(self._lib.bg_env_eval_step(self._env, _lib.ptr(self.rew_buf), _lib.ptr(self.reset_buf), _lib.ptr(self.time_out_buf), int(settle_steps),
+                                              _lib.ptr(record), _lib.current_stream_ptr()), "bg_env_eval_step")
+
     def _as_actions(self, actions):
         if actions.shape != (self.num_envs, self.num_actions):
             raise ValueError(f"actions must have shape {(self.num_envs, self.num_actions)}, got {tuple(actions.shape)}")

@@ -111,16 +111,35 @@ def student_frame_stack_of(cfg):
     return Hs
 
 
+def student_overrides(num_observations, student_frame_stack=None):
+    """The rule under which a student re-enters Runner / play.py / export_model.py / evaluate.py, written once: the teacher's config without the
+    actor's scan, the student's own history when it has one, and the row its actor takes.  student_cfg_overrides derives the arguments from the
+    teacher's config, checkpoint_student_overrides from a student checkpoint."""
+    over = {"terrain.actor_heights": False}
+    if student_frame_stack is not None:
+        over["env.frame_stack"] = int(student_frame_stack)
+    over["env.num_observations"] = int(num_observations)
+    return over
+
+
 def student_cfg_overrides(cfg):
     """The overrides under which the student checkpoint re-enters Runner / play.py / export_model.py: the teacher's config without the actor's scan,
     and with distillation.student_frame_stack = Hs > H the student's own history."""
     H = int(cfg["env"].get("frame_stack", 1) or 1)
-    over = {"terrain.actor_heights": False, "env.num_observations": _lib.NUM_OBS * H}
     if isinstance(cfg.get("distillation"), dict) and cfg["distillation"].get("student_frame_stack") is not None:
         Hs = student_frame_stack_of(cfg)
         if Hs > H:
-            over = {"terrain.actor_heights": False, "env.frame_stack": Hs, "env.num_observations": _lib.NUM_OBS * Hs}
-    return over
+            return student_overrides(_lib.NUM_OBS * Hs, Hs)
+    return student_overrides(_lib.NUM_OBS * H)
+
+
+def checkpoint_student_overrides(checkpoint):
+    """student_overrides from a loaded checkpoint dict alone, or None for a checkpoint that is no student's (no "distillation" entry): the frame
+    stack from the entry's "student_frame_stack" when present, the row from the width of the actor's first layer."""
+    entry = checkpoint.get("distillation")
+    if entry is None:
+        return None
+    return student_overrides(int(checkpoint["model"]["actor.0.weight"].shape[1]), entry.get("student_frame_stack"))
 
 
 class Distiller:

@@ -250,6 +250,20 @@ int bg_env_get_terrain_level_sum(bg_env* env, int32_t* sum_device, void* stream)
 int bg_env_set_terrain_level_sum(bg_env* env, const int32_t* sum_device, void* stream);
 int64_t bg_env_step_count(const bg_env* env);
 int bg_env_set_step_count(bg_env* env, int64_t count);
+/* ---- evaluation record: per-robot metrics of every env's FIRST episode, kept by one launch after each env step (evaluate.py).  Not part of
+ * bg_env_step's launch sequence: a training run that never calls these launches nothing new.  `record` is the caller's device float
+ * [BG_EVAL_PLANES][N], plane-major (a wave's loads and stores are contiguous):
+ *   0 STATE (0 running, 1 ended by the time-out, 2 ended by a termination)   1 LEN   2 REW   3 LEVEL   4 TYPE (terrain level and column, 0 / 0
+ *   without cfg.terrain_curriculum)   5, 6 X0, Y0   7, 8 X1, Y1   9 CLASS   10 POWER   11 + 4 c + {0, 1, 2, 3}: CNT, SQ_vx, SQ_vy, SQ_yaw of the
+ *   command class c = 0 (every |cmd_a| <= 1e-6), 1 (max |cmd_a| <= 0.5), 2 (the rest).
+ * begin is called after bg_env_reset, step after every env step with the rew / done / time_outs (uint8) that step wrote; settle_steps: the steps
+ * at the start of an episode that give no tracking sample.  The rule of both is stated once, at the kernel (bg_eval_step, csrc/bg_sim.hip), and
+ * once for users, in the README's evaluation paragraph.
+ * A null env / record / rew / done / time_outs or a negative settle_steps is -1 naming the argument, before anything is launched. */
+#define BG_EVAL_PLANES 23
+int bg_env_eval_begin(bg_env* env, float* record, void* stream);
+int bg_env_eval_step(bg_env* env, const float* rew, const uint8_t* done, const uint8_t* time_outs, int32_t settle_steps, float* record,
+                     void* stream);
 
 /* ---- dynamics only (what north_star calls "per-step joint accelerations"): forward dynamics of N
  * independent states.  Device float arrays, env-major: root [N][13], dof_pos/dof_vel/tau [N][12],

@@ -2,21 +2,17 @@
 
 The reference ships one trained actor (deploy/models/T1.pt; its weights only are kept as tests/golden/t1_actor.npz).  Its weights encode the
 PhysX dynamics it was trained on, so its behaviour here is the one quantitative statement about PhysX-versus-this-contact-model that can be made
-offline (MuJoCo and Isaac Gym are absent).  The actor drives `num_envs` robots for a full episode (1,500 env steps = 30 s) under the SHIPPED
-envs/T1.yaml -- observation noise, domain randomisation, actuation latency, kicks and pushes all on, commands resampled as in training --
-exactly as play_mujoco.py:734-756 / deploy/utils/policy.py:47-62 would feed it (47 observations -> 12 actions, deterministic mean).
+offline (MuJoCo and Isaac Gym are absent).  The protocol is evaluate.py's (booster_gym_amd/utils/evaluate.py, README "Evaluation"): the actor's
+mean action drives `num_envs` robots through their first episode under the SHIPPED envs/T1.yaml -- observation noise, domain randomisation,
+actuation latency, kicks and pushes all on, commands resampled as in training -- and every scenario's report has that tool's keys.  This file
+keeps the scenario list (terrain x asset.self_collisions, and one run without noise, kicks and pushes) and the contact-parameter sweep.
 
-Reported per scenario (terrain x asset.self_collisions [x contact overrides]):
-  fall_rate_first_episode   fraction of robots whose FIRST episode ends in a termination (height / velocity / contact), not the time-out
-  falls_per_robot_minute    terminations over the whole run, per robot and simulated minute (robots are reset and go on, as in training)
-  mean_first_episode_length mean length in env steps of every robot's first episode (1,501 = all of them ran to the time-out); fell_within_steps = the
-                            cumulative fall fraction over episode time; falls_by_command = what the fallen robots had been told to do
-  tracking_rmse             per axis: sqrt(mean((command - filtered velocity)^2)) over robots given a moving command (|cmd| > 0), after the first
-                            second of each episode; `filtered_*` is what the tracking rewards see (t1.py:610-620); `tracking_rmse_still` for cmd = 0
-  reward_terms              mean of each scaled reward term per env step (extras["rew_terms"], t1.py:566-570) and of the total
+    python tools/eval_reference_actor.py [num_envs=4096] [steps=1502] [--sweep] [--checkpoint logs/.../model.pth] -> logs/reference_actor_eval.json
+(--checkpoint: the same scenarios for an actor trained by THIS build -> logs/own_actor_eval.json: the yardstick for the reference actor's numbers)
 
-    python tools/eval_reference_actor.py [num_envs=4096] [steps=1600] [--sweep] [--checkpoint logs/.../model.pth] -> gpurun_out/reference_actor_eval.json
-(--checkpoint: the same protocol for an actor trained by THIS build -> gpurun_out/own_actor_eval.json: the yardstick for the reference actor's numbers)
+`evaluate()` below, with its own torch actor and accumulators, is the protocol of before evaluate.py existed (whole run instead of first episode,
+tracking sampled every fifth step).  tests/test_gpu_env.py::test_trained_reference_policy_walks_on_the_gpu holds bounds on its figures, so it stays
+for that test alone; main() no longer calls it.
 """
 import json
 import os
@@ -30,6 +26,7 @@ import torch
 
 from booster_gym_amd.envs import T1
 from booster_gym_amd.utils.config import load_cfg
+from booster_gym_amd.utils.evaluate import Evaluator
 
 
 ACTOR_CHECKPOINT = None  # --checkpoint <.pth of this build's Runner>: evaluate that actor instead (how a policy TRAINED HERE fares under the same protocol)
@@ -52,6 +49,20 @@ def load_actor(dev):
         return x
 
     return actor
+
+
+def evaluate_first_episode(n, steps, overrides, seed=42):
+    """One scenario under evaluate.py's protocol: its report, with the loop's time."""
+    over = dict({"env.num_envs": n, "basic.seed": seed}, **overrides)
+    if ACTOR_CHECKPOINT:
+        ev = Evaluator(checkpoint=ACTOR_CHECKPOINT, overrides=over)
+    else:
+        with np.load(os.path.join(ROOT, "tests", "golden", "t1_actor.npz")) as W:
+            ev = Evaluator(actor={k: W[k] for k in W.files}, overrides=over)
+    rep = ev.run(steps)
+    rep["scenario_overrides"], rep["loop_s"] = overrides, ev.loop_s
+    del ev
+    return rep
 
 
 def evaluate(n, steps, overrides, seed=42):
@@ -125,38 +136,41 @@ def main():
         del sys.argv[k : k + 2]
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     n = int(args[0]) if len(args) > 0 else 4096
-    steps = int(args[1]) if len(args) > 1 else 1600  # one full episode (1,500 steps) and its time-out
+    steps = int(args[1]) if len(args) > 1 else None  # None: the episode length + 2, every first episode ends
     res = {"what": __doc__.split("\n\n")[0],
            "actor": f"{ACTOR_CHECKPOINT} (an actor trained by this build)" if ACTOR_CHECKPOINT else "tests/golden/t1_actor.npz (weights of the reference's deploy/models/T1.pt)",
            "config": "envs/T1.yaml as shipped",
            "scenarios": {}}
+
+    def brief(r):
+        g = r["all"]
+        return {"fall_rate": g["fall_rate"], "unfinished": g["unfinished"], "mean_episode_length": g["mean_episode_length"],
+                "tracking_rmse": g["tracking_rmse"], "mean_reward_per_step": g["mean_reward_per_step"]}
+
     for terrain in ("plane", "trimesh"):
         for sc in (0, 1):
             key = f"{terrain}/self_collisions={sc}"
-            res["scenarios"][key] = evaluate(n, steps, {"terrain.type": terrain, "asset.self_collisions": sc})
-            r = res["scenarios"][key]
-            print(key, "fall rate (first episode)", round(r["fall_rate_first_episode"], 4), "mean episode length", round(r["mean_first_episode_length"], 1),
-                  "rmse", {k: round(v, 3) for k, v in r["tracking_rmse"].items()}, flush=True)
+            res["scenarios"][key] = r = evaluate_first_episode(n, steps, {"terrain.type": terrain, "asset.self_collisions": sc})
+            print(key, brief(r), flush=True)
     # the same actor without the perturbations, to separate "the contact model differs" from "kicks, pushes and noise are hard"
     quiet = {"terrain.type": "plane", "noise.gravity": None, "noise.ang_vel": None, "noise.dof_pos": None, "noise.dof_vel": None,
              "randomization.kick_lin_vel": None, "randomization.kick_ang_vel": None, "randomization.push_force": None, "randomization.push_torque": None}
-    res["scenarios"]["plane/no_noise_no_kicks_no_pushes"] = evaluate(n, steps, quiet)
-    print("quiet", res["scenarios"]["plane/no_noise_no_kicks_no_pushes"]["fall_rate_first_episode"], flush=True)
+    res["scenarios"]["plane/no_noise_no_kicks_no_pushes"] = r = evaluate_first_episode(n, steps, quiet)
+    print("quiet", brief(r), flush=True)
     if "--sweep" in sys.argv:
         # which contact parameter moves the fall rate: one at a time around the defaults (contact.* of T1.yaml), plane, shipped perturbations
         sweep = {}
         for name, values in (("contact.stiffness", (1.0e4, 2.0e4, 8.0e4, 1.6e5)), ("contact.damping", (150.0, 300.0, 1200.0, 2400.0)),
                              ("contact.friction_viscosity", (2.5e3, 5.0e3, 2.0e4, 4.0e4))):
             for v in values:
-                r = evaluate(n, steps, {"terrain.type": "plane", name: v})
-                sweep[f"{name}={v:g}"] = {k: r[k] for k in ("fall_rate_first_episode", "falls_per_robot_minute", "mean_first_episode_length", "tracking_rmse", "mean_reward_per_step")}
-                print(name, v, sweep[f"{name}={v:g}"]["fall_rate_first_episode"], flush=True)
+                sweep[f"{name}={v:g}"] = b = brief(evaluate_first_episode(n, steps, {"terrain.type": "plane", name: v}))
+                print(name, v, b["fall_rate"], flush=True)
         res["contact_parameter_sweep_plane"] = sweep
-    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
+    os.makedirs(os.path.join(ROOT, "logs"), exist_ok=True)
     name = "own_actor_eval.json" if ACTOR_CHECKPOINT else "reference_actor_eval.json"
-    with open(os.path.join(ROOT, "gpurun_out", name), "w") as f:
+    with open(os.path.join(ROOT, "logs", name), "w") as f:
         json.dump(res, f, indent=1)
-    print("written gpurun_out/" + name)
+    print("written logs/" + name)
 
 
 if __name__ == "__main__":
