@@ -22,6 +22,8 @@
 // bg_distill_act (teacher-student distillation, utils/distill.py) runs TWO such networks on the same rows in one launch: the grid is split, workgroups
 // [0, nb) evaluate the teacher on all 47 H + P columns of their 16 rows and write its mean, workgroups [nb, 2 nb) the student on the first 47 H
 // columns and sample.  Both kernels are one body, actor_rows, so a half computes what the stand-alone kernel does on the same operands, bit for bit.
+// bg_distill_act_mix (distillation.teacher_action_prob, DAgger's mixing) is the same split grid in which the teacher's half acts on a row with
+// probability beta: a Philox uniform per (row, step) on a stream of its own, evaluated by both halves, decides which half writes the row's action.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -132,9 +134,13 @@ __device__ __forceinline__ void layer(const float* __restrict__ W, const float* 
 
 // One workgroup's 16 rows [r0, r0 + 16) through one network: the body of both kernels below.  The rows are `stride` floats apart and the network reads
 // its own first net.in[0] columns of them.  act_out == nullptr: the mean alone goes to mu_out and no noise is drawn (bg_distill_act's teacher).
-template <int MAXW>
+// MIX (bg_distill_act_mix, compiled into its kernel alone): the row's action comes from ONE of two calls on the same rows, the teacher's when
+// u < beta and the student's otherwise, u = entry 0 of rand4_uniform(seed, row, counter, RS_DAGGER): both calls evaluate u and the one that acts
+// writes act_out, with the noise draw the other would have used (the teacher without it when teacher_noise is 0: its mean alone).
+template <int MAXW, bool MIX = false>
 __device__ __forceinline__ void actor_rows(int N, int r0, const float* __restrict__ obs, int stride, const ActorNet& net, const float* __restrict__ logstd,
-                                           uint64_t seed, uint32_t counter, float* __restrict__ mu_out, float* __restrict__ act_out) {
+                                           uint64_t seed, uint32_t counter, float* __restrict__ mu_out, float* __restrict__ act_out, bool teacher_half = false,
+                                           float beta = 0.f, int teacher_noise = 0) {
     constexpr int LDA = MAXW + 4;  // row stride (floats): = 4 mod 64 banks, as bg_actor_sample's 260
     __shared__ __attribute__((aligned(16))) float buf[2][MR * LDA];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -156,7 +162,20 @@ __device__ __forceinline__ void actor_rows(int N, int r0, const float* __restric
     if (threadIdx.x < MR * 3) {
         const int r = threadIdx.x / 3, g = threadIdx.x % 3, row = r0 + r;
         if (row < N) {
-            if (!act_out) {
+            if constexpr (MIX) {
+                float u[4];
+                bg::rand4_uniform(seed, (uint32_t)row, counter, bg::RS_DAGGER, u);
+                const bool acts = (u[0] < beta) == teacher_half, noise = acts && (!teacher_half || teacher_noise != 0);
+                bg::Rand4 rn = {};
+                if (noise) rn = bg::rand4(seed, (uint32_t)row, counter, bg::RS_ACTOR + g);
+                for (int k = 0; k < 4; k++) {
+                    const int a = g * 4 + k;
+                    const float m = buf[cur][r * LDA + a];
+                    if (mu_out) mu_out[(size_t)row * BG_NUM_DOFS + a] = m;
+                    if (noise) act_out[(size_t)row * BG_NUM_DOFS + a] = m + expf(logstd[a]) * rn.n[k];
+                    else if (acts) act_out[(size_t)row * BG_NUM_DOFS + a] = m;
+                }
+            } else if (!act_out) {
                 for (int k = 0; k < 4; k++) mu_out[(size_t)row * BG_NUM_DOFS + g * 4 + k] = buf[cur][r * LDA + g * 4 + k];
             } else {
                 bg::Rand4 rn = bg::rand4(seed, (uint32_t)row, counter, bg::RS_ACTOR + g);
@@ -189,6 +208,19 @@ __global__ __launch_bounds__(256) void distill_act_kernel(int N, int nb, const f
     const int r0 = (teacher ? blockIdx.x : blockIdx.x - nb) * MR;
     actor_rows<MAXW>(N, r0, teacher ? obs : sobs, teacher ? stride : sstride, nets.n[teacher ? 0 : 1], logstd, seed, counter, teacher ? teacher_mu : student_mu,
                      teacher ? nullptr : act_out);
+}
+
+// bg_distill_act_mix: distill_act_kernel's split grid with the DAgger choice per row (actor_rows' MIX form).  Both halves write their mean; `act_out`
+// receives each row from the half that acts on it: the two sets of rows are disjoint, so no atomics and no second pass.
+template <int MAXW>
+__global__ __launch_bounds__(256) void distill_act_mix_kernel(int N, int nb, const float* __restrict__ obs, int stride, const float* __restrict__ sobs, int sstride,
+                                                              DistillNets nets, const float* __restrict__ logstd, uint64_t seed, uint32_t counter, float beta,
+                                                              int teacher_noise, float* __restrict__ student_mu, float* __restrict__ act_out,
+                                                              float* __restrict__ teacher_mu) {
+    const bool teacher = (int)blockIdx.x < nb;
+    const int r0 = (teacher ? blockIdx.x : blockIdx.x - nb) * MR;
+    actor_rows<MAXW, true>(N, r0, teacher ? obs : sobs, teacher ? stride : sstride, nets.n[teacher ? 0 : 1], logstd, seed, counter, teacher ? teacher_mu : student_mu,
+                           act_out, teacher, beta, teacher_noise);
 }
 
 }  // namespace
@@ -244,11 +276,16 @@ extern "C" int bg_actor_sample_mlp_scan(int32_t N, const float* obs, int32_t n_l
     return sample_mlp(N, obs, n_layers, layers, scan_points, logstd, seed, counter, mu, actions, stream);
 }
 
-// Both distillation entry points: hist = bg_distill_act_hist (the student's own buffer), else bg_distill_act (sobs = obs, sstride = stride).
-static int distill_act(bool hist, int32_t N, const float* obs, int32_t stride, const float* sobs, int32_t sstride, int32_t n_student, const bg_mlp_layer_desc* student,
+// The distillation entry points: DA_PLAIN = bg_distill_act (sobs = obs, sstride = stride), DA_HIST = bg_distill_act_hist (the student's own buffer),
+// DA_MIX = bg_distill_act_mix (DA_HIST's rows and rules, the teacher acting with probability beta).
+enum { DA_PLAIN = 0, DA_HIST = 1, DA_MIX = 2 };
+static int distill_act(int kind, float beta, int32_t teacher_noise, int32_t N, const float* obs, int32_t stride, const float* sobs, int32_t sstride, int32_t n_student, const bg_mlp_layer_desc* student,
                        int32_t n_teacher, const bg_mlp_layer_desc* teacher, int32_t scan_points, const float* student_logstd, uint64_t seed, uint64_t counter,
                        float* student_mu, float* actions, float* teacher_mu, void* stream) {
-    const std::string who(hist ? "bg_distill_act_hist" : "bg_distill_act");
+    const bool hist = kind != DA_PLAIN;
+    const std::string who(kind == DA_MIX ? "bg_distill_act_mix" : hist ? "bg_distill_act_hist" : "bg_distill_act");
+    if (kind == DA_MIX && !(beta >= 0.f && beta <= 1.f))  // (a NaN fails both comparisons)
+        return bg_set_error(-1, (who + ": bad argument (beta: the teacher's probability of acting, a finite number in [0, 1])").c_str());
     if (N <= 0 || !obs || !sobs || !student || !teacher || !student_logstd || !actions || !teacher_mu) return bg_set_error(-1, (who + ": bad argument").c_str());
     if (scan_points < 0 || scan_points > BG_MAX_HEIGHT_SCAN_POINTS) return bg_set_error(-1, (who + ": bad argument (scan_points)").c_str());
     DistillNets nets;
@@ -262,13 +299,13 @@ static int distill_act(bool hist, int32_t N, const float* obs, int32_t stride, c
             return bg_set_error(-4, "bg_distill_act: the student's first layer takes the 47 H observation columns in front of the teacher's scan_points");
     } else {
         if (stride != teacher[0].in)
-            return bg_set_error(-4, "bg_distill_act_hist: teacher_stride must equal the teacher's first-layer input (47 H + scan_points columns per row)");
+            return bg_set_error(-4, (who + ": teacher_stride must equal the teacher's first-layer input (47 H + scan_points columns per row)").c_str());
         // (the student on the teacher's own rows, same buffer and same stride: bg_distill_act's case, its prefix rule)
         if (sobs == obs && sstride == stride ? student[0].in != teacher[0].in - scan_points : sstride != student[0].in)
-            return bg_set_error(-4, "bg_distill_act_hist: student_stride must equal the student's first-layer input (47 Hs columns per row; or, on the teacher's "
-                                    "buffer at the teacher's stride, the student's first layer takes the teacher's 47 H columns)");
+            return bg_set_error(-4, (who + ": student_stride must equal the student's first-layer input (47 Hs columns per row; or, on the teacher's "
+                                          "buffer at the teacher's stride, the student's first layer takes the teacher's 47 H columns)").c_str());
         if (student[0].in < teacher[0].in - scan_points)
-            return bg_set_error(-4, "bg_distill_act_hist: the student's first layer (47 Hs) must take at least the teacher's 47 H observation columns");
+            return bg_set_error(-4, (who + ": the student's first layer (47 Hs) must take at least the teacher's 47 H observation columns").c_str());
     }
     const int nb = (N + MR - 1) / MR;
     const dim3 grid(2 * nb), block(256);
@@ -276,7 +313,14 @@ static int distill_act(bool hist, int32_t N, const float* obs, int32_t stride, c
     // one LDS form for both halves: the wider input tile of the two (the student's with a longer history) and the wider hidden layer of the two
     const int kin = teacher[0].in > student[0].in ? teacher[0].in : student[0].in;
     const int kp = (kin + KC - 1) / KC * KC, maxw = maxw_t > maxw_s ? maxw_t : maxw_s;
-    if (maxw <= 256 && kp <= 256)
+    if (kind == DA_MIX) {
+        if (maxw <= 256 && kp <= 256)
+            hipLaunchKernelGGL(distill_act_mix_kernel<256>, grid, block, 0, st, N, nb, obs, stride, sobs, sstride, nets, student_logstd, seed, (uint32_t)counter, beta,
+                               teacher_noise, student_mu, actions, teacher_mu);
+        else
+            hipLaunchKernelGGL(distill_act_mix_kernel<512>, grid, block, 0, st, N, nb, obs, stride, sobs, sstride, nets, student_logstd, seed, (uint32_t)counter, beta,
+                               teacher_noise, student_mu, actions, teacher_mu);
+    } else if (maxw <= 256 && kp <= 256)
         hipLaunchKernelGGL(distill_act_kernel<256>, grid, block, 0, st, N, nb, obs, stride, sobs, sstride, nets, student_logstd, seed, (uint32_t)counter, student_mu, actions, teacher_mu);
     else
         hipLaunchKernelGGL(distill_act_kernel<512>, grid, block, 0, st, N, nb, obs, stride, sobs, sstride, nets, student_logstd, seed, (uint32_t)counter, student_mu, actions, teacher_mu);
@@ -287,7 +331,7 @@ static int distill_act(bool hist, int32_t N, const float* obs, int32_t stride, c
 extern "C" int bg_distill_act(int32_t N, const float* obs, int32_t obs_stride, int32_t n_student, const bg_mlp_layer_desc* student, int32_t n_teacher,
                               const bg_mlp_layer_desc* teacher, int32_t scan_points, const float* student_logstd, uint64_t seed, uint64_t counter,
                               float* student_mu, float* actions, float* teacher_mu, void* stream) {
-    return distill_act(false, N, obs, obs_stride, obs, obs_stride, n_student, student, n_teacher, teacher, scan_points, student_logstd, seed, counter, student_mu,
+    return distill_act(DA_PLAIN, 0.f, 0, N, obs, obs_stride, obs, obs_stride, n_student, student, n_teacher, teacher, scan_points, student_logstd, seed, counter, student_mu,
                        actions, teacher_mu, stream);
 }
 
@@ -295,6 +339,14 @@ extern "C" int bg_distill_act_hist(int32_t N, const float* teacher_obs, int32_t 
                                    const bg_mlp_layer_desc* student, int32_t n_teacher, const bg_mlp_layer_desc* teacher, int32_t scan_points,
                                    const float* student_logstd, uint64_t seed, uint64_t counter, float* student_mu, float* actions, float* teacher_mu,
                                    void* stream) {
-    return distill_act(true, N, teacher_obs, teacher_stride, student_obs, student_stride, n_student, student, n_teacher, teacher, scan_points, student_logstd, seed,
+    return distill_act(DA_HIST, 0.f, 0, N, teacher_obs, teacher_stride, student_obs, student_stride, n_student, student, n_teacher, teacher, scan_points, student_logstd, seed,
                        counter, student_mu, actions, teacher_mu, stream);
+}
+
+extern "C" int bg_distill_act_mix(int32_t N, const float* teacher_obs, int32_t teacher_stride, const float* student_obs, int32_t student_stride, int32_t n_student,
+                                  const bg_mlp_layer_desc* student, int32_t n_teacher, const bg_mlp_layer_desc* teacher, int32_t scan_points,
+                                  const float* student_logstd, uint64_t seed, uint64_t counter, float beta, int32_t teacher_noise, float* student_mu,
+                                  float* actions, float* teacher_mu, void* stream) {
+    return distill_act(DA_MIX, beta, teacher_noise, N, teacher_obs, teacher_stride, student_obs, student_stride, n_student, student, n_teacher, teacher, scan_points,
+                       student_logstd, seed, counter, student_mu, actions, teacher_mu, stream);
 }

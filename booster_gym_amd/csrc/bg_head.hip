@@ -12,6 +12,8 @@
 //                           utils/distill.py): bg_actor_head's forward and backward mappings around bg_critic_head_backward's form of loss
 //   bg_actor_head_sym       bg_actor_head on a batch of 2B rows (the rollout's, then their mirror images) plus the mirror-symmetry loss
 //                           (algorithm.symmetry_loss); bg_mirror_rows writes the mirrored network inputs
+//   bg_distill_head_sym     bg_distill_head on the original rows of such a batch of 2B rows plus the mirror-symmetry loss on the student's mean
+//                           (distillation.symmetric_coef)
 // Arithmetic is plain fp32 FMA on the vector ALU: 4.6 kflop per row against 1 KB of traffic is under the HBM ridge, so nothing here is
 // reshaped into an MFMA GEMM.  Reductions over rows are deterministic: every workgroup writes its partial sums, a second kernel adds them
 // in a fixed order (the loss statistics and the log-std gradient keep the float64 atomics of bg_ppo_loss).
@@ -702,6 +704,145 @@ __global__ __launch_bounds__(256) void actor_head_sym_kernel(int B, int tiles, c
     }
 }
 
+// ---- mirror-symmetry loss on the distillation's student (bg_distill_head_sym): actor_head_sym_kernel's tile (HTS original rows and their HTS mirror
+// images meet in LDS) with distill_head_kernel's loss on the original rows.  L = 1 / (A B) sum_r |mu_r - target_r|^2 + coef / (A B) sum_r |d_r|^2,
+// d = mu(M_o x) - M_a mu(x); with s = sym_scale = 2 coef / (A B):  dL/dmu of the mirrored row = s d,  of the original row = 2 (mu - target) / (A B) -
+// s M_a d.  Two float64 statistics per workgroup: the squared errors and sum d^2.  A kernel of its own: the two it resembles keep their bits.
+__global__ __launch_bounds__(256) void distill_head_sym_kernel(int B, int tiles, const float* __restrict__ h, const float* __restrict__ W,
+                                                               const float* __restrict__ bias, const float* __restrict__ target, float sym_scale,
+                                                               ActionMirror am, float* __restrict__ mu_out, float* __restrict__ g_hidden,
+                                                               float* __restrict__ partial) {
+    constexpr int A = HA;
+    __shared__ __attribute__((aligned(16))) float s_h[HT * HLD];
+    __shared__ __attribute__((aligned(16))) float s_w[A * HLD];
+    __shared__ __attribute__((aligned(16))) float s_g[HT * A];
+    __shared__ float s_mu[HT * A];
+    __shared__ int s_src[A];
+    __shared__ float s_sign[A];
+    const int t = threadIdx.x;
+    for (int i = t; i < A * HK; i += 256) s_w[(i >> 7) * HLD + (i & (HK - 1))] = W[i];
+    if (t < A) { s_src[t] = am.src[t]; s_sign[t] = am.sign[t]; }
+    const int fr = t >> 2, fq = t & 3, pr = fr & (HTS - 1);
+    const bool mirror = fr >= HTS;
+    float fb[3];
+    for (int i = 0; i < 3; i++) fb[i] = bias[3 * fq + i];
+    const int kc = t & (HK - 1), half = t >> 7;  // backward: half 0 = the original rows, half 1 = their mirror images
+    float wcol[A], dW[A], cs = 0.f, dbias[3] = {0.f, 0.f, 0.f};
+    for (int j = 0; j < A; j++) { wcol[j] = W[j * HK + kc]; dW[j] = 0.f; }
+    const float gscale = 2.0f / ((float)A * (float)B);
+    double sse = 0.0, acc_sym = 0.0;
+    __syncthreads();
+    int src[3];
+    float sgn[3];
+    for (int i = 0; i < 3; i++) { src[i] = s_src[3 * fq + i]; sgn[i] = s_sign[3 * fq + i]; }
+    // the pair tile: LDS rows [0, HTS) from rows row0 .., LDS rows [HTS, 2 HTS) from rows B + row0 ..; the NEXT tile's 8 float4 per thread are in flight
+    // under this tile's compute (critic_head_backward_kernel's scheme: LDS, not registers, bounds this kernel's three workgroups per CU)
+    auto pair_fetch = [&](int row0, float4 (&v)[HTV]) {
+#pragma unroll
+        for (int i = 0; i < HTV; i++) {
+            const int idx = t + 256 * i, r = idx >> 5, c4 = idx & 31, o = row0 + (r & (HTS - 1));
+            v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (o < B) v[i] = *reinterpret_cast<const float4*>(h + (size_t)(r < HTS ? o : B + o) * HK + c4 * 4);
+        }
+    };
+    float4 nxt[HTV];
+    pair_fetch(blockIdx.x * HTS, nxt);
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int row0 = tile * HTS;
+        tile_put(nxt, s_h);
+        if (tile + (int)gridDim.x < tiles) pair_fetch((tile + gridDim.x) * HTS, nxt);
+        __syncthreads();
+        const int b = row0 + pr;
+        const bool live = b < B;
+        float m[3];
+        {   // mu = h W^T + b (bg_actor_head's arithmetic)
+            float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+            const float4* hr = reinterpret_cast<const float4*>(s_h + fr * HLD);
+            const float4* w0 = reinterpret_cast<const float4*>(s_w + (3 * fq) * HLD);
+            const float4* w1 = reinterpret_cast<const float4*>(s_w + (3 * fq + 1) * HLD);
+            const float4* w2 = reinterpret_cast<const float4*>(s_w + (3 * fq + 2) * HLD);
+#pragma unroll 2
+            for (int k4 = 0; k4 < HK / 4; k4++) {
+                const float4 x = hr[k4], u = w0[k4], v = w1[k4], w = w2[k4];
+                a0 = fmaf(x.x, u.x, a0); a0 = fmaf(x.y, u.y, a0); a0 = fmaf(x.z, u.z, a0); a0 = fmaf(x.w, u.w, a0);
+                a1 = fmaf(x.x, v.x, a1); a1 = fmaf(x.y, v.y, a1); a1 = fmaf(x.z, v.z, a1); a1 = fmaf(x.w, v.w, a1);
+                a2 = fmaf(x.x, w.x, a2); a2 = fmaf(x.y, w.y, a2); a2 = fmaf(x.z, w.z, a2); a2 = fmaf(x.w, w.w, a2);
+            }
+            m[0] = a0 + fb[0]; m[1] = a1 + fb[1]; m[2] = a2 + fb[2];
+        }
+        for (int i = 0; i < 3; i++) s_mu[fr * A + 3 * fq + i] = m[i];
+        if (mu_out && live) for (int i = 0; i < 3; i++) mu_out[(size_t)(mirror ? B + b : b) * A + 3 * fq + i] = m[i];
+        __syncthreads();
+        float gm[3] = {0.f, 0.f, 0.f};
+        {   // symmetry term of the pair (pr, HTS + pr)
+            const float* mo = s_mu + pr * A;
+            const float* mm = s_mu + (HTS + pr) * A;
+            for (int i = 0; i < 3; i++) {
+                const int a = 3 * fq + i;
+                if (mirror) {
+                    const float d = mm[a] - sgn[i] * mo[src[i]];
+                    if (live) { gm[i] = sym_scale * d; acc_sym += (double)(d * d); }
+                } else {
+                    const float d = mm[src[i]] - sgn[i] * mo[a];  // d[src[a]] (sign[src[a]] = sign[a])
+                    if (live) gm[i] = -sym_scale * sgn[i] * d;
+                }
+            }
+        }
+        if (!mirror) {  // behaviour-cloning loss of the original row (bg_distill_head)
+            const size_t o = (size_t)(live ? b : B - 1) * A + 3 * fq;
+            for (int i = 0; i < 3; i++) {
+                const float e = m[i] - target[o + i];
+                if (live) { gm[i] += gscale * e; sse += (double)(e * e); }
+            }
+        }
+        for (int i = 0; i < 3; i++) { s_g[fr * A + 3 * fq + i] = gm[i]; dbias[i] += gm[i]; }
+        __syncthreads();
+        // g_hidden = (dL/dmu W) * elu'(h), dW += dL/dmu^T h, hidden bias gradient = column sums of g_hidden: over all 2B rows
+        for (int rr = 0; rr < HTS; rr++) {
+            const int r = half * HTS + rr;
+            const float hv = s_h[r * HLD + kc];
+            const float4* gp = reinterpret_cast<const float4*>(s_g + r * A);
+            const float4 g0 = gp[0], g1 = gp[1], g2 = gp[2];
+            const float g[A] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w, g2.x, g2.y, g2.z, g2.w};
+            float sa = 0.f, sb = 0.f;
+#pragma unroll
+            for (int j = 0; j < A; j += 2) {
+                sa = fmaf(g[j], wcol[j], sa); sb = fmaf(g[j + 1], wcol[j + 1], sb);
+                dW[j] = fmaf(g[j], hv, dW[j]); dW[j + 1] = fmaf(g[j + 1], hv, dW[j + 1]);
+            }
+            const float gz = (sa + sb) * elu_grad_from_output(hv);
+            cs += gz;
+            if (row0 + rr < B) g_hidden[(size_t)(half ? B + row0 + rr : row0 + rr) * HK + kc] = gz;
+        }
+        __syncthreads();
+    }
+    // ---- this workgroup's partial sums (bg_actor_head's record layout; TWO float64 statistics, statistic-major)
+    float* red = s_h;  // [2][A + 1][HK]
+    for (int j = 0; j < A; j++) red[(half * (A + 1) + j) * HK + kc] = dW[j];
+    red[(half * (A + 1) + A) * HK + kc] = cs;
+    __syncthreads();
+    float* rec = partial + (size_t)blockIdx.x * head_record<A>();
+    for (int i = t; i < (A + 1) * HK; i += 256) rec[i] = red[i] + red[(A + 1) * HK + i];
+    const int wave = t >> 6, lane = t & 63;
+    __syncthreads();
+    float* redf = s_h;                                    // [4 waves][16]
+    double* redd = reinterpret_cast<double*>(s_h + 64);  // [2][4 waves]
+    for (int i = 0; i < 3; i++) {
+        const float v = quadcol_sum(dbias[i]);
+        if (lane < 4) redf[wave * 16 + 3 * lane + i] = v;
+    }
+    {
+        const double w0 = wave_sum_d(sse), w1 = wave_sum_d(acc_sym);
+        if (lane == 0) { redd[wave] = w0; redd[4 + wave] = w1; }
+    }
+    __syncthreads();
+    if (t < A) rec[(A + 1) * HK + t] = redf[t] + redf[16 + t] + redf[32 + t] + redf[48 + t];
+    if (t < 2) {
+        double* srec = reinterpret_cast<double*>(partial + head_stat_base<A>());
+        srec[(size_t)t * gridDim.x + blockIdx.x] = redd[4 * t] + redd[4 * t + 1] + redd[4 * t + 2] + redd[4 * t + 3];
+    }
+}
+
 // y[r][c] = sign[c] x[r][src[c]] (src[c] < 0: 0) for rows x cols elements: exact, only signs change.  Up to MIRROR_MAX_COLS columns (the widest
 // network input: a frame stack's 47 H observations padded to 512); the map travels as a kernel argument, one 16-bit code per column: -1 for a zero
 // column, else src with MIRROR_NEG set where the sign is -1.
@@ -907,6 +1048,35 @@ extern "C" int bg_actor_head_sym_partial(int32_t B, const float* h, const float*
     if (!finish) return bg_set_error(-1, "bg_actor_head_sym_partial: bad argument");
     return actor_head_sym("bg_actor_head_sym_partial", B, h, W, bias, logstd, actions, old_mu, old_logstd, old_logp, adv, adv_stats, e_clip, bound_coef, entropy_coef,
                           sym_coef, act_src, act_sign, mu_out, g_hidden, grad_W, grad_b, grad_b_hidden, grad_logstd, stats, scratch, finish, (hipStream_t)stream);
+}
+
+// ---- mirror-symmetry loss on the distillation's student
+static int distill_head_sym(const char* who, int32_t B, const float* h, const float* W, const float* bias, const float* target, float sym_coef,
+                            const int32_t* act_src, const float* act_sign, float* mu_out, float* g_hidden, float* grad_W, float* grad_b, float* grad_b_hidden,
+                            double* stats, float* scratch, bg_reduce_problem* finish, hipStream_t st) {
+    if (B <= 0 || !h || !W || !bias || !target || !g_hidden || !grad_W || !grad_b || !grad_b_hidden || !stats || !scratch) return bg_fail(who, -1, "bad argument");
+    if (!(sym_coef >= 0.f) || sym_coef > 3.0e38f) return bg_fail(who, -1, "sym_coef must be a finite number >= 0");
+    ActionMirror am;
+    if (action_mirror(&am, act_src, act_sign))
+        return bg_fail(who, -1, "act_src / act_sign must be a symmetric signed permutation of the 12 actions that is its own inverse");
+    if (!aligned16(h)) return bg_fail(who, -1, "h must be 16-byte aligned");
+    const int tiles = (B + HTS - 1) / HTS, grid = head_grid(tiles);
+    const float sym_scale = (float)(2.0 * (double)sym_coef / ((double)B * HA));
+    hipLaunchKernelGGL(distill_head_sym_kernel, dim3(grid), dim3(256), 0, st, B, tiles, h, W, bias, target, sym_scale, am, mu_out, g_hidden, scratch);
+    return head_finish(finish, scratch, grid, head_record<HA>(), grad_W, HA * HK, grad_b_hidden, grad_b, HA, head_stat_base<HA>(), 2, 0, 0u, 0.0, nullptr, stats, st);
+}
+extern "C" int bg_distill_head_sym(int32_t B, const float* h, const float* W, const float* bias, const float* target, float sym_coef, const int32_t* act_src,
+                                   const float* act_sign, float* mu_out, float* g_hidden, float* grad_W, float* grad_b, float* grad_b_hidden, double* stats,
+                                   float* scratch, void* stream) {
+    return distill_head_sym("bg_distill_head_sym", B, h, W, bias, target, sym_coef, act_src, act_sign, mu_out, g_hidden, grad_W, grad_b, grad_b_hidden, stats, scratch,
+                            nullptr, (hipStream_t)stream);
+}
+extern "C" int bg_distill_head_sym_partial(int32_t B, const float* h, const float* W, const float* bias, const float* target, float sym_coef, const int32_t* act_src,
+                                           const float* act_sign, float* mu_out, float* g_hidden, float* grad_W, float* grad_b, float* grad_b_hidden, double* stats,
+                                           float* scratch, bg_reduce_problem* finish, void* stream) {
+    if (!finish) return bg_set_error(-1, "bg_distill_head_sym_partial: bad argument");
+    return distill_head_sym("bg_distill_head_sym_partial", B, h, W, bias, target, sym_coef, act_src, act_sign, mu_out, g_hidden, grad_W, grad_b, grad_b_hidden, stats,
+                            scratch, finish, (hipStream_t)stream);
 }
 
 extern "C" int bg_mirror_rows(int32_t rows, int32_t cols, const int32_t* src, const float* sign, const float* x, float* y, void* stream) {

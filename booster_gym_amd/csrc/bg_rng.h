@@ -65,6 +65,7 @@ enum {
     RS_CURR = 26,     // curriculum: grid cell, cmd x / y / yaw jitter
     RS_TLEVEL = 27,   // terrain curriculum: the level of an env that passed the top one
     RS_PERM = 28,     // mini-batch shuffle: the Feistel round functions of bg_perm.h (counter words: half, round | mini-epoch << 8, this, update)
+    RS_DAGGER = 29,   // distillation's DAgger mixing: entry 0 = the uniform that decides whether the teacher drives this (row, step) (bg_distill_act_mix)
     RS_ACTOR = 32,    // + k : action noise (bg_actor_sample)
     // (the env-step kernels and resample_apply_kernel add 64 to their ids at reset-all: 64 .. 64 + RS_TLEVEL are in use as well)
     RS_SCAN = 128,       // + (p >> 2), p < 1024 : noise of the actor's height scan, point p at entry p & 3 (bg_obs_assemble): 128 .. 383

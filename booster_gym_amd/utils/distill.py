@@ -19,8 +19,21 @@ what its joints and IMU did over the last steps, a perceptive teacher does not n
 writes a second row per step, the student's [47 Hs] (env.student_frame_stack; the last 47 H columns are the teacher's first 47 H, noise included), the
 rollout's launch is bg_distill_act_hist (the student half on its own buffer), the update regresses on buffer["student_obses"], and the checkpoint
 re-enters under env.frame_stack: Hs, env.num_observations: 47 Hs.  Absent, null or equal to H: every call is the one described above.
+
+distillation.symmetric_coef: c > 0 adds the mirror-symmetry loss of algorithm.symmetry_loss to the student: an epoch minimises
+1 / (A B) sum_r |mu(x_r) - label_r|^2 + c / (A B) sum_r |mu(M_o x_r) - M_a mu(x_r)|^2, M_o / M_a the maps of envs/mirror.py for the student's row
+(47 H or 47 Hs columns, the single observation's map tiled over the frames; no scan).  The student's input then holds 2B rows, the batch and behind it
+its mirror images (bg_mirror_rows, once per update), the hidden layers and the grouped weight gradients run on 2B rows under the plan of 2B rows, and
+the output layer is bg_distill_head_sym.  Nothing but the teacher's labels ties a blind student's left to its right; this term does.
+
+distillation.teacher_action_prob: beta_0 > 0 is DAgger's mixing (Ross et al. 2011): in iteration i the teacher drives each (env, step) with
+probability beta_i = beta_0 max(0, 1 - i / teacher_action_iterations) (teacher_action_iterations: 0 = constant), the student otherwise; the rollout's
+launch is bg_distill_act_mix, on the same buffers.  teacher_action_noise: a teacher-driven step carries the student's exploration noise (the very
+draw the student would have used), false: the teacher's mean alone.  The update is untouched: labels are the teacher's mean on every visited row,
+whoever drove.  With both keys at their defaults every launch, random stream, buffer, log name and checkpoint key is what it is without them.
 """
 import argparse
+import ctypes
 import math
 import os
 import random
@@ -31,6 +44,7 @@ import torch
 
 from .. import _lib
 from ..envs import TASKS
+from ..envs.mirror import mirror_maps
 from ..envs.t1 import MAX_CRITIC_INPUT, MAX_FRAME_STACK, frame_stack_of
 from .buffer import ExperienceBuffer
 from .config import load_cfg
@@ -38,10 +52,11 @@ from .model import CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, MLPTrainer, We
 from .recorder import Recorder
 from .runner import FlatAdam, hidden_widths, pad_input, wgrad_products
 from .terrain import actor_heights_of, height_scan_points
-from .utils import head_scratch, reduce_group
+from .utils import head_scratch, mirror_rows, reduce_group
 
 DEFAULTS = {"teacher_checkpoint": None, "student_hidden": [256, 128, 128], "num_epochs": 5, "learning_rate": 1.0e-3, "max_grad_norm": 1.0,
-            "student_noise_std": 0.1, "student_frame_stack": None}
+            "student_noise_std": 0.1, "student_frame_stack": None, "symmetric_coef": 0.0, "teacher_action_prob": 0.0, "teacher_action_iterations": 0,
+            "teacher_action_noise": True}
 
 
 class DistillCfg(NamedTuple):
@@ -111,6 +126,49 @@ def student_frame_stack_of(cfg):
     return Hs
 
 
+def _key(cfg, key):
+    sec = cfg.get("distillation")
+    return sec.get(key, DEFAULTS[key]) if isinstance(sec, dict) else DEFAULTS[key]
+
+
+def _number(x):
+    return not isinstance(x, bool) and isinstance(x, (int, float)) and math.isfinite(x)
+
+
+def symmetric_coef_of(cfg):
+    """distillation.symmetric_coef as a float: the weight c of the mirror-symmetry loss on the student's mean, 0 (the default, also absent) = off.
+    Pure.  ValueError naming the key unless it is a finite number >= 0."""
+    c = _key(cfg, "symmetric_coef")
+    if not _number(c) or c < 0:
+        raise ValueError(f"distillation.symmetric_coef must be a finite number >= 0 (0: no symmetry loss on the student), got {c!r}")
+    return float(c)
+
+
+def teacher_action_of(cfg):
+    """(beta_0, iterations, noise) of DAgger's mixing: distillation.teacher_action_prob in [0, 1] (0, the default: the student always acts),
+    teacher_action_iterations (an integer >= 0: beta reaches 0 after that many iterations, 0 = constant) and teacher_action_noise (a bool).  Pure.
+    ValueError naming the key of a bad value."""
+    b0, n, noise = (_key(cfg, k) for k in ("teacher_action_prob", "teacher_action_iterations", "teacher_action_noise"))
+    if not _number(b0) or not 0 <= b0 <= 1:
+        raise ValueError(f"distillation.teacher_action_prob must be a number in [0, 1] (the probability with which the teacher acts; 0: never), got {b0!r}")
+    if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+        raise ValueError(f"distillation.teacher_action_iterations must be an integer >= 0 (iterations until the probability is 0; 0: constant), got {n!r}")
+    if not isinstance(noise, bool):
+        raise ValueError(f"distillation.teacher_action_noise must be true or false, got {noise!r}")
+    return float(b0), n, noise
+
+
+def teacher_action_prob_at(beta0, iterations, it):
+    """beta of iteration `it`: beta0 max(0, 1 - it / iterations), constant beta0 with iterations = 0."""
+    return float(beta0) if not iterations else float(beta0) * max(0.0, 1.0 - it / iterations)
+
+
+def student_mirror_maps(dof_names, dof_axes, default_dof_pos, frames):
+    """(obs_src, obs_sign, act_src, act_sign) of the student's row: `frames` single observations side by side (H, or Hs with
+    distillation.student_frame_stack), the single observation's map tiled over them, and no height scan behind them.  mirror_maps' ValueErrors."""
+    return mirror_maps(dof_names, dof_axes, default_dof_pos, _lib.NUM_OBS * int(frames), int(frames), None)
+
+
 def student_overrides(num_observations, student_frame_stack=None):
     """The rule under which a student re-enters Runner / play.py / export_model.py / evaluate.py, written once: the teacher's config without the
     actor's scan, the student's own history when it has one, and the row its actor takes.  student_cfg_overrides derives the arguments from the
@@ -157,16 +215,19 @@ class Distiller:
                 cfg.setdefault("distillation", {})
                 if isinstance(cfg["distillation"], dict):
                     cfg["distillation"]["teacher_checkpoint"] = self.args.teacher
-            if self.args.student_frame_stack is not None:
-                cfg.setdefault("distillation", {})
-                if isinstance(cfg["distillation"], dict):
-                    cfg["distillation"]["student_frame_stack"] = self.args.student_frame_stack
+            for arg in ("student_frame_stack", "symmetric_coef", "teacher_action_prob", "teacher_action_iterations"):
+                if getattr(self.args, arg) is not None:
+                    cfg.setdefault("distillation", {})
+                    if isinstance(cfg["distillation"], dict):
+                        cfg["distillation"][arg] = getattr(self.args, arg)
         self.cfg = cfg
         cfg["basic"].setdefault("task", "T1")
         cfg["basic"]["rank"] = self.rank = 0
         self.dcfg = distillation_cfg(cfg, int(os.environ.get("WORLD_SIZE", "1")))  # (ValueError before anything is built)
         if not self.dcfg.teacher_checkpoint:
             raise ValueError("distillation.teacher_checkpoint is not set: the path of a checkpoint trained with terrain.actor_heights (distill.py --teacher=PATH)")
+        self.symmetric_coef = symmetric_coef_of(cfg)
+        self.beta0, self.beta_iterations, self.teacher_noise = teacher_action_of(cfg)
         Hs, H = student_frame_stack_of(cfg), frame_stack_of(cfg)
         self.history = Hs > H  # the student's own, longer history: a second row of the env, bg_distill_act_hist
         if self.history:
@@ -205,26 +266,33 @@ class Distiller:
         buf.add_buffer("dones", (), dtype=torch.bool)
         buf.add_buffer("time_outs", (), dtype=torch.bool)
         kin = pad_input(self.student_obs)
-        self._student_in = torch.zeros(self.B, kin, device=dev)  # (the padded columns stay zero)
+        self.symmetry = self.symmetric_coef > 0
+        rows = 2 * self.B if self.symmetry else self.B  # with the symmetry loss: the batch, then its mirror images (bg_mirror_rows in update())
+        if self.symmetry:  # (ValueError for a model without a left / right pairing or with an asymmetric default pose)
+            axes = [int(a) for a in env.model.joint_axis if int(a) != 0]
+            obs_src, obs_sign, act_src, act_sign = student_mirror_maps(env.dof_names, axes, env.default_dof_pos[0].cpu().numpy(), Hs if self.history else H)
+            self._act_mirror = ((ctypes.c_int32 * A)(*[int(v) for v in act_src]), (ctypes.c_float * A)(*[float(v) for v in act_sign]))
+            self._obs_mirror = (obs_src.tolist() + [-1] * (kin - len(obs_src)), obs_sign.tolist() + [1.0] * (kin - len(obs_sign)))
+        self._student_in = torch.zeros(rows, kin, device=dev)  # (the padded columns stay zero)
         self._clock = WeightClock()  # (of the student's actor parameters; one trainer reads it)
         self._trainer = tr = MLPTrainer(self.student.actor, clock=self._clock)
         widths = (tr.layers[0].in_features,) + tuple(l.out_features for l in tr.layers)
         sw = MLPTrainer
-        tr.plan = plan = plan_network(widths, kin, self.B, sw.SPLIT, sw.FUSED, sw.CHAIN, sw.CHAIN_SPLIT, sw.CHAIN_SPLIT_BWD, sw.CHAIN_ALTERNATE, sw.FUSED_WGRAD)
+        tr.plan = plan = plan_network(widths, kin, rows, sw.SPLIT, sw.FUSED, sw.CHAIN, sw.CHAIN_SPLIT, sw.CHAIN_SPLIT_BWD, sw.CHAIN_ALTERNATE, sw.FUSED_WGRAD)
         if "library" in (plan.fwd, plan.bwd) or not all(plan.grouped[:-1]):
             raise ValueError(f"distillation: a batch of runner.horizon_length x env.num_envs = {T} x {N} = {self.B} rows is outside the range of the layer "
                              "kernels (an even number of 64 rows or more)")
         shapes = [(co, ci) for ci, co in zip((kin,) + widths[1:-2], widths[1:-1])]
         # the products of the grouped weight-gradient launch, by runner.plan_update's rule: the bf16 splits behind the chained split backward only
-        self._wgrad_terms = wgrad_products(self.B, shapes, plan.bwd == "chain_split", sw.SPLIT, sw.WGRAD_SPLIT)
+        self._wgrad_terms = wgrad_products(rows, shapes, plan.bwd == "chain_split", sw.SPLIT, sw.WGRAD_SPLIT)
         self._wgrad = GroupedWeightGrad()
         self._head_scratch = head_scratch(dev)
-        self._stats = torch.zeros(1, dtype=torch.float64, device=dev)
-        self._losses = torch.zeros(self.dcfg.num_epochs, dtype=torch.float64, device=dev)
+        self._stats = torch.zeros(2 if self.symmetry else 1, dtype=torch.float64, device=dev)  # squared errors (, squared mean asymmetries)
+        self._losses = torch.zeros(self.dcfg.num_epochs, self._stats.numel(), dtype=torch.float64, device=dev)
         self._act_counter = 0
         self._descs = (None, None, None)
         self.iteration_count = 0
-        self.last_loss = float("nan")
+        self.last_loss = self.last_symmetry_loss = float("nan")
 
     # ------------------------------------------------------------------ config / seed / teacher
     def _get_args(self, args=None):
@@ -233,6 +301,11 @@ class Distiller:
         parser.add_argument("--teacher", type=str, help="Path of the perceptive teacher's checkpoint. Overrides distillation.teacher_checkpoint.")
         parser.add_argument("--student_frame_stack", type=int, help="Observation frames of the student's input (at least the teacher's env.frame_stack). "
                             "Overrides distillation.student_frame_stack.")
+        parser.add_argument("--symmetric_coef", type=float, help="Weight of the mirror-symmetry loss on the student's mean (0: off). Overrides distillation.symmetric_coef.")
+        parser.add_argument("--teacher_action_prob", type=float, help="Probability with which the teacher acts in the rollout (DAgger's mixing; 0: never). "
+                            "Overrides distillation.teacher_action_prob.")
+        parser.add_argument("--teacher_action_iterations", type=int, help="Iterations over which that probability falls to 0 (0: constant). "
+                            "Overrides distillation.teacher_action_iterations.")
         parser.add_argument("--max_iterations", type=int, help="Number of distillation iterations. Overrides config file if provided.")
         parser.add_argument("--num_envs", type=int, help="Number of environments to create. Overrides config file if provided.")
         parser.add_argument("--sim_device", type=str, help="Device for physics simulation. Overrides config file if provided.")
@@ -292,6 +365,10 @@ class Distiller:
              "distillation": {"teacher": str(self.dcfg.teacher_checkpoint), "iteration": int(self.iteration_count), "loss": float(self.last_loss)}}
         if self.history:
             d["distillation"]["student_frame_stack"] = self.env.student_frame_stack
+        if self.symmetry:
+            d["distillation"]["symmetric_coef"] = self.symmetric_coef
+        if self.beta0 > 0:
+            d["distillation"]["teacher_action_prob"] = [self.beta0, self.beta_iterations]
         if self.env.terrain.curriculum:
             d["terrain_levels"] = self.env.terrain_levels
         return d
@@ -307,13 +384,30 @@ class Distiller:
             self._descs = (key, arrs[0], arrs[1])
         return self._descs[1], self._descs[2]
 
+    def teacher_action_prob(self):
+        """beta of the current iteration (distillation.teacher_action_prob and teacher_action_iterations): 0 with the key off."""
+        return teacher_action_prob_at(self.beta0, self.beta_iterations, self.iteration_count)
+
     def rollout(self):
-        """T env steps with the student's sampled actions; every visited row and the teacher's mean action on it are kept."""
+        """T env steps with the student's sampled actions (with distillation.teacher_action_prob: the teacher's on a share beta of the rows); every
+        visited row and the teacher's mean action on it are kept."""
         buf, T, N = self.buffer, self.T, self.N
         obses, priv, actions, labels = buf["obses"], buf["privileged_obses"], buf["actions"], buf["teacher_mu"]
         seed = int(self.cfg["basic"]["seed"]) + 1000003  # (Runner's rollout seed of rank 0)
         sd, td = self._descriptors()
         lib, logstd = _lib.load(), self.student.logstd
+        if self.beta0 > 0:  # DAgger's mixing: one launch of its own kind on the same buffers, the student's rows its own with a longer history
+            beta, noise = self.teacher_action_prob(), int(self.teacher_noise)
+            sobs = buf["student_obses"] if self.history else obses
+            with torch.no_grad():
+                for n in range(T):
+                    _lib.check(lib.bg_distill_act_mix(N, _lib.ptr(obses[n]), obses.shape[-1], _lib.ptr(sobs[n]), sobs.shape[-1], len(sd), sd, len(td), td, self.scan,
+                                                      _lib.ptr(logstd), seed, self._act_counter, beta, noise, None, _lib.ptr(actions[n]), _lib.ptr(labels[n]),
+                                                      _lib.current_stream_ptr()), "bg_distill_act_mix")
+                    self._act_counter += 1
+                    self.env.step_to(actions[n], obses[n + 1], priv[n + 1], buf["rewards"][n], buf["dones"][n], buf["time_outs"][n],
+                                     **({"student_obs": sobs[n + 1]} if self.history else {}))
+            return
         if self.history:
             sobs = buf["student_obses"]
             with torch.no_grad():
@@ -333,28 +427,38 @@ class Distiller:
 
     def update(self):
         """num_epochs full-batch behaviour-cloning steps on the rollout's rows.  Returns the per-epoch mean losses (float64 device tensor: the loss
-        each step's gradient was taken of)."""
+        each step's gradient was taken of); with distillation.symmetric_coef the per-epoch mean squared asymmetries are left in symmetry_losses."""
         tr, B, A = self._trainer, self.B, self.env.num_actions
         out, hid = tr.layers[-1], tr.layers[-2]
         target = self.buffer["teacher_mu"].reshape(B, A)
         with torch.no_grad():
             rows = self.buffer["student_obses" if self.history else "obses"][: self.T].reshape(B, -1)
-            self._student_in[:, : self.student_obs].copy_(rows[:, : self.student_obs])
+            self._student_in[:B, : self.student_obs].copy_(rows[:, : self.student_obs])
+            if self.symmetry:  # rows [B, 2B): the mirror images M_o x of the batch (the padded columns stay zero)
+                mirror_rows(self._student_in[:B], self._student_in[B:], *self._obs_mirror)
             for e in range(self.dcfg.num_epochs):
                 h = tr.forward_hidden(self._student_in)
                 self._stats.zero_()
                 fin, fins = _lib.ReduceProblem(), []
-                _lib.check(_lib.load().bg_distill_head_partial(B, _lib.ptr(h), _lib.ptr(out.weight), _lib.ptr(out.bias), _lib.ptr(target), None,
-                                                               _lib.ptr(tr.hidden_grad), _lib.ptr(out.weight.grad), _lib.ptr(out.bias.grad), _lib.ptr(hid.bias.grad),
-                                                               _lib.ptr(self._stats), _lib.ptr(self._head_scratch), fin, _lib.current_stream_ptr()),
-                           "bg_distill_head_partial")
+                if self.symmetry:
+                    _lib.check(_lib.load().bg_distill_head_sym_partial(B, _lib.ptr(h), _lib.ptr(out.weight), _lib.ptr(out.bias), _lib.ptr(target), self.symmetric_coef,
+                                                                       *self._act_mirror, None, _lib.ptr(tr.hidden_grad), _lib.ptr(out.weight.grad),
+                                                                       _lib.ptr(out.bias.grad), _lib.ptr(hid.bias.grad), _lib.ptr(self._stats),
+                                                                       _lib.ptr(self._head_scratch), fin, _lib.current_stream_ptr()), "bg_distill_head_sym_partial")
+                else:
+                    _lib.check(_lib.load().bg_distill_head_partial(B, _lib.ptr(h), _lib.ptr(out.weight), _lib.ptr(out.bias), _lib.ptr(target), None,
+                                                                   _lib.ptr(tr.hidden_grad), _lib.ptr(out.weight.grad), _lib.ptr(out.bias.grad), _lib.ptr(hid.bias.grad),
+                                                                   _lib.ptr(self._stats), _lib.ptr(self._head_scratch), fin, _lib.current_stream_ptr()),
+                               "bg_distill_head_partial")
                 tr.backward_hidden(finishes=fins)
                 self._wgrad.run((tr,), self._wgrad_terms, False)
                 reduce_group([fin] + fins)
                 self.optimizer.step()
                 self._clock.tick()
-                self._losses[e : e + 1].copy_(self._stats)
-        return self._losses / float(A * B)
+                self._losses[e].copy_(self._stats)
+        if self.symmetry:
+            self.symmetry_losses = self._losses[:, 1] / float(A * B)
+        return self._losses[:, 0] / float(A * B)
 
     def iteration(self):
         self.rollout()
@@ -373,10 +477,18 @@ class Distiller:
             self.buffer["student_obses"][0].copy_(infos["student_obs"])
 
     def train_iteration(self, it):
+        beta = self.teacher_action_prob()  # (of the iteration about to run)
         losses = self.iteration()
-        self.last_loss = float(losses[-1].item())  # (one host read per iteration)
+        if self.symmetry:
+            self.last_loss, self.last_symmetry_loss = (float(v) for v in (self._losses[-1] / float(self.env.num_actions * self.B)).tolist())  # (one host read)
+        else:
+            self.last_loss = float(losses[-1].item())  # (one host read per iteration)
         self.recorder.record_episode_statistics(self.env, self.env.reward_names, it)
         stats = {"distill/behaviour_loss": self.last_loss}
+        if self.symmetry:
+            stats["distill/symmetry_loss"] = self.last_symmetry_loss
+        if self.beta0 > 0:
+            stats["distill/teacher_action_prob"] = beta
         if self.env.terrain.curriculum:
             stats["terrain/mean_level"] = float(self.env.terrain_level_sum().item()) / self.env.num_envs
         self.recorder.record_statistics(stats, it)

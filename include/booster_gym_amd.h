@@ -371,6 +371,18 @@ int bg_distill_act(int32_t N, const float* obs, int32_t obs_stride, int32_t n_st
 int bg_distill_act_hist(int32_t N, const float* teacher_obs, int32_t teacher_stride, const float* student_obs, int32_t student_stride, int32_t n_student,
                         const bg_mlp_layer_desc* student, int32_t n_teacher, const bg_mlp_layer_desc* teacher, int32_t scan_points,
                         const float* student_logstd, uint64_t seed, uint64_t counter, float* student_mu, float* actions, float* teacher_mu, void* stream);
+/* bg_distill_act_hist with DAgger's mixing (T1.yaml distillation.teacher_action_prob): per row the teacher acts with probability beta, else the student.
+ * Arguments and rules of bg_distill_act_hist (the same buffer and stride twice: bg_distill_act's case) plus beta in [0, 1] (outside it, or not finite:
+ * -1, the message naming beta, before any launch) and teacher_noise.  Per row: u = entry 0 of Philox(seed, row, counter, RS_DAGGER = 29), the teacher
+ * acts iff u < beta (fp32).  student_mu and teacher_mu are bg_distill_act_hist's.  actions[row]: the student acts: bg_distill_act_hist's value, mu_s +
+ * exp(student_logstd) n; the teacher acts: mu_t + exp(student_logstd) n with the SAME n (Philox(seed, row, counter, RS_ACTOR + group of 4 actions)),
+ * or mu_t alone with teacher_noise = 0.  One launch on the split grid: both halves evaluate u, the half that acts writes the row (disjoint rows: no
+ * atomics, no second pass).  beta = 0 equals bg_distill_act_hist in all three outputs, beta = 1 gives bg_actor_sample_mlp_scan's actions of the
+ * teacher under the student's logstd, bit for bit. */
+int bg_distill_act_mix(int32_t N, const float* teacher_obs, int32_t teacher_stride, const float* student_obs, int32_t student_stride, int32_t n_student,
+                       const bg_mlp_layer_desc* student, int32_t n_teacher, const bg_mlp_layer_desc* teacher, int32_t scan_points,
+                       const float* student_logstd, uint64_t seed, uint64_t counter, float beta, int32_t teacher_noise, float* student_mu, float* actions,
+                       float* teacher_mu, void* stream);
 /* Fused global-norm clip + Adam over one flat parameter buffer (runner.py:162-165); lr is read from device memory
  * so the KL-adaptive schedule (runner.py:174-180) needs no host sync.  gnorm_scratch [1] device float64. */
 int bg_adam_step(int32_t n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const float* lr_device, int32_t step,
@@ -564,6 +576,16 @@ int bg_actor_head_sym(int32_t B, const float* h, const float* W, const float* bi
 /* y [rows][cols] = the rows of x [rows][cols] mirrored: y[r][c] = sign[c] x[r][src[c]] (src[c] = -1: 0), cols <= 512, src / sign host arrays of cols,
  * sign +-1; x and y must not overlap.  Exact. */
 int bg_mirror_rows(int32_t rows, int32_t cols, const int32_t* src, const float* sign, const float* x, float* y, void* stream);
+/* Mirror-symmetry loss on the distillation's student (T1.yaml distillation.symmetric_coef): bg_distill_head on a batch of 2B rows laid out as for
+ * bg_actor_head_sym (h / g_hidden / mu_out [2B] rows, rows [B, 2B) the mirror images of rows [0, B); target [B][12]).  L = 1 / (12 B) sum_r |mu_r -
+ * target_r|^2 over the original rows + sym_coef / (12 B) sum_r |d_r|^2, d_r = mu(M_o x_r) - M_a mu(x_r), differentiated through both means: with s = 2
+ * sym_coef / (12 B), dL/dmu of a mirrored row is s d and of an original row 2 (mu - target) / (12 B) - s M_a d.  g_hidden [2B][128], grad_W / grad_b /
+ * grad_b_hidden over all 2B rows, stats[0] += the sum of squared errors, stats[1] += sum_r |d_r|^2 (float64; the caller zeroes).  sym_coef finite and
+ * >= 0, M_a as for bg_actor_head_sym (-1 otherwise).  mu_out [2B][12] may be NULL; its rows [0, B) are bg_distill_head's bits.  Fixed-order sums:
+ * deterministic; nothing is written past row 2B. */
+int bg_distill_head_sym(int32_t B, const float* h, const float* W, const float* bias, const float* target, float sym_coef, const int32_t* act_src,
+                        const float* act_sign, float* mu_out, float* g_hidden, float* grad_W, float* grad_b, float* grad_b_hidden, double* stats, float* scratch,
+                        void* stream);
 
 /* ---- deferred fixed-order reductions.  The head kernels and the backward layer kernel leave per-workgroup partial sums that a small second
  * kernel adds up (head: output-layer weight / bias gradients, last hidden layer's bias gradient, float64 loss statistics; backward layer: the
@@ -639,6 +661,10 @@ int bg_mlp_layer_backward_partial(int32_t M, int32_t K, int32_t N, const float* 
 /* bg_distill_head without its finishing launch (as bg_actor_head_partial). */
 int bg_distill_head_partial(int32_t B, const float* h, const float* W, const float* bias, const float* target, float* mu_out, float* g_hidden, float* grad_W,
                             float* grad_b, float* grad_b_hidden, double* stats, float* scratch, bg_reduce_problem* finish, void* stream);
+/* bg_distill_head_sym without its finishing launch (as bg_actor_head_partial). */
+int bg_distill_head_sym_partial(int32_t B, const float* h, const float* W, const float* bias, const float* target, float sym_coef, const int32_t* act_src,
+                                const float* act_sign, float* mu_out, float* g_hidden, float* grad_W, float* grad_b, float* grad_b_hidden, double* stats,
+                                float* scratch, bg_reduce_problem* finish, void* stream);
 
 /* ---- empirical observation normalisation (algorithm.empirical_normalization; bg_obs_norm.hip).  Two launches of their own beside the hot path:
  * nothing of them runs when the key is false.

@@ -14,6 +14,14 @@
           here (the run under a kernel trace, which gives the launch's own time);
       (5) bg_distill_act_hist on a buffer of the student's own against bg_distill_act at Hs = H (same networks, expected equal), and at Hs;
       (6) the loop of (3) with the key absent and with it, one Distiller after the other, `pairs` times each.
+  With symmetric_coef=C and / or teacher_action_prob=BETA anywhere among the arguments (distillation.symmetric_coef / teacher_action_prob; out "-" =
+  profiles/distill_symmetry_dagger_time.txt; each defaults to 10 / 0.5 when only the other is given) the sections are those of the two keys instead:
+      (7) bg_distill_act_mix at beta = 0, 0.5 and 1 against bg_distill_act on the same rows at H = 1 / P = 187, and with Hs (5 unless given) against
+          bg_distill_act_hist, the same way as (1);
+      (8) bg_distill_head_sym at B = 98,304 (2B rows) against bg_distill_head at B and at 2B rows and against bg_actor_head_sym at B, and the bytes
+          it moves as a fraction of the float4-copy rate;
+      (9) the loop of (3) with neither key, with the loss, with the mixing, and with both, one Distiller after the other, `pairs` times each.
+          `only` = "head" runs (8) alone, "loop" (9) alone.
   The outputs of (1) are compared bit for bit before they are timed.  The committed profile carries two more sections that this tool does not
   write: the figures tests/test_gpu_distill.py prints under -s, and bench.py of this tree against a checkout of its parent commit."""
 import os
@@ -184,7 +192,94 @@ def act_hist(pairs=3, N=4096, Hs=5, P=187):
                 say(f"rollout inference, {N} rows, H = 1, P = {P}, both 256-128-128, Hs = {hs} ({47 * hs} student columns): bg_distill_act_hist {_best(hist, 200):.2f} us")
 
 
-def loop(K=20, W=5, pairs=3, N=4096, Hs=None):
+def act_mix(pairs=3, N=4096, Hs=5, P=187):
+    from booster_gym_amd import _lib
+    from booster_gym_amd.utils.model import ActorCritic
+
+    lib, p = _lib.load(), _lib.ptr
+    torch.manual_seed(1)
+    teacher = ActorCritic(12, 47 + P, 14 + P).to(DEV)
+    obs = torch.randn(N, 47 + P, device=DEV)
+    (td, nt), st = _descs(teacher), _lib.current_stream_ptr()
+    for hs in (1, Hs):
+        student = ActorCritic(12, 47 * hs, 14 + P).to(DEV)
+        sobs = obs if hs == 1 else torch.randn(N, 47 * hs, device=DEV)
+        (sd, ns) = _descs(student)
+        a1, t1, a2, t2 = (torch.empty(N, 12, device=DEV) for _ in range(4))
+        base = "bg_distill_act" if hs == 1 else "bg_distill_act_hist"
+
+        def plain(k):
+            if hs == 1:
+                _lib.check(lib.bg_distill_act(N, p(obs), 47 + P, ns, sd, nt, td, P, p(student.logstd), 1, k, None, p(a2), p(t2), st), base)
+            else:
+                _lib.check(lib.bg_distill_act_hist(N, p(obs), 47 + P, p(sobs), 47 * hs, ns, sd, nt, td, P, p(student.logstd), 1, k, None, p(a2), p(t2), st), base)
+
+        def mix(beta):
+            return lambda k: _lib.check(lib.bg_distill_act_mix(N, p(obs), 47 + P, p(sobs), sobs.shape[1], ns, sd, nt, td, P, p(student.logstd), 1, k, beta, 1, None, p(a1),
+                                                               p(t1), st), "bg_distill_act_mix")
+
+        mix(0.0)(7); plain(7); torch.cuda.synchronize()
+        assert torch.equal(a1, a2) and torch.equal(t1, t2), f"bg_distill_act_mix at beta = 0 differs from {base}"
+        fns = (("plain", plain), ("mix 0", mix(0.0)), ("mix 0.5", mix(0.5)), ("mix 1", mix(1.0)))
+        for q in range(pairs):
+            us = {m: _best(f, 200) for m, f in _orders(q, fns)}
+            say(f"rollout inference, {N} rows, H = 1, P = {P}, both 256-128-128, student columns {47 * hs}: {base} {us['plain']:.2f} us, bg_distill_act_mix beta = 0 "
+                f"{us['mix 0']:.2f} us ({us['mix 0'] / us['plain']:.4f}x), beta = 0.5 {us['mix 0.5']:.2f} us ({us['mix 0.5'] / us['plain']:.4f}x), beta = 1 "
+                f"{us['mix 1']:.2f} us ({us['mix 1'] / us['plain']:.4f}x)")
+
+
+def head_sym(pairs=3, B=98304, coef=10.0):
+    import json
+
+    from booster_gym_amd import _lib
+    from booster_gym_amd.envs.mirror import mirror_maps
+    from booster_gym_amd.utils.utils import actor_head_sym_loss_backward, head_scratch
+
+    m = json.load(open(os.path.join(ROOT, "booster_gym_amd", "resources", "T1", "T1_locomotion.flat.json")))
+    _, _, act_src, act_sign = mirror_maps(m["dof_names"], [a for a in m["joint_axis"] if a], [-0.2, 0, 0, 0.4, -0.25, 0] * 2, 47)
+    import ctypes
+
+    src, sign = (ctypes.c_int32 * 12)(*[int(v) for v in act_src]), (ctypes.c_float * 12)(*[float(v) for v in act_sign])
+    g = torch.Generator(device="cpu").manual_seed(0)
+    A = 12
+    h = torch.nn.functional.elu(torch.randn(2 * B, 128, generator=g)).to(DEV)
+    W, b = (torch.randn(A, 128, generator=g) * 0.1).to(DEV), (torch.randn(A, generator=g) * 0.1).to(DEV)
+    target = torch.randn(2 * B, A, generator=g).to(DEV)
+    logstd = torch.full((A,), -2.0, device=DEV)
+    old_mu = h[:B] @ W.t() + b + 0.02 * torch.randn(B, A, generator=g).to(DEV)
+    actions = old_mu + 0.135 * torch.randn(B, A, generator=g).to(DEV)
+    old_logp = (-0.5 * ((actions - old_mu) / logstd.exp()) ** 2 - logstd - 0.9189385332046727).sum(-1)
+    adv = torch.randn(B, generator=g).to(DEV)
+    adv_stats = torch.stack([adv.double().sum(), (adv.double() ** 2).sum(), torch.tensor(float(B), dtype=torch.float64, device=DEV)])
+    gh, dW, db, dbh = torch.empty(2 * B, 128, device=DEV), torch.empty(A, 128, device=DEV), torch.empty(A, device=DEV), torch.empty(128, device=DEV)
+    gls, st6, st2, scr = torch.zeros(A, dtype=torch.float64, device=DEV), torch.zeros(6, dtype=torch.float64, device=DEV), torch.zeros(2, dtype=torch.float64, device=DEV), head_scratch(DEV)
+    lib, p = _lib.load(), _lib.ptr
+
+    def sym(k):
+        _lib.check(lib.bg_distill_head_sym(B, p(h), p(W), p(b), p(target), coef, src, sign, None, p(gh), p(dW), p(db), p(dbh), p(st2), p(scr), _lib.current_stream_ptr()),
+                   "bg_distill_head_sym")
+
+    def plain(rows):
+        return lambda k: _lib.check(lib.bg_distill_head(rows, p(h), p(W), p(b), p(target), None, p(gh), p(dW), p(db), p(dbh), p(st2), p(scr), _lib.current_stream_ptr()),
+                                    "bg_distill_head")
+
+    def actor_sym(k):
+        actor_head_sym_loss_backward(h, W, b, logstd, actions, old_mu, logstd, old_logp, adv, adv_stats, 0.2, 1.0, -0.01, coef, (act_src, act_sign), gh, dW, db, dbh, gls,
+                                     st6, scr)
+
+    fns = (("sym", sym), ("plain B", plain(B)), ("plain 2B", plain(2 * B)), ("actor sym", actor_sym))
+    for q in range(pairs):
+        us = {m: _best(f, 100) for m, f in _orders(q, fns)}
+        # the kernel reads h [2B][128] and target [B][12] and writes g_hidden [2B][128]
+        nbytes = (2 * B * 128 * 2 + B * 12) * 4
+        tbs = nbytes / (us["sym"] * 1e-6) / 1e12
+        say(f"loss head, B = {B}: bg_distill_head_sym (2B rows) {us['sym']:.2f} us ({nbytes / 1e6:.1f} MB of h + target read and g_hidden written = {tbs:.2f} TB/s, "
+            f"{100 * tbs / 6.29:.0f} % of the 6.29 TB/s of a float4 copy; finish launch included), bg_distill_head at B rows {us['plain B']:.2f} us "
+            f"(sym / plain = {us['sym'] / us['plain B']:.4f}), at 2B rows {us['plain 2B']:.2f} us (sym / plain = {us['sym'] / us['plain 2B']:.4f}), "
+            f"bg_actor_head_sym at B {us['actor sym']:.2f} us (distill sym / actor sym = {us['sym'] / us['actor sym']:.4f})")
+
+
+def loop(K=20, W=5, pairs=3, N=4096, Hs=None, coef=0.0, beta=0.0):
     from booster_gym_amd.utils.config import load_cfg
     from booster_gym_amd.utils.distill import Distiller
     from booster_gym_amd.utils.model import ActorCritic
@@ -200,6 +295,10 @@ def loop(K=20, W=5, pairs=3, N=4096, Hs=None):
     cfg["distillation"]["teacher_checkpoint"] = ck
     if Hs:
         cfg["distillation"]["student_frame_stack"] = Hs
+    if coef:
+        cfg["distillation"]["symmetric_coef"] = coef
+    if beta:
+        cfg["distillation"]["teacher_action_prob"] = beta
     d = Distiller(cfg=cfg)
     d.begin(Recorder(cfg, root=tmp, rank=0))
     it = 0
@@ -216,7 +315,8 @@ def loop(K=20, W=5, pairs=3, N=4096, Hs=None):
     T, E = cfg["runner"]["horizon_length"], d.dcfg.num_epochs
     for q in range(pairs):
         ms = run(K)
-        say(f"distillation loop, {N} envs, H = 1, P = 187, student_frame_stack {Hs or 'absent'} ({d.student_obs} student columns padded to {d._student_in.shape[1]}), horizon {T}, {E} epochs, student 256-128-128 (plan {d._trainer.plan.fwd} / {d._trainer.plan.bwd}, weight "
+        keys = f"symmetric_coef {coef:g}, teacher_action_prob {beta:g}, " if coef or beta or KEYS else ""
+        say(f"distillation loop, {N} envs, H = 1, P = 187, {keys}student_frame_stack {Hs or 'absent'} ({d.student_obs} student columns padded to {d._student_in.shape[1]}), horizon {T}, {E} epochs, student 256-128-128 (plan {d._trainer.plan.fwd} / {d._trainer.plan.bwd}, weight "
             f"gradients {d._wgrad_terms or 'fp32'}): {ms:.3f} ms per iteration = {1e3 / ms:.2f} iterations/s = {N * T / ms / 1e3:.3f} M env-steps/s; last loss "
             f"{d.last_loss:.6f}")
     for ph, fn in (("rollout", d.rollout), ("update", d.update)):
@@ -229,13 +329,27 @@ def loop(K=20, W=5, pairs=3, N=4096, Hs=None):
         say(f"  {ph} alone: {best:.3f} ms (best of 3)")
 
 
+KEYS = {}  # symmetric_coef / teacher_action_prob given on the command line: sections (7) to (9)
+
+
 if __name__ == "__main__":
-    a = sys.argv[1:]
+    KEYS.update({k: float(v) for k, v in (x.split("=", 1) for x in sys.argv[1:] if "=" in x) if k in ("symmetric_coef", "teacher_action_prob")})
+    a = [x for x in sys.argv[1:] if "=" not in x]
     K, W, pairs, N = (int(a[i]) if len(a) > i else v for i, v in enumerate((20, 5, 3, 4096)))
     Hs, only = (int(a[5]) if len(a) > 5 else 0), (a[6] if len(a) > 6 else "")
-    out = a[4] if len(a) > 4 and a[4] != "-" else os.path.join(ROOT, "profiles", "distill_history_time.txt" if Hs else "distill_time.txt")
-    say(f"tools/distill_time.py {' '.join(a) or f'{K} {W} {pairs} {N}'} on {torch.cuda.get_device_name(0)}")
-    if Hs:
+    name = "distill_symmetry_dagger_time.txt" if KEYS else "distill_history_time.txt" if Hs else "distill_time.txt"
+    out = a[4] if len(a) > 4 and a[4] != "-" else os.path.join(ROOT, "profiles", name)
+    say(f"tools/distill_time.py {' '.join(sys.argv[1:]) or f'{K} {W} {pairs} {N}'} on {torch.cuda.get_device_name(0)}")
+    if KEYS:
+        coef, beta = KEYS.get("symmetric_coef", 10.0), KEYS.get("teacher_action_prob", 0.5)
+        if only not in ("loop", "head"):
+            act_mix(pairs, N, Hs or 5)
+        if only != "loop":
+            head_sym(pairs, coef=coef)
+        for q in range(pairs if only != "head" else 0):  # (a Distiller each: the buffers and the plan are per configuration)
+            for c, bt in _orders(q, ((0.0, 0.0), (coef, 0.0), (0.0, beta), (coef, beta))):
+                loop(K, W, 1, N, None, c, bt)
+    elif Hs:
         assemble(pairs, N, Hs)
         if only != "assemble":
             act_hist(pairs, N, Hs)
