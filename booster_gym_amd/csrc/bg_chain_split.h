@@ -14,9 +14,6 @@ constexpr int CHAIN_MAX = 4;
 
 template <int V> using IC = std::integral_constant<int, V>;
 
-#define BG_PIN() __builtin_amdgcn_sched_barrier(0)
-#define BG_MFMA(ACC, A, B) ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A), __builtin_bit_cast(bf16x8, B), ACC, 0, 0, 0)
-
 // The split of one pair of fp32 values into the three planes' packed bf16 pairs (low half = x0), in four pieces that ride behind four MFMAs:
 // 3 + 3 + 3 + 2 VALU instructions (an MFMA gap takes four for free).
 struct SplitTmp { unsigned m0, m1, n0, n1; float r0, r1, s0; };

@@ -26,11 +26,14 @@ namespace {
 
 constexpr int HK = 128;    // hidden width (both networks end in a 128-wide ELU layer)
 constexpr int HT = 64;     // rows per tile
+constexpr int HTS = HT / 2;  // pairs per tile of the heads with a mirror-symmetry term: HTS rows and their HTS mirror images
 constexpr int HLD = 132;   // LDS row stride of the activation tile: 16-byte aligned, rows 4 banks apart
 constexpr int HA = BG_NUM_DOFS;
 constexpr int HEAD_MAX_GRID = 768;
 
 __device__ __forceinline__ float elu_grad_from_output(float a) { return a > 0.f ? 1.0f : a + 1.0f; }
+// dL/dz of an ELU layer from dL/d(its output hv)
+__device__ __forceinline__ float elu_back(float g, float hv) { return g * elu_grad_from_output(hv); }
 
 // coalesced load of a [HT][HK] activation tile into LDS (rows past B read as zero), in two halves so that a persistent workgroup can have the
 // NEXT tile's 8 float4 per thread in flight while it computes on the current one (tile_fetch before the compute, tile_put after it)
@@ -53,6 +56,20 @@ __device__ __forceinline__ void tile_put(const float4 (&v)[HTV], float* s_h) {
 __device__ __forceinline__ void load_tile(const float* __restrict__ h, int row0, int B, float* s_h) {
     float4 v[HTV];
     tile_fetch(h, row0, B, v);
+    tile_put(v, s_h);
+}
+// the pair tile of the heads with a mirror-symmetry term: LDS rows [0, HTS) from rows row0 .. of h, LDS rows [HTS, 2 HTS) from rows B + row0 ..
+__device__ __forceinline__ void pair_fetch(const float* __restrict__ h, int row0, int B, float4 (&v)[HTV]) {
+#pragma unroll
+    for (int i = 0; i < HTV; i++) {
+        const int idx = threadIdx.x + 256 * i, r = idx >> 5, c4 = idx & 31, o = row0 + (r & (HTS - 1));
+        v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (o < B) v[i] = *reinterpret_cast<const float4*>(h + (size_t)(r < HTS ? o : B + o) * HK + c4 * 4);
+    }
+}
+__device__ __forceinline__ void load_pair_tile(const float* __restrict__ h, int row0, int B, float* s_h) {
+    float4 v[HTV];
+    pair_fetch(h, row0, B, v);
     tile_put(v, s_h);
 }
 
@@ -78,10 +95,203 @@ __device__ __forceinline__ float quadcol_sum(float v) {
     return v;
 }
 
-// MODE 0: forward only (mu_out), MODE 1: forward + loss + backward.
-// Thread mappings: forward + loss: thread = (row t >> 2 of the tile, actions 3 (t & 3) .. + 2), the four threads of a row exchange their
-// partial log-prob / KL / bound sums with two DPP moves; backward: thread = (hidden column t & 127, row half t >> 7) with its column of W and
-// its accumulators in registers for the whole launch.
+// ---- The four loss heads on the 12-wide actor output (actor_head_kernel, distill_head_kernel and their _sym forms) are one kernel around different
+// loss lines; what they share stands here once, as functions on the kernels' own registers and LDS arrays.
+// Thread mappings: forward + loss: thread = (row fr = t >> 2 of the tile, actions 3 fq .. 3 fq + 2, fq = t & 3), the four threads of a row exchange their
+// partial sums with two DPP moves; backward: thread = (hidden column kc = t & 127, row half = t >> 7) with its column of W (wcol) and its accumulators (dW,
+// cs) in registers for the whole launch.
+// Two pieces stand twice.  The PPO row loss with its constants, in actor_head_kernel<1> and actor_head_sym_kernel: as a function, or on a struct of the
+// thread's state, it compiled to other sums (the build's -fassociative-math groups the loop-invariant terms of the log-prob and KL sums by where their
+// operands are defined), and the update promises the bits it had (profiles/one_head_arithmetic_identity.txt).  And the behaviour-cloning row, in bc_row
+// and in distill_head_kernel, for speed (there).
+
+// W into LDS, the thread's biases, its column of W (BACK: a forward-only launch has no use for it) and its zeroed weight-gradient accumulators.
+// s_w keeps the rows of W 132 floats apart: the four (t & 3) groups of a wave read rows 3 apart at the same k, which with a 128-float stride were the
+// same banks (a 4-way conflict on three of the four LDS reads of the forward loop)
+template <bool BACK>
+__device__ __forceinline__ void head_stage(const float* __restrict__ W, const float* __restrict__ bias, float* s_w, float (&fb)[3], float (&wcol)[HA],
+                                           float (&dW)[HA]) {
+    const int t = threadIdx.x;
+    for (int i = t; i < HA * HK; i += 256) s_w[(i >> 7) * HLD + (i & (HK - 1))] = W[i];
+    for (int i = 0; i < 3; i++) fb[i] = bias[3 * (t & 3) + i];
+    for (int j = 0; j < HA; j++) { wcol[j] = BACK ? W[j * HK + (t & (HK - 1))] : 0.f; dW[j] = 0.f; }
+}
+// mu = h W^T + b of row fr of the tile for the thread's three actions
+__device__ __forceinline__ void head_mu(const float* s_h, const float* s_w, int fr, int fq, const float (&fb)[3], float (&m)[3]) {
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    const float4* hr = reinterpret_cast<const float4*>(s_h + fr * HLD);
+    const float4* w0 = reinterpret_cast<const float4*>(s_w + (3 * fq) * HLD);
+    const float4* w1 = reinterpret_cast<const float4*>(s_w + (3 * fq + 1) * HLD);
+    const float4* w2 = reinterpret_cast<const float4*>(s_w + (3 * fq + 2) * HLD);
+#pragma unroll 2
+    for (int k4 = 0; k4 < HK / 4; k4++) {
+        const float4 x = hr[k4], u = w0[k4], v = w1[k4], w = w2[k4];
+        a0 = fmaf(x.x, u.x, a0); a0 = fmaf(x.y, u.y, a0); a0 = fmaf(x.z, u.z, a0); a0 = fmaf(x.w, u.w, a0);
+        a1 = fmaf(x.x, v.x, a1); a1 = fmaf(x.y, v.y, a1); a1 = fmaf(x.z, v.z, a1); a1 = fmaf(x.w, v.w, a1);
+        a2 = fmaf(x.x, w.x, a2); a2 = fmaf(x.y, w.y, a2); a2 = fmaf(x.z, w.z, a2); a2 = fmaf(x.w, w.w, a2);
+    }
+    m[0] = a0 + fb[0]; m[1] = a1 + fb[1]; m[2] = a2 + fb[2];
+}
+// dL/dmu of the thread's three actions, for the backward mapping (s_g) and the output bias gradient
+__device__ __forceinline__ void head_put_grad(float* s_g, int fr, int fq, const float (&gm)[3], float (&dbias)[3]) {
+    for (int i = 0; i < 3; i++) { s_g[fr * HA + 3 * fq + i] = gm[i]; dbias[i] += gm[i]; }
+}
+// row r of the tile at hidden column kc: returns dL/dz = (dL/dmu W) * elu'(h); dW += dL/dmu^T h
+__device__ __forceinline__ float head_back_row(const float* s_h, const float* s_g, int r, int kc, const float (&wcol)[HA], float (&dW)[HA]) {
+    constexpr int A = HA;
+    const float hv = s_h[r * HLD + kc];
+    const float4* gp = reinterpret_cast<const float4*>(s_g + r * A);
+    const float4 g0 = gp[0], g1 = gp[1], g2 = gp[2];
+    const float g[A] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w, g2.x, g2.y, g2.z, g2.w};
+    float sa = 0.f, sb = 0.f;
+#pragma unroll
+    for (int j = 0; j < A; j += 2) {
+        sa = fmaf(g[j], wcol[j], sa); sb = fmaf(g[j + 1], wcol[j + 1], sb);
+        dW[j] = fmaf(g[j], hv, dW[j]); dW[j + 1] = fmaf(g[j + 1], hv, dW[j + 1]);
+    }
+    return elu_back(sa + sb, hv);
+}
+// the tile's rows of the thread's half: g_hidden, dW and cs (the hidden bias gradient: column sums of dL/dz).  PAIR: LDS rows [0, HTS) are rows row0 ..
+// of the batch, LDS rows [HTS, 2 HTS) their mirror images at B + row0 ..
+template <bool PAIR>
+__device__ __forceinline__ void head_back_rows(const float* s_h, const float* s_g, int row0, int B, int kc, int half, const float (&wcol)[HA],
+                                               float (&dW)[HA], float& cs, float* __restrict__ g_hidden) {
+    for (int rr = 0; rr < HT / 2; rr++) {
+        const int r = half * (HT / 2) + rr, o = row0 + (PAIR ? rr : r);
+        const float gz = head_back_row(s_h, s_g, r, kc, wcol, dW);
+        cs += gz;
+        if (o < B) g_hidden[(size_t)(PAIR && half ? B + o : o) * HK + kc] = gz;
+    }
+}
+// The float part of the workgroup's record: the two row halves of the column-mapped sums meet in LDS; the per-action sums of the output bias gradient go
+// over the lanes sharing (lane & 3) within a wave into redf = s_h [4 waves][16], slot 3 fq + i.  The kernel's float64 statistics follow from s_h + 64
+// on, then a barrier, then head_record_bias().
+__device__ __forceinline__ float* head_record_sums(const float (&dW)[HA], float cs, const float (&dbias)[3], float* s_h, float* __restrict__ partial) {
+    constexpr int A = HA;
+    const int t = threadIdx.x, kc = t & (HK - 1), half = t >> 7, wave = t >> 6, lane = t & 63;
+    float* red = s_h;  // [2][A + 1][HK]
+    for (int j = 0; j < A; j++) red[(half * (A + 1) + j) * HK + kc] = dW[j];
+    red[(half * (A + 1) + A) * HK + kc] = cs;
+    __syncthreads();
+    float* rec = partial + (size_t)blockIdx.x * head_record<A>();
+    for (int i = t; i < (A + 1) * HK; i += 256) rec[i] = red[i] + red[(A + 1) * HK + i];
+    __syncthreads();
+    for (int i = 0; i < 3; i++) {
+        const float v = quadcol_sum(dbias[i]);
+        if (lane < 4) s_h[wave * 16 + 3 * lane + i] = v;
+    }
+    return rec;
+}
+__device__ __forceinline__ void head_record_bias(float* rec, const float* redf) {  // the four waves' sums
+    const int t = threadIdx.x;
+    if (t < HA) rec[(HA + 1) * HK + t] = redf[t] + redf[16 + t] + redf[32 + t] + redf[48 + t];
+}
+
+// N float64 statistics, each the sum of one value per thread: waves, then the four waves through LDS; statistic-major in the scratch
+template <int N>
+__device__ __forceinline__ void head_wave_stats(const double (&v)[N], float* s_h, float* __restrict__ partial) {
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    double* redd = reinterpret_cast<double*>(s_h + 64);  // [N][4 waves]
+    for (int k = 0; k < N; k++) {
+        const double w = wave_sum_d(v[k]);
+        if (lane == 0) redd[4 * k + wave] = w;
+    }
+    __syncthreads();
+    if (t < N) {
+        double* srec = reinterpret_cast<double*>(partial + head_stat_base<HA>());
+        srec[(size_t)t * gridDim.x + blockIdx.x] = redd[4 * t] + redd[4 * t + 1] + redd[4 * t + 2] + redd[4 * t + 3];
+    }
+}
+
+// The PPO heads' float64 statistics behind head_record_sums(): lanes sharing (lane & 3) within a wave, then the four waves through LDS.  Slot 3 fq + i
+// = dL/dlogstd (acc_ls), slots 12..15 = the loss terms (acc_st), slot 16 (N_STAT = 17) = the sum of `extra` over the threads.
+// Statistic index: [0, A) dL/dlogstd, A unused (the value error is the critic head's), A+1.. = surrogate, bound, entropy, kl, (symmetry)
+template <int N_STAT>
+__device__ __forceinline__ void ppo_store_stats(const double (&acc_ls)[3], const double (&acc_st)[4], float* s_h, float* __restrict__ partial, double extra = 0.0) {
+    static_assert(N_STAT == 16 || N_STAT == 17, "");
+    constexpr int A = HA, SL = N_STAT == 16 ? 16 : 20;  // slots per wave
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    double* redd = reinterpret_cast<double*>(s_h + 64);  // [4 waves][SL]
+    for (int i = 0; i < 3; i++) {
+        const double w = quadcol_sum(acc_ls[i]);
+        if (lane < 4) redd[wave * SL + 3 * lane + i] = w;
+    }
+    for (int i = 0; i < 4; i++) {
+        const double w = quadcol_sum(acc_st[i]);  // only fq == 0 lanes carry values
+        if (lane == 0) redd[wave * SL + 12 + i] = w;
+    }
+    if (N_STAT == 17) {
+        const double w = wave_sum_d(extra);
+        if (lane == 0) redd[wave * SL + 16] = w;
+    }
+    __syncthreads();
+    if (t < N_STAT) {
+        double* srec = reinterpret_cast<double*>(partial + head_stat_base<A>());
+        const double w = redd[t] + redd[SL + t] + redd[2 * SL + t] + redd[3 * SL + t];
+        const int k = t < A ? t : t + 1;
+        srec[(size_t)k * gridDim.x + blockIdx.x] = w;
+    }
+}
+
+// behaviour-cloning loss of one live row on a thread's three actions, on top of what gm holds: L = 1 / (A B) sum_r |mu_r - target_r|^2, gscale = 2 / (A B)
+__device__ __forceinline__ void bc_row(bool live, float gscale, const float (&m)[3], const float* __restrict__ target, float (&gm)[3], double& sse) {
+    for (int i = 0; i < 3; i++) {
+        const float e = m[i] - target[i];
+        if (live) { gm[i] += gscale * e; sse += (double)(e * e); }
+    }
+}
+
+// Mirror-symmetry loss: the batch is 2B rows, rows [B, 2B) the mirror images of rows [0, B).  A tile holds HTS original rows in LDS rows [0, HTS) and
+// their mirror images in LDS rows [HTS, 2 HTS), so that the pair's means meet in LDS (s_mu).  Per pair, with d = mu(M_o x) - M_a mu(x) and
+// c = sym_scale = 2 coef / (B A):  dL/dmu of the mirrored row = c d,  of the original row = -c M_a d  (M_a a symmetric involution:
+// (M_a d)[a] = sign[a] d[src[a]]); acc_sym = sum d^2.  A wave holds 16 rows, all of them original or all mirrored: `mirror` is uniform per wave,
+// so what runs under it may use the DPP moves, which run in whole waves.
+constexpr int HEAD_NSTAT_SYM = HEAD_NSTAT + 1;
+struct ActionMirror { int src[HA]; float sign[HA]; };
+struct SymThread {
+    static constexpr int A = HA;
+    int pr, src[3];
+    bool mirror;
+    float sgn[3];
+    double acc_sym;
+
+    // before the kernel's first barrier / behind it
+    __device__ __forceinline__ void stage(const ActionMirror& am, int* s_src, float* s_sign) {
+        const int t = threadIdx.x;
+        if (t < A) { s_src[t] = am.src[t]; s_sign[t] = am.sign[t]; }
+        pr = (t >> 2) & (HTS - 1); mirror = (t >> 2) >= HTS;
+        acc_sym = 0.0;
+    }
+    __device__ __forceinline__ void load(const int* s_src, const float* s_sign) {
+        const int fq = threadIdx.x & 3;
+        for (int i = 0; i < 3; i++) { src[i] = s_src[3 * fq + i]; sgn[i] = s_sign[3 * fq + i]; }
+    }
+    // the means of row b = row0 + pr of the pair tile into s_mu and, for a live row, into mu_out
+    __device__ __forceinline__ void put_mu(const float (&m)[3], int b, int B, float* s_mu, float* __restrict__ mu_out) const {
+        const int fr = threadIdx.x >> 2, fq = threadIdx.x & 3;
+        for (int i = 0; i < 3; i++) s_mu[fr * A + 3 * fq + i] = m[i];
+        if (mu_out && b < B) for (int i = 0; i < 3; i++) mu_out[(size_t)(mirror ? B + b : b) * A + 3 * fq + i] = m[i];
+    }
+    // gm = the symmetry term of the pair (pr, HTS + pr) for this thread's row and actions
+    __device__ __forceinline__ void pair(bool live, float sym_scale, const float* s_mu, float (&gm)[3]) {
+        const int fq = threadIdx.x & 3;
+        const float* mo = s_mu + pr * A;
+        const float* mm = s_mu + (HTS + pr) * A;
+        for (int i = 0; i < 3; i++) {
+            const int a = 3 * fq + i;
+            gm[i] = 0.f;
+            if (mirror) {
+                const float d = mm[a] - sgn[i] * mo[src[i]];
+                if (live) { gm[i] = sym_scale * d; acc_sym += (double)(d * d); }
+            } else {
+                const float d = mm[src[i]] - sgn[i] * mo[a];  // d[src[a]] (sign[src[a]] = sign[a])
+                if (live) gm[i] = -sym_scale * sgn[i] * d;
+            }
+        }
+    }
+};
+
+// MODE 0: forward only (mu_out), MODE 1: forward + PPO loss + backward.
 template <int MODE>
 __global__ __launch_bounds__(256) void actor_head_kernel(int B, int tiles, const float* __restrict__ h, const float* __restrict__ W,
                                                          const float* __restrict__ bias, const float* __restrict__ logstd,
@@ -92,18 +302,14 @@ __global__ __launch_bounds__(256) void actor_head_kernel(int B, int tiles, const
                                                          float* __restrict__ partial) {
     constexpr int A = HA;
     __shared__ __attribute__((aligned(16))) float s_h[HT * HLD];
-    // rows of W 132 floats apart: the four (t & 3) groups of a wave read rows 3 apart at the same k, which with a 128-float stride were the same
-    // banks (a 4-way conflict on three of the four LDS reads of the forward loop)
     __shared__ __attribute__((aligned(16))) float s_w[A * HLD];
     __shared__ __attribute__((aligned(16))) float s_g[HT * A];  // dL/dmu of the tile's rows
     const int t = threadIdx.x;
-    for (int i = t; i < A * HK; i += 256) s_w[(i >> 7) * HLD + (i & (HK - 1))] = W[i];
     const int fr = t >> 2, fq = t & 3;
     float fb[3];
-    for (int i = 0; i < 3; i++) fb[i] = bias[3 * fq + i];
     const int kc = t & (HK - 1), half = t >> 7;
     float wcol[A], dW[A], cs = 0.f;
-    for (int j = 0; j < A; j++) { wcol[j] = MODE == 1 ? W[j * HK + kc] : 0.f; dW[j] = 0.f; }
+    head_stage<MODE == 1>(W, bias, s_w, fb, wcol, dW);
     // loss constants of this thread's three actions (bg_ppo_math.h states the same formulas for a whole row)
     float ls[3], ols[3], isig2[3], osig2[3], dbias[3] = {0.f, 0.f, 0.f};
     float ent = 0.f, mean = 0.f, inv_std = 0.f, invB = 0.f, bscale = 0.f;
@@ -122,25 +328,14 @@ __global__ __launch_bounds__(256) void actor_head_kernel(int B, int tiles, const
         const int row0 = tile * HT;
         load_tile(h, row0, B, s_h);
         __syncthreads();
-        {   // mu = h W^T + b
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-            const float4* hr = reinterpret_cast<const float4*>(s_h + fr * HLD);
-            const float4* w0 = reinterpret_cast<const float4*>(s_w + (3 * fq) * HLD);
-            const float4* w1 = reinterpret_cast<const float4*>(s_w + (3 * fq + 1) * HLD);
-            const float4* w2 = reinterpret_cast<const float4*>(s_w + (3 * fq + 2) * HLD);
-#pragma unroll 2
-            for (int k4 = 0; k4 < HK / 4; k4++) {
-                const float4 x = hr[k4], u = w0[k4], v = w1[k4], w = w2[k4];
-                a0 = fmaf(x.x, u.x, a0); a0 = fmaf(x.y, u.y, a0); a0 = fmaf(x.z, u.z, a0); a0 = fmaf(x.w, u.w, a0);
-                a1 = fmaf(x.x, v.x, a1); a1 = fmaf(x.y, v.y, a1); a1 = fmaf(x.z, v.z, a1); a1 = fmaf(x.w, v.w, a1);
-                a2 = fmaf(x.x, w.x, a2); a2 = fmaf(x.y, w.y, a2); a2 = fmaf(x.z, w.z, a2); a2 = fmaf(x.w, w.w, a2);
-            }
-            const float m[3] = {a0 + fb[0], a1 + fb[1], a2 + fb[2]};
+        {
+            float m[3];
+            head_mu(s_h, s_w, fr, fq, fb, m);
             const int b = row0 + fr;
             const bool live = b < B;
             const size_t o = (size_t)(live ? b : B - 1) * A + 3 * fq;
             if (mu_out && live) for (int i = 0; i < 3; i++) mu_out[o + i] = m[i];
-            if (MODE == 1) {
+            if (MODE == 1) {  // PPO actor loss of the row (the same lines stand in actor_head_sym_kernel: see the shared pieces' header)
                 float d[3], hl[3], lp = 0.f, kl = 0.f, bound = 0.f;
                 for (int i = 0; i < 3; i++) {
                     d[i] = actions[o + i] - m[i];
@@ -175,17 +370,7 @@ __global__ __launch_bounds__(256) void actor_head_kernel(int B, int tiles, const
             // g_hidden = (dL/dmu W) * elu'(h), dW += dL/dmu^T h, hidden bias gradient = column sums of g_hidden
             for (int rr = 0; rr < HT / 2; rr++) {
                 const int r = half * (HT / 2) + rr;
-                const float hv = s_h[r * HLD + kc];
-                const float4* gp = reinterpret_cast<const float4*>(s_g + r * A);
-                const float4 g0 = gp[0], g1 = gp[1], g2 = gp[2];
-                const float g[A] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w, g2.x, g2.y, g2.z, g2.w};
-                float sa = 0.f, sb = 0.f;
-#pragma unroll
-                for (int j = 0; j < A; j += 2) {
-                    sa = fmaf(g[j], wcol[j], sa); sb = fmaf(g[j + 1], wcol[j + 1], sb);
-                    dW[j] = fmaf(g[j], hv, dW[j]); dW[j + 1] = fmaf(g[j + 1], hv, dW[j + 1]);
-                }
-                const float gz = (sa + sb) * elu_grad_from_output(hv);
+                const float gz = head_back_row(s_h, s_g, r, kc, wcol, dW);
                 cs += gz;
                 if (row0 + r < B) g_hidden[(size_t)(row0 + r) * HK + kc] = gz;
             }
@@ -193,36 +378,9 @@ __global__ __launch_bounds__(256) void actor_head_kernel(int B, int tiles, const
         }
     }
     if (MODE == 0) return;
-    // ---- this workgroup's partial sums: the two row halves of the column-mapped sums meet in LDS
-    float* red = s_h;  // [2][A + 1][HK]
-    for (int j = 0; j < A; j++) red[(half * (A + 1) + j) * HK + kc] = dW[j];
-    red[(half * (A + 1) + A) * HK + kc] = cs;
-    __syncthreads();
-    float* rec = partial + (size_t)blockIdx.x * head_record<A>();
-    for (int i = t; i < (A + 1) * HK; i += 256) rec[i] = red[i] + red[(A + 1) * HK + i];
-    // per-action sums: lanes sharing (lane & 3) within a wave, then the four waves through LDS.  slot = 3 fq + i; slots 12..15 = loss terms.
-    const int wave = t >> 6, lane = t & 63;
-    __syncthreads();
-    float* redf = s_h;          // [4 waves][16]
-    double* redd = reinterpret_cast<double*>(s_h + 64);  // [4 waves][16]
-    for (int i = 0; i < 3; i++) {
-        const float v = quadcol_sum(dbias[i]);
-        const double w = quadcol_sum(acc_ls[i]);
-        if (lane < 4) { redf[wave * 16 + 3 * lane + i] = v; redd[wave * 16 + 3 * lane + i] = w; }
-    }
-    for (int i = 0; i < 4; i++) {
-        const double w = quadcol_sum(acc_st[i]);  // only fq == 0 lanes carry values
-        if (lane == 0) redd[wave * 16 + 12 + i] = w;
-    }
-    __syncthreads();
-    if (t < 16) {
-        double* srec = reinterpret_cast<double*>(partial + head_stat_base<A>());
-        const double w = redd[t] + redd[16 + t] + redd[32 + t] + redd[48 + t];
-        // statistic index: [0, A) dL/dlogstd, A unused (the value error is the critic head's), A+1.. = surrogate, bound, entropy, kl
-        const int k = t < A ? t : t + 1;
-        srec[(size_t)k * gridDim.x + blockIdx.x] = w;
-        if (t < A) rec[(A + 1) * HK + t] = redf[t] + redf[16 + t] + redf[32 + t] + redf[48 + t];
-    }
+    float* rec = head_record_sums(dW, cs, dbias, s_h, partial);
+    ppo_store_stats<16>(acc_ls, acc_st, s_h, partial);
+    head_record_bias(rec, s_h);
 }
 
 __global__ __launch_bounds__(256) void critic_head_backward_kernel(int B, int tiles, const float* __restrict__ h, const float* __restrict__ w,
@@ -256,7 +414,7 @@ __global__ __launch_bounds__(256) void critic_head_backward_kernel(int B, int ti
             const int r = half * (HT / 2) + rr;
             const float hv = s_h[r * HLD + kc], g = s_g[r];
             dW = fmaf(g, hv, dW);
-            const float gz = g * wk * elu_grad_from_output(hv);
+            const float gz = elu_back(g * wk, hv);
             cs += gz;
             if (row0 + r < B) g_hidden[(size_t)(row0 + r) * HK + kc] = gz;
         }
@@ -436,8 +594,8 @@ __global__ __launch_bounds__(256) void critic_values_gae_kernel(int T, int N, co
     }
 }
 
-// Behaviour-cloning head (bg_distill_head): L = 1 / (A B) sum_r |mu_r - target_r|^2, dL/dmu = 2 (mu - target) / (A B).  actor_head_kernel's thread
-// mappings, tile walk and record layout (the forward sums are its sums: the same mu bits), one float64 statistic per workgroup: the squared errors.
+// Behaviour-cloning head (bg_distill_head): actor_head_kernel with the behaviour-cloning row for the PPO loss, dL/dmu = 2 (mu - target) / (A B); one
+// float64 statistic per workgroup: the squared errors.
 __global__ __launch_bounds__(256) void distill_head_kernel(int B, int tiles, const float* __restrict__ h, const float* __restrict__ W,
                                                            const float* __restrict__ bias, const float* __restrict__ target, float* __restrict__ mu_out,
                                                            float* __restrict__ g_hidden, float* __restrict__ partial) {
@@ -445,99 +603,43 @@ __global__ __launch_bounds__(256) void distill_head_kernel(int B, int tiles, con
     __shared__ __attribute__((aligned(16))) float s_h[HT * HLD];
     __shared__ __attribute__((aligned(16))) float s_w[A * HLD];
     __shared__ __attribute__((aligned(16))) float s_g[HT * A];
-    const int t = threadIdx.x;
-    for (int i = t; i < A * HK; i += 256) s_w[(i >> 7) * HLD + (i & (HK - 1))] = W[i];
-    const int fr = t >> 2, fq = t & 3;
-    float fb[3];
-    for (int i = 0; i < 3; i++) fb[i] = bias[3 * fq + i];
+    const int t = threadIdx.x, fr = t >> 2, fq = t & 3;
     const int kc = t & (HK - 1), half = t >> 7;
-    float wcol[A], dW[A], cs = 0.f, dbias[3] = {0.f, 0.f, 0.f};
-    for (int j = 0; j < A; j++) { wcol[j] = W[j * HK + kc]; dW[j] = 0.f; }
+    float fb[3], wcol[A], dW[A], cs = 0.f, dbias[3] = {0.f, 0.f, 0.f};
+    head_stage<true>(W, bias, s_w, fb, wcol, dW);
     const float gscale = 2.0f / ((float)A * (float)B);
-    double sse = 0.0;
+    double sse[1] = {0.0};
     __syncthreads();
     for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int row0 = tile * HT;
         load_tile(h, row0, B, s_h);
         __syncthreads();
-        {   // mu = h W^T + b (bg_actor_head's arithmetic)
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-            const float4* hr = reinterpret_cast<const float4*>(s_h + fr * HLD);
-            const float4* w0 = reinterpret_cast<const float4*>(s_w + (3 * fq) * HLD);
-            const float4* w1 = reinterpret_cast<const float4*>(s_w + (3 * fq + 1) * HLD);
-            const float4* w2 = reinterpret_cast<const float4*>(s_w + (3 * fq + 2) * HLD);
-#pragma unroll 2
-            for (int k4 = 0; k4 < HK / 4; k4++) {
-                const float4 x = hr[k4], u = w0[k4], v = w1[k4], w = w2[k4];
-                a0 = fmaf(x.x, u.x, a0); a0 = fmaf(x.y, u.y, a0); a0 = fmaf(x.z, u.z, a0); a0 = fmaf(x.w, u.w, a0);
-                a1 = fmaf(x.x, v.x, a1); a1 = fmaf(x.y, v.y, a1); a1 = fmaf(x.z, v.z, a1); a1 = fmaf(x.w, v.w, a1);
-                a2 = fmaf(x.x, w.x, a2); a2 = fmaf(x.y, w.y, a2); a2 = fmaf(x.z, w.z, a2); a2 = fmaf(x.w, w.w, a2);
-            }
-            const float m[3] = {a0 + fb[0], a1 + fb[1], a2 + fb[2]};
+        {
+            float m[3];
+            head_mu(s_h, s_w, fr, fq, fb, m);
             const int b = row0 + fr;
             const bool live = b < B;
             const size_t o = (size_t)(live ? b : B - 1) * A + 3 * fq;
             if (mu_out && live) for (int i = 0; i < 3; i++) mu_out[o + i] = m[i];
+            // (bc_row's lines with a select for its branch: through bc_row the target's load moved under the branch, and the launch was 1.2 % slower)
             for (int i = 0; i < 3; i++) {
                 const float e = m[i] - target[o + i];
-                const float gm = live ? gscale * e : 0.f;
+                const float gm = live ? e * gscale : 0.f;
                 s_g[fr * A + 3 * fq + i] = gm;
                 dbias[i] += gm;
-                if (live) sse += (double)(e * e);
+                if (live) sse[0] += (double)(e * e);
             }
         }
         __syncthreads();
-        // g_hidden = (dL/dmu W) * elu'(h), dW += dL/dmu^T h, hidden bias gradient = column sums of g_hidden (as actor_head_kernel)
-        for (int rr = 0; rr < HT / 2; rr++) {
-            const int r = half * (HT / 2) + rr;
-            const float hv = s_h[r * HLD + kc];
-            const float4* gp = reinterpret_cast<const float4*>(s_g + r * A);
-            const float4 g0 = gp[0], g1 = gp[1], g2 = gp[2];
-            const float g[A] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w, g2.x, g2.y, g2.z, g2.w};
-            float sa = 0.f, sb = 0.f;
-#pragma unroll
-            for (int j = 0; j < A; j += 2) {
-                sa = fmaf(g[j], wcol[j], sa); sb = fmaf(g[j + 1], wcol[j + 1], sb);
-                dW[j] = fmaf(g[j], hv, dW[j]); dW[j + 1] = fmaf(g[j + 1], hv, dW[j + 1]);
-            }
-            const float gz = (sa + sb) * elu_grad_from_output(hv);
-            cs += gz;
-            if (row0 + r < B) g_hidden[(size_t)(row0 + r) * HK + kc] = gz;
-        }
+        head_back_rows<false>(s_h, s_g, row0, B, kc, half, wcol, dW, cs, g_hidden);
         __syncthreads();
     }
-    // ---- this workgroup's partial sums (bg_actor_head's record layout; ONE float64 statistic)
-    float* red = s_h;  // [2][A + 1][HK]
-    for (int j = 0; j < A; j++) red[(half * (A + 1) + j) * HK + kc] = dW[j];
-    red[(half * (A + 1) + A) * HK + kc] = cs;
-    __syncthreads();
-    float* rec = partial + (size_t)blockIdx.x * head_record<A>();
-    for (int i = t; i < (A + 1) * HK; i += 256) rec[i] = red[i] + red[(A + 1) * HK + i];
-    const int wave = t >> 6, lane = t & 63;
-    __syncthreads();
-    float* redf = s_h;                                    // [4 waves][16]
-    double* redd = reinterpret_cast<double*>(s_h + 64);  // [4 waves]
-    for (int i = 0; i < 3; i++) {
-        const float v = quadcol_sum(dbias[i]);
-        if (lane < 4) redf[wave * 16 + 3 * lane + i] = v;
-    }
-    {
-        const double w = wave_sum_d(sse);
-        if (lane == 0) redd[wave] = w;
-    }
-    __syncthreads();
-    if (t < A) rec[(A + 1) * HK + t] = redf[t] + redf[16 + t] + redf[32 + t] + redf[48 + t];
-    if (t == 0) reinterpret_cast<double*>(partial + head_stat_base<A>())[blockIdx.x] = redd[0] + redd[1] + redd[2] + redd[3];
+    float* rec = head_record_sums(dW, cs, dbias, s_h, partial);
+    head_wave_stats(sse, s_h, partial);
+    head_record_bias(rec, s_h);
 }
 
-// ---- mirror-symmetry loss (bg_actor_head_sym): the actor's batch is 2B rows, rows [B, 2B) the mirror images of rows [0, B).  A tile holds HTS
-// original rows in LDS rows [0, HTS) and their mirror images in LDS rows [HTS, 2 HTS), so that the pair's means meet in LDS.  Per pair, with
-// d = mu(M_o x) - M_a mu(x) and c = sym_scale = 2 coef / (B A):  dL/dmu of the mirrored row += c d,  of the original row += -c M_a d  (M_a a
-// symmetric involution: (M_a d)[a] = sign[a] d[src[a]]), on top of the PPO, bound and entropy terms of the original row; statistic A + 5 = sum d^2.
-constexpr int HTS = HT / 2;
-constexpr int HEAD_NSTAT_SYM = HEAD_NSTAT + 1;
-struct ActionMirror { int src[HA]; float sign[HA]; };
-
+// bg_actor_head_sym: the PPO, bound and entropy terms of the original rows plus the symmetry term of both rows of a pair; statistic A + 5 = sum d^2.
 __global__ __launch_bounds__(256) void actor_head_sym_kernel(int B, int tiles, const float* __restrict__ h, const float* __restrict__ W,
                                                              const float* __restrict__ bias, const float* __restrict__ logstd,
                                                              const float* __restrict__ actions, const float* __restrict__ old_mu,
@@ -552,74 +654,33 @@ __global__ __launch_bounds__(256) void actor_head_sym_kernel(int B, int tiles, c
     __shared__ float s_mu[HT * A];
     __shared__ int s_src[A];
     __shared__ float s_sign[A];
-    const int t = threadIdx.x;
-    for (int i = t; i < A * HK; i += 256) s_w[(i >> 7) * HLD + (i & (HK - 1))] = W[i];
-    if (t < A) { s_src[t] = am.src[t]; s_sign[t] = am.sign[t]; }
-    const int fr = t >> 2, fq = t & 3, pr = fr & (HTS - 1);
-    const bool mirror = fr >= HTS;
-    float fb[3];
-    for (int i = 0; i < 3; i++) fb[i] = bias[3 * fq + i];
-    const int kc = t & (HK - 1), half = t >> 7;  // backward: half 0 = the original rows, half 1 = their mirror images
-    float wcol[A], dW[A], cs = 0.f;
-    for (int j = 0; j < A; j++) { wcol[j] = W[j * HK + kc]; dW[j] = 0.f; }
+    const int t = threadIdx.x, fr = t >> 2, fq = t & 3;
+    const int kc = t & (HK - 1), half = t >> 7;
+    float fb[3], wcol[A], dW[A], cs = 0.f;
+    head_stage<true>(W, bias, s_w, fb, wcol, dW);
+    SymThread sym;
+    sym.stage(am, s_src, s_sign);
+    // loss constants of this thread's three actions (actor_head_kernel's lines)
     float ls[3], ols[3], isig2[3], osig2[3], dbias[3] = {0.f, 0.f, 0.f};
-    double acc_ls[3] = {0.0, 0.0, 0.0}, acc_st[4] = {0.0, 0.0, 0.0, 0.0}, acc_sym = 0.0;
+    double acc_ls[3] = {0.0, 0.0, 0.0}, acc_st[4] = {0.0, 0.0, 0.0, 0.0};
     bg::ActorLossConsts<A> c;
     bg::actor_loss_consts<A>(c, B, logstd, old_logstd, adv_stats, e_clip, bound_coef);
     for (int i = 0; i < 3; i++) { ls[i] = logstd[3 * fq + i]; ols[i] = old_logstd[3 * fq + i]; }
     for (int i = 0; i < 3; i++) { const float sg = expf(ls[i]), os = expf(ols[i]); isig2[i] = 1.0f / (sg * sg); osig2[i] = os * os; }
     const float ent = c.ent, mean = c.mean, inv_std = c.inv_std, invB = c.invB, bscale = c.bscale;
     __syncthreads();
-    int src[3];
-    float sgn[3];
-    for (int i = 0; i < 3; i++) { src[i] = s_src[3 * fq + i]; sgn[i] = s_sign[3 * fq + i]; }
+    sym.load(s_src, s_sign);
     for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int row0 = tile * HTS;
-#pragma unroll
-        for (int i = 0; i < HTV; i++) {
-            const int idx = t + 256 * i, r = idx >> 5, c4 = idx & 31, o = row0 + (r & (HTS - 1));
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (o < B) v = *reinterpret_cast<const float4*>(h + (size_t)(r < HTS ? o : B + o) * HK + c4 * 4);
-            *reinterpret_cast<float4*>(s_h + r * HLD + c4 * 4) = v;
-        }
+        const int row0 = tile * HTS, b = row0 + sym.pr;
+        load_pair_tile(h, row0, B, s_h);
         __syncthreads();
-        const int b = row0 + pr;
+        float m[3], gm[3];
+        head_mu(s_h, s_w, fr, fq, fb, m);
+        sym.put_mu(m, b, B, s_mu, mu_out);
+        __syncthreads();
         const bool live = b < B;
-        float m[3];
-        {   // mu = h W^T + b (bg_actor_head's arithmetic)
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-            const float4* hr = reinterpret_cast<const float4*>(s_h + fr * HLD);
-            const float4* w0 = reinterpret_cast<const float4*>(s_w + (3 * fq) * HLD);
-            const float4* w1 = reinterpret_cast<const float4*>(s_w + (3 * fq + 1) * HLD);
-            const float4* w2 = reinterpret_cast<const float4*>(s_w + (3 * fq + 2) * HLD);
-#pragma unroll 2
-            for (int k4 = 0; k4 < HK / 4; k4++) {
-                const float4 x = hr[k4], u = w0[k4], v = w1[k4], w = w2[k4];
-                a0 = fmaf(x.x, u.x, a0); a0 = fmaf(x.y, u.y, a0); a0 = fmaf(x.z, u.z, a0); a0 = fmaf(x.w, u.w, a0);
-                a1 = fmaf(x.x, v.x, a1); a1 = fmaf(x.y, v.y, a1); a1 = fmaf(x.z, v.z, a1); a1 = fmaf(x.w, v.w, a1);
-                a2 = fmaf(x.x, w.x, a2); a2 = fmaf(x.y, w.y, a2); a2 = fmaf(x.z, w.z, a2); a2 = fmaf(x.w, w.w, a2);
-            }
-            m[0] = a0 + fb[0]; m[1] = a1 + fb[1]; m[2] = a2 + fb[2];
-        }
-        for (int i = 0; i < 3; i++) s_mu[fr * A + 3 * fq + i] = m[i];
-        if (mu_out && live) for (int i = 0; i < 3; i++) mu_out[(size_t)(mirror ? B + b : b) * A + 3 * fq + i] = m[i];
-        __syncthreads();
-        float gm[3] = {0.f, 0.f, 0.f};
-        {   // symmetry term of the pair (pr, HTS + pr)
-            const float* mo = s_mu + pr * A;
-            const float* mm = s_mu + (HTS + pr) * A;
-            for (int i = 0; i < 3; i++) {
-                const int a = 3 * fq + i;
-                if (mirror) {
-                    const float d = mm[a] - sgn[i] * mo[src[i]];
-                    if (live) { gm[i] = sym_scale * d; acc_sym += (double)(d * d); }
-                } else {
-                    const float d = mm[src[i]] - sgn[i] * mo[a];  // d[src[a]] (sign[src[a]] = sign[a])
-                    if (live) gm[i] = -sym_scale * sgn[i] * d;
-                }
-            }
-        }
-        if (!mirror) {  // PPO actor loss of the original row (bg_actor_head MODE 1)
+        sym.pair(live, sym_scale, s_mu, gm);
+        if (!sym.mirror) {  // PPO actor loss of the original row (actor_head_kernel's lines)
             const size_t o = (size_t)(live ? b : B - 1) * A + 3 * fq;
             float d[3], hl[3], lp = 0.f, kl = 0.f, bound = 0.f;
             for (int i = 0; i < 3; i++) {
@@ -631,7 +692,6 @@ __global__ __launch_bounds__(256) void actor_head_sym_kernel(int B, int tiles, c
                 bound += hi * hi + lo * lo;
                 hl[i] = hi + lo;
             }
-            // (a wave holds 16 rows, all of them original or all mirrored: `mirror` is uniform per wave, and the DPP moves run in whole waves)
             lp = quad_sum(lp); kl = quad_sum(kl); bound = quad_sum(bound);
             const float An = (adv[live ? b : B - 1] - mean) * inv_std;
             const float ratio = expf(lp - old_logp[live ? b : B - 1]);
@@ -647,67 +707,19 @@ __global__ __launch_bounds__(256) void actor_head_sym_kernel(int B, int tiles, c
                 acc_st[0] += (double)fmaxf(s1, s2); acc_st[1] += (double)bound; acc_st[2] += (double)ent; acc_st[3] += (double)kl;
             }
         }
-        for (int i = 0; i < 3; i++) { s_g[fr * A + 3 * fq + i] = gm[i]; dbias[i] += gm[i]; }
+        head_put_grad(s_g, fr, fq, gm, dbias);
         __syncthreads();
-        // g_hidden = (dL/dmu W) * elu'(h), dW += dL/dmu^T h, hidden bias gradient = column sums of g_hidden: over all 2B rows
-        for (int rr = 0; rr < HTS; rr++) {
-            const int r = half * HTS + rr;
-            const float hv = s_h[r * HLD + kc];
-            const float4* gp = reinterpret_cast<const float4*>(s_g + r * A);
-            const float4 g0 = gp[0], g1 = gp[1], g2 = gp[2];
-            const float g[A] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w, g2.x, g2.y, g2.z, g2.w};
-            float sa = 0.f, sb = 0.f;
-#pragma unroll
-            for (int j = 0; j < A; j += 2) {
-                sa = fmaf(g[j], wcol[j], sa); sb = fmaf(g[j + 1], wcol[j + 1], sb);
-                dW[j] = fmaf(g[j], hv, dW[j]); dW[j + 1] = fmaf(g[j + 1], hv, dW[j + 1]);
-            }
-            const float gz = (sa + sb) * elu_grad_from_output(hv);
-            cs += gz;
-            if (row0 + rr < B) g_hidden[(size_t)(half ? B + row0 + rr : row0 + rr) * HK + kc] = gz;
-        }
+        head_back_rows<true>(s_h, s_g, row0, B, kc, half, wcol, dW, cs, g_hidden);
         __syncthreads();
     }
-    // ---- this workgroup's partial sums (bg_actor_head's record layout; one float64 statistic more)
-    float* red = s_h;  // [2][A + 1][HK]
-    for (int j = 0; j < A; j++) red[(half * (A + 1) + j) * HK + kc] = dW[j];
-    red[(half * (A + 1) + A) * HK + kc] = cs;
-    __syncthreads();
-    float* rec = partial + (size_t)blockIdx.x * head_record<A>();
-    for (int i = t; i < (A + 1) * HK; i += 256) rec[i] = red[i] + red[(A + 1) * HK + i];
-    const int wave = t >> 6, lane = t & 63;
-    constexpr int SL = 20;  // slots per wave: 0..11 per action, 12..15 loss terms, 16 symmetry
-    __syncthreads();
-    float* redf = s_h;                                    // [4 waves][16]
-    double* redd = reinterpret_cast<double*>(s_h + 64);  // [4 waves][SL]
-    for (int i = 0; i < 3; i++) {
-        const float v = quadcol_sum(dbias[i]);
-        const double w = quadcol_sum(acc_ls[i]);
-        if (lane < 4) { redf[wave * 16 + 3 * lane + i] = v; redd[wave * SL + 3 * lane + i] = w; }
-    }
-    for (int i = 0; i < 4; i++) {
-        const double w = quadcol_sum(acc_st[i]);
-        if (lane == 0) redd[wave * SL + 12 + i] = w;
-    }
-    {
-        const double w = wave_sum_d(acc_sym);
-        if (lane == 0) redd[wave * SL + 16] = w;
-    }
-    __syncthreads();
-    if (t < 17) {
-        double* srec = reinterpret_cast<double*>(partial + head_stat_base<A>());
-        const double w = redd[t] + redd[SL + t] + redd[2 * SL + t] + redd[3 * SL + t];
-        // statistic index: [0, A) dL/dlogstd, A unused (the critic head's), A+1.. = surrogate, bound, entropy, kl, symmetry
-        const int k = t < A ? t : t + 1;
-        srec[(size_t)k * gridDim.x + blockIdx.x] = w;
-        if (t < A) rec[(A + 1) * HK + t] = redf[t] + redf[16 + t] + redf[32 + t] + redf[48 + t];
-    }
+    float* rec = head_record_sums(dW, cs, dbias, s_h, partial);
+    ppo_store_stats<17>(acc_ls, acc_st, s_h, partial, sym.acc_sym);
+    head_record_bias(rec, s_h);
 }
 
-// ---- mirror-symmetry loss on the distillation's student (bg_distill_head_sym): actor_head_sym_kernel's tile (HTS original rows and their HTS mirror
-// images meet in LDS) with distill_head_kernel's loss on the original rows.  L = 1 / (A B) sum_r |mu_r - target_r|^2 + coef / (A B) sum_r |d_r|^2,
-// d = mu(M_o x) - M_a mu(x); with s = sym_scale = 2 coef / (A B):  dL/dmu of the mirrored row = s d,  of the original row = 2 (mu - target) / (A B) -
-// s M_a d.  Two float64 statistics per workgroup: the squared errors and sum d^2.  A kernel of its own: the two it resembles keep their bits.
+// bg_distill_head_sym: bc_row on the original rows plus the symmetry term of both rows of a pair.  L = 1 / (A B) sum_r |mu_r - target_r|^2 +
+// coef / (A B) sum_r |d_r|^2; two float64 statistics per workgroup: the squared errors and sum d^2.  The NEXT tile's 8 float4 per thread are in flight
+// under this tile's compute (critic_head_backward_kernel's scheme: LDS, not registers, bounds this kernel's three workgroups per CU).
 __global__ __launch_bounds__(256) void distill_head_sym_kernel(int B, int tiles, const float* __restrict__ h, const float* __restrict__ W,
                                                                const float* __restrict__ bias, const float* __restrict__ target, float sym_scale,
                                                                ActionMirror am, float* __restrict__ mu_out, float* __restrict__ g_hidden,
@@ -719,128 +731,39 @@ __global__ __launch_bounds__(256) void distill_head_sym_kernel(int B, int tiles,
     __shared__ float s_mu[HT * A];
     __shared__ int s_src[A];
     __shared__ float s_sign[A];
-    const int t = threadIdx.x;
-    for (int i = t; i < A * HK; i += 256) s_w[(i >> 7) * HLD + (i & (HK - 1))] = W[i];
-    if (t < A) { s_src[t] = am.src[t]; s_sign[t] = am.sign[t]; }
-    const int fr = t >> 2, fq = t & 3, pr = fr & (HTS - 1);
-    const bool mirror = fr >= HTS;
-    float fb[3];
-    for (int i = 0; i < 3; i++) fb[i] = bias[3 * fq + i];
-    const int kc = t & (HK - 1), half = t >> 7;  // backward: half 0 = the original rows, half 1 = their mirror images
-    float wcol[A], dW[A], cs = 0.f, dbias[3] = {0.f, 0.f, 0.f};
-    for (int j = 0; j < A; j++) { wcol[j] = W[j * HK + kc]; dW[j] = 0.f; }
+    const int t = threadIdx.x, fr = t >> 2, fq = t & 3;
+    const int kc = t & (HK - 1), half = t >> 7;
+    float fb[3], wcol[A], dW[A], cs = 0.f, dbias[3] = {0.f, 0.f, 0.f};
+    head_stage<true>(W, bias, s_w, fb, wcol, dW);
+    SymThread sym;
+    sym.stage(am, s_src, s_sign);
     const float gscale = 2.0f / ((float)A * (float)B);
-    double sse = 0.0, acc_sym = 0.0;
+    double sse = 0.0;
     __syncthreads();
-    int src[3];
-    float sgn[3];
-    for (int i = 0; i < 3; i++) { src[i] = s_src[3 * fq + i]; sgn[i] = s_sign[3 * fq + i]; }
-    // the pair tile: LDS rows [0, HTS) from rows row0 .., LDS rows [HTS, 2 HTS) from rows B + row0 ..; the NEXT tile's 8 float4 per thread are in flight
-    // under this tile's compute (critic_head_backward_kernel's scheme: LDS, not registers, bounds this kernel's three workgroups per CU)
-    auto pair_fetch = [&](int row0, float4 (&v)[HTV]) {
-#pragma unroll
-        for (int i = 0; i < HTV; i++) {
-            const int idx = t + 256 * i, r = idx >> 5, c4 = idx & 31, o = row0 + (r & (HTS - 1));
-            v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (o < B) v[i] = *reinterpret_cast<const float4*>(h + (size_t)(r < HTS ? o : B + o) * HK + c4 * 4);
-        }
-    };
+    sym.load(s_src, s_sign);
     float4 nxt[HTV];
-    pair_fetch(blockIdx.x * HTS, nxt);
+    pair_fetch(h, blockIdx.x * HTS, B, nxt);
     for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int row0 = tile * HTS;
+        const int row0 = tile * HTS, b = row0 + sym.pr;
         tile_put(nxt, s_h);
-        if (tile + (int)gridDim.x < tiles) pair_fetch((tile + gridDim.x) * HTS, nxt);
+        if (tile + (int)gridDim.x < tiles) pair_fetch(h, (tile + gridDim.x) * HTS, B, nxt);
         __syncthreads();
-        const int b = row0 + pr;
         const bool live = b < B;
-        float m[3];
-        {   // mu = h W^T + b (bg_actor_head's arithmetic)
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-            const float4* hr = reinterpret_cast<const float4*>(s_h + fr * HLD);
-            const float4* w0 = reinterpret_cast<const float4*>(s_w + (3 * fq) * HLD);
-            const float4* w1 = reinterpret_cast<const float4*>(s_w + (3 * fq + 1) * HLD);
-            const float4* w2 = reinterpret_cast<const float4*>(s_w + (3 * fq + 2) * HLD);
-#pragma unroll 2
-            for (int k4 = 0; k4 < HK / 4; k4++) {
-                const float4 x = hr[k4], u = w0[k4], v = w1[k4], w = w2[k4];
-                a0 = fmaf(x.x, u.x, a0); a0 = fmaf(x.y, u.y, a0); a0 = fmaf(x.z, u.z, a0); a0 = fmaf(x.w, u.w, a0);
-                a1 = fmaf(x.x, v.x, a1); a1 = fmaf(x.y, v.y, a1); a1 = fmaf(x.z, v.z, a1); a1 = fmaf(x.w, v.w, a1);
-                a2 = fmaf(x.x, w.x, a2); a2 = fmaf(x.y, w.y, a2); a2 = fmaf(x.z, w.z, a2); a2 = fmaf(x.w, w.w, a2);
-            }
-            m[0] = a0 + fb[0]; m[1] = a1 + fb[1]; m[2] = a2 + fb[2];
-        }
-        for (int i = 0; i < 3; i++) s_mu[fr * A + 3 * fq + i] = m[i];
-        if (mu_out && live) for (int i = 0; i < 3; i++) mu_out[(size_t)(mirror ? B + b : b) * A + 3 * fq + i] = m[i];
+        float m[3], gm[3];
+        head_mu(s_h, s_w, fr, fq, fb, m);
+        sym.put_mu(m, b, B, s_mu, mu_out);
         __syncthreads();
-        float gm[3] = {0.f, 0.f, 0.f};
-        {   // symmetry term of the pair (pr, HTS + pr)
-            const float* mo = s_mu + pr * A;
-            const float* mm = s_mu + (HTS + pr) * A;
-            for (int i = 0; i < 3; i++) {
-                const int a = 3 * fq + i;
-                if (mirror) {
-                    const float d = mm[a] - sgn[i] * mo[src[i]];
-                    if (live) { gm[i] = sym_scale * d; acc_sym += (double)(d * d); }
-                } else {
-                    const float d = mm[src[i]] - sgn[i] * mo[a];  // d[src[a]] (sign[src[a]] = sign[a])
-                    if (live) gm[i] = -sym_scale * sgn[i] * d;
-                }
-            }
-        }
-        if (!mirror) {  // behaviour-cloning loss of the original row (bg_distill_head)
-            const size_t o = (size_t)(live ? b : B - 1) * A + 3 * fq;
-            for (int i = 0; i < 3; i++) {
-                const float e = m[i] - target[o + i];
-                if (live) { gm[i] += gscale * e; sse += (double)(e * e); }
-            }
-        }
-        for (int i = 0; i < 3; i++) { s_g[fr * A + 3 * fq + i] = gm[i]; dbias[i] += gm[i]; }
+        sym.pair(live, sym_scale, s_mu, gm);
+        if (!sym.mirror) bc_row(live, gscale, m, target + (size_t)(live ? b : B - 1) * A + 3 * fq, gm, sse);
+        head_put_grad(s_g, fr, fq, gm, dbias);
         __syncthreads();
-        // g_hidden = (dL/dmu W) * elu'(h), dW += dL/dmu^T h, hidden bias gradient = column sums of g_hidden: over all 2B rows
-        for (int rr = 0; rr < HTS; rr++) {
-            const int r = half * HTS + rr;
-            const float hv = s_h[r * HLD + kc];
-            const float4* gp = reinterpret_cast<const float4*>(s_g + r * A);
-            const float4 g0 = gp[0], g1 = gp[1], g2 = gp[2];
-            const float g[A] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w, g2.x, g2.y, g2.z, g2.w};
-            float sa = 0.f, sb = 0.f;
-#pragma unroll
-            for (int j = 0; j < A; j += 2) {
-                sa = fmaf(g[j], wcol[j], sa); sb = fmaf(g[j + 1], wcol[j + 1], sb);
-                dW[j] = fmaf(g[j], hv, dW[j]); dW[j + 1] = fmaf(g[j + 1], hv, dW[j + 1]);
-            }
-            const float gz = (sa + sb) * elu_grad_from_output(hv);
-            cs += gz;
-            if (row0 + rr < B) g_hidden[(size_t)(half ? B + row0 + rr : row0 + rr) * HK + kc] = gz;
-        }
+        head_back_rows<true>(s_h, s_g, row0, B, kc, half, wcol, dW, cs, g_hidden);
         __syncthreads();
     }
-    // ---- this workgroup's partial sums (bg_actor_head's record layout; TWO float64 statistics, statistic-major)
-    float* red = s_h;  // [2][A + 1][HK]
-    for (int j = 0; j < A; j++) red[(half * (A + 1) + j) * HK + kc] = dW[j];
-    red[(half * (A + 1) + A) * HK + kc] = cs;
-    __syncthreads();
-    float* rec = partial + (size_t)blockIdx.x * head_record<A>();
-    for (int i = t; i < (A + 1) * HK; i += 256) rec[i] = red[i] + red[(A + 1) * HK + i];
-    const int wave = t >> 6, lane = t & 63;
-    __syncthreads();
-    float* redf = s_h;                                    // [4 waves][16]
-    double* redd = reinterpret_cast<double*>(s_h + 64);  // [2][4 waves]
-    for (int i = 0; i < 3; i++) {
-        const float v = quadcol_sum(dbias[i]);
-        if (lane < 4) redf[wave * 16 + 3 * lane + i] = v;
-    }
-    {
-        const double w0 = wave_sum_d(sse), w1 = wave_sum_d(acc_sym);
-        if (lane == 0) { redd[wave] = w0; redd[4 + wave] = w1; }
-    }
-    __syncthreads();
-    if (t < A) rec[(A + 1) * HK + t] = redf[t] + redf[16 + t] + redf[32 + t] + redf[48 + t];
-    if (t < 2) {
-        double* srec = reinterpret_cast<double*>(partial + head_stat_base<A>());
-        srec[(size_t)t * gridDim.x + blockIdx.x] = redd[4 * t] + redd[4 * t + 1] + redd[4 * t + 2] + redd[4 * t + 3];
-    }
+    float* rec = head_record_sums(dW, cs, dbias, s_h, partial);
+    const double st[2] = {sse, sym.acc_sym};
+    head_wave_stats(st, s_h, partial);
+    head_record_bias(rec, s_h);
 }
 
 // y[r][c] = sign[c] x[r][src[c]] (src[c] < 0: 0) for rows x cols elements: exact, only signs change.  Up to MIRROR_MAX_COLS columns (the widest

@@ -38,8 +38,6 @@ __device__ __forceinline__ void split_a8(const f32x4& lo4, const f32x4& hi4, u32
     pl[1] = u32x4{mp[0], mp[1], mp[2], mp[3]};
     pl[2] = u32x4{lp[0], lp[1], lp[2], lp[3]};
 }
-#define BG_MFMA(ACC, A, B) ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A), __builtin_bit_cast(bf16x8, B), ACC, 0, 0, 0)
-#define BG_PIN() __builtin_amdgcn_sched_barrier(0)
 __device__ __forceinline__ void read_b3(u32x4 (&bp)[3], const unsigned* sw) {
 #pragma unroll
     for (int q = 0; q < 3; q++) bp[q] = *reinterpret_cast<const u32x4*>(sw + q * 16);

@@ -18,9 +18,6 @@
 
 #include "bg_wgrad.h"
 
-#define BG_MFMA(ACC, A, B) ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A), __builtin_bit_cast(bf16x8, B), ACC, 0, 0, 0)
-#define BG_PIN() __builtin_amdgcn_sched_barrier(0)
-
 constexpr int WS_BLOCK = 16;                  // batch rows per MFMA step
 constexpr int WS_LDS_FLOATS = 36864;          // 144 KB: three buffers of row blocks where they fit (two for the 128 x 128 layer), reused by the reduction (128 KB)
 // one block of zeros in device memory: the source of the copies a sub-range asks for past its end (sub-ranges of a workgroup may differ by one pair of

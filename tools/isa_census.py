@@ -6,7 +6,7 @@ per cent from the product kernel's; the product kernel's own total is printed ne
 import collections, json, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "booster_gym_amd", "csrc", "bg_sim.hip")
-FLAGS = "-O3 -std=c++17 --offload-arch=gfx950 -Wno-unused-function -fno-slp-vectorize -fno-signed-zeros -ffinite-math-only -fassociative-math -freciprocal-math -fno-trapping-math -mllvm -amdgpu-sched-strategy=max-ilp".split()
+FLAGS = subprocess.check_output(["make", "-s", "-C", os.path.dirname(SRC), "print-cxxflags"], text=True).split()  # the Makefile's, not a copy of them
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 want = args[0] if args else "forward_dynamics_kernelILb0"
 PLANE = ["-DBG_CENSUS_PLANE"] if "--plane" in sys.argv else []  # flat ground: leave the (never executed) height-field lookups out of the count

@@ -6,7 +6,7 @@ in between = one wait state, s_nop N = N + 1).  Fewer than two = a hazard.  No G
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "booster_gym_amd", "csrc", "bg_mlp_chain_split_bwd.hip")
-FLAGS = "-O3 -std=c++17 --offload-arch=gfx950 -Wno-unused-function -fno-slp-vectorize -fno-signed-zeros -ffinite-math-only -fassociative-math -freciprocal-math -fno-trapping-math -mllvm -amdgpu-sched-strategy=max-ilp".split()
+FLAGS = subprocess.check_output(["make", "-s", "-C", os.path.dirname(SRC), "print-cxxflags"], text=True).split()  # the Makefile's, not a copy of them
 NEED = 2
 
 
