@@ -156,7 +156,7 @@ SYMBOLS = [
     "bg_env_set_state", "bg_env_get_field", "bg_env_set_field", "bg_env_field_info", "bg_env_get_curriculum", "bg_env_set_curriculum", "bg_env_step_count", "bg_env_set_step_count",
     "bg_env_get_terrain_level_sum", "bg_env_set_terrain_level_sum", "bg_env_eval_begin", "bg_env_eval_step",
     "bg_env_forward_dynamics", "bg_env_forward_dynamics_packed", "bg_sim_bind_state", "bg_sim_set_actuation", "bg_sim_apply_body_wrench_local", "bg_sim_simulate",
-    "bg_sim_refresh_body_state", "bg_sim_write_root_state", "bg_sim_write_dof_state", "bg_gae", "bg_ppo_loss", "bg_gaussian_logp", "bg_actor_pack", "bg_actor_sample", "bg_actor_sample_mlp", "bg_actor_sample_mlp_scan", "bg_distill_act", "bg_distill_act_hist", "bg_distill_act_mix", "bg_adam_step", "bg_adapt_lr", "bg_optimizer_step", "bg_elu_backward_colsum", "bg_mlp_layer_forward", "bg_mlp_chain_forward", "bg_critic_values_gae", "bg_mlp_chain_forward_group", "bg_mlp_chain_forward_split", "bg_mlp_chain_backward_split", "bg_mlp_split_weights_pm", "bg_mlp_layer_backward", "bg_mlp_split_weights", "bg_mlp_layer_forward_split", "bg_mlp_layer_backward_split", "bg_mlp_weight_grad", "bg_mlp_weight_grad_group", "bg_mlp_weight_grad_group_partial", "bg_update_tail", "bg_update_tail_sums", "bg_mlp_weight_grad_group_split", "bg_mlp_weight_grad_group_split_partial",
+    "bg_sim_refresh_body_state", "bg_sim_write_root_state", "bg_sim_write_dof_state", "bg_gae", "bg_ppo_loss", "bg_gaussian_logp", "bg_actor_pack", "bg_actor_sample", "bg_actor_sample_mlp", "bg_actor_sample_mlp_scan", "bg_distill_act", "bg_distill_act_hist", "bg_distill_act_mix", "bg_actor_sample_est", "bg_adam_step", "bg_adapt_lr", "bg_optimizer_step", "bg_elu_backward_colsum", "bg_mlp_layer_forward", "bg_mlp_chain_forward", "bg_critic_values_gae", "bg_mlp_chain_forward_group", "bg_mlp_chain_forward_split", "bg_mlp_chain_backward_split", "bg_mlp_split_weights_pm", "bg_mlp_layer_backward", "bg_mlp_split_weights", "bg_mlp_layer_forward_split", "bg_mlp_layer_backward_split", "bg_mlp_weight_grad", "bg_mlp_weight_grad_group", "bg_mlp_weight_grad_group_partial", "bg_update_tail", "bg_update_tail_sums", "bg_mlp_weight_grad_group_split", "bg_mlp_weight_grad_group_split_partial",
     "bg_critic_head_forward", "bg_actor_head", "bg_critic_head_backward",
     "bg_reduce_group", "bg_actor_head_partial", "bg_critic_head_backward_partial", "bg_mlp_layer_backward_partial",
     "bg_actor_head_sym", "bg_actor_head_sym_partial", "bg_mirror_rows",
@@ -231,6 +231,7 @@ def load():
         "bg_distill_act": (i32, [i32, vp, i32, i32, C.POINTER(MlpLayerDesc), i32, C.POINTER(MlpLayerDesc), i32, vp, u64, u64, vp, vp, vp, vp]),
         "bg_distill_act_hist": (i32, [i32, vp, i32, vp, i32, i32, C.POINTER(MlpLayerDesc), i32, C.POINTER(MlpLayerDesc), i32, vp, u64, u64, vp, vp, vp, vp]),
         "bg_distill_act_mix": (i32, [i32, vp, i32, vp, i32, i32, C.POINTER(MlpLayerDesc), i32, C.POINTER(MlpLayerDesc), i32, vp, u64, u64, f32, i32, vp, vp, vp, vp]),
+        "bg_actor_sample_est": (i32, [i32, vp, i32, C.POINTER(MlpLayerDesc), i32, i32, C.POINTER(MlpLayerDesc), vp, u64, u64, vp, vp, vp, vp]),
         "bg_adam_step": (i32, [i32, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, vp, vp]),
         "bg_adapt_lr": (i32, [vp, f32, f32, f32, f32, vp, vp]),
         "bg_optimizer_step": (i32, [i32, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, vp, i32, i32, vp, vp, vp, i32, i32, f32, f32, f32, f32, vp, vp, i32, vp]),

@@ -24,6 +24,11 @@
 // columns and sample.  Both kernels are one body, actor_rows, so a half computes what the stand-alone kernel does on the same operands, bit for bit.
 // bg_distill_act_mix (distillation.teacher_action_prob, DAgger's mixing) is the same split grid in which the teacher's half acts on a row with
 // probability beta: a Philox uniform per (row, step) on a stream of its own, evaluated by both halves, decides which half writes the row's action.
+//
+// bg_actor_sample_est (the learned state estimator, T1.yaml estimator.enabled; its targets are columns of the reference's privileged observation,
+// envs/t1.py:593-602) runs two networks on the same rows one BEHIND the other in the same workgroup: the estimator 47 H -> hidden -> 12, whose
+// means go to memory, then the actor on the tile [obs | the first E means | zeros] rebuilt in LDS.  Same pieces (load_tile, run_layers, sample), same
+// two LDS tiles: the launch costs about the two stand-alone launches it replaces, without their two boundaries and the concatenation copy.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -132,33 +137,50 @@ __device__ __forceinline__ void layer(const float* __restrict__ W, const float* 
     }
 }
 
-// One workgroup's 16 rows [r0, r0 + 16) through one network: the body of both kernels below.  The rows are `stride` floats apart and the network reads
-// its own first net.in[0] columns of them.  act_out == nullptr: the mean alone goes to mu_out and no noise is drawn (bg_distill_act's teacher).
-// MIX (bg_distill_act_mix, compiled into its kernel alone): the row's action comes from ONE of two calls on the same rows, the teacher's when
-// u < beta and the student's otherwise, u = entry 0 of rand4_uniform(seed, row, counter, RS_DAGGER): both calls evaluate u and the one that acts
-// writes act_out, with the noise draw the other would have used (the teacher without it when teacher_noise is 0: its mean alone).
-template <int MAXW, bool MIX = false>
-__device__ __forceinline__ void actor_rows(int N, int r0, const float* __restrict__ obs, int stride, const ActorNet& net, const float* __restrict__ logstd,
-                                           uint64_t seed, uint32_t counter, float* __restrict__ mu_out, float* __restrict__ act_out, bool teacher_half = false,
-                                           float beta = 0.f, int teacher_noise = 0) {
-    constexpr int LDA = MAXW + 4;  // row stride (floats): = 4 mod 64 banks, as bg_actor_sample's 260
-    __shared__ __attribute__((aligned(16))) float buf[2][MR * LDA];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int K = net.in[0], KP = (K + KC - 1) / KC * KC;  // 47 H (+ P) columns; the tile's columns padded to whole k-chunks with zeros (KP <= LDA: host)
+// The pieces of a workgroup's pass over its 16 rows [r0, r0 + 16): load_tile, run_layers, sample.  actor_rows strings them together for one network,
+// actor_est_sample_kernel for two networks back to back.
+
+// The input tile [16][KP] (KP = K padded to whole k-chunks) into `tile`: columns [0, KO) from the rows of `obs`, `stride` floats apart, columns [KO, K)
+// from `ext` (an LDS tile of row stride LDA: bg_actor_sample_est's estimates; nullptr with KO == K), zeros behind them and in the rows past N.
+template <int LDA>
+__device__ __forceinline__ void load_tile(float* tile, int N, int r0, const float* __restrict__ obs, int stride, int KO, const float* ext, int K) {
+    const int KP = (K + KC - 1) / KC * KC;  // 47 H (+ P) columns; the tile's columns padded to whole k-chunks with zeros (KP <= LDA: host)
     for (int k = threadIdx.x; k < MR * KP; k += blockDim.x) {
         const int r = k / KP, c = k - r * KP;
-        buf[0][r * LDA + c] = (r0 + r < N && c < K) ? obs[(size_t)(r0 + r) * stride + c] : 0.f;
+        float v = 0.f;
+        if (r0 + r < N) {
+            if (c < KO) v = obs[(size_t)(r0 + r) * stride + c];
+            else if (c < K) v = ext[r * LDA + c - KO];
+        }
+        tile[r * LDA + c] = v;
     }
     __syncthreads();
-    first_layer<LDA>(net.W[0], net.b[0], K, net.out[0], buf[0], buf[1], wave, lane);
+}
+
+// Every layer of `net` on the input tile buf[in], the activations ping-ponging between the two tiles; returns the index of the tile that holds the
+// 12 outputs of the 16 rows (columns [0, 12)).  Ends behind a barrier.
+template <int LDA>
+__device__ __forceinline__ int run_layers(const ActorNet& net, float (*buf)[MR * LDA], int in) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    first_layer<LDA>(net.W[0], net.b[0], net.in[0], net.out[0], buf[in], buf[in ^ 1], wave, lane);
     __syncthreads();
-    int cur = 1;
+    int cur = in ^ 1;
     for (int l = 1; l < net.n; l++) {
         layer<LDA>(net.W[l], net.b[l], net.in[l], net.out[l], l + 1 < net.n, buf[cur], buf[cur ^ 1], wave, lane);
         __syncthreads();
         cur ^= 1;
     }
-    // sample: one thread per (row, group of 4 actions), as bg_actor_sample
+    return cur;
+}
+
+// sample: one thread per (row, group of 4 actions), as bg_actor_sample, from the means in `m` (an LDS tile of row stride LDA).  act_out == nullptr: the
+// mean alone goes to mu_out and no noise is drawn (bg_distill_act's teacher, bg_actor_sample_est's estimator).
+// MIX (bg_distill_act_mix, compiled into its kernel alone): the row's action comes from ONE of two calls on the same rows, the teacher's when
+// u < beta and the student's otherwise, u = entry 0 of rand4_uniform(seed, row, counter, RS_DAGGER): both calls evaluate u and the one that acts
+// writes act_out, with the noise draw the other would have used (the teacher without it when teacher_noise is 0: its mean alone).
+template <int LDA, bool MIX>
+__device__ __forceinline__ void sample(const float* m_tile, int N, int r0, const float* __restrict__ logstd, uint64_t seed, uint32_t counter,
+                                       float* __restrict__ mu_out, float* __restrict__ act_out, bool teacher_half, float beta, int teacher_noise) {
     if (threadIdx.x < MR * 3) {
         const int r = threadIdx.x / 3, g = threadIdx.x % 3, row = r0 + r;
         if (row < N) {
@@ -170,24 +192,57 @@ __device__ __forceinline__ void actor_rows(int N, int r0, const float* __restric
                 if (noise) rn = bg::rand4(seed, (uint32_t)row, counter, bg::RS_ACTOR + g);
                 for (int k = 0; k < 4; k++) {
                     const int a = g * 4 + k;
-                    const float m = buf[cur][r * LDA + a];
+                    const float m = m_tile[r * LDA + a];
                     if (mu_out) mu_out[(size_t)row * BG_NUM_DOFS + a] = m;
                     if (noise) act_out[(size_t)row * BG_NUM_DOFS + a] = m + expf(logstd[a]) * rn.n[k];
                     else if (acts) act_out[(size_t)row * BG_NUM_DOFS + a] = m;
                 }
             } else if (!act_out) {
-                for (int k = 0; k < 4; k++) mu_out[(size_t)row * BG_NUM_DOFS + g * 4 + k] = buf[cur][r * LDA + g * 4 + k];
+                for (int k = 0; k < 4; k++) mu_out[(size_t)row * BG_NUM_DOFS + g * 4 + k] = m_tile[r * LDA + g * 4 + k];
             } else {
                 bg::Rand4 rn = bg::rand4(seed, (uint32_t)row, counter, bg::RS_ACTOR + g);
                 for (int k = 0; k < 4; k++) {
                     const int a = g * 4 + k;
-                    const float m = buf[cur][r * LDA + a];
+                    const float m = m_tile[r * LDA + a];
                     if (mu_out) mu_out[(size_t)row * BG_NUM_DOFS + a] = m;
                     act_out[(size_t)row * BG_NUM_DOFS + a] = m + expf(logstd[a]) * rn.n[k];
                 }
             }
         }
     }
+}
+
+// One workgroup's 16 rows [r0, r0 + 16) through one network: the body of the three kernels below.  The rows are `stride` floats apart and the network
+// reads its own first net.in[0] columns of them.
+template <int MAXW, bool MIX = false>
+__device__ __forceinline__ void actor_rows(int N, int r0, const float* __restrict__ obs, int stride, const ActorNet& net, const float* __restrict__ logstd,
+                                           uint64_t seed, uint32_t counter, float* __restrict__ mu_out, float* __restrict__ act_out, bool teacher_half = false,
+                                           float beta = 0.f, int teacher_noise = 0) {
+    constexpr int LDA = MAXW + 4;  // row stride (floats): = 4 mod 64 banks, as bg_actor_sample's 260
+    __shared__ __attribute__((aligned(16))) float buf[2][MR * LDA];
+    load_tile<LDA>(buf[0], N, r0, obs, stride, net.in[0], nullptr, net.in[0]);
+    const int cur = run_layers<LDA>(net, buf, 0);
+    sample<LDA, MIX>(buf[cur], N, r0, logstd, seed, counter, mu_out, act_out, teacher_half, beta, teacher_noise);
+}
+
+// bg_actor_sample_est: the estimator, then the actor on [obs | estimates], on the same 16 rows in one workgroup.  The estimator's 12 means go to est_out
+// (sample's mean-only form); the actor's input tile is rebuilt in the activation tile the estimator's last layer read (free behind run_layers' last
+// barrier): the 47 H observation columns from global memory again (L2-hot), columns [47 H, 47 H + E) from the tile that holds the estimator's means,
+// zeros to the k-chunk boundary -- what load_tile builds from a contiguous row [obs | est_out[:E]], so the actor's half computes what
+// bg_actor_sample_mlp_scan(scan_points = E) does on that row, bit for bit.  The tile of the means is overwritten only behind load_tile's barrier.
+struct EstNets { ActorNet est, actor; };
+template <int MAXW>
+__global__ __launch_bounds__(256) void actor_est_sample_kernel(int N, const float* __restrict__ obs, EstNets nets, const float* __restrict__ logstd, uint64_t seed,
+                                                               uint32_t counter, float* __restrict__ est_out, float* __restrict__ mu_out, float* __restrict__ act_out) {
+    constexpr int LDA = MAXW + 4;
+    __shared__ __attribute__((aligned(16))) float buf[2][MR * LDA];
+    const int r0 = blockIdx.x * MR, KO = nets.est.in[0];
+    load_tile<LDA>(buf[0], N, r0, obs, KO, KO, nullptr, KO);
+    int cur = run_layers<LDA>(nets.est, buf, 0);
+    sample<LDA, false>(buf[cur], N, r0, nullptr, seed, counter, est_out, nullptr, false, 0.f, 0);
+    load_tile<LDA>(buf[cur ^ 1], N, r0, obs, KO, KO, buf[cur], nets.actor.in[0]);
+    cur = run_layers<LDA>(nets.actor, buf, cur ^ 1);
+    sample<LDA, false>(buf[cur], N, r0, logstd, seed, counter, mu_out, act_out, false, 0.f, 0);
 }
 
 template <int MAXW>
@@ -274,6 +329,29 @@ extern "C" int bg_actor_sample_mlp_scan(int32_t N, const float* obs, int32_t n_l
                                         const float* logstd, uint64_t seed, uint64_t counter, float* mu, float* actions, void* stream) {
     if (scan_points < 0 || scan_points > BG_MAX_HEIGHT_SCAN_POINTS) return bg_set_error(-1, "bg_actor_sample_mlp_scan: bad argument (scan_points)");
     return sample_mlp(N, obs, n_layers, layers, scan_points, logstd, seed, counter, mu, actions, stream);
+}
+
+extern "C" int bg_actor_sample_est(int32_t N, const float* obs, int32_t n_est, const bg_mlp_layer_desc* est, int32_t est_cols, int32_t n_actor,
+                                   const bg_mlp_layer_desc* actor, const float* logstd, uint64_t seed, uint64_t counter, float* est_out, float* mu, float* actions,
+                                   void* stream) {
+    if (N <= 0 || !obs || !est || !actor || !logstd || !est_out || !actions) return bg_set_error(-1, "bg_actor_sample_est: bad argument");
+    if (est_cols < 1 || est_cols > BG_NUM_DOFS) return bg_set_error(-1, "bg_actor_sample_est: bad argument (est_cols: 1 to 12 of the estimator's outputs)");
+    EstNets nets;
+    int maxw_e = 0, maxw_a = 0;
+    if (const int rc = fill_net("bg_actor_sample_est (estimator)", n_est, est, 0, nets.est, maxw_e)) return rc;
+    if (const int rc = fill_net("bg_actor_sample_est (actor)", n_actor, actor, est_cols, nets.actor, maxw_a)) return rc;
+    if (actor[0].in != est[0].in + est_cols)
+        return bg_set_error(-4, "bg_actor_sample_est (actor): the first layer takes the estimator's 47 H observation columns and est_cols estimates behind them");
+    const dim3 grid((N + MR - 1) / MR), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    // one LDS form for both networks: the wider hidden layer of the two and the actor's input tile (the wider of the two tiles)
+    const int kp = (actor[0].in + KC - 1) / KC * KC, maxw = maxw_e > maxw_a ? maxw_e : maxw_a;
+    if (maxw <= 256 && kp <= 256)
+        hipLaunchKernelGGL(actor_est_sample_kernel<256>, grid, block, 0, st, N, obs, nets, logstd, seed, (uint32_t)counter, est_out, mu, actions);
+    else
+        hipLaunchKernelGGL(actor_est_sample_kernel<512>, grid, block, 0, st, N, obs, nets, logstd, seed, (uint32_t)counter, est_out, mu, actions);
+    HIP_OK(hipGetLastError());
+    return 0;
 }
 
 // The distillation entry points: DA_PLAIN = bg_distill_act (sobs = obs, sstride = stride), DA_HIST = bg_distill_act_hist (the student's own buffer),

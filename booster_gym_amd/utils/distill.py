@@ -48,6 +48,7 @@ from ..envs.mirror import mirror_maps
 from ..envs.t1 import MAX_CRITIC_INPUT, MAX_FRAME_STACK, frame_stack_of
 from .buffer import ExperienceBuffer
 from .config import load_cfg
+from .estimator import estimator_enabled
 from .model import CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, MLPTrainer, WeightClock, check_hidden, hidden_of, plan_network
 from .recorder import Recorder
 from .runner import FlatAdam, hidden_widths, pad_input, wgrad_products
@@ -85,6 +86,9 @@ def distillation_cfg(cfg, world_size=1):
     if (cfg.get("algorithm", {}) or {}).get("empirical_normalization", False):
         raise ValueError("algorithm.empirical_normalization: true is not supported with distillation for now (a teacher trained with it carries "
                          "statistics of its own row, the student's would be others)")
+    if estimator_enabled(cfg):
+        raise ValueError("estimator.enabled: true is not supported with distillation for now (the student's row would need the estimates of a network "
+                         "the Distiller does not train): set estimator.enabled to false")
     if int(world_size) != 1:
         raise ValueError(f"distillation runs on one rank (WORLD_SIZE = {world_size}): data parallelism is out of scope")
     v = dict(DEFAULTS, **sec)

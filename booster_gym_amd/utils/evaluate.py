@@ -145,6 +145,8 @@ class Evaluator:
         self._mu = torch.zeros(N, A, device=env.device)       # the action: the mean of the rollout's own launch
         self._sampled = torch.zeros(N, A, device=env.device)  # ... whose sample is not used
         self._obs_normed = torch.zeros(N, env.num_obs, device=env.device) if self.obs_norm is not None else None
+        # estimator.enabled: the launch writes the estimator's 12 means somewhere; nobody here reads them
+        self._est_scratch = torch.zeros(N, _lib.NUM_DOFS, device=env.device) if r.model.has_estimator else None
         self.record, self.steps, self.loop_s = None, 0, None
 
     def run(self, steps=None):
@@ -167,7 +169,7 @@ class Evaluator:
             t0.record()
             for k in range(K):
                 x = obs if norm is None else norm.normalize_into(obs, self._obs_normed)
-                model.sample_actions(x, self._sampled, seed, k, mu_out=self._mu, scan=scan, packed=packed)
+                model.sample_actions(x, self._sampled, seed, k, mu_out=self._mu, scan=scan, packed=packed, est_out=self._est_scratch)
                 obs = env.step(self._mu)[0]
                 env.eval_step(record, self.settle_steps)
             t1.record()

@@ -9,7 +9,8 @@ The PPO update's GEMMs run on hand-written HIP kernels (MLPTrainer: the chained 
 gradients), in the form its NetPlan names, on copies of the weights that one object per trainer owns (WeightCopies: padded, transposed, bf16 planes;
 each current exactly when written or stamped at the present value of the parameters' WeightClock); the rollout-time inference + sampling is one fused HIP launch
 (`sample_actions` -> bg_actor_sample at the reference's widths on 47 inputs, bg_actor_sample_mlp at any other supported widths and on a
-frame stack of 47 H inputs).
+frame stack of 47 H inputs).  With estimator.enabled a third network, `estimator` (47 H -> hidden -> 12), feeds the first E of its outputs to the
+actor behind the observations; the rollout runs both in one launch (bg_actor_sample_est).
 """
 import ctypes
 import os
@@ -617,18 +618,56 @@ class MLPTrainer:
             torch.sum(self.dw[i], dim=0, out=l.weight.grad)
 
 
+class EstimatorActor(torch.nn.Module):
+    """What export_model.py scripts for a checkpoint with a state estimator: actor(cat(x, estimator(x)[:, :E])) on rows x of 47 H observations -- the
+    deploy contract stays "47 H floats in, 12 out"."""
+
+    def __init__(self, actor, estimator, estimator_cols):
+        super().__init__()
+        self.actor, self.estimator, self.estimator_cols = actor, estimator, int(estimator_cols)
+
+    def forward(self, x):
+        return self.actor(torch.cat((x, self.estimator(x)[..., : self.estimator_cols]), dim=-1))
+
+
 class ActorCritic(torch.nn.Module):
-    def __init__(self, num_act, num_obs, num_privileged_obs, actor_hidden=ACTOR_HIDDEN, critic_hidden=CRITIC_HIDDEN):
+    """estimator_hidden (estimator.enabled, utils/estimator.py; None = without, exactly the reference's parameters in the reference's order): a third
+    network `estimator`, num_obs -> estimator_hidden -> 12, registered behind `logstd`; the actor then takes num_obs + estimator_cols inputs, the
+    observations and the first estimator_cols = E of the estimator's 12 outputs.  num_obs stays the env's row (47 H): what callers pass as `obs`."""
+
+    def __init__(self, num_act, num_obs, num_privileged_obs, actor_hidden=ACTOR_HIDDEN, critic_hidden=CRITIC_HIDDEN, estimator_hidden=None, estimator_cols=0):
         super().__init__()
         self.actor_hidden, self.critic_hidden = tuple(actor_hidden), tuple(critic_hidden)
+        self.estimator_hidden = None if estimator_hidden is None else tuple(estimator_hidden)
+        self.estimator_cols = int(estimator_cols) if estimator_hidden is not None else 0
+        if estimator_hidden is not None and not 1 <= self.estimator_cols <= _lib.NUM_DOFS:
+            raise ValueError(f"estimator_cols = {estimator_cols!r}: 1 to {_lib.NUM_DOFS} of the estimator's outputs enter the actor")
         self.critic = _mlp(num_obs + num_privileged_obs, self.critic_hidden, 1)
-        self.actor = _mlp(num_obs, self.actor_hidden, num_act)
+        self.actor = _mlp(num_obs + self.estimator_cols, self.actor_hidden, num_act)
         self.logstd = torch.nn.parameter.Parameter(torch.full((1, num_act), fill_value=-2.0), requires_grad=True)
+        if estimator_hidden is not None:
+            self.estimator = _mlp(num_obs, self.estimator_hidden, _lib.NUM_DOFS)
         self._sample_key, self._sample_layers = None, None
+        self._est_key, self._est_layers = None, None
         self._packed = None  # pack_actor()
 
+    @property
+    def has_estimator(self):
+        return self.estimator_hidden is not None
+
+    def ppo_parameters(self):
+        """What PPO's optimiser holds: critic, actor, logstd in the module's order (all parameters of a model without an estimator); the estimator's
+        are stepped by an optimiser of their own."""
+        return [p for n, p in self.named_parameters() if not n.startswith("estimator.")]
+
+    def actor_input(self, obs):
+        """The actor's row of observation rows: obs itself, or [obs | the first E of the estimator's outputs]."""
+        if not self.has_estimator:
+            return obs
+        return torch.cat((obs, self.estimator(obs)[..., : self.estimator_cols]), dim=-1)
+
     def act(self, obs):
-        mean = self.actor(obs)
+        mean = self.actor(self.actor_input(obs))
         return torch.distributions.Normal(mean, torch.exp(self.logstd).expand_as(mean))
 
     def est_value(self, obs, privileged_obs):
@@ -644,7 +683,7 @@ class ActorCritic(torch.nn.Module):
         or None where the architecture samples through bg_actor_sample_mlp, which reads the parameters themselves.  The packed copy is a snapshot:
         whoever passes it to sample_actions packs again after anything that may have changed a parameter (the rollout: at its start, every iteration)."""
         lin, w = self._sample_params()
-        if self.actor_hidden != ACTOR_HIDDEN or lin[0].in_features != _lib.NUM_OBS:
+        if self.actor_hidden != ACTOR_HIDDEN or lin[0].in_features != _lib.NUM_OBS or self.has_estimator:
             return None
         if not w[0].is_cuda:
             raise RuntimeError("pack_actor runs a HIP kernel and needs CUDA parameters")
@@ -656,19 +695,22 @@ class ActorCritic(torch.nn.Module):
         _lib.check(_lib.load().bg_actor_pack(*[_lib.ptr(t) for t in w], _lib.ptr(self._packed), _lib.current_stream_ptr()), "bg_actor_pack")
         return self._packed
 
-    def sample_actions(self, obs, actions_out, seed, counter, mu_out=None, scan=0, packed=None):
+    def sample_actions(self, obs, actions_out, seed, counter, mu_out=None, scan=0, packed=None, est_out=None):
         """One launch: the actor's mean and a Gaussian sample around it.  The reference's widths on 47 inputs run bg_actor_sample (its widths built
         into the kernel) on a packed copy of the parameters: `packed` from pack_actor() where the caller knows that no parameter has changed since
         (the rollout packs once for its 24 steps), else packed here, one more small launch.  Every other architecture, and every actor on a frame stack
         (47 H inputs, env.frame_stack), runs bg_actor_sample_mlp (widths from descriptors, the weights read from the parameters themselves); both draw
         the same noise for the same seed and counter.  scan = P (terrain.actor_heights): the rows end with the height scan's P values behind the 47 H
-        observations (bg_actor_sample_mlp_scan, the same kernel)."""
+        observations (bg_actor_sample_mlp_scan, the same kernel).  A model with an estimator runs bg_actor_sample_est, both networks in one launch:
+        obs has the env's 47 H columns and est_out [N][12] (required) receives the estimator's 12 means, the first E of which the actor has read."""
         if not obs.is_cuda:
             raise RuntimeError("sample_actions runs the fused HIP actor kernel and needs CUDA tensors")
         lin, w = self._sample_params()
         for t in w + [obs, actions_out]:
             if not t.is_contiguous():
                 raise RuntimeError("sample_actions needs contiguous tensors")
+        if self.has_estimator:
+            return self._sample_actions_est(obs, actions_out, seed, counter, mu_out, scan, est_out, lin, w)
         if self.actor_hidden == ACTOR_HIDDEN and lin[0].in_features == _lib.NUM_OBS:
             if packed is None:
                 packed = self.pack_actor()
@@ -689,4 +731,31 @@ class ActorCritic(torch.nn.Module):
             return actions_out
         _lib.check(_lib.load().bg_actor_sample_mlp(obs.shape[0], _lib.ptr(obs), len(lin), self._sample_layers, _lib.ptr(self.logstd), int(seed), int(counter),
                                                    _lib.ptr(mu_out), _lib.ptr(actions_out), _lib.current_stream_ptr()), "bg_actor_sample_mlp")
+        return actions_out
+
+    def _sample_actions_est(self, obs, actions_out, seed, counter, mu_out, scan, est_out, lin, w):
+        """sample_actions of a model with an estimator: ONE launch (bg_actor_sample_est) runs the estimator on obs, writes its 12 means to est_out and
+        samples from the actor on [obs | the first E means]."""
+        elin = [m for m in self.estimator if isinstance(m, torch.nn.Linear)]
+        if scan:
+            raise ValueError("sample_actions: a model with an estimator takes no height scan in the actor's row (terrain.actor_heights)")
+        if est_out is None:
+            raise ValueError("sample_actions: a model with an estimator needs est_out, a [N][12] tensor for the estimator's means (a scratch tensor for "
+                             "callers that do not keep them)")
+        if (not est_out.is_cuda or not est_out.is_contiguous() or est_out.dtype != torch.float32 or tuple(est_out.shape) != (obs.shape[0], _lib.NUM_DOFS)):
+            raise ValueError(f"sample_actions: est_out must be a contiguous float32 CUDA tensor of shape [{obs.shape[0]}][{_lib.NUM_DOFS}]")
+        if obs.shape[-1] != elin[0].in_features:
+            raise ValueError(f"sample_actions: observations of {obs.shape[-1]} columns, the estimator takes {elin[0].in_features}")
+        ew = [t for l in elin for t in (l.weight, l.bias)]
+        for t in ew:
+            if not t.is_contiguous():
+                raise RuntimeError("sample_actions needs contiguous tensors")
+        key = tuple(t.data_ptr() for t in w + ew)
+        if key != self._est_key:  # descriptors of the current parameter storage of both networks
+            desc = lambda ls: (_lib.MlpLayerDesc * len(ls))(*[_lib.MlpLayerDesc(l.weight.data_ptr(), l.bias.data_ptr(), l.in_features, l.out_features) for l in ls])
+            self._est_layers, self._est_key = (desc(elin), desc(lin)), key
+        ed, ad = self._est_layers
+        _lib.check(_lib.load().bg_actor_sample_est(obs.shape[0], _lib.ptr(obs), len(elin), ed, self.estimator_cols, len(lin), ad, _lib.ptr(self.logstd), int(seed),
+                                                   int(counter), _lib.ptr(est_out), _lib.ptr(mu_out), _lib.ptr(actions_out), _lib.current_stream_ptr()),
+                   "bg_actor_sample_est")
         return actions_out

@@ -26,6 +26,10 @@ Same surface: `Runner(test=False)` parses the reference's 8 CLI flags (runner.py
             every optimiser step, in invalidate() and at the start of an update() that does not start from the rollout's passes; the tail stamps what it wrote.
             The sequence is written once, on the rows of a StepRows (the whole batch, or one of runner.num_mini_batches' K-ths of it): Runner.update ->
             _whole_batch_values, then per optimiser step _step and _epoch_gradients_and_step; _epoch_on_two_streams places the same pieces on two streams.
+  estimator estimator.enabled (utils/estimator.py; off by default): a third network regresses chosen privileged columns from the observations and the actor
+            takes [observations | estimates].  The rollout's launch is then bg_actor_sample_est (both networks, the estimates kept in the buffer
+            `estimates`), the update builds the actor's input from the stored rows, and behind the last PPO step the estimator takes its own
+            supervised Adam steps (_estimator_update: distillation's kernels, an optimiser and a WeightClock of its own).  No forward-ahead then.
   multi-GPU one process per GPU (torchrun), environments sharded; per mini-epoch one float64 moments all-reduce on the side stream and ONE grouped RCCL
             launch on the main stream (gradient bucket mean, loss / KL sums, log-std gradient mean) through an own communicator (utils/rccl.py) --
             SURVEY section 8e; the enqueue-order contract of the two communicators is written in utils/parallel.py.
@@ -49,6 +53,7 @@ import torch
 from .. import _lib
 from ..envs import TASKS
 from .buffer import ExperienceBuffer
+from .estimator import EST_WIDTH, check_estimator_checkpoint, estimator_cfg
 from .config import load_cfg
 from .obs_norm import ObsNormalizer, check_checkpoint, normalization_cfg
 from .model import ACTOR_HIDDEN, CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, MLPTrainer, NetPlan, WeightClock, check_hidden, hidden_of, plan_network
@@ -332,6 +337,8 @@ class Runner:
         if self.world_size > 1:  # one process per GPU: each rank simulates and learns on its own device
             self.cfg["basic"]["sim_device"] = self.cfg["basic"]["rl_device"] = f"cuda:{self.dp.device_index}"
         self._mini_batches = mini_batches(self.cfg)[1]  # (ValueError before anything is built; 1 = off: the one switch every branch below reads)
+        # estimator.enabled: a learned state estimator in front of the actor (utils/estimator.py); None = off, the one switch every branch below reads
+        self._est = estimator_cfg(self.cfg, self.world_size)
         self._set_seed()
         task = self.cfg["basic"]["task"]
         if task not in TASKS:
@@ -347,14 +354,19 @@ class Runner:
         if self._symmetry:  # (ValueError for a model without a left / right pairing or with an asymmetric default pose)
             obs_src, obs_sign, act_src, act_sign = self.env.mirror_maps()
             self._act_mirror = (act_src.tolist(), act_sign.tolist())
-        self.model = ActorCritic(self.env.num_actions, self.env.num_obs, self.env.num_privileged_obs, self.actor_hidden, self.critic_hidden).to(self.device)
+        est_args = {} if self._est is None else {"estimator_hidden": self._est.hidden, "estimator_cols": len(self._est.targets)}
+        self.model = ActorCritic(self.env.num_actions, self.env.num_obs, self.env.num_privileged_obs, self.actor_hidden, self.critic_hidden, **est_args).to(self.device)
         self.dp.broadcast_parameters(self.model)  # identical initial weights on every rank
         # algorithm.empirical_normalization: running mean / variance of the critic's input columns (the actor's are its first num_obs), applied where rows
         # enter a network and updated at the end of update(); None = off, the one switch every branch below reads
         self.obs_norm = ObsNormalizer(self.env.num_obs + self.env.num_privileged_obs, obs_norm_eps, self.device) if obs_norm_on else None
         self._clock = WeightClock()  # the version of the parameters, shared by every trainer over them: see invalidate()
+        # ... and of the estimator's, a clock of its own: PPO's steps do not change its parameters, its steps not PPO's
+        self._est_clock = WeightClock() if self._est is not None else None
         self.invalidate()
-        self.optimizer = FlatAdam(self.model.parameters(), lr=self.learning_rate)
+        self.optimizer = FlatAdam(self.model.ppo_parameters(), lr=self.learning_rate)  # (critic, actor, logstd: all parameters of a model without an estimator)
+        if self._est is not None:  # the estimator's own optimiser: no PPO gradient reaches it, PPO's buffer holds what it holds without the key
+            self._est_opt = FlatAdam(self.model.estimator.parameters(), lr=self._est.learning_rate, max_grad_norm=self._est.max_grad_norm)
         self._load()
         # Resume semantics of the reference (runner.py:31-34,174-180): the restored param_group lr serves the FIRST optimiser step only; the
         # first KL adaptation then overwrites it with a value derived from self.learning_rate = the yaml value, so adaptation restarts from
@@ -371,17 +383,20 @@ class Runner:
         self.buffer.add_buffer("rewards", ())
         self.buffer.add_buffer("dones", (), dtype=torch.bool)
         self.buffer.add_buffer("time_outs", (), dtype=torch.bool)
+        if self._est is not None:  # step n's 12 estimator outputs, computed from obses[n] by the estimator as it was then (rollout)
+            self.buffer.add_buffer("estimates", (EST_WIDTH,))
         B, A = T * N, self.env.num_actions
         dev = self.device
         # network inputs with the feature dimension zero-padded, each network on its own (pad_input: actor 47 -> 64, critic 61 -> 64, or 61 + P -> 128 /
         # 256 / 512 with the terrain height scan; with env.frame_stack = H the actor's 47 H and the critic's 47 H + 14 + P likewise) so that the first
         # layers run on the fused MFMA kernels
         no, npv = self.env.num_obs, self.env.num_privileged_obs
-        self._pad_actor = pad_input(no) if MLPTrainer.FUSED else None
+        E = self._est_cols = 0 if self._est is None else len(self._est.targets)  # the actor's input: the env's row and, behind it, E estimates
+        self._pad_actor = pad_input(no + E) if MLPTrainer.FUSED else None
         self._pad_critic = pad_input(no + npv) if MLPTrainer.FUSED else None
         if self._pad_actor and self._pad_actor > 256 and (int((self.cfg.get("parallel", {}) or {}).get("gemm_split", 0) or 0) or MLPTrainer.SPLIT):
             raise ValueError(f"parallel.gemm_split / BG_GEMM_SPLIT runs split-bf16 layer kernels that take layer inputs of 64, 128 or 256 columns only; the "
-                             f"actor's input of {no} observations pads to {self._pad_actor} (env.frame_stack 5 or less, without terrain.actor_heights or with fewer points of its scan, or gemm_split 0)")
+                             f"actor's input of {no + E} observations pads to {self._pad_actor} (env.frame_stack 5 or less, without terrain.actor_heights or with fewer points of its scan, or gemm_split 0)")
         if self._pad_critic and self._pad_critic > 256 and (int((self.cfg.get("parallel", {}) or {}).get("gemm_split", 0) or 0) or MLPTrainer.SPLIT):
             raise ValueError(f"parallel.gemm_split / BG_GEMM_SPLIT runs split-bf16 layer kernels that take layer inputs of 64, 128 or 256 columns only; the "
                              f"critic's input {no} + {npv} pads to {self._pad_critic} (fewer terrain.measured_points_x / _y points, or gemm_split 0)")
@@ -459,7 +474,8 @@ class Runner:
         self._head_scratch_a, self._head_scratch_c = head_scratch(dev), head_scratch(dev)
         self._act_counter = 0
         # The forward passes of the first mini-epoch run DURING the rollout (see rollout()): 1 = on (default where the chained kernels apply), 0 = off
-        self._rollout_forward = os.environ.get("BG_ROLLOUT_FORWARD", "1") == "1" and self._pad_actor is not None and N % 128 == 0
+        # (off with the estimator: step n's estimate, a part of the actor's row, does not exist when step n's rows would be forwarded)
+        self._rollout_forward = os.environ.get("BG_ROLLOUT_FORWARD", "1") == "1" and self._pad_actor is not None and N % 128 == 0 and self._est is None
         # ... the rows of this many consecutive steps per group of side-stream launches.  Every group costs the main stream one event record (2.9 us, 5.7
         # with a waiter on another queue: tools/event_cost_probe.py), and from four steps per group on the chained launches need more than the 128 CUs
         # the env step leaves idle and slow it down (110 against 102.5 us).  Same box, 20 iterations each, ms per iteration: off 24.78-24.92, one step
@@ -471,6 +487,8 @@ class Runner:
             self._init_mini_batches()
         if self._symmetry:
             self._resolve_plan()  # (a plan the symmetric head cannot serve is a ValueError here, not at the first update)
+        if self._est is not None:
+            self._init_estimator()
 
     # ------------------------------------------------------------------ config / seed / checkpoint (runner.py:44-97)
     def _get_args(self, args=None):
@@ -520,6 +538,8 @@ class Runner:
         print("Loading model from {}".format(ck))
         model_dict = torch.load(ck, map_location=self.device, weights_only=True)
         ck_ain, a_in = int(model_dict["model"]["actor.0.weight"].shape[1]), self.model.actor[0].in_features
+        est = getattr(self, "_est", None)
+        check_estimator_checkpoint(ck, model_dict, est, ck_ain, a_in)  # (before the frame-stack message below can misfire on a width that differs by E)
         scan_ck, scan_cfg = (int(model_dict["height_points"].shape[0]) if "height_points" in model_dict else 0), getattr(self.env, "num_scan_obs", 0)
         if ck_ain != a_in and ck_ain - scan_ck == a_in - scan_cfg:  # (the widths differ by the height scan in the actor's row)
             raise ValueError(f"checkpoint {ck} has an actor of {ck_ain} inputs, {scan_ck} of them the terrain height scan, the config's actor takes {a_in} "
@@ -558,6 +578,11 @@ class Runner:
             self.optimizer.load_state_dict(model_dict["optimizer"])
         except Exception as e:
             print(f"Failed to load optimizer: {e}")
+        if est is not None:
+            try:
+                self._est_opt.load_state_dict(model_dict["estimator"]["optimizer"])
+            except Exception as e:
+                print(f"Failed to load the estimator's optimizer: {e}")
 
     def invalidate(self):
         """Call after changing the model's parameters or the rollout buffers by any means other than this runner's own rollout() / update() (a
@@ -568,9 +593,13 @@ class Runner:
         buffers as they are."""
         self._fwd_plan = None
         self._clock.tick()
+        if self._est is not None:
+            self._est_clock.tick()
 
     def checkpoint_dict(self):
         d = {"model": self.model.state_dict(), "optimizer": self.optimizer.state_dict(), "curriculum": self.env.curriculum_prob}
+        if getattr(self, "_est", None) is not None:  # (the network itself: "estimator.*" inside "model")
+            d["estimator"] = {"targets": list(self._est.targets), "optimizer": self._est_opt.state_dict()}
         if self.env.terrain.curriculum:
             d["terrain_levels"] = self.env.terrain_levels
         if self.obs_norm is not None:
@@ -587,7 +616,7 @@ class Runner:
         sw.update((k[1:], getattr(self, k)) for k in ("_one_stream", "_defer_finish", "_one_launch_tail", "_fused_opt", "_fused_head", "_fused_gae", "_chain_values",
                                                       "_rollout_forward"))
         widths = lambda tr: (tr.layers[0].in_features,) + tuple(l.out_features for l in tr.layers)
-        kin_a = self._actor_in.shape[-1] if self._actor_in is not None else self.env.num_obs
+        kin_a = self._actor_in.shape[-1] if self._actor_in is not None else self.env.num_obs + self._est_cols  # (the actor's true input width)
         plan = plan_update((widths(ct), self._critic_in.shape[-1]), (widths(at), kin_a), self._old_logp.numel(), dp_active=self.dp.active, symmetry=self._symmetry, **sw)
         ct.plan, at.plan = plan.critic, plan.actor
         c_out = ct.layers[-1]
@@ -599,6 +628,64 @@ class Runner:
             self._critic_mb.plan, self._actor_mb.plan = mp.critic, mp.actor
             self._critic_mb.value_head = (c_out.weight.reshape(-1), c_out.bias, self._mb_values) if mp.chain_values else None
         return plan
+
+    # ------------------------------------------------------------------ estimator.enabled
+    def _init_estimator(self):
+        """What estimator.enabled adds to the runner behind the model, the second FlatAdam and the `estimates` buffer: an MLPTrainer over the estimator
+        under its own WeightClock, its zero-padded input, the regression target
+        [B][12] and the workspaces of Distiller.update's sequence."""
+        T, N, dev = self.cfg["runner"]["horizon_length"], self.env.num_envs, self.device
+        B, no = T * N, self.env.num_obs
+        self._est_tr = MLPTrainer(self.model.estimator, clock=self._est_clock)
+        self._est_in = torch.zeros(B, pad_input(no), device=dev)  # (the padded columns stay zero)
+        self._est_target = torch.zeros(B, EST_WIDTH, device=dev)  # columns [E, 12) stay zero: what the unread outputs regress onto
+        self._est_idx = torch.tensor(self._est.targets, dtype=torch.long, device=dev)
+        self._est_sel = torch.zeros(B, len(self._est.targets), device=dev)
+        self._est_wgrad = GroupedWeightGrad()
+        self._est_head_scratch = head_scratch(dev)
+        self._est_stats = torch.zeros(1, dtype=torch.float64, device=dev)  # an epoch's sum of squared errors
+        self._est_loss = torch.zeros(1, dtype=torch.float64, device=dev)   # the last epoch's loss, SSE / (12 B): estimator/loss of the log
+        self._resolve_estimator_plan()  # (a batch outside the layer kernels' range is a ValueError here, not at the first update)
+
+    def _resolve_estimator_plan(self):
+        """The estimator's NetPlan of MLPTrainer's switches as they are now (plan_network, as utils/distill.py) and the products of its grouped
+        weight-gradient launch; ValueError where a pass would fall to a library GEMM."""
+        tr, B = self._est_tr, self._est_target.shape[0]
+        widths, kin, sw = (tr.layers[0].in_features,) + tuple(l.out_features for l in tr.layers), self._est_in.shape[1], MLPTrainer
+        if sw.SPLIT and (kin > 256 or any(w > 256 for w in widths[1:-2])):
+            raise ValueError(f"parallel.gemm_split / BG_GEMM_SPLIT runs split-bf16 layer kernels that take layer inputs of 64, 128 or 256 columns only; the "
+                             f"estimator's input pads to {kin} and estimator.hidden = {list(widths[1:-1])} (use gemm_split 0)")
+        tr.plan = plan = plan_network(widths, kin, B, sw.SPLIT, sw.FUSED, sw.CHAIN, sw.CHAIN_SPLIT, sw.CHAIN_SPLIT_BWD, sw.CHAIN_ALTERNATE, sw.FUSED_WGRAD)
+        if "library" in (plan.fwd, plan.bwd) or not all(plan.grouped[:-1]):
+            raise ValueError(f"estimator.enabled: a batch of runner.horizon_length x env.num_envs = {B} rows is outside the range of the layer kernels (an "
+                             "even number of 64 rows or more)")
+        shapes = [(co, ci) for ci, co in zip((kin,) + widths[1:-2], widths[1:-1])]
+        self._est_wgrad_terms = wgrad_products(B, shapes, plan.bwd == "chain_split", sw.SPLIT, sw.WGRAD_SPLIT)
+
+    def _estimator_update(self, u):
+        """estimator.num_epochs full-batch Adam steps of L = 1 / (12 B) sum |estimator(obses) - target|^2 on the iteration's T x N rows, target = the
+        chosen privileged columns, then zeros: Distiller.update's sequence (forward_hidden, bg_distill_head_partial, backward_hidden, the grouped weight
+        gradients, reduce_group, step, clock tick) on the main stream; no library GEMM.  Leaves the last epoch's loss in _est_loss (device)."""
+        e, tr, B, T = self._est, self._est_tr, u.B, u.T
+        self._resolve_estimator_plan()
+        out, hid = tr.layers[-1], tr.layers[-2]
+        self._est_in[:, : self.env.num_obs].copy_(u.buf["obses"][:T].reshape(B, -1))
+        torch.index_select(u.buf["privileged_obses"][:T].reshape(B, -1), 1, self._est_idx, out=self._est_sel)
+        self._est_target[:, : len(e.targets)].copy_(self._est_sel)
+        for _ in range(e.num_epochs):
+            h = tr.forward_hidden(self._est_in)
+            self._est_stats.zero_()
+            fin, fins = _lib.ReduceProblem(), []
+            _lib.check(_lib.load().bg_distill_head_partial(B, _lib.ptr(h), _lib.ptr(out.weight), _lib.ptr(out.bias), _lib.ptr(self._est_target), None,
+                                                           _lib.ptr(tr.hidden_grad), _lib.ptr(out.weight.grad), _lib.ptr(out.bias.grad), _lib.ptr(hid.bias.grad),
+                                                           _lib.ptr(self._est_stats), _lib.ptr(self._est_head_scratch), fin, _lib.current_stream_ptr()),
+                       "bg_distill_head_partial")
+            tr.backward_hidden(finishes=fins)
+            self._est_wgrad.run((tr,), self._est_wgrad_terms, False)
+            reduce_group([fin] + fins)
+            self._est_opt.step()
+            self._est_clock.tick()
+        torch.mul(self._est_stats, 1.0 / (EST_WIDTH * B), out=self._est_loss)
 
     # ------------------------------------------------------------------ runner.num_mini_batches > 1
     def _init_mini_batches(self):
@@ -677,7 +764,9 @@ class Runner:
                 if plan.ahead and n + 1 - start >= g:
                     self._forward_rows(start, n, main)  # rows of steps start .. n: on the side stream, beside this step's launches
                     start = n + 1
-                if norm is None:
+                if self._est is not None:  # estimator and actor in ONE launch; the estimate the actor read is kept: the update's rows are these
+                    self.model.sample_actions(obses[n], buf["actions"][n], seed, self._act_counter, est_out=buf["estimates"][n])
+                elif norm is None:
                     self.model.sample_actions(obses[n], buf["actions"][n], seed, self._act_counter, scan=scan, packed=packed)
                 else:  # the buffer keeps the raw rows; the actor samples from their normalised copy (one more launch per step: bg_obs_normalize)
                     self.model.sample_actions(norm.normalize_into(obses[n], self._obs_normed), buf["actions"][n], seed, self._act_counter, scan=scan,
@@ -775,6 +864,8 @@ class Runner:
                 # behind the last optimiser step: this iteration's T x N rows enter the statistics (row T is the next iteration's row 0), under data
                 # parallelism all ranks' rows through ONE float64 exchange (tag "obs_norm", main stream, behind the last "bucket": utils/parallel.py)
                 self.obs_norm.update_from(u.buf["obses"][: u.T], u.buf["privileged_obses"][: u.T], self.dp)
+            if self._est is not None:
+                self._estimator_update(u)  # behind the last PPO optimiser step: the next rollout runs the estimator trained on this iteration's rows
         if K > 1:
             self._mb_updates += 1
         return self._stats_acc
@@ -801,6 +892,9 @@ class Runner:
                 self._critic_in[:, :, no : no + npv].copy_(buf["privileged_obses"])
                 if self._actor_in is not None:
                     self._actor_in[:T, :, :no].copy_(buf["obses"][:T])
+            if self._est is not None and self._actor_in is not None:
+                # the estimate is an observation: the stored rows [obses | estimates[:E] | 0], so old mu and the first ratio come from what the rollout acted on
+                self._actor_in[:T, :, no : no + self._est_cols].copy_(buf["estimates"][..., : self._est_cols])
             if plan.symmetry and self.obs_norm is not None:  # rows [B, 2B): normalise(M_o x), what the policy computes on the mirrored raw observation
                 mirror_rows(buf["obses"][:T].reshape(B, -1), self._mirror_raw, *self._obs_mirror_raw)
                 self.obs_norm.normalize_into(self._mirror_raw, self._actor_in[T:].reshape(B, -1), dst_cols=self._actor_in.shape[-1])
@@ -810,6 +904,8 @@ class Runner:
             obs_flat = self._actor_in.reshape(-1, self._actor_in.shape[-1])
         elif self.obs_norm is not None:  # (no padded input: the per-layer library path reads the normalised rows from a copy of its own)
             obs_flat = self.obs_norm.normalize_into(buf["obses"][:T].reshape(B, -1), torch.empty(B, no, device=self.device))
+        elif self._est is not None:  # (no padded input: the library path reads the concatenated rows from a copy of its own)
+            obs_flat = torch.cat((buf["obses"][:T], buf["estimates"][..., : self._est_cols]), dim=-1).reshape(B, -1)
         else:
             obs_flat = buf["obses"][:T].reshape(B, -1)
         critic_all = self._critic_in.reshape((T + 1) * N, -1)  # rows [B, B+N) = the observation after the last step (last_values)
@@ -1082,8 +1178,12 @@ class Runner:
 
     def _summarize(self, stats_acc):
         """Host-side means of the loss terms over the mini-epochs (runner.py:182-204); one device->host read (blocking: tests and tools)."""
-        s = torch.cat((stats_acc, self._stats_last, self.optimizer.lr.double())).cpu().tolist()
-        return self._summary_from(s)
+        extra = () if self._est is None else (self._est_loss,)  # (read with the same one copy)
+        s = torch.cat((stats_acc, self._stats_last, self.optimizer.lr.double()) + extra).cpu().tolist()
+        out = self._summary_from(s)
+        if self._est is not None:
+            out["estimator/loss"] = s[-1]
+        return out
 
     def _summary_from(self, s):
         T, N = self.cfg["runner"]["horizon_length"], self.env.num_envs
@@ -1107,7 +1207,8 @@ class Runner:
         self.buffer["obses"][0].copy_(obs)
         self.buffer["privileged_obses"][0].copy_(infos["privileged_obs"])
         # (+1 with the terrain curriculum: the sum of this rank's terrain levels)
-        n = 2 * self._n_stats + 1 + 4 + _lib.NUM_REWARD_TERMS + 4 + (1 if self.env.terrain.curriculum else 0)
+        # (+1 with the estimator, last: its loss rides in the iteration's one host read)
+        n = 2 * self._n_stats + 1 + 4 + _lib.NUM_REWARD_TERMS + 4 + (1 if self.env.terrain.curriculum else 0) + (1 if self._est is not None else 0)
         self._log_dev = torch.zeros(n, dtype=torch.float64, device=self.device)
         self._log_host = [torch.zeros(n, dtype=torch.float64).pin_memory() for _ in range(2)]
         self._log_event = [torch.cuda.Event() for _ in range(2)]
@@ -1136,6 +1237,8 @@ class Runner:
             summary["terrain/mean_level"] = s[h + ne + 4] / self.env.num_envs
         if self.obs_norm is not None:
             summary.update(self._log_obs_norm[slot])
+        if self._est is not None:  # the last epoch's SSE / (12 B) of the iteration's estimator update
+            summary["estimator/loss"] = s[-1]
         self.recorder.record_statistics(summary, it)
 
     def train_iteration(self, it):
@@ -1152,7 +1255,9 @@ class Runner:
             ang = self.env.get_field("env_curriculum_level_ang").abs().double()
             d[h + ne : h + ne + 4].copy_(torch.stack((lin.mean(), ang.mean(), lin.max(), ang.max())))
         if self.env.terrain.curriculum:
-            d[h + ne + 4 :].copy_(self.env.terrain_level_sum())
+            d[h + ne + 4 : h + ne + 5].copy_(self.env.terrain_level_sum())
+        if self._est is not None:
+            d[-1:].copy_(self._est_loss)
         self._flush_log()  # the previous iteration's scalars: their copy finished long ago
         slot = it & 1
         self._log_host[slot].copy_(d, non_blocking=True)
@@ -1177,12 +1282,19 @@ class Runner:
         by an optional .npz trajectory dump; `max_steps=None` runs until interrupted like the reference."""
         obs, infos = self.env.reset()
         traj, step = [], 0
+        if self._est is not None:  # the rollout's own launch: its mean is the action; its sample and the estimates go to scratch tensors
+            mean, sampled = (torch.zeros(self.env.num_envs, self.env.num_actions, device=self.device) for _ in range(2))
+            est_scratch = torch.zeros(self.env.num_envs, EST_WIDTH, device=self.device)
         try:
             while max_steps is None or step < max_steps:
                 with torch.no_grad():
                     if self.obs_norm is not None:
                         obs = self.obs_norm.normalize_into(obs, torch.empty_like(obs))
-                    act = self.model.actor(obs)
+                    if self._est is not None:
+                        self.model.sample_actions(obs.contiguous(), sampled, 0, step, mu_out=mean, est_out=est_scratch)
+                        act = mean
+                    else:
+                        act = self.model.actor(obs)
                     obs, rew, done, infos = self.env.step(act)
                 if record_path is not None:
                     traj.append({"root": self.env.root_states[0].cpu().numpy(), "dof_pos": self.env.dof_pos[0].cpu().numpy(), "rew": float(rew[0])})

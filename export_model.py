@@ -9,7 +9,7 @@ import os
 import torch
 
 from booster_gym_amd.utils.config import load_cfg
-from booster_gym_amd.utils.model import ActorCritic, hidden_of
+from booster_gym_amd.utils.model import ActorCritic, EstimatorActor, hidden_of
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
@@ -26,6 +26,16 @@ if __name__ == "__main__":
     # the actor's input from the checkpoint (47, or 47 H with env.frame_stack), and the critic's privileged inputs too (14, or 14 + P with
     # terrain.measure_heights); only the actor is exported
     num_obs = int(sd["actor.0.weight"].shape[1])
+    # estimator.enabled: the actor's row ends with E estimates of a network the checkpoint carries ("estimator.*"); the exported module computes
+    # actor(cat(x, estimator(x)[:, :E])), so the deploy contract stays "47 H floats in, 12 out"
+    est_args = {}
+    if any(k.startswith("estimator.") for k in sd):
+        targets = [int(i) for i in ckpt["estimator"]["targets"]]
+        est_args = {"estimator_hidden": hidden_of(sd, "estimator"), "estimator_cols": len(targets)}
+        num_obs -= len(targets)
+        print("Actor input of {} columns: 47 x {} observations, then {} estimates of the privileged columns {} from the checkpoint's estimator "
+              "(hidden {}); the exported module takes the {} observations and computes the estimates itself".format(
+                  num_obs + len(targets), num_obs // 47, len(targets), targets, list(est_args["estimator_hidden"]), num_obs))
     num_priv = int(sd["critic.0.weight"].shape[1]) - num_obs
     if num_obs % 47:
         # terrain.actor_heights: the actor's row ends with the height scan, whose grid the checkpoint carries
@@ -38,7 +48,7 @@ if __name__ == "__main__":
         print("Actor input of {} columns: 47 x {} observations, then {} heights, grid x {:.3g} .. {:.3g} ({}) by y {:.3g} .. {:.3g} ({}), point p = i * {} + j "
               "at (x_i, y_j) in the robot's yaw frame".format(num_obs, (num_obs - P) // 47, P, xs[0], xs[-1], len(xs), ys[0], ys[-1], len(ys), len(ys)))
     model = ActorCritic(cfg["env"]["num_actions"], num_obs, num_priv, actor_hidden=hidden_of(sd, "actor"),
-                        critic_hidden=hidden_of(sd, "critic"))
+                        critic_hidden=hidden_of(sd, "critic"), **est_args)
     model.load_state_dict(sd)
     if ckpt.get("obs_normalizer") is not None:
         # algorithm.empirical_normalization: the statistics go into the first Linear layer (W' = W diag(inv_std), b' = b - W' mean), so the exported
@@ -55,5 +65,5 @@ if __name__ == "__main__":
         print("Folded the observation normaliser ({} columns, count {:.0f}) into the actor's first layer".format(norm.cols, norm.count))
     os.makedirs("deploy/models", exist_ok=True)
     out = os.path.join("deploy", "models", f"{args.task}.pt")
-    torch.jit.script(model.actor).save(out)
+    torch.jit.script(EstimatorActor(model.actor, model.estimator, model.estimator_cols) if model.has_estimator else model.actor).save(out)
     print("Exported actor to {}".format(out))

@@ -383,6 +383,20 @@ int bg_distill_act_mix(int32_t N, const float* teacher_obs, int32_t teacher_stri
                        const bg_mlp_layer_desc* student, int32_t n_teacher, const bg_mlp_layer_desc* teacher, int32_t scan_points,
                        const float* student_logstd, uint64_t seed, uint64_t counter, float beta, int32_t teacher_noise, float* student_mu, float* actions,
                        float* teacher_mu, void* stream);
+/* The rollout's launch with a learned state estimator in front of the actor (T1.yaml estimator.enabled; the privileged quantities it regresses are
+ * columns of the reference's privileged observation, envs/t1.py:593-602; the actor is utils/model.py:8-25 + dist.sample(), runner.py:109-111): TWO
+ * networks of bg_actor_sample_mlp's kind on the same rows, one behind the other in the same workgroup.  obs [N][47 H] contiguous; est [n_est]: an MLP
+ * 47 H -> hidden -> 12 (est[0].in = 47 H) whose 12 means go to est_out [N][12]; actor [n_actor]: its first layer takes 47 H + est_cols inputs
+ * (1 <= est_cols <= 12; actor[0].in = est[0].in + est_cols <= BG_ACTOR_MAX_INPUT), the row [obs | est_out[:est_cols]] that the workgroup builds in LDS
+ * (no round trip through memory, no copy), and it samples actions [N][12] with bg_actor_sample_mlp's noise (Philox(seed, row, counter, RS_ACTOR + group
+ * of 4 actions)); mu [N][12] may be NULL.  Width rules per network as bg_actor_sample_mlp, the actor's those of scan_points = est_cols; a violation is
+ * -4 or -1 with a message naming the side, before any launch.  One LDS form for both: the 256-wide form when both networks' widest hidden layer is at
+ * most 256 and the actor's padded input tile at most 256 columns.  est_out equals bg_actor_sample_mlp's mu of the estimator on obs, and mu / actions
+ * equal bg_actor_sample_mlp_scan(scan_points = est_cols) of the actor on a contiguous copy of [obs | est_out[:, :est_cols]], bit for bit.  Nothing is
+ * written past row N. */
+int bg_actor_sample_est(int32_t N, const float* obs, int32_t n_est, const bg_mlp_layer_desc* est, int32_t est_cols, int32_t n_actor,
+                        const bg_mlp_layer_desc* actor, const float* logstd, uint64_t seed, uint64_t counter, float* est_out, float* mu, float* actions,
+                        void* stream);
 /* Fused global-norm clip + Adam over one flat parameter buffer (runner.py:162-165); lr is read from device memory
  * so the KL-adaptive schedule (runner.py:174-180) needs no host sync.  gnorm_scratch [1] device float64. */
 int bg_adam_step(int32_t n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const float* lr_device, int32_t step,

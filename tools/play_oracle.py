@@ -29,6 +29,30 @@ def load_actor(path):
     return layers
 
 
+def load_estimator(path):
+    """(layers, E) of the state estimator a checkpoint carries (estimator.enabled: "estimator.*" in its model, the targets under "estimator"), or
+    None: the actor's row is then [observations | the first E outputs of the estimator on the observations]."""
+    if path.endswith(".npz"):
+        return None
+    import torch
+
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    sd = ck["model"]
+    idx = sorted(int(k.split(".")[1]) for k in sd if k.startswith("estimator.") and k.endswith(".weight"))
+    if not idx:
+        return None
+    return [(sd[f"estimator.{i}.weight"].numpy(), sd[f"estimator.{i}.bias"].numpy()) for i in idx], len(ck["estimator"]["targets"])
+
+
+def mlp(layers, x):
+    """An ELU MLP with a linear output layer on one row."""
+    for k, (w, b) in enumerate(layers):
+        x = w @ x + b
+        if k + 1 < len(layers):
+            x = np.where(x > 0, x, np.exp(np.minimum(x, 0)) - 1)
+    return x
+
+
 def normalizer_of(ck):
     """The ObsNormalizer (host only) a checkpoint carries under "obs_normalizer"."""
     from booster_gym_amd.utils.obs_norm import ObsNormalizer
@@ -97,7 +121,7 @@ def gait_frequency(cmd, cfg_commands, max_lin=1.0, max_ang=1.0):
     return lo + min(1.0, mag / max(max_lin, max_ang)) * (hi - lo)
 
 
-def rollout(layers, cmd, seconds, cfg=None, dyn=None, model=None, height_points=None):
+def rollout(layers, cmd, seconds, cfg=None, dyn=None, model=None, height_points=None, estimator=None):
     from booster_gym_amd.utils.config import load_cfg
     from booster_gym_amd.utils.urdf import load_model
     from oracle import task_ref as tr
@@ -117,7 +141,8 @@ def rollout(layers, cmd, seconds, cfg=None, dyn=None, model=None, height_points=
     actions, targets = np.zeros(12), default.copy()
     dec, dt = cfg["control"]["decimation"], cfg["sim"]["dt"]
     P = 0 if height_points is None else len(height_points)  # terrain.actor_heights: the row ends with the newest scan, not stacked
-    stack = FrameStack(actor_frames(layers, scan=P))  # (H = 1: the single observation itself)
+    est_layers, E = estimator if estimator is not None else (None, 0)  # estimator.enabled: E estimates behind the observations
+    stack = FrameStack(actor_frames(layers, scan=P + E))  # (H = 1: the single observation itself)
     traj = []
     for it in range(int(round(seconds / dt))):
         if it % dec == 0:  # play_mujoco.py:733-748
@@ -130,6 +155,8 @@ def rollout(layers, cmd, seconds, cfg=None, dyn=None, model=None, height_points=
             x = stack.push(o)
             if P:
                 x = np.concatenate([x, height_scan(root, height_points, cfg)])
+            if E:
+                x = np.concatenate([x, mlp(est_layers, x)[:E]])
             for k, (w, b) in enumerate(layers):
                 x = w @ x + b
                 if k < 3:
@@ -148,6 +175,6 @@ if __name__ == "__main__":
     ap.add_argument("--cmd", type=float, nargs=3, default=[0.5, 0.0, 0.0])
     ap.add_argument("--seconds", type=float, default=8.0)
     a = ap.parse_args()
-    tr_ = rollout(load_actor(a.policy), a.cmd, a.seconds, height_points=load_height_points(a.policy))
+    tr_ = rollout(load_actor(a.policy), a.cmd, a.seconds, height_points=load_height_points(a.policy), estimator=load_estimator(a.policy))
     up = 1 - 2 * (tr_[-1, 3] ** 2 + tr_[-1, 4] ** 2)
     print(f"cmd {a.cmd}: final pos {np.round(tr_[-1, :3], 3)}, mean velocity {np.round((tr_[-1, :2] - tr_[0, :2]) / a.seconds, 3)}, min height {tr_[:, 2].min():.3f}, upright {up:.3f}")
