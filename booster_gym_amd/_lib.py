@@ -84,6 +84,11 @@ class MlpLayerDesc(C.Structure):
     _fields_ = [("W", C.c_void_p), ("b", C.c_void_p), ("in_", C.c_int32), ("out", C.c_int32)]
 
 
+class GruDesc(C.Structure):
+    """bg_gru_desc: a GRU cell in torch.nn.GRUCell's layout (include/booster_gym_amd.h)."""
+    _fields_ = [("W_ih", C.c_void_p), ("W_hh", C.c_void_p), ("b_ih", C.c_void_p), ("b_hh", C.c_void_p), ("in_", C.c_int32), ("hidden", C.c_int32)]
+
+
 class GatherStream(C.Structure):
     """bg_gather_stream: one row-major fp32 stream of bg_gather_rows (include/booster_gym_amd.h)."""
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("width", C.c_int32), ("pad", C.c_int32)]
@@ -163,6 +168,7 @@ SYMBOLS = [
     "bg_distill_head", "bg_distill_head_partial", "bg_distill_head_sym", "bg_distill_head_sym_partial",
     "bg_obs_moments", "bg_obs_normalize",
     "bg_perm_fill", "bg_gather_rows",
+    "bg_actor_sample_gru", "bg_distill_act_gru", "bg_gru_sequence_forward", "bg_gru_sequence_backward",
     "bg_last_error", "bg_version",
 ]
 
@@ -232,6 +238,11 @@ def load():
         "bg_distill_act_hist": (i32, [i32, vp, i32, vp, i32, i32, C.POINTER(MlpLayerDesc), i32, C.POINTER(MlpLayerDesc), i32, vp, u64, u64, vp, vp, vp, vp]),
         "bg_distill_act_mix": (i32, [i32, vp, i32, vp, i32, i32, C.POINTER(MlpLayerDesc), i32, C.POINTER(MlpLayerDesc), i32, vp, u64, u64, f32, i32, vp, vp, vp, vp]),
         "bg_actor_sample_est": (i32, [i32, vp, i32, C.POINTER(MlpLayerDesc), i32, i32, C.POINTER(MlpLayerDesc), vp, u64, u64, vp, vp, vp, vp]),
+        "bg_actor_sample_gru": (i32, [i32, vp, i32, C.POINTER(GruDesc), i32, C.POINTER(MlpLayerDesc), vp, u64, u64, vp, vp, vp, vp, vp, vp]),
+        "bg_distill_act_gru": (i32, [i32, vp, i32, i32, C.POINTER(MlpLayerDesc), i32, C.POINTER(GruDesc), i32, C.POINTER(MlpLayerDesc), vp, u64, u64, f32, i32,
+                                     vp, vp, vp, vp, vp, vp, vp]),
+        "bg_gru_sequence_forward": (i32, [i32, i32, i32] + [vp] * 9),
+        "bg_gru_sequence_backward": (i32, [i32, i32, i32] + [vp] * 9),
         "bg_adam_step": (i32, [i32, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, vp, vp]),
         "bg_adapt_lr": (i32, [vp, f32, f32, f32, f32, vp, vp]),
         "bg_optimizer_step": (i32, [i32, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, vp, i32, i32, vp, vp, vp, i32, i32, f32, f32, f32, f32, vp, vp, i32, vp]),

@@ -29,11 +29,15 @@
 // envs/t1.py:593-602) runs two networks on the same rows one BEHIND the other in the same workgroup: the estimator 47 H -> hidden -> 12, whose
 // means go to memory, then the actor on the tile [obs | the first E means | zeros] rebuilt in LDS.  Same pieces (load_tile, run_layers, sample), same
 // two LDS tiles: the launch costs about the two stand-alone launches it replaces, without their two boundaries and the concatenation copy.
+//
+// bg_actor_sample_gru and bg_distill_act_gru (a recurrent student, T1.yaml distillation.student_memory; rsl_rl's recurrent `Distillation` student) put
+// a GRU cell in front of the network, on the same 16 rows and the same layer code: gru_rows, below.
 #include <hip/hip_runtime.h>
 
 #include <string>
 
 #include "bg_common.h"
+#include "bg_gru.h"
 #include "bg_rng.h"
 
 namespace {
@@ -53,7 +57,7 @@ __device__ __forceinline__ float elu(float x) { return x > 0.f ? x : expm1f(x); 
 
 // first layer: K = 47 H (+ P) inputs (rows not 16-byte aligned): scalar weight loads, k padded to a multiple of KC with zeros; OUT a multiple of 16.  A wave
 // walks its (tile, k-chunk) steps in one flat loop, the weights of step s + 1 in flight under the 12 MFMAs of step s; with H = 1 one step per tile.
-template <int LDA>
+template <int LDA, int LDO = LDA, bool ACT = true>
 __device__ __forceinline__ void first_layer(const float* __restrict__ W, const float* __restrict__ bv, int K, int OUT, const float* in, float* out,
                                             int wave, int lane) {
     constexpr int STEPS = KC / 4;
@@ -79,7 +83,7 @@ __device__ __forceinline__ void first_layer(const float* __restrict__ W, const f
         for (int s2 = 0; s2 < STEPS; s2++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[4 * s2], cur[s2], acc, 0, 0, 0);
         if (c == cpt - 1) {
 #pragma unroll
-            for (int q = 0; q < 4; q++) out[(kg * 4 + q) * LDA + tile * 16 + r] = elu(acc[q]);
+            for (int q = 0; q < 4; q++) out[(kg * 4 + q) * LDO + tile * 16 + r] = ACT ? elu(acc[q]) : acc[q];
         }
 #pragma unroll
         for (int s2 = 0; s2 < STEPS; s2++) cur[s2] = nxt[s2];
@@ -88,7 +92,7 @@ __device__ __forceinline__ void first_layer(const float* __restrict__ W, const f
 }
 
 // a layer of K inputs (a multiple of 128) and OUT outputs; neurons >= OUT (the 12-wide output layer's last tile) compute zeros that nobody reads
-template <int LDA>
+template <int LDA, int LDO = LDA>
 __device__ __forceinline__ void layer(const float* __restrict__ W, const float* __restrict__ bv, int K, int OUT, bool act, const float* in, float* out,
                                       int wave, int lane) {
     const int r = lane & 15, kg = lane >> 4, tiles = (OUT + 15) / 16, cpt = K >> 7;
@@ -129,7 +133,7 @@ __device__ __forceinline__ void layer(const float* __restrict__ W, const float* 
         if (c == cpt - 1) {
             const f32x4 v = acc0 + acc1;
 #pragma unroll
-            for (int q = 0; q < 4; q++) out[(kg * 4 + q) * LDA + tile * 16 + r] = act ? elu(v[q]) : v[q];
+            for (int q = 0; q < 4; q++) out[(kg * 4 + q) * LDO + tile * 16 + r] = act ? elu(v[q]) : v[q];
         }
 #pragma unroll
         for (int u = 0; u < 8; u++) cur[u] = nxt[u];
@@ -278,11 +282,102 @@ __global__ __launch_bounds__(256) void distill_act_mix_kernel(int N, int nb, con
                            act_out, teacher, beta, teacher_noise);
 }
 
+// ---- a recurrent student (distillation.student_memory, torch.nn.GRUCell(47, H) in front of the trunk): bg_actor_sample_gru, bg_distill_act_gru.
+// The same 16 rows per workgroup and the same pieces: the x-side gate pre-activations gi = x W_ih^T + b_ih [16][3H] are first_layer's scalar-load form
+// without the ELU on the 48-column tile of the newest observation, the h-side gh = h W_hh^T + b_hh [16][3H] are layer's form on the LDS tile of h, the
+// gate arithmetic (bg_gru.h) runs on the two tiles, h' goes to memory and, in place of h, is the input tile of the trunk, whose every layer is
+// `layer` (its first takes H inputs, a multiple of 128).  LDS: gi | gh | h | x; the trunk's two activation tiles lie over gi once the gates are done.
+//   floats: max(16 (3H + 4), 2 x 16 (MAXW + 4)) + 16 (3H + 4) + 16 (H + 4) + 16 x 52
+//   H = 128: 68 kB (MAXW = 256), 100 kB (512); H = 256: 116 kB (256), 132 kB (512), of the CU's 160 kB: one workgroup per CU at H = 256, two at 128
+//   with MAXW = 256.
+struct GruCell { const float *W_ih, *W_hh, *b_ih, *b_hh; };
+
+template <int H, int MAXW>
+struct GruLds {
+    static constexpr int LDA = MAXW + 4, LDG = 3 * H + 4, LDH = H + 4, LDX = KC + 4;  // row strides (floats), multiples of 4; the three wide ones = 4 mod 32 banks
+    static constexpr int TRUNK = 2 * MR * LDA, GI = MR * LDG;
+    static constexpr int A = GI > TRUNK ? GI : TRUNK, B = MR * LDG, HT = MR * LDH, X = MR * LDX;
+    static constexpr int FLOATS = A + B + HT + X;
+};
+
+// One workgroup's 16 rows through the cell and the trunk.  h_in and h_out may be the same buffer: the rows are read here, in front of the first barrier,
+// and written behind the second, and no other workgroup touches them.  reset (may be nullptr): a row with a non-zero entry reads h_in as zero.
+template <int H, int MAXW, bool MIX>
+__device__ __forceinline__ void gru_rows(float* lds, int N, int r0, const float* __restrict__ obs, int stride, const GruCell& cell, const ActorNet& net,
+                                         const float* __restrict__ logstd, uint64_t seed, uint32_t counter, const uint8_t* __restrict__ reset, const float* h_in,
+                                         float* h_out, float* __restrict__ mu_out, float* __restrict__ act_out, float beta, int teacher_noise) {
+    using L = GruLds<H, MAXW>;
+    float *gi = lds, *gh = lds + L::A, *ht = gh + L::B, *xt = ht + L::HT;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int k = threadIdx.x; k < MR * KC; k += blockDim.x) {
+        const int r = k / KC, c = k - r * KC;
+        xt[r * L::LDX + c] = (r0 + r < N && c < BG_NUM_OBS) ? obs[(size_t)(r0 + r) * stride + c] : 0.f;
+    }
+    for (int k = threadIdx.x; k < MR * H; k += blockDim.x) {
+        const int r = k / H, c = k - r * H, row = r0 + r;
+        float v = 0.f;
+        if (row < N && !(reset && reset[row])) v = h_in[(size_t)row * H + c];
+        ht[r * L::LDH + c] = v;
+    }
+    __syncthreads();
+    first_layer<L::LDX, L::LDG, false>(cell.W_ih, cell.b_ih, BG_NUM_OBS, 3 * H, xt, gi, wave, lane);
+    layer<L::LDH, L::LDG>(cell.W_hh, cell.b_hh, H, 3 * H, false, ht, gh, wave, lane);
+    __syncthreads();
+    for (int k = threadIdx.x; k < MR * H; k += blockDim.x) {
+        const int r = k / H, c = k - r * H, row = r0 + r;
+        const float *a = gi + r * L::LDG + c, *b = gh + r * L::LDG + c;
+        const bg::GruGates g = bg::gru_gates(a[0], a[H], a[2 * H], b[0], b[H], b[2 * H], ht[r * L::LDH + c]);
+        ht[r * L::LDH + c] = g.h;
+        if (row < N) h_out[(size_t)row * H + c] = g.h;
+    }
+    __syncthreads();
+    float(*buf)[MR * L::LDA] = reinterpret_cast<float(*)[MR * L::LDA]>(lds);  // (over gi, which nobody reads any more)
+    layer<L::LDH, L::LDA>(net.W[0], net.b[0], H, net.out[0], true, ht, buf[0], wave, lane);
+    __syncthreads();
+    int cur = 0;
+    for (int l = 1; l < net.n; l++) {
+        layer<L::LDA>(net.W[l], net.b[l], net.in[l], net.out[l], l + 1 < net.n, buf[cur], buf[cur ^ 1], wave, lane);
+        __syncthreads();
+        cur ^= 1;
+    }
+    sample<L::LDA, MIX>(buf[cur], N, r0, logstd, seed, counter, mu_out, act_out, false, beta, teacher_noise);
+}
+
+template <int H, int MAXW>
+__global__ __launch_bounds__(256) void actor_gru_sample_kernel(int N, const float* __restrict__ obs, int stride, GruCell cell, ActorNet net,
+                                                               const float* __restrict__ logstd, uint64_t seed, uint32_t counter, const uint8_t* __restrict__ reset,
+                                                               const float* h_in, float* h_out, float* __restrict__ mu_out, float* __restrict__ act_out) {
+    __shared__ __attribute__((aligned(16))) float lds[GruLds<H, MAXW>::FLOATS];
+    gru_rows<H, MAXW, false>(lds, N, blockIdx.x * MR, obs, stride, cell, net, logstd, seed, counter, reset, h_in, h_out, mu_out, act_out, 0.f, 0);
+}
+
+// bg_distill_act_gru: distill_act_mix_kernel's split grid (MIX = false: distill_act_kernel's) with the recurrent student in the second half.  The
+// teacher's half is actor_rows' sequence of pieces on the front of the same LDS block.
+template <int H, int MAXW, bool MIX>
+__global__ __launch_bounds__(256) void distill_act_gru_kernel(int N, int nb, const float* __restrict__ obs, int stride, DistillNets nets, GruCell cell,
+                                                              const float* __restrict__ logstd, uint64_t seed, uint32_t counter, float beta, int teacher_noise,
+                                                              const uint8_t* __restrict__ reset, const float* h_in, float* h_out, float* __restrict__ student_mu,
+                                                              float* __restrict__ act_out, float* __restrict__ teacher_mu) {
+    using L = GruLds<H, MAXW>;
+    __shared__ __attribute__((aligned(16))) float lds[L::FLOATS];
+    if ((int)blockIdx.x < nb) {
+        const int r0 = blockIdx.x * MR;
+        float(*buf)[MR * L::LDA] = reinterpret_cast<float(*)[MR * L::LDA]>(lds);
+        load_tile<L::LDA>(buf[0], N, r0, obs, stride, nets.n[0].in[0], nullptr, nets.n[0].in[0]);
+        const int cur = run_layers<L::LDA>(nets.n[0], buf, 0);
+        sample<L::LDA, MIX>(buf[cur], N, r0, logstd, seed, counter, teacher_mu, MIX ? act_out : nullptr, true, beta, teacher_noise);
+    } else {
+        gru_rows<H, MAXW, MIX>(lds, N, (blockIdx.x - nb) * MR, obs, stride, cell, nets.n[1], logstd, seed, counter, reset, h_in, h_out, student_mu, act_out, beta,
+                               teacher_noise);
+    }
+}
+
 }  // namespace
 
 // The descriptors of one network -> ActorNet, with the width rules of the kernel; scan: the height-scan values behind the 47 H observations of a row
 // (bg_env_cfg.actor_heights), 0 without them.  maxw: the widest hidden layer.  `who` heads the error messages.
-static int fill_net(const char* who, int32_t n_layers, const bg_mlp_layer_desc* layers, int32_t scan, ActorNet& net, int& maxw) {
+// first_in > 0: the trunk behind a GRU cell, whose first layer takes the first_in = H values of the hidden state (a 16-byte aligned matrix as the others).
+static int fill_net(const char* who, int32_t n_layers, const bg_mlp_layer_desc* layers, int32_t scan, ActorNet& net, int& maxw, int32_t first_in = 0) {
     const std::string w(who);
     if (n_layers < 3 || n_layers > MAX_LAYERS) return bg_set_error(-4, (w + ": 2 to 4 hidden layers (n_layers 3 to 5)").c_str());
     net = ActorNet{};
@@ -292,13 +387,13 @@ static int fill_net(const char* who, int32_t n_layers, const bg_mlp_layer_desc* 
         const bg_mlp_layer_desc& d = layers[l];
         if (!d.W || !d.b) return bg_set_error(-1, (w + ": bad argument (layer weights)").c_str());
         const bool last = l + 1 == n_layers;
-        if (l == 0 ? (d.in - scan < BG_NUM_OBS || d.in - scan > BG_NUM_OBS * BG_MAX_FRAME_STACK || (d.in - scan) % BG_NUM_OBS != 0 || d.in > BG_ACTOR_MAX_INPUT)
+        if (l == 0 && first_in ? d.in != first_in : l == 0 ? (d.in - scan < BG_NUM_OBS || d.in - scan > BG_NUM_OBS * BG_MAX_FRAME_STACK || (d.in - scan) % BG_NUM_OBS != 0 || d.in > BG_ACTOR_MAX_INPUT)
                    : d.in != layers[l - 1].out)
             return bg_set_error(-4, (w + ": layer widths do not chain (first layer: 47 H inputs, H = 1 .. 10 observation frames, and the "
                                          "height scan's points behind them, BG_ACTOR_MAX_INPUT at most)").c_str());
         if (last ? d.out != BG_NUM_DOFS : (d.out % 128 != 0 || d.out < 128 || d.out > 512))
             return bg_set_error(-4, (w + ": unsupported widths (hidden: multiples of 128 up to 512; output: 12)").c_str());
-        if (l > 0 && ((uintptr_t)d.W & 15)) return bg_set_error(-1, (w + ": weight matrices after the first must be 16-byte aligned").c_str());
+        if ((l > 0 || first_in) && ((uintptr_t)d.W & 15)) return bg_set_error(-1, (w + ": weight matrices after the first must be 16-byte aligned").c_str());
         net.W[l] = d.W; net.b[l] = d.b; net.in[l] = d.in; net.out[l] = d.out;
         if (!last && d.out > maxw) maxw = d.out;
     }
@@ -427,4 +522,77 @@ extern "C" int bg_distill_act_mix(int32_t N, const float* teacher_obs, int32_t t
                                   float* actions, float* teacher_mu, void* stream) {
     return distill_act(DA_MIX, beta, teacher_noise, N, teacher_obs, teacher_stride, student_obs, student_stride, n_student, student, n_teacher, teacher, scan_points,
                        student_logstd, seed, counter, student_mu, actions, teacher_mu, stream);
+}
+
+// ---- the recurrent student's entry points
+static int fill_cell(const std::string& who, const bg_gru_desc* gru, GruCell& cell) {
+    if (!gru || !gru->W_ih || !gru->W_hh || !gru->b_ih || !gru->b_hh) return bg_set_error(-1, (who + ": bad argument (gru)").c_str());
+    if (gru->in != BG_NUM_OBS) return bg_set_error(-4, (who + ": the cell takes one observation (gru.in = 47)").c_str());
+    if (gru->hidden != 128 && gru->hidden != 256) return bg_set_error(-4, (who + ": unsupported gru.hidden (128 or 256)").c_str());
+    if ((uintptr_t)gru->W_hh & 15) return bg_set_error(-1, (who + ": gru.W_hh must be 16-byte aligned").c_str());
+    cell = GruCell{gru->W_ih, gru->W_hh, gru->b_ih, gru->b_hh};
+    return 0;
+}
+
+// the kernel template K at the cell's width and the LDS form `wide` (MAXW = 512) names
+#define BG_GRU_LAUNCH(K, TAIL, ...)                                                                                  \
+    do {                                                                                                             \
+        if (H == 128 && !wide) hipLaunchKernelGGL((K<128, 256 TAIL>), grid, block, 0, st, __VA_ARGS__);             \
+        else if (H == 128) hipLaunchKernelGGL((K<128, 512 TAIL>), grid, block, 0, st, __VA_ARGS__);                 \
+        else if (!wide) hipLaunchKernelGGL((K<256, 256 TAIL>), grid, block, 0, st, __VA_ARGS__);                    \
+        else hipLaunchKernelGGL((K<256, 512 TAIL>), grid, block, 0, st, __VA_ARGS__);                               \
+    } while (0)
+#define BG_COMMA ,
+
+extern "C" int bg_actor_sample_gru(int32_t N, const float* obs, int32_t obs_stride, const bg_gru_desc* gru, int32_t n_layers, const bg_mlp_layer_desc* layers,
+                                   const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, float* mu,
+                                   float* actions, void* stream) {
+    const std::string who("bg_actor_sample_gru");
+    if (N <= 0 || !obs || !layers || !logstd || !h_in || !h_out || !actions) return bg_set_error(-1, (who + ": bad argument").c_str());
+    if (obs_stride < BG_NUM_OBS) return bg_set_error(-1, (who + ": bad argument (obs_stride: at least the 47 columns the cell reads)").c_str());
+    GruCell cell;
+    if (const int rc = fill_cell(who, gru, cell)) return rc;
+    ActorNet net;
+    int maxw = 0;
+    if (const int rc = fill_net((who + " (trunk)").c_str(), n_layers, layers, 0, net, maxw, gru->hidden)) return rc;
+    const int H = gru->hidden;
+    const bool wide = maxw > 256;
+    const dim3 grid((N + MR - 1) / MR), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    BG_GRU_LAUNCH(actor_gru_sample_kernel, , N, obs, obs_stride, cell, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, mu, actions);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int bg_distill_act_gru(int32_t N, const float* teacher_obs, int32_t teacher_stride, int32_t n_teacher, const bg_mlp_layer_desc* teacher,
+                                  int32_t scan_points, const bg_gru_desc* gru, int32_t n_student, const bg_mlp_layer_desc* student, const float* student_logstd,
+                                  uint64_t seed, uint64_t counter, float beta, int32_t teacher_noise, const uint8_t* reset, const float* h_in, float* h_out,
+                                  float* student_mu, float* actions, float* teacher_mu, void* stream) {
+    const std::string who("bg_distill_act_gru");
+    if (!(beta >= 0.f && beta <= 1.f))  // (a NaN fails both comparisons)
+        return bg_set_error(-1, (who + ": bad argument (beta: the teacher's probability of acting, a finite number in [0, 1])").c_str());
+    if (N <= 0 || !teacher_obs || !student || !teacher || !student_logstd || !h_in || !h_out || !actions || !teacher_mu)
+        return bg_set_error(-1, (who + ": bad argument").c_str());
+    if (scan_points < 0 || scan_points > BG_MAX_HEIGHT_SCAN_POINTS) return bg_set_error(-1, (who + ": bad argument (scan_points)").c_str());
+    GruCell cell;
+    if (const int rc = fill_cell(who, gru, cell)) return rc;
+    DistillNets nets;
+    int maxw_t = 0, maxw_s = 0;
+    if (const int rc = fill_net((who + " (teacher)").c_str(), n_teacher, teacher, scan_points, nets.n[0], maxw_t)) return rc;
+    if (const int rc = fill_net((who + " (student)").c_str(), n_student, student, 0, nets.n[1], maxw_s, gru->hidden)) return rc;
+    if (teacher_stride != teacher[0].in)
+        return bg_set_error(-4, (who + ": teacher_stride must equal the teacher's first-layer input (47 H + scan_points columns per row)").c_str());
+    const int H = gru->hidden, nb = (N + MR - 1) / MR;
+    const int kp = (teacher[0].in + KC - 1) / KC * KC, maxw = maxw_t > maxw_s ? maxw_t : maxw_s;
+    const bool wide = maxw > 256 || kp > 256;
+    const dim3 grid(2 * nb), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (beta > 0.f)
+        BG_GRU_LAUNCH(distill_act_gru_kernel, BG_COMMA true, N, nb, teacher_obs, teacher_stride, nets, cell, student_logstd, seed, (uint32_t)counter, beta, teacher_noise,
+                      reset, h_in, h_out, student_mu, actions, teacher_mu);
+    else
+        BG_GRU_LAUNCH(distill_act_gru_kernel, BG_COMMA false, N, nb, teacher_obs, teacher_stride, nets, cell, student_logstd, seed, (uint32_t)counter, beta, teacher_noise,
+                      reset, h_in, h_out, student_mu, actions, teacher_mu);
+    HIP_OK(hipGetLastError());
+    return 0;
 }

@@ -31,6 +31,13 @@ probability beta_i = beta_0 max(0, 1 - i / teacher_action_iterations) (teacher_a
 launch is bg_distill_act_mix, on the same buffers.  teacher_action_noise: a teacher-driven step carries the student's exploration noise (the very
 draw the student would have used), false: the teacher's mean alone.  The update is untouched: labels are the teacher's mean on every visited row,
 whoever drove.  With both keys at their defaults every launch, random stream, buffer, log name and checkpoint key is what it is without them.
+
+distillation.student_memory: H = 128 or 256 makes the student recurrent (rsl_rl's recurrent student): `memory`, a torch.nn.GRUCell(47, H), reads the
+newest single observation (columns [0, 47) of the teacher's row) and the actor's MLP reads its new state h' instead of the observation.  The state
+[N][H] is zero at begin(), advances in every env step whoever drives (bg_distill_act_gru, in place; an env the step before reset enters with h = 0,
+the frame stack's rule) and carries across iterations; the update back-propagates through the iteration's T steps from the state h0 stored at its
+start (the gradient is truncated there): model.GRUTrainer around the trunk's MLPTrainer.  The optimiser holds memory.* and actor.*; the checkpoint
+carries memory.* and re-enters under algorithm.actor_memory: H.  0 (the default, also absent): everything above, unchanged.
 """
 import argparse
 import ctypes
@@ -49,7 +56,7 @@ from ..envs.t1 import MAX_CRITIC_INPUT, MAX_FRAME_STACK, frame_stack_of
 from .buffer import ExperienceBuffer
 from .config import load_cfg
 from .estimator import estimator_enabled
-from .model import CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, MLPTrainer, WeightClock, check_hidden, hidden_of, plan_network
+from .model import CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, GRUTrainer, MLPTrainer, WeightClock, check_hidden, hidden_of, plan_network
 from .recorder import Recorder
 from .runner import FlatAdam, hidden_widths, pad_input, wgrad_products
 from .terrain import actor_heights_of, height_scan_points
@@ -57,7 +64,8 @@ from .utils import head_scratch, mirror_rows, reduce_group
 
 DEFAULTS = {"teacher_checkpoint": None, "student_hidden": [256, 128, 128], "num_epochs": 5, "learning_rate": 1.0e-3, "max_grad_norm": 1.0,
             "student_noise_std": 0.1, "student_frame_stack": None, "symmetric_coef": 0.0, "teacher_action_prob": 0.0, "teacher_action_iterations": 0,
-            "teacher_action_noise": True}
+            "teacher_action_noise": True, "student_memory": 0}
+STUDENT_MEMORY = (0, 128, 256)  # the widths of the recurrent student's cell the kernels take (0: no memory)
 
 
 class DistillCfg(NamedTuple):
@@ -91,6 +99,7 @@ def distillation_cfg(cfg, world_size=1):
                          "the Distiller does not train): set estimator.enabled to false")
     if int(world_size) != 1:
         raise ValueError(f"distillation runs on one rank (WORLD_SIZE = {world_size}): data parallelism is out of scope")
+    student_memory_of(cfg)  # (ValueError naming the key: its value, and what a recurrent student excludes)
     v = dict(DEFAULTS, **sec)
     ck = v["teacher_checkpoint"]
     if ck is not None and not isinstance(ck, str):
@@ -148,6 +157,29 @@ def symmetric_coef_of(cfg):
     return float(c)
 
 
+def student_memory_of(cfg):
+    """distillation.student_memory as the width H of the recurrent student's GRU cell: 0 (the default, also absent) = a memoryless student.  Pure.
+    ValueError naming the key unless it is one of STUDENT_MEMORY, and with H > 0 unless env.frame_stack is 1, distillation.student_frame_stack is
+    not above the teacher's and distillation.symmetric_coef is 0: the cell reads one observation, and the mirror image of a hidden state is not defined."""
+    H = _key(cfg, "student_memory")
+    if isinstance(H, bool) or not isinstance(H, int) or H not in STUDENT_MEMORY:
+        raise ValueError(f"distillation.student_memory must be one of {', '.join(map(str, STUDENT_MEMORY))} (the width of the student's GRU cell; 0: a "
+                         f"memoryless student), got {H!r}")
+    if H == 0:
+        return 0
+    fs = frame_stack_of(cfg)
+    if fs != 1:
+        raise ValueError(f"distillation.student_memory = {H} needs env.frame_stack: 1 (got {fs}): the cell reads the newest single observation; a frame "
+                         "stack in front of it is not supported for now")
+    if student_frame_stack_of(cfg) > fs:
+        raise ValueError(f"distillation.student_memory = {H} is not supported with distillation.student_frame_stack above the teacher's env.frame_stack "
+                         "for now: the memory is the student's history")
+    if symmetric_coef_of(cfg) > 0:
+        raise ValueError(f"distillation.student_memory = {H} is not supported with distillation.symmetric_coef > 0: the mirror image of a hidden state "
+                         "is not defined")
+    return H
+
+
 def teacher_action_of(cfg):
     """(beta_0, iterations, noise) of DAgger's mixing: distillation.teacher_action_prob in [0, 1] (0, the default: the student always acts),
     teacher_action_iterations (an integer >= 0: beta reaches 0 after that many iterations, 0 = constant) and teacher_action_noise (a bool).  Pure.
@@ -173,7 +205,7 @@ def student_mirror_maps(dof_names, dof_axes, default_dof_pos, frames):
     return mirror_maps(dof_names, dof_axes, default_dof_pos, _lib.NUM_OBS * int(frames), int(frames), None)
 
 
-def student_overrides(num_observations, student_frame_stack=None):
+def student_overrides(num_observations, student_frame_stack=None, student_memory=None):
     """The rule under which a student re-enters Runner / play.py / export_model.py / evaluate.py, written once: the teacher's config without the
     actor's scan, the student's own history when it has one, and the row its actor takes.  student_cfg_overrides derives the arguments from the
     teacher's config, checkpoint_student_overrides from a student checkpoint."""
@@ -181,6 +213,8 @@ def student_overrides(num_observations, student_frame_stack=None):
     if student_frame_stack is not None:
         over["env.frame_stack"] = int(student_frame_stack)
     over["env.num_observations"] = int(num_observations)
+    if student_memory:  # a recurrent student: Runner(test=True) builds its actor behind a GRU cell of that width
+        over["algorithm.actor_memory"] = int(student_memory)
     return over
 
 
@@ -192,7 +226,7 @@ def student_cfg_overrides(cfg):
         Hs = student_frame_stack_of(cfg)
         if Hs > H:
             return student_overrides(_lib.NUM_OBS * Hs, Hs)
-    return student_overrides(_lib.NUM_OBS * H)
+    return student_overrides(_lib.NUM_OBS * H, None, student_memory_of(cfg) if isinstance(cfg.get("distillation"), dict) else None)
 
 
 def checkpoint_student_overrides(checkpoint):
@@ -201,7 +235,10 @@ def checkpoint_student_overrides(checkpoint):
     entry = checkpoint.get("distillation")
     if entry is None:
         return None
-    return student_overrides(int(checkpoint["model"]["actor.0.weight"].shape[1]), entry.get("student_frame_stack"))
+    sd = checkpoint["model"]
+    if "memory.weight_ih" in sd:  # a recurrent student: the row is what its cell reads, the actor takes the cell's state
+        return student_overrides(int(sd["memory.weight_ih"].shape[1]), entry.get("student_frame_stack"), int(sd["memory.weight_hh"].shape[1]))
+    return student_overrides(int(sd["actor.0.weight"].shape[1]), entry.get("student_frame_stack"))
 
 
 class Distiller:
@@ -219,7 +256,7 @@ class Distiller:
                 cfg.setdefault("distillation", {})
                 if isinstance(cfg["distillation"], dict):
                     cfg["distillation"]["teacher_checkpoint"] = self.args.teacher
-            for arg in ("student_frame_stack", "symmetric_coef", "teacher_action_prob", "teacher_action_iterations"):
+            for arg in ("student_frame_stack", "symmetric_coef", "teacher_action_prob", "teacher_action_iterations", "student_memory"):
                 if getattr(self.args, arg) is not None:
                     cfg.setdefault("distillation", {})
                     if isinstance(cfg["distillation"], dict):
@@ -232,6 +269,7 @@ class Distiller:
             raise ValueError("distillation.teacher_checkpoint is not set: the path of a checkpoint trained with terrain.actor_heights (distill.py --teacher=PATH)")
         self.symmetric_coef = symmetric_coef_of(cfg)
         self.beta0, self.beta_iterations, self.teacher_noise = teacher_action_of(cfg)
+        self.memory = student_memory_of(cfg)  # the width of the recurrent student's GRU cell; 0: none
         Hs, H = student_frame_stack_of(cfg), frame_stack_of(cfg)
         self.history = Hs > H  # the student's own, longer history: a second row of the env, bg_distill_act_hist
         if self.history:
@@ -250,12 +288,14 @@ class Distiller:
             self.student_obs = env.num_student_obs  # 47 Hs columns of a row of their own
         self.teacher = self._load_teacher(self.dcfg.teacher_checkpoint)
         A = env.num_actions
-        self.student = ActorCritic(A, self.student_obs, env.num_privileged_obs, self.dcfg.student_hidden, critic_hidden).to(dev)
+        self.student = ActorCritic(A, self.student_obs, env.num_privileged_obs, self.dcfg.student_hidden, critic_hidden,
+                                   **({"memory_hidden": self.memory} if self.memory else {})).to(dev)
         with torch.no_grad():
             self.student.logstd.fill_(math.log(self.dcfg.student_noise_std))
         self.student.logstd.requires_grad_(False)  # fixed exploration noise of the data-collecting student; not trained
         # only the student's actor is trained: the critic and logstd keep their storage outside the flat Adam buffer
-        self.optimizer = FlatAdam(self.student.actor.parameters(), lr=self.dcfg.learning_rate, max_grad_norm=self.dcfg.max_grad_norm)
+        trained = (list(self.student.memory.parameters()) if self.memory else []) + list(self.student.actor.parameters())
+        self.optimizer = FlatAdam(trained, lr=self.dcfg.learning_rate, max_grad_norm=self.dcfg.max_grad_norm)
 
         T, N = int(cfg["runner"]["horizon_length"]), env.num_envs
         self.T, self.N, self.B = T, N, T * N
@@ -282,13 +322,23 @@ class Distiller:
         self._trainer = tr = MLPTrainer(self.student.actor, clock=self._clock)
         widths = (tr.layers[0].in_features,) + tuple(l.out_features for l in tr.layers)
         sw = MLPTrainer
-        tr.plan = plan = plan_network(widths, kin, rows, sw.SPLIT, sw.FUSED, sw.CHAIN, sw.CHAIN_SPLIT, sw.CHAIN_SPLIT_BWD, sw.CHAIN_ALTERNATE, sw.FUSED_WGRAD)
+        if self.memory:  # the trunk's input is the cell's state [B][H]: the per-layer fp32 kernels (the chains take a 64-column input only)
+            tr.plan = plan = plan_network(widths, self.memory, rows, 0, True, False, False, False, False, True)
+        else:
+            tr.plan = plan = plan_network(widths, kin, rows, sw.SPLIT, sw.FUSED, sw.CHAIN, sw.CHAIN_SPLIT, sw.CHAIN_SPLIT_BWD, sw.CHAIN_ALTERNATE, sw.FUSED_WGRAD)
         if "library" in (plan.fwd, plan.bwd) or not all(plan.grouped[:-1]):
             raise ValueError(f"distillation: a batch of runner.horizon_length x env.num_envs = {T} x {N} = {self.B} rows is outside the range of the layer "
                              "kernels (an even number of 64 rows or more)")
         shapes = [(co, ci) for ci, co in zip((kin,) + widths[1:-2], widths[1:-1])]
         # the products of the grouped weight-gradient launch, by runner.plan_update's rule: the bf16 splits behind the chained split backward only
-        self._wgrad_terms = wgrad_products(rows, shapes, plan.bwd == "chain_split", sw.SPLIT, sw.WGRAD_SPLIT)
+        self._wgrad_terms = 0 if self.memory else wgrad_products(rows, shapes, plan.bwd == "chain_split", sw.SPLIT, sw.WGRAD_SPLIT)
+        if self.memory:
+            # the cell around the trunk (model.GRUTrainer), its rollout state [N][H] (advanced in place by bg_distill_act_gru, zero at begin()) and the
+            # done flags of the previous iteration's last step: the resets of this iteration's step 0
+            self._memory_trainer = GRUTrainer(self.student.memory, tr, T, N, clock=self._clock)
+            self.state = torch.zeros(N, self.memory, device=dev)
+            self._last_dones = torch.zeros(N, dtype=torch.uint8, device=dev)
+            self._gru_desc = (None, None)
         self._wgrad = GroupedWeightGrad()
         self._head_scratch = head_scratch(dev)
         self._stats = torch.zeros(2 if self.symmetry else 1, dtype=torch.float64, device=dev)  # squared errors (, squared mean asymmetries)
@@ -310,6 +360,8 @@ class Distiller:
                             "Overrides distillation.teacher_action_prob.")
         parser.add_argument("--teacher_action_iterations", type=int, help="Iterations over which that probability falls to 0 (0: constant). "
                             "Overrides distillation.teacher_action_iterations.")
+        parser.add_argument("--student_memory", type=int, help="Width of the recurrent student's GRU cell (128 or 256; 0: a memoryless student). "
+                            "Overrides distillation.student_memory.")
         parser.add_argument("--max_iterations", type=int, help="Number of distillation iterations. Overrides config file if provided.")
         parser.add_argument("--num_envs", type=int, help="Number of environments to create. Overrides config file if provided.")
         parser.add_argument("--sim_device", type=str, help="Device for physics simulation. Overrides config file if provided.")
@@ -373,6 +425,8 @@ class Distiller:
             d["distillation"]["symmetric_coef"] = self.symmetric_coef
         if self.beta0 > 0:
             d["distillation"]["teacher_action_prob"] = [self.beta0, self.beta_iterations]
+        if self.memory:
+            d["distillation"]["student_memory"] = self.memory
         if self.env.terrain.curriculum:
             d["terrain_levels"] = self.env.terrain_levels
         return d
@@ -400,6 +454,8 @@ class Distiller:
         seed = int(self.cfg["basic"]["seed"]) + 1000003  # (Runner's rollout seed of rank 0)
         sd, td = self._descriptors()
         lib, logstd = _lib.load(), self.student.logstd
+        if self.memory:
+            return self._rollout_memory(sd, td, seed)
         if self.beta0 > 0:  # DAgger's mixing: one launch of its own kind on the same buffers, the student's rows its own with a longer history
             beta, noise = self.teacher_action_prob(), int(self.teacher_noise)
             sobs = buf["student_obses"] if self.history else obses
@@ -429,6 +485,31 @@ class Distiller:
                 self._act_counter += 1
                 self.env.step_to(actions[n], obses[n + 1], priv[n + 1], buf["rewards"][n], buf["dones"][n], buf["time_outs"][n])
 
+    def _rollout_memory(self, sd, td, seed):
+        """rollout() of a recurrent student: one launch per env step, bg_distill_act_gru, which also advances the state in place; an env that the
+        step before reset enters with a zero state (dones[n - 1]; at step 0 the previous iteration's last flags).  beta = 0 is the plain form."""
+        buf, T, N, tr = self.buffer, self.T, self.N, self._memory_trainer
+        obses, priv, actions, labels, dones = buf["obses"], buf["privileged_obses"], buf["actions"], buf["teacher_mu"], buf["dones"]
+        m = self.student.memory
+        key = tuple(t.data_ptr() for t in (m.weight_ih, m.weight_hh, m.bias_ih, m.bias_hh))
+        if key != self._gru_desc[0]:
+            self._gru_desc = (key, self.student.gru_descriptor())
+        gd, lib, logstd, h = self._gru_desc[1], _lib.load(), self.student.logstd, self.state
+        beta, noise = self.teacher_action_prob(), int(self.teacher_noise)
+        with torch.no_grad():
+            tr.h0.copy_(h)  # the state the update's recurrence starts from
+            tr.resets[0].copy_(self._last_dones)
+            for n in range(T):
+                reset = self._last_dones if n == 0 else dones[n - 1]
+                _lib.check(lib.bg_distill_act_gru(N, _lib.ptr(obses[n]), obses.shape[-1], len(td), td, self.scan, gd, len(sd), sd, _lib.ptr(logstd), seed,
+                                                  self._act_counter, beta, noise, _lib.ptr(reset), _lib.ptr(h), _lib.ptr(h), None, _lib.ptr(actions[n]),
+                                                  _lib.ptr(labels[n]), _lib.current_stream_ptr()), "bg_distill_act_gru")
+                self._act_counter += 1
+                self.env.step_to(actions[n], obses[n + 1], priv[n + 1], buf["rewards"][n], dones[n], buf["time_outs"][n])
+            if T > 1:
+                tr.resets[1:].copy_(dones[: T - 1])
+            self._last_dones.copy_(dones[T - 1])
+
     def update(self):
         """num_epochs full-batch behaviour-cloning steps on the rollout's rows.  Returns the per-epoch mean losses (float64 device tensor: the loss
         each step's gradient was taken of); with distillation.symmetric_coef the per-epoch mean squared asymmetries are left in symmetry_losses."""
@@ -440,8 +521,9 @@ class Distiller:
             self._student_in[:B, : self.student_obs].copy_(rows[:, : self.student_obs])
             if self.symmetry:  # rows [B, 2B): the mirror images M_o x of the batch (the padded columns stay zero)
                 mirror_rows(self._student_in[:B], self._student_in[B:], *self._obs_mirror)
+            mt = self._memory_trainer if self.memory else None
             for e in range(self.dcfg.num_epochs):
-                h = tr.forward_hidden(self._student_in)
+                h = tr.forward_hidden(self._student_in if mt is None else mt.forward(self._student_in))
                 self._stats.zero_()
                 fin, fins = _lib.ReduceProblem(), []
                 if self.symmetry:
@@ -455,7 +537,9 @@ class Distiller:
                                                                    _lib.ptr(self._stats), _lib.ptr(self._head_scratch), fin, _lib.current_stream_ptr()),
                                "bg_distill_head_partial")
                 tr.backward_hidden(finishes=fins)
-                self._wgrad.run((tr,), self._wgrad_terms, False)
+                if mt is not None:
+                    mt.backward()
+                self._wgrad.run((tr,) if mt is None else (tr, mt), self._wgrad_terms, False)
                 reduce_group([fin] + fins)
                 self.optimizer.step()
                 self._clock.tick()
@@ -479,6 +563,9 @@ class Distiller:
         self.buffer["privileged_obses"][0].copy_(infos["privileged_obs"])
         if self.history:
             self.buffer["student_obses"][0].copy_(infos["student_obs"])
+        if self.memory:
+            self.state.zero_()
+            self._last_dones.zero_()
 
     def train_iteration(self, it):
         beta = self.teacher_action_prob()  # (of the iteration about to run)

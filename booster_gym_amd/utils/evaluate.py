@@ -164,13 +164,19 @@ class Evaluator:
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         with torch.no_grad():
             obs, _ = env.reset()
+            model.reset_memory()  # (a recurrent student's hidden state; nothing for every other model)
+            done = None
             record = env.eval_begin()
             packed = model.pack_actor()  # once: no parameter changes during the loop
             t0.record()
             for k in range(K):
                 x = obs if norm is None else norm.normalize_into(obs, self._obs_normed)
-                model.sample_actions(x, self._sampled, seed, k, mu_out=self._mu, scan=scan, packed=packed, est_out=self._est_scratch)
-                obs = env.step(self._mu)[0]
+                if model.memory_hidden:  # the env's done flags of the step just taken: the rows whose memory restarts
+                    model.sample_actions(x, self._sampled, seed, k, mu_out=self._mu, reset=done)
+                    obs, _, done, _ = env.step(self._mu)
+                else:
+                    model.sample_actions(x, self._sampled, seed, k, mu_out=self._mu, scan=scan, packed=packed, est_out=self._est_scratch)
+                    obs = env.step(self._mu)[0]
                 env.eval_step(record, self.settle_steps)
             t1.record()
         torch.cuda.synchronize()

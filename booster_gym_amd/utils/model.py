@@ -10,12 +10,14 @@ gradients), in the form its NetPlan names, on copies of the weights that one obj
 each current exactly when written or stamped at the present value of the parameters' WeightClock); the rollout-time inference + sampling is one fused HIP launch
 (`sample_actions` -> bg_actor_sample at the reference's widths on 47 inputs, bg_actor_sample_mlp at any other supported widths and on a
 frame stack of 47 H inputs).  With estimator.enabled a third network, `estimator` (47 H -> hidden -> 12), feeds the first E of its outputs to the
-actor behind the observations; the rollout runs both in one launch (bg_actor_sample_est).
+actor behind the observations; the rollout runs both in one launch (bg_actor_sample_est).  A distilled student may be recurrent
+(distillation.student_memory, `memory_hidden`): a GRU cell `memory` in front of the actor, one launch per step as well (bg_actor_sample_gru).
 """
 import ctypes
 import os
 from contextlib import contextmanager
 from functools import partial
+from types import SimpleNamespace
 from typing import Callable, NamedTuple, Optional
 
 import torch
@@ -618,6 +620,61 @@ class MLPTrainer:
             torch.sum(self.dw[i], dim=0, out=l.weight.grad)
 
 
+class GRUTrainer:
+    """Forward / backward of a GRU cell in front of an MLPTrainer's network over the T steps of an iteration, for the recurrent student's full-batch
+    update (utils/distill.py; rsl_rl's recurrent `Distillation`: back-propagation through the iteration's steps from the stored state h0).  Rows are
+    [T][N] step-major, B = T N.  Same schedule rules as MLPTrainer: no library GEMM, gradients WRITTEN into the parameters' `.grad`, the weight
+    gradients deferred to the grouped launch (pending_wgrad_problems), the padded copy of W_ih in a WeightCopies under the caller's clock.
+      forward(x)   gi = x W_ih^T + b_ih on all B rows (bg_mlp_layer_forward on the 64-column input), then the recurrence as ONE launch
+                   (bg_gru_sequence_forward) from h0 [N][H] and resets [T][N]; returns h [B][H], the trunk's input;
+      backward()   behind the trunk's backward_hidden: dh_ext = G1 W1, the gradient into the trunk's input that MLPTrainer does not produce (the
+                   same layer kernel on the trunk's transposed first layer), the recurrence backwards as ONE launch (bg_gru_sequence_backward), and
+                   the bias gradients = the column sums of dgi and dgh in a fixed order (bg_elu_backward_colsum without an activation)."""
+
+    KIN = 64  # the zero-padded width of the cell's input rows (47 observations)
+
+    def __init__(self, cell, trunk, T, N, clock=None):
+        self.cell, self.trunk, self.T, self.N, self.H = cell, trunk, int(T), int(N), int(cell.hidden_size)
+        B, H, dev = self.T * self.N, self.H, cell.weight_ih.device
+        self.B = B
+        self.copies = WeightCopies([SimpleNamespace(weight=cell.weight_ih)], clock, self.KIN)
+        new = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+        self.gi, self.h_prev, self.h, self.gates = new(B, 3 * H), new(B, H), new(B, H), new(B, 4 * H)
+        self.dh_ext, self.dgi, self.dgh = new(B, H), new(B, 3 * H), new(B, 3 * H)
+        self.h0 = new(self.N, H)                                                    # the state entering the iteration (detached)
+        self.resets = torch.zeros(self.T, self.N, dtype=torch.uint8, device=dev)    # non-zero: the state entering step t of env n is zero
+        self._zero_bias = new(H)
+        self._cs = new((B + 127) // 128 * 3 * H)
+        self.x = None
+        self._pending = False
+
+    def forward(self, x):
+        lib, st, p, c, H = _lib.load(), _lib.current_stream_ptr(), _lib.ptr, self.cell, self.H
+        self.x = x
+        _lib.check(lib.bg_mlp_layer_forward(self.B, self.KIN, 3 * H, p(x), p(self.copies.get("w0pad", 0)), p(c.bias_ih), p(self.gi), 0, st), "bg_mlp_layer_forward")
+        _lib.check(lib.bg_gru_sequence_forward(self.T, self.N, H, p(self.gi), p(self.h0), p(self.resets), p(c.weight_hh), p(c.bias_hh), p(self.h_prev), p(self.h),
+                                               p(self.gates), st), "bg_gru_sequence_forward")
+        return self.h
+
+    def backward(self):
+        lib, st, p, c, H, tr = _lib.load(), _lib.current_stream_ptr(), _lib.ptr, self.cell, self.H, self.trunk
+        g1, l0 = tr.gin[1], tr.layers[0]  # dL/dz of the trunk's first layer [B][out], behind backward_hidden
+        _lib.check(lib.bg_mlp_layer_forward(self.B, l0.weight.shape[0], H, p(g1), p(tr.copies.get("wt", 0)), p(self._zero_bias), p(self.dh_ext), 0, st),
+                   "bg_mlp_layer_forward")
+        _lib.check(lib.bg_gru_sequence_backward(self.T, self.N, H, p(self.dh_ext), p(self.gates), p(self.h_prev), p(self.resets), p(c.weight_hh), p(self.dgi),
+                                                p(self.dgh), None, st), "bg_gru_sequence_backward")
+        for g, b in ((self.dgi, c.bias_ih), (self.dgh, c.bias_hh)):
+            _lib.check(lib.bg_elu_backward_colsum(self.B, 3 * H, p(g), None, p(b.grad), p(self._cs), st), "bg_elu_backward_colsum")
+        self._pending = True
+
+    def pending_wgrad_problems(self):
+        """(G, A, dW, C_out, C_in (padded), C_in_real) of the cell's two weight gradients, for the grouped launch (GroupedWeightGrad.run)."""
+        if not self._pending:
+            return []
+        self._pending, c, H = False, self.cell, self.H
+        return [(self.dgi, self.x, c.weight_ih.grad, 3 * H, self.KIN, c.weight_ih.shape[1]), (self.dgh, self.h_prev, c.weight_hh.grad, 3 * H, H, H)]
+
+
 class EstimatorActor(torch.nn.Module):
     """What export_model.py scripts for a checkpoint with a state estimator: actor(cat(x, estimator(x)[:, :E])) on rows x of 47 H observations -- the
     deploy contract stays "47 H floats in, 12 out"."""
@@ -630,23 +687,53 @@ class EstimatorActor(torch.nn.Module):
         return self.actor(torch.cat((x, self.estimator(x)[..., : self.estimator_cols]), dim=-1))
 
 
+class RecurrentActor(torch.nn.Module):
+    """What export_model.py scripts for a recurrent student (distillation.student_memory): forward(obs [B][47]) -> [B][12] advances the hidden state,
+    a buffer this module owns (zero at first and again whenever B changes), by one GRU step and returns the actor's mean on the new state; reset()
+    (an exported method) zeroes it: call it where the robot's episode starts."""
+
+    def __init__(self, memory, actor):
+        super().__init__()
+        self.memory, self.actor, self.hidden = memory, actor, int(memory.hidden_size)
+        self.register_buffer("h", torch.zeros(0, self.hidden))
+
+    def forward(self, x):
+        if self.h.shape[0] != x.shape[0]:
+            self.h = torch.zeros(x.shape[0], self.hidden, dtype=x.dtype, device=x.device)
+        self.h = self.memory(x, self.h)
+        return self.actor(self.h)
+
+    @torch.jit.export
+    def reset(self):
+        self.h = torch.zeros_like(self.h)
+
+
 class ActorCritic(torch.nn.Module):
     """estimator_hidden (estimator.enabled, utils/estimator.py; None = without, exactly the reference's parameters in the reference's order): a third
     network `estimator`, num_obs -> estimator_hidden -> 12, registered behind `logstd`; the actor then takes num_obs + estimator_cols inputs, the
-    observations and the first estimator_cols = E of the estimator's 12 outputs.  num_obs stays the env's row (47 H): what callers pass as `obs`."""
+    observations and the first estimator_cols = E of the estimator's 12 outputs.  num_obs stays the env's row (47 H): what callers pass as `obs`.
+    memory_hidden = H > 0 (a recurrent student, distillation.student_memory; 0 = without, today's parameters in today's order): a
+    torch.nn.GRUCell(num_obs, H) `memory`, registered last, and the actor takes the H values of its new state instead of the observations."""
 
-    def __init__(self, num_act, num_obs, num_privileged_obs, actor_hidden=ACTOR_HIDDEN, critic_hidden=CRITIC_HIDDEN, estimator_hidden=None, estimator_cols=0):
+    def __init__(self, num_act, num_obs, num_privileged_obs, actor_hidden=ACTOR_HIDDEN, critic_hidden=CRITIC_HIDDEN, estimator_hidden=None, estimator_cols=0,
+                 memory_hidden=0):
         super().__init__()
+        self.memory_hidden = int(memory_hidden or 0)
+        if self.memory_hidden and estimator_hidden is not None:
+            raise ValueError("memory_hidden: a recurrent actor with a state estimator is not supported")
         self.actor_hidden, self.critic_hidden = tuple(actor_hidden), tuple(critic_hidden)
         self.estimator_hidden = None if estimator_hidden is None else tuple(estimator_hidden)
         self.estimator_cols = int(estimator_cols) if estimator_hidden is not None else 0
         if estimator_hidden is not None and not 1 <= self.estimator_cols <= _lib.NUM_DOFS:
             raise ValueError(f"estimator_cols = {estimator_cols!r}: 1 to {_lib.NUM_DOFS} of the estimator's outputs enter the actor")
         self.critic = _mlp(num_obs + num_privileged_obs, self.critic_hidden, 1)
-        self.actor = _mlp(num_obs + self.estimator_cols, self.actor_hidden, num_act)
+        self.actor = _mlp(self.memory_hidden or num_obs + self.estimator_cols, self.actor_hidden, num_act)
         self.logstd = torch.nn.parameter.Parameter(torch.full((1, num_act), fill_value=-2.0), requires_grad=True)
         if estimator_hidden is not None:
             self.estimator = _mlp(num_obs, self.estimator_hidden, _lib.NUM_DOFS)
+        if self.memory_hidden:
+            self.memory = torch.nn.GRUCell(num_obs, self.memory_hidden)
+        self._memory_state, self._gru_key, self._gru_descs = None, None, None
         self._sample_key, self._sample_layers = None, None
         self._est_key, self._est_layers = None, None
         self._packed = None  # pack_actor()
@@ -666,7 +753,14 @@ class ActorCritic(torch.nn.Module):
             return obs
         return torch.cat((obs, self.estimator(obs)[..., : self.estimator_cols]), dim=-1)
 
+    def reset_memory(self):
+        """Zero the hidden state that sample_actions carries for a model with memory (with env.reset()); nothing to do without one."""
+        if self._memory_state is not None:
+            self._memory_state.zero_()
+
     def act(self, obs):
+        if self.memory_hidden:
+            raise ValueError("act: a model with memory is stateful; sample_actions carries its hidden state (PPO on a recurrent actor is out of scope)")
         mean = self.actor(self.actor_input(obs))
         return torch.distributions.Normal(mean, torch.exp(self.logstd).expand_as(mean))
 
@@ -683,7 +777,7 @@ class ActorCritic(torch.nn.Module):
         or None where the architecture samples through bg_actor_sample_mlp, which reads the parameters themselves.  The packed copy is a snapshot:
         whoever passes it to sample_actions packs again after anything that may have changed a parameter (the rollout: at its start, every iteration)."""
         lin, w = self._sample_params()
-        if self.actor_hidden != ACTOR_HIDDEN or lin[0].in_features != _lib.NUM_OBS or self.has_estimator:
+        if self.actor_hidden != ACTOR_HIDDEN or lin[0].in_features != _lib.NUM_OBS or self.has_estimator or self.memory_hidden:
             return None
         if not w[0].is_cuda:
             raise RuntimeError("pack_actor runs a HIP kernel and needs CUDA parameters")
@@ -695,14 +789,16 @@ class ActorCritic(torch.nn.Module):
         _lib.check(_lib.load().bg_actor_pack(*[_lib.ptr(t) for t in w], _lib.ptr(self._packed), _lib.current_stream_ptr()), "bg_actor_pack")
         return self._packed
 
-    def sample_actions(self, obs, actions_out, seed, counter, mu_out=None, scan=0, packed=None, est_out=None):
+    def sample_actions(self, obs, actions_out, seed, counter, mu_out=None, scan=0, packed=None, est_out=None, reset=None):
         """One launch: the actor's mean and a Gaussian sample around it.  The reference's widths on 47 inputs run bg_actor_sample (its widths built
         into the kernel) on a packed copy of the parameters: `packed` from pack_actor() where the caller knows that no parameter has changed since
         (the rollout packs once for its 24 steps), else packed here, one more small launch.  Every other architecture, and every actor on a frame stack
         (47 H inputs, env.frame_stack), runs bg_actor_sample_mlp (widths from descriptors, the weights read from the parameters themselves); both draw
         the same noise for the same seed and counter.  scan = P (terrain.actor_heights): the rows end with the height scan's P values behind the 47 H
         observations (bg_actor_sample_mlp_scan, the same kernel).  A model with an estimator runs bg_actor_sample_est, both networks in one launch:
-        obs has the env's 47 H columns and est_out [N][12] (required) receives the estimator's 12 means, the first E of which the actor has read."""
+        obs has the env's 47 H columns and est_out [N][12] (required) receives the estimator's 12 means, the first E of which the actor has read.
+        A model with memory runs bg_actor_sample_gru on a state tensor [N][H] it owns (zero on first use and when N changes; reset_memory() zeroes
+        it), updated in place; reset [N] (bool or uint8, optional): the rows whose state is read as zero, the env's done flags of the step before."""
         if not obs.is_cuda:
             raise RuntimeError("sample_actions runs the fused HIP actor kernel and needs CUDA tensors")
         lin, w = self._sample_params()
@@ -711,6 +807,8 @@ class ActorCritic(torch.nn.Module):
                 raise RuntimeError("sample_actions needs contiguous tensors")
         if self.has_estimator:
             return self._sample_actions_est(obs, actions_out, seed, counter, mu_out, scan, est_out, lin, w)
+        if self.memory_hidden:
+            return self._sample_actions_gru(obs, actions_out, seed, counter, mu_out, scan, reset, lin, w)
         if self.actor_hidden == ACTOR_HIDDEN and lin[0].in_features == _lib.NUM_OBS:
             if packed is None:
                 packed = self.pack_actor()
@@ -758,4 +856,38 @@ class ActorCritic(torch.nn.Module):
         _lib.check(_lib.load().bg_actor_sample_est(obs.shape[0], _lib.ptr(obs), len(elin), ed, self.estimator_cols, len(lin), ad, _lib.ptr(self.logstd), int(seed),
                                                    int(counter), _lib.ptr(est_out), _lib.ptr(mu_out), _lib.ptr(actions_out), _lib.current_stream_ptr()),
                    "bg_actor_sample_est")
+        return actions_out
+
+    def gru_descriptor(self):
+        """bg_gru_desc of `memory` on its current parameter storage."""
+        m = self.memory
+        return _lib.GruDesc(m.weight_ih.data_ptr(), m.weight_hh.data_ptr(), m.bias_ih.data_ptr(), m.bias_hh.data_ptr(), m.input_size, m.hidden_size)
+
+    def _sample_actions_gru(self, obs, actions_out, seed, counter, mu_out, scan, reset, lin, w):
+        """sample_actions of a model with memory: ONE launch (bg_actor_sample_gru) advances the state this model keeps and samples from the actor on it."""
+        if scan:
+            raise ValueError("sample_actions: a model with memory takes no height scan in the actor's row (terrain.actor_heights)")
+        N, m = obs.shape[0], self.memory
+        if obs.shape[-1] != m.input_size:
+            raise ValueError(f"sample_actions: observations of {obs.shape[-1]} columns, the memory takes {m.input_size}")
+        if reset is not None:
+            if reset.dtype == torch.bool:
+                reset = reset.view(torch.uint8)
+            if reset.dtype != torch.uint8 or not reset.is_cuda or not reset.is_contiguous() or reset.numel() != N:
+                raise ValueError(f"sample_actions: reset must be a contiguous bool or uint8 CUDA tensor of {N} entries")
+        mw = [m.weight_ih, m.weight_hh, m.bias_ih, m.bias_hh]
+        for t in mw:
+            if not t.is_contiguous():
+                raise RuntimeError("sample_actions needs contiguous tensors")
+        if self._memory_state is None or self._memory_state.shape[0] != N or self._memory_state.device != obs.device:
+            self._memory_state = torch.zeros(N, self.memory_hidden, dtype=torch.float32, device=obs.device)
+        key = tuple(t.data_ptr() for t in w + mw)
+        if key != self._gru_key:
+            layers = (_lib.MlpLayerDesc * len(lin))(*[_lib.MlpLayerDesc(l.weight.data_ptr(), l.bias.data_ptr(), l.in_features, l.out_features) for l in lin])
+            self._gru_descs, self._gru_key = (self.gru_descriptor(), layers), key
+        gd, layers = self._gru_descs
+        h = self._memory_state
+        _lib.check(_lib.load().bg_actor_sample_gru(N, _lib.ptr(obs), obs.shape[-1], gd, len(lin), layers, _lib.ptr(self.logstd), int(seed), int(counter),
+                                                   _lib.ptr(reset), _lib.ptr(h), _lib.ptr(h), _lib.ptr(mu_out), _lib.ptr(actions_out), _lib.current_stream_ptr()),
+                   "bg_actor_sample_gru")
         return actions_out

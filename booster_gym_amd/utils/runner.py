@@ -53,7 +53,7 @@ import torch
 from .. import _lib
 from ..envs import TASKS
 from .buffer import ExperienceBuffer
-from .estimator import EST_WIDTH, check_estimator_checkpoint, estimator_cfg
+from .estimator import EST_WIDTH, check_estimator_checkpoint, estimator_cfg, estimator_enabled
 from .config import load_cfg
 from .obs_norm import ObsNormalizer, check_checkpoint, normalization_cfg
 from .model import ACTOR_HIDDEN, CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, MLPTrainer, NetPlan, WeightClock, check_hidden, hidden_of, plan_network
@@ -86,6 +86,18 @@ def hidden_widths(cfg):
 
 
 INPUT_PADS = (64, 128, 256, 512)  # first-layer inputs of the per-layer fused kernels (bg_mlp.hip); the chained kernels take 64 only
+
+
+def actor_memory_of(cfg):
+    """algorithm.actor_memory as the width H of the GRU cell in front of the actor: 0 (absent: the shipped yaml does not list it) = none.  Set by a
+    recurrent distilled student's checkpoint on re-entry (distill.student_overrides).  Pure.  ValueError naming the key for any other value than 0,
+    128 or 256, and with estimator.enabled."""
+    H = (cfg.get("algorithm", {}) or {}).get("actor_memory", 0) or 0
+    if isinstance(H, bool) or not isinstance(H, int) or H not in (0, 128, 256):
+        raise ValueError(f"algorithm.actor_memory must be 0, 128 or 256 (the width of a recurrent student's GRU cell, distillation.student_memory), got {H!r}")
+    if H and estimator_enabled(cfg):
+        raise ValueError(f"algorithm.actor_memory = {H} is not supported with estimator.enabled: true")
+    return H
 
 
 def pad_input(width):
@@ -339,6 +351,11 @@ class Runner:
         self._mini_batches = mini_batches(self.cfg)[1]  # (ValueError before anything is built; 1 = off: the one switch every branch below reads)
         # estimator.enabled: a learned state estimator in front of the actor (utils/estimator.py); None = off, the one switch every branch below reads
         self._est = estimator_cfg(self.cfg, self.world_size)
+        # algorithm.actor_memory: a recurrent distilled student re-entering for play / evaluation / export; 0 = none, the one switch the branches below read
+        self._memory = actor_memory_of(self.cfg)
+        if self._memory and not test:
+            raise ValueError(f"algorithm.actor_memory = {self._memory}: PPO on a recurrent actor is out of scope; the key is for a distilled student's "
+                             "checkpoint under play.py, evaluate.py and export_model.py (training a recurrent student: distill.py --student_memory)")
         self._set_seed()
         task = self.cfg["basic"]["task"]
         if task not in TASKS:
@@ -355,6 +372,8 @@ class Runner:
             obs_src, obs_sign, act_src, act_sign = self.env.mirror_maps()
             self._act_mirror = (act_src.tolist(), act_sign.tolist())
         est_args = {} if self._est is None else {"estimator_hidden": self._est.hidden, "estimator_cols": len(self._est.targets)}
+        if self._memory:
+            est_args = {"memory_hidden": self._memory}
         self.model = ActorCritic(self.env.num_actions, self.env.num_obs, self.env.num_privileged_obs, self.actor_hidden, self.critic_hidden, **est_args).to(self.device)
         self.dp.broadcast_parameters(self.model)  # identical initial weights on every rank
         # algorithm.empirical_normalization: running mean / variance of the critic's input columns (the actor's are its first num_obs), applied where rows
@@ -537,6 +556,11 @@ class Runner:
             self.cfg["basic"]["checkpoint"] = ck
         print("Loading model from {}".format(ck))
         model_dict = torch.load(ck, map_location=self.device, weights_only=True)
+        ck_mem = int(model_dict["model"]["memory.weight_hh"].shape[1]) if "memory.weight_hh" in model_dict["model"] else 0
+        if ck_mem != getattr(self, "_memory", 0):
+            raise ValueError(f"checkpoint {ck} has " + (f"a recurrent actor (memory.* of width {ck_mem})" if ck_mem else "no memory.* (its actor is not recurrent)")
+                             + f", the config has algorithm.actor_memory = {getattr(self, '_memory', 0)}: set algorithm.actor_memory to {ck_mem}"
+                             + (" (a student of distillation.student_memory; evaluate.py and export_model.py do so from the checkpoint)" if ck_mem else ""))
         ck_ain, a_in = int(model_dict["model"]["actor.0.weight"].shape[1]), self.model.actor[0].in_features
         est = getattr(self, "_est", None)
         check_estimator_checkpoint(ck, model_dict, est, ck_ain, a_in)  # (before the frame-stack message below can misfire on a width that differs by E)
@@ -1282,6 +1306,10 @@ class Runner:
         by an optional .npz trajectory dump; `max_steps=None` runs until interrupted like the reference."""
         obs, infos = self.env.reset()
         traj, step = [], 0
+        if self._memory:  # a recurrent student: the rollout's own launch carries its state; the done flags of a step restart the rows' memory in the next
+            mean, sampled = (torch.zeros(self.env.num_envs, self.env.num_actions, device=self.device) for _ in range(2))
+            self.model.reset_memory()
+            done = None
         if self._est is not None:  # the rollout's own launch: its mean is the action; its sample and the estimates go to scratch tensors
             mean, sampled = (torch.zeros(self.env.num_envs, self.env.num_actions, device=self.device) for _ in range(2))
             est_scratch = torch.zeros(self.env.num_envs, EST_WIDTH, device=self.device)
@@ -1292,6 +1320,9 @@ class Runner:
                         obs = self.obs_norm.normalize_into(obs, torch.empty_like(obs))
                     if self._est is not None:
                         self.model.sample_actions(obs.contiguous(), sampled, 0, step, mu_out=mean, est_out=est_scratch)
+                        act = mean
+                    elif self._memory:
+                        self.model.sample_actions(obs.contiguous(), sampled, 0, step, mu_out=mean, reset=done)
                         act = mean
                     else:
                         act = self.model.actor(obs)

@@ -1,7 +1,9 @@
 """python export_model.py --task=T1 [--checkpoint path|-1]: TorchScript export of the actor (reference export_model.py:8-30) so that
 the reference's deployment code (deploy/utils/policy.py:9) can load what this framework trains.  The actor's widths are read from the checkpoint's tensors (any supported architecture, with or without the terrain height
 scan, a frame stack or the actor's own height scan, exports without editing the YAML); the TorchScript module is still a plain Sequential.  A checkpoint trained with
-algorithm.empirical_normalization carries its observation statistics: they are folded into the actor's first layer, so the exported module takes raw observations."""
+algorithm.empirical_normalization carries its observation statistics: they are folded into the actor's first layer, so the exported module takes raw observations.
+A recurrent student (distillation.student_memory: the checkpoint carries "memory.*") exports as a STATEFUL module, utils/model.py's RecurrentActor; the
+script prints its contract.  tools/play_oracle.py does not take one yet."""
 import argparse
 import glob
 import os
@@ -9,7 +11,7 @@ import os
 import torch
 
 from booster_gym_amd.utils.config import load_cfg
-from booster_gym_amd.utils.model import ActorCritic, EstimatorActor, hidden_of
+from booster_gym_amd.utils.model import ActorCritic, EstimatorActor, RecurrentActor, hidden_of
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
@@ -36,6 +38,10 @@ if __name__ == "__main__":
         print("Actor input of {} columns: 47 x {} observations, then {} estimates of the privileged columns {} from the checkpoint's estimator "
               "(hidden {}); the exported module takes the {} observations and computes the estimates itself".format(
                   num_obs + len(targets), num_obs // 47, len(targets), targets, list(est_args["estimator_hidden"]), num_obs))
+    # distillation.student_memory: a GRU cell `memory` reads the observation and the actor reads the cell's state
+    if "memory.weight_ih" in sd:
+        est_args = {"memory_hidden": int(sd["memory.weight_hh"].shape[1])}
+        num_obs = int(sd["memory.weight_ih"].shape[1])
     num_priv = int(sd["critic.0.weight"].shape[1]) - num_obs
     if num_obs % 47:
         # terrain.actor_heights: the actor's row ends with the height scan, whose grid the checkpoint carries
@@ -65,5 +71,12 @@ if __name__ == "__main__":
         print("Folded the observation normaliser ({} columns, count {:.0f}) into the actor's first layer".format(norm.cols, norm.count))
     os.makedirs("deploy/models", exist_ok=True)
     out = os.path.join("deploy", "models", f"{args.task}.pt")
-    torch.jit.script(EstimatorActor(model.actor, model.estimator, model.estimator_cols) if model.has_estimator else model.actor).save(out)
+    if model.memory_hidden:
+        module = RecurrentActor(model.memory, model.actor)
+        print("Recurrent actor (GRU cell of width {}): the exported module is STATEFUL.  forward(obs [B][{}]) -> actions [B][12] advances its hidden state by "
+              "one step: call it once per control step, on the newest observation only.  The state is a buffer of the module, zero at first and "
+              "re-created zero whenever B changes; call reset() where an episode starts.".format(model.memory_hidden, num_obs))
+    else:
+        module = EstimatorActor(model.actor, model.estimator, model.estimator_cols) if model.has_estimator else model.actor
+    torch.jit.script(module).save(out)
     print("Exported actor to {}".format(out))

@@ -397,6 +397,43 @@ int bg_distill_act_mix(int32_t N, const float* teacher_obs, int32_t teacher_stri
 int bg_actor_sample_est(int32_t N, const float* obs, int32_t n_est, const bg_mlp_layer_desc* est, int32_t est_cols, int32_t n_actor,
                         const bg_mlp_layer_desc* actor, const float* logstd, uint64_t seed, uint64_t counter, float* est_out, float* mu, float* actions,
                         void* stream);
+/* A recurrent student (T1.yaml distillation.student_memory; rsl_rl's recurrent student of `Distillation`): a GRU cell in torch.nn.GRUCell's layout and
+ * gate order r | z | n, W_ih [3 hidden][in], W_hh [3 hidden][hidden] (16-byte aligned), b_ih / b_hh [3 hidden]:
+ *   gi = x W_ih^T + b_ih, gh = h W_hh^T + b_hh, r = sigmoid(gi_r + gh_r), z = sigmoid(gi_z + gh_z), n = tanh(gi_n + r gh_n), h' = (1 - z) n + z h.
+ * in = 47 (the newest single observation), hidden = 128 or 256; anything else is -4. */
+typedef struct bg_gru_desc {
+    const float *W_ih, *W_hh, *b_ih, *b_hh;
+    int32_t in, hidden;
+} bg_gru_desc;
+/* bg_actor_sample_mlp with the cell in front: per row x = columns [0, 47) of obs (rows obs_stride >= 47 floats apart), h = h_in [N][hidden] (read as
+ * zero where reset [N] (uint8, may be NULL) is non-zero), h' to h_out [N][hidden], and the trunk `layers` (layers[0].in = hidden, then
+ * bg_actor_sample_mlp's width rules, every matrix 16-byte aligned) on h': mu [N][12] (may be NULL), actions = mu + exp(logstd) n with
+ * bg_actor_sample_mlp's noise (Philox(seed, row, counter, RS_ACTOR + group of 4 actions)).  h_in == h_out is allowed: a workgroup reads its 16 rows
+ * before it writes them.  Nothing is written past row N.  Violations: -1 / -4 with a message, before any launch. */
+int bg_actor_sample_gru(int32_t N, const float* obs, int32_t obs_stride, const bg_gru_desc* gru, int32_t n_layers, const bg_mlp_layer_desc* layers,
+                        const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, float* mu,
+                        float* actions, void* stream);
+/* bg_distill_act_mix's split grid with the recurrent student in the student's half: the teacher's half is unchanged (teacher_mu equals
+ * bg_actor_sample_mlp_scan's mean, bit for bit), the student's half is bg_actor_sample_gru's body on columns [0, 47) of the teacher's rows (student_mu,
+ * h_out, and at beta = 0 actions equal bg_actor_sample_gru's, bit for bit).  beta in [0, 1] and teacher_noise: bg_distill_act_mix's rules (the same
+ * RS_DAGGER draw decides which half acts; a teacher-driven row carries the student's noise draw); the memory advances on every row, whoever acts. */
+int bg_distill_act_gru(int32_t N, const float* teacher_obs, int32_t teacher_stride, int32_t n_teacher, const bg_mlp_layer_desc* teacher,
+                       int32_t scan_points, const bg_gru_desc* gru, int32_t n_student, const bg_mlp_layer_desc* student, const float* student_logstd,
+                       uint64_t seed, uint64_t counter, float beta, int32_t teacher_noise, const uint8_t* reset, const float* h_in, float* h_out,
+                       float* student_mu, float* actions, float* teacher_mu, void* stream);
+/* The recurrence of the recurrent student's update over T steps as ONE launch each way (csrc/bg_gru.hip); H = 128 or 256, any N >= 1, T >= 1.  Envs are
+ * independent: a workgroup owns 16 rows and walks the steps itself, its state tile in LDS; W_hh [3H][H] (16-byte aligned) streams from L2.
+ * Forward: gi [T][N][3H] the x-side pre-activations (b_ih included), h0 [N][H] the state entering step 0 (NULL: zero), reset [T][N] (uint8, NULL: none):
+ * non-zero = the state entering step t is zero.  Out: h_prev [T][N][H] the state entering each step after the reset, h [T][N][H] the new state,
+ * gates [T][N][4H] = r | z | n | gh_n.  Deterministic; nothing is written past row N of any step. */
+int bg_gru_sequence_forward(int32_t T, int32_t N, int32_t H, const float* gi, const float* h0, const uint8_t* reset, const float* W_hh, const float* b_hh,
+                            float* h_prev, float* h, float* gates, void* stream);
+/* Back-propagation through those T steps from dh_ext [T][N][H] = dL/dh[t] of whatever reads h[t]; walks t = T - 1 .. 0 with a carried dh (zero at T - 1):
+ *   dh = dh_ext[t] + carry, dn = dh (1 - z), dz = dh (h_prev - n), dn_pre = dn (1 - n^2), dz_pre = dz z (1 - z), dr_pre = dn_pre gh_n r (1 - r),
+ *   dgi[t] = [dr_pre | dz_pre | dn_pre], dgh[t] = [dr_pre | dz_pre | dn_pre r] (both [T][N][3H]), carry = dh z + dgh[t] W_hh, zero for a row with reset[t].
+ * dh0 [N][H] (may be NULL): the carry left after step 0.  Deterministic. */
+int bg_gru_sequence_backward(int32_t T, int32_t N, int32_t H, const float* dh_ext, const float* gates, const float* h_prev, const uint8_t* reset,
+                             const float* W_hh, float* dgi, float* dgh, float* dh0, void* stream);
 /* Fused global-norm clip + Adam over one flat parameter buffer (runner.py:162-165); lr is read from device memory
  * so the KL-adaptive schedule (runner.py:174-180) needs no host sync.  gnorm_scratch [1] device float64. */
 int bg_adam_step(int32_t n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const float* lr_device, int32_t step,

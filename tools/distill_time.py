@@ -22,6 +22,13 @@
           it moves as a fraction of the float4-copy rate;
       (9) the loop of (3) with neither key, with the loss, with the mixing, and with both, one Distiller after the other, `pairs` times each.
           `only` = "head" runs (8) alone, "loop" (9) alone.
+  With student_memory=H among the arguments (distillation.student_memory; out "-" = profiles/distill_memory_time.txt) the sections are the recurrent
+  student's instead, all at H = 1 / P = 187:
+      (10) bg_distill_act_gru with a cell of 128 and of 256 against bg_distill_act (a memoryless student) and bg_distill_act_hist at Hs (5 unless
+           given), the same way as (1);
+      (11) bg_gru_sequence_forward / _backward at T = 24 on num_envs rows against 24 launches of bg_mlp_layer_forward(num_envs, H, 3H), the per-step
+           form of the h-side GEMM they replace, and against their own fp32-MFMA time from the flop count (157.3 TFLOPS);
+      (12) the loop of (3) with a memoryless student, with Hs, and with the cell of H, one Distiller after the other, `pairs` times each.
   The outputs of (1) are compared bit for bit before they are timed.  The committed profile carries two more sections that this tool does not
   write: the figures tests/test_gpu_distill.py prints under -s, and bench.py of this tree against a checkout of its parent commit."""
 import os
@@ -279,7 +286,74 @@ def head_sym(pairs=3, B=98304, coef=10.0):
             f"bg_actor_head_sym at B {us['actor sym']:.2f} us (distill sym / actor sym = {us['sym'] / us['actor sym']:.4f})")
 
 
-def loop(K=20, W=5, pairs=3, N=4096, Hs=None, coef=0.0, beta=0.0):
+def act_gru(pairs=3, N=4096, Hs=5, P=187):
+    from booster_gym_amd import _lib
+    from booster_gym_amd.utils.model import ActorCritic
+
+    lib, p = _lib.load(), _lib.ptr
+    torch.manual_seed(1)
+    teacher = ActorCritic(12, 47 + P, 14 + P).to(DEV)
+    obs, sobs = torch.randn(N, 47 + P, device=DEV), torch.randn(N, 47 * Hs, device=DEV)
+    plain_s, hist_s = ActorCritic(12, 47, 14 + P).to(DEV), ActorCritic(12, 47 * Hs, 14 + P).to(DEV)
+    gru_s = {H: ActorCritic(12, 47, 14 + P, memory_hidden=H).to(DEV) for H in (128, 256)}
+    state = {H: torch.zeros(N, H, device=DEV) for H in gru_s}
+    (td, nt), st = _descs(teacher), _lib.current_stream_ptr()
+    (pd, npl), (hd, nh) = _descs(plain_s), _descs(hist_s)
+    gd = {H: (m.gru_descriptor(),) + _descs(m) for H, m in gru_s.items()}
+    a1, t1 = (torch.empty(N, 12, device=DEV) for _ in range(2))
+
+    def plain(k):
+        _lib.check(lib.bg_distill_act(N, p(obs), 47 + P, npl, pd, nt, td, P, p(plain_s.logstd), 1, k, None, p(a1), p(t1), st), "bg_distill_act")
+
+    def hist(k):
+        _lib.check(lib.bg_distill_act_hist(N, p(obs), 47 + P, p(sobs), 47 * Hs, nh, hd, nt, td, P, p(hist_s.logstd), 1, k, None, p(a1), p(t1), st), "bg_distill_act_hist")
+
+    def gru(H):
+        g, sd, ns = gd[H]
+        return lambda k: _lib.check(lib.bg_distill_act_gru(N, p(obs), 47 + P, nt, td, P, g, ns, sd, p(gru_s[H].logstd), 1, k, 0.0, 1, None, p(state[H]), p(state[H]), None,
+                                                           p(a1), p(t1), st), "bg_distill_act_gru")
+
+    fns = (("plain", plain), ("hist", hist), ("gru 128", gru(128)), ("gru 256", gru(256)))
+    for q in range(pairs):
+        us = {m: _best(f, 200) for m, f in _orders(q, fns)}
+        say(f"rollout inference, {N} rows, H = 1, P = {P}, teacher and trunks 256-128-128: bg_distill_act (memoryless, 47 columns) {us['plain']:.2f} us, "
+            f"bg_distill_act_hist at Hs = {Hs} {us['hist']:.2f} us, bg_distill_act_gru with a cell of 128 {us['gru 128']:.2f} us ({us['gru 128'] / us['plain']:.3f}x plain, "
+            f"{us['gru 128'] / us['hist']:.3f}x hist), of 256 {us['gru 256']:.2f} us ({us['gru 256'] / us['plain']:.3f}x plain, {us['gru 256'] / us['hist']:.3f}x hist)")
+
+
+def sequence(pairs=3, N=4096, T=24):
+    from booster_gym_amd import _lib
+
+    lib, p, st = _lib.load(), _lib.ptr, _lib.current_stream_ptr()
+    for H in (128, 256):
+        torch.manual_seed(H)
+        cell = torch.nn.GRUCell(47, H).to(DEV)
+        B = T * N
+        gi, dh = torch.randn(B, 3 * H, device=DEV), torch.randn(B, H, device=DEV)
+        h0, reset = torch.zeros(N, H, device=DEV), (torch.rand(T, N, device=DEV) < 0.02).to(torch.uint8)
+        h_prev, h, gates = torch.empty(B, H, device=DEV), torch.empty(B, H, device=DEV), torch.empty(B, 4 * H, device=DEV)
+        dgi, dgh, gh = torch.empty(B, 3 * H, device=DEV), torch.empty(B, 3 * H, device=DEV), torch.empty(N, 3 * H, device=DEV)
+
+        def fwd(k):
+            _lib.check(lib.bg_gru_sequence_forward(T, N, H, p(gi), p(h0), p(reset), p(cell.weight_hh), p(cell.bias_hh), p(h_prev), p(h), p(gates), st), "bg_gru_sequence_forward")
+
+        def bwd(k):
+            _lib.check(lib.bg_gru_sequence_backward(T, N, H, p(dh), p(gates), p(h_prev), p(reset), p(cell.weight_hh), p(dgi), p(dgh), None, st), "bg_gru_sequence_backward")
+
+        def steps(k):
+            for t in range(T):
+                _lib.check(lib.bg_mlp_layer_forward(N, H, 3 * H, p(h[t * N :]), p(cell.weight_hh), p(cell.bias_hh), p(gh), 0, st), "bg_mlp_layer_forward")
+
+        fwd(0); torch.cuda.synchronize()
+        floor = 2.0 * B * H * 3 * H / 157.3e12 * 1e6  # us of the h-side GEMM (forward) = of the carry's GEMM (backward) at the fp32 matrix rate
+        for q in range(pairs):
+            us = {m: _best(f, 20) for m, f in _orders(q, (("fwd", fwd), ("bwd", bwd), ("steps", steps)))}
+            say(f"recurrence, T = {T}, {N} envs, H = {H}: bg_gru_sequence_forward {us['fwd']:.1f} us, bg_gru_sequence_backward {us['bwd']:.1f} us, {T} launches of "
+                f"bg_mlp_layer_forward({N}, {H}, {3 * H}) {us['steps']:.1f} us (forward / per-step GEMMs = {us['fwd'] / us['steps']:.3f}); fp32-MFMA time of the "
+                f"{2.0 * B * H * 3 * H / 1e9:.1f} GFLOP {floor:.1f} us (forward {us['fwd'] / floor:.1f}x, backward {us['bwd'] / floor:.1f}x)")
+
+
+def loop(K=20, W=5, pairs=3, N=4096, Hs=None, coef=0.0, beta=0.0, memory=0):
     from booster_gym_amd.utils.config import load_cfg
     from booster_gym_amd.utils.distill import Distiller
     from booster_gym_amd.utils.model import ActorCritic
@@ -299,6 +373,8 @@ def loop(K=20, W=5, pairs=3, N=4096, Hs=None, coef=0.0, beta=0.0):
         cfg["distillation"]["symmetric_coef"] = coef
     if beta:
         cfg["distillation"]["teacher_action_prob"] = beta
+    if memory:
+        cfg["distillation"]["student_memory"] = memory
     d = Distiller(cfg=cfg)
     d.begin(Recorder(cfg, root=tmp, rank=0))
     it = 0
@@ -316,6 +392,7 @@ def loop(K=20, W=5, pairs=3, N=4096, Hs=None, coef=0.0, beta=0.0):
     for q in range(pairs):
         ms = run(K)
         keys = f"symmetric_coef {coef:g}, teacher_action_prob {beta:g}, " if coef or beta or KEYS else ""
+        keys += f"student_memory {memory}, " if memory or MEMORY else ""
         say(f"distillation loop, {N} envs, H = 1, P = 187, {keys}student_frame_stack {Hs or 'absent'} ({d.student_obs} student columns padded to {d._student_in.shape[1]}), horizon {T}, {E} epochs, student 256-128-128 (plan {d._trainer.plan.fwd} / {d._trainer.plan.bwd}, weight "
             f"gradients {d._wgrad_terms or 'fp32'}): {ms:.3f} ms per iteration = {1e3 / ms:.2f} iterations/s = {N * T / ms / 1e3:.3f} M env-steps/s; last loss "
             f"{d.last_loss:.6f}")
@@ -330,17 +407,26 @@ def loop(K=20, W=5, pairs=3, N=4096, Hs=None, coef=0.0, beta=0.0):
 
 
 KEYS = {}  # symmetric_coef / teacher_action_prob given on the command line: sections (7) to (9)
+MEMORY = []  # student_memory given on the command line: sections (10) to (12)
 
 
 if __name__ == "__main__":
     KEYS.update({k: float(v) for k, v in (x.split("=", 1) for x in sys.argv[1:] if "=" in x) if k in ("symmetric_coef", "teacher_action_prob")})
+    MEMORY.extend(int(v) for k, v in (x.split("=", 1) for x in sys.argv[1:] if "=" in x) if k == "student_memory")
     a = [x for x in sys.argv[1:] if "=" not in x]
     K, W, pairs, N = (int(a[i]) if len(a) > i else v for i, v in enumerate((20, 5, 3, 4096)))
     Hs, only = (int(a[5]) if len(a) > 5 else 0), (a[6] if len(a) > 6 else "")
-    name = "distill_symmetry_dagger_time.txt" if KEYS else "distill_history_time.txt" if Hs else "distill_time.txt"
+    name = "distill_memory_time.txt" if MEMORY else "distill_symmetry_dagger_time.txt" if KEYS else "distill_history_time.txt" if Hs else "distill_time.txt"
     out = a[4] if len(a) > 4 and a[4] != "-" else os.path.join(ROOT, "profiles", name)
     say(f"tools/distill_time.py {' '.join(sys.argv[1:]) or f'{K} {W} {pairs} {N}'} on {torch.cuda.get_device_name(0)}")
-    if KEYS:
+    if MEMORY:
+        if only != "loop":
+            act_gru(pairs, N, Hs or 5)
+            sequence(pairs, N)
+        for q in range(pairs):  # (a Distiller each: the env, the buffers and the plan are per configuration)
+            for hs, mem in _orders(q, ((None, 0), (Hs or 5, 0), (None, MEMORY[0]))):
+                loop(K, W, 1, N, hs, memory=mem)
+    elif KEYS:
         coef, beta = KEYS.get("symmetric_coef", 10.0), KEYS.get("teacher_action_prob", 0.5)
         if only not in ("loop", "head"):
             act_mix(pairs, N, Hs or 5)

@@ -21,6 +21,9 @@ def load_actor(path):
 
     ck = torch.load(path, map_location="cpu", weights_only=True)
     sd = ck["model"]
+    if "memory.weight_ih" in sd:
+        raise ValueError(f"{path} is a recurrent student (distillation.student_memory: it carries memory.*): not supported here for now; "
+                         "play.py and evaluate.py run it")
     layers = [(sd[f"actor.{i}.weight"].numpy(), sd[f"actor.{i}.bias"].numpy()) for i in (0, 2, 4, 6)]
     if ck.get("obs_normalizer") is not None:
         # algorithm.empirical_normalization: the actor was trained on (x - mean) / (sqrt(var) + eps); the first layer takes the statistics in, so the
