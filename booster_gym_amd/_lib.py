@@ -169,6 +169,7 @@ SYMBOLS = [
     "bg_obs_moments", "bg_obs_normalize",
     "bg_perm_fill", "bg_gather_rows",
     "bg_actor_sample_gru", "bg_distill_act_gru", "bg_gru_sequence_forward", "bg_gru_sequence_backward",
+    "bg_gru_bias_partial",
     "bg_last_error", "bg_version",
 ]
 
@@ -243,6 +244,7 @@ def load():
                                      vp, vp, vp, vp, vp, vp, vp]),
         "bg_gru_sequence_forward": (i32, [i32, i32, i32] + [vp] * 9),
         "bg_gru_sequence_backward": (i32, [i32, i32, i32] + [vp] * 9),
+        "bg_gru_bias_partial": (i32, [i32, i32, vp, vp, vp, vp]),
         "bg_adam_step": (i32, [i32, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, vp, vp]),
         "bg_adapt_lr": (i32, [vp, f32, f32, f32, f32, vp, vp]),
         "bg_optimizer_step": (i32, [i32, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, vp, i32, i32, vp, vp, vp, i32, i32, f32, f32, f32, f32, vp, vp, i32, vp]),

@@ -216,6 +216,40 @@ __global__ __launch_bounds__(256) void gru_sequence_backward_kernel(int T, int N
     }
 }
 
+// The cell's two bias gradients of the PPO update (algorithm.rnn_hidden_size): the column sums of dgi and dgh [B][3H] as ONE launch that leaves one
+// record [6H] = dgi's sums | dgh's per 128-row block, for a bg_reduce_problem of the update's deferred group to add up (bg_reduce.h).  Memory-bound: a
+// lane owns one 16-byte column of the joined row [dgi row | dgh row] per 64-lane group (3 groups at H = 128, 6 at H = 256: a wave reads 1 KiB, or two
+// 512-byte runs where a group straddles the two tensors), a wave the rows wave, wave + 4, ... of the block in ascending order, its loads of four rows
+// in flight; the four waves' sums meet in LDS and are added in wave order: every term once, a fixed order, no atomics.
+constexpr int BP_ROWS = 128;  // rows per workgroup = per record
+
+template <int H>
+__global__ __launch_bounds__(256) void gru_bias_partial_kernel(int B, const float* __restrict__ dgi, const float* __restrict__ dgh, float* __restrict__ records) {
+    constexpr int C = 3 * H, C4 = C / 4, G = 2 * C4 / 64;
+    static_assert(2 * C4 % 64 == 0, "");
+    __shared__ f32x4 sm[4][2 * C4];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r0 = blockIdx.x * BP_ROWS, r1 = min(r0 + BP_ROWS, B);  // (rows at or beyond B are never read)
+    const float* src[G];
+    f32x4 acc[G];
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+        const int v = 64 * g + lane;
+        src[g] = v < C4 ? dgi + 4 * v : dgh + 4 * (v - C4);
+        acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll 4
+    for (int r = r0 + wave; r < r1; r += 4) {
+#pragma unroll
+        for (int g = 0; g < G; g++) acc[g] += *reinterpret_cast<const f32x4*>(src[g] + (size_t)r * C);
+    }
+#pragma unroll
+    for (int g = 0; g < G; g++) sm[wave][64 * g + lane] = acc[g];
+    __syncthreads();
+    f32x4* rec = reinterpret_cast<f32x4*>(records + (size_t)blockIdx.x * 2 * C);
+    for (int v = threadIdx.x; v < 2 * C4; v += 256) rec[v] = ((sm[0][v] + sm[1][v]) + sm[2][v]) + sm[3][v];
+}
+
 int check_shape(const char* who, int32_t T, int32_t N, int32_t H) {
     if (T <= 0 || N <= 0) return bg_fail(who, -1, "bad argument (T, N: at least 1)");
     if (H != 128 && H != 256) return bg_fail(who, -4, "unsupported H (128 or 256)");
@@ -247,6 +281,20 @@ extern "C" int bg_gru_sequence_backward(int32_t T, int32_t N, int32_t H, const f
     hipStream_t st = (hipStream_t)stream;
     if (H == 128) hipLaunchKernelGGL(gru_sequence_backward_kernel<128>, grid, block, 0, st, T, N, dh_ext, gates, h_prev, reset, W_hh, dgi, dgh, dh0);
     else hipLaunchKernelGGL(gru_sequence_backward_kernel<256>, grid, block, 0, st, T, N, dh_ext, gates, h_prev, reset, W_hh, dgi, dgh, dh0);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int bg_gru_bias_partial(int32_t B, int32_t H, const float* dgi, const float* dgh, float* records, void* stream) {
+    const char* who = "bg_gru_bias_partial";
+    if (B <= 0) return bg_fail(who, -1, "bad argument (B: at least 1)");
+    if (H != 128 && H != 256) return bg_fail(who, -4, "unsupported H (128 or 256)");
+    if (!dgi || !dgh || !records) return bg_fail(who, -1, "bad argument");
+    if (!aligned16(dgi) || !aligned16(dgh) || !aligned16(records)) return bg_fail(who, -1, "dgi, dgh and records must be 16-byte aligned");
+    const dim3 grid((B + BP_ROWS - 1) / BP_ROWS), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (H == 128) hipLaunchKernelGGL(gru_bias_partial_kernel<128>, grid, block, 0, st, B, dgi, dgh, records);
+    else hipLaunchKernelGGL(gru_bias_partial_kernel<256>, grid, block, 0, st, B, dgi, dgh, records);
     HIP_OK(hipGetLastError());
     return 0;
 }

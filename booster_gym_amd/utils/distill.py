@@ -388,6 +388,9 @@ class Distiller:
         if d.get("obs_normalizer") is not None:
             raise ValueError(f"teacher checkpoint {ck} was trained with algorithm.empirical_normalization (it has an \"obs_normalizer\"): not supported "
                              "with distillation for now")
+        if any(k.startswith("memory.") for k in sd):
+            raise ValueError(f"teacher checkpoint {ck} carries memory.* (a recurrent actor, algorithm.rnn_hidden_size or a recurrent student): the teacher "
+                             "of a distillation is a feed-forward perceptive actor")
         a_in = int(sd["actor.0.weight"].shape[1])
         if a_in != env.num_obs:
             raise ValueError(f"teacher checkpoint {ck} has an actor of {a_in} inputs, the env's row has {env.num_obs} (env.num_observations = 47 x "
@@ -497,18 +500,15 @@ class Distiller:
         gd, lib, logstd, h = self._gru_desc[1], _lib.load(), self.student.logstd, self.state
         beta, noise = self.teacher_action_prob(), int(self.teacher_noise)
         with torch.no_grad():
-            tr.h0.copy_(h)  # the state the update's recurrence starts from
-            tr.resets[0].copy_(self._last_dones)
+            tr.rollout_begin(h, self._last_dones)  # the state the update's recurrence starts from, step 0's resets
             for n in range(T):
-                reset = self._last_dones if n == 0 else dones[n - 1]
+                reset = tr.rollout_reset(n, self._last_dones, dones)
                 _lib.check(lib.bg_distill_act_gru(N, _lib.ptr(obses[n]), obses.shape[-1], len(td), td, self.scan, gd, len(sd), sd, _lib.ptr(logstd), seed,
                                                   self._act_counter, beta, noise, _lib.ptr(reset), _lib.ptr(h), _lib.ptr(h), None, _lib.ptr(actions[n]),
                                                   _lib.ptr(labels[n]), _lib.current_stream_ptr()), "bg_distill_act_gru")
                 self._act_counter += 1
                 self.env.step_to(actions[n], obses[n + 1], priv[n + 1], buf["rewards"][n], dones[n], buf["time_outs"][n])
-            if T > 1:
-                tr.resets[1:].copy_(dones[: T - 1])
-            self._last_dones.copy_(dones[T - 1])
+            tr.rollout_end(dones, self._last_dones)
 
     def update(self):
         """num_epochs full-batch behaviour-cloning steps on the rollout's rows.  Returns the per-epoch mean losses (float64 device tensor: the loss

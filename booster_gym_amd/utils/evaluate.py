@@ -112,7 +112,7 @@ class Evaluator:
 
         from .config import load_cfg
         from .distill import checkpoint_student_overrides
-        from .runner import Runner
+        from .runner import Runner, checkpoint_memory_overrides
 
         if (checkpoint is None) == (actor is None):
             raise ValueError("Evaluator needs a checkpoint path or an actor state dict, one of the two")
@@ -121,7 +121,9 @@ class Evaluator:
         self.settle_s, self.spread = evaluation_cfg(cfg)  # (ValueError before anything is built)
         self.applied = {}
         if checkpoint is not None:
-            over = checkpoint_student_overrides(torch.load(checkpoint, map_location="cpu", weights_only=True))
+            loaded = torch.load(checkpoint, map_location="cpu", weights_only=True)
+            # a student's re-entry overrides, or the memory width of an actor trained under algorithm.rnn_hidden_size (a rule of its own)
+            over = checkpoint_student_overrides(loaded) or checkpoint_memory_overrides(loaded)
             for k, v in (over or {}).items():
                 _set_dotted(cfg, k, v)
                 self.applied[k] = v

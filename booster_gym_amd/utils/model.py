@@ -10,8 +10,9 @@ gradients), in the form its NetPlan names, on copies of the weights that one obj
 each current exactly when written or stamped at the present value of the parameters' WeightClock); the rollout-time inference + sampling is one fused HIP launch
 (`sample_actions` -> bg_actor_sample at the reference's widths on 47 inputs, bg_actor_sample_mlp at any other supported widths and on a
 frame stack of 47 H inputs).  With estimator.enabled a third network, `estimator` (47 H -> hidden -> 12), feeds the first E of its outputs to the
-actor behind the observations; the rollout runs both in one launch (bg_actor_sample_est).  A distilled student may be recurrent
-(distillation.student_memory, `memory_hidden`): a GRU cell `memory` in front of the actor, one launch per step as well (bg_actor_sample_gru).
+actor behind the observations; the rollout runs both in one launch (bg_actor_sample_est).  An actor may be recurrent (`memory_hidden`: a distilled
+student of distillation.student_memory, or PPO's own under algorithm.rnn_hidden_size): a GRU cell `memory` in front of the actor, one launch per
+step as well (bg_actor_sample_gru), and GRUTrainer around the trunk's MLPTrainer in the update.
 """
 import ctypes
 import os
@@ -629,12 +630,17 @@ class GRUTrainer:
                    (bg_gru_sequence_forward) from h0 [N][H] and resets [T][N]; returns h [B][H], the trunk's input;
       backward()   behind the trunk's backward_hidden: dh_ext = G1 W1, the gradient into the trunk's input that MLPTrainer does not produce (the
                    same layer kernel on the trunk's transposed first layer), the recurrence backwards as ONE launch (bg_gru_sequence_backward), and
-                   the bias gradients = the column sums of dgi and dgh in a fixed order (bg_elu_backward_colsum without an activation)."""
+                   the bias gradients = the column sums of dgi and dgh in a fixed order (bg_elu_backward_colsum without an activation).
+    bias_partial (PPO on a recurrent actor, algorithm.rnn_hidden_size; False: the four launches above, distillation's): the two column sums as ONE
+    launch that leaves a record per 128 rows (bg_gru_bias_partial) and a reduction descriptor for the update's deferred group (backward(finishes=)).
+    The rollout's side of the state lives here too (rollout_begin / rollout_reset / rollout_end): the one statement of which state the recurrence
+    starts from and which env enters which step with a zero state, for Distiller and Runner alike."""
 
     KIN = 64  # the zero-padded width of the cell's input rows (47 observations)
 
-    def __init__(self, cell, trunk, T, N, clock=None):
+    def __init__(self, cell, trunk, T, N, clock=None, bias_partial=False):
         self.cell, self.trunk, self.T, self.N, self.H = cell, trunk, int(T), int(N), int(cell.hidden_size)
+        self.bias_partial = bool(bias_partial)
         B, H, dev = self.T * self.N, self.H, cell.weight_ih.device
         self.B = B
         self.copies = WeightCopies([SimpleNamespace(weight=cell.weight_ih)], clock, self.KIN)
@@ -644,9 +650,27 @@ class GRUTrainer:
         self.h0 = new(self.N, H)                                                    # the state entering the iteration (detached)
         self.resets = torch.zeros(self.T, self.N, dtype=torch.uint8, device=dev)    # non-zero: the state entering step t of env n is zero
         self._zero_bias = new(H)
-        self._cs = new((B + 127) // 128 * 3 * H)
+        self._cs = new((B + 127) // 128 * (6 if self.bias_partial else 3) * H)  # (bias_partial: one record [6H] per 128 rows)
         self.x = None
         self._pending = False
+
+    # ------------------------------------------------------------------ the rollout's side of the state
+    def rollout_begin(self, state, last_dones):
+        """At the start of a rollout: the state [N][H] the update's recurrence starts from (detached: the gradient is truncated there) and step 0's
+        reset flags = the done flags of the previous iteration's last step."""
+        self.h0.copy_(state)
+        self.resets[0].copy_(last_dones)
+
+    @staticmethod
+    def rollout_reset(n, last_dones, dones):
+        """The reset flags [N] of step n's launch: an env that the step before reset enters with a zero state."""
+        return last_dones if n == 0 else dones[n - 1]
+
+    def rollout_end(self, dones, last_dones):
+        """Behind the last step: the reset flags [T][N] of the update's recurrence, and the last step's done flags for the next iteration's step 0."""
+        if self.T > 1:
+            self.resets[1:].copy_(dones[: self.T - 1])
+        last_dones.copy_(dones[self.T - 1])
 
     def forward(self, x):
         lib, st, p, c, H = _lib.load(), _lib.current_stream_ptr(), _lib.ptr, self.cell, self.H
@@ -656,16 +680,34 @@ class GRUTrainer:
                                                p(self.gates), st), "bg_gru_sequence_forward")
         return self.h
 
-    def backward(self):
+    def backward(self, finishes=None):
+        """finishes (a list; bias_partial only): receives the descriptor of the bias gradients' reduction, for the caller's deferred group; None: it
+        runs here, as a bg_reduce_group of its own."""
         lib, st, p, c, H, tr = _lib.load(), _lib.current_stream_ptr(), _lib.ptr, self.cell, self.H, self.trunk
         g1, l0 = tr.gin[1], tr.layers[0]  # dL/dz of the trunk's first layer [B][out], behind backward_hidden
         _lib.check(lib.bg_mlp_layer_forward(self.B, l0.weight.shape[0], H, p(g1), p(tr.copies.get("wt", 0)), p(self._zero_bias), p(self.dh_ext), 0, st),
                    "bg_mlp_layer_forward")
         _lib.check(lib.bg_gru_sequence_backward(self.T, self.N, H, p(self.dh_ext), p(self.gates), p(self.h_prev), p(self.resets), p(c.weight_hh), p(self.dgi),
                                                 p(self.dgh), None, st), "bg_gru_sequence_backward")
+        self._pending = True
+        if self.bias_partial:
+            _lib.check(lib.bg_gru_bias_partial(self.B, H, p(self.dgi), p(self.dgh), p(self._cs), st), "bg_gru_bias_partial")
+            fin = self.bias_finish()
+            if finishes is not None:
+                finishes.append(fin)
+            else:
+                from .utils import reduce_group
+                reduce_group([fin])
+            return
         for g, b in ((self.dgi, c.bias_ih), (self.dgh, c.bias_hh)):
             _lib.check(lib.bg_elu_backward_colsum(self.B, 3 * H, p(g), None, p(b.grad), p(self._cs), st), "bg_elu_backward_colsum")
-        self._pending = True
+
+    def bias_finish(self):
+        """The bg_reduce_problem behind bg_gru_bias_partial: the records [ceil(B / 128)][6H] added up into bias_ih.grad | bias_hh.grad."""
+        c, H, fin = self.cell, self.H, _lib.ReduceProblem()
+        fin.partial, fin.groups, fin.record, fin.n_out = self._cs.data_ptr(), (self.B + 127) // 128, 6 * H, 6 * H
+        fin.out[0], fin.out[1], fin.n[0], fin.n[1] = c.bias_ih.grad.data_ptr(), c.bias_hh.grad.data_ptr(), 3 * H, 3 * H
+        return fin
 
     def pending_wgrad_problems(self):
         """(G, A, dW, C_out, C_in (padded), C_in_real) of the cell's two weight gradients, for the grouped launch (GroupedWeightGrad.run)."""
@@ -758,9 +800,16 @@ class ActorCritic(torch.nn.Module):
         if self._memory_state is not None:
             self._memory_state.zero_()
 
+    def memory_state(self, N, device):
+        """The hidden state [N][H] that sample_actions advances in place: created (zero) on first use and when N or the device changes."""
+        if self._memory_state is None or self._memory_state.shape[0] != N or self._memory_state.device != torch.device(device):
+            self._memory_state = torch.zeros(N, self.memory_hidden, dtype=torch.float32, device=device)
+        return self._memory_state
+
     def act(self, obs):
         if self.memory_hidden:
-            raise ValueError("act: a model with memory is stateful; sample_actions carries its hidden state (PPO on a recurrent actor is out of scope)")
+            raise ValueError("act: a model with memory is stateful; sample_actions carries its hidden state (the rollout of PPO on a recurrent actor, "
+                             "algorithm.rnn_hidden_size, and of a recurrent student's play)")
         mean = self.actor(self.actor_input(obs))
         return torch.distributions.Normal(mean, torch.exp(self.logstd).expand_as(mean))
 
@@ -879,14 +928,12 @@ class ActorCritic(torch.nn.Module):
         for t in mw:
             if not t.is_contiguous():
                 raise RuntimeError("sample_actions needs contiguous tensors")
-        if self._memory_state is None or self._memory_state.shape[0] != N or self._memory_state.device != obs.device:
-            self._memory_state = torch.zeros(N, self.memory_hidden, dtype=torch.float32, device=obs.device)
+        h = self.memory_state(N, obs.device)
         key = tuple(t.data_ptr() for t in w + mw)
         if key != self._gru_key:
             layers = (_lib.MlpLayerDesc * len(lin))(*[_lib.MlpLayerDesc(l.weight.data_ptr(), l.bias.data_ptr(), l.in_features, l.out_features) for l in lin])
             self._gru_descs, self._gru_key = (self.gru_descriptor(), layers), key
         gd, layers = self._gru_descs
-        h = self._memory_state
         _lib.check(_lib.load().bg_actor_sample_gru(N, _lib.ptr(obs), obs.shape[-1], gd, len(lin), layers, _lib.ptr(self.logstd), int(seed), int(counter),
                                                    _lib.ptr(reset), _lib.ptr(h), _lib.ptr(h), _lib.ptr(mu_out), _lib.ptr(actions_out), _lib.current_stream_ptr()),
                    "bg_actor_sample_gru")

@@ -30,6 +30,10 @@ Same surface: `Runner(test=False)` parses the reference's 8 CLI flags (runner.py
             takes [observations | estimates].  The rollout's launch is then bg_actor_sample_est (both networks, the estimates kept in the buffer
             `estimates`), the update builds the actor's input from the stored rows, and behind the last PPO step the estimator takes its own
             supervised Adam steps (_estimator_update: distillation's kernels, an optimiser and a WeightClock of its own).  No forward-ahead then.
+  recurrent algorithm.rnn_hidden_size (off by default): a GRU cell in front of the actor's hidden layers.  The rollout's launch is then bg_actor_sample_gru
+            on a state [N][H] carried over steps and iterations and zeroed where an env reset; the update runs the cell over the iteration's T steps
+            from the state stored at the rollout's start (model.GRUTrainer: back-propagation through time, truncated there) around the trunk's
+            per-layer kernels, its bias gradients as one launch (bg_gru_bias_partial) among the deferred reductions, the tail as separate launches.
   multi-GPU one process per GPU (torchrun), environments sharded; per mini-epoch one float64 moments all-reduce on the side stream and ONE grouped RCCL
             launch on the main stream (gradient bucket mean, loss / KL sums, log-std gradient mean) through an own communicator (utils/rccl.py) --
             SURVEY section 8e; the enqueue-order contract of the two communicators is written in utils/parallel.py.
@@ -56,7 +60,7 @@ from .buffer import ExperienceBuffer
 from .estimator import EST_WIDTH, check_estimator_checkpoint, estimator_cfg, estimator_enabled
 from .config import load_cfg
 from .obs_norm import ObsNormalizer, check_checkpoint, normalization_cfg
-from .model import ACTOR_HIDDEN, CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, MLPTrainer, NetPlan, WeightClock, check_hidden, hidden_of, plan_network
+from .model import ACTOR_HIDDEN, CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, GRUTrainer, MLPTrainer, NetPlan, WeightClock, check_hidden, hidden_of, plan_network
 from .parallel import DataParallel
 from .recorder import Recorder
 from .utils import (actor_head_forward, actor_head_loss_backward, actor_head_sym_loss_backward, critic_head_backward, critic_head_forward, critic_values_gae, gae,
@@ -98,6 +102,53 @@ def actor_memory_of(cfg):
     if H and estimator_enabled(cfg):
         raise ValueError(f"algorithm.actor_memory = {H} is not supported with estimator.enabled: true")
     return H
+
+
+RNN_WIDTHS = (128, 256)  # the widths of the GRU cell that the rollout's and the update's kernels take
+
+
+def rnn_hidden_size_of(cfg, world_size=1):
+    """algorithm.rnn_hidden_size (legged_gym's name; an addition of this build) as the width H of the GRU cell in front of an actor that PPO trains:
+    0 (absent: the shipped yaml does not list it) = a feed-forward actor.  Pure.  ValueError naming the key for any other value than 0, 128 or 256, for
+    an algorithm.rnn_type other than "gru" (the one cell there is), for an algorithm.actor_memory of another width, and, naming both keys, with every
+    option a recurrent actor does not compose with: estimator.enabled, env.frame_stack above 1, terrain.actor_heights, algorithm.symmetry_loss,
+    algorithm.empirical_normalization, runner.num_mini_batches above 1, more than one rank."""
+    alg = cfg.get("algorithm", {}) or {}
+    H = alg.get("rnn_hidden_size", 0)
+    H = 0 if H is None else H
+    if isinstance(H, bool) or not isinstance(H, int) or H not in (0,) + RNN_WIDTHS:
+        raise ValueError(f"algorithm.rnn_hidden_size must be 0, 128 or 256 (the width of the GRU cell in front of the actor; 0 or absent: none), got {H!r}")
+    kind = alg.get("rnn_type")
+    if kind is not None and kind != "gru":
+        raise ValueError(f"algorithm.rnn_type = {kind!r}: the cell of algorithm.rnn_hidden_size is a GRU; the key, if present, must be \"gru\"")
+    if not H:
+        return 0
+    mem = alg.get("actor_memory", 0) or 0
+    if mem and mem != H:
+        raise ValueError(f"algorithm.rnn_hidden_size = {H} and algorithm.actor_memory = {mem!r} name two widths of one cell: set them equal, or one of them only")
+    K = (cfg.get("runner", {}) or {}).get("num_mini_batches", 1) or 1
+    refused = (("estimator.enabled: true", estimator_enabled(cfg)),
+               ("env.frame_stack above 1", int((cfg.get("env", {}) or {}).get("frame_stack", 1) or 1) > 1),
+               ("terrain.actor_heights: true", bool((cfg.get("terrain", {}) or {}).get("actor_heights", False))),
+               ("algorithm.symmetry_loss: true", bool(alg.get("symmetry_loss", False))),
+               ("algorithm.empirical_normalization: true", bool(alg.get("empirical_normalization", False))),
+               ("runner.num_mini_batches above 1", not isinstance(K, bool) and isinstance(K, int) and K > 1),
+               (f"more than one rank (WORLD_SIZE = {world_size})", int(world_size) > 1))
+    for what, on in refused:
+        if on:
+            raise ValueError(f"algorithm.rnn_hidden_size = {H} is not supported with {what} (a recurrent actor reads the newest single observation, "
+                             "on one rank, its update on the whole batch as sequences)")
+    return H
+
+
+def checkpoint_memory_overrides(checkpoint):
+    """{"algorithm.rnn_hidden_size": H} for a loaded checkpoint dict whose model carries memory.* and that is no student's (no "distillation" entry: an
+    actor trained under algorithm.rnn_hidden_size; a student re-enters under distill.checkpoint_student_overrides), H from memory.weight_hh; None for
+    every other checkpoint.  What evaluate.py applies so that such a checkpoint evaluates without editing the yaml."""
+    sd = checkpoint.get("model") or {}
+    if checkpoint.get("distillation") is not None or "memory.weight_hh" not in sd:
+        return None
+    return {"algorithm.rnn_hidden_size": int(sd["memory.weight_hh"].shape[1])}
 
 
 def pad_input(width):
@@ -203,17 +254,28 @@ def wgrad_products(rows, grouped, bwd_chained, split, wgrad_split):
 
 
 def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_split_bwd, chain_alternate, fused_wgrad, wgrad_split, one_stream,
-                defer_finish, one_launch_tail, fused_opt, fused_head, fused_gae, chain_values, rollout_forward, dp_active, symmetry=False):
+                defer_finish, one_launch_tail, fused_opt, fused_head, fused_gae, chain_values, rollout_forward, dp_active, symmetry=False, memory=0):
     """UpdatePlan from the switches (MLPTrainer.SPLIT ... WGRAD_SPLIT and Runner._one_stream ... _rollout_forward, by the same names in lower case;
     dp.active; symmetry = algorithm.symmetry_loss) and the shapes: critic / actor = (layer widths, padded input width), rows = the batch.  Pure: no
     tensors, no device.  symmetry: the actor's passes differentiate 2 x rows rows (the batch and its mirror images) and the rollout runs no
     forward passes for the update (ahead = False: update() mirrors the batch and runs the first mini-epoch's passes itself); a plan whose output
-    layers are not the fused head kernels is a ValueError (bg_actor_head_sym is the only form of the loss)."""
+    layers are not the fused head kernels is a ValueError (bg_actor_head_sym is the only form of the loss).  memory = H > 0
+    (algorithm.rnn_hidden_size): `actor` is the trunk behind the GRU cell, its input the cell's state of H columns, so it runs the per-layer kernels
+    beside whatever the critic runs (as on a frame stack), without forward-ahead; the cell's gradients come out of launches that bg_update_tail's sums
+    do not cover (its weight gradients' finish, its bias gradients' reduction), so the tail runs as the separate launches (one_tail = False:
+    bg_reduce_group, the weight gradients with their finish, bg_optimizer_step, which takes the norm over the whole flat gradient, the cell's
+    included); a plan without the fused heads or the deferred reductions is a ValueError."""
+    if memory and not (fused_head and fused and defer_finish and not split):
+        raise ValueError("algorithm.rnn_hidden_size needs the fused output layers of bg_head.hip, the per-layer fp32 kernels and the deferred reductions "
+                         "(no parallel.gemm_split / BG_GEMM_SPLIT, BG_DEFER_FINISH=1)")
     if symmetry and not fused_head:
         raise ValueError("algorithm.symmetry_loss needs the fused output layers of bg_head.hip (bg_actor_head_sym: an actor whose last hidden layer is "
                          "128 wide with 12 actions); this plan runs the output layers as library GEMMs")
     nets = [plan_network(w, kin, r, split, fused, chain, chain_split, chain_split_bwd and fused_head, chain_alternate, fused_wgrad)
             for (w, kin), r in ((critic, rows), (actor, 2 * rows if symmetry else rows))]
+    if memory and ((nets[1].fwd, nets[1].bwd) != ("layer", "layer") or not all(nets[1].grouped[:-1])):
+        raise ValueError(f"algorithm.rnn_hidden_size: a batch of runner.horizon_length x env.num_envs = {rows} rows is outside the range of the layer kernels "
+                         "(an even number of 64 rows or more)")
     bwd_chained = all(n.bwd == "chain_split" for n in nets)
     grouped = [(co, ci) for (w, kin), n in zip((critic, actor), nets) for ci, co, g in zip((kin,) + tuple(w[1:-1]), w[1:], n.grouped) if g]
     wgrad = wgrad_products(rows, grouped, bwd_chained, split, wgrad_split)
@@ -231,7 +293,7 @@ def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_
     sums = sum((co * ci // 4 + 15) // 16 for co, ci in grouped) + sum((w[-2] * w[-1] + w[-2] + w[-1] + 15) // 16 + 32 + sum((ci + 15) // 16 for ci in w[1:-2])
                                                                        for w, _ in (critic, actor))
     one_tail = (fused_opt and one_launch_tail and defer and finishing and all(all(n.grouped[:-1]) for n in nets) and sum(fins) + 2 <= 8
-                and sums <= TAIL_MAX_ITEMS)
+                and sums <= TAIL_MAX_ITEMS and not memory)
     return UpdatePlan(nets[0], nets[1], wgrad, fused_head, fused_gae, chain_values, one_stream and chain_values and defer and bwd_chained, defer, fused_opt,
                       one_tail, rollout_forward and chain_values and nets[1].chained and not symmetry, dp_active, bool(symmetry))
 
@@ -353,9 +415,17 @@ class Runner:
         self._est = estimator_cfg(self.cfg, self.world_size)
         # algorithm.actor_memory: a recurrent distilled student re-entering for play / evaluation / export; 0 = none, the one switch the branches below read
         self._memory = actor_memory_of(self.cfg)
-        if self._memory and not test:
-            raise ValueError(f"algorithm.actor_memory = {self._memory}: PPO on a recurrent actor is out of scope; the key is for a distilled student's "
-                             "checkpoint under play.py, evaluate.py and export_model.py (training a recurrent student: distill.py --student_memory)")
+        # algorithm.rnn_hidden_size: PPO on a recurrent actor; the same cell, and the one key under which a model with memory trains (a student's
+        # re-entry overrides alone must not start a PPO run: its critic is untrained)
+        self._rnn = rnn_hidden_size_of(self.cfg, self.world_size)
+        if self._memory and not self._rnn and not test:
+            raise ValueError(f"algorithm.actor_memory = {self._memory}: training is out of scope for this key, which is for a distilled student's checkpoint "
+                             "under play.py, evaluate.py and export_model.py; PPO on a recurrent actor (from scratch, or fine-tuning that student) is "
+                             f"algorithm.rnn_hidden_size: {self._memory} (training a recurrent student: distill.py --student_memory)")
+        self._memory = self._memory or self._rnn
+        if self._rnn and not test and (int((self.cfg.get("parallel", {}) or {}).get("gemm_split", 0) or 0) or MLPTrainer.SPLIT):
+            raise ValueError(f"algorithm.rnn_hidden_size = {self._rnn} is not supported with parallel.gemm_split / BG_GEMM_SPLIT (the trunk behind the cell "
+                             "runs the per-layer fp32 kernels): use gemm_split 0")
         self._set_seed()
         task = self.cfg["basic"]["task"]
         if task not in TASKS:
@@ -455,6 +525,13 @@ class Runner:
         self._logstd_grad_view = self.model.logstd.grad.view(-1)
         self._logstd_off = (self._logstd_grad_view.data_ptr() - self.optimizer.grad.data_ptr()) // 4  # position of logstd in the flat buffers
         self._actor_tr, self._critic_tr = MLPTrainer(self.model.actor, clock=self._clock), MLPTrainer(self.model.critic, clock=self._clock)
+        # algorithm.rnn_hidden_size: the cell around the actor's trunk over the T steps of an iteration (model.GRUTrainer, as utils/distill.py; its bias
+        # gradients as ONE launch that joins the deferred reductions) and the done flags of the previous iteration's last step; None = a feed-forward
+        # actor (or a recurrent one that only plays), the one switch rollout() and update() read.  The state itself is the model's (sample_actions).
+        self._mem_tr = None
+        if self._rnn and not test:
+            self._mem_tr = GRUTrainer(self.model.memory, self._actor_tr, T, N, clock=self._clock, bias_partial=True)
+            self._last_dones = torch.zeros(N, dtype=torch.uint8, device=dev)
         gs = (self.cfg.get("parallel", {}) or {}).get("gemm_split", 0)
         if gs:  # yaml switch for the split-bf16 GEMMs (process-wide, like the environment variable)
             if int(gs) not in (6, 9):
@@ -488,6 +565,9 @@ class Runner:
         self._fused_head = A == 12 and self.model.actor[-1].in_features == 128 and self.model.critic[-1].in_features == 128
         if self._symmetry and not self._fused_head:
             raise ValueError("algorithm.symmetry_loss needs the fused output layers of bg_head.hip: an actor whose last hidden layer is 128 wide with 12 actions")
+        if self._mem_tr is not None and not (self._fused_head and self._pad_actor == GRUTrainer.KIN):
+            raise ValueError(f"algorithm.rnn_hidden_size = {self._rnn} needs the fused output layers of bg_head.hip (12 actions) and an observation of at "
+                             f"most {GRUTrainer.KIN} columns (env.num_observations = {no})")
         self._old_mu = torch.zeros(B, A, device=dev)
         self._values_all = torch.zeros(B + N, device=dev)
         self._head_scratch_a, self._head_scratch_c = head_scratch(dev), head_scratch(dev)
@@ -560,7 +640,8 @@ class Runner:
         if ck_mem != getattr(self, "_memory", 0):
             raise ValueError(f"checkpoint {ck} has " + (f"a recurrent actor (memory.* of width {ck_mem})" if ck_mem else "no memory.* (its actor is not recurrent)")
                              + f", the config has algorithm.actor_memory = {getattr(self, '_memory', 0)}: set algorithm.actor_memory to {ck_mem}"
-                             + (" (a student of distillation.student_memory; evaluate.py and export_model.py do so from the checkpoint)" if ck_mem else ""))
+                             + (" (a student of distillation.student_memory, or an actor trained under algorithm.rnn_hidden_size, the key to train it "
+                                "further under; evaluate.py and export_model.py set the width from the checkpoint)" if ck_mem else ""))
         ck_ain, a_in = int(model_dict["model"]["actor.0.weight"].shape[1]), self.model.actor[0].in_features
         est = getattr(self, "_est", None)
         check_estimator_checkpoint(ck, model_dict, est, ck_ain, a_in)  # (before the frame-stack message below can misfire on a width that differs by E)
@@ -641,7 +722,10 @@ class Runner:
                                                       "_rollout_forward"))
         widths = lambda tr: (tr.layers[0].in_features,) + tuple(l.out_features for l in tr.layers)
         kin_a = self._actor_in.shape[-1] if self._actor_in is not None else self.env.num_obs + self._est_cols  # (the actor's true input width)
-        plan = plan_update((widths(ct), self._critic_in.shape[-1]), (widths(at), kin_a), self._old_logp.numel(), dp_active=self.dp.active, symmetry=self._symmetry, **sw)
+        if self._mem_tr is not None:  # the trunk's input is the cell's state [B][H], not the padded observation rows (those are the cell's)
+            kin_a = self._memory
+        plan = plan_update((widths(ct), self._critic_in.shape[-1]), (widths(at), kin_a), self._old_logp.numel(), dp_active=self.dp.active, symmetry=self._symmetry,
+                           memory=self._memory if self._mem_tr is not None else 0, **sw)
         ct.plan, at.plan = plan.critic, plan.actor
         c_out = ct.layers[-1]
         ct.value_head = (c_out.weight.reshape(-1), c_out.bias, self._values_all) if plan.chain_values else None
@@ -784,12 +868,17 @@ class Runner:
             # the default actor samples from a packed copy of its parameters: laid out here, once for the T steps and in every rollout (whatever changed
             # the parameters since the last one -- optimiser, checkpoint, broadcast -- is behind this launch on the stream); None for other architectures
             packed = self.model.pack_actor()
+            mt = self._mem_tr
+            if mt is not None:  # a recurrent actor: the state the update's recurrence starts from = the state as the last rollout left it
+                mt.rollout_begin(self.model.memory_state(self.env.num_envs, obses.device), self._last_dones)
             for n in range(T):
                 if plan.ahead and n + 1 - start >= g:
                     self._forward_rows(start, n, main)  # rows of steps start .. n: on the side stream, beside this step's launches
                     start = n + 1
                 if self._est is not None:  # estimator and actor in ONE launch; the estimate the actor read is kept: the update's rows are these
                     self.model.sample_actions(obses[n], buf["actions"][n], seed, self._act_counter, est_out=buf["estimates"][n])
+                elif mt is not None:  # cell and trunk in ONE launch that advances the state in place; an env the step before reset enters with a zero state
+                    self.model.sample_actions(obses[n], buf["actions"][n], seed, self._act_counter, reset=mt.rollout_reset(n, self._last_dones, buf["dones"]))
                 elif norm is None:
                     self.model.sample_actions(obses[n], buf["actions"][n], seed, self._act_counter, scan=scan, packed=packed)
                 else:  # the buffer keeps the raw rows; the actor samples from their normalised copy (one more launch per step: bg_obs_normalize)
@@ -799,6 +888,8 @@ class Runner:
                 self.env.step_to(buf["actions"][n], obses[n + 1], priv[n + 1], buf["rewards"][n], buf["dones"][n], buf["time_outs"][n])
             if plan.ahead:
                 self._forward_rows(start, T, main)  # ... and the observation after the last step: the critic's last_values rows
+            if mt is not None:
+                mt.rollout_end(buf["dones"], self._last_dones)
         self._fwd_plan = plan if plan.ahead else None
 
     def _forward_rows(self, a, b, main):
@@ -937,8 +1028,12 @@ class Runner:
         a_out, c_out = self._actor_tr.layers[-1], self._critic_tr.layers[-1]
         with torch.no_grad():
             # old mu through the same kernels as the mini-epochs: the first ratio is exactly 1
+            ha0 = None
             if ahead:
                 old_mu = self._old_mu
+            elif self._mem_tr is not None:  # ... the cell over the T steps from h0, then the trunk; mini-epoch 0 reuses this pass (no parameter changes in between)
+                ha0 = self._actor_hidden(self._actor_tr, obs_flat)
+                old_mu = actor_head_forward(ha0[:B], a_out.weight, a_out.bias, self._old_mu)
             elif plan.fused_head:
                 old_mu = actor_head_forward(self._actor_tr.forward_hidden(obs_flat)[:B], a_out.weight, a_out.bias, self._old_mu)
             else:
@@ -954,14 +1049,26 @@ class Runner:
                          self._ret.view(B), self._values_all)
         # whole: the batch as the rows of one optimiser step; steps: what the steps of a mini-epoch run on (runner.num_mini_batches > 1: _mini_batch_begin)
         return types.SimpleNamespace(cfg=cfg, buf=buf, T=T, N=N, B=B, alg=alg, ahead=ahead, plan=plan, logstd_flat=logstd_flat, old_logstd=old_logstd,
-                                     main=torch.cuda.current_stream(), side=self._side_stream, mirrors=None, whole=whole, steps=[whole])
+                                     main=torch.cuda.current_stream(), side=self._side_stream, mirrors=None, whole=whole, steps=[whole], ha0=ha0)
 
     # ------------------------------------------------------------------ the pieces of a mini-epoch, each on the rows of a StepRows, on the current stream
+    def _actor_hidden(self, at, x):
+        """The actor's last hidden activations on the rows x; with a recurrent actor (algorithm.rnn_hidden_size) x are the cell's padded [B][64] rows:
+        gi on all of them, the recurrence from h0 with the resets (GRUTrainer.forward), then the trunk on h."""
+        return at.forward_hidden(x if self._mem_tr is None else self._mem_tr.forward(x))
+
+    def _actor_backward_hidden(self, at, fins):
+        """The actor's backward-data pass; with a recurrent actor the trunk's, then the cell's through time (GRUTrainer.backward: truncated at h0), whose
+        bias gradients join the deferred reductions."""
+        at.backward_hidden(finishes=fins)
+        if self._mem_tr is not None:
+            self._mem_tr.backward(finishes=fins)
+
     def _forward_hidden(self, v):
         """The hidden layers of both networks on v's rows: one grouped launch, or one pass per network.  Returns their last hidden activations."""
         if v.plan.one_stream:
             return MLPTrainer.forward_hidden_group([(v.ct, v.x_c, v.train_rows), (v.at, v.x_a, None)])
-        return v.ct.forward_hidden(v.x_c, train_rows=v.train_rows), v.at.forward_hidden(v.x_a)
+        return v.ct.forward_hidden(v.x_c, train_rows=v.train_rows), self._actor_hidden(v.at, v.x_a)
 
     def _head_values(self, v, hc):
         """The critic's values of v.x_c's rows in v.values: left there by the chained forward launch's value head (plan.chain_values: from the registers
@@ -1048,7 +1155,7 @@ class Runner:
                 MLPTrainer.backward_hidden_group([ct, at], fins)
             else:
                 ct.backward_hidden(finishes=fins)
-                at.backward_hidden(finishes=fins)
+                self._actor_backward_hidden(at, fins)
         else:
             g_val, g_mu = self._library_loss(u, v, at.forward(v.x_a), ct.forward(v.x_c, train_rows=v.train_rows).squeeze(-1)[: v.rows])
             self._exchange_sums()  # exchange (3)
@@ -1070,7 +1177,12 @@ class Runner:
         fins = fin_c = fin_a = None
         if plan.fused_head:
             fins, fin_c, fin_a = self._deferred_finishes(plan)
-            ha = at.acts[2] if have_fwd else at.forward_hidden(v.x_a)
+            if have_fwd:
+                ha = at.acts[2]
+            elif u.ha0 is not None:  # a recurrent actor's mini-epoch 0: old mu's forward pass, run through these same launches on these parameters
+                ha, u.ha0 = u.ha0, None
+            else:
+                ha = self._actor_hidden(at, v.x_a)
             with torch.cuda.stream(side):
                 self._critic_loss_head(v, hc, values, fin_c)
                 ct.backward_hidden(finishes=fins)
@@ -1080,7 +1192,7 @@ class Runner:
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
                     self._exchange_sums()  # exchange (3): loss / KL sums, hidden under the backward passes
-            at.backward_hidden(finishes=fins)
+            self._actor_backward_hidden(at, fins)
         else:
             mu = at.forward(v.x_a)
             main.wait_stream(side)
@@ -1109,7 +1221,8 @@ class Runner:
                     self._exchange_sums()  # exchange (3), beside the weight gradients
         # all weight gradients after both backward chains, alone on the GPU: one launch pair for the six hidden layers (shapes outside the
         # kernel's range, or MLPTrainer.FUSED_WGRAD = False: library GEMMs, layer by layer); one_tail: their finish inside bg_update_tail
-        wg_partial = v.wgrad.run((v.ct, v.at), plan.wgrad, one_tail)
+        mt = self._mem_tr  # (a recurrent actor: the cell's two weight gradients ride in the same launch, its padded W_ih among the copies)
+        wg_partial = v.wgrad.run((v.ct, v.at) if mt is None else (v.ct, v.at, mt), plan.wgrad, one_tail)
         if plan.defer and plan.ranks:
             main.wait_stream(side)
         if one_tail and plan.ranks:
@@ -1125,6 +1238,8 @@ class Runner:
             # same launch instead of six strided torch copies inside the chains of the next mini-epoch
             if mirrors is None:
                 ms = v.ct.copies.descriptors(self.optimizer.flat, v.ct.plan) + v.at.copies.descriptors(self.optimizer.flat, v.at.plan)
+                if mt is not None:
+                    ms += mt.copies.descriptors(self.optimizer.flat, v.at.plan)
                 mirrors = (_lib.ParamMirror * len(ms))(*ms) if 0 < len(ms) <= 16 else None
             if one_tail and not plan.ranks:
                 self.optimizer.step_tail(wg_partial, [fin_c, fin_a] + fins, self._stats, self._stats_acc, self._stats_last, 4, B, alg["desired_kl"],
@@ -1146,6 +1261,8 @@ class Runner:
         self._clock.tick()  # the parameters have changed: every weight copy of every trainer over them is stale, but those this launch listed and wrote
         if fused_tail and mirrors is not None:
             v.ct.copies.stamp(); v.at.copies.stamp()
+            if mt is not None:
+                mt.copies.stamp()
         u.mirrors = mirrors
 
     def _plan_chain_split(self, x_c, x_a, plan, ct=None, at=None):
@@ -1230,6 +1347,9 @@ class Runner:
         obs, infos = self.env.reset()
         self.buffer["obses"][0].copy_(obs)
         self.buffer["privileged_obses"][0].copy_(infos["privileged_obs"])
+        if self._mem_tr is not None:  # a recurrent actor starts (and, from a checkpoint, resumes: the state is not saved) on a reset env with a zero state
+            self.model.memory_state(self.env.num_envs, obs.device).zero_()
+            self._last_dones.zero_()
         # (+1 with the terrain curriculum: the sum of this rank's terrain levels)
         # (+1 with the estimator, last: its loss rides in the iteration's one host read)
         n = 2 * self._n_stats + 1 + 4 + _lib.NUM_REWARD_TERMS + 4 + (1 if self.env.terrain.curriculum else 0) + (1 if self._est is not None else 0)

@@ -2,8 +2,8 @@
 the reference's deployment code (deploy/utils/policy.py:9) can load what this framework trains.  The actor's widths are read from the checkpoint's tensors (any supported architecture, with or without the terrain height
 scan, a frame stack or the actor's own height scan, exports without editing the YAML); the TorchScript module is still a plain Sequential.  A checkpoint trained with
 algorithm.empirical_normalization carries its observation statistics: they are folded into the actor's first layer, so the exported module takes raw observations.
-A recurrent student (distillation.student_memory: the checkpoint carries "memory.*") exports as a STATEFUL module, utils/model.py's RecurrentActor; the
-script prints its contract.  tools/play_oracle.py does not take one yet."""
+A recurrent actor (algorithm.rnn_hidden_size, or a student of distillation.student_memory: the checkpoint carries "memory.*", from which the cell's
+width is read) exports as a STATEFUL module, utils/model.py's RecurrentActor; the script prints its contract."""
 import argparse
 import glob
 import os

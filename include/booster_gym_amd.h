@@ -434,6 +434,13 @@ int bg_gru_sequence_forward(int32_t T, int32_t N, int32_t H, const float* gi, co
  * dh0 [N][H] (may be NULL): the carry left after step 0.  Deterministic. */
 int bg_gru_sequence_backward(int32_t T, int32_t N, int32_t H, const float* dh_ext, const float* gates, const float* h_prev, const uint8_t* reset,
                              const float* W_hh, float* dgi, float* dgh, float* dh0, void* stream);
+/* The cell's bias gradients of a PPO update on a recurrent actor (T1.yaml algorithm.rnn_hidden_size), without their finish: ONE launch in which
+ * workgroup g sums rows [128 g, min(128 g + 128, B)) of dgi and dgh ([B][3H] each, as bg_gru_sequence_backward leaves them) down their columns and writes
+ * record g of `records` ([ceil(B / 128)][6H] floats) = dgi's 3H column sums | dgh's.  Rows at or beyond B are never read, nothing is written past record
+ * ceil(B / 128); fixed order, no atomics: deterministic.  The finish is the caller's bg_reduce_problem with partial = records, groups = ceil(B / 128),
+ * record = n_out = 6H, out[0] = b_ih's gradient, out[1] = b_hh's, n = 3H each, in a bg_reduce_group / bg_update_tail.  B >= 1; H = 128 or 256 (else -4);
+ * the three pointers 16-byte aligned (-1). */
+int bg_gru_bias_partial(int32_t B, int32_t H, const float* dgi, const float* dgh, float* records, void* stream);
 /* Fused global-norm clip + Adam over one flat parameter buffer (runner.py:162-165); lr is read from device memory
  * so the KL-adaptive schedule (runner.py:174-180) needs no host sync.  gnorm_scratch [1] device float64. */
 int bg_adam_step(int32_t n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const float* lr_device, int32_t step,

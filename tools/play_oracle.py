@@ -13,7 +13,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def load_actor(path):
+def load_actor(path, memory=False):
+    """The actor's layers.  memory: the caller runs the cell of a recurrent actor in front of them (load_memory); without it a checkpoint that
+    carries memory.* is a ValueError, because its layers are the trunk behind the cell and read the cell's state, not the observation."""
     if path.endswith(".npz"):
         W = np.load(path)
         return [(W[f"{i}.weight"], W[f"{i}.bias"]) for i in (0, 2, 4, 6)]
@@ -21,9 +23,9 @@ def load_actor(path):
 
     ck = torch.load(path, map_location="cpu", weights_only=True)
     sd = ck["model"]
-    if "memory.weight_ih" in sd:
-        raise ValueError(f"{path} is a recurrent student (distillation.student_memory: it carries memory.*): not supported here for now; "
-                         "play.py and evaluate.py run it")
+    if "memory.weight_ih" in sd and not memory:
+        raise ValueError(f"{path} is a recurrent student or actor (distillation.student_memory, algorithm.rnn_hidden_size: it carries memory.*): its "
+                         "layers read the cell's state; load them with load_actor(path, memory=True) and the cell with load_memory(path)")
     layers = [(sd[f"actor.{i}.weight"].numpy(), sd[f"actor.{i}.bias"].numpy()) for i in (0, 2, 4, 6)]
     if ck.get("obs_normalizer") is not None:
         # algorithm.empirical_normalization: the actor was trained on (x - mean) / (sqrt(var) + eps); the first layer takes the statistics in, so the
@@ -45,6 +47,41 @@ def load_estimator(path):
     if not idx:
         return None
     return [(sd[f"estimator.{i}.weight"].numpy(), sd[f"estimator.{i}.bias"].numpy()) for i in idx], len(ck["estimator"]["targets"])
+
+
+def load_memory(path):
+    """The GRU cell in front of a recurrent actor (algorithm.rnn_hidden_size, or a student of distillation.student_memory: "memory.*" in the
+    checkpoint's model) as a GRUMemory, or None: the actor then reads the cell's state instead of the observation."""
+    if path.endswith(".npz"):
+        return None
+    import torch
+
+    sd = torch.load(path, map_location="cpu", weights_only=True)["model"]
+    if "memory.weight_ih" not in sd:
+        return None
+    return GRUMemory(*[sd[f"memory.{k}"].numpy() for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")])
+
+
+class GRUMemory:
+    """The deploy side of a recurrent actor: torch.nn.GRUCell's equations (gate order r | z | n) in float64 on one row, the state zero at the start
+    and after reset()."""
+
+    def __init__(self, weight_ih, weight_hh, bias_ih, bias_hh):
+        self.w_ih, self.w_hh, self.b_ih, self.b_hh = (np.asarray(t, dtype=np.float64) for t in (weight_ih, weight_hh, bias_ih, bias_hh))
+        self.hidden = int(self.w_hh.shape[1])
+        self.reset()
+
+    def reset(self):
+        self.h = np.zeros(self.hidden)
+
+    def step(self, x):
+        """One step on the newest single observation x; returns the new state [hidden] (kept: the next step starts from it)."""
+        H, sig = self.hidden, lambda v: 1.0 / (1.0 + np.exp(-v))
+        gi, gh = self.w_ih @ np.asarray(x, dtype=np.float64) + self.b_ih, self.w_hh @ self.h + self.b_hh
+        r, z = sig(gi[:H] + gh[:H]), sig(gi[H : 2 * H] + gh[H : 2 * H])
+        n = np.tanh(gi[2 * H :] + r * gh[2 * H :])
+        self.h = (1.0 - z) * n + z * self.h
+        return self.h
 
 
 def mlp(layers, x):
@@ -124,7 +161,7 @@ def gait_frequency(cmd, cfg_commands, max_lin=1.0, max_ang=1.0):
     return lo + min(1.0, mag / max(max_lin, max_ang)) * (hi - lo)
 
 
-def rollout(layers, cmd, seconds, cfg=None, dyn=None, model=None, height_points=None, estimator=None):
+def rollout(layers, cmd, seconds, cfg=None, dyn=None, model=None, height_points=None, estimator=None, memory=None):
     from booster_gym_amd.utils.config import load_cfg
     from booster_gym_amd.utils.urdf import load_model
     from oracle import task_ref as tr
@@ -145,7 +182,10 @@ def rollout(layers, cmd, seconds, cfg=None, dyn=None, model=None, height_points=
     dec, dt = cfg["control"]["decimation"], cfg["sim"]["dt"]
     P = 0 if height_points is None else len(height_points)  # terrain.actor_heights: the row ends with the newest scan, not stacked
     est_layers, E = estimator if estimator is not None else (None, 0)  # estimator.enabled: E estimates behind the observations
-    stack = FrameStack(actor_frames(layers, scan=P + E))  # (H = 1: the single observation itself)
+    # a recurrent actor (memory: a GRUMemory): the cell reads the newest single observation and the trunk its state, zero at the start
+    stack = FrameStack(1 if memory is not None else actor_frames(layers, scan=P + E))  # (H = 1: the single observation itself)
+    if memory is not None:
+        memory.reset()
     traj = []
     for it in range(int(round(seconds / dt))):
         if it % dec == 0:  # play_mujoco.py:733-748
@@ -160,6 +200,8 @@ def rollout(layers, cmd, seconds, cfg=None, dyn=None, model=None, height_points=
                 x = np.concatenate([x, height_scan(root, height_points, cfg)])
             if E:
                 x = np.concatenate([x, mlp(est_layers, x)[:E]])
+            if memory is not None:
+                x = memory.step(x)
             for k, (w, b) in enumerate(layers):
                 x = w @ x + b
                 if k < 3:
@@ -178,6 +220,7 @@ if __name__ == "__main__":
     ap.add_argument("--cmd", type=float, nargs=3, default=[0.5, 0.0, 0.0])
     ap.add_argument("--seconds", type=float, default=8.0)
     a = ap.parse_args()
-    tr_ = rollout(load_actor(a.policy), a.cmd, a.seconds, height_points=load_height_points(a.policy), estimator=load_estimator(a.policy))
+    tr_ = rollout(load_actor(a.policy, memory=True), a.cmd, a.seconds, height_points=load_height_points(a.policy), estimator=load_estimator(a.policy),
+                  memory=load_memory(a.policy))
     up = 1 - 2 * (tr_[-1, 3] ** 2 + tr_[-1, 4] ** 2)
     print(f"cmd {a.cmd}: final pos {np.round(tr_[-1, :3], 3)}, mean velocity {np.round((tr_[-1, :2] - tr_[0, :2]) / a.seconds, 3)}, min height {tr_[:, 2].min():.3f}, upright {up:.3f}")
