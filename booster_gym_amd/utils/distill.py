@@ -56,11 +56,13 @@ from ..envs.t1 import MAX_CRITIC_INPUT, MAX_FRAME_STACK, frame_stack_of
 from .buffer import ExperienceBuffer
 from .config import load_cfg
 from .estimator import estimator_enabled
-from .model import CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, GRUTrainer, MLPTrainer, WeightClock, check_hidden, hidden_of, plan_network
+from .model import CRITIC_HIDDEN, ActorCritic, WeightClock, check_hidden, hidden_of, layer_descriptors, pad_input
+from .optim import FlatAdam
 from .recorder import Recorder
-from .runner import FlatAdam, hidden_widths, pad_input, wgrad_products
+from .runner import hidden_widths
+from .supervised import SupervisedTrainer
 from .terrain import actor_heights_of, height_scan_points
-from .utils import head_scratch, mirror_rows, reduce_group
+from .utils import mirror_rows
 
 DEFAULTS = {"teacher_checkpoint": None, "student_hidden": [256, 128, 128], "num_epochs": 5, "learning_rate": 1.0e-3, "max_grad_norm": 1.0,
             "student_noise_std": 0.1, "student_frame_stack": None, "symmetric_coef": 0.0, "teacher_action_prob": 0.0, "teacher_action_iterations": 0,
@@ -318,31 +320,19 @@ class Distiller:
             self._act_mirror = ((ctypes.c_int32 * A)(*[int(v) for v in act_src]), (ctypes.c_float * A)(*[float(v) for v in act_sign]))
             self._obs_mirror = (obs_src.tolist() + [-1] * (kin - len(obs_src)), obs_sign.tolist() + [1.0] * (kin - len(obs_sign)))
         self._student_in = torch.zeros(rows, kin, device=dev)  # (the padded columns stay zero)
-        self._clock = WeightClock()  # (of the student's actor parameters; one trainer reads it)
-        self._trainer = tr = MLPTrainer(self.student.actor, clock=self._clock)
-        widths = (tr.layers[0].in_features,) + tuple(l.out_features for l in tr.layers)
-        sw = MLPTrainer
-        if self.memory:  # the trunk's input is the cell's state [B][H]: the per-layer fp32 kernels (the chains take a 64-column input only)
-            tr.plan = plan = plan_network(widths, self.memory, rows, 0, True, False, False, False, False, True)
-        else:
-            tr.plan = plan = plan_network(widths, kin, rows, sw.SPLIT, sw.FUSED, sw.CHAIN, sw.CHAIN_SPLIT, sw.CHAIN_SPLIT_BWD, sw.CHAIN_ALTERNATE, sw.FUSED_WGRAD)
-        if "library" in (plan.fwd, plan.bwd) or not all(plan.grouped[:-1]):
-            raise ValueError(f"distillation: a batch of runner.horizon_length x env.num_envs = {T} x {N} = {self.B} rows is outside the range of the layer "
-                             "kernels (an even number of 64 rows or more)")
-        shapes = [(co, ci) for ci, co in zip((kin,) + widths[1:-2], widths[1:-1])]
-        # the products of the grouped weight-gradient launch, by runner.plan_update's rule: the bf16 splits behind the chained split backward only
-        self._wgrad_terms = 0 if self.memory else wgrad_products(rows, shapes, plan.bwd == "chain_split", sw.SPLIT, sw.WGRAD_SPLIT)
+        self._clock = WeightClock()  # (of the student's trained parameters; one trainer reads it)
+        # the supervised update: the actor's MLPTrainer, with a memory the cell around it (model.GRUTrainer), the statistics [squared errors (, squared
+        # mean asymmetries)]; its plan is resolved once, here (a batch the layer kernels cannot take is a ValueError before the first iteration)
+        self._sup = SupervisedTrainer("distillation", self.student.actor, self.optimizer, self._clock, rows, kin, n_stats=2 if self.symmetry else 1,
+                                      **({"cell": self.student.memory, "steps": T} if self.memory else {}))
+        self._sup.resolve_plan()
         if self.memory:
-            # the cell around the trunk (model.GRUTrainer), its rollout state [N][H] (advanced in place by bg_distill_act_gru, zero at begin()) and the
-            # done flags of the previous iteration's last step: the resets of this iteration's step 0
-            self._memory_trainer = GRUTrainer(self.student.memory, tr, T, N, clock=self._clock)
+            # the cell's rollout state [N][H] (advanced in place by bg_distill_act_gru, zero at begin()) and the done flags of the previous iteration's
+            # last step: the resets of this iteration's step 0
             self.state = torch.zeros(N, self.memory, device=dev)
             self._last_dones = torch.zeros(N, dtype=torch.uint8, device=dev)
             self._gru_desc = (None, None)
-        self._wgrad = GroupedWeightGrad()
-        self._head_scratch = head_scratch(dev)
-        self._stats = torch.zeros(2 if self.symmetry else 1, dtype=torch.float64, device=dev)  # squared errors (, squared mean asymmetries)
-        self._losses = torch.zeros(self.dcfg.num_epochs, self._stats.numel(), dtype=torch.float64, device=dev)
+        self._losses = torch.zeros(self.dcfg.num_epochs, self._sup.stats.numel(), dtype=torch.float64, device=dev)
         self._act_counter = 0
         self._descs = (None, None, None)
         self.iteration_count = 0
@@ -440,9 +430,7 @@ class Distiller:
         lins = [[m for m in net.actor if isinstance(m, torch.nn.Linear)] for net in (self.student, self.teacher)]
         key = tuple(t.data_ptr() for lin in lins for l in lin for t in (l.weight, l.bias))
         if key != self._descs[0]:
-            arrs = [(_lib.MlpLayerDesc * len(lin))(*[_lib.MlpLayerDesc(l.weight.data_ptr(), l.bias.data_ptr(), l.in_features, l.out_features) for l in lin])
-                    for lin in lins]
-            self._descs = (key, arrs[0], arrs[1])
+            self._descs = (key, layer_descriptors(lins[0]), layer_descriptors(lins[1]))
         return self._descs[1], self._descs[2]
 
     def teacher_action_prob(self):
@@ -451,99 +439,55 @@ class Distiller:
 
     def rollout(self):
         """T env steps with the student's sampled actions (with distillation.teacher_action_prob: the teacher's on a share beta of the rows); every
-        visited row and the teacher's mean action on it are kept."""
-        buf, T, N = self.buffer, self.T, self.N
-        obses, priv, actions, labels = buf["obses"], buf["privileged_obses"], buf["actions"], buf["teacher_mu"]
+        visited row and the teacher's mean action on it are kept.  One launch per env step for both networks, its kind chosen once in front of the
+        loop (the mixing by beta_0, not by the decayed beta); a recurrent student's also advances the state in place, and an env that the step
+        before reset enters with a zero state (dones[n - 1]; at step 0 the previous iteration's last flags)."""
+        buf, T, N, p = self.buffer, self.T, self.N, _lib.ptr
+        obses, priv, actions, labels, dones = buf["obses"], buf["privileged_obses"], buf["actions"], buf["teacher_mu"], buf["dones"]
         seed = int(self.cfg["basic"]["seed"]) + 1000003  # (Runner's rollout seed of rank 0)
         sd, td = self._descriptors()
-        lib, logstd = _lib.load(), self.student.logstd
-        if self.memory:
-            return self._rollout_memory(sd, td, seed)
-        if self.beta0 > 0:  # DAgger's mixing: one launch of its own kind on the same buffers, the student's rows its own with a longer history
-            beta, noise = self.teacher_action_prob(), int(self.teacher_noise)
-            sobs = buf["student_obses"] if self.history else obses
-            with torch.no_grad():
-                for n in range(T):
-                    _lib.check(lib.bg_distill_act_mix(N, _lib.ptr(obses[n]), obses.shape[-1], _lib.ptr(sobs[n]), sobs.shape[-1], len(sd), sd, len(td), td, self.scan,
-                                                      _lib.ptr(logstd), seed, self._act_counter, beta, noise, None, _lib.ptr(actions[n]), _lib.ptr(labels[n]),
-                                                      _lib.current_stream_ptr()), "bg_distill_act_mix")
-                    self._act_counter += 1
-                    self.env.step_to(actions[n], obses[n + 1], priv[n + 1], buf["rewards"][n], buf["dones"][n], buf["time_outs"][n],
-                                     **({"student_obs": sobs[n + 1]} if self.history else {}))
-            return
-        if self.history:
-            sobs = buf["student_obses"]
-            with torch.no_grad():
-                for n in range(T):
-                    _lib.check(lib.bg_distill_act_hist(N, _lib.ptr(obses[n]), obses.shape[-1], _lib.ptr(sobs[n]), sobs.shape[-1], len(sd), sd, len(td), td, self.scan,
-                                                       _lib.ptr(logstd), seed, self._act_counter, None, _lib.ptr(actions[n]), _lib.ptr(labels[n]),
-                                                       _lib.current_stream_ptr()), "bg_distill_act_hist")
-                    self._act_counter += 1
-                    self.env.step_to(actions[n], obses[n + 1], priv[n + 1], buf["rewards"][n], buf["dones"][n], buf["time_outs"][n], student_obs=sobs[n + 1])
-            return
+        logstd, beta, noise, mt = self.student.logstd, self.teacher_action_prob(), int(self.teacher_noise), self._sup.gru
+        sobs = buf["student_obses"] if self.history else obses  # the student's rows: its own with a longer history
+        # what the four launches take between the teacher's rows and the outputs: the student's rows, the networks, the noise stream (, the mixing)
+        own, nets, rng = (lambda n: (p(sobs[n]), sobs.shape[-1])), (len(sd), sd, len(td), td, self.scan), (lambda: (p(logstd), seed, self._act_counter))
+        if mt is not None:  # a recurrent student (beta = 0 is its plain form): the cell between the networks, the resets and the state behind the mixing
+            m, h = self.student.memory, self.state
+            key = tuple(t.data_ptr() for t in (m.weight_ih, m.weight_hh, m.bias_ih, m.bias_hh))
+            if key != self._gru_desc[0]:
+                self._gru_desc = (key, self.student.gru_descriptor())
+            gnets = (len(td), td, self.scan, self._gru_desc[1], len(sd), sd)
+            name, mid = "bg_distill_act_gru", lambda n: gnets + rng() + (beta, noise, p(mt.rollout_reset(n, self._last_dones, dones)), p(h), p(h))
+        elif self.beta0 > 0:  # DAgger's mixing: one launch of its own kind on the same buffers
+            name, mid = "bg_distill_act_mix", lambda n: own(n) + nets + rng() + (beta, noise)
+        elif self.history:
+            name, mid = "bg_distill_act_hist", lambda n: own(n) + nets + rng()
+        else:
+            name, mid = "bg_distill_act", lambda n: nets + rng()
+        launch, student_obs = getattr(_lib.load(), name), (lambda n: {"student_obs": sobs[n + 1]}) if self.history else (lambda n: {})
         with torch.no_grad():
+            if mt is not None:
+                mt.rollout_begin(h, self._last_dones)  # the state the update's recurrence starts from, step 0's resets
             for n in range(T):
-                _lib.check(lib.bg_distill_act(N, _lib.ptr(obses[n]), obses.shape[-1], len(sd), sd, len(td), td, self.scan, _lib.ptr(logstd), seed, self._act_counter,
-                                              None, _lib.ptr(actions[n]), _lib.ptr(labels[n]), _lib.current_stream_ptr()), "bg_distill_act")
+                _lib.check(launch(N, p(obses[n]), obses.shape[-1], *mid(n), None, p(actions[n]), p(labels[n]), _lib.current_stream_ptr()), name)
                 self._act_counter += 1
-                self.env.step_to(actions[n], obses[n + 1], priv[n + 1], buf["rewards"][n], buf["dones"][n], buf["time_outs"][n])
-
-    def _rollout_memory(self, sd, td, seed):
-        """rollout() of a recurrent student: one launch per env step, bg_distill_act_gru, which also advances the state in place; an env that the
-        step before reset enters with a zero state (dones[n - 1]; at step 0 the previous iteration's last flags).  beta = 0 is the plain form."""
-        buf, T, N, tr = self.buffer, self.T, self.N, self._memory_trainer
-        obses, priv, actions, labels, dones = buf["obses"], buf["privileged_obses"], buf["actions"], buf["teacher_mu"], buf["dones"]
-        m = self.student.memory
-        key = tuple(t.data_ptr() for t in (m.weight_ih, m.weight_hh, m.bias_ih, m.bias_hh))
-        if key != self._gru_desc[0]:
-            self._gru_desc = (key, self.student.gru_descriptor())
-        gd, lib, logstd, h = self._gru_desc[1], _lib.load(), self.student.logstd, self.state
-        beta, noise = self.teacher_action_prob(), int(self.teacher_noise)
-        with torch.no_grad():
-            tr.rollout_begin(h, self._last_dones)  # the state the update's recurrence starts from, step 0's resets
-            for n in range(T):
-                reset = tr.rollout_reset(n, self._last_dones, dones)
-                _lib.check(lib.bg_distill_act_gru(N, _lib.ptr(obses[n]), obses.shape[-1], len(td), td, self.scan, gd, len(sd), sd, _lib.ptr(logstd), seed,
-                                                  self._act_counter, beta, noise, _lib.ptr(reset), _lib.ptr(h), _lib.ptr(h), None, _lib.ptr(actions[n]),
-                                                  _lib.ptr(labels[n]), _lib.current_stream_ptr()), "bg_distill_act_gru")
-                self._act_counter += 1
-                self.env.step_to(actions[n], obses[n + 1], priv[n + 1], buf["rewards"][n], dones[n], buf["time_outs"][n])
-            tr.rollout_end(dones, self._last_dones)
+                self.env.step_to(actions[n], obses[n + 1], priv[n + 1], buf["rewards"][n], dones[n], buf["time_outs"][n], **student_obs(n))
+            if mt is not None:
+                mt.rollout_end(dones, self._last_dones)
 
     def update(self):
         """num_epochs full-batch behaviour-cloning steps on the rollout's rows.  Returns the per-epoch mean losses (float64 device tensor: the loss
         each step's gradient was taken of); with distillation.symmetric_coef the per-epoch mean squared asymmetries are left in symmetry_losses."""
-        tr, B, A = self._trainer, self.B, self.env.num_actions
-        out, hid = tr.layers[-1], tr.layers[-2]
+        B, A = self.B, self.env.num_actions
         target = self.buffer["teacher_mu"].reshape(B, A)
+        symmetry = (self.symmetric_coef, self._act_mirror) if self.symmetry else None
         with torch.no_grad():
             rows = self.buffer["student_obses" if self.history else "obses"][: self.T].reshape(B, -1)
             self._student_in[:B, : self.student_obs].copy_(rows[:, : self.student_obs])
             if self.symmetry:  # rows [B, 2B): the mirror images M_o x of the batch (the padded columns stay zero)
                 mirror_rows(self._student_in[:B], self._student_in[B:], *self._obs_mirror)
-            mt = self._memory_trainer if self.memory else None
             for e in range(self.dcfg.num_epochs):
-                h = tr.forward_hidden(self._student_in if mt is None else mt.forward(self._student_in))
-                self._stats.zero_()
-                fin, fins = _lib.ReduceProblem(), []
-                if self.symmetry:
-                    _lib.check(_lib.load().bg_distill_head_sym_partial(B, _lib.ptr(h), _lib.ptr(out.weight), _lib.ptr(out.bias), _lib.ptr(target), self.symmetric_coef,
-                                                                       *self._act_mirror, None, _lib.ptr(tr.hidden_grad), _lib.ptr(out.weight.grad),
-                                                                       _lib.ptr(out.bias.grad), _lib.ptr(hid.bias.grad), _lib.ptr(self._stats),
-                                                                       _lib.ptr(self._head_scratch), fin, _lib.current_stream_ptr()), "bg_distill_head_sym_partial")
-                else:
-                    _lib.check(_lib.load().bg_distill_head_partial(B, _lib.ptr(h), _lib.ptr(out.weight), _lib.ptr(out.bias), _lib.ptr(target), None,
-                                                                   _lib.ptr(tr.hidden_grad), _lib.ptr(out.weight.grad), _lib.ptr(out.bias.grad), _lib.ptr(hid.bias.grad),
-                                                                   _lib.ptr(self._stats), _lib.ptr(self._head_scratch), fin, _lib.current_stream_ptr()),
-                               "bg_distill_head_partial")
-                tr.backward_hidden(finishes=fins)
-                if mt is not None:
-                    mt.backward()
-                self._wgrad.run((tr,) if mt is None else (tr, mt), self._wgrad_terms, False)
-                reduce_group([fin] + fins)
-                self.optimizer.step()
-                self._clock.tick()
-                self._losses[e].copy_(self._stats)
+                self._sup.step(self._student_in, target, symmetry)
+                self._losses[e].copy_(self._sup.stats)
         if self.symmetry:
             self.symmetry_losses = self._losses[:, 1] / float(A * B)
         return self._losses[:, 0] / float(A * B)

@@ -7,7 +7,8 @@ The output layer is 12 wide at any E, the width of every fused output layer of t
 [0, E) are the estimates, columns [E, 12) regress onto zero and are never read by the actor.  So the rollout's layer code and the regression head run
 unchanged; the price is 12 - E output neurons that learn a constant.
 
-Runner reads the section (utils/runner.py), utils/distill.py refuses it.  With `enabled` false or the section absent nothing else in this file is used.
+Runner reads the section (utils/runner.py) and trains the network through EstimatorTrainer, utils/distill.py refuses it.  With `enabled` false or the
+section absent nothing else in this file is used.
 """
 import math
 from typing import NamedTuple
@@ -17,7 +18,8 @@ import torch
 from .. import _lib
 from ..envs.t1 import MAX_ACTOR_INPUT
 from .terrain import actor_heights_of
-from .model import CRITIC_HIDDEN, check_hidden, hidden_of
+from .model import CRITIC_HIDDEN, MLPTrainer, check_hidden, hidden_of, pad_input
+from .supervised import SupervisedTrainer
 
 EST_WIDTH = _lib.NUM_DOFS  # the estimator's output layer: 12 columns, E <= 12 of them estimates
 DEFAULTS = {"enabled": False, "targets": [4, 5, 6, 7], "hidden": [256, 128], "num_epochs": 2, "learning_rate": 1.0e-3, "max_grad_norm": 1.0}
@@ -109,6 +111,44 @@ def estimator_targets(privileged, targets, out=None):
     out[..., : len(targets)].copy_(privileged.index_select(-1, idx))
     out[..., len(targets):].zero_()
     return out
+
+
+class EstimatorTrainer:
+    """The estimator's supervised update, what estimator.enabled adds to a Runner behind the model, the second FlatAdam (`optimizer`, over the
+    estimator's parameters under `clock`) and the `estimates` buffer: the zero-padded input, the regression target [B][12] of B = T x N rows, the
+    target columns' index and gather buffer, the last epoch's loss and the SupervisedTrainer that takes the steps."""
+
+    def __init__(self, est, net, optimizer, clock, T, N, num_obs, device):
+        B = int(T) * int(N)
+        self.est, self.num_obs = est, int(num_obs)
+        self.x = torch.zeros(B, pad_input(num_obs), device=device)  # (the padded columns stay zero)
+        self.target = torch.zeros(B, EST_WIDTH, device=device)  # columns [E, 12) stay zero: what the unread outputs regress onto
+        self.idx = torch.tensor(est.targets, dtype=torch.long, device=device)
+        self.sel = torch.zeros(B, len(est.targets), device=device)
+        self.loss = torch.zeros(1, dtype=torch.float64, device=device)  # the last epoch's loss, SSE / (12 B): estimator/loss of the log
+        self.sup = SupervisedTrainer("estimator.enabled", net, optimizer, clock, B, self.x.shape[1])
+        self.resolve_plan()  # (a batch outside the layer kernels' range is a ValueError here, not at the first update)
+
+    def resolve_plan(self):
+        """The plan of MLPTrainer's switches as they are now (SupervisedTrainer.resolve_plan), behind the width check of the split-bf16 layer kernels."""
+        kin, hidden = self.x.shape[1], [l.out_features for l in self.sup.mlp.layers[:-1]]
+        if MLPTrainer.SPLIT and (kin > 256 or any(w > 256 for w in hidden[:-1])):
+            raise ValueError(f"parallel.gemm_split / BG_GEMM_SPLIT runs split-bf16 layer kernels that take layer inputs of 64, 128 or 256 columns only; the "
+                             f"estimator's input pads to {kin} and estimator.hidden = {hidden} (use gemm_split 0)")
+        return self.sup.resolve_plan()
+
+    def update(self, obses, privileged):
+        """estimator.num_epochs full-batch Adam steps of L = 1 / (12 B) sum |estimator(obses) - target|^2 on the iteration's rows obses [T][N][num_obs]
+        and privileged [T][N][num_privileged_obs], target = the chosen privileged columns, then zeros, on the current stream; no library GEMM.  The
+        plan is resolved anew (MLPTrainer's switches are process-wide).  Leaves the last epoch's loss in `loss` (device)."""
+        B = self.target.shape[0]
+        self.resolve_plan()
+        self.x[:, : self.num_obs].copy_(obses.reshape(B, -1))
+        torch.index_select(privileged.reshape(B, -1), 1, self.idx, out=self.sel)
+        self.target[:, : len(self.est.targets)].copy_(self.sel)
+        for _ in range(self.est.num_epochs):
+            self.sup.step(self.x, self.target)
+        torch.mul(self.sup.stats, 1.0 / (EST_WIDTH * B), out=self.loss)
 
 
 def check_estimator_checkpoint(ck, model_dict, est, ck_ain, a_in):

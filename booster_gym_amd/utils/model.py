@@ -122,6 +122,34 @@ def plan_network(widths, kin, rows, split, fused, chain, chain_split, chain_spli
     return NetPlan(fwd, bwd, bool(alternate), int(split) if fused else 0, grouped)
 
 
+INPUT_PADS = (64, 128, 256, 512)  # first-layer inputs of the per-layer fused kernels (bg_mlp.hip); the chained kernels take 64 only
+WGRAD_SPLIT_SHAPES = ((256, 256), (128, 256), (128, 128), (256, 64))  # (C_out, C_in padded) that bg_wgrad_split.hip has kernels for
+
+
+def pad_input(width):
+    """The zero-padded input width of a network whose input has `width` features: the next of 64, 128, 256, 512 (actor 47 -> 64; critic 61 -> 64,
+    61 + 187 = 248 -> 256 with the default height scan); ValueError beyond 512."""
+    for p in INPUT_PADS:
+        if width <= p:
+            return p
+    raise ValueError(f"a network input of {width} features exceeds the widest first layer of the kernels ({INPUT_PADS[-1]})")
+
+
+def wgrad_products(rows, grouped, bwd_chained, split, wgrad_split):
+    """Products of the grouped weight-gradient launch over the layers `grouped` = [(C_out, C_in padded)]: 0 = fp32 MFMA (bg_wgrad.hip), 6 / 9 = bf16
+    splits (bg_wgrad_split.hip: its shapes, rows a multiple of 32 from 128 up; `split` everywhere, `wgrad_split` behind the chained split backward of
+    every network only).  The one rule of runner.plan_update and of utils/supervised.py."""
+    if rows % 32 != 0 or rows < 128 or not all(s in WGRAD_SPLIT_SHAPES for s in grouped):
+        return 0
+    return split or (wgrad_split if bwd_chained else 0)
+
+
+def layer_descriptors(linears):
+    """The bg_mlp_layer_desc array of a list of Linear layers on their current parameter storage, for the launches that take a network by descriptors
+    (callers cache it behind a key of the parameters' data_ptr: an optimiser moves the storage into its flat buffer once)."""
+    return (_lib.MlpLayerDesc * len(linears))(*[_lib.MlpLayerDesc(l.weight.data_ptr(), l.bias.data_ptr(), l.in_features, l.out_features) for l in linears])
+
+
 class GroupedWeightGrad:
     """All deferred weight gradients of several MLPTrainers in one launch pair (bg_mlp_weight_grad_group)."""
 
@@ -868,9 +896,7 @@ class ActorCritic(torch.nn.Module):
             raise ValueError(f"sample_actions: observations of {obs.shape[-1]} columns, the actor takes {lin[0].in_features}")
         key = tuple(t.data_ptr() for t in w)
         if key != self._sample_key:  # descriptors of the current parameter storage (the optimiser moves it into its flat buffer once)
-            self._sample_layers = (_lib.MlpLayerDesc * len(lin))(*[_lib.MlpLayerDesc(l.weight.data_ptr(), l.bias.data_ptr(), l.in_features, l.out_features)
-                                                                   for l in lin])
-            self._sample_key = key
+            self._sample_layers, self._sample_key = layer_descriptors(lin), key
         if scan:
             _lib.check(_lib.load().bg_actor_sample_mlp_scan(obs.shape[0], _lib.ptr(obs), len(lin), self._sample_layers, int(scan), _lib.ptr(self.logstd), int(seed),
                                                             int(counter), _lib.ptr(mu_out), _lib.ptr(actions_out), _lib.current_stream_ptr()),
@@ -899,8 +925,7 @@ class ActorCritic(torch.nn.Module):
                 raise RuntimeError("sample_actions needs contiguous tensors")
         key = tuple(t.data_ptr() for t in w + ew)
         if key != self._est_key:  # descriptors of the current parameter storage of both networks
-            desc = lambda ls: (_lib.MlpLayerDesc * len(ls))(*[_lib.MlpLayerDesc(l.weight.data_ptr(), l.bias.data_ptr(), l.in_features, l.out_features) for l in ls])
-            self._est_layers, self._est_key = (desc(elin), desc(lin)), key
+            self._est_layers, self._est_key = (layer_descriptors(elin), layer_descriptors(lin)), key
         ed, ad = self._est_layers
         _lib.check(_lib.load().bg_actor_sample_est(obs.shape[0], _lib.ptr(obs), len(elin), ed, self.estimator_cols, len(lin), ad, _lib.ptr(self.logstd), int(seed),
                                                    int(counter), _lib.ptr(est_out), _lib.ptr(mu_out), _lib.ptr(actions_out), _lib.current_stream_ptr()),
@@ -931,8 +956,7 @@ class ActorCritic(torch.nn.Module):
         h = self.memory_state(N, obs.device)
         key = tuple(t.data_ptr() for t in w + mw)
         if key != self._gru_key:
-            layers = (_lib.MlpLayerDesc * len(lin))(*[_lib.MlpLayerDesc(l.weight.data_ptr(), l.bias.data_ptr(), l.in_features, l.out_features) for l in lin])
-            self._gru_descs, self._gru_key = (self.gru_descriptor(), layers), key
+            self._gru_descs, self._gru_key = (self.gru_descriptor(), layer_descriptors(lin)), key
         gd, layers = self._gru_descs
         _lib.check(_lib.load().bg_actor_sample_gru(N, _lib.ptr(obs), obs.shape[-1], gd, len(lin), layers, _lib.ptr(self.logstd), int(seed), int(counter),
                                                    _lib.ptr(reset), _lib.ptr(h), _lib.ptr(h), _lib.ptr(mu_out), _lib.ptr(actions_out), _lib.current_stream_ptr()),

@@ -29,7 +29,7 @@ Same surface: `Runner(test=False)` parses the reference's 8 CLI flags (runner.py
   estimator estimator.enabled (utils/estimator.py; off by default): a third network regresses chosen privileged columns from the observations and the actor
             takes [observations | estimates].  The rollout's launch is then bg_actor_sample_est (both networks, the estimates kept in the buffer
             `estimates`), the update builds the actor's input from the stored rows, and behind the last PPO step the estimator takes its own
-            supervised Adam steps (_estimator_update: distillation's kernels, an optimiser and a WeightClock of its own).  No forward-ahead then.
+            supervised Adam steps (estimator.EstimatorTrainer: distillation's kernels, an optimiser and a WeightClock of its own).  No forward-ahead then.
   recurrent algorithm.rnn_hidden_size (off by default): a GRU cell in front of the actor's hidden layers.  The rollout's launch is then bg_actor_sample_gru
             on a state [N][H] carried over steps and iterations and zeroed where an env reset; the update runs the cell over the iteration's T steps
             from the state stored at the rollout's start (model.GRUTrainer: back-propagation through time, truncated there) around the trunk's
@@ -42,7 +42,6 @@ Reference quirks kept on purpose: GAE recomputed from the cu
 time-out reward overwrite repeated in place (Q4), KL measured with the pre-step distribution (Q6), entropy_coef < 0 (Q7).
 """
 import argparse
-import ctypes
 import glob
 import os
 import random
@@ -57,10 +56,12 @@ import torch
 from .. import _lib
 from ..envs import TASKS
 from .buffer import ExperienceBuffer
-from .estimator import EST_WIDTH, check_estimator_checkpoint, estimator_cfg, estimator_enabled
+from .estimator import EST_WIDTH, EstimatorTrainer, check_estimator_checkpoint, estimator_cfg, estimator_enabled
 from .config import load_cfg
 from .obs_norm import ObsNormalizer, check_checkpoint, normalization_cfg
-from .model import ACTOR_HIDDEN, CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, GRUTrainer, MLPTrainer, NetPlan, WeightClock, check_hidden, hidden_of, plan_network
+from .model import (ACTOR_HIDDEN, CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, GRUTrainer, MLPTrainer, NetPlan, WeightClock, check_hidden, hidden_of, pad_input,
+                    plan_network, wgrad_products)
+from .optim import FlatAdam
 from .parallel import DataParallel
 from .recorder import Recorder
 from .utils import (actor_head_forward, actor_head_loss_backward, actor_head_sym_loss_backward, critic_head_backward, critic_head_forward, critic_values_gae, gae,
@@ -87,9 +88,6 @@ def hidden_widths(cfg):
     alg = cfg.get("algorithm", {}) or {}
     split = int((cfg.get("parallel", {}) or {}).get("gemm_split", 0) or 0) or MLPTrainer.SPLIT
     return check_hidden(alg.get("actor_hidden", ACTOR_HIDDEN), alg.get("critic_hidden", CRITIC_HIDDEN), split)
-
-
-INPUT_PADS = (64, 128, 256, 512)  # first-layer inputs of the per-layer fused kernels (bg_mlp.hip); the chained kernels take 64 only
 
 
 def actor_memory_of(cfg):
@@ -149,15 +147,6 @@ def checkpoint_memory_overrides(checkpoint):
     if checkpoint.get("distillation") is not None or "memory.weight_hh" not in sd:
         return None
     return {"algorithm.rnn_hidden_size": int(sd["memory.weight_hh"].shape[1])}
-
-
-def pad_input(width):
-    """The zero-padded input width of a network whose input has `width` features: the next of 64, 128, 256, 512 (actor 47 -> 64; critic 61 -> 64,
-    61 + 187 = 248 -> 256 with the default height scan); ValueError beyond 512."""
-    for p in INPUT_PADS:
-        if width <= p:
-            return p
-    raise ValueError(f"a network input of {width} features exceeds the widest first layer of the kernels ({INPUT_PADS[-1]})")
 
 
 def symmetry_loss(cfg):
@@ -241,18 +230,6 @@ class StepRows(NamedTuple):
 TAIL_MAX_ITEMS = 8192  # blocks of sums of one bg_update_tail launch (bg_tail.hip)
 
 
-WGRAD_SPLIT_SHAPES = ((256, 256), (128, 256), (128, 128), (256, 64))  # (C_out, C_in padded) that bg_wgrad_split.hip has kernels for
-
-
-def wgrad_products(rows, grouped, bwd_chained, split, wgrad_split):
-    """Products of the grouped weight-gradient launch over the layers `grouped` = [(C_out, C_in padded)]: 0 = fp32 MFMA (bg_wgrad.hip), 6 / 9 = bf16
-    splits (bg_wgrad_split.hip: its shapes, rows a multiple of 32 from 128 up; `split` everywhere, `wgrad_split` behind the chained split backward of
-    every network only).  The one rule of plan_update and of utils/distill.py."""
-    if rows % 32 != 0 or rows < 128 or not all(s in WGRAD_SPLIT_SHAPES for s in grouped):
-        return 0
-    return split or (wgrad_split if bwd_chained else 0)
-
-
 def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_split_bwd, chain_alternate, fused_wgrad, wgrad_split, one_stream,
                 defer_finish, one_launch_tail, fused_opt, fused_head, fused_gae, chain_values, rollout_forward, dp_active, symmetry=False, memory=0):
     """UpdatePlan from the switches (MLPTrainer.SPLIT ... WGRAD_SPLIT and Runner._one_stream ... _rollout_forward, by the same names in lower case;
@@ -296,103 +273,6 @@ def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_
                 and sums <= TAIL_MAX_ITEMS and not memory)
     return UpdatePlan(nets[0], nets[1], wgrad, fused_head, fused_gae, chain_values, one_stream and chain_values and defer and bwd_chained, defer, fused_opt,
                       one_tail, rollout_forward and chain_values and nets[1].chained and not symmetry, dp_active, bool(symmetry))
-
-
-class FlatAdam:
-    """Adam state on one flat fp32 buffer, stepped by bg_adam_step.  Exposes a torch.optim.Adam-compatible state_dict."""
-
-    def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0):
-        self.params = list(params)
-        dev = self.params[0].device
-        self.sizes = [p.numel() for p in self.params]
-        # every tensor starts on a 16-byte boundary of the flat buffer (the MFMA actor kernel reads weight rows with 16-byte loads);
-        # the padding floats stay zero in params / grads / moments, so norms, Adam and the all-reduce are unaffected
-        self.offsets, n = [], 0
-        for k in self.sizes:
-            self.offsets.append(n)
-            n += (k + 3) // 4 * 4
-        self.flat = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.grad = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.exp_avg = torch.zeros_like(self.flat)
-        self.exp_avg_sq = torch.zeros_like(self.flat)
-        for p, k, off in zip(self.params, self.sizes, self.offsets):
-            self.flat[off : off + k].copy_(p.data.reshape(-1))
-            p.data = self.flat[off : off + k].view_as(p)
-            p.grad = self.grad[off : off + k].view_as(p)
-        self.lr = torch.full((1,), float(lr), dtype=torch.float32, device=dev)
-        self.betas, self.eps, self.max_grad_norm = betas, eps, max_grad_norm
-        self.step_count = 0
-        self._gnorm = torch.zeros(1, dtype=torch.float64, device=dev)
-        self._ticket = torch.zeros(1, dtype=torch.int32, device=dev)  # bg_optimizer_step's ticket
-        self._tail_sync = torch.zeros(4, dtype=torch.int32, device=dev)  # bg_update_tail's ticket and squared-norm pieces
-        self._tail_norm = torch.zeros(8192, dtype=torch.float64, device=dev)
-
-    def zero_grad(self):
-        self.grad.zero_()
-
-    def step(self):
-        self.step_count += 1
-        _lib.check(_lib.load().bg_adam_step(self.flat.numel(), _lib.ptr(self.flat), _lib.ptr(self.grad), _lib.ptr(self.exp_avg),
-                                            _lib.ptr(self.exp_avg_sq), _lib.ptr(self.lr), self.step_count, self.betas[0], self.betas[1], self.eps,
-                                            self.max_grad_norm, _lib.ptr(self._gnorm), _lib.current_stream_ptr()), "bg_adam_step")
-
-    def _opt_args(self, stats, stats_acc, stats_last, kl_index, count, desired_kl, grad_logstd, ls_off, lr_min, lr_max):
-        """The arguments bg_optimizer_step and bg_update_tail share, from `n` to `lr_max` (the step is counted by the caller)."""
-        return [self.flat.numel(), _lib.ptr(self.flat), _lib.ptr(self.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(self.lr), self.step_count,
-                self.betas[0], self.betas[1], self.eps, self.max_grad_norm, _lib.ptr(grad_logstd), int(ls_off), 0 if grad_logstd is None else grad_logstd.numel(),
-                _lib.ptr(stats), _lib.ptr(stats_acc), _lib.ptr(stats_last), stats.numel(), int(kl_index), float(count), desired_kl, lr_min, lr_max]
-
-    @staticmethod
-    def _sums_args(wgrad, reductions):
-        """The two descriptor lists of bg_update_tail / bg_update_tail_sums: wgrad = (descriptor array, count) of a weight-gradient launch made without its
-        finish (GroupedWeightGrad.run(..., partial=True)) or None, reductions = the deferred _lib.ReduceProblem descriptors."""
-        warr, wn = wgrad if wgrad is not None else (None, 0)
-        rarr = (_lib.ReduceProblem * len(reductions))(*reductions) if reductions else None
-        return [warr, wn, rarr, len(reductions) if reductions else 0]
-
-    def step_fused(self, stats, stats_acc, stats_last, kl_index, count, desired_kl, grad_logstd=None, ls_off=0, lr_min=1e-5, lr_max=1e-2, mirrors=None):
-        """clip + Adam + KL learning-rate rule + statistics bookkeeping in one launch (bg_optimizer_step): what `step()`, `adapt_lr()` and the
-        runner's `stats_acc += stats` / zero fills do as seven dependent launches."""
-        self.step_count += 1
-        args = self._opt_args(stats, stats_acc, stats_last, kl_index, count, desired_kl, grad_logstd, ls_off, lr_min, lr_max)
-        _lib.check(_lib.load().bg_optimizer_step(*args, _lib.ptr(self._ticket), None if mirrors is None else ctypes.addressof(mirrors),
-                                                 0 if mirrors is None else len(mirrors), _lib.current_stream_ptr()), "bg_optimizer_step")
-
-    def step_tail(self, wgrad, reductions, stats, stats_acc, stats_last, kl_index, count, desired_kl, grad_logstd=None, ls_off=0, lr_min=1e-5, lr_max=1e-2,
-                  mirrors=None):
-        """`step_fused` together with the sums in front of it (bg_update_tail: two launches for four); wgrad, reductions: see _sums_args."""
-        self.step_count += 1
-        args = self._opt_args(stats, stats_acc, stats_last, kl_index, count, desired_kl, grad_logstd, ls_off, lr_min, lr_max)
-        _lib.check(_lib.load().bg_update_tail(*self._sums_args(wgrad, reductions), *args, _lib.ptr(self._tail_sync), _lib.ptr(self._tail_norm),
-                                              None if mirrors is None else ctypes.addressof(mirrors), 0 if mirrors is None else len(mirrors),
-                                              _lib.current_stream_ptr()), "bg_update_tail")
-
-    def tail_sums(self, wgrad, reductions):
-        """Launch (1) of `step_tail` alone (bg_update_tail_sums): the ranks of a multi-GPU job average the gradient between the sums and `step_fused`."""
-        _lib.check(_lib.load().bg_update_tail_sums(*self._sums_args(wgrad, reductions), _lib.ptr(self._tail_norm), _lib.current_stream_ptr()),
-                   "bg_update_tail_sums")
-
-    def adapt_lr(self, kl_sum, count, desired_kl, lr_min=1e-5, lr_max=1e-2):
-        _lib.check(_lib.load().bg_adapt_lr(_lib.ptr(kl_sum), float(count), desired_kl, lr_min, lr_max, _lib.ptr(self.lr), _lib.current_stream_ptr()),
-                   "bg_adapt_lr")
-
-    def state_dict(self):
-        state = {}
-        for i, (k, off) in enumerate(zip(self.sizes, self.offsets)):
-            state[i] = {"step": torch.tensor(float(self.step_count)), "exp_avg": self.exp_avg[off : off + k].view_as(self.params[i]).clone(),
-                        "exp_avg_sq": self.exp_avg_sq[off : off + k].view_as(self.params[i]).clone()}
-        group = {"lr": float(self.lr.item()), "betas": self.betas, "eps": self.eps, "weight_decay": 0, "amsgrad": False, "maximize": False,
-                 "foreach": None, "capturable": False, "differentiable": False, "fused": None, "params": list(range(len(self.sizes)))}
-        return {"state": state, "param_groups": [group]}
-
-    def load_state_dict(self, sd):
-        for i, (k, off) in enumerate(zip(self.sizes, self.offsets)):
-            st = sd["state"].get(i)
-            if st is not None:
-                self.exp_avg[off : off + k].copy_(st["exp_avg"].reshape(-1))
-                self.exp_avg_sq[off : off + k].copy_(st["exp_avg_sq"].reshape(-1))
-                self.step_count = int(float(st["step"]))
-        self.lr.fill_(float(sd["param_groups"][0]["lr"]))
 
 
 class Runner:
@@ -586,8 +466,8 @@ class Runner:
             self._init_mini_batches()
         if self._symmetry:
             self._resolve_plan()  # (a plan the symmetric head cannot serve is a ValueError here, not at the first update)
-        if self._est is not None:
-            self._init_estimator()
+        if self._est is not None:  # its supervised update (a batch outside the layer kernels' range is a ValueError here, not at the first update)
+            self._est_trainer = EstimatorTrainer(self._est, self.model.estimator, self._est_opt, self._est_clock, T, N, no, dev)
 
     # ------------------------------------------------------------------ config / seed / checkpoint (runner.py:44-97)
     def _get_args(self, args=None):
@@ -736,64 +616,6 @@ class Runner:
             self._critic_mb.plan, self._actor_mb.plan = mp.critic, mp.actor
             self._critic_mb.value_head = (c_out.weight.reshape(-1), c_out.bias, self._mb_values) if mp.chain_values else None
         return plan
-
-    # ------------------------------------------------------------------ estimator.enabled
-    def _init_estimator(self):
-        """What estimator.enabled adds to the runner behind the model, the second FlatAdam and the `estimates` buffer: an MLPTrainer over the estimator
-        under its own WeightClock, its zero-padded input, the regression target
-        [B][12] and the workspaces of Distiller.update's sequence."""
-        T, N, dev = self.cfg["runner"]["horizon_length"], self.env.num_envs, self.device
-        B, no = T * N, self.env.num_obs
-        self._est_tr = MLPTrainer(self.model.estimator, clock=self._est_clock)
-        self._est_in = torch.zeros(B, pad_input(no), device=dev)  # (the padded columns stay zero)
-        self._est_target = torch.zeros(B, EST_WIDTH, device=dev)  # columns [E, 12) stay zero: what the unread outputs regress onto
-        self._est_idx = torch.tensor(self._est.targets, dtype=torch.long, device=dev)
-        self._est_sel = torch.zeros(B, len(self._est.targets), device=dev)
-        self._est_wgrad = GroupedWeightGrad()
-        self._est_head_scratch = head_scratch(dev)
-        self._est_stats = torch.zeros(1, dtype=torch.float64, device=dev)  # an epoch's sum of squared errors
-        self._est_loss = torch.zeros(1, dtype=torch.float64, device=dev)   # the last epoch's loss, SSE / (12 B): estimator/loss of the log
-        self._resolve_estimator_plan()  # (a batch outside the layer kernels' range is a ValueError here, not at the first update)
-
-    def _resolve_estimator_plan(self):
-        """The estimator's NetPlan of MLPTrainer's switches as they are now (plan_network, as utils/distill.py) and the products of its grouped
-        weight-gradient launch; ValueError where a pass would fall to a library GEMM."""
-        tr, B = self._est_tr, self._est_target.shape[0]
-        widths, kin, sw = (tr.layers[0].in_features,) + tuple(l.out_features for l in tr.layers), self._est_in.shape[1], MLPTrainer
-        if sw.SPLIT and (kin > 256 or any(w > 256 for w in widths[1:-2])):
-            raise ValueError(f"parallel.gemm_split / BG_GEMM_SPLIT runs split-bf16 layer kernels that take layer inputs of 64, 128 or 256 columns only; the "
-                             f"estimator's input pads to {kin} and estimator.hidden = {list(widths[1:-1])} (use gemm_split 0)")
-        tr.plan = plan = plan_network(widths, kin, B, sw.SPLIT, sw.FUSED, sw.CHAIN, sw.CHAIN_SPLIT, sw.CHAIN_SPLIT_BWD, sw.CHAIN_ALTERNATE, sw.FUSED_WGRAD)
-        if "library" in (plan.fwd, plan.bwd) or not all(plan.grouped[:-1]):
-            raise ValueError(f"estimator.enabled: a batch of runner.horizon_length x env.num_envs = {B} rows is outside the range of the layer kernels (an "
-                             "even number of 64 rows or more)")
-        shapes = [(co, ci) for ci, co in zip((kin,) + widths[1:-2], widths[1:-1])]
-        self._est_wgrad_terms = wgrad_products(B, shapes, plan.bwd == "chain_split", sw.SPLIT, sw.WGRAD_SPLIT)
-
-    def _estimator_update(self, u):
-        """estimator.num_epochs full-batch Adam steps of L = 1 / (12 B) sum |estimator(obses) - target|^2 on the iteration's T x N rows, target = the
-        chosen privileged columns, then zeros: Distiller.update's sequence (forward_hidden, bg_distill_head_partial, backward_hidden, the grouped weight
-        gradients, reduce_group, step, clock tick) on the main stream; no library GEMM.  Leaves the last epoch's loss in _est_loss (device)."""
-        e, tr, B, T = self._est, self._est_tr, u.B, u.T
-        self._resolve_estimator_plan()
-        out, hid = tr.layers[-1], tr.layers[-2]
-        self._est_in[:, : self.env.num_obs].copy_(u.buf["obses"][:T].reshape(B, -1))
-        torch.index_select(u.buf["privileged_obses"][:T].reshape(B, -1), 1, self._est_idx, out=self._est_sel)
-        self._est_target[:, : len(e.targets)].copy_(self._est_sel)
-        for _ in range(e.num_epochs):
-            h = tr.forward_hidden(self._est_in)
-            self._est_stats.zero_()
-            fin, fins = _lib.ReduceProblem(), []
-            _lib.check(_lib.load().bg_distill_head_partial(B, _lib.ptr(h), _lib.ptr(out.weight), _lib.ptr(out.bias), _lib.ptr(self._est_target), None,
-                                                           _lib.ptr(tr.hidden_grad), _lib.ptr(out.weight.grad), _lib.ptr(out.bias.grad), _lib.ptr(hid.bias.grad),
-                                                           _lib.ptr(self._est_stats), _lib.ptr(self._est_head_scratch), fin, _lib.current_stream_ptr()),
-                       "bg_distill_head_partial")
-            tr.backward_hidden(finishes=fins)
-            self._est_wgrad.run((tr,), self._est_wgrad_terms, False)
-            reduce_group([fin] + fins)
-            self._est_opt.step()
-            self._est_clock.tick()
-        torch.mul(self._est_stats, 1.0 / (EST_WIDTH * B), out=self._est_loss)
 
     # ------------------------------------------------------------------ runner.num_mini_batches > 1
     def _init_mini_batches(self):
@@ -980,7 +802,8 @@ class Runner:
                 # parallelism all ranks' rows through ONE float64 exchange (tag "obs_norm", main stream, behind the last "bucket": utils/parallel.py)
                 self.obs_norm.update_from(u.buf["obses"][: u.T], u.buf["privileged_obses"][: u.T], self.dp)
             if self._est is not None:
-                self._estimator_update(u)  # behind the last PPO optimiser step: the next rollout runs the estimator trained on this iteration's rows
+                # behind the last PPO optimiser step: the next rollout runs the estimator trained on this iteration's rows
+                self._est_trainer.update(u.buf["obses"][: u.T], u.buf["privileged_obses"][: u.T])
         if K > 1:
             self._mb_updates += 1
         return self._stats_acc
@@ -1319,7 +1142,7 @@ class Runner:
 
     def _summarize(self, stats_acc):
         """Host-side means of the loss terms over the mini-epochs (runner.py:182-204); one device->host read (blocking: tests and tools)."""
-        extra = () if self._est is None else (self._est_loss,)  # (read with the same one copy)
+        extra = () if self._est is None else (self._est_trainer.loss,)  # (read with the same one copy)
         s = torch.cat((stats_acc, self._stats_last, self.optimizer.lr.double()) + extra).cpu().tolist()
         out = self._summary_from(s)
         if self._est is not None:
@@ -1401,7 +1224,7 @@ class Runner:
         if self.env.terrain.curriculum:
             d[h + ne + 4 : h + ne + 5].copy_(self.env.terrain_level_sum())
         if self._est is not None:
-            d[-1:].copy_(self._est_loss)
+            d[-1:].copy_(self._est_trainer.loss)
         self._flush_log()  # the previous iteration's scalars: their copy finished long ago
         slot = it & 1
         self._log_host[slot].copy_(d, non_blocking=True)

@@ -223,8 +223,8 @@ def _check_one_iteration(d, frames, kin, plan, wgrad):
     """rollout() against bg_actor_sample_mlp_scan, update() against float64 autograd + clip_grad_norm_ + torch.optim.Adam on the same rows and labels."""
     F = 47 * frames
     assert (d.student_obs, d.scan, d.env.num_obs) == (F, P, F + P) and d.student.actor[0].in_features == F and d.student.critic[0].in_features == F + 14 + P
-    assert d._student_in.shape == (T * N, kin) and (d._trainer.plan.fwd, d._trainer.plan.bwd) == (plan, plan) and all(d._trainer.plan.grouped[:-1])
-    assert d._wgrad_terms == wgrad
+    assert d._student_in.shape == (T * N, kin) and (d._sup.mlp.plan.fwd, d._sup.mlp.plan.bwd) == (plan, plan) and all(d._sup.mlp.plan.grouped[:-1])
+    assert d._sup.wgrad_terms == wgrad
     assert abs(d.student.logstd[0, 0].item() - math.log(0.1)) < 1e-7
     frozen = lambda: {**{"student." + k: v.clone() for k, v in d.student.state_dict().items() if not k.startswith("actor.")},
                       **{"teacher." + k: v.clone() for k, v in d.teacher.state_dict().items()}}

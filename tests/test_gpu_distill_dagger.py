@@ -230,7 +230,7 @@ def test_keys_absent_or_at_their_defaults_run_todays_calls_alone(monkeypatch, te
                 del cfg["distillation"][k]
         d = Distiller(cfg=cfg)
         d.begin(recorder=_Rec())
-        assert not d.symmetry and d.beta0 == 0 and d._student_in.shape[0] == d.B and d._stats.numel() == 1
+        assert not d.symmetry and d.beta0 == 0 and d._student_in.shape[0] == d.B and d._sup.stats.numel() == 1
         for it in range(2):
             d.train_iteration(it)
         torch.cuda.synchronize()

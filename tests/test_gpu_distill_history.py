@@ -260,7 +260,7 @@ def test_one_iteration_with_a_longer_history_matches_the_float64_restatement(tea
     F, Fs = 47 * H, 47 * HS
     assert d.history and (d.student_obs, d.scan, d.env.num_obs, d.env.student_frame_stack) == (Fs, P, F + P, HS)
     assert d.student.actor[0].in_features == Fs and d.student.critic[0].in_features == Fs + 14 + P and d._student_in.shape == (T * N, 256)
-    assert all(d._trainer.plan.grouped[:-1]) and "library" not in (d._trainer.plan.fwd, d._trainer.plan.bwd)
+    assert all(d._sup.mlp.plan.grouped[:-1]) and "library" not in (d._sup.mlp.plan.fwd, d._sup.mlp.plan.bwd)
     assert abs(d.student.logstd[0, 0].item() - math.log(0.1)) < 1e-7
     sob = d.buffer["student_obses"]
     assert tuple(sob.shape) == (T + 1, N, Fs) and torch.equal(sob[0, :, -F:], d.buffer["obses"][0, :, :F]) and not sob[0, :, :-47].any()

@@ -344,8 +344,8 @@ def test_one_update_matches_float64_autograd_through_time(teacher_ck):
     from booster_gym_amd.utils.model import ActorCritic
 
     d = _distiller(teacher_ck)
-    tr = d._memory_trainer
-    assert d.memory == MEM and d.student.actor[0].in_features == MEM and (d._trainer.plan.fwd, d._trainer.plan.bwd) == ("layer", "layer")
+    tr = d._sup.gru
+    assert d.memory == MEM and d.student.actor[0].in_features == MEM and (d._sup.mlp.plan.fwd, d._sup.mlp.plan.bwd) == ("layer", "layer")
     assert [k for k, _ in _trained(d.student)] == [k for k, p in d.student.named_parameters() if any(p is q for q in d.optimizer.params)]
     d.rollout()  # a rollout first: the one below starts from a state that is not zero (no update: Adam's moments start with the restatement's)
     d.buffer.roll()
@@ -410,7 +410,7 @@ def test_the_state_carries_over_iterations_and_runs_reproduce(teacher_ck):
     digests = []
     for run in range(2):
         d = _distiller(teacher_ck)
-        tr = d._memory_trainer
+        tr = d._sup.gru
         assert torch.all(d.state == 0)
         for it in range(3):
             state, last = d.state.clone(), d._last_dones.clone()

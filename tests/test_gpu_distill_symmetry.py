@@ -139,8 +139,8 @@ def _check_one_symmetric_iteration(d, s_frames, kin, plan, wgrad):
 
     B, Fs = T * N, 47 * s_frames
     assert d.symmetry and d.symmetric_coef == COEF and (d.T, d.N, d.B) == (T, N, B) and d.student_obs == Fs
-    assert d._student_in.shape == (2 * B, kin) and (d._trainer.plan.fwd, d._trainer.plan.bwd) == (plan, plan) and all(d._trainer.plan.grouped[:-1])
-    assert d._wgrad_terms == wgrad
+    assert d._student_in.shape == (2 * B, kin) and (d._sup.mlp.plan.fwd, d._sup.mlp.plan.bwd) == (plan, plan) and all(d._sup.mlp.plan.grouped[:-1])
+    assert d._sup.wgrad_terms == wgrad
     d.rollout()
     torch.cuda.synchronize()
     obs_src, obs_sign, act_src, act_sign = _student_maps(d, s_frames)

@@ -393,8 +393,8 @@ def loop(K=20, W=5, pairs=3, N=4096, Hs=None, coef=0.0, beta=0.0, memory=0):
         ms = run(K)
         keys = f"symmetric_coef {coef:g}, teacher_action_prob {beta:g}, " if coef or beta or KEYS else ""
         keys += f"student_memory {memory}, " if memory or MEMORY else ""
-        say(f"distillation loop, {N} envs, H = 1, P = 187, {keys}student_frame_stack {Hs or 'absent'} ({d.student_obs} student columns padded to {d._student_in.shape[1]}), horizon {T}, {E} epochs, student 256-128-128 (plan {d._trainer.plan.fwd} / {d._trainer.plan.bwd}, weight "
-            f"gradients {d._wgrad_terms or 'fp32'}): {ms:.3f} ms per iteration = {1e3 / ms:.2f} iterations/s = {N * T / ms / 1e3:.3f} M env-steps/s; last loss "
+        say(f"distillation loop, {N} envs, H = 1, P = 187, {keys}student_frame_stack {Hs or 'absent'} ({d.student_obs} student columns padded to {d._student_in.shape[1]}), horizon {T}, {E} epochs, student 256-128-128 (plan {d._sup.mlp.plan.fwd} / {d._sup.mlp.plan.bwd}, weight "
+            f"gradients {d._sup.wgrad_terms or 'fp32'}): {ms:.3f} ms per iteration = {1e3 / ms:.2f} iterations/s = {N * T / ms / 1e3:.3f} M env-steps/s; last loss "
             f"{d.last_loss:.6f}")
     for ph, fn in (("rollout", d.rollout), ("update", d.update)):
         best = 1e9

@@ -13,7 +13,6 @@
 import os
 import sys
 import time
-import types
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -113,12 +112,12 @@ def update(pairs=3, N=4096, W=3):
         for it in range(W):
             r.train_iteration(it)
         T = r.cfg["runner"]["horizon_length"]
-        u = types.SimpleNamespace(buf=r.buffer, T=T, B=T * N)
+        et, obses, priv = r._est_trainer, r.buffer["obses"][:T], r.buffer["privileged_obses"][:T]
         for q in range(pairs):
             with torch.no_grad():
-                ms = _best(lambda k: r._estimator_update(u), 5) * 1e-3
-            say(f"estimator update, {T} x {N} rows, H = {H}, {r._est.num_epochs} epochs, plan {r._est_tr.plan.fwd} / {r._est_tr.plan.bwd}, weight gradients of "
-                f"{r._est_wgrad_terms} products: {ms:.3f} ms per iteration")
+                ms = _best(lambda k: et.update(obses, priv), 5) * 1e-3
+            say(f"estimator update, {T} x {N} rows, H = {H}, {r._est.num_epochs} epochs, plan {et.sup.plan.fwd} / {et.sup.plan.bwd}, weight gradients of "
+                f"{et.sup.wgrad_terms} products: {ms:.3f} ms per iteration")
         del r
 
 
