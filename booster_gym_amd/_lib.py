@@ -142,6 +142,7 @@ HEAD_SCRATCH_FLOATS = 768 * 1720  # BG_HEAD_SCRATCH_FLOATS
 OBS_MOMENTS_MAX_GROUPS = 1024  # BG_OBS_MOMENTS_MAX_GROUPS
 GATHER_MAX_STREAMS = 8  # BG_GATHER_MAX_STREAMS
 ACTOR_PACKED_FLOATS = 65616  # BG_ACTOR_PACKED_FLOATS
+TAIL_MAX_BLOCKS = 8192  # BG_TAIL_MAX_BLOCKS: blocks of sums of one bg_update_tail launch = float64 slots of its norm_scratch
 # planes of the evaluation record [EVAL_PLANES][N] (bg_env_eval_begin / bg_env_eval_step): the one place that names them, for the kernel's callers
 # and for the report (utils/evaluate.py).  Command class c = 0 still, 1 slow (max |cmd| <= 0.5), 2 fast.
 EVAL_PLANES = 23  # BG_EVAL_PLANES

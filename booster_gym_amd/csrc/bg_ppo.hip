@@ -9,7 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <string>
 
-#include "bg_mirror.h"
+#include "bg_optim.h"
 #include "bg_ppo_math.h"
 #include "bg_reduce.h"
 #include "bg_rng.h"
@@ -391,22 +391,12 @@ __global__ __launch_bounds__(256) void adam_kernel(int n, float* __restrict__ p,
                                                    float beta2, float eps, float max_norm, const double* __restrict__ sqnorm) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float total = (float)sqrt(*sqnorm);
-    const float coef = max_norm > 0.f ? fminf(max_norm / (total + 1e-6f), 1.0f) : 1.0f;  // torch.nn.utils.clip_grad_norm_
-    const float gi = g[i] * coef;
-    const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
-    const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
-    m[i] = mi; v[i] = vi;
-    const float step_size = *lr_dev / bc1;
-    p[i] -= step_size * mi / (sqrtf(vi) / bc2_sqrt + eps);
+    adam_element(p, g, m, v, i, clip_coef(*sqnorm, max_norm), *lr_dev / bc1, beta1, beta2, bc2_sqrt, eps);
 }
 __global__ void adapt_lr_kernel(const double* __restrict__ kl_sum, float count, float desired, float lr_min, float lr_max, float* __restrict__ lr) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const float kl = (float)(kl_sum[0] / (double)count);
-    float l = *lr;
-    if (kl > desired * 2.0f) l = fmaxf(lr_min, l / 1.5f);
-    else if (kl < desired / 2.0f) l = fminf(lr_max, l * 1.5f);
-    *lr = l;
+    *lr = kl_rule(*lr, kl, desired, lr_min, lr_max);
 }
 
 // The whole tail of a mini-epoch in ONE launch (reference utils/runner.py:162-180: clip_grad_norm_, Adam step, KL-adaptive learning rate, plus
@@ -421,7 +411,9 @@ __global__ void adapt_lr_kernel(const double* __restrict__ kl_sum, float count, 
 //   mirrors  every updated parameter inside one of the caller's [rows][cols] weight matrices is also written to that matrix's mirror: a transposed
 //            copy (the operand layout of the backward layer kernel) or a copy with a wider row stride (the zero-padded first layer).  Six strided torch
 //            copies per mini-epoch (5-20 us each, inside the two chains) otherwise.
-constexpr int OPT_GRID = 64, OPT_THREADS = 1024;
+// The norm pass is this kernel's own; the rest of the step: bg_optim.h.  (Loose __restrict__ parameters, packed into OptArgs here: with OptArgs as the
+// kernel's parameter, as tail_adam_kernel has it, the slice loop's instructions come out in another order than this kernel's always had.)
+constexpr int OPT_GRID = 64;
 __global__ __launch_bounds__(OPT_THREADS) void optimizer_step_kernel(int n, float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                                      float* __restrict__ v, float* __restrict__ lr_dev, float bc1, float bc2_sqrt,
                                                                      float beta1, float beta2, float eps, float max_norm,
@@ -430,8 +422,8 @@ __global__ __launch_bounds__(OPT_THREADS) void optimizer_step_kernel(int n, floa
                                                                      double* __restrict__ stats_last, int n_stats, int kl_index, float kl_count,
                                                                      float desired_kl, float lr_min, float lr_max, unsigned* __restrict__ ticket,
                                                                      ParamMirrors mir) {
-    __shared__ double s_part[OPT_THREADS / 64];
-    __shared__ double s_total;
+    const OptArgs o = {n, p, g, m, v, lr_dev, bc1, bc2_sqrt, beta1, beta2, eps, max_norm, grad_logstd, ls_off, ls_n,
+                       stats, stats_acc, stats_last, n_stats, kl_index, kl_count, desired_kl, lr_min, lr_max};
     const int t = threadIdx.x;
     const float lr = *lr_dev;  // read by every thread before this workgroup takes its ticket
     // the log-std gradient arrives in float64 from the heads: put it into the flat buffer (every workgroup writes the same values)
@@ -446,58 +438,8 @@ __global__ __launch_bounds__(OPT_THREADS) void optimizer_step_kernel(int n, floa
         acc += (double)x.x * (double)x.x + (double)x.y * (double)x.y + (double)x.z * (double)x.z + (double)x.w * (double)x.w;
     }
     for (int i = (n4 << 2) + t; i < n; i += OPT_THREADS) acc += (double)g[i] * (double)g[i];
-    acc = wave_sum_d(acc);
-    if ((t & 63) == 0) s_part[t >> 6] = acc;
-    __syncthreads();
-    if (t == 0) {
-        double tot = 0.0;
-        for (int w = 0; w < OPT_THREADS / 64; w++) tot += s_part[w];
-        s_total = tot;
-    }
-    __syncthreads();
-    const float total = (float)sqrt(s_total);
-    const float coef = max_norm > 0.f ? fminf(max_norm / (total + 1e-6f), 1.0f) : 1.0f;  // torch.nn.utils.clip_grad_norm_
-    const float step_size = lr / bc1;
-    const int per = (n + OPT_GRID - 1) / OPT_GRID, i0 = blockIdx.x * per, i1 = min(n, i0 + per);
-    for (int i = i0 + t; i < i1; i += OPT_THREADS) {
-        const float gi = g[i] * coef;
-        const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
-        const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        const float pn = p[i] - step_size * mi / (sqrtf(vi) / bc2_sqrt + eps);
-        p[i] = pn;
-        for (int k = 0; k < mir.n; k++) {
-            const bg_param_mirror& mm = mir.m[k];
-            const int j = i - mm.offset;
-            if (j >= 0 && j < mm.rows * mm.cols) {
-                const int r = j / mm.cols, c = j - r * mm.cols;
-                bg_mirror_write(mm, r, c, pn);
-            }
-        }
-    }
-    __syncthreads();
-    if (t == 0) {
-        // (no fence: the last workgroup needs the others' READS of lr and the log-std gradient to be over, which they are behind the barrier above --
-        // nothing they wrote; see tail_adam_kernel)
-        const unsigned k = atomicAdd(ticket, 1u);
-        if (k == gridDim.x - 1) {  // every workgroup has read lr and finished its slice
-            if (stats) {
-                const float kl = (float)(stats[kl_index] / (double)kl_count);
-                float l = lr;
-                if (kl > desired_kl * 2.0f) l = fmaxf(lr_min, l / 1.5f);
-                else if (kl < desired_kl / 2.0f) l = fminf(lr_max, l * 1.5f);
-                *lr_dev = l;
-                for (int j = 0; j < n_stats; j++) {
-                    const double sj = stats[j];
-                    stats_last[j] = sj;
-                    stats_acc[j] += sj;
-                    stats[j] = 0.0;
-                }
-            }
-            if (grad_logstd) for (int j = 0; j < ls_n; j++) grad_logstd[j] = 0.0;
-            *ticket = 0u;
-        }
-    }
+    opt_slice(o, mir, OPT_GRID, lr, clip_coef(opt_block_total(acc), max_norm));
+    opt_last_ticket(o, lr, ticket);
 }
 
 
@@ -645,7 +587,8 @@ extern "C" int bg_adam_step(int32_t n, float* params, const float* grads, float*
     HIP_OK(hipMemsetAsync(gnorm_scratch, 0, sizeof(double), (hipStream_t)stream));
     int blocks = (n + 255) / 256;
     hipLaunchKernelGGL(sqnorm_kernel, dim3(blocks < 256 ? blocks : 256), dim3(256), 0, (hipStream_t)stream, n, grads, gnorm_scratch);
-    const float bc1 = 1.0f - powf(beta1, (float)step), bc2s = sqrtf(1.0f - powf(beta2, (float)step));
+    float bc1, bc2s;
+    adam_bias_corrections(beta1, beta2, step, bc1, bc2s);
     hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n, params, grads, exp_avg, exp_avg_sq, lr_device, bc1, bc2s,
                        beta1, beta2, eps, max_grad_norm, gnorm_scratch);
     HIP_OK(hipGetLastError());
@@ -663,23 +606,16 @@ extern "C" int bg_optimizer_step(int32_t n, float* params, float* grads, float* 
                                  float beta2, float eps, float max_grad_norm, double* grad_logstd, int32_t ls_off, int32_t ls_n, double* stats,
                                  double* stats_acc, double* stats_last, int32_t n_stats, int32_t kl_index, float kl_count, float desired_kl,
                                  float lr_min, float lr_max, uint32_t* ticket, const bg_param_mirror* mirrors, int32_t n_mirrors, void* stream) {
-    if (n <= 0 || !params || !grads || !exp_avg || !exp_avg_sq || !lr_device || !ticket || step < 1) return bg_set_error(-1, "bg_optimizer_step: bad argument");
-    if (n_mirrors < 0 || n_mirrors > OPT_MAX_MIRRORS || (n_mirrors > 0 && !mirrors)) return bg_set_error(-1, "bg_optimizer_step: 0 to 16 mirrors");
+    OptArgs o;
     ParamMirrors mir;
-    mir.n = n_mirrors;
-    for (int k = 0; k < n_mirrors; k++) {
-        const bg_param_mirror& q = mirrors[k];
-        if (!bg_mirror_ok(q, n)) return bg_set_error(-1, "bg_optimizer_step: bad mirror descriptor");
-        mir.m[k] = q;
-    }
-    if ((((uintptr_t)grads) & 15) != 0) return bg_set_error(-1, "bg_optimizer_step: grads must be 16-byte aligned");
-    if (grad_logstd && (ls_n <= 0 || ls_n > OPT_THREADS || ls_off < 0 || ls_off + ls_n > n)) return bg_set_error(-1, "bg_optimizer_step: log-std slice out of range");
-    if (stats && (!stats_acc || !stats_last || n_stats <= 0 || kl_index < 0 || kl_index >= n_stats || !(kl_count > 0.f)))
-        return bg_set_error(-1, "bg_optimizer_step: statistics arguments");
-    const float bc1 = 1.0f - powf(beta1, (float)step), bc2s = sqrtf(1.0f - powf(beta2, (float)step));
-    hipLaunchKernelGGL(optimizer_step_kernel, dim3(OPT_GRID), dim3(OPT_THREADS), 0, (hipStream_t)stream, n, params, grads, exp_avg, exp_avg_sq, lr_device, bc1,
-                       bc2s, beta1, beta2, eps, max_grad_norm, grad_logstd, ls_off, ls_n, stats, stats_acc, stats_last, n_stats, kl_index, kl_count,
-                       desired_kl, lr_min, lr_max, ticket, mir);
+    if (const int rc = opt_args_fill("bg_optimizer_step", n, params, grads, exp_avg, exp_avg_sq, lr_device, step, beta1, beta2, eps, max_grad_norm, grad_logstd,
+                                     ls_off, ls_n, stats, stats_acc, stats_last, n_stats, kl_index, kl_count, desired_kl, lr_min, lr_max, ticket, mirrors,
+                                     n_mirrors, o, mir))
+        return rc;
+    if (!aligned16(grads)) return bg_set_error(-1, "bg_optimizer_step: grads must be 16-byte aligned");  // (the norm pass reads float4)
+    hipLaunchKernelGGL(optimizer_step_kernel, dim3(OPT_GRID), dim3(OPT_THREADS), 0, (hipStream_t)stream, o.n, o.p, o.g, o.m, o.v, o.lr_dev, o.bc1, o.bc2_sqrt,
+                       o.beta1, o.beta2, o.eps, o.max_norm, o.grad_logstd, o.ls_off, o.ls_n, o.stats, o.stats_acc, o.stats_last, o.n_stats, o.kl_index,
+                       o.kl_count, o.desired_kl, o.lr_min, o.lr_max, ticket, mir);
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -34,7 +34,7 @@ class FlatAdam:
         self._gnorm = torch.zeros(1, dtype=torch.float64, device=dev)
         self._ticket = torch.zeros(1, dtype=torch.int32, device=dev)  # bg_optimizer_step's ticket
         self._tail_sync = torch.zeros(4, dtype=torch.int32, device=dev)  # bg_update_tail's ticket and squared-norm pieces
-        self._tail_norm = torch.zeros(8192, dtype=torch.float64, device=dev)
+        self._tail_norm = torch.zeros(_lib.TAIL_MAX_BLOCKS, dtype=torch.float64, device=dev)
 
     def zero_grad(self):
         self.grad.zero_()
@@ -75,6 +75,22 @@ class FlatAdam:
         _lib.check(_lib.load().bg_update_tail(*self._sums_args(wgrad, reductions), *args, _lib.ptr(self._tail_sync), _lib.ptr(self._tail_norm),
                                               None if mirrors is None else ctypes.addressof(mirrors), 0 if mirrors is None else len(mirrors),
                                               _lib.current_stream_ptr()), "bg_update_tail")
+
+    def step_separate(self, stats, stats_acc, stats_last, kl_index, count, desired_kl, grad_logstd=None, ls_off=0, lr_min=1e-5, lr_max=1e-2, lr_restart=None):
+        """What `step_fused` does, as separate launches: `step()` (bg_adam_step), `adapt_lr()` (bg_adapt_lr) and the bookkeeping of the kernels' last
+        ticket in torch.  lr_restart: a learning rate to start the KL rule from instead of the stored one (the first step after a restore, which was
+        taken at the stored rate)."""
+        if grad_logstd is not None:
+            self.grad[ls_off : ls_off + grad_logstd.numel()].copy_(grad_logstd)
+        self.step()
+        if lr_restart is not None:
+            self.lr.fill_(float(lr_restart))
+        self.adapt_lr(stats[kl_index : kl_index + 1], count, desired_kl, lr_min, lr_max)
+        stats_acc += stats
+        stats_last.copy_(stats)
+        stats.zero_()
+        if grad_logstd is not None:
+            grad_logstd.zero_()
 
     def tail_sums(self, wgrad, reductions):
         """Launch (1) of `step_tail` alone (bg_update_tail_sums): the ranks of a multi-GPU job average the gradient between the sums and `step_fused`."""

@@ -227,7 +227,7 @@ class StepRows(NamedTuple):
     values: torch.Tensor          # where the value head of the fused kernels writes the values of x_c's rows
 
 
-TAIL_MAX_ITEMS = 8192  # blocks of sums of one bg_update_tail launch (bg_tail.hip)
+TAIL_MAX_ITEMS = _lib.TAIL_MAX_BLOCKS  # blocks of sums of one bg_update_tail launch (bg_tail.hip)
 
 
 def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_split_bwd, chain_alternate, fused_wgrad, wgrad_split, one_stream,
@@ -402,8 +402,7 @@ class Runner:
         # reduce_group, weight gradients + finish, optimizer_step as separate launches (what the ranks of a multi-GPU job run: the norm is the averaged gradient's)
         self._one_launch_tail = os.environ.get("BG_ONE_LAUNCH_TAIL", "1") == "1"
         self._old_logp = torch.zeros(B, device=dev)
-        self._logstd_grad_view = self.model.logstd.grad.view(-1)
-        self._logstd_off = (self._logstd_grad_view.data_ptr() - self.optimizer.grad.data_ptr()) // 4  # position of logstd in the flat buffers
+        self._logstd_off = (self.model.logstd.grad.data_ptr() - self.optimizer.grad.data_ptr()) // 4  # position of logstd in the flat buffers
         self._actor_tr, self._critic_tr = MLPTrainer(self.model.actor, clock=self._clock), MLPTrainer(self.model.critic, clock=self._clock)
         # algorithm.rnn_hidden_size: the cell around the actor's trunk over the T steps of an iteration (model.GRUTrainer, as utils/distill.py; its bias
         # gradients as ONE launch that joins the deferred reductions) and the done flags of the previous iteration's last step; None = a feed-forward
@@ -1044,8 +1043,9 @@ class Runner:
                     self._exchange_sums()  # exchange (3), beside the weight gradients
         # all weight gradients after both backward chains, alone on the GPU: one launch pair for the six hidden layers (shapes outside the
         # kernel's range, or MLPTrainer.FUSED_WGRAD = False: library GEMMs, layer by layer); one_tail: their finish inside bg_update_tail
-        mt = self._mem_tr  # (a recurrent actor: the cell's two weight gradients ride in the same launch, its padded W_ih among the copies)
-        wg_partial = v.wgrad.run((v.ct, v.at) if mt is None else (v.ct, v.at, mt), plan.wgrad, one_tail)
+        # (a recurrent actor: the cell's two weight gradients ride in the same launch, its padded W_ih among the copies)
+        trainers = (v.ct, v.at) if self._mem_tr is None else (v.ct, v.at, self._mem_tr)
+        wg_partial = v.wgrad.run(trainers, plan.wgrad, one_tail)
         if plan.defer and plan.ranks:
             main.wait_stream(side)
         if one_tail and plan.ranks:
@@ -1055,37 +1055,29 @@ class Runner:
             self.dp.exchange_tail_(self.optimizer.grad, self._stats, self._grad_logstd)
         elif not one_tail:
             self.dp.average_(self.optimizer.grad)  # exchange (2): the one collective on the critical path
+        # clip + Adam + KL rule + statistics bookkeeping (and the zeroing of the accumulators for the next mini-epoch): one of FlatAdam's three forms
+        opt = dict(stats=self._stats, stats_acc=self._stats_acc, stats_last=self._stats_last, kl_index=4, count=B * self.world_size,
+                   desired_kl=alg["desired_kl"], grad_logstd=self._grad_logstd, ls_off=self._logstd_off)
         if fused_tail:
-            # clip + Adam + KL rule + statistics bookkeeping (and the zeroing of the accumulators for the next mini-epoch) in ONE launch
-            # ... and the copies of the weights that the layer kernels read (zero-padded first layers, transposed hidden layers): written by the
-            # same launch instead of six strided torch copies inside the chains of the next mini-epoch
+            # ... in ONE launch, with the copies of the weights that the layer kernels read (zero-padded first layers, transposed hidden layers):
+            # written by the same launch instead of six strided torch copies inside the chains of the next mini-epoch
             if mirrors is None:
-                ms = v.ct.copies.descriptors(self.optimizer.flat, v.ct.plan) + v.at.copies.descriptors(self.optimizer.flat, v.at.plan)
-                if mt is not None:
-                    ms += mt.copies.descriptors(self.optimizer.flat, v.at.plan)
+                plans = (v.ct.plan, v.at.plan, v.at.plan)  # (the cell's copies follow the actor's plan)
+                ms = [d for tr, pl in zip(trainers, plans) for d in tr.copies.descriptors(self.optimizer.flat, pl)]
                 mirrors = (_lib.ParamMirror * len(ms))(*ms) if 0 < len(ms) <= 16 else None
             if one_tail and not plan.ranks:
-                self.optimizer.step_tail(wg_partial, [fin_c, fin_a] + fins, self._stats, self._stats_acc, self._stats_last, 4, B, alg["desired_kl"],
-                                         grad_logstd=self._grad_logstd, ls_off=self._logstd_off, mirrors=mirrors)
+                self.optimizer.step_tail(wg_partial, [fin_c, fin_a] + fins, mirrors=mirrors, **opt)
             else:
-                self.optimizer.step_fused(self._stats, self._stats_acc, self._stats_last, 4, B * self.world_size, alg["desired_kl"],
-                                          grad_logstd=self._grad_logstd, ls_off=self._logstd_off, mirrors=mirrors)
+                self.optimizer.step_fused(mirrors=mirrors, **opt)
         else:
-            self._logstd_grad_view.copy_(self._grad_logstd)  # (behind the bucket's all-reduce, which carries a stale value in this slot)
-            self.optimizer.step()
-            if self._lr_restart:  # first step after a checkpoint load: see __init__
-                self.optimizer.lr.fill_(float(cfg["algorithm"]["learning_rate"]))
-                self._lr_restart = False
-            self.optimizer.adapt_lr(self._stats[4:5], B * self.world_size, alg["desired_kl"])
-            self._stats_acc += self._stats
-            self._stats_last.copy_(self._stats)
-            self._stats.zero_()
-            self._grad_logstd.zero_()
+            # ... as separate launches (the log-std gradient's copy: behind the bucket's all-reduce, which carries a stale value in this slot);
+            # the first step after a checkpoint load: see __init__
+            self.optimizer.step_separate(lr_restart=cfg["algorithm"]["learning_rate"] if self._lr_restart else None, **opt)
+            self._lr_restart = False
         self._clock.tick()  # the parameters have changed: every weight copy of every trainer over them is stale, but those this launch listed and wrote
         if fused_tail and mirrors is not None:
-            v.ct.copies.stamp(); v.at.copies.stamp()
-            if mt is not None:
-                mt.copies.stamp()
+            for tr in trainers:
+                tr.copies.stamp()
         u.mirrors = mirrors
 
     def _plan_chain_split(self, x_c, x_a, plan, ct=None, at=None):

@@ -695,7 +695,9 @@ int bg_mlp_chain_backward_split(const bg_mlp_chain_split_bwd* nets, int32_t coun
  * the whole gradient per workgroup.  REQUIRES that the two lists together produce every element of grads except the log-std slice (true for the
  * reference's networks: hidden-layer weights from the weight gradients, all biases and the output layers from the reductions); elements they do not
  * write must be zero.  Gradients: the same bits as the separate launches; the norm is summed in another (fixed) order.  sync: uint32 [1],
- * zero-initialised once by the caller (the launch leaves it zero); norm_scratch: float64 [8192]. */
+ * zero-initialised once by the caller (the launch leaves it zero); norm_scratch: float64 [BG_TAIL_MAX_BLOCKS], one slot per block of launch (1): a
+ * call whose two lists need more blocks is refused (-4). */
+#define BG_TAIL_MAX_BLOCKS 8192
 int bg_update_tail(const bg_wgrad_problem* wgrad, int32_t n_wgrad, const bg_reduce_problem* reduce, int32_t n_reduce, int32_t n, float* params, float* grads,
                    float* exp_avg, float* exp_avg_sq, float* lr_device, int32_t step, float beta1, float beta2, float eps, float max_grad_norm,
                    double* grad_logstd, int32_t ls_off, int32_t ls_n, double* stats, double* stats_acc, double* stats_last, int32_t n_stats, int32_t kl_index,
@@ -703,7 +705,7 @@ int bg_update_tail(const bg_wgrad_problem* wgrad, int32_t n_wgrad, const bg_redu
                    int32_t n_mirrors, void* stream);
 /* Launch (1) of bg_update_tail alone, for the ranks of a multi-GPU job: the gradient's last sums, THEN the all-reduce over the ranks, THEN
  * bg_optimizer_step, which takes the norm of the averaged gradient itself (the reference clips what `loss.backward()` left on its one process,
- * runner.py:162-165; under data parallelism that is the mean over the ranks).  norm_scratch: float64 [8192] (written, not used by the caller). */
+ * runner.py:162-165; under data parallelism that is the mean over the ranks).  norm_scratch: float64 [BG_TAIL_MAX_BLOCKS] (written, not used by the caller). */
 int bg_update_tail_sums(const bg_wgrad_problem* wgrad, int32_t n_wgrad, const bg_reduce_problem* reduce, int32_t n_reduce, double* norm_scratch, void* stream);
 /* bg_actor_head mode 1 / bg_critic_head_backward / bg_mlp_layer_backward without their finishing launch: same arguments, plus the descriptor
  * of the reduction that produces grad_W, grad_b, grad_b_hidden, grad_logstd, stats / bias_grad_below when handed to bg_reduce_group. */

@@ -1,6 +1,8 @@
 """Record the library entry points that two training iterations call, in order, for the supervised paths: a Runner with estimator.enabled and a
 Distiller plain, with student_frame_stack 3, teacher_action_prob 0.5, symmetric_coef 10, student_memory 128 and student_memory 128 with
-teacher_action_prob 0.5.  tests/test_gpu_launch_sequences.py holds the tree against the committed record, so a refactor of the host code cannot
+teacher_action_prob 0.5; and for the forms of PPO's optimiser step: a Runner under the default plan (bg_update_tail), with _one_launch_tail = False
+(bg_reduce_group, the weight gradients' finish, bg_optimizer_step), with _fused_opt = False (bg_adam_step, bg_adapt_lr) and with
+algorithm.rnn_hidden_size 128 (the GRU trainer in the grouped launch and among the mirrors).  tests/test_gpu_launch_sequences.py holds the tree against the committed record, so a refactor of the host code cannot
 drop, add or reorder a launch (a clock tick lost or an order swapped passes the float64 comparisons of the other tests).
 
 The cases run at 128 envs under the `_cfg` helpers of tests/test_gpu_estimator.py and tests/test_gpu_distill.py with the latter's seeded teacher, no BG_*
@@ -9,7 +11,7 @@ variable set, through public names only (Runner(cfg=), begin_training, train_ite
 
   python tests/golden/make_launch_sequences.py [--tree DIR] [--out tests/golden/launch_sequences.json]
 
---tree: the checkout to record (default: the one this file lies in); the committed record is the parent commit's of the change that added this file.
+--tree: the checkout to record (default: the one this file lies in); the committed record is the parent commit's of the change that added the case.
 Every case is recorded twice, in two orders, and the two must agree (nothing in a sequence depends on what ran before in the process).  Per case
 it also prints a SHA-256 over the parameters, the optimisers' flat / exp_avg / exp_avg_sq and every buffer after the two iterations: equal between
 two trees exactly when they computed the same bits (not committed: a later compiler may change them).  Needs a GPU.
@@ -23,7 +25,14 @@ import sys
 import tempfile
 
 ITERATIONS = 2
-CASES = {"runner_estimator": None,  # (a Runner; every other case: the overrides of a Distiller's config)
+PPO = {"estimator.enabled": False}
+# a Runner: (overrides of its config, attributes set on it before the first iteration)
+RUNNER_CASES = {"runner_estimator": ({}, {}),
+                "ppo_default_plan": (PPO, {}),
+                "ppo_tail_as_three_launches": (PPO, {"_one_launch_tail": False}),
+                "ppo_separate_optimizer_launches": (PPO, {"_fused_opt": False}),
+                "ppo_rnn_hidden_size_128": ({**PPO, "algorithm.rnn_hidden_size": 128}, {})}
+CASES = {**RUNNER_CASES,  # (every other case: the overrides of a Distiller's config)
          "distill_plain": {},
          "distill_student_frame_stack_3": {"distillation.student_frame_stack": 3},
          "distill_teacher_action_prob": {"distillation.teacher_action_prob": 0.5},
@@ -66,10 +75,14 @@ def teachers(tmp):
 def build(case, teacher_by_frames):
     """The trainer of a case, begun: a Runner or a Distiller."""
     over = CASES[case]
-    if over is None:
+    if case in RUNNER_CASES:
         from test_gpu_estimator import _runner
 
-        return _runner(1, 128)
+        r = _runner(1, 128, **over[0])
+        for k, x in over[1].items():
+            assert hasattr(r, k), k
+            setattr(r, k, x)
+        return r
     from test_gpu_distill import H, _Rec, _cfg
 
     from booster_gym_amd.utils.distill import Distiller

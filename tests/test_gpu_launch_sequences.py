@@ -1,5 +1,6 @@
-"""The library entry points that two training iterations of the supervised paths call, in order, against the record of
-tests/golden/make_launch_sequences.py (tests/golden/launch_sequences.json): the estimator's Runner and the Distiller with each of its keys.  The
+"""The library entry points that two training iterations call, in order, against the record of tests/golden/make_launch_sequences.py
+(tests/golden/launch_sequences.json): the estimator's Runner, the Distiller with each of its keys, and a PPO Runner with each form of its optimiser
+step (bg_update_tail; bg_reduce_group + bg_optimizer_step; bg_adam_step + bg_adapt_lr; a recurrent actor's cell in the grouped launch).  The
 other tests count launches and compare results with float64 restatements to rtol 1e-3; a lost clock tick or two launches swapped can pass both."""
 import importlib.util
 import json

@@ -239,6 +239,123 @@ def test_fused_optimizer_step_equals_the_separate_launches():
     assert torch.equal(outs[0], outs[1])
 
 
+def test_optimizer_forms_share_one_adam_step():
+    """The three forms of one optimiser step on the same inputs: bg_optimizer_step (64 workgroups, its own norm pass), bg_update_tail with no sums
+    (n_wgrad = n_reduce = 0: its sums launch is skipped; 256 workgroups, the norm from the slots and the log-std squares) and bg_adam_step +
+    bg_adapt_lr + torch's bookkeeping (FlatAdam.step_separate), through FlatAdam's methods on flat buffers of this test's own size.
+
+    n = 66,051: above 64 x 1024, so a workgroup of the 64-workgroup form walks its slice of 1,033 in two strides; n % 4 = 3, so its norm pass takes the
+    scalar remainder; the 256-workgroup form gets slices of 259.  One mirror of each kind, all inside the buffer: transpose 0 with ld > cols (256 x 47,
+    ld 64), transpose 1, 2 and 3 (the planes with pad > 0) of one 128 x 256 matrix, whose 32,768 elements straddle slice boundaries of both grids.
+    Twelve log-std entries as float64, five statistics with kl_index 4.
+
+    A, clip off (max_grad_norm = 0: the coefficient is exactly 1, no norm is used): two consecutive steps on seeded gradients of scale 2.0 and then
+    0.003, a KL mean below desired / 2 and then above 2 desired, so the learning rate moves both ways and the ticket is used twice.  The two fused
+    forms agree in every bit of everything they write; the planes are those bg_mlp_split_weights_pm makes of the new parameters.  The third form is
+    held to the same bits of p, m, v and lr: it agrees with the other two bit for bit under the parent commit's library as well.
+    B, clip on with an exact norm: the gradient is zero but for grad_logstd[k] = (k + 1) / 4, max_grad_norm = 1.  Every square is a multiple of 1 / 16,
+    so the sum, 650 / 16, is exact in float64 in any order: both fused forms see the same total, the step is clipped (norm 6.37), and the same
+    comparisons hold; the twelve moved parameters against torch.optim.Adam behind clip_grad_norm_ at the tolerance of
+    test_fused_optimizer_step_equals_the_separate_launches."""
+    from booster_gym_amd import _lib
+    from booster_gym_amd.utils.model import _write_planes
+    from booster_gym_amd.utils.optim import FlatAdam
+
+    n, ls_off, ls_n, count, desired, lr0 = 66051, 50001, 12, 1000.0, 0.01, 1e-3
+    w0, w1, R, Cc = 0, 256 * 47, 128, 256  # a 256 x 47 matrix at the buffer's start, the 128 x 256 matrix behind it
+    z = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=DEV)
+    torch.manual_seed(11)
+    start = torch.randn(n, device=DEV)
+
+    class Form:
+        def __init__(self, max_norm):
+            self.fa = fa = FlatAdam([torch.nn.Parameter(z(4))], lr=lr0, max_grad_norm=max_norm)
+            fa.flat, fa.grad, fa.exp_avg, fa.exp_avg_sq = start.clone(), z(n), z(n), z(n)
+            self.stats, self.acc, self.last, self.gls = z(5, dtype=torch.float64), z(5, dtype=torch.float64), z(5, dtype=torch.float64), z(ls_n, dtype=torch.float64)
+            self.pad, self.wt = torch.full((256, 64), 7.0, device=DEV), torch.full((Cc, R), 7.0, device=DEV)
+            self.pad[:, 47:] = 0.0
+            self.planes, self.planes_t = z(2 * R * Cc * 3, dtype=torch.int16), z(2 * R * Cc * 3, dtype=torch.int16)
+            ms = [_lib.ParamMirror(w0, 256, 47, 0, 64, 0, _lib.ptr(self.pad)), _lib.ParamMirror(w1, R, Cc, 1, R, 0, _lib.ptr(self.wt)),
+                  _lib.ParamMirror(w1, R, Cc, 2, Cc, R * Cc * 3, _lib.ptr(self.planes)), _lib.ParamMirror(w1, R, Cc, 3, R, R * Cc * 3, _lib.ptr(self.planes_t))]
+            self.mirrors = (_lib.ParamMirror * 4)(*ms)
+
+        def load(self, g, gl, st):
+            self.fa.grad.copy_(g); self.gls.copy_(gl); self.stats.copy_(st)
+            self.fa.grad[ls_off : ls_off + ls_n] = 123.0  # must be overwritten from the float64 log-std gradient
+
+        def args(self):
+            return dict(stats=self.stats, stats_acc=self.acc, stats_last=self.last, kl_index=4, count=count, desired_kl=desired, grad_logstd=self.gls, ls_off=ls_off)
+
+        def step(self, form):
+            if form == "fused":
+                self.fa.step_fused(mirrors=self.mirrors, **self.args())
+            elif form == "tail":
+                self.fa.step_tail(None, [], mirrors=self.mirrors, **self.args())
+            else:
+                self.fa.step_separate(**self.args())
+
+        def written(self, mirrors):
+            fa = self.fa
+            out = {"p": fa.flat, "m": fa.exp_avg, "v": fa.exp_avg_sq, "lr": fa.lr, "g_logstd": fa.grad[ls_off : ls_off + ls_n], "stats": self.stats,
+                   "stats_acc": self.acc, "stats_last": self.last, "grad_logstd": self.gls}
+            if mirrors:
+                out.update(pad=self.pad, wt=self.wt, planes=self.planes, planes_t=self.planes_t, ticket=fa._ticket, sync=fa._tail_sync)
+            return out
+
+    def assert_equal(a, b, mirrors, what):
+        wa, wb = a.written(mirrors), b.written(mirrors)
+        for k in wa:
+            assert torch.equal(wa[k], wb[k]), (what, k, (wa[k].double() - wb[k].double()).abs().max().item())
+
+    def assert_fused_pair(fused, tail, what):
+        assert_equal(fused, tail, True, what)
+        assert float(tail.stats.abs().sum()) == 0.0 and float(tail.gls.abs().sum()) == 0.0 and int(tail.fa._tail_sync.abs().sum()) == 0 and int(fused.fa._ticket) == 0
+        w = tail.fa.flat[w1 : w1 + R * Cc].view(R, Cc)
+        assert torch.equal(tail.pad[:, :47], tail.fa.flat[:w1].view(256, 47)) and float(tail.pad[:, 47:].abs().sum()) == 0.0 and torch.equal(tail.wt, w.t()), what
+        for transpose, got in ((0, tail.planes), (1, tail.planes_t)):
+            want = torch.empty_like(got)
+            _write_planes("bg_mlp_split_weights_pm", transpose, w, Cc, want)
+            assert torch.equal(got, want), (what, transpose)
+
+    # A: clip off
+    forms = {k: Form(0.0) for k in ("fused", "tail", "separate")}
+    lr_want = lr0
+    for it, (scale, kl_mean) in enumerate(((2.0, 0.001), (0.003, 0.05))):
+        g, gl = torch.randn(n, device=DEV) * scale, torch.randn(ls_n, dtype=torch.float64, device=DEV) * scale
+        st = torch.tensor([1.5 + it, -2.0, 0.25, 3.0, kl_mean * count], dtype=torch.float64, device=DEV)
+        before = forms["fused"].fa.flat.clone()
+        for k, f in forms.items():
+            f.load(g, gl, st)
+            f.step(k)
+        assert not torch.equal(before, forms["fused"].fa.flat)
+        assert_fused_pair(forms["fused"], forms["tail"], ("A", it))
+        assert torch.equal(forms["tail"].last, st) and torch.equal(forms["tail"].fa.grad[ls_off : ls_off + ls_n], gl.float())
+        lr_want = lr_want * 1.5 if it == 0 else lr_want / 1.5
+        assert abs(forms["tail"].fa.lr.item() - lr_want) < 1e-9, (it, forms["tail"].fa.lr.item())
+        d = {k: (x.double() - y.double()).abs().max().item() for (k, x), y in zip(forms["separate"].written(False).items(), forms["fused"].written(False).values())}
+        print(f"step {it + 1}: bg_adam_step + bg_adapt_lr against bg_optimizer_step, largest differences {d}")
+        assert_equal(forms["separate"], forms["fused"], False, ("A, separate launches", it))
+    assert all(f.fa.step_count == 2 for f in forms.values())
+
+    # B: clip on, a norm that is exact in any order
+    forms = {k: Form(1.0) for k in ("fused", "tail")}
+    gl = torch.arange(1, ls_n + 1, dtype=torch.float64, device=DEV) / 4
+    st = torch.tensor([0.5, 1.0, -1.0, 2.0, desired * count], dtype=torch.float64, device=DEV)
+    for k, f in forms.items():
+        f.load(z(n), gl, st)
+        f.step(k)
+    assert_fused_pair(forms["fused"], forms["tail"], "B")
+    q = torch.nn.Parameter(start[ls_off : ls_off + ls_n].clone())
+    ref = torch.optim.Adam([q], lr=lr0)
+    q.grad = gl.float()
+    assert abs(torch.nn.utils.clip_grad_norm_([q], 1.0).item() - (650 / 16) ** 0.5) < 1e-5
+    ref.step()
+    got = forms["tail"].fa.flat
+    assert torch.allclose(got[ls_off : ls_off + ls_n], q.detach(), rtol=2e-5, atol=2e-6) and not torch.equal(got[ls_off : ls_off + ls_n], start[ls_off : ls_off + ls_n])
+    moved = got != start
+    assert int(moved.sum()) == ls_n and bool(moved[ls_off : ls_off + ls_n].all()) and forms["tail"].fa.lr.item() == forms["fused"].fa.lr.item() == pytest.approx(lr0)
+
+
 def _assert_same_adam_steps(name, p, q, start):
     """Two fp32 evaluations of the same update.  Adam normalises every step to ~lr per parameter whatever the gradient's size, so a rounding-size
     difference in a gradient becomes a FRACTION OF A STEP in the parameter -- and the whole step (both signs) for the few elements whose gradient

@@ -2,7 +2,8 @@
 gfx950 code object, disassembles it, cuts the text into functions and compares each function's instruction text with addresses, encodings, branch-target
 labels and the padding between functions removed.  Whole texts are compared; no instruction is looked for.  No GPU needed.
     python tools/isa_diff.py PARENT_CSRC TREE_CSRC -> one line per function: object, same / differs / gone / new, instructions in the parent and in the
-    tree, demangled name (no parameter list, no `(anonymous namespace)::`); kernels: VGPRs, SGPRs, LDS bytes, scratch bytes as parent -> tree"""
+    tree, demangled name (no parameter list, no `(anonymous namespace)::`); kernels: VGPRs, SGPRs, LDS bytes, scratch bytes as parent -> tree; a function that differs: whether its floating-point opcodes are the parent's in order
+    python tools/isa_diff.py PARENT_CSRC TREE_CSRC OBJECT FUNCTION -> the unified diff of that function's instruction text"""
 import glob, os, re, shutil, subprocess, sys, tempfile
 LLVM = "/opt/rocm/llvm/bin/"
 META = ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size")
@@ -36,6 +37,12 @@ def functions(obj, tmp):
     return out
 
 
+def float_ops(ins):
+    """the opcodes of the floating-point instructions of a function, in order: v_* on f32 / f64 (conversions included) and the rcp / sqrt / rsq forms"""
+    ops = [l.split()[0] for l in ins]
+    return [o for o in ops if o.startswith("v_") and re.search(r"f32|f64|rcp|sqrt|rsq", o)]
+
+
 def main(parent, tree):
     count = {"same": 0, "differs": 0, "gone": 0, "new": 0}
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
@@ -49,9 +56,19 @@ def main(parent, tree):
                 res = ""
                 if ma or mb:
                     res = "  " + " ".join(f"{k} {x if x == y else f'{x} -> {y}'}" for k, x, y in zip(("vgpr", "sgpr", "lds", "scratch"), ma or ("-",) * 4, mb or ("-",) * 4))
+                if what == "differs":  # is the arithmetic the parent's?  The floating-point opcodes in order, operands aside
+                    fa, fb = float_ops(ia), float_ops(ib)
+                    res += f"  float opcodes {len(fa)} -> {len(fb)}, {'the same sequence' if fa == fb else 'ANOTHER sequence'}"
                 print(f"{o:28s} {what:8s} {len(ia):6d} {len(ib):6d}  {f}{res}")
     print("\n" + ", ".join(f"{v} {k}" for k, v in count.items()))
 
 
+def show(parent, tree, obj, func):
+    import difflib
+    with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
+        a, b = (functions(os.path.join(d, obj), t)[func][0] for d, t in ((parent, ta), (tree, tb)))
+    print("\n".join(difflib.unified_diff(a, b, "parent", "tree", lineterm="", n=2)))
+
+
 if __name__ == "__main__":
-    main(*sys.argv[1:3])
+    show(*sys.argv[1:5]) if len(sys.argv) > 3 else main(*sys.argv[1:3])
