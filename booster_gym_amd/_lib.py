@@ -134,7 +134,13 @@ class EnvCfg(C.Structure):
         ("frame_stack", C.c_int32),
         ("actor_heights", C.c_int32), ("noise_height_measurements", Rand),
         ("student_frame_stack", C.c_int32),
+        ("priv_extras", C.c_int32), ("priv_force_scale", C.c_float), ("priv_clearance_scale", C.c_float),
     ]
+
+
+# bits of EnvCfg.priv_extras (BG_PRIV_EXTRA_*) and the columns of each group, in the row's fixed order (env.privileged_extras; envs/t1.py)
+PRIV_EXTRA_FEET, PRIV_EXTRA_GROUND, PRIV_EXTRA_JOINTS = 1, 2, 4
+PRIV_EXTRA_GROUPS = (("feet", PRIV_EXTRA_FEET, 6), ("ground", PRIV_EXTRA_GROUND, 6), ("joints", PRIV_EXTRA_JOINTS, 12))
 
 
 # every symbol include/booster_gym_amd.h declares (tests check that the .so exports all of them)

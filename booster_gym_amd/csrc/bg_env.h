@@ -85,12 +85,12 @@ struct EnvDev {
 
 struct StepOut {
     float* obs;      // [N][47]: the caller's output, or with cfg.frame_stack > 1 a plane of the env's observation ring (bg_obs_stack, bg_sim.hip)
-    float* priv;     // [N][priv_stride]: columns 0..13 from the env step; 14.. the height scan (bg_height_scan), when there is one
+    float* priv;     // [N][priv_stride]: columns 0..13 from the env step; 14.. the height scan (bg_height_scan), when there is one; then cfg.priv_extras' columns (bg_priv_extras)
     float* rew;      // [N]
     uint8_t* done;   // [N]
     uint8_t* tout;   // [N]
     float* terms;    // [26][N] or null
-    int priv_stride; // floats per privileged row: 14 + cfg.height_scan_points
+    int priv_stride; // floats per privileged row: 14 + cfg.height_scan_points + the columns of cfg.priv_extras
 };
 
 BG_HD float apply_rand(float x, const bg_rand& r, float u, float nrm) {

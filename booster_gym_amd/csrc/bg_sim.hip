@@ -192,6 +192,59 @@ __global__ __launch_bounds__(SCAN_BLOCK) void bg_height_scan(EnvDev E, const flo
     priv[(size_t)e * stride + BG_NUM_PRIV + p] = v * E.cfg.height_scan_scale;
 }
 
+// ------------------------------------------------------------------ privileged extras of the critic (cfg.priv_extras != 0)
+// Feet, ground and joint friction behind the 14 (+ P) privileged columns: columns [off, off + X) of every row, off = 14 + P, from the fields the env
+// step has STORED (so a host restatement through bg_env_get_field sees the same values; on the step an env resets, the feet fields are the ones
+// stored before the reset pose: include/booster_gym_amd.h).  A block owns PX_ENVS = 64 envs and has one wave per role: left foot, right foot,
+// ground, joints.  Reads run along envs: the state is field-major [field][n], so lane l of a wave reads env e0 + l of one field plane, 64
+// consecutive floats; the role is wave-uniform, a group that is off costs its wave one uniform branch.  Writes run along columns: the waves stage
+// their values in LDS (64 envs x 24 floats at most, the row stride odd so that the lanes of a wave fall on different banks), and after the barrier
+// one thread per destination element, consecutive lanes on consecutive columns, stores each row's X floats as one contiguous run.  The bilinear
+// ground height is evaluated once per (env, foot).  No atomics.
+constexpr int PX_ENVS = 64, PX_BLOCK = 256, PX_MAX = 24, PX_LD = PX_MAX + 1;
+static int priv_extras_columns(int mask) {
+    return ((mask & BG_PRIV_EXTRA_FEET) ? 6 : 0) + ((mask & BG_PRIV_EXTRA_GROUND) ? 6 : 0) + ((mask & BG_PRIV_EXTRA_JOINTS) ? 12 : 0);
+}
+template <bool H16>
+__global__ __launch_bounds__(PX_BLOCK) void bg_priv_extras(EnvDev E, float* __restrict__ priv, int stride, int off) {
+    __shared__ float s_x[PX_ENVS * PX_LD];
+    const int n = E.n, e0 = blockIdx.x * PX_ENVS, rows = min(PX_ENVS, n - e0);
+    const int mask = E.cfg.priv_extras;
+    const int c_ground = (mask & BG_PRIV_EXTRA_FEET) ? 6 : 0, c_joints = c_ground + ((mask & BG_PRIV_EXTRA_GROUND) ? 6 : 0);
+    const int X = c_joints + ((mask & BG_PRIV_EXTRA_JOINTS) ? 12 : 0);
+    const int role = threadIdx.x >> 6, el = threadIdx.x & 63, e = e0 + el;
+    if (el < rows) {  // (e < n)
+        float* sx = s_x + el * PX_LD;
+#define SFLD(off_) field_ref<H16>(E.f, E.h, (off_), n, e)
+        if (role < 2) {
+            if (mask & BG_PRIV_EXTRA_FEET) {
+                const int leg = role;
+                const float fz = SFLD(F_CONTACT + 3 * leg + 2);
+                const float px = SFLD(F_FEET_POS + 3 * leg + 0), py = SFLD(F_FEET_POS + 3 * leg + 1), pz = SFLD(F_FEET_POS + 3 * leg + 2);
+                sx[leg] = SFLD(F_FEET_CONTACT + leg);
+                sx[2 + leg] = fminf(fmaxf(fz * E.cfg.priv_force_scale, -5.f), 5.f);
+                sx[4 + leg] = fminf(fmaxf(pz - terrain_height(E.terrain, px, py), -1.f), 1.f) * E.cfg.priv_clearance_scale;
+            }
+        } else if (role == 2) {
+            if (mask & BG_PRIV_EXTRA_GROUND) {
+#pragma unroll
+                for (int k = 0; k < 6; k++) sx[c_ground + k] = SFLD(F_FOOT_MAT + k);
+            }
+        } else {
+            if (mask & BG_PRIV_EXTRA_JOINTS) {
+#pragma unroll
+                for (int j = 0; j < BG_NUM_DOFS; j++) sx[c_joints + j] = SFLD(F_FRIC + j);
+            }
+        }
+#undef SFLD
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < rows * X; t += PX_BLOCK) {
+        const int r = t / X, c = t - r * X;
+        priv[(size_t)(e0 + r) * stride + off + c] = s_x[r * PX_LD + c];
+    }
+}
+
 // ------------------------------------------------------------------ evaluation record (bg_env_eval_begin / bg_env_eval_step; evaluate.py)
 // Per-robot metrics of every env's FIRST episode in the caller's record [BG_EVAL_PLANES][n], plane-major: one thread per env, so a wave loads and
 // stores 64 consecutive floats of a plane.  No atomics, no LDS, nothing across envs: the report (utils/evaluate.py) reduces on the host, once.  A
@@ -940,7 +993,7 @@ static int env_create_fill(bg_env* e, const bg_env_cfg* cfg, const bg_model* mod
     HIP_OK(hipMemcpy(e->pair_dev, &pmh, sizeof(pmh), hipMemcpyHostToDevice));
     e->terrain.type = 0; e->terrain.rows = e->terrain.cols = e->terrain.border_px = 0; e->terrain.inv_hscale = 1.f; e->terrain.vscale = 0.f; e->terrain.hf = nullptr;
     memset(&e->bound, 0, sizeof(e->bound));
-    e->bound.priv_stride = BG_NUM_PRIV + cfg->height_scan_points;
+    e->bound.priv_stride = BG_NUM_PRIV + cfg->height_scan_points + priv_extras_columns(cfg->priv_extras);
     e->cfg.height_scan_xy = nullptr;  // (the caller's host array: read here, never kept)
     if (cfg->height_scan_points > 0) {
         HIP_OK(hipMalloc(&e->scan_xy, sizeof(float) * 2 * cfg->height_scan_points));
@@ -1002,6 +1055,9 @@ extern "C" int bg_env_create(const bg_env_cfg* cfg, const bg_model* model, bg_en
     if (cfg->student_frame_stack != 0 && (!cfg->actor_heights || cfg->student_frame_stack < (cfg->frame_stack > 1 ? cfg->frame_stack : 1) || cfg->student_frame_stack > BG_MAX_FRAME_STACK ||
                                           (int64_t)cfg->num_envs * BG_NUM_OBS * cfg->student_frame_stack >= (int64_t)1 << 31))
         return fail(-1, "bg_env_create: student_frame_stack needs actor_heights and a value in frame_stack .. BG_MAX_FRAME_STACK (0 = off) with num_envs x 47 x student_frame_stack below 2^31");
+    if ((cfg->priv_extras & ~BG_PRIV_EXTRA_ALL) != 0 ||
+        (cfg->priv_extras != 0 && (int64_t)cfg->num_envs * (BG_NUM_PRIV + cfg->height_scan_points + priv_extras_columns(cfg->priv_extras)) >= (int64_t)1 << 31))
+        return fail(-1, "bg_env_create: priv_extras must be a combination of BG_PRIV_EXTRA_FEET | GROUND | JOINTS (0 = off) with num_envs x (14 + height_scan_points + extras) below 2^31");
     int ndev = 0;
     hipError_t de = hipGetDeviceCount(&ndev);
     if (de != hipSuccess || ndev == 0) return fail(-3, "bg_env_create: no HIP device available (this library has no CPU path)");
@@ -1115,6 +1171,12 @@ static int launch_step(bg_env* e, const float* actions, int mode, const StepOut&
         hipLaunchKernelGGL(resample_count_kernel, dim3(nb), dim3(RS_BLOCK), 0, st, env_dev(e), e->rs_counts);
         hipLaunchKernelGGL(resample_offsets_kernel, dim3(1), dim3(RS_BLOCK), 0, st, e->rs_counts, nb);
         hipLaunchKernelGGL(resample_apply_kernel, dim3(nb), dim3(RS_BLOCK), 0, st, env_dev(e), (const int*)e->rs_counts, nb, cnt, mode, out.obs);
+    }
+    if (e->cfg.priv_extras) {  // the critic's extras from the fields the launches above have stored: columns [14 + P, 14 + P + X), nobody else's (bg_priv_extras)
+        dim3 gs((unsigned)((e->n + PX_ENVS - 1) / PX_ENVS));
+        const int off = BG_NUM_PRIV + e->cfg.height_scan_points;
+        if (e->h) hipLaunchKernelGGL(bg_priv_extras<true>, gs, dim3(PX_BLOCK), 0, st, env_dev(e), out.priv, out.priv_stride, off);
+        else hipLaunchKernelGGL(bg_priv_extras<false>, gs, dim3(PX_BLOCK), 0, st, env_dev(e), out.priv, out.priv_stride, off);
     }
     if (e->cfg.actor_heights) {  // last, in place of the two launches below: the actor's row [47 H + P] and the critic's clean scan (bg_obs_assemble)
         const int P = e->cfg.height_scan_points, H = e->cfg.frame_stack;

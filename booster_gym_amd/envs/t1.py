@@ -64,11 +64,89 @@ def student_frame_stack_of(cfg):
     return Hs
 
 
+PRIVILEGED_EXTRAS = tuple(g for g, _, _ in _lib.PRIV_EXTRA_GROUPS)  # the legal names of env.privileged_extras, in the row's order
+
+
+def privileged_extras_of(cfg):
+    """env.privileged_extras (an addition of this build; absent, null or [] = off): (groups, X), the chosen groups as a tuple in the ROW's order (feet,
+    ground, joints, whatever the order in the list) and the number X of privileged columns they add behind the 14 (+ P).  Pure.  ValueError naming the
+    key and the legal names unless it is a list of distinct names among them."""
+    v = cfg["env"].get("privileged_extras")
+    if v is None:
+        return (), 0
+    legal = ", ".join(f'"{g}"' for g in PRIVILEGED_EXTRAS)
+    if not isinstance(v, (list, tuple)):
+        raise ValueError(f"env.privileged_extras = {v!r} must be a list of group names among {legal} (absent, null or [] = off)")
+    for g in v:
+        if not isinstance(g, str) or g not in PRIVILEGED_EXTRAS:
+            raise ValueError(f"env.privileged_extras names {g!r}: the groups are {legal}")
+        if list(v).count(g) > 1:
+            raise ValueError(f"env.privileged_extras names {g!r} more than once: each of {legal} at most once")
+    groups = tuple(g for g in PRIVILEGED_EXTRAS if g in v)
+    return groups, sum(x for g, _, x in _lib.PRIV_EXTRA_GROUPS if g in groups)
+
+
+CONTACT_FORCE_SCALE = 0.003  # normalization.contact_force when absent: about one over the robot's weight in newtons (a design default, not a measurement)
+
+
+def contact_force_scale_of(cfg):
+    """normalization.contact_force (absent = CONTACT_FORCE_SCALE), the scale of the feet group's force columns; read with "feet" in
+    env.privileged_extras only.  ValueError naming the key unless it is a number above 0."""
+    s = cfg["normalization"].get("contact_force", CONTACT_FORCE_SCALE)
+    if isinstance(s, bool) or not isinstance(s, (int, float)) or not s > 0:
+        raise ValueError(f"normalization.contact_force = {s!r} must be a number above 0 (the feet group of env.privileged_extras shows the critic "
+                         f"clip(Fz x contact_force, -5, 5); default {CONTACT_FORCE_SCALE})")
+    return float(s)
+
+
+def privileged_extra_names(groups):
+    """The X column labels of the groups, in row order: "feet.contact_left" ... "ground.friction_left" ... "joints.friction_0" ..."""
+    names = []
+    if "feet" in groups:
+        names += [f"feet.{q}_{s}" for q in ("contact", "force", "clearance") for s in ("left", "right")]
+    if "ground" in groups:
+        names += [f"ground.{q}_{s}" for s in ("left", "right") for q in ("friction", "compliance", "restitution")]
+    if "joints" in groups:
+        names += [f"joints.friction_{j}" for j in range(_lib.NUM_DOFS)]
+    return tuple(names)
+
+
+def _check_env_sizes_with_extras(cfg, P, groups, X):
+    """check_env_sizes with env.privileged_extras on: the same sizes, the privileged row 14 + P + X, every message naming the key."""
+    env, H = cfg["env"], frame_stack_of(cfg)
+    no, npv, na = env["num_observations"], env["num_privileged_obs"], env["num_actions"]
+    actor = actor_heights_of(cfg["terrain"])
+    want_obs = _lib.NUM_OBS * H + (P if actor else 0)
+    want_priv = _lib.NUM_PRIV + P + X
+    listed = "[" + ", ".join(groups) + "]"
+    if no != want_obs:  # (the extras add nothing to the actor's row)
+        scan = f" + {P} (terrain.actor_heights)" if actor else ""
+        raise ValueError(f"env.num_observations = {no}, but env.frame_stack = {H} computes {_lib.NUM_OBS} x {H}{scan} = {want_obs} observations: set "
+                         f"env.num_observations to {want_obs}")
+    if actor and want_obs > MAX_ACTOR_INPUT:
+        raise ValueError(f"terrain.actor_heights: the actor's input {_lib.NUM_OBS} x {H} (env.frame_stack) + {P} = {want_obs} exceeds {MAX_ACTOR_INPUT} "
+                         f"(the widest first layer of the rollout's sampling kernel): a smaller env.frame_stack, or fewer points of the height scan")
+    if npv != want_priv:
+        scan = f" + {P} (terrain.measure_heights)" if P else ""
+        raise ValueError(f"env.num_privileged_obs = {npv}, but env.privileged_extras = {listed} computes {_lib.NUM_PRIV}{scan} + {X} = {want_priv} "
+                         f"privileged observations: set env.num_privileged_obs to {want_priv}")
+    if want_obs + want_priv > MAX_CRITIC_INPUT:
+        raise ValueError(f"env.privileged_extras = {listed}: the critic's input {want_obs} (env.num_observations) + {_lib.NUM_PRIV} + {P} + {X} = "
+                         f"{want_obs + want_priv} exceeds {MAX_CRITIC_INPUT} (the widest first layer of the kernels): fewer groups, a smaller "
+                         f"env.frame_stack, or fewer points of the height scan")
+    if na != _lib.NUM_DOFS:
+        raise ValueError("this build computes 12 actions (envs/T1.yaml env.num_actions)")
+
+
 def check_env_sizes(cfg, num_height_points):
     """ValueError unless env.num_observations / num_privileged_obs / num_actions are what this build computes: 47 H (H = env.frame_stack single
     observations, 47 without the key; 47 H + P with terrain.actor_heights), 14 (+ P with the terrain height scan's P points: legged_gym requires
-    num_observations to match what the env computes) and 12; and the critic's input, observations + privileged observations, within MAX_CRITIC_INPUT."""
+    num_observations to match what the env computes; + X with env.privileged_extras) and 12; and the critic's input, observations + privileged
+    observations, within MAX_CRITIC_INPUT."""
     env, P, H = cfg["env"], num_height_points, frame_stack_of(cfg)
+    groups, X = privileged_extras_of(cfg)
+    if X:
+        return _check_env_sizes_with_extras(cfg, P, groups, X)
     no, npv, na = env["num_observations"], env["num_privileged_obs"], env["num_actions"]
     if actor_heights_of(cfg["terrain"]):
         want = _lib.NUM_OBS * H + P
@@ -131,6 +209,8 @@ class T1(BaseTask):
         super().__init__(cfg)
         check_env_sizes(cfg, len(self.terrain.height_points))  # (before anything touches the device)
         student_frame_stack_of(cfg)
+        if "feet" in privileged_extras_of(cfg)[0]:
+            contact_force_scale_of(cfg)
         self._lib = _lib.load()
         self._model = None
         self._env = None
@@ -247,6 +327,10 @@ class T1(BaseTask):
         # the critic's terrain height scan (terrain.measure_heights): P more privileged columns after the 14 (checked in __init__)
         P = self.num_height_points = len(self.terrain.height_points)
         self.height_points = torch.tensor(self.terrain.height_points, dtype=torch.float, device=self.device).reshape(P, 2)
+        # the critic's extras (env.privileged_extras): X more privileged columns behind the 14 + P, the groups in the row's order (checked in __init__)
+        self.privileged_extras, self.num_privileged_extras = privileged_extras_of(cfg)
+        self.privileged_extras_offset = _lib.NUM_PRIV + P
+        self.privileged_extra_names = privileged_extra_names(self.privileged_extras)
         # the actor's height scan (terrain.actor_heights): the row is [47 H single observations | P scan values], the newest scan only, with noise
         self.actor_heights = self.terrain.actor_heights
         self.num_scan_obs, self.scan_obs_offset = (P if self.actor_heights else 0), self.num_single_obs * self.frame_stack
@@ -372,6 +456,11 @@ class T1(BaseTask):
                     setr(c.noise_height_measurements, nc.get("height_measurements"))
         c.frame_stack = self.frame_stack
         c.student_frame_stack = self.student_frame_stack
+        if self.privileged_extras:  # (off: the three fields stay zero, as in a struct older than them)
+            c.priv_extras = sum(bit for g, bit, _ in _lib.PRIV_EXTRA_GROUPS if g in self.privileged_extras)
+            if "feet" in self.privileged_extras:
+                c.priv_force_scale = contact_force_scale_of(cfg)
+                c.priv_clearance_scale = float(nz.get("height_measurements", 5.0))
         sd = str(cfg["sim"].get("state_dtype", "fp32")).lower()
         if sd not in ("fp32", "float32", "fp16", "float16", "half"):
             raise ValueError(f"sim.state_dtype must be fp32 or fp16, got {sd!r}")

@@ -52,7 +52,7 @@ import torch
 from .. import _lib
 from ..envs import TASKS
 from ..envs.mirror import mirror_maps
-from ..envs.t1 import MAX_CRITIC_INPUT, MAX_FRAME_STACK, frame_stack_of
+from ..envs.t1 import MAX_CRITIC_INPUT, MAX_FRAME_STACK, frame_stack_of, privileged_extras_of
 from .buffer import ExperienceBuffer
 from .config import load_cfg
 from .estimator import estimator_enabled
@@ -123,7 +123,8 @@ def distillation_cfg(cfg, world_size=1):
 def student_frame_stack_of(cfg):
     """distillation.student_frame_stack as the number Hs of single observations in the student's row: null or absent = the teacher's env.frame_stack = H.
     Pure.  ValueError naming the key unless it is an integer in H .. MAX_FRAME_STACK whose student config passes the env's own size check: the
-    student's critic takes 47 Hs + 14 + P columns (P points of terrain.measured_points_x x measured_points_y), MAX_CRITIC_INPUT at most."""
+    student's critic takes 47 Hs + 14 + P (+ X) columns (P points of terrain.measured_points_x x measured_points_y, X columns of
+    env.privileged_extras), MAX_CRITIC_INPUT at most."""
     H = frame_stack_of(cfg)
     sec = cfg.get("distillation")
     Hs = sec.get("student_frame_stack") if isinstance(sec, dict) else None
@@ -133,10 +134,12 @@ def student_frame_stack_of(cfg):
         raise ValueError(f"distillation.student_frame_stack = {Hs!r} must be null or an integer from env.frame_stack = {H} (the teacher's) to "
                          f"{MAX_FRAME_STACK}: the student sees the env's last student_frame_stack observations, the teacher's {H} among them")
     P = len(height_scan_points(cfg["terrain"])[1])
-    if _lib.NUM_OBS * Hs + _lib.NUM_PRIV + P > MAX_CRITIC_INPUT:
+    X = privileged_extras_of(cfg)[1]  # (env.privileged_extras: the student's untrained critic has the teacher config's privileged row)
+    if _lib.NUM_OBS * Hs + _lib.NUM_PRIV + P + X > MAX_CRITIC_INPUT:
+        extras = f" + {X} (env.privileged_extras)" if X else ""
         raise ValueError(f"distillation.student_frame_stack = {Hs}: the student's config (env.frame_stack: {Hs}, terrain.actor_heights: false) has a critic of "
-                         f"{_lib.NUM_OBS} x {Hs} + {_lib.NUM_PRIV} + {P} (terrain.measured_points_x x terrain.measured_points_y) = "
-                         f"{_lib.NUM_OBS * Hs + _lib.NUM_PRIV + P} inputs, above {MAX_CRITIC_INPUT} (the widest first layer of the kernels): a smaller "
+                         f"{_lib.NUM_OBS} x {Hs} + {_lib.NUM_PRIV} + {P} (terrain.measured_points_x x terrain.measured_points_y){extras} = "
+                         f"{_lib.NUM_OBS * Hs + _lib.NUM_PRIV + P + X} inputs, above {MAX_CRITIC_INPUT} (the widest first layer of the kernels): a smaller "
                          f"distillation.student_frame_stack, or fewer points of the height scan")
     return Hs
 

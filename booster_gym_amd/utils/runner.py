@@ -534,6 +534,10 @@ class Runner:
                              f"{self.env.num_single_obs} x env.frame_stack): env.frame_stack must be as in the run that saved the checkpoint "
                              f"({ck_ain // self.env.num_single_obs if ck_ain % self.env.num_single_obs == 0 else '?'})")
         ck_in, c_in = int(model_dict["model"]["critic.0.weight"].shape[1]), self.model.critic[0].in_features
+        ex_ck, ex_cfg = list(model_dict.get("privileged_extras", [])), list(getattr(self.env, "privileged_extras", ()))
+        if ex_ck != ex_cfg:  # (before the width message below: groups of equal width, feet and ground, would pass it)
+            raise ValueError(f"checkpoint {ck} was saved with env.privileged_extras = {ex_ck}, the config has env.privileged_extras = {ex_cfg}: the critic's "
+                             f"privileged columns differ; set env.privileged_extras (and env.num_privileged_obs) as in the run that saved the checkpoint")
         if ck_in != c_in:  # (the critic's input: observations + privileged observations, with the terrain height scan 14 + P of the latter)
             raise ValueError(f"checkpoint {ck} has a critic of {ck_in} inputs, the config's critic takes {c_in} (env.num_observations + "
                              f"env.num_privileged_obs): terrain.measure_heights and its measured_points_x / measured_points_y must be as in the run "
@@ -590,6 +594,8 @@ class Runner:
             d["obs_normalizer"] = self.obs_norm.state_dict()
         if getattr(self.env, "num_scan_obs", 0):  # terrain.actor_heights: the grid of the scan at the end of the actor's row, for whoever deploys the actor
             d["height_points"] = self.env.height_points.clone()
+        if getattr(self.env, "privileged_extras", ()):  # env.privileged_extras: the groups behind the critic's 14 + P columns, in the row's order
+            d["privileged_extras"] = list(self.env.privileged_extras)
         return d
 
     # ------------------------------------------------------------------ one PPO iteration

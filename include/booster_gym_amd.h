@@ -145,7 +145,7 @@ typedef struct {
     float terrain_tile_width, terrain_tile_length, terrain_down_time;
     /* Terrain height scan of the critic (T1.yaml terrain.measure_heights; an addition of this build, legged_gym's measured heights).  0 points =
      * off: nothing below is read and the privileged row is the 14 values.  P > 0 (a height field only): after every env step and reset-all, one
-     * more launch (bg_height_scan) writes columns 14 .. 14 + P of each privileged row [N][14 + P]:
+     * more launch (bg_height_scan) writes columns 14 .. 14 + P of each privileged row [N][14 + P] ([N][14 + P + X] with priv_extras, below):
      *   clip(base z - h(base xy + Rz(yaw) (x_p, y_p)) - base_height_target, -1, 1) * height_scan_scale
      * with h the bilinear ground height, yaw that of the stored base quaternion, no noise. */
     int32_t height_scan_points;       /* P: points of the scan (0 = off) */
@@ -177,7 +177,26 @@ typedef struct {
      * The destination comes from bg_env_bind_student_obs (bg_env_reset, bg_env_step) or bg_env_step_to_student; a reset or step without one is an
      * error, and so is bg_env_step_to.  num_envs x 47 Hs must stay below 2^31. */
     int32_t student_frame_stack;
+    /* More of what the env randomises and computes, for the critic (T1.yaml env.privileged_extras; an addition of this build, humanoid-gym's
+     * env_frictions / contact_mask and the foot height / contact targets of Ji et al. 2022).  priv_extras = 0 = off (a zero-initialised struct: every
+     * caller older than the field): nothing below is read and no launch is added.  Otherwise a bitmask of BG_PRIV_EXTRA_*; the privileged row is
+     * [N][14 + P + X] and one more launch (bg_priv_extras) behind the env-step kernels of every env step and reset-all, in front of bg_height_scan /
+     * bg_obs_stack / bg_obs_assemble, writes its columns [14 + P, 14 + P + X), the groups in the fixed order feet, ground, joints (left foot = leg 0
+     * first), all from the STORED per-env fields (bg_env_get_field's names), without noise:
+     *   FEET (6):    feet_contact[0], [1];  clip(feet_contact_forces[leg][z] * priv_force_scale, -5, 5) of leg 0, 1;
+     *                clip(feet_pos[leg][z] - h(feet_pos[leg][xy]), -1, 1) * priv_clearance_scale of leg 0, 1, h the bilinear ground height (0 on a plane)
+     *   GROUND (6):  foot_material[0..6) = friction, compliance, restitution of the left foot, then of the right
+     *   JOINTS (12): dof_friction[0..12)
+     * On the step in which an env resets, the feet fields are those the env step stored BEFORE the reset pose (the reference's buffers of the same
+     * names behave so), while the root and the 14 columns are the new episode's.  An unknown bit or num_envs x (14 + P + X) >= 2^31: bg_env_create fails. */
+    int32_t priv_extras;
+    float priv_force_scale;     /* normalization.contact_force; read with BG_PRIV_EXTRA_FEET only */
+    float priv_clearance_scale; /* normalization.height_measurements; read with BG_PRIV_EXTRA_FEET only */
 } bg_env_cfg;
+#define BG_PRIV_EXTRA_FEET 1
+#define BG_PRIV_EXTRA_GROUND 2
+#define BG_PRIV_EXTRA_JOINTS 4
+#define BG_PRIV_EXTRA_ALL 7
 
 /* ---- model (replaces gym.load_asset and the asset queries, t1.py:54-108) */
 int bg_model_create(const bg_model_desc* desc, bg_model** out);
@@ -214,7 +233,7 @@ int bg_env_set_heightfield(bg_env* env, const int16_t* hf_host, int32_t rows, in
 int bg_env_set_params(bg_env* env, const float* kp, const float* kd, const float* friction, const float* mass_scale, const float* com_offset,
                       const float* foot_material, const float* base_mass_scaled, const float* env_origins);
 /* outputs of reset/step, device pointers owned by the caller (torch tensors): obs [N][47 H] (H = cfg.frame_stack, [N][47] without a
- * history; [N][47 H + P] with cfg.actor_heights), privileged [N][14 + P] (P = cfg.height_scan_points, 0 without the height scan: [N][14]), rew [N], done uint8 [N], time_outs uint8 [N], rew_terms [26][N] (rows of dropped terms stay 0) */
+ * history; [N][47 H + P] with cfg.actor_heights), privileged [N][14 + P + X] (P = cfg.height_scan_points, 0 without the height scan; X = the columns of cfg.priv_extras, 0 without: [N][14]), rew [N], done uint8 [N], time_outs uint8 [N], rew_terms [26][N] (rows of dropped terms stay 0) */
 int bg_env_bind_outputs(bg_env* env, float* obs, float* privileged_obs, float* rew, uint8_t* done, uint8_t* time_outs, float* rew_terms);
 /* The student's row of bg_env_reset / bg_env_step (bg_env_cfg.student_frame_stack = Hs): device float [N][47 Hs], owned by the caller.  An error
  * naming the field when it is 0. */
