@@ -148,6 +148,7 @@ HEAD_SCRATCH_FLOATS = 768 * 1720  # BG_HEAD_SCRATCH_FLOATS
 OBS_MOMENTS_MAX_GROUPS = 1024  # BG_OBS_MOMENTS_MAX_GROUPS
 GATHER_MAX_STREAMS = 8  # BG_GATHER_MAX_STREAMS
 ACTOR_PACKED_FLOATS = 65616  # BG_ACTOR_PACKED_FLOATS
+PARTNER_NEXT, PARTNER_INTERPOLATE = 0, 1  # BG_PARTNER_NEXT / BG_PARTNER_INTERPOLATE: the modes of bg_partner_rows (algorithm.smoothness_pairs)
 TAIL_MAX_BLOCKS = 8192  # BG_TAIL_MAX_BLOCKS: blocks of sums of one bg_update_tail launch = float64 slots of its norm_scratch
 # planes of the evaluation record [EVAL_PLANES][N] (bg_env_eval_begin / bg_env_eval_step): the one place that names them, for the kernel's callers
 # and for the report (utils/evaluate.py).  Command class c = 0 still, 1 slow (max |cmd| <= 0.5), 2 fast.
@@ -171,7 +172,7 @@ SYMBOLS = [
     "bg_sim_refresh_body_state", "bg_sim_write_root_state", "bg_sim_write_dof_state", "bg_gae", "bg_ppo_loss", "bg_gaussian_logp", "bg_actor_pack", "bg_actor_sample", "bg_actor_sample_mlp", "bg_actor_sample_mlp_scan", "bg_distill_act", "bg_distill_act_hist", "bg_distill_act_mix", "bg_actor_sample_est", "bg_adam_step", "bg_adapt_lr", "bg_optimizer_step", "bg_elu_backward_colsum", "bg_mlp_layer_forward", "bg_mlp_chain_forward", "bg_critic_values_gae", "bg_mlp_chain_forward_group", "bg_mlp_chain_forward_split", "bg_mlp_chain_backward_split", "bg_mlp_split_weights_pm", "bg_mlp_layer_backward", "bg_mlp_split_weights", "bg_mlp_layer_forward_split", "bg_mlp_layer_backward_split", "bg_mlp_weight_grad", "bg_mlp_weight_grad_group", "bg_mlp_weight_grad_group_partial", "bg_update_tail", "bg_update_tail_sums", "bg_mlp_weight_grad_group_split", "bg_mlp_weight_grad_group_split_partial",
     "bg_critic_head_forward", "bg_actor_head", "bg_critic_head_backward",
     "bg_reduce_group", "bg_actor_head_partial", "bg_critic_head_backward_partial", "bg_mlp_layer_backward_partial",
-    "bg_actor_head_sym", "bg_actor_head_sym_partial", "bg_mirror_rows",
+    "bg_actor_head_sym", "bg_actor_head_sym_partial", "bg_mirror_rows", "bg_partner_rows",
     "bg_distill_head", "bg_distill_head_partial", "bg_distill_head_sym", "bg_distill_head_sym_partial",
     "bg_obs_moments", "bg_obs_normalize",
     "bg_perm_fill", "bg_gather_rows",
@@ -285,6 +286,7 @@ def load():
         "bg_actor_head_sym": (i32, [i32] + [vp] * 10 + [f32] * 4 + [vp] * 11),
         "bg_actor_head_sym_partial": (i32, [i32] + [vp] * 10 + [f32] * 4 + [vp] * 10 + [C.POINTER(ReduceProblem), vp]),
         "bg_mirror_rows": (i32, [i32, i32, vp, vp, vp, vp, vp]),
+        "bg_partner_rows": (i32, [i32, i32, i32, vp, vp, vp, vp, i32, u64, C.c_uint32, C.c_uint32, vp, vp]),
         "bg_distill_head": (i32, [i32] + [vp] * 12),
         "bg_distill_head_partial": (i32, [i32] + [vp] * 11 + [C.POINTER(ReduceProblem), vp]),
         "bg_distill_head_sym": (i32, [i32] + [vp] * 4 + [f32] + [vp] * 10),

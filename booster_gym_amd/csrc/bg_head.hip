@@ -11,7 +11,8 @@
 //   bg_distill_head         mu = h W^T + b -> behaviour-cloning loss mean((mu - target)^2) and its backward (teacher-student distillation,
 //                           utils/distill.py): bg_actor_head's forward and backward mappings around bg_critic_head_backward's form of loss
 //   bg_actor_head_sym       bg_actor_head on a batch of 2B rows (the rollout's, then their mirror images) plus the mirror-symmetry loss
-//                           (algorithm.symmetry_loss); bg_mirror_rows writes the mirrored network inputs
+//                           (algorithm.symmetry_loss); bg_mirror_rows writes the mirrored network inputs.  With the identity action map and
+//                           bg_partner_rows' rows in the second half: the action-smoothness loss (algorithm.smoothness_loss)
 //   bg_distill_head_sym     bg_distill_head on the original rows of such a batch of 2B rows plus the mirror-symmetry loss on the student's mean
 //                           (distillation.symmetric_coef)
 // Arithmetic is plain fp32 FMA on the vector ALU: 4.6 kflop per row against 1 KB of traffic is under the HBM ridge, so nothing here is
@@ -21,6 +22,7 @@
 
 #include "bg_ppo_math.h"
 #include "bg_reduce.h"
+#include "bg_rng.h"
 
 namespace {
 
@@ -785,6 +787,42 @@ __global__ __launch_bounds__(256) void mirror_rows_kernel(int rows, int cols, Co
     }
 }
 
+// The partner rows of the action-smoothness loss (algorithm.smoothness_loss): y[r] = x[r] + u_r (x+[r] - x[r]) for the rows r = t N + e of x [T][N][cols],
+// x+[r] = the same env's row one step later (row r + N; for t = T - 1 the row e of x_last).  Where dones[r] or time_outs[r] is set (the steps at which
+// GAE cuts the trajectory) y[r] is a copy of x[r]; mode 0 (next): u = 1 as a plain copy of x+[r], no arithmetic; mode 1 (interpolate): u in [0, 1) =
+// the upper 24 bits of philox entry 0 on the key (seed) and the counter (r, update, RS_PARTNER, mini-epoch), one fma per element.
+// Memory-bound (mode 1: two rows read, one written; mode 0: one read, one written), shaped as bg_gather_rows: 16 bytes per lane, consecutive lanes on consecutive 16-byte pieces of one row
+// (cols / 4 lanes per row, a wave on 64 / (cols / 4) whole rows or on 1 KiB of one row), so every load and store of a wave covers whole consecutive
+// lines; the two flag bytes are read once per row (the lanes of a row read the same byte: one request per wave and row) and the draw, which is
+// arithmetic alone, is the same in every lane of a row.  Every lane writes its own 16 bytes: no atomics, nothing past row T N.
+constexpr int PARTNER_MAX_COLS = 512;
+__global__ __launch_bounds__(256) void partner_rows_kernel(uint32_t rows, uint32_t N, uint32_t per_row, int mode, uint64_t seed, uint32_t update, uint32_t epoch,
+                                                           const float* __restrict__ x, const float* __restrict__ x_last, const uint8_t* __restrict__ dones,
+                                                           const uint8_t* __restrict__ time_outs, float* __restrict__ y) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t row = t / per_row, piece = t - row * per_row;
+    if (row >= rows) return;
+    const size_t cols = 4 * (size_t)per_row, at = 4 * (size_t)piece;
+    const float* own = x + (size_t)row * cols + at;
+    float4 v;
+    if (dones[row] | time_outs[row]) {
+        v = *reinterpret_cast<const float4*>(own);
+    } else {
+        const float* nx = row + N < rows ? x + (size_t)(row + N) * cols : x_last + (size_t)(row + N - rows) * cols;
+        const float4 b = *reinterpret_cast<const float4*>(nx + at);
+        v = b;
+        if (mode) {  // (mode "next" reads one row per row, the successor or the row itself)
+            const float4 a = *reinterpret_cast<const float4*>(own);
+            uint32_t o[4];
+            bg::philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), row, update, (uint32_t)bg::RS_PARTNER, epoch, o);
+            const float u = (float)(o[0] >> 8) * (1.0f / 16777216.0f);
+            v = make_float4(__builtin_fmaf(u, b.x - a.x, a.x), __builtin_fmaf(u, b.y - a.y, a.y), __builtin_fmaf(u, b.z - a.z, a.z),
+                            __builtin_fmaf(u, b.w - a.w, a.w));
+        }
+    }
+    *reinterpret_cast<float4*>(y + (size_t)row * cols + at) = v;
+}
+
 int head_grid(int tiles) { return tiles < HEAD_MAX_GRID ? tiles : HEAD_MAX_GRID; }
 
 }  // namespace
@@ -1015,6 +1053,23 @@ extern "C" int bg_mirror_rows(int32_t rows, int32_t cols, const int32_t* src, co
     size_t blocks = ((size_t)rows * cols + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(mirror_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rows, cols, cm, x, y);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int bg_partner_rows(int32_t T, int32_t N, int32_t cols, const float* x, const float* x_last, const uint8_t* dones, const uint8_t* time_outs, int32_t mode,
+                               uint64_t seed, uint32_t update, uint32_t epoch, float* y, void* stream) {
+    if (T <= 0 || N <= 0 || !x || !x_last || !dones || !time_outs || !y) return bg_set_error(-1, "bg_partner_rows: bad argument");
+    if (cols < 4 || cols > PARTNER_MAX_COLS || cols % 4) return bg_set_error(-1, "bg_partner_rows: bad argument (cols a multiple of 4, 4 to 512)");
+    if (mode != BG_PARTNER_NEXT && mode != BG_PARTNER_INTERPOLATE) return bg_set_error(-1, "bg_partner_rows: bad argument (mode 0 = next or 1 = interpolate)");
+    if (!aligned16(x) || !aligned16(x_last) || !aligned16(y)) return bg_set_error(-1, "bg_partner_rows: x, x_last and y must be 16-byte aligned");
+    const uint64_t rows = (uint64_t)T * (uint64_t)N, per_row = (uint64_t)cols / 4;
+    if (rows >= (1ull << 31) || rows * per_row + 256 >= (1ull << 32)) return bg_set_error(-1, "bg_partner_rows: bad argument (the launch would exceed 2^32 threads)");
+    const float *xe = x + rows * cols, *le = x_last + (size_t)N * cols, *ye = y + rows * cols;
+    if ((x < ye && y < xe) || (x_last < ye && y < le)) return bg_set_error(-1, "bg_partner_rows: y overlaps x or x_last");
+    const uint64_t blocks = (rows * per_row + 255) / 256;
+    hipLaunchKernelGGL(partner_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (uint32_t)rows, (uint32_t)N, (uint32_t)per_row, (int)mode, seed,
+                       update, epoch, x, x_last, dones, time_outs, y);
     HIP_OK(hipGetLastError());
     return 0;
 }

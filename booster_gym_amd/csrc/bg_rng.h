@@ -66,6 +66,8 @@ enum {
     RS_TLEVEL = 27,   // terrain curriculum: the level of an env that passed the top one
     RS_PERM = 28,     // mini-batch shuffle: the Feistel round functions of bg_perm.h (counter words: half, round | mini-epoch << 8, this, update)
     RS_DAGGER = 29,   // distillation's DAgger mixing: entry 0 = the uniform that decides whether the teacher drives this (row, step) (bg_distill_act_mix)
+    RS_PARTNER = 30,  // action-smoothness loss, pairs "interpolate": entry 0 = the u of a row's partner (bg_partner_rows; counter words: row t N + e, update, this,
+                      // mini-epoch), as a uniform in [0, 1): the entry's upper 24 bits x 2^-24
     RS_ACTOR = 32,    // + k : action noise (bg_actor_sample)
     // (the env-step kernels and resample_apply_kernel add 64 to their ids at reset-all: 64 .. 64 + RS_TLEVEL are in use as well)
     RS_SCAN = 128,       // + (p >> 2), p < 1024 : noise of the actor's height scan, point p at entry p & 3 (bg_obs_assemble): 128 .. 383

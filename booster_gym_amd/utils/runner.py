@@ -34,6 +34,9 @@ Same surface: `Runner(test=False)` parses the reference's 8 CLI flags (runner.py
             on a state [N][H] carried over steps and iterations and zeroed where an env reset; the update runs the cell over the iteration's T steps
             from the state stored at the rollout's start (model.GRUTrainer: back-propagation through time, truncated there) around the trunk's
             per-layer kernels, its bias gradients as one launch (bg_gru_bias_partial) among the deferred reductions, the tail as separate launches.
+  smoothness algorithm.smoothness_loss (off by default): the action-smoothness loss, a second source of partner rows for the symmetry loss's 2B-row actor
+            path: rows [B, 2B) of the actor's input are every row's successor (bg_partner_rows: cut where GAE cuts, optionally interpolated with a
+            fresh draw per row and mini-epoch), the output layer runs as bg_actor_head_sym on the identity action map.  No forward-ahead then.
   multi-GPU one process per GPU (torchrun), environments sharded; per mini-epoch one float64 moments all-reduce on the side stream and ONE grouped RCCL
             launch on the main stream (gradient bucket mean, loss / KL sums, log-std gradient mean) through an own communicator (utils/rccl.py) --
             SURVEY section 8e; the enqueue-order contract of the two communicators is written in utils/parallel.py.
@@ -65,7 +68,7 @@ from .optim import FlatAdam
 from .parallel import DataParallel
 from .recorder import Recorder
 from .utils import (actor_head_forward, actor_head_loss_backward, actor_head_sym_loss_backward, critic_head_backward, critic_head_forward, critic_values_gae, gae,
-                    gaussian_logp, head_scratch, mirror_rows, reduce_group, ppo_loss_fused)
+                    gaussian_logp, head_scratch, mirror_rows, partner_rows, reduce_group, ppo_loss_fused)
 
 
 def plan_chain_split(slabs_c, slabs_a, cost_c, cost_a, cus, xcds=8):
@@ -166,6 +169,41 @@ def symmetry_loss(cfg):
     return True, float(coef)
 
 
+SMOOTHNESS_PAIRS = ("next", "interpolate")  # algorithm.smoothness_pairs: the modes of bg_partner_rows
+
+
+def smoothness_loss(cfg):
+    """(on, coefficient, pairs) of the action-smoothness loss (additions of this build; the shipped yaml lists none of them): algorithm.smoothness_loss
+    (absent, null or false = off: (False, 0.0, "next"), the other two keys are then not read), algorithm.smoothness_coef (a finite number >= 0, required
+    when the loss is on: nobody has measured a default) and algorithm.smoothness_pairs ("next", the default, or "interpolate").  Pure.  ValueError naming
+    the key for every other value and, naming both keys, with what the loss does not compose with: algorithm.symmetry_loss (both claim rows [B, 2B) of
+    the actor's batch), runner.num_mini_batches above 1, estimator.enabled (no estimate exists for the row after the last step),
+    algorithm.rnn_hidden_size."""
+    alg = cfg.get("algorithm", {}) or {}
+    on = alg.get("smoothness_loss", False)
+    if on is None:
+        on = False
+    if not isinstance(on, bool):
+        raise ValueError(f"algorithm.smoothness_loss must be true or false, got {on!r}")
+    if not on:
+        return False, 0.0, SMOOTHNESS_PAIRS[0]
+    coef = alg.get("smoothness_coef")
+    if isinstance(coef, bool) or not isinstance(coef, (int, float)) or not np.isfinite(coef) or coef < 0:
+        raise ValueError(f"algorithm.smoothness_coef must be a finite number >= 0 when algorithm.smoothness_loss is on (there is no default), got {coef!r}")
+    mode = alg.get("smoothness_pairs", SMOOTHNESS_PAIRS[0])
+    if not isinstance(mode, str) or mode not in SMOOTHNESS_PAIRS:
+        raise ValueError(f"algorithm.smoothness_pairs must be \"next\" or \"interpolate\", got {mode!r}")
+    K = (cfg.get("runner", {}) or {}).get("num_mini_batches", 1) or 1
+    refused = (("algorithm.symmetry_loss: true (both losses claim rows [B, 2B) of the actor's batch)", alg.get("symmetry_loss", False) is True),
+               ("runner.num_mini_batches above 1", not isinstance(K, bool) and isinstance(K, int) and K > 1),
+               ("estimator.enabled: true (there is no estimate for the row after the last step)", estimator_enabled(cfg)),
+               ("algorithm.rnn_hidden_size (a recurrent actor's rows are sequences)", bool(alg.get("rnn_hidden_size", 0))))
+    for what, hit in refused:
+        if hit:
+            raise ValueError(f"algorithm.smoothness_loss: true is not supported with {what}")
+    return True, float(coef), mode
+
+
 def mini_batches(cfg):
     """(on, K) of runner.num_mini_batches (an addition of this build, rsl_rl's name; absent or 1 = off: (False, 1)): every mini-epoch takes K optimiser
     steps on disjoint shuffled K-ths of the batch of B = runner.horizon_length x env.num_envs rows (per rank) instead of one step on all of it.
@@ -206,6 +244,7 @@ class UpdatePlan(NamedTuple):
     ahead: bool         # the rollout runs the first mini-epoch's forward passes
     ranks: bool         # several ranks: the exchanges run
     symmetry: bool = False  # the mirror-symmetry loss: the actor trains on 2B rows (the batch, then its mirror images) through bg_actor_head_sym
+    smoothness: bool = False  # ... the same plan (symmetry = True) with the partner rows of the action-smoothness loss in rows [B, 2B) (bg_partner_rows)
 
 
 class StepRows(NamedTuple):
@@ -231,12 +270,14 @@ TAIL_MAX_ITEMS = _lib.TAIL_MAX_BLOCKS  # blocks of sums of one bg_update_tail la
 
 
 def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_split_bwd, chain_alternate, fused_wgrad, wgrad_split, one_stream,
-                defer_finish, one_launch_tail, fused_opt, fused_head, fused_gae, chain_values, rollout_forward, dp_active, symmetry=False, memory=0):
+                defer_finish, one_launch_tail, fused_opt, fused_head, fused_gae, chain_values, rollout_forward, dp_active, symmetry=False, memory=0, smoothness=False):
     """UpdatePlan from the switches (MLPTrainer.SPLIT ... WGRAD_SPLIT and Runner._one_stream ... _rollout_forward, by the same names in lower case;
     dp.active; symmetry = algorithm.symmetry_loss) and the shapes: critic / actor = (layer widths, padded input width), rows = the batch.  Pure: no
     tensors, no device.  symmetry: the actor's passes differentiate 2 x rows rows (the batch and its mirror images) and the rollout runs no
     forward passes for the update (ahead = False: update() mirrors the batch and runs the first mini-epoch's passes itself); a plan whose output
-    layers are not the fused head kernels is a ValueError (bg_actor_head_sym is the only form of the loss).  memory = H > 0
+    layers are not the fused head kernels is a ValueError (bg_actor_head_sym is the only form of the loss).  smoothness = algorithm.smoothness_loss:
+    a second source of partner rows for the same 2B-row actor path, so the plan is the one of symmetry = True (its `symmetry` field included) with
+    `smoothness` set, and the same ValueError without the fused heads.  memory = H > 0
     (algorithm.rnn_hidden_size): `actor` is the trunk behind the GRU cell, its input the cell's state of H columns, so it runs the per-layer kernels
     beside whatever the critic runs (as on a frame stack), without forward-ahead; the cell's gradients come out of launches that bg_update_tail's sums
     do not cover (its weight gradients' finish, its bias gradients' reduction), so the tail runs as the separate launches (one_tail = False:
@@ -245,6 +286,10 @@ def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_
     if memory and not (fused_head and fused and defer_finish and not split):
         raise ValueError("algorithm.rnn_hidden_size needs the fused output layers of bg_head.hip, the per-layer fp32 kernels and the deferred reductions "
                          "(no parallel.gemm_split / BG_GEMM_SPLIT, BG_DEFER_FINISH=1)")
+    if smoothness and not fused_head:
+        raise ValueError("algorithm.smoothness_loss needs the fused output layers of bg_head.hip (bg_actor_head_sym: an actor whose last hidden layer is "
+                         "128 wide with 12 actions); this plan runs the output layers as library GEMMs")
+    symmetry = bool(symmetry or smoothness)
     if symmetry and not fused_head:
         raise ValueError("algorithm.symmetry_loss needs the fused output layers of bg_head.hip (bg_actor_head_sym: an actor whose last hidden layer is "
                          "128 wide with 12 actions); this plan runs the output layers as library GEMMs")
@@ -272,7 +317,7 @@ def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_
     one_tail = (fused_opt and one_launch_tail and defer and finishing and all(all(n.grouped[:-1]) for n in nets) and sum(fins) + 2 <= 8
                 and sums <= TAIL_MAX_ITEMS and not memory)
     return UpdatePlan(nets[0], nets[1], wgrad, fused_head, fused_gae, chain_values, one_stream and chain_values and defer and bwd_chained, defer, fused_opt,
-                      one_tail, rollout_forward and chain_values and nets[1].chained and not symmetry, dp_active, bool(symmetry))
+                      one_tail, rollout_forward and chain_values and nets[1].chained and not symmetry, dp_active, bool(symmetry), bool(smoothness))
 
 
 class Runner:
@@ -290,6 +335,9 @@ class Runner:
         self.actor_hidden, self.critic_hidden = hidden_widths(self.cfg)  # (before anything is built: a width outside the supported set is a ValueError)
         if self.world_size > 1:  # one process per GPU: each rank simulates and learns on its own device
             self.cfg["basic"]["sim_device"] = self.cfg["basic"]["rl_device"] = f"cuda:{self.dp.device_index}"
+        # algorithm.smoothness_loss: the action-smoothness loss, a second source of partner rows for the symmetry loss's 2B-row actor path (ValueError
+        # before anything is built, also for what it does not compose with); False = off, the one switch every branch below reads
+        self._smooth, self._smooth_coef, self._smooth_pairs = smoothness_loss(self.cfg)
         self._mini_batches = mini_batches(self.cfg)[1]  # (ValueError before anything is built; 1 = off: the one switch every branch below reads)
         # estimator.enabled: a learned state estimator in front of the actor (utils/estimator.py); None = off, the one switch every branch below reads
         self._est = estimator_cfg(self.cfg, self.world_size)
@@ -371,6 +419,16 @@ class Runner:
                              f"critic's input {no} + {npv} pads to {self._pad_critic} (fewer terrain.measured_points_x / _y points, or gemm_split 0)")
         self._critic_in = torch.zeros(T + 1, N, self._pad_critic or (no + npv), device=dev)
         self._actor_in = torch.zeros(T, N, self._pad_actor, device=dev) if self._pad_actor else None
+        if self._smooth:
+            # the actor's input of 2B rows: the batch, then its partner rows (bg_partner_rows in update()), and the one more step of source rows that
+            # the last step's partners come from: the actor's rows of obses[T]
+            if not self._pad_actor or self._pad_actor > 512:
+                raise ValueError(f"algorithm.smoothness_loss needs the actor's padded input of at most 512 columns (bg_partner_rows moves 16-byte pieces of "
+                                 f"rows), env.num_observations = {no}" + (" pads to " + str(self._pad_actor) if self._pad_actor else " is not padded on this path"))
+            self._actor_in = torch.zeros(2 * T, N, self._pad_actor, device=dev)
+            self._actor_last = torch.zeros(N, self._pad_actor, device=dev)
+            self._act_identity = (list(range(A)), [1.0] * A)  # the head's action map: d = mu(x') - mu(x)
+            self._smooth_updates = 0  # the update counter of the draw's key (pairs "interpolate"); restarts at 0 on resume, like _mb_updates
         if self._symmetry:
             # the actor's input of 2B rows: the batch, then its mirror images (bg_mirror_rows in update(); the padded columns stay zero)
             kin = self._pad_actor or self.env.num_obs
@@ -389,7 +447,8 @@ class Runner:
         # the float64 sums of a mini-epoch that every rank needs in full: loss / KL statistics [5] and the log-std gradient [A], contiguous so that ONE
         # collective carries both (exchange (3); the log-std gradient then enters the optimiser launch in float64 and not through the fp32 bucket)
         # (with the symmetry loss a sixth statistic: the sum of squared mean asymmetries; without it the layout, and what the ranks exchange, stays five)
-        S = self._n_stats = 6 if self._symmetry else 5
+        # (the action-smoothness loss uses the same sixth slot: the sum of squared differences of the pairs' means)
+        S = self._n_stats = 6 if self._symmetry or self._smooth else 5
         self._sums = torch.zeros(S + A, dtype=torch.float64, device=dev)
         self._stats, self._grad_logstd = self._sums[:S], self._sums[S:]
         self._stats_acc = torch.zeros(S, dtype=torch.float64, device=dev)
@@ -442,6 +501,8 @@ class Runner:
         # fused output layers + loss (bg_head.hip): both networks end in a 128-wide ELU layer, 12 actions / 1 value (utils/model.py); a model of
         # other widths runs the output layers as library GEMMs + bg_ppo_loss (as an attribute for the test that compares the two forms)
         self._fused_head = A == 12 and self.model.actor[-1].in_features == 128 and self.model.critic[-1].in_features == 128
+        if self._smooth and not self._fused_head:
+            raise ValueError("algorithm.smoothness_loss needs the fused output layers of bg_head.hip: an actor whose last hidden layer is 128 wide with 12 actions")
         if self._symmetry and not self._fused_head:
             raise ValueError("algorithm.symmetry_loss needs the fused output layers of bg_head.hip: an actor whose last hidden layer is 128 wide with 12 actions")
         if self._mem_tr is not None and not (self._fused_head and self._pad_actor == GRUTrainer.KIN):
@@ -463,7 +524,7 @@ class Runner:
         self.timers = {"rollout": 0.0, "update": 0.0}
         if self._mini_batches > 1:
             self._init_mini_batches()
-        if self._symmetry:
+        if self._symmetry or self._smooth:
             self._resolve_plan()  # (a plan the symmetric head cannot serve is a ValueError here, not at the first update)
         if self._est is not None:  # its supervised update (a batch outside the layer kernels' range is a ValueError here, not at the first update)
             self._est_trainer = EstimatorTrainer(self._est, self.model.estimator, self._est_opt, self._est_clock, T, N, no, dev)
@@ -610,7 +671,7 @@ class Runner:
         if self._mem_tr is not None:  # the trunk's input is the cell's state [B][H], not the padded observation rows (those are the cell's)
             kin_a = self._memory
         plan = plan_update((widths(ct), self._critic_in.shape[-1]), (widths(at), kin_a), self._old_logp.numel(), dp_active=self.dp.active, symmetry=self._symmetry,
-                           memory=self._memory if self._mem_tr is not None else 0, **sw)
+                           memory=self._memory if self._mem_tr is not None else 0, smoothness=self._smooth, **sw)
         ct.plan, at.plan = plan.critic, plan.actor
         c_out = ct.layers[-1]
         ct.value_head = (c_out.weight.reshape(-1), c_out.bias, self._values_all) if plan.chain_values else None
@@ -758,6 +819,13 @@ class Runner:
                 gaussian_logp(self._old_mu[r0:], logstd, buf["actions"][self._logp_done :].reshape(-1, self.env.num_actions), out=self._old_logp[r0:])
                 self._logp_done = T
 
+    def _partner_rows(self, T, epoch):
+        """algorithm.smoothness_loss: rows [B, 2B) of the actor's input from rows [0, B) and the rows of the step after the last (bg_partner_rows), on the
+        current stream.  The draw of pairs "interpolate" is keyed by basic.seed with the rank folded in as in permutation(), this rank's update number and
+        the mini-epoch."""
+        buf, seed = self.buffer, int(self.cfg["basic"]["seed"]) + 1000003 * (self.rank + 1)
+        partner_rows(self._actor_in[:T], self._actor_last, buf["dones"], buf["time_outs"], self._actor_in[T:], self._smooth_pairs, seed, self._smooth_updates, epoch)
+
     def _normalize_inputs(self, a, b, b_actor):
         """algorithm.empirical_normalization: the padded network inputs of steps [a, b) (critic: observation and privileged block) and [a, b_actor)
         (actor) from the raw rows of the experience buffer through bg_obs_normalize, on the current stream, in place of the copies; with the
@@ -783,6 +851,8 @@ class Runner:
             for epoch in range(self.cfg["runner"]["mini_epochs"]):
                 # this mini-epoch's hidden activations and values may be the rollout's: same kernels, same weights
                 have_fwd = u.ahead and epoch == 0
+                if u.plan.smoothness and self._smooth_pairs == "interpolate":  # a fresh draw per row in front of every mini-epoch's forward pass
+                    self._partner_rows(u.T, epoch)
                 if K == 1 and not u.plan.one_stream:
                     self._epoch_on_two_streams(u, have_fwd)  # the same pieces, the critic's on the side stream beside the actor's
                     self._epoch_gradients_and_step(u, w)
@@ -811,6 +881,8 @@ class Runner:
                 self._est_trainer.update(u.buf["obses"][: u.T], u.buf["privileged_obses"][: u.T])
         if K > 1:
             self._mb_updates += 1
+        if u.plan.smoothness:
+            self._smooth_updates += 1
         return self._stats_acc
 
     def _update_begin(self, plan):
@@ -838,7 +910,17 @@ class Runner:
             if self._est is not None and self._actor_in is not None:
                 # the estimate is an observation: the stored rows [obses | estimates[:E] | 0], so old mu and the first ratio come from what the rollout acted on
                 self._actor_in[:T, :, no : no + self._est_cols].copy_(buf["estimates"][..., : self._est_cols])
-            if plan.symmetry and self.obs_norm is not None:  # rows [B, 2B): normalise(M_o x), what the policy computes on the mirrored raw observation
+            if plan.smoothness:
+                # the actor's rows of obses[T], as the network sees them (padded, normalised), then rows [B, 2B): every row's successor -- pairs
+                # "next": copies, once per update; "interpolate": a fresh draw in front of every mini-epoch's forward pass (update(); the old-mu
+                # pass below reads rows [0, B) only)
+                if self.obs_norm is not None:
+                    self.obs_norm.normalize_into(buf["obses"][T], self._actor_last, dst_cols=self._actor_last.shape[-1])
+                else:
+                    self._actor_last[:, :no].copy_(buf["obses"][T])
+                if self._smooth_pairs == "next":
+                    self._partner_rows(T, 0)
+            elif plan.symmetry and self.obs_norm is not None:  # rows [B, 2B): normalise(M_o x), what the policy computes on the mirrored raw observation
                 mirror_rows(buf["obses"][:T].reshape(B, -1), self._mirror_raw, *self._obs_mirror_raw)
                 self.obs_norm.normalize_into(self._mirror_raw, self._actor_in[T:].reshape(B, -1), dst_cols=self._actor_in.shape[-1])
             elif plan.symmetry:  # rows [B, 2B): the mirror images M_o x of the batch
@@ -948,7 +1030,9 @@ class Runner:
         args = (ha, a_out.weight, a_out.bias, u.logstd_flat, v.actions, v.old_mu, u.old_logstd, v.old_logp, v.adv, self._adv_sums, 0.2, alg["bound_coef"],
                 alg["entropy_coef"])
         outs = (at.hidden_grad, a_out.weight.grad, a_out.bias.grad, at.layers[-2].bias.grad, self._grad_logstd, self._stats, self._head_scratch_a)
-        if v.plan.symmetry:
+        if v.plan.smoothness:  # the same head on the identity action map: d = mu(x') - mu(x)
+            actor_head_sym_loss_backward(*args, self._smooth_coef, self._act_identity, *outs, finish=finish)
+        elif v.plan.symmetry:
             actor_head_sym_loss_backward(*args, self._symmetric_coef, self._act_mirror, *outs, finish=finish)
         else:
             actor_head_loss_backward(*args, *outs, finish=finish)
@@ -1153,7 +1237,9 @@ class Runner:
         self.learning_rate = s[2 * S]
         out = {"value_loss": s[0] / (B * E), "actor_loss": s[1] / (B * E), "bound_loss": s[2] / (B * A * E), "entropy": s[3] / (B * E),
                "kl_mean": s[S + 4] / (B // self._mini_batches), "lr": s[2 * S]}  # (the last optimiser step's KL sum: over its b = B / K rows of every rank)
-        if S > 5:  # mean squared asymmetry of the actor's mean, before symmetric_coef (like bound_loss before bound_coef)
+        if S > 5 and self._smooth:  # mean squared difference of the actor's mean over the pairs (x, x'), before smoothness_coef
+            out["smoothness_loss"] = s[5] / (B * A * E)
+        elif S > 5:  # mean squared asymmetry of the actor's mean, before symmetric_coef (like bound_loss before bound_coef)
             out["symmetry_loss"] = s[5] / (B * A * E)
         return out
 

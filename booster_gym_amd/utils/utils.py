@@ -199,6 +199,26 @@ def mirror_rows(x, y, src, sign):
     return y
 
 
+def partner_rows(x, x_last, dones, time_outs, y, mode="next", seed=0, update=0, epoch=0):
+    """The partner rows of the action-smoothness loss (bg_partner_rows): y[t, e] = x[t, e] + u (x+ - x[t, e]) on x / y [T, N, cols] and x_last [N, cols],
+    x+ = x[t + 1, e] (x_last[e] behind the last step); where dones[t, e] or time_outs[t, e] (bool or uint8 [T, N]) is set, y[t, e] = x[t, e].  mode
+    "next": u = 1, a bit-exact copy; "interpolate": u in [0, 1), one Philox draw per row on the key (seed) and the counter (t N + e, update, 30, epoch)."""
+    _need_cuda(x, x_last, dones, time_outs, y)
+    if mode not in ("next", "interpolate"):
+        raise ValueError(f"partner_rows: mode must be \"next\" or \"interpolate\", got {mode!r}")
+    T, N, cols = x.shape
+    if y.shape != x.shape or x_last.shape != (N, cols) or dones.shape != (T, N) or time_outs.shape != (T, N):
+        raise ValueError("partner_rows: x and y [T, N, cols], x_last [N, cols], dones and time_outs [T, N]")
+    if not all(t.is_contiguous() for t in (x, x_last, dones, time_outs, y)) or x.dtype != torch.float32 or x_last.dtype != torch.float32 or y.dtype != torch.float32:
+        raise ValueError("partner_rows: contiguous tensors, float32 rows")
+    if any(t.dtype not in (torch.bool, torch.uint8) for t in (dones, time_outs)):
+        raise ValueError("partner_rows: dones and time_outs of one byte per flag (bool or uint8)")
+    _lib.check(_lib.load().bg_partner_rows(T, N, cols, _lib.ptr(x), _lib.ptr(x_last), _lib.ptr(dones), _lib.ptr(time_outs),
+                                           _lib.PARTNER_INTERPOLATE if mode == "interpolate" else _lib.PARTNER_NEXT, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                           int(update) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, _lib.ptr(y), _lib.current_stream_ptr()), "bg_partner_rows")
+    return y
+
+
 def critic_head_backward(h, weight, values, returns, g_hidden, grad_weight, grad_bias, grad_bias_hidden, stats, scratch, finish=None):
     """Backward of mean((values - returns)^2) (runner.py:148) through the 128 -> 1 output layer; stats[0] += sum of squared errors.
     finish: as for actor_head_loss_backward."""

@@ -653,6 +653,20 @@ int bg_actor_head_sym(int32_t B, const float* h, const float* W, const float* bi
 /* y [rows][cols] = the rows of x [rows][cols] mirrored: y[r][c] = sign[c] x[r][src[c]] (src[c] = -1: 0), cols <= 512, src / sign host arrays of cols,
  * sign +-1; x and y must not overlap.  Exact. */
 int bg_mirror_rows(int32_t rows, int32_t cols, const int32_t* src, const float* sign, const float* x, float* y, void* stream);
+/* Partner rows of the action-smoothness loss (algorithm.smoothness_loss): the second source of rows [B, 2B) of bg_actor_head_sym's batch, which then
+ * runs with the identity action map (act_src = 0..11, act_sign = +1: d_r = mu(x'_r) - mu(x_r)).  x [T][N][cols] are the actor's input rows of T steps
+ * of N envs, x_last [N][cols] those of the step after the last, dones / time_outs [T][N] bytes (0 / not 0).  For row r = t N + e:
+ *   y[r] = x[r] + u_r (x+[r] - x[r]),  x+[r] = x[r + N] (t < T - 1) or x_last[e] (t = T - 1);
+ *   dones[r] or time_outs[r] set (a reset or a command resample: where GAE cuts): y[r] = x[r], a bit-exact copy;
+ *   mode BG_PARTNER_NEXT: u_r = 1, y[r] a bit-exact copy of x+[r]; seed / update / epoch are not read;
+ *   mode BG_PARTNER_INTERPOLATE: u_r = (o >> 8) 2^-24 in [0, 1), o = word 0 of Philox4x32-10 on the key (seed) and the counter (r, update, 30, epoch):
+ *   one draw per row, y[r][c] = fma(u_r, x+[r][c] - x[r][c], x[r][c]) in fp32.
+ * cols a multiple of 4 and <= 512; x, x_last and y 16-byte aligned; y overlaps neither x nor x_last; T N < 2^31 (-1 with a message otherwise, before any
+ * launch).  Deterministic, no atomics; every element of y's T N rows is written, nothing past them. */
+#define BG_PARTNER_NEXT 0
+#define BG_PARTNER_INTERPOLATE 1
+int bg_partner_rows(int32_t T, int32_t N, int32_t cols, const float* x, const float* x_last, const uint8_t* dones, const uint8_t* time_outs, int32_t mode,
+                    uint64_t seed, uint32_t update, uint32_t epoch, float* y, void* stream);
 /* Mirror-symmetry loss on the distillation's student (T1.yaml distillation.symmetric_coef): bg_distill_head on a batch of 2B rows laid out as for
  * bg_actor_head_sym (h / g_hidden / mu_out [2B] rows, rows [B, 2B) the mirror images of rows [0, B); target [B][12]).  L = 1 / (12 B) sum_r |mu_r -
  * target_r|^2 over the original rows + sym_coef / (12 B) sum_r |d_r|^2, d_r = mu(M_o x_r) - M_a mu(x_r), differentiated through both means: with s = 2
