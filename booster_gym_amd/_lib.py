@@ -94,6 +94,12 @@ class GatherStream(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("width", C.c_int32), ("pad", C.c_int32)]
 
 
+class SequenceStream(C.Structure):
+    """bg_sequence_stream: one row-major stream of bg_gather_sequences, elements of 4 bytes or 1 byte, per (step, env) or per env
+    (include/booster_gym_amd.h)."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("width", C.c_int32), ("elem_size", C.c_int32), ("per_env", C.c_int32), ("pad", C.c_int32)]
+
+
 class Rand(C.Structure):
     _fields_ = [("mode", C.c_int32), ("a", C.c_float), ("b", C.c_float)]
 
@@ -147,6 +153,7 @@ PRIV_EXTRA_GROUPS = (("feet", PRIV_EXTRA_FEET, 6), ("ground", PRIV_EXTRA_GROUND,
 HEAD_SCRATCH_FLOATS = 768 * 1720  # BG_HEAD_SCRATCH_FLOATS
 OBS_MOMENTS_MAX_GROUPS = 1024  # BG_OBS_MOMENTS_MAX_GROUPS
 GATHER_MAX_STREAMS = 8  # BG_GATHER_MAX_STREAMS
+SEQUENCE_MAX_STREAMS = 12  # BG_SEQUENCE_MAX_STREAMS
 ACTOR_PACKED_FLOATS = 65616  # BG_ACTOR_PACKED_FLOATS
 PARTNER_NEXT, PARTNER_INTERPOLATE = 0, 1  # BG_PARTNER_NEXT / BG_PARTNER_INTERPOLATE: the modes of bg_partner_rows (algorithm.smoothness_pairs)
 TAIL_MAX_BLOCKS = 8192  # BG_TAIL_MAX_BLOCKS: blocks of sums of one bg_update_tail launch = float64 slots of its norm_scratch
@@ -175,7 +182,7 @@ SYMBOLS = [
     "bg_actor_head_sym", "bg_actor_head_sym_partial", "bg_mirror_rows", "bg_partner_rows",
     "bg_distill_head", "bg_distill_head_partial", "bg_distill_head_sym", "bg_distill_head_sym_partial",
     "bg_obs_moments", "bg_obs_normalize",
-    "bg_perm_fill", "bg_gather_rows",
+    "bg_perm_fill", "bg_gather_rows", "bg_gather_sequences",
     "bg_actor_sample_gru", "bg_distill_act_gru", "bg_gru_sequence_forward", "bg_gru_sequence_backward",
     "bg_gru_bias_partial",
     "bg_last_error", "bg_version",
@@ -295,6 +302,7 @@ def load():
         "bg_obs_normalize": (i32, [i32, i32, vp, i32, vp, i32, i32, vp, vp, i32, vp]),
         "bg_perm_fill": (i32, [i32, u64, C.c_uint32, C.c_uint32, vp, vp]),
         "bg_gather_rows": (i32, [i32, i32, vp, C.POINTER(GatherStream), i32, vp]),
+        "bg_gather_sequences": (i32, [i32, i32, i32, vp, C.POINTER(SequenceStream), i32, vp]),
         "bg_last_error": (C.c_char_p, []),
         "bg_version": (C.c_char_p, []),
     }

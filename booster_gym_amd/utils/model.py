@@ -677,6 +677,7 @@ class GRUTrainer:
         self.dh_ext, self.dgi, self.dgh = new(B, H), new(B, 3 * H), new(B, 3 * H)
         self.h0 = new(self.N, H)                                                    # the state entering the iteration (detached)
         self.resets = torch.zeros(self.T, self.N, dtype=torch.uint8, device=dev)    # non-zero: the state entering step t of env n is zero
+        self._resets = self.resets                                                  # ... as the last forward() read them (backward() reads the same)
         self._zero_bias = new(H)
         self._cs = new((B + 127) // 128 * (6 if self.bias_partial else 3) * H)  # (bias_partial: one record [6H] per 128 rows)
         self.x = None
@@ -700,11 +701,16 @@ class GRUTrainer:
             self.resets[1:].copy_(dones[: self.T - 1])
         last_dones.copy_(dones[self.T - 1])
 
-    def forward(self, x):
+    def forward(self, x, h0=None, resets=None):
+        """h0 [N][H] / resets [T][N] uint8: the state the recurrence starts from and the reset flags it (and the backward pass behind it) reads, where
+        they are not this trainer's own (an env-wise mini-batch: rows of the runner's gathered buffers)."""
         lib, st, p, c, H = _lib.load(), _lib.current_stream_ptr(), _lib.ptr, self.cell, self.H
         self.x = x
+        h0, self._resets = self.h0 if h0 is None else h0, self.resets if resets is None else resets
+        if h0.shape != self.h0.shape or self._resets.shape != self.resets.shape or self._resets.dtype != torch.uint8 or not (h0.is_contiguous() and self._resets.is_contiguous()):
+            raise ValueError(f"GRUTrainer.forward: h0 {tuple(h0.shape)} / resets {tuple(self._resets.shape)} are not contiguous [{self.N}][{H}] / uint8 [{self.T}][{self.N}]")
         _lib.check(lib.bg_mlp_layer_forward(self.B, self.KIN, 3 * H, p(x), p(self.copies.get("w0pad", 0)), p(c.bias_ih), p(self.gi), 0, st), "bg_mlp_layer_forward")
-        _lib.check(lib.bg_gru_sequence_forward(self.T, self.N, H, p(self.gi), p(self.h0), p(self.resets), p(c.weight_hh), p(c.bias_hh), p(self.h_prev), p(self.h),
+        _lib.check(lib.bg_gru_sequence_forward(self.T, self.N, H, p(self.gi), p(h0), p(self._resets), p(c.weight_hh), p(c.bias_hh), p(self.h_prev), p(self.h),
                                                p(self.gates), st), "bg_gru_sequence_forward")
         return self.h
 
@@ -715,7 +721,7 @@ class GRUTrainer:
         g1, l0 = tr.gin[1], tr.layers[0]  # dL/dz of the trunk's first layer [B][out], behind backward_hidden
         _lib.check(lib.bg_mlp_layer_forward(self.B, l0.weight.shape[0], H, p(g1), p(tr.copies.get("wt", 0)), p(self._zero_bias), p(self.dh_ext), 0, st),
                    "bg_mlp_layer_forward")
-        _lib.check(lib.bg_gru_sequence_backward(self.T, self.N, H, p(self.dh_ext), p(self.gates), p(self.h_prev), p(self.resets), p(c.weight_hh), p(self.dgi),
+        _lib.check(lib.bg_gru_sequence_backward(self.T, self.N, H, p(self.dh_ext), p(self.gates), p(self.h_prev), p(self._resets), p(c.weight_hh), p(self.dgi),
                                                 p(self.dgh), None, st), "bg_gru_sequence_backward")
         self._pending = True
         if self.bias_partial:

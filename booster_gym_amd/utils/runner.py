@@ -34,6 +34,9 @@ Same surface: `Runner(test=False)` parses the reference's 8 CLI flags (runner.py
             on a state [N][H] carried over steps and iterations and zeroed where an env reset; the update runs the cell over the iteration's T steps
             from the state stored at the rollout's start (model.GRUTrainer: back-propagation through time, truncated there) around the trunk's
             per-layer kernels, its bias gradients as one launch (bg_gru_bias_partial) among the deferred reductions, the tail as separate launches.
+            runner.num_env_mini_batches = K (off by default): K optimiser steps per mini-epoch, step k on the whole sequences of N / K envs of a fresh
+            env permutation, laid out by ONE launch (bg_gather_sequences) with their rows of h0 and of the reset flags; a StepRows carries the cell
+            trainer of its rows (CellRows).
   smoothness algorithm.smoothness_loss (off by default): the action-smoothness loss, a second source of partner rows for the symmetry loss's 2B-row actor
             path: rows [B, 2B) of the actor's input are every row's successor (bg_partner_rows: cut where GAE cuts, optionally interpolated with a
             fresh draw per row and mini-epoch), the output layer runs as bg_actor_head_sym on the identity action map.  No forward-ahead then.
@@ -229,6 +232,37 @@ def mini_batches(cfg):
     return True, K
 
 
+def env_mini_batches(cfg):
+    """(on, K) of runner.num_env_mini_batches (an addition of this build; absent, null or 1 = off: (False, 1); the shipped yaml does not list it): with
+    a recurrent actor (algorithm.rnn_hidden_size) every mini-epoch takes K optimiser steps, step k on the whole T-step sequences of N / K envs of a
+    fresh env permutation (rsl_rl's recurrent_mini_batch_generator; runner.num_mini_batches shuffles single rows, which a recurrence cannot run on).
+    Pure.  ValueError naming the key unless K is an integer >= 1 that divides env.num_envs = N with T N / K a multiple of 128 (the critic's chained
+    kernels run on the step's rows, as under runner.num_mini_batches); and, naming both keys, without algorithm.rnn_hidden_size (a feed-forward actor
+    has runner.num_mini_batches) and together with runner.num_mini_batches above 1."""
+    run = cfg.get("runner", {}) or {}
+    K = run.get("num_env_mini_batches", 1)
+    if K is None:
+        K = 1
+    if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+        raise ValueError(f"runner.num_env_mini_batches must be an integer >= 1, got {K!r}")
+    if K == 1:
+        return False, 1
+    if not (cfg.get("algorithm", {}) or {}).get("rnn_hidden_size", 0):
+        raise ValueError(f"runner.num_env_mini_batches = {K} needs a recurrent actor (algorithm.rnn_hidden_size: 128 or 256): its mini-batches are whole "
+                         "sequences of envs; a feed-forward actor has the shuffle of single rows, runner.num_mini_batches")
+    M = run.get("num_mini_batches", 1) or 1
+    if not isinstance(M, bool) and isinstance(M, int) and M > 1:
+        raise ValueError(f"runner.num_env_mini_batches = {K} together with runner.num_mini_batches = {M} is not supported: a mini-epoch is cut one way, "
+                         "by envs (a recurrent actor) or by rows")
+    T, N = int(run["horizon_length"]), int(cfg["env"]["num_envs"])
+    if N % K:
+        raise ValueError(f"runner.num_env_mini_batches = {K} does not divide env.num_envs = {N}")
+    if (T * N // K) % 128:
+        raise ValueError(f"runner.num_env_mini_batches = {K} gives mini-batches of runner.horizon_length x env.num_envs / {K} = {T} x {N // K} = {T * N // K} "
+                         "rows, which is not a multiple of 128 (the critic's kernels work on whole 128-row slabs)")
+    return True, K
+
+
 class UpdatePlan(NamedTuple):
     """The kernels of one Runner.update() and of the rollout's forward-ahead (plan_update): resolved once per call, read by every branch."""
     critic: NetPlan
@@ -247,9 +281,18 @@ class UpdatePlan(NamedTuple):
     smoothness: bool = False  # ... the same plan (symmetry = True) with the partner rows of the action-smoothness loss in rows [B, 2B) (bg_partner_rows)
 
 
+class CellRows(NamedTuple):
+    """The recurrent side of a StepRows (algorithm.rnn_hidden_size): the cell's trainer for the step's rows [T][envs], the state [envs][H] its
+    recurrence starts from and the reset flags [T][envs] it reads."""
+    trainer: GRUTrainer
+    h0: torch.Tensor
+    resets: torch.Tensor
+
+
 class StepRows(NamedTuple):
-    """What one optimiser step of Runner.update() reads and writes, built once per update(): the whole batch (Runner._update_begin), or one of the K
-    mini-batches of runner.num_mini_batches (Runner._mini_batch_begin: rows [k b, (k + 1) b) of the gathered buffers)."""
+    """What one optimiser step of Runner.update() reads and writes, built once per update(): the whole batch (Runner._update_begin), one of the K
+    mini-batches of runner.num_mini_batches (Runner._mini_batch_begin: rows [k b, (k + 1) b) of the gathered buffers), or one of the K env-wise
+    mini-batches of runner.num_env_mini_batches (Runner._env_mini_batch_begin: the same rows of the buffers bg_gather_sequences fills)."""
     ct: MLPTrainer                # the critic's and the actor's trainer
     at: MLPTrainer
     plan: UpdatePlan              # ... and the plan they run under
@@ -264,6 +307,7 @@ class StepRows(NamedTuple):
     adv: torch.Tensor
     ret: torch.Tensor
     values: torch.Tensor          # where the value head of the fused kernels writes the values of x_c's rows
+    mem: Optional[CellRows] = None  # a recurrent actor: the cell around the trunk `at` on these rows (x_a: the cell's padded rows)
 
 
 TAIL_MAX_ITEMS = _lib.TAIL_MAX_BLOCKS  # blocks of sums of one bg_update_tail launch (bg_tail.hip)
@@ -339,6 +383,9 @@ class Runner:
         # before anything is built, also for what it does not compose with); False = off, the one switch every branch below reads
         self._smooth, self._smooth_coef, self._smooth_pairs = smoothness_loss(self.cfg)
         self._mini_batches = mini_batches(self.cfg)[1]  # (ValueError before anything is built; 1 = off: the one switch every branch below reads)
+        # runner.num_env_mini_batches: the K steps of a mini-epoch on whole sequences of N / K envs, a recurrent actor's mini-batches (likewise; the key
+        # belongs to training: play and evaluation do not read it)
+        self._env_mini_batches = 1 if test else env_mini_batches(self.cfg)[1]
         # estimator.enabled: a learned state estimator in front of the actor (utils/estimator.py); None = off, the one switch every branch below reads
         self._est = estimator_cfg(self.cfg, self.world_size)
         # algorithm.actor_memory: a recurrent distilled student re-entering for play / evaluation / export; 0 = none, the one switch the branches below read
@@ -524,6 +571,8 @@ class Runner:
         self.timers = {"rollout": 0.0, "update": 0.0}
         if self._mini_batches > 1:
             self._init_mini_batches()
+        if self._env_mini_batches > 1:
+            self._init_env_mini_batches()
         if self._symmetry or self._smooth:
             self._resolve_plan()  # (a plan the symmetric head cannot serve is a ValueError here, not at the first update)
         if self._est is not None:  # its supervised update (a batch outside the layer kernels' range is a ValueError here, not at the first update)
@@ -675,10 +724,11 @@ class Runner:
         ct.plan, at.plan = plan.critic, plan.actor
         c_out = ct.layers[-1]
         ct.value_head = (c_out.weight.reshape(-1), c_out.bias, self._values_all) if plan.chain_values else None
-        if self._mini_batches > 1:
-            # runner.num_mini_batches: the plan above serves the whole-batch passes (forward-ahead, old mu, values + GAE); the K optimiser steps of a
-            # mini-epoch run a plan of their own for b = B / K rows on the second pair of trainers
-            mp = self._mb_plan = plan_update((widths(ct), self._critic_in.shape[-1]), (widths(at), kin_a), self._mb_rows, dp_active=self.dp.active, **sw)
+        if self._mini_batches > 1 or self._env_mini_batches > 1:
+            # runner.num_mini_batches / num_env_mini_batches: the plan above serves the whole-batch passes (forward-ahead, old mu, values + GAE); the K
+            # optimiser steps of a mini-epoch run a plan of their own for b = B / K rows on the second pair of trainers
+            mp = self._mb_plan = plan_update((widths(ct), self._critic_in.shape[-1]), (widths(at), kin_a), self._mb_rows, dp_active=self.dp.active,
+                                             memory=self._memory if self._env_mini_batches > 1 else 0, **sw)
             self._critic_mb.plan, self._actor_mb.plan = mp.critic, mp.actor
             self._critic_mb.value_head = (c_out.weight.reshape(-1), c_out.bias, self._mb_values) if mp.chain_values else None
         return plan
@@ -703,7 +753,14 @@ class Runner:
     def permutation(self, update, epoch, out=None):
         """The permutation of [0, B) that mini-epoch `epoch` of this rank's update number `update` shuffles its rows with (bg_perm_fill), as an int32
         device tensor: keyed by (basic.seed with the rank folded in as in the rollout's action noise, update, epoch)."""
-        out = torch.empty_like(self._perm) if out is None else out
+        return self._perm_fill(torch.empty_like(self._perm) if out is None else out, update, epoch)
+
+    def env_permutation(self, update, epoch, out=None):
+        """The permutation of the envs [0, N) that mini-epoch `epoch` of this rank's update number `update` cuts into runner.num_env_mini_batches
+        mini-batches of whole sequences, as an int32 device tensor: the key rule of permutation(), over N in place of B."""
+        return self._perm_fill(torch.empty_like(self._env_perm) if out is None else out, update, epoch)
+
+    def _perm_fill(self, out, update, epoch):
         seed = (int(self.cfg["basic"]["seed"]) + 1000003 * (self.rank + 1)) & 0xFFFFFFFFFFFFFFFF
         _lib.check(_lib.load().bg_perm_fill(out.numel(), seed, int(update) & 0xFFFFFFFF, int(epoch), _lib.ptr(out), _lib.current_stream_ptr()), "bg_perm_fill")
         return out
@@ -730,6 +787,52 @@ class Runner:
         """A fresh permutation of the batch's rows and ONE gather of every per-row stream the K steps read, mini-batch after mini-batch."""
         self.permutation(self._mb_updates, epoch, out=self._perm)
         _lib.check(_lib.load().bg_gather_rows(u.B, u.B, _lib.ptr(self._perm), u.gather, len(u.gather), _lib.current_stream_ptr()), "bg_gather_rows")
+
+    # ------------------------------------------------------------------ runner.num_env_mini_batches > 1
+    def _init_env_mini_batches(self):
+        """What K = runner.num_env_mini_batches > 1 adds to the runner, after _init_mini_batches: the second pair of trainers sized for b = T n rows,
+        n = N / K, a second cell trainer around that pair's actor for [T][n] rows, the permutation of the envs, and the gathered copies of everything
+        the steps read: the seven per-row streams, the recurrence's starting state [K][n][H] and its reset flags [K][T][n]."""
+        K, A, H, dev = self._env_mini_batches, self.env.num_actions, self._memory, self.device
+        T, N = self.cfg["runner"]["horizon_length"], self.env.num_envs
+        B, n = T * N, N // K
+        self._mb_rows = T * n
+        self._actor_mb, self._critic_mb = MLPTrainer(self.model.actor, clock=self._clock), MLPTrainer(self.model.critic, clock=self._clock)
+        self._mem_mb = GRUTrainer(self.model.memory, self._actor_mb, T, n, clock=self._clock, bias_partial=True)
+        self._mb_wgrad = [GroupedWeightGrad() for _ in range(K)]  # (descriptors per input buffer: one per mini-batch position)
+        self._env_perm = torch.zeros(N, dtype=torch.int32, device=dev)
+        f = lambda *shape: torch.zeros(*shape, device=dev)
+        self._mb = types.SimpleNamespace(critic_in=f(B, self._critic_in.shape[-1]), actor_in=f(B, GRUTrainer.KIN), actions=f(B, A), old_mu=f(B, A), old_logp=f(B),
+                                         adv=f(B), ret=f(B), h0=f(N, H), resets=torch.zeros(B, dtype=torch.uint8, device=dev))
+        self._mb_values = f(self._mb_rows)
+        self._mb_updates = 0  # the update counter of the permutation's key
+
+    def _env_mini_batch_begin(self, u):
+        """Once per update(), as _mini_batch_begin: step k runs on rows [k b, (k + 1) b) of the gathered buffers -- the T steps of the n envs
+        sigma[k n : (k + 1) n], step-major -- with the cell trainer of b rows from the gathered state h0[k] and reset flags resets[k]; the descriptors
+        of the gather (nine streams: seven per row, the state per env, the one-byte reset flags)."""
+        m, b, w, K, T = self._mb, self._mb_rows, u.whole, self._env_mini_batches, u.T
+        n = u.N // K
+        u.steps = [StepRows(self._critic_mb, self._actor_mb, self._mb_plan, b, self._mb_wgrad[k], m.critic_in[r], None, m.actor_in[r], m.actions[r], m.old_mu[r],
+                            m.old_logp[r], m.adv[r], m.ret[r], self._mb_values, CellRows(self._mem_mb, m.h0[k * n : (k + 1) * n], m.resets[r].view(T, n)))
+                   for k, r in enumerate(slice(k * b, (k + 1) * b) for k in range(K))]
+        self._plan_chain_split(u.steps[0].x_c, u.steps[0].x_a, self._mb_plan, self._critic_mb, self._actor_mb)
+        self._critic_tr.chain_workgroups = self._actor_tr.chain_workgroups = 0  # the whole-batch passes run one network at a time
+        B, whole = u.B, w.mem
+        streams = [(w.x_c[:B], m.critic_in, 0), (w.x_a[:B], m.actor_in, 0), (w.actions, m.actions, 0), (w.old_mu, m.old_mu, 0), (w.old_logp, m.old_logp, 0),
+                   (w.adv, m.adv, 0), (w.ret, m.ret, 0), (whole.h0, m.h0, 1), (whole.resets.view(B), m.resets, 0)]
+        for src, dst, _ in streams:
+            if not (src.is_contiguous() and src.dtype == dst.dtype and src.dtype in (torch.float32, torch.uint8) and src.shape == dst.shape):
+                raise RuntimeError(f"env mini-batch gather: a stream of shape {tuple(src.shape)} ({src.dtype}) does not match its buffer {tuple(dst.shape)} ({dst.dtype})")
+        u.gather = (_lib.SequenceStream * len(streams))(*[_lib.SequenceStream(src.data_ptr(), dst.data_ptr(), src.numel() // src.shape[0], src.element_size(), per_env, 0)
+                                                          for src, dst, per_env in streams])
+        u.gather_keep = streams
+
+    def _shuffle_envs(self, u, epoch):
+        """A fresh permutation of the envs and ONE gather of everything the K steps read, mini-batch after mini-batch."""
+        self.env_permutation(self._mb_updates, epoch, out=self._env_perm)
+        _lib.check(_lib.load().bg_gather_sequences(u.T, u.N, self._env_mini_batches, _lib.ptr(self._env_perm), u.gather, len(u.gather), _lib.current_stream_ptr()),
+                   "bg_gather_sequences")
 
     def rollout(self):
         """runner.py:106-121: horizon_length env steps with sampled actions, outputs written in place.
@@ -844,9 +947,14 @@ class Runner:
         method starts from them and from the weight copies the last optimiser launch wrote -- parameters and rollout buffers must not have been changed
         in between except through `invalidate()` (which `_load` and the initial broadcast call)."""
         u = self._update_begin(self._resolve_plan())
-        K, w = self._mini_batches, u.whole
-        if K > 1:
+        # K steps per mini-epoch: on shuffled rows (runner.num_mini_batches) or on the sequences of shuffled envs (runner.num_env_mini_batches), never both
+        K, w = max(self._mini_batches, self._env_mini_batches), u.whole
+        if self._mini_batches > 1:
             self._mini_batch_begin(u)
+            shuffle = self._shuffle
+        elif K > 1:
+            self._env_mini_batch_begin(u)
+            shuffle = self._shuffle_envs
         with torch.no_grad():
             for epoch in range(self.cfg["runner"]["mini_epochs"]):
                 # this mini-epoch's hidden activations and values may be the rollout's: same kernels, same weights
@@ -859,7 +967,8 @@ class Runner:
                     continue
                 # Per mini-epoch: the whole-batch values, returns and advantages from the current critic; then the optimiser steps, each on its rows (K = 1:
                 # one step on the whole batch; runner.num_mini_batches = K: on disjoint shuffled K-ths of it -- returns and advantages stay fixed for the
-                # K steps, the KL rule moves the learning rate after every one of them).  Every launch on the main stream.
+                # K steps, the KL rule moves the learning rate after every one of them; runner.num_env_mini_batches = K: likewise on the whole sequences
+                # of disjoint shuffled K-ths of the envs).  Every launch on the main stream.
                 hc = ha = None
                 if have_fwd:
                     u.main.wait_stream(u.side)  # the rollout ran the forward passes on the side stream
@@ -868,7 +977,7 @@ class Runner:
                     hc, ha = self._forward_hidden(w)  # the one step's rows are the values pass's: both networks' forward passes as its grouped launch
                 hc, v_all = self._whole_batch_values(u, hc)
                 if K > 1:
-                    self._shuffle(u, epoch)
+                    shuffle(u, epoch)
                 for v in u.steps:
                     self._step(u, v, (hc, ha, v_all[: u.B]) if K == 1 else None)
                     self._epoch_gradients_and_step(u, v)
@@ -941,8 +1050,9 @@ class Runner:
             ha0 = None
             if ahead:
                 old_mu = self._old_mu
-            elif self._mem_tr is not None:  # ... the cell over the T steps from h0, then the trunk; mini-epoch 0 reuses this pass (no parameter changes in between)
-                ha0 = self._actor_hidden(self._actor_tr, obs_flat)
+            elif self._mem_tr is not None:  # ... the cell over the T steps from h0, then the trunk; mini-epoch 0 reuses this pass (no parameter changes in
+                # between; not under runner.num_env_mini_batches: a step's rows are not these)
+                ha0 = self._actor_hidden(self._actor_tr, obs_flat, self._whole_cell())
                 old_mu = actor_head_forward(ha0[:B], a_out.weight, a_out.bias, self._old_mu)
             elif plan.fused_head:
                 old_mu = actor_head_forward(self._actor_tr.forward_hidden(obs_flat)[:B], a_out.weight, a_out.bias, self._old_mu)
@@ -956,29 +1066,36 @@ class Runner:
         self._grad_logstd.zero_()
         self._plan_chain_split(critic_all, obs_flat, plan)
         whole = StepRows(self._critic_tr, self._actor_tr, plan, B, self._wgrad_group, critic_all, B, obs_flat, act_flat, old_mu, self._old_logp, self._adv.view(B),
-                         self._ret.view(B), self._values_all)
+                         self._ret.view(B), self._values_all, self._whole_cell())
         # whole: the batch as the rows of one optimiser step; steps: what the steps of a mini-epoch run on (runner.num_mini_batches > 1: _mini_batch_begin)
         return types.SimpleNamespace(cfg=cfg, buf=buf, T=T, N=N, B=B, alg=alg, ahead=ahead, plan=plan, logstd_flat=logstd_flat, old_logstd=old_logstd,
                                      main=torch.cuda.current_stream(), side=self._side_stream, mirrors=None, whole=whole, steps=[whole], ha0=ha0)
 
     # ------------------------------------------------------------------ the pieces of a mini-epoch, each on the rows of a StepRows, on the current stream
-    def _actor_hidden(self, at, x):
-        """The actor's last hidden activations on the rows x; with a recurrent actor (algorithm.rnn_hidden_size) x are the cell's padded [B][64] rows:
-        gi on all of them, the recurrence from h0 with the resets (GRUTrainer.forward), then the trunk on h."""
-        return at.forward_hidden(x if self._mem_tr is None else self._mem_tr.forward(x))
+    def _whole_cell(self):
+        """The CellRows of the whole batch: the cell's trainer with its own state and reset flags (None: a feed-forward actor)."""
+        mt = self._mem_tr
+        return None if mt is None else CellRows(mt, mt.h0, mt.resets)
 
-    def _actor_backward_hidden(self, at, fins):
+    @staticmethod
+    def _actor_hidden(at, x, mem):
+        """The actor's last hidden activations on the rows x; with a recurrent actor (mem: the rows' CellRows) x are the cell's padded [rows][64] rows:
+        gi on all of them, the recurrence from the rows' h0 with their resets (GRUTrainer.forward), then the trunk on h."""
+        return at.forward_hidden(x if mem is None else mem.trainer.forward(x, mem.h0, mem.resets))
+
+    @staticmethod
+    def _actor_backward_hidden(at, fins, mem):
         """The actor's backward-data pass; with a recurrent actor the trunk's, then the cell's through time (GRUTrainer.backward: truncated at h0), whose
         bias gradients join the deferred reductions."""
         at.backward_hidden(finishes=fins)
-        if self._mem_tr is not None:
-            self._mem_tr.backward(finishes=fins)
+        if mem is not None:
+            mem.trainer.backward(finishes=fins)
 
     def _forward_hidden(self, v):
         """The hidden layers of both networks on v's rows: one grouped launch, or one pass per network.  Returns their last hidden activations."""
         if v.plan.one_stream:
             return MLPTrainer.forward_hidden_group([(v.ct, v.x_c, v.train_rows), (v.at, v.x_a, None)])
-        return v.ct.forward_hidden(v.x_c, train_rows=v.train_rows), self._actor_hidden(v.at, v.x_a)
+        return v.ct.forward_hidden(v.x_c, train_rows=v.train_rows), self._actor_hidden(v.at, v.x_a, v.mem)
 
     def _head_values(self, v, hc):
         """The critic's values of v.x_c's rows in v.values: left there by the chained forward launch's value head (plan.chain_values: from the registers
@@ -1067,7 +1184,7 @@ class Runner:
                 MLPTrainer.backward_hidden_group([ct, at], fins)
             else:
                 ct.backward_hidden(finishes=fins)
-                self._actor_backward_hidden(at, fins)
+                self._actor_backward_hidden(at, fins, v.mem)
         else:
             g_val, g_mu = self._library_loss(u, v, at.forward(v.x_a), ct.forward(v.x_c, train_rows=v.train_rows).squeeze(-1)[: v.rows])
             self._exchange_sums()  # exchange (3)
@@ -1094,7 +1211,7 @@ class Runner:
             elif u.ha0 is not None:  # a recurrent actor's mini-epoch 0: old mu's forward pass, run through these same launches on these parameters
                 ha, u.ha0 = u.ha0, None
             else:
-                ha = self._actor_hidden(at, v.x_a)
+                ha = self._actor_hidden(at, v.x_a, v.mem)
             with torch.cuda.stream(side):
                 self._critic_loss_head(v, hc, values, fin_c)
                 ct.backward_hidden(finishes=fins)
@@ -1104,7 +1221,7 @@ class Runner:
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
                     self._exchange_sums()  # exchange (3): loss / KL sums, hidden under the backward passes
-            self._actor_backward_hidden(at, fins)
+            self._actor_backward_hidden(at, fins, v.mem)
         else:
             mu = at.forward(v.x_a)
             main.wait_stream(side)
@@ -1134,7 +1251,7 @@ class Runner:
         # all weight gradients after both backward chains, alone on the GPU: one launch pair for the six hidden layers (shapes outside the
         # kernel's range, or MLPTrainer.FUSED_WGRAD = False: library GEMMs, layer by layer); one_tail: their finish inside bg_update_tail
         # (a recurrent actor: the cell's two weight gradients ride in the same launch, its padded W_ih among the copies)
-        trainers = (v.ct, v.at) if self._mem_tr is None else (v.ct, v.at, self._mem_tr)
+        trainers = (v.ct, v.at) if v.mem is None else (v.ct, v.at, v.mem.trainer)
         wg_partial = v.wgrad.run(trainers, plan.wgrad, one_tail)
         if plan.defer and plan.ranks:
             main.wait_stream(side)
@@ -1236,7 +1353,7 @@ class Runner:
         B, A, E, S = T * N * self.world_size, self.env.num_actions, self.cfg["runner"]["mini_epochs"], self._n_stats
         self.learning_rate = s[2 * S]
         out = {"value_loss": s[0] / (B * E), "actor_loss": s[1] / (B * E), "bound_loss": s[2] / (B * A * E), "entropy": s[3] / (B * E),
-               "kl_mean": s[S + 4] / (B // self._mini_batches), "lr": s[2 * S]}  # (the last optimiser step's KL sum: over its b = B / K rows of every rank)
+               "kl_mean": s[S + 4] / (B // max(self._mini_batches, self._env_mini_batches)), "lr": s[2 * S]}  # (the last optimiser step's KL sum: over its b = B / K rows of every rank)
         if S > 5 and self._smooth:  # mean squared difference of the actor's mean over the pairs (x, x'), before smoothness_coef
             out["smoothness_loss"] = s[5] / (B * A * E)
         elif S > 5:  # mean squared asymmetry of the actor's mean, before symmetric_coef (like bound_loss before bound_coef)

@@ -799,6 +799,27 @@ typedef struct {
  * A stream's src and dst must not overlap. */
 int bg_gather_rows(int32_t rows, int32_t src_rows, const int32_t* perm, const bg_gather_stream* streams, int32_t n_streams, void* stream);
 
+/* ---- env-wise mini-batches of sequences for PPO on a recurrent actor (runner.num_env_mini_batches > 1; bg_minibatch.hip).  One launch of its own
+ * per mini-epoch (beside a bg_perm_fill over the envs): nothing of it runs when the key is absent or 1.
+ *
+ * One row-major stream of bg_gather_sequences.  per_env = 0: src [T][N][width] -> dst [K][T][n][width]; per_env != 0: src [N][width] -> dst
+ * [K][n][width] (the recurrence's starting state). */
+typedef struct {
+    const void* src;
+    void* dst;
+    int32_t width;     /* elements per row, 1 to 4096; a row of a multiple of 16 bytes with 16-byte aligned buffers moves 16 bytes per thread */
+    int32_t elem_size; /* bytes per element: 4, or 1 (the reset flags) */
+    int32_t per_env;
+    int32_t pad;
+} bg_sequence_stream;
+#define BG_SEQUENCE_MAX_STREAMS 12
+/* With n = N / K (K must divide N) and sigma an int32 permutation of the envs [0, N): for every per-row stream
+ *   dst[(k T + t) n + j][:] = src[t N + sigma[k n + j]][:],  k < K, t < T, j < n
+ * -- mini-batch k holds the whole T-step sequences of its n envs, step-major -- and for every per-env stream dst[i][:] = src[sigma[i]][:], i < N; all
+ * streams (1 to BG_SEQUENCE_MAX_STREAMS) in ONE launch: bit copies, no arithmetic.  A value of sigma outside [0, N) leaves its T destination rows
+ * (its one per-env row) as they were and is never read out of bounds.  A stream's src and dst must not overlap; T x N stays below 2^31. */
+int bg_gather_sequences(int32_t T, int32_t N, int32_t K, const int32_t* sigma, const bg_sequence_stream* streams, int32_t n_streams, void* stream);
+
 const char* bg_last_error(void);
 const char* bg_version(void);
 
