@@ -69,7 +69,7 @@ class MlpChain(C.Structure):
 class MlpChainSplit(C.Structure):
     """bg_mlp_chain_split: the forward chain of one network on the bf16 matrix pipe (9 exact products) for bg_mlp_chain_forward_split."""
     _fields_ = [("M", C.c_int32), ("K0", C.c_int32), ("N1", C.c_int32), ("N2", C.c_int32), ("N3", C.c_int32), ("workgroups", C.c_int32),
-                ("alternate", C.c_int32), ("pad", C.c_int32)] + \
+                ("alternate", C.c_int32), ("slab0", C.c_int32)] + \
                [(n, C.c_void_p) for n in ("X", "P1", "P2", "P3", "b1", "b2", "b3", "Y1", "Y2", "Y3", "v_w", "v_b", "v_out")]
 
 

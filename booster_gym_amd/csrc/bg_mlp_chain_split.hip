@@ -170,7 +170,7 @@ __device__ __forceinline__ void split_net(const bg_mlp_chain_split& a, int first
     // ---- prologue of the first slab
     int slab = first;
     int row = slab * 128 + wave * 32 + i;
-    negc = a.alternate && (slab & 1);
+    negc = a.alternate && ((a.slab0 + slab) & 1);
     sgn = sgnp = negc ? -1.0f : 1.0f;
     BG_STAMP(0);
     BG_STAMP_WALL(62);
@@ -334,7 +334,7 @@ __device__ __forceinline__ void split_net(const bg_mlp_chain_split& a, int first
         const int next = slab + stride;
         const bool has_next = next < nslabs;
         const int rown = (has_next ? next : slab) * 128 + wave * 32 + i;
-        negn = a.alternate && ((has_next ? next : slab) & 1);
+        negn = a.alternate && ((a.slab0 + (has_next ? next : slab)) & 1);
         layer(IC<1>{}, a1, x0in, IC<K0>{}, IC<N1>{}, IC<0>{}, rown);
         layer(IC<2>{}, a2, a1in, IC<N1>{}, IC<N2>{}, IC<C0>{}, rown);
         layer(IC<3>{}, a3, a2in, IC<N2>{}, IC<N3>{}, IC<C0 + C1>{}, rown);
@@ -403,6 +403,7 @@ int split_check(const bg_mlp_chain_split& q) {
     if (!(q.K0 == 64 && q.N1 == 256 && (q.N2 == 128 || q.N2 == 256) && q.N3 == 128))
         return bg_set_error(-4, "bg_mlp_chain_forward_split: unsupported widths (64-256-128-128 and 64-256-256-128)");
     if (q.workgroups < 0) return bg_set_error(-1, "bg_mlp_chain_forward_split: workgroups < 0");
+    if (q.slab0 < 0) return bg_set_error(-1, "bg_mlp_chain_forward_split: slab0 < 0");
     return 0;
 }
 

@@ -447,12 +447,14 @@ class MLPTrainer:
     def chain_rows_descriptor(self, row0, nrows):
         """bg_mlp_chain of rows [row0, row0 + nrows) of the pass prepared by `prepare` (whole 128-row slabs: the kernel stores every slab in full):
         the same launch the full-batch forward makes, restricted to these slabs -- bit-identical outputs in the same places of the activation buffers
-        (and of the value head's output).  Used by the rollout, which evaluates each step's rows as soon as the simulator has produced them."""
+        (and of the value head's output; slab0 tells the kernel the place of the piece's first slab in the batch).  Used by the rollout, which
+        evaluates each step's rows as soon as the simulator has produced them."""
         if row0 % 128 or nrows % 128 or row0 + nrows > self.x.shape[0]:
             raise ValueError("chain_rows_descriptor: row0 and nrows must be multiples of 128 inside the prepared batch")
         d = self._chain_descriptor()
         d.M = nrows
         d.workgroups = 0  # (a few slabs during the rollout: one workgroup each)
+        d.slab0 = row0 // 128  # (which slabs accumulate the negated sums follows their place in the batch, not in this launch)
         d.X = d.X + 4 * row0 * self._kin
         d.Y1, d.Y2, d.Y3 = (y + 4 * row0 * l.weight.shape[0] for y, l in zip((d.Y1, d.Y2, d.Y3), self.layers[:3]))
         if d.v_out:

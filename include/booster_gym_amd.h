@@ -557,8 +557,11 @@ typedef struct bg_mlp_chain_split {
     /* alternate != 0: odd slabs accumulate the NEGATED sums (the planes of -W: P1 / P2 / P3 then hold both sets, bg_mlp_split_weights_pm) and the
      * sign is put back where a tile is finished.  The bf16 MFMA's accumulator does not round to nearest: every accumulated element carries a small
      * bias of one sign (measured: -0.05 of the rms error), which adds up in everything summed over rows downstream (bias and weight gradients);
-     * alternating the sign of the accumulation slab by slab makes the bias cancel.  Same products, same exactness. */
-    int32_t alternate, pad;
+     * alternating the sign of the accumulation slab by slab makes the bias cancel.  Same products, same exactness.
+     * slab0 >= 0: the place in its batch of the launch's first 128-row slab (X / Y1 / Y2 / Y3 / v_out point at row 128 * slab0 of a larger batch);
+     * slab slab0 + s of the batch is odd or even, not slab s of the launch, so a piece leaves the bits the launch on the whole batch leaves.
+     * A launch on a whole batch passes 0. */
+    int32_t alternate, slab0;
     const float* X;
     const uint16_t *P1, *P2, *P3;
     const float *b1, *b2, *b3;

@@ -178,8 +178,37 @@ def test_split_chain_value_head_group_and_bad_arguments():
     dc.v_b = None
     assert lib.bg_mlp_chain_forward_split(ctypes.addressof(dc), 1, st) == -1 and b"value head" in lib.bg_last_error()
     dc.v_b = p(vb)
-    for field, val, rc in (("N1", 512, -4), ("K0", 47, -4), ("M", 0, -1), ("X", dc.X + 4, -1), ("P2", None, -1), ("workgroups", -1, -1)):
+    for field, val, rc in (("N1", 512, -4), ("K0", 47, -4), ("M", 0, -1), ("X", dc.X + 4, -1), ("P2", None, -1), ("workgroups", -1, -1), ("slab0", -1, -1)):
         bad = _lib.MlpChainSplit.from_buffer_copy(dc)
         setattr(bad, field, val)
         assert lib.bg_mlp_chain_forward_split(ctypes.addressof(bad), 1, st) == rc, field
     assert lib.bg_mlp_chain_forward_split(ctypes.addressof(arr), 5, st) == -1
+
+
+@pytest.mark.parametrize("alternate", [1, 0])
+def test_split_chain_piece_that_starts_on_an_odd_slab_leaves_the_full_launch_bits(alternate):
+    """A piece of a batch that starts on an ODD 128-row slab: rows [1408, 1408 + 2560) = slabs 11 .. 30 of the 6496-row batch above.  Which slabs
+    accumulate the negated sums is decided by the slab's place in the BATCH, not in the launch, so the piece leaves the full launch's bits in all
+    three activations and in the value head's output (the pieces of the test above start on slab 10, where the two counts agree)."""
+    from booster_gym_amd import _lib
+
+    lib, st, p = _lib.load(), _lib.current_stream_ptr(), _lib.ptr
+    M, r0, nr = 2400 + 4096, 1408, 2560
+    dc, xc, Wc, bc, yc, Pc = _case(M, (64, 256, 256, 128), seed=1, k_real=61, alternate=alternate)
+    g = torch.Generator(device="cpu").manual_seed(5)
+    vw, vb = (torch.randn(128, generator=g) * 0.1).to(DEV), torch.randn(1, generator=g).to(DEV)
+    vo = torch.full((M,), float("nan"), device=DEV)
+    dc.v_w, dc.v_b, dc.v_out = p(vw), p(vb), p(vo)
+    _lib.check(lib.bg_mlp_chain_forward_split(ctypes.addressof(dc), 1, st), "bg_mlp_chain_forward_split")
+    keep = [y.clone() for y in yc] + [vo.clone()]
+    assert all(torch.isfinite(t[:M]).all() for t in keep)
+    for y in yc + [vo]:
+        y[r0 : r0 + nr].fill_(float("nan"))
+    part = _lib.MlpChainSplit.from_buffer_copy(dc)
+    part.M, part.slab0 = nr, r0 // 128
+    part.X = dc.X + 4 * r0 * 64
+    part.Y1, part.Y2, part.Y3 = dc.Y1 + 4 * r0 * 256, dc.Y2 + 4 * r0 * 256, dc.Y3 + 4 * r0 * 128
+    part.v_out = dc.v_out + 4 * r0
+    _lib.check(lib.bg_mlp_chain_forward_split(ctypes.addressof(part), 1, st), "bg_mlp_chain_forward_split")
+    for k, (a, b) in enumerate(zip(keep, yc + [vo])):
+        assert torch.equal(a[:M], b[:M]), (k, int((a[:M] != b[:M]).sum()), (a[:M] - b[:M]).abs().max().item())

@@ -415,10 +415,15 @@ def test_forward_passes_run_during_the_rollout_change_no_bit():
     from booster_gym_amd.utils.config import load_cfg
     from booster_gym_amd.utils.runner import Runner
 
-    # (the last two: a horizon that the group size does not divide, and a group larger than the horizon -- every row still gets its pass exactly once)
+    # (groups 2 and 8: a horizon that the group size does not divide, and a group larger than the horizon -- every row still gets its pass exactly once)
     for over, group in (({"terrain.type": "plane"}, None), ({"terrain.type": "trimesh", "commands.curriculum": True}, None),
                         ({"terrain.type": "plane", "runner.horizon_length": 5, "env.num_envs": 128}, 2),
-                        ({"terrain.type": "plane", "runner.horizon_length": 5, "env.num_envs": 128}, 8)):
+                        ({"terrain.type": "plane", "runner.horizon_length": 5, "env.num_envs": 128}, 8),
+                        # an odd number of slabs per step with an odd group: pieces that start on ODD slabs of the batch (the negated accumulation
+                        # follows the slab's place in the batch, MlpChainSplit.slab0)
+                        ({"terrain.type": "plane", "runner.horizon_length": 5, "env.num_envs": 128}, 1),
+                        ({"terrain.type": "plane", "runner.horizon_length": 5, "env.num_envs": 384}, 1),
+                        ({"terrain.type": "plane", "runner.horizon_length": 5, "env.num_envs": 384}, 3)):
         res = []
         for ahead in (True, False):
             cfg = load_cfg("T1", dict({"env.num_envs": 256, "runner.mini_epochs": 3, "basic.seed": 7}, **over))
