@@ -28,6 +28,63 @@ FLAG_TERMS = ("feet_slip", "feet_swing")          # functions of the foot-contac
 COUNT_TERMS = ("dof_pos_limits", "collision")     # integer counts of threshold crossings
 
 
+def gru_sequence_case(T, N, H, gi_scale=1.0, reset=0.2, h0=True, device="cpu"):
+    """Inputs of bg_gru_sequence_forward / _backward at one shape, with the float64 restatement of the recurrence and an fp32 torch twin of the same
+    loop (what torch's own fp32 arithmetic leaves of it: the yardstick a kernel's error is printed beside).
+      gi_scale  multiplies the x-side pre-activations gi (8: a large share of the gates saturates)
+      reset     a rate (each flag set with that probability), "step2" (every env at t = 2 and nowhere else), "t0" (the rate-0.2 flags of step 0,
+                none later), "none" (an all-zero tensor) or None (no tensor: the launch's reset == NULL)
+      h0        False: no tensor (h0 == NULL); the restatement then starts from a zero state
+    The draws are made in one fixed order whatever the options, so two cases of one (T, N, H) share gi, h0, the rate-0.2 flags and dh_ext.
+    Returns T, N, H, cell (torch.nn.GRUCell(47, H)), gi [T][N][3H], h0 [N][H] or None, reset uint8 [T][N] or None, dh_ext [T][N][H] on `device`, and
+    ref / twin: dicts of h_prev, h [T][N][H], gates [T][N][4H] = r | z | n | gh_n, and autograd's dgi, dgh [T][N][3H], dh0 [N][H] of
+    sum(h * dh_ext), in float64 / float32."""
+    import torch
+
+    g = torch.Generator(device="cpu").manual_seed(40 + H)
+    torch.manual_seed(7)
+    cell = torch.nn.GRUCell(47, H)
+    gi = torch.randn(T, N, 3 * H, generator=g) * gi_scale
+    h0_t = torch.randn(N, H, generator=g) * 0.5
+    drawn = torch.rand(T, N, generator=g)
+    dh_ext = torch.randn(T, N, H, generator=g)
+    if reset is None:
+        flags = None
+    elif reset == "none":
+        flags = torch.zeros(T, N, dtype=torch.uint8)
+    elif reset == "step2":
+        flags = torch.zeros(T, N, dtype=torch.uint8)
+        flags[2] = 1
+    elif reset == "t0":
+        flags = (drawn < 0.2).to(torch.uint8)
+        flags[1:] = 0
+    else:
+        flags = (drawn < float(reset)).to(torch.uint8)
+    if not h0:
+        h0_t = None
+
+    def loop(dtype):
+        W, b = cell.weight_hh.detach().to(dtype), cell.bias_hh.detach().to(dtype)
+        gi_, h0_ = gi.to(dtype).requires_grad_(), (torch.zeros(N, H, dtype=dtype) if h0_t is None else h0_t.to(dtype)).requires_grad_()
+        h, hp_l, h_l, gates_l, gh_l = h0_, [], [], [], []
+        for t in range(T):
+            hp = h if flags is None else h * (1 - flags[t].to(dtype)).view(N, 1)
+            gh = hp @ W.t() + b
+            gh.retain_grad()
+            r, z = torch.sigmoid(gi_[t, :, :H] + gh[:, :H]), torch.sigmoid(gi_[t, :, H : 2 * H] + gh[:, H : 2 * H])
+            n = torch.tanh(gi_[t, :, 2 * H :] + r * gh[:, 2 * H :])
+            h = (1 - z) * n + z * hp
+            hp_l.append(hp); h_l.append(h); gh_l.append(gh); gates_l.append(torch.cat((r, z, n, gh[:, 2 * H :]), 1))
+        (torch.stack(h_l) * dh_ext.to(dtype)).sum().backward()
+        out = dict(h_prev=torch.stack(hp_l).detach(), h=torch.stack(h_l).detach(), gates=torch.stack(gates_l).detach(), dgi=gi_.grad,
+                   dgh=torch.stack([x.grad for x in gh_l]), dh0=h0_.grad)
+        return {k: v.to(device) for k, v in out.items()}
+
+    ref, twin = loop(torch.float64), loop(torch.float32)
+    to = lambda x: None if x is None else x.to(device)
+    return dict(T=T, N=N, H=H, cell=cell.to(device), gi=to(gi), h0=to(h0_t), reset=to(flags), dh_ext=to(dh_ext), ref=ref, twin=twin)
+
+
 def rel_state(a, b):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     return (np.abs(a - b) / np.maximum(1.0, np.abs(b))).reshape(a.shape[0], -1).max(axis=1)

@@ -64,11 +64,11 @@ def _launch(name, student, teacher, tobs, sobs, P, counter, N, beta=None, noise=
     return [t[:N] for t in outs]
 
 
-def _choice(N, counter, beta):
+def _choice(N, counter, beta, seed=SEED):
     """The host's restatement of who acts: u < beta in fp32, u = entry 0 of rand4(seed, row, counter, 29)."""
     from oracle.task_ref import rand4
 
-    u, _ = rand4(SEED, np.arange(N), counter, RS_DAGGER)
+    u, _ = rand4(seed, np.arange(N), counter, RS_DAGGER)
     assert u.dtype == np.float32
     return torch.from_numpy(u[:, 0] < np.float32(beta)).to(DEV)
 

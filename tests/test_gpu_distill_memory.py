@@ -5,7 +5,8 @@ reproducibility, the checkpoint's way back through Evaluator, Runner.play and ex
 
 Bounds: tests/test_gpu_distill.py's for the actor kernels (2e-5 max(1, |ref|max)) on every forward quantity; gradients 1e-4 of the tensor's largest
 entry (torch's own fp32 autograd of the recurrence sits at 4e-7 of it; a wrong or missing term moves a tensor by O(1)); parameters after an update
-rtol 1e-3, atol 2e-6 at the learning rate 1e-5.  Shapes: N = 40 = two 16-row tiles and a tail of 8; T = 5; both widths of the cell."""
+rtol 1e-3, atol 2e-6 at the learning rate 1e-5.  Shapes: N = 40 = two 16-row tiles and a tail of 8; T = 5; both widths of the cell (every other shape of the four launches:
+tests/test_gpu_gru_shapes.py)."""
 import copy
 import functools
 import hashlib
@@ -219,37 +220,18 @@ def test_distill_act_gru(H, t_hidden):
 # ------------------------------------------------------------------ 3. / 4. the update's recurrence
 @functools.lru_cache(maxsize=None)
 def _sequence(H):
-    """Inputs of the two sequence launches, the forward launch's outputs and the float64 restatement with its autograd gradients (computed once)."""
-    from booster_gym_amd import _lib
+    """Inputs of the two sequence launches, the forward launch's outputs and the float64 restatement with its autograd gradients (computed once):
+    tests/parity_util.gru_sequence_case at this file's one shape."""
+    from parity_util import gru_sequence_case
 
     T, N = 5, 40
-    g = torch.Generator(device="cpu").manual_seed(40 + H)
-    torch.manual_seed(7)
-    cell = torch.nn.GRUCell(47, H).to(DEV)
-    gi = torch.randn(T, N, 3 * H, generator=g).to(DEV)
-    h0 = (torch.randn(N, H, generator=g) * 0.5).to(DEV)
-    reset = (torch.rand(T, N, generator=g) < 0.2).to(torch.uint8).to(DEV)
+    c = gru_sequence_case(T, N, H, device=DEV)
+    cell, gi, h0, reset, dh_ext = c["cell"], c["gi"], c["h0"], c["reset"], c["dh_ext"]
     assert 0 < int(reset[0].sum()) < N and 0 < int(reset[1:].sum())
-    dh_ext = torch.randn(T, N, H, generator=g).to(DEV)
     pad = lambda w: torch.full((T * N + 16, w), 7.0, device=DEV)
     run = lambda: _run_forward(T, N, H, gi, h0, reset, cell, [pad(H), pad(H), pad(4 * H)])
     out, again = run(), run()
-    # float64
-    W, b = cell.weight_hh.double(), cell.bias_hh.double()
-    gi64, h064 = gi.double().requires_grad_(), h0.double().requires_grad_()
-    h, hp_l, h_l, gates_l, gh_l = h064, [], [], [], []
-    for t in range(T):
-        hp = h * (1 - reset[t].double()).view(N, 1)
-        gh = hp @ W.t() + b
-        gh.retain_grad()
-        r, z = torch.sigmoid(gi64[t, :, :H] + gh[:, :H]), torch.sigmoid(gi64[t, :, H : 2 * H] + gh[:, H : 2 * H])
-        n = torch.tanh(gi64[t, :, 2 * H :] + r * gh[:, 2 * H :])
-        h = (1 - z) * n + z * hp
-        hp_l.append(hp); h_l.append(h); gh_l.append(gh); gates_l.append(torch.cat((r, z, n, gh[:, 2 * H :]), 1))
-    (torch.stack(h_l) * dh_ext.double()).sum().backward()
-    ref = dict(h_prev=torch.stack(hp_l).detach(), h=torch.stack(h_l).detach(), gates=torch.stack(gates_l).detach(), dgi=gi64.grad,
-               dgh=torch.stack([x.grad for x in gh_l]), dh0=h064.grad)
-    return dict(T=T, N=N, cell=cell, gi=gi, h0=h0, reset=reset, dh_ext=dh_ext, out=out, again=again, ref=ref)
+    return dict(T=T, N=N, cell=cell, gi=gi, h0=h0, reset=reset, dh_ext=dh_ext, out=out, again=again, ref=c["ref"])
 
 
 def _run_forward(T, N, H, gi, h0, reset, cell, bufs):

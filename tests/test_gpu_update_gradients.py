@@ -23,7 +23,15 @@ error / |ref|max, the fp32 twin's in brackets:
          .4.weight 1.08e-6 (3.29e-6)  .4.bias 8.60e-7 (3.03e-6)  .6.weight 1.18e-6 (4.21e-6)  .6.bias 1.07e-6 (3.44e-6)
 The clip's norm agrees with float64's to 8.4e-7.  Rows the reference clips: 0 / 86.9 % / 91.1 % in steps 0 / 1 / 2, the nearest ratio 2.9e-3 from a
 boundary.  (d): against the population-std reference actor.2.weight is off by 7.81e-4 in every step, 7.8 x the bound.  The largest error of any case:
-4.6e-5 (twin 1.0e-5) in critic.6.bias of key:hidden_widths' first step (the sum of v - ret over the rows, whose terms cancel).  No tensor of any case needed a bound of its own (BOUNDS is empty), and no gradient was found wrong."""
+4.6e-5 (twin 1.0e-5) in critic.6.bias of key:hidden_widths' first step (the sum of v - ret over the rows, whose terms cancel).  No tensor of any case needed a bound of its own (BOUNDS is empty), and no gradient was found wrong.
+
+A recurrent actor (RECURRENT: algorithm.rnn_hidden_size at 100 x 5 / H = 128 and 48 x 24 / H = 256, runner.num_env_mini_batches = 3 at 384 x 5): the record
+carries the step's h0 and reset flags and the reference runs the cell through time (update_grad_ref.recurrent_means); one iteration runs in front of
+the recorded one, so that every step starts from a state that is not zero and, under episodes of 7 control steps, some env enters a step behind the
+first with a zero state (asserted, with the cell's four tensors, the trunk's eight and logstd among the compared).  Measured on an MI355X, the
+largest error / |ref|max of any step and tensor (the twin's in brackets): 1.6e-6 (8.5e-7) in critic.6.weight / 4.3e-6 (2.9e-6) in critic.6.weight / 1.3e-6
+(1.4e-7) in critic.4.bias; of the cell's four tensors alone 1.3e-6 (1.5e-6) / 8.0e-7 (1.4e-6) / 7.9e-7 (1.4e-6).  Control: against a restatement that detaches the
+state between steps (no back-propagation through time) memory.weight_hh of key:rnn_hidden_size's first step is off by 0.277 of its largest entry, 2769 x the bound."""
 import math
 
 import pytest
@@ -104,6 +112,18 @@ def _mini_batches(seed, lr):
     return _runner(256, **{KEY: 2}, **_common(5, 2, seed, lr))  # (two mini-batches of 640 rows: whole slabs)
 
 
+def _recurrent(n, T, E, H, **over):
+    """PPO on a recurrent actor (algorithm.rnn_hidden_size = H), under episodes of 7 control steps (tests/test_gpu_actor_memory.SHORT_EPISODES): every
+    env times out on its 8th step, so resets fall inside the recorded horizon -- the second one at T = 5, the first at T = 24."""
+    def make(seed, lr):
+        from booster_gym_amd.utils.config import load_cfg
+        from booster_gym_amd.utils.runner import Runner
+        from test_gpu_actor_memory import KEY, SHORT_EPISODES
+
+        return Runner(cfg=load_cfg("T1", {"env.num_envs": n, KEY: H, **SHORT_EPISODES, **over, **_common(T, E, seed, lr)}))
+    return make
+
+
 # name: (runner factory (seed, lr), key into SWITCHES, iterations run in front of the recorded one)
 CASES = {f"plan:{k}": (_plain(128, 5, 3), k, 0) for k in PLAN_CASES}
 CASES.update({"shape:100x5": (_plain(100, 5, 3), "default", 0),      # ragged last slab everywhere, no forward-ahead
@@ -116,11 +136,21 @@ CASES.update({"shape:100x5": (_plain(100, 5, 3), "default", 0),      # ragged la
               "key:actor_heights": (_actor_heights, "default", 0),
               "key:privileged_extras": (_privileged_extras, "default", 0),
               "key:hidden_widths": (_widths, "default", 0),
-              "key:num_mini_batches": (_mini_batches, "default", 0)})
+              "key:num_mini_batches": (_mini_batches, "default", 0),
+              # a recurrent actor: the cell's gradients through time, every optimiser step from its own parameters (ratios away from 1 after the first)
+              "key:rnn_hidden_size": (_recurrent(100, 5, 3, 128), "default", 1),          # 6 tiles of the recurrence and a tail of 4 rows; B = 500: three
+                                                                                          # 128-row blocks of bg_gru_bias_partial and a ragged one
+              "key:rnn_hidden_size_wide_24": (_recurrent(48, 24, 2, 256), "default", 1),  # the workload's horizon; B = 1152: nine 128-row blocks
+              # three env-wise mini-batches, six optimiser steps, each from its own gathered state and flags.  384 envs, not 96: a step's rows
+              # T x envs / K must be whole 128-row slabs (runner.env_mini_batches refuses 5 x 32 = 160), so 128 envs a step is the smallest at T = 5
+              "key:num_env_mini_batches": (_recurrent(384, 5, 2, 128, **{"runner.num_env_mini_batches": 3}), "default", 1)})
+RECURRENT = ("key:rnn_hidden_size", "key:rnn_hidden_size_wide_24", "key:num_env_mini_batches")
 # (basic.seed, algorithm.learning_rate) per case, chosen on the GPU so that (c) holds -- conditions on the float64 reference alone -- and kept fixed
 SEED, LR = 11, 1e-3
 TUNED = {"shape:256x24": (12, LR),           # seed 11: a row 1.86e-5 from the boundary
          "key:hidden_widths": (SEED, LR / 3)}  # at 1e-3 the wider networks move further: 96.7 % of the rows clipped, fewer than 5 % left
+# The three recurrent cases hold (c) at the default pair (11, 1e-3), the first one tried: the float64 reference clips 47.2 % / 63.9 % / 58.1 % of the
+# last step's rows (key:rnn_hidden_size / _wide_24 / key:num_env_mini_batches), the nearest ratio 7.3e-4 / 5.8e-5 / 1.9e-3 from a boundary.
 # (case, tensor): a bound other than BOUND, 4 x the fp32 twin's measured error where the twin itself is above TWIN_FLOOR (see the docstring)
 BOUNDS = {}
 
@@ -148,7 +178,7 @@ def run_case(name, seed=None, lr=None):
             r.iteration()
         r.rollout()
         plan, fwd_plan = r._resolve_plan(), r._fwd_plan
-        K, E = r._mini_batches, r.cfg["runner"]["mini_epochs"]
+        K, E = max(r._mini_batches, r._env_mini_batches), r.cfg["runner"]["mini_epochs"]
         step_plan = r._mb_plan if K > 1 else plan
         with record_steps(r) as steps:
             assert r._resolve_plan() == plan and (K == 1 or r._mb_plan == step_plan), "the recorder changed the plan"
@@ -171,6 +201,14 @@ def run_case(name, seed=None, lr=None):
     make_model, alg = model_factory(r), r.cfg["algorithm"]
     out = dict(name=name, seed=seed, lr=lr, plan=plan, ahead=fwd_plan == plan, B=B, steps=[], extra=extra,
                numel={k: p.numel() for k, p in r.model.named_parameters()})
+    if name in RECURRENT:  # every step reads a state and flags of its own rows, and some env enters a step behind the first with a zero state
+        T, n = r.cfg["runner"]["horizon_length"], r.env.num_envs // K
+        assert all(tuple(rec["h0"].shape) == (n, r._memory) and tuple(rec["resets"].shape) == (T, n) for rec in steps)
+        out["resets_inside"] = [int(rec["resets"][1:].sum()) for rec in steps]
+        out["h0_max"] = [rec["h0"].abs().max().item() for rec in steps]
+        if K > 1:
+            assert not torch.equal(steps[0]["h0"], steps[1]["h0"])
+        print(f"{name}: reset flags behind step 0 per optimiser step {out['resets_inside']}, |h0|max {out['h0_max']}")
     for s, rec in enumerate(steps):
         aux = {}
         ref = step_gradients_f64(rec, make_model, alg, extra, aux=aux)
@@ -189,6 +227,9 @@ def run_case(name, seed=None, lr=None):
         if name == "plan:default":
             wrong = step_gradients_f64(rec, make_model, alg, extra, unbiased=False)
             m["wrong"] = {k: (rec["grads"][k].double() - g).abs().max().item() / g.abs().max().item() for k, g in wrong.items()}
+        if name == "key:rnn_hidden_size" and s == 0:  # the control: a restatement without back-propagation through time
+            k, cut = "memory.weight_hh", step_gradients_f64(rec, make_model, alg, extra, bptt=False)
+            m["no_bptt"] = (rec["grads"][k].double() - cut[k]).abs().max().item() / cut[k].abs().max().item()
         out["steps"].append(m)
         for k, (e, t, top) in rows.items():
             print(f"{name} step {s} {k}: error {e:.3e} of |ref|max {top:.3e}; fp32 twin {t:.3e}")
@@ -210,6 +251,11 @@ def check_case(m):
         assert plan.critic.fwd == plan.actor.fwd == "chain_split" and plan.critic.bwd == plan.actor.bwd == "chain_split"
     if m["extra"] is not None:
         assert all(s["pair_loss"] > 0 for s in m["steps"])
+    if name in RECURRENT:
+        assert all(n > 0 for n in m["resets_inside"]) and all(h > 1e-3 for h in m["h0_max"]), (name, m["resets_inside"], m["h0_max"])
+        for st in m["steps"]:  # the cell's four tensors, the trunk's eight and the log-std are among the compared
+            assert {"memory.weight_ih", "memory.weight_hh", "memory.bias_ih", "memory.bias_hh", "logstd"} <= set(st["rows"])
+            assert sum(k.startswith("actor.") for k in st["rows"]) == 8
     # (c): conditions on the float64 reference
     last = m["steps"][-1]
     assert 0.05 <= last["clipped"] <= 0.95, (name, last["clipped"])
@@ -225,6 +271,10 @@ def check_case(m):
     assert not missed, (name, missed)
     # (bg_optimizer_step alone keeps its norm in registers)
     assert all((st["norm_used"] is None) == (st["form"] == "fused") for st in m["steps"])
+    if name == "key:rnn_hidden_size":  # the control: without back-propagation through time the recurrent weights' gradient is another one
+        off = m["steps"][0]["no_bptt"]
+        print(f"{name} step 0: against a restatement that detaches the state between steps memory.weight_hh is off by {off:.3e} ({off / BOUND:.0f} x the bound)")
+        assert off > BOUND, off
     if name == "plan:default":  # (d)
         k = max((k for k in last["rows"] if k.startswith("actor.") and k.endswith(".weight")), key=m["numel"].get)
         for s, st in enumerate(m["steps"]):

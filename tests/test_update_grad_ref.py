@@ -1,6 +1,7 @@
 """tests/update_grad_ref.step_gradients_f64 against the oracle it restates (oracle/ppo_ref.ppo_update_reference, pinned by tests/golden/ppo_*.npz): a
 hand-built record of a tiny float64 batch gives the gradients of the reference loop's first step to 1e-12 of each tensor's largest entry -- plain, and
-with the mirror-symmetry term against a copy of tests/test_gpu_symmetry.ppo_update_sym_reference's loss.  No GPU."""
+with the mirror-symmetry term against a copy of tests/test_gpu_symmetry.ppo_update_sym_reference's loss; and the recurrent form (a record with h0 and
+resets) against the same loop on tests/test_gpu_actor_memory._Restated's model, a GRU cell of 128 in front of the trunk, with resets.  No GPU."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -125,3 +126,58 @@ def test_step_gradients_with_the_symmetry_term_reproduce_the_symmetric_loops_fir
     # the smoothness term is the same pair term on the identity action map
     ident = (obs_src.numpy(), obs_sign.numpy(), np.arange(A), np.ones(A))
     _assert_same(step_gradients_f64(record, _make_model, ALG, extra=("smoothness", coef)), step_gradients_f64(record, _make_model, ALG, extra=("symmetry", coef, ident)))
+
+
+def test_recurrent_step_gradients_reproduce_the_reference_loop_on_the_restated_model():
+    """The reference's loop (oracle/ppo_ref.py, unedited) on _Restated -- the cell over the T steps from h0, a zero state behind a reset, the trunk on
+    every state -- against step_gradients_f64 on a hand-built record with h0 and resets.  Without back-propagation through time the cell's recurrent
+    weights get another gradient."""
+    from booster_gym_amd.utils.model import ActorCritic
+    from test_gpu_actor_memory import _Restated
+
+    H = 128
+    make = lambda: ActorCritic(A, NO, NP, WIDTHS, WIDTHS, memory_hidden=H)
+    g = torch.Generator().manual_seed(5)
+    rn = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
+    torch.manual_seed(5)
+    model = make().double()
+    with torch.no_grad():
+        model.logstd.copy_(torch.linspace(-1.0, 0.2, A).view(1, A))
+        model.actor[-1].bias.add_(1.2)
+    obses, priv, last_obs, last_priv, actions, rewards = rn(T, N, NO), rn(T, N, NP), rn(N, NO), rn(N, NP), rn(T, N, A), rn(T, N)
+    h0 = rn(N, H) * 0.5
+    dones, time_outs = torch.zeros(T, N, dtype=torch.bool), torch.zeros(T, N, dtype=torch.bool)
+    dones[1, 2] = dones[0, 5] = time_outs[1, 6] = time_outs[2, 0] = True
+    resets = torch.zeros(T, N, dtype=torch.uint8)
+    resets[0, 3] = resets[0, 4] = 1                      # (step 0: the done flags of the iteration before)
+    resets[1:] = (dones | time_outs)[: T - 1].to(torch.uint8)  # an env that ended enters its next step with a zero state
+    assert bool(resets[1:].any()) and not bool(resets.all())
+    params = {k: p.detach().clone() for k, p in model.named_parameters()}
+    rec = {}
+    ppo_update_reference(_Restated(model, h0, resets), torch.optim.Adam(model.parameters(), lr=1e-5), obses, priv, actions, rewards.clone(), dones, time_outs, last_obs,
+                         last_priv, mini_epochs=1, record=rec)
+    assert any(not torch.equal(p, params[k]) for k, p in model.named_parameters())
+    start = make().double()
+    start.load_state_dict(params)
+    B = T * N
+    with torch.no_grad():
+        old_logp = _Restated(start, h0, resets).act(obses).log_prob(actions).sum(-1).reshape(B)
+    record = dict(params=params, x_c=_padded(torch.cat((obses, priv), -1).reshape(B, NO + NP), 16), x_a=_padded(obses.reshape(B, NO), 16), actions=actions.reshape(B, A),
+                  old_logp=old_logp, adv=rec["raw_adv"].reshape(B), ret=rec["returns"].reshape(B), rows=B, adv_all=rec["raw_adv"].clone(), h0=h0, resets=resets)
+    aux = {}
+    got = step_gradients_f64(record, make, ALG, aux=aux)
+    assert {"memory.weight_ih", "memory.weight_hh", "memory.bias_ih", "memory.bias_hh"} <= set(got)
+    _assert_same(got, rec["grads"])
+    assert np.allclose((aux["value_loss"], aux["actor_loss"], aux["bound_loss"], aux["entropy"]), rec["losses"], rtol=1e-12, atol=0)
+    # no back-propagation through time is another gradient of the recurrent weights (and the same one of the critic)
+    cut = step_gradients_f64(record, make, ALG, bptt=False)
+    k = "memory.weight_hh"
+    assert (cut[k] - rec["grads"][k]).abs().max().item() > 1e-2 * rec["grads"][k].abs().max().item()
+    assert torch.equal(cut["critic.0.weight"], got["critic.0.weight"])
+    # a recurrent record against a feed-forward model is refused (the parameters do not load)
+    try:
+        step_gradients_f64(record, _make_model, ALG)
+    except (AssertionError, RuntimeError):
+        pass
+    else:
+        raise AssertionError("a recurrent record went through a feed-forward model")

@@ -22,6 +22,8 @@ def record_steps(runner):
       x_c, x_a  the critic's rows [rows][padded width], the actor's rows (2 x rows with a pair loss: the batch, then the partners)
       actions, old_logp, adv, ret, rows   the step's per-row streams (adv: raw) and the number of rows its loss is a mean over
       adv_all   the whole batch's raw advantages (the moments the step normalises with are the whole batch's)
+      h0, resets   a recurrent actor only (v.mem is not None): the state [envs][H] the step's recurrence starts from and its reset flags uint8 [T][envs]
+                   (an env-wise mini-batch: the gathered ones of its envs); x_a then holds the cell's padded rows [T envs][64], step-major
       grads     {name: clone} of the parameters' .grad views of FlatAdam.grad behind the step: the fused tails finish the weight gradients and write
                 the log-std slice inside the launch, and no form of the step stores the clipped gradient back, so this is the complete unclipped one
       clip_sqnorm   the squared norm the clip divided by where the form leaves it readable (the separate launches: FlatAdam._gnorm; bg_update_tail:
@@ -39,6 +41,8 @@ def record_steps(runner):
         B, plan, opt = v.rows, v.plan, runner.optimizer
         rec = dict(params={k: p.detach().clone() for k, p in named()}, x_c=v.x_c[:B].clone(), x_a=v.x_a.clone(), actions=v.actions.clone(),
                    old_logp=v.old_logp.clone(), adv=v.adv.clone(), ret=v.ret.clone(), rows=B, adv_all=runner._adv.clone(), plan=plan)
+        if v.mem is not None:
+            rec.update(h0=v.mem.h0.clone(), resets=v.mem.resets.clone())
         fused, one_tail = plan.fused_opt and not runner._lr_restart, plan.one_tail and not runner._lr_restart
         inner(u, v)
         rec["grads"] = {k: p.grad.clone() for k, p in named()}
@@ -61,14 +65,28 @@ def record_steps(runner):
 
 
 def model_factory(runner):
-    """make_model for a runner's feed-forward ActorCritic: the constructor call Runner.__init__ makes."""
+    """make_model for a runner's ActorCritic, with the cell of a recurrent actor: the constructor call Runner.__init__ makes."""
     from booster_gym_amd.utils.model import ActorCritic
 
-    env = runner.env
-    return lambda: ActorCritic(env.num_actions, env.num_obs, env.num_privileged_obs, runner.actor_hidden, runner.critic_hidden)
+    env, memory = runner.env, getattr(runner, "_memory", 0)
+    return lambda: ActorCritic(env.num_actions, env.num_obs, env.num_privileged_obs, runner.actor_hidden, runner.critic_hidden, memory_hidden=memory)
 
 
-def step_gradients_f64(record, make_model, alg, extra=None, *, dtype=torch.float64, unbiased=True, aux=None):
+def recurrent_means(model, x_a, h0, resets, bptt=True):
+    """The actor's means [T envs][12] of a recurrent model on the cell's rows x_a [T envs][47], step-major: the cell over the T steps from h0 [envs][H]
+    with a zero state behind a reset (resets [T][envs]), the trunk on every state.  bptt = False detaches the state between steps: no
+    back-propagation through time, a WRONG gradient for sensitivity controls."""
+    T, n = resets.shape
+    x, h, mus = x_a.reshape(T, n, -1), h0, []
+    for t in range(T):
+        h = model.memory(x[t], h * (1 - resets[t].to(h0.dtype)).view(n, 1))
+        mus.append(model.actor(h))
+        if not bptt:
+            h = h.detach()
+    return torch.cat(mus)
+
+
+def step_gradients_f64(record, make_model, alg, extra=None, *, dtype=torch.float64, unbiased=True, aux=None, bptt=True):
     """The gradient of the step's loss at the recorded parameters, by torch autograd: the loss written out as oracle/ppo_ref.py:52-58 writes it.
       value term      mse(critic(x_c[:, :k_c]), ret)
       surrogate term  surrogate_loss on exp(logp - old_logp) with the recorded fp32 old_logp and the advantages (adv - mean) / (std + 1e-8), the
@@ -81,11 +99,16 @@ def step_gradients_f64(record, make_model, alg, extra=None, *, dtype=torch.float
     The networks read the first in_features columns of x_c / x_a; the padding columns must be zero.  make_model() builds the ActorCritic, which
     is cast to `dtype` and loaded with the recorded parameters.  dtype = torch.float32: the same loss as torch's own fp32 autograd computes it (the
     moments still in float64).  unbiased = False: the population std, a WRONG reference for sensitivity controls.  aux: a dict that receives
-    "ratio" (the rows' probability ratios) and the loss terms.  Returns {name: gradient} in `dtype`."""
+    "ratio" (the rows' probability ratios) and the loss terms.  Returns {name: gradient} in `dtype`.
+    A record with h0 / resets (a recurrent actor): x_a is read as [T][envs][padded 64], the means are recurrent_means' -- the cell over the T steps from
+    h0, a zero state behind a reset, the trunk on every state -- and every loss line is the same (bptt: recurrent_means').  A feed-forward record
+    takes the path it always took."""
     B, dev = record["rows"], record["x_c"].device
     model = make_model().to(device=dev, dtype=dtype)
     model.load_state_dict({k: v.to(dtype) for k, v in record["params"].items()})
-    k_c, k_a = model.critic[0].in_features, model.actor[0].in_features
+    recurrent = "h0" in record
+    assert recurrent == bool(getattr(model, "memory_hidden", 0)) and not (recurrent and extra is not None)
+    k_c, k_a = model.critic[0].in_features, model.memory.input_size if recurrent else model.actor[0].in_features
     x_c, x_a = record["x_c"], record["x_a"]
     assert x_c.shape[0] == B and x_a.shape[0] == (2 * B if extra is not None else B), (tuple(x_c.shape), tuple(x_a.shape), B)
     assert not x_c[:, k_c:].any() and not x_a[:, k_a:].any(), "the padding columns of the network inputs must be zero"
@@ -96,7 +119,7 @@ def step_gradients_f64(record, make_model, alg, extra=None, *, dtype=torch.float
         advantages = ((record["adv"].double() - adv_all.mean()) / (adv_all.std(unbiased=unbiased) + 1e-8)).to(dtype)
     values = model.critic(x_c).squeeze(-1)
     value_loss = F.mse_loss(values, ret)
-    mean = model.actor(x_a[:B])
+    mean = recurrent_means(model, x_a, record["h0"].to(dtype), record["resets"], bptt) if recurrent else model.actor(x_a[:B])
     dist = torch.distributions.Normal(mean, torch.exp(model.logstd).expand_as(mean))
     actions_log_prob = dist.log_prob(actions).sum(dim=-1)
     actor_loss = surrogate_loss(old_logp, actions_log_prob, advantages)
