@@ -6,7 +6,10 @@
 //     column i.  At 9 x 32 cycles per 32 x 32 x 16 block a 128 x 128 tile per wave needs its rows 1.8 x faster than the fp32 form, which already
 //     sat on the flop / byte ridge with every wave fetching its own rows: so here the waves of a workgroup that work on the SAME rows (all tiles of
 //     a layer: 256 x 256 = 4 tiles, 128 x 256 = 2, ...) share them.  Each 16-row block of G and A (one contiguous span of the row-major arrays) is
-//     copied ONCE per workgroup into LDS by global_load_lds_dwordx4, two blocks ahead of its use, and every wave picks its operands out of LDS.
+//     copied ONCE per workgroup into LDS by buffer_load_dwordx4 ... lds, two blocks ahead of its use, and every wave picks its operands out of LDS.
+//     A wave's pieces of that copy (1 KB each) are DEALT over the MFMAs of the block that runs meanwhile, one behind the first MFMA of a tile group
+//     (CopySchedule): as a burst behind the block's barrier, where no MFMA of the CU is in flight, issuing them took 9 - 24 % of a block
+//     (tools/wgrad_split_stamps.py, profiles/wgrad_copies_time.txt).
 //   * The split runs in the shadow of the MFMAs: while block b is multiplied, the planes of block b + 1 are built two floats at a time (one
 //     row pair of one tile: 11 VALU, 2 ds_read_b32) between the MFMAs -- an MFMA holds the issue port 8 of its 32 cycles.  Planes are
 //     double-buffered in registers (2 x 96), the 256 accumulators live in the AGPR half of the file.
@@ -17,12 +20,14 @@
 #include <type_traits>
 
 #include "bg_wgrad.h"
+#include "bg_stamps.h"
 
 constexpr int WS_BLOCK = 16;                  // batch rows per MFMA step
 constexpr int WS_LDS_FLOATS = 36864;          // 144 KB: three buffers of row blocks where they fit (two for the 128 x 128 layer), reused by the reduction (128 KB)
 // one block of zeros in device memory: the source of the copies a sub-range asks for past its end (sub-ranges of a workgroup may differ by one pair of
 // blocks and all waves keep the same schedule of copies, barriers and MFMAs: the extra blocks multiply zeros)
 __device__ float ws_zero_block[WS_BLOCK * 512];
+BG_STAMP_BUFFER(bg_wgrad_split_stamp_buf, bg_probe_read_wgrad_split_stamps, 1024, 5)  // tools/wgrad_split_stamps.py: [workgroup][wave][slot], cycles summed over the blocks: 0 wait + barrier, 1 copy issue, 2 block loop, 3 epilogue; 4: the loop in wall-clock ticks
 
 // (x0, x1) -> one dword (low half = x0) of each of the three planes
 struct Pair3 { unsigned h, m, l; };
@@ -68,8 +73,11 @@ __device__ __forceinline__ void split_op(int o, SplitUnit (&s)[4], const float (
         default: out[k].l = __builtin_amdgcn_perm(__float_as_uint(q.r1), __float_as_uint(q.r0), 0x07060302u); break;
     }
 }
-template <int TERMS, int NU>
-__device__ __forceinline__ void tile_mfmas(f32x16& acc, const u32x4 (&g)[3], const u32x4 (&a)[3], const float (&x)[4], const float (&y)[4], Pair3 (&o)[4], unsigned sgn) {
+// pj >= 0: piece pj of the workgroup's LDS copy (copy(pj): one 1 KB direct-to-LDS load) is issued behind the group's FIRST MFMA, the gap with the
+// fewest fillers (2 or 3 of the 11 NU)
+template <int TERMS, int NU, class Copy>
+__device__ __forceinline__ void tile_mfmas(f32x16& acc, const u32x4 (&g)[3], const u32x4 (&a)[3], const float (&x)[4], const float (&y)[4], Pair3 (&o)[4], unsigned sgn,
+                                           int pj, Copy copy) {
     // cross terms, small first: (g plane, a plane); the last 6 are the 6-term set
     constexpr int GP[9] = {2, 1, 2, 0, 1, 2, 0, 1, 0}, AP[9] = {2, 2, 1, 2, 1, 0, 1, 0, 0};
     constexpr int NOPS = 11 * NU;
@@ -78,6 +86,7 @@ __device__ __forceinline__ void tile_mfmas(f32x16& acc, const u32x4 (&g)[3], con
     for (int m = 0; m < TERMS; m++) {
         const int term = 9 - TERMS + m;
         BG_MFMA(acc, g[GP[term]], a[AP[term]]);
+        if (m == 0 && pj >= 0) copy(pj);
 #pragma unroll
         for (int op = (m * NOPS) / TERMS; op < ((m + 1) * NOPS) / TERMS; op++) {
             split_op<NU == 0 ? 1 : NU>(op, s, x, y, o, NU - 1, sgn);  // (units 0 .. NU - 2: G's; the last: A's)
@@ -85,6 +94,28 @@ __device__ __forceinline__ void tile_mfmas(f32x16& acc, const u32x4 (&g)[3], con
         BG_PIN();
     }
 }
+
+// Where a wave issues its N pieces of the copy of block c + NBUF during block c: at most one behind the first MFMA of a tile group (g = t * TCI + u),
+// the rest as a burst at the block's top.  Groups u = 0 start with the row's four LDS reads and are taken last; with two buffers the copy is waited
+// for in full at the next block's top, so only the first two tile rows carry pieces (the later ones would have no cover).
+template <int TCI, int N, int NBUF>
+struct CopySchedule {
+    static constexpr int NG = 4 * TCI, USABLE = NBUF >= 3 ? NG : NG / 2, DEALT = N < USABLE ? N : USABLE, BURST = N - DEALT;
+    static constexpr int cls(int g) { return g % TCI == 0 ? 2 : (g % TCI) & 1 ? 0 : 1; }
+    static constexpr bool dealt(int g) {
+        if (g >= USABLE) return false;
+        int rank = 0;
+        for (int o = 0; o < USABLE; o++) rank += cls(o) < cls(g) || (cls(o) == cls(g) && o < g);
+        return rank < DEALT;
+    }
+    // the piece behind group g's first MFMA (-1: none); pieces 0 .. BURST - 1 are the burst's
+    static constexpr int piece(int g) {
+        if (!dealt(g)) return -1;
+        int j = BURST;
+        for (int o = 0; o < g; o++) j += dealt(o);
+        return j;
+    }
+};
 
 // A workgroup's 4 waves cover tw output tiles x ks = 4 / tw sub-ranges of the slice's rows (bg_wgrad.hip's wgrad_tile); the tw waves of one
 // sub-range share its rows through LDS.  TCI: 32-column C_in tiles per wave (4: 128 input columns, 2: the 64-wide zero-padded first layers).
@@ -96,6 +127,7 @@ __device__ __forceinline__ void wgrad_split_tile(float* lds, int M, const float*
     constexpr int TCI = Cin == 64 ? 2 : 4;
     constexpr int UPG = 4 / TCI;  // row pairs handled per (t, u) group for each operand: 4 pairs per tile operand over TCI groups
     typedef float avec __attribute__((ext_vector_type(TCI)));
+    BG_STAMP_LOCALS(5);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
     const int ks = 4 / tw, tl = wave % tw, ksub = wave / tw, tile = tile0 + tl;
     const int tco = tile / ntile_ci, tci = tile % ntile_ci;
@@ -111,22 +143,33 @@ __device__ __forceinline__ void wgrad_split_tile(float* lds, int M, const float*
     constexpr int gfl = WS_BLOCK * Cout, afl = WS_BLOCK * Cin, grp_fl = gfl + afl;
     const int buf_fl = ks * grp_fl;
     float* my0 = lds + ksub * grp_fl;  // this group's block in buffer 0 (buffer n: + n * buf_fl)
-    // NBUF buffers: the copy of block c + NBUF is started at the top of block c, NBUF - 1 blocks before its first use
+    // NBUF buffers: the copy of block c + NBUF is issued during block c (Sched: a burst at its top, the rest behind its MFMAs), NBUF - 1 blocks before its first use
     constexpr int NT = (Cout / 128) * (Cin >= 128 ? Cin / 128 : 1), KS = 4 / NT, NBUF = 3 * KS * grp_fl <= WS_LDS_FLOATS ? 3 : 2;  // (four and five buffers in 160 KB: measured no faster, round 6)
     // this wave's share of the group's copy: wave-instructions (1 KB each) q = tl, tl + tw, ... of the block's (gfl + afl) / 256
     constexpr int n_inst = grp_fl / 256, N_MINE = n_inst / NT;
     static_assert(n_inst % NT == 0, "every wave of a group issues the same number of copies");
-    auto stage = [&](int blk) {  // blk relative to b0; past the end of the sub-range: zeros
-        const bool real = blk < nb;
-        const float* gsrc = real ? G + (size_t)(b0 + blk) * gfl : ws_zero_block;
-        const float* asrc = real ? A + (size_t)(b0 + blk) * afl : ws_zero_block;
-        float* dst = my0 + (blk % NBUF) * buf_fl;
+    constexpr int NG_MINE = gfl / 256 / NT;  // pieces 0 .. NG_MINE - 1 are G's, the others A's
+    static_assert((gfl / 256) % NT == 0, "a wave's piece j is G's or A's for every wave of the group");
+    using Sched = CopySchedule<TCI, N_MINE, NBUF>;
+    // The copies are buffer loads to LDS: the sub-range's rows of G and A and the zero block as three resources in scalar registers (a wrong offset
+    // reads zeros), the piece's place as a scalar offset, the LDS address in M0, and ONE vector register (16 bytes per lane) for all of them.
+    const int sub_bytes = nb * WS_BLOCK * 4;
+    const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(G + (size_t)b0 * gfl), 0, sub_bytes * Cout, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A + (size_t)b0 * afl), 0, sub_bytes * Cin, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_z = __builtin_amdgcn_make_buffer_rsrc(ws_zero_block, 0, (int)sizeof(ws_zero_block), 0x00020000);
+    const int lane16 = lane * 16;
+    // piece j of block blk (relative to b0; past the end of the sub-range: zeros); j is a compile-time constant at every call site
+    auto piece = [&](int blk, int j) {
+        const bool real = blk < nb, is_g = j < NG_MINE;
+        const int q = tl + j * NT;  // the piece's 1 KB inside the group's block (wave-uniform)
+        const int in_op = is_g ? q * 1024 : q * 1024 - gfl * 4;
+        const int soff = real ? blk * ((is_g ? gfl : afl) * 4) + in_op : in_op;
+        float* dst = my0 + (blk % NBUF) * buf_fl + q * 256;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(real ? (is_g ? rs_g : rs_a) : rs_z, (__attribute__((address_space(3))) void*)dst, 16, lane16, soff, 0, 0);
+    };
+    auto stage = [&](int blk) {
 #pragma unroll
-        for (int j = 0; j < N_MINE; j++) {
-            const int f = (tl + j * NT) * 256;  // float offset of this instruction inside the group's block (wave-uniform)
-            const float* src = f < gfl ? gsrc + f : asrc + (f - gfl);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + lane * 4), (__attribute__((address_space(3))) void*)(dst + f), 16, 0, 0);
-        }
+        for (int j = 0; j < N_MINE; j++) piece(blk, j);
     };
     // LDS float index of this lane's operands inside a group's block: G row r, tile t: r * Cout + tco * 128 + 4 i + t; A row r, tile u: gfl + r * Cin + ...
     const int gofs = (8 * h) * Cout + tco * 128 + 4 * i, aofs = gfl + (8 * h) * Cin + tci * (32 * TCI) + TCI * i;
@@ -160,7 +203,7 @@ __device__ __forceinline__ void wgrad_split_tile(float* lds, int M, const float*
     // In row t of the tile grid the NEXT block's row pair t (rows 8 h + 2 t, + 1 of the lane's half) is split for all tiles: the lane's four G floats
     // (one per tile) and TCI A floats of a row come as ONE 16- / 8-byte LDS read each (4-byte reads of this pattern are 4-way bank conflicts and
     // four times as many), and are consumed within the row.
-    auto block = [&](auto cur_c, const float* src) {
+    auto block = [&](auto cur_c, const float* src, int cblk) {  // cblk: the block whose copy is dealt over this one's tile groups
         constexpr int CUR = decltype(cur_c)::value, NXT = 1 - CUR;
         // the lane's four G floats and TCI A floats of a row pair, read ONE ROW PAIR AHEAD of their use (round 2 had no registers for this -- 16 more and
         // the kernel spilled; it fits since the split's first step carries its values in the unit's own registers: 232 of 256): 320 -> 308 us
@@ -185,7 +228,7 @@ __device__ __forceinline__ void wgrad_split_tile(float* lds, int M, const float*
                 for (int k = 0; k < UPG; k++) { x[k] = g0[u * UPG + k]; y[k] = g1[u * UPG + k]; }
                 x[UPG] = a0[u]; y[UPG] = a1[u];
                 BG_PIN();
-                tile_mfmas<TERMS, UPG + 1>(acc[t][u], gp[CUR][t], ap[CUR][u], x, y, o, sgn);
+                tile_mfmas<TERMS, UPG + 1>(acc[t][u], gp[CUR][t], ap[CUR][u], x, y, o, sgn, Sched::piece(t * TCI + u), [&](int j) { piece(cblk, j); });
 #pragma unroll
                 for (int k = 0; k < UPG; k++) set_dword(gp[NXT][u * UPG + k], t, o[k]);
                 set_dword(ap[NXT][u], t, o[UPG]);
@@ -198,11 +241,18 @@ __device__ __forceinline__ void wgrad_split_tile(float* lds, int M, const float*
     // MFMAs (peeled tails made the register allocator pass accumulators through scratch): a sub-range is an even number of blocks, and the last
     // block of a sub-range builds planes nobody uses from whatever the other buffer holds.
     // top of block c: its successor's rows (copy started NBUF - 1 blocks ago) must have landed -- a COUNTED wait, the younger copies stay in flight
-    // (raw s_barrier: __syncthreads() would drain them) -- then everybody is done with buffer c % NBUF and the copy of block c + NBUF goes there
+    // (raw s_barrier: __syncthreads() would drain them) -- then everybody is done with buffer c % NBUF and the copy of block c + NBUF may go there: the
+    // schedule's burst here, its other pieces from block c's tile groups
     auto top = [&](int c) {
+        BG_PIN();  // (the top is a scheduling region of its own: with the block's reads and splits moved into it the 128 x 128 shape spilled)
+        BG_STAMP_OPEN(0);
         __builtin_amdgcn_s_waitcnt(0x0F70 | ((NBUF - 2) * N_MINE & 15) | (((NBUF - 2) * N_MINE >> 4) << 14));
         __builtin_amdgcn_s_barrier();
-        stage(c + NBUF);
+        BG_STAMP_TURN(0, 1);
+#pragma unroll
+        for (int j = 0; j < Sched::BURST; j++) piece(c + NBUF, j);
+        BG_STAMP_CLOSE(1);
+        BG_PIN();
     };
     int nbmax = 0;
     for (int c = 0; c < ks; c++) {
@@ -210,12 +260,16 @@ __device__ __forceinline__ void wgrad_split_tile(float* lds, int M, const float*
         const int len = 2 * (int)(NB2 * (wc + 1) / W) - 2 * (int)(NB2 * wc / W);
         nbmax = len > nbmax ? len : nbmax;
     }
+    BG_STAMP_WALL_OPEN(4);
+    BG_STAMP_OPEN(2);
     for (int b = 0; b < nbmax; b += 2) {
         top(b);
-        block(c0{}, my0 + ((b + 1) % NBUF) * buf_fl);
+        block(c0{}, my0 + ((b + 1) % NBUF) * buf_fl, b + NBUF);
         top(b + 1);
-        block(c1{}, my0 + ((b + 2) % NBUF) * buf_fl);
+        block(c1{}, my0 + ((b + 2) % NBUF) * buf_fl, b + 1 + NBUF);
     }
+    BG_STAMP_TURN(2, 3);
+    BG_STAMP_WALL_CLOSE(4);
     __builtin_amdgcn_s_waitcnt(0x0F70);  // the copies past the end (zeros) must not land in the reduction buffer
     __syncthreads();
     // In-workgroup reduction and store: as bg_wgrad.hip's wgrad_tile (C layout of a 32 x 32 tile: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 h;
@@ -249,6 +303,8 @@ __device__ __forceinline__ void wgrad_split_tile(float* lds, int M, const float*
             *reinterpret_cast<avec*>(pt + (size_t)(4 * row + t) * Cin) = v;
         }
     }
+    BG_STAMP_CLOSE(3);
+    BG_STAMP_FLUSH(bg_wgrad_split_stamp_buf, 5, blockIdx.x < 1024, blockIdx.x);
 }
 
 template <int TERMS>
