@@ -89,6 +89,18 @@ class GruDesc(C.Structure):
     _fields_ = [("W_ih", C.c_void_p), ("W_hh", C.c_void_p), ("b_ih", C.c_void_p), ("b_hh", C.c_void_p), ("in_", C.c_int32), ("hidden", C.c_int32)]
 
 
+class GruForwardProblem(C.Structure):
+    """bg_gru_forward_problem: one recurrence of bg_gru_sequence_forward_group, the arguments of bg_gru_sequence_forward (include/booster_gym_amd.h)."""
+    _fields_ = [("T", C.c_int32), ("N", C.c_int32), ("gi", C.c_void_p), ("h0", C.c_void_p), ("reset", C.c_void_p), ("W_hh", C.c_void_p), ("b_hh", C.c_void_p),
+                ("h_prev", C.c_void_p), ("h", C.c_void_p), ("gates", C.c_void_p)]
+
+
+class GruBackwardProblem(C.Structure):
+    """bg_gru_backward_problem: one recurrence of bg_gru_sequence_backward_group, the arguments of bg_gru_sequence_backward."""
+    _fields_ = [("T", C.c_int32), ("N", C.c_int32), ("dh_ext", C.c_void_p), ("gates", C.c_void_p), ("h_prev", C.c_void_p), ("reset", C.c_void_p),
+                ("W_hh", C.c_void_p), ("dgi", C.c_void_p), ("dgh", C.c_void_p), ("dh0", C.c_void_p)]
+
+
 class GatherStream(C.Structure):
     """bg_gather_stream: one row-major fp32 stream of bg_gather_rows (include/booster_gym_amd.h)."""
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("width", C.c_int32), ("pad", C.c_int32)]
@@ -184,7 +196,7 @@ SYMBOLS = [
     "bg_obs_moments", "bg_obs_normalize",
     "bg_perm_fill", "bg_gather_rows", "bg_gather_sequences",
     "bg_actor_sample_gru", "bg_distill_act_gru", "bg_gru_sequence_forward", "bg_gru_sequence_backward",
-    "bg_gru_bias_partial",
+    "bg_gru_bias_partial", "bg_gru_sequence_forward_group", "bg_gru_sequence_backward_group",
     "bg_last_error", "bg_version",
 ]
 
@@ -260,6 +272,8 @@ def load():
         "bg_gru_sequence_forward": (i32, [i32, i32, i32] + [vp] * 9),
         "bg_gru_sequence_backward": (i32, [i32, i32, i32] + [vp] * 9),
         "bg_gru_bias_partial": (i32, [i32, i32, vp, vp, vp, vp]),
+        "bg_gru_sequence_forward_group": (i32, [C.POINTER(GruForwardProblem), i32, i32, vp]),
+        "bg_gru_sequence_backward_group": (i32, [C.POINTER(GruBackwardProblem), i32, i32, vp]),
         "bg_adam_step": (i32, [i32, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, vp, vp]),
         "bg_adapt_lr": (i32, [vp, f32, f32, f32, f32, vp, vp]),
         "bg_optimizer_step": (i32, [i32, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, vp, i32, i32, vp, vp, vp, i32, i32, f32, f32, f32, f32, vp, vp, i32, vp]),

@@ -39,13 +39,14 @@ constexpr int MR = 16;  // envs per workgroup
         ACC1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, WV[u + 1].w, ACC1, 0, 0, 0);                                                  \
     }
 
+// The forward recurrence of the 16 envs [16 block, 16 block + 16) of one problem: the one body of bg_gru_sequence_forward's kernel (block = blockIdx.x)
+// and of the grouped launch's (block = the workgroup's place among its problem's).
 template <int H>
-__global__ __launch_bounds__(256) void gru_sequence_forward_kernel(int T, int N, const float* __restrict__ gi, const float* __restrict__ h0,
-                                                                   const uint8_t* __restrict__ reset, const float* __restrict__ W, const float* __restrict__ bh,
-                                                                   float* __restrict__ h_prev, float* __restrict__ h, float* __restrict__ gates) {
+__device__ __forceinline__ void gru_sequence_forward_body(float (&tile)[2][MR * (H + 4)], unsigned block, int T, int N, const float* __restrict__ gi, const float* __restrict__ h0,
+                                                          const uint8_t* __restrict__ reset, const float* __restrict__ W, const float* __restrict__ bh,
+                                                          float* __restrict__ h_prev, float* __restrict__ h, float* __restrict__ gates) {
     constexpr int LDH = H + 4, TPW = H / 64, CPT = H / 128;  // row stride of the state tiles; column tiles per wave; 128-wide k-chunks
-    __shared__ __attribute__((aligned(16))) float tile[2][MR * LDH];
-    const int r0 = blockIdx.x * MR, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, kg = lane >> 4;
+    const int r0 = block * MR, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, kg = lane >> 4;
     for (int k = threadIdx.x; k < MR * H; k += blockDim.x) {
         const int rr = k / H, c = k - rr * H, row = r0 + rr;
         tile[0][rr * LDH + c] = (h0 && row < N) ? h0[(size_t)row * H + c] : 0.f;
@@ -105,7 +106,16 @@ __global__ __launch_bounds__(256) void gru_sequence_forward_kernel(int T, int N,
                 else if (jt + 1 < TPW) fetch(w0, 0, j + 4, 0);
                 BG_GRU_MFMA32(acc[2][0], acc[2][1], arow, w2)
             }
-            const f32x4 ghr = acc[0][0] + acc[0][1], ghz = acc[1][0] + acc[1][1], ghn = acc[2][0] + acc[2][1];
+            // gh = acc0 + acc1 first, then gru_gates adds gi: (acc0 + acc1) + gi, the association bg_gru_sequence_forward has always run.  Under this
+            // file's -fassociative-math the optimiser is free to split the sum as (acc0 + gi) + acc1, and whether it does depends on the code around
+            // the body (it did once the body was a function); a sum without the reassociation flag cannot be taken apart
+            f32x4 ghr, ghz, ghn;
+            {
+#pragma clang fp reassociate(off)
+                ghr = acc[0][0] + acc[0][1];
+                ghz = acc[1][0] + acc[1][1];
+                ghn = acc[2][0] + acc[2][1];
+            }
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 const int rr = kg * 4 + q, row = r0 + rr;
@@ -124,14 +134,21 @@ __global__ __launch_bounds__(256) void gru_sequence_forward_kernel(int T, int N,
 }
 
 template <int H>
-__global__ __launch_bounds__(256) void gru_sequence_backward_kernel(int T, int N, const float* __restrict__ dh_ext, const float* __restrict__ gates,
-                                                                    const float* __restrict__ h_prev, const uint8_t* __restrict__ reset,
-                                                                    const float* __restrict__ W, float* __restrict__ dgi, float* __restrict__ dgh,
-                                                                    float* __restrict__ dh0) {
+__global__ __launch_bounds__(256) void gru_sequence_forward_kernel(int T, int N, const float* __restrict__ gi, const float* __restrict__ h0,
+                                                                   const uint8_t* __restrict__ reset, const float* __restrict__ W, const float* __restrict__ bh,
+                                                                   float* __restrict__ h_prev, float* __restrict__ h, float* __restrict__ gates) {
+    __shared__ __attribute__((aligned(16))) float tile[2][MR * (H + 4)];
+    gru_sequence_forward_body<H>(tile, blockIdx.x, T, N, gi, h0, reset, W, bh, h_prev, h, gates);
+}
+
+// ... and the backward recurrence of those envs, likewise the one body of both launches.
+template <int H>
+__device__ __forceinline__ void gru_sequence_backward_body(float (&gt)[MR * (3 * H + 4)], float (&carry)[MR * (H + 4)], unsigned block, int T, int N, const float* __restrict__ dh_ext, const float* __restrict__ gates,
+                                                           const float* __restrict__ h_prev, const uint8_t* __restrict__ reset,
+                                                           const float* __restrict__ W, float* __restrict__ dgi, float* __restrict__ dgh,
+                                                           float* __restrict__ dh0) {
     constexpr int LDH = H + 4, LDG = 3 * H + 4, TPW = H / 64, CPT = 3 * H / 128;
-    __shared__ __attribute__((aligned(16))) float gt[MR * LDG];     // dgh of the step: the GEMM's A operand
-    __shared__ __attribute__((aligned(16))) float carry[MR * LDH];  // dh carried to the step below
-    const int r0 = blockIdx.x * MR, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, kg = lane >> 4;
+    const int r0 = block * MR, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, kg = lane >> 4;
     for (int k = threadIdx.x; k < MR * LDH; k += blockDim.x) carry[k] = 0.f;
     __syncthreads();
     // the 32 weights of column tile j, k-chunk c for this lane: W_hh[128 c + 16 u + 4 kg + e][16 j + r], u = 0 .. 7, e = 0 .. 3
@@ -164,14 +181,19 @@ __global__ __launch_bounds__(256) void gru_sequence_backward_kernel(int T, int N
             const int k = threadIdx.x + 256 * e, rr = k / H, c = k - rr * H, row = r0 + rr;
             float dr_pre = 0.f, dz_pre = 0.f, dn_pre = 0.f, dn_r = 0.f, dhz = 0.f;
             if (row < N) {
+                // dn = dh (1 - z), dz = dh (h_prev - n), dn_pre = dn (1 - n^2), dz_pre = dz z (1 - z), dr_pre = dn_pre gh_n r (1 - r), each product and each
+                // fused multiply-add written out and nothing left to contract or reassociate: which of the equivalent forms the compiler picks depends
+                // on the code around the body.  These are the forms bg_gru_sequence_backward has always run (x (1 - y) as x - y x in one rounding), so
+                // the single launch keeps its bits and the grouped one has the same
+#pragma clang fp contract(off) reassociate(off)
                 const float dh = in[e][0] + carry[rr * LDH + c];
                 const float gr = in[e][1], gz = in[e][2], gn = in[e][3], ghn = in[e][4], hp = in[e][5];
-                const float dn = dh * (1.0f - gz), dz = dh * (hp - gn);
-                dn_pre = dn * (1.0f - gn * gn);
-                dz_pre = dz * gz * (1.0f - gz);
-                dr_pre = dn_pre * ghn * gr * (1.0f - gr);
+                const float dn = __builtin_fmaf(-gz, dh, dh);
+                dhz = gz * dh;
+                dn_pre = __builtin_fmaf(-(gn * gn), dn, dn);
+                dz_pre = __builtin_fmaf(-gz, dhz, dhz) * (hp - gn);
                 dn_r = dn_pre * gr;
-                dhz = dh * gz;
+                dr_pre = __builtin_fmaf(-gr, dn_r, dn_r) * ghn;
                 float *a = dgi + (tn + row) * (3 * H) + c, *b = dgh + (tn + row) * (3 * H) + c;
                 a[0] = dr_pre; a[H] = dz_pre; a[2 * H] = dn_pre;
                 b[0] = dr_pre; b[H] = dz_pre; b[2 * H] = dn_r;
@@ -214,6 +236,105 @@ __global__ __launch_bounds__(256) void gru_sequence_backward_kernel(int T, int N
             if (row < N) dh0[(size_t)row * H + c] = carry[rr * LDH + c];
         }
     }
+}
+
+template <int H>
+__global__ __launch_bounds__(256) void gru_sequence_backward_kernel(int T, int N, const float* __restrict__ dh_ext, const float* __restrict__ gates,
+                                                                    const float* __restrict__ h_prev, const uint8_t* __restrict__ reset,
+                                                                    const float* __restrict__ W, float* __restrict__ dgi, float* __restrict__ dgh,
+                                                                    float* __restrict__ dh0) {
+    __shared__ __attribute__((aligned(16))) float gt[MR * (3 * H + 4)];  // dgh of the step: the GEMM's A operand
+    __shared__ __attribute__((aligned(16))) float carry[MR * (H + 4)];   // dh carried to the step below
+    gru_sequence_backward_body<H>(gt, carry, blockIdx.x, T, N, dh_ext, gates, h_prev, reset, W, dgi, dgh, dh0);
+}
+
+// Several recurrences in ONE grid (bg_gru_sequence_forward_group / _backward_group).  A recurrence is a chain of dependent round trips on one wave per
+// SIMD, so its time hardly depends on its number of envs, and two of them launched one after the other on one stream cost twice that.  Here a workgroup
+// serves one problem through the bodies above (the outputs are the single launches' bit for bit), and the workgroups of the problems ALTERNATE in
+// dispatch order: round r of the grid holds workgroup r of every problem that has one, so that the problems share the CUs from the first workgroups on
+// (two workgroups fit a CU's LDS at every H; two forward waves fit a SIMD's registers, two backward ones do not).  The grouped backward kernel at
+// H = 128 compiles to the whole register file with spills where the single one takes 356 registers: the runner issues the
+// backward recurrences as single launches unless BG_GRU_GROUP=2.
+constexpr int GROUP_MAX = BG_GRU_GROUP_MAX;
+static_assert(GROUP_MAX == 4, "the group kernels select among four problems");
+
+// The problem that workgroup b of such a grid serves, and in `local` its place among that problem's workgroups; nb[p]: the problems' workgroup counts.
+// At most n segments of rounds over a constant set of unfinished problems.  -1 for a b outside the grid (the sum of nb).
+__device__ __forceinline__ int group_block(int nb0, int nb1, int nb2, int nb3, int n, int b, int& local) {
+    const int nb[GROUP_MAX] = {nb0, nb1, nb2, nb3};
+    int r = 0, rem = b;
+#pragma unroll
+    for (int seg = 0; seg < GROUP_MAX; seg++) {
+        int active = 0, next = 0x7fffffff;
+#pragma unroll
+        for (int p = 0; p < GROUP_MAX; p++) {
+            if (p < n && nb[p] > r) {
+                active++;
+                next = min(next, nb[p]);
+            }
+        }
+        if (active == 0) break;
+        const int span = (next - r) * active;
+        if (rem < span) {
+            const int k = rem % active;  // the k-th unfinished problem, in ascending order
+            int found = 0, seen = 0;
+#pragma unroll
+            for (int p = 0; p < GROUP_MAX; p++) {
+                if (p < n && nb[p] > r) {
+                    if (seen == k) found = p;
+                    seen++;
+                }
+            }
+            local = r + rem / active;
+            return found;
+        }
+        rem -= span;
+        r = next;
+    }
+    local = -1;
+    return -1;
+}
+
+// Field F of problem p of the kernel's one argument (a ForwardGroup / BackwardGroup by value, at the start of the kernel-argument segment): read from
+// that segment at a workgroup-uniform offset, a scalar load, so that the pointers live in scalar registers as the single kernels' arguments do
+// (indexing the by-value argument with p makes the compiler copy it to private memory; selecting among the four problems keeps all of them live).
+// This reads offset 0 of the segment: the struct must stay the grouped kernels' ONLY explicit argument, nothing may be placed in front of `g`.
+#define BG_GRU_PICK(GROUP, F) (((const __attribute__((address_space(4))) GROUP*)__builtin_amdgcn_kernarg_segment_ptr())->p[p].F)
+
+struct ForwardGroup {
+    bg_gru_forward_problem p[GROUP_MAX];
+    int nb[GROUP_MAX];
+    int n;
+};
+
+struct BackwardGroup {
+    bg_gru_backward_problem p[GROUP_MAX];
+    int nb[GROUP_MAX];
+    int n;
+};
+static_assert(offsetof(ForwardGroup, p) == 0 && offsetof(BackwardGroup, p) == 0, "BG_GRU_PICK reads the problems at the start of the kernel-argument segment");
+
+template <int H>
+__global__ __launch_bounds__(256) void gru_sequence_forward_group_kernel(const ForwardGroup g) {
+    int local;
+    const int p = group_block(g.nb[0], g.nb[1], g.nb[2], g.nb[3], g.n, blockIdx.x, local);
+    if (p < 0) return;
+#define PICK(F) BG_GRU_PICK(ForwardGroup, F)
+    __shared__ __attribute__((aligned(16))) float tile[2][MR * (H + 4)];
+    gru_sequence_forward_body<H>(tile, local, PICK(T), PICK(N), PICK(gi), PICK(h0), PICK(reset), PICK(W_hh), PICK(b_hh), PICK(h_prev), PICK(h), PICK(gates));
+#undef PICK
+}
+
+template <int H>
+__global__ __launch_bounds__(256) void gru_sequence_backward_group_kernel(const BackwardGroup g) {
+    int local;
+    const int p = group_block(g.nb[0], g.nb[1], g.nb[2], g.nb[3], g.n, blockIdx.x, local);
+    if (p < 0) return;
+#define PICK(F) BG_GRU_PICK(BackwardGroup, F)
+    __shared__ __attribute__((aligned(16))) float gt[MR * (3 * H + 4)];  // dgh of the step: the GEMM's A operand
+    __shared__ __attribute__((aligned(16))) float carry[MR * (H + 4)];   // dh carried to the step below
+    gru_sequence_backward_body<H>(gt, carry, local, PICK(T), PICK(N), PICK(dh_ext), PICK(gates), PICK(h_prev), PICK(reset), PICK(W_hh), PICK(dgi), PICK(dgh), PICK(dh0));
+#undef PICK
 }
 
 // The cell's two bias gradients of the PPO update (algorithm.rnn_hidden_size): the column sums of dgi and dgh [B][3H] as ONE launch that leaves one
@@ -281,6 +402,64 @@ extern "C" int bg_gru_sequence_backward(int32_t T, int32_t N, int32_t H, const f
     hipStream_t st = (hipStream_t)stream;
     if (H == 128) hipLaunchKernelGGL(gru_sequence_backward_kernel<128>, grid, block, 0, st, T, N, dh_ext, gates, h_prev, reset, W_hh, dgi, dgh, dh0);
     else hipLaunchKernelGGL(gru_sequence_backward_kernel<256>, grid, block, 0, st, T, N, dh_ext, gates, h_prev, reset, W_hh, dgi, dgh, dh0);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+namespace {
+
+// The checks both grouped entry points share, before any launch: 1 to GROUP_MAX problems of one supported H.
+int check_group(const char* who, const void* problems, int32_t n_problems, int32_t H) {
+    if (!problems || n_problems < 1) return bg_fail(who, -1, "bad argument (no problem)");
+    if (n_problems > GROUP_MAX) return bg_fail(who, -1, "bad argument (more than 4 problems)");
+    if (H != 128 && H != 256) return bg_fail(who, -4, "unsupported H (128 or 256)");
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int bg_gru_sequence_forward_group(const bg_gru_forward_problem* problems, int32_t n_problems, int32_t H, void* stream) {
+    const char* who = "bg_gru_sequence_forward_group";
+    if (const int rc = check_group(who, problems, n_problems, H)) return rc;
+    ForwardGroup g = {};
+    int blocks = 0;
+    for (int k = 0; k < n_problems; k++) {
+        const bg_gru_forward_problem& q = problems[k];
+        if (const int rc = check_shape(who, q.T, q.N, H)) return rc;
+        if (!q.gi || !q.W_hh || !q.b_hh || !q.h_prev || !q.h || !q.gates) return bg_fail(who, -1, "bad argument (a null pointer)");
+        if (!aligned16(q.W_hh)) return bg_fail(who, -1, "W_hh must be 16-byte aligned");
+        g.p[k] = q;
+        g.nb[k] = (q.N + MR - 1) / MR;
+        blocks += g.nb[k];
+    }
+    g.n = n_problems;
+    const dim3 grid(blocks), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (H == 128) hipLaunchKernelGGL(gru_sequence_forward_group_kernel<128>, grid, block, 0, st, g);
+    else hipLaunchKernelGGL(gru_sequence_forward_group_kernel<256>, grid, block, 0, st, g);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int bg_gru_sequence_backward_group(const bg_gru_backward_problem* problems, int32_t n_problems, int32_t H, void* stream) {
+    const char* who = "bg_gru_sequence_backward_group";
+    if (const int rc = check_group(who, problems, n_problems, H)) return rc;
+    BackwardGroup g = {};
+    int blocks = 0;
+    for (int k = 0; k < n_problems; k++) {
+        const bg_gru_backward_problem& q = problems[k];
+        if (const int rc = check_shape(who, q.T, q.N, H)) return rc;
+        if (!q.dh_ext || !q.gates || !q.h_prev || !q.W_hh || !q.dgi || !q.dgh) return bg_fail(who, -1, "bad argument (a null pointer)");
+        if (!aligned16(q.W_hh)) return bg_fail(who, -1, "W_hh must be 16-byte aligned");
+        g.p[k] = q;
+        g.nb[k] = (q.N + MR - 1) / MR;
+        blocks += g.nb[k];
+    }
+    g.n = n_problems;
+    const dim3 grid(blocks), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (H == 128) hipLaunchKernelGGL(gru_sequence_backward_group_kernel<128>, grid, block, 0, st, g);
+    else hipLaunchKernelGGL(gru_sequence_backward_group_kernel<256>, grid, block, 0, st, g);
     HIP_OK(hipGetLastError());
     return 0;
 }

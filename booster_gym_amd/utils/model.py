@@ -153,12 +153,15 @@ def layer_descriptors(linears):
 class GroupedWeightGrad:
     """All deferred weight gradients of several MLPTrainers in one launch pair (bg_mlp_weight_grad_group)."""
 
+    MAX_PROBLEMS = 8  # layers per launch (csrc/bg_wgrad.h: WG_MAX_PROBLEMS)
+
     def __init__(self, workgroups=None):
         self.workgroups = workgroups or MLPTrainer.WGRAD_WORKGROUPS
         # waves of a workgroup on the same rows, different tiles (plan_wgrad_slices): measured no faster alone (329.6 vs 329.2 us for the six layers) and
         # 0.3 ms slower per update in the loop (4x the partial-tile traffic for the 256 x 256 layer), so the pure split over rows stays the default
         self.share_rows = False
         self._key, self._arr, self._scratch = None, None, None
+        self._more = None  # a second launch, for the problems beyond MAX_PROBLEMS
         self.timed_events = None
 
     def run(self, trainers, split, partial):
@@ -169,6 +172,17 @@ class GroupedWeightGrad:
         probs = [p for tr in trainers for p in tr.pending_wgrad_problems()]
         if not probs:
             return None
+        if len(probs) > self.MAX_PROBLEMS:
+            # more layers than one launch takes (two networks and two cells: 10): the first MAX_PROBLEMS here, the rest in a launch of its own
+            if partial:
+                raise ValueError(f"GroupedWeightGrad: {len(probs)} weight gradients do not fit the one launch whose finish bg_update_tail runs")
+            if self._more is None:
+                self._more = GroupedWeightGrad(self.workgroups)
+            self._launch(probs[: self.MAX_PROBLEMS], split, partial)
+            return self._more._launch(probs[self.MAX_PROBLEMS :], split, partial)
+        return self._launch(probs, split, partial)
+
+    def _launch(self, probs, split, partial):
         key = (split,) + tuple((g.data_ptr(), a.data_ptr(), dw.data_ptr(), g.shape[0], co, ci, cr) for g, a, dw, co, ci, cr in probs)
         if key != self._key:  # buffers are static: built once per form
             rows = probs[0][0].shape[0]
@@ -666,20 +680,30 @@ class GRUTrainer:
     The rollout's side of the state lives here too (rollout_begin / rollout_reset / rollout_end): the one statement of which state the recurrence
     starts from and which env enters which step with a zero state, for Distiller and Runner alike."""
 
-    KIN = 64  # the zero-padded width of the cell's input rows (47 observations)
+    KIN = 64  # the zero-padded width of the cell's input rows by default (47 observations)
 
-    def __init__(self, cell, trunk, T, N, clock=None, bias_partial=False):
+    def __init__(self, cell, trunk, T, N, clock=None, bias_partial=False, kin=None, extra_steps=0):
+        """kin: the zero-padded width of the cell's input rows (pad_input of its real width; default KIN).  extra_steps = E: forward() walks T + E steps,
+        on (T + E) N rows, and backward() differentiates the first T of them (a recurrent critic, algorithm.rnn_critic: the values of the observation
+        after the last step are read, never differentiated)."""
         self.cell, self.trunk, self.T, self.N, self.H = cell, trunk, int(T), int(N), int(cell.hidden_size)
         self.bias_partial = bool(bias_partial)
+        self.kin = int(kin or self.KIN)
+        if self.kin not in INPUT_PADS or self.kin < cell.weight_ih.shape[1]:
+            raise ValueError(f"GRUTrainer: an input of {cell.weight_ih.shape[1]} columns padded to {self.kin} (one of {INPUT_PADS}, at least the cell's input)")
+        self.TF = self.T + int(extra_steps)  # the steps of the forward pass
         B, H, dev = self.T * self.N, self.H, cell.weight_ih.device
-        self.B = B
-        self.copies = WeightCopies([SimpleNamespace(weight=cell.weight_ih)], clock, self.KIN)
+        self.B, BF = B, self.TF * self.N
+        self.BF = BF
+        self.copies = WeightCopies([SimpleNamespace(weight=cell.weight_ih)], clock, self.kin)
         new = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
-        self.gi, self.h_prev, self.h, self.gates = new(B, 3 * H), new(B, H), new(B, H), new(B, 4 * H)
+        self.gi, self.h_prev, self.h, self.gates = new(BF, 3 * H), new(BF, H), new(BF, H), new(BF, 4 * H)
         self.dh_ext, self.dgi, self.dgh = new(B, H), new(B, 3 * H), new(B, 3 * H)
         self.h0 = new(self.N, H)                                                    # the state entering the iteration (detached)
-        self.resets = torch.zeros(self.T, self.N, dtype=torch.uint8, device=dev)    # non-zero: the state entering step t of env n is zero
+        self.resets = torch.zeros(self.TF, self.N, dtype=torch.uint8, device=dev)   # non-zero: the state entering step t of env n is zero
         self._resets = self.resets                                                  # ... as the last forward() read them (backward() reads the same)
+        self._h0 = self.h0
+        self.next_state = new(self.N, H) if extra_steps else None                   # carry_state()
         self._zero_bias = new(H)
         self._cs = new((B + 127) // 128 * (6 if self.bias_partial else 3) * H)  # (bias_partial: one record [6H] per 128 rows)
         self.x = None
@@ -697,34 +721,62 @@ class GRUTrainer:
         """The reset flags [N] of step n's launch: an env that the step before reset enters with a zero state."""
         return last_dones if n == 0 else dones[n - 1]
 
-    def rollout_end(self, dones, last_dones):
-        """Behind the last step: the reset flags [T][N] of the update's recurrence, and the last step's done flags for the next iteration's step 0."""
-        if self.T > 1:
-            self.resets[1:].copy_(dones[: self.T - 1])
-        last_dones.copy_(dones[self.T - 1])
+    def rollout_end(self, dones, last_dones=None):
+        """Behind the last step: the reset flags of the update's recurrence (row t = the done flags of step t - 1, for every step the forward pass
+        walks), and the last step's done flags for the next iteration's step 0 (last_dones = None: another cell's call keeps them)."""
+        if self.TF > 1:
+            self.resets[1:].copy_(dones[: self.TF - 1])
+        if last_dones is not None:
+            last_dones.copy_(dones[self.T - 1])
 
-    def forward(self, x, h0=None, resets=None):
-        """h0 [N][H] / resets [T][N] uint8: the state the recurrence starts from and the reset flags it (and the backward pass behind it) reads, where
-        they are not this trainer's own (an env-wise mini-batch: rows of the runner's gathered buffers)."""
+    def carry_state(self):
+        """A cell that no rollout launch advances (extra_steps: the critic's): the state the next iteration starts from is this cell's output on step
+        T - 1, taken from a forward pass on the parameters the rollout ran on (the update's first, before any optimiser step), on the current stream
+        right behind that pass.  It enters step T, and the next iteration's step 0, through that step's reset flags.  rollout_begin(next_state, ...)
+        then starts the next iteration from it."""
+        self.next_state.copy_(self.h[(self.T - 1) * self.N : self.T * self.N])
+
+    # ------------------------------------------------------------------ the update's passes
+    def _input_side(self, x, h0, resets):
+        """gi = x W_ih^T + b_ih on all rows of the forward pass; returns the recurrence's problem (bg_gru_forward_problem) on this trainer's buffers."""
         lib, st, p, c, H = _lib.load(), _lib.current_stream_ptr(), _lib.ptr, self.cell, self.H
         self.x = x
         h0, self._resets = self.h0 if h0 is None else h0, self.resets if resets is None else resets
         if h0.shape != self.h0.shape or self._resets.shape != self.resets.shape or self._resets.dtype != torch.uint8 or not (h0.is_contiguous() and self._resets.is_contiguous()):
-            raise ValueError(f"GRUTrainer.forward: h0 {tuple(h0.shape)} / resets {tuple(self._resets.shape)} are not contiguous [{self.N}][{H}] / uint8 [{self.T}][{self.N}]")
-        _lib.check(lib.bg_mlp_layer_forward(self.B, self.KIN, 3 * H, p(x), p(self.copies.get("w0pad", 0)), p(c.bias_ih), p(self.gi), 0, st), "bg_mlp_layer_forward")
-        _lib.check(lib.bg_gru_sequence_forward(self.T, self.N, H, p(self.gi), p(h0), p(self._resets), p(c.weight_hh), p(c.bias_hh), p(self.h_prev), p(self.h),
-                                               p(self.gates), st), "bg_gru_sequence_forward")
+            raise ValueError(f"GRUTrainer.forward: h0 {tuple(h0.shape)} / resets {tuple(self._resets.shape)} are not contiguous [{self.N}][{H}] / uint8 [{self.TF}][{self.N}]")
+        if x.shape != (self.BF, self.kin) or not x.is_contiguous():
+            raise ValueError(f"GRUTrainer.forward: x {tuple(x.shape)} is not contiguous [{self.BF}][{self.kin}]")
+        self._h0 = h0
+        _lib.check(lib.bg_mlp_layer_forward(self.BF, self.kin, 3 * H, p(x), p(self.copies.get("w0pad", 0)), p(c.bias_ih), p(self.gi), 0, st), "bg_mlp_layer_forward")
+        return _lib.GruForwardProblem(self.TF, self.N, p(self.gi), p(h0), p(self._resets), p(c.weight_hh), p(c.bias_hh), p(self.h_prev), p(self.h), p(self.gates))
+
+    def forward(self, x, h0=None, resets=None):
+        """h0 [N][H] / resets [T][N] uint8: the state the recurrence starts from and the reset flags it (and the backward pass behind it) reads, where
+        they are not this trainer's own (an env-wise mini-batch: rows of the runner's gathered buffers)."""
+        q = self._input_side(x, h0, resets)
+        _lib.check(_lib.load().bg_gru_sequence_forward(q.T, q.N, self.H, q.gi, q.h0, q.reset, q.W_hh, q.b_hh, q.h_prev, q.h, q.gates, _lib.current_stream_ptr()),
+                   "bg_gru_sequence_forward")
         return self.h
 
-    def backward(self, finishes=None):
-        """finishes (a list; bias_partial only): receives the descriptor of the bias gradients' reduction, for the caller's deferred group; None: it
-        runs here, as a bg_reduce_group of its own."""
+    @staticmethod
+    def forward_group(jobs):
+        """jobs = [(trainer, x, h0, resets), ...] (1 to 4 cells of one width): `forward` of every job with the recurrences as ONE launch
+        (bg_gru_sequence_forward_group: the single launches' code per cell, bit-identical outputs).  Returns every job's h."""
+        qs = [tr._input_side(x, h0, resets) for tr, x, h0, resets in jobs]
+        arr = (_lib.GruForwardProblem * len(qs))(*qs)
+        _lib.check(_lib.load().bg_gru_sequence_forward_group(arr, len(qs), jobs[0][0].H, _lib.current_stream_ptr()), "bg_gru_sequence_forward_group")
+        return [tr.h for tr, _, _, _ in jobs]
+
+    def _trunk_side(self):
+        """dh_ext = G1 W1 behind the trunk's backward_hidden; returns the backward recurrence's problem (bg_gru_backward_problem)."""
         lib, st, p, c, H, tr = _lib.load(), _lib.current_stream_ptr(), _lib.ptr, self.cell, self.H, self.trunk
         g1, l0 = tr.gin[1], tr.layers[0]  # dL/dz of the trunk's first layer [B][out], behind backward_hidden
         _lib.check(lib.bg_mlp_layer_forward(self.B, l0.weight.shape[0], H, p(g1), p(tr.copies.get("wt", 0)), p(self._zero_bias), p(self.dh_ext), 0, st),
                    "bg_mlp_layer_forward")
-        _lib.check(lib.bg_gru_sequence_backward(self.T, self.N, H, p(self.dh_ext), p(self.gates), p(self.h_prev), p(self._resets), p(c.weight_hh), p(self.dgi),
-                                                p(self.dgh), None, st), "bg_gru_sequence_backward")
+        return _lib.GruBackwardProblem(self.T, self.N, p(self.dh_ext), p(self.gates), p(self.h_prev), p(self._resets), p(c.weight_hh), p(self.dgi), p(self.dgh), None)
+
+    def _bias_side(self, finishes):
+        lib, st, p, c, H = _lib.load(), _lib.current_stream_ptr(), _lib.ptr, self.cell, self.H
         self._pending = True
         if self.bias_partial:
             _lib.check(lib.bg_gru_bias_partial(self.B, H, p(self.dgi), p(self.dgh), p(self._cs), st), "bg_gru_bias_partial")
@@ -738,6 +790,23 @@ class GRUTrainer:
         for g, b in ((self.dgi, c.bias_ih), (self.dgh, c.bias_hh)):
             _lib.check(lib.bg_elu_backward_colsum(self.B, 3 * H, p(g), None, p(b.grad), p(self._cs), st), "bg_elu_backward_colsum")
 
+    def backward(self, finishes=None):
+        """finishes (a list; bias_partial only): receives the descriptor of the bias gradients' reduction, for the caller's deferred group; None: it
+        runs here, as a bg_reduce_group of its own.  Differentiates the first T steps of the forward pass."""
+        q = self._trunk_side()
+        _lib.check(_lib.load().bg_gru_sequence_backward(q.T, q.N, self.H, q.dh_ext, q.gates, q.h_prev, q.reset, q.W_hh, q.dgi, q.dgh, None, _lib.current_stream_ptr()),
+                   "bg_gru_sequence_backward")
+        self._bias_side(finishes)
+
+    @staticmethod
+    def backward_group(trainers, finishes=None):
+        """`backward(finishes)` of every trainer (1 to 4 cells of one width) with the recurrences as ONE launch (bg_gru_sequence_backward_group)."""
+        qs = [tr._trunk_side() for tr in trainers]
+        arr = (_lib.GruBackwardProblem * len(qs))(*qs)
+        _lib.check(_lib.load().bg_gru_sequence_backward_group(arr, len(qs), trainers[0].H, _lib.current_stream_ptr()), "bg_gru_sequence_backward_group")
+        for tr in trainers:
+            tr._bias_side(finishes)
+
     def bias_finish(self):
         """The bg_reduce_problem behind bg_gru_bias_partial: the records [ceil(B / 128)][6H] added up into bias_ih.grad | bias_hh.grad."""
         c, H, fin = self.cell, self.H, _lib.ReduceProblem()
@@ -746,11 +815,12 @@ class GRUTrainer:
         return fin
 
     def pending_wgrad_problems(self):
-        """(G, A, dW, C_out, C_in (padded), C_in_real) of the cell's two weight gradients, for the grouped launch (GroupedWeightGrad.run)."""
+        """(G, A, dW, C_out, C_in (padded), C_in_real) of the cell's two weight gradients, for the grouped launch (GroupedWeightGrad.run): on the B rows
+        the backward pass differentiated."""
         if not self._pending:
             return []
-        self._pending, c, H = False, self.cell, self.H
-        return [(self.dgi, self.x, c.weight_ih.grad, 3 * H, self.KIN, c.weight_ih.shape[1]), (self.dgh, self.h_prev, c.weight_hh.grad, 3 * H, H, H)]
+        self._pending, c, H, B = False, self.cell, self.H, self.B
+        return [(self.dgi, self.x[:B], c.weight_ih.grad, 3 * H, self.kin, c.weight_ih.shape[1]), (self.dgh, self.h_prev[:B], c.weight_hh.grad, 3 * H, H, H)]
 
 
 class EstimatorActor(torch.nn.Module):
@@ -791,12 +861,16 @@ class ActorCritic(torch.nn.Module):
     network `estimator`, num_obs -> estimator_hidden -> 12, registered behind `logstd`; the actor then takes num_obs + estimator_cols inputs, the
     observations and the first estimator_cols = E of the estimator's 12 outputs.  num_obs stays the env's row (47 H): what callers pass as `obs`.
     memory_hidden = H > 0 (a recurrent student, distillation.student_memory; 0 = without, today's parameters in today's order): a
-    torch.nn.GRUCell(num_obs, H) `memory`, registered last, and the actor takes the H values of its new state instead of the observations."""
+    torch.nn.GRUCell(num_obs, H) `memory`, registered last, and the actor takes the H values of its new state instead of the observations.
+    critic_memory_hidden = H > 0 (a recurrent critic, algorithm.rnn_critic; 0 = without, today's parameters in today's order): a
+    torch.nn.GRUCell(num_obs + num_privileged_obs, H) `critic_memory`, registered behind `memory`, and the critic's first layer takes the H values of
+    its state instead of the rows.  Its state belongs to whoever walks the rows (the runner's update); est_value on single rows raises."""
 
     def __init__(self, num_act, num_obs, num_privileged_obs, actor_hidden=ACTOR_HIDDEN, critic_hidden=CRITIC_HIDDEN, estimator_hidden=None, estimator_cols=0,
-                 memory_hidden=0):
+                 memory_hidden=0, critic_memory_hidden=0):
         super().__init__()
         self.memory_hidden = int(memory_hidden or 0)
+        self.critic_memory_hidden = int(critic_memory_hidden or 0)
         if self.memory_hidden and estimator_hidden is not None:
             raise ValueError("memory_hidden: a recurrent actor with a state estimator is not supported")
         self.actor_hidden, self.critic_hidden = tuple(actor_hidden), tuple(critic_hidden)
@@ -804,13 +878,15 @@ class ActorCritic(torch.nn.Module):
         self.estimator_cols = int(estimator_cols) if estimator_hidden is not None else 0
         if estimator_hidden is not None and not 1 <= self.estimator_cols <= _lib.NUM_DOFS:
             raise ValueError(f"estimator_cols = {estimator_cols!r}: 1 to {_lib.NUM_DOFS} of the estimator's outputs enter the actor")
-        self.critic = _mlp(num_obs + num_privileged_obs, self.critic_hidden, 1)
+        self.critic = _mlp(self.critic_memory_hidden or num_obs + num_privileged_obs, self.critic_hidden, 1)
         self.actor = _mlp(self.memory_hidden or num_obs + self.estimator_cols, self.actor_hidden, num_act)
         self.logstd = torch.nn.parameter.Parameter(torch.full((1, num_act), fill_value=-2.0), requires_grad=True)
         if estimator_hidden is not None:
             self.estimator = _mlp(num_obs, self.estimator_hidden, _lib.NUM_DOFS)
         if self.memory_hidden:
             self.memory = torch.nn.GRUCell(num_obs, self.memory_hidden)
+        if self.critic_memory_hidden:
+            self.critic_memory = torch.nn.GRUCell(num_obs + num_privileged_obs, self.critic_memory_hidden)
         self._memory_state, self._gru_key, self._gru_descs = None, None, None
         self._sample_key, self._sample_layers = None, None
         self._est_key, self._est_layers = None, None
@@ -850,6 +926,9 @@ class ActorCritic(torch.nn.Module):
         return torch.distributions.Normal(mean, torch.exp(self.logstd).expand_as(mean))
 
     def est_value(self, obs, privileged_obs):
+        if self.critic_memory_hidden:
+            raise ValueError("est_value: a critic with memory is stateful; the update walks the iteration's rows from the state it carries "
+                             "(algorithm.rnn_critic)")
         return self.critic(torch.cat((obs, privileged_obs), dim=-1)).squeeze(-1)
 
     # ---- fused rollout inference (reference runner.py:109-111: dist = model.act(obs); act = dist.sample())

@@ -145,14 +145,38 @@ def rnn_hidden_size_of(cfg, world_size=1):
     return H
 
 
+def rnn_critic_of(cfg, world_size=1):
+    """algorithm.rnn_critic (an addition of this build; absent, null or false = off: the shipped yaml does not list it) as the width H of a second GRU
+    cell, in front of the critic: algorithm.rnn_hidden_size when the key is on (one width serves both cells, as in rsl_rl's ActorCriticRecurrent), else
+    0.  Pure.  ValueError naming the key for a value that is no bool and, naming both keys, for true without a non-zero algorithm.rnn_hidden_size (a
+    recurrent critic stands beside a recurrent actor); everything a recurrent actor does not compose with is rnn_hidden_size_of's to refuse."""
+    alg = cfg.get("algorithm", {}) or {}
+    on = alg.get("rnn_critic", False)
+    if on is None:
+        on = False
+    if not isinstance(on, bool):
+        raise ValueError(f"algorithm.rnn_critic must be true or false, got {on!r}")
+    if not on:
+        return 0
+    H = rnn_hidden_size_of(cfg, world_size)
+    if not H:
+        raise ValueError("algorithm.rnn_critic: true needs algorithm.rnn_hidden_size: 128 or 256 (the critic's cell stands beside a recurrent actor's and has "
+                         "its width)")
+    return H
+
+
 def checkpoint_memory_overrides(checkpoint):
     """{"algorithm.rnn_hidden_size": H} for a loaded checkpoint dict whose model carries memory.* and that is no student's (no "distillation" entry: an
     actor trained under algorithm.rnn_hidden_size; a student re-enters under distill.checkpoint_student_overrides), H from memory.weight_hh; None for
-    every other checkpoint.  What evaluate.py applies so that such a checkpoint evaluates without editing the yaml."""
+    every other checkpoint.  With critic_memory.* in the model (algorithm.rnn_critic) also "algorithm.rnn_critic": True.  What evaluate.py applies so
+    that such a checkpoint evaluates without editing the yaml."""
     sd = checkpoint.get("model") or {}
     if checkpoint.get("distillation") is not None or "memory.weight_hh" not in sd:
         return None
-    return {"algorithm.rnn_hidden_size": int(sd["memory.weight_hh"].shape[1])}
+    over = {"algorithm.rnn_hidden_size": int(sd["memory.weight_hh"].shape[1])}
+    if "critic_memory.weight_hh" in sd:
+        over["algorithm.rnn_critic"] = True
+    return over
 
 
 def symmetry_loss(cfg):
@@ -279,6 +303,7 @@ class UpdatePlan(NamedTuple):
     ranks: bool         # several ranks: the exchanges run
     symmetry: bool = False  # the mirror-symmetry loss: the actor trains on 2B rows (the batch, then its mirror images) through bg_actor_head_sym
     smoothness: bool = False  # ... the same plan (symmetry = True) with the partner rows of the action-smoothness loss in rows [B, 2B) (bg_partner_rows)
+    gru_group: int = 0  # a recurrent critic beside the recurrent actor, a one-stream step: 1 = both cells' forward recurrences as ONE launch, 2 = the backward ones too
 
 
 class CellRows(NamedTuple):
@@ -308,13 +333,15 @@ class StepRows(NamedTuple):
     ret: torch.Tensor
     values: torch.Tensor          # where the value head of the fused kernels writes the values of x_c's rows
     mem: Optional[CellRows] = None  # a recurrent actor: the cell around the trunk `at` on these rows (x_a: the cell's padded rows)
+    cmem: Optional[CellRows] = None  # a recurrent critic: the cell around the trunk `ct` on these rows (x_c: the cell's padded rows)
 
 
 TAIL_MAX_ITEMS = _lib.TAIL_MAX_BLOCKS  # blocks of sums of one bg_update_tail launch (bg_tail.hip)
 
 
 def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_split_bwd, chain_alternate, fused_wgrad, wgrad_split, one_stream,
-                defer_finish, one_launch_tail, fused_opt, fused_head, fused_gae, chain_values, rollout_forward, dp_active, symmetry=False, memory=0, smoothness=False):
+                defer_finish, one_launch_tail, fused_opt, fused_head, fused_gae, chain_values, rollout_forward, dp_active, symmetry=False, memory=0, smoothness=False, critic_memory=0,
+                gru_group=0):
     """UpdatePlan from the switches (MLPTrainer.SPLIT ... WGRAD_SPLIT and Runner._one_stream ... _rollout_forward, by the same names in lower case;
     dp.active; symmetry = algorithm.symmetry_loss) and the shapes: critic / actor = (layer widths, padded input width), rows = the batch.  Pure: no
     tensors, no device.  symmetry: the actor's passes differentiate 2 x rows rows (the batch and its mirror images) and the rollout runs no
@@ -326,7 +353,9 @@ def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_
     beside whatever the critic runs (as on a frame stack), without forward-ahead; the cell's gradients come out of launches that bg_update_tail's sums
     do not cover (its weight gradients' finish, its bias gradients' reduction), so the tail runs as the separate launches (one_tail = False:
     bg_reduce_group, the weight gradients with their finish, bg_optimizer_step, which takes the norm over the whole flat gradient, the cell's
-    included); a plan without the fused heads or the deferred reductions is a ValueError."""
+    included); a plan without the fused heads or the deferred reductions is a ValueError.  critic_memory = H > 0 (algorithm.rnn_critic, with memory):
+    `critic` is likewise the trunk behind the critic's cell, on the per-layer kernels, its values from the stored activations; gru_group
+    (BG_GRU_GROUP): the plan's field of that name."""
     if memory and not (fused_head and fused and defer_finish and not split):
         raise ValueError("algorithm.rnn_hidden_size needs the fused output layers of bg_head.hip, the per-layer fp32 kernels and the deferred reductions "
                          "(no parallel.gemm_split / BG_GEMM_SPLIT, BG_DEFER_FINISH=1)")
@@ -341,6 +370,11 @@ def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_
             for (w, kin), r in ((critic, rows), (actor, 2 * rows if symmetry else rows))]
     if memory and ((nets[1].fwd, nets[1].bwd) != ("layer", "layer") or not all(nets[1].grouped[:-1])):
         raise ValueError(f"algorithm.rnn_hidden_size: a batch of runner.horizon_length x env.num_envs = {rows} rows is outside the range of the layer kernels "
+                         "(an even number of 64 rows or more)")
+    if critic_memory and not memory:
+        raise ValueError("algorithm.rnn_critic needs algorithm.rnn_hidden_size (a recurrent critic stands beside a recurrent actor)")
+    if critic_memory and ((nets[0].fwd, nets[0].bwd) != ("layer", "layer") or not all(nets[0].grouped[:-1])):
+        raise ValueError(f"algorithm.rnn_critic: a batch of runner.horizon_length x env.num_envs = {rows} rows is outside the range of the layer kernels "
                          "(an even number of 64 rows or more)")
     bwd_chained = all(n.bwd == "chain_split" for n in nets)
     grouped = [(co, ci) for (w, kin), n in zip((critic, actor), nets) for ci, co, g in zip((kin,) + tuple(w[1:-1]), w[1:], n.grouped) if g]
@@ -361,7 +395,8 @@ def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_
     one_tail = (fused_opt and one_launch_tail and defer and finishing and all(all(n.grouped[:-1]) for n in nets) and sum(fins) + 2 <= 8
                 and sums <= TAIL_MAX_ITEMS and not memory)
     return UpdatePlan(nets[0], nets[1], wgrad, fused_head, fused_gae, chain_values, one_stream and chain_values and defer and bwd_chained, defer, fused_opt,
-                      one_tail, rollout_forward and chain_values and nets[1].chained and not symmetry, dp_active, bool(symmetry), bool(smoothness))
+                      one_tail, rollout_forward and chain_values and nets[1].chained and not symmetry, dp_active, bool(symmetry), bool(smoothness),
+                      int(gru_group) if critic_memory else 0)
 
 
 class Runner:
@@ -398,6 +433,8 @@ class Runner:
                              "under play.py, evaluate.py and export_model.py; PPO on a recurrent actor (from scratch, or fine-tuning that student) is "
                              f"algorithm.rnn_hidden_size: {self._memory} (training a recurrent student: distill.py --student_memory)")
         self._memory = self._memory or self._rnn
+        # algorithm.rnn_critic: a second cell of the same width in front of the critic; 0 = a feed-forward critic, the one switch the branches below read
+        self._rnn_critic = rnn_critic_of(self.cfg, self.world_size)
         if self._rnn and not test and (int((self.cfg.get("parallel", {}) or {}).get("gemm_split", 0) or 0) or MLPTrainer.SPLIT):
             raise ValueError(f"algorithm.rnn_hidden_size = {self._rnn} is not supported with parallel.gemm_split / BG_GEMM_SPLIT (the trunk behind the cell "
                              "runs the per-layer fp32 kernels): use gemm_split 0")
@@ -419,6 +456,8 @@ class Runner:
         est_args = {} if self._est is None else {"estimator_hidden": self._est.hidden, "estimator_cols": len(self._est.targets)}
         if self._memory:
             est_args = {"memory_hidden": self._memory}
+        if self._rnn_critic:
+            est_args["critic_memory_hidden"] = self._rnn_critic
         self.model = ActorCritic(self.env.num_actions, self.env.num_obs, self.env.num_privileged_obs, self.actor_hidden, self.critic_hidden, **est_args).to(self.device)
         self.dp.broadcast_parameters(self.model)  # identical initial weights on every rank
         # algorithm.empirical_normalization: running mean / variance of the critic's input columns (the actor's are its first num_obs), applied where rows
@@ -517,6 +556,18 @@ class Runner:
         if self._rnn and not test:
             self._mem_tr = GRUTrainer(self.model.memory, self._actor_tr, T, N, clock=self._clock, bias_partial=True)
             self._last_dones = torch.zeros(N, dtype=torch.uint8, device=dev)
+        # algorithm.rnn_critic: the second cell around the critic's trunk.  Its forward pass walks T + 1 steps (the row after the last step gives
+        # last_values) from a state that no rollout launch advances: GRUTrainer.carry_state.  None = a feed-forward critic
+        self._cmem_tr = None
+        if self._rnn_critic and not test:
+            if not self._pad_critic:
+                raise ValueError("algorithm.rnn_critic needs the critic's zero-padded input (the fused layer kernels)")
+            self._cmem_tr = GRUTrainer(self.model.critic_memory, self._critic_tr, T, N, clock=self._clock, bias_partial=True, kin=self._pad_critic, extra_steps=1)
+        # BG_GRU_GROUP: both cells' recurrences of a one-stream step (runner.num_env_mini_batches) as ONE launch.  1 (the default): the forward ones
+        # (bg_gru_sequence_forward_group: 0.53x the two single launches at 1,024 envs each); 2: the backward ones too (bg_gru_sequence_backward_group,
+        # not the faster side: its H = 128 kernel compiles to 512 registers with spills where the single one takes 356 -- DESIGN.md section 6.21);
+        # 0: single launches both ways.  Resolved into the plan like the other switches
+        self._gru_group = {"0": 0, "1": 1, "2": 2}[os.environ.get("BG_GRU_GROUP", "1")]
         gs = (self.cfg.get("parallel", {}) or {}).get("gemm_split", 0)
         if gs:  # yaml switch for the split-bf16 GEMMs (process-wide, like the environment variable)
             if int(gs) not in (6, 9):
@@ -631,6 +682,14 @@ class Runner:
                              + f", the config has algorithm.actor_memory = {getattr(self, '_memory', 0)}: set algorithm.actor_memory to {ck_mem}"
                              + (" (a student of distillation.student_memory, or an actor trained under algorithm.rnn_hidden_size, the key to train it "
                                 "further under; evaluate.py and export_model.py set the width from the checkpoint)" if ck_mem else ""))
+        ck_cmem = int(model_dict["model"]["critic_memory.weight_hh"].shape[1]) if "critic_memory.weight_hh" in model_dict["model"] else 0
+        # (a recurrent student re-entering for fine-tuning carries an UNTRAINED feed-forward critic: under algorithm.rnn_critic the critic built here,
+        # cell and trunk, stays as initialised and the student's critic.* is not loaded)
+        fresh_critic = bool(getattr(self, "_rnn_critic", 0)) and not ck_cmem and model_dict.get("distillation") is not None
+        if ck_cmem != getattr(self, "_rnn_critic", 0) and not fresh_critic:
+            raise ValueError(f"checkpoint {ck} has " + (f"a recurrent critic (critic_memory.* of width {ck_cmem})" if ck_cmem else "no critic_memory.* (its critic "
+                             "is not recurrent)") + f", the config has algorithm.rnn_critic: {'true' if getattr(self, '_rnn_critic', 0) else 'false'}: set "
+                             f"algorithm.rnn_critic to {'true' if ck_cmem else 'false'} (evaluate.py sets it from the checkpoint)")
         ck_ain, a_in = int(model_dict["model"]["actor.0.weight"].shape[1]), self.model.actor[0].in_features
         est = getattr(self, "_est", None)
         check_estimator_checkpoint(ck, model_dict, est, ck_ain, a_in)  # (before the frame-stack message below can misfire on a width that differs by E)
@@ -644,6 +703,8 @@ class Runner:
                              f"{self.env.num_single_obs} x env.frame_stack): env.frame_stack must be as in the run that saved the checkpoint "
                              f"({ck_ain // self.env.num_single_obs if ck_ain % self.env.num_single_obs == 0 else '?'})")
         ck_in, c_in = int(model_dict["model"]["critic.0.weight"].shape[1]), self.model.critic[0].in_features
+        if fresh_critic:
+            ck_in = c_in
         ex_ck, ex_cfg = list(model_dict.get("privileged_extras", [])), list(getattr(self.env, "privileged_extras", ()))
         if ex_ck != ex_cfg:  # (before the width message below: groups of equal width, feet and ground, would pass it)
             raise ValueError(f"checkpoint {ck} was saved with env.privileged_extras = {ex_ck}, the config has env.privileged_extras = {ex_cfg}: the critic's "
@@ -658,7 +719,7 @@ class Runner:
                              f"algorithm.actor_hidden = {list(self.actor_hidden)} and algorithm.critic_hidden = {list(self.critic_hidden)}: set these to the "
                              "checkpoint's widths")
         check_checkpoint(ck, model_dict.get("obs_normalizer"), self.obs_norm)  # (ValueError naming algorithm.empirical_normalization)
-        self.model.load_state_dict(model_dict["model"], strict=False)
+        self.model.load_state_dict({k: v for k, v in model_dict["model"].items() if not (fresh_critic and k.startswith("critic."))}, strict=False)
         self.invalidate()
         try:
             self.env.curriculum_prob = model_dict["curriculum"]
@@ -714,21 +775,25 @@ class Runner:
         ct, at = self._critic_tr, self._actor_tr
         sw = {k.lower(): getattr(MLPTrainer, k) for k in ("SPLIT", "FUSED", "CHAIN", "CHAIN_SPLIT", "CHAIN_SPLIT_BWD", "CHAIN_ALTERNATE", "FUSED_WGRAD", "WGRAD_SPLIT")}
         sw.update((k[1:], getattr(self, k)) for k in ("_one_stream", "_defer_finish", "_one_launch_tail", "_fused_opt", "_fused_head", "_fused_gae", "_chain_values",
-                                                      "_rollout_forward"))
+                                                      "_rollout_forward", "_gru_group"))
         widths = lambda tr: (tr.layers[0].in_features,) + tuple(l.out_features for l in tr.layers)
         kin_a = self._actor_in.shape[-1] if self._actor_in is not None else self.env.num_obs + self._est_cols  # (the actor's true input width)
         if self._mem_tr is not None:  # the trunk's input is the cell's state [B][H], not the padded observation rows (those are the cell's)
             kin_a = self._memory
-        plan = plan_update((widths(ct), self._critic_in.shape[-1]), (widths(at), kin_a), self._old_logp.numel(), dp_active=self.dp.active, symmetry=self._symmetry,
-                           memory=self._memory if self._mem_tr is not None else 0, smoothness=self._smooth, **sw)
+        kin_c = self._critic_in.shape[-1]
+        cmem = self._rnn_critic if self._cmem_tr is not None else 0
+        if cmem:  # likewise the critic's trunk behind its cell
+            kin_c = cmem
+        plan = plan_update((widths(ct), kin_c), (widths(at), kin_a), self._old_logp.numel(), dp_active=self.dp.active, symmetry=self._symmetry,
+                           memory=self._memory if self._mem_tr is not None else 0, smoothness=self._smooth, critic_memory=cmem, **sw)
         ct.plan, at.plan = plan.critic, plan.actor
         c_out = ct.layers[-1]
         ct.value_head = (c_out.weight.reshape(-1), c_out.bias, self._values_all) if plan.chain_values else None
         if self._mini_batches > 1 or self._env_mini_batches > 1:
             # runner.num_mini_batches / num_env_mini_batches: the plan above serves the whole-batch passes (forward-ahead, old mu, values + GAE); the K
             # optimiser steps of a mini-epoch run a plan of their own for b = B / K rows on the second pair of trainers
-            mp = self._mb_plan = plan_update((widths(ct), self._critic_in.shape[-1]), (widths(at), kin_a), self._mb_rows, dp_active=self.dp.active,
-                                             memory=self._memory if self._env_mini_batches > 1 else 0, **sw)
+            mp = self._mb_plan = plan_update((widths(ct), kin_c), (widths(at), kin_a), self._mb_rows, dp_active=self.dp.active,
+                                             memory=self._memory if self._env_mini_batches > 1 else 0, critic_memory=cmem if self._env_mini_batches > 1 else 0, **sw)
             self._critic_mb.plan, self._actor_mb.plan = mp.critic, mp.actor
             self._critic_mb.value_head = (c_out.weight.reshape(-1), c_out.bias, self._mb_values) if mp.chain_values else None
         return plan
@@ -799,28 +864,37 @@ class Runner:
         self._mb_rows = T * n
         self._actor_mb, self._critic_mb = MLPTrainer(self.model.actor, clock=self._clock), MLPTrainer(self.model.critic, clock=self._clock)
         self._mem_mb = GRUTrainer(self.model.memory, self._actor_mb, T, n, clock=self._clock, bias_partial=True)
+        # algorithm.rnn_critic: likewise a second trainer of the critic's cell for [T][n] rows (a step differentiates all of its rows: no extra step)
+        self._cmem_mb = None
+        if self._cmem_tr is not None:
+            self._cmem_mb = GRUTrainer(self.model.critic_memory, self._critic_mb, T, n, clock=self._clock, bias_partial=True, kin=self._pad_critic)
         self._mb_wgrad = [GroupedWeightGrad() for _ in range(K)]  # (descriptors per input buffer: one per mini-batch position)
         self._env_perm = torch.zeros(N, dtype=torch.int32, device=dev)
         f = lambda *shape: torch.zeros(*shape, device=dev)
         self._mb = types.SimpleNamespace(critic_in=f(B, self._critic_in.shape[-1]), actor_in=f(B, GRUTrainer.KIN), actions=f(B, A), old_mu=f(B, A), old_logp=f(B),
-                                         adv=f(B), ret=f(B), h0=f(N, H), resets=torch.zeros(B, dtype=torch.uint8, device=dev))
+                                         adv=f(B), ret=f(B), h0=f(N, H), resets=torch.zeros(B, dtype=torch.uint8, device=dev),
+                                         h0_c=f(N, H) if self._cmem_tr is not None else None)
         self._mb_values = f(self._mb_rows)
         self._mb_updates = 0  # the update counter of the permutation's key
 
     def _env_mini_batch_begin(self, u):
         """Once per update(), as _mini_batch_begin: step k runs on rows [k b, (k + 1) b) of the gathered buffers -- the T steps of the n envs
         sigma[k n : (k + 1) n], step-major -- with the cell trainer of b rows from the gathered state h0[k] and reset flags resets[k]; the descriptors
-        of the gather (nine streams: seven per row, the state per env, the one-byte reset flags)."""
+        of the gather (nine streams: seven per row, the state per env, the one-byte reset flags; with a recurrent critic a tenth, its state per env:
+        the first T rows of its reset flags are the actor's)."""
         m, b, w, K, T = self._mb, self._mb_rows, u.whole, self._env_mini_batches, u.T
         n = u.N // K
         u.steps = [StepRows(self._critic_mb, self._actor_mb, self._mb_plan, b, self._mb_wgrad[k], m.critic_in[r], None, m.actor_in[r], m.actions[r], m.old_mu[r],
-                            m.old_logp[r], m.adv[r], m.ret[r], self._mb_values, CellRows(self._mem_mb, m.h0[k * n : (k + 1) * n], m.resets[r].view(T, n)))
+                            m.old_logp[r], m.adv[r], m.ret[r], self._mb_values, CellRows(self._mem_mb, m.h0[k * n : (k + 1) * n], m.resets[r].view(T, n)),
+                            None if self._cmem_mb is None else CellRows(self._cmem_mb, m.h0_c[k * n : (k + 1) * n], m.resets[r].view(T, n)))
                    for k, r in enumerate(slice(k * b, (k + 1) * b) for k in range(K))]
         self._plan_chain_split(u.steps[0].x_c, u.steps[0].x_a, self._mb_plan, self._critic_mb, self._actor_mb)
         self._critic_tr.chain_workgroups = self._actor_tr.chain_workgroups = 0  # the whole-batch passes run one network at a time
         B, whole = u.B, w.mem
         streams = [(w.x_c[:B], m.critic_in, 0), (w.x_a[:B], m.actor_in, 0), (w.actions, m.actions, 0), (w.old_mu, m.old_mu, 0), (w.old_logp, m.old_logp, 0),
                    (w.adv, m.adv, 0), (w.ret, m.ret, 0), (whole.h0, m.h0, 1), (whole.resets.view(B), m.resets, 0)]
+        if w.cmem is not None:
+            streams.append((w.cmem.h0, m.h0_c, 1))
         for src, dst, _ in streams:
             if not (src.is_contiguous() and src.dtype == dst.dtype and src.dtype in (torch.float32, torch.uint8) and src.shape == dst.shape):
                 raise RuntimeError(f"env mini-batch gather: a stream of shape {tuple(src.shape)} ({src.dtype}) does not match its buffer {tuple(dst.shape)} ({dst.dtype})")
@@ -862,6 +936,9 @@ class Runner:
             mt = self._mem_tr
             if mt is not None:  # a recurrent actor: the state the update's recurrence starts from = the state as the last rollout left it
                 mt.rollout_begin(self.model.memory_state(self.env.num_envs, obses.device), self._last_dones)
+            cm = self._cmem_tr
+            if cm is not None:  # a recurrent critic: the state its last update carried over (GRUTrainer.carry_state), the same flags
+                cm.rollout_begin(cm.next_state, self._last_dones)
             for n in range(T):
                 if plan.ahead and n + 1 - start >= g:
                     self._forward_rows(start, n, main)  # rows of steps start .. n: on the side stream, beside this step's launches
@@ -879,6 +956,8 @@ class Runner:
                 self.env.step_to(buf["actions"][n], obses[n + 1], priv[n + 1], buf["rewards"][n], buf["dones"][n], buf["time_outs"][n])
             if plan.ahead:
                 self._forward_rows(start, T, main)  # ... and the observation after the last step: the critic's last_values rows
+            if cm is not None:
+                cm.rollout_end(buf["dones"])
             if mt is not None:
                 mt.rollout_end(buf["dones"], self._last_dones)
         self._fwd_plan = plan if plan.ahead else None
@@ -1066,16 +1145,37 @@ class Runner:
         self._grad_logstd.zero_()
         self._plan_chain_split(critic_all, obs_flat, plan)
         whole = StepRows(self._critic_tr, self._actor_tr, plan, B, self._wgrad_group, critic_all, B, obs_flat, act_flat, old_mu, self._old_logp, self._adv.view(B),
-                         self._ret.view(B), self._values_all, self._whole_cell())
+                         self._ret.view(B), self._values_all, self._whole_cell(), self._whole_critic_cell())
         # whole: the batch as the rows of one optimiser step; steps: what the steps of a mini-epoch run on (runner.num_mini_batches > 1: _mini_batch_begin)
         return types.SimpleNamespace(cfg=cfg, buf=buf, T=T, N=N, B=B, alg=alg, ahead=ahead, plan=plan, logstd_flat=logstd_flat, old_logstd=old_logstd,
-                                     main=torch.cuda.current_stream(), side=self._side_stream, mirrors=None, whole=whole, steps=[whole], ha0=ha0)
+                                     main=torch.cuda.current_stream(), side=self._side_stream, mirrors=None, whole=whole, steps=[whole], ha0=ha0,
+                                     carry=self._cmem_tr is not None)
 
     # ------------------------------------------------------------------ the pieces of a mini-epoch, each on the rows of a StepRows, on the current stream
     def _whole_cell(self):
         """The CellRows of the whole batch: the cell's trainer with its own state and reset flags (None: a feed-forward actor)."""
         mt = self._mem_tr
         return None if mt is None else CellRows(mt, mt.h0, mt.resets)
+
+    def _whole_critic_cell(self):
+        """The CellRows of the whole batch's critic: its cell's trainer, over T + 1 steps, with its own state and reset flags (None: a feed-forward critic)."""
+        cm = self._cmem_tr
+        return None if cm is None else CellRows(cm, cm.h0, cm.resets)
+
+    @staticmethod
+    def _critic_hidden(v):
+        """The critic's last hidden activations on v's rows; with a recurrent critic x_c are the cell's padded rows: the cell first (GRUTrainer.forward from
+        the rows' h0 with their resets), then the trunk on h, which differentiates the first train_rows rows."""
+        if v.cmem is None:
+            return v.ct.forward_hidden(v.x_c, train_rows=v.train_rows)
+        return v.ct.forward_hidden(v.cmem.trainer.forward(v.x_c, v.cmem.h0, v.cmem.resets), train_rows=v.train_rows)
+
+    @staticmethod
+    def _critic_backward_hidden(ct, fins, cmem):
+        """The critic's backward-data pass; with a recurrent critic the trunk's, then the cell's through the T steps (truncated at h0)."""
+        ct.backward_hidden(finishes=fins)
+        if cmem is not None:
+            cmem.trainer.backward(finishes=fins)
 
     @staticmethod
     def _actor_hidden(at, x, mem):
@@ -1095,7 +1195,10 @@ class Runner:
         """The hidden layers of both networks on v's rows: one grouped launch, or one pass per network.  Returns their last hidden activations."""
         if v.plan.one_stream:
             return MLPTrainer.forward_hidden_group([(v.ct, v.x_c, v.train_rows), (v.at, v.x_a, None)])
-        return v.ct.forward_hidden(v.x_c, train_rows=v.train_rows), self._actor_hidden(v.at, v.x_a, v.mem)
+        if v.plan.gru_group and v.mem is not None and v.cmem is not None:  # both cells' recurrences as ONE launch, then both trunks
+            h_c, h_a = GRUTrainer.forward_group([(v.cmem.trainer, v.x_c, v.cmem.h0, v.cmem.resets), (v.mem.trainer, v.x_a, v.mem.h0, v.mem.resets)])
+            return v.ct.forward_hidden(h_c, train_rows=v.train_rows), v.at.forward_hidden(h_a)
+        return self._critic_hidden(v), self._actor_hidden(v.at, v.x_a, v.mem)
 
     def _head_values(self, v, hc):
         """The critic's values of v.x_c's rows in v.values: left there by the chained forward launch's value head (plan.chain_values: from the registers
@@ -1110,7 +1213,10 @@ class Runner:
         forward-ahead in mini-epoch 0, the grouped launch of both networks), None: the pass runs here.  Returns hc and the values of all rows."""
         v, plan, buf, alg, T, N, B = u.whole, u.plan, u.buf, u.alg, u.T, u.N, u.B
         if plan.fused_head and hc is None:
-            hc = v.ct.forward_hidden(v.x_c, train_rows=v.train_rows)
+            hc = self._critic_hidden(v)
+            if u.carry:  # a recurrent critic's first pass of the update, on the parameters the rollout ran on: the state the next iteration starts from
+                v.cmem.trainer.carry_state()
+                u.carry = False
         if plan.fused_head and plan.fused_gae:
             # output layer + timeout bootstrap + GAE + returns + advantage moments in ONE launch in front of the actor's loss
             c_out = v.ct.layers[-1]
@@ -1182,8 +1288,12 @@ class Runner:
                 self._exchange_sums()  # exchange (3)
             if plan.one_stream:
                 MLPTrainer.backward_hidden_group([ct, at], fins)
-            else:
+            elif plan.gru_group == 2 and v.mem is not None and v.cmem is not None:  # both trunks, then both cells' recurrences as ONE launch
                 ct.backward_hidden(finishes=fins)
+                at.backward_hidden(finishes=fins)
+                GRUTrainer.backward_group([v.cmem.trainer, v.mem.trainer], fins)
+            else:
+                self._critic_backward_hidden(ct, fins, v.cmem)
                 self._actor_backward_hidden(at, fins, v.mem)
         else:
             g_val, g_mu = self._library_loss(u, v, at.forward(v.x_a), ct.forward(v.x_c, train_rows=v.train_rows).squeeze(-1)[: v.rows])
@@ -1214,7 +1324,7 @@ class Runner:
                 ha = self._actor_hidden(at, v.x_a, v.mem)
             with torch.cuda.stream(side):
                 self._critic_loss_head(v, hc, values, fin_c)
-                ct.backward_hidden(finishes=fins)
+                self._critic_backward_hidden(ct, fins, v.cmem)
             main.wait_event(gae_done)  # advantages and their moments
             self._actor_loss_head(u, v, ha, fin_a)
             if plan.ranks and not plan.defer:
@@ -1252,6 +1362,8 @@ class Runner:
         # kernel's range, or MLPTrainer.FUSED_WGRAD = False: library GEMMs, layer by layer); one_tail: their finish inside bg_update_tail
         # (a recurrent actor: the cell's two weight gradients ride in the same launch, its padded W_ih among the copies)
         trainers = (v.ct, v.at) if v.mem is None else (v.ct, v.at, v.mem.trainer)
+        if v.cmem is not None:
+            trainers += (v.cmem.trainer,)
         wg_partial = v.wgrad.run(trainers, plan.wgrad, one_tail)
         if plan.defer and plan.ranks:
             main.wait_stream(side)
@@ -1269,7 +1381,7 @@ class Runner:
             # ... in ONE launch, with the copies of the weights that the layer kernels read (zero-padded first layers, transposed hidden layers):
             # written by the same launch instead of six strided torch copies inside the chains of the next mini-epoch
             if mirrors is None:
-                plans = (v.ct.plan, v.at.plan, v.at.plan)  # (the cell's copies follow the actor's plan)
+                plans = (v.ct.plan, v.at.plan, v.at.plan, v.ct.plan)  # (a cell's copies follow its trunk's plan)
                 ms = [d for tr, pl in zip(trainers, plans) for d in tr.copies.descriptors(self.optimizer.flat, pl)]
                 mirrors = (_lib.ParamMirror * len(ms))(*ms) if 0 < len(ms) <= 16 else None
             if one_tail and not plan.ranks:
@@ -1374,6 +1486,8 @@ class Runner:
         if self._mem_tr is not None:  # a recurrent actor starts (and, from a checkpoint, resumes: the state is not saved) on a reset env with a zero state
             self.model.memory_state(self.env.num_envs, obs.device).zero_()
             self._last_dones.zero_()
+        if self._cmem_tr is not None:  # ... and a recurrent critic likewise
+            self._cmem_tr.next_state.zero_()
         # (+1 with the terrain curriculum: the sum of this rank's terrain levels)
         # (+1 with the estimator, last: its loss rides in the iteration's one host read)
         n = 2 * self._n_stats + 1 + 4 + _lib.NUM_REWARD_TERMS + 4 + (1 if self.env.terrain.curriculum else 0) + (1 if self._est is not None else 0)

@@ -43,6 +43,10 @@ if __name__ == "__main__":
         est_args = {"memory_hidden": int(sd["memory.weight_hh"].shape[1])}
         num_obs = int(sd["memory.weight_ih"].shape[1])
     num_priv = int(sd["critic.0.weight"].shape[1]) - num_obs
+    # algorithm.rnn_critic: a second cell `critic_memory` reads the critic's row and the critic its state; loaded with the rest, never exported
+    if "critic_memory.weight_ih" in sd:
+        est_args["critic_memory_hidden"] = int(sd["critic_memory.weight_hh"].shape[1])
+        num_priv = int(sd["critic_memory.weight_ih"].shape[1]) - num_obs
     if num_obs % 47:
         # terrain.actor_heights: the actor's row ends with the height scan, whose grid the checkpoint carries
         pts = ckpt.get("height_points")

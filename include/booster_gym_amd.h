@@ -453,6 +453,37 @@ int bg_gru_sequence_forward(int32_t T, int32_t N, int32_t H, const float* gi, co
  * dh0 [N][H] (may be NULL): the carry left after step 0.  Deterministic. */
 int bg_gru_sequence_backward(int32_t T, int32_t N, int32_t H, const float* dh_ext, const float* gates, const float* h_prev, const uint8_t* reset,
                              const float* W_hh, float* dgi, float* dgh, float* dh0, void* stream);
+/* Several such recurrences as ONE launch each way (a PPO update with a recurrent critic beside the recurrent actor, T1.yaml algorithm.rnn_critic, where
+ * both cells' recurrences would otherwise follow each other on one stream; a recurrence's time hardly depends on its number of envs).  A problem holds
+ * the arguments of the single entry point by the same names; 1 to 4 problems share one H (128 or 256), each with its own T, N and pointers.  A workgroup
+ * serves one problem through the single launches' own code, so every output equals theirs bit for bit, and the problems' workgroups alternate in
+ * dispatch order (round r: workgroup r of every problem that has one).  Checked before any launch, with a message naming the entry point: no problem,
+ * more than 4, a T or N below 1, a null pointer other than h0 / reset / dh0 (-1); a W_hh that is not 16-byte aligned (-1); an unsupported H (-4). */
+typedef struct bg_gru_forward_problem {
+    int32_t T, N;
+    const float* gi;
+    const float* h0;       /* may be NULL: zero */
+    const uint8_t* reset;  /* may be NULL: none */
+    const float* W_hh;
+    const float* b_hh;
+    float* h_prev;
+    float* h;
+    float* gates;
+} bg_gru_forward_problem;
+typedef struct bg_gru_backward_problem {
+    int32_t T, N;
+    const float* dh_ext;
+    const float* gates;
+    const float* h_prev;
+    const uint8_t* reset;  /* may be NULL: none */
+    const float* W_hh;
+    float* dgi;
+    float* dgh;
+    float* dh0;            /* may be NULL: not written */
+} bg_gru_backward_problem;
+#define BG_GRU_GROUP_MAX 4
+int bg_gru_sequence_forward_group(const bg_gru_forward_problem* problems, int32_t n_problems, int32_t H, void* stream);
+int bg_gru_sequence_backward_group(const bg_gru_backward_problem* problems, int32_t n_problems, int32_t H, void* stream);
 /* The cell's bias gradients of a PPO update on a recurrent actor (T1.yaml algorithm.rnn_hidden_size), without their finish: ONE launch in which
  * workgroup g sums rows [128 g, min(128 g + 128, B)) of dgi and dgh ([B][3H] each, as bg_gru_sequence_backward leaves them) down their columns and writes
  * record g of `records` ([ceil(B / 128)][6H] floats) = dgi's 3H column sums | dgh's.  Rows at or beyond B are never read, nothing is written past record
