@@ -194,6 +194,7 @@ SYMBOLS = [
     "bg_actor_head_sym", "bg_actor_head_sym_partial", "bg_mirror_rows", "bg_partner_rows",
     "bg_distill_head", "bg_distill_head_partial", "bg_distill_head_sym", "bg_distill_head_sym_partial",
     "bg_obs_moments", "bg_obs_normalize",
+    "bg_critic_values_gae_norm", "bg_value_denormalize", "bg_value_norm_update",
     "bg_perm_fill", "bg_gather_rows", "bg_gather_sequences",
     "bg_actor_sample_gru", "bg_distill_act_gru", "bg_gru_sequence_forward", "bg_gru_sequence_backward",
     "bg_gru_bias_partial", "bg_gru_sequence_forward_group", "bg_gru_sequence_backward_group",
@@ -314,6 +315,9 @@ def load():
         "bg_distill_head_sym_partial": (i32, [i32] + [vp] * 4 + [f32] + [vp] * 9 + [C.POINTER(ReduceProblem), vp]),
         "bg_obs_moments": (i32, [i32, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp]),
         "bg_obs_normalize": (i32, [i32, i32, vp, i32, vp, i32, i32, vp, vp, i32, vp]),
+        "bg_critic_values_gae_norm": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp]),
+        "bg_value_denormalize": (i32, [i32, vp, vp, vp]),
+        "bg_value_norm_update": (i32, [vp, vp, vp, C.c_double, vp]),
         "bg_perm_fill": (i32, [i32, u64, C.c_uint32, C.c_uint32, vp, vp]),
         "bg_gather_rows": (i32, [i32, i32, vp, C.POINTER(GatherStream), i32, vp]),
         "bg_gather_sequences": (i32, [i32, i32, i32, vp, C.POINTER(SequenceStream), i32, vp]),

@@ -480,16 +480,24 @@ __global__ __launch_bounds__(256) void critic_head_forward_kernel(int rows, cons
 #define BG_GAE_SCAN_ENVS 64
 #endif
 constexpr int VG_ENVS_VALUES = 16, VG_ENVS_SCAN = BG_GAE_SCAN_ENVS;
-template <int TMAX, int VG_ENVS>
+// NORM (bg_critic_values_gae_norm, algorithm.normalize_value): the critic's output is u, its value v = fmaf(sigma, u, m) with (m, sigma, 1 / sigma) =
+// value_stats.  The values are de-standardised where they enter LDS, so the scan, the bootstrap store into rewards and the advantages run on v with the
+// arithmetic of the other form; values_all keeps u; ret receives (R - m) * (1 / sigma), R = v + adv, each step rounded (bg_obs_normalize's rule: this
+// file compiles with contraction and reassociation on, so those three expressions are pinned); three more float64 sums per workgroup and in `sums`:
+// sum R, sum R^2 and the count of the un-normalised returns, which bg_value_norm_update merges into the statistics once per iteration.
+template <int TMAX, int VG_ENVS, bool NORM>
 __global__ __launch_bounds__(256) void critic_values_gae_kernel(int T, int N, const float* __restrict__ h, const float* __restrict__ w,
                                                                 const float* __restrict__ b, float* __restrict__ rewards,
                                                                 const uint8_t* __restrict__ dones, const uint8_t* __restrict__ touts, float gamma,
                                                                 float lam, float* __restrict__ values_all, float* __restrict__ adv,
                                                                 float* __restrict__ ret, double* __restrict__ partial, unsigned* __restrict__ ticket,
-                                                                double* __restrict__ sums) {
+                                                                double* __restrict__ sums, const float* __restrict__ value_stats) {
+    constexpr int NS = NORM ? 6 : 3;  // float64 sums per workgroup
     __shared__ float sv[(TMAX + 1) * VG_ENVS];
-    __shared__ double sd[3 * 4];
+    __shared__ double sd[NS * 4];
     __shared__ unsigned s_last;
+    float vm = 0.f, vsig = 1.f, vinv = 1.f;
+    if constexpr (NORM) { vm = value_stats[0]; vsig = value_stats[1]; vinv = value_stats[2]; }
     const int e0 = blockIdx.x * VG_ENVS, ne = N - e0 < VG_ENVS ? N - e0 : VG_ENVS;
     // the scan's operands (threads 0..15: one env each), in flight during the value phase
     float r[TMAX];
@@ -507,7 +515,9 @@ __global__ __launch_bounds__(256) void critic_values_gae_kernel(int T, int N, co
     if (!h) {  // the values are an input (the chained forward kernel's value head wrote them)
         for (int q = threadIdx.x; q < R; q += 256) {
             const int t = q / VG_ENVS, e = q % VG_ENVS;
-            sv[q] = values_all[(size_t)t * N + e0 + (e < ne ? e : ne - 1)];
+            const float u = values_all[(size_t)t * N + e0 + (e < ne ? e : ne - 1)];
+            if constexpr (NORM) sv[q] = __builtin_fmaf(vsig, u, vm);
+            else sv[q] = u;
         }
     }
     const float4 wv = h ? *reinterpret_cast<const float4*>(w + lane * 4) : float4{0.f, 0.f, 0.f, 0.f};
@@ -526,13 +536,14 @@ __global__ __launch_bounds__(256) void critic_values_gae_kernel(int T, int N, co
             for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o);
             const int q = r0 + u, t = q / VG_ENVS, e = q % VG_ENVS;
             if (lane == 0 && q < R) {
-                sv[q] = s + bias;
+                if constexpr (NORM) sv[q] = __builtin_fmaf(vsig, s + bias, vm);
+                else sv[q] = s + bias;
                 if (e < ne) values_all[(size_t)t * N + e0 + e] = s + bias;
             }
         }
     }
     __syncthreads();
-    double acc[3] = {0.0, 0.0, 0.0};
+    double acc[NS] = {};
     if (scan) {
         float next_v = sv[T * VG_ENVS + threadIdx.x], last_adv = 0.f;
 #pragma unroll
@@ -546,13 +557,25 @@ __global__ __launch_bounds__(256) void critic_values_gae_kernel(int T, int N, co
                 const float delta = rr + gamma * nn * next_v - v;
                 last_adv = delta + gamma * lam * nn * last_adv;
                 adv[k] = last_adv;
-                ret[k] = v + last_adv;
+                if constexpr (NORM) {
+                    float R, Rn;
+                    {
+#pragma clang fp contract(off) reassociate(off)
+                        R = v + last_adv;
+                        const float c = R - vm;
+                        Rn = c * vinv;
+                    }
+                    ret[k] = Rn;
+                    acc[3] += (double)R; acc[4] += (double)R * (double)R; acc[5] += 1.0;
+                } else {
+                    ret[k] = v + last_adv;
+                }
                 acc[0] += (double)last_adv; acc[1] += (double)last_adv * (double)last_adv; acc[2] += 1.0;
                 next_v = v;
             }
     }
 #pragma unroll
-    for (int k = 0; k < 3; k++) {  // (the scanning threads are the first VG_ENVS of the workgroup; the others carry zeros)
+    for (int k = 0; k < NS; k++) {  // (the scanning threads are the first VG_ENVS of the workgroup; the others carry zeros)
         const double s = wave_sum_d(acc[k]);
         if ((threadIdx.x & 63) == 0) sd[k * 4 + (threadIdx.x >> 6)] = s;
     }
@@ -565,16 +588,16 @@ __global__ __launch_bounds__(256) void critic_values_gae_kernel(int T, int N, co
     // visible at agent scope; one vmcnt counter for loads and stores), so it is compiled for those targets only: anything else gets the portable
     // release (fence + relaxed ticket), slower but correct by the model.  DESIGN.md section 5 records the assumption.
 #if defined(__gfx942__) || defined(__gfx950__)
-    if (threadIdx.x < 3) {
-        __hip_atomic_store(&partial[(size_t)blockIdx.x * 3 + threadIdx.x], sd[threadIdx.x * 4] + sd[threadIdx.x * 4 + 1] + sd[threadIdx.x * 4 + 2] + sd[threadIdx.x * 4 + 3],
+    if (threadIdx.x < NS) {
+        __hip_atomic_store(&partial[(size_t)blockIdx.x * NS + threadIdx.x], sd[threadIdx.x * 4] + sd[threadIdx.x * 4 + 1] + sd[threadIdx.x * 4 + 2] + sd[threadIdx.x * 4 + 3],
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // threads 0..2 and the ticket's thread 0 are one wave
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // threads 0..NS-1 and the ticket's thread 0 are one wave
     }
     __syncthreads();
     if (threadIdx.x == 0) s_last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1u : 0u;
 #else
-    if (threadIdx.x < 3)
-        __hip_atomic_store(&partial[(size_t)blockIdx.x * 3 + threadIdx.x], sd[threadIdx.x * 4] + sd[threadIdx.x * 4 + 1] + sd[threadIdx.x * 4 + 2] + sd[threadIdx.x * 4 + 3],
+    if (threadIdx.x < NS)
+        __hip_atomic_store(&partial[(size_t)blockIdx.x * NS + threadIdx.x], sd[threadIdx.x * 4] + sd[threadIdx.x * 4 + 1] + sd[threadIdx.x * 4 + 2] + sd[threadIdx.x * 4 + 3],
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -584,14 +607,14 @@ __global__ __launch_bounds__(256) void critic_values_gae_kernel(int T, int N, co
 #endif
     __syncthreads();
     if (s_last) {  // every workgroup's triple has arrived: fixed-order total
-        for (int k = 0; k < 3; k++) {
+        for (int k = 0; k < NS; k++) {
             double s = 0.0;
-            for (int g = threadIdx.x; g < (int)gridDim.x; g += 256) s += __hip_atomic_load(&partial[(size_t)g * 3 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int g = threadIdx.x; g < (int)gridDim.x; g += 256) s += __hip_atomic_load(&partial[(size_t)g * NS + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             s = wave_sum_d(s);
             if ((threadIdx.x & 63) == 0) sd[k * 4 + (threadIdx.x >> 6)] = s;
         }
         __syncthreads();
-        if (threadIdx.x < 3) sums[threadIdx.x] = sd[threadIdx.x * 4] + sd[threadIdx.x * 4 + 1] + sd[threadIdx.x * 4 + 2] + sd[threadIdx.x * 4 + 3];
+        if (threadIdx.x < NS) sums[threadIdx.x] = sd[threadIdx.x * 4] + sd[threadIdx.x * 4 + 1] + sd[threadIdx.x * 4 + 2] + sd[threadIdx.x * 4 + 3];
         if (threadIdx.x == 0) *ticket = 0u;
     }
 }
@@ -847,20 +870,29 @@ extern "C" int bg_critic_head_forward(int32_t rows, const float* h, const float*
     return 0;
 }
 
+// bg_critic_values_gae (value_stats == NULL: 3 float64 per workgroup in the scratch) and bg_critic_values_gae_norm (6) are one function
+template <bool NORM>
+static int critic_values_gae(const char* who, int32_t T, int32_t N, const float* h, const float* w, const float* b, float* rewards, const uint8_t* dones,
+                             const uint8_t* time_outs, float gamma, float lam, float* values_all, float* advantages, float* returns, const float* value_stats,
+                             double* sums, double* scratch, void* stream) {
+    if (T <= 0 || N <= 0 || (h && (!w || !b)) || !rewards || !dones || !time_outs || !values_all || !advantages || !returns || !sums || !scratch ||
+        (NORM && !value_stats))
+        return bg_fail(who, -1, "bad argument");
+    if (h && (!aligned16(h) || !aligned16(w))) return bg_fail(who, -1, "h and w must be 16-byte aligned");
+    if (T > 32) return bg_fail(who, -4, "horizon above 32 (use bg_critic_head_forward + bg_gae)");
+    unsigned* ticket = reinterpret_cast<unsigned*>(scratch + (size_t)((N + 15) / 16) * (NORM ? 6 : 3));  // the scratch's last element, whichever form runs
+    if (h) hipLaunchKernelGGL((critic_values_gae_kernel<32, VG_ENVS_VALUES, NORM>), dim3((N + VG_ENVS_VALUES - 1) / VG_ENVS_VALUES), dim3(256), 0, (hipStream_t)stream, T, N, h, w,
+                              b, rewards, dones, time_outs, gamma, lam, values_all, advantages, returns, scratch, ticket, sums, value_stats);
+    else hipLaunchKernelGGL((critic_values_gae_kernel<32, VG_ENVS_SCAN, NORM>), dim3((N + VG_ENVS_SCAN - 1) / VG_ENVS_SCAN), dim3(256), 0, (hipStream_t)stream, T, N, h, w, b,
+                            rewards, dones, time_outs, gamma, lam, values_all, advantages, returns, scratch, ticket, sums, value_stats);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
 extern "C" int bg_critic_values_gae(int32_t T, int32_t N, const float* h, const float* w, const float* b, float* rewards, const uint8_t* dones,
                                     const uint8_t* time_outs, float gamma, float lam, float* values_all, float* advantages, float* returns, double* sums,
                                     double* scratch, void* stream) {
-    if (T <= 0 || N <= 0 || (h && (!w || !b)) || !rewards || !dones || !time_outs || !values_all || !advantages || !returns || !sums || !scratch)
-        return bg_set_error(-1, "bg_critic_values_gae: bad argument");
-    if (h && (!aligned16(h) || !aligned16(w))) return bg_set_error(-1, "bg_critic_values_gae: h and w must be 16-byte aligned");
-    if (T > 32) return bg_set_error(-4, "bg_critic_values_gae: horizon above 32 (use bg_critic_head_forward + bg_gae)");
-    unsigned* ticket = reinterpret_cast<unsigned*>(scratch + (size_t)((N + 15) / 16) * 3);  // the scratch's last element, whichever form runs
-    if (h) hipLaunchKernelGGL((critic_values_gae_kernel<32, VG_ENVS_VALUES>), dim3((N + VG_ENVS_VALUES - 1) / VG_ENVS_VALUES), dim3(256), 0, (hipStream_t)stream, T, N, h, w,
-                              b, rewards, dones, time_outs, gamma, lam, values_all, advantages, returns, scratch, ticket, sums);
-    else hipLaunchKernelGGL((critic_values_gae_kernel<32, VG_ENVS_SCAN>), dim3((N + VG_ENVS_SCAN - 1) / VG_ENVS_SCAN), dim3(256), 0, (hipStream_t)stream, T, N, h, w, b,
-                            rewards, dones, time_outs, gamma, lam, values_all, advantages, returns, scratch, ticket, sums);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return critic_values_gae<false>("bg_critic_values_gae", T, N, h, w, b, rewards, dones, time_outs, gamma, lam, values_all, advantages, returns, nullptr, sums,
+                                    scratch, stream);
 }
 
 // ---- the heads with a loss.  Each is ONE function for its immediate and its deferred entry point: the main kernel, then the sums over its workgroups'
@@ -1070,6 +1102,65 @@ extern "C" int bg_partner_rows(int32_t T, int32_t N, int32_t cols, const float* 
     const uint64_t blocks = (rows * per_row + 255) / 256;
     hipLaunchKernelGGL(partner_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (uint32_t)rows, (uint32_t)N, (uint32_t)per_row, (int)mode, seed,
                        update, epoch, x, x_last, dones, time_outs, y);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ---- value normalisation (algorithm.normalize_value).  Its device code and entry points stand at the end of the file, so that every kernel above keeps
+// its place in the code object.  (The two small kernels are templates for that reason alone: a template's code is emitted behind the plain kernels'.)
+namespace {
+
+// values[i] = fmaf(sigma, values[i], m): the critic's standardised output u of algorithm.normalize_value in reward units, the one rounding that
+// critic_values_gae_kernel<NORM> gives it on the way into LDS
+template <int = 0>
+__global__ __launch_bounds__(256) void value_denormalize_kernel(int rows, float* __restrict__ values, const float* __restrict__ value_stats) {
+    const float m = value_stats[0], sigma = value_stats[1];
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < rows; i += gridDim.x * 256) values[i] = __builtin_fmaf(sigma, values[i], m);
+}
+
+// Chan et al.'s merge of the running (mean, population variance, count) in state with the batch whose (sum R, sum R^2, count) stand in sums[3..5]
+// (utils/obs_norm.py: moments_from_sums, merge_moments, restated in float64 on the device), then the fp32 triple (m, sigma, 1 / sigma) the kernels
+// read, sigma = sqrt(var) + eps.  A batch of no rows changes nothing.  One wave, one lane at work: 30 flops once per iteration.
+template <int = 0>
+__global__ __launch_bounds__(64) void value_norm_update_kernel(const double* __restrict__ sums, double* __restrict__ state, float* __restrict__ value_stats,
+                                                               double eps) {
+#pragma clang fp contract(off) reassociate(off)
+    const double n = sums[5];
+    if (threadIdx.x != 0 || !(n > 0.0)) return;
+    const double mean = state[0], var = state[1], count = state[2];
+    const double m_b = sums[3] / n;
+    double v_b = sums[4] / n - m_b * m_b;
+    v_b = v_b > 0.0 ? v_b : 0.0;
+    const double total = count + n, r = n / total, d = m_b - mean;
+    const double new_mean = mean + r * d;
+    double new_var = var + r * (v_b - var + d * (m_b - new_mean));
+    new_var = new_var > 0.0 ? new_var : 0.0;
+    state[0] = new_mean; state[1] = new_var; state[2] = total;
+    const double sigma = sqrt(new_var) + eps;
+    value_stats[0] = (float)new_mean; value_stats[1] = (float)sigma; value_stats[2] = (float)(1.0 / sigma);
+}
+
+}  // namespace
+
+extern "C" int bg_critic_values_gae_norm(int32_t T, int32_t N, const float* h, const float* w, const float* b, float* rewards, const uint8_t* dones,
+                                         const uint8_t* time_outs, float gamma, float lam, float* values_all, float* advantages, float* returns,
+                                         const float* value_stats, double* sums, double* scratch, void* stream) {
+    return critic_values_gae<true>("bg_critic_values_gae_norm", T, N, h, w, b, rewards, dones, time_outs, gamma, lam, values_all, advantages, returns, value_stats,
+                                   sums, scratch, stream);
+}
+
+extern "C" int bg_value_denormalize(int32_t rows, float* values, const float* value_stats, void* stream) {
+    if (rows <= 0 || !values || !value_stats) return bg_set_error(-1, "bg_value_denormalize: bad argument");
+    int blocks = (rows + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(value_denormalize_kernel<>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rows, values, value_stats);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int bg_value_norm_update(const double* sums, double* state, float* value_stats, double eps, void* stream) {
+    if (!sums || !state || !value_stats || !(eps > 0.0)) return bg_set_error(-1, "bg_value_norm_update: bad argument (eps > 0)");
+    hipLaunchKernelGGL(value_norm_update_kernel<>, dim3(1), dim3(64), 0, (hipStream_t)stream, sums, state, value_stats, eps);
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -21,10 +21,13 @@ that enqueue the same communicator's collectives in different orders dead-lock o
     with algorithm.empirical_normalization (and only then) tag "obs_norm": ONE float64 vector [column sums, column sums of squares, row count] of
     the iteration's observation rows, once per ITERATION, enqueued on the main stream behind the last mini-epoch's "bucket" (Runner.update ->
     ObsNormalizer.update_from), after which every rank merges the same totals into identical statistics;
+    with algorithm.normalize_value (and only then) tag "value_norm": ONE float64 vector [sum, sum of squares, count] of the last mini-epoch's
+    un-normalised returns, once per ITERATION, on the main stream behind the last "bucket" and behind "obs_norm" (Runner.update ->
+    ValueNormalizer.update_from), after which every rank's bg_value_norm_update merges the same totals;
   * the PROCESS GROUP's communicator for everything outside the mini-epochs (seed, initial weights, curriculum grid, barriers).
 With runner.num_mini_batches = K > 1 a mini-epoch has K optimiser steps and so K "bucket" exchanges behind its one "moments": moments(e), bucket(e, 0), ...,
 bucket(e, K - 1), all on the main stream.
-The host enqueues strictly in program order -- moments(e), bucket(e), moments(e + 1), ..., bucket(last), [obs_norm] -- on every rank, whatever the streams do on the device, and
+The host enqueues strictly in program order -- moments(e), bucket(e), moments(e + 1), ..., bucket(last), [obs_norm], [value_norm] -- on every rank, whatever the streams do on the device, and
 nothing else touches the own communicator; the process group's collectives are issued only between iterations.  Any change that makes the ORDER OF
 HOST CALLS depend on rank-local data (an early exit, a rank-dependent branch around an exchange) breaks the contract.  `BG_DP_LOG_ORDER=1` records the
 sequence of (tag, stream) per rank (DataParallel.order_log); tests/test_host_logic.py compares it across the ranks of a two-process job.

@@ -70,7 +70,9 @@ from .model import (ACTOR_HIDDEN, CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad,
 from .optim import FlatAdam
 from .parallel import DataParallel
 from .recorder import Recorder
-from .utils import (actor_head_forward, actor_head_loss_backward, actor_head_sym_loss_backward, critic_head_backward, critic_head_forward, critic_values_gae, gae,
+from .value_norm import KEY as VALUE_NORM_KEY, ValueNormalizer, check_checkpoint as check_value_checkpoint, normalize_value_of
+from .utils import (actor_head_forward, actor_head_loss_backward, actor_head_sym_loss_backward, critic_head_backward, critic_head_forward, critic_values_gae,
+                    critic_values_gae_norm, gae,
                     gaussian_logp, head_scratch, mirror_rows, partner_rows, reduce_group, ppo_loss_fused)
 
 
@@ -304,6 +306,7 @@ class UpdatePlan(NamedTuple):
     symmetry: bool = False  # the mirror-symmetry loss: the actor trains on 2B rows (the batch, then its mirror images) through bg_actor_head_sym
     smoothness: bool = False  # ... the same plan (symmetry = True) with the partner rows of the action-smoothness loss in rows [B, 2B) (bg_partner_rows)
     gru_group: int = 0  # a recurrent critic beside the recurrent actor, a one-stream step: 1 = both cells' forward recurrences as ONE launch, 2 = the backward ones too
+    value_norm: bool = False  # algorithm.normalize_value: the whole-batch pass runs bg_critic_values_gae_norm (the critic's output is standardised)
 
 
 class CellRows(NamedTuple):
@@ -341,7 +344,7 @@ TAIL_MAX_ITEMS = _lib.TAIL_MAX_BLOCKS  # blocks of sums of one bg_update_tail la
 
 def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_split_bwd, chain_alternate, fused_wgrad, wgrad_split, one_stream,
                 defer_finish, one_launch_tail, fused_opt, fused_head, fused_gae, chain_values, rollout_forward, dp_active, symmetry=False, memory=0, smoothness=False, critic_memory=0,
-                gru_group=0):
+                gru_group=0, value_norm=False):
     """UpdatePlan from the switches (MLPTrainer.SPLIT ... WGRAD_SPLIT and Runner._one_stream ... _rollout_forward, by the same names in lower case;
     dp.active; symmetry = algorithm.symmetry_loss) and the shapes: critic / actor = (layer widths, padded input width), rows = the batch.  Pure: no
     tensors, no device.  symmetry: the actor's passes differentiate 2 x rows rows (the batch and its mirror images) and the rollout runs no
@@ -355,7 +358,12 @@ def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_
     bg_reduce_group, the weight gradients with their finish, bg_optimizer_step, which takes the norm over the whole flat gradient, the cell's
     included); a plan without the fused heads or the deferred reductions is a ValueError.  critic_memory = H > 0 (algorithm.rnn_critic, with memory):
     `critic` is likewise the trunk behind the critic's cell, on the per-layer kernels, its values from the stored activations; gru_group
-    (BG_GRU_GROUP): the plan's field of that name."""
+    (BG_GRU_GROUP): the plan's field of that name.  value_norm = algorithm.normalize_value: the plan's field of that name; the de-standardised values
+    exist only inside bg_critic_values_gae_norm, so a plan without the fused heads or without the fused GAE launch is a ValueError."""
+    if value_norm and not (fused_head and fused_gae):
+        raise ValueError(f"{VALUE_NORM_KEY} needs " + ("the fused output layers of bg_head.hip (a critic whose last hidden layer is 128 wide, 12 actions)"
+                                                       if not fused_head else "the fused GAE launch bg_critic_values_gae_norm (runner.horizon_length of 32 or less)")
+                         + ": the value is de-standardised inside that launch only")
     if memory and not (fused_head and fused and defer_finish and not split):
         raise ValueError("algorithm.rnn_hidden_size needs the fused output layers of bg_head.hip, the per-layer fp32 kernels and the deferred reductions "
                          "(no parallel.gemm_split / BG_GEMM_SPLIT, BG_DEFER_FINISH=1)")
@@ -396,7 +404,7 @@ def plan_update(critic, actor, rows, *, split, fused, chain, chain_split, chain_
                 and sums <= TAIL_MAX_ITEMS and not memory)
     return UpdatePlan(nets[0], nets[1], wgrad, fused_head, fused_gae, chain_values, one_stream and chain_values and defer and bwd_chained, defer, fused_opt,
                       one_tail, rollout_forward and chain_values and nets[1].chained and not symmetry, dp_active, bool(symmetry), bool(smoothness),
-                      int(gru_group) if critic_memory else 0)
+                      int(gru_group) if critic_memory else 0, bool(value_norm))
 
 
 class Runner:
@@ -463,6 +471,10 @@ class Runner:
         # algorithm.empirical_normalization: running mean / variance of the critic's input columns (the actor's are its first num_obs), applied where rows
         # enter a network and updated at the end of update(); None = off, the one switch every branch below reads
         self.obs_norm = ObsNormalizer(self.env.num_obs + self.env.num_privileged_obs, obs_norm_eps, self.device) if obs_norm_on else None
+        # algorithm.normalize_value: running mean / variance of the returns; the critic's output is standardised (utils/value_norm.py).  None = off, the
+        # one switch every branch below reads; also None in a runner that only plays (it never evaluates the critic)
+        value_norm_on, value_norm_eps = normalize_value_of(self.cfg)  # (ValueError for anything but a bool, and for normalization_eps <= 0)
+        self.value_norm = ValueNormalizer(value_norm_eps, self.device) if value_norm_on and not test else None
         self._clock = WeightClock()  # the version of the parameters, shared by every trainer over them: see invalidate()
         # ... and of the estimator's, a clock of its own: PPO's steps do not change its parameters, its steps not PPO's
         self._est_clock = WeightClock() if self._est is not None else None
@@ -527,7 +539,8 @@ class Runner:
                 self._obs_mirror_raw = (obs_src.tolist(), obs_sign.tolist())
         self._adv = torch.zeros(T, N, device=dev)
         self._ret = torch.zeros(T, N, device=dev)
-        self._adv_sums = torch.zeros(3, dtype=torch.float64, device=dev)
+        # (algorithm.normalize_value: the first three of the launch's six sums; what the ranks exchange per mini-epoch stays these three)
+        self._adv_sums = torch.zeros(3, dtype=torch.float64, device=dev) if self.value_norm is None else self.value_norm.sums[:3]
         self._grad_mu = torch.zeros(B, A, device=dev)
         self._grad_val = torch.zeros(B, device=dev)
         # the float64 sums of a mini-epoch that every rank needs in full: loss / KL statistics [5] and the log-std gradient [A], contiguous so that ONE
@@ -594,7 +607,7 @@ class Runner:
         # networks share the chip by CUs inside one grid exactly as the two launches did, and no kernel of the mini-epoch waits for an event of another
         # stream any more (three hand-overs on its critical path, 7-20 us each in a kernel trace).  0: two launches on two streams
         self._one_stream = os.environ.get("BG_ONE_STREAM", "1") == "1"
-        self._gae_scratch = torch.zeros(3 * ((self.env.num_envs + 15) // 16) + 1, dtype=torch.float64, device=self.device)
+        self._gae_scratch = torch.zeros((3 if self.value_norm is None else 6) * ((self.env.num_envs + 15) // 16) + 1, dtype=torch.float64, device=self.device)
 
         # fused output layers + loss (bg_head.hip): both networks end in a 128-wide ELU layer, 12 actions / 1 value (utils/model.py); a model of
         # other widths runs the output layers as library GEMMs + bg_ppo_loss (as an attribute for the test that compares the two forms)
@@ -626,6 +639,11 @@ class Runner:
             self._init_env_mini_batches()
         if self._symmetry or self._smooth:
             self._resolve_plan()  # (a plan the symmetric head cannot serve is a ValueError here, not at the first update)
+        if self.value_norm is not None:
+            if self.cfg["runner"]["horizon_length"] > 32:
+                raise ValueError(f"{VALUE_NORM_KEY} needs runner.horizon_length of 32 or less, got {self.cfg['runner']['horizon_length']}: the value is "
+                                 "de-standardised inside the fused GAE launch bg_critic_values_gae_norm, which scans up to 32 steps")
+            self._resolve_plan()  # (ValueError for a plan without the fused heads: here, not at the first update)
         if self._est is not None:  # its supervised update (a batch outside the layer kernels' range is a ValueError here, not at the first update)
             self._est_trainer = EstimatorTrainer(self._est, self.model.estimator, self._est_opt, self._est_clock, T, N, no, dev)
 
@@ -719,6 +737,8 @@ class Runner:
                              f"algorithm.actor_hidden = {list(self.actor_hidden)} and algorithm.critic_hidden = {list(self.critic_hidden)}: set these to the "
                              "checkpoint's widths")
         check_checkpoint(ck, model_dict.get("obs_normalizer"), self.obs_norm)  # (ValueError naming algorithm.empirical_normalization)
+        if not getattr(self, "test", False):  # (a runner that plays never evaluates the critic: it loads such a checkpoint under either setting)
+            check_value_checkpoint(ck, model_dict.get("value_normalizer"), getattr(self, "value_norm", None))  # (ValueError naming algorithm.normalize_value)
         self.model.load_state_dict({k: v for k, v in model_dict["model"].items() if not (fresh_critic and k.startswith("critic."))}, strict=False)
         self.invalidate()
         try:
@@ -763,6 +783,8 @@ class Runner:
             d["terrain_levels"] = self.env.terrain_levels
         if self.obs_norm is not None:
             d["obs_normalizer"] = self.obs_norm.state_dict()
+        if getattr(self, "value_norm", None) is not None:
+            d["value_normalizer"] = self.value_norm.state_dict()
         if getattr(self.env, "num_scan_obs", 0):  # terrain.actor_heights: the grid of the scan at the end of the actor's row, for whoever deploys the actor
             d["height_points"] = self.env.height_points.clone()
         if getattr(self.env, "privileged_extras", ()):  # env.privileged_extras: the groups behind the critic's 14 + P columns, in the row's order
@@ -776,6 +798,7 @@ class Runner:
         sw = {k.lower(): getattr(MLPTrainer, k) for k in ("SPLIT", "FUSED", "CHAIN", "CHAIN_SPLIT", "CHAIN_SPLIT_BWD", "CHAIN_ALTERNATE", "FUSED_WGRAD", "WGRAD_SPLIT")}
         sw.update((k[1:], getattr(self, k)) for k in ("_one_stream", "_defer_finish", "_one_launch_tail", "_fused_opt", "_fused_head", "_fused_gae", "_chain_values",
                                                       "_rollout_forward", "_gru_group"))
+        sw["value_norm"] = self.value_norm is not None
         widths = lambda tr: (tr.layers[0].in_features,) + tuple(l.out_features for l in tr.layers)
         kin_a = self._actor_in.shape[-1] if self._actor_in is not None else self.env.num_obs + self._est_cols  # (the actor's true input width)
         if self._mem_tr is not None:  # the trunk's input is the cell's state [B][H], not the padded observation rows (those are the cell's)
@@ -1064,6 +1087,10 @@ class Runner:
                 # behind the last optimiser step: this iteration's T x N rows enter the statistics (row T is the next iteration's row 0), under data
                 # parallelism all ranks' rows through ONE float64 exchange (tag "obs_norm", main stream, behind the last "bucket": utils/parallel.py)
                 self.obs_norm.update_from(u.buf["obses"][: u.T], u.buf["privileged_obses"][: u.T], self.dp)
+            if u.plan.value_norm:
+                # behind the last optimiser step (and "obs_norm"): the last mini-epoch's un-normalised returns enter the statistics, all ranks' through
+                # ONE float64 exchange (tag "value_norm", main stream); merge and fp32 triple in one small launch, no host read
+                self.value_norm.update_from(dp=self.dp)
             if self._est is not None:
                 # behind the last PPO optimiser step: the next rollout runs the estimator trained on this iteration's rows
                 self._est_trainer.update(u.buf["obses"][: u.T], u.buf["privileged_obses"][: u.T])
@@ -1220,8 +1247,13 @@ class Runner:
         if plan.fused_head and plan.fused_gae:
             # output layer + timeout bootstrap + GAE + returns + advantage moments in ONE launch in front of the actor's loss
             c_out = v.ct.layers[-1]
-            v_all = critic_values_gae(None if plan.chain_values else hc, c_out.weight, c_out.bias, buf["rewards"], buf["dones"], buf["time_outs"], alg["gamma"],
-                                      alg["lam"], v.values, self._adv, self._ret, self._adv_sums, self._gae_scratch)
+            if plan.value_norm:  # v.values keeps the critic's standardised output u, _ret receives the standardised returns: the loss head's operands
+                v_all = critic_values_gae_norm(None if plan.chain_values else hc, c_out.weight, c_out.bias, buf["rewards"], buf["dones"], buf["time_outs"],
+                                               alg["gamma"], alg["lam"], v.values, self._adv, self._ret, self.value_norm.stats, self.value_norm.sums,
+                                               self._gae_scratch)
+            else:
+                v_all = critic_values_gae(None if plan.chain_values else hc, c_out.weight, c_out.bias, buf["rewards"], buf["dones"], buf["time_outs"], alg["gamma"],
+                                          alg["lam"], v.values, self._adv, self._ret, self._adv_sums, self._gae_scratch)
         else:
             v_all = self._head_values(v, hc) if plan.fused_head else v.ct.forward(v.x_c, train_rows=v.train_rows).squeeze(-1)
             gae(buf["rewards"], buf["dones"], buf["time_outs"], v_all[:B].view(T, N), v_all[B:], alg["gamma"], alg["lam"], advantages=self._adv,
@@ -1490,7 +1522,9 @@ class Runner:
             self._cmem_tr.next_state.zero_()
         # (+1 with the terrain curriculum: the sum of this rank's terrain levels)
         # (+1 with the estimator, last: its loss rides in the iteration's one host read)
-        n = 2 * self._n_stats + 1 + 4 + _lib.NUM_REWARD_TERMS + 4 + (1 if self.env.terrain.curriculum else 0) + (1 if self._est is not None else 0)
+        # (+3 with algorithm.normalize_value, in front of the estimator's: the normaliser's mean, variance and count)
+        self._log_vn = 2 * self._n_stats + 1 + 4 + _lib.NUM_REWARD_TERMS + 4 + (1 if self.env.terrain.curriculum else 0)
+        n = self._log_vn + (3 if self.value_norm is not None else 0) + (1 if self._est is not None else 0)
         self._log_dev = torch.zeros(n, dtype=torch.float64, device=self.device)
         self._log_host = [torch.zeros(n, dtype=torch.float64).pin_memory() for _ in range(2)]
         self._log_event = [torch.cuda.Event() for _ in range(2)]
@@ -1519,6 +1553,8 @@ class Runner:
             summary["terrain/mean_level"] = s[h + ne + 4] / self.env.num_envs
         if self.obs_norm is not None:
             summary.update(self._log_obs_norm[slot])
+        if self.value_norm is not None:
+            summary.update(ValueNormalizer.scalars_from(s[self._log_vn : self._log_vn + 3]))
         if self._est is not None:  # the last epoch's SSE / (12 B) of the iteration's estimator update
             summary["estimator/loss"] = s[-1]
         self.recorder.record_statistics(summary, it)
@@ -1538,6 +1574,8 @@ class Runner:
             d[h + ne : h + ne + 4].copy_(torch.stack((lin.mean(), ang.mean(), lin.max(), ang.max())))
         if self.env.terrain.curriculum:
             d[h + ne + 4 : h + ne + 5].copy_(self.env.terrain_level_sum())
+        if self.value_norm is not None:
+            d[self._log_vn : self._log_vn + 3].copy_(self.value_norm.state)
         if self._est is not None:
             d[-1:].copy_(self._est_trainer.loss)
         self._flush_log()  # the previous iteration's scalars: their copy finished long ago

@@ -95,6 +95,44 @@ def critic_values_gae(h, w, b, rewards, dones, time_outs, gamma, lam, values_all
     return values_all
 
 
+def critic_values_gae_norm(h, w, b, rewards, dones, time_outs, gamma, lam, values_all, advantages, returns, value_stats, sums, scratch):
+    """critic_values_gae under algorithm.normalize_value (bg_critic_values_gae_norm): values_all holds the critic's standardised output u (h = None:
+    given; else written), the scan runs on v = fmaf(sigma, u, m) with value_stats = fp32 [3] (m, sigma, 1 / sigma), returns receives
+    (R - m) * (1 / sigma); sums float64[6]: the advantage moments, then (sum R, sum R^2, count) of the un-normalised returns; scratch: float64
+    [6 * ceil(N / 16) + 1] whose last element the caller zeroed once."""
+    T, N = rewards.shape
+    d8 = dones.view(torch.uint8) if dones.dtype == torch.bool else dones
+    t8 = time_outs.view(torch.uint8) if time_outs.dtype == torch.bool else time_outs
+    _need_cuda(rewards, d8, t8, values_all, advantages, returns, value_stats, sums, scratch, *([] if h is None else [h, w, b]))
+    if (h is not None and h.shape[0] != (T + 1) * N) or values_all.numel() != (T + 1) * N or scratch.numel() < 6 * ((N + 15) // 16) + 1 or sums.numel() < 6:
+        raise ValueError("critic_values_gae_norm: h / values_all must have (T + 1) N rows, sums 6 and scratch 6 ceil(N / 16) + 1 float64")
+    if value_stats.dtype != torch.float32 or value_stats.numel() != 3 or sums.dtype != torch.float64 or scratch.dtype != torch.float64:
+        raise ValueError("critic_values_gae_norm: value_stats is fp32 [3], sums and scratch are float64")
+    _lib.check(_lib.load().bg_critic_values_gae_norm(T, N, _lib.ptr(h), _lib.ptr(w), _lib.ptr(b), _lib.ptr(rewards), _lib.ptr(d8), _lib.ptr(t8), gamma, lam,
+                                                     _lib.ptr(values_all), _lib.ptr(advantages), _lib.ptr(returns), _lib.ptr(value_stats), _lib.ptr(sums),
+                                                     _lib.ptr(scratch), _lib.current_stream_ptr()), "bg_critic_values_gae_norm")
+    return values_all
+
+
+def value_denormalize(values, value_stats):
+    """values = fmaf(sigma, values, m) in place (bg_value_denormalize): fp32, contiguous; value_stats fp32 [3] = (m, sigma, 1 / sigma)."""
+    _need_cuda(values, value_stats)
+    if values.dtype != torch.float32 or value_stats.dtype != torch.float32 or value_stats.numel() != 3:
+        raise ValueError("value_denormalize: fp32 values and value_stats fp32 [3]")
+    if values.numel():
+        _lib.check(_lib.load().bg_value_denormalize(values.numel(), _lib.ptr(values), _lib.ptr(value_stats), _lib.current_stream_ptr()), "bg_value_denormalize")
+    return values
+
+
+def value_norm_update(sums, state, value_stats, eps):
+    """Chan's merge of state float64 [3] (mean, variance, count) with sums[3:6] = (sum, sum of squares, count) on the device, then the fp32 triple
+    (bg_value_norm_update)."""
+    _need_cuda(sums, state, value_stats)
+    if sums.dtype != torch.float64 or sums.numel() < 6 or state.dtype != torch.float64 or state.numel() != 3 or value_stats.dtype != torch.float32 or value_stats.numel() != 3:
+        raise ValueError("value_norm_update: sums float64 [6], state float64 [3], value_stats fp32 [3]")
+    _lib.check(_lib.load().bg_value_norm_update(_lib.ptr(sums), _lib.ptr(state), _lib.ptr(value_stats), float(eps), _lib.current_stream_ptr()), "bg_value_norm_update")
+
+
 def discount_values(rewards, dones, values, last_values, gamma, lam):
     """Reference signature (utils/utils.py:33): `dones` already includes the time-outs; rewards are not touched."""
     zeros = torch.zeros_like(dones, dtype=torch.uint8)

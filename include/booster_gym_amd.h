@@ -654,6 +654,21 @@ int bg_critic_head_forward(int32_t rows, const float* h, const float* w, const f
 int bg_critic_values_gae(int32_t T, int32_t N, const float* h, const float* w, const float* b, float* rewards, const uint8_t* dones,
                          const uint8_t* time_outs, float gamma, float lam, float* values_all, float* advantages, float* returns, double* sums,
                          double* scratch, void* stream);
+/* ---- value normalisation (algorithm.normalize_value): the critic's output is u, its value v = fmaf(sigma, u, m); value_stats = device fp32
+ * [3] = (m, sigma, 1 / sigma), sigma = sqrt(var) + eps.
+ * bg_critic_values_gae under it: values_all keeps u (h == NULL: reads it); the time-out bootstrap written into rewards, the GAE scan, advantages and
+ * sums[0..2] run on v, bit-identical to bg_value_denormalize followed by bg_critic_values_gae; returns receives (R - m) * (1 / sigma) with
+ * R = v + advantage, subtract and multiply each rounded (bg_obs_normalize's rule).  sums float64 [6] WRITTEN: the three above, then sum R, sum R^2 and
+ * the count of the un-normalised returns.  scratch: float64 [6 * ceil(N / 16) + 1], its last element zero-initialised once.  -4: T > 32. */
+int bg_critic_values_gae_norm(int32_t T, int32_t N, const float* h, const float* w, const float* b, float* rewards, const uint8_t* dones,
+                              const uint8_t* time_outs, float gamma, float lam, float* values_all, float* advantages, float* returns,
+                              const float* value_stats, double* sums, double* scratch, void* stream);
+/* values[i] = fmaf(sigma, values[i], m) in place, i < rows: one rounding per value */
+int bg_value_denormalize(int32_t rows, float* values, const float* value_stats, void* stream);
+/* Chan et al.'s merge of state float64 [3] = (mean, population variance, count) with the batch of sums[3..5] = (sum, sum of squares, count), the
+ * layout bg_critic_values_gae_norm writes, in float64; then value_stats = ((float)mean, (float)sigma, (float)(1 / sigma)), sigma = sqrt(var) + eps.
+ * A count of zero leaves state and value_stats as they are.  One wave. */
+int bg_value_norm_update(const double* sums, double* state, float* value_stats, double eps, void* stream);
 /* actor.6 forward (mode 0: mu_out [B][12] = h W^T + b, nothing else is touched) or forward + PPO actor loss + backward (mode 1), with the
  * argument meaning of bg_ppo_loss: out g_hidden [B][128] = dL/dz of the last hidden layer, grad_W [12][128], grad_b [12],
  * grad_b_hidden [128] (bias gradient of the last hidden layer = column sums of g_hidden), grad_logstd [12] float64 and
