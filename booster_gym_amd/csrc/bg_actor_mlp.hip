@@ -34,6 +34,7 @@
 // a GRU cell in front of the network, on the same 16 rows and the same layer code: gru_rows, below.
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <string>
 
 #include "bg_common.h"
@@ -177,6 +178,22 @@ __device__ __forceinline__ int run_layers(const ActorNet& net, float (*buf)[MR *
     return cur;
 }
 
+// run_layers on an input tile `x` of its own (row stride LDA) that stays as it is: the first layer writes buf[0] and the activations ping-pong between
+// the two tiles of `buf` from there (bg_rnd_reward: two networks read the one tile).
+template <int LDA>
+__device__ __forceinline__ int run_layers_keep(const ActorNet& net, const float* x, float (*buf)[MR * LDA]) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    first_layer<LDA>(net.W[0], net.b[0], net.in[0], net.out[0], x, buf[0], wave, lane);
+    __syncthreads();
+    int cur = 0;
+    for (int l = 1; l < net.n; l++) {
+        layer<LDA>(net.W[l], net.b[l], net.in[l], net.out[l], l + 1 < net.n, buf[cur], buf[cur ^ 1], wave, lane);
+        __syncthreads();
+        cur ^= 1;
+    }
+    return cur;
+}
+
 // sample: one thread per (row, group of 4 actions), as bg_actor_sample, from the means in `m` (an LDS tile of row stride LDA).  act_out == nullptr: the
 // mean alone goes to mu_out and no noise is drawn (bg_distill_act's teacher, bg_actor_sample_est's estimator).
 // MIX (bg_distill_act_mix, compiled into its kernel alone): the row's action comes from ONE of two calls on the same rows, the teacher's when
@@ -282,6 +299,61 @@ __global__ __launch_bounds__(256) void distill_act_mix_kernel(int N, int nb, con
                            act_out, teacher, beta, teacher_noise);
 }
 
+// bg_rnd_reward (random network distillation, T1.yaml rnd.enabled; rsl_rl's rnd_cfg): a fixed random target network and a trained predictor on the
+// same 16 state rows, one BEHIND the other in the same workgroup, as bg_actor_sample_est runs its two.  The input tile [obs | priv | zeros] is built
+// ONCE, from the two row blocks of the experience buffer (no concatenated copy in memory), in a third LDS tile that neither network's activations
+// touch; both 16 x 12 embeddings stay on chip (the target's in `emb`, the predictor's in its last activation tile) and one thread per row adds the 12
+// squared differences in ascending j.  Every layer is first_layer / layer on the operands bg_actor_sample_mlp_scan has on a contiguous copy of the
+// rows, so both embeddings are that launch's means, bit for bit.  LDS: 3 x 16 x (MAXW + 4) floats + 768 B = 50 kB at MAXW = 256, 99 kB at 512.
+// The in-place add runs in float64 ((double)rew + (double)weight * inv_sigma * rho, the product of three fp32 numbers rounded once at 2^-53) and is
+// rounded to fp32 once, whatever the signs of the two terms.
+struct RndNets { ActorNet target, pred; };
+template <int MAXW>
+__global__ __launch_bounds__(256) void rnd_reward_kernel(int N, const float* __restrict__ obs, int obs_cols, const float* __restrict__ priv, int priv_cols, RndNets nets,
+                                                         const uint8_t* __restrict__ dones, const float* __restrict__ reward_stats, float weight,
+                                                         float* __restrict__ target_out, float* __restrict__ intrinsic, float* __restrict__ rewards) {
+    constexpr int LDA = MAXW + 4;
+    __shared__ __attribute__((aligned(16))) float xt[MR * LDA];
+    __shared__ __attribute__((aligned(16))) float buf[2][MR * LDA];
+    __shared__ float emb[MR * BG_NUM_DOFS];
+    const int r0 = blockIdx.x * MR, K = obs_cols + priv_cols, KP = (K + KC - 1) / KC * KC;  // (KP <= MAXW: host)
+    for (int k = threadIdx.x; k < MR * KP; k += blockDim.x) {
+        const int r = k / KP, c = k - r * KP;
+        float v = 0.f;
+        if (r0 + r < N) {
+            if (c < obs_cols) v = obs[(size_t)(r0 + r) * obs_cols + c];
+            else if (c < K) v = priv[(size_t)(r0 + r) * priv_cols + c - obs_cols];
+        }
+        xt[r * LDA + c] = v;
+    }
+    __syncthreads();
+    int cur = run_layers_keep<LDA>(nets.target, xt, buf);
+    if (threadIdx.x < MR * BG_NUM_DOFS) {
+        const int r = threadIdx.x / BG_NUM_DOFS, j = threadIdx.x % BG_NUM_DOFS;
+        const float v = buf[cur][r * LDA + j];
+        emb[threadIdx.x] = v;
+        if (r0 + r < N) target_out[(size_t)(r0 + r) * BG_NUM_DOFS + j] = v;
+    }
+    __syncthreads();  // (the predictor's first layer overwrites buf[0])
+    cur = run_layers_keep<LDA>(nets.pred, xt, buf);
+    if (threadIdx.x < MR && r0 + (int)threadIdx.x < N) {
+        const int r = threadIdx.x, row = r0 + r;
+        float ss = 0.f;
+#pragma unroll
+        for (int j = 0; j < BG_NUM_DOFS; j++) {
+            const float d = buf[cur][r * LDA + j] - emb[r * BG_NUM_DOFS + j];
+            ss = fmaf(d, d, ss);
+        }
+        const bool done = dones[row] != 0;  // the successor row opens the next episode: reaching a reset is not novelty
+        const float rho = done ? 0.f : sqrtf(ss);
+        intrinsic[row] = rho;
+        if (weight != 0.f && !done) {
+            const double scale = (double)weight * (double)(reward_stats ? reward_stats[2] : 1.f);
+            rewards[row] = (float)((double)rewards[row] + scale * (double)rho);
+        }
+    }
+}
+
 // ---- a recurrent student (distillation.student_memory, torch.nn.GRUCell(47, H) in front of the trunk): bg_actor_sample_gru, bg_distill_act_gru.
 // The same 16 rows per workgroup and the same pieces: the x-side gate pre-activations gi = x W_ih^T + b_ih [16][3H] are first_layer's scalar-load form
 // without the ELU on the 48-column tile of the newest observation, the h-side gh = h W_hh^T + b_hh [16][3H] are layer's form on the LDS tile of h, the
@@ -377,7 +449,9 @@ __global__ __launch_bounds__(256) void distill_act_gru_kernel(int N, int nb, con
 // The descriptors of one network -> ActorNet, with the width rules of the kernel; scan: the height-scan values behind the 47 H observations of a row
 // (bg_env_cfg.actor_heights), 0 without them.  maxw: the widest hidden layer.  `who` heads the error messages.
 // first_in > 0: the trunk behind a GRU cell, whose first layer takes the first_in = H values of the hidden state (a 16-byte aligned matrix as the others).
-static int fill_net(const char* who, int32_t n_layers, const bg_mlp_layer_desc* layers, int32_t scan, ActorNet& net, int& maxw, int32_t first_in = 0) {
+// any_in: a network on a state row (bg_rnd_reward), whose first layer takes any 1 to BG_ACTOR_MAX_INPUT columns.
+static int fill_net(const char* who, int32_t n_layers, const bg_mlp_layer_desc* layers, int32_t scan, ActorNet& net, int& maxw, int32_t first_in = 0,
+                    bool any_in = false) {
     const std::string w(who);
     if (n_layers < 3 || n_layers > MAX_LAYERS) return bg_set_error(-4, (w + ": 2 to 4 hidden layers (n_layers 3 to 5)").c_str());
     net = ActorNet{};
@@ -387,7 +461,7 @@ static int fill_net(const char* who, int32_t n_layers, const bg_mlp_layer_desc* 
         const bg_mlp_layer_desc& d = layers[l];
         if (!d.W || !d.b) return bg_set_error(-1, (w + ": bad argument (layer weights)").c_str());
         const bool last = l + 1 == n_layers;
-        if (l == 0 && first_in ? d.in != first_in : l == 0 ? (d.in - scan < BG_NUM_OBS || d.in - scan > BG_NUM_OBS * BG_MAX_FRAME_STACK || (d.in - scan) % BG_NUM_OBS != 0 || d.in > BG_ACTOR_MAX_INPUT)
+        if (l == 0 && any_in ? (d.in < 1 || d.in > BG_ACTOR_MAX_INPUT) : l == 0 && first_in ? d.in != first_in : l == 0 ? (d.in - scan < BG_NUM_OBS || d.in - scan > BG_NUM_OBS * BG_MAX_FRAME_STACK || (d.in - scan) % BG_NUM_OBS != 0 || d.in > BG_ACTOR_MAX_INPUT)
                    : d.in != layers[l - 1].out)
             return bg_set_error(-4, (w + ": layer widths do not chain (first layer: 47 H inputs, H = 1 .. 10 observation frames, and the "
                                          "height scan's points behind them, BG_ACTOR_MAX_INPUT at most)").c_str());
@@ -445,6 +519,36 @@ extern "C" int bg_actor_sample_est(int32_t N, const float* obs, int32_t n_est, c
         hipLaunchKernelGGL(actor_est_sample_kernel<256>, grid, block, 0, st, N, obs, nets, logstd, seed, (uint32_t)counter, est_out, mu, actions);
     else
         hipLaunchKernelGGL(actor_est_sample_kernel<512>, grid, block, 0, st, N, obs, nets, logstd, seed, (uint32_t)counter, est_out, mu, actions);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int bg_rnd_reward(int32_t N, const float* obs, int32_t obs_cols, const float* priv, int32_t priv_cols, int32_t n_target, const bg_mlp_layer_desc* target,
+                             int32_t n_pred, const bg_mlp_layer_desc* predictor, const uint8_t* dones, const float* reward_stats, float weight, float* target_out,
+                             float* intrinsic, float* rewards, void* stream) {
+    if (N <= 0 || !obs || !target || !predictor || !dones || !target_out || !intrinsic || !rewards) return bg_set_error(-1, "bg_rnd_reward: bad argument");
+    if (obs_cols < 1 || priv_cols < 0 || (priv_cols > 0) != (priv != nullptr))
+        return bg_set_error(-1, "bg_rnd_reward: bad argument (obs_cols at least 1; priv NULL with priv_cols 0 and only then)");
+    uint32_t wbits;
+    memcpy(&wbits, &weight, sizeof wbits);  // (a bit test: this file is compiled with -ffinite-math-only)
+    if ((wbits >> 31) ? wbits != 0x80000000u : (wbits & 0x7f800000u) == 0x7f800000u)
+        return bg_set_error(-1, "bg_rnd_reward: bad argument (weight: a finite number >= 0)");
+    const int64_t K = (int64_t)obs_cols + priv_cols;
+    if (K > BG_ACTOR_MAX_INPUT) return bg_set_error(-4, "bg_rnd_reward: the state row obs_cols + priv_cols exceeds BG_ACTOR_MAX_INPUT");
+    RndNets nets;
+    int maxw_t = 0, maxw_p = 0;
+    if (const int rc = fill_net("bg_rnd_reward (target)", n_target, target, 0, nets.target, maxw_t, 0, true)) return rc;
+    if (const int rc = fill_net("bg_rnd_reward (predictor)", n_pred, predictor, 0, nets.pred, maxw_p, 0, true)) return rc;
+    if (target[0].in != K) return bg_set_error(-4, "bg_rnd_reward (target): the first layer takes the obs_cols + priv_cols columns of the state row");
+    if (predictor[0].in != K) return bg_set_error(-4, "bg_rnd_reward (predictor): the first layer takes the obs_cols + priv_cols columns of the state row");
+    const dim3 grid((N + MR - 1) / MR), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    // one LDS form for both networks: the wider hidden layer of the two and the padded state tile
+    const int kp = ((int)K + KC - 1) / KC * KC, maxw = maxw_t > maxw_p ? maxw_t : maxw_p;
+    if (maxw <= 256 && kp <= 256)
+        hipLaunchKernelGGL(rnd_reward_kernel<256>, grid, block, 0, st, N, obs, obs_cols, priv, priv_cols, nets, dones, reward_stats, weight, target_out, intrinsic, rewards);
+    else
+        hipLaunchKernelGGL(rnd_reward_kernel<512>, grid, block, 0, st, N, obs, obs_cols, priv, priv_cols, nets, dones, reward_stats, weight, target_out, intrinsic, rewards);
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -393,7 +393,7 @@ class Distiller:
             raise ValueError(f"teacher checkpoint {ck} " + ("has no \"height_points\" (it was not trained with terrain.actor_heights)" if pts is None else
                                                             "has other \"height_points\" than the env's terrain.measured_points_x / measured_points_y"))
         teacher = ActorCritic(env.num_actions, a_in, int(sd["critic.0.weight"].shape[1]) - a_in, hidden_of(sd, "actor"), hidden_of(sd, "critic")).to(self.device)
-        teacher.load_state_dict(sd)
+        teacher.load_state_dict({k: v for k, v in sd.items() if not k.startswith(("rnd_predictor.", "rnd_target."))})  # (a teacher trained under rnd.enabled: its curiosity networks stay behind)
         teacher.requires_grad_(False)
         if "curriculum" in d:
             try:

@@ -15,6 +15,7 @@ student of distillation.student_memory, or PPO's own under algorithm.rnn_hidden_
 step as well (bg_actor_sample_gru), and GRUTrainer around the trunk's MLPTrainer in the update.
 """
 import ctypes
+import math
 import os
 from contextlib import contextmanager
 from functools import partial
@@ -864,10 +865,12 @@ class ActorCritic(torch.nn.Module):
     torch.nn.GRUCell(num_obs, H) `memory`, registered last, and the actor takes the H values of its new state instead of the observations.
     critic_memory_hidden = H > 0 (a recurrent critic, algorithm.rnn_critic; 0 = without, today's parameters in today's order): a
     torch.nn.GRUCell(num_obs + num_privileged_obs, H) `critic_memory`, registered behind `memory`, and the critic's first layer takes the H values of
-    its state instead of the rows.  Its state belongs to whoever walks the rows (the runner's update); est_value on single rows raises."""
+    its state instead of the rows.  Its state belongs to whoever walks the rows (the runner's update); est_value on single rows raises.
+    rnd = (state width, predictor_hidden, target_hidden, seed) (rnd.enabled, utils/rnd.py; None = without, today's parameters in today's order and
+    today's draws of the global generator): two more networks, `rnd_predictor` and `rnd_target`, registered last; nothing of this class evaluates them."""
 
     def __init__(self, num_act, num_obs, num_privileged_obs, actor_hidden=ACTOR_HIDDEN, critic_hidden=CRITIC_HIDDEN, estimator_hidden=None, estimator_cols=0,
-                 memory_hidden=0, critic_memory_hidden=0):
+                 memory_hidden=0, critic_memory_hidden=0, rnd=None):
         super().__init__()
         self.memory_hidden = int(memory_hidden or 0)
         self.critic_memory_hidden = int(critic_memory_hidden or 0)
@@ -887,6 +890,8 @@ class ActorCritic(torch.nn.Module):
             self.memory = torch.nn.GRUCell(num_obs, self.memory_hidden)
         if self.critic_memory_hidden:
             self.critic_memory = torch.nn.GRUCell(num_obs + num_privileged_obs, self.critic_memory_hidden)
+        if rnd is not None:
+            self._add_rnd(*rnd)
         self._memory_state, self._gru_key, self._gru_descs = None, None, None
         self._sample_key, self._sample_layers = None, None
         self._est_key, self._est_layers = None, None
@@ -896,10 +901,28 @@ class ActorCritic(torch.nn.Module):
     def has_estimator(self):
         return self.estimator_hidden is not None
 
+    def _add_rnd(self, width, predictor_hidden, target_hidden, seed):
+        """rnd.enabled (utils/rnd.py): `rnd_predictor` and `rnd_target`, width -> hidden -> 12, registered last.  Built with the global generator's
+        state put back behind them and initialised (torch.nn.Linear's rule: uniform in +- 1 / sqrt(fan_in), weights and biases) from a generator
+        of their own seeded with `seed`, so every other draw of the process is as without them.  The target is never trained: no gradients."""
+        with torch.random.fork_rng(devices=[]):
+            self.rnd_predictor = _mlp(width, tuple(predictor_hidden), _lib.NUM_DOFS)
+            self.rnd_target = _mlp(width, tuple(target_hidden), _lib.NUM_DOFS)
+        g = torch.Generator().manual_seed(int(seed))
+        with torch.no_grad():
+            for net in (self.rnd_predictor, self.rnd_target):
+                for m in net:
+                    if isinstance(m, torch.nn.Linear):
+                        bound = 1.0 / math.sqrt(m.in_features)
+                        m.weight.uniform_(-bound, bound, generator=g)
+                        m.bias.uniform_(-bound, bound, generator=g)
+        for p in self.rnd_target.parameters():
+            p.requires_grad_(False)
+
     def ppo_parameters(self):
         """What PPO's optimiser holds: critic, actor, logstd in the module's order (all parameters of a model without an estimator); the estimator's
-        are stepped by an optimiser of their own."""
-        return [p for n, p in self.named_parameters() if not n.startswith("estimator.")]
+        and the RND predictor's are stepped by optimisers of their own, the RND target's by none."""
+        return [p for n, p in self.named_parameters() if not n.startswith(("estimator.", "rnd_predictor.", "rnd_target."))]
 
     def actor_input(self, obs):
         """The actor's row of observation rows: obs itself, or [obs | the first E of the estimator's outputs]."""

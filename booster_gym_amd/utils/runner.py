@@ -30,6 +30,11 @@ Same surface: `Runner(test=False)` parses the reference's 8 CLI flags (runner.py
             takes [observations | estimates].  The rollout's launch is then bg_actor_sample_est (both networks, the estimates kept in the buffer
             `estimates`), the update builds the actor's input from the stored rows, and behind the last PPO step the estimator takes its own
             supervised Adam steps (estimator.EstimatorTrainer: distillation's kernels, an optimiser and a WeightClock of its own).  No forward-ahead then.
+  curiosity rnd.enabled (utils/rnd.py; off by default): random network distillation.  Behind every env step of the rollout ONE more launch
+            (bg_rnd_reward) runs a fixed random target network and a trained predictor on the state the step has just written, keeps the target's
+            embedding and the raw intrinsic reward in the buffer (`rnd_targets`, `intrinsic_rewards`) and adds weight / sigma x it to the step's reward
+            in place; behind the last PPO step the predictor takes its own supervised Adam steps and the reward normaliser moves (rnd.RndTrainer: an
+            optimiser and a WeightClock of its own).  The forward-ahead stays on: it never reads rewards.
   recurrent algorithm.rnn_hidden_size (off by default): a GRU cell in front of the actor's hidden layers.  The rollout's launch is then bg_actor_sample_gru
             on a state [N][H] carried over steps and iterations and zeroed where an env reset; the update runs the cell over the iteration's T steps
             from the state stored at the rollout's start (model.GRUTrainer: back-propagation through time, truncated there) around the trunk's
@@ -70,6 +75,7 @@ from .model import (ACTOR_HIDDEN, CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad,
 from .optim import FlatAdam
 from .parallel import DataParallel
 from .recorder import Recorder
+from .rnd import RND_WIDTH, RndTrainer, check_rnd_checkpoint, module_seed, rnd_cfg
 from .value_norm import KEY as VALUE_NORM_KEY, ValueNormalizer, check_checkpoint as check_value_checkpoint, normalize_value_of
 from .utils import (actor_head_forward, actor_head_loss_backward, actor_head_sym_loss_backward, critic_head_backward, critic_head_forward, critic_values_gae,
                     critic_values_gae_norm, gae,
@@ -339,6 +345,8 @@ class StepRows(NamedTuple):
     cmem: Optional[CellRows] = None  # a recurrent critic: the cell around the trunk `ct` on these rows (x_c: the cell's padded rows)
 
 
+RND_LOG = ("rnd/intrinsic_reward", "rnd/weight", "rnd/reward_std", "rnd/loss")  # the log scalars of rnd.enabled, in RndTrainer.log's order
+
 TAIL_MAX_ITEMS = _lib.TAIL_MAX_BLOCKS  # blocks of sums of one bg_update_tail launch (bg_tail.hip)
 
 
@@ -431,6 +439,9 @@ class Runner:
         self._env_mini_batches = 1 if test else env_mini_batches(self.cfg)[1]
         # estimator.enabled: a learned state estimator in front of the actor (utils/estimator.py); None = off, the one switch every branch below reads
         self._est = estimator_cfg(self.cfg, self.world_size)
+        # rnd.enabled: an intrinsic reward by random network distillation (utils/rnd.py); None = off, the one switch every branch below reads.  The
+        # section belongs to training: a runner that only plays never evaluates these networks and does not read it
+        self._rnd = None if test else rnd_cfg(self.cfg, self.world_size)
         # algorithm.actor_memory: a recurrent distilled student re-entering for play / evaluation / export; 0 = none, the one switch the branches below read
         self._memory = actor_memory_of(self.cfg)
         # algorithm.rnn_hidden_size: PPO on a recurrent actor; the same cell, and the one key under which a model with memory trains (a student's
@@ -466,6 +477,11 @@ class Runner:
             est_args = {"memory_hidden": self._memory}
         if self._rnn_critic:
             est_args["critic_memory_hidden"] = self._rnn_critic
+        if self._rnd is not None:
+            if self._rnd.width != self.env.num_obs + (self.env.num_privileged_obs if self._rnd.state == "critic" else 0):
+                raise ValueError(f"rnd.state = {self._rnd.state!r}: the config's rows have {self._rnd.width} columns, the env's "
+                                 f"{self.env.num_obs} + {self.env.num_privileged_obs}")
+            est_args["rnd"] = (self._rnd.width, self._rnd.predictor_hidden, self._rnd.target_hidden, module_seed(self.cfg["basic"]["seed"]))
         self.model = ActorCritic(self.env.num_actions, self.env.num_obs, self.env.num_privileged_obs, self.actor_hidden, self.critic_hidden, **est_args).to(self.device)
         self.dp.broadcast_parameters(self.model)  # identical initial weights on every rank
         # algorithm.empirical_normalization: running mean / variance of the critic's input columns (the actor's are its first num_obs), applied where rows
@@ -478,10 +494,16 @@ class Runner:
         self._clock = WeightClock()  # the version of the parameters, shared by every trainer over them: see invalidate()
         # ... and of the estimator's, a clock of its own: PPO's steps do not change its parameters, its steps not PPO's
         self._est_clock = WeightClock() if self._est is not None else None
+        self._rnd_clock = WeightClock() if self._rnd is not None else None  # ... and of the RND predictor's, likewise
         self.invalidate()
         self.optimizer = FlatAdam(self.model.ppo_parameters(), lr=self.learning_rate)  # (critic, actor, logstd: all parameters of a model without an estimator)
         if self._est is not None:  # the estimator's own optimiser: no PPO gradient reaches it, PPO's buffer holds what it holds without the key
             self._est_opt = FlatAdam(self.model.estimator.parameters(), lr=self._est.learning_rate, max_grad_norm=self._est.max_grad_norm)
+        self._rnd_trainer = None
+        if self._rnd is not None:  # the predictor's own optimiser, the reward normaliser and the launch's descriptors; the target has no optimiser
+            rnd_opt = FlatAdam(self.model.rnd_predictor.parameters(), lr=self._rnd.learning_rate, max_grad_norm=self._rnd.max_grad_norm)
+            self._rnd_trainer = RndTrainer(self._rnd, self.model, rnd_opt, self._rnd_clock, self.cfg["runner"]["horizon_length"], self.env.num_envs, self.env.num_obs,
+                                           value_norm_eps, self.device)
         self._load()
         # Resume semantics of the reference (runner.py:31-34,174-180): the restored param_group lr serves the FIRST optimiser step only; the
         # first KL adaptation then overwrites it with a value derived from self.learning_rate = the yaml value, so adaptation restarts from
@@ -500,6 +522,9 @@ class Runner:
         self.buffer.add_buffer("time_outs", (), dtype=torch.bool)
         if self._est is not None:  # step n's 12 estimator outputs, computed from obses[n] by the estimator as it was then (rollout)
             self.buffer.add_buffer("estimates", (EST_WIDTH,))
+        if self._rnd is not None:  # step n's raw rho and the target's 12 outputs on the state after step n: the predictor's labels
+            self.buffer.add_buffer("intrinsic_rewards", ())
+            self.buffer.add_buffer("rnd_targets", (RND_WIDTH,))
         B, A = T * N, self.env.num_actions
         dev = self.device
         # network inputs with the feature dimension zero-padded, each network on its own (pad_input: actor 47 -> 64, critic 61 -> 64, or 61 + P -> 128 /
@@ -711,6 +736,8 @@ class Runner:
         ck_ain, a_in = int(model_dict["model"]["actor.0.weight"].shape[1]), self.model.actor[0].in_features
         est = getattr(self, "_est", None)
         check_estimator_checkpoint(ck, model_dict, est, ck_ain, a_in)  # (before the frame-stack message below can misfire on a width that differs by E)
+        if not getattr(self, "test", False):  # (a runner that plays never evaluates the RND networks: it loads such a checkpoint under either setting)
+            check_rnd_checkpoint(ck, model_dict, getattr(self, "_rnd", None))  # (ValueError naming rnd.enabled / rnd.state / the widths)
         scan_ck, scan_cfg = (int(model_dict["height_points"].shape[0]) if "height_points" in model_dict else 0), getattr(self.env, "num_scan_obs", 0)
         if ck_ain != a_in and ck_ain - scan_ck == a_in - scan_cfg:  # (the widths differ by the height scan in the actor's row)
             raise ValueError(f"checkpoint {ck} has an actor of {ck_ain} inputs, {scan_ck} of them the terrain height scan, the config's actor takes {a_in} "
@@ -762,6 +789,8 @@ class Runner:
                 self._est_opt.load_state_dict(model_dict["estimator"]["optimizer"])
             except Exception as e:
                 print(f"Failed to load the estimator's optimizer: {e}")
+        if getattr(self, "_rnd_trainer", None) is not None:
+            self._rnd_trainer.load_state_dict(model_dict.get("rnd") or {})
 
     def invalidate(self):
         """Call after changing the model's parameters or the rollout buffers by any means other than this runner's own rollout() / update() (a
@@ -774,11 +803,15 @@ class Runner:
         self._clock.tick()
         if self._est is not None:
             self._est_clock.tick()
+        if getattr(self, "_rnd_clock", None) is not None:
+            self._rnd_clock.tick()
 
     def checkpoint_dict(self):
         d = {"model": self.model.state_dict(), "optimizer": self.optimizer.state_dict(), "curriculum": self.env.curriculum_prob}
         if getattr(self, "_est", None) is not None:  # (the network itself: "estimator.*" inside "model")
             d["estimator"] = {"targets": list(self._est.targets), "optimizer": self._est_opt.state_dict()}
+        if getattr(self, "_rnd_trainer", None) is not None:  # (the networks themselves: "rnd_predictor.*" and "rnd_target.*" inside "model")
+            d["rnd"] = self._rnd_trainer.state_dict()
         if self.env.terrain.curriculum:
             d["terrain_levels"] = self.env.terrain_levels
         if self.obs_norm is not None:
@@ -962,6 +995,9 @@ class Runner:
             cm = self._cmem_tr
             if cm is not None:  # a recurrent critic: the state its last update carried over (GRUTrainer.carry_state), the same flags
                 cm.rollout_begin(cm.next_state, self._last_dones)
+            rt = self._rnd_trainer
+            if rt is not None:
+                rt.begin_rollout()  # this iteration's weight
             for n in range(T):
                 if plan.ahead and n + 1 - start >= g:
                     self._forward_rows(start, n, main)  # rows of steps start .. n: on the side stream, beside this step's launches
@@ -977,6 +1013,8 @@ class Runner:
                                               packed=packed)
                 self._act_counter += 1
                 self.env.step_to(buf["actions"][n], obses[n + 1], priv[n + 1], buf["rewards"][n], buf["dones"][n], buf["time_outs"][n])
+                if rt is not None:  # both RND networks on the state the step has just written, the add into its reward in place: ONE launch
+                    rt.reward(obses[n + 1], priv[n + 1], buf["dones"][n], buf["rnd_targets"][n], buf["intrinsic_rewards"][n], buf["rewards"][n])
             if plan.ahead:
                 self._forward_rows(start, T, main)  # ... and the observation after the last step: the critic's last_values rows
             if cm is not None:
@@ -1091,6 +1129,10 @@ class Runner:
                 # behind the last optimiser step (and "obs_norm"): the last mini-epoch's un-normalised returns enter the statistics, all ranks' through
                 # ONE float64 exchange (tag "value_norm", main stream); merge and fp32 triple in one small launch, no host read
                 self.value_norm.update_from(dp=self.dp)
+            if self._rnd_trainer is not None:
+                # behind the last PPO optimiser step (in front of the estimator's): the predictor on the iteration's successor rows, then the reward
+                # normaliser's move; the next rollout runs on both
+                self._rnd_trainer.update(u.buf["obses"][1:], u.buf["privileged_obses"][1:], u.buf["dones"], u.buf["rnd_targets"], u.buf["intrinsic_rewards"])
             if self._est is not None:
                 # behind the last PPO optimiser step: the next rollout runs the estimator trained on this iteration's rows
                 self._est_trainer.update(u.buf["obses"][: u.T], u.buf["privileged_obses"][: u.T])
@@ -1486,10 +1528,15 @@ class Runner:
     def _summarize(self, stats_acc):
         """Host-side means of the loss terms over the mini-epochs (runner.py:182-204); one device->host read (blocking: tests and tools)."""
         extra = () if self._est is None else (self._est_trainer.loss,)  # (read with the same one copy)
+        if self._rnd_trainer is not None:
+            extra = (self._rnd_trainer.log,) + extra
         s = torch.cat((stats_acc, self._stats_last, self.optimizer.lr.double()) + extra).cpu().tolist()
         out = self._summary_from(s)
         if self._est is not None:
             out["estimator/loss"] = s[-1]
+        if self._rnd_trainer is not None:
+            h = 2 * self._n_stats + 1
+            out.update(zip(RND_LOG, s[h : h + 4]))
         return out
 
     def _summary_from(self, s):
@@ -1524,7 +1571,9 @@ class Runner:
         # (+1 with the estimator, last: its loss rides in the iteration's one host read)
         # (+3 with algorithm.normalize_value, in front of the estimator's: the normaliser's mean, variance and count)
         self._log_vn = 2 * self._n_stats + 1 + 4 + _lib.NUM_REWARD_TERMS + 4 + (1 if self.env.terrain.curriculum else 0)
-        n = self._log_vn + (3 if self.value_norm is not None else 0) + (1 if self._est is not None else 0)
+        # (+4 with rnd.enabled, behind the value normaliser's and in front of the estimator's: RND_LOG)
+        self._log_rnd = self._log_vn + (3 if self.value_norm is not None else 0)
+        n = self._log_rnd + (4 if self._rnd_trainer is not None else 0) + (1 if self._est is not None else 0)
         self._log_dev = torch.zeros(n, dtype=torch.float64, device=self.device)
         self._log_host = [torch.zeros(n, dtype=torch.float64).pin_memory() for _ in range(2)]
         self._log_event = [torch.cuda.Event() for _ in range(2)]
@@ -1555,6 +1604,8 @@ class Runner:
             summary.update(self._log_obs_norm[slot])
         if self.value_norm is not None:
             summary.update(ValueNormalizer.scalars_from(s[self._log_vn : self._log_vn + 3]))
+        if self._rnd_trainer is not None:
+            summary.update(zip(RND_LOG, s[self._log_rnd : self._log_rnd + 4]))
         if self._est is not None:  # the last epoch's SSE / (12 B) of the iteration's estimator update
             summary["estimator/loss"] = s[-1]
         self.recorder.record_statistics(summary, it)
@@ -1576,6 +1627,8 @@ class Runner:
             d[h + ne + 4 : h + ne + 5].copy_(self.env.terrain_level_sum())
         if self.value_norm is not None:
             d[self._log_vn : self._log_vn + 3].copy_(self.value_norm.state)
+        if self._rnd_trainer is not None:
+            d[self._log_rnd : self._log_rnd + 4].copy_(self._rnd_trainer.log)
         if self._est is not None:
             d[-1:].copy_(self._est_trainer.loss)
         self._flush_log()  # the previous iteration's scalars: their copy finished long ago

@@ -59,7 +59,8 @@ if __name__ == "__main__":
               "at (x_i, y_j) in the robot's yaw frame".format(num_obs, (num_obs - P) // 47, P, xs[0], xs[-1], len(xs), ys[0], ys[-1], len(ys), len(ys)))
     model = ActorCritic(cfg["env"]["num_actions"], num_obs, num_priv, actor_hidden=hidden_of(sd, "actor"),
                         critic_hidden=hidden_of(sd, "critic"), **est_args)
-    model.load_state_dict(sd)
+    # rnd.enabled: the checkpoint's curiosity networks ("rnd_predictor.*", "rnd_target.*") belong to training and are not built here
+    model.load_state_dict({k: v for k, v in sd.items() if not k.startswith(("rnd_predictor.", "rnd_target."))})
     if ckpt.get("obs_normalizer") is not None:
         # algorithm.empirical_normalization: the statistics go into the first Linear layer (W' = W diag(inv_std), b' = b - W' mean), so the exported
         # module still takes the raw observation deploy/utils/policy.py builds

@@ -416,6 +416,22 @@ int bg_distill_act_mix(int32_t N, const float* teacher_obs, int32_t teacher_stri
 int bg_actor_sample_est(int32_t N, const float* obs, int32_t n_est, const bg_mlp_layer_desc* est, int32_t est_cols, int32_t n_actor,
                         const bg_mlp_layer_desc* actor, const float* logstd, uint64_t seed, uint64_t counter, float* est_out, float* mu, float* actions,
                         void* stream);
+/* Random network distillation (T1.yaml rnd.enabled; rsl_rl's rnd_cfg, Burda et al. 2018): the rollout's launch behind the env step.  TWO networks of
+ * bg_actor_sample_mlp's kind on the same state rows, one behind the other in the same workgroup: `target` (random, never trained) and `predictor`,
+ * each an MLP K -> hidden -> 12 with K = obs_cols + priv_cols (1 <= K <= BG_ACTOR_MAX_INPUT, any K; hidden widths as bg_actor_sample_mlp).  The state
+ * row is [obs row | priv row], the two blocks contiguous each ([N][obs_cols], [N][priv_cols]; priv NULL with priv_cols 0 and only then) and joined in
+ * LDS, without a concatenated copy.  Per row r < N:
+ *   target_out[r][0..12) = target(s);  rho = sqrt(sum_j (predictor(s)_j - target(s)_j)^2), the 12 terms added in ascending j in fp32;
+ *   intrinsic[r] = dones[r] ? 0 : rho;  and, where weight != 0 and dones[r] == 0,
+ *   rewards[r] = (float)((double)rewards[r] + (double)weight * reward_stats[2] * rho)      (one rounding to fp32)
+ * reward_stats: device fp32 [3] = (mean, sigma, 1 / sigma) as bg_value_norm_update writes it, of which 1 / sigma alone is read; NULL = 1.  With
+ * weight == 0 (of either sign) rewards is not written at all; a row with dones never is.  weight: a finite number >= 0, else -1.  Both embeddings equal
+ * the mu of bg_actor_sample_mlp_scan of the network on a contiguous copy of the rows, bit for bit.  One LDS form for both networks: the 256-wide form
+ * when both networks' widest hidden layer and the padded state tile (K rounded up to whole 48-column k-chunks) are at most 256 columns.  A violation
+ * is -1 or -4 with a message naming the side, before any launch.  No atomics; nothing is written past row N. */
+int bg_rnd_reward(int32_t N, const float* obs, int32_t obs_cols, const float* priv, int32_t priv_cols, int32_t n_target, const bg_mlp_layer_desc* target,
+                  int32_t n_pred, const bg_mlp_layer_desc* predictor, const uint8_t* dones, const float* reward_stats, float weight, float* target_out,
+                  float* intrinsic, float* rewards, void* stream);
 /* A recurrent student (T1.yaml distillation.student_memory; rsl_rl's recurrent student of `Distillation`): a GRU cell in torch.nn.GRUCell's layout and
  * gate order r | z | n, W_ih [3 hidden][in], W_hh [3 hidden][hidden] (16-byte aligned), b_ih / b_hh [3 hidden]:
  *   gi = x W_ih^T + b_ih, gh = h W_hh^T + b_hh, r = sigmoid(gi_r + gh_r), z = sigmoid(gi_z + gh_z), n = tanh(gi_n + r gh_n), h' = (1 - z) n + z h.
