@@ -153,6 +153,8 @@ class EnvCfg(C.Structure):
         ("actor_heights", C.c_int32), ("noise_height_measurements", Rand),
         ("student_frame_stack", C.c_int32),
         ("priv_extras", C.c_int32), ("priv_force_scale", C.c_float), ("priv_clearance_scale", C.c_float),
+        ("sensor_model", C.c_int32), ("sensor_bias_gravity", Rand), ("sensor_bias_ang_vel", Rand), ("sensor_bias_dof_pos", Rand),
+        ("sensor_bias_dof_vel", Rand), ("sensor_latency_lo", C.c_float), ("sensor_latency_hi", C.c_float),
     ]
 
 
@@ -185,7 +187,7 @@ def eval_track_plane(c, k):
 SYMBOLS = [
     "bg_model_create", "bg_model_get", "bg_model_destroy", "bg_model_load_urdf", "bg_model_body_name", "bg_model_dof_name", "bg_model_find_body", "bg_env_create", "bg_env_destroy", "bg_env_set_heightfield",
     "bg_env_set_params", "bg_env_bind_outputs", "bg_env_reset", "bg_env_step", "bg_env_step_to", "bg_env_bind_student_obs", "bg_env_step_to_student", "bg_env_get_state",
-    "bg_env_set_state", "bg_env_get_field", "bg_env_set_field", "bg_env_field_info", "bg_env_get_curriculum", "bg_env_set_curriculum", "bg_env_step_count", "bg_env_set_step_count",
+    "bg_env_set_state", "bg_env_get_field", "bg_env_set_field", "bg_env_field_info", "bg_env_get_curriculum", "bg_env_set_curriculum", "bg_env_step_count", "bg_env_set_step_count", "bg_env_sensor_launches",
     "bg_env_get_terrain_level_sum", "bg_env_set_terrain_level_sum", "bg_env_eval_begin", "bg_env_eval_step",
     "bg_env_forward_dynamics", "bg_env_forward_dynamics_packed", "bg_sim_bind_state", "bg_sim_set_actuation", "bg_sim_apply_body_wrench_local", "bg_sim_simulate",
     "bg_sim_refresh_body_state", "bg_sim_write_root_state", "bg_sim_write_dof_state", "bg_gae", "bg_ppo_loss", "bg_gaussian_logp", "bg_actor_pack", "bg_actor_sample", "bg_actor_sample_mlp", "bg_actor_sample_mlp_scan", "bg_distill_act", "bg_distill_act_hist", "bg_distill_act_mix", "bg_actor_sample_est", "bg_adam_step", "bg_adapt_lr", "bg_optimizer_step", "bg_elu_backward_colsum", "bg_mlp_layer_forward", "bg_mlp_chain_forward", "bg_critic_values_gae", "bg_mlp_chain_forward_group", "bg_mlp_chain_forward_split", "bg_mlp_chain_backward_split", "bg_mlp_split_weights_pm", "bg_mlp_layer_backward", "bg_mlp_split_weights", "bg_mlp_layer_forward_split", "bg_mlp_layer_backward_split", "bg_mlp_weight_grad", "bg_mlp_weight_grad_group", "bg_mlp_weight_grad_group_partial", "bg_update_tail", "bg_update_tail_sums", "bg_mlp_weight_grad_group_split", "bg_mlp_weight_grad_group_split_partial",
@@ -248,6 +250,7 @@ def load():
         "bg_env_eval_step": (i32, [vp, vp, vp, vp, i32, vp, vp]),
         "bg_env_step_count": (i64, [vp]),
         "bg_env_set_step_count": (i32, [vp, i64]),
+        "bg_env_sensor_launches": (i64, [vp]),
         "bg_env_forward_dynamics": (i32, [vp, vp, vp, vp, vp, vp, vp, vp]),
         "bg_env_forward_dynamics_packed": (i32, [vp, vp, vp, vp, vp, vp, vp, vp]),
         "bg_sim_bind_state": (i32, [vp, vp, vp, vp, vp]),

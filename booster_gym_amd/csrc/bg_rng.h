@@ -71,7 +71,10 @@ enum {
     RS_ACTOR = 32,    // + k : action noise (bg_actor_sample)
     // (the env-step kernels and resample_apply_kernel add 64 to their ids at reset-all: 64 .. 64 + RS_TLEVEL are in use as well)
     RS_SCAN = 128,       // + (p >> 2), p < 1024 : noise of the actor's height scan, point p at entry p & 3 (bg_obs_assemble): 128 .. 383
-    RS_SCAN_RESET = 384  // + (p >> 2) : the same at reset-all, which shares its step counter with the step that follows it: 384 .. 639
+    RS_SCAN_RESET = 384, // + (p >> 2) : the same at reset-all, which shares its step counter with the step that follows it: 384 .. 639
+    RS_SENSOR = 640,       // + (s >> 2), s < 30 : the episode's bias of sensor column s at entry s & 3; + 8 : entry 0 = the u of the episode's latency
+                           // (bg_obs_sensor, on the step that resets the env): 640 .. 648
+    RS_SENSOR_RESET = 656  // the same at reset-all: 656 .. 664
 };
 
 }  // namespace bg

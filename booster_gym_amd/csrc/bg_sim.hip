@@ -48,6 +48,9 @@ struct bg_env {
     int hist_head = 0;        // ... the plane of the newest one: the env-step kernels of a launch sequence write their observations there
     int hist_planes = 0;      // R, the planes of the ring: cfg.frame_stack, or cfg.student_frame_stack = Hs when that is on
     float* student_bound = nullptr;  // [n][47 Hs]: the student's row of bg_env_reset / bg_env_step (bg_env_bind_student_obs), the caller's
+    float* sensor_bias = nullptr;    // [n][30]: the episode's bias of every sensor column, normalisation included (cfg.sensor_model; bg_obs_sensor)
+    float* sensor_lat = nullptr;     // [n]: the episode's latency in env steps
+    int64_t sensor_launches = 0;     // bg_obs_sensor launches enqueued (bg_env_sensor_launches)
     ModelDev* model_dev = nullptr;
     PairModel* pair_dev = nullptr;  // the leg constants with the two legs side by side (packed ABA kernel)
     int16_t* hf = nullptr;
@@ -331,6 +334,91 @@ __global__ __launch_bounds__(STACK_BLOCK) void bg_obs_stack(int n, int H, int he
     float v = 0.f;
     if (k + 1u == (unsigned)H || !(all_reset || done[e])) v = *src;
     else *src = 0.f;
+    dst[t] = v;
+}
+
+// ------------------------------------------------------------------ sensor model of the actor's row (cfg.sensor_model)
+// A bias that stays put for an episode and a sensing delay on the 30 sensor columns (gravity 0-2, angular velocity 3-5, dof_pos 11-22, dof_vel 23-34;
+// sensor column s = c for c < 6, c - 5 otherwise) of every frame of the row [47 H]; commands, gait clock and last actions are the controller's own
+// values and pass untouched.  The launch stands where bg_obs_stack stands (the last of every env step and reset-all) and has its form: one thread
+// per destination element, a row's elements on consecutive lanes, the destination out in whole lines, the ring read in runs of 47 floats.  The ring
+// has R = H + ceil(latency hi) planes and is never zeroed: with age = the env's stored episode length (I_EP_LEN: 0 on the step that reset the env and
+// after reset-all, + 1 per env step), the observation of j steps ago is plane head - j (mod R) for j <= age, and
+//   frame k (d = H - 1 - k steps ago):  zero when d > age (bg_obs_stack's reset rule, by comparison instead of by zeroed planes);
+//   a non-sensor column: o(d), bit for bit;
+//   a sensor column: a = o(min(d + i, age)), b = o(min(d + i + 1, age)), i = floor(lam), f = lam - i:  a + f (b - a) + beta[s]
+// (a sensor that has only seen this episode reports its first reading, never the episode before).  d + i <= R - 1 always, and d + i + 1 <= R - 1 where
+// f != 0; b is not read where f = 0, the interpolation not compiled into the path at all when the range is [0, 0], the add skipped for a group without
+// a bias entry, so an env with nothing configured gets bg_obs_stack's bits.  Per-env scalars (reset flag, age, lam) are read once per thread.
+// On a step that resets the env only the newest frame is non-zero (age = 0) and needs neither lam (a = b) nor a stored bias: its thread of sensor
+// column s draws beta[s] itself (Philox is counter-based: no exchange) and stores it, the thread of column 6 stores lam.  Nobody reads bias or
+// latency of an env in the launch that writes them, and nobody writes the ring: deterministic, no atomics, no LDS.
+struct SensorArgs {
+    bg_rand bias[4];  // gravity, ang_vel, dof_pos, dof_vel (mode 0, 1 or 3)
+    float norm[4];    // the groups' normalization.* factors
+    float lo, hi;     // latency range, env steps
+    uint64_t seed;
+};
+constexpr int SENSOR_COLS = BG_NUM_SENSOR_COLS, SENSOR_LAT_STREAM = 8, SENSOR_LAT_COL = 6;
+__global__ __launch_bounds__(STACK_BLOCK) void bg_obs_sensor(int n, int H, int R, int head, int all_reset, uint32_t step, uint32_t stream0, SensorArgs A,
+                                                             const float* __restrict__ ring, const uint8_t* __restrict__ done,
+                                                             const int32_t* __restrict__ ep_len, float* bias, float* lat, float* __restrict__ dst) {
+    const unsigned W = (unsigned)(BG_NUM_OBS * H);
+    const unsigned t = blockIdx.x * STACK_BLOCK + threadIdx.x;  // (n 47 H < 2^31: bg_env_create)
+    if (t >= (unsigned)n * W) return;
+    const unsigned e = t / W, col = t - e * W, k = col / BG_NUM_OBS, c = col - k * BG_NUM_OBS;
+    const bool reset = all_reset || done[e];
+    const int age = reset ? 0 : ep_len[e];
+    const int d = H - 1 - (int)k;  // frame k = the observation of d steps ago
+    const bool delayed = A.hi > 0.f;
+    if (reset && d == 0 && c == SENSOR_LAT_COL) {  // the episode's latency, by the one thread of the env's newest command column
+        float u[4];
+        rand4_uniform(A.seed, e, step, stream0 + SENSOR_LAT_STREAM, u);
+        lat[e] = A.lo + (A.hi - A.lo) * u[0];
+    }
+    if (d > age) { dst[t] = 0.f; return; }
+    const int s = c < 6u ? (int)c : (c >= 11u && c < 35u) ? (int)c - 5 : -1;
+    int j = d, i = 0;
+    float f = 0.f;
+    if (s >= 0 && delayed && !reset) {
+        const float lam = lat[e];
+        i = (int)lam;  // (lam >= 0: floor)
+        f = lam - (float)i;
+        j = min(min(d + i, age), R - 1);  // (the second min never binds: d + i <= H - 1 + ceil(hi))
+    }
+    int slot = head - j;
+    if (slot < 0) slot += R;
+    float v = ring[((size_t)slot * n + e) * BG_NUM_OBS + c];
+    if (s < 0) { dst[t] = v; return; }
+    if (delayed && f != 0.f) {
+        int sb = head - min(min(d + i + 1, age), R - 1);
+        if (sb < 0) sb += R;
+        const float b = ring[((size_t)sb * n + e) * BG_NUM_OBS + c];
+        v = v + f * (b - v);
+    }
+    const int g = s < 3 ? 0 : s < 6 ? 1 : s < 18 ? 2 : 3;
+    const bg_rand spec = g == 0 ? A.bias[0] : g == 1 ? A.bias[1] : g == 2 ? A.bias[2] : A.bias[3];
+    if (spec.mode != 0) {
+        float beta;
+        if (reset) {
+            const int q = s & 3;
+            float u = 0.f, nr = 0.f;
+            if (spec.mode <= 2) {
+                const Rand4 r = rand4(A.seed, e, step, stream0 + (uint32_t)(s >> 2));
+                nr = q == 0 ? r.n[0] : q == 1 ? r.n[1] : q == 2 ? r.n[2] : r.n[3];
+            } else {
+                float uu[4];
+                rand4_uniform(A.seed, e, step, stream0 + (uint32_t)(s >> 2), uu);
+                u = q == 0 ? uu[0] : q == 1 ? uu[1] : q == 2 ? uu[2] : uu[3];
+            }
+            const float norm = g == 0 ? A.norm[0] : g == 1 ? A.norm[1] : g == 2 ? A.norm[2] : A.norm[3];
+            beta = apply_rand(0.f, spec, u, nr) * norm;
+            bias[(size_t)e * SENSOR_COLS + s] = beta;
+        } else {
+            beta = bias[(size_t)e * SENSOR_COLS + s];
+        }
+        v += beta;
+    }
     dst[t] = v;
 }
 
@@ -1000,8 +1088,16 @@ static int env_create_fill(bg_env* e, const bg_env_cfg* cfg, const bg_model* mod
         HIP_OK(hipMemcpy(e->scan_xy, cfg->height_scan_xy, sizeof(float) * 2 * cfg->height_scan_points, hipMemcpyHostToDevice));
     }
     if (cfg->actor_heights && cfg->frame_stack == 0) e->cfg.frame_stack = 1;  // (a ring of one plane; without the key the field stays as passed)
-    if (cfg->frame_stack > 1 || cfg->actor_heights) {  // the ring of single observations, all zeros: an env that has never been reset has an empty history
+    if (cfg->sensor_model && cfg->frame_stack == 0) e->cfg.frame_stack = 1;  // (the same: the sensor model's ring exists at H = 1 too)
+    if (cfg->sensor_model) {  // the episode's draws, zeros until the first reset writes them (a group without a bias entry keeps its zeros)
+        HIP_OK(hipMalloc(&e->sensor_bias, sizeof(float) * n * SENSOR_COLS));
+        HIP_OK(hipMemset(e->sensor_bias, 0, sizeof(float) * n * SENSOR_COLS));
+        HIP_OK(hipMalloc(&e->sensor_lat, sizeof(float) * n));
+        HIP_OK(hipMemset(e->sensor_lat, 0, sizeof(float) * n));
+    }
+    if (cfg->frame_stack > 1 || cfg->actor_heights || cfg->sensor_model) {  // the ring of single observations, all zeros: an env that has never been reset has an empty history
         e->hist_planes = cfg->student_frame_stack ? cfg->student_frame_stack : e->cfg.frame_stack;  // (the student's longer history: R = Hs planes)
+        if (cfg->sensor_model) e->hist_planes += (int)ceilf(cfg->sensor_latency_hi);  // (the delayed reading of the oldest frame: at most BG_MAX_SENSOR_LATENCY more)
         const size_t hb = sizeof(float) * (size_t)e->hist_planes * n * BG_NUM_OBS;
         HIP_OK(hipMalloc(&e->hist, hb));
         HIP_OK(hipMemset(e->hist, 0, hb));
@@ -1058,6 +1154,19 @@ extern "C" int bg_env_create(const bg_env_cfg* cfg, const bg_model* model, bg_en
     if ((cfg->priv_extras & ~BG_PRIV_EXTRA_ALL) != 0 ||
         (cfg->priv_extras != 0 && (int64_t)cfg->num_envs * (BG_NUM_PRIV + cfg->height_scan_points + priv_extras_columns(cfg->priv_extras)) >= (int64_t)1 << 31))
         return fail(-1, "bg_env_create: priv_extras must be a combination of BG_PRIV_EXTRA_FEET | GROUND | JOINTS (0 = off) with num_envs x (14 + height_scan_points + extras) below 2^31");
+    if (cfg->sensor_model != 0) {
+        if (cfg->sensor_model != 1) return fail(-1, "bg_env_create: sensor_model must be 0 (off) or 1");
+        if (cfg->actor_heights) return fail(-1, "bg_env_create: sensor_model is not available with actor_heights (bg_obs_assemble writes those rows, and the student's)");
+        const bg_rand* sb[4] = {&cfg->sensor_bias_gravity, &cfg->sensor_bias_ang_vel, &cfg->sensor_bias_dof_pos, &cfg->sensor_bias_dof_vel};
+        // (a test on the stored bits, never on a float value: this file is compiled with finite-math-only, which folds any other form away)
+        const auto finite = [](const float& x) { uint32_t b; memcpy(&b, &x, sizeof(b)); return ((b >> 23) & 0xFFu) != 0xFFu; };
+        for (const bg_rand* r : sb)
+            if ((r->mode != 0 && r->mode != 1 && r->mode != 3) || (r->mode != 0 && (!finite(r->a) || !finite(r->b) || (r->mode == 1 && r->b < 0.f))))
+                return fail(-1, "bg_env_create: sensor_bias_* must be mode 0 (none), 1 (gaussian additive, std >= 0) or 3 (uniform additive) with a finite range");
+        if (!finite(cfg->sensor_latency_lo) || !finite(cfg->sensor_latency_hi) ||
+            !(cfg->sensor_latency_lo >= 0.f && cfg->sensor_latency_lo <= cfg->sensor_latency_hi && cfg->sensor_latency_hi <= (float)BG_MAX_SENSOR_LATENCY))
+            return fail(-1, "bg_env_create: the sensor latency needs 0 <= sensor_latency_lo <= sensor_latency_hi <= BG_MAX_SENSOR_LATENCY");
+    }
     int ndev = 0;
     hipError_t de = hipGetDeviceCount(&ndev);
     if (de != hipSuccess || ndev == 0) return fail(-3, "bg_env_create: no HIP device available (this library has no CPU path)");
@@ -1077,6 +1186,7 @@ extern "C" void bg_env_destroy(bg_env* e) {
     if (!e) return;
     (void)hipFree(e->sim_tau); (void)hipFree(e->sim_bforce); (void)hipFree(e->sim_btorque);
     (void)hipFree(e->f); (void)hipFree(e->h); (void)hipFree(e->lowmask); (void)hipFree(e->fd_mask); (void)hipFree(e->fd_list); (void)hipFree(e->fd_count); (void)hipFree(e->rs_counts); (void)hipFree(e->i); (void)hipFree(e->stats); (void)hipFree(e->model_dev); (void)hipFree(e->pair_dev); (void)hipFree(e->hf); (void)hipFree(e->curr); (void)hipFree(e->curr_read); (void)hipFree(e->tcur); (void)hipFree(e->scan_xy); (void)hipFree(e->hist);
+    (void)hipFree(e->sensor_bias); (void)hipFree(e->sensor_lat);
     delete e;
 }
 
@@ -1198,7 +1308,17 @@ static int launch_step(bg_env* e, const float* actions, int mode, const StepOut&
     if (e->hist && !e->cfg.actor_heights) {  // last: every launch that writes the single observation (kernel B and resample_apply_kernel included) is in front of it
         const int H = e->cfg.frame_stack;
         dim3 gs((unsigned)(((int64_t)e->n * BG_NUM_OBS * H + STACK_BLOCK - 1) / STACK_BLOCK));
-        hipLaunchKernelGGL(bg_obs_stack, gs, dim3(STACK_BLOCK), 0, st, e->n, H, e->hist_head, mode, e->hist, (const uint8_t*)out.done, dst.obs);
+        if (e->cfg.sensor_model) {  // in its place: the same row through the sensor model (bg_obs_sensor), H = 1 included
+            const bg_env_cfg& c = e->cfg;
+            const SensorArgs A = {{c.sensor_bias_gravity, c.sensor_bias_ang_vel, c.sensor_bias_dof_pos, c.sensor_bias_dof_vel},
+                                  {c.norm_gravity, c.norm_ang_vel, c.norm_dof_pos, c.norm_dof_vel}, c.sensor_latency_lo, c.sensor_latency_hi, c.seed};
+            const uint32_t base = mode ? (uint32_t)bg::RS_SENSOR_RESET : (uint32_t)bg::RS_SENSOR;
+            hipLaunchKernelGGL(bg_obs_sensor, gs, dim3(STACK_BLOCK), 0, st, e->n, H, e->hist_planes, e->hist_head, mode, cnt, base, A, (const float*)e->hist,
+                               (const uint8_t*)out.done, (const int32_t*)(e->i + (size_t)I_EP_LEN * e->n), e->sensor_bias, e->sensor_lat, dst.obs);
+            e->sensor_launches++;
+        } else {
+            hipLaunchKernelGGL(bg_obs_stack, gs, dim3(STACK_BLOCK), 0, st, e->n, H, e->hist_head, mode, e->hist, (const uint8_t*)out.done, dst.obs);
+        }
     }
     HIP_OK(hipGetLastError());
     if (e->cfg.curriculum && mode == 0)  // publish this step's curriculum increments to the next step's samplers
@@ -1298,7 +1418,20 @@ static int terrain_field(const char* name) {
     if (strcmp(name, "terrain_type") == 0) return 1;
     return -1;
 }
+// the sensor model's per-env draws (allocated only with cfg.sensor_model; read-only: bg_env_get_field): components, or 0
+static int sensor_field(const char* name) {
+    if (!name) return 0;
+    if (strcmp(name, "sensor_bias") == 0) return SENSOR_COLS;
+    if (strcmp(name, "sensor_latency") == 0) return 1;
+    return 0;
+}
 extern "C" int bg_env_field_info(bg_env* e, const char* name, int32_t* comps, int32_t* is_int) {
+    if (const int sf = sensor_field(name); sf > 0) {
+        if (!e || !e->sensor_bias) return fail(-1, std::string("field ") + name + " exists only with the sensor model (sensors.enabled: true)");
+        if (comps) *comps = sf;
+        if (is_int) *is_int = 0;
+        return 0;
+    }
     if (terrain_field(name) >= 0) {
         if (!e || !e->tcur) return fail(-1, std::string("field ") + name + " exists only with the terrain curriculum (terrain.curriculum: true)");
         if (comps) *comps = 1;
@@ -1315,6 +1448,11 @@ extern "C" int bg_env_get_field(bg_env* e, const char* name, void* dst, void* st
     if (!e || !dst) return fail(-1, "bg_env_get_field: null argument");
     if (name && strcmp(name, "episode_stats") == 0) {  // global accumulator, STATS_COUNT floats
         HIP_OK(hipMemcpyAsync(dst, e->stats, sizeof(float) * STATS_COUNT, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return 0;
+    }
+    if (const int sf = sensor_field(name); sf > 0) {  // env-major already: [n][30], [n]
+        if (!e->sensor_bias) return fail(-1, std::string("field ") + name + " exists only with the sensor model (sensors.enabled: true)");
+        HIP_OK(hipMemcpyAsync(dst, sf == 1 ? e->sensor_lat : e->sensor_bias, sizeof(float) * e->n * sf, hipMemcpyDeviceToDevice, (hipStream_t)stream));
         return 0;
     }
     if (const int tf = terrain_field(name); tf >= 0) {
@@ -1376,6 +1514,7 @@ extern "C" int bg_env_set_terrain_level_sum(bg_env* e, const int32_t* sum, void*
     return 0;
 }
 extern "C" int64_t bg_env_step_count(const bg_env* e) { return e ? e->step_count : -1; }
+extern "C" int64_t bg_env_sensor_launches(const bg_env* e) { return e ? e->sensor_launches : -1; }
 extern "C" int bg_env_set_step_count(bg_env* e, int64_t c) {
     if (!e) return fail(-1, "bg_env_set_step_count: null env");
     e->step_count = c;

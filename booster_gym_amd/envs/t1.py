@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..utils.sensors import GROUPS as SENSOR_GROUPS, SENSOR_COLUMNS, sensors_cfg
 from ..utils.terrain import actor_heights_of
 from ..utils.urdf import load_model
 from ..utils.utils import rand_spec
@@ -211,6 +212,7 @@ class T1(BaseTask):
         student_frame_stack_of(cfg)
         if "feet" in privileged_extras_of(cfg)[0]:
             contact_force_scale_of(cfg)
+        sensors_cfg(cfg)
         self._lib = _lib.load()
         self._model = None
         self._env = None
@@ -338,6 +340,8 @@ class T1(BaseTask):
         # the student's longer history (distillation.student_frame_stack through env.student_frame_stack): a second row [47 Hs] per env; 0 = off
         self.student_frame_stack = student_frame_stack_of(cfg)
         self.num_student_obs = self.num_single_obs * self.student_frame_stack
+        # the sensor model (sensors.enabled): an episode's bias and latency on the 30 sensor columns of every frame, by bg_obs_sensor; None = off
+        self.sensors = sensors_cfg(cfg)
         self.dt = cfg["control"]["decimation"] * cfg["sim"]["dt"]
         N, dev = self.num_envs, self.device
         self.obs_buf = torch.zeros(N, self.num_obs, dtype=torch.float, device=dev)
@@ -456,6 +460,11 @@ class T1(BaseTask):
                     setr(c.noise_height_measurements, nc.get("height_measurements"))
         c.frame_stack = self.frame_stack
         c.student_frame_stack = self.student_frame_stack
+        if self.sensors is not None:  # (off: the seven fields stay zero, as in a struct older than them)
+            c.sensor_model = 1
+            for g, entry in zip(SENSOR_GROUPS, self.sensors.bias):
+                setr(getattr(c, "sensor_bias_" + g), entry)
+            c.sensor_latency_lo, c.sensor_latency_hi = self.sensors.latency_steps
         if self.privileged_extras:  # (off: the three fields stay zero, as in a struct older than them)
             c.priv_extras = sum(bit for g, bit, _ in _lib.PRIV_EXTRA_GROUPS if g in self.privileged_extras)
             if "feet" in self.privileged_extras:
@@ -757,6 +766,31 @@ class T1(BaseTask):
     @property
     def commands(self):
         return self.get_field("commands")
+
+    # ---- the sensor model's state (sensors.enabled: true only; the library refuses the two fields without it)
+    @property
+    def sensor_model(self):
+        return self.sensors is not None
+
+    @property
+    def sensor_columns(self):
+        """The 30 columns of the single observation that carry the bias and the latency, in the order of `sensor_bias`'s columns."""
+        return SENSOR_COLUMNS
+
+    @property
+    def sensor_bias(self):
+        """[N][30]: every env's bias of this episode per sensor column, in the observation's units (normalization.* included)."""
+        return self.get_field("sensor_bias")
+
+    @property
+    def sensor_latency(self):
+        """[N]: every env's sensing delay of this episode, in policy steps."""
+        return self.get_field("sensor_latency").squeeze(-1)
+
+    @property
+    def sensor_launches(self):
+        """bg_obs_sensor launches this env has enqueued (0 for ever with the model off)."""
+        return int(self._lib.bg_env_sensor_launches(self._env))
 
     @property
     def episode_length_buf(self):

@@ -192,7 +192,27 @@ typedef struct {
     int32_t priv_extras;
     float priv_force_scale;     /* normalization.contact_force; read with BG_PRIV_EXTRA_FEET only */
     float priv_clearance_scale; /* normalization.height_measurements; read with BG_PRIV_EXTRA_FEET only */
+    /* Sensor model of the actor's row (T1.yaml sensors; an addition of this build, IsaacLab's NoiseModelWithAdditiveBias and a sensing delay).
+     * sensor_model = 0 = off (a zero-initialised struct: every caller older than the field): nothing below is read and every launch is as without it.
+     * 1 (not with actor_heights, else bg_env_create fails): the env keeps a ring of frame_stack + ceil(sensor_latency_hi) single observations, also
+     * at frame_stack 1, and one launch (bg_obs_sensor), the last of every env step and reset-all, in the place of bg_obs_stack, writes the actor's row
+     * [N][47 H].  With age = the env steps since the env's last reset (0 on the step that reset it; the field "episode_length_buf") and o(j) the stored
+     * single observation of j steps ago, frame k (d = H - 1 - k steps ago) is zero when d > age (bg_obs_stack's reset rule), else o(d) in every column
+     * but the 30 sensor columns (gravity 0-2, angular velocity 3-5, dof_pos 11-22, dof_vel 23-34; sensor column s = c for c < 6, c - 5 otherwise), which
+     * are, with i = floor(lam), f = lam - i, a = o(min(d + i, age)), b = o(min(d + i + 1, age)):  a + f (b - a) + beta[s]  in fp32.  The interpolation
+     * is left out when sensor_latency_lo = sensor_latency_hi = 0 (and b is not read where f = 0), the add for a group whose sensor_bias_* has mode 0.
+     * On the step that resets an env (every env, for bg_env_reset) the launch draws and stores, until the env's next reset,
+     *   beta[s] = apply_rand(0, sensor_bias_<group of s>, u, n) * norm_<group>  on entry s & 3 of Philox(seed, env, step count, RS_SENSOR + (s >> 2)),
+     *   lam     = sensor_latency_lo + (sensor_latency_hi - sensor_latency_lo) * u  on entry 0 of stream RS_SENSOR + 8
+     * (RS_SENSOR_RESET at bg_env_reset; csrc/bg_rng.h).  Fields "sensor_bias" [N][30] and "sensor_latency" [N] read them back (bg_env_get_field only).
+     * The env-step kernels, the privileged row and every other stream are untouched.  sensor_bias_*: mode 0 (none), 1 (gaussian additive: a = mean,
+     * b = std >= 0) or 3 (uniform additive: a = low, b = high), finite; 0 <= sensor_latency_lo <= sensor_latency_hi <= BG_MAX_SENSOR_LATENCY. */
+    int32_t sensor_model;
+    bg_rand sensor_bias_gravity, sensor_bias_ang_vel, sensor_bias_dof_pos, sensor_bias_dof_vel; /* sensors.bias.*, in physical units */
+    float sensor_latency_lo, sensor_latency_hi;                                                 /* sensors.latency_steps, in env steps */
 } bg_env_cfg;
+#define BG_NUM_SENSOR_COLS 30    /* columns of the field "sensor_bias" */
+#define BG_MAX_SENSOR_LATENCY 2  /* the most of sensor_latency_hi */
 #define BG_PRIV_EXTRA_FEET 1
 #define BG_PRIV_EXTRA_GROUND 2
 #define BG_PRIV_EXTRA_JOINTS 4
@@ -269,6 +289,9 @@ int bg_env_get_terrain_level_sum(bg_env* env, int32_t* sum_device, void* stream)
 int bg_env_set_terrain_level_sum(bg_env* env, const int32_t* sum_device, void* stream);
 int64_t bg_env_step_count(const bg_env* env);
 int bg_env_set_step_count(bg_env* env, int64_t count);
+/* bg_obs_sensor launches this env has enqueued since bg_env_create (cfg.sensor_model: one per env step and per reset-all; 0 for ever with the
+ * model off), -1 for a null env.  A host counter, for tests and tools that must know which launch wrote the actor's row. */
+int64_t bg_env_sensor_launches(const bg_env* env);
 /* ---- evaluation record: per-robot metrics of every env's FIRST episode, kept by one launch after each env step (evaluate.py).  Not part of
  * bg_env_step's launch sequence: a training run that never calls these launches nothing new.  `record` is the caller's device float
  * [BG_EVAL_PLANES][N], plane-major (a wave's loads and stores are contiguous):

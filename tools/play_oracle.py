@@ -168,6 +168,8 @@ def rollout(layers, cmd, seconds, cfg=None, dyn=None, model=None, height_points=
     from oracle.dyn_ref import DynRef
 
     cfg = cfg or load_cfg("T1")
+    if (cfg.get("sensors") or {}).get("enabled"):
+        print("play_oracle: sensors.enabled is not modelled here: the oracle feeds the policy the true, undelayed observation (noise, bias and latency are the env's)")
     model = model or load_model(cfg["asset"]["file"])
     dyn = dyn or DynRef(model, feet_edge_pos=cfg["asset"]["feet_edge_pos"])
     nz = cfg["normalization"]
