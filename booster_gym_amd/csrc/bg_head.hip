@@ -249,6 +249,11 @@ __device__ __forceinline__ void bc_row(bool live, float gscale, const float (&m)
 // (M_a d)[a] = sign[a] d[src[a]]); acc_sym = sum d^2.  A wave holds 16 rows, all of them original or all mirrored: `mirror` is uniform per wave,
 // so what runs under it may use the DPP moves, which run in whole waves.
 constexpr int HEAD_NSTAT_SYM = HEAD_NSTAT + 1;
+// the scratch the header promises holds the largest launch: HEAD_MAX_GRID records of the widest head and, behind them, the float64 statistics
+// (2 floats each) of the head with the most of them, one per workgroup
+static_assert(head_stat_base<HA>() + 2 * (size_t)HEAD_MAX_GRID * HEAD_NSTAT_SYM <= (size_t)BG_HEAD_SCRATCH_FLOATS,
+              "BG_HEAD_SCRATCH_FLOATS is too small for the heads' records and statistics");
+static_assert(HEAD_NSTAT_SYM >= HEAD_NSTAT && head_record<HA>() >= head_record<1>(), "the sym head is the largest user of the scratch");
 struct ActionMirror { int src[HA]; float sign[HA]; };
 struct SymThread {
     static constexpr int A = HA;

@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void mlp_colsum_finish_kernel(int nb, int C, c
 extern "C" int bg_mlp_layer_forward(int32_t M, int32_t K, int32_t N, const float* X, const float* W, const float* bias, float* Y, int32_t elu,
                                     void* stream) {
     if (M <= 0 || !X || !W || !bias || !Y) return bg_set_error(-1, "bg_mlp_layer_forward: bad argument");
-    if ((((uintptr_t)X | (uintptr_t)W | (uintptr_t)Y) & 15) != 0) return bg_set_error(-1, "bg_mlp_layer_forward: pointers must be 16-byte aligned");
+    if ((((uintptr_t)X | (uintptr_t)W | (uintptr_t)bias | (uintptr_t)Y) & 15) != 0) return bg_set_error(-1, "bg_mlp_layer_forward: pointers must be 16-byte aligned");
     if (N % 128 != 0 || N > 1024) return bg_set_error(-4, "bg_mlp_layer_forward: unsupported N (multiples of 128 up to 1024)");
     dim3 grid((((M + FW_BM - 1) / FW_BM + 7) / 8) * 8 * (N / 128)), block(256);  // slabs padded to groups of 8 (mlp_fwd_kernel's XCD-aware mapping)
     hipStream_t st = (hipStream_t)stream;

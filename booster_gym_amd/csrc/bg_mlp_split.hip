@@ -245,7 +245,7 @@ extern "C" int bg_mlp_split_weights_pm(int32_t n_out, int32_t k_out, const float
 extern "C" int bg_mlp_layer_forward_split(int32_t M, int32_t K, int32_t N, const float* X, const uint16_t* planes, const float* bias, float* Y,
                                           int32_t elu, int32_t terms, void* stream) {
     if (M <= 0 || !X || !planes || !bias || !Y) return bg_set_error(-1, "bg_mlp_layer_forward_split: bad argument");
-    if ((((uintptr_t)X | (uintptr_t)planes | (uintptr_t)Y) & 15) != 0) return bg_set_error(-1, "bg_mlp_layer_forward_split: pointers must be 16-byte aligned");
+    if ((((uintptr_t)X | (uintptr_t)planes | (uintptr_t)bias | (uintptr_t)Y) & 15) != 0) return bg_set_error(-1, "bg_mlp_layer_forward_split: pointers must be 16-byte aligned");
     if (N % 128 != 0 || N > 1024) return bg_set_error(-4, "bg_mlp_layer_forward_split: unsupported N (multiples of 128 up to 1024)");
     if (terms != 9 && terms != 6) return bg_set_error(-4, "bg_mlp_layer_forward_split: terms must be 9 or 6");
     dim3 grid((((M + FW_BM - 1) / FW_BM + 7) / 8) * 8 * (N / 128)), block(256);

@@ -623,7 +623,8 @@ extern "C" int bg_optimizer_step(int32_t n, float* params, float* grads, float* 
 extern "C" int bg_elu_backward_colsum(int32_t B, int32_t C, float* grad, const float* act, float* colsum, float* scratch, void* stream) {
     if (B <= 0 || C <= 0 || !grad || !colsum || !scratch) return bg_set_error(-1, "bg_elu_backward_colsum: bad argument");
     const int nb = (B + CS_ROWS - 1) / CS_ROWS;
-    if (act && C % 4 == 0 && C <= 256 && 256 % (C / 4) == 0)
+    // (the 16-byte form only on 16-byte aligned buffers: the header promises no alignment, and the generic form needs none)
+    if (act && C % 4 == 0 && C <= 256 && 256 % (C / 4) == 0 && aligned16(grad) && aligned16(act) && aligned16(scratch))
         hipLaunchKernelGGL(elu_bwd_colsum_vec4_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, B, C, grad, act, scratch);
     else
         hipLaunchKernelGGL(elu_bwd_colsum_kernel, dim3(nb), dim3(C >= 256 ? 256 : (C >= 128 ? 128 : 64)), 0, (hipStream_t)stream, B, C, grad, act, scratch);

@@ -551,8 +551,8 @@ typedef struct bg_param_mirror {
  * lr_device (as bg_adapt_lr, with kl_sum = stats[kl_index]), and the bookkeeping of the float64 loss statistics: stats_last = stats,
  * stats_acc += stats, stats = 0 (and grad_logstd = 0) for the next mini-epoch.  grad_logstd (optional, float64 [ls_n]) is the log-std gradient as
  * the head kernels accumulate it; it is written into grads[ls_off .. ls_off + ls_n) first.  stats may be NULL (no learning-rate rule, no
- * bookkeeping).  ticket: one zero-initialised uint32 of device memory owned by the caller.  mirrors (optional, up to 16): see bg_param_mirror.
- * Deterministic (no float atomics). */
+ * bookkeeping).  ticket: one zero-initialised uint32 of device memory owned by the caller (the launch leaves it zero).  grads 16-byte aligned (-1
+ * otherwise).  mirrors (optional, up to 16): see bg_param_mirror.  Deterministic (no float atomics). */
 int bg_optimizer_step(int32_t n, float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* lr_device, int32_t step, float beta1, float beta2,
                       float eps, float max_grad_norm, double* grad_logstd, int32_t ls_off, int32_t ls_n, double* stats, double* stats_acc,
                       double* stats_last, int32_t n_stats, int32_t kl_index, float kl_count, float desired_kl, float lr_min, float lr_max,
@@ -560,18 +560,21 @@ int bg_optimizer_step(int32_t n, float* params, float* grads, float* exp_avg, fl
 
 /* MLP backward helper for the ELU layers of utils/model.py:9-26: grad [B][C] <- grad * elu'(.) in place, expressed through the layer OUTPUT
  * act [B][C] (1 if act > 0 else act + 1; act == NULL: identity), and colsum [C] = column sums of the result (= bias gradient).
- * scratch: ceil(B/128) * C floats.  Deterministic (no atomics). */
+ * scratch: ceil(B/128) * C floats.  No alignment is asked of any buffer; with act, C a power of two from 4 to 256 and grad, act and scratch all 16-byte aligned a
+ * wider form runs that adds the same terms of a column in another fixed order (colsum's bits then depend on the alignment, on nothing else).
+ * Deterministic (no atomics). */
 int bg_elu_backward_colsum(int32_t B, int32_t C, float* grad, const float* act, float* colsum, float* scratch, void* stream);
 
 /* Fused MLP layer forward: Y [M][N] = act(X [M][K] . W[N][K]^T + bias[N]) in fp32 MFMA with bias + ELU in the GEMM epilogue
- * (utils/model.py:9-26 Linear + ELU).  Supported: K in {64, 128, 256}, N a multiple of 128; other shapes return -4 (caller uses the library GEMM). */
+ * (utils/model.py:9-26 Linear + ELU).  Supported: K in {64, 128, 256, 512}, N a multiple of 128 up to 1024; other shapes return -4 (caller uses the
+ * library GEMM).  X, W, bias and Y 16-byte aligned (-1 otherwise).  Exactly the M rows of Y are written; rows of X at or beyond M are never read. */
 int bg_mlp_layer_forward(int32_t M, int32_t K, int32_t N, const float* X, const float* W, const float* bias, float* Y, int32_t elu, void* stream);
 /* The three hidden Linear + ELU layers of one network (utils/model.py:9-26, forward of runner.py:132,147) in ONE launch: Y1 = elu(X W1^T + b1) [M][N1],
  * Y2 = elu(Y1 W2^T + b2) [M][N2], Y3 = elu(Y2 W3^T + b3) [M][N3], every activation stored for the backward pass; between the layers the
  * activations stay in registers (bg_mlp_chain.hip).  X [M][K0] with K0 = 64 (zero-padded input columns), W row-major [out][in] as torch's Linear.
  * Supported widths (N1, N2, N3): (256, 128, 128) and (256, 256, 128), the reference's actor and critic.  Y1 / Y2 / Y3 must hold
  * ceil(M / 128) * 128 rows (rows >= M of the last slab are written with unspecified values).  Bit-identical to three bg_mlp_layer_forward
- * launches.  -4: unsupported widths. */
+ * launches.  X, W1 .. W3, b1 .. b3, Y1 .. Y3 and v_w 16-byte aligned (-1 otherwise; v_b and v_out need no alignment).  -4: unsupported widths. */
 typedef struct bg_mlp_chain {
     int32_t M, K0, N1, N2, N3;
     int32_t workgroups;  /* 0: one workgroup per 128-row slab; > 0: that many workgroups walk the slabs (each fills a CU: two launches side by side then
@@ -591,7 +594,8 @@ int bg_mlp_chain_forward_group(const bg_mlp_chain* nets, int32_t count, void* st
 /* Fused MLP layer backward through one Linear and the ELU below it:  Gout [M][N] = (G [M][K] . Wt[N][K]^T) * elu'(act_below [M][N]) and
  * bias_grad_below [N] = column sums of Gout.  G = dL/dz of the upper layer (K = its width), Wt = that layer's weight TRANSPOSED to [N][K]
  * (N = width of the layer below), act_below = the lower layer's output activations.  scratch: ceil(M/128) * N floats.
- * Replaces torch.mm(G, W) + elu_backward + the bias-gradient reduction.  K in {128, 256}, N a multiple of 128; otherwise -4. */
+ * Replaces torch.mm(G, W) + elu_backward + the bias-gradient reduction.  K in {128, 256, 512}, N a multiple of 128 up to 1024; otherwise -4.
+ * G, Wt, act_below and Gout 16-byte aligned (-1 otherwise).  Exactly the M rows of Gout are written; rows of G / act_below at or beyond M are never read. */
 int bg_mlp_layer_backward(int32_t M, int32_t K, int32_t N, const float* G, const float* Wt, const float* act_below, float* Gout,
                           float* bias_grad_below, float* scratch, void* stream);
 
@@ -601,7 +605,8 @@ int bg_mlp_layer_backward(int32_t M, int32_t K, int32_t N, const float* G, const
  * against the fp32 MFMA form; terms = 6 drops mid*lo, lo*mid, lo*lo (<= 2^-23 of each product).  The weights come pre-split:
  * bg_mlp_split_weights writes planes[n_out][k_out / 32][3][32] bf16 from W [src_rows][ldw] (transpose != 0: element (n, k) = W[k][n]);
  * elements outside the source are zero (the zero-padded first layers), k_out a multiple of 32, 6 bytes per element.
- * Same shape limits and error codes as bg_mlp_layer_forward / _backward. */
+ * Same N limits and error codes as bg_mlp_layer_forward / _backward; K in {64, 128, 256} forward, {128, 256} backward (K = 512 runs in the fp32
+ * form only).  planes 16-byte aligned, as the other matrix pointers of the two layer kernels. */
 int bg_mlp_split_weights(int32_t n_out, int32_t k_out, const float* W, int32_t ldw, int32_t src_rows, int32_t src_cols, int32_t transpose,
                          uint16_t* planes, void* stream);
 /* bg_mlp_split_weights, and behind its planes (n_out * k_out * 3 uint16 further) the planes of -W: what the chained split kernels read with
@@ -620,7 +625,7 @@ int bg_mlp_layer_backward_split(int32_t M, int32_t K, int32_t N, const float* G,
  * padding of Y1 / Y2 / Y3, `workgroups` and value head as bg_mlp_chain.  Not bit-identical to the fp32-MFMA chain (another summation order; the bias is
  * the accumulators' initial value): both are exact-product fp32 sums.  1 to 4 networks per launch (each on its own `workgroups` persistent
  * workgroups inside one grid: how the update shares the chip between the critic and the actor); which workgroup walks which slab changes no bit of
- * any output (tests/test_gpu_mlp_chain_split.py). */
+ * any output (tests/test_gpu_mlp_chain_split.py).  X, P1 .. P3, b1 .. b3, Y1 .. Y3 and v_w 16-byte aligned (-1 otherwise). */
 typedef struct bg_mlp_chain_split {
     int32_t M, K0, N1, N2, N3;
     int32_t workgroups;
@@ -647,7 +652,8 @@ int bg_mlp_chain_forward_split(const bg_mlp_chain_split* nets, int32_t count, vo
  * the feature dimension C_in possibly zero-padded (the first layers: 47 / 61 -> 64); only the first C_in_real columns are written, with
  * row stride C_in_real, so dW can be the parameter's .grad view in the flat gradient buffer.
  * C_out a multiple of 128, C_in 64 or a multiple of 128, M even, slices a multiple of 8 with slices * 8 <= M;
- * scratch: slices * C_out * C_in floats.  Otherwise -4 / -1. */
+ * scratch: slices * C_out * C_in floats.  G, A and scratch 16-byte aligned, dW too when C_in_real == C_in (a narrower dW is written float by float and
+ * needs no alignment).  Otherwise -4 / -1. */
 int bg_mlp_weight_grad(int32_t M, int32_t C_out, int32_t C_in, int32_t C_in_real, const float* G, const float* A, float* dW, float* scratch,
                        int32_t slices, void* stream);
 
@@ -680,16 +686,17 @@ int bg_mlp_weight_grad_group_split_partial(const bg_wgrad_problem* problems, int
 /* ---- output ("head") layers fused with the loss: the 128 -> 12 / 128 -> 1 Linear layers of utils/model.py:13,21 together with
  * runner.py:145-174.  h [rows][128] = activations of the last hidden (ELU) layer, 16-byte aligned.  One launch reads h once instead of
  * the seven library GEMM / elementwise passes these skinny layers otherwise take per network and mini-epoch.
- * scratch: BG_HEAD_SCRATCH_FLOATS floats of device memory per concurrent call (per-workgroup partial sums, added in a fixed order). */
+ * scratch: BG_HEAD_SCRATCH_FLOATS floats of device memory per concurrent call, 16-byte aligned (per-workgroup partial sums, added in a fixed order:
+ * up to 768 records of 12 * 128 + 128 + 16 floats and, behind them, up to 18 float64 statistics per workgroup; bg_head.hip asserts that they fit). */
 #define BG_HEAD_SCRATCH_FLOATS (768 * 1720)
-/* critic.6 forward: values [rows] = h w + b   (w [128], b [1]) */
+/* critic.6 forward: values [rows] = h w + b   (w [128], 16-byte aligned as h is (-1 otherwise); b [1]) */
 int bg_critic_head_forward(int32_t rows, const float* h, const float* w, const float* b, float* values, void* stream);
 /* bg_critic_head_forward on all (T + 1) N rows of h (time-major: row t N + e), then bg_gae on the result, in ONE launch (utils/runner.py:132-141: values,
  * last values, timeout bootstrap, discount_values, returns): values_all [(T + 1) N] (the last N = last_values), advantages / returns [T][N], rewards
  * overwritten at time-outs as bg_gae does, sums float64 [3] WRITTEN (sum, sum of squares, count; fixed order: deterministic).  scratch: float64
  * [3 * ceil(N / 16) + 1], its last element zero-initialised once by the caller (the launch leaves it zero).  Values bit-identical to
  * bg_critic_head_forward, advantages to bg_gae.  h == NULL: values_all is an INPUT (e.g. written by bg_mlp_chain_forward's value head) and only the
- * GAE half runs (w, b unused).  -4: T > 32. */
+ * GAE half runs (w, b unused).  With h: h and w 16-byte aligned (-1 otherwise), in bg_critic_values_gae_norm as well.  -4: T > 32. */
 int bg_critic_values_gae(int32_t T, int32_t N, const float* h, const float* w, const float* b, float* rewards, const uint8_t* dones,
                          const uint8_t* time_outs, float gamma, float lam, float* values_all, float* advantages, float* returns, double* sums,
                          double* scratch, void* stream);
@@ -796,7 +803,7 @@ int bg_actor_head_sym_partial(int32_t B, const float* h, const float* W, const f
  * leaves one record of column sums per slab in colsum_partial ([ceil(M / 128) * 4][N2 + N1] floats); `finishes[k]` receives the descriptor of the
  * fixed-order reduction that produces bias_grad2 [N2] and bias_grad1 [N1] when handed to bg_reduce_group / bg_update_tail.  Widths (N1, N2, N3):
  * (256, 128, 128), (256, 256, 128).  1 to 4 networks per launch; `workgroups` as in bg_mlp_chain_split: which workgroup walks which slab changes no
- * bit of any output. */
+ * bit of any output.  G3, PT3, PT2, A2, A1, G2 and G1 16-byte aligned (-1 otherwise); colsum_partial and the bias gradients need no alignment. */
 typedef struct bg_mlp_chain_split_bwd {
     int32_t M, N1, N2, N3;
     int32_t workgroups, alternate;   /* alternate: as in bg_mlp_chain_split; PT3 / PT2 then hold the planes of W^T and of -W^T */
