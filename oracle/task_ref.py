@@ -419,7 +419,9 @@ class T1Ref:
         if teleport and self.terrain is not None:
             t = cfg["terrain"]
             ew, el, b = t["num_terrains"] * t["terrain_width"], t["terrain_length"], t["border_size"]
-            sx = np.where(self.root[:, 0] < -0.75 * b, ew + b, 0.0) - np.where(self.root[:, 0] > ew + 0.75 * b, ew + b, 0.0)
+            if t.get("curriculum", False):  # this build's terrain curriculum lays num_levels rows of terrain_length along y (utils/terrain.py)
+                el *= int(t.get("num_levels", 10))
+            sx =np.where(self.root[:, 0] < -0.75 * b, ew + b, 0.0) - np.where(self.root[:, 0] > ew + 0.75 * b, ew + b, 0.0)
             sy = np.where(self.root[:, 1] < -0.75 * b, el + b, 0.0) - np.where(self.root[:, 1] > el + 0.75 * b, el + b, 0.0)
             self.root[:, 0] += sx; self.root[:, 1] += sy
             feet_store[:, :, 0] += sx[:, None]; feet_store[:, :, 1] += sy[:, None]

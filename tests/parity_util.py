@@ -13,6 +13,9 @@ One env step of the fused HIP kernel is compared with the float64 oracle from ID
                            turns rounding-level differences into visible ones; a kernel defect is not reproduced by such perturbations.
 A tight bound on the number of explained envs keeps the explanations from becoming the rule.
 """
+import math
+import os
+
 import numpy as np
 
 FIELDS = ["root_states", "dof_pos", "dof_vel", "last_dof_targets", "actions", "last_actions", "last_dof_vel", "last_root_vel", "commands",
@@ -230,3 +233,447 @@ class StepParity:
         # always in the test output (pytest -s / the captured log of a failure): a regression that starts leaning on the explanations shows here
         print("StepParity:", out, flush=True)
         return out
+
+
+def assert_close(a, b, tol, frac=0.99, hard=None, what=""):
+    """At least `frac` of the envs within `tol` (relative to max(1, |b|), worst element per env); `hard`: no env beyond it."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    err = np.abs(a - b) / np.maximum(1.0, np.abs(b))
+    per_env = err.reshape(err.shape[0], -1).max(axis=1)
+    ok = (per_env < tol).mean()
+    assert ok >= frac, f"{what}: only {ok:.3f} of envs within {tol}; worst {per_env.max():.3e}"
+    if hard is not None:
+        assert per_env.max() < hard, f"{what}: worst env error {per_env.max():.3e}"
+
+
+# ================================================================== one constructor for the (env, oracle) pair
+def phys_of(cfg):
+    """Every physics key of the config as DynRef's `phys`, with the defaults T1._cfg_struct gives an absent key: an override of sim.dt, sim.gravity or
+    contact.* reaches the oracle as it reaches bg_env_cfg."""
+    ct = cfg.get("contact", {}) or {}
+    t = cfg["terrain"]
+    return {"dt": float(cfg["sim"]["dt"]), "g": tuple(float(v) for v in cfg["sim"]["gravity"]), "contact_k": float(ct.get("stiffness", 4.0e4)),
+            "contact_d": float(ct.get("damping", 600.0)), "contact_ramp": float(ct.get("damping_ramp", 1.0e-3)),
+            "friction_visc": float(ct.get("friction_viscosity", 1.0e4)), "limit_k": float(ct.get("joint_limit_stiffness", 2000.0)),
+            "limit_d": float(ct.get("joint_limit_damping", 20.0)), "clamp_qd": int(bool(ct.get("clamp_dof_velocity", True))),
+            "body_gate_height": float(ct.get("body_gate_height", 0.45)), "terrain_mu": 0.5 * (t["static_friction"] + t["dynamic_friction"]),
+            "terrain_restitution": t["restitution"], "self_collisions": int(int(cfg["asset"].get("self_collisions", 0)) == 0),
+            "self_k": float(ct.get("self_stiffness", 4.0e4)), "self_d": float(ct.get("self_damping", 150.0)), "self_mu": float(ct.get("self_friction", 1.0)),
+            "self_visc": float(ct.get("self_friction_viscosity", 100.0))}
+
+
+def make_oracle(cfg, model, params, tdict=None, real="f64"):
+    """T1Ref over a DynRef whose physics constants are the config's (real="f32": the single-precision twin, task logic float64 either way)."""
+    from oracle.dyn_ref import DynRef
+    from oracle.task_ref import T1Ref
+
+    dyn = DynRef(model, feet_edge_pos=cfg["asset"]["feet_edge_pos"], terrain=tdict, phys=phys_of(cfg), real=real)
+    return T1Ref(cfg, model, dyn, params, terrain=tdict, seed=cfg["basic"]["seed"], rank=0)
+
+
+def make_pair(terrain, n, overrides=None):
+    """cfg, env (the HIP T1), ref (the float64 oracle on the env's model, terrain and per-env parameters)."""
+    from booster_gym_amd.envs import T1
+    from booster_gym_amd.utils.config import load_cfg
+
+    ov = {"env.num_envs": n, "terrain.type": terrain}
+    ov.update(overrides or {})
+    cfg = load_cfg("T1", ov)
+    env = T1(cfg)
+    tdict = None
+    if terrain != "plane":
+        t = env.terrain
+        tdict = dict(height_field_raw=t.height_field_raw, hscale=t.horizontal_scale, vscale=t.vertical_scale, border_px=t.border_pixels)
+    f32 = lambda a: np.asarray(a, dtype=np.float32).astype(np.float64)
+    params = dict(kp=f32(env._kp), kd=f32(env._kd), fric=f32(env._fric), mass_scale=f32(env._mass_scale), com_off=f32(env._com_off),
+                  foot_mat=f32(env._foot_mat), bms=f32(env._bms), origins=f32(env._origins))
+    return cfg, env, make_oracle(cfg, env.model, params, tdict)
+
+
+def make_twin(cfg, model, ref):
+    """The same oracle with its physics in single precision (oracle/dyn_ref.c built as libdynref32.so): how far fp32 rounding alone moves this
+    algorithm on a given state.  Task logic stays the float64 numpy code; parameters and terrain are `ref`'s."""
+    return make_oracle(cfg, model, ref.p, ref.terrain, real="f32")
+
+
+def host_params(cfg, model, n):
+    """Per-env parameters drawn in the yaml's randomization.* ranges on the host, for an oracle that has no env beside it (flat ground).  Its own
+    seeded draws, not T1._create_envs': two configs that differ in control.stiffness / damping alone get the same scaling draws."""
+    rng = np.random.default_rng(int(cfg["basic"]["seed"]))
+    rnd = cfg["randomization"]
+
+    def draw(x, spec):
+        if spec is None:
+            return x, np.zeros_like(x)
+        a, b = spec["range"]
+        raw = rng.standard_normal(x.shape) if spec["distribution"] == "gaussian" else rng.random(x.shape)
+        val = a + b * raw if spec["distribution"] == "gaussian" else a + (b - a) * raw
+        return (x + val if spec["operation"] == "additive" else x * val), raw
+
+    kp, kd = np.zeros((n, 12)), np.zeros((n, 12))
+    for i, name in enumerate(model.dof_names):
+        for key in cfg["control"]["stiffness"]:
+            if key in name:
+                kp[:, i], kd[:, i] = cfg["control"]["stiffness"][key], cfg["control"]["damping"][key]
+    kp, kd, fric = draw(kp, rnd.get("dof_stiffness"))[0], draw(kd, rnd.get("dof_damping"))[0], draw(np.zeros((n, 12)), rnd.get("dof_friction"))[0]
+    mass_scale, com_off, bms = np.ones((n, 13)), np.zeros((n, 13, 3)), np.zeros((n, 4))
+    for b in range(13):
+        ck, mk = ("base_com", "base_mass") if b == 0 else ("other_com", "other_mass")
+        com_off[:, b], craw = draw(np.zeros((n, 3)), rnd.get(ck))
+        mass_scale[:, b], sraw = draw(np.ones(n), rnd.get(mk))
+        if b == 0:
+            bms[:, :3], bms[:, 3] = craw, sraw
+    fm = np.zeros((n, 2, 3))
+    for k, key in enumerate(("friction", "compliance", "restitution")):
+        fm[:, :, k] = draw(np.zeros((n, 2)), rnd.get(key))[0]
+    fm[:, :, 1] = np.maximum(fm[:, :, 1], 1e-3)
+    origins = np.zeros((n, 3))
+    cols = np.floor(np.sqrt(n))
+    xx, yy = np.meshgrid(np.arange(np.ceil(n / cols)), np.arange(cols), indexing="ij")
+    origins[:, 0], origins[:, 1] = cfg["env"]["env_spacing"] * xx.flatten()[:n], cfg["env"]["env_spacing"] * yy.flatten()[:n]
+    f32 = lambda a: np.asarray(a, dtype=np.float32).astype(np.float64)
+    return dict(kp=f32(kp), kd=f32(kd), fric=f32(fric), mass_scale=f32(mass_scale), com_off=f32(com_off), foot_mat=f32(fm), bms=f32(bms), origins=f32(origins))
+
+
+_ATTR = {"root_states": "root", "dof_pos": "q", "dof_vel": "qd", "last_dof_targets": "last_tgt", "actions": "actions", "last_actions": "last_actions",
+         "last_dof_vel": "last_qd", "last_root_vel": "last_rootvel", "commands": "cmd", "gait_frequency": "gait_f", "gait_process": "gait_p",
+         "filtered_lin_vel": "filt_lin", "filtered_ang_vel": "filt_ang", "last_feet_pos": "last_feet", "pushing": "push",
+         "episode_length_buf": "ep_len", "cmd_resample_time": "cmd_time", "delay_steps": "delay"}
+_INT_ATTR = ("ep_len", "cmd_time", "delay")
+
+
+def snapshot(ref):
+    """The oracle's whole mutable state (to start a second oracle from the same inputs)."""
+    s = {a: np.array(getattr(ref, a), copy=True) for a in _ATTR.values()}
+    s["step_count"] = ref.step_count
+    return s
+
+
+def restore(ref, snap):
+    for a in _ATTR.values():
+        setattr(ref, a, snap[a].copy())
+    ref.step_count = snap["step_count"]
+
+
+class OracleEnv:
+    """The oracle's fp32 twin behind the part of T1's interface that StepParity and run_case use, so that the twin is held to the float64 oracle by the
+    very code that holds the HIP env to it.  Like the kernel it keeps its state in fp32 between steps: both sides of a step start from identical inputs."""
+
+    def __init__(self, cfg, twin):
+        import torch
+
+        self._t, self.cfg, self.r, self.device, self.dt = torch, cfg, twin, "cpu", twin.dt
+        self.reward_names, self._derived, self._finished = list(twin.scales), None, 0
+
+    def _round(self):
+        for a in _ATTR.values():
+            if a not in _INT_ATTR:
+                setattr(self.r, a, np.asarray(getattr(self.r, a), dtype=np.float32).astype(np.float64))
+
+    def get_field(self, name):
+        n = self.r.n
+        if name in ("feet_contact", "torques", "feet_pos"):
+            return self._t.as_tensor(np.asarray(self._derived[name], dtype=np.float32).reshape(n, -1).copy())
+        a = _ATTR[name]
+        return self._t.as_tensor(np.asarray(getattr(self.r, a)).astype(np.int32 if a in _INT_ATTR else np.float32).reshape(n, -1).copy())
+
+    def set_field(self, name, value):
+        a = _ATTR[name]
+        old = np.asarray(getattr(self.r, a))
+        setattr(self.r, a, np.asarray(self._t.as_tensor(value).cpu().numpy(), dtype=np.float32).astype(old.dtype).reshape(old.shape))
+
+    root_states = property(lambda self: self.get_field("root_states"))
+    dof_pos = property(lambda self: self.get_field("dof_pos"))
+    dof_vel = property(lambda self: self.get_field("dof_vel"))
+    commands = property(lambda self: self.get_field("commands"))
+
+    @property
+    def common_step_counter(self):
+        return self.r.step_count
+
+    @common_step_counter.setter
+    def common_step_counter(self, v):
+        self.r.step_count = int(v)
+
+    def _pack(self, obs, priv):
+        f = lambda a: self._t.as_tensor(np.asarray(a, dtype=np.float32))
+        return f(obs), {"privileged_obs": f(priv)}
+
+    def reset(self):
+        obs, priv = self.r.reset()
+        self._round()
+        return self._pack(obs, priv)
+
+    def step(self, actions):
+        obs, priv, rew, done, tout, scaled, derived = self.r.step(self._t.as_tensor(actions).cpu().numpy().astype(np.float64))
+        self._derived = derived
+        self._round()
+        self._finished += int(np.sum(done))
+        f = lambda a: self._t.as_tensor(np.asarray(a, dtype=np.float32))
+        o, extras = self._pack(obs, priv)
+        extras.update(time_outs=self._t.as_tensor(np.asarray(tout)), rew_terms={k: f(v) for k, v in scaled.items()})
+        return o, f(rew), self._t.as_tensor(np.asarray(done)), extras
+
+    def episode_stats(self, reset=False):
+        return self._t.tensor([float(self._finished)] + [0.0] * 29)
+
+
+def make_oracle_pair(n, overrides=None):
+    """cfg, OracleEnv(fp32 twin), float64 oracle on flat ground, without a GPU."""
+    from booster_gym_amd.utils.config import load_cfg
+    from booster_gym_amd.utils.urdf import FlatModel
+
+    ov = {"env.num_envs": n, "terrain.type": "plane"}
+    ov.update(overrides or {})
+    cfg = load_cfg("T1", ov)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    model = FlatModel.load(os.path.join(root, "booster_gym_amd", "resources", "T1", "T1_locomotion.flat.json"))
+    ref = make_oracle(cfg, model, host_params(cfg, model, n))
+    return cfg, OracleEnv(cfg, make_twin(cfg, model, ref)), ref
+
+
+# ================================================================== the config surface away from the shipped values
+# One table for tests/test_config_surface_ref.py (the cases are well-posed on the oracle alone) and tests/test_gpu_config_surface.py (the kernel matches
+# the oracle under them).  Per key: the value, the outputs the key governs, and the steps of the window at which it can show ("any", or the step of a
+# kick, a push start, a push end, a step with a push in force, "limit": the first step, over the envs arranged past a joint limit, or "reset":
+# T1.reset()).  Outputs, each with the tolerance StepParity holds it to:
+#   ("obs", a, b) / ("priv", a, b)   columns [a, b) of the observation / privileged observation           STATE_TOL["obs"] / ["priv"]
+#   ("term", name) / ("total",)      a scaled reward term / the total reward                               REW_TOL (relative to max(|.|, REW_FLOOR))
+#   ("state",)                       the post-physics state: root, dof_pos, dof_vel, mean torques          STATE_TOL of each
+#   ("root_vel",) / ("push",)        the root's velocities after the kick / the stored push wrench         STATE_TOL["root"] / 1e-4 (the step test's bound)
+#   ("reset", attr)                  the oracle attribute after reset()                                    1e-5 (the reset test's bound on the root)
+# The values started from the issue's list; where one moved, the reason stands beside it.  The thresholds (SENS_FACTOR x tolerance in SENS_SHARE of
+# the envs; ACTIVE_SHARE of the env-steps above REW_FLOOR) never moved.
+SENS_FACTOR, SENS_SHARE, ACTIVE_SHARE, SWING_SHARE = 10.0, 0.5, 0.5, 0.10
+TOTAL_POS_SHARE, TOTAL_CLIP_SHARE, TOTAL_NONZERO_SHARE = 0.25, 0.25, 0.90
+TRACKING = [("term", "tracking_lin_vel_x"), ("term", "tracking_lin_vel_y"), ("term", "tracking_ang_vel")]
+
+
+def _rs(dist, op, a, b):
+    return {"range": [a, b], "operation": op, "distribution": dist}
+
+
+REWARD_KEYS = {
+    "rewards.scales.dof_vel_limits": (-0.05, [("term", "dof_vel_limits")], "any"),
+    "rewards.scales.torque_limits": (-0.01, [("term", "torque_limits")], "any"),
+    "rewards.scales.feet_vel_z": (-0.5, [("term", "feet_vel_z")], "any"),
+    # 4.0, not the issue's 5.0: the unclipped total is then negative in clearly more than half of the env-steps, which only_positive_rewards: false needs
+    "rewards.scales.survival": (4.0, [("term", "survival")], "any"),
+    "rewards.scales.torques": (-1.0e-4, [("term", "torques")], "any"),
+    "rewards.scales.base_height": (-5.0, [("term", "base_height")], "any"),
+    "rewards.scales.action_rate": (-0.3, [("term", "action_rate")], "any"),
+    "rewards.soft_dof_pos_limit": (0.6, [("term", "dof_pos_limits")], "any"),
+    "rewards.soft_dof_vel_limit": (0.1, [("term", "dof_vel_limits")], "any"),
+    "rewards.soft_torque_limit": (0.3, [("term", "torque_limits")], "any"),
+    "rewards.tracking_sigma": (0.5, TRACKING, "any"),
+    "rewards.base_height_target": (0.62, [("term", "base_height")], "any"),
+    "rewards.swing_period": (0.3, [("swing",)], "any"),
+    "rewards.feet_distance_ref": (0.25, [("term", "feet_distance")], "any"),
+    "control.action_scale": (0.5, [("state",)], "any"),
+    "normalization.clip_actions": (0.4, [("obs", 35, 47)], "any"),
+    "normalization.filter_weight": (0.3, [("term", "lin_vel_z")] + TRACKING, "any"),
+    "normalization.gravity": (0.5, [("obs", 0, 3)], "any"),
+    "normalization.lin_vel": (2.0, [("priv", 4, 7), ("obs", 6, 8)], "any"),
+    # 2.0, not the issue's 0.25: with the combined case's noise.ang_vel: null, a factor below 1 shrinks the shipped noise that the null entry removes
+    # under 10 x the observation tolerance
+    "normalization.ang_vel": (2.0, [("obs", 3, 6), ("obs", 8, 9)], "any"),
+    "normalization.dof_pos": (2.0, [("obs", 11, 23)], "any"),
+    "normalization.dof_vel": (0.05, [("obs", 23, 35)], "any"),
+    "normalization.push_force": (0.05, [("priv", 8, 11)], "pushed"),
+    "normalization.push_torque": (0.25, [("priv", 11, 14)], "pushed"),
+}
+# the reward terms the group activates or re-parameterises (feet_swing has its own condition, SWING_SHARE)
+REWARD_TERMS = ["dof_vel_limits", "torque_limits", "feet_vel_z", "survival", "torques", "base_height", "action_rate", "dof_pos_limits",
+                "tracking_lin_vel_x", "tracking_lin_vel_y", "tracking_ang_vel", "feet_distance"]
+NEW_TERMS = ["dof_vel_limits", "torque_limits", "feet_vel_z"]
+
+# Modes of apply_rand (0 null, 1 gaussian additive, 2 gaussian scaling, 3 uniform additive, 4 uniform scaling): observation sites 3 2 0 4 1 2, state
+# sites 3 2 3 3 4 1 0.  Moved from the issue's list, all for the 10 x tolerance rule (0.05 in observation units): the null entry sits on ang_vel, whose
+# shipped noise (0.1) is large enough to be missed, not on dof_pos (0.01); dof_pos takes the uniform scaling; gravity, height and kick_ang_vel got wider
+# ranges; dof_vel is gaussian ADDITIVE with a non-zero mean, which no shipped entry has; init_dof_pos takes a scaling (the shipped default pose is
+# non-zero on the pitch joints), so that mode 4 occurs at a state site where it is not degenerate (a scaled zero push is a zero push); the null state
+# entry sits on init_base_lin_vel_xy and not on push_torque, so that normalization.push_torque still has a torque to scale in the combined case.
+# The intervals are no multiples of either step length (0.05 / 0.02 and 0.05 / 0.021 both round up to 3), so the step counts do not hang on one
+# rounding of a quotient.  friction_viscosity 200 and damping_ramp 5e-3 (below): 5000 and 2e-3 moved the post-physics state in too few envs.
+NOISE_KEYS = {
+    "noise.gravity": (_rs("uniform", "additive", -0.2, 0.2), [("obs", 0, 3)], "any"),
+    "noise.lin_vel": (_rs("gaussian", "scaling", 1.0, 0.02), [("priv", 4, 7)], "any"),
+    "noise.ang_vel": (None, [("obs", 3, 6)], "any"),
+    "noise.dof_pos": (_rs("uniform", "scaling", 0.5, 1.5), [("obs", 11, 23)], "any"),
+    "noise.dof_vel": (_rs("gaussian", "additive", 0.5, 2.0), [("obs", 23, 35)], "any"),
+    "noise.height": (_rs("gaussian", "scaling", 1.0, 0.3), [("priv", 7, 8)], "any"),
+    "randomization.kick_lin_vel": (_rs("uniform", "additive", -0.2, 0.2), [("root_vel",)], "kick"),
+    "randomization.kick_ang_vel": (_rs("gaussian", "scaling", 0.5, 0.3), [("root_vel",)], "kick"),
+    "randomization.push_force": (_rs("uniform", "additive", -20.0, 20.0), [("push",)], "push_start"),
+    "randomization.push_torque": (_rs("uniform", "additive", -3.0, 3.0), [("push",)], "push_start"),
+    "randomization.init_dof_pos": (_rs("uniform", "scaling", 0.8, 1.2), [("reset", "q")], "reset"),
+    "randomization.init_base_pos_xy": (_rs("gaussian", "additive", 0.0, 0.3), [("reset", "root")], "reset"),
+    "randomization.init_base_lin_vel_xy": (None, [("reset", "root")], "reset"),
+    "randomization.kick_interval_s": (0.05, [("root_vel",)], "kick"),
+    "randomization.push_interval_s": (0.09, [("push",)], "push_start"),
+    "randomization.push_duration_s": (0.03, [("push",)], "push_end"),
+}
+
+PHYSICS_KEYS = {
+    "control.decimation": (7, [("state",)], "any"),
+    "sim.dt": (0.003, [("state",)], "any"),
+    "sim.gravity": ([0.0, 0.0, -8.0], [("state",)], "any"),
+    "contact.stiffness": (30000.0, [("state",)], "any"),
+    "contact.damping": (400.0, [("state",)], "any"),
+    "contact.joint_limit_stiffness": (1000.0, [("state",)], "limit"),
+    "contact.joint_limit_damping": (10.0, [("state",)], "limit"),
+    "contact.friction_viscosity": (200.0, [("state",)], "any"),
+    "contact.damping_ramp": (5.0e-3, [("state",)], "any"),
+    "control.stiffness": ({"Hip": 150.0, "Knee": 180.0, "Ankle": 40.0}, [("state",)], "any"),
+    "control.damping": ({"Hip": 4.0, "Knee": 6.0, "Ankle": 1.5}, [("state",)], "any"),
+}
+# terms whose value hangs on the policy-step length beyond their scale x dt, and the mean torque's divisor
+PHYSICS_TERMS = ["survival", "dof_acc", "root_acc", "torques"]
+SIGNED = {"rewards.only_positive_rewards": (False, [("total",)], "any")}
+
+
+def _case(start_count, terms, total, *groups):
+    keys = {}
+    for g in groups:
+        keys.update(g)
+    return {"keys": keys, "overrides": {k: v[0] for k, v in keys.items()}, "terms": terms, "total": total, "start_count": start_count,
+            "new_terms": [t for t in NEW_TERMS if "rewards.scales." + t in keys], "swing": "rewards.swing_period" in keys,
+            "limits": "contact.joint_limit_stiffness" in keys}
+
+
+# start_count places the window's steps (counter values start_count + 1 .. + 6) over a kick, a push start and a push end where the case has them:
+# rewards: the shipped 250-step push schedule, start at 250; noise and combined: kicks every 3 steps, pushes every 5, for 2; physics: at 21 ms the shipped
+# schedule is 96 / 239 / 48 steps, push start at 239, kick at 240.  The noise and physics groups run with only_positive_rewards: false so that their
+# total reward is compared as a number and not as 0 against 0 (the shipped scales give a negative total throughout).
+CONFIG_CASES = {
+    "rewards_positive": _case(246, REWARD_TERMS, "clipped", REWARD_KEYS),
+    "rewards_signed": _case(246, REWARD_TERMS, "signed", REWARD_KEYS, SIGNED),
+    "noise": _case(4, [], "signed", NOISE_KEYS, SIGNED),
+    "physics": _case(236, PHYSICS_TERMS, "signed", PHYSICS_KEYS, SIGNED),
+    "combined": _case(4, REWARD_TERMS + ["dof_acc", "root_acc"], "clipped", REWARD_KEYS, NOISE_KEYS, PHYSICS_KEYS),
+}
+N_CASE = 96
+AIRBORNE = slice(12, 28)  # the envs with an arranged state (arrange_for)
+
+
+def schedule(cfg, dt):
+    r = cfg["randomization"]
+    return tuple(int(math.ceil(r[k] / dt)) for k in ("kick_interval_s", "push_interval_s", "push_duration_s"))
+
+
+def kick_step(cfg, env):
+    """Does the env step that is about to run apply a kick (t1.py:501: global counter, all envs at once)?"""
+    return (env.common_step_counter + 1) % schedule(cfg, env.dt)[0] == 0
+
+
+def arrange_for(case, lift=0.15, phase=0.12, freq=0.1, past=0.03, spread=0.3):
+    """The window's arranged states of a case, all on the envs of AIRBORNE, which are lifted clear of the ground for the whole window (both feet out
+    of contact, no stiff contact near them).
+      rewards.swing_period    a slow gait clock at a phase inside the left foot's swing window of width 0.3 (|phase - 0.25| < 0.15) and outside the
+                              shipped one (< 0.1): feet_swing is 1 under the case and 0 under the shipped period
+      contact.joint_limit_*   the limit spring acts on a joint past its limit only, and the window's actions leave none there: the left hip yaw starts
+                              `past` rad beyond its limit of 1 rad, toes out, with that leg abducted by `spread` rad so that its heel stays
+                              clear of the right foot (no leg-against-leg contact), held by the actuators until the env's delayed target
+                              arrives; spring and actuator bring it back within the first compared step, at which the two keys are judged
+                              ("limit": over these envs)"""
+    if not (case["swing"] or case["limits"]):
+        return None
+
+    def arrange(env):
+        import torch
+
+        put = lambda k, v: env.set_field(k, torch.as_tensor(v).float())
+        root, feet = env.get_field("root_states"), env.get_field("last_feet_pos")
+        root[AIRBORNE, 2] += lift
+        feet[AIRBORNE, 2] += lift; feet[AIRBORNE, 5] += lift
+        put("root_states", root); put("last_feet_pos", feet)
+        if case["swing"]:
+            gf, gp = env.get_field("gait_frequency"), env.get_field("gait_process")
+            gf[AIRBORNE, 0] = freq; gp[AIRBORNE, 0] = phase
+            put("gait_frequency", gf); put("gait_process", gp)
+        if case["limits"]:
+            q, tgt = env.get_field("dof_pos"), env.get_field("last_dof_targets")
+            q[AIRBORNE, 2] = tgt[AIRBORNE, 2] = 1.0 + past
+            q[AIRBORNE, 1] = tgt[AIRBORNE, 1] = spread
+            put("dof_pos", q); put("last_dof_targets", tgt)
+    return arrange
+
+
+def run_case(cfg, env, ref, start_count, settle=15, steps=6, arrange=None, before_step=None, after_step=None, fp16=False, state_tol=None):
+    """test_step_matches_oracle's procedure as a function of (cfg, env, ref): settle, forced time-outs and command resamples, `steps` compared env
+    steps through StepParity from identical inputs.  Returns the StepParity summary and, per compared step, the oracle's and the env's total and
+    scaled terms with the mask of compared envs (for the non-vacuity shares).  fp16: the oracle's stored state is rounded as the kernel's is."""
+    import torch
+
+    n = ref.n
+    env.reset(); ref.reset()
+    rng = np.random.default_rng(11)
+    for _ in range(settle):  # feet on the ground; then seed episode ends / resamples for some envs
+        env.step(torch.tensor(rng.uniform(-0.3, 0.3, (n, 12)), dtype=torch.float32, device=env.device))
+    max_ep = int(math.ceil(cfg["rewards"]["episode_length_s"] / env.dt))
+    ep = env.get_field("episode_length_buf")
+    ep[:6, 0] = max_ep - 2  # time-out within the window
+    env.set_field("episode_length_buf", ep)
+    ct = env.get_field("cmd_resample_time")
+    ct[6:12, 0] = ep[6:12, 0] + 2  # command resample within the window
+    ct[:6, 0] = 5000
+    env.set_field("cmd_resample_time", ct)
+    env.common_step_counter = start_count
+    if arrange is not None:
+        arrange(env)
+    sp = StepParity(cfg, env, ref, state_tol=state_tol)
+    flags_bad, rec = 0, {"ref_total": [], "env_total": [], "ref_terms": [], "env_terms": [], "keep": []}
+    ptol, ctol = (2e-3, 2e-3) if fp16 else (1e-4, 1e-5)  # fp16 state: one fp16 ulp where the two sides round a near-tie differently
+    for s in range(steps):
+        sp.begin()
+        if before_step is not None:
+            before_step(s)
+        kicked = kick_step(cfg, env)
+        act = rng.uniform(-0.6, 0.6, (n, 12)).astype(np.float32)
+        obs, rew, done, extras = env.step(torch.tensor(act, device=env.device))
+        out = ref.step(act.astype(np.float64))
+        if fp16:
+            ref.quantize_state_fp16()
+        keep = sp.check(s, act, obs, rew, done, extras, out, kicked=kicked)
+        flags_bad += int((~keep).sum()) + int((extras["time_outs"].cpu().numpy() != out[4]).sum())
+        assert (env.get_field("cmd_resample_time").cpu().numpy()[:, 0][keep] == ref.cmd_time[keep]).all()
+        assert (env.get_field("episode_length_buf").cpu().numpy()[:, 0][keep] == ref.ep_len[keep]).all()
+        assert rel_state(env.get_field("pushing").cpu().numpy(), ref.push).max() < ptol, f"step {s} push"
+        assert rel_state(env.commands.cpu().numpy()[keep], ref.cmd[keep]).max() < ctol, f"step {s} commands"
+        rec["ref_total"].append(np.asarray(out[2], dtype=np.float64)); rec["env_total"].append(rew.cpu().numpy().astype(np.float64))
+        rec["ref_terms"].append({k: np.asarray(v, dtype=np.float64) for k, v in out[5].items()})
+        rec["env_terms"].append({k: extras["rew_terms"][k].cpu().numpy().astype(np.float64) for k in out[5]})
+        rec["keep"].append(keep)
+        if after_step is not None:
+            after_step(s, sp, act, out, keep)
+    summary = sp.finish()
+    print("step parity:", summary, sp.log)
+    assert flags_bad <= 2, f"{flags_bad} termination / time-out flags differ"
+    st = env.episode_stats(reset=False).cpu().numpy()
+    assert st[-1] == 0, "non-finite resets during a benign rollout"
+    assert st[0] >= 6  # the forced time-outs were counted as finished episodes
+    return summary, rec
+
+
+def shares(case, rec, side):
+    """The non-vacuity shares of one side ("ref": the oracle's outputs, "env": the env's own) over the compared env-steps: per term of the case the
+    share above REW_FLOOR, the shares of the total above the floor / exactly zero / beyond the floor in magnitude, and feet_swing's share."""
+    keep = np.concatenate(rec["keep"])
+    tot = np.concatenate(rec[side + "_total"])[keep]
+    cat = lambda name: np.concatenate([t[name] for t in rec[side + "_terms"]])[keep]
+    out = {"terms": {name: float((np.abs(cat(name)) > REW_FLOOR).mean()) for name in case["terms"]},
+           "total_positive": float((tot > REW_FLOOR).mean()), "total_zero": float((tot == 0.0).mean()), "total_nonzero": float((np.abs(tot) > REW_FLOOR).mean())}
+    if case["swing"]:
+        out["feet_swing"] = float((np.abs(cat("feet_swing")) > REW_FLOOR).mean())
+    return out
+
+
+def assert_not_vacuous(case, sh, what):
+    for name, v in sh["terms"].items():
+        assert v >= ACTIVE_SHARE, f"{what}: reward term {name} above the floor in {v:.3f} of the env-steps only"
+    if case["total"] == "clipped":
+        assert sh["total_positive"] >= TOTAL_POS_SHARE and sh["total_zero"] >= TOTAL_CLIP_SHARE, f"{what}: total reward positive in {sh['total_positive']:.3f}, clipped in {sh['total_zero']:.3f}"
+    else:
+        assert sh["total_nonzero"] >= TOTAL_NONZERO_SHARE, f"{what}: total reward non-zero in {sh['total_nonzero']:.3f} of the env-steps only"
+    if case["swing"]:
+        assert sh["feet_swing"] >= SWING_SHARE, f"{what}: feet_swing non-zero in {sh['feet_swing']:.3f} of the env-steps only"
