@@ -198,7 +198,7 @@ SYMBOLS = [
     "bg_obs_moments", "bg_obs_normalize",
     "bg_critic_values_gae_norm", "bg_value_denormalize", "bg_value_norm_update",
     "bg_perm_fill", "bg_gather_rows", "bg_gather_sequences",
-    "bg_actor_sample_gru", "bg_distill_act_gru", "bg_gru_sequence_forward", "bg_gru_sequence_backward",
+    "bg_actor_sample_gru", "bg_distill_act_gru", "bg_distill_act_gru_own", "bg_gru_sequence_forward", "bg_gru_sequence_backward",
     "bg_gru_bias_partial", "bg_gru_sequence_forward_group", "bg_gru_sequence_backward_group",
     "bg_rnd_reward",
     "bg_last_error", "bg_version",
@@ -274,6 +274,8 @@ def load():
         "bg_actor_sample_gru": (i32, [i32, vp, i32, C.POINTER(GruDesc), i32, C.POINTER(MlpLayerDesc), vp, u64, u64, vp, vp, vp, vp, vp, vp]),
         "bg_distill_act_gru": (i32, [i32, vp, i32, i32, C.POINTER(MlpLayerDesc), i32, C.POINTER(GruDesc), i32, C.POINTER(MlpLayerDesc), vp, u64, u64, f32, i32,
                                      vp, vp, vp, vp, vp, vp, vp]),
+        "bg_distill_act_gru_own": (i32, [i32, vp, i32, vp, i32, i32, C.POINTER(MlpLayerDesc), i32, C.POINTER(GruDesc), i32, C.POINTER(MlpLayerDesc), vp, u64, u64,
+                                         f32, i32, vp, vp, vp, vp, vp, vp, vp]),
         "bg_rnd_reward": (i32, [i32, vp, i32, vp, i32, i32, C.POINTER(MlpLayerDesc), i32, C.POINTER(MlpLayerDesc), vp, vp, f32, vp, vp, vp, vp]),
         "bg_gru_sequence_forward": (i32, [i32, i32, i32] + [vp] * 9),
         "bg_gru_sequence_backward": (i32, [i32, i32, i32] + [vp] * 9),

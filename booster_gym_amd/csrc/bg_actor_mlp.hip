@@ -424,9 +424,11 @@ __global__ __launch_bounds__(256) void actor_gru_sample_kernel(int N, const floa
 }
 
 // bg_distill_act_gru: distill_act_mix_kernel's split grid (MIX = false: distill_act_kernel's) with the recurrent student in the second half.  The
-// teacher's half is actor_rows' sequence of pieces on the front of the same LDS block.
+// teacher's half is actor_rows' sequence of pieces on the front of the same LDS block.  sobs / sstride: the rows the cell reads its 47 inputs from: the
+// teacher's own (bg_distill_act_gru) or the student's buffer (bg_distill_act_gru_own: a student row that is no prefix of the teacher's).
 template <int H, int MAXW, bool MIX>
-__global__ __launch_bounds__(256) void distill_act_gru_kernel(int N, int nb, const float* __restrict__ obs, int stride, DistillNets nets, GruCell cell,
+__global__ __launch_bounds__(256) void distill_act_gru_kernel(int N, int nb, const float* __restrict__ obs, int stride, const float* __restrict__ sobs, int sstride,
+                                                              DistillNets nets, GruCell cell,
                                                               const float* __restrict__ logstd, uint64_t seed, uint32_t counter, float beta, int teacher_noise,
                                                               const uint8_t* __restrict__ reset, const float* h_in, float* h_out, float* __restrict__ student_mu,
                                                               float* __restrict__ act_out, float* __restrict__ teacher_mu) {
@@ -439,7 +441,7 @@ __global__ __launch_bounds__(256) void distill_act_gru_kernel(int N, int nb, con
         const int cur = run_layers<L::LDA>(nets.n[0], buf, 0);
         sample<L::LDA, MIX>(buf[cur], N, r0, logstd, seed, counter, teacher_mu, MIX ? act_out : nullptr, true, beta, teacher_noise);
     } else {
-        gru_rows<H, MAXW, MIX>(lds, N, (blockIdx.x - nb) * MR, obs, stride, cell, nets.n[1], logstd, seed, counter, reset, h_in, h_out, student_mu, act_out, beta,
+        gru_rows<H, MAXW, MIX>(lds, N, (blockIdx.x - nb) * MR, sobs, sstride, cell, nets.n[1], logstd, seed, counter, reset, h_in, h_out, student_mu, act_out, beta,
                                teacher_noise);
     }
 }
@@ -668,14 +670,14 @@ extern "C" int bg_actor_sample_gru(int32_t N, const float* obs, int32_t obs_stri
     return 0;
 }
 
-extern "C" int bg_distill_act_gru(int32_t N, const float* teacher_obs, int32_t teacher_stride, int32_t n_teacher, const bg_mlp_layer_desc* teacher,
-                                  int32_t scan_points, const bg_gru_desc* gru, int32_t n_student, const bg_mlp_layer_desc* student, const float* student_logstd,
-                                  uint64_t seed, uint64_t counter, float beta, int32_t teacher_noise, const uint8_t* reset, const float* h_in, float* h_out,
-                                  float* student_mu, float* actions, float* teacher_mu, void* stream) {
-    const std::string who("bg_distill_act_gru");
+// who: the entry point's name; student_obs / student_stride: the rows of the cell's 47 inputs (bg_distill_act_gru: the teacher's)
+static int distill_act_gru(const std::string& who, int32_t N, const float* teacher_obs, int32_t teacher_stride, const float* student_obs, int32_t student_stride,
+                           int32_t n_teacher, const bg_mlp_layer_desc* teacher, int32_t scan_points, const bg_gru_desc* gru, int32_t n_student,
+                           const bg_mlp_layer_desc* student, const float* student_logstd, uint64_t seed, uint64_t counter, float beta, int32_t teacher_noise,
+                           const uint8_t* reset, const float* h_in, float* h_out, float* student_mu, float* actions, float* teacher_mu, void* stream) {
     if (!(beta >= 0.f && beta <= 1.f))  // (a NaN fails both comparisons)
         return bg_set_error(-1, (who + ": bad argument (beta: the teacher's probability of acting, a finite number in [0, 1])").c_str());
-    if (N <= 0 || !teacher_obs || !student || !teacher || !student_logstd || !h_in || !h_out || !actions || !teacher_mu)
+    if (N <= 0 || !teacher_obs || !student_obs || !student || !teacher || !student_logstd || !h_in || !h_out || !actions || !teacher_mu)
         return bg_set_error(-1, (who + ": bad argument").c_str());
     if (scan_points < 0 || scan_points > BG_MAX_HEIGHT_SCAN_POINTS) return bg_set_error(-1, (who + ": bad argument (scan_points)").c_str());
     GruCell cell;
@@ -686,17 +688,35 @@ extern "C" int bg_distill_act_gru(int32_t N, const float* teacher_obs, int32_t t
     if (const int rc = fill_net((who + " (student)").c_str(), n_student, student, 0, nets.n[1], maxw_s, gru->hidden)) return rc;
     if (teacher_stride != teacher[0].in)
         return bg_set_error(-4, (who + ": teacher_stride must equal the teacher's first-layer input (47 H + scan_points columns per row)").c_str());
+    if (student_stride < BG_NUM_OBS) return bg_set_error(-1, (who + ": bad argument (student_stride: at least the 47 columns the cell reads)").c_str());
     const int H = gru->hidden, nb = (N + MR - 1) / MR;
     const int kp = (teacher[0].in + KC - 1) / KC * KC, maxw = maxw_t > maxw_s ? maxw_t : maxw_s;
     const bool wide = maxw > 256 || kp > 256;
     const dim3 grid(2 * nb), block(256);
     hipStream_t st = (hipStream_t)stream;
     if (beta > 0.f)
-        BG_GRU_LAUNCH(distill_act_gru_kernel, BG_COMMA true, N, nb, teacher_obs, teacher_stride, nets, cell, student_logstd, seed, (uint32_t)counter, beta, teacher_noise,
+        BG_GRU_LAUNCH(distill_act_gru_kernel, BG_COMMA true, N, nb, teacher_obs, teacher_stride, student_obs, student_stride, nets, cell, student_logstd, seed, (uint32_t)counter, beta, teacher_noise,
                       reset, h_in, h_out, student_mu, actions, teacher_mu);
     else
-        BG_GRU_LAUNCH(distill_act_gru_kernel, BG_COMMA false, N, nb, teacher_obs, teacher_stride, nets, cell, student_logstd, seed, (uint32_t)counter, beta, teacher_noise,
+        BG_GRU_LAUNCH(distill_act_gru_kernel, BG_COMMA false, N, nb, teacher_obs, teacher_stride, student_obs, student_stride, nets, cell, student_logstd, seed, (uint32_t)counter, beta, teacher_noise,
                       reset, h_in, h_out, student_mu, actions, teacher_mu);
     HIP_OK(hipGetLastError());
     return 0;
+}
+
+extern "C" int bg_distill_act_gru(int32_t N, const float* teacher_obs, int32_t teacher_stride, int32_t n_teacher, const bg_mlp_layer_desc* teacher,
+                                  int32_t scan_points, const bg_gru_desc* gru, int32_t n_student, const bg_mlp_layer_desc* student, const float* student_logstd,
+                                  uint64_t seed, uint64_t counter, float beta, int32_t teacher_noise, const uint8_t* reset, const float* h_in, float* h_out,
+                                  float* student_mu, float* actions, float* teacher_mu, void* stream) {
+    return distill_act_gru("bg_distill_act_gru", N, teacher_obs, teacher_stride, teacher_obs, teacher_stride, n_teacher, teacher, scan_points, gru, n_student, student,
+                           student_logstd, seed, counter, beta, teacher_noise, reset, h_in, h_out, student_mu, actions, teacher_mu, stream);
+}
+
+extern "C" int bg_distill_act_gru_own(int32_t N, const float* teacher_obs, int32_t teacher_stride, const float* student_obs, int32_t student_stride,
+                                      int32_t n_teacher, const bg_mlp_layer_desc* teacher, int32_t scan_points, const bg_gru_desc* gru, int32_t n_student,
+                                      const bg_mlp_layer_desc* student, const float* student_logstd, uint64_t seed, uint64_t counter, float beta,
+                                      int32_t teacher_noise, const uint8_t* reset, const float* h_in, float* h_out, float* student_mu, float* actions,
+                                      float* teacher_mu, void* stream) {
+    return distill_act_gru("bg_distill_act_gru_own", N, teacher_obs, teacher_stride, student_obs, student_stride, n_teacher, teacher, scan_points, gru, n_student, student,
+                           student_logstd, seed, counter, beta, teacher_noise, reset, h_in, h_out, student_mu, actions, teacher_mu, stream);
 }

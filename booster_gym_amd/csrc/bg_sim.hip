@@ -46,9 +46,9 @@ struct bg_env {
     float* scan_xy = nullptr; // height scan: [P][2] points in the robot's yaw frame (cfg.height_scan_points > 0 only)
     float* hist = nullptr;    // observation history: ring [H][n][47] of the last H single observations (cfg.frame_stack = H > 1, or cfg.actor_heights at any H)
     int hist_head = 0;        // ... the plane of the newest one: the env-step kernels of a launch sequence write their observations there
-    int hist_planes = 0;      // R, the planes of the ring: cfg.frame_stack, or cfg.student_frame_stack = Hs when that is on
+    int hist_planes = 0;      // R, the planes of the ring: cfg.frame_stack, or cfg.student_frame_stack = Hs when that is on; + ceil(latency hi) with cfg.sensor_model
     float* student_bound = nullptr;  // [n][47 Hs]: the student's row of bg_env_reset / bg_env_step (bg_env_bind_student_obs), the caller's
-    float* sensor_bias = nullptr;    // [n][30]: the episode's bias of every sensor column, normalisation included (cfg.sensor_model; bg_obs_sensor)
+    float* sensor_bias = nullptr;    // [n][30]: the episode's bias of every sensor column, normalisation included (cfg.sensor_model; bg_obs_sensor, or bg_obs_assemble at 2)
     float* sensor_lat = nullptr;     // [n]: the episode's latency in env steps
     int64_t sensor_launches = 0;     // bg_obs_sensor launches enqueued (bg_env_sensor_launches)
     ModelDev* model_dev = nullptr;
@@ -360,28 +360,24 @@ struct SensorArgs {
     uint64_t seed;
 };
 constexpr int SENSOR_COLS = BG_NUM_SENSOR_COLS, SENSOR_LAT_STREAM = 8, SENSOR_LAT_COL = 6;
-__global__ __launch_bounds__(STACK_BLOCK) void bg_obs_sensor(int n, int H, int R, int head, int all_reset, uint32_t step, uint32_t stream0, SensorArgs A,
-                                                             const float* __restrict__ ring, const uint8_t* __restrict__ done,
-                                                             const int32_t* __restrict__ ep_len, float* bias, float* lat, float* __restrict__ dst) {
-    const unsigned W = (unsigned)(BG_NUM_OBS * H);
-    const unsigned t = blockIdx.x * STACK_BLOCK + threadIdx.x;  // (n 47 H < 2^31: bg_env_create)
-    if (t >= (unsigned)n * W) return;
-    const unsigned e = t / W, col = t - e * W, k = col / BG_NUM_OBS, c = col - k * BG_NUM_OBS;
-    const bool reset = all_reset || done[e];
-    const int age = reset ? 0 : ep_len[e];
-    const int d = H - 1 - (int)k;  // frame k = the observation of d steps ago
+// The rule above for one element: column c of the frame of d steps ago of env e, in a ring of R planes.  reset / age: the env's, as above; lam: where
+// the env's stored latency stands for a thread that needs it (read only where the env was not reset and the range is not [0, 0]).  The draws of a
+// reset env are made and stored here, by the threads of its newest frame.  Written once for bg_obs_sensor and for the student's row of
+// bg_obs_assemble<.., SENSOR>, so that the two give the same bits.
+__device__ __forceinline__ float sensor_element(const SensorArgs& A, const float* __restrict__ ring, int n, int R, int head, unsigned e, unsigned c, int d,
+                                                bool reset, int age, const float* lam_at, uint32_t step, uint32_t stream0, float* bias, float* lat) {
     const bool delayed = A.hi > 0.f;
     if (reset && d == 0 && c == SENSOR_LAT_COL) {  // the episode's latency, by the one thread of the env's newest command column
         float u[4];
         rand4_uniform(A.seed, e, step, stream0 + SENSOR_LAT_STREAM, u);
         lat[e] = A.lo + (A.hi - A.lo) * u[0];
     }
-    if (d > age) { dst[t] = 0.f; return; }
+    if (d > age) return 0.f;
     const int s = c < 6u ? (int)c : (c >= 11u && c < 35u) ? (int)c - 5 : -1;
     int j = d, i = 0;
     float f = 0.f;
     if (s >= 0 && delayed && !reset) {
-        const float lam = lat[e];
+        const float lam = *lam_at;
         i = (int)lam;  // (lam >= 0: floor)
         f = lam - (float)i;
         j = min(min(d + i, age), R - 1);  // (the second min never binds: d + i <= H - 1 + ceil(hi))
@@ -389,7 +385,7 @@ __global__ __launch_bounds__(STACK_BLOCK) void bg_obs_sensor(int n, int H, int R
     int slot = head - j;
     if (slot < 0) slot += R;
     float v = ring[((size_t)slot * n + e) * BG_NUM_OBS + c];
-    if (s < 0) { dst[t] = v; return; }
+    if (s < 0) return v;
     if (delayed && f != 0.f) {
         int sb = head - min(min(d + i + 1, age), R - 1);
         if (sb < 0) sb += R;
@@ -397,7 +393,11 @@ __global__ __launch_bounds__(STACK_BLOCK) void bg_obs_sensor(int n, int H, int R
         v = v + f * (b - v);
     }
     const int g = s < 3 ? 0 : s < 6 ? 1 : s < 18 ? 2 : 3;
-    const bg_rand spec = g == 0 ? A.bias[0] : g == 1 ? A.bias[1] : g == 2 ? A.bias[2] : A.bias[3];
+    // (field by field: a select of whole structs makes the compiler keep a copy of A in scratch and index it)
+    bg_rand spec;
+    spec.mode = g == 0 ? A.bias[0].mode : g == 1 ? A.bias[1].mode : g == 2 ? A.bias[2].mode : A.bias[3].mode;
+    spec.a = g == 0 ? A.bias[0].a : g == 1 ? A.bias[1].a : g == 2 ? A.bias[2].a : A.bias[3].a;
+    spec.b = g == 0 ? A.bias[0].b : g == 1 ? A.bias[1].b : g == 2 ? A.bias[2].b : A.bias[3].b;
     if (spec.mode != 0) {
         float beta;
         if (reset) {
@@ -419,7 +419,19 @@ __global__ __launch_bounds__(STACK_BLOCK) void bg_obs_sensor(int n, int H, int R
         }
         v += beta;
     }
-    dst[t] = v;
+    return v;
+}
+__global__ __launch_bounds__(STACK_BLOCK) void bg_obs_sensor(int n, int H, int R, int head, int all_reset, uint32_t step, uint32_t stream0, SensorArgs A,
+                                                             const float* __restrict__ ring, const uint8_t* __restrict__ done,
+                                                             const int32_t* __restrict__ ep_len, float* bias, float* lat, float* __restrict__ dst) {
+    const unsigned W = (unsigned)(BG_NUM_OBS * H);
+    const unsigned t = blockIdx.x * STACK_BLOCK + threadIdx.x;  // (n 47 H < 2^31: bg_env_create)
+    if (t >= (unsigned)n * W) return;
+    const unsigned e = t / W, col = t - e * W, k = col / BG_NUM_OBS, c = col - k * BG_NUM_OBS;
+    const bool reset = all_reset || done[e];
+    const int age = reset ? 0 : ep_len[e];
+    const int d = H - 1 - (int)k;  // frame k = the observation of d steps ago
+    dst[t] = sensor_element(A, ring, n, R, head, e, c, d, reset, age, lat + e, step, stream0, bias, lat);
 }
 
 // ------------------------------------------------------------------ the actor's row with the terrain height scan (cfg.actor_heights)
@@ -446,12 +458,29 @@ __global__ __launch_bounds__(STACK_BLOCK) void bg_obs_sensor(int n, int H, int R
 //   - the actor-row threads of a reset env neither read nor write the older planes (their H - 1 older frames lie among the R - 1 the student row zeroes).
 // So no ring element is read after another thread has changed it, and none is written twice.  STUDENT is a template parameter, not a uniform branch:
 // the instantiations without it keep today's code (head + 1 + k mod H, the single loop) and today's registers, and the extra arguments are unused there.
+//
+// SENSOR (cfg.sensor_model = 2, distillation.student_sensors; with STUDENT only): the student's row [47 Hs], and only that row, goes through the sensor
+// model: every element is sensor_element, bg_obs_sensor's rule and its draws on its streams (stream1 = RS_SENSOR / RS_SENSOR_RESET), so the row has the
+// bits of a sensors.enabled env's actor row at frame_stack Hs.  The ring has R = Hs + ceil(latency hi) planes, so the student's frame count Hs and the
+// ring modulus R are two arguments.  The discipline of the ring in this instantiation is bg_obs_sensor's, the simplest that holds:
+//   - NOBODY writes the ring here: every plane is read-only in this launch, whoever was reset;
+//   - both rows decide "older than the episode" by d > age (age = 0 for a reset env, else its I_EP_LEN) and take the constant 0 there.  A plane of d
+//     steps ago holds this episode's observation exactly when d <= age, and the zero-the-planes rule above gives 0 exactly when d > age (the planes
+//     zeroed at the reset are overwritten one per step), so the teacher's row has today's bits;
+//   - a delayed read goes to plane min(d + i (+ 1), age) <= age steps ago: this episode's, never a stale one (a reset env reads plane `head` only);
+//   - bias [n][30] and latency [n] of an env are written only by the student-row threads of its newest frame on the step that resets it, and read only
+//     for envs that were not reset: no element is read in the launch that writes it.
+// The per-env scalars (reset flag, age, lam) are read once, in front of the barrier, into two more floats of the LDS row the block already has.
+// Deterministic, no atomics.  The instantiations without SENSOR keep their code and registers; A, sbias, slat, Hs and stream1 are unused there.  (A is
+// a kernel argument as in bg_obs_sensor, not a copy made from E.cfg: the compiler keeps such a copy in scratch and indexes it by the column's group.)
 constexpr int ASM_BLOCK = 256, ASM_ENVS = 4;
-template <bool H16, bool STUDENT = false>
+template <bool H16, bool STUDENT = false, bool SENSOR = false>
 __global__ __launch_bounds__(ASM_BLOCK) void bg_obs_assemble(EnvDev E, const float2* __restrict__ pts, int P, int H, int head, int all_reset, uint32_t step,
                                                              uint32_t stream0, float* ring, const uint8_t* __restrict__ done, float* __restrict__ dst,
-                                                             float* __restrict__ priv, int stride, int R, float* __restrict__ sdst) {
-    __shared__ float s_pose[ASM_ENVS][6];  // base x, y, z, sin yaw, cos yaw, reset in this step
+                                                             float* __restrict__ priv, int stride, int R, float* __restrict__ sdst, int Hs, uint32_t stream1,
+                                                             SensorArgs A, float* sbias, float* slat) {
+    static_assert(STUDENT || !SENSOR, "the sensor model of bg_obs_assemble is the student's row's");
+    __shared__ float s_pose[ASM_ENVS][SENSOR ? 8 : 6];  // base x, y, z, sin yaw, cos yaw, reset in this step (, SENSOR: age as its int bits, lam)
     extern __shared__ float s_noise[];     // [ASM_ENVS][P]: S n_p
     const int n = E.n, e0 = blockIdx.x * ASM_ENVS, rows = min(ASM_ENVS, n - e0);
     const float S = E.cfg.height_scan_scale;
@@ -465,6 +494,11 @@ __global__ __launch_bounds__(ASM_BLOCK) void bg_obs_assemble(EnvDev E, const flo
 #undef SFLD
         bg_sincos(quat_yaw(q), &sp[3], &sp[4]);
         sp[5] = (all_reset || done[e]) ? 1.f : 0.f;
+        if (SENSOR) {
+            const bool reset = all_reset || done[e];
+            sp[6] = __int_as_float(reset ? 0 : E.i[(size_t)I_EP_LEN * n + e]);
+            sp[7] = (!reset && A.hi > 0.f) ? slat[e] : 0.f;
+        }
     }
     if (spec.mode != 0) {
         const int G = (P + 3) >> 2;
@@ -491,7 +525,12 @@ __global__ __launch_bounds__(ASM_BLOCK) void bg_obs_assemble(EnvDev E, const flo
         float v;
         if (col < F) {
             const unsigned k = col / BG_NUM_OBS, c = col - k * BG_NUM_OBS;
-            if (STUDENT) {  // frame k = the observation of H - 1 - k steps ago = plane head - (H - 1 - k) mod R; read only (the invariant above)
+            if (SENSOR) {  // the same plane, "older than the episode" by d > age; nobody writes the ring (the discipline above)
+                const unsigned d = (unsigned)H - 1u - k;
+                unsigned slot = (unsigned)head + (unsigned)R - d;
+                if (slot >= (unsigned)R) slot -= (unsigned)R;
+                v = (int)d <= __float_as_int(sp[6]) ? ring[((size_t)slot * n + e) * BG_NUM_OBS + c] : 0.f;
+            } else if (STUDENT) {  // frame k = the observation of H - 1 - k steps ago = plane head - (H - 1 - k) mod R; read only (the invariant above)
                 unsigned slot = (unsigned)head + (unsigned)R - ((unsigned)H - 1u - k);
                 if (slot >= (unsigned)R) slot -= (unsigned)R;
                 v = (k + 1u == (unsigned)H || sp[5] == 0.f) ? ring[((size_t)slot * n + e) * BG_NUM_OBS + c] : 0.f;
@@ -514,7 +553,15 @@ __global__ __launch_bounds__(ASM_BLOCK) void bg_obs_assemble(EnvDev E, const flo
         }
         dst[(size_t)e0 * W + t] = v;
     }
-    if (STUDENT) {  // the student's rows [47 R]: every plane, oldest first; the only threads that zero a reset env's older planes
+    if (SENSOR) {  // the student's rows [47 Hs] through the sensor model: the existing student loop's shape, every element by bg_obs_sensor's rule
+        const unsigned Ws = (unsigned)(BG_NUM_OBS * Hs);  // (n Ws < 2^31: bg_env_create)
+        for (unsigned t = threadIdx.x; t < (unsigned)rows * Ws; t += ASM_BLOCK) {
+            const unsigned el = t / Ws, col = t - el * Ws, e = (unsigned)e0 + el;
+            const unsigned k = col / BG_NUM_OBS, cc = col - k * BG_NUM_OBS;
+            const float* sp = s_pose[el];
+            sdst[(size_t)e0 * Ws + t] = sensor_element(A, ring, n, R, head, e, cc, Hs - 1 - (int)k, sp[5] != 0.f, __float_as_int(sp[6]), &sp[7], step, stream1, sbias, slat);
+        }
+    } else if (STUDENT) {  // the student's rows [47 R]: every plane, oldest first; the only threads that zero a reset env's older planes
         const unsigned Ws = (unsigned)(BG_NUM_OBS * R);  // (n Ws < 2^31: bg_env_create)
         for (unsigned t = threadIdx.x; t < (unsigned)rows * Ws; t += ASM_BLOCK) {
             const unsigned el = t / Ws, col = t - el * Ws, e = (unsigned)e0 + el;
@@ -1155,8 +1202,10 @@ extern "C" int bg_env_create(const bg_env_cfg* cfg, const bg_model* model, bg_en
         (cfg->priv_extras != 0 && (int64_t)cfg->num_envs * (BG_NUM_PRIV + cfg->height_scan_points + priv_extras_columns(cfg->priv_extras)) >= (int64_t)1 << 31))
         return fail(-1, "bg_env_create: priv_extras must be a combination of BG_PRIV_EXTRA_FEET | GROUND | JOINTS (0 = off) with num_envs x (14 + height_scan_points + extras) below 2^31");
     if (cfg->sensor_model != 0) {
-        if (cfg->sensor_model != 1) return fail(-1, "bg_env_create: sensor_model must be 0 (off) or 1");
-        if (cfg->actor_heights) return fail(-1, "bg_env_create: sensor_model is not available with actor_heights (bg_obs_assemble writes those rows, and the student's)");
+        if (cfg->sensor_model != 1 && cfg->sensor_model != 2) return fail(-1, "bg_env_create: sensor_model must be 0 (off), 1 (the actor's row) or 2 (the student's row only)");
+        if (cfg->sensor_model == 1 && cfg->actor_heights) return fail(-1, "bg_env_create: sensor_model is not available with actor_heights (bg_obs_assemble writes those rows, and the student's)");
+        if (cfg->sensor_model == 2 && !(cfg->actor_heights && cfg->student_frame_stack >= 1))
+            return fail(-1, "bg_env_create: sensor_model 2 (the student's row only) needs actor_heights and student_frame_stack >= 1: the row is bg_obs_assemble's third output");
         const bg_rand* sb[4] = {&cfg->sensor_bias_gravity, &cfg->sensor_bias_ang_vel, &cfg->sensor_bias_dof_pos, &cfg->sensor_bias_dof_vel};
         // (a test on the stored bits, never on a float value: this file is compiled with finite-math-only, which folds any other form away)
         const auto finite = [](const float& x) { uint32_t b; memcpy(&b, &x, sizeof(b)); return ((b >> 23) & 0xFFu) != 0xFFu; };
@@ -1239,6 +1288,12 @@ extern "C" int bg_env_bind_student_obs(bg_env* e, float* student_obs) {
     return 0;
 }
 
+// the sensor model's parameters as its launches take them (bg_obs_sensor; bg_obs_assemble with cfg.sensor_model = 2); all zero with the model off
+static SensorArgs sensor_args(const bg_env_cfg& c) {
+    return {{c.sensor_bias_gravity, c.sensor_bias_ang_vel, c.sensor_bias_dof_pos, c.sensor_bias_dof_vel},
+            {c.norm_gravity, c.norm_ang_vel, c.norm_dof_pos, c.norm_dof_vel}, c.sensor_latency_lo, c.sensor_latency_hi, c.seed};
+}
+
 // student: the destination of the student's row [n][47 Hs] (cfg.student_frame_stack), required exactly when the field is on
 static int launch_step(bg_env* e, const float* actions, int mode, const StepOut& dst, float* student, void* stream) {
     if (!dst.obs || !dst.priv || !dst.rew || !dst.done || !dst.tout) return fail(-1, "bg_env_step: outputs are not bound");
@@ -1293,12 +1348,19 @@ static int launch_step(bg_env* e, const float* actions, int mode, const StepOut&
         dim3 gs((unsigned)((e->n + ASM_ENVS - 1) / ASM_ENVS));
         const uint32_t base = mode ? (uint32_t)bg::RS_SCAN_RESET : (uint32_t)bg::RS_SCAN;
         const size_t lds = e->cfg.noise_height_measurements.mode != 0 ? sizeof(float) * ASM_ENVS * P : 0;  // (at most 16 kB: P <= 1024)
-        const int R = e->hist_planes;
-        if (e->cfg.student_frame_stack) {  // the same one launch, with the student's row as its third output
-            if (e->h) hipLaunchKernelGGL((bg_obs_assemble<true, true>), gs, dim3(ASM_BLOCK), lds, st, env_dev(e), (const float2*)e->scan_xy, P, H, e->hist_head, mode, cnt, base, e->hist, (const uint8_t*)out.done, dst.obs, out.priv, out.priv_stride, R, student);
-            else hipLaunchKernelGGL((bg_obs_assemble<false, true>), gs, dim3(ASM_BLOCK), lds, st, env_dev(e), (const float2*)e->scan_xy, P, H, e->hist_head, mode, cnt, base, e->hist, (const uint8_t*)out.done, dst.obs, out.priv, out.priv_stride, R, student);
-        } else if (e->h) hipLaunchKernelGGL((bg_obs_assemble<true, false>), gs, dim3(ASM_BLOCK), lds, st, env_dev(e), (const float2*)e->scan_xy, P, H, e->hist_head, mode, cnt, base, e->hist, (const uint8_t*)out.done, dst.obs, out.priv, out.priv_stride, R, student);
-        else hipLaunchKernelGGL((bg_obs_assemble<false, false>), gs, dim3(ASM_BLOCK), lds, st, env_dev(e), (const float2*)e->scan_xy, P, H, e->hist_head, mode, cnt, base, e->hist, (const uint8_t*)out.done, dst.obs, out.priv, out.priv_stride, R, student);
+        // R: the ring's planes; Hs: the student's frames (R without the sensor model's latency planes); sbase: the sensor model's streams (sensor_model 2)
+        const int R = e->hist_planes, Hs = e->cfg.student_frame_stack;
+        const uint32_t sbase = mode ? (uint32_t)bg::RS_SENSOR_RESET : (uint32_t)bg::RS_SENSOR;
+#define BG_ASM_LAUNCH(...) hipLaunchKernelGGL((bg_obs_assemble<__VA_ARGS__>), gs, dim3(ASM_BLOCK), lds, st, env_dev(e), (const float2*)e->scan_xy, P, H, e->hist_head, mode, cnt, base, e->hist, (const uint8_t*)out.done, dst.obs, out.priv, out.priv_stride, R, student, Hs, sbase, sensor_args(e->cfg), e->sensor_bias, e->sensor_lat)
+        if (e->cfg.sensor_model == 2) {  // the same one launch, the student's row through the sensor model (never bg_obs_sensor: sensor_launches stays 0)
+            if (e->h) BG_ASM_LAUNCH(true, true, true);
+            else BG_ASM_LAUNCH(false, true, true);
+        } else if (e->cfg.student_frame_stack) {  // the same one launch, with the student's row as its third output
+            if (e->h) BG_ASM_LAUNCH(true, true);
+            else BG_ASM_LAUNCH(false, true);
+        } else if (e->h) BG_ASM_LAUNCH(true, false);
+        else BG_ASM_LAUNCH(false, false);
+#undef BG_ASM_LAUNCH
     } else if (e->scan_xy) {  // the critic's height scan from the state this launch sequence has just stored (bg_height_scan)
         const int P = e->cfg.height_scan_points;
         dim3 gs((unsigned)(((int64_t)e->n * P + SCAN_BLOCK - 1) / SCAN_BLOCK));
@@ -1309,9 +1371,7 @@ static int launch_step(bg_env* e, const float* actions, int mode, const StepOut&
         const int H = e->cfg.frame_stack;
         dim3 gs((unsigned)(((int64_t)e->n * BG_NUM_OBS * H + STACK_BLOCK - 1) / STACK_BLOCK));
         if (e->cfg.sensor_model) {  // in its place: the same row through the sensor model (bg_obs_sensor), H = 1 included
-            const bg_env_cfg& c = e->cfg;
-            const SensorArgs A = {{c.sensor_bias_gravity, c.sensor_bias_ang_vel, c.sensor_bias_dof_pos, c.sensor_bias_dof_vel},
-                                  {c.norm_gravity, c.norm_ang_vel, c.norm_dof_pos, c.norm_dof_vel}, c.sensor_latency_lo, c.sensor_latency_hi, c.seed};
+            const SensorArgs A = sensor_args(e->cfg);
             const uint32_t base = mode ? (uint32_t)bg::RS_SENSOR_RESET : (uint32_t)bg::RS_SENSOR;
             hipLaunchKernelGGL(bg_obs_sensor, gs, dim3(STACK_BLOCK), 0, st, e->n, H, e->hist_planes, e->hist_head, mode, cnt, base, A, (const float*)e->hist,
                                (const uint8_t*)out.done, (const int32_t*)(e->i + (size_t)I_EP_LEN * e->n), e->sensor_bias, e->sensor_lat, dst.obs);

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..utils.sensors import GROUPS as SENSOR_GROUPS, SENSOR_COLUMNS, sensors_cfg
+from ..utils.sensors import GROUPS as SENSOR_GROUPS, SENSOR_COLUMNS, sensors_cfg, sensors_section
 from ..utils.terrain import actor_heights_of
 from ..utils.urdf import load_model
 from ..utils.utils import rand_spec
@@ -63,6 +63,25 @@ def student_frame_stack_of(cfg):
         raise ValueError("distillation.student_frame_stack needs terrain.actor_heights: true: the student's row is an output of the perceptive "
                          "teacher's env (bg_obs_assemble) only")
     return Hs
+
+
+STUDENT_SENSORS_KEYS = ("bias", "latency_steps")  # the `sensors:` section's keys minus `enabled`
+
+
+def student_sensors_of(cfg):
+    """env.student_sensors (set by utils/distill.py's Distiller from distillation.student_sensors, never shipped in a yaml's env: section; absent or
+    None = off): the sensor model of the student's row, and of that row only, as a SensorsCfg.  ValueError naming distillation.student_sensors.<key>
+    by the rules of the `sensors:` section, and unless the env writes a student's row (env.student_frame_stack)."""
+    sec = cfg["env"].get("student_sensors")
+    if sec is None:
+        return None
+    if not isinstance(sec, dict):
+        raise ValueError(f"distillation.student_sensors must be null or a mapping of its keys ({', '.join(STUDENT_SENSORS_KEYS)}), got {sec!r}")
+    parsed = sensors_section(sec, "distillation.student_sensors", STUDENT_SENSORS_KEYS)
+    if not student_frame_stack_of(cfg):
+        raise ValueError("distillation.student_sensors needs the student's own row (env.student_frame_stack, which the Distiller sets with the key on, "
+                         "also at the teacher's env.frame_stack): the sensor model is on that row only")
+    return parsed
 
 
 PRIVILEGED_EXTRAS = tuple(g for g, _, _ in _lib.PRIV_EXTRA_GROUPS)  # the legal names of env.privileged_extras, in the row's order
@@ -210,6 +229,7 @@ class T1(BaseTask):
         super().__init__(cfg)
         check_env_sizes(cfg, len(self.terrain.height_points))  # (before anything touches the device)
         student_frame_stack_of(cfg)
+        student_sensors_of(cfg)
         if "feet" in privileged_extras_of(cfg)[0]:
             contact_force_scale_of(cfg)
         sensors_cfg(cfg)
@@ -342,6 +362,8 @@ class T1(BaseTask):
         self.num_student_obs = self.num_single_obs * self.student_frame_stack
         # the sensor model (sensors.enabled): an episode's bias and latency on the 30 sensor columns of every frame, by bg_obs_sensor; None = off
         self.sensors = sensors_cfg(cfg)
+        # the sensor model of the student's row only (distillation.student_sensors through env.student_sensors), by bg_obs_assemble itself; None = off
+        self.student_sensors = student_sensors_of(cfg)
         self.dt = cfg["control"]["decimation"] * cfg["sim"]["dt"]
         N, dev = self.num_envs, self.device
         self.obs_buf = torch.zeros(N, self.num_obs, dtype=torch.float, device=dev)
@@ -460,11 +482,12 @@ class T1(BaseTask):
                     setr(c.noise_height_measurements, nc.get("height_measurements"))
         c.frame_stack = self.frame_stack
         c.student_frame_stack = self.student_frame_stack
-        if self.sensors is not None:  # (off: the seven fields stay zero, as in a struct older than them)
-            c.sensor_model = 1
-            for g, entry in zip(SENSOR_GROUPS, self.sensors.bias):
-                setr(getattr(c, "sensor_bias_" + g), entry)
-            c.sensor_latency_lo, c.sensor_latency_hi = self.sensors.latency_steps
+        for model, sc in ((1, self.sensors), (2, self.student_sensors)):  # (both off: the seven fields stay zero, as in a struct older than them)
+            if sc is not None:  # (never both: sensors.enabled refuses terrain.actor_heights, the student's row needs it)
+                c.sensor_model = model
+                for g, entry in zip(SENSOR_GROUPS, sc.bias):
+                    setr(getattr(c, "sensor_bias_" + g), entry)
+                c.sensor_latency_lo, c.sensor_latency_hi = sc.latency_steps
         if self.privileged_extras:  # (off: the three fields stay zero, as in a struct older than them)
             c.priv_extras = sum(bit for g, bit, _ in _lib.PRIV_EXTRA_GROUPS if g in self.privileged_extras)
             if "feet" in self.privileged_extras:
@@ -771,6 +794,12 @@ class T1(BaseTask):
     @property
     def sensor_model(self):
         return self.sensors is not None
+
+    @property
+    def student_sensor_model(self):
+        """The student's row, and only that row, goes through the sensor model (distillation.student_sensors), inside bg_obs_assemble; `sensor_bias`
+        and `sensor_latency` are readable then too, and `sensor_launches` stays 0."""
+        return self.student_sensors is not None
 
     @property
     def sensor_columns(self):

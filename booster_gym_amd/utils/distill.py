@@ -38,6 +38,13 @@ newest single observation (columns [0, 47) of the teacher's row) and the actor's
 the frame stack's rule) and carries across iterations; the update back-propagates through the iteration's T steps from the state h0 stored at its
 start (the gradient is truncated there): model.GRUTrainer around the trunk's MLPTrainer.  The optimiser holds memory.* and actor.*; the checkpoint
 carries memory.* and re-enters under algorithm.actor_memory: H.  0 (the default, also absent): everything above, unchanged.
+
+distillation.student_sensors: {bias: {gravity, ang_vel, dof_pos, dof_vel}, latency_steps: [lo, hi]} (the `sensors:` section without `enabled`, its
+meaning, defaults and rules: utils/sensors.py) distils the student under the sensor model it will meet on the robot while the teacher keeps acting
+and labelling on its clean row: the env's last launch sends the student's row, and only that row, through bg_obs_sensor's rule (bg_env_cfg.sensor_model
+= 2, inside bg_obs_assemble).  The student's row is then no prefix of the teacher's, so it always has a buffer of its own (env.student_frame_stack
+also at Hs = H; bg_distill_act_hist / _mix, a recurrent student's cell through bg_distill_act_gru_own), the checkpoint's entry carries the section, and
+the student re-enters under sensors.enabled: true with the same bias and latency_steps.  Absent or null: everything above, unchanged.
 """
 import argparse
 import ctypes
@@ -60,13 +67,14 @@ from .model import CRITIC_HIDDEN, ActorCritic, WeightClock, check_hidden, hidden
 from .optim import FlatAdam
 from .recorder import Recorder
 from .runner import hidden_widths
+from .sensors import sensors_as_section, sensors_section
 from .supervised import SupervisedTrainer
 from .terrain import actor_heights_of, height_scan_points
 from .utils import mirror_rows
 
 DEFAULTS = {"teacher_checkpoint": None, "student_hidden": [256, 128, 128], "num_epochs": 5, "learning_rate": 1.0e-3, "max_grad_norm": 1.0,
             "student_noise_std": 0.1, "student_frame_stack": None, "symmetric_coef": 0.0, "teacher_action_prob": 0.0, "teacher_action_iterations": 0,
-            "teacher_action_noise": True, "student_memory": 0}
+            "teacher_action_noise": True, "student_memory": 0, "student_sensors": None}
 STUDENT_MEMORY = (0, 128, 256)  # the widths of the recurrent student's cell the kernels take (0: no memory)
 
 
@@ -102,6 +110,7 @@ def distillation_cfg(cfg, world_size=1):
     if int(world_size) != 1:
         raise ValueError(f"distillation runs on one rank (WORLD_SIZE = {world_size}): data parallelism is out of scope")
     student_memory_of(cfg)  # (ValueError naming the key: its value, and what a recurrent student excludes)
+    student_sensors_of(cfg)
     v = dict(DEFAULTS, **sec)
     ck = v["teacher_checkpoint"]
     if ck is not None and not isinstance(ck, str):
@@ -185,6 +194,21 @@ def student_memory_of(cfg):
     return H
 
 
+STUDENT_SENSORS_KEYS = ("bias", "latency_steps")  # the `sensors:` section's keys minus `enabled`
+
+
+def student_sensors_of(cfg):
+    """distillation.student_sensors as a SensorsCfg: the sensor model of the student's row (bias per episode and a sensing delay on its 30 sensor
+    columns; the teacher's row stays clean), None with the key absent or null (off).  Pure.  The rules are the `sensors:` section's
+    (sensors.sensors_section); every refusal is a ValueError naming distillation.student_sensors.<key>."""
+    sec = _key(cfg, "student_sensors")
+    if sec is None:
+        return None
+    if not isinstance(sec, dict):
+        raise ValueError(f"distillation.student_sensors must be null or a mapping of its keys ({', '.join(STUDENT_SENSORS_KEYS)}), got {sec!r}")
+    return sensors_section(sec, "distillation.student_sensors", STUDENT_SENSORS_KEYS)
+
+
 def teacher_action_of(cfg):
     """(beta_0, iterations, noise) of DAgger's mixing: distillation.teacher_action_prob in [0, 1] (0, the default: the student always acts),
     teacher_action_iterations (an integer >= 0: beta reaches 0 after that many iterations, 0 = constant) and teacher_action_noise (a bool).  Pure.
@@ -210,16 +234,21 @@ def student_mirror_maps(dof_names, dof_axes, default_dof_pos, frames):
     return mirror_maps(dof_names, dof_axes, default_dof_pos, _lib.NUM_OBS * int(frames), int(frames), None)
 
 
-def student_overrides(num_observations, student_frame_stack=None, student_memory=None):
+def student_overrides(num_observations, student_frame_stack=None, student_memory=None, student_sensors=None):
     """The rule under which a student re-enters Runner / play.py / export_model.py / evaluate.py, written once: the teacher's config without the
-    actor's scan, the student's own history when it has one, and the row its actor takes.  student_cfg_overrides derives the arguments from the
-    teacher's config, checkpoint_student_overrides from a student checkpoint."""
+    actor's scan, the student's own history when it has one, the row its actor takes, and the sensor model it was distilled under
+    (student_sensors: the section {bias, latency_steps} as plain dicts and lists; bg_obs_sensor then writes the row the student trained on).
+    student_cfg_overrides derives the arguments from the teacher's config, checkpoint_student_overrides from a student checkpoint."""
     over = {"terrain.actor_heights": False}
     if student_frame_stack is not None:
         over["env.frame_stack"] = int(student_frame_stack)
     over["env.num_observations"] = int(num_observations)
     if student_memory:  # a recurrent student: Runner(test=True) builds its actor behind a GRU cell of that width
         over["algorithm.actor_memory"] = int(student_memory)
+    if student_sensors is not None:
+        over["sensors.enabled"] = True
+        over["sensors.bias"] = dict(student_sensors["bias"])
+        over["sensors.latency_steps"] = list(student_sensors["latency_steps"])
     return over
 
 
@@ -227,11 +256,13 @@ def student_cfg_overrides(cfg):
     """The overrides under which the student checkpoint re-enters Runner / play.py / export_model.py: the teacher's config without the actor's scan,
     and with distillation.student_frame_stack = Hs > H the student's own history."""
     H = int(cfg["env"].get("frame_stack", 1) or 1)
+    sc = student_sensors_of(cfg)
+    sensors = None if sc is None else sensors_as_section(sc)
     if isinstance(cfg.get("distillation"), dict) and cfg["distillation"].get("student_frame_stack") is not None:
         Hs = student_frame_stack_of(cfg)
         if Hs > H:
-            return student_overrides(_lib.NUM_OBS * Hs, Hs)
-    return student_overrides(_lib.NUM_OBS * H, None, student_memory_of(cfg) if isinstance(cfg.get("distillation"), dict) else None)
+            return student_overrides(_lib.NUM_OBS * Hs, Hs, None, sensors)
+    return student_overrides(_lib.NUM_OBS * H, None, student_memory_of(cfg) if isinstance(cfg.get("distillation"), dict) else None, sensors)
 
 
 def checkpoint_student_overrides(checkpoint):
@@ -242,8 +273,9 @@ def checkpoint_student_overrides(checkpoint):
         return None
     sd = checkpoint["model"]
     if "memory.weight_ih" in sd:  # a recurrent student: the row is what its cell reads, the actor takes the cell's state
-        return student_overrides(int(sd["memory.weight_ih"].shape[1]), entry.get("student_frame_stack"), int(sd["memory.weight_hh"].shape[1]))
-    return student_overrides(int(sd["actor.0.weight"].shape[1]), entry.get("student_frame_stack"))
+        return student_overrides(int(sd["memory.weight_ih"].shape[1]), entry.get("student_frame_stack"), int(sd["memory.weight_hh"].shape[1]),
+                                 entry.get("student_sensors"))
+    return student_overrides(int(sd["actor.0.weight"].shape[1]), entry.get("student_frame_stack"), None, entry.get("student_sensors"))
 
 
 class Distiller:
@@ -276,9 +308,15 @@ class Distiller:
         self.beta0, self.beta_iterations, self.teacher_noise = teacher_action_of(cfg)
         self.memory = student_memory_of(cfg)  # the width of the recurrent student's GRU cell; 0: none
         Hs, H = student_frame_stack_of(cfg), frame_stack_of(cfg)
-        self.history = Hs > H  # the student's own, longer history: a second row of the env, bg_distill_act_hist
+        sensors = student_sensors_of(cfg)
+        self.student_sensors = None if sensors is None else sensors_as_section(sensors)  # the validated section as plain dicts, lists and floats
+        # the student's own row, a second output of the env, through bg_distill_act_hist: a longer history, or the sensor model at any Hs (the
+        # student's row is then no prefix of the teacher's)
+        self.history = Hs > H or sensors is not None
         if self.history:
             cfg["env"]["student_frame_stack"] = Hs  # (the env's name of it; T1 builds the ring of Hs planes and the third output of its last launch)
+        if sensors is not None:
+            cfg["env"]["student_sensors"] = self.student_sensors  # (the env's name of it: bg_env_cfg.sensor_model = 2)
         critic_hidden = hidden_widths(cfg)[1]
         self._set_seed()
         task = cfg["basic"]["task"]
@@ -415,8 +453,10 @@ class Distiller:
         "height_points", no "optimizer"; the critic is the untrained one built here."""
         d = {"model": self.student.state_dict(), "curriculum": self.env.curriculum_prob,
              "distillation": {"teacher": str(self.dcfg.teacher_checkpoint), "iteration": int(self.iteration_count), "loss": float(self.last_loss)}}
-        if self.history:
+        if self.history and self.env.student_frame_stack > self.env.frame_stack:
             d["distillation"]["student_frame_stack"] = self.env.student_frame_stack
+        if self.student_sensors is not None:
+            d["distillation"]["student_sensors"] = self.student_sensors
         if self.symmetry:
             d["distillation"]["symmetric_coef"] = self.symmetric_coef
         if self.beta0 > 0:
@@ -459,7 +499,9 @@ class Distiller:
             if key != self._gru_desc[0]:
                 self._gru_desc = (key, self.student.gru_descriptor())
             gnets = (len(td), td, self.scan, self._gru_desc[1], len(sd), sd)
-            name, mid = "bg_distill_act_gru", lambda n: gnets + rng() + (beta, noise, p(mt.rollout_reset(n, self._last_dones, dones)), p(h), p(h))
+            tail = lambda n: gnets + rng() + (beta, noise, p(mt.rollout_reset(n, self._last_dones, dones)), p(h), p(h))
+            # (the cell's 47 inputs from the student's own row where it has one: the sensor model)
+            name, mid = ("bg_distill_act_gru_own", lambda n: own(n) + tail(n)) if self.history else ("bg_distill_act_gru", tail)
         elif self.beta0 > 0:  # DAgger's mixing: one launch of its own kind on the same buffers
             name, mid = "bg_distill_act_mix", lambda n: own(n) + nets + rng() + (beta, noise)
         elif self.history:

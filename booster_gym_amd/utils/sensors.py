@@ -58,8 +58,8 @@ def _number(x):
     return not isinstance(x, bool) and isinstance(x, (int, float)) and math.isfinite(x)
 
 
-def _bias_entry(group, entry):
-    key = f"sensors.bias.{group}"
+def _bias_entry(group, entry, prefix="sensors"):
+    key = f"{prefix}.bias.{group}"
     if entry is None:
         return None
     if not isinstance(entry, dict):
@@ -85,25 +85,40 @@ def sensors_cfg(cfg):
     the section is read then), or ValueError naming the key.  Pure: no tensors, no device."""
     if not sensors_enabled(cfg):
         return None
-    sec = cfg["sensors"]
-    unknown = sorted(set(sec) - set(DEFAULTS))
+    parsed = sensors_section(cfg["sensors"], "sensors", tuple(DEFAULTS))
+    if actor_heights_of(cfg["terrain"]):
+        raise ValueError("sensors.enabled is not available with terrain.actor_heights: true: those rows, and a distillation's student row with them, "
+                         "are written by bg_obs_assemble, which knows nothing of the sensor model")
+    return parsed
+
+
+def sensors_section(sec, prefix, keys):
+    """A mapping {bias: {gravity, ang_vel, dof_pos, dof_vel}, latency_steps: [lo, hi]} as a SensorsCfg (absent keys: DEFAULTS), or ValueError naming
+    `prefix`.<key>.  keys: the keys the mapping may hold.  The rules of the `sensors:` section, written once for it and for
+    distillation.student_sensors (utils/distill.py).  Pure."""
+    unknown = sorted(set(sec) - set(keys))
     if unknown:
-        raise ValueError(f"sensors.{unknown[0]} is not a key of the section ({', '.join(DEFAULTS)})")
+        raise ValueError(f"{prefix}.{unknown[0]} is not a key of the section ({', '.join(keys)})")
     bias = sec.get("bias")
     if bias is None:
         bias = {}
     if not isinstance(bias, dict):
-        raise ValueError(f"sensors.bias must be null or a mapping of {', '.join(GROUPS)}, got {bias!r}")
+        raise ValueError(f"{prefix}.bias must be null or a mapping of {', '.join(GROUPS)}, got {bias!r}")
     unknown = sorted(set(bias) - set(GROUPS))
     if unknown:
-        raise ValueError(f"sensors.bias.{unknown[0]} is not a group of sensor columns ({', '.join(GROUPS)})")
-    entries = tuple(_bias_entry(g, bias.get(g)) for g in GROUPS)
+        raise ValueError(f"{prefix}.bias.{unknown[0]} is not a group of sensor columns ({', '.join(GROUPS)})")
+    entries = tuple(_bias_entry(g, bias.get(g), prefix) for g in GROUPS)
     lat = sec.get("latency_steps", DEFAULTS["latency_steps"])
     if lat is None:
         lat = DEFAULTS["latency_steps"]
     if not isinstance(lat, (list, tuple)) or len(lat) != 2 or not all(_number(x) for x in lat) or not 0 <= lat[0] <= lat[1] <= MAX_LATENCY_STEPS:
-        raise ValueError(f"sensors.latency_steps must be [lo, hi] in policy steps with 0 <= lo <= hi <= {MAX_LATENCY_STEPS}, got {lat!r}")
-    if actor_heights_of(cfg["terrain"]):
-        raise ValueError("sensors.enabled is not available with terrain.actor_heights: true: those rows, and a distillation's student row with them, "
-                         "are written by bg_obs_assemble, which knows nothing of the sensor model")
+        raise ValueError(f"{prefix}.latency_steps must be [lo, hi] in policy steps with 0 <= lo <= hi <= {MAX_LATENCY_STEPS}, got {lat!r}")
     return SensorsCfg(entries, (float(lat[0]), float(lat[1])))
+
+
+def sensors_as_section(sc):
+    """A SensorsCfg as plain dicts, lists and floats: {bias: {group: entry or None}, latency_steps: [lo, hi]} (a checkpoint's entry, a config's
+    `sensors.bias` and `sensors.latency_steps`)."""
+    return {"bias": {g: (None if e is None else {"range": [float(e["range"][0]), float(e["range"][1])], "operation": e["operation"],
+                                                  "distribution": e["distribution"]}) for g, e in zip(GROUPS, sc.bias)},
+            "latency_steps": [float(sc.latency_steps[0]), float(sc.latency_steps[1])]}

@@ -206,7 +206,13 @@ typedef struct {
      *   lam     = sensor_latency_lo + (sensor_latency_hi - sensor_latency_lo) * u  on entry 0 of stream RS_SENSOR + 8
      * (RS_SENSOR_RESET at bg_env_reset; csrc/bg_rng.h).  Fields "sensor_bias" [N][30] and "sensor_latency" [N] read them back (bg_env_get_field only).
      * The env-step kernels, the privileged row and every other stream are untouched.  sensor_bias_*: mode 0 (none), 1 (gaussian additive: a = mean,
-     * b = std >= 0) or 3 (uniform additive: a = low, b = high), finite; 0 <= sensor_latency_lo <= sensor_latency_hi <= BG_MAX_SENSOR_LATENCY. */
+     * b = std >= 0) or 3 (uniform additive: a = low, b = high), finite; 0 <= sensor_latency_lo <= sensor_latency_hi <= BG_MAX_SENSOR_LATENCY.
+     * 2 = the student's row only (T1.yaml distillation.student_sensors; with actor_heights and student_frame_stack = Hs >= 1 only, else bg_env_create
+     * fails): the actor's row [47 H + P] and the privileged row stay bit for bit what they are at 0, and the student's row [N][47 Hs], the third
+     * output of bg_obs_assemble, follows the rule above at Hs frames, with the draws above on the same streams: it has the bits of the actor's row of
+     * an env with sensor_model = 1, frame_stack = Hs and the same seed.  The ring has Hs + ceil(sensor_latency_hi) planes, bg_obs_assemble stays
+     * the one and last launch of every env step and reset-all and does not write the ring, bg_obs_sensor never runs (bg_env_sensor_launches stays 0),
+     * and the two fields are readable as with 1.  The sensor_bias_* and sensor_latency_* fields and their ranges are the same; no field is added. */
     int32_t sensor_model;
     bg_rand sensor_bias_gravity, sensor_bias_ang_vel, sensor_bias_dof_pos, sensor_bias_dof_vel; /* sensors.bias.*, in physical units */
     float sensor_latency_lo, sensor_latency_hi;                                                 /* sensors.latency_steps, in env steps */
@@ -479,6 +485,13 @@ int bg_distill_act_gru(int32_t N, const float* teacher_obs, int32_t teacher_stri
                        int32_t scan_points, const bg_gru_desc* gru, int32_t n_student, const bg_mlp_layer_desc* student, const float* student_logstd,
                        uint64_t seed, uint64_t counter, float beta, int32_t teacher_noise, const uint8_t* reset, const float* h_in, float* h_out,
                        float* student_mu, float* actions, float* teacher_mu, void* stream);
+/* bg_distill_act_gru with the cell's 47 inputs from rows of the student's own: columns [0, 47) of student_obs (rows student_stride >= 47 floats apart)
+ * in place of the teacher's rows (a student row that is no prefix of the teacher's: bg_env_cfg.sensor_model = 2).  The same kernel; the teacher's half
+ * is untouched.  With student_obs on rows that equal the teacher's first 47 columns, every output and the state equal bg_distill_act_gru's, bit for bit. */
+int bg_distill_act_gru_own(int32_t N, const float* teacher_obs, int32_t teacher_stride, const float* student_obs, int32_t student_stride, int32_t n_teacher,
+                           const bg_mlp_layer_desc* teacher, int32_t scan_points, const bg_gru_desc* gru, int32_t n_student, const bg_mlp_layer_desc* student,
+                           const float* student_logstd, uint64_t seed, uint64_t counter, float beta, int32_t teacher_noise, const uint8_t* reset,
+                           const float* h_in, float* h_out, float* student_mu, float* actions, float* teacher_mu, void* stream);
 /* The recurrence of the recurrent student's update over T steps as ONE launch each way (csrc/bg_gru.hip); H = 128 or 256, any N >= 1, T >= 1.  Envs are
  * independent: a workgroup owns 16 rows and walks the steps itself, its state tile in LDS; W_hh [3H][H] (16-byte aligned) streams from L2.
  * Forward: gi [T][N][3H] the x-side pre-activations (b_ih included), h0 [N][H] the state entering step 0 (NULL: zero), reset [T][N] (uint8, NULL: none):

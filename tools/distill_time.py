@@ -29,6 +29,12 @@
       (11) bg_gru_sequence_forward / _backward at T = 24 on num_envs rows against 24 launches of bg_mlp_layer_forward(num_envs, H, 3H), the per-step
            form of the h-side GEMM they replace, and against their own fp32-MFMA time from the flop count (157.3 TFLOPS);
       (12) the loop of (3) with a memoryless student, with Hs, and with the cell of H, one Distiller after the other, `pairs` times each.
+  With student_sensors=full (or =empty: a section with nothing configured) among the arguments (distillation.student_sensors; out "-" =
+  profiles/student_sensors_time.txt) the sections are the student's sensor model's instead, all at H = 1 / P = 187:
+      (13) the env step (bg_env_step_to, whose last launch is bg_obs_assemble) with the key (full bias and latency_steps [0, 1.5] for "full") against
+           the same env without it, at Hs (5 unless given) and at Hs = H = 1 (without the key: no student's row at all), the way of (4), and the bytes
+           bg_obs_assemble moves in each; `only` = "assemble" stops here (the run under a kernel trace, which gives the launch's own time);
+      (14) the loop of (3) without the key and with it, at Hs = H and at Hs, one Distiller after the other, `pairs` times each.
   The outputs of (1) are compared bit for bit before they are timed.  The committed profile carries two more sections that this tool does not
   write: the figures tests/test_gpu_distill.py prints under -s, and bench.py of this tree against a checkout of its parent commit."""
 import os
@@ -163,6 +169,52 @@ def assemble(pairs=3, N=4096, Hs=5, P=187):
         us = {m: _best(fns[m], 200) for m in _orders(q, ("with", "without"))}
         say(f"env step (bg_env_step_to, all launches), {N} envs: with the student's row {us['with']:.2f} us, without {us['without']:.2f} us, "
             f"difference {us['with'] - us['without']:+.2f} us, with / without = {us['with'] / us['without']:.4f}")
+
+
+FULL_SENSORS = {"bias": {"gravity": {"range": [0.0, 0.05], "operation": "additive", "distribution": "gaussian"},
+                         "ang_vel": {"range": [-0.2, 0.2], "operation": "additive", "distribution": "uniform"},
+                         "dof_pos": {"range": [0.01, 0.03], "operation": "additive", "distribution": "gaussian"},
+                         "dof_vel": {"range": [-0.5, 0.3], "operation": "additive", "distribution": "uniform"}}, "latency_steps": [0.0, 1.5]}
+
+
+def assemble_sensors(pairs=3, N=4096, Hs=5, P=187, sensors=None):
+    """(13): the env step with distillation.student_sensors (as the Distiller hands it over: env.student_frame_stack and env.student_sensors)."""
+    from booster_gym_amd.envs import T1
+    from booster_gym_amd.utils.config import load_cfg
+
+    ov = {"env.num_envs": N, "terrain.measure_heights": True, "terrain.actor_heights": True, "env.num_observations": 47 + P, "env.num_privileged_obs": 14 + P}
+    g = torch.Generator(device="cpu").manual_seed(0)
+    a = ((torch.rand(N, 12, generator=g) * 2 - 1) * 0.3).to(DEV)
+    obs, priv = torch.empty(N, 47 + P, device=DEV), torch.empty(N, 14 + P, device=DEV)
+    rew, done, tout = torch.empty(N, device=DEV), torch.empty(N, dtype=torch.bool, device=DEV), torch.empty(N, dtype=torch.bool, device=DEV)
+    lat_hi = float(sensors.get("latency_steps", [0.0, 0.0])[1])
+    for hs in (Hs, 1):
+        sob = torch.empty(N, 47 * hs, device=DEV)
+        envs = {"with": T1(load_cfg("T1", dict(ov, **{"env.student_frame_stack": hs, "env.student_sensors": sensors}))),
+                "without": T1(load_cfg("T1", dict(ov, **({"env.student_frame_stack": hs} if hs > 1 else {}))))}
+        for e in envs.values():
+            e.reset()
+        fns = {"with": lambda k: envs["with"].step_to(a, obs, priv, rew, done, tout, student_obs=sob),
+               "without": (lambda k: envs["without"].step_to(a, obs, priv, rew, done, tout, student_obs=sob)) if hs > 1 else
+                          (lambda k: envs["without"].step_to(a, obs, priv, rew, done, tout))}
+        for f in fns.values():
+            for k in range(20):
+                f(k)
+        torch.cuda.synchronize()
+        # writes: the actor's row [47 + P], the critic's P clean scan columns, the student's row [47 hs] (bias and latency only on a reset);
+        # reads: the ring for the teacher's frame and for the student's frames, with the key a second plane for the 30 sensor columns of every frame
+        # where the latency has a fraction, the env's 30 biases once and its reset flag, age and latency
+        w0 = N * (47 + P + P) * 4 + (N * 47 * hs * 4 if hs > 1 else 0)
+        r0 = N * 47 * 4 + (N * 47 * hs * 4 if hs > 1 else 0)
+        w1, r1 = N * (47 + P + P) * 4 + N * 47 * hs * 4, N * 47 * 4 + N * 47 * hs * 4 + (N * 30 * hs * 4 if lat_hi > 0 else 0) + N * 30 * 4 + N * 9
+        say(f"bg_obs_assemble, {N} envs, H = 1, P = {P}, Hs = {hs}: without the key {'(no student row) ' if hs == 1 else ''}writes {w0 / 1e6:.3f} MB + ring reads "
+            f"{r0 / 1e6:.3f} MB = {(w0 + r0) / 1e6:.3f} MB; with it writes {w1 / 1e6:.3f} MB + reads {r1 / 1e6:.3f} MB = {(w1 + r1) / 1e6:.3f} MB "
+            f"(= {(w1 + r1) / 6.29e12 * 1e6:.3f} us at the float4-copy rate of 6.29 TB/s)")
+        for q in range(pairs):
+            us = {m: _best(fns[m], 200) for m in _orders(q, ("with", "without"))}
+            say(f"env step (bg_env_step_to, all launches), {N} envs, Hs = {hs}: with student_sensors {us['with']:.2f} us, without {us['without']:.2f} us, "
+                f"difference {us['with'] - us['without']:+.2f} us, with / without = {us['with'] / us['without']:.4f}")
+        del envs, fns
 
 
 def act_hist(pairs=3, N=4096, Hs=5, P=187):
@@ -353,7 +405,7 @@ def sequence(pairs=3, N=4096, T=24):
                 f"{2.0 * B * H * 3 * H / 1e9:.1f} GFLOP {floor:.1f} us (forward {us['fwd'] / floor:.1f}x, backward {us['bwd'] / floor:.1f}x)")
 
 
-def loop(K=20, W=5, pairs=3, N=4096, Hs=None, coef=0.0, beta=0.0, memory=0):
+def loop(K=20, W=5, pairs=3, N=4096, Hs=None, coef=0.0, beta=0.0, memory=0, student_sensors=None):
     from booster_gym_amd.utils.config import load_cfg
     from booster_gym_amd.utils.distill import Distiller
     from booster_gym_amd.utils.model import ActorCritic
@@ -375,6 +427,8 @@ def loop(K=20, W=5, pairs=3, N=4096, Hs=None, coef=0.0, beta=0.0, memory=0):
         cfg["distillation"]["teacher_action_prob"] = beta
     if memory:
         cfg["distillation"]["student_memory"] = memory
+    if student_sensors is not None:
+        cfg["distillation"]["student_sensors"] = student_sensors
     d = Distiller(cfg=cfg)
     d.begin(Recorder(cfg, root=tmp, rank=0))
     it = 0
@@ -393,6 +447,7 @@ def loop(K=20, W=5, pairs=3, N=4096, Hs=None, coef=0.0, beta=0.0, memory=0):
         ms = run(K)
         keys = f"symmetric_coef {coef:g}, teacher_action_prob {beta:g}, " if coef or beta or KEYS else ""
         keys += f"student_memory {memory}, " if memory or MEMORY else ""
+        keys += f"student_sensors {'absent' if student_sensors is None else SENSORS[0]}, " if SENSORS else ""
         say(f"distillation loop, {N} envs, H = 1, P = 187, {keys}student_frame_stack {Hs or 'absent'} ({d.student_obs} student columns padded to {d._student_in.shape[1]}), horizon {T}, {E} epochs, student 256-128-128 (plan {d._sup.mlp.plan.fwd} / {d._sup.mlp.plan.bwd}, weight "
             f"gradients {d._sup.wgrad_terms or 'fp32'}): {ms:.3f} ms per iteration = {1e3 / ms:.2f} iterations/s = {N * T / ms / 1e3:.3f} M env-steps/s; last loss "
             f"{d.last_loss:.6f}")
@@ -408,18 +463,29 @@ def loop(K=20, W=5, pairs=3, N=4096, Hs=None, coef=0.0, beta=0.0, memory=0):
 
 KEYS = {}  # symmetric_coef / teacher_action_prob given on the command line: sections (7) to (9)
 MEMORY = []  # student_memory given on the command line: sections (10) to (12)
+SENSORS = []  # student_sensors given on the command line ("full" or "empty"): sections (13) and (14)
 
 
 if __name__ == "__main__":
     KEYS.update({k: float(v) for k, v in (x.split("=", 1) for x in sys.argv[1:] if "=" in x) if k in ("symmetric_coef", "teacher_action_prob")})
     MEMORY.extend(int(v) for k, v in (x.split("=", 1) for x in sys.argv[1:] if "=" in x) if k == "student_memory")
+    SENSORS.extend(v for k, v in (x.split("=", 1) for x in sys.argv[1:] if "=" in x) if k == "student_sensors")
     a = [x for x in sys.argv[1:] if "=" not in x]
     K, W, pairs, N = (int(a[i]) if len(a) > i else v for i, v in enumerate((20, 5, 3, 4096)))
     Hs, only = (int(a[5]) if len(a) > 5 else 0), (a[6] if len(a) > 6 else "")
-    name = "distill_memory_time.txt" if MEMORY else "distill_symmetry_dagger_time.txt" if KEYS else "distill_history_time.txt" if Hs else "distill_time.txt"
+    name = "student_sensors_time.txt" if SENSORS else "distill_memory_time.txt" if MEMORY else "distill_symmetry_dagger_time.txt" if KEYS else "distill_history_time.txt" if Hs else "distill_time.txt"
     out = a[4] if len(a) > 4 and a[4] != "-" else os.path.join(ROOT, "profiles", name)
     say(f"tools/distill_time.py {' '.join(sys.argv[1:]) or f'{K} {W} {pairs} {N}'} on {torch.cuda.get_device_name(0)}")
-    if MEMORY:
+    if SENSORS:
+        if SENSORS[0] not in ("full", "empty"):
+            raise SystemExit("student_sensors=full or student_sensors=empty")
+        section = FULL_SENSORS if SENSORS[0] == "full" else {}
+        if only != "loop":
+            assemble_sensors(pairs, N, Hs or 5, sensors=section)
+        for q in range(pairs if only != "assemble" else 0):  # (a Distiller each: the env and the buffers are per configuration)
+            for hs, sec in _orders(q, ((None, None), (None, section), (Hs or 5, None), (Hs or 5, section))):
+                loop(K, W, 1, N, hs, student_sensors=sec)
+    elif MEMORY:
         if only != "loop":
             act_gru(pairs, N, Hs or 5)
             sequence(pairs, N)
