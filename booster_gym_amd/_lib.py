@@ -184,11 +184,40 @@ def eval_track_plane(c, k):
     return EVAL_TRACK + 4 * c + k
 
 
+# planes of the gait record [GAIT_PLANES][N] (bg_env_gait_begin / bg_env_gait_step): ten scalars, eight per-foot pairs, the kernel's own carries
+GAIT_PLANES = 60  # BG_GAIT_PLANES
+(GAIT_STATE, GAIT_LEN, GAIT_MOV, GAIT_D1, GAIT_D2, GAIT_TAU2, GAIT_TILT, GAIT_WOBBLE, GAIT_DS, GAIT_FL, GAIT_FOOT) = range(11)
+(GAIT_STANCE, GAIT_TD, GAIT_IMP, GAIT_PEAK, GAIT_SLIP, GAIT_CLR, GAIT_SWT, GAIT_SWC) = range(8)  # k of gait_foot_plane(k, f)
+GAIT_FOOT_NAMES = ("STANCE", "TD", "IMP", "PEAK", "SLIP", "CLR", "SWT", "SWC")
+GAIT_A1, GAIT_A2, GAIT_CPREV, GAIT_PPREV, GAIT_SWMAX, GAIT_SWN = 26, 38, 50, 52, 56, 58  # carries: A1[12], A2[12], CPREV[2], PPREV[2][xy], SWMAX[2], SWN[2]
+GAIT_FEET = ("left", "right")
+
+
+def gait_foot_plane(k, f):
+    """Plane of the per-foot quantity k (GAIT_STANCE .. GAIT_SWC) of foot f (0 left, 1 right)."""
+    return GAIT_FOOT + 2 * k + f
+
+
+def gait_plane_names():
+    """The GAIT_PLANES names, in plane order."""
+    names = ["STATE", "LEN", "MOV", "D1", "D2", "TAU2", "TILT", "WOBBLE", "DS", "FL"]
+    names += [f"{q}_{f}" for q in GAIT_FOOT_NAMES for f in range(2)]
+    names += [f"A1_{j}" for j in range(NUM_DOFS)] + [f"A2_{j}" for j in range(NUM_DOFS)] + ["CPREV_0", "CPREV_1"]
+    names += ["PPREV_0_x", "PPREV_0_y", "PPREV_1_x", "PPREV_1_y", "SWMAX_0", "SWMAX_1", "SWN_0", "SWN_1"]
+    return names
+
+
+def eval_plane_names():
+    """The EVAL_PLANES names, in plane order."""
+    names = ["STATE", "LEN", "REW", "LEVEL", "TYPE", "X0", "Y0", "X1", "Y1", "CLASS", "POWER"]
+    return names + [f"{q}_{c}" for c in EVAL_CLASS_NAMES for q in ("CNT", "SQ_vx", "SQ_vy", "SQ_yaw")]
+
+
 SYMBOLS = [
     "bg_model_create", "bg_model_get", "bg_model_destroy", "bg_model_load_urdf", "bg_model_body_name", "bg_model_dof_name", "bg_model_find_body", "bg_env_create", "bg_env_destroy", "bg_env_set_heightfield",
     "bg_env_set_params", "bg_env_bind_outputs", "bg_env_reset", "bg_env_step", "bg_env_step_to", "bg_env_bind_student_obs", "bg_env_step_to_student", "bg_env_get_state",
     "bg_env_set_state", "bg_env_get_field", "bg_env_set_field", "bg_env_field_info", "bg_env_get_curriculum", "bg_env_set_curriculum", "bg_env_step_count", "bg_env_set_step_count", "bg_env_sensor_launches",
-    "bg_env_get_terrain_level_sum", "bg_env_set_terrain_level_sum", "bg_env_eval_begin", "bg_env_eval_step",
+    "bg_env_get_terrain_level_sum", "bg_env_set_terrain_level_sum", "bg_env_eval_begin", "bg_env_eval_step", "bg_env_gait_begin", "bg_env_gait_step",
     "bg_env_forward_dynamics", "bg_env_forward_dynamics_packed", "bg_sim_bind_state", "bg_sim_set_actuation", "bg_sim_apply_body_wrench_local", "bg_sim_simulate",
     "bg_sim_refresh_body_state", "bg_sim_write_root_state", "bg_sim_write_dof_state", "bg_gae", "bg_ppo_loss", "bg_gaussian_logp", "bg_actor_pack", "bg_actor_sample", "bg_actor_sample_mlp", "bg_actor_sample_mlp_scan", "bg_distill_act", "bg_distill_act_hist", "bg_distill_act_mix", "bg_actor_sample_est", "bg_adam_step", "bg_adapt_lr", "bg_optimizer_step", "bg_elu_backward_colsum", "bg_mlp_layer_forward", "bg_mlp_chain_forward", "bg_critic_values_gae", "bg_mlp_chain_forward_group", "bg_mlp_chain_forward_split", "bg_mlp_chain_backward_split", "bg_mlp_split_weights_pm", "bg_mlp_layer_backward", "bg_mlp_split_weights", "bg_mlp_layer_forward_split", "bg_mlp_layer_backward_split", "bg_mlp_weight_grad", "bg_mlp_weight_grad_group", "bg_mlp_weight_grad_group_partial", "bg_update_tail", "bg_update_tail_sums", "bg_mlp_weight_grad_group_split", "bg_mlp_weight_grad_group_split_partial",
     "bg_critic_head_forward", "bg_actor_head", "bg_critic_head_backward",
@@ -248,6 +277,8 @@ def load():
         "bg_env_set_terrain_level_sum": (i32, [vp, vp, vp]),
         "bg_env_eval_begin": (i32, [vp, vp, vp]),
         "bg_env_eval_step": (i32, [vp, vp, vp, vp, i32, vp, vp]),
+        "bg_env_gait_begin": (i32, [vp, vp, vp]),
+        "bg_env_gait_step": (i32, [vp, vp, i32, vp, vp]),
         "bg_env_step_count": (i64, [vp]),
         "bg_env_set_step_count": (i32, [vp, i64]),
         "bg_env_sensor_launches": (i64, [vp]),

@@ -313,6 +313,125 @@ __global__ __launch_bounds__(EVAL_BLOCK) void bg_eval_step(EnvDev E, const float
 #undef REC
 }
 
+// ------------------------------------------------------------------ gait record (bg_env_gait_begin / bg_env_gait_step; evaluate.py --gait)
+// A second, opt-in per-robot record of every env's FIRST episode, [BG_GAIT_PLANES][n], plane-major, with bg_eval_step's form: one thread per env (a
+// wave loads and stores 64 consecutive floats of a plane or of a field), one launch per step, no atomics, no LDS, nothing across envs, reading the
+// fields the env step has STORED.  It is independent of the first record (its own STATE and LEN: either step may run first), and it keeps its own
+// carries: the env overwrites last_actions, last_feet_pos and its contact state inside the step, so after a step they equal the current values
+// and the previous ones are nowhere.  The whole record and the 45 fields are loaded ahead of the arithmetic (about 105
+// independent loads per thread); only the terrain look-up under each foot waits for loads of this thread (the foot's x, y, then four int16).
+//
+// The rule, per env e (the README's evaluation paragraph holds the other copy).  Foot f = 0 left, 1 right.  From the stored fields: a[12] actions,
+// tau[12] torques, g projected_gravity, w base_ang_vel, cmd[3] commands, c_f = feet_contact[f] > 0.5, Fz_f = feet_contact_forces[3 f + 2],
+// p_f = feet_pos[3 f ..], clr_f = p_f.z - terrain_height(p_f.x, p_f.y) (bg_priv_extras' clearance; the ground is at 0 on a plane).
+//   begin (after bg_env_reset): every plane 0.
+//   step:
+//    1. STATE != 0: return without writing any plane of e -- a finished record is frozen bit for bit.
+//    2. LEN += 1; len = the new value.
+//    3. done[e]: STATE = 1 and return -- the fields already belong to the next episode, this step gives no sample.
+//    4. TAU2 += sum tau_j^2; TILT += g.x^2 + g.y^2; WOBBLE += w.x^2 + w.y^2; PEAK_f = max(PEAK_f, Fz_f).
+//    5. len >= 2: D1 += sum_j (a_j - A1_j)^2.
+//    6. len >= 3: D2 += sum_j (a_j - 2 A1_j + A2_j)^2.
+//    7. !c_f: SWMAX_f = (SWN_f == 0) ? clr_f : max(SWMAX_f, clr_f); SWN_f += 1.
+//    8. moving = len > settle_steps && max_a |cmd_a| > 1e-6 (command classes 1 and 2 of the first record).  If moving:
+//         MOV += 1; STANCE_f += c_f; DS += c_0 && c_1; FL += !c_0 && !c_1;
+//         td_f = len >= 2 && c_f && !CPREV_f: TD_f += 1, IMP_f += Fz_f, and if SWN_f > 0: CLR_f += SWMAX_f, SWT_f += SWN_f, SWC_f += 1;
+//         len >= 2 && c_f && CPREV_f: d = |p_f.xy - PPREV_f|; d <= 0.5: SLIP_f += d (a stance foot that moved more than half a metre in one step
+//         crossed the terrain's teleport wrap: not slip).
+//    9. c_f: SWN_f = 0, SWMAX_f = 0.
+//   10. A2 = A1, A1 = a, CPREV_f = c_f, PPREV_f = p_f.xy.
+enum { GT_STATE = 0, GT_LEN = 1, GT_MOV = 2, GT_D1 = 3, GT_D2 = 4, GT_TAU2 = 5, GT_TILT = 6, GT_WOBBLE = 7, GT_DS = 8, GT_FL = 9,
+       GT_FOOT = 10,  // GT_FOOT + 2 k + f, k one of GF_*
+       GT_A1 = 26, GT_A2 = 38, GT_CPREV = 50, GT_PPREV = 52 /* + 2 f + {x, y} */, GT_SWMAX = 56, GT_SWN = 58 };
+enum { GF_STANCE = 0, GF_TD = 1, GF_IMP = 2, GF_PEAK = 3, GF_SLIP = 4, GF_CLR = 5, GF_SWT = 6, GF_SWC = 7, GF_COUNT = 8 };
+static_assert(GT_FOOT + 2 * GF_COUNT == GT_A1 && GT_A2 == GT_A1 + BG_NUM_DOFS && GT_CPREV == GT_A2 + BG_NUM_DOFS && GT_SWN + 2 == BG_GAIT_PLANES,
+              "ten scalar planes, sixteen per-foot planes, thirty-four carries");
+__global__ __launch_bounds__(EVAL_BLOCK) void bg_gait_begin(int n, float* __restrict__ rec) {
+    const int e = blockIdx.x * EVAL_BLOCK + threadIdx.x;
+    if (e >= n) return;
+    for (int p = 0; p < BG_GAIT_PLANES; p++) rec[(size_t)p * n + e] = 0.f;
+}
+template <bool H16>
+__global__ __launch_bounds__(EVAL_BLOCK) void bg_gait_step(EnvDev E, const uint8_t* __restrict__ done, int settle_steps, float* __restrict__ rec) {
+    const int e = blockIdx.x * EVAL_BLOCK + threadIdx.x, n = E.n;
+    if (e >= n) return;
+#define REC(p) rec[(size_t)(p) * n + e]
+#define SFLD(off) field_ref<H16>(E.f, E.h, (off), n, e)
+    // every load first: the record, then the fields
+    float r[BG_GAIT_PLANES];
+#pragma unroll
+    for (int p = 0; p < BG_GAIT_PLANES; p++) r[p] = REC(p);
+    const bool dn = done[e] != 0;
+    float a[BG_NUM_DOFS], tau[BG_NUM_DOFS], pf[2][3], fz[2], clr[2];
+    bool c[2];
+#pragma unroll
+    for (int j = 0; j < BG_NUM_DOFS; j++) { a[j] = SFLD(F_ACT + j); tau[j] = SFLD(F_TORQUES + j); }
+    const float gx = SFLD(F_PROJ_G + 0), gy = SFLD(F_PROJ_G + 1), wx = SFLD(F_BASE_ANG + 0), wy = SFLD(F_BASE_ANG + 1);
+    const float cmd[3] = {SFLD(F_CMD + 0), SFLD(F_CMD + 1), SFLD(F_CMD + 2)};
+#pragma unroll
+    for (int f = 0; f < 2; f++) {
+        c[f] = SFLD(F_FEET_CONTACT + f) > 0.5f;
+        fz[f] = SFLD(F_CONTACT + 3 * f + 2);
+#pragma unroll
+        for (int k = 0; k < 3; k++) pf[f][k] = SFLD(F_FEET_POS + 3 * f + k);
+    }
+#pragma unroll
+    for (int f = 0; f < 2; f++) clr[f] = pf[f][2] - terrain_height(E.terrain, pf[f][0], pf[f][1]);
+
+    if (r[GT_STATE] != 0.f) return;                                              // 1
+    const float len = r[GT_LEN] + 1.f;                                           // 2
+    if (dn) { REC(GT_LEN) = len; REC(GT_STATE) = 1.f; return; }                  // 3
+    r[GT_LEN] = len;
+    float t2 = 0.f, d1 = 0.f, d2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < BG_NUM_DOFS; j++) {
+        const float u = a[j] - r[GT_A1 + j], v = a[j] - 2.f * r[GT_A1 + j] + r[GT_A2 + j];
+        t2 += tau[j] * tau[j]; d1 += u * u; d2 += v * v;
+    }
+    r[GT_TAU2] += t2;                                                            // 4
+    r[GT_TILT] += gx * gx + gy * gy;
+    r[GT_WOBBLE] += wx * wx + wy * wy;
+    if (len >= 2.f) r[GT_D1] += d1;                                              // 5
+    if (len >= 3.f) r[GT_D2] += d2;                                              // 6
+    const bool moving = len > (float)settle_steps && fmaxf(fmaxf(fabsf(cmd[0]), fabsf(cmd[1])), fabsf(cmd[2])) > 1e-6f;
+    if (moving) {                                                                // 8 (the part that is not per foot)
+        r[GT_MOV] += 1.f;
+        if (c[0] && c[1]) r[GT_DS] += 1.f;
+        if (!c[0] && !c[1]) r[GT_FL] += 1.f;
+    }
+#pragma unroll
+    for (int f = 0; f < 2; f++) {
+#define FOOT(k) r[GT_FOOT + 2 * (k) + f]
+        float swmax = r[GT_SWMAX + f], swn = r[GT_SWN + f];
+        const bool cprev = r[GT_CPREV + f] != 0.f;
+        FOOT(GF_PEAK) = fmaxf(FOOT(GF_PEAK), fz[f]);                             // 4
+        if (!c[f]) { swmax = swn == 0.f ? clr[f] : fmaxf(swmax, clr[f]); swn += 1.f; }  // 7
+        if (moving) {                                                            // 8
+            if (c[f]) FOOT(GF_STANCE) += 1.f;
+            if (len >= 2.f && c[f] && !cprev) {
+                FOOT(GF_TD) += 1.f; FOOT(GF_IMP) += fz[f];
+                if (swn > 0.f) { FOOT(GF_CLR) += swmax; FOOT(GF_SWT) += swn; FOOT(GF_SWC) += 1.f; }
+            }
+            if (len >= 2.f && c[f] && cprev) {
+                const float dx = pf[f][0] - r[GT_PPREV + 2 * f + 0], dy = pf[f][1] - r[GT_PPREV + 2 * f + 1];
+                const float d = sqrtf(dx * dx + dy * dy);
+                if (d <= 0.5f) FOOT(GF_SLIP) += d;
+            }
+        }
+        if (c[f]) { swn = 0.f; swmax = 0.f; }                                    // 9
+        r[GT_SWMAX + f] = swmax; r[GT_SWN + f] = swn;
+        r[GT_CPREV + f] = c[f] ? 1.f : 0.f;                                      // 10
+        r[GT_PPREV + 2 * f + 0] = pf[f][0]; r[GT_PPREV + 2 * f + 1] = pf[f][1];
+#undef FOOT
+    }
+#pragma unroll
+    for (int j = 0; j < BG_NUM_DOFS; j++) { r[GT_A2 + j] = r[GT_A1 + j]; r[GT_A1 + j] = a[j]; }
+#pragma unroll
+    for (int p = GT_LEN; p < BG_GAIT_PLANES; p++) REC(p) = r[p];  // (STATE stays 0)
+#undef SFLD
+#undef REC
+}
+
 // ------------------------------------------------------------------ observation history of the actor's input (cfg.frame_stack = H > 1)
 // humanoid-gym's frame stack: the row [47 H] of an env is its last H single observations, oldest first, newest last.  The env keeps them as a
 // ring of H planes [n][47]; the env-step kernels (and resample_apply_kernel's patch) of a launch sequence write their 47-wide rows into plane
@@ -1436,6 +1555,27 @@ extern "C" int bg_env_eval_step(bg_env* e, const float* rew, const uint8_t* done
     const dim3 grid((e->n + EVAL_BLOCK - 1) / EVAL_BLOCK), block(EVAL_BLOCK);
     if (e->h) hipLaunchKernelGGL(bg_eval_step<true>, grid, block, 0, (hipStream_t)stream, env_dev(e), rew, done, time_outs, (int)settle_steps, record);
     else hipLaunchKernelGGL(bg_eval_step<false>, grid, block, 0, (hipStream_t)stream, env_dev(e), rew, done, time_outs, (int)settle_steps, record);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// gait record: the same conventions, a buffer and a STATE / LEN of its own
+extern "C" int bg_env_gait_begin(bg_env* e, float* record, void* stream) {
+    if (!e) return fail(-1, "bg_env_gait_begin: null env");
+    if (!record) return fail(-1, "bg_env_gait_begin: null record");
+    const dim3 grid((e->n + EVAL_BLOCK - 1) / EVAL_BLOCK), block(EVAL_BLOCK);
+    hipLaunchKernelGGL(bg_gait_begin, grid, block, 0, (hipStream_t)stream, e->n, record);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+extern "C" int bg_env_gait_step(bg_env* e, const uint8_t* done, int32_t settle_steps, float* record, void* stream) {
+    if (!e) return fail(-1, "bg_env_gait_step: null env");
+    if (!done) return fail(-1, "bg_env_gait_step: null done");
+    if (settle_steps < 0) return fail(-1, "bg_env_gait_step: settle_steps = " + std::to_string(settle_steps) + " is negative");
+    if (!record) return fail(-1, "bg_env_gait_step: null record");
+    const dim3 grid((e->n + EVAL_BLOCK - 1) / EVAL_BLOCK), block(EVAL_BLOCK);
+    if (e->h) hipLaunchKernelGGL(bg_gait_step<true>, grid, block, 0, (hipStream_t)stream, env_dev(e), done, (int)settle_steps, record);
+    else hipLaunchKernelGGL(bg_gait_step<false>, grid, block, 0, (hipStream_t)stream, env_dev(e), done, (int)settle_steps, record);
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -659,6 +659,25 @@ class T1(BaseTask):
         _lib.check(self._lib.bg_env_eval_step(self._env, _lib.ptr(self.rew_buf), _lib.ptr(self.reset_buf), _lib.ptr(self.time_out_buf), int(settle_steps),
                                               _lib.ptr(record), _lib.current_stream_ptr()), "bg_env_eval_step")
 
+    # ------------------------------------------------------------------ gait record (bg_env_gait_begin / bg_env_gait_step; evaluate.py --gait)
+    def gait_begin(self, record=None):
+        """Start the per-robot gait record of every env's first episode, after reset(): float [_lib.GAIT_PLANES][N] (the planes are named in _lib),
+        the caller's tensor or a new one.  Independent of eval_begin's record.  One launch, no host sync."""
+        shape = (_lib.GAIT_PLANES, self.num_envs)
+        if record is None:
+            record = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif tuple(record.shape) != shape or record.dtype != torch.float32 or not (record.is_cuda and record.is_contiguous()):
+            raise ValueError(f"gait_begin needs a contiguous float32 CUDA record of shape {shape}, got {tuple(record.shape)} {record.dtype}")
+        _lib.check(self._lib.bg_env_gait_begin(self._env, _lib.ptr(record), _lib.current_stream_ptr()), "bg_env_gait_begin")
+        return record
+
+    def gait_step(self, record, settle_steps):
+        """Add the last step() to the gait record, from its reset_buf and the fields it stored.  One launch, no host sync."""
+        if tuple(record.shape) != (_lib.GAIT_PLANES, self.num_envs) or record.dtype != torch.float32 or not (record.is_cuda and record.is_contiguous()):
+            raise ValueError(f"gait_step needs the record of gait_begin, float32 {(_lib.GAIT_PLANES, self.num_envs)}")
+        _lib.check(self._lib.bg_env_gait_step(self._env, _lib.ptr(self.reset_buf), int(settle_steps), _lib.ptr(record), _lib.current_stream_ptr()),
+                   "bg_env_gait_step")
+
     def _as_actions(self, actions):
         if actions.shape != (self.num_envs, self.num_actions):
             raise ValueError(f"actions must have shape {(self.num_envs, self.num_actions)}, got {tuple(actions.shape)}")

@@ -312,6 +312,29 @@ int64_t bg_env_sensor_launches(const bg_env* env);
 int bg_env_eval_begin(bg_env* env, float* record, void* stream);
 int bg_env_eval_step(bg_env* env, const float* rew, const uint8_t* done, const uint8_t* time_outs, int32_t settle_steps, float* record,
                      void* stream);
+/* ---- gait record: a second, opt-in per-robot record of every env's FIRST episode (evaluate.py --gait): action smoothness, effort, body wobble,
+ * duty factor, touchdowns, slip, swing clearance.  The conventions are the evaluation record's: the caller's device float [BG_GAIT_PLANES][N],
+ * plane-major, one launch per call, no bg_env_cfg field, not part of bg_env_step's launch sequence.  It is independent of the evaluation record (its
+ * own STATE and LEN planes: either step may be called first).  Planes (foot f = 0 left, 1 right):
+ *   0 STATE (0 running, 1 ended)  1 LEN  2 MOV  3 D1  4 D2  5 TAU2  6 TILT  7 WOBBLE  8 DS  9 FL
+ *   10 + 2 k + f, k = 0 .. 7: STANCE, TD, IMP, PEAK, SLIP, CLR, SWT, SWC of foot f
+ *   carries: 26 .. 37 A1[12]  38 .. 49 A2[12]  50, 51 CPREV[f]  52 + 2 f + {0, 1} PPREV[f].xy  56, 57 SWMAX[f]  58, 59 SWN[f]
+ * The rule (stated once more at the kernel, bg_gait_step in csrc/bg_sim.hip, and for users in the README's evaluation paragraph), from the fields the
+ * env step has stored: a actions, tau torques, g projected_gravity, w base_ang_vel, cmd commands, c_f = feet_contact[f] > 0.5, Fz_f =
+ * feet_contact_forces[3 f + 2], p_f = feet_pos[3 f ..], clr_f = p_f.z - terrain height under p_f.xy (0 on a plane):
+ *   begin (after bg_env_reset): every plane 0.
+ *   step (after an env step that wrote `done`):  STATE != 0: nothing of the env is written.  LEN += 1 (len = the new value).  done: STATE = 1, no sample.
+ *     Otherwise  TAU2 += sum tau_j^2, TILT += g.x^2 + g.y^2, WOBBLE += w.x^2 + w.y^2, PEAK_f = max(PEAK_f, Fz_f);
+ *     len >= 2: D1 += sum (a_j - A1_j)^2;  len >= 3: D2 += sum (a_j - 2 A1_j + A2_j)^2;
+ *     !c_f: SWMAX_f = SWN_f == 0 ? clr_f : max(SWMAX_f, clr_f), SWN_f += 1;
+ *     moving = len > settle_steps and max |cmd_a| > 1e-6:  MOV += 1, STANCE_f += c_f, DS += c_0 and c_1, FL += neither;
+ *         touchdown (len >= 2, c_f, not CPREV_f): TD_f += 1, IMP_f += Fz_f, and with SWN_f > 0: CLR_f += SWMAX_f, SWT_f += SWN_f, SWC_f += 1;
+ *         stance (len >= 2, c_f, CPREV_f): d = |p_f.xy - PPREV_f|, SLIP_f += d where d <= 0.5 (a larger jump is the terrain's teleport wrap);
+ *     c_f: SWN_f = SWMAX_f = 0;  then A2 = A1, A1 = a, CPREV_f = c_f, PPREV_f = p_f.xy.
+ * A null env / record / done or a negative settle_steps is -1 naming the argument, before anything is launched. */
+#define BG_GAIT_PLANES 60
+int bg_env_gait_begin(bg_env* env, float* record, void* stream);
+int bg_env_gait_step(bg_env* env, const uint8_t* done, int32_t settle_steps, float* record, void* stream);
 
 /* ---- dynamics only (what north_star calls "per-step joint accelerations"): forward dynamics of N
  * independent states.  Device float arrays, env-major: root [N][13], dof_pos/dof_vel/tau [N][12],

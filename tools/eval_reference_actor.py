@@ -7,8 +7,9 @@ mean action drives `num_envs` robots through their first episode under the SHIPP
 actuation latency, kicks and pushes all on, commands resampled as in training -- and every scenario's report has that tool's keys.  This file
 keeps the scenario list (terrain x asset.self_collisions, and one run without noise, kicks and pushes) and the contact-parameter sweep.
 
-    python tools/eval_reference_actor.py [num_envs=4096] [steps=1502] [--sweep] [--checkpoint logs/.../model.pth] -> logs/reference_actor_eval.json
-(--checkpoint: the same scenarios for an actor trained by THIS build -> logs/own_actor_eval.json: the yardstick for the reference actor's numbers)
+    python tools/eval_reference_actor.py [num_envs=4096] [steps=1502] [--sweep] [--gait] [--checkpoint logs/.../model.pth] -> logs/reference_actor_eval.json
+(--checkpoint: the same scenarios for an actor trained by THIS build -> logs/own_actor_eval.json: the yardstick for the reference actor's numbers;
+--gait: evaluation.gait: true in every scenario, whose gait table is printed and whose report carries the "gait" entries)
 
 `evaluate()` below, with its own torch actor and accumulators, is the protocol of before evaluate.py existed (whole run instead of first episode,
 tracking sampled every fifth step).  tests/test_gpu_env.py::test_trained_reference_policy_walks_on_the_gpu holds bounds on its figures, so it stays
@@ -26,9 +27,10 @@ import torch
 
 from booster_gym_amd.envs import T1
 from booster_gym_amd.utils.config import load_cfg
-from booster_gym_amd.utils.evaluate import Evaluator
+from booster_gym_amd.utils.evaluate import Evaluator, format_report
 
 
+GAIT = False  # --gait: every scenario keeps the gait record too
 ACTOR_CHECKPOINT = None  # --checkpoint <.pth of this build's Runner>: evaluate that actor instead (how a policy TRAINED HERE fares under the same protocol)
 
 
@@ -54,6 +56,8 @@ def load_actor(dev):
 def evaluate_first_episode(n, steps, overrides, seed=42):
     """One scenario under evaluate.py's protocol: its report, with the loop's time."""
     over = dict({"env.num_envs": n, "basic.seed": seed}, **overrides)
+    if GAIT:
+        over["evaluation.gait"] = True
     if ACTOR_CHECKPOINT:
         ev = Evaluator(checkpoint=ACTOR_CHECKPOINT, overrides=over)
     else:
@@ -61,6 +65,8 @@ def evaluate_first_episode(n, steps, overrides, seed=42):
             ev = Evaluator(actor={k: W[k] for k in W.files}, overrides=over)
     rep = ev.run(steps)
     rep["scenario_overrides"], rep["loop_s"] = overrides, ev.loop_s
+    if GAIT:
+        print(format_report(rep), flush=True)
     del ev
     return rep
 
@@ -129,7 +135,8 @@ def evaluate(n, steps, overrides, seed=42):
 
 
 def main():
-    global ACTOR_CHECKPOINT
+    global ACTOR_CHECKPOINT, GAIT
+    GAIT = "--gait" in sys.argv
     if "--checkpoint" in sys.argv:
         k = sys.argv.index("--checkpoint")
         ACTOR_CHECKPOINT = sys.argv[k + 1]
