@@ -28,8 +28,17 @@ static void setup(const hh_cfg* c, Phys& ph, ContactCfg& cc) {
     ph.self_on = c->self_on; ph.self_k = c->self_k; ph.self_d = c->self_d; ph.self_mu = c->self_mu; ph.self_visc = c->self_visc;
 }
 
+}  // extern "C"
+
+// The store of the fused env step (RegStore) with the z-axis specialisation of the sweeps ON, as LdsLinkStore has it in the ABA kernel: the same
+// lane code then takes the specialised branch of every link whose bit is set in hh_cfg::zmask (RegStore itself ignores the mask).  No product
+// kernel uses this store: it stands for the branches only.  LdsLinkStore's own link_pos / link (the origin table and the link constants read back
+// through LDS) run on the GPU alone, where tests/test_gpu_model_surface.py covers them.
+struct ZSpecRegStore : RegStore { static constexpr bool ZSPEC = true; };
+
 // one env; arrays are in the SoA layout with n = 1.  root: pos3 quat4 lin3 ang3.  step != 0 integrates in place.
-int hh_forward(const ModelDev* m, const hh_cfg* c, const TerrainDev* tr, const float* mass_scale, const float* com_off, const float* foot_mat,
+template <class Ctx>
+static int forward_impl(const ModelDev* m, const hh_cfg* c, const TerrainDev* tr, const float* mass_scale, const float* com_off, const float* foot_mat,
                float* root, float* q, float* qd, const float* tau, const float* wrench /*force3 torque3*/, float* qacc, float* cf /*2x3*/,
                int step, float* body_cf /* [13][3] net contact force of the non-foot bodies, may be null */) {
     Phys ph; ContactCfg cc; setup(c, ph, cc);
@@ -38,7 +47,7 @@ int hh_forward(const ModelDev* m, const hh_cfg* c, const TerrainDev* tr, const f
     for (int i = 0; i < 4; i++) bs.quat[i] = root[3 + i];
     bs.vlin = v3(root[7], root[8], root[9]); bs.vang = v3(root[10], root[11], root[12]);
     LinkConst bk = load_base_link(*m, 0, 1, mass_scale, com_off);
-    LegParams lp[2]; LegState ls[2]; SubstepCtx cx[2]; BaseContribution bc[2]; BodyContactOut bo[2];
+    LegParams lp[2]; LegState ls[2]; Ctx cx[2]; BaseContribution bc[2]; BodyContactOut bo[2];
     TapeSwap tape[2][2];  // [pass parity][leg]
     for (int pass = 0; pass < 4; pass++) {
         const int cur = pass & 1, prev = cur ^ 1;
@@ -83,6 +92,17 @@ int hh_forward(const ModelDev* m, const hh_cfg* c, const TerrainDev* tr, const f
         for (int i = 0; i < 4; i++) root[3 + i] = bs.quat[i];
     }
     return 0;
+}
+
+extern "C" {
+int hh_forward(const ModelDev* m, const hh_cfg* c, const TerrainDev* tr, const float* mass_scale, const float* com_off, const float* foot_mat,
+               float* root, float* q, float* qd, const float* tau, const float* wrench, float* qacc, float* cf, int step, float* body_cf) {
+    return forward_impl<SubstepCtx>(m, c, tr, mass_scale, com_off, foot_mat, root, q, qd, tau, wrench, qacc, cf, step, body_cf);
+}
+// ... and with the sweeps specialised by hh_cfg::zmask
+int hh_forward_zspec(const ModelDev* m, const hh_cfg* c, const TerrainDev* tr, const float* mass_scale, const float* com_off, const float* foot_mat,
+                     float* root, float* q, float* qd, const float* tau, const float* wrench, float* qacc, float* cf, int step, float* body_cf) {
+    return forward_impl<SubstepCtxT<LegWorkT<ZSpecRegStore>>>(m, c, tr, mass_scale, com_off, foot_mat, root, q, qd, tau, wrench, qacc, cf, step, body_cf);
 }
 
 // The PACKED lane code (bg_dyn_pk.h: one env per lane, both legs in two-wide values -- g++ vector_size here, ext_vector_type on the GPU): one env,

@@ -419,15 +419,14 @@ class OracleEnv:
 
 
 def make_oracle_pair(n, overrides=None):
-    """cfg, OracleEnv(fp32 twin), float64 oracle on flat ground, without a GPU."""
+    """cfg, OracleEnv(fp32 twin), float64 oracle on flat ground, without a GPU.  The model is the config's asset.file, resolved as T1 resolves it."""
     from booster_gym_amd.utils.config import load_cfg
-    from booster_gym_amd.utils.urdf import FlatModel
+    from booster_gym_amd.utils.urdf import load_model
 
     ov = {"env.num_envs": n, "terrain.type": "plane"}
     ov.update(overrides or {})
     cfg = load_cfg("T1", ov)
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    model = FlatModel.load(os.path.join(root, "booster_gym_amd", "resources", "T1", "T1_locomotion.flat.json"))
+    model = load_model(cfg["asset"]["file"], cfg["asset"].get("collapse_fixed_joints", True))
     ref = make_oracle(cfg, model, host_params(cfg, model, n))
     return cfg, OracleEnv(cfg, make_twin(cfg, model, ref)), ref
 

@@ -36,19 +36,11 @@ def _states(rng, m, n, contact):
     return root, q, qd, tau, w
 
 
-@pytest.mark.parametrize("terrain,contact,tol,n", [("plane", False, 1e-4, 256), ("plane", True, 5e-4, 256), ("trimesh", True, 5e-4, 256), ("plane", "low", 1e-3, 256),
-                                                   ("trimesh", "low", 1e-3, 256), ("plane", "crossed", 5e-4, 256),
-                                                   # a ragged last block (100 = 3 x 32 + 4 envs) with every env's legs crossed: the item-parallel narrow
-                                                   # phase runs five passes of seven envs per wave, the clamped lanes of the last wave vote with env 99
-                                                   ("plane", "crossed", 5e-4, 100),
-                                                   # ... and a few crossed envs among many (one pass, partly filled): crossed-leg states in every 9th env
-                                                   ("plane", "sparse_crossed", 5e-4, 288),
-                                                   # crossed legs with the trunk-low gate ON (terminate_height 0.05): the two-kernel launch, where kernel A
-                                                   # defers every env whose legs can meet (SELF_DEFER), aba_compact_kernel lists them and kernel B evaluates
-                                                   # the contacts lane per leg (SELF_INLINE) -- the path a config with body_gate_height > terminate_height ships
-                                                   ("plane", "crossed_gated", 5e-4, 256)])
-@pytest.mark.parametrize("packed", [False, True], ids=["leg_per_lane", "env_per_lane"])
-def test_forward_dynamics_matches_oracle(flat_model, terrain, contact, tol, n, packed):
+def forward_dynamics_parity(flat_model, terrain, contact, tol, n, packed, overrides=None, phys=None, twin_all=False):
+    """One case of the forward-dynamics parity on `flat_model`, which the env loads itself: the shipped T1, or with overrides["asset.file"] the flat-model
+    file that `flat_model` was loaded from (tests/test_gpu_model_surface.py).  phys: DynRef's physics overrides that mirror `overrides`.  Asserts
+    the tolerances, the twin rule of an excused state and the contact forces; returns worst, the twin's worst (over the excused states; twin_all: over every state), ncontact and the
+    excused env indices for the caller to pin."""
     from booster_gym_amd.envs import T1
     from booster_gym_amd.utils.config import load_cfg
     from oracle.dyn_ref import DynRef
@@ -56,18 +48,18 @@ def test_forward_dynamics_matches_oracle(flat_model, terrain, contact, tol, n, p
     # rewards.terminate_height below the body-contact gate height switches the non-foot body contacts on (bg_env_cfg.body_gate_height): the ABA launch's
     # two-kernel scheme; the crossed-leg cases keep the shipped heights, where the launch is the ONE kernel with the narrow phase through LDS.
     # packed = bg_env_forward_dynamics_packed (one env per lane, both legs in 64-bit register pairs): shipped heights only (it has no body contacts)
-    if packed and contact in ("low", "crossed_gated"):
-        pytest.skip("the packed kernel carries no non-foot body contacts (refused with the trunk-low gate: test_packed_form_refuses_the_body_gate)")
     over = {} if contact in ("crossed", "sparse_crossed") or packed else {"rewards.terminate_height": 0.05}
     assert bool(over) == (contact in (False, True, "low", "crossed_gated") and not packed)
-    cfg = load_cfg("T1", dict({"env.num_envs": n, "terrain.type": terrain}, **over))
+    cfg = load_cfg("T1", dict({"env.num_envs": n, "terrain.type": terrain}, **over, **(overrides or {})))
     env = T1(cfg)
+    if overrides and "asset.file" in overrides:
+        assert np.array_equal(env.model.body_pos, flat_model.body_pos) and np.array_equal(env.model.inertia, flat_model.inertia)
     tdict = None
     if terrain != "plane":
         t = env.terrain
         tdict = dict(height_field_raw=t.height_field_raw, hscale=t.horizontal_scale, vscale=t.vertical_scale, border_px=t.border_pixels)
-    ref = DynRef(flat_model, feet_edge_pos=cfg["asset"]["feet_edge_pos"], terrain=tdict)
-    twin = DynRef(flat_model, feet_edge_pos=cfg["asset"]["feet_edge_pos"], terrain=tdict, real="f32")  # the oracle's own source in single precision
+    ref = DynRef(flat_model, feet_edge_pos=cfg["asset"]["feet_edge_pos"], terrain=tdict, phys=phys)
+    twin = DynRef(flat_model, feet_edge_pos=cfg["asset"]["feet_edge_pos"], terrain=tdict, phys=phys, real="f32")  # the oracle's own source in single precision
     rng = np.random.default_rng(3)
     if contact == "sparse_crossed":
         root, q, qd, tau, w = _states(rng, flat_model, n, False)
@@ -83,7 +75,7 @@ def test_forward_dynamics_matches_oracle(flat_model, terrain, contact, tol, n, p
     f = lambda a: torch.tensor(a, dtype=torch.float32, device=dev)
     qacc = env.forward_dynamics(f(root), f(q), f(qd), f(tau), f(w), packed=packed).cpu().numpy().astype(np.float64)
     cf = env.get_field("feet_contact_forces").cpu().numpy().reshape(n, 2, 3)
-    worst, ncontact, nexcused, excused = 0.0, 0, 0, []
+    worst, worst_twin, ncontact, nexcused, excused = 0.0, 0.0, 0, 0, []
     for e in range(n):
         r32 = root[e].astype(np.float32).astype(np.float64)  # oracle sees the same rounded inputs
         args = (r32, q[e].astype(np.float32), qd[e].astype(np.float32), tau[e].astype(np.float32))
@@ -93,11 +85,14 @@ def test_forward_dynamics_matches_oracle(flat_model, terrain, contact, tol, n, p
         # any active contact is stiff (also a chance leg-against-leg one among the random airborne poses): 5e-4 at least
         raw = np.abs(qacc[e] - qa).max() / max(1.0, np.abs(qa).max())
         err = raw * (tol / max(tol, 5e-4) if np.abs(cfr).max() > 0 else 1.0)
+        if twin_all:
+            worst_twin = max(worst_twin, np.abs(twin.forward(*args, **kw)[0] - qa).max() / max(1.0, np.abs(qa).max()))
         if err >= tol and np.abs(cfr).max() > 0:
             # a kN-range contact can make a state ill-conditioned in single precision altogether: then the oracle's OWN source built in float deviates
             # from its float64 build by more than the tolerance too, and the kernel is held to that deviation instead (x 1: no slack on top)
             qt, _ = twin.forward(*args, **kw)
             twin_err = np.abs(qt - qa).max() / max(1.0, np.abs(qa).max())
+            worst_twin = max(worst_twin, twin_err)
             assert raw <= twin_err, f"env {e}: relative qacc error {raw:.2e} beyond both the tolerance and the oracle's fp32 twin ({twin_err:.2e})"
             nexcused += 1
             excused.append(e)
@@ -109,6 +104,26 @@ def test_forward_dynamics_matches_oracle(flat_model, terrain, contact, tol, n, p
             assert np.abs(cf[e] - cfr[[6, 12]]).max() <= 2e-3 * max(1.0, np.abs(cfr).max())
     assert np.isfinite(qacc).all()
     assert worst < tol, f"worst relative qacc error {worst}"
+    return dict(worst=worst, worst_twin=worst_twin, ncontact=ncontact, excused=excused)
+
+
+@pytest.mark.parametrize("terrain,contact,tol,n", [("plane", False, 1e-4, 256), ("plane", True, 5e-4, 256), ("trimesh", True, 5e-4, 256), ("plane", "low", 1e-3, 256),
+                                                   ("trimesh", "low", 1e-3, 256), ("plane", "crossed", 5e-4, 256),
+                                                   # a ragged last block (100 = 3 x 32 + 4 envs) with every env's legs crossed: the item-parallel narrow
+                                                   # phase runs five passes of seven envs per wave, the clamped lanes of the last wave vote with env 99
+                                                   ("plane", "crossed", 5e-4, 100),
+                                                   # ... and a few crossed envs among many (one pass, partly filled): crossed-leg states in every 9th env
+                                                   ("plane", "sparse_crossed", 5e-4, 288),
+                                                   # crossed legs with the trunk-low gate ON (terminate_height 0.05): the two-kernel launch, where kernel A
+                                                   # defers every env whose legs can meet (SELF_DEFER), aba_compact_kernel lists them and kernel B evaluates
+                                                   # the contacts lane per leg (SELF_INLINE) -- the path a config with body_gate_height > terminate_height ships
+                                                   ("plane", "crossed_gated", 5e-4, 256)])
+@pytest.mark.parametrize("packed", [False, True], ids=["leg_per_lane", "env_per_lane"])
+def test_forward_dynamics_matches_oracle(flat_model, terrain, contact, tol, n, packed):
+    if packed and contact in ("low", "crossed_gated"):
+        pytest.skip("the packed kernel carries no non-foot body contacts (refused with the trunk-low gate: test_packed_form_refuses_the_body_gate)")
+    r = forward_dynamics_parity(flat_model, terrain, contact, tol, n, packed)
+    ncontact, nexcused, excused = r["ncontact"], len(r["excused"]), r["excused"]
     # the excused set is PINNED: one env of one case -- sparse_crossed: env 13, a 3.4 kN shank contact, twin 1.2e-3 -- and none anywhere else,
     # so a regression confined to stiff-contact states cannot hide behind the twin's own ill-conditioning
     assert excused == ([13] if contact == "sparse_crossed" and excused else []), (contact, nexcused, excused)
@@ -139,14 +154,21 @@ def test_mirrored_pose_gives_mirrored_accelerations_on_the_gpu(flat_model, tmp_p
     mirrored foot forces and no lateral / roll / yaw acceleration of the trunk.  In the lane-per-leg kernel the two legs are the two lanes of a pair
     and the trunk's share is split between them; in the packed kernel they are the halves of register pairs: a left / right slip in either shows at
     order one.  Tolerance: the parity tolerances of this file (fp32 sums in mirrored order differ in the last bits; stiff contacts amplify them)."""
-    from conftest import MIRROR_SIGN, mirrored_states, symmetrised
+    from conftest import symmetrised
+
+    mirrored_pose_parity(symmetrised(flat_model), tmp_path, standing, packed)
+
+
+def mirrored_pose_parity(sym_model, tmp_path, standing, packed):
+    """The body of test_mirrored_pose_gives_mirrored_accelerations_on_the_gpu on any exactly mirror-symmetric flat model."""
+    from conftest import MIRROR_SIGN, mirrored_states
 
     from booster_gym_amd.envs import T1
     from booster_gym_amd.utils.config import load_cfg
 
     n = 256
     path = tmp_path / "T1_symmetrised.flat.json"
-    symmetrised(flat_model).save(str(path))
+    sym_model.save(str(path))
     off = {f"randomization.{k}": None for k in ("base_com", "base_mass", "other_com", "other_mass", "friction", "compliance", "restitution")}
     env = T1(load_cfg("T1", dict({"env.num_envs": n, "terrain.type": "plane", "asset.file": str(path)}, **off)))
     assert np.all(env._mass_scale == 1.0) and np.all(env._com_off == 0.0) and np.ptp(env._foot_mat, axis=(0, 1)).max() == 0.0

@@ -28,11 +28,18 @@ def _make(n, terrain="plane", **over):
 
 @pytest.mark.parametrize("contact,tol", [(False, 1e-4), (True, 5e-4), ("low", 1e-3)])
 def test_simulate_matches_oracle_step(flat_model, contact, tol):
+    simulate_parity(flat_model, contact, tol)
+
+
+def simulate_parity(flat_model, contact, tol, n=256, overrides=None, phys=None):
+    """Two gym.simulate calls against the oracle's step on `flat_model`: the shipped T1, or with overrides["asset.file"] the flat-model file that
+    `flat_model` was loaded from (tests/test_gpu_model_surface.py); phys: DynRef's physics overrides that mirror `overrides`."""
     from oracle.dyn_ref import DynRef
 
-    n = 256
-    cfg, env, gym = _make(n)
-    ref = DynRef(flat_model, feet_edge_pos=cfg["asset"]["feet_edge_pos"])
+    cfg, env, gym = _make(n, **(overrides or {}))
+    if overrides and "asset.file" in overrides:
+        assert np.array_equal(env.model.body_pos, flat_model.body_pos) and np.array_equal(env.model.inertia, flat_model.inertia)
+    ref = DynRef(flat_model, feet_edge_pos=cfg["asset"]["feet_edge_pos"], phys=phys)
     dt = ref.phys.dt
     rng = np.random.default_rng(11)
     root, q, qd, tau, _ = _states(rng, flat_model, n, contact)
@@ -93,12 +100,18 @@ def test_simulate_matches_oracle_step(flat_model, contact, tol):
         assert ncontact > n // 4
     if contact == "low":  # the non-foot rows of the contact tensor (trunk, hip-yaw, shank) were exercised
         assert (np.abs(got1[2][:, [0, 3, 4, 9, 10]]).max(axis=(1, 2)) > 1.0).mean() > 0.3
+    return worst, ncontact
 
 
 def test_decimation_loop_on_gym_calls_equals_fused_step(flat_model):
     """t1.py:439-456 written against the granular calls reproduces the state the fused kernel reaches in one launch."""
+    decimation_loop_parity(flat_model)
+
+
+def decimation_loop_parity(flat_model, overrides=None):
+    """The body of test_decimation_loop_on_gym_calls_equals_fused_step; overrides["asset.file"]: on the flat model `flat_model` was loaded from."""
     n = 512
-    cfg, env, gym = _make(n)
+    cfg, env, gym = _make(n, **(overrides or {}))
     env.reset()
     dev = env.device
     g = torch.Generator(device="cpu").manual_seed(5)

@@ -400,115 +400,16 @@ def test_product_rng_header_matches_oracle_philox(harness):
 def test_product_dynamics_header_matches_oracle(harness, flat_model):
     """The per-lane fp32 articulated-body code of the HIP kernels, compiled for the host, against the float64 oracle: one leg per lane (bg_dyn.h)
     and, the same generic code with two-wide scalars, one env per lane (bg_dyn_pk.h)."""
-    from oracle.dyn_ref import DEFAULT_PHYS, DynRef
+    from dyn_header_util import assert_parity, header_parity
+    from model_variants import zmask_of
 
-    hh, m = harness["harness"], flat_model
-
-    class ModelDev(C.Structure):
-        _fields_ = [("pos", C.c_float * 3 * 13), ("mass", C.c_float * 13), ("com", C.c_float * 3 * 13), ("inertia", C.c_float * 6 * 13), ("q_lo", C.c_float * 12),
-                    ("q_hi", C.c_float * 12), ("qd_max", C.c_float * 12), ("tau_lim", C.c_float * 12), ("corner", C.c_float * 3 * 4),
-                    ("sph_n", C.c_int), ("sph_first", C.c_int * 13), ("sph_cnt", C.c_int * 13), ("sph_pos", C.c_float * 3 * 16), ("sph_r", C.c_float * 16),
-                    ("cap_c", C.c_float * 3 * 2 * 2), ("cap_h", C.c_float * 2 * 2), ("cap_r", C.c_float * 2 * 2)]
-
-    class Cfg(C.Structure):
-        _fields_ = [("dt", C.c_float), ("g", C.c_float * 3)] + [(k, C.c_float) for k in ("contact_k", "contact_d", "contact_ramp", "friction_visc", "limit_k", "limit_d",
-                                                                                      "terrain_mu", "terrain_restitution")] + [("clamp_qd", C.c_int), ("body_gate", C.c_float), ("self_on", C.c_int)] + \
-                   [(k, C.c_float) for k in ("self_k", "self_d", "self_mu", "self_visc")] + [("zmask", C.c_int)]
-
-    class Terr(C.Structure):
-        _fields_ = [("type", C.c_int), ("rows", C.c_int), ("cols", C.c_int), ("border_px", C.c_int), ("inv_hscale", C.c_float), ("vscale", C.c_float), ("hf", C.c_void_p)]
-
-    md = ModelDev()
-    for b in range(13):
-        md.mass[b] = m.mass[b]
-        for a in range(3):
-            md.pos[b][a], md.com[b][a] = m.body_pos[b, a], m.com[b, a]
-        for a in range(6):
-            md.inertia[b][a] = m.inertia[b, a]
-    for j in range(12):
-        md.q_lo[j], md.q_hi[j], md.qd_max[j], md.tau_lim[j] = m.dof_lower[j], m.dof_upper[j], m.dof_velocity[j], m.dof_effort[j]
-    corners = [[0.1215, 0.05, -0.03], [0.1215, -0.05, -0.03], [-0.1015, 0.05, -0.03], [-0.1015, -0.05, -0.03]]
-    for k in range(4):
-        for a in range(3):
-            md.corner[k][a] = corners[k][a]
-    sph = m.contact_spheres(exclude_bodies=[6, 12])  # the product's own derivation of the contact spheres (utils/urdf.py)
-    md.sph_n = len(sph)
-    for k, (b, c, r) in enumerate(sph):
-        if md.sph_cnt[b] == 0:
-            md.sph_first[b] = k
-        md.sph_cnt[b] += 1
-        md.sph_r[k] = r
-        for a in range(3):
-            md.sph_pos[k][a] = c[a]
-    assert len(sph) == 16 and [md.sph_cnt[b] for b in (0, 3, 4, 9, 10)] == [8, 2, 2, 2, 2]
-    for leg, caps in enumerate(m.self_collision_capsules([6, 12])):  # the product's own derivation of the self-collision capsules
-        for k, (body, a, b, r) in enumerate(caps):
-            assert body == (4, 6)[k] + 6 * leg
-            ax = (2, 0)[k]
-            md.cap_h[leg][k], md.cap_r[leg][k] = 0.5 * (b[ax] - a[ax]), r
-            for i in range(3):
-                md.cap_c[leg][k][i] = 0.5 * (a[i] + b[i])
-    cfg = Cfg(); cfg.dt = DEFAULT_PHYS["dt"]; cfg.clamp_qd = 1; cfg.body_gate = DEFAULT_PHYS["body_gate_height"]
-    cfg.self_on = 1
-    for k in ("self_k", "self_d", "self_mu", "self_visc"):
-        setattr(cfg, k, DEFAULT_PHYS[k])
     # links whose origin lies on the parent's z axis in both legs take the kernels' specialised code (Phys::zmask); the T1: hip roll, hip yaw, ankle pitch
-    cfg.zmask = sum(1 << i for i in range(6) if all(m.body_pos[1 + 6 * leg + i, 0] == 0 and m.body_pos[1 + 6 * leg + i, 1] == 0 for leg in range(2)))
-    assert cfg.zmask == 0b010110
-    for a in range(3):
-        cfg.g[a] = DEFAULT_PHYS["g"][a]
-    for k in ("contact_k", "contact_d", "contact_ramp", "friction_visc", "limit_k", "limit_d", "terrain_mu", "terrain_restitution"):
-        setattr(cfg, k, DEFAULT_PHYS[k])
-    rng = np.random.default_rng(1)
-    hf = rng.integers(-10, 10, size=(60, 60)).astype(np.int16)
-    # contact: False = airborne, True = standing height (sole contacts), "low" = trunk 0.15-0.5 m above the ground in any orientation, so that
-    # the trunk box and the hip-yaw / shank cylinders touch (explicit sphere contacts) as well
-    # "crossed": airborne with the hip rolls drawn inwards, so that shanks / feet of the two legs overlap (leg-against-leg contacts)
-    for terrain, contact, tol in ((None, False, 2e-5), (None, True, 5e-4), (dict(height_field_raw=hf, hscale=0.1, vscale=0.005, border_px=30), True, 5e-4),
-                                  (None, "low", 1e-3), (dict(height_field_raw=hf, hscale=0.1, vscale=0.005, border_px=30), "low", 1e-3),
-                                  (None, "crossed", 5e-4)):
-        d = DynRef(m, terrain=terrain)
-        t = Terr()
-        if terrain is not None:
-            t.type, t.rows, t.cols, t.border_px, t.inv_hscale, t.vscale, t.hf = 1, 60, 60, 30, 10.0, 0.005, hf.ctypes.data
-        worst, worst_pk, ncontact, nbody, crossed = 0.0, 0.0, 0, 0, contact == "crossed"
-        if crossed:
-            contact = False
-        for _ in range(150):
-            root = np.zeros(13); root[2] = (rng.uniform(0.15, 0.5) if contact == "low" else rng.uniform(0.55, 0.72)) if contact else 5.0
-            root[:2] = rng.uniform(-1, 1, 2)
-            ax = rng.normal(size=3); ax /= np.linalg.norm(ax); ang = rng.uniform(0, 3.0 if contact == "low" else 0.3)
-            root[3:6], root[6] = ax * np.sin(ang / 2), np.cos(ang / 2)
-            root[7:13] = rng.normal(size=6) * (0.3 if contact else 1.0)
-            q = (np.array([-0.2, 0, 0, 0.4, -0.25, 0] * 2) + rng.normal(size=12) * 0.1) if contact else rng.uniform(m.dof_lower - 0.05, m.dof_upper + 0.05)
-            if crossed:
-                q[[1, 7]], q[[0, 6]], q[[3, 9]] = (rng.uniform(-0.3, 0.0), rng.uniform(0.0, 0.3)), rng.uniform(-0.6, 0.2, 2), rng.uniform(0.0, 0.8, 2)
-            elif not contact:  # plain airborne case: smooth dynamics only, legs apart
-                q[[1, 7]] = rng.uniform(0.2, 1.0), rng.uniform(-1.0, -0.2)
-            qd, tau, w = rng.normal(size=12), rng.uniform(-m.dof_effort, m.dof_effort), rng.normal(size=6) * 10
-            ms, co = rng.uniform(0.8, 1.2, 13), rng.uniform(-0.05, 0.05, (13, 3))
-            fm = np.array([rng.uniform(0.1, 2), rng.uniform(0.5, 1.5), rng.uniform(0.1, 0.9)] * 2)
-            f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
-            arrs = [f32(ms), f32(co.reshape(39)), f32(fm), f32(root), f32(q), f32(qd), f32(tau), f32(w)]
-            qa, cf32, bcf = np.zeros(18, np.float32), np.zeros(6, np.float32), np.zeros((13, 3), np.float32)
-            p = lambda a: a.ctypes.data_as(C.c_void_p)
-            hh.hh_forward(C.byref(md), C.byref(cfg), C.byref(t), *[p(a) for a in arrs], p(qa), p(cf32), 0, p(bcf))
-            qacc, cf = d.forward(arrs[3], arrs[4], arrs[5], arrs[6], base_wrench=arrs[7], mass_scale=arrs[0], com_off=arrs[1].reshape(13, 3), foot_mat=arrs[2])
-            tol_s = tol if np.abs(cf).max() == 0 else max(tol, 5e-4)  # any contact (also a chance leg-against-leg one in the airborne case) is stiff
-            worst = max(worst, np.abs(qa - qacc).max() / max(1.0, np.abs(qacc).max()) / tol_s)
-            if contact != "low":  # the packed lane code (one env per lane, bg_dyn_pk.h) carries no non-foot body contacts: every other case
-                qp, cfp = np.zeros(18, np.float32), np.zeros(6, np.float32)
-                hh.hh_forward_pk(C.byref(md), C.byref(cfg), C.byref(t), *[p(a) for a in arrs], p(qp), p(cfp))
-                worst_pk = max(worst_pk, np.abs(qp - qacc).max() / max(1.0, np.abs(qacc).max()) / tol_s)
-                assert np.abs(cfp.reshape(2, 3) - cf[[6, 12]]).max() <= 2e-3 * max(1.0, np.abs(cf).max())
-            ncontact += int(np.abs(cf).max() > 0)
-            body_rows = [0, 1, 2, 3, 4, 5, 7, 8, 9, 10, 11]
-            nbody += int(np.abs(cf[body_rows]).max() > 0)
-            assert np.abs(bcf[body_rows] - cf[body_rows]).max() <= 2e-3 * max(1.0, np.abs(cf).max())
-        assert worst < 1.0, (terrain is not None, contact, crossed, worst)
-        assert worst_pk < 1.0, ("packed", terrain is not None, contact, crossed, worst_pk)
-        assert (ncontact > 50) == bool(contact or crossed), ncontact
-        assert (nbody > 30) == (contact == "low" or crossed), nbody  # crossed: the shank rows carry leg-against-leg forces
+    zmask = zmask_of(flat_model)
+    assert zmask == 0b010110
+    # the T1 with its shipped sole corners and physics; the body is dyn_header_util.header_parity (tests/test_model_surface_ref.py runs it on other models)
+    recs = header_parity(harness["harness"], flat_model, zmask, feet_edge_pos=None, phys=None)
+    assert len(recs) == 6
+    assert_parity(recs, "T1")
 
 
 # ------------------------------------------------------------------ data parallel under gloo, world_size 2
