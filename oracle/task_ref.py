@@ -314,6 +314,92 @@ def keyed_perm(p, K, key):
     return int(p)
 
 
+def _mix32_vec(x):
+    x = np.asarray(x, dtype=np.uint32).copy()
+    with np.errstate(over="ignore"):
+        x ^= x >> np.uint32(16); x *= np.uint32(0x85EBCA6B); x ^= x >> np.uint32(13); x *= np.uint32(0xC2B2AE35); x ^= x >> np.uint32(16)
+    return x
+
+
+def keyed_perm_vec(p, K, key):
+    """keyed_perm for an array of positions at once (identical values): every position walks its cycle until it lands inside [0, K)."""
+    p = np.asarray(p, dtype=np.int64)
+    if K <= 1:
+        return np.zeros_like(p)
+    bits = 2
+    while bits < 32 and (1 << bits) < K:
+        bits += 2
+    hb = bits >> 1
+    hm = np.uint32((1 << hb) - 1)
+    keys = [np.uint32((int(key) + r * 0x9E3779B9) & 0xFFFFFFFF) for r in range(4)]
+    x, out = p.astype(np.uint32), p.copy()
+    walking = np.ones(p.shape, dtype=bool)
+    for _ in range(64):
+        if not walking.any():
+            break
+        xs = x[walking]
+        L, R = xs >> np.uint32(hb), xs & hm
+        for r in range(4):
+            L, R = R, L ^ (_mix32_vec(R ^ keys[r]) & hm)
+        xs = (L << np.uint32(hb)) | R
+        x[walking] = xs
+        landed = xs < np.uint32(K)
+        idx = np.nonzero(walking)[0]
+        out[idx[landed]] = xs[landed].astype(np.int64)
+        walking[idx[landed]] = False
+    return out
+
+
+def resample_commands(rs, step, so, grid, cfg, seed, exact_still_count=None):
+    """_resample_commands (t1.py:362-389) as a function of the resample flags `rs` [n] (bool, env order), the step counter, the stream offset (0: a
+    step, 64: reset()), the curriculum grid the draw reads and the config: the part of the step that couples envs.  Without
+    parallel.exact_still_count the still envs are a per-env Bernoulli draw (this build's documented deviation); with it, exactly
+    int(still_proportion * K) of the K resampling envs stand still, chosen by keyed_perm of the env's position among them.
+    Returns per env (meaningful where rs): commands [n,3], gait_frequency [n], still [n], add [n] (the increment of cmd_resample_time) and, with
+    commands.curriculum, the drawn levels lin / ang [n]."""
+    rs = np.asarray(rs, dtype=bool)
+    n = rs.shape[0]
+    cm = cfg["commands"]
+    dt = cfg["control"]["decimation"] * cfg["sim"]["dt"]
+    if exact_still_count is None:
+        exact_still_count = bool((cfg.get("parallel", {}) or {}).get("exact_still_count", False))
+    env = np.arange(n, dtype=np.uint32)
+    c0u, _ = rand4(seed, env, step, so + RS_CMD0)
+    c1u, _ = rand4(seed, env, step, so + RS_CMD1)
+    new = np.stack([cm["lin_vel_x"][0] + (cm["lin_vel_x"][1] - cm["lin_vel_x"][0]) * c0u[:, 0],
+                    cm["lin_vel_y"][0] + (cm["lin_vel_y"][1] - cm["lin_vel_y"][0]) * c0u[:, 1],
+                    cm["ang_vel_yaw"][0] + (cm["ang_vel_yaw"][1] - cm["ang_vel_yaw"][0]) * c0u[:, 2]], axis=1).astype(np.float64)
+    out = {}
+    if bool(cm.get("curriculum", False)):
+        grid = np.asarray(grid)
+        cru, _ = rand4(seed, env, step, so + RS_CURR)
+        p = np.minimum(grid, 1.0).astype(np.float32).reshape(-1)
+        total = np.float32(0.0)
+        for v in p:
+            total = np.float32(total + v)
+        cum = np.cumsum(p, dtype=np.float32)  # sequential float32 accumulation like the kernel
+        target = cru[:, 0] * total
+        idx = np.minimum(np.searchsorted(cum, target, side="right").astype(np.int64), p.size - 1)
+        lin, ang, new = curriculum_commands(idx, cru[:, 1].astype(np.float64) - 0.5, 2.0 * cru[:, 2].astype(np.float64) - 1.0,
+                                            cru[:, 3].astype(np.float64) - 0.5, cm, grid.shape[1])
+        out["lin"], out["ang"] = lin, ang
+    gf = (cm["gait_frequency"][0] + (cm["gait_frequency"][1] - cm["gait_frequency"][0]) * c0u[:, 3]).astype(np.float64)
+    if exact_still_count:
+        ids = np.nonzero(rs)[0]  # positions in env order
+        K = len(ids)
+        m = int(float(np.float32(cm["still_proportion"])) * K)
+        key = _mix32(np.uint32(seed & 0xFFFFFFFF) ^ _mix32(np.uint32((step + 0x632BE5AB * (so + 1)) & 0xFFFFFFFF)))
+        still = np.zeros(n, dtype=bool)
+        still[ids] = keyed_perm_vec(np.arange(K), K, key) < m
+    else:
+        still = c1u[:, 0] < np.float32(cm["still_proportion"])
+    new[still] = 0.0; gf[still] = 0.0
+    lo, hi = int(cm["resampling_time_s"][0] / dt), int(cm["resampling_time_s"][1] / dt)
+    add = lo + np.minimum((c1u[:, 1] * np.float32(hi - lo)).astype(np.int64), hi - lo - 1) if hi > lo else np.full(n, lo)
+    out.update(commands=new, gait_frequency=gf, still=still, add=add)
+    return out
+
+
 # ------------------------------------------------------------------ full env: t1.py:294-341, 437-497 around the C physics oracle
 class T1Ref:
     """State arrays are float64 numpy, env-major.  `dyn` is an oracle.dyn_ref.DynRef (its terrain must match `terrain`)."""
@@ -425,43 +511,14 @@ class T1Ref:
             sy = np.where(self.root[:, 1] < -0.75 * b, el + b, 0.0) - np.where(self.root[:, 1] > el + 0.75 * b, el + b, 0.0)
             self.root[:, 0] += sx; self.root[:, 1] += sy
             feet_store[:, :, 0] += sx[:, None]; feet_store[:, :, 1] += sy[:, None]
-        # ---- _resample_commands (t1.py:362-389); still envs by per-env Bernoulli (this build's documented deviation)
+        # ---- _resample_commands (t1.py:362-389): resample_commands below
         rs = self.ep_len == self.cmd_time
         if rs.any():
-            cm = cfg["commands"]
-            c0u, _ = self._r4(RS_CMD0, step, so)
-            c1u, _ = self._r4(RS_CMD1, step, so)
-            new = np.stack([cm["lin_vel_x"][0] + (cm["lin_vel_x"][1] - cm["lin_vel_x"][0]) * c0u[:, 0],
-                            cm["lin_vel_y"][0] + (cm["lin_vel_y"][1] - cm["lin_vel_y"][0]) * c0u[:, 1],
-                            cm["ang_vel_yaw"][0] + (cm["ang_vel_yaw"][1] - cm["ang_vel_yaw"][0]) * c0u[:, 2]], axis=1).astype(np.float64)
+            grid = self.curr_prob if self.same_step_curriculum else self.curr_prob_read
+            r = resample_commands(rs, step, so, grid, cfg, self.seed, exact_still_count=self.exact_still_count)
             if self.curriculum:
-                cru, _ = self._r4(RS_CURR, step, so)
-                p = np.minimum(self.curr_prob if self.same_step_curriculum else self.curr_prob_read, 1.0).astype(np.float32).reshape(-1)
-                total = np.float32(0.0)
-                for v in p:
-                    total = np.float32(total + v)
-                cum = np.cumsum(p, dtype=np.float32)  # sequential float32 accumulation like the kernel
-                target = cru[:, 0] * total
-                idx = np.minimum(np.array([int(np.searchsorted(cum, t, side="right")) for t in target]), p.size - 1)
-                lin, ang, ccmd = curriculum_commands(idx, cru[:, 1].astype(np.float64) - 0.5, 2.0 * cru[:, 2].astype(np.float64) - 1.0,
-                                                     cru[:, 3].astype(np.float64) - 0.5, cm, self.curr_prob.shape[1])
-                new = ccmd
-                self.curr_levels[rs, 0] = lin[rs]; self.curr_levels[rs, 1] = ang[rs]
-            gf = (cm["gait_frequency"][0] + (cm["gait_frequency"][1] - cm["gait_frequency"][0]) * c0u[:, 3]).astype(np.float64)
-            if self.exact_still_count:
-                ids = np.nonzero(rs)[0]  # positions in env order
-                K = len(ids)
-                m = int(float(np.float32(cm["still_proportion"])) * K)
-                key = _mix32(np.uint32(self.seed & 0xFFFFFFFF) ^ _mix32(np.uint32((step + 0x632BE5AB * (so + 1)) & 0xFFFFFFFF)))
-                still = np.zeros(n, dtype=bool)
-                for pos, e in enumerate(ids):
-                    still[e] = keyed_perm(pos, K, key) < m
-            else:
-                still = c1u[:, 0] < np.float32(cm["still_proportion"])
-            new[still] = 0.0; gf[still] = 0.0
-            lo, hi = int(cm["resampling_time_s"][0] / self.dt), int(cm["resampling_time_s"][1] / self.dt)
-            add = lo + np.minimum((c1u[:, 1] * np.float32(hi - lo)).astype(np.int64), hi - lo - 1) if hi > lo else np.full(n, lo)
-            self.cmd[rs] = new[rs]; self.gait_f[rs] = gf[rs]; self.cmd_time[rs] += add[rs]
+                self.curr_levels[rs, 0] = r["lin"][rs]; self.curr_levels[rs, 1] = r["ang"][rs]
+            self.cmd[rs] = r["commands"][rs]; self.gait_f[rs] = r["gait_frequency"][rs]; self.cmd_time[rs] += r["add"][rs]
         # ---- _compute_observations (t1.py:574-603) with this build's noise streams
         o0u, o0n = self._r4(RS_OBS0, step, so); o1u, o1n = self._r4(RS_OBS1, step, so); o2u, o2n = self._r4(RS_OBS2, step, so)
         dpu, dpn, dvu, dvn = np.zeros((n, 12), np.float32), np.zeros((n, 12), np.float32), np.zeros((n, 12), np.float32), np.zeros((n, 12), np.float32)

@@ -676,3 +676,220 @@ def assert_not_vacuous(case, sh, what):
         assert sh["total_nonzero"] >= TOTAL_NONZERO_SHARE, f"{what}: total reward non-zero in {sh['total_nonzero']:.3f} of the env-steps only"
     if case["swing"]:
         assert sh["feet_swing"] >= SWING_SHARE, f"{what}: feet_swing non-zero in {sh['feet_swing']:.3f} of the env-steps only"
+
+
+# ================================================================== stages that couple envs, or walk them with a grid smaller than the work
+# One table for tests/test_env_scale_ref.py (the sizes and placements cross the thresholds they claim to cross, the references satisfy the
+# conditions on their own) and tests/test_gpu_env_scale.py (the kernels).  A large run whose env e carries the state and per-env parameters of env
+# src[e] of a 256-env run must reproduce that env's outputs bit for bit, whichever kernel, trip or list position served it.
+SCALE_N, SCALE_SRC = 33000, 256        # 1,032 blocks of 32 envs, the last one of 8
+RESAMPLE_NS = (70000, 600)             # 274 resample blocks (two per thread of the offsets scan, threads 137.. empty) / three with a ragged tail
+SPARSE_ONE = (0, 255, 256, 511, 512, 1023, 1024, 1031)   # forward dynamics, sparse batch: blocks with one listed env ...
+SPARSE_FULL = (300, 1031)                                # ... blocks listed whole (1031 is the ragged last block), plus 3 % of all others
+LOW_BASES = (0, 3, 7)                  # gated simulate / env step: low envs in blocks b, b + BODY_GRID, b + 2 BODY_GRID
+PER_ENV_PARAMS = ("dof_stiffness", "dof_damping", "dof_friction", "mass_scale", "com_offset", "foot_material", "base_mass_scaled", "delay_steps")
+# The stated tolerance per contact family of tests/test_gpu_dynamics.py and tests/test_gpu_sim_calls.py, the one table those files'
+# parametrisations and the scale cases read: relative 1e-4 on the accelerations without a contact, 5e-4 with stiff sole or leg-against-leg contacts, 1e-3
+# with the trunk box and the hip-yaw / shank cylinders on the ground.
+FAMILY_TOL = {False: 1e-4, True: 5e-4, "low": 1e-3, "crossed": 5e-4, "sparse_crossed": 5e-4, "crossed_gated": 5e-4}
+
+
+def kernel_constants(text=None):
+    """The constants the sizes of the scale cases rest on, read from the source text of csrc/bg_sim.hip."""
+    import re
+
+    if text is None:
+        with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "booster_gym_amd", "csrc", "bg_sim.hip")) as f:
+            text = f.read()
+    one = lambda pat: int(re.search(pat, text, re.S).group(1))
+    return {"ENVS_PER_BLOCK": one(r"constexpr int ENVS_PER_BLOCK = (\d+);"), "BODY_GRID": one(r"constexpr int BODY_GRID = (\d+);"),
+            "RS_BLOCK": one(r"constexpr int RS_BLOCK = (\d+);"),
+            "FD_GRID": one(r"forward_dynamics_body_kernel<true>, dim3\(nb < (\d+) \? nb : \1\)"),
+            "COMPACT_BLOCK": one(r"__launch_bounds__\((\d+)\) void aba_compact_kernel"),
+            "COMPACT_GRID_DIV": one(r"aba_compact_kernel, dim3\(\(nb \+ \d+\) / (\d+)\)")}
+
+
+def sparse_listed(n=SCALE_N, epb=32, seed=5):
+    """The sparse forward-dynamics batch: which envs are to be listed for kernel B."""
+    rng = np.random.default_rng(seed)
+    listed = rng.random(n) < 0.03
+    for b in SPARSE_ONE + SPARSE_FULL:
+        listed[b * epb:(b + 1) * epb] = False
+    for b in SPARSE_ONE:
+        rows = min(epb, n - b * epb)
+        listed[b * epb + int(rng.integers(0, rows))] = True
+    for b in SPARSE_FULL:
+        listed[b * epb:(b + 1) * epb] = True
+    return listed
+
+
+def low_placement(n=SCALE_N, epb=32, grid=512, seed=6):
+    """Gated simulate / env step: which envs lie low.  Blocks b, b + grid, b + 2 grid for b in LOW_BASES hold some; block 3 + grid is low whole, block 7
+    holds a single one, the ragged last block (7 + 2 grid at the shipped constants) holds low envs too."""
+    rng = np.random.default_rng(seed)
+    low = np.zeros(n, dtype=bool)
+    for base in LOW_BASES:
+        for trip in range(3):
+            b = base + trip * grid
+            rows = min(epb, n - b * epb)
+            if rows <= 0:
+                continue
+            k = rows if (base, trip) == (3, 1) else 1 if (base, trip) == (7, 0) else min(rows, 5)
+            low[b * epb + rng.choice(rows, size=k, replace=False)] = True
+    return low
+
+
+def block_masks(flags, epb=32):
+    """Per block of `epb` envs the number of flagged envs and the block's size."""
+    n = len(flags)
+    nb = (n + epb - 1) // epb
+    pad = np.zeros(nb * epb, dtype=bool); pad[:n] = flags
+    return pad.reshape(nb, epb).sum(axis=1), np.minimum(epb, n - np.arange(nb) * epb)
+
+
+def shuffled_src(member, classes, seed=7):
+    """src [N] onto the source envs: env e of class member[e] (an int) takes a source env of classes[member[e]] (an index array), every source env
+    occurring at least once, in a fixed-seed random arrangement."""
+    rng = np.random.default_rng(seed)
+    member = np.asarray(member)
+    src = np.empty(len(member), dtype=np.int64)
+    for c, pool in enumerate(classes):
+        where = np.nonzero(member == c)[0]
+        assert len(where) >= len(pool), f"class {c}: {len(where)} envs cannot hold {len(pool)} source envs"
+        pick = np.concatenate([pool, rng.choice(pool, size=len(where) - len(pool))])
+        rng.shuffle(pick)
+        src[where] = pick
+    return src
+
+
+def spot_positions(n, must=(), count=64, epb=32, seed=8):
+    """`count` env positions for the oracle's spot check: the first and the last env, both sides of the boundaries at 16,384 and 32,768 envs, the
+    ragged last block, the positions of `must`, the rest at random."""
+    fixed = [0, n - 1] + [e for e in (16383, 16384, 32767, 32768) if e < n] + list(range((n - 1) // epb * epb, n))
+    pos = list(dict.fromkeys([int(e) for e in fixed] + [int(e) for e in must]))[:count]
+    rng = np.random.default_rng(seed)
+    rest = [int(e) for e in rng.permutation(n) if int(e) not in set(pos)]
+    return np.array(sorted(pos + rest[:count - len(pos)]))
+
+
+def leg_clearance(dyn, flat_model, root, q):
+    """self_clearance of csrc/bg_dyn.h in float64: the lateral gap between the capsules of the two legs along the trunk's y axis; kernel A of the
+    gated forward dynamics leaves an env to kernel B when it is negative."""
+    from oracle.dyn_ref import self_capsules
+
+    pos, rot = dyn.body_poses(np.asarray(root, dtype=np.float64), np.asarray(q, dtype=np.float64))
+    ey = rot[0][:, 1]
+    inner = []
+    for leg, fb in enumerate((6, 12)):
+        ext = []
+        for body, a, b, r in self_capsules(flat_model, [fb]):
+            ys = [float(ey @ (pos[body] + rot[body] @ np.asarray(p) - pos[0])) for p in (a, b)]
+            ext.append(min(ys) - r if leg == 0 else -(max(ys) + r))
+        inner.append(min(ext))
+    return inner[0] + inner[1]
+
+
+def fd_listed(dyn, flat_model, root, q, gate=0.45):
+    """(listed, margin): does kernel A of the gated forward dynamics leave this state to kernel B (trunk lower than the gate above the terrain, or the
+    legs can meet), and by how much the nearer of the two tests is decided."""
+    h = float(root[2]) - dyn.terrain_height(float(root[0]), float(root[1])) - gate
+    c = leg_clearance(dyn, flat_model, root, q)
+    return (h < 0 or c < 0), (max(-h, -c) if (h < 0 or c < 0) else min(h, c))
+
+
+def fd_tables(dyn, flat_model, states_of, terrain_shift=None, margin=1e-4):
+    """Source states of the forward-dynamics scale cases from test_gpu_dynamics._states at that file's seed (3) and size (256), whose excused list is
+    empty: source env i carries state i of one family, chosen per i as the first family whose state is listed / not listed by more than `margin`
+    (metres; fp32 rounding of the two tests is 1e-7).  Returns {"all": every source env listed, "sparse": even source envs listed and odd ones not,
+    "crossed": the crossed family (ungated env)}, each a dict of root, q, qd, tau, w [256, .], family [256], listed [256] and ok [256]: by the
+    kernel's rule not every "crossed_gated" or "low" state is left to kernel B (218 and 224 of the 256 are), so a source env with no such state in
+    either family is not ok, and pool = the source envs that are ok in "all" and in "sparse" (the only ones a large batch may point to)."""
+    fams = {}
+    for fam in (False, True, "low", "crossed", "crossed_gated"):
+        root, q, qd, tau, w = states_of(np.random.default_rng(3), flat_model, SCALE_SRC, fam)
+        if terrain_shift is not None:
+            terrain_shift(root)
+        fams[fam] = (root, q, qd, tau, w)
+
+    def table(want, order):
+        out = {k: [] for k in ("root", "q", "qd", "tau", "w", "family", "listed", "ok")}
+        for i in range(SCALE_SRC):
+            ok = False
+            for fam in order(i):
+                listed, m = fd_listed(dyn, flat_model, fams[fam][0][i], fams[fam][1][i])
+                if listed == want(i) and m > margin:
+                    ok = True
+                    break
+            for k, a in zip(("root", "q", "qd", "tau", "w"), fams[fam]):
+                out[k].append(a[i])
+            out["family"].append(fam); out["listed"].append(listed); out["ok"].append(ok)
+        return {k: (np.array(v) if k != "family" else v) for k, v in out.items()}
+
+    lst = lambda i: ("crossed_gated", "low") if i % 4 < 2 else ("low", "crossed_gated")
+    tabs = {"all": table(lambda i: True, lst), "sparse": table(lambda i: i % 2 == 0, lambda i: lst(i) if i % 2 == 0 else (True, False)),
+            "crossed": dict(zip(("root", "q", "qd", "tau", "w"), fams["crossed"]), family=["crossed"] * SCALE_SRC, listed=np.zeros(SCALE_SRC, bool),
+                            ok=np.ones(SCALE_SRC, bool))}
+    tabs["pool"] = np.nonzero(tabs["all"]["ok"] & tabs["sparse"]["ok"])[0]
+    return tabs
+
+
+def fd_spot_check(dyn, tab, src, spots, qacc, cf, params, twin=None):
+    """The float64 oracle on the envs `spots` of a large forward-dynamics run (qacc [N,18], cf [N,2,3]; the state of env e is row src[e] of `tab`,
+    its parameters are params[.][e] as the kernel holds them), at the tolerance of its source's contact family in tests/test_gpu_dynamics.py: 5e-4
+    at least with an active contact, nothing excused.  twin: hold the oracle's fp32 build to the same bounds instead of a kernel.  Returns the worst
+    error over its bound and the number of states with a contact."""
+    worst, ncontact = 0.0, 0
+    f32 = lambda a: np.asarray(a, dtype=np.float32).astype(np.float64)
+    for e in spots:
+        i = int(src[e])
+        args = tuple(f32(tab[k][i]) for k in ("root", "q", "qd", "tau"))
+        kw = dict(base_wrench=f32(tab["w"][i]), mass_scale=f32(params["mass_scale"][e]), com_off=f32(params["com_offset"][e]).reshape(13, 3),
+                  foot_mat=f32(params["foot_material"][e]).reshape(6))
+        qa, cfr = dyn.forward(*args, **kw)
+        got, gcf = (twin.forward(*args, **kw)[0], None) if twin is not None else (np.asarray(qacc[e], dtype=np.float64), cf[e])
+        touching = np.abs(cfr).max() > 0
+        tol = max(FAMILY_TOL[tab["family"][i]], 5e-4) if touching else FAMILY_TOL[tab["family"][i]]
+        raw = np.abs(got - qa).max() / max(1.0, np.abs(qa).max())
+        assert raw < tol, f"env {e} (source {i}, {tab['family'][i]}): relative qacc error {raw:.2e}, tolerance {tol:g}"
+        worst = max(worst, raw / tol)
+        if touching:
+            ncontact += 1
+            if gcf is not None:
+                assert np.abs(np.asarray(gcf, dtype=np.float64) - cfr[[6, 12]]).max() <= 2e-3 * max(1.0, np.abs(cfr).max()), f"env {e}: foot forces"
+    return worst, ncontact
+
+
+def copy_params(small, big, src):
+    """The per-env parameters of the small env, through src, into the large one (set_field); returns them as numpy for the oracle."""
+    import torch
+
+    idx = torch.as_tensor(src, device=small.device)
+    for k in PER_ENV_PARAMS:
+        big.set_field(k, small.get_field(k)[idx])
+    return {k: big.get_field(k).cpu().numpy() for k in PER_ENV_PARAMS}
+
+
+def sim_sources(flat_model, states_of, gate, n=SCALE_SRC):
+    """Source states of the gated-simulate scale case from test_gpu_dynamics._states at the seed (11) and families of tests/test_gpu_sim_calls.py:
+    every fourth source env a "low" state whose trunk is more than 5 cm under the gate (it stays low through ten calls), the others standing states;
+    the body wrench of that file.  Returns root, q, qd, tau, bf, bt and is_low [n]."""
+    lo = states_of(np.random.default_rng(11), flat_model, n, "low")
+    rng = np.random.default_rng(11)
+    st = states_of(rng, flat_model, n, True)
+    is_low = (np.arange(n) % 4 == 0) & (lo[0][:, 2] < gate - 0.05)
+    root, q, qd, tau = (np.where(is_low[:, None], a, b) for a, b in zip(lo[:4], st[:4]))
+    assert is_low.sum() >= 32 and (root[~is_low, 2] > gate + 0.05).all()
+    bf, bt = rng.normal(size=(n, 13, 3)) * 10.0, rng.normal(size=(n, 13, 3)) * 2.0
+    return root, q, qd, tau, bf, bt, is_low
+
+
+def sim_implied_error(dyn, root, q, qd, tau, bf, bt, par, vel_after):
+    """The velocity part of tests/test_gpu_sim_calls.simulate_parity for one env and one gym.simulate: the accelerations implied by the velocities
+    `vel_after` [18] (root lin / ang, dof) against the float64 oracle's step from (root, q, qd), relative to max(1, |qacc|), less the fp32 rounding
+    of the stored velocities themselves.  bf / bt: the pending body wrench or None."""
+    r, qq, qv = np.array(root, dtype=np.float64), np.array(q, dtype=np.float64), np.array(qd, dtype=np.float64)
+    qa, _ = dyn.forward_bw(r, qq, qv, tau, bf, bt, **par)
+    dyn.step_bw(r, qq, qv, tau, bf, bt, **par)
+    vel_r = np.concatenate([r[7:13], qv])
+    dt = dyn.phys.dt
+    return (np.abs(np.asarray(vel_after, dtype=np.float64) - vel_r).max() / dt - 2e-7 * max(1.0, np.abs(vel_r).max()) / dt) / max(1.0, np.abs(qa).max())

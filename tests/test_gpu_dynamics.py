@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from parity_util import FAMILY_TOL as TOL
+
 pytestmark = pytest.mark.gpu
 
 
@@ -107,17 +109,17 @@ def forward_dynamics_parity(flat_model, terrain, contact, tol, n, packed, overri
     return dict(worst=worst, worst_twin=worst_twin, ncontact=ncontact, excused=excused)
 
 
-@pytest.mark.parametrize("terrain,contact,tol,n", [("plane", False, 1e-4, 256), ("plane", True, 5e-4, 256), ("trimesh", True, 5e-4, 256), ("plane", "low", 1e-3, 256),
-                                                   ("trimesh", "low", 1e-3, 256), ("plane", "crossed", 5e-4, 256),
+@pytest.mark.parametrize("terrain,contact,tol,n", [("plane", False, TOL[False], 256), ("plane", True, TOL[True], 256), ("trimesh", True, TOL[True], 256), ("plane", "low", TOL["low"], 256),
+                                                   ("trimesh", "low", TOL["low"], 256), ("plane", "crossed", TOL["crossed"], 256),
                                                    # a ragged last block (100 = 3 x 32 + 4 envs) with every env's legs crossed: the item-parallel narrow
                                                    # phase runs five passes of seven envs per wave, the clamped lanes of the last wave vote with env 99
-                                                   ("plane", "crossed", 5e-4, 100),
+                                                   ("plane", "crossed", TOL["crossed"], 100),
                                                    # ... and a few crossed envs among many (one pass, partly filled): crossed-leg states in every 9th env
-                                                   ("plane", "sparse_crossed", 5e-4, 288),
+                                                   ("plane", "sparse_crossed", TOL["sparse_crossed"], 288),
                                                    # crossed legs with the trunk-low gate ON (terminate_height 0.05): the two-kernel launch, where kernel A
                                                    # defers every env whose legs can meet (SELF_DEFER), aba_compact_kernel lists them and kernel B evaluates
                                                    # the contacts lane per leg (SELF_INLINE) -- the path a config with body_gate_height > terminate_height ships
-                                                   ("plane", "crossed_gated", 5e-4, 256)])
+                                                   ("plane", "crossed_gated", TOL["crossed_gated"], 256)])
 @pytest.mark.parametrize("packed", [False, True], ids=["leg_per_lane", "env_per_lane"])
 def test_forward_dynamics_matches_oracle(flat_model, terrain, contact, tol, n, packed):
     if packed and contact in ("low", "crossed_gated"):

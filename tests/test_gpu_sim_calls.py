@@ -11,6 +11,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from parity_util import FAMILY_TOL  # noqa: E402
 from test_gpu_dynamics import _states  # noqa: E402
 
 
@@ -26,7 +27,7 @@ def _make(n, terrain="plane", **over):
     return cfg, env, GymCalls(env)
 
 
-@pytest.mark.parametrize("contact,tol", [(False, 1e-4), (True, 5e-4), ("low", 1e-3)])
+@pytest.mark.parametrize("contact,tol", [(c, FAMILY_TOL[c]) for c in (False, True, "low")])
 def test_simulate_matches_oracle_step(flat_model, contact, tol):
     simulate_parity(flat_model, contact, tol)
 
