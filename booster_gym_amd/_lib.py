@@ -89,6 +89,11 @@ class GruDesc(C.Structure):
     _fields_ = [("W_ih", C.c_void_p), ("W_hh", C.c_void_p), ("b_ih", C.c_void_p), ("b_hh", C.c_void_p), ("in_", C.c_int32), ("hidden", C.c_int32)]
 
 
+class LstmDesc(C.Structure):
+    """bg_lstm_desc: an LSTM cell in torch.nn.LSTMCell's layout (include/booster_gym_amd.h)."""
+    _fields_ = GruDesc._fields_
+
+
 class GruForwardProblem(C.Structure):
     """bg_gru_forward_problem: one recurrence of bg_gru_sequence_forward_group, the arguments of bg_gru_sequence_forward (include/booster_gym_amd.h)."""
     _fields_ = [("T", C.c_int32), ("N", C.c_int32), ("gi", C.c_void_p), ("h0", C.c_void_p), ("reset", C.c_void_p), ("W_hh", C.c_void_p), ("b_hh", C.c_void_p),
@@ -229,6 +234,7 @@ SYMBOLS = [
     "bg_perm_fill", "bg_gather_rows", "bg_gather_sequences",
     "bg_actor_sample_gru", "bg_distill_act_gru", "bg_distill_act_gru_own", "bg_gru_sequence_forward", "bg_gru_sequence_backward",
     "bg_gru_bias_partial", "bg_gru_sequence_forward_group", "bg_gru_sequence_backward_group",
+    "bg_actor_sample_lstm", "bg_lstm_sequence_forward", "bg_lstm_sequence_backward", "bg_lstm_bias_partial",
     "bg_rnd_reward",
     "bg_last_error", "bg_version",
 ]
@@ -311,6 +317,10 @@ def load():
         "bg_gru_sequence_forward": (i32, [i32, i32, i32] + [vp] * 9),
         "bg_gru_sequence_backward": (i32, [i32, i32, i32] + [vp] * 9),
         "bg_gru_bias_partial": (i32, [i32, i32, vp, vp, vp, vp]),
+        "bg_actor_sample_lstm": (i32, [i32, vp, i32, C.POINTER(LstmDesc), i32, C.POINTER(MlpLayerDesc), vp, u64, u64] + [vp] * 8),
+        "bg_lstm_sequence_forward": (i32, [i32, i32, i32] + [vp] * 12),
+        "bg_lstm_sequence_backward": (i32, [i32, i32, i32] + [vp] * 9),
+        "bg_lstm_bias_partial": (i32, [i32, i32, vp, vp, vp]),
         "bg_gru_sequence_forward_group": (i32, [C.POINTER(GruForwardProblem), i32, i32, vp]),
         "bg_gru_sequence_backward_group": (i32, [C.POINTER(GruBackwardProblem), i32, i32, vp]),
         "bg_adam_step": (i32, [i32, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, vp, vp]),

@@ -31,7 +31,8 @@
 // two LDS tiles: the launch costs about the two stand-alone launches it replaces, without their two boundaries and the concatenation copy.
 //
 // bg_actor_sample_gru and bg_distill_act_gru (a recurrent student, T1.yaml distillation.student_memory; rsl_rl's recurrent `Distillation` student) put
-// a GRU cell in front of the network, on the same 16 rows and the same layer code: gru_rows, below.
+// a GRU cell in front of the network, on the same 16 rows and the same layer code: gru_rows, below.  bg_actor_sample_lstm (PPO on an LSTM actor,
+// algorithm.rnn_cell: "lstm") puts an LSTM cell there: actor_lstm_sample_kernel.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -39,6 +40,7 @@
 
 #include "bg_common.h"
 #include "bg_gru.h"
+#include "bg_lstm.h"
 #include "bg_rng.h"
 
 namespace {
@@ -92,8 +94,10 @@ __device__ __forceinline__ void first_layer(const float* __restrict__ W, const f
     }
 }
 
-// a layer of K inputs (a multiple of 128) and OUT outputs; neurons >= OUT (the 12-wide output layer's last tile) compute zeros that nobody reads
-template <int LDA, int LDO = LDA>
+// a layer of K inputs (a multiple of 128) and OUT outputs; neurons >= OUT (the 12-wide output layer's last tile) compute zeros that nobody reads.
+// ADD (the LSTM cell's h-side, actor_lstm_sample_kernel): the result is added onto the output tile instead of replacing it, without an activation.  A lane owns the
+// elements of `out` that first_layer's lane of the same wave owns, so a tile that first_layer has just written needs no barrier in between.
+template <int LDA, int LDO = LDA, bool ADD = false>
 __device__ __forceinline__ void layer(const float* __restrict__ W, const float* __restrict__ bv, int K, int OUT, bool act, const float* in, float* out,
                                       int wave, int lane) {
     const int r = lane & 15, kg = lane >> 4, tiles = (OUT + 15) / 16, cpt = K >> 7;
@@ -134,7 +138,10 @@ __device__ __forceinline__ void layer(const float* __restrict__ W, const float* 
         if (c == cpt - 1) {
             const f32x4 v = acc0 + acc1;
 #pragma unroll
-            for (int q = 0; q < 4; q++) out[(kg * 4 + q) * LDO + tile * 16 + r] = act ? elu(v[q]) : v[q];
+            for (int q = 0; q < 4; q++) {
+                if constexpr (ADD) out[(kg * 4 + q) * LDO + tile * 16 + r] += v[q];
+                else out[(kg * 4 + q) * LDO + tile * 16 + r] = act ? elu(v[q]) : v[q];
+            }
         }
 #pragma unroll
         for (int u = 0; u < 8; u++) cur[u] = nxt[u];
@@ -446,6 +453,82 @@ __global__ __launch_bounds__(256) void distill_act_gru_kernel(int N, int nb, con
     }
 }
 
+// ---- an LSTM cell in front of the trunk (algorithm.rnn_cell: "lstm", torch.nn.LSTMCell(47, H)): bg_actor_sample_lstm.  The two sides of a gate's
+// pre-activation simply add, so there is ONE gate tile [16][4H + 4]: first_layer's form without the ELU writes gi = x W_ih^T + b_ih into it and layer's
+// ADD form accumulates gh = h W_hh^T + b_hh onto it (two separate 4H tiles at H = 256 would need more than the CU's 160 kB).  The second state c is
+// elementwise and gets no LDS tile: the thread that computes element (row, column) of the gates reads its c_in element straight from memory, coalesced,
+// requested in front of the two GEMMs, and writes c_out.  h' goes to memory and, in place of h, is the input tile of the trunk, whose two activation
+// tiles lie over the gate tile once the gates are done.
+//   floats: max(16 (4H + 4), 2 x 16 (MAXW + 4)) + 16 (H + 4) + 16 x 52
+//   H = 128: 45 kB (MAXW = 256), 76 kB (512); H = 256: 86 kB (256 and 512), of the CU's 160 kB: three workgroups per CU at H = 128 with MAXW = 256, one
+//   at H = 256.
+// (this kernel's scalar fp32 arithmetic stays scalar: the attribute belongs to the device pass, the host pass does not know the feature)
+#ifdef __HIP_DEVICE_COMPILE__
+#define BG_NO_PACKED_FP32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define BG_NO_PACKED_FP32
+#endif
+template <int H, int MAXW>
+struct LstmLds {
+    static constexpr int LDA = MAXW + 4, LDG = 4 * H + 4, LDH = H + 4, LDX = KC + 4;  // row strides (floats), multiples of 4
+    static constexpr int TRUNK = 2 * MR * LDA, GT = MR * LDG;
+    static constexpr int A = GT > TRUNK ? GT : TRUNK, HT = MR * LDH, X = MR * LDX;
+    static constexpr int FLOATS = A + HT + X;
+};
+
+// h_in / h_out and c_in / c_out may be the same buffers: a workgroup reads its 16 rows of h in front of the first barrier and writes them behind the
+// second, an element of c is read and written by one thread, and no other workgroup touches the rows.  reset (may be nullptr): a row with a non-zero
+// entry reads both states as zero.
+template <int H, int MAXW>
+__global__ __launch_bounds__(256) BG_NO_PACKED_FP32 void actor_lstm_sample_kernel(int N, const float* __restrict__ obs, int stride, GruCell cell, ActorNet net,
+                                                                const float* __restrict__ logstd, uint64_t seed, uint32_t counter, const uint8_t* __restrict__ reset,
+                                                                const float* h_in, float* h_out, const float* c_in, float* c_out, float* __restrict__ mu_out,
+                                                                float* __restrict__ act_out) {
+    using L = LstmLds<H, MAXW>;
+    constexpr int EPT = MR * H / 256;  // a thread's elements of the [16][H] state tiles
+    __shared__ __attribute__((aligned(16))) float lds[L::FLOATS];
+    float *gt = lds, *ht = lds + L::A, *xt = ht + L::HT;
+    const int r0 = blockIdx.x * MR, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int k = threadIdx.x; k < MR * KC; k += blockDim.x) {
+        const int r = k / KC, c = k - r * KC;
+        xt[r * L::LDX + c] = (r0 + r < N && c < BG_NUM_OBS) ? obs[(size_t)(r0 + r) * stride + c] : 0.f;
+    }
+    float cv[EPT];
+#pragma unroll
+    for (int e = 0; e < EPT; e++) {
+        const int k = threadIdx.x + 256 * e, r = k / H, c = k - r * H, row = r0 + r;
+        const bool live = row < N && !(reset && reset[row]);
+        ht[r * L::LDH + c] = live ? h_in[(size_t)row * H + c] : 0.f;
+        cv[e] = live ? c_in[(size_t)row * H + c] : 0.f;
+    }
+    __syncthreads();
+    first_layer<L::LDX, L::LDG, false>(cell.W_ih, cell.b_ih, BG_NUM_OBS, 4 * H, xt, gt, wave, lane);
+    layer<L::LDH, L::LDG, true>(cell.W_hh, cell.b_hh, H, 4 * H, false, ht, gt, wave, lane);
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < EPT; e++) {
+        const int k = threadIdx.x + 256 * e, r = k / H, c = k - r * H, row = r0 + r;
+        const float* a = gt + r * L::LDG + c;
+        const bg::LstmGates s = bg::lstm_gates(a[0], a[H], a[2 * H], a[3 * H], cv[e]);
+        ht[r * L::LDH + c] = s.h;
+        if (row < N) {
+            h_out[(size_t)row * H + c] = s.h;
+            c_out[(size_t)row * H + c] = s.c;
+        }
+    }
+    __syncthreads();
+    float(*buf)[MR * L::LDA] = reinterpret_cast<float(*)[MR * L::LDA]>(lds);  // (over the gate tile, which nobody reads any more)
+    layer<L::LDH, L::LDA>(net.W[0], net.b[0], H, net.out[0], true, ht, buf[0], wave, lane);
+    __syncthreads();
+    int cur = 0;
+    for (int l = 1; l < net.n; l++) {
+        layer<L::LDA>(net.W[l], net.b[l], net.in[l], net.out[l], l + 1 < net.n, buf[cur], buf[cur ^ 1], wave, lane);
+        __syncthreads();
+        cur ^= 1;
+    }
+    sample<L::LDA, false>(buf[cur], N, r0, logstd, seed, counter, mu_out, act_out, false, 0.f, 0);
+}
+
 }  // namespace
 
 // The descriptors of one network -> ActorNet, with the width rules of the kernel; scan: the height-scan values behind the 47 H observations of a row
@@ -719,4 +802,28 @@ extern "C" int bg_distill_act_gru_own(int32_t N, const float* teacher_obs, int32
                                       float* teacher_mu, void* stream) {
     return distill_act_gru("bg_distill_act_gru_own", N, teacher_obs, teacher_stride, student_obs, student_stride, n_teacher, teacher, scan_points, gru, n_student, student,
                            student_logstd, seed, counter, beta, teacher_noise, reset, h_in, h_out, student_mu, actions, teacher_mu, stream);
+}
+
+// ---- the LSTM actor's entry point
+extern "C" int bg_actor_sample_lstm(int32_t N, const float* obs, int32_t obs_stride, const bg_lstm_desc* lstm, int32_t n_layers, const bg_mlp_layer_desc* layers,
+                                    const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, const float* c_in,
+                                    float* c_out, float* mu, float* actions, void* stream) {
+    const std::string who("bg_actor_sample_lstm");
+    if (N <= 0 || !obs || !layers || !logstd || !h_in || !h_out || !c_in || !c_out || !actions) return bg_set_error(-1, (who + ": bad argument").c_str());
+    if (obs_stride < BG_NUM_OBS) return bg_set_error(-1, (who + ": bad argument (obs_stride: at least the 47 columns the cell reads)").c_str());
+    if (!lstm || !lstm->W_ih || !lstm->W_hh || !lstm->b_ih || !lstm->b_hh) return bg_set_error(-1, (who + ": bad argument (lstm)").c_str());
+    if (lstm->in != BG_NUM_OBS) return bg_set_error(-4, (who + ": the cell takes one observation (lstm.in = 47)").c_str());
+    if (lstm->hidden != 128 && lstm->hidden != 256) return bg_set_error(-4, (who + ": unsupported lstm.hidden (128 or 256)").c_str());
+    if ((uintptr_t)lstm->W_hh & 15) return bg_set_error(-1, (who + ": lstm.W_hh must be 16-byte aligned").c_str());
+    const GruCell cell{lstm->W_ih, lstm->W_hh, lstm->b_ih, lstm->b_hh};  // (the four pointers; the layout is torch.nn.LSTMCell's, 4 hidden rows)
+    ActorNet net;
+    int maxw = 0;
+    if (const int rc = fill_net((who + " (trunk)").c_str(), n_layers, layers, 0, net, maxw, lstm->hidden)) return rc;
+    const int H = lstm->hidden;
+    const bool wide = maxw > 256;
+    const dim3 grid((N + MR - 1) / MR), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    BG_GRU_LAUNCH(actor_lstm_sample_kernel, , N, obs, obs_stride, cell, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, c_in, c_out, mu, actions);
+    HIP_OK(hipGetLastError());
+    return 0;
 }

@@ -12,7 +12,8 @@ each current exactly when written or stamped at the present value of the paramet
 frame stack of 47 H inputs).  With estimator.enabled a third network, `estimator` (47 H -> hidden -> 12), feeds the first E of its outputs to the
 actor behind the observations; the rollout runs both in one launch (bg_actor_sample_est).  An actor may be recurrent (`memory_hidden`: a distilled
 student of distillation.student_memory, or PPO's own under algorithm.rnn_hidden_size): a GRU cell `memory` in front of the actor, one launch per
-step as well (bg_actor_sample_gru), and GRUTrainer around the trunk's MLPTrainer in the update.
+step as well (bg_actor_sample_gru), and GRUTrainer around the trunk's MLPTrainer in the update; under algorithm.rnn_cell: "lstm" an LSTM cell
+(bg_actor_sample_lstm, LSTMTrainer).
 """
 import ctypes
 import math
@@ -824,6 +825,103 @@ class GRUTrainer:
         return [(self.dgi, self.x[:B], c.weight_ih.grad, 3 * H, self.kin, c.weight_ih.shape[1]), (self.dgh, self.h_prev[:B], c.weight_hh.grad, 3 * H, H, H)]
 
 
+class LSTMTrainer(GRUTrainer):
+    """GRUTrainer's interface around a torch.nn.LSTMCell (PPO on an LSTM actor, algorithm.rnn_cell: "lstm"): the same rollout side, the same passes,
+    the same deferred weight and bias gradients, so the Runner's mini-epoch code does not fork.  What differs is the cell:
+      the state     ONE tensor [2][N][H], h then c (`h0` here, the model's memory_state): the copies and the zeroing stay one op;
+      forward(x)    gi [B][4H] from bg_mlp_layer_forward on the padded W_ih, the recurrence as ONE launch (bg_lstm_sequence_forward), which also keeps
+                    c_prev and gates [B][5H] = i | f | g | o | tanh(c') for the backward pass;
+      backward()    dh_ext from the trunk's transposed first layer, the recurrence backwards as ONE launch (bg_lstm_sequence_backward) that leaves ONE
+                    gate gradient dg [B][4H] (the two sides of a pre-activation simply add: dgi == dgh), its column sums as ONE launch
+                    (bg_lstm_bias_partial) and two reduction descriptors on the same records, one per bias, for the update's deferred group;
+      the weight gradients (dg, x) and (dg, h_prev) join the grouped launch (pending_wgrad_problems).
+    No extra steps (a recurrent critic is a GRU's) and no grouped recurrences."""
+
+    def __init__(self, cell, trunk, T, N, clock=None, kin=None):
+        self.cell, self.trunk, self.T, self.N, self.H = cell, trunk, int(T), int(N), int(cell.hidden_size)
+        self.bias_partial = True
+        self.kin = int(kin or self.KIN)
+        if self.kin not in INPUT_PADS or self.kin < cell.weight_ih.shape[1]:
+            raise ValueError(f"LSTMTrainer: an input of {cell.weight_ih.shape[1]} columns padded to {self.kin} (one of {INPUT_PADS}, at least the cell's input)")
+        self.TF = self.T
+        B, H, dev = self.T * self.N, self.H, cell.weight_ih.device
+        self.B = self.BF = B
+        self.copies = WeightCopies([SimpleNamespace(weight=cell.weight_ih)], clock, self.kin)
+        new = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+        self.gi, self.gates, self.dg = new(B, 4 * H), new(B, 5 * H), new(B, 4 * H)
+        self.h_prev, self.c_prev, self.h, self.c, self.dh_ext = new(B, H), new(B, H), new(B, H), new(B, H), new(B, H)
+        self.h0 = new(2, self.N, H)                                                # the states entering the iteration, h then c (detached)
+        self.resets = torch.zeros(self.T, self.N, dtype=torch.uint8, device=dev)   # non-zero: both states entering step t of env n are zero
+        self._resets, self._h0 = self.resets, self.h0
+        self.next_state = None
+        self._zero_bias = new(H)
+        self._cs = new((B + 127) // 128 * 4 * H)  # one record [4H] per 128 rows
+        self.x = None
+        self._pending = False
+
+    def carry_state(self):
+        raise ValueError("LSTMTrainer: no extra steps, nothing to carry (a recurrent critic's cell is a GRU)")
+
+    def forward(self, x, h0=None, resets=None):
+        """h0 [2][N][H] / resets [T][N] uint8: the states the recurrence starts from and the reset flags it (and the backward pass behind it) reads,
+        where they are not this trainer's own."""
+        lib, st, p, c, H = _lib.load(), _lib.current_stream_ptr(), _lib.ptr, self.cell, self.H
+        self.x = x
+        h0, self._resets = self.h0 if h0 is None else h0, self.resets if resets is None else resets
+        if h0.shape != self.h0.shape or self._resets.shape != self.resets.shape or self._resets.dtype != torch.uint8 or not (h0.is_contiguous() and self._resets.is_contiguous()):
+            raise ValueError(f"LSTMTrainer.forward: h0 {tuple(h0.shape)} / resets {tuple(self._resets.shape)} are not contiguous [2][{self.N}][{H}] / uint8 [{self.T}][{self.N}]")
+        if x.shape != (self.B, self.kin) or not x.is_contiguous():
+            raise ValueError(f"LSTMTrainer.forward: x {tuple(x.shape)} is not contiguous [{self.B}][{self.kin}]")
+        self._h0 = h0
+        _lib.check(lib.bg_mlp_layer_forward(self.B, self.kin, 4 * H, p(x), p(self.copies.get("w0pad", 0)), p(c.bias_ih), p(self.gi), 0, st), "bg_mlp_layer_forward")
+        _lib.check(lib.bg_lstm_sequence_forward(self.T, self.N, H, p(self.gi), p(h0[0]), p(h0[1]), p(self._resets), p(c.weight_hh), p(c.bias_hh), p(self.h_prev),
+                                                p(self.c_prev), p(self.h), p(self.c), p(self.gates), st), "bg_lstm_sequence_forward")
+        return self.h
+
+    @staticmethod
+    def forward_group(jobs):
+        raise ValueError("LSTMTrainer: the grouped recurrences are the GRU's (bg_gru_sequence_forward_group)")
+
+    def backward(self, finishes=None):
+        """finishes (a list): receives the two descriptors of the bias gradients' reductions, for the caller's deferred group; None: they run here, as a
+        bg_reduce_group of their own."""
+        lib, st, p, c, H, tr = _lib.load(), _lib.current_stream_ptr(), _lib.ptr, self.cell, self.H, self.trunk
+        g1, l0 = tr.gin[1], tr.layers[0]  # dL/dz of the trunk's first layer [B][out], behind backward_hidden
+        _lib.check(lib.bg_mlp_layer_forward(self.B, l0.weight.shape[0], H, p(g1), p(tr.copies.get("wt", 0)), p(self._zero_bias), p(self.dh_ext), 0, st),
+                   "bg_mlp_layer_forward")
+        _lib.check(lib.bg_lstm_sequence_backward(self.T, self.N, H, p(self.dh_ext), p(self.gates), p(self.c_prev), p(self._resets), p(c.weight_hh), p(self.dg),
+                                                 None, None, st), "bg_lstm_sequence_backward")
+        self._pending = True
+        _lib.check(lib.bg_lstm_bias_partial(self.B, H, p(self.dg), p(self._cs), st), "bg_lstm_bias_partial")
+        fins = self.bias_finish()
+        if finishes is not None:
+            finishes.extend(fins)
+        else:
+            from .utils import reduce_group
+            reduce_group(fins)
+
+    @staticmethod
+    def backward_group(trainers, finishes=None):
+        raise ValueError("LSTMTrainer: the grouped recurrences are the GRU's (bg_gru_sequence_backward_group)")
+
+    def bias_finish(self):
+        """The two bg_reduce_problems behind bg_lstm_bias_partial: the records [ceil(B / 128)][4H] added up into bias_ih.grad and into bias_hh.grad."""
+        fins = []
+        for b in (self.cell.bias_ih, self.cell.bias_hh):
+            fin = _lib.ReduceProblem()
+            fin.partial, fin.groups, fin.record, fin.n_out = self._cs.data_ptr(), (self.B + 127) // 128, 4 * self.H, 4 * self.H
+            fin.out[0], fin.n[0] = b.grad.data_ptr(), 4 * self.H
+            fins.append(fin)
+        return fins
+
+    def pending_wgrad_problems(self):
+        """(G, A, dW, C_out, C_in (padded), C_in_real) of the cell's two weight gradients, for the grouped launch: both on the ONE gate gradient dg."""
+        if not self._pending:
+            return []
+        self._pending, c, H = False, self.cell, self.H
+        return [(self.dg, self.x, c.weight_ih.grad, 4 * H, self.kin, c.weight_ih.shape[1]), (self.dg, self.h_prev, c.weight_hh.grad, 4 * H, H, H)]
+
+
 class EstimatorActor(torch.nn.Module):
     """What export_model.py scripts for a checkpoint with a state estimator: actor(cat(x, estimator(x)[:, :E])) on rows x of 47 H observations -- the
     deploy contract stays "47 H floats in, 12 out"."""
@@ -841,20 +939,32 @@ class RecurrentActor(torch.nn.Module):
     a buffer this module owns (zero at first and again whenever B changes), by one GRU step and returns the actor's mean on the new state; reset()
     (an exported method) zeroes it: call it where the robot's episode starts."""
 
+    __constants__ = ["lstm"]  # (the cell type selects the branch when the module is scripted)
+
     def __init__(self, memory, actor):
         super().__init__()
         self.memory, self.actor, self.hidden = memory, actor, int(memory.hidden_size)
+        self.lstm = isinstance(memory, torch.nn.LSTMCell)  # an LSTM actor (algorithm.rnn_cell: "lstm") carries a second state, c
         self.register_buffer("h", torch.zeros(0, self.hidden))
+        if self.lstm:
+            self.register_buffer("c", torch.zeros(0, self.hidden))
 
     def forward(self, x):
         if self.h.shape[0] != x.shape[0]:
             self.h = torch.zeros(x.shape[0], self.hidden, dtype=x.dtype, device=x.device)
-        self.h = self.memory(x, self.h)
+            if self.lstm:
+                self.c = torch.zeros(x.shape[0], self.hidden, dtype=x.dtype, device=x.device)
+        if self.lstm:
+            self.h, self.c = self.memory(x, (self.h, self.c))
+        else:
+            self.h = self.memory(x, self.h)
         return self.actor(self.h)
 
     @torch.jit.export
     def reset(self):
         self.h = torch.zeros_like(self.h)
+        if self.lstm:
+            self.c = torch.zeros_like(self.c)
 
 
 class ActorCritic(torch.nn.Module):
@@ -863,6 +973,8 @@ class ActorCritic(torch.nn.Module):
     observations and the first estimator_cols = E of the estimator's 12 outputs.  num_obs stays the env's row (47 H): what callers pass as `obs`.
     memory_hidden = H > 0 (a recurrent student, distillation.student_memory; 0 = without, today's parameters in today's order): a
     torch.nn.GRUCell(num_obs, H) `memory`, registered last, and the actor takes the H values of its new state instead of the observations.
+    memory_cell = "lstm" (algorithm.rnn_cell; "gru" = today's cell): `memory` is a torch.nn.LSTMCell(num_obs, H) in the same place; the state that
+    sample_actions carries is then ONE tensor [2][N][H], h then c.
     critic_memory_hidden = H > 0 (a recurrent critic, algorithm.rnn_critic; 0 = without, today's parameters in today's order): a
     torch.nn.GRUCell(num_obs + num_privileged_obs, H) `critic_memory`, registered behind `memory`, and the critic's first layer takes the H values of
     its state instead of the rows.  Its state belongs to whoever walks the rows (the runner's update); est_value on single rows raises.
@@ -870,9 +982,14 @@ class ActorCritic(torch.nn.Module):
     today's draws of the global generator): two more networks, `rnd_predictor` and `rnd_target`, registered last; nothing of this class evaluates them."""
 
     def __init__(self, num_act, num_obs, num_privileged_obs, actor_hidden=ACTOR_HIDDEN, critic_hidden=CRITIC_HIDDEN, estimator_hidden=None, estimator_cols=0,
-                 memory_hidden=0, critic_memory_hidden=0, rnd=None):
+                 memory_hidden=0, critic_memory_hidden=0, rnd=None, memory_cell="gru"):
         super().__init__()
         self.memory_hidden = int(memory_hidden or 0)
+        if memory_cell not in ("gru", "lstm"):
+            raise ValueError(f"memory_cell = {memory_cell!r}: \"gru\" or \"lstm\"")
+        self.memory_cell = memory_cell if self.memory_hidden else "gru"
+        if self.memory_cell == "lstm" and critic_memory_hidden:
+            raise ValueError("memory_cell = \"lstm\": a recurrent critic (critic_memory_hidden) is not supported beside an LSTM actor")
         self.critic_memory_hidden = int(critic_memory_hidden or 0)
         if self.memory_hidden and estimator_hidden is not None:
             raise ValueError("memory_hidden: a recurrent actor with a state estimator is not supported")
@@ -887,7 +1004,7 @@ class ActorCritic(torch.nn.Module):
         if estimator_hidden is not None:
             self.estimator = _mlp(num_obs, self.estimator_hidden, _lib.NUM_DOFS)
         if self.memory_hidden:
-            self.memory = torch.nn.GRUCell(num_obs, self.memory_hidden)
+            self.memory = (torch.nn.LSTMCell if self.memory_cell == "lstm" else torch.nn.GRUCell)(num_obs, self.memory_hidden)
         if self.critic_memory_hidden:
             self.critic_memory = torch.nn.GRUCell(num_obs + num_privileged_obs, self.critic_memory_hidden)
         if rnd is not None:
@@ -936,9 +1053,11 @@ class ActorCritic(torch.nn.Module):
             self._memory_state.zero_()
 
     def memory_state(self, N, device):
-        """The hidden state [N][H] that sample_actions advances in place: created (zero) on first use and when N or the device changes."""
-        if self._memory_state is None or self._memory_state.shape[0] != N or self._memory_state.device != torch.device(device):
-            self._memory_state = torch.zeros(N, self.memory_hidden, dtype=torch.float32, device=device)
+        """The hidden state [N][H] (an LSTM cell: [2][N][H], h then c) that sample_actions advances in place: created (zero) on first use and when N or
+        the device changes."""
+        shape = (2, N, self.memory_hidden) if self.memory_cell == "lstm" else (N, self.memory_hidden)
+        if self._memory_state is None or tuple(self._memory_state.shape) != shape or self._memory_state.device != torch.device(device):
+            self._memory_state = torch.zeros(*shape, dtype=torch.float32, device=device)
         return self._memory_state
 
     def act(self, obs):
@@ -1043,9 +1162,9 @@ class ActorCritic(torch.nn.Module):
         return actions_out
 
     def gru_descriptor(self):
-        """bg_gru_desc of `memory` on its current parameter storage."""
+        """bg_gru_desc (an LSTM cell: bg_lstm_desc) of `memory` on its current parameter storage."""
         m = self.memory
-        return _lib.GruDesc(m.weight_ih.data_ptr(), m.weight_hh.data_ptr(), m.bias_ih.data_ptr(), m.bias_hh.data_ptr(), m.input_size, m.hidden_size)
+        return (_lib.LstmDesc if self.memory_cell == "lstm" else _lib.GruDesc)(m.weight_ih.data_ptr(), m.weight_hh.data_ptr(), m.bias_ih.data_ptr(), m.bias_hh.data_ptr(), m.input_size, m.hidden_size)
 
     def _sample_actions_gru(self, obs, actions_out, seed, counter, mu_out, scan, reset, lin, w):
         """sample_actions of a model with memory: ONE launch (bg_actor_sample_gru) advances the state this model keeps and samples from the actor on it."""
@@ -1068,6 +1187,11 @@ class ActorCritic(torch.nn.Module):
         if key != self._gru_key:
             self._gru_descs, self._gru_key = (self.gru_descriptor(), layer_descriptors(lin)), key
         gd, layers = self._gru_descs
+        if self.memory_cell == "lstm":  # ONE launch as well (bg_actor_sample_lstm), both states of the one tensor [2][N][H] advanced in place
+            _lib.check(_lib.load().bg_actor_sample_lstm(N, _lib.ptr(obs), obs.shape[-1], gd, len(lin), layers, _lib.ptr(self.logstd), int(seed), int(counter),
+                                                        _lib.ptr(reset), _lib.ptr(h[0]), _lib.ptr(h[0]), _lib.ptr(h[1]), _lib.ptr(h[1]), _lib.ptr(mu_out),
+                                                        _lib.ptr(actions_out), _lib.current_stream_ptr()), "bg_actor_sample_lstm")
+            return actions_out
         _lib.check(_lib.load().bg_actor_sample_gru(N, _lib.ptr(obs), obs.shape[-1], gd, len(lin), layers, _lib.ptr(self.logstd), int(seed), int(counter),
                                                    _lib.ptr(reset), _lib.ptr(h), _lib.ptr(h), _lib.ptr(mu_out), _lib.ptr(actions_out), _lib.current_stream_ptr()),
                    "bg_actor_sample_gru")

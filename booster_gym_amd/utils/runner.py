@@ -70,7 +70,7 @@ from .buffer import ExperienceBuffer
 from .estimator import EST_WIDTH, EstimatorTrainer, check_estimator_checkpoint, estimator_cfg, estimator_enabled
 from .config import load_cfg
 from .obs_norm import ObsNormalizer, check_checkpoint, normalization_cfg
-from .model import (ACTOR_HIDDEN, CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, GRUTrainer, MLPTrainer, NetPlan, WeightClock, check_hidden, hidden_of, pad_input,
+from .model import (ACTOR_HIDDEN, CRITIC_HIDDEN, ActorCritic, GroupedWeightGrad, GRUTrainer, LSTMTrainer, MLPTrainer, NetPlan, WeightClock, check_hidden, hidden_of, pad_input,
                     plan_network, wgrad_products)
 from .optim import FlatAdam
 from .parallel import DataParallel
@@ -132,7 +132,8 @@ def rnn_hidden_size_of(cfg, world_size=1):
         raise ValueError(f"algorithm.rnn_hidden_size must be 0, 128 or 256 (the width of the GRU cell in front of the actor; 0 or absent: none), got {H!r}")
     kind = alg.get("rnn_type")
     if kind is not None and kind != "gru":
-        raise ValueError(f"algorithm.rnn_type = {kind!r}: the cell of algorithm.rnn_hidden_size is a GRU; the key, if present, must be \"gru\"")
+        raise ValueError(f"algorithm.rnn_type = {kind!r}: the cell of algorithm.rnn_hidden_size is a GRU; the key, if present, must be \"gru\" (an LSTM cell is "
+                         "algorithm.rnn_cell: \"lstm\")")
     if not H:
         return 0
     mem = alg.get("actor_memory", 0) or 0
@@ -151,6 +152,35 @@ def rnn_hidden_size_of(cfg, world_size=1):
             raise ValueError(f"algorithm.rnn_hidden_size = {H} is not supported with {what} (a recurrent actor reads the newest single observation, "
                              "on one rank, its update on the whole batch as sequences)")
     return H
+
+
+RNN_CELLS = ("gru", "lstm")  # the cells of algorithm.rnn_cell
+
+
+def rnn_cell_of(cfg, world_size=1):
+    """algorithm.rnn_cell (an addition of this build; absent, null or "gru" = the GRU cell: the shipped yaml does not list it) as the cell in front of an
+    actor that PPO trains under algorithm.rnn_hidden_size: "gru" or "lstm" (legged_gym / rsl_rl's ActorCriticRecurrent default, torch.nn.LSTMCell; the
+    key is not rnn_type, whose one value stays "gru").  Read only together with a non-zero algorithm.rnn_hidden_size: without one the result is
+    "gru" whatever the key holds.  Pure.  ValueError naming the key for any other value and, naming both keys, for "lstm" with algorithm.rnn_type:
+    "gru", with algorithm.rnn_critic: true (the critic's cell is a GRU and its recurrences are grouped with the actor's) and with
+    runner.num_env_mini_batches above 1 (bg_gather_sequences has no stream for c0); rnn_hidden_size_of's own refusals apply as well."""
+    alg = cfg.get("algorithm", {}) or {}
+    if not rnn_hidden_size_of(cfg, world_size):
+        return "gru"
+    cell = alg.get("rnn_cell")
+    cell = "gru" if cell is None else cell
+    if not isinstance(cell, str) or cell not in RNN_CELLS:
+        raise ValueError(f"algorithm.rnn_cell must be \"gru\" or \"lstm\" (the cell of algorithm.rnn_hidden_size; absent: \"gru\"), got {cell!r}")
+    if cell == "gru":
+        return cell
+    K = (cfg.get("runner", {}) or {}).get("num_env_mini_batches", 1) or 1
+    refused = (("algorithm.rnn_type: \"gru\" (the two keys name two cells: drop one)", alg.get("rnn_type") == "gru"),
+               ("algorithm.rnn_critic: true (the critic's cell is a GRU)", alg.get("rnn_critic") is True),
+               ("runner.num_env_mini_batches above 1 (the sequence gather has no stream for the cell state)", not isinstance(K, bool) and isinstance(K, int) and K > 1))
+    for what, on in refused:
+        if on:
+            raise ValueError(f"algorithm.rnn_cell = \"lstm\" is not supported with {what}")
+    return cell
 
 
 def rnn_critic_of(cfg, world_size=1):
@@ -176,12 +206,14 @@ def rnn_critic_of(cfg, world_size=1):
 def checkpoint_memory_overrides(checkpoint):
     """{"algorithm.rnn_hidden_size": H} for a loaded checkpoint dict whose model carries memory.* and that is no student's (no "distillation" entry: an
     actor trained under algorithm.rnn_hidden_size; a student re-enters under distill.checkpoint_student_overrides), H from memory.weight_hh; None for
-    every other checkpoint.  With critic_memory.* in the model (algorithm.rnn_critic) also "algorithm.rnn_critic": True.  What evaluate.py applies so
+    every other checkpoint.  With 4H rows in memory.weight_hh (an LSTM cell) also "algorithm.rnn_cell": "lstm".  With critic_memory.* in the model (algorithm.rnn_critic) also "algorithm.rnn_critic": True.  What evaluate.py applies so
     that such a checkpoint evaluates without editing the yaml."""
     sd = checkpoint.get("model") or {}
     if checkpoint.get("distillation") is not None or "memory.weight_hh" not in sd:
         return None
     over = {"algorithm.rnn_hidden_size": int(sd["memory.weight_hh"].shape[1])}
+    if sd["memory.weight_hh"].shape[0] == 4 * sd["memory.weight_hh"].shape[1]:  # torch.nn.LSTMCell's four gates (a GRU cell has three)
+        over["algorithm.rnn_cell"] = "lstm"
     if "critic_memory.weight_hh" in sd:
         over["algorithm.rnn_critic"] = True
     return over
@@ -452,6 +484,8 @@ class Runner:
                              "under play.py, evaluate.py and export_model.py; PPO on a recurrent actor (from scratch, or fine-tuning that student) is "
                              f"algorithm.rnn_hidden_size: {self._memory} (training a recurrent student: distill.py --student_memory)")
         self._memory = self._memory or self._rnn
+        # algorithm.rnn_cell: the cell of algorithm.rnn_hidden_size, "gru" (also without a recurrent actor) or "lstm"
+        self._rnn_cell = rnn_cell_of(self.cfg, self.world_size)
         # algorithm.rnn_critic: a second cell of the same width in front of the critic; 0 = a feed-forward critic, the one switch the branches below read
         self._rnn_critic = rnn_critic_of(self.cfg, self.world_size)
         if self._rnn and not test and (int((self.cfg.get("parallel", {}) or {}).get("gemm_split", 0) or 0) or MLPTrainer.SPLIT):
@@ -474,7 +508,7 @@ class Runner:
             self._act_mirror = (act_src.tolist(), act_sign.tolist())
         est_args = {} if self._est is None else {"estimator_hidden": self._est.hidden, "estimator_cols": len(self._est.targets)}
         if self._memory:
-            est_args = {"memory_hidden": self._memory}
+            est_args = {"memory_hidden": self._memory, "memory_cell": self._rnn_cell}
         if self._rnn_critic:
             est_args["critic_memory_hidden"] = self._rnn_critic
         if self._rnd is not None:
@@ -592,7 +626,10 @@ class Runner:
         # actor (or a recurrent one that only plays), the one switch rollout() and update() read.  The state itself is the model's (sample_actions).
         self._mem_tr = None
         if self._rnn and not test:
-            self._mem_tr = GRUTrainer(self.model.memory, self._actor_tr, T, N, clock=self._clock, bias_partial=True)
+            if self._rnn_cell == "lstm":  # the same interface around the LSTM's kernels (model.LSTMTrainer)
+                self._mem_tr = LSTMTrainer(self.model.memory, self._actor_tr, T, N, clock=self._clock)
+            else:
+                self._mem_tr = GRUTrainer(self.model.memory, self._actor_tr, T, N, clock=self._clock, bias_partial=True)
             self._last_dones = torch.zeros(N, dtype=torch.uint8, device=dev)
         # algorithm.rnn_critic: the second cell around the critic's trunk.  Its forward pass walks T + 1 steps (the row after the last step gives
         # last_values) from a state that no rollout launch advances: GRUTrainer.carry_state.  None = a feed-forward critic
@@ -725,6 +762,11 @@ class Runner:
                              + f", the config has algorithm.actor_memory = {getattr(self, '_memory', 0)}: set algorithm.actor_memory to {ck_mem}"
                              + (" (a student of distillation.student_memory, or an actor trained under algorithm.rnn_hidden_size, the key to train it "
                                 "further under; evaluate.py and export_model.py set the width from the checkpoint)" if ck_mem else ""))
+        ck_cell = "lstm" if ck_mem and model_dict["model"]["memory.weight_hh"].shape[0] == 4 * ck_mem else "gru"
+        if ck_mem and ck_cell != getattr(self, "_rnn_cell", "gru"):
+            raise ValueError(f"checkpoint {ck} has {'an LSTM' if ck_cell == 'lstm' else 'a GRU'} cell (memory.weight_hh of {model_dict['model']['memory.weight_hh'].shape[0]} "
+                             f"rows), the config has algorithm.rnn_cell = {getattr(self, '_rnn_cell', 'gru')!r}: set algorithm.rnn_cell to \"{ck_cell}\" "
+                             "(evaluate.py and export_model.py set it from the checkpoint)")
         ck_cmem = int(model_dict["model"]["critic_memory.weight_hh"].shape[1]) if "critic_memory.weight_hh" in model_dict["model"] else 0
         # (a recurrent student re-entering for fine-tuning carries an UNTRAINED feed-forward critic: under algorithm.rnn_critic the critic built here,
         # cell and trunk, stays as initialised and the student's critic.* is not loaded)

@@ -41,6 +41,8 @@ if __name__ == "__main__":
     # distillation.student_memory: a GRU cell `memory` reads the observation and the actor reads the cell's state
     if "memory.weight_ih" in sd:
         est_args = {"memory_hidden": int(sd["memory.weight_hh"].shape[1])}
+        if sd["memory.weight_hh"].shape[0] == 4 * sd["memory.weight_hh"].shape[1]:  # algorithm.rnn_cell: "lstm" (four gates; a GRU cell has three)
+            est_args["memory_cell"] = "lstm"
         num_obs = int(sd["memory.weight_ih"].shape[1])
     num_priv = int(sd["critic.0.weight"].shape[1]) - num_obs
     # algorithm.rnn_critic: a second cell `critic_memory` reads the critic's row and the critic its state; loaded with the rest, never exported
@@ -78,9 +80,9 @@ if __name__ == "__main__":
     out = os.path.join("deploy", "models", f"{args.task}.pt")
     if model.memory_hidden:
         module = RecurrentActor(model.memory, model.actor)
-        print("Recurrent actor (GRU cell of width {}): the exported module is STATEFUL.  forward(obs [B][{}]) -> actions [B][12] advances its hidden state by "
+        print("Recurrent actor ({} cell of width {}): the exported module is STATEFUL.  forward(obs [B][{}]) -> actions [B][12] advances its hidden state by "
               "one step: call it once per control step, on the newest observation only.  The state is a buffer of the module, zero at first and "
-              "re-created zero whenever B changes; call reset() where an episode starts.".format(model.memory_hidden, num_obs))
+              "re-created zero whenever B changes; call reset() where an episode starts.".format("LSTM" if model.memory_cell == "lstm" else "GRU", model.memory_hidden, num_obs))
     else:
         module = EstimatorActor(model.actor, model.estimator, model.estimator_cols) if model.has_estimator else model.actor
     torch.jit.script(module).save(out)

@@ -566,6 +566,41 @@ int bg_gru_sequence_backward_group(const bg_gru_backward_problem* problems, int3
  * record = n_out = 6H, out[0] = b_ih's gradient, out[1] = b_hh's, n = 3H each, in a bg_reduce_group / bg_update_tail.  B >= 1; H = 128 or 256 (else -4);
  * the three pointers 16-byte aligned (-1). */
 int bg_gru_bias_partial(int32_t B, int32_t H, const float* dgi, const float* dgh, float* records, void* stream);
+/* PPO on an LSTM actor (T1.yaml algorithm.rnn_cell: "lstm"; legged_gym / rsl_rl's ActorCriticRecurrent with its default cell): an LSTM cell in
+ * torch.nn.LSTMCell's layout and gate order i | f | g | o, W_ih [4 hidden][in], W_hh [4 hidden][hidden] (16-byte aligned), b_ih / b_hh [4 hidden]:
+ *   p = x W_ih^T + b_ih + h W_hh^T + b_hh, i = sigmoid(p_i), f = sigmoid(p_f), g = tanh(p_g), o = sigmoid(p_o), c' = f c + i g, h' = o tanh(c').
+ * in = 47 (the newest single observation), hidden = 128 or 256; anything else is -4. */
+typedef struct bg_lstm_desc {
+    const float *W_ih, *W_hh, *b_ih, *b_hh;
+    int32_t in, hidden;
+} bg_lstm_desc;
+/* bg_actor_sample_gru with that cell: h = h_in, c = c_in [N][hidden] (both read as zero where reset [N] (uint8, may be NULL) is non-zero), h' to h_out,
+ * c' to c_out, the trunk `layers` (layers[0].in = hidden) on h': mu [N][12] (may be NULL), actions = mu + exp(logstd) n with bg_actor_sample_mlp's
+ * noise (the same stream).  h_in == h_out and c_in == c_out are allowed.  Nothing is written past row N.  Violations: -1 / -4 with a message, before
+ * any launch. */
+int bg_actor_sample_lstm(int32_t N, const float* obs, int32_t obs_stride, const bg_lstm_desc* lstm, int32_t n_layers, const bg_mlp_layer_desc* layers,
+                         const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, const float* c_in,
+                         float* c_out, float* mu, float* actions, void* stream);
+/* The recurrence of that actor's update over T steps as ONE launch each way (csrc/bg_lstm.hip); H = 128 or 256, any N >= 1, T >= 1; a workgroup owns 16
+ * envs and walks the steps itself, h in an LDS tile, c in registers; W_hh [4H][H] (16-byte aligned) streams from L2.
+ * Forward: gi [T][N][4H] the x-side pre-activations (b_ih included), h0 / c0 [N][H] the states entering step 0 (NULL: zero), reset [T][N] (uint8, NULL:
+ * none): non-zero = both states entering step t are zero.  Out: h_prev, c_prev [T][N][H] the states entering each step after the reset, h, c [T][N][H]
+ * the new states, gates [T][N][5H] = i | f | g | o | tanh(c').  Deterministic; nothing is written past row N of any step. */
+int bg_lstm_sequence_forward(int32_t T, int32_t N, int32_t H, const float* gi, const float* h0, const float* c0, const uint8_t* reset, const float* W_hh,
+                             const float* b_hh, float* h_prev, float* c_prev, float* h, float* c, float* gates, void* stream);
+/* Back-propagation through those T steps from dh_ext [T][N][H] = dL/dh[t] of whatever reads h[t]; walks t = T - 1 .. 0 with carried dh and dc (zero at
+ * T - 1):  dh = dh_ext[t] + carry_h, do = dh tanh_c, dc = carry_c + dh o (1 - tanh_c^2), di = dc g, dg_ = dc i, df = dc c_prev,
+ *   dg[t] = [di i (1 - i) | df f (1 - f) | dg_ (1 - g^2) | do o (1 - o)] ([T][N][4H]: the gradient of BOTH sides' pre-activations),
+ *   carry_c = dc f, carry_h = dg[t] W_hh, both zero for a row with reset[t].
+ * dh0, dc0 [N][H] (each may be NULL): the carries left after step 0.  Deterministic. */
+int bg_lstm_sequence_backward(int32_t T, int32_t N, int32_t H, const float* dh_ext, const float* gates, const float* c_prev, const uint8_t* reset,
+                              const float* W_hh, float* dg, float* dh0, float* dc0, void* stream);
+/* The cell's bias gradients without their finish: ONE launch in which workgroup g sums rows [128 g, min(128 g + 128, B)) of dg ([B][4H]) down their columns
+ * and writes record g of `records` ([ceil(B / 128)][4H] floats).  Rows at or beyond B are never read, nothing is written past record ceil(B / 128); fixed
+ * order, no atomics: deterministic.  b_ih's and b_hh's gradients are the same sums: the finish is two bg_reduce_problems on the same records (partial =
+ * records, groups = ceil(B / 128), record = n_out = n[0] = 4H), out[0] = b_ih's gradient in one and b_hh's in the other.  B >= 1; H = 128 or 256 (else
+ * -4); both pointers 16-byte aligned (-1). */
+int bg_lstm_bias_partial(int32_t B, int32_t H, const float* dg, float* records, void* stream);
 /* Fused global-norm clip + Adam over one flat parameter buffer (runner.py:162-165); lr is read from device memory
  * so the KL-adaptive schedule (runner.py:174-180) needs no host sync.  gnorm_scratch [1] device float64. */
 int bg_adam_step(int32_t n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const float* lr_device, int32_t step,

@@ -50,8 +50,8 @@ def load_estimator(path):
 
 
 def load_memory(path):
-    """The GRU cell in front of a recurrent actor (algorithm.rnn_hidden_size, or a student of distillation.student_memory: "memory.*" in the
-    checkpoint's model) as a GRUMemory, or None: the actor then reads the cell's state instead of the observation."""
+    """The cell (GRU, or LSTM under algorithm.rnn_cell: "lstm": read from the shapes) in front of a recurrent actor (algorithm.rnn_hidden_size, or a student of distillation.student_memory: "memory.*" in the
+    checkpoint's model) as a GRUMemory / LSTMMemory, or None: the actor then reads the cell's state instead of the observation."""
     if path.endswith(".npz"):
         return None
     import torch
@@ -59,7 +59,30 @@ def load_memory(path):
     sd = torch.load(path, map_location="cpu", weights_only=True)["model"]
     if "memory.weight_ih" not in sd:
         return None
-    return GRUMemory(*[sd[f"memory.{k}"].numpy() for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")])
+    lstm = sd["memory.weight_hh"].shape[0] == 4 * sd["memory.weight_hh"].shape[1]  # an LSTM cell (algorithm.rnn_cell: "lstm"): four gates
+    return (LSTMMemory if lstm else GRUMemory)(*[sd[f"memory.{k}"].numpy() for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")])
+
+
+class LSTMMemory:
+    """The deploy side of an LSTM actor (algorithm.rnn_cell: "lstm"): torch.nn.LSTMCell's equations (gate order i | f | g | o) in float64 on one row,
+    both states zero at the start and after reset().  GRUMemory's interface."""
+
+    def __init__(self, weight_ih, weight_hh, bias_ih, bias_hh):
+        self.w_ih, self.w_hh, self.b_ih, self.b_hh = (np.asarray(t, dtype=np.float64) for t in (weight_ih, weight_hh, bias_ih, bias_hh))
+        self.hidden = int(self.w_hh.shape[1])
+        self.reset()
+
+    def reset(self):
+        self.h, self.c = np.zeros(self.hidden), np.zeros(self.hidden)
+
+    def step(self, x):
+        """One step on the newest single observation x; returns the new state h [hidden] (h and c are kept: the next step starts from them)."""
+        H, sig = self.hidden, lambda v: 1.0 / (1.0 + np.exp(-v))
+        p = self.w_ih @ np.asarray(x, dtype=np.float64) + self.b_ih + self.w_hh @ self.h + self.b_hh
+        i, f, g, o = sig(p[:H]), sig(p[H : 2 * H]), np.tanh(p[2 * H : 3 * H]), sig(p[3 * H :])
+        self.c = f * self.c + i * g
+        self.h = o * np.tanh(self.c)
+        return self.h
 
 
 class GRUMemory:
