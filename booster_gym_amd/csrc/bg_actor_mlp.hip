@@ -32,7 +32,8 @@
 //
 // bg_actor_sample_gru and bg_distill_act_gru (a recurrent student, T1.yaml distillation.student_memory; rsl_rl's recurrent `Distillation` student) put
 // a GRU cell in front of the network, on the same 16 rows and the same layer code: gru_rows, below.  bg_actor_sample_lstm (PPO on an LSTM actor,
-// algorithm.rnn_cell: "lstm") puts an LSTM cell there: actor_lstm_sample_kernel.
+// algorithm.rnn_cell: "lstm") puts an LSTM cell there: lstm_rows, which bg_distill_act_lstm (distillation.student_cell: "lstm") runs in the student's half
+// of the split grid, on an LDS block that both halves share.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -476,19 +477,20 @@ struct LstmLds {
     static constexpr int FLOATS = A + HT + X;
 };
 
+// One workgroup's 16 rows through the cell and the trunk: the body of actor_lstm_sample_kernel and of distill_act_lstm_kernel's student half (its MIX
+// form: sample's DAgger choice), so that half computes what the stand-alone launch does on the same operands, bit for bit.
 // h_in / h_out and c_in / c_out may be the same buffers: a workgroup reads its 16 rows of h in front of the first barrier and writes them behind the
 // second, an element of c is read and written by one thread, and no other workgroup touches the rows.  reset (may be nullptr): a row with a non-zero
 // entry reads both states as zero.
-template <int H, int MAXW>
-__global__ __launch_bounds__(256) BG_NO_PACKED_FP32 void actor_lstm_sample_kernel(int N, const float* __restrict__ obs, int stride, GruCell cell, ActorNet net,
-                                                                const float* __restrict__ logstd, uint64_t seed, uint32_t counter, const uint8_t* __restrict__ reset,
-                                                                const float* h_in, float* h_out, const float* c_in, float* c_out, float* __restrict__ mu_out,
-                                                                float* __restrict__ act_out) {
+template <int H, int MAXW, bool MIX>
+__device__ __forceinline__ void lstm_rows(float* lds, int N, int r0, const float* __restrict__ obs, int stride, const GruCell& cell, const ActorNet& net,
+                                          const float* __restrict__ logstd, uint64_t seed, uint32_t counter, const uint8_t* __restrict__ reset, const float* h_in,
+                                          float* h_out, const float* c_in, float* c_out, float* __restrict__ mu_out, float* __restrict__ act_out, float beta,
+                                          int teacher_noise) {
     using L = LstmLds<H, MAXW>;
     constexpr int EPT = MR * H / 256;  // a thread's elements of the [16][H] state tiles
-    __shared__ __attribute__((aligned(16))) float lds[L::FLOATS];
     float *gt = lds, *ht = lds + L::A, *xt = ht + L::HT;
-    const int r0 = blockIdx.x * MR, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int k = threadIdx.x; k < MR * KC; k += blockDim.x) {
         const int r = k / KC, c = k - r * KC;
         xt[r * L::LDX + c] = (r0 + r < N && c < BG_NUM_OBS) ? obs[(size_t)(r0 + r) * stride + c] : 0.f;
@@ -526,7 +528,52 @@ __global__ __launch_bounds__(256) BG_NO_PACKED_FP32 void actor_lstm_sample_kerne
         __syncthreads();
         cur ^= 1;
     }
-    sample<L::LDA, false>(buf[cur], N, r0, logstd, seed, counter, mu_out, act_out, false, 0.f, 0);
+    sample<L::LDA, MIX>(buf[cur], N, r0, logstd, seed, counter, mu_out, act_out, false, beta, teacher_noise);
+}
+
+template <int H, int MAXW>
+__global__ __launch_bounds__(256) BG_NO_PACKED_FP32 void actor_lstm_sample_kernel(int N, const float* __restrict__ obs, int stride, GruCell cell, ActorNet net,
+                                                                const float* __restrict__ logstd, uint64_t seed, uint32_t counter, const uint8_t* __restrict__ reset,
+                                                                const float* h_in, float* h_out, const float* c_in, float* c_out, float* __restrict__ mu_out,
+                                                                float* __restrict__ act_out) {
+    __shared__ __attribute__((aligned(16))) float lds[LstmLds<H, MAXW>::FLOATS];
+    lstm_rows<H, MAXW, false>(lds, N, blockIdx.x * MR, obs, stride, cell, net, logstd, seed, counter, reset, h_in, h_out, c_in, c_out, mu_out, act_out, 0.f, 0);
+}
+
+// ---- an LSTM student (distillation.student_cell: "lstm"): bg_distill_act_lstm, bg_distill_act_lstm_own.  distill_act_gru_kernel's split grid, the DAgger
+// choice a template flag again, but not its LDS plan: there the cell's four tiles (gi | gh | h | x) are so much larger than the teacher's two that the
+// teacher's half simply takes the front of the block.  Here the two halves are of one size and of different shapes, and ONE block serves both:
+//   the student's half (workgroups [nb, 2 nb)), lstm_rows:     [ gate tile 16 (4H + 4), later the trunk's two tiles | h 16 (H + 4) | x 16 x 52 ]
+//   the teacher's half (workgroups [0, nb)), actor_rows' pieces: [ tile 0: the row, up to 480 columns | tile 1 ], 16 (MAXW + 4) floats each,
+// the teacher's two tiles over region A = max(16 (4H + 4), 2 x 16 (MAXW + 4)) floats, which the student's trunk needs in any case; h and x behind it stay
+// unused in a teacher's workgroup.  Nothing is added for the teacher: the launch's LDS is LstmLds<H, MAXW>::FLOATS, bg_actor_sample_lstm's, bytes
+//   H = 128: 45,056 (MAXW = 256), 77,824 (512); H = 256: 85,760 (256), 86,016 (512)
+// against distill_act_gru_kernel's 68 / 100 / 116 / 132 kB: three workgroups per CU at H = 128 / MAXW = 256 where the GRU launch has two, and at
+// H = 256 one workgroup of either half with 74 kB of the CU's 160 kB to spare (the static_assert below holds every form to the CU).  The wide form is
+// taken where either network has a hidden layer above 256 or the teacher's row tile does not fit 256 columns (host), as in the GRU launch.
+// Without packed fp32 arithmetic, as actor_lstm_sample_kernel: the student's half then has that kernel's instructions on the same operands; the
+// teacher's half is MFMAs, scalar loads and expm1f, which have no packed form to lose.
+// state_in / state_out: h = [0][N][H], c = [1][N][H] of the one tensor [2][N][H]; they may be the same buffer (lstm_rows' rule).
+template <int H, int MAXW, bool MIX>
+__global__ __launch_bounds__(256) BG_NO_PACKED_FP32 void distill_act_lstm_kernel(int N, int nb, const float* __restrict__ obs, int stride, const float* __restrict__ sobs,
+                                                               int sstride, DistillNets nets, GruCell cell, const float* __restrict__ logstd, uint64_t seed,
+                                                               uint32_t counter, float beta, int teacher_noise, const uint8_t* __restrict__ reset,
+                                                               const float* state_in, float* state_out, float* __restrict__ student_mu,
+                                                               float* __restrict__ act_out, float* __restrict__ teacher_mu) {
+    using L = LstmLds<H, MAXW>;
+    static_assert(L::TRUNK <= L::A && L::FLOATS * sizeof(float) <= 160 * 1024, "both halves within one block of the CU's LDS");
+    __shared__ __attribute__((aligned(16))) float lds[L::FLOATS];
+    if ((int)blockIdx.x < nb) {
+        const int r0 = blockIdx.x * MR;
+        float(*buf)[MR * L::LDA] = reinterpret_cast<float(*)[MR * L::LDA]>(lds);
+        load_tile<L::LDA>(buf[0], N, r0, obs, stride, nets.n[0].in[0], nullptr, nets.n[0].in[0]);
+        const int cur = run_layers<L::LDA>(nets.n[0], buf, 0);
+        sample<L::LDA, MIX>(buf[cur], N, r0, logstd, seed, counter, teacher_mu, MIX ? act_out : nullptr, true, beta, teacher_noise);
+    } else {
+        const size_t c_off = (size_t)N * H;
+        lstm_rows<H, MAXW, MIX>(lds, N, (blockIdx.x - nb) * MR, sobs, sstride, cell, nets.n[1], logstd, seed, counter, reset, state_in, state_out, state_in + c_off,
+                                state_out + c_off, student_mu, act_out, beta, teacher_noise);
+    }
 }
 
 }  // namespace
@@ -804,18 +851,24 @@ extern "C" int bg_distill_act_gru_own(int32_t N, const float* teacher_obs, int32
                            student_logstd, seed, counter, beta, teacher_noise, reset, h_in, h_out, student_mu, actions, teacher_mu, stream);
 }
 
-// ---- the LSTM actor's entry point
+// ---- the LSTM cell's entry points
+static int fill_lstm(const std::string& who, const bg_lstm_desc* lstm, GruCell& cell) {
+    if (!lstm || !lstm->W_ih || !lstm->W_hh || !lstm->b_ih || !lstm->b_hh) return bg_set_error(-1, (who + ": bad argument (lstm)").c_str());
+    if (lstm->in != BG_NUM_OBS) return bg_set_error(-4, (who + ": the cell takes one observation (lstm.in = 47)").c_str());
+    if (lstm->hidden != 128 && lstm->hidden != 256) return bg_set_error(-4, (who + ": unsupported lstm.hidden (128 or 256)").c_str());
+    if ((uintptr_t)lstm->W_hh & 15) return bg_set_error(-1, (who + ": lstm.W_hh must be 16-byte aligned").c_str());
+    cell = GruCell{lstm->W_ih, lstm->W_hh, lstm->b_ih, lstm->b_hh};  // (the four pointers; the layout is torch.nn.LSTMCell's, 4 hidden rows)
+    return 0;
+}
+
 extern "C" int bg_actor_sample_lstm(int32_t N, const float* obs, int32_t obs_stride, const bg_lstm_desc* lstm, int32_t n_layers, const bg_mlp_layer_desc* layers,
                                     const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, const float* c_in,
                                     float* c_out, float* mu, float* actions, void* stream) {
     const std::string who("bg_actor_sample_lstm");
     if (N <= 0 || !obs || !layers || !logstd || !h_in || !h_out || !c_in || !c_out || !actions) return bg_set_error(-1, (who + ": bad argument").c_str());
     if (obs_stride < BG_NUM_OBS) return bg_set_error(-1, (who + ": bad argument (obs_stride: at least the 47 columns the cell reads)").c_str());
-    if (!lstm || !lstm->W_ih || !lstm->W_hh || !lstm->b_ih || !lstm->b_hh) return bg_set_error(-1, (who + ": bad argument (lstm)").c_str());
-    if (lstm->in != BG_NUM_OBS) return bg_set_error(-4, (who + ": the cell takes one observation (lstm.in = 47)").c_str());
-    if (lstm->hidden != 128 && lstm->hidden != 256) return bg_set_error(-4, (who + ": unsupported lstm.hidden (128 or 256)").c_str());
-    if ((uintptr_t)lstm->W_hh & 15) return bg_set_error(-1, (who + ": lstm.W_hh must be 16-byte aligned").c_str());
-    const GruCell cell{lstm->W_ih, lstm->W_hh, lstm->b_ih, lstm->b_hh};  // (the four pointers; the layout is torch.nn.LSTMCell's, 4 hidden rows)
+    GruCell cell;
+    if (const int rc = fill_lstm(who, lstm, cell)) return rc;
     ActorNet net;
     int maxw = 0;
     if (const int rc = fill_net((who + " (trunk)").c_str(), n_layers, layers, 0, net, maxw, lstm->hidden)) return rc;
@@ -826,4 +879,57 @@ extern "C" int bg_actor_sample_lstm(int32_t N, const float* obs, int32_t obs_str
     BG_GRU_LAUNCH(actor_lstm_sample_kernel, , N, obs, obs_stride, cell, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, c_in, c_out, mu, actions);
     HIP_OK(hipGetLastError());
     return 0;
+}
+
+// who: the entry point's name; student_obs / student_stride: the rows of the cell's 47 inputs (bg_distill_act_lstm: the teacher's).  distill_act_gru's
+// checks on the same arguments; the two states travel as ONE tensor [2][N][H].
+static int distill_act_lstm(const std::string& who, int32_t N, const float* teacher_obs, int32_t teacher_stride, const float* student_obs, int32_t student_stride,
+                            int32_t n_teacher, const bg_mlp_layer_desc* teacher, int32_t scan_points, const bg_lstm_desc* lstm, int32_t n_student,
+                            const bg_mlp_layer_desc* student, const float* student_logstd, uint64_t seed, uint64_t counter, float beta, int32_t teacher_noise,
+                            const uint8_t* reset, const float* state_in, float* state_out, float* student_mu, float* actions, float* teacher_mu, void* stream) {
+    if (!(beta >= 0.f && beta <= 1.f))  // (a NaN fails both comparisons)
+        return bg_set_error(-1, (who + ": bad argument (beta: the teacher's probability of acting, a finite number in [0, 1])").c_str());
+    if (N <= 0 || !teacher_obs || !student_obs || !student || !teacher || !student_logstd || !state_in || !state_out || !actions || !teacher_mu)
+        return bg_set_error(-1, (who + ": bad argument").c_str());
+    if (scan_points < 0 || scan_points > BG_MAX_HEIGHT_SCAN_POINTS) return bg_set_error(-1, (who + ": bad argument (scan_points)").c_str());
+    GruCell cell;
+    if (const int rc = fill_lstm(who, lstm, cell)) return rc;
+    DistillNets nets;
+    int maxw_t = 0, maxw_s = 0;
+    if (const int rc = fill_net((who + " (teacher)").c_str(), n_teacher, teacher, scan_points, nets.n[0], maxw_t)) return rc;
+    if (const int rc = fill_net((who + " (student)").c_str(), n_student, student, 0, nets.n[1], maxw_s, lstm->hidden)) return rc;
+    if (teacher_stride != teacher[0].in)
+        return bg_set_error(-4, (who + ": teacher_stride must equal the teacher's first-layer input (47 H + scan_points columns per row)").c_str());
+    if (student_stride < BG_NUM_OBS) return bg_set_error(-1, (who + ": bad argument (student_stride: at least the 47 columns the cell reads)").c_str());
+    const int H = lstm->hidden, nb = (N + MR - 1) / MR;
+    // one LDS form for both halves: the wider hidden layer of the two networks, and the teacher's row tile within its first activation tile
+    const int kp = (teacher[0].in + KC - 1) / KC * KC, maxw = maxw_t > maxw_s ? maxw_t : maxw_s;
+    const bool wide = maxw > 256 || kp > 256;
+    const dim3 grid(2 * nb), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (beta > 0.f)
+        BG_GRU_LAUNCH(distill_act_lstm_kernel, BG_COMMA true, N, nb, teacher_obs, teacher_stride, student_obs, student_stride, nets, cell, student_logstd, seed,
+                      (uint32_t)counter, beta, teacher_noise, reset, state_in, state_out, student_mu, actions, teacher_mu);
+    else
+        BG_GRU_LAUNCH(distill_act_lstm_kernel, BG_COMMA false, N, nb, teacher_obs, teacher_stride, student_obs, student_stride, nets, cell, student_logstd, seed,
+                      (uint32_t)counter, beta, teacher_noise, reset, state_in, state_out, student_mu, actions, teacher_mu);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int bg_distill_act_lstm(int32_t N, const float* teacher_obs, int32_t teacher_stride, int32_t n_teacher, const bg_mlp_layer_desc* teacher,
+                                   int32_t scan_points, const bg_lstm_desc* lstm, int32_t n_student, const bg_mlp_layer_desc* student, const float* student_logstd,
+                                   uint64_t seed, uint64_t counter, float beta, int32_t teacher_noise, const uint8_t* reset, const float* state_in,
+                                   float* state_out, float* student_mu, float* actions, float* teacher_mu, void* stream) {
+    return distill_act_lstm("bg_distill_act_lstm", N, teacher_obs, teacher_stride, teacher_obs, teacher_stride, n_teacher, teacher, scan_points, lstm, n_student, student,
+                            student_logstd, seed, counter, beta, teacher_noise, reset, state_in, state_out, student_mu, actions, teacher_mu, stream);
+}
+
+extern "C" int bg_distill_act_lstm_own(int32_t N, const float* teacher_obs, int32_t teacher_stride, const float* student_obs, int32_t student_stride,
+                                       int32_t n_teacher, const bg_mlp_layer_desc* teacher, int32_t scan_points, const bg_lstm_desc* lstm, int32_t n_student,
+                                       const bg_mlp_layer_desc* student, const float* student_logstd, uint64_t seed, uint64_t counter, float beta,
+                                       int32_t teacher_noise, const uint8_t* reset, const float* state_in, float* state_out, float* student_mu, float* actions,
+                                       float* teacher_mu, void* stream) {
+    return distill_act_lstm("bg_distill_act_lstm_own", N, teacher_obs, teacher_stride, student_obs, student_stride, n_teacher, teacher, scan_points, lstm, n_student,
+                            student, student_logstd, seed, counter, beta, teacher_noise, reset, state_in, state_out, student_mu, actions, teacher_mu, stream);
 }

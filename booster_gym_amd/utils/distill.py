@@ -39,6 +39,11 @@ the frame stack's rule) and carries across iterations; the update back-propagate
 start (the gradient is truncated there): model.GRUTrainer around the trunk's MLPTrainer.  The optimiser holds memory.* and actor.*; the checkpoint
 carries memory.* and re-enters under algorithm.actor_memory: H.  0 (the default, also absent): everything above, unchanged.
 
+distillation.student_cell: "lstm" (read only with a non-zero student_memory; absent, null or "gru": the cell above, nothing moved) makes `memory` a
+torch.nn.LSTMCell(47, H), the default of rsl_rl's recurrent student.  The state is ONE tensor [2][N][H], h then c, under the GRU state's rules; the
+rollout's launch is bg_distill_act_lstm (_own under student_sensors), the update's cell is model.LSTMTrainer, and the checkpoint (4H-row memory.*,
+"student_cell" in its entry) re-enters under algorithm.actor_memory: H and algorithm.rnn_cell: "lstm".
+
 distillation.student_sensors: {bias: {gravity, ang_vel, dof_pos, dof_vel}, latency_steps: [lo, hi]} (the `sensors:` section without `enabled`, its
 meaning, defaults and rules: utils/sensors.py) distils the student under the sensor model it will meet on the robot while the teacher keeps acting
 and labelling on its clean row: the env's last launch sends the student's row, and only that row, through bg_obs_sensor's rule (bg_env_cfg.sensor_model
@@ -74,8 +79,9 @@ from .utils import mirror_rows
 
 DEFAULTS = {"teacher_checkpoint": None, "student_hidden": [256, 128, 128], "num_epochs": 5, "learning_rate": 1.0e-3, "max_grad_norm": 1.0,
             "student_noise_std": 0.1, "student_frame_stack": None, "symmetric_coef": 0.0, "teacher_action_prob": 0.0, "teacher_action_iterations": 0,
-            "teacher_action_noise": True, "student_memory": 0, "student_sensors": None}
+            "teacher_action_noise": True, "student_memory": 0, "student_sensors": None, "student_cell": None}
 STUDENT_MEMORY = (0, 128, 256)  # the widths of the recurrent student's cell the kernels take (0: no memory)
+STUDENT_CELLS = ("gru", "lstm")  # the cells of distillation.student_cell
 
 
 class DistillCfg(NamedTuple):
@@ -109,7 +115,7 @@ def distillation_cfg(cfg, world_size=1):
                          "the Distiller does not train): set estimator.enabled to false")
     if int(world_size) != 1:
         raise ValueError(f"distillation runs on one rank (WORLD_SIZE = {world_size}): data parallelism is out of scope")
-    student_memory_of(cfg)  # (ValueError naming the key: its value, and what a recurrent student excludes)
+    student_cell_of(cfg)  # (ValueError naming the key: student_memory's value and what a recurrent student excludes, then the cell's name)
     student_sensors_of(cfg)
     v = dict(DEFAULTS, **sec)
     ck = v["teacher_checkpoint"]
@@ -194,6 +200,20 @@ def student_memory_of(cfg):
     return H
 
 
+def student_cell_of(cfg):
+    """distillation.student_cell as the cell of the recurrent student: "gru" (also absent or null: today's torch.nn.GRUCell) or "lstm" (rsl_rl's
+    StudentTeacherRecurrent default, a torch.nn.LSTMCell).  Read only together with a non-zero distillation.student_memory, as runner.rnn_cell_of
+    reads algorithm.rnn_cell only with algorithm.rnn_hidden_size: without a memory the result is "gru" whatever the key holds.  Pure.  ValueError
+    naming the key for any other value; student_memory_of's own refusals apply unchanged."""
+    if not student_memory_of(cfg):
+        return "gru"
+    cell = _key(cfg, "student_cell")
+    cell = "gru" if cell is None else cell
+    if not isinstance(cell, str) or cell not in STUDENT_CELLS:
+        raise ValueError(f"distillation.student_cell must be \"gru\" or \"lstm\" (the cell of distillation.student_memory; absent or null: \"gru\"), got {cell!r}")
+    return cell
+
+
 STUDENT_SENSORS_KEYS = ("bias", "latency_steps")  # the `sensors:` section's keys minus `enabled`
 
 
@@ -234,7 +254,7 @@ def student_mirror_maps(dof_names, dof_axes, default_dof_pos, frames):
     return mirror_maps(dof_names, dof_axes, default_dof_pos, _lib.NUM_OBS * int(frames), int(frames), None)
 
 
-def student_overrides(num_observations, student_frame_stack=None, student_memory=None, student_sensors=None):
+def student_overrides(num_observations, student_frame_stack=None, student_memory=None, student_sensors=None, student_cell=None):
     """The rule under which a student re-enters Runner / play.py / export_model.py / evaluate.py, written once: the teacher's config without the
     actor's scan, the student's own history when it has one, the row its actor takes, and the sensor model it was distilled under
     (student_sensors: the section {bias, latency_steps} as plain dicts and lists; bg_obs_sensor then writes the row the student trained on).
@@ -245,6 +265,8 @@ def student_overrides(num_observations, student_frame_stack=None, student_memory
     over["env.num_observations"] = int(num_observations)
     if student_memory:  # a recurrent student: Runner(test=True) builds its actor behind a GRU cell of that width
         over["algorithm.actor_memory"] = int(student_memory)
+        if student_cell == "lstm":  # ... behind an LSTM cell (beside algorithm.rnn_hidden_size: H the same key trains it further under PPO)
+            over["algorithm.rnn_cell"] = "lstm"
     if student_sensors is not None:
         over["sensors.enabled"] = True
         over["sensors.bias"] = dict(student_sensors["bias"])
@@ -262,7 +284,8 @@ def student_cfg_overrides(cfg):
         Hs = student_frame_stack_of(cfg)
         if Hs > H:
             return student_overrides(_lib.NUM_OBS * Hs, Hs, None, sensors)
-    return student_overrides(_lib.NUM_OBS * H, None, student_memory_of(cfg) if isinstance(cfg.get("distillation"), dict) else None, sensors)
+    on = isinstance(cfg.get("distillation"), dict)
+    return student_overrides(_lib.NUM_OBS * H, None, student_memory_of(cfg) if on else None, sensors, student_cell_of(cfg) if on else None)
 
 
 def checkpoint_student_overrides(checkpoint):
@@ -273,8 +296,9 @@ def checkpoint_student_overrides(checkpoint):
         return None
     sd = checkpoint["model"]
     if "memory.weight_ih" in sd:  # a recurrent student: the row is what its cell reads, the actor takes the cell's state
-        return student_overrides(int(sd["memory.weight_ih"].shape[1]), entry.get("student_frame_stack"), int(sd["memory.weight_hh"].shape[1]),
-                                 entry.get("student_sensors"))
+        mem = int(sd["memory.weight_hh"].shape[1])  # (four gates' rows: torch.nn.LSTMCell, distillation.student_cell: "lstm"; a GRU cell has three)
+        return student_overrides(int(sd["memory.weight_ih"].shape[1]), entry.get("student_frame_stack"), mem, entry.get("student_sensors"),
+                                 "lstm" if sd["memory.weight_hh"].shape[0] == 4 * mem else "gru")
     return student_overrides(int(sd["actor.0.weight"].shape[1]), entry.get("student_frame_stack"), None, entry.get("student_sensors"))
 
 
@@ -293,7 +317,7 @@ class Distiller:
                 cfg.setdefault("distillation", {})
                 if isinstance(cfg["distillation"], dict):
                     cfg["distillation"]["teacher_checkpoint"] = self.args.teacher
-            for arg in ("student_frame_stack", "symmetric_coef", "teacher_action_prob", "teacher_action_iterations", "student_memory"):
+            for arg in ("student_frame_stack", "symmetric_coef", "teacher_action_prob", "teacher_action_iterations", "student_memory", "student_cell"):
                 if getattr(self.args, arg) is not None:
                     cfg.setdefault("distillation", {})
                     if isinstance(cfg["distillation"], dict):
@@ -306,7 +330,8 @@ class Distiller:
             raise ValueError("distillation.teacher_checkpoint is not set: the path of a checkpoint trained with terrain.actor_heights (distill.py --teacher=PATH)")
         self.symmetric_coef = symmetric_coef_of(cfg)
         self.beta0, self.beta_iterations, self.teacher_noise = teacher_action_of(cfg)
-        self.memory = student_memory_of(cfg)  # the width of the recurrent student's GRU cell; 0: none
+        self.memory = student_memory_of(cfg)  # the width of the recurrent student's cell; 0: none
+        self.cell = student_cell_of(cfg)  # "gru" (also without a memory) or "lstm"
         Hs, H = student_frame_stack_of(cfg), frame_stack_of(cfg)
         sensors = student_sensors_of(cfg)
         self.student_sensors = None if sensors is None else sensors_as_section(sensors)  # the validated section as plain dicts, lists and floats
@@ -332,7 +357,7 @@ class Distiller:
         self.teacher = self._load_teacher(self.dcfg.teacher_checkpoint)
         A = env.num_actions
         self.student = ActorCritic(A, self.student_obs, env.num_privileged_obs, self.dcfg.student_hidden, critic_hidden,
-                                   **({"memory_hidden": self.memory} if self.memory else {})).to(dev)
+                                   **({"memory_hidden": self.memory} if self.memory else {}), **({"memory_cell": "lstm"} if self.cell == "lstm" else {})).to(dev)
         with torch.no_grad():
             self.student.logstd.fill_(math.log(self.dcfg.student_noise_std))
         self.student.logstd.requires_grad_(False)  # fixed exploration noise of the data-collecting student; not trained
@@ -368,9 +393,9 @@ class Distiller:
                                       **({"cell": self.student.memory, "steps": T} if self.memory else {}))
         self._sup.resolve_plan()
         if self.memory:
-            # the cell's rollout state [N][H] (advanced in place by bg_distill_act_gru, zero at begin()) and the done flags of the previous iteration's
-            # last step: the resets of this iteration's step 0
-            self.state = torch.zeros(N, self.memory, device=dev)
+            # the cell's rollout state [N][H] (advanced in place by bg_distill_act_gru, zero at begin(); an LSTM cell's ONE tensor [2][N][H], h then c,
+            # by bg_distill_act_lstm) and the done flags of the previous iteration's last step: the resets of this iteration's step 0
+            self.state = torch.zeros(*((2,) if self.cell == "lstm" else ()), N, self.memory, device=dev)
             self._last_dones = torch.zeros(N, dtype=torch.uint8, device=dev)
             self._gru_desc = (None, None)
         self._losses = torch.zeros(self.dcfg.num_epochs, self._sup.stats.numel(), dtype=torch.float64, device=dev)
@@ -393,6 +418,8 @@ class Distiller:
                             "Overrides distillation.teacher_action_iterations.")
         parser.add_argument("--student_memory", type=int, help="Width of the recurrent student's GRU cell (128 or 256; 0: a memoryless student). "
                             "Overrides distillation.student_memory.")
+        parser.add_argument("--student_cell", type=str, help="Cell of the recurrent student, gru or lstm (read with a non-zero student_memory). "
+                            "Overrides distillation.student_cell.")
         parser.add_argument("--max_iterations", type=int, help="Number of distillation iterations. Overrides config file if provided.")
         parser.add_argument("--num_envs", type=int, help="Number of environments to create. Overrides config file if provided.")
         parser.add_argument("--sim_device", type=str, help="Device for physics simulation. Overrides config file if provided.")
@@ -463,6 +490,8 @@ class Distiller:
             d["distillation"]["teacher_action_prob"] = [self.beta0, self.beta_iterations]
         if self.memory:
             d["distillation"]["student_memory"] = self.memory
+            if self.cell == "lstm":
+                d["distillation"]["student_cell"] = self.cell
         if self.env.terrain.curriculum:
             d["terrain_levels"] = self.env.terrain_levels
         return d
@@ -501,7 +530,8 @@ class Distiller:
             gnets = (len(td), td, self.scan, self._gru_desc[1], len(sd), sd)
             tail = lambda n: gnets + rng() + (beta, noise, p(mt.rollout_reset(n, self._last_dones, dones)), p(h), p(h))
             # (the cell's 47 inputs from the student's own row where it has one: the sensor model)
-            name, mid = ("bg_distill_act_gru_own", lambda n: own(n) + tail(n)) if self.history else ("bg_distill_act_gru", tail)
+            name = "bg_distill_act_" + self.cell  # (bg_distill_act_lstm: the same arguments, `h` the one tensor [2][N][H] of both states)
+            name, mid = (name + "_own", lambda n: own(n) + tail(n)) if self.history else (name, tail)
         elif self.beta0 > 0:  # DAgger's mixing: one launch of its own kind on the same buffers
             name, mid = "bg_distill_act_mix", lambda n: own(n) + nets + rng() + (beta, noise)
         elif self.history:

@@ -183,6 +183,17 @@ def rnn_cell_of(cfg, world_size=1):
     return cell
 
 
+def actor_memory_cell_of(cfg):
+    """The cell of algorithm.actor_memory where no algorithm.rnn_hidden_size stands beside it (a recurrent distilled student re-entering to play, to be
+    evaluated or exported: distill.student_overrides): algorithm.rnn_cell, "gru" (also absent or null) or "lstm" (distillation.student_cell).  Pure.
+    ValueError naming the key for any other value.  What "lstm" excludes in training is rnn_cell_of's to refuse; nothing of it plays a part here."""
+    cell = (cfg.get("algorithm", {}) or {}).get("rnn_cell")
+    cell = "gru" if cell is None else cell
+    if not isinstance(cell, str) or cell not in RNN_CELLS:
+        raise ValueError(f"algorithm.rnn_cell must be \"gru\" or \"lstm\" (the cell of algorithm.actor_memory; absent: \"gru\"), got {cell!r}")
+    return cell
+
+
 def rnn_critic_of(cfg, world_size=1):
     """algorithm.rnn_critic (an addition of this build; absent, null or false = off: the shipped yaml does not list it) as the width H of a second GRU
     cell, in front of the critic: algorithm.rnn_hidden_size when the key is on (one width serves both cells, as in rsl_rl's ActorCriticRecurrent), else
@@ -486,6 +497,8 @@ class Runner:
         self._memory = self._memory or self._rnn
         # algorithm.rnn_cell: the cell of algorithm.rnn_hidden_size, "gru" (also without a recurrent actor) or "lstm"
         self._rnn_cell = rnn_cell_of(self.cfg, self.world_size)
+        if self._memory and not self._rnn:  # a recurrent student re-entering to play: the cell its overrides name beside algorithm.actor_memory
+            self._rnn_cell = actor_memory_cell_of(self.cfg)
         # algorithm.rnn_critic: a second cell of the same width in front of the critic; 0 = a feed-forward critic, the one switch the branches below read
         self._rnn_critic = rnn_critic_of(self.cfg, self.world_size)
         if self._rnn and not test and (int((self.cfg.get("parallel", {}) or {}).get("gemm_split", 0) or 0) or MLPTrainer.SPLIT):

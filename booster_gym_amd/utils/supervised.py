@@ -2,7 +2,7 @@
 import torch
 
 from .. import _lib
-from .model import GroupedWeightGrad, GRUTrainer, MLPTrainer, plan_network, wgrad_products
+from .model import GroupedWeightGrad, GRUTrainer, LSTMTrainer, MLPTrainer, plan_network, wgrad_products
 from .utils import head_scratch, reduce_group
 
 
@@ -17,7 +17,9 @@ class SupervisedTrainer:
     def __init__(self, name, net, optimizer, clock, rows, kin, cell=None, steps=None, n_stats=1):
         self.name, self.optimizer, self.clock, self.rows, self.kin = name, optimizer, clock, int(rows), int(kin)
         self.mlp = MLPTrainer(net, clock=clock)
-        self.gru = GRUTrainer(cell, self.mlp, steps, self.rows // steps, clock=clock) if cell is not None else None
+        # (an LSTM cell: the same interface around its own kernels; its four-launch backward is its bias records and their two finishes run at once)
+        trainer = LSTMTrainer if isinstance(cell, torch.nn.LSTMCell) else GRUTrainer
+        self.gru = trainer(cell, self.mlp, steps, self.rows // steps, clock=clock) if cell is not None else None
         self.wgrad = GroupedWeightGrad()
         dev = self.mlp.layers[0].weight.device
         self.head_scratch = head_scratch(dev)

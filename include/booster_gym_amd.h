@@ -581,6 +581,25 @@ typedef struct bg_lstm_desc {
 int bg_actor_sample_lstm(int32_t N, const float* obs, int32_t obs_stride, const bg_lstm_desc* lstm, int32_t n_layers, const bg_mlp_layer_desc* layers,
                          const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, const float* c_in,
                          float* c_out, float* mu, float* actions, void* stream);
+/* A recurrent student with that cell (T1.yaml distillation.student_cell: "lstm"; rsl_rl's StudentTeacherRecurrent with its default cell):
+ * bg_distill_act_gru's split grid and arguments with bg_actor_sample_lstm's body in the student's half.  The two states travel as ONE tensor: state_in /
+ * state_out [2][N][hidden], h then c (both read as zero where reset [N] is non-zero); state_in == state_out is allowed.  The teacher's half is unchanged
+ * (teacher_mu equals bg_actor_sample_mlp_scan's mean, bit for bit); student_mu, state_out and at beta = 0 actions equal bg_actor_sample_lstm's on columns
+ * [0, 47) of the teacher's rows, bit for bit.  beta in [0, 1] and teacher_noise: bg_distill_act_mix's rules (the same RS_DAGGER draw decides which half
+ * acts; a teacher-driven row carries the student's noise draw); both states advance on every row, whoever acts.  One block of LDS serves both halves
+ * (the teacher's two tiles over the student's gate tile): 45,056 B at hidden = 128 with hidden layers up to 256 and a teacher's row up to 256 columns,
+ * 77,824 B at hidden = 128 otherwise, 85,760 / 86,016 B at hidden = 256.  Violations: -1 / -4 with a message naming the entry point, before any launch. */
+int bg_distill_act_lstm(int32_t N, const float* teacher_obs, int32_t teacher_stride, int32_t n_teacher, const bg_mlp_layer_desc* teacher,
+                        int32_t scan_points, const bg_lstm_desc* lstm, int32_t n_student, const bg_mlp_layer_desc* student, const float* student_logstd,
+                        uint64_t seed, uint64_t counter, float beta, int32_t teacher_noise, const uint8_t* reset, const float* state_in, float* state_out,
+                        float* student_mu, float* actions, float* teacher_mu, void* stream);
+/* bg_distill_act_lstm with the cell's 47 inputs from rows of the student's own: columns [0, 47) of student_obs (rows student_stride >= 47 floats apart)
+ * in place of the teacher's rows (bg_env_cfg.sensor_model = 2, as bg_distill_act_gru_own).  The same kernel; the teacher's half is untouched.  With
+ * student_obs on rows that equal the teacher's first 47 columns, every output and the state equal bg_distill_act_lstm's, bit for bit. */
+int bg_distill_act_lstm_own(int32_t N, const float* teacher_obs, int32_t teacher_stride, const float* student_obs, int32_t student_stride, int32_t n_teacher,
+                            const bg_mlp_layer_desc* teacher, int32_t scan_points, const bg_lstm_desc* lstm, int32_t n_student, const bg_mlp_layer_desc* student,
+                            const float* student_logstd, uint64_t seed, uint64_t counter, float beta, int32_t teacher_noise, const uint8_t* reset,
+                            const float* state_in, float* state_out, float* student_mu, float* actions, float* teacher_mu, void* stream);
 /* The recurrence of that actor's update over T steps as ONE launch each way (csrc/bg_lstm.hip); H = 128 or 256, any N >= 1, T >= 1; a workgroup owns 16
  * envs and walks the steps itself, h in an LDS tile, c in registers; W_hh [4H][H] (16-byte aligned) streams from L2.
  * Forward: gi [T][N][4H] the x-side pre-activations (b_ih included), h0 / c0 [N][H] the states entering step 0 (NULL: zero), reset [T][N] (uint8, NULL:

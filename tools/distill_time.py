@@ -35,6 +35,12 @@
            the same env without it, at Hs (5 unless given) and at Hs = H = 1 (without the key: no student's row at all), the way of (4), and the bytes
            bg_obs_assemble moves in each; `only` = "assemble" stops here (the run under a kernel trace, which gives the launch's own time);
       (14) the loop of (3) without the key and with it, at Hs = H and at Hs, one Distiller after the other, `pairs` times each.
+  With student_cell=lstm among the arguments (distillation.student_cell; out "-" = profiles/distill_lstm_time.txt) the sections are the LSTM
+  student's instead, all at H = 1 / P = 187:
+      (15) bg_distill_act_lstm with a cell of 128 and of 256 against bg_distill_act_gru at the same width, and against the sum of the two launches it
+           fuses (bg_actor_sample_lstm + bg_actor_sample_mlp_scan), the same way as (1); the outputs are compared bit for bit first;
+      (16) the loop of (3) with the GRU cell and with the LSTM cell of student_memory=H (128 unless given), one Distiller after the other, `pairs`
+           times each, rollout and update alone behind each.
   The outputs of (1) are compared bit for bit before they are timed.  The committed profile carries two more sections that this tool does not
   write: the figures tests/test_gpu_distill.py prints under -s, and bench.py of this tree against a checkout of its parent commit."""
 import os
@@ -373,6 +379,44 @@ def act_gru(pairs=3, N=4096, Hs=5, P=187):
             f"{us['gru 128'] / us['hist']:.3f}x hist), of 256 {us['gru 256']:.2f} us ({us['gru 256'] / us['plain']:.3f}x plain, {us['gru 256'] / us['hist']:.3f}x hist)")
 
 
+def act_lstm(pairs=3, N=4096, P=187):
+    """(15): the LSTM student's rollout launch beside the GRU student's and beside the two launches it fuses."""
+    from booster_gym_amd import _lib
+    from booster_gym_amd.utils.model import ActorCritic
+
+    lib, p, st = _lib.load(), _lib.ptr, _lib.current_stream_ptr()
+    torch.manual_seed(1)
+    teacher = ActorCritic(12, 47 + P, 14 + P).to(DEV)
+    obs = torch.randn(N, 47 + P, device=DEV)
+    td, nt = _descs(teacher)
+    a1, t1, a2, t2, tmp = (torch.empty(N, 12, device=DEV) for _ in range(5))
+    for H in (128, 256):
+        gru_s, lstm_s = ActorCritic(12, 47, 14 + P, memory_hidden=H).to(DEV), ActorCritic(12, 47, 14 + P, memory_hidden=H, memory_cell="lstm").to(DEV)
+        (gd, gn), (ld, ln), gdesc, ldesc = _descs(gru_s), _descs(lstm_s), gru_s.gru_descriptor(), lstm_s.gru_descriptor()
+        h, s1, s2, s0 = torch.zeros(N, H, device=DEV), torch.zeros(2, N, H, device=DEV), torch.zeros(2, N, H, device=DEV), torch.randn(2, N, H, device=DEV) * 0.5
+
+        def gru(k):
+            _lib.check(lib.bg_distill_act_gru(N, p(obs), 47 + P, nt, td, P, gdesc, gn, gd, p(gru_s.logstd), 1, k, 0.0, 1, None, p(h), p(h), None, p(a1), p(t1), st),
+                       "bg_distill_act_gru")
+
+        def lstm(k, sin=s1):
+            _lib.check(lib.bg_distill_act_lstm(N, p(obs), 47 + P, nt, td, P, ldesc, ln, ld, p(lstm_s.logstd), 1, k, 0.0, 1, None, p(sin), p(s1), None, p(a1), p(t1), st),
+                       "bg_distill_act_lstm")
+
+        def separate(k, sin=s2):
+            _lib.check(lib.bg_actor_sample_lstm(N, p(obs), 47 + P, ldesc, ln, ld, p(lstm_s.logstd), 1, k, None, p(sin[0]), p(s2[0]), p(sin[1]), p(s2[1]), None, p(a2), st),
+                       "bg_actor_sample_lstm")
+            _lib.check(lib.bg_actor_sample_mlp_scan(N, p(obs), nt, td, P, p(teacher.logstd), 1, k, p(t2), p(tmp), st), "bg_actor_sample_mlp_scan")
+
+        lstm(7, s0); separate(7, s0); torch.cuda.synchronize()
+        assert torch.equal(a1, a2) and torch.equal(t1, t2) and torch.equal(s1, s2), "bg_distill_act_lstm differs from its stand-alone launches"
+        for q in range(pairs):
+            us = {m: _best(f, 200) for m, f in _orders(q, (("lstm", lstm), ("gru", gru), ("separate", separate)))}
+            say(f"rollout inference, {N} rows, H = 1, P = {P}, teacher and trunks 256-128-128, cell of {H}: bg_distill_act_lstm {us['lstm']:.2f} us, bg_distill_act_gru "
+                f"{us['gru']:.2f} us (lstm / gru = {us['lstm'] / us['gru']:.4f}), bg_actor_sample_lstm + bg_actor_sample_mlp_scan {us['separate']:.2f} us "
+                f"(fused / separate = {us['lstm'] / us['separate']:.4f})")
+
+
 def sequence(pairs=3, N=4096, T=24):
     from booster_gym_amd import _lib
 
@@ -405,7 +449,7 @@ def sequence(pairs=3, N=4096, T=24):
                 f"{2.0 * B * H * 3 * H / 1e9:.1f} GFLOP {floor:.1f} us (forward {us['fwd'] / floor:.1f}x, backward {us['bwd'] / floor:.1f}x)")
 
 
-def loop(K=20, W=5, pairs=3, N=4096, Hs=None, coef=0.0, beta=0.0, memory=0, student_sensors=None):
+def loop(K=20, W=5, pairs=3, N=4096, Hs=None, coef=0.0, beta=0.0, memory=0, student_sensors=None, cell=None):
     from booster_gym_amd.utils.config import load_cfg
     from booster_gym_amd.utils.distill import Distiller
     from booster_gym_amd.utils.model import ActorCritic
@@ -429,6 +473,8 @@ def loop(K=20, W=5, pairs=3, N=4096, Hs=None, coef=0.0, beta=0.0, memory=0, stud
         cfg["distillation"]["student_memory"] = memory
     if student_sensors is not None:
         cfg["distillation"]["student_sensors"] = student_sensors
+    if cell is not None:
+        cfg["distillation"]["student_cell"] = cell
     d = Distiller(cfg=cfg)
     d.begin(Recorder(cfg, root=tmp, rank=0))
     it = 0
@@ -447,6 +493,7 @@ def loop(K=20, W=5, pairs=3, N=4096, Hs=None, coef=0.0, beta=0.0, memory=0, stud
         ms = run(K)
         keys = f"symmetric_coef {coef:g}, teacher_action_prob {beta:g}, " if coef or beta or KEYS else ""
         keys += f"student_memory {memory}, " if memory or MEMORY else ""
+        keys += f"student_cell {cell}, " if cell is not None else ""
         keys += f"student_sensors {'absent' if student_sensors is None else SENSORS[0]}, " if SENSORS else ""
         say(f"distillation loop, {N} envs, H = 1, P = 187, {keys}student_frame_stack {Hs or 'absent'} ({d.student_obs} student columns padded to {d._student_in.shape[1]}), horizon {T}, {E} epochs, student 256-128-128 (plan {d._sup.mlp.plan.fwd} / {d._sup.mlp.plan.bwd}, weight "
             f"gradients {d._sup.wgrad_terms or 'fp32'}): {ms:.3f} ms per iteration = {1e3 / ms:.2f} iterations/s = {N * T / ms / 1e3:.3f} M env-steps/s; last loss "
@@ -463,20 +510,30 @@ def loop(K=20, W=5, pairs=3, N=4096, Hs=None, coef=0.0, beta=0.0, memory=0, stud
 
 KEYS = {}  # symmetric_coef / teacher_action_prob given on the command line: sections (7) to (9)
 MEMORY = []  # student_memory given on the command line: sections (10) to (12)
+CELL = []  # student_cell given on the command line ("lstm"): sections (15) and (16)
 SENSORS = []  # student_sensors given on the command line ("full" or "empty"): sections (13) and (14)
 
 
 if __name__ == "__main__":
     KEYS.update({k: float(v) for k, v in (x.split("=", 1) for x in sys.argv[1:] if "=" in x) if k in ("symmetric_coef", "teacher_action_prob")})
     MEMORY.extend(int(v) for k, v in (x.split("=", 1) for x in sys.argv[1:] if "=" in x) if k == "student_memory")
+    CELL.extend(v for k, v in (x.split("=", 1) for x in sys.argv[1:] if "=" in x) if k == "student_cell")
     SENSORS.extend(v for k, v in (x.split("=", 1) for x in sys.argv[1:] if "=" in x) if k == "student_sensors")
     a = [x for x in sys.argv[1:] if "=" not in x]
     K, W, pairs, N = (int(a[i]) if len(a) > i else v for i, v in enumerate((20, 5, 3, 4096)))
     Hs, only = (int(a[5]) if len(a) > 5 else 0), (a[6] if len(a) > 6 else "")
-    name = "student_sensors_time.txt" if SENSORS else "distill_memory_time.txt" if MEMORY else "distill_symmetry_dagger_time.txt" if KEYS else "distill_history_time.txt" if Hs else "distill_time.txt"
+    name = "distill_lstm_time.txt" if CELL else "student_sensors_time.txt" if SENSORS else "distill_memory_time.txt" if MEMORY else "distill_symmetry_dagger_time.txt" if KEYS else "distill_history_time.txt" if Hs else "distill_time.txt"
     out = a[4] if len(a) > 4 and a[4] != "-" else os.path.join(ROOT, "profiles", name)
     say(f"tools/distill_time.py {' '.join(sys.argv[1:]) or f'{K} {W} {pairs} {N}'} on {torch.cuda.get_device_name(0)}")
-    if SENSORS:
+    if CELL:
+        if CELL[0] != "lstm":
+            raise SystemExit("student_cell=lstm")
+        if only != "loop":
+            act_lstm(pairs, N)
+        for q in range(pairs):  # (a Distiller each: the cell, the buffers and the trainer are per configuration)
+            for cell in _orders(q, ("gru", "lstm")):
+                loop(K, W, 1, N, None, memory=MEMORY[0] if MEMORY else 128, cell=cell)
+    elif SENSORS:
         if SENSORS[0] not in ("full", "empty"):
             raise SystemExit("student_sensors=full or student_sensors=empty")
         section = FULL_SENSORS if SENSORS[0] == "full" else {}
