@@ -88,6 +88,84 @@ def gru_sequence_case(T, N, H, gi_scale=1.0, reset=0.2, h0=True, device="cpu"):
     return dict(T=T, N=N, H=H, cell=cell.to(device), gi=to(gi), h0=to(h0_t), reset=to(flags), dh_ext=to(dh_ext), ref=ref, twin=twin)
 
 
+def lstm_sequence_case(T, N, H, gi_scale=1.0, reset=0.2, h0=True, c0=True, device="cpu"):
+    """gru_sequence_case for bg_lstm_sequence_forward / _backward: the inputs at one shape, the float64 restatement of torch.nn.LSTMCell's recurrence
+    (gate order i | f | g | o, both states zero behind a reset) and an fp32 torch twin of the same loop.
+      gi_scale  multiplies the x-side pre-activations gi (8: a large share of the gates saturates)
+      reset     a rate, "none" (an all-zero tensor), "step2" (every env at t = 2 and nowhere else), "t0" (the rate-0.2 flags of step 0, none later),
+                "last" (every env at t = T - 1 and nowhere else) or None (no tensor: the launch's reset == NULL)
+      h0, c0    False: no tensor (NULL); the restatement then starts that state from zero
+    The draws (gi, h0, c0, the reset draws, dh_ext) are made in one fixed order whatever the options, so two cases of one (T, N, H) share them.
+    Returns T, N, H, cell (torch.nn.LSTMCell(47, H): W_hh and b_hh only), gi [T][N][4H], h0 / c0 [N][H] or None, reset uint8 [T][N] or None, dh_ext
+    [T][N][H] on `device`, and ref / twin: dicts of h_prev, c_prev, h, c [T][N][H], gates [T][N][5H] = i | f | g | o | tanh(c'), and autograd's dg
+    [T][N][4H] (the gradient of gi), dh0, dc0 [N][H] of sum(h * dh_ext), in float64 / float32."""
+    import torch
+
+    g = torch.Generator(device="cpu").manual_seed(40 + H)
+    torch.manual_seed(7)
+    cell = torch.nn.LSTMCell(47, H)
+    gi = torch.randn(T, N, 4 * H, generator=g) * gi_scale
+    h0_t = torch.randn(N, H, generator=g) * 0.5
+    c0_t = torch.randn(N, H, generator=g) * 0.5
+    drawn = torch.rand(T, N, generator=g)
+    dh_ext = torch.randn(T, N, H, generator=g)
+    if reset is None:
+        flags = None
+    elif isinstance(reset, str):
+        flags = torch.zeros(T, N, dtype=torch.uint8)
+        if reset == "step2":
+            flags[2] = 1
+        elif reset == "last":
+            flags[T - 1] = 1
+        elif reset == "t0":
+            flags[0] = (drawn[0] < 0.2).to(torch.uint8)
+        elif reset != "none":
+            raise ValueError(f"lstm_sequence_case: reset {reset!r}")
+    else:
+        flags = (drawn < float(reset)).to(torch.uint8)
+    if not h0:
+        h0_t = None
+    if not c0:
+        c0_t = None
+
+    def loop(dtype):
+        W, b = cell.weight_hh.detach().to(dtype), cell.bias_hh.detach().to(dtype)
+        start = lambda x: (torch.zeros(N, H, dtype=dtype) if x is None else x.to(dtype).clone()).requires_grad_()  # (a copy: the inputs stay plain tensors)
+        gi_, h0_, c0_ = gi.to(dtype).clone().requires_grad_(), start(h0_t), start(c0_t)
+        h, c, rows = h0_, c0_, {k: [] for k in ("h_prev", "c_prev", "h", "c", "gates")}
+        for t in range(T):
+            keep = None if flags is None else (1 - flags[t].to(dtype)).view(N, 1)
+            hp, cp = (h, c) if keep is None else (h * keep, c * keep)
+            p = gi_[t] + hp @ W.t() + b
+            i, f, gg, o = torch.sigmoid(p[:, :H]), torch.sigmoid(p[:, H : 2 * H]), torch.tanh(p[:, 2 * H : 3 * H]), torch.sigmoid(p[:, 3 * H :])
+            c = f * cp + i * gg
+            tc = torch.tanh(c)
+            h = o * tc
+            for k, v in zip(rows, (hp, cp, h, c, torch.cat((i, f, gg, o, tc), 1))):
+                rows[k].append(v)
+        (torch.stack(rows["h"]) * dh_ext.to(dtype)).sum().backward()
+        out = {k: torch.stack(v).detach() for k, v in rows.items()}
+        out.update(dg=gi_.grad, dh0=h0_.grad, dc0=c0_.grad)
+        return {k: v.to(device) for k, v in out.items()}
+
+    ref, twin = loop(torch.float64), loop(torch.float32)
+    to = lambda x: None if x is None else x.to(device)
+    return dict(T=T, N=N, H=H, cell=cell.to(device), gi=to(gi), h0=to(h0_t), c0=to(c0_t), reset=to(flags), dh_ext=to(dh_ext), ref=ref, twin=twin)
+
+
+# The cases of tests/test_gpu_lstm_shapes.py, which tests/test_lstm_shapes_ref.py holds the fp32 twin to a tenth of the bounds at:
+# name: (T, N, gi_scale, reset, h0 given, c0 given)
+LSTM_CASES = {"a:1x1": (1, 1, 1.0, 1.0, True, True), "a:1x1_no_reset": (1, 1, 1.0, "none", True, True),  # (rate 1: the one flag is set; the second form reads h0 and c0)
+              "b:1x16": (1, 16, 1.0, 0.2, True, True), "b:2x32": (2, 32, 1.0, 0.2, True, True),
+              "c:3x17": (3, 17, 1.0, 0.2, True, True),
+              "d:24x33": (24, 33, 1.0, 0.2, True, True), "d:24x33_scale8": (24, 33, 8.0, 0.2, True, True),
+              "e:h0_null": (5, 40, 1.0, 0.2, False, True), "e:c0_null": (5, 40, 1.0, 0.2, True, False), "e:h0_c0_null": (5, 40, 1.0, 0.2, False, False),
+              "e:reset_null": (5, 40, 1.0, None, True, True), "e:all_null": (5, 40, 1.0, None, False, False),
+              "f:step2": (5, 40, 1.0, "step2", True, True), "f:t0": (5, 40, 1.0, "t0", True, True), "f:last": (5, 40, 1.0, "last", True, True),
+              "f:none": (5, 40, 1.0, "none", True, True),
+              "g:4x129": (4, 129, 1.0, 0.2, True, True)}
+
+
 def rel_state(a, b):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     return (np.abs(a - b) / np.maximum(1.0, np.abs(b))).reshape(a.shape[0], -1).max(axis=1)
