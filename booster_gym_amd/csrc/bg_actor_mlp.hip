@@ -540,6 +540,85 @@ __global__ __launch_bounds__(256) BG_NO_PACKED_FP32 void actor_lstm_sample_kerne
     lstm_rows<H, MAXW, false>(lds, N, blockIdx.x * MR, obs, stride, cell, net, logstd, seed, counter, reset, h_in, h_out, c_in, c_out, mu_out, act_out, 0.f, 0);
 }
 
+// ---- the LSTM cell at H = 512 (legged_gym's rnn_hidden_size; bg_actor_sample_lstm alone: the distillation launches keep 128 and 256).  ONE gate tile
+// [16][4 x 512 + 4] and the h tile would be 167,680 B with the x tile, over the CU's 160 kB, so the gate tile is run in TWO COLUMN PASSES: pass p holds
+// the pre-activations of the h-columns [256 p, 256 p + 256) of all four gates, [16][4 x 256 + 4] with gate g at columns [256 g, 256 g + 256).  Per pass
+// and gate the same two pieces as lstm_rows on a 256-row block of W_ih / W_hh (rows 512 g + 256 p ..): first_layer without the ELU writes
+// gi = x W_ih^T + b_ih, layer's ADD form accumulates gh = h W_hh^T + b_hh onto it (same lane, no barrier in between), so an element is the sum that
+// lstm_rows forms, in its order.  Pass 1 still reads the old h, so h' goes to a SECOND h tile, the trunk's input.  c is read (in front of a pass's GEMMs)
+// and written by the thread that owns the element, 16 per thread and pass.  The trunk's two tiles lie over the gate tile.
+//   floats: max(16 x 1028, 2 x 16 (MAXW + 4)) + 2 x 16 x 516 + 16 x 52: 135,168 B (MAXW = 256), 135,424 B (512): one workgroup per CU.
+template <int MAXW>
+struct LstmWideLds {
+    static constexpr int H = 512, HP = 256;                                                           // the cell's width; h-columns per pass
+    static constexpr int LDA = MAXW + 4, LDG = 4 * HP + 4, LDH = H + 4, LDX = KC + 4;  // row strides (floats), multiples of 4
+    static constexpr int TRUNK = 2 * MR * LDA, GT = MR * LDG;
+    static constexpr int A = GT > TRUNK ? GT : TRUNK, HT = MR * LDH, X = MR * LDX;
+    static constexpr int FLOATS = A + 2 * HT + X;
+};
+
+// h_in / h_out and c_in / c_out may be the same buffers (lstm_rows' rule: the 16 rows of h are in LDS in front of the first barrier, an element of c is
+// read and written by one thread).
+template <int MAXW>
+__global__ __launch_bounds__(256) BG_NO_PACKED_FP32 void actor_lstm_wide_sample_kernel(int N, const float* __restrict__ obs, int stride, GruCell cell, ActorNet net,
+                                                                     const float* __restrict__ logstd, uint64_t seed, uint32_t counter,
+                                                                     const uint8_t* __restrict__ reset, const float* h_in, float* h_out, const float* c_in,
+                                                                     float* c_out, float* __restrict__ mu_out, float* __restrict__ act_out) {
+    using L = LstmWideLds<MAXW>;
+    constexpr int H = L::H, HP = L::HP, EPT = MR * HP / 256;  // a thread's elements of a pass's [16][256] columns
+    static_assert(L::FLOATS * sizeof(float) <= 160 * 1024, "within the CU's LDS");
+    __shared__ __attribute__((aligned(16))) float lds[L::FLOATS];
+    float *gt = lds, *ht = lds + L::A, *hn = ht + L::HT, *xt = hn + L::HT;
+    const int r0 = blockIdx.x * MR, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int k = threadIdx.x; k < MR * KC; k += blockDim.x) {
+        const int r = k / KC, c = k - r * KC;
+        xt[r * L::LDX + c] = (r0 + r < N && c < BG_NUM_OBS) ? obs[(size_t)(r0 + r) * stride + c] : 0.f;
+    }
+    for (int k = threadIdx.x; k < MR * H; k += blockDim.x) {
+        const int r = k / H, c = k - r * H, row = r0 + r;
+        ht[r * L::LDH + c] = (row < N && !(reset && reset[row])) ? h_in[(size_t)row * H + c] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int p = 0; p < 2; p++) {
+        float cv[EPT];
+#pragma unroll
+        for (int e = 0; e < EPT; e++) {
+            const int k = threadIdx.x + 256 * e, r = k / HP, c = HP * p + (k - r * HP), row = r0 + r;
+            cv[e] = (row < N && !(reset && reset[row])) ? c_in[(size_t)row * H + c] : 0.f;
+        }
+#pragma unroll 1
+        for (int g = 0; g < 4; g++) {
+            const int w0 = g * H + HP * p;  // the first of this gate's 256 rows of W_ih / W_hh in this pass
+            first_layer<L::LDX, L::LDG, false>(cell.W_ih + (size_t)w0 * BG_NUM_OBS, cell.b_ih + w0, BG_NUM_OBS, HP, xt, gt + g * HP, wave, lane);
+            layer<L::LDH, L::LDG, true>(cell.W_hh + (size_t)w0 * H, cell.b_hh + w0, H, HP, false, ht, gt + g * HP, wave, lane);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < EPT; e++) {
+            const int k = threadIdx.x + 256 * e, r = k / HP, cl = k - r * HP, c = HP * p + cl, row = r0 + r;
+            const float* a = gt + r * L::LDG + cl;
+            const bg::LstmGates s = bg::lstm_gates(a[0], a[HP], a[2 * HP], a[3 * HP], cv[e]);
+            hn[r * L::LDH + c] = s.h;
+            if (row < N) {
+                h_out[(size_t)row * H + c] = s.h;
+                c_out[(size_t)row * H + c] = s.c;
+            }
+        }
+        __syncthreads();  // (pass 1 overwrites the gate tile; behind pass 1 the trunk's tiles do)
+    }
+    float(*buf)[MR * L::LDA] = reinterpret_cast<float(*)[MR * L::LDA]>(lds);
+    layer<L::LDH, L::LDA>(net.W[0], net.b[0], H, net.out[0], true, hn, buf[0], wave, lane);
+    __syncthreads();
+    int cur = 0;
+    for (int l = 1; l < net.n; l++) {
+        layer<L::LDA>(net.W[l], net.b[l], net.in[l], net.out[l], l + 1 < net.n, buf[cur], buf[cur ^ 1], wave, lane);
+        __syncthreads();
+        cur ^= 1;
+    }
+    sample<L::LDA, false>(buf[cur], N, r0, logstd, seed, counter, mu_out, act_out, false, 0.f, 0);
+}
+
 // ---- an LSTM student (distillation.student_cell: "lstm"): bg_distill_act_lstm, bg_distill_act_lstm_own.  distill_act_gru_kernel's split grid, the DAgger
 // choice a template flag again, but not its LDS plan: there the cell's four tiles (gi | gh | h | x) are so much larger than the teacher's two that the
 // teacher's half simply takes the front of the block.  Here the two halves are of one size and of different shapes, and ONE block serves both:
@@ -852,10 +931,13 @@ extern "C" int bg_distill_act_gru_own(int32_t N, const float* teacher_obs, int32
 }
 
 // ---- the LSTM cell's entry points
-static int fill_lstm(const std::string& who, const bg_lstm_desc* lstm, GruCell& cell) {
+// wide: the launch has a form for hidden = 512 (bg_actor_sample_lstm: actor_lstm_wide_sample_kernel)
+static int fill_lstm(const std::string& who, const bg_lstm_desc* lstm, GruCell& cell, bool wide = false) {
     if (!lstm || !lstm->W_ih || !lstm->W_hh || !lstm->b_ih || !lstm->b_hh) return bg_set_error(-1, (who + ": bad argument (lstm)").c_str());
     if (lstm->in != BG_NUM_OBS) return bg_set_error(-4, (who + ": the cell takes one observation (lstm.in = 47)").c_str());
-    if (lstm->hidden != 128 && lstm->hidden != 256) return bg_set_error(-4, (who + ": unsupported lstm.hidden (128 or 256)").c_str());
+    if (wide && lstm->hidden == 512) {}
+    else if (lstm->hidden != 128 && lstm->hidden != 256)
+        return bg_set_error(-4, (who + (wide ? ": unsupported lstm.hidden (128, 256 or 512)" : ": unsupported lstm.hidden (128 or 256)")).c_str());
     if ((uintptr_t)lstm->W_hh & 15) return bg_set_error(-1, (who + ": lstm.W_hh must be 16-byte aligned").c_str());
     cell = GruCell{lstm->W_ih, lstm->W_hh, lstm->b_ih, lstm->b_hh};  // (the four pointers; the layout is torch.nn.LSTMCell's, 4 hidden rows)
     return 0;
@@ -868,7 +950,7 @@ extern "C" int bg_actor_sample_lstm(int32_t N, const float* obs, int32_t obs_str
     if (N <= 0 || !obs || !layers || !logstd || !h_in || !h_out || !c_in || !c_out || !actions) return bg_set_error(-1, (who + ": bad argument").c_str());
     if (obs_stride < BG_NUM_OBS) return bg_set_error(-1, (who + ": bad argument (obs_stride: at least the 47 columns the cell reads)").c_str());
     GruCell cell;
-    if (const int rc = fill_lstm(who, lstm, cell)) return rc;
+    if (const int rc = fill_lstm(who, lstm, cell, true)) return rc;
     ActorNet net;
     int maxw = 0;
     if (const int rc = fill_net((who + " (trunk)").c_str(), n_layers, layers, 0, net, maxw, lstm->hidden)) return rc;
@@ -876,6 +958,12 @@ extern "C" int bg_actor_sample_lstm(int32_t N, const float* obs, int32_t obs_str
     const bool wide = maxw > 256;
     const dim3 grid((N + MR - 1) / MR), block(256);
     hipStream_t st = (hipStream_t)stream;
+    if (H == 512) {
+        if (!wide) hipLaunchKernelGGL(actor_lstm_wide_sample_kernel<256>, grid, block, 0, st, N, obs, obs_stride, cell, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, c_in, c_out, mu, actions);
+        else hipLaunchKernelGGL(actor_lstm_wide_sample_kernel<512>, grid, block, 0, st, N, obs, obs_stride, cell, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, c_in, c_out, mu, actions);
+        HIP_OK(hipGetLastError());
+        return 0;
+    }
     BG_GRU_LAUNCH(actor_lstm_sample_kernel, , N, obs, obs_stride, cell, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, c_in, c_out, mu, actions);
     HIP_OK(hipGetLastError());
     return 0;

@@ -5,7 +5,7 @@
 // As in bg_gru.hip the x-side gi = X W_ih^T + b_ih runs on all T N rows at once (bg_mlp_layer_forward) and a workgroup (4 waves) owns 16 envs and walks the
 // steps itself, the state tile [16][H + 4] in LDS, the operands of v_mfma_f32_16x16x4_f32 as there:
 //     A[i = lane & 15][k = lane >> 4]  h (forward) / dg (backward) from LDS, one ds_read_b128 feeds 4 MFMAs
-//     B[k = lane >> 4][j = lane & 15]  W_hh from global memory / L2: 262 kB at H = 128, 1 MB at H = 256
+//     B[k = lane >> 4][j = lane & 15]  W_hh from global memory / L2: 262 kB at H = 128, 1 MB at H = 256, 4 MB at H = 512
 //     C/D: column j = lane & 15, row i = (lane >> 4) * 4 + reg
 // What the LSTM changes:
 //   - the two sides of a pre-activation simply add, so the forward accumulators START from gi + b_hh and the gate arithmetic (bg_lstm.h, the rollout's)
@@ -275,6 +275,134 @@ __global__ __launch_bounds__(256) void lstm_sequence_backward_kernel(int T, int 
     }
 }
 
+// ---- H = 512 (legged_gym's rnn_hidden_size; algorithm.rnn_hidden_size: 512 with rnn_cell: "lstm").  The forward kernel and the bias sums above are
+// instantiated at 512 as they are (the forward: c and b_hh in 32 + 32 registers of a lane, two h tiles = 66,048 B of LDS, no scratch).  The backward
+// kernel above is not: its dg tile [16][4H + 4] and the dh tile come to 164,352 B, over the CU's 160 kB, and its seven prefetched operands of 32
+// elements per thread to 224 registers.  This form runs the K = 4H GEMM carry_h = dg W_hh in TWO K PASSES over gate pairs, in this fixed order:
+//   pass 0: K = the rows [0, 2H) of W_hh, the gates (i, f);   pass 1: K = the rows [2H, 4H), the gates (g, o).
+// The elementwise phase of a step computes all four gate gradients of a thread's 32 elements, writes them to dg in memory, puts (di, df) into the ONE
+// tile [16][2H + 4] and keeps (dg_g, do) in registers; the MFMAs of pass 0 consume the tile and park their sums in the dh tile (free in this phase: the
+// carry was consumed by the elementwise phase), each lane its own elements; behind a barrier the tile takes (dg_g, do) and the MFMAs of pass 1 start
+// their accumulator from the parked sums: an element is ((acc0 + acc1 of pass 0) + pass 1's even k-groups) + pass 1's odd k-groups, k ascending within
+// each.  LDS 65,792 + 33,024 = 98,816 B.  dc stays in the elementwise mapping's 32 registers.  The operands of a step are loaded in its elementwise
+// phase, eight elements' loads in flight at a time, not under the step above's GEMM (no registers for them beside dc, dg_g and do): per step that
+// exposes a few memory round trips beside 2 x 2,048 MFMAs per wave.  dh0 / dc0 / reset may be NULL as above.
+__global__ __launch_bounds__(256) void lstm_sequence_backward_wide_kernel(int T, int N, const float* __restrict__ dh_ext, const float* __restrict__ gates,
+                                                                          const float* __restrict__ c_prev, const uint8_t* __restrict__ reset,
+                                                                          const float* __restrict__ W, float* __restrict__ dg, float* __restrict__ dh0,
+                                                                          float* __restrict__ dc0) {
+    constexpr int H = 512, LDH = H + 4, LDG = 2 * H + 4, TPW = H / 64, CPT = 2 * H / 128, EPT = MR * H / 256, EB = 8;
+    __shared__ __attribute__((aligned(16))) float gt[MR * LDG];     // dg of the step, one gate pair at a time: the GEMM's A operand
+    __shared__ __attribute__((aligned(16))) float carry[MR * LDH];  // dh carried to the step below; between the passes: pass 0's sums
+    static_assert(sizeof(float) * (MR * LDG + MR * LDH) <= 160 * 1024, "within the CU's LDS");
+    const int r0 = blockIdx.x * MR, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, kg = lane >> 4;
+    for (int k = threadIdx.x; k < MR * LDH; k += blockDim.x) carry[k] = 0.f;
+    __syncthreads();
+    // the 32 weights of column tile j, k-chunk kc of pass `pass` for this lane: W_hh[2H pass + 128 kc + 16 u + 4 kg + e][16 j + r], u = 0 .. 7, e = 0 .. 3
+    auto fetch = [&](f32x4 (&w)[8], int pass, int s) {
+        const int j = wave + 4 * (s / CPT), kc = s % CPT;
+        const float* wcol = W + (size_t)(pass * 2 * H + kc * 128 + 4 * kg) * H + j * 16 + r;
+#pragma unroll
+        for (int u = 0; u < 8; u++) w[u] = f32x4{wcol[(size_t)(16 * u) * H], wcol[(size_t)(16 * u + 1) * H], wcol[(size_t)(16 * u + 2) * H], wcol[(size_t)(16 * u + 3) * H]};
+    };
+    float dcc[EPT], dgg[EPT], dout[EPT];
+#pragma unroll
+    for (int e = 0; e < EPT; e++) dcc[e] = 0.f;
+    for (int t = T - 1; t >= 0; t--) {
+        const size_t tn = (size_t)t * N;
+        bool rq[4];  // the reset flags of the rows this lane finishes behind the GEMM
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int row = r0 + kg * 4 + q;
+            rq[q] = row >= N || (reset && reset[tn + row]);
+        }
+#pragma unroll
+        for (int eb = 0; eb < EPT; eb += EB) {
+            float in[EB][7];
+            bool rs[EB];
+#pragma unroll
+            for (int x = 0; x < EB; x++) {
+                const int k = threadIdx.x + 256 * (eb + x), rr = k / H, cc = k - rr * H, row = r0 + rr;
+                rs[x] = false;
+                if (row < N) {
+                    const float* g = gates + (tn + row) * (5 * H) + cc;
+                    in[x][0] = dh_ext[(tn + row) * H + cc];
+                    in[x][1] = g[0]; in[x][2] = g[H]; in[x][3] = g[2 * H]; in[x][4] = g[3 * H]; in[x][5] = g[4 * H];
+                    in[x][6] = c_prev[(tn + row) * H + cc];
+                    rs[x] = reset && reset[tn + row];
+                }
+            }
+#pragma unroll
+            for (int x = 0; x < EB; x++) {
+                const int e = eb + x, k = threadIdx.x + 256 * e, rr = k / H, cc = k - rr * H, row = r0 + rr;
+                float di = 0.f, df = 0.f;
+                dgg[e] = dout[e] = 0.f;
+                if (row < N) {
+                    const float dh = in[x][0] + carry[rr * LDH + cc];
+                    const float gi_ = in[x][1], gf = in[x][2], gg = in[x][3], go = in[x][4], tc = in[x][5], cp = in[x][6];
+                    const float dc = dcc[e] + dh * go * (1.0f - tc * tc);
+                    dout[e] = dh * tc * (go * (1.0f - go));
+                    di = dc * gg * (gi_ * (1.0f - gi_));
+                    df = dc * cp * (gf * (1.0f - gf));
+                    dgg[e] = dc * gi_ * (1.0f - gg * gg);
+                    dcc[e] = rs[x] ? 0.f : dc * gf;
+                    float* o = dg + (tn + row) * (4 * H) + cc;
+                    o[0] = di; o[H] = df; o[2 * H] = dgg[e]; o[3 * H] = dout[e];
+                }
+                float* gl = gt + rr * LDG + cc;
+                gl[0] = di; gl[H] = df;
+            }
+            __builtin_amdgcn_sched_barrier(0);  // (the next eight elements' loads stay behind these eight's arithmetic: 56 operand registers, not 224)
+        }
+        __syncthreads();
+        constexpr int steps = TPW * CPT;
+#pragma unroll 1
+        for (int pass = 0; pass < 2; pass++) {
+            if (pass) {
+                __syncthreads();  // every wave is through with the (i, f) tile
+#pragma unroll
+                for (int e = 0; e < EPT; e++) {
+                    const int k = threadIdx.x + 256 * e, rr = k / H, cc = k - rr * H;
+                    float* gl = gt + rr * LDG + cc;
+                    gl[0] = dgg[e]; gl[H] = dout[e];
+                }
+                __syncthreads();
+            }
+            f32x4 cur[8], nxt[8] = {};
+            fetch(cur, pass, 0);
+            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
+            for (int s = 0; s < steps; s++) {
+                if (s + 1 < steps) fetch(nxt, pass, s + 1);
+                const int j = wave + 4 * (s / CPT), kc = s % CPT, col = j * 16 + r;
+                if (kc == 0) {
+                    acc0 = acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
+                    if (pass) {  // pass 0's sums of this lane's own elements
+#pragma unroll
+                        for (int q = 0; q < 4; q++) acc0[q] = carry[(kg * 4 + q) * LDH + col];
+                    }
+                }
+                const float* arow = gt + r * LDG + kc * 128 + 4 * kg;
+                BG_LSTM_MFMA32(acc0, acc1, arow, cur)
+                if (kc == CPT - 1) {
+#pragma unroll
+                    for (int q = 0; q < 4; q++) carry[(kg * 4 + q) * LDH + col] = (pass && rq[q]) ? 0.f : acc0[q] + acc1[q];  // (no other thread reads the tile in this phase)
+                }
+#pragma unroll
+                for (int u = 0; u < 8; u++) cur[u] = nxt[u];
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int e = 0; e < EPT; e++) {
+        const int k = threadIdx.x + 256 * e, rr = k / H, cc = k - rr * H, row = r0 + rr;
+        if (row < N) {
+            if (dh0) dh0[(size_t)row * H + cc] = carry[rr * LDH + cc];
+            if (dc0) dc0[(size_t)row * H + cc] = dcc[e];
+        }
+    }
+}
+
 // The cell's bias gradients: the column sums of dg [B][4H] as ONE launch that leaves one record [4H] per 128-row block, for bg_reduce_problems of the
 // update's deferred group to add up (bg_reduce.h): b_ih's and b_hh's gradients are the same sums, two finishes on the same records.  Memory-bound, the
 // design of bg_gru_bias_partial on one tensor: a lane owns one 16-byte column per 64-lane group (H / 64 groups: a wave reads 1 KiB runs), a wave the
@@ -305,7 +433,7 @@ __global__ __launch_bounds__(256) void lstm_bias_partial_kernel(int B, const flo
 
 int check_shape(const char* who, int32_t T, int32_t N, int32_t H) {
     if (T <= 0 || N <= 0) return bg_fail(who, -1, "bad argument (T, N: at least 1)");
-    if (H != 128 && H != 256) return bg_fail(who, -4, "unsupported H (128 or 256)");
+    if (H != 128 && H != 256 && H != 512) return bg_fail(who, -4, "unsupported H (128, 256 or 512)");
     return 0;
 }
 
@@ -320,6 +448,7 @@ extern "C" int bg_lstm_sequence_forward(int32_t T, int32_t N, int32_t H, const f
     const dim3 grid((N + MR - 1) / MR), block(256);
     hipStream_t st = (hipStream_t)stream;
     if (H == 128) hipLaunchKernelGGL(lstm_sequence_forward_kernel<128>, grid, block, 0, st, T, N, gi, h0, c0, reset, W_hh, b_hh, h_prev, c_prev, h, c, gates);
+    else if (H == 512) hipLaunchKernelGGL(lstm_sequence_forward_kernel<512>, grid, block, 0, st, T, N, gi, h0, c0, reset, W_hh, b_hh, h_prev, c_prev, h, c, gates);
     else hipLaunchKernelGGL(lstm_sequence_forward_kernel<256>, grid, block, 0, st, T, N, gi, h0, c0, reset, W_hh, b_hh, h_prev, c_prev, h, c, gates);
     HIP_OK(hipGetLastError());
     return 0;
@@ -333,6 +462,7 @@ extern "C" int bg_lstm_sequence_backward(int32_t T, int32_t N, int32_t H, const 
     const dim3 grid((N + MR - 1) / MR), block(256);
     hipStream_t st = (hipStream_t)stream;
     if (H == 128) hipLaunchKernelGGL(lstm_sequence_backward_kernel<128>, grid, block, 0, st, T, N, dh_ext, gates, c_prev, reset, W_hh, dg, dh0, dc0);
+    else if (H == 512) hipLaunchKernelGGL(lstm_sequence_backward_wide_kernel, grid, block, 0, st, T, N, dh_ext, gates, c_prev, reset, W_hh, dg, dh0, dc0);
     else hipLaunchKernelGGL(lstm_sequence_backward_kernel<256>, grid, block, 0, st, T, N, dh_ext, gates, c_prev, reset, W_hh, dg, dh0, dc0);
     HIP_OK(hipGetLastError());
     return 0;
@@ -341,12 +471,13 @@ extern "C" int bg_lstm_sequence_backward(int32_t T, int32_t N, int32_t H, const 
 extern "C" int bg_lstm_bias_partial(int32_t B, int32_t H, const float* dg, float* records, void* stream) {
     const char* who = "bg_lstm_bias_partial";
     if (B <= 0) return bg_fail(who, -1, "bad argument (B: at least 1)");
-    if (H != 128 && H != 256) return bg_fail(who, -4, "unsupported H (128 or 256)");
+    if (H != 128 && H != 256 && H != 512) return bg_fail(who, -4, "unsupported H (128, 256 or 512)");
     if (!dg || !records) return bg_fail(who, -1, "bad argument");
     if (!aligned16(dg) || !aligned16(records)) return bg_fail(who, -1, "dg and records must be 16-byte aligned");
     const dim3 grid((B + BP_ROWS - 1) / BP_ROWS), block(256);
     hipStream_t st = (hipStream_t)stream;
     if (H == 128) hipLaunchKernelGGL(lstm_bias_partial_kernel<128>, grid, block, 0, st, B, dg, records);
+    else if (H == 512) hipLaunchKernelGGL(lstm_bias_partial_kernel<512>, grid, block, 0, st, B, dg, records);
     else hipLaunchKernelGGL(lstm_bias_partial_kernel<256>, grid, block, 0, st, B, dg, records);
     HIP_OK(hipGetLastError());
     return 0;

@@ -213,7 +213,7 @@ int bg_wgrad_group_fill(const bg_wgrad_problem* problems, int32_t count, WgradGr
         if (q.M <= 0 || !q.G || !q.A || !q.dW || !q.scratch) return bg_fail(who, -1, "bad argument");
         if ((((uintptr_t)q.G | (uintptr_t)q.A | (uintptr_t)q.scratch) & 15) != 0) return bg_fail(who, -1, "G, A, scratch must be 16-byte aligned");
         if (q.C_in_real == q.C_in && (((uintptr_t)q.dW) & 15) != 0) return bg_fail(who, -1, "dW must be 16-byte aligned");
-        if (q.C_out % 128 != 0 || q.C_out > 1024) return bg_fail(who, -4, "unsupported C_out (multiples of 128 up to 1024)");
+        if (q.C_out % 128 != 0 || q.C_out > 2048) return bg_fail(who, -4, "unsupported C_out (multiples of 128 up to 2048)");
         if (q.C_in != 64 && (q.C_in % 128 != 0 || q.C_in > 1024)) return bg_fail(who, -4, "unsupported C_in (64, or multiples of 128 up to 1024)");
         if (q.C_in_real <= 0 || q.C_in_real > q.C_in) return bg_fail(who, -1, "C_in_real must be in [1, C_in]");
         if (q.M % 2 != 0) return bg_fail(who, -4, "M must be even (rows are consumed in pairs)");

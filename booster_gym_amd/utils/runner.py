@@ -107,29 +107,40 @@ def hidden_widths(cfg):
 def actor_memory_of(cfg):
     """algorithm.actor_memory as the width H of the GRU cell in front of the actor: 0 (absent: the shipped yaml does not list it) = none.  Set by a
     recurrent distilled student's checkpoint on re-entry (distill.student_overrides).  Pure.  ValueError naming the key for any other value than 0,
-    128 or 256, and with estimator.enabled."""
-    H = (cfg.get("algorithm", {}) or {}).get("actor_memory", 0) or 0
-    if isinstance(H, bool) or not isinstance(H, int) or H not in (0, 128, 256):
-        raise ValueError(f"algorithm.actor_memory must be 0, 128 or 256 (the width of a recurrent student's GRU cell, distillation.student_memory), got {H!r}")
+    128 or 256 (512 as well with algorithm.rnn_cell: "lstm", the width of an actor trained under algorithm.rnn_hidden_size: 512), and with
+    estimator.enabled."""
+    alg = cfg.get("algorithm", {}) or {}
+    H = alg.get("actor_memory", 0) or 0
+    if isinstance(H, bool) or not isinstance(H, int) or H not in (0,) + rnn_widths(alg.get("rnn_cell")):
+        raise ValueError(f"algorithm.actor_memory must be 0, 128 or 256 (the width of a recurrent student's GRU cell, distillation.student_memory; 512 is "
+                         f"the LSTM's width: with algorithm.rnn_cell: \"lstm\" only), got {H!r}")
     if H and estimator_enabled(cfg):
         raise ValueError(f"algorithm.actor_memory = {H} is not supported with estimator.enabled: true")
     return H
 
 
-RNN_WIDTHS = (128, 256)  # the widths of the GRU cell that the rollout's and the update's kernels take
+RNN_WIDTHS = {"gru": (128, 256), "lstm": (128, 256, 512)}  # per cell: the widths that the rollout's and the update's kernels take
+
+
+def rnn_widths(cell):
+    """The widths of algorithm.rnn_hidden_size / algorithm.actor_memory under algorithm.rnn_cell = `cell`: the GRU's for every value that is not
+    "lstm" (absent, null, "gru", and what rnn_cell_of refuses in its own words)."""
+    return RNN_WIDTHS["lstm" if isinstance(cell, str) and cell == "lstm" else "gru"]
 
 
 def rnn_hidden_size_of(cfg, world_size=1):
     """algorithm.rnn_hidden_size (legged_gym's name; an addition of this build) as the width H of the GRU cell in front of an actor that PPO trains:
-    0 (absent: the shipped yaml does not list it) = a feed-forward actor.  Pure.  ValueError naming the key for any other value than 0, 128 or 256, for
+    0 (absent: the shipped yaml does not list it) = a feed-forward actor.  Pure.  ValueError naming the key for any other value than 0, 128 or 256 (512
+    as well with algorithm.rnn_cell: "lstm": legged_gym's width, which the LSTM kernels alone have a form for), for
     an algorithm.rnn_type other than "gru" (the one cell there is), for an algorithm.actor_memory of another width, and, naming both keys, with every
     option a recurrent actor does not compose with: estimator.enabled, env.frame_stack above 1, terrain.actor_heights, algorithm.symmetry_loss,
     algorithm.empirical_normalization, runner.num_mini_batches above 1, more than one rank."""
     alg = cfg.get("algorithm", {}) or {}
     H = alg.get("rnn_hidden_size", 0)
     H = 0 if H is None else H
-    if isinstance(H, bool) or not isinstance(H, int) or H not in (0,) + RNN_WIDTHS:
-        raise ValueError(f"algorithm.rnn_hidden_size must be 0, 128 or 256 (the width of the GRU cell in front of the actor; 0 or absent: none), got {H!r}")
+    if isinstance(H, bool) or not isinstance(H, int) or H not in (0,) + rnn_widths(alg.get("rnn_cell")):
+        raise ValueError(f"algorithm.rnn_hidden_size must be 0, 128 or 256 (the width of the GRU cell in front of the actor; 0 or absent: none; 512 is the "
+                         f"LSTM's width: with algorithm.rnn_cell: \"lstm\" only), got {H!r}")
     kind = alg.get("rnn_type")
     if kind is not None and kind != "gru":
         raise ValueError(f"algorithm.rnn_type = {kind!r}: the cell of algorithm.rnn_hidden_size is a GRU; the key, if present, must be \"gru\" (an LSTM cell is "

@@ -569,15 +569,17 @@ int bg_gru_bias_partial(int32_t B, int32_t H, const float* dgi, const float* dgh
 /* PPO on an LSTM actor (T1.yaml algorithm.rnn_cell: "lstm"; legged_gym / rsl_rl's ActorCriticRecurrent with its default cell): an LSTM cell in
  * torch.nn.LSTMCell's layout and gate order i | f | g | o, W_ih [4 hidden][in], W_hh [4 hidden][hidden] (16-byte aligned), b_ih / b_hh [4 hidden]:
  *   p = x W_ih^T + b_ih + h W_hh^T + b_hh, i = sigmoid(p_i), f = sigmoid(p_f), g = tanh(p_g), o = sigmoid(p_o), c' = f c + i g, h' = o tanh(c').
- * in = 47 (the newest single observation), hidden = 128 or 256; anything else is -4. */
+ * in = 47 (the newest single observation), hidden = 128 or 256, and 512 for bg_actor_sample_lstm alone (legged_gym's rnn_hidden_size; the distillation
+ * launches keep 128 and 256); anything else is -4. */
 typedef struct bg_lstm_desc {
     const float *W_ih, *W_hh, *b_ih, *b_hh;
     int32_t in, hidden;
 } bg_lstm_desc;
 /* bg_actor_sample_gru with that cell: h = h_in, c = c_in [N][hidden] (both read as zero where reset [N] (uint8, may be NULL) is non-zero), h' to h_out,
  * c' to c_out, the trunk `layers` (layers[0].in = hidden) on h': mu [N][12] (may be NULL), actions = mu + exp(logstd) n with bg_actor_sample_mlp's
- * noise (the same stream).  h_in == h_out and c_in == c_out are allowed.  Nothing is written past row N.  Violations: -1 / -4 with a message, before
- * any launch. */
+ * noise (the same stream).  h_in == h_out and c_in == c_out are allowed.  Nothing is written past row N.  hidden = 512: a kernel of its own that runs
+ * the gate tile in two column passes of 256 h-columns and keeps h' in a second h tile (135 kB of LDS, one workgroup per CU); the same sums in the same
+ * order per element.  Violations: -1 / -4 with a message, before any launch. */
 int bg_actor_sample_lstm(int32_t N, const float* obs, int32_t obs_stride, const bg_lstm_desc* lstm, int32_t n_layers, const bg_mlp_layer_desc* layers,
                          const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, const float* c_in,
                          float* c_out, float* mu, float* actions, void* stream);
@@ -600,7 +602,7 @@ int bg_distill_act_lstm_own(int32_t N, const float* teacher_obs, int32_t teacher
                             const bg_mlp_layer_desc* teacher, int32_t scan_points, const bg_lstm_desc* lstm, int32_t n_student, const bg_mlp_layer_desc* student,
                             const float* student_logstd, uint64_t seed, uint64_t counter, float beta, int32_t teacher_noise, const uint8_t* reset,
                             const float* state_in, float* state_out, float* student_mu, float* actions, float* teacher_mu, void* stream);
-/* The recurrence of that actor's update over T steps as ONE launch each way (csrc/bg_lstm.hip); H = 128 or 256, any N >= 1, T >= 1; a workgroup owns 16
+/* The recurrence of that actor's update over T steps as ONE launch each way (csrc/bg_lstm.hip); H = 128, 256 or 512, any N >= 1, T >= 1; a workgroup owns 16
  * envs and walks the steps itself, h in an LDS tile, c in registers; W_hh [4H][H] (16-byte aligned) streams from L2.
  * Forward: gi [T][N][4H] the x-side pre-activations (b_ih included), h0 / c0 [N][H] the states entering step 0 (NULL: zero), reset [T][N] (uint8, NULL:
  * none): non-zero = both states entering step t are zero.  Out: h_prev, c_prev [T][N][H] the states entering each step after the reset, h, c [T][N][H]
@@ -611,13 +613,14 @@ int bg_lstm_sequence_forward(int32_t T, int32_t N, int32_t H, const float* gi, c
  * T - 1):  dh = dh_ext[t] + carry_h, do = dh tanh_c, dc = carry_c + dh o (1 - tanh_c^2), di = dc g, dg_ = dc i, df = dc c_prev,
  *   dg[t] = [di i (1 - i) | df f (1 - f) | dg_ (1 - g^2) | do o (1 - o)] ([T][N][4H]: the gradient of BOTH sides' pre-activations),
  *   carry_c = dc f, carry_h = dg[t] W_hh, both zero for a row with reset[t].
- * dh0, dc0 [N][H] (each may be NULL): the carries left after step 0.  Deterministic. */
+ * dh0, dc0 [N][H] (each may be NULL): the carries left after step 0.  Deterministic.  H = 512: a kernel of its own whose K = 4H product runs in two K
+ * passes in a fixed order, the rows [0, 2H) of W_hh (gates i, f) first, then [2H, 4H) (g, o), on one dg tile [16][2H + 4] of LDS. */
 int bg_lstm_sequence_backward(int32_t T, int32_t N, int32_t H, const float* dh_ext, const float* gates, const float* c_prev, const uint8_t* reset,
                               const float* W_hh, float* dg, float* dh0, float* dc0, void* stream);
 /* The cell's bias gradients without their finish: ONE launch in which workgroup g sums rows [128 g, min(128 g + 128, B)) of dg ([B][4H]) down their columns
  * and writes record g of `records` ([ceil(B / 128)][4H] floats).  Rows at or beyond B are never read, nothing is written past record ceil(B / 128); fixed
  * order, no atomics: deterministic.  b_ih's and b_hh's gradients are the same sums: the finish is two bg_reduce_problems on the same records (partial =
- * records, groups = ceil(B / 128), record = n_out = n[0] = 4H), out[0] = b_ih's gradient in one and b_hh's in the other.  B >= 1; H = 128 or 256 (else
+ * records, groups = ceil(B / 128), record = n_out = n[0] = 4H), out[0] = b_ih's gradient in one and b_hh's in the other.  B >= 1; H = 128, 256 or 512 (else
  * -4); both pointers 16-byte aligned (-1). */
 int bg_lstm_bias_partial(int32_t B, int32_t H, const float* dg, float* records, void* stream);
 /* Fused global-norm clip + Adam over one flat parameter buffer (runner.py:162-165); lr is read from device memory
@@ -656,7 +659,7 @@ int bg_optimizer_step(int32_t n, float* params, float* grads, float* exp_avg, fl
 int bg_elu_backward_colsum(int32_t B, int32_t C, float* grad, const float* act, float* colsum, float* scratch, void* stream);
 
 /* Fused MLP layer forward: Y [M][N] = act(X [M][K] . W[N][K]^T + bias[N]) in fp32 MFMA with bias + ELU in the GEMM epilogue
- * (utils/model.py:9-26 Linear + ELU).  Supported: K in {64, 128, 256, 512}, N a multiple of 128 up to 1024; other shapes return -4 (caller uses the
+ * (utils/model.py:9-26 Linear + ELU).  Supported: K in {64, 128, 256, 512}, N a multiple of 128 up to 2048 (an LSTM cell's 4 x 512 gate rows); other shapes return -4 (caller uses the
  * library GEMM).  X, W, bias and Y 16-byte aligned (-1 otherwise).  Exactly the M rows of Y are written; rows of X at or beyond M are never read. */
 int bg_mlp_layer_forward(int32_t M, int32_t K, int32_t N, const float* X, const float* W, const float* bias, float* Y, int32_t elu, void* stream);
 /* The three hidden Linear + ELU layers of one network (utils/model.py:9-26, forward of runner.py:132,147) in ONE launch: Y1 = elu(X W1^T + b1) [M][N1],

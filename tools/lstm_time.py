@@ -9,7 +9,10 @@
           bg_gru_bias_partial with its one;
       (4) the training loop (tools/actor_memory_time.py's `loop`), rnn_hidden_size 128 with rnn_cell "gru" and "lstm": a Runner each in a process of
           its own, every child under its own time limit.
-  `only` = "kernels" runs (1) to (3), "loop" (4).  The committed profile carries sections this tool does not write: bench.py of this tree against a
+  `only` = "kernels" runs (1) to (3), "loop" (4); "wide" (out: profiles/lstm_512_time.txt) runs the LSTM at H = 512 (algorithm.rnn_hidden_size: 512)
+  beside the LSTM at H = 256 in the same run: the rollout launch, both recurrences, the bias sums, the 24 bg_mlp_layer_forward(num_envs, H, 4H)
+  launches and the peak time of the FLOPs at either width, then the training loop at 256 and 512; "wide_kernels" / "wide_loop" run its halves.
+  The committed profile carries sections this tool does not write: bench.py of this tree against a
   checkout of its parent commit, and the SHA-256 digests."""
 import os
 import subprocess
@@ -23,7 +26,8 @@ from actor_memory_time import DEV, LINES, _best, _descs, _orders, loop, say
 
 PEAK_FP32_MFMA = 157.3e12  # MI355X, fp32 matrix FLOP/s (vendor figure)
 T = 24
-SIDES = (("rnn_cell gru", {"algorithm.rnn_hidden_size": 128}), ("rnn_cell lstm", {"algorithm.rnn_hidden_size": 128, "algorithm.rnn_cell": "lstm"}))
+SIDES = (("rnn_cell gru", {"algorithm.rnn_hidden_size": 128}), ("rnn_cell lstm", {"algorithm.rnn_hidden_size": 128, "algorithm.rnn_cell": "lstm"}),
+         ("lstm 256", {"algorithm.rnn_hidden_size": 256, "algorithm.rnn_cell": "lstm"}), ("lstm 512", {"algorithm.rnn_hidden_size": 512, "algorithm.rnn_cell": "lstm"}))
 
 
 def rollout_launch(pairs, N):
@@ -98,31 +102,85 @@ def recurrences(pairs, N):
                 f"bg_gru_bias_partial + its finish {us['gru bias']:.1f} us ({B * 6 * H * 4 / 1e6:.0f} MB read)")
 
 
+def wide(pairs, N):
+    """The LSTM's launches at H = 512 beside the same launches at H = 256 (a quarter of the FLOPs), the sides alternating."""
+    from booster_gym_amd import _lib
+    from booster_gym_amd.utils.model import ActorCritic
+    from booster_gym_amd.utils.utils import reduce_group
+
+    lib, p, st, B, ck = _lib.load(), _lib.ptr, _lib.current_stream_ptr(), T * N, _lib.check
+    torch.manual_seed(1)
+    obs, act = torch.randn(N, 47, device=DEV), torch.empty(N, 12, device=DEV)
+    reset1, reset = (torch.rand(N, device=DEV) < 0.02).to(torch.uint8), (torch.rand(T, N, device=DEV) < 0.02).to(torch.uint8)
+    z = lambda *s: torch.zeros(*s, device=DEV)
+    r = lambda *s: torch.randn(*s, device=DEV)
+    fns, keep = {}, []
+    for H in (256, 512):
+        m = ActorCritic(12, 47, 14, memory_hidden=H, memory_cell="lstm").to(DEV)
+        d, s = (m.gru_descriptor(),) + _descs(m), z(2, N, H)
+        L = dict(gi=r(B, 4 * H), W=r(4 * H, H) * H ** -0.5, b=r(4 * H) * 0.1, s0=r(2, N, H), hp=z(B, H), cp=z(B, H), h=z(B, H), c=z(B, H), gates=z(B, 5 * H), dg=z(B, 4 * H),
+                 dh=r(B, H), x=r(N, H), Wl=r(4 * H, H), yl=z(N, 4 * H), rec=z((B + 127) // 128 * 4 * H), sums=[z(4 * H) for _ in range(2)])
+        fins = []
+        for sm in L["sums"]:
+            f = _lib.ReduceProblem()
+            f.partial, f.groups, f.record, f.n_out, f.out[0], f.n[0] = L["rec"].data_ptr(), (B + 127) // 128, 4 * H, 4 * H, sm.data_ptr(), 4 * H
+            fins.append(f)
+        keep.append((m, d, s, L, fins))
+        fns[f"act {H}"] = lambda k, H=H, m=m, d=d, s=s: ck(lib.bg_actor_sample_lstm(N, p(obs), 47, d[0], d[2], d[1], p(m.logstd), 1, k, p(reset1), p(s[0]), p(s[0]), p(s[1]),
+                                                                                      p(s[1]), None, p(act), st), "bg_actor_sample_lstm")
+        fns[f"fwd {H}"] = lambda k, H=H, L=L: ck(lib.bg_lstm_sequence_forward(T, N, H, p(L["gi"]), p(L["s0"][0]), p(L["s0"][1]), p(reset), p(L["W"]), p(L["b"]), p(L["hp"]), p(L["cp"]),
+                                                                               p(L["h"]), p(L["c"]), p(L["gates"]), st), "lstm fwd")
+        fns[f"bwd {H}"] = lambda k, H=H, L=L: ck(lib.bg_lstm_sequence_backward(T, N, H, p(L["dh"]), p(L["gates"]), p(L["cp"]), p(reset), p(L["W"]), p(L["dg"]), None, None, st), "lstm bwd")
+        fns[f"layers {H}"] = lambda k, H=H, L=L: [ck(lib.bg_mlp_layer_forward(N, H, 4 * H, p(L["x"]), p(L["Wl"]), p(L["b"]), p(L["yl"]), 0, st), "bg_mlp_layer_forward") for _ in range(T)]
+        fns[f"bias {H}"] = lambda k, H=H, L=L, fins=fins: (ck(lib.bg_lstm_bias_partial(B, H, p(L["dg"]), p(L["rec"]), st), "lstm bias"), reduce_group(fins))
+    for q in range(pairs):
+        us = {k: _best(f, 200 if k.startswith("act") else 50 if k.startswith("bias") else 10) for k, f in _orders(q, tuple(fns.items()))}
+        for what, k in (("rollout launch bg_actor_sample_lstm, trunk 256-128-128", "act"), (f"bg_lstm_sequence_forward, T = {T}", "fwd"),
+                        (f"bg_lstm_sequence_backward, T = {T}", "bwd"), (f"bg_lstm_bias_partial + its two finishes, B = {B}", "bias"),
+                        (f"the {T} bg_mlp_layer_forward({N}, H, 4H) launches a recurrence replaces", "layers")):
+            say(f"{what}, {N} envs: H = 512 {us[k + ' 512']:.1f} us, H = 256 {us[k + ' 256']:.1f} us (512 / 256 = {us[k + ' 512'] / us[k + ' 256']:.2f})")
+        for H in (256, 512):
+            flops = 2.0 * T * N * H * 4 * H
+            peak = flops / PEAK_FP32_MFMA * 1e6
+            say(f"  H = {H}: {flops / 1e9:.1f} GFLOP one way = {peak:.0f} us at the fp32-MFMA peak; forward = {us[f'fwd {H}'] / peak:.2f}x, backward = {us[f'bwd {H}'] / peak:.2f}x that; "
+                f"forward / layers = {us[f'fwd {H}'] / us[f'layers {H}']:.2f}, backward / layers = {us[f'bwd {H}'] / us[f'layers {H}']:.2f}")
+
+
+def loops(pairs, K, W, N, sides, base):
+    got = {}
+    for q in range(pairs):
+        for k, (name, over) in _orders(q, tuple((k, SIDES[k]) for k in sides)):
+            res = subprocess.run(["timeout", "-k", "10", "240", sys.executable, os.path.abspath(__file__), str(K), str(W), "1", str(N), os.devnull, f"one:{k}"],
+                                 capture_output=True, text=True, check=True)
+            for line in res.stdout.splitlines():
+                if line.startswith("training loop"):
+                    say(line)
+                elif line.startswith("MS "):
+                    got.setdefault(name, []).append(float(line[3:]))
+    for name, ms in got.items():
+        say(f"  {name}: {min(ms):.3f} to {max(ms):.3f} ms per iteration, best = {min(ms) / min(got[base]):.3f}x the best of {base}")
+
+
 if __name__ == "__main__":
     a = sys.argv[1:]
     K, W, pairs, N = (int(a[i]) if len(a) > i else v for i, v in enumerate((20, 5, 3, 4096)))
-    out = a[4] if len(a) > 4 and a[4] != "-" else os.path.join(ROOT, "profiles", "lstm_time.txt")
     only = a[5] if len(a) > 5 else ""
+    out = a[4] if len(a) > 4 and a[4] != "-" else os.path.join(ROOT, "profiles", "lstm_512_time.txt" if only.startswith("wide") else "lstm_time.txt")
     if only.startswith("one:"):  # a child of the loop section: one Runner in a process of its own
         name, over = SIDES[int(only[4:])]
         print("MS %.6f" % loop(name, over, K, W, N), flush=True)
         sys.exit(0)
     say(f"tools/lstm_time.py {' '.join(a) or f'{K} {W} {pairs} {N}'} on {torch.cuda.get_device_name(0)}")
-    if only != "loop":
-        rollout_launch(pairs, N)
-        recurrences(pairs, N)
-    if only != "kernels":
-        got = {}
-        for q in range(pairs):
-            for k, (name, over) in _orders(q, tuple(enumerate(SIDES))):
-                res = subprocess.run(["timeout", "-k", "10", "240", sys.executable, os.path.abspath(__file__), str(K), str(W), "1", str(N), os.devnull, f"one:{k}"],
-                                     capture_output=True, text=True, check=True)
-                for line in res.stdout.splitlines():
-                    if line.startswith("training loop"):
-                        say(line)
-                    elif line.startswith("MS "):
-                        got.setdefault(name, []).append(float(line[3:]))
-        for name, ms in got.items():
-            say(f"  {name}: {min(ms):.3f} to {max(ms):.3f} ms per iteration, best = {min(ms) / min(got['rnn_cell gru']):.3f}x the GRU loop's best")
+    if only.startswith("wide"):
+        if only != "wide_loop":
+            wide(pairs, N)
+        if only != "wide_kernels":
+            loops(pairs, K, W, N, (2, 3), "lstm 256")
+    else:
+        if only != "loop":
+            rollout_launch(pairs, N)
+            recurrences(pairs, N)
+        if only != "kernels":
+            loops(pairs, K, W, N, (0, 1), "rnn_cell gru")
     with open(out, "w") as f:
         f.write("\n".join(LINES) + "\n")
