@@ -236,6 +236,7 @@ SYMBOLS = [
     "bg_gru_bias_partial", "bg_gru_sequence_forward_group", "bg_gru_sequence_backward_group",
     "bg_actor_sample_lstm", "bg_lstm_sequence_forward", "bg_lstm_sequence_backward", "bg_lstm_bias_partial",
     "bg_distill_act_lstm", "bg_distill_act_lstm_own",
+    "bg_actor_sample_gru_row", "bg_actor_sample_lstm_row",
     "bg_rnd_reward",
     "bg_last_error", "bg_version",
 ]
@@ -319,6 +320,8 @@ def load():
         "bg_gru_sequence_backward": (i32, [i32, i32, i32] + [vp] * 9),
         "bg_gru_bias_partial": (i32, [i32, i32, vp, vp, vp, vp]),
         "bg_actor_sample_lstm": (i32, [i32, vp, i32, C.POINTER(LstmDesc), i32, C.POINTER(MlpLayerDesc), vp, u64, u64] + [vp] * 8),
+        "bg_actor_sample_gru_row": (i32, [i32, vp, i32, C.POINTER(GruDesc), i32, C.POINTER(MlpLayerDesc), vp, u64, u64, vp, vp, vp, vp, vp, vp]),
+        "bg_actor_sample_lstm_row": (i32, [i32, vp, i32, C.POINTER(LstmDesc), i32, C.POINTER(MlpLayerDesc), vp, u64, u64] + [vp] * 8),
         "bg_distill_act_lstm": (i32, [i32, vp, i32, i32, C.POINTER(MlpLayerDesc), i32, C.POINTER(LstmDesc), i32, C.POINTER(MlpLayerDesc), vp, u64, u64, f32, i32,
                                       vp, vp, vp, vp, vp, vp, vp]),
         "bg_distill_act_lstm_own": (i32, [i32, vp, i32, vp, i32, i32, C.POINTER(MlpLayerDesc), i32, C.POINTER(LstmDesc), i32, C.POINTER(MlpLayerDesc), vp, u64, u64,

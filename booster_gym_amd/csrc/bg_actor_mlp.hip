@@ -372,9 +372,24 @@ __global__ __launch_bounds__(256) void rnd_reward_kernel(int N, const float* __r
 //   with MAXW = 256.
 struct GruCell { const float *W_ih, *W_hh, *b_ih, *b_hh; };
 
-template <int H, int MAXW>
+// The x tile's compile-time width KX (algorithm.rnn_input: "row", bg_actor_sample_gru_row / _lstm_row): KC is the one-observation tile [16][48 + 4] of
+// every launch above; KX_ROW serves any cell input K in [47, 256], the actor's whole row (frames and height scan).  first_layer walks whole 48-column
+// k-chunks, so K = 256 reads through column 287 (against zero weights beyond K): the tile holds the 6 whole chunks, [16][288 + 4], zero from column K on,
+// so that no lane reads a neighbouring row (whose Inf or NaN times the zero weight would be a NaN) or past the tile.  292 = 36 mod 64 banks: the 16 rows
+// x 4 k-groups of an A-operand read fall on 64 different banks, as with 52.
+// The x-side product stays on first_layer's scalar-load form: layer's 16-byte loads need a row of W_ih to start on 16 bytes, which [gates][K] does only
+// when K % 4 == 0 (K = 234: 936 B rows), and a padded copy of the matrix is what first_layer exists to avoid (it could go stale against the parameters).
+constexpr int KX_ROW = 256;
+struct RowCell : GruCell { int in; };  // (the launches of KX_ROW alone carry the width: the kernel arguments of the KC forms stay as they are)
+template <int KX> struct CellArg { using type = RowCell; };
+template <> struct CellArg<KC> { using type = GruCell; };
+template <int KX> __device__ __forceinline__ int cell_in(const RowCell& cell) { return cell.in; }
+template <int KX> __device__ __forceinline__ constexpr int cell_in(const GruCell&) { return BG_NUM_OBS; }
+template <int KX> constexpr int x_cols = (KX + KC - 1) / KC * KC;  // the x tile's columns: whole k-chunks
+
+template <int H, int MAXW, int KX = KC>
 struct GruLds {
-    static constexpr int LDA = MAXW + 4, LDG = 3 * H + 4, LDH = H + 4, LDX = KC + 4;  // row strides (floats), multiples of 4; the three wide ones = 4 mod 32 banks
+    static constexpr int LDA = MAXW + 4, LDG = 3 * H + 4, LDH = H + 4, LDX = x_cols<KX> + 4;  // row strides (floats), multiples of 4; the three wide ones = 4 mod 32 banks
     static constexpr int TRUNK = 2 * MR * LDA, GI = MR * LDG;
     static constexpr int A = GI > TRUNK ? GI : TRUNK, B = MR * LDG, HT = MR * LDH, X = MR * LDX;
     static constexpr int FLOATS = A + B + HT + X;
@@ -382,16 +397,19 @@ struct GruLds {
 
 // One workgroup's 16 rows through the cell and the trunk.  h_in and h_out may be the same buffer: the rows are read here, in front of the first barrier,
 // and written behind the second, and no other workgroup touches them.  reset (may be nullptr): a row with a non-zero entry reads h_in as zero.
-template <int H, int MAXW, bool MIX>
+// K: the cell's inputs, the first K columns of a row (BG_NUM_OBS with KX = KC; up to KX otherwise).
+template <int H, int MAXW, bool MIX, int KX = KC>
 __device__ __forceinline__ void gru_rows(float* lds, int N, int r0, const float* __restrict__ obs, int stride, const GruCell& cell, const ActorNet& net,
                                          const float* __restrict__ logstd, uint64_t seed, uint32_t counter, const uint8_t* __restrict__ reset, const float* h_in,
-                                         float* h_out, float* __restrict__ mu_out, float* __restrict__ act_out, float beta, int teacher_noise) {
-    using L = GruLds<H, MAXW>;
+                                         float* h_out, float* __restrict__ mu_out, float* __restrict__ act_out, float beta, int teacher_noise,
+                                         int K = BG_NUM_OBS) {
+    using L = GruLds<H, MAXW, KX>;
     float *gi = lds, *gh = lds + L::A, *ht = gh + L::B, *xt = ht + L::HT;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int k = threadIdx.x; k < MR * KC; k += blockDim.x) {
-        const int r = k / KC, c = k - r * KC;
-        xt[r * L::LDX + c] = (r0 + r < N && c < BG_NUM_OBS) ? obs[(size_t)(r0 + r) * stride + c] : 0.f;
+    constexpr int XC = x_cols<KX>;  // the x tile [16][XC]: the row's first K columns, zeros behind them and in the rows past N
+    for (int k = threadIdx.x; k < MR * XC; k += blockDim.x) {
+        const int r = k / XC, c = k - r * XC;
+        xt[r * L::LDX + c] = (r0 + r < N && c < K) ? obs[(size_t)(r0 + r) * stride + c] : 0.f;
     }
     for (int k = threadIdx.x; k < MR * H; k += blockDim.x) {
         const int r = k / H, c = k - r * H, row = r0 + r;
@@ -400,7 +418,7 @@ __device__ __forceinline__ void gru_rows(float* lds, int N, int r0, const float*
         ht[r * L::LDH + c] = v;
     }
     __syncthreads();
-    first_layer<L::LDX, L::LDG, false>(cell.W_ih, cell.b_ih, BG_NUM_OBS, 3 * H, xt, gi, wave, lane);
+    first_layer<L::LDX, L::LDG, false>(cell.W_ih, cell.b_ih, K, 3 * H, xt, gi, wave, lane);
     layer<L::LDH, L::LDG>(cell.W_hh, cell.b_hh, H, 3 * H, false, ht, gh, wave, lane);
     __syncthreads();
     for (int k = threadIdx.x; k < MR * H; k += blockDim.x) {
@@ -423,12 +441,15 @@ __device__ __forceinline__ void gru_rows(float* lds, int N, int r0, const float*
     sample<L::LDA, MIX>(buf[cur], N, r0, logstd, seed, counter, mu_out, act_out, false, beta, teacher_noise);
 }
 
-template <int H, int MAXW>
-__global__ __launch_bounds__(256) void actor_gru_sample_kernel(int N, const float* __restrict__ obs, int stride, GruCell cell, ActorNet net,
+template <int H, int MAXW, int KX = KC>
+__global__ __launch_bounds__(256) void actor_gru_sample_kernel(int N, const float* __restrict__ obs, int stride, typename CellArg<KX>::type cell, ActorNet net,
                                                                const float* __restrict__ logstd, uint64_t seed, uint32_t counter, const uint8_t* __restrict__ reset,
                                                                const float* h_in, float* h_out, float* __restrict__ mu_out, float* __restrict__ act_out) {
-    __shared__ __attribute__((aligned(16))) float lds[GruLds<H, MAXW>::FLOATS];
-    gru_rows<H, MAXW, false>(lds, N, blockIdx.x * MR, obs, stride, cell, net, logstd, seed, counter, reset, h_in, h_out, mu_out, act_out, 0.f, 0);
+    using L = GruLds<H, MAXW, KX>;
+    static_assert(L::FLOATS * sizeof(float) <= 160 * 1024, "within the CU's LDS");
+    __shared__ __attribute__((aligned(16))) float lds[L::FLOATS];
+    gru_rows<H, MAXW, false, KX>(lds, N, blockIdx.x * MR, obs, stride, cell, net, logstd, seed, counter, reset, h_in, h_out, mu_out, act_out, 0.f, 0,
+                                 cell_in<KX>(cell));
 }
 
 // bg_distill_act_gru: distill_act_mix_kernel's split grid (MIX = false: distill_act_kernel's) with the recurrent student in the second half.  The
@@ -469,9 +490,9 @@ __global__ __launch_bounds__(256) void distill_act_gru_kernel(int N, int nb, con
 #else
 #define BG_NO_PACKED_FP32
 #endif
-template <int H, int MAXW>
+template <int H, int MAXW, int KX = KC>
 struct LstmLds {
-    static constexpr int LDA = MAXW + 4, LDG = 4 * H + 4, LDH = H + 4, LDX = KC + 4;  // row strides (floats), multiples of 4
+    static constexpr int LDA = MAXW + 4, LDG = 4 * H + 4, LDH = H + 4, LDX = x_cols<KX> + 4;  // row strides (floats), multiples of 4
     static constexpr int TRUNK = 2 * MR * LDA, GT = MR * LDG;
     static constexpr int A = GT > TRUNK ? GT : TRUNK, HT = MR * LDH, X = MR * LDX;
     static constexpr int FLOATS = A + HT + X;
@@ -482,18 +503,20 @@ struct LstmLds {
 // h_in / h_out and c_in / c_out may be the same buffers: a workgroup reads its 16 rows of h in front of the first barrier and writes them behind the
 // second, an element of c is read and written by one thread, and no other workgroup touches the rows.  reset (may be nullptr): a row with a non-zero
 // entry reads both states as zero.
-template <int H, int MAXW, bool MIX>
+// K: the cell's inputs, the first K columns of a row (BG_NUM_OBS with KX = KC; up to KX otherwise).
+template <int H, int MAXW, bool MIX, int KX = KC>
 __device__ __forceinline__ void lstm_rows(float* lds, int N, int r0, const float* __restrict__ obs, int stride, const GruCell& cell, const ActorNet& net,
                                           const float* __restrict__ logstd, uint64_t seed, uint32_t counter, const uint8_t* __restrict__ reset, const float* h_in,
                                           float* h_out, const float* c_in, float* c_out, float* __restrict__ mu_out, float* __restrict__ act_out, float beta,
-                                          int teacher_noise) {
-    using L = LstmLds<H, MAXW>;
+                                          int teacher_noise, int K = BG_NUM_OBS) {
+    using L = LstmLds<H, MAXW, KX>;
     constexpr int EPT = MR * H / 256;  // a thread's elements of the [16][H] state tiles
     float *gt = lds, *ht = lds + L::A, *xt = ht + L::HT;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int k = threadIdx.x; k < MR * KC; k += blockDim.x) {
-        const int r = k / KC, c = k - r * KC;
-        xt[r * L::LDX + c] = (r0 + r < N && c < BG_NUM_OBS) ? obs[(size_t)(r0 + r) * stride + c] : 0.f;
+    constexpr int XC = x_cols<KX>;  // the x tile [16][XC]: the row's first K columns, zeros behind them and in the rows past N
+    for (int k = threadIdx.x; k < MR * XC; k += blockDim.x) {
+        const int r = k / XC, c = k - r * XC;
+        xt[r * L::LDX + c] = (r0 + r < N && c < K) ? obs[(size_t)(r0 + r) * stride + c] : 0.f;
     }
     float cv[EPT];
 #pragma unroll
@@ -504,7 +527,7 @@ __device__ __forceinline__ void lstm_rows(float* lds, int N, int r0, const float
         cv[e] = live ? c_in[(size_t)row * H + c] : 0.f;
     }
     __syncthreads();
-    first_layer<L::LDX, L::LDG, false>(cell.W_ih, cell.b_ih, BG_NUM_OBS, 4 * H, xt, gt, wave, lane);
+    first_layer<L::LDX, L::LDG, false>(cell.W_ih, cell.b_ih, K, 4 * H, xt, gt, wave, lane);
     layer<L::LDH, L::LDG, true>(cell.W_hh, cell.b_hh, H, 4 * H, false, ht, gt, wave, lane);
     __syncthreads();
 #pragma unroll
@@ -531,13 +554,16 @@ __device__ __forceinline__ void lstm_rows(float* lds, int N, int r0, const float
     sample<L::LDA, MIX>(buf[cur], N, r0, logstd, seed, counter, mu_out, act_out, false, beta, teacher_noise);
 }
 
-template <int H, int MAXW>
-__global__ __launch_bounds__(256) BG_NO_PACKED_FP32 void actor_lstm_sample_kernel(int N, const float* __restrict__ obs, int stride, GruCell cell, ActorNet net,
-                                                                const float* __restrict__ logstd, uint64_t seed, uint32_t counter, const uint8_t* __restrict__ reset,
-                                                                const float* h_in, float* h_out, const float* c_in, float* c_out, float* __restrict__ mu_out,
-                                                                float* __restrict__ act_out) {
-    __shared__ __attribute__((aligned(16))) float lds[LstmLds<H, MAXW>::FLOATS];
-    lstm_rows<H, MAXW, false>(lds, N, blockIdx.x * MR, obs, stride, cell, net, logstd, seed, counter, reset, h_in, h_out, c_in, c_out, mu_out, act_out, 0.f, 0);
+template <int H, int MAXW, int KX = KC>
+__global__ __launch_bounds__(256) BG_NO_PACKED_FP32 void actor_lstm_sample_kernel(int N, const float* __restrict__ obs, int stride, typename CellArg<KX>::type cell,
+                                                                ActorNet net, const float* __restrict__ logstd, uint64_t seed, uint32_t counter,
+                                                                const uint8_t* __restrict__ reset, const float* h_in, float* h_out, const float* c_in, float* c_out,
+                                                                float* __restrict__ mu_out, float* __restrict__ act_out) {
+    using L = LstmLds<H, MAXW, KX>;
+    static_assert(L::FLOATS * sizeof(float) <= 160 * 1024, "within the CU's LDS");
+    __shared__ __attribute__((aligned(16))) float lds[L::FLOATS];
+    lstm_rows<H, MAXW, false, KX>(lds, N, blockIdx.x * MR, obs, stride, cell, net, logstd, seed, counter, reset, h_in, h_out, c_in, c_out, mu_out, act_out, 0.f, 0,
+                                  cell_in<KX>(cell));
 }
 
 // ---- the LSTM cell at H = 512 (legged_gym's rnn_hidden_size; bg_actor_sample_lstm alone: the distillation launches keep 128 and 256).  ONE gate tile
@@ -548,10 +574,10 @@ __global__ __launch_bounds__(256) BG_NO_PACKED_FP32 void actor_lstm_sample_kerne
 // lstm_rows forms, in its order.  Pass 1 still reads the old h, so h' goes to a SECOND h tile, the trunk's input.  c is read (in front of a pass's GEMMs)
 // and written by the thread that owns the element, 16 per thread and pass.  The trunk's two tiles lie over the gate tile.
 //   floats: max(16 x 1028, 2 x 16 (MAXW + 4)) + 2 x 16 x 516 + 16 x 52: 135,168 B (MAXW = 256), 135,424 B (512): one workgroup per CU.
-template <int MAXW>
+template <int MAXW, int KX = KC>
 struct LstmWideLds {
     static constexpr int H = 512, HP = 256;                                                           // the cell's width; h-columns per pass
-    static constexpr int LDA = MAXW + 4, LDG = 4 * HP + 4, LDH = H + 4, LDX = KC + 4;  // row strides (floats), multiples of 4
+    static constexpr int LDA = MAXW + 4, LDG = 4 * HP + 4, LDH = H + 4, LDX = x_cols<KX> + 4;  // row strides (floats), multiples of 4
     static constexpr int TRUNK = 2 * MR * LDA, GT = MR * LDG;
     static constexpr int A = GT > TRUNK ? GT : TRUNK, HT = MR * LDH, X = MR * LDX;
     static constexpr int FLOATS = A + 2 * HT + X;
@@ -559,20 +585,23 @@ struct LstmWideLds {
 
 // h_in / h_out and c_in / c_out may be the same buffers (lstm_rows' rule: the 16 rows of h are in LDS in front of the first barrier, an element of c is
 // read and written by one thread).
-template <int MAXW>
-__global__ __launch_bounds__(256) BG_NO_PACKED_FP32 void actor_lstm_wide_sample_kernel(int N, const float* __restrict__ obs, int stride, GruCell cell, ActorNet net,
+template <int MAXW, int KX = KC>
+__global__ __launch_bounds__(256) BG_NO_PACKED_FP32 void actor_lstm_wide_sample_kernel(int N, const float* __restrict__ obs, int stride,
+                                                                     typename CellArg<KX>::type cell, ActorNet net,
                                                                      const float* __restrict__ logstd, uint64_t seed, uint32_t counter,
                                                                      const uint8_t* __restrict__ reset, const float* h_in, float* h_out, const float* c_in,
                                                                      float* c_out, float* __restrict__ mu_out, float* __restrict__ act_out) {
-    using L = LstmWideLds<MAXW>;
+    using L = LstmWideLds<MAXW, KX>;
     constexpr int H = L::H, HP = L::HP, EPT = MR * HP / 256;  // a thread's elements of a pass's [16][256] columns
     static_assert(L::FLOATS * sizeof(float) <= 160 * 1024, "within the CU's LDS");
     __shared__ __attribute__((aligned(16))) float lds[L::FLOATS];
     float *gt = lds, *ht = lds + L::A, *hn = ht + L::HT, *xt = hn + L::HT;
     const int r0 = blockIdx.x * MR, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int k = threadIdx.x; k < MR * KC; k += blockDim.x) {
-        const int r = k / KC, c = k - r * KC;
-        xt[r * L::LDX + c] = (r0 + r < N && c < BG_NUM_OBS) ? obs[(size_t)(r0 + r) * stride + c] : 0.f;
+    const int K = cell_in<KX>(cell);  // the cell's inputs: the first K columns of a row, a row of W_ih
+    constexpr int XC = x_cols<KX>;  // the x tile [16][XC]: the row's first K columns, zeros behind them and in the rows past N
+    for (int k = threadIdx.x; k < MR * XC; k += blockDim.x) {
+        const int r = k / XC, c = k - r * XC;
+        xt[r * L::LDX + c] = (r0 + r < N && c < K) ? obs[(size_t)(r0 + r) * stride + c] : 0.f;
     }
     for (int k = threadIdx.x; k < MR * H; k += blockDim.x) {
         const int r = k / H, c = k - r * H, row = r0 + r;
@@ -590,7 +619,7 @@ __global__ __launch_bounds__(256) BG_NO_PACKED_FP32 void actor_lstm_wide_sample_
 #pragma unroll 1
         for (int g = 0; g < 4; g++) {
             const int w0 = g * H + HP * p;  // the first of this gate's 256 rows of W_ih / W_hh in this pass
-            first_layer<L::LDX, L::LDG, false>(cell.W_ih + (size_t)w0 * BG_NUM_OBS, cell.b_ih + w0, BG_NUM_OBS, HP, xt, gt + g * HP, wave, lane);
+            first_layer<L::LDX, L::LDG, false>(cell.W_ih + (size_t)w0 * K, cell.b_ih + w0, K, HP, xt, gt + g * HP, wave, lane);
             layer<L::LDH, L::LDG, true>(cell.W_hh + (size_t)w0 * H, cell.b_hh + w0, H, HP, false, ht, gt + g * HP, wave, lane);
         }
         __syncthreads();
@@ -840,9 +869,11 @@ extern "C" int bg_distill_act_mix(int32_t N, const float* teacher_obs, int32_t t
 }
 
 // ---- the recurrent student's entry points
-static int fill_cell(const std::string& who, const bg_gru_desc* gru, GruCell& cell) {
+// row: the launch reads the cell's width from the descriptor (bg_actor_sample_gru_row: 47 to KX_ROW columns of the actor's row)
+static int fill_cell(const std::string& who, const bg_gru_desc* gru, GruCell& cell, bool row = false) {
     if (!gru || !gru->W_ih || !gru->W_hh || !gru->b_ih || !gru->b_hh) return bg_set_error(-1, (who + ": bad argument (gru)").c_str());
-    if (gru->in != BG_NUM_OBS) return bg_set_error(-4, (who + ": the cell takes one observation (gru.in = 47)").c_str());
+    if (row && (gru->in < BG_NUM_OBS || gru->in > KX_ROW)) return bg_set_error(-4, (who + ": the cell takes the actor's row (gru.in from 47 to 256)").c_str());
+    if (!row && gru->in != BG_NUM_OBS) return bg_set_error(-4, (who + ": the cell takes one observation (gru.in = 47)").c_str());
     if (gru->hidden != 128 && gru->hidden != 256) return bg_set_error(-4, (who + ": unsupported gru.hidden (128 or 256)").c_str());
     if ((uintptr_t)gru->W_hh & 15) return bg_set_error(-1, (who + ": gru.W_hh must be 16-byte aligned").c_str());
     cell = GruCell{gru->W_ih, gru->W_hh, gru->b_ih, gru->b_hh};
@@ -859,14 +890,15 @@ static int fill_cell(const std::string& who, const bg_gru_desc* gru, GruCell& ce
     } while (0)
 #define BG_COMMA ,
 
-extern "C" int bg_actor_sample_gru(int32_t N, const float* obs, int32_t obs_stride, const bg_gru_desc* gru, int32_t n_layers, const bg_mlp_layer_desc* layers,
-                                   const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, float* mu,
-                                   float* actions, void* stream) {
-    const std::string who("bg_actor_sample_gru");
+// row: bg_actor_sample_gru_row, the cell on the first gru->in columns of a row (the KX_ROW form of the kernel)
+static int sample_gru(const std::string& who, bool row, int32_t N, const float* obs, int32_t obs_stride, const bg_gru_desc* gru, int32_t n_layers,
+                      const bg_mlp_layer_desc* layers, const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out,
+                      float* mu, float* actions, void* stream) {
     if (N <= 0 || !obs || !layers || !logstd || !h_in || !h_out || !actions) return bg_set_error(-1, (who + ": bad argument").c_str());
-    if (obs_stride < BG_NUM_OBS) return bg_set_error(-1, (who + ": bad argument (obs_stride: at least the 47 columns the cell reads)").c_str());
+    if (!row && obs_stride < BG_NUM_OBS) return bg_set_error(-1, (who + ": bad argument (obs_stride: at least the 47 columns the cell reads)").c_str());
     GruCell cell;
-    if (const int rc = fill_cell(who, gru, cell)) return rc;
+    if (const int rc = fill_cell(who, gru, cell, row)) return rc;
+    if (row && obs_stride < gru->in) return bg_set_error(-1, (who + ": bad argument (obs_stride: at least the gru.in columns the cell reads)").c_str());
     ActorNet net;
     int maxw = 0;
     if (const int rc = fill_net((who + " (trunk)").c_str(), n_layers, layers, 0, net, maxw, gru->hidden)) return rc;
@@ -874,9 +906,26 @@ extern "C" int bg_actor_sample_gru(int32_t N, const float* obs, int32_t obs_stri
     const bool wide = maxw > 256;
     const dim3 grid((N + MR - 1) / MR), block(256);
     hipStream_t st = (hipStream_t)stream;
-    BG_GRU_LAUNCH(actor_gru_sample_kernel, , N, obs, obs_stride, cell, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, mu, actions);
+    if (row) {
+        const RowCell rc{cell, gru->in};
+        BG_GRU_LAUNCH(actor_gru_sample_kernel, BG_COMMA KX_ROW, N, obs, obs_stride, rc, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, mu, actions);
+    } else {
+        BG_GRU_LAUNCH(actor_gru_sample_kernel, , N, obs, obs_stride, cell, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, mu, actions);
+    }
     HIP_OK(hipGetLastError());
     return 0;
+}
+
+extern "C" int bg_actor_sample_gru(int32_t N, const float* obs, int32_t obs_stride, const bg_gru_desc* gru, int32_t n_layers, const bg_mlp_layer_desc* layers,
+                                   const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, float* mu,
+                                   float* actions, void* stream) {
+    return sample_gru("bg_actor_sample_gru", false, N, obs, obs_stride, gru, n_layers, layers, logstd, seed, counter, reset, h_in, h_out, mu, actions, stream);
+}
+
+extern "C" int bg_actor_sample_gru_row(int32_t N, const float* obs, int32_t obs_stride, const bg_gru_desc* gru, int32_t n_layers, const bg_mlp_layer_desc* layers,
+                                       const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, float* mu,
+                                       float* actions, void* stream) {
+    return sample_gru("bg_actor_sample_gru_row", true, N, obs, obs_stride, gru, n_layers, layers, logstd, seed, counter, reset, h_in, h_out, mu, actions, stream);
 }
 
 // who: the entry point's name; student_obs / student_stride: the rows of the cell's 47 inputs (bg_distill_act_gru: the teacher's)
@@ -932,9 +981,11 @@ extern "C" int bg_distill_act_gru_own(int32_t N, const float* teacher_obs, int32
 
 // ---- the LSTM cell's entry points
 // wide: the launch has a form for hidden = 512 (bg_actor_sample_lstm: actor_lstm_wide_sample_kernel)
-static int fill_lstm(const std::string& who, const bg_lstm_desc* lstm, GruCell& cell, bool wide = false) {
+// row: the launch reads the cell's width from the descriptor (bg_actor_sample_lstm_row: 47 to KX_ROW columns of the actor's row)
+static int fill_lstm(const std::string& who, const bg_lstm_desc* lstm, GruCell& cell, bool wide = false, bool row = false) {
     if (!lstm || !lstm->W_ih || !lstm->W_hh || !lstm->b_ih || !lstm->b_hh) return bg_set_error(-1, (who + ": bad argument (lstm)").c_str());
-    if (lstm->in != BG_NUM_OBS) return bg_set_error(-4, (who + ": the cell takes one observation (lstm.in = 47)").c_str());
+    if (row && (lstm->in < BG_NUM_OBS || lstm->in > KX_ROW)) return bg_set_error(-4, (who + ": the cell takes the actor's row (lstm.in from 47 to 256)").c_str());
+    if (!row && lstm->in != BG_NUM_OBS) return bg_set_error(-4, (who + ": the cell takes one observation (lstm.in = 47)").c_str());
     if (wide && lstm->hidden == 512) {}
     else if (lstm->hidden != 128 && lstm->hidden != 256)
         return bg_set_error(-4, (who + (wide ? ": unsupported lstm.hidden (128, 256 or 512)" : ": unsupported lstm.hidden (128 or 256)")).c_str());
@@ -943,14 +994,15 @@ static int fill_lstm(const std::string& who, const bg_lstm_desc* lstm, GruCell& 
     return 0;
 }
 
-extern "C" int bg_actor_sample_lstm(int32_t N, const float* obs, int32_t obs_stride, const bg_lstm_desc* lstm, int32_t n_layers, const bg_mlp_layer_desc* layers,
-                                    const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, const float* c_in,
-                                    float* c_out, float* mu, float* actions, void* stream) {
-    const std::string who("bg_actor_sample_lstm");
+// row: bg_actor_sample_lstm_row, the cell on the first lstm->in columns of a row (the KX_ROW forms of the two kernels)
+static int sample_lstm(const std::string& who, bool row, int32_t N, const float* obs, int32_t obs_stride, const bg_lstm_desc* lstm, int32_t n_layers,
+                       const bg_mlp_layer_desc* layers, const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out,
+                       const float* c_in, float* c_out, float* mu, float* actions, void* stream) {
     if (N <= 0 || !obs || !layers || !logstd || !h_in || !h_out || !c_in || !c_out || !actions) return bg_set_error(-1, (who + ": bad argument").c_str());
-    if (obs_stride < BG_NUM_OBS) return bg_set_error(-1, (who + ": bad argument (obs_stride: at least the 47 columns the cell reads)").c_str());
+    if (!row && obs_stride < BG_NUM_OBS) return bg_set_error(-1, (who + ": bad argument (obs_stride: at least the 47 columns the cell reads)").c_str());
     GruCell cell;
-    if (const int rc = fill_lstm(who, lstm, cell, true)) return rc;
+    if (const int rc = fill_lstm(who, lstm, cell, true, row)) return rc;
+    if (row && obs_stride < lstm->in) return bg_set_error(-1, (who + ": bad argument (obs_stride: at least the lstm.in columns the cell reads)").c_str());
     ActorNet net;
     int maxw = 0;
     if (const int rc = fill_net((who + " (trunk)").c_str(), n_layers, layers, 0, net, maxw, lstm->hidden)) return rc;
@@ -958,15 +1010,33 @@ extern "C" int bg_actor_sample_lstm(int32_t N, const float* obs, int32_t obs_str
     const bool wide = maxw > 256;
     const dim3 grid((N + MR - 1) / MR), block(256);
     hipStream_t st = (hipStream_t)stream;
+    const RowCell rc{cell, lstm->in};
     if (H == 512) {
-        if (!wide) hipLaunchKernelGGL(actor_lstm_wide_sample_kernel<256>, grid, block, 0, st, N, obs, obs_stride, cell, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, c_in, c_out, mu, actions);
+        if (row && !wide) hipLaunchKernelGGL((actor_lstm_wide_sample_kernel<256, KX_ROW>), grid, block, 0, st, N, obs, obs_stride, rc, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, c_in, c_out, mu, actions);
+        else if (row) hipLaunchKernelGGL((actor_lstm_wide_sample_kernel<512, KX_ROW>), grid, block, 0, st, N, obs, obs_stride, rc, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, c_in, c_out, mu, actions);
+        else if (!wide) hipLaunchKernelGGL(actor_lstm_wide_sample_kernel<256>, grid, block, 0, st, N, obs, obs_stride, cell, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, c_in, c_out, mu, actions);
         else hipLaunchKernelGGL(actor_lstm_wide_sample_kernel<512>, grid, block, 0, st, N, obs, obs_stride, cell, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, c_in, c_out, mu, actions);
         HIP_OK(hipGetLastError());
         return 0;
     }
-    BG_GRU_LAUNCH(actor_lstm_sample_kernel, , N, obs, obs_stride, cell, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, c_in, c_out, mu, actions);
+    if (row) BG_GRU_LAUNCH(actor_lstm_sample_kernel, BG_COMMA KX_ROW, N, obs, obs_stride, rc, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, c_in, c_out, mu, actions);
+    else BG_GRU_LAUNCH(actor_lstm_sample_kernel, , N, obs, obs_stride, cell, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, c_in, c_out, mu, actions);
     HIP_OK(hipGetLastError());
     return 0;
+}
+
+extern "C" int bg_actor_sample_lstm(int32_t N, const float* obs, int32_t obs_stride, const bg_lstm_desc* lstm, int32_t n_layers, const bg_mlp_layer_desc* layers,
+                                    const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, const float* c_in,
+                                    float* c_out, float* mu, float* actions, void* stream) {
+    return sample_lstm("bg_actor_sample_lstm", false, N, obs, obs_stride, lstm, n_layers, layers, logstd, seed, counter, reset, h_in, h_out, c_in, c_out, mu, actions,
+                       stream);
+}
+
+extern "C" int bg_actor_sample_lstm_row(int32_t N, const float* obs, int32_t obs_stride, const bg_lstm_desc* lstm, int32_t n_layers,
+                                        const bg_mlp_layer_desc* layers, const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in,
+                                        float* h_out, const float* c_in, float* c_out, float* mu, float* actions, void* stream) {
+    return sample_lstm("bg_actor_sample_lstm_row", true, N, obs, obs_stride, lstm, n_layers, layers, logstd, seed, counter, reset, h_in, h_out, c_in, c_out, mu,
+                       actions, stream);
 }
 
 // who: the entry point's name; student_obs / student_stride: the rows of the cell's 47 inputs (bg_distill_act_lstm: the teacher's).  distill_act_gru's

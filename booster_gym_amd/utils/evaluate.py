@@ -266,7 +266,7 @@ class Evaluator:
             for k in range(K):
                 x = obs if norm is None else norm.normalize_into(obs, self._obs_normed)
                 if model.memory_hidden:  # the env's done flags of the step just taken: the rows whose memory restarts
-                    model.sample_actions(x, self._sampled, seed, k, mu_out=self._mu, reset=done)
+                    model.sample_actions(x, self._sampled, seed, k, mu_out=self._mu, reset=done, scan=scan)
                     obs, _, done, _ = env.step(self._mu)
                 else:
                     model.sample_actions(x, self._sampled, seed, k, mu_out=self._mu, scan=scan, packed=packed, est_out=self._est_scratch)

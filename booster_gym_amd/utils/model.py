@@ -975,6 +975,8 @@ class ActorCritic(torch.nn.Module):
     torch.nn.GRUCell(num_obs, H) `memory`, registered last, and the actor takes the H values of its new state instead of the observations.
     memory_cell = "lstm" (algorithm.rnn_cell; "gru" = today's cell): `memory` is a torch.nn.LSTMCell(num_obs, H) in the same place; the state that
     sample_actions carries is then ONE tensor [2][N][H], h then c.
+    memory_input = K (algorithm.rnn_input: "row"; None = num_obs): the cell is built on K inputs, the first K columns of the rows that sample_actions
+    gets (K = num_obs: the env's whole actor row, frames and height scan); K other than 47 runs the rollout's bg_actor_sample_gru_row / _lstm_row.
     critic_memory_hidden = H > 0 (a recurrent critic, algorithm.rnn_critic; 0 = without, today's parameters in today's order): a
     torch.nn.GRUCell(num_obs + num_privileged_obs, H) `critic_memory`, registered behind `memory`, and the critic's first layer takes the H values of
     its state instead of the rows.  Its state belongs to whoever walks the rows (the runner's update); est_value on single rows raises.
@@ -982,9 +984,12 @@ class ActorCritic(torch.nn.Module):
     today's draws of the global generator): two more networks, `rnd_predictor` and `rnd_target`, registered last; nothing of this class evaluates them."""
 
     def __init__(self, num_act, num_obs, num_privileged_obs, actor_hidden=ACTOR_HIDDEN, critic_hidden=CRITIC_HIDDEN, estimator_hidden=None, estimator_cols=0,
-                 memory_hidden=0, critic_memory_hidden=0, rnd=None, memory_cell="gru"):
+                 memory_hidden=0, critic_memory_hidden=0, rnd=None, memory_cell="gru", memory_input=None):
         super().__init__()
         self.memory_hidden = int(memory_hidden or 0)
+        self.memory_input = int(memory_input or num_obs)
+        if self.memory_hidden and not 1 <= self.memory_input <= num_obs:
+            raise ValueError(f"memory_input = {memory_input!r}: the cell reads the first 1 to num_obs = {num_obs} columns of the actor's row")
         if memory_cell not in ("gru", "lstm"):
             raise ValueError(f"memory_cell = {memory_cell!r}: \"gru\" or \"lstm\"")
         self.memory_cell = memory_cell if self.memory_hidden else "gru"
@@ -1004,7 +1009,7 @@ class ActorCritic(torch.nn.Module):
         if estimator_hidden is not None:
             self.estimator = _mlp(num_obs, self.estimator_hidden, _lib.NUM_DOFS)
         if self.memory_hidden:
-            self.memory = (torch.nn.LSTMCell if self.memory_cell == "lstm" else torch.nn.GRUCell)(num_obs, self.memory_hidden)
+            self.memory = (torch.nn.LSTMCell if self.memory_cell == "lstm" else torch.nn.GRUCell)(self.memory_input, self.memory_hidden)
         if self.critic_memory_hidden:
             self.critic_memory = torch.nn.GRUCell(num_obs + num_privileged_obs, self.critic_memory_hidden)
         if rnd is not None:
@@ -1167,11 +1172,14 @@ class ActorCritic(torch.nn.Module):
         return (_lib.LstmDesc if self.memory_cell == "lstm" else _lib.GruDesc)(m.weight_ih.data_ptr(), m.weight_hh.data_ptr(), m.bias_ih.data_ptr(), m.bias_hh.data_ptr(), m.input_size, m.hidden_size)
 
     def _sample_actions_gru(self, obs, actions_out, seed, counter, mu_out, scan, reset, lin, w):
-        """sample_actions of a model with memory: ONE launch (bg_actor_sample_gru) advances the state this model keeps and samples from the actor on it."""
-        if scan:
-            raise ValueError("sample_actions: a model with memory takes no height scan in the actor's row (terrain.actor_heights)")
+        """sample_actions of a model with memory: ONE launch (bg_actor_sample_gru) advances the state this model keeps and samples from the actor on it.
+        A cell on the actor's whole row (memory_input other than 47: frames, and with scan the height scan's values behind them) runs the same launch's
+        _row form on the first memory_input columns of obs."""
         N, m = obs.shape[0], self.memory
-        if obs.shape[-1] != m.input_size:
+        row = "_row" if m.input_size != _lib.NUM_OBS else ""
+        if scan and not row:
+            raise ValueError("sample_actions: a model with memory takes no height scan in the actor's row (terrain.actor_heights)")
+        if obs.shape[-1] != m.input_size and not (row and obs.shape[-1] > m.input_size):  # (the _row launches read the first columns of wider rows)
             raise ValueError(f"sample_actions: observations of {obs.shape[-1]} columns, the memory takes {m.input_size}")
         if reset is not None:
             if reset.dtype == torch.bool:
@@ -1188,11 +1196,13 @@ class ActorCritic(torch.nn.Module):
             self._gru_descs, self._gru_key = (self.gru_descriptor(), layer_descriptors(lin)), key
         gd, layers = self._gru_descs
         if self.memory_cell == "lstm":  # ONE launch as well (bg_actor_sample_lstm), both states of the one tensor [2][N][H] advanced in place
-            _lib.check(_lib.load().bg_actor_sample_lstm(N, _lib.ptr(obs), obs.shape[-1], gd, len(lin), layers, _lib.ptr(self.logstd), int(seed), int(counter),
-                                                        _lib.ptr(reset), _lib.ptr(h[0]), _lib.ptr(h[0]), _lib.ptr(h[1]), _lib.ptr(h[1]), _lib.ptr(mu_out),
-                                                        _lib.ptr(actions_out), _lib.current_stream_ptr()), "bg_actor_sample_lstm")
+            name = "bg_actor_sample_lstm" + row
+            _lib.check(getattr(_lib.load(), name)(N, _lib.ptr(obs), obs.shape[-1], gd, len(lin), layers, _lib.ptr(self.logstd), int(seed), int(counter),
+                                                  _lib.ptr(reset), _lib.ptr(h[0]), _lib.ptr(h[0]), _lib.ptr(h[1]), _lib.ptr(h[1]), _lib.ptr(mu_out),
+                                                  _lib.ptr(actions_out), _lib.current_stream_ptr()), name)
             return actions_out
-        _lib.check(_lib.load().bg_actor_sample_gru(N, _lib.ptr(obs), obs.shape[-1], gd, len(lin), layers, _lib.ptr(self.logstd), int(seed), int(counter),
-                                                   _lib.ptr(reset), _lib.ptr(h), _lib.ptr(h), _lib.ptr(mu_out), _lib.ptr(actions_out), _lib.current_stream_ptr()),
-                   "bg_actor_sample_gru")
+        name = "bg_actor_sample_gru" + row
+        _lib.check(getattr(_lib.load(), name)(N, _lib.ptr(obs), obs.shape[-1], gd, len(lin), layers, _lib.ptr(self.logstd), int(seed), int(counter),
+                                              _lib.ptr(reset), _lib.ptr(h), _lib.ptr(h), _lib.ptr(mu_out), _lib.ptr(actions_out), _lib.current_stream_ptr()),
+                   name)
         return actions_out

@@ -151,9 +151,12 @@ def rnn_hidden_size_of(cfg, world_size=1):
     if mem and mem != H:
         raise ValueError(f"algorithm.rnn_hidden_size = {H} and algorithm.actor_memory = {mem!r} name two widths of one cell: set them equal, or one of them only")
     K = (cfg.get("runner", {}) or {}).get("num_mini_batches", 1) or 1
+    row = rnn_input_value(cfg) == "row"  # the cell reads the actor's whole row: frames and the height scan are its inputs (rnn_input_of)
     refused = (("estimator.enabled: true", estimator_enabled(cfg)),
-               ("env.frame_stack above 1", int((cfg.get("env", {}) or {}).get("frame_stack", 1) or 1) > 1),
-               ("terrain.actor_heights: true", bool((cfg.get("terrain", {}) or {}).get("actor_heights", False))),
+               ("env.frame_stack above 1 (algorithm.rnn_input: \"row\" gives the cell the stacked row)",
+                not row and int((cfg.get("env", {}) or {}).get("frame_stack", 1) or 1) > 1),
+               ("terrain.actor_heights: true (algorithm.rnn_input: \"row\" gives the cell the row with the scan)",
+                not row and bool((cfg.get("terrain", {}) or {}).get("actor_heights", False))),
                ("algorithm.symmetry_loss: true", bool(alg.get("symmetry_loss", False))),
                ("algorithm.empirical_normalization: true", bool(alg.get("empirical_normalization", False))),
                ("runner.num_mini_batches above 1", not isinstance(K, bool) and isinstance(K, int) and K > 1),
@@ -163,6 +166,38 @@ def rnn_hidden_size_of(cfg, world_size=1):
             raise ValueError(f"algorithm.rnn_hidden_size = {H} is not supported with {what} (a recurrent actor reads the newest single observation, "
                              "on one rank, its update on the whole batch as sequences)")
     return H
+
+
+RNN_INPUTS = ("observation", "row")  # algorithm.rnn_input
+RNN_INPUT_MAX = 256  # the widest row the rollout's cell launches take (bg_actor_sample_gru_row / _lstm_row: the x tile in LDS beside the H = 512 forms)
+
+
+def rnn_input_value(cfg):
+    """algorithm.rnn_input as written: "observation" (also absent or null) or "row"; ValueError naming the key for any other value.  Pure."""
+    v = (cfg.get("algorithm", {}) or {}).get("rnn_input")
+    v = "observation" if v is None else v
+    if not isinstance(v, str) or v not in RNN_INPUTS:
+        raise ValueError(f"algorithm.rnn_input must be \"observation\" or \"row\" (what the cell of algorithm.rnn_hidden_size reads; absent: "
+                         f"\"observation\"), got {v!r}")
+    return v
+
+
+def rnn_input_of(cfg, world_size=1):
+    """algorithm.rnn_input (an addition of this build; absent, null or "observation" = the newest single observation: the shipped yaml does not list it)
+    as the number of columns K that the cell in front of the actor reads: 47 for "observation"; for "row" env.num_observations = 47 x env.frame_stack +
+    (the height scan's points under terrain.actor_heights), the env's actor row as a feed-forward actor gets it (legged_gym / rsl_rl's
+    ActorCriticRecurrent, whose memory reads the policy's observation).  Read only together with a non-zero algorithm.rnn_hidden_size or
+    algorithm.actor_memory: without one the result is 47 whatever the key holds.  Pure.  ValueError naming the key for any other value, and for a row
+    wider than 256 columns; rnn_hidden_size_of's own refusals apply as well (with "row", env.frame_stack and terrain.actor_heights are none of them)."""
+    if not (rnn_hidden_size_of(cfg, world_size) or actor_memory_of(cfg)):
+        return _lib.NUM_OBS
+    if rnn_input_value(cfg) != "row":
+        return _lib.NUM_OBS
+    K = int((cfg.get("env", {}) or {}).get("num_observations", _lib.NUM_OBS))
+    if K < _lib.NUM_OBS or K > RNN_INPUT_MAX:
+        raise ValueError(f"algorithm.rnn_input: \"row\" takes an actor row of {_lib.NUM_OBS} to {RNN_INPUT_MAX} columns (the cell's input tile in LDS), got "
+                         f"env.num_observations = {K}")
+    return K
 
 
 RNN_CELLS = ("gru", "lstm")  # the cells of algorithm.rnn_cell
@@ -238,6 +273,8 @@ def checkpoint_memory_overrides(checkpoint):
         over["algorithm.rnn_cell"] = "lstm"
     if "critic_memory.weight_hh" in sd:
         over["algorithm.rnn_critic"] = True
+    if "memory.weight_ih" in sd and sd["memory.weight_ih"].shape[1] > _lib.NUM_OBS:  # the cell reads the actor's whole row (algorithm.rnn_input)
+        over["algorithm.rnn_input"] = "row"
     return over
 
 
@@ -512,6 +549,8 @@ class Runner:
             self._rnn_cell = actor_memory_cell_of(self.cfg)
         # algorithm.rnn_critic: a second cell of the same width in front of the critic; 0 = a feed-forward critic, the one switch the branches below read
         self._rnn_critic = rnn_critic_of(self.cfg, self.world_size)
+        # algorithm.rnn_input: the columns the cell reads, 47 (the newest single observation) or, with "row", the env's whole actor row
+        self._rnn_input = rnn_input_of(self.cfg, self.world_size)
         if self._rnn and not test and (int((self.cfg.get("parallel", {}) or {}).get("gemm_split", 0) or 0) or MLPTrainer.SPLIT):
             raise ValueError(f"algorithm.rnn_hidden_size = {self._rnn} is not supported with parallel.gemm_split / BG_GEMM_SPLIT (the trunk behind the cell "
                              "runs the per-layer fp32 kernels): use gemm_split 0")
@@ -533,6 +572,11 @@ class Runner:
         est_args = {} if self._est is None else {"estimator_hidden": self._est.hidden, "estimator_cols": len(self._est.targets)}
         if self._memory:
             est_args = {"memory_hidden": self._memory, "memory_cell": self._rnn_cell}
+            if self._rnn_input != _lib.NUM_OBS:  # (today's call, and with it today's module, without the key)
+                if self._rnn_input != self.env.num_obs:
+                    raise ValueError(f"algorithm.rnn_input: \"row\" reads env.num_observations = {self._rnn_input} columns, the env's actor row has "
+                                     f"{self.env.num_obs}")
+                est_args["memory_input"] = self._rnn_input
         if self._rnn_critic:
             est_args["critic_memory_hidden"] = self._rnn_critic
         if self._rnd is not None:
@@ -651,9 +695,9 @@ class Runner:
         self._mem_tr = None
         if self._rnn and not test:
             if self._rnn_cell == "lstm":  # the same interface around the LSTM's kernels (model.LSTMTrainer)
-                self._mem_tr = LSTMTrainer(self.model.memory, self._actor_tr, T, N, clock=self._clock)
+                self._mem_tr = LSTMTrainer(self.model.memory, self._actor_tr, T, N, clock=self._clock, kin=self._pad_actor)
             else:
-                self._mem_tr = GRUTrainer(self.model.memory, self._actor_tr, T, N, clock=self._clock, bias_partial=True)
+                self._mem_tr = GRUTrainer(self.model.memory, self._actor_tr, T, N, clock=self._clock, bias_partial=True, kin=self._pad_actor)
             self._last_dones = torch.zeros(N, dtype=torch.uint8, device=dev)
         # algorithm.rnn_critic: the second cell around the critic's trunk.  Its forward pass walks T + 1 steps (the row after the last step gives
         # last_values) from a state that no rollout launch advances: GRUTrainer.carry_state.  None = a feed-forward critic
@@ -702,9 +746,9 @@ class Runner:
             raise ValueError("algorithm.smoothness_loss needs the fused output layers of bg_head.hip: an actor whose last hidden layer is 128 wide with 12 actions")
         if self._symmetry and not self._fused_head:
             raise ValueError("algorithm.symmetry_loss needs the fused output layers of bg_head.hip: an actor whose last hidden layer is 128 wide with 12 actions")
-        if self._mem_tr is not None and not (self._fused_head and self._pad_actor == GRUTrainer.KIN):
-            raise ValueError(f"algorithm.rnn_hidden_size = {self._rnn} needs the fused output layers of bg_head.hip (12 actions) and an observation of at "
-                             f"most {GRUTrainer.KIN} columns (env.num_observations = {no})")
+        if self._mem_tr is not None and not (self._fused_head and self._pad_actor == pad_input(self._rnn_input)):
+            raise ValueError(f"algorithm.rnn_hidden_size = {self._rnn} needs the fused output layers of bg_head.hip (12 actions) and the cell's input of "
+                             f"{self._rnn_input} columns zero-padded as the actor's rows are (env.num_observations = {no})")
         self._old_mu = torch.zeros(B, A, device=dev)
         self._values_all = torch.zeros(B + N, device=dev)
         self._head_scratch_a, self._head_scratch_c = head_scratch(dev), head_scratch(dev)
@@ -791,6 +835,11 @@ class Runner:
             raise ValueError(f"checkpoint {ck} has {'an LSTM' if ck_cell == 'lstm' else 'a GRU'} cell (memory.weight_hh of {model_dict['model']['memory.weight_hh'].shape[0]} "
                              f"rows), the config has algorithm.rnn_cell = {getattr(self, '_rnn_cell', 'gru')!r}: set algorithm.rnn_cell to \"{ck_cell}\" "
                              "(evaluate.py and export_model.py set it from the checkpoint)")
+        ck_k, k = (int(model_dict["model"]["memory.weight_ih"].shape[1]) if ck_mem else 0), getattr(self, "_rnn_input", _lib.NUM_OBS)
+        if ck_mem and ck_k != k:
+            raise ValueError(f"checkpoint {ck} has a cell of {ck_k} inputs (memory.weight_ih), the config's cell takes {k}: set algorithm.rnn_input to "
+                             f"\"{'row' if ck_k > _lib.NUM_OBS else 'observation'}\" (and env.frame_stack, terrain.actor_heights with its points, "
+                             "env.num_observations as in the run that saved the checkpoint; evaluate.py and export_model.py set the key from the checkpoint)")
         ck_cmem = int(model_dict["model"]["critic_memory.weight_hh"].shape[1]) if "critic_memory.weight_hh" in model_dict["model"] else 0
         # (a recurrent student re-entering for fine-tuning carries an UNTRAINED feed-forward critic: under algorithm.rnn_critic the critic built here,
         # cell and trunk, stays as initialised and the student's critic.* is not loaded)
@@ -985,7 +1034,7 @@ class Runner:
         B, n = T * N, N // K
         self._mb_rows = T * n
         self._actor_mb, self._critic_mb = MLPTrainer(self.model.actor, clock=self._clock), MLPTrainer(self.model.critic, clock=self._clock)
-        self._mem_mb = GRUTrainer(self.model.memory, self._actor_mb, T, n, clock=self._clock, bias_partial=True)
+        self._mem_mb = GRUTrainer(self.model.memory, self._actor_mb, T, n, clock=self._clock, bias_partial=True, kin=self._pad_actor)
         # algorithm.rnn_critic: likewise a second trainer of the critic's cell for [T][n] rows (a step differentiates all of its rows: no extra step)
         self._cmem_mb = None
         if self._cmem_tr is not None:
@@ -993,7 +1042,7 @@ class Runner:
         self._mb_wgrad = [GroupedWeightGrad() for _ in range(K)]  # (descriptors per input buffer: one per mini-batch position)
         self._env_perm = torch.zeros(N, dtype=torch.int32, device=dev)
         f = lambda *shape: torch.zeros(*shape, device=dev)
-        self._mb = types.SimpleNamespace(critic_in=f(B, self._critic_in.shape[-1]), actor_in=f(B, GRUTrainer.KIN), actions=f(B, A), old_mu=f(B, A), old_logp=f(B),
+        self._mb = types.SimpleNamespace(critic_in=f(B, self._critic_in.shape[-1]), actor_in=f(B, self._pad_actor), actions=f(B, A), old_mu=f(B, A), old_logp=f(B),
                                          adv=f(B), ret=f(B), h0=f(N, H), resets=torch.zeros(B, dtype=torch.uint8, device=dev),
                                          h0_c=f(N, H) if self._cmem_tr is not None else None)
         self._mb_values = f(self._mb_rows)
@@ -1071,7 +1120,8 @@ class Runner:
                 if self._est is not None:  # estimator and actor in ONE launch; the estimate the actor read is kept: the update's rows are these
                     self.model.sample_actions(obses[n], buf["actions"][n], seed, self._act_counter, est_out=buf["estimates"][n])
                 elif mt is not None:  # cell and trunk in ONE launch that advances the state in place; an env the step before reset enters with a zero state
-                    self.model.sample_actions(obses[n], buf["actions"][n], seed, self._act_counter, reset=mt.rollout_reset(n, self._last_dones, buf["dones"]))
+                    self.model.sample_actions(obses[n], buf["actions"][n], seed, self._act_counter, scan=scan,
+                                              reset=mt.rollout_reset(n, self._last_dones, buf["dones"]))
                 elif norm is None:
                     self.model.sample_actions(obses[n], buf["actions"][n], seed, self._act_counter, scan=scan, packed=packed)
                 else:  # the buffer keeps the raw rows; the actor samples from their normalised copy (one more launch per step: bg_obs_normalize)
@@ -1737,7 +1787,7 @@ class Runner:
                         self.model.sample_actions(obs.contiguous(), sampled, 0, step, mu_out=mean, est_out=est_scratch)
                         act = mean
                     elif self._memory:
-                        self.model.sample_actions(obs.contiguous(), sampled, 0, step, mu_out=mean, reset=done)
+                        self.model.sample_actions(obs.contiguous(), sampled, 0, step, mu_out=mean, reset=done, scan=getattr(self.env, "num_scan_obs", 0))
                         act = mean
                     else:
                         act = self.model.actor(obs)

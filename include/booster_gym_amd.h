@@ -500,6 +500,15 @@ typedef struct bg_gru_desc {
 int bg_actor_sample_gru(int32_t N, const float* obs, int32_t obs_stride, const bg_gru_desc* gru, int32_t n_layers, const bg_mlp_layer_desc* layers,
                         const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, float* mu,
                         float* actions, void* stream);
+/* bg_actor_sample_gru with the cell on the actor's whole row (T1.yaml algorithm.rnn_input: "row"; rsl_rl's ActorCriticRecurrent, whose memory reads the
+ * policy's observation): x = columns [0, gru->in) of obs, gru->in from 47 to 256 (else -4), rows obs_stride >= gru->in floats apart (else -1); columns
+ * at or beyond gru->in are never read.  W_ih [3 hidden][gru->in] in torch's layout, any alignment.  Extents: obs [N][obs_stride] (the last row through
+ * column gru->in - 1), h_in / h_out [N][hidden], mu / actions [N][12], reset [N].  Every other argument, rule and return code is bg_actor_sample_gru's;
+ * with gru->in = 47 every output equals bg_actor_sample_gru's, bit for bit (the same sums in the same order).  The x tile is [16][292] floats of LDS
+ * (whole 48-column k-chunks, zero from column gru->in on) where bg_actor_sample_gru's is [16][52]: 15,360 B more per workgroup. */
+int bg_actor_sample_gru_row(int32_t N, const float* obs, int32_t obs_stride, const bg_gru_desc* gru, int32_t n_layers, const bg_mlp_layer_desc* layers,
+                            const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, float* mu,
+                            float* actions, void* stream);
 /* bg_distill_act_mix's split grid with the recurrent student in the student's half: the teacher's half is unchanged (teacher_mu equals
  * bg_actor_sample_mlp_scan's mean, bit for bit), the student's half is bg_actor_sample_gru's body on columns [0, 47) of the teacher's rows (student_mu,
  * h_out, and at beta = 0 actions equal bg_actor_sample_gru's, bit for bit).  beta in [0, 1] and teacher_noise: bg_distill_act_mix's rules (the same
@@ -583,6 +592,14 @@ typedef struct bg_lstm_desc {
 int bg_actor_sample_lstm(int32_t N, const float* obs, int32_t obs_stride, const bg_lstm_desc* lstm, int32_t n_layers, const bg_mlp_layer_desc* layers,
                          const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, const float* c_in,
                          float* c_out, float* mu, float* actions, void* stream);
+/* bg_actor_sample_lstm with the cell on the actor's whole row (T1.yaml algorithm.rnn_input: "row"), as bg_actor_sample_gru_row: x = columns
+ * [0, lstm->in) of obs, lstm->in from 47 to 256 (else -4), obs_stride >= lstm->in (else -1), W_ih [4 hidden][lstm->in]; hidden = 128, 256 or 512 (at 512
+ * each gate block of W_ih starts lstm->in floats times its first row in).  Extents: obs [N][obs_stride] (the last row through column lstm->in - 1),
+ * h_in / h_out / c_in / c_out [N][hidden], mu / actions [N][12], reset [N].  With lstm->in = 47 every output equals bg_actor_sample_lstm's, bit for bit.
+ * LDS: 15,360 B more than bg_actor_sample_lstm's form of the same widths (150,784 B at hidden = 512 with a 512-wide trunk). */
+int bg_actor_sample_lstm_row(int32_t N, const float* obs, int32_t obs_stride, const bg_lstm_desc* lstm, int32_t n_layers, const bg_mlp_layer_desc* layers,
+                             const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, const float* c_in,
+                             float* c_out, float* mu, float* actions, void* stream);
 /* A recurrent student with that cell (T1.yaml distillation.student_cell: "lstm"; rsl_rl's StudentTeacherRecurrent with its default cell):
  * bg_distill_act_gru's split grid and arguments with bg_actor_sample_lstm's body in the student's half.  The two states travel as ONE tensor: state_in /
  * state_out [2][N][hidden], h then c (both read as zero where reset [N] is non-zero); state_in == state_out is allowed.  The teacher's half is unchanged

@@ -12,6 +12,9 @@
   `only` = "kernels" runs (1) to (3), "loop" (4); "wide" (out: profiles/lstm_512_time.txt) runs the LSTM at H = 512 (algorithm.rnn_hidden_size: 512)
   beside the LSTM at H = 256 in the same run: the rollout launch, both recurrences, the bias sums, the 24 bg_mlp_layer_forward(num_envs, H, 4H)
   launches and the peak time of the FLOPs at either width, then the training loop at 256 and 512; "wide_kernels" / "wide_loop" run its halves.
+  "row" (out: profiles/rnn_input_time.txt; algorithm.rnn_input: "row") runs every cell's _row launch at K = 234 (47 + the 187-point height scan) beside
+  the same cell's 47-input launch and beside bg_actor_sample_mlp_scan at that K, then the training loop of the LSTM at H = 256 on the perceptive env
+  with the cell on the observation and on the row; "row_kernels" / "row_loop" run its halves.
   The committed profile carries sections this tool does not write: bench.py of this tree against a
   checkout of its parent commit, and the SHA-256 digests."""
 import os
@@ -27,7 +30,10 @@ from actor_memory_time import DEV, LINES, _best, _descs, _orders, loop, say
 PEAK_FP32_MFMA = 157.3e12  # MI355X, fp32 matrix FLOP/s (vendor figure)
 T = 24
 SIDES = (("rnn_cell gru", {"algorithm.rnn_hidden_size": 128}), ("rnn_cell lstm", {"algorithm.rnn_hidden_size": 128, "algorithm.rnn_cell": "lstm"}),
-         ("lstm 256", {"algorithm.rnn_hidden_size": 256, "algorithm.rnn_cell": "lstm"}), ("lstm 512", {"algorithm.rnn_hidden_size": 512, "algorithm.rnn_cell": "lstm"}))
+         ("lstm 256", {"algorithm.rnn_hidden_size": 256, "algorithm.rnn_cell": "lstm"}), ("lstm 512", {"algorithm.rnn_hidden_size": 512, "algorithm.rnn_cell": "lstm"}),
+         ("lstm 256, critic scan", {"algorithm.rnn_hidden_size": 256, "algorithm.rnn_cell": "lstm", "terrain.measure_heights": True, "env.num_privileged_obs": 201}),
+         ("lstm 256, row 234", {"algorithm.rnn_hidden_size": 256, "algorithm.rnn_cell": "lstm", "algorithm.rnn_input": "row", "terrain.measure_heights": True,
+                                "terrain.actor_heights": True, "env.num_observations": 234, "env.num_privileged_obs": 201}))
 
 
 def rollout_launch(pairs, N):
@@ -146,6 +152,34 @@ def wide(pairs, N):
                 f"forward / layers = {us[f'fwd {H}'] / us[f'layers {H}']:.2f}, backward / layers = {us[f'bwd {H}'] / us[f'layers {H}']:.2f}")
 
 
+def row_launch(pairs, N, K=234):
+    """Every cell's _row launch at K inputs beside its 47-input launch and beside the feed-forward actor's launch on the same row, the sides alternating."""
+    from booster_gym_amd import _lib
+    from booster_gym_amd.utils.model import ActorCritic
+
+    lib, p, st, ck = _lib.load(), _lib.ptr, _lib.current_stream_ptr(), _lib.check
+    torch.manual_seed(1)
+    obs, row, act = torch.randn(N, 47, device=DEV), torch.randn(N, K, device=DEV), torch.empty(N, 12, device=DEV)
+    reset = (torch.rand(N, device=DEV) < 0.02).to(torch.uint8)
+    ff = ActorCritic(12, K, 14).to(DEV)
+    fl, fn = _descs(ff)
+    fns = {"mlp_scan": lambda k: ck(lib.bg_actor_sample_mlp_scan(N, p(row), fn, fl, K - 47, p(ff.logstd), 1, k, None, p(act), st), "bg_actor_sample_mlp_scan")}
+    keep = []
+    for cell, H in (("gru", 128), ("gru", 256), ("lstm", 128), ("lstm", 256), ("lstm", 512)):
+        for x, kin, tail in ((obs, 47, ""), (row, K, "_row")):
+            m = ActorCritic(12, kin, 14, memory_hidden=H, memory_cell=cell, memory_input=kin).to(DEV)
+            d, s = (m.gru_descriptor(),) + _descs(m), torch.zeros(2, N, H, device=DEV)
+            keep.append((m, d, s))
+            states = (s[0], s[0], s[1], s[1]) if cell == "lstm" else (s[0], s[0])
+            fns[f"{cell} {H}{tail}"] = lambda k, f=getattr(lib, f"bg_actor_sample_{cell}{tail}"), x=x, kin=kin, d=d, m=m, states=states: ck(
+                f(N, p(x), kin, d[0], d[2], d[1], p(m.logstd), 1, k, p(reset), *[p(t) for t in states], None, p(act), st), "the cell's launch")
+    for q in range(pairs):
+        us = {k: _best(f, 200) for k, f in _orders(q, tuple(fns.items()))}
+        for k in (k for k in fns if k.endswith("_row")):
+            say(f"rollout launch, {N} rows, trunk 256-128-128, {k[:-4]}: bg_actor_sample_{k.split()[0]}_row at K = {K} {us[k]:.2f} us, the 47-input launch "
+                f"{us[k[:-4]]:.2f} us (row / 47 = {us[k] / us[k[:-4]]:.3f}), bg_actor_sample_mlp_scan at K = {K} {us['mlp_scan']:.2f} us")
+
+
 def loops(pairs, K, W, N, sides, base):
     got = {}
     for q in range(pairs):
@@ -165,13 +199,19 @@ if __name__ == "__main__":
     a = sys.argv[1:]
     K, W, pairs, N = (int(a[i]) if len(a) > i else v for i, v in enumerate((20, 5, 3, 4096)))
     only = a[5] if len(a) > 5 else ""
-    out = a[4] if len(a) > 4 and a[4] != "-" else os.path.join(ROOT, "profiles", "lstm_512_time.txt" if only.startswith("wide") else "lstm_time.txt")
+    name = "rnn_input_time.txt" if only.startswith("row") else "lstm_512_time.txt" if only.startswith("wide") else "lstm_time.txt"
+    out = a[4] if len(a) > 4 and a[4] != "-" else os.path.join(ROOT, "profiles", name)
     if only.startswith("one:"):  # a child of the loop section: one Runner in a process of its own
         name, over = SIDES[int(only[4:])]
         print("MS %.6f" % loop(name, over, K, W, N), flush=True)
         sys.exit(0)
     say(f"tools/lstm_time.py {' '.join(a) or f'{K} {W} {pairs} {N}'} on {torch.cuda.get_device_name(0)}")
-    if only.startswith("wide"):
+    if only.startswith("row"):
+        if only != "row_loop":
+            row_launch(pairs, N)
+        if only != "row_kernels":
+            loops(pairs, K, W, N, (4, 5), "lstm 256, critic scan")
+    elif only.startswith("wide"):
         if only != "wide_loop":
             wide(pairs, N)
         if only != "wide_kernels":

@@ -207,8 +207,9 @@ def rollout(layers, cmd, seconds, cfg=None, dyn=None, model=None, height_points=
     dec, dt = cfg["control"]["decimation"], cfg["sim"]["dt"]
     P = 0 if height_points is None else len(height_points)  # terrain.actor_heights: the row ends with the newest scan, not stacked
     est_layers, E = estimator if estimator is not None else (None, 0)  # estimator.enabled: E estimates behind the observations
-    # a recurrent actor (memory: a GRUMemory): the cell reads the newest single observation and the trunk its state, zero at the start
-    stack = FrameStack(1 if memory is not None else actor_frames(layers, scan=P + E))  # (H = 1: the single observation itself)
+    # a recurrent actor (memory: a GRUMemory): the cell reads the newest single observation, or under algorithm.rnn_input: "row" the row built below
+    # (its frames and scan read from the cell's input width), and the trunk its state, zero at the start
+    stack = FrameStack(actor_frames([(memory.w_ih, None)] if memory is not None else layers, scan=P + E))  # (H = 1: the single observation itself)
     if memory is not None:
         memory.reset()
     traj = []
