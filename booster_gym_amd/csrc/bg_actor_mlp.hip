@@ -868,181 +868,110 @@ extern "C" int bg_distill_act_mix(int32_t N, const float* teacher_obs, int32_t t
                        student_logstd, seed, counter, student_mu, actions, teacher_mu, stream);
 }
 
-// ---- the recurrent student's entry points
-// row: the launch reads the cell's width from the descriptor (bg_actor_sample_gru_row: 47 to KX_ROW columns of the actor's row)
-static int fill_cell(const std::string& who, const bg_gru_desc* gru, GruCell& cell, bool row = false) {
-    if (!gru || !gru->W_ih || !gru->W_hh || !gru->b_ih || !gru->b_hh) return bg_set_error(-1, (who + ": bad argument (gru)").c_str());
-    if (row && (gru->in < BG_NUM_OBS || gru->in > KX_ROW)) return bg_set_error(-4, (who + ": the cell takes the actor's row (gru.in from 47 to 256)").c_str());
-    if (!row && gru->in != BG_NUM_OBS) return bg_set_error(-4, (who + ": the cell takes one observation (gru.in = 47)").c_str());
-    if (gru->hidden != 128 && gru->hidden != 256) return bg_set_error(-4, (who + ": unsupported gru.hidden (128 or 256)").c_str());
-    if ((uintptr_t)gru->W_hh & 15) return bg_set_error(-1, (who + ": gru.W_hh must be 16-byte aligned").c_str());
-    cell = GruCell{gru->W_ih, gru->W_hh, gru->b_ih, gru->b_hh};
+// ---- the recurrent cells' entry points: the checks and the launch selection written once, for the GRU and the LSTM cell alike
+// A cell's states at a launch: the GRU's h, the LSTM's h and c (in and out may be the same buffers: gru_rows' / lstm_rows' rule).
+struct CellState { const float* h_in; float* h_out; const float* c_in; float* c_out; };
+
+// What the shared host code asks of a cell: its descriptor, its word in the messages, whether bg_actor_sample_* serves hidden = 512, and its kernels.
+struct GruKind {
+    using Desc = bg_gru_desc;
+    static constexpr const char* word = "gru";
+    static constexpr bool wide_hidden = false;
+    static bool has_states(const CellState& s) { return s.h_in && s.h_out; }
+    template <int H, int MAXW, int KX, class Cell>
+    static void sample(dim3 grid, dim3 block, hipStream_t st, int N, const float* obs, int stride, const Cell& cell, const ActorNet& net, const float* logstd,
+                       uint64_t seed, uint32_t counter, const uint8_t* reset, const CellState& s, float* mu, float* actions) {
+        hipLaunchKernelGGL((actor_gru_sample_kernel<H, MAXW, KX>), grid, block, 0, st, N, obs, stride, cell, net, logstd, seed, counter, reset, s.h_in, s.h_out, mu, actions);
+    }
+    template <int H, int MAXW, bool MIX, class... A>
+    static void distill(dim3 grid, dim3 block, hipStream_t st, A... a) { hipLaunchKernelGGL((distill_act_gru_kernel<H, MAXW, MIX>), grid, block, 0, st, a...); }
+};
+
+struct LstmKind {
+    using Desc = bg_lstm_desc;
+    static constexpr const char* word = "lstm";
+    static constexpr bool wide_hidden = true;  // actor_lstm_wide_sample_kernel
+    static bool has_states(const CellState& s) { return s.h_in && s.h_out && s.c_in && s.c_out; }
+    template <int H, int MAXW, int KX, class Cell>
+    static void sample(dim3 grid, dim3 block, hipStream_t st, int N, const float* obs, int stride, const Cell& cell, const ActorNet& net, const float* logstd,
+                       uint64_t seed, uint32_t counter, const uint8_t* reset, const CellState& s, float* mu, float* actions) {
+        if constexpr (H == 512)
+            hipLaunchKernelGGL((actor_lstm_wide_sample_kernel<MAXW, KX>), grid, block, 0, st, N, obs, stride, cell, net, logstd, seed, counter, reset, s.h_in, s.h_out,
+                               s.c_in, s.c_out, mu, actions);
+        else
+            hipLaunchKernelGGL((actor_lstm_sample_kernel<H, MAXW, KX>), grid, block, 0, st, N, obs, stride, cell, net, logstd, seed, counter, reset, s.h_in, s.h_out,
+                               s.c_in, s.c_out, mu, actions);
+    }
+    template <int H, int MAXW, bool MIX, class... A>
+    static void distill(dim3 grid, dim3 block, hipStream_t st, A... a) { hipLaunchKernelGGL((distill_act_lstm_kernel<H, MAXW, MIX>), grid, block, 0, st, a...); }
+};
+
+// The descriptor of a cell -> the four pointers (the layout is torch.nn.GRUCell's / LSTMCell's: 3 / 4 hidden rows).  word: the cell's name in the messages;
+// wide: the launch has a form for hidden = 512; row: the launch reads the cell's width from the descriptor (the _row entry points: 47 to KX_ROW columns of
+// the actor's row)
+template <class Desc>
+static int fill_cell(const std::string& who, const std::string& word, const Desc* d, GruCell& cell, bool wide = false, bool row = false) {
+    if (!d || !d->W_ih || !d->W_hh || !d->b_ih || !d->b_hh) return bg_set_error(-1, (who + ": bad argument (" + word + ")").c_str());
+    if (row && (d->in < BG_NUM_OBS || d->in > KX_ROW)) return bg_set_error(-4, (who + ": the cell takes the actor's row (" + word + ".in from 47 to 256)").c_str());
+    if (!row && d->in != BG_NUM_OBS) return bg_set_error(-4, (who + ": the cell takes one observation (" + word + ".in = 47)").c_str());
+    if (d->hidden != 128 && d->hidden != 256 && !(wide && d->hidden == 512))
+        return bg_set_error(-4, (who + ": unsupported " + word + ".hidden (" + (wide ? "128, 256 or 512" : "128 or 256") + ")").c_str());
+    if ((uintptr_t)d->W_hh & 15) return bg_set_error(-1, (who + ": " + word + ".W_hh must be 16-byte aligned").c_str());
+    cell = GruCell{d->W_ih, d->W_hh, d->b_ih, d->b_hh};
     return 0;
 }
 
-// the kernel template K at the cell's width and the LDS form `wide` (MAXW = 512) names
-#define BG_GRU_LAUNCH(K, TAIL, ...)                                                                                  \
-    do {                                                                                                             \
-        if (H == 128 && !wide) hipLaunchKernelGGL((K<128, 256 TAIL>), grid, block, 0, st, __VA_ARGS__);             \
-        else if (H == 128) hipLaunchKernelGGL((K<128, 512 TAIL>), grid, block, 0, st, __VA_ARGS__);                 \
-        else if (!wide) hipLaunchKernelGGL((K<256, 256 TAIL>), grid, block, 0, st, __VA_ARGS__);                    \
-        else hipLaunchKernelGGL((K<256, 512 TAIL>), grid, block, 0, st, __VA_ARGS__);                               \
+// F<H, MAXW TAIL>(...) at the cell's width H = 128 or 256 and the LDS form `wide` (MAXW = 512) names
+#define BG_CELL_FORM(F, TAIL, ...)                                 \
+    do {                                                           \
+        if (H == 128 && !wide) F<128, 256 TAIL>(__VA_ARGS__);      \
+        else if (H == 128) F<128, 512 TAIL>(__VA_ARGS__);          \
+        else if (!wide) F<256, 256 TAIL>(__VA_ARGS__);             \
+        else F<256, 512 TAIL>(__VA_ARGS__);                        \
     } while (0)
 #define BG_COMMA ,
 
-// row: bg_actor_sample_gru_row, the cell on the first gru->in columns of a row (the KX_ROW form of the kernel)
-static int sample_gru(const std::string& who, bool row, int32_t N, const float* obs, int32_t obs_stride, const bg_gru_desc* gru, int32_t n_layers,
-                      const bg_mlp_layer_desc* layers, const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out,
-                      float* mu, float* actions, void* stream) {
-    if (N <= 0 || !obs || !layers || !logstd || !h_in || !h_out || !actions) return bg_set_error(-1, (who + ": bad argument").c_str());
+// bg_actor_sample_gru / _lstm and their _row forms (row: the cell on the first desc->in columns of a row, the KX_ROW forms of the kernels)
+template <class Kind>
+static int sample_cell(const std::string& who, bool row, int32_t N, const float* obs, int32_t obs_stride, const typename Kind::Desc* desc, int32_t n_layers,
+                       const bg_mlp_layer_desc* layers, const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const CellState& s, float* mu,
+                       float* actions, void* stream) {
+    const std::string word(Kind::word);
+    if (N <= 0 || !obs || !layers || !logstd || !Kind::has_states(s) || !actions) return bg_set_error(-1, (who + ": bad argument").c_str());
     if (!row && obs_stride < BG_NUM_OBS) return bg_set_error(-1, (who + ": bad argument (obs_stride: at least the 47 columns the cell reads)").c_str());
     GruCell cell;
-    if (const int rc = fill_cell(who, gru, cell, row)) return rc;
-    if (row && obs_stride < gru->in) return bg_set_error(-1, (who + ": bad argument (obs_stride: at least the gru.in columns the cell reads)").c_str());
+    if (const int rc = fill_cell(who, word, desc, cell, Kind::wide_hidden, row)) return rc;
+    if (row && obs_stride < desc->in) return bg_set_error(-1, (who + ": bad argument (obs_stride: at least the " + word + ".in columns the cell reads)").c_str());
     ActorNet net;
     int maxw = 0;
-    if (const int rc = fill_net((who + " (trunk)").c_str(), n_layers, layers, 0, net, maxw, gru->hidden)) return rc;
-    const int H = gru->hidden;
+    if (const int rc = fill_net((who + " (trunk)").c_str(), n_layers, layers, 0, net, maxw, desc->hidden)) return rc;
+    const int H = desc->hidden;
     const bool wide = maxw > 256;
     const dim3 grid((N + MR - 1) / MR), block(256);
     hipStream_t st = (hipStream_t)stream;
-    if (row) {
-        const RowCell rc{cell, gru->in};
-        BG_GRU_LAUNCH(actor_gru_sample_kernel, BG_COMMA KX_ROW, N, obs, obs_stride, rc, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, mu, actions);
-    } else {
-        BG_GRU_LAUNCH(actor_gru_sample_kernel, , N, obs, obs_stride, cell, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, mu, actions);
+    const uint32_t ctr = (uint32_t)counter;
+    const RowCell rc{cell, desc->in};
+    if constexpr (Kind::wide_hidden) {
+        if (H == 512) {
+            if (row && !wide) Kind::template sample<512, 256, KX_ROW>(grid, block, st, N, obs, obs_stride, rc, net, logstd, seed, ctr, reset, s, mu, actions);
+            else if (row) Kind::template sample<512, 512, KX_ROW>(grid, block, st, N, obs, obs_stride, rc, net, logstd, seed, ctr, reset, s, mu, actions);
+            else if (!wide) Kind::template sample<512, 256, KC>(grid, block, st, N, obs, obs_stride, cell, net, logstd, seed, ctr, reset, s, mu, actions);
+            else Kind::template sample<512, 512, KC>(grid, block, st, N, obs, obs_stride, cell, net, logstd, seed, ctr, reset, s, mu, actions);
+            HIP_OK(hipGetLastError());
+            return 0;
+        }
     }
+    if (row) BG_CELL_FORM(Kind::template sample, BG_COMMA KX_ROW, grid, block, st, N, obs, obs_stride, rc, net, logstd, seed, ctr, reset, s, mu, actions);
+    else BG_CELL_FORM(Kind::template sample, BG_COMMA KC, grid, block, st, N, obs, obs_stride, cell, net, logstd, seed, ctr, reset, s, mu, actions);
     HIP_OK(hipGetLastError());
     return 0;
 }
 
-extern "C" int bg_actor_sample_gru(int32_t N, const float* obs, int32_t obs_stride, const bg_gru_desc* gru, int32_t n_layers, const bg_mlp_layer_desc* layers,
-                                   const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, float* mu,
-                                   float* actions, void* stream) {
-    return sample_gru("bg_actor_sample_gru", false, N, obs, obs_stride, gru, n_layers, layers, logstd, seed, counter, reset, h_in, h_out, mu, actions, stream);
-}
-
-extern "C" int bg_actor_sample_gru_row(int32_t N, const float* obs, int32_t obs_stride, const bg_gru_desc* gru, int32_t n_layers, const bg_mlp_layer_desc* layers,
-                                       const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, float* mu,
-                                       float* actions, void* stream) {
-    return sample_gru("bg_actor_sample_gru_row", true, N, obs, obs_stride, gru, n_layers, layers, logstd, seed, counter, reset, h_in, h_out, mu, actions, stream);
-}
-
-// who: the entry point's name; student_obs / student_stride: the rows of the cell's 47 inputs (bg_distill_act_gru: the teacher's)
-static int distill_act_gru(const std::string& who, int32_t N, const float* teacher_obs, int32_t teacher_stride, const float* student_obs, int32_t student_stride,
-                           int32_t n_teacher, const bg_mlp_layer_desc* teacher, int32_t scan_points, const bg_gru_desc* gru, int32_t n_student,
-                           const bg_mlp_layer_desc* student, const float* student_logstd, uint64_t seed, uint64_t counter, float beta, int32_t teacher_noise,
-                           const uint8_t* reset, const float* h_in, float* h_out, float* student_mu, float* actions, float* teacher_mu, void* stream) {
-    if (!(beta >= 0.f && beta <= 1.f))  // (a NaN fails both comparisons)
-        return bg_set_error(-1, (who + ": bad argument (beta: the teacher's probability of acting, a finite number in [0, 1])").c_str());
-    if (N <= 0 || !teacher_obs || !student_obs || !student || !teacher || !student_logstd || !h_in || !h_out || !actions || !teacher_mu)
-        return bg_set_error(-1, (who + ": bad argument").c_str());
-    if (scan_points < 0 || scan_points > BG_MAX_HEIGHT_SCAN_POINTS) return bg_set_error(-1, (who + ": bad argument (scan_points)").c_str());
-    GruCell cell;
-    if (const int rc = fill_cell(who, gru, cell)) return rc;
-    DistillNets nets;
-    int maxw_t = 0, maxw_s = 0;
-    if (const int rc = fill_net((who + " (teacher)").c_str(), n_teacher, teacher, scan_points, nets.n[0], maxw_t)) return rc;
-    if (const int rc = fill_net((who + " (student)").c_str(), n_student, student, 0, nets.n[1], maxw_s, gru->hidden)) return rc;
-    if (teacher_stride != teacher[0].in)
-        return bg_set_error(-4, (who + ": teacher_stride must equal the teacher's first-layer input (47 H + scan_points columns per row)").c_str());
-    if (student_stride < BG_NUM_OBS) return bg_set_error(-1, (who + ": bad argument (student_stride: at least the 47 columns the cell reads)").c_str());
-    const int H = gru->hidden, nb = (N + MR - 1) / MR;
-    const int kp = (teacher[0].in + KC - 1) / KC * KC, maxw = maxw_t > maxw_s ? maxw_t : maxw_s;
-    const bool wide = maxw > 256 || kp > 256;
-    const dim3 grid(2 * nb), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    if (beta > 0.f)
-        BG_GRU_LAUNCH(distill_act_gru_kernel, BG_COMMA true, N, nb, teacher_obs, teacher_stride, student_obs, student_stride, nets, cell, student_logstd, seed, (uint32_t)counter, beta, teacher_noise,
-                      reset, h_in, h_out, student_mu, actions, teacher_mu);
-    else
-        BG_GRU_LAUNCH(distill_act_gru_kernel, BG_COMMA false, N, nb, teacher_obs, teacher_stride, student_obs, student_stride, nets, cell, student_logstd, seed, (uint32_t)counter, beta, teacher_noise,
-                      reset, h_in, h_out, student_mu, actions, teacher_mu);
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int bg_distill_act_gru(int32_t N, const float* teacher_obs, int32_t teacher_stride, int32_t n_teacher, const bg_mlp_layer_desc* teacher,
-                                  int32_t scan_points, const bg_gru_desc* gru, int32_t n_student, const bg_mlp_layer_desc* student, const float* student_logstd,
-                                  uint64_t seed, uint64_t counter, float beta, int32_t teacher_noise, const uint8_t* reset, const float* h_in, float* h_out,
-                                  float* student_mu, float* actions, float* teacher_mu, void* stream) {
-    return distill_act_gru("bg_distill_act_gru", N, teacher_obs, teacher_stride, teacher_obs, teacher_stride, n_teacher, teacher, scan_points, gru, n_student, student,
-                           student_logstd, seed, counter, beta, teacher_noise, reset, h_in, h_out, student_mu, actions, teacher_mu, stream);
-}
-
-extern "C" int bg_distill_act_gru_own(int32_t N, const float* teacher_obs, int32_t teacher_stride, const float* student_obs, int32_t student_stride,
-                                      int32_t n_teacher, const bg_mlp_layer_desc* teacher, int32_t scan_points, const bg_gru_desc* gru, int32_t n_student,
-                                      const bg_mlp_layer_desc* student, const float* student_logstd, uint64_t seed, uint64_t counter, float beta,
-                                      int32_t teacher_noise, const uint8_t* reset, const float* h_in, float* h_out, float* student_mu, float* actions,
-                                      float* teacher_mu, void* stream) {
-    return distill_act_gru("bg_distill_act_gru_own", N, teacher_obs, teacher_stride, student_obs, student_stride, n_teacher, teacher, scan_points, gru, n_student, student,
-                           student_logstd, seed, counter, beta, teacher_noise, reset, h_in, h_out, student_mu, actions, teacher_mu, stream);
-}
-
-// ---- the LSTM cell's entry points
-// wide: the launch has a form for hidden = 512 (bg_actor_sample_lstm: actor_lstm_wide_sample_kernel)
-// row: the launch reads the cell's width from the descriptor (bg_actor_sample_lstm_row: 47 to KX_ROW columns of the actor's row)
-static int fill_lstm(const std::string& who, const bg_lstm_desc* lstm, GruCell& cell, bool wide = false, bool row = false) {
-    if (!lstm || !lstm->W_ih || !lstm->W_hh || !lstm->b_ih || !lstm->b_hh) return bg_set_error(-1, (who + ": bad argument (lstm)").c_str());
-    if (row && (lstm->in < BG_NUM_OBS || lstm->in > KX_ROW)) return bg_set_error(-4, (who + ": the cell takes the actor's row (lstm.in from 47 to 256)").c_str());
-    if (!row && lstm->in != BG_NUM_OBS) return bg_set_error(-4, (who + ": the cell takes one observation (lstm.in = 47)").c_str());
-    if (wide && lstm->hidden == 512) {}
-    else if (lstm->hidden != 128 && lstm->hidden != 256)
-        return bg_set_error(-4, (who + (wide ? ": unsupported lstm.hidden (128, 256 or 512)" : ": unsupported lstm.hidden (128 or 256)")).c_str());
-    if ((uintptr_t)lstm->W_hh & 15) return bg_set_error(-1, (who + ": lstm.W_hh must be 16-byte aligned").c_str());
-    cell = GruCell{lstm->W_ih, lstm->W_hh, lstm->b_ih, lstm->b_hh};  // (the four pointers; the layout is torch.nn.LSTMCell's, 4 hidden rows)
-    return 0;
-}
-
-// row: bg_actor_sample_lstm_row, the cell on the first lstm->in columns of a row (the KX_ROW forms of the two kernels)
-static int sample_lstm(const std::string& who, bool row, int32_t N, const float* obs, int32_t obs_stride, const bg_lstm_desc* lstm, int32_t n_layers,
-                       const bg_mlp_layer_desc* layers, const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out,
-                       const float* c_in, float* c_out, float* mu, float* actions, void* stream) {
-    if (N <= 0 || !obs || !layers || !logstd || !h_in || !h_out || !c_in || !c_out || !actions) return bg_set_error(-1, (who + ": bad argument").c_str());
-    if (!row && obs_stride < BG_NUM_OBS) return bg_set_error(-1, (who + ": bad argument (obs_stride: at least the 47 columns the cell reads)").c_str());
-    GruCell cell;
-    if (const int rc = fill_lstm(who, lstm, cell, true, row)) return rc;
-    if (row && obs_stride < lstm->in) return bg_set_error(-1, (who + ": bad argument (obs_stride: at least the lstm.in columns the cell reads)").c_str());
-    ActorNet net;
-    int maxw = 0;
-    if (const int rc = fill_net((who + " (trunk)").c_str(), n_layers, layers, 0, net, maxw, lstm->hidden)) return rc;
-    const int H = lstm->hidden;
-    const bool wide = maxw > 256;
-    const dim3 grid((N + MR - 1) / MR), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    const RowCell rc{cell, lstm->in};
-    if (H == 512) {
-        if (row && !wide) hipLaunchKernelGGL((actor_lstm_wide_sample_kernel<256, KX_ROW>), grid, block, 0, st, N, obs, obs_stride, rc, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, c_in, c_out, mu, actions);
-        else if (row) hipLaunchKernelGGL((actor_lstm_wide_sample_kernel<512, KX_ROW>), grid, block, 0, st, N, obs, obs_stride, rc, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, c_in, c_out, mu, actions);
-        else if (!wide) hipLaunchKernelGGL(actor_lstm_wide_sample_kernel<256>, grid, block, 0, st, N, obs, obs_stride, cell, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, c_in, c_out, mu, actions);
-        else hipLaunchKernelGGL(actor_lstm_wide_sample_kernel<512>, grid, block, 0, st, N, obs, obs_stride, cell, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, c_in, c_out, mu, actions);
-        HIP_OK(hipGetLastError());
-        return 0;
-    }
-    if (row) BG_GRU_LAUNCH(actor_lstm_sample_kernel, BG_COMMA KX_ROW, N, obs, obs_stride, rc, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, c_in, c_out, mu, actions);
-    else BG_GRU_LAUNCH(actor_lstm_sample_kernel, , N, obs, obs_stride, cell, net, logstd, seed, (uint32_t)counter, reset, h_in, h_out, c_in, c_out, mu, actions);
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int bg_actor_sample_lstm(int32_t N, const float* obs, int32_t obs_stride, const bg_lstm_desc* lstm, int32_t n_layers, const bg_mlp_layer_desc* layers,
-                                    const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, const float* c_in,
-                                    float* c_out, float* mu, float* actions, void* stream) {
-    return sample_lstm("bg_actor_sample_lstm", false, N, obs, obs_stride, lstm, n_layers, layers, logstd, seed, counter, reset, h_in, h_out, c_in, c_out, mu, actions,
-                       stream);
-}
-
-extern "C" int bg_actor_sample_lstm_row(int32_t N, const float* obs, int32_t obs_stride, const bg_lstm_desc* lstm, int32_t n_layers,
-                                        const bg_mlp_layer_desc* layers, const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in,
-                                        float* h_out, const float* c_in, float* c_out, float* mu, float* actions, void* stream) {
-    return sample_lstm("bg_actor_sample_lstm_row", true, N, obs, obs_stride, lstm, n_layers, layers, logstd, seed, counter, reset, h_in, h_out, c_in, c_out, mu,
-                       actions, stream);
-}
-
-// who: the entry point's name; student_obs / student_stride: the rows of the cell's 47 inputs (bg_distill_act_lstm: the teacher's).  distill_act_gru's
-// checks on the same arguments; the two states travel as ONE tensor [2][N][H].
-static int distill_act_lstm(const std::string& who, int32_t N, const float* teacher_obs, int32_t teacher_stride, const float* student_obs, int32_t student_stride,
-                            int32_t n_teacher, const bg_mlp_layer_desc* teacher, int32_t scan_points, const bg_lstm_desc* lstm, int32_t n_student,
+// bg_distill_act_gru / _lstm and their _own forms.  who: the entry point's name; student_obs / student_stride: the rows of the cell's 47 inputs (the
+// teacher's, or with _own the student's buffer).  state_in / state_out: the GRU's h [N][H]; the LSTM's two states as ONE tensor [2][N][H].
+template <class Kind>
+static int distill_act_cell(const std::string& who, int32_t N, const float* teacher_obs, int32_t teacher_stride, const float* student_obs, int32_t student_stride,
+                            int32_t n_teacher, const bg_mlp_layer_desc* teacher, int32_t scan_points, const typename Kind::Desc* desc, int32_t n_student,
                             const bg_mlp_layer_desc* student, const float* student_logstd, uint64_t seed, uint64_t counter, float beta, int32_t teacher_noise,
                             const uint8_t* reset, const float* state_in, float* state_out, float* student_mu, float* actions, float* teacher_mu, void* stream) {
     if (!(beta >= 0.f && beta <= 1.f))  // (a NaN fails both comparisons)
@@ -1051,36 +980,81 @@ static int distill_act_lstm(const std::string& who, int32_t N, const float* teac
         return bg_set_error(-1, (who + ": bad argument").c_str());
     if (scan_points < 0 || scan_points > BG_MAX_HEIGHT_SCAN_POINTS) return bg_set_error(-1, (who + ": bad argument (scan_points)").c_str());
     GruCell cell;
-    if (const int rc = fill_lstm(who, lstm, cell)) return rc;
+    if (const int rc = fill_cell(who, Kind::word, desc, cell)) return rc;
     DistillNets nets;
     int maxw_t = 0, maxw_s = 0;
     if (const int rc = fill_net((who + " (teacher)").c_str(), n_teacher, teacher, scan_points, nets.n[0], maxw_t)) return rc;
-    if (const int rc = fill_net((who + " (student)").c_str(), n_student, student, 0, nets.n[1], maxw_s, lstm->hidden)) return rc;
+    if (const int rc = fill_net((who + " (student)").c_str(), n_student, student, 0, nets.n[1], maxw_s, desc->hidden)) return rc;
     if (teacher_stride != teacher[0].in)
         return bg_set_error(-4, (who + ": teacher_stride must equal the teacher's first-layer input (47 H + scan_points columns per row)").c_str());
     if (student_stride < BG_NUM_OBS) return bg_set_error(-1, (who + ": bad argument (student_stride: at least the 47 columns the cell reads)").c_str());
-    const int H = lstm->hidden, nb = (N + MR - 1) / MR;
+    const int H = desc->hidden, nb = (N + MR - 1) / MR;
     // one LDS form for both halves: the wider hidden layer of the two networks, and the teacher's row tile within its first activation tile
     const int kp = (teacher[0].in + KC - 1) / KC * KC, maxw = maxw_t > maxw_s ? maxw_t : maxw_s;
     const bool wide = maxw > 256 || kp > 256;
     const dim3 grid(2 * nb), block(256);
     hipStream_t st = (hipStream_t)stream;
     if (beta > 0.f)
-        BG_GRU_LAUNCH(distill_act_lstm_kernel, BG_COMMA true, N, nb, teacher_obs, teacher_stride, student_obs, student_stride, nets, cell, student_logstd, seed,
-                      (uint32_t)counter, beta, teacher_noise, reset, state_in, state_out, student_mu, actions, teacher_mu);
+        BG_CELL_FORM(Kind::template distill, BG_COMMA true, grid, block, st, N, nb, teacher_obs, teacher_stride, student_obs, student_stride, nets, cell, student_logstd, seed,
+                     (uint32_t)counter, beta, teacher_noise, reset, state_in, state_out, student_mu, actions, teacher_mu);
     else
-        BG_GRU_LAUNCH(distill_act_lstm_kernel, BG_COMMA false, N, nb, teacher_obs, teacher_stride, student_obs, student_stride, nets, cell, student_logstd, seed,
-                      (uint32_t)counter, beta, teacher_noise, reset, state_in, state_out, student_mu, actions, teacher_mu);
+        BG_CELL_FORM(Kind::template distill, BG_COMMA false, grid, block, st, N, nb, teacher_obs, teacher_stride, student_obs, student_stride, nets, cell, student_logstd, seed,
+                     (uint32_t)counter, beta, teacher_noise, reset, state_in, state_out, student_mu, actions, teacher_mu);
     HIP_OK(hipGetLastError());
     return 0;
+}
+
+extern "C" int bg_actor_sample_gru(int32_t N, const float* obs, int32_t obs_stride, const bg_gru_desc* gru, int32_t n_layers, const bg_mlp_layer_desc* layers,
+                                   const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, float* mu,
+                                   float* actions, void* stream) {
+    return sample_cell<GruKind>("bg_actor_sample_gru", false, N, obs, obs_stride, gru, n_layers, layers, logstd, seed, counter, reset, {h_in, h_out, nullptr, nullptr}, mu,
+                                actions, stream);
+}
+
+extern "C" int bg_actor_sample_gru_row(int32_t N, const float* obs, int32_t obs_stride, const bg_gru_desc* gru, int32_t n_layers, const bg_mlp_layer_desc* layers,
+                                       const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, float* mu,
+                                       float* actions, void* stream) {
+    return sample_cell<GruKind>("bg_actor_sample_gru_row", true, N, obs, obs_stride, gru, n_layers, layers, logstd, seed, counter, reset, {h_in, h_out, nullptr, nullptr},
+                                mu, actions, stream);
+}
+
+extern "C" int bg_distill_act_gru(int32_t N, const float* teacher_obs, int32_t teacher_stride, int32_t n_teacher, const bg_mlp_layer_desc* teacher,
+                                  int32_t scan_points, const bg_gru_desc* gru, int32_t n_student, const bg_mlp_layer_desc* student, const float* student_logstd,
+                                  uint64_t seed, uint64_t counter, float beta, int32_t teacher_noise, const uint8_t* reset, const float* h_in, float* h_out,
+                                  float* student_mu, float* actions, float* teacher_mu, void* stream) {
+    return distill_act_cell<GruKind>("bg_distill_act_gru", N, teacher_obs, teacher_stride, teacher_obs, teacher_stride, n_teacher, teacher, scan_points, gru, n_student,
+                                     student, student_logstd, seed, counter, beta, teacher_noise, reset, h_in, h_out, student_mu, actions, teacher_mu, stream);
+}
+
+extern "C" int bg_distill_act_gru_own(int32_t N, const float* teacher_obs, int32_t teacher_stride, const float* student_obs, int32_t student_stride,
+                                      int32_t n_teacher, const bg_mlp_layer_desc* teacher, int32_t scan_points, const bg_gru_desc* gru, int32_t n_student,
+                                      const bg_mlp_layer_desc* student, const float* student_logstd, uint64_t seed, uint64_t counter, float beta,
+                                      int32_t teacher_noise, const uint8_t* reset, const float* h_in, float* h_out, float* student_mu, float* actions,
+                                      float* teacher_mu, void* stream) {
+    return distill_act_cell<GruKind>("bg_distill_act_gru_own", N, teacher_obs, teacher_stride, student_obs, student_stride, n_teacher, teacher, scan_points, gru, n_student,
+                                     student, student_logstd, seed, counter, beta, teacher_noise, reset, h_in, h_out, student_mu, actions, teacher_mu, stream);
+}
+
+extern "C" int bg_actor_sample_lstm(int32_t N, const float* obs, int32_t obs_stride, const bg_lstm_desc* lstm, int32_t n_layers, const bg_mlp_layer_desc* layers,
+                                    const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in, float* h_out, const float* c_in,
+                                    float* c_out, float* mu, float* actions, void* stream) {
+    return sample_cell<LstmKind>("bg_actor_sample_lstm", false, N, obs, obs_stride, lstm, n_layers, layers, logstd, seed, counter, reset, {h_in, h_out, c_in, c_out}, mu,
+                                 actions, stream);
+}
+
+extern "C" int bg_actor_sample_lstm_row(int32_t N, const float* obs, int32_t obs_stride, const bg_lstm_desc* lstm, int32_t n_layers,
+                                        const bg_mlp_layer_desc* layers, const float* logstd, uint64_t seed, uint64_t counter, const uint8_t* reset, const float* h_in,
+                                        float* h_out, const float* c_in, float* c_out, float* mu, float* actions, void* stream) {
+    return sample_cell<LstmKind>("bg_actor_sample_lstm_row", true, N, obs, obs_stride, lstm, n_layers, layers, logstd, seed, counter, reset, {h_in, h_out, c_in, c_out},
+                                 mu, actions, stream);
 }
 
 extern "C" int bg_distill_act_lstm(int32_t N, const float* teacher_obs, int32_t teacher_stride, int32_t n_teacher, const bg_mlp_layer_desc* teacher,
                                    int32_t scan_points, const bg_lstm_desc* lstm, int32_t n_student, const bg_mlp_layer_desc* student, const float* student_logstd,
                                    uint64_t seed, uint64_t counter, float beta, int32_t teacher_noise, const uint8_t* reset, const float* state_in,
                                    float* state_out, float* student_mu, float* actions, float* teacher_mu, void* stream) {
-    return distill_act_lstm("bg_distill_act_lstm", N, teacher_obs, teacher_stride, teacher_obs, teacher_stride, n_teacher, teacher, scan_points, lstm, n_student, student,
-                            student_logstd, seed, counter, beta, teacher_noise, reset, state_in, state_out, student_mu, actions, teacher_mu, stream);
+    return distill_act_cell<LstmKind>("bg_distill_act_lstm", N, teacher_obs, teacher_stride, teacher_obs, teacher_stride, n_teacher, teacher, scan_points, lstm, n_student,
+                                      student, student_logstd, seed, counter, beta, teacher_noise, reset, state_in, state_out, student_mu, actions, teacher_mu, stream);
 }
 
 extern "C" int bg_distill_act_lstm_own(int32_t N, const float* teacher_obs, int32_t teacher_stride, const float* student_obs, int32_t student_stride,
@@ -1088,6 +1062,7 @@ extern "C" int bg_distill_act_lstm_own(int32_t N, const float* teacher_obs, int3
                                        const bg_mlp_layer_desc* student, const float* student_logstd, uint64_t seed, uint64_t counter, float beta,
                                        int32_t teacher_noise, const uint8_t* reset, const float* state_in, float* state_out, float* student_mu, float* actions,
                                        float* teacher_mu, void* stream) {
-    return distill_act_lstm("bg_distill_act_lstm_own", N, teacher_obs, teacher_stride, student_obs, student_stride, n_teacher, teacher, scan_points, lstm, n_student,
-                            student, student_logstd, seed, counter, beta, teacher_noise, reset, state_in, state_out, student_mu, actions, teacher_mu, stream);
+    return distill_act_cell<LstmKind>("bg_distill_act_lstm_own", N, teacher_obs, teacher_stride, student_obs, student_stride, n_teacher, teacher, scan_points, lstm,
+                                      n_student, student, student_logstd, seed, counter, beta, teacher_noise, reset, state_in, state_out, student_mu, actions, teacher_mu,
+                                      stream);
 }

@@ -17,27 +17,14 @@
 // A step is a chain of dependent round trips (operands from memory, barrier, MFMAs, gates, barrier), one wave per SIMD, so what a step reads from
 // memory is requested in front of MFMAs that do not need it: the forward loads a tile's gi in front of the tile's MFMAs, the backward loads step
 // t - 1's dh_ext, gates and h_prev into registers in front of step t's GEMM.
+// MR, the 32-MFMA step and the two fetches of W_hh are bg_rnn_seq.h's, shared with bg_lstm.hip.
 #include <hip/hip_runtime.h>
 
 #include "bg_common.h"
 #include "bg_gru.h"
+#include "bg_rnn_seq.h"
 
 namespace {
-
-constexpr int MR = 16;  // envs per workgroup
-
-#define BG_GRU_MFMA32(ACC0, ACC1, AROW, WV)                                                                                            \
-    _Pragma("unroll") for (int u = 0; u < 8; u += 2) {                                                                                 \
-        const f32x4 a0 = *reinterpret_cast<const f32x4*>((AROW) + 16 * u), a1 = *reinterpret_cast<const f32x4*>((AROW) + 16 * (u + 1)); \
-        ACC0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, WV[u].x, ACC0, 0, 0, 0);                                                      \
-        ACC1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, WV[u + 1].x, ACC1, 0, 0, 0);                                                  \
-        ACC0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, WV[u].y, ACC0, 0, 0, 0);                                                      \
-        ACC1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, WV[u + 1].y, ACC1, 0, 0, 0);                                                  \
-        ACC0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, WV[u].z, ACC0, 0, 0, 0);                                                      \
-        ACC1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, WV[u + 1].z, ACC1, 0, 0, 0);                                                  \
-        ACC0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, WV[u].w, ACC0, 0, 0, 0);                                                      \
-        ACC1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, WV[u + 1].w, ACC1, 0, 0, 0);                                                  \
-    }
 
 // The forward recurrence of the 16 envs [16 block, 16 block + 16) of one problem: the one body of bg_gru_sequence_forward's kernel (block = blockIdx.x)
 // and of the grouped launch's (block = the workgroup's place among its problem's).
@@ -52,12 +39,7 @@ __device__ __forceinline__ void gru_sequence_forward_body(float (&tile)[2][MR * 
         tile[0][rr * LDH + c] = (h0 && row < N) ? h0[(size_t)row * H + c] : 0.f;
     }
     __syncthreads();
-    // the 8 weight vectors of gate g, column tile j, k-chunk c for this lane: row g H + 16 j + r of W_hh, columns 128 c + 16 u + 4 kg + [0, 4)
-    auto fetch = [&](f32x4 (&w)[8], int g, int j, int c) {
-        const float* wrow = W + (size_t)(g * H + j * 16 + r) * H + c * 128 + 4 * kg;
-#pragma unroll
-        for (int u = 0; u < 8; u++) w[u] = *reinterpret_cast<const f32x4*>(wrow + 16 * u);
-    };
+    auto fetch = [&](f32x4 (&w)[8], int g, int j, int c) { seq_fetch_along_k<H>(w, W, g, j, c, r, kg); };
     int cur = 0;
     for (int t = 0; t < T; t++) {
         float *hc = tile[cur], *hn = tile[cur ^ 1];
@@ -99,12 +81,12 @@ __device__ __forceinline__ void gru_sequence_forward_body(float (&tile)[2][MR * 
                 }
                 const float* arow = hc + r * LDH + c * 128 + 4 * kg;
                 fetch(w1, 1, j, c);
-                BG_GRU_MFMA32(acc[0][0], acc[0][1], arow, w0)
+                BG_RNN_MFMA32(acc[0][0], acc[0][1], arow, w0)
                 fetch(w2, 2, j, c);
-                BG_GRU_MFMA32(acc[1][0], acc[1][1], arow, w1)
+                BG_RNN_MFMA32(acc[1][0], acc[1][1], arow, w1)
                 if (c + 1 < CPT) fetch(w0, 0, j, c + 1);
                 else if (jt + 1 < TPW) fetch(w0, 0, j + 4, 0);
-                BG_GRU_MFMA32(acc[2][0], acc[2][1], arow, w2)
+                BG_RNN_MFMA32(acc[2][0], acc[2][1], arow, w2)
             }
             // gh = acc0 + acc1 first, then gru_gates adds gi: (acc0 + acc1) + gi, the association bg_gru_sequence_forward has always run.  Under this
             // file's -fassociative-math the optimiser is free to split the sum as (acc0 + gi) + acc1, and whether it does depends on the code around
@@ -151,13 +133,8 @@ __device__ __forceinline__ void gru_sequence_backward_body(float (&gt)[MR * (3 *
     const int r0 = block * MR, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, kg = lane >> 4;
     for (int k = threadIdx.x; k < MR * LDH; k += blockDim.x) carry[k] = 0.f;
     __syncthreads();
-    // the 32 weights of column tile j, k-chunk c for this lane: W_hh[128 c + 16 u + 4 kg + e][16 j + r], u = 0 .. 7, e = 0 .. 3
-    auto fetch = [&](f32x4 (&w)[8], int s) {
-        const int j = wave + 4 * (s / CPT), c = s % CPT;
-        const float* wcol = W + (size_t)(c * 128 + 4 * kg) * H + j * 16 + r;
-#pragma unroll
-        for (int u = 0; u < 8; u++) w[u] = f32x4{wcol[(size_t)(16 * u) * H], wcol[(size_t)(16 * u + 1) * H], wcol[(size_t)(16 * u + 2) * H], wcol[(size_t)(16 * u + 3) * H]};
-    };
+    // step s of the GEMM's flat loop over (column tile, k-chunk): tile wave + 4 (s / CPT), chunk s % CPT
+    auto fetch = [&](f32x4 (&w)[8], int s) { seq_fetch_down_rows<H>(w, W, 0, wave + 4 * (s / CPT), s % CPT, r, kg); };
     // a thread's elements of a step's operands (dh_ext, r, z, n, gh_n, h_prev): those of step t - 1 are loaded under step t's GEMM
     constexpr int EPT = MR * H / 256;
     float in[EPT][6];
@@ -213,7 +190,7 @@ __device__ __forceinline__ void gru_sequence_backward_body(float (&gt)[MR * (3 *
             const int j = wave + 4 * (s / CPT), c = s % CPT;
             if (c == 0) acc0 = acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
             const float* arow = gt + r * LDG + c * 128 + 4 * kg;
-            BG_GRU_MFMA32(acc0, acc1, arow, cur)
+            BG_RNN_MFMA32(acc0, acc1, arow, cur)
             if (c == CPT - 1) {
                 const f32x4 v = acc0 + acc1;
                 const int col = j * 16 + r;

@@ -18,27 +18,14 @@
 // Both write every value they produce once and add in a fixed order: deterministic.  What a step reads from memory is requested in front of MFMAs that
 // do not need it: the forward loads the next tile's (at a step's last tile: the next step's first tile's) gi under this tile's MFMAs, the backward
 // loads step t - 1's dh_ext, gates and c_prev into registers under step t's GEMM.
+// MR, the 32-MFMA step and the two fetches of W_hh are bg_rnn_seq.h's, shared with bg_gru.hip.
 #include <hip/hip_runtime.h>
 
 #include "bg_common.h"
 #include "bg_lstm.h"
+#include "bg_rnn_seq.h"
 
 namespace {
-
-constexpr int MR = 16;  // envs per workgroup
-
-#define BG_LSTM_MFMA32(ACC0, ACC1, AROW, WV)                                                                                           \
-    _Pragma("unroll") for (int u = 0; u < 8; u += 2) {                                                                                 \
-        const f32x4 a0 = *reinterpret_cast<const f32x4*>((AROW) + 16 * u), a1 = *reinterpret_cast<const f32x4*>((AROW) + 16 * (u + 1)); \
-        ACC0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, WV[u].x, ACC0, 0, 0, 0);                                                      \
-        ACC1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, WV[u + 1].x, ACC1, 0, 0, 0);                                                  \
-        ACC0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, WV[u].y, ACC0, 0, 0, 0);                                                      \
-        ACC1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, WV[u + 1].y, ACC1, 0, 0, 0);                                                  \
-        ACC0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, WV[u].z, ACC0, 0, 0, 0);                                                      \
-        ACC1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, WV[u + 1].z, ACC1, 0, 0, 0);                                                  \
-        ACC0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, WV[u].w, ACC0, 0, 0, 0);                                                      \
-        ACC1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, WV[u + 1].w, ACC1, 0, 0, 0);                                                  \
-    }
 
 // The forward recurrence of the 16 envs [16 blockIdx.x, 16 blockIdx.x + 16).
 template <int H>
@@ -68,12 +55,7 @@ __global__ __launch_bounds__(256) void lstm_sequence_forward_kernel(int T, int N
         for (int g = 0; g < 4; g++) bias[jt][g] = bh[g * H + col];
     }
     __syncthreads();
-    // the 8 weight vectors of gate g, column tile j, k-chunk kc for this lane: row g H + 16 j + r of W_hh, columns 128 kc + 16 u + 4 kg + [0, 4)
-    auto fetch = [&](f32x4 (&w)[8], int g, int j, int kc) {
-        const float* wrow = W + (size_t)(g * H + j * 16 + r) * H + kc * 128 + 4 * kg;
-#pragma unroll
-        for (int u = 0; u < 8; u++) w[u] = *reinterpret_cast<const f32x4*>(wrow + 16 * u);
-    };
+    auto fetch = [&](f32x4 (&w)[8], int g, int j, int kc) { seq_fetch_along_k<H>(w, W, g, j, kc, r, kg); };
     // the x-side pre-activations of column tile j at step t: v[q][gate]
     auto load_gi = [&](float (&v)[4][4], int t, int j) {
 #pragma unroll
@@ -137,14 +119,14 @@ __global__ __launch_bounds__(256) void lstm_sequence_forward_kernel(int T, int N
             for (int kc = 0; kc < CPT; kc++) {
                 const float* arow = hc + r * LDH + kc * 128 + 4 * kg;
                 fetch(wb, 1, j, kc);
-                BG_LSTM_MFMA32(acc[0][0], acc[0][1], arow, wa)
+                BG_RNN_MFMA32(acc[0][0], acc[0][1], arow, wa)
                 fetch(wa, 2, j, kc);
-                BG_LSTM_MFMA32(acc[1][0], acc[1][1], arow, wb)
+                BG_RNN_MFMA32(acc[1][0], acc[1][1], arow, wb)
                 fetch(wb, 3, j, kc);
-                BG_LSTM_MFMA32(acc[2][0], acc[2][1], arow, wa)
+                BG_RNN_MFMA32(acc[2][0], acc[2][1], arow, wa)
                 if (kc + 1 < CPT) fetch(wa, 0, j, kc + 1);
                 else if (jt + 1 < TPW) fetch(wa, 0, j + 4, 0);
-                BG_LSTM_MFMA32(acc[3][0], acc[3][1], arow, wb)
+                BG_RNN_MFMA32(acc[3][0], acc[3][1], arow, wb)
             }
             float p[4][4];
             {
@@ -186,13 +168,8 @@ __global__ __launch_bounds__(256) void lstm_sequence_backward_kernel(int T, int 
     const int r0 = blockIdx.x * MR, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, kg = lane >> 4;
     for (int k = threadIdx.x; k < MR * LDH; k += blockDim.x) carry[k] = 0.f;
     __syncthreads();
-    // the 32 weights of column tile j, k-chunk kc for this lane: W_hh[128 kc + 16 u + 4 kg + e][16 j + r], u = 0 .. 7, e = 0 .. 3
-    auto fetch = [&](f32x4 (&w)[8], int s) {
-        const int j = wave + 4 * (s / CPT), kc = s % CPT;
-        const float* wcol = W + (size_t)(kc * 128 + 4 * kg) * H + j * 16 + r;
-#pragma unroll
-        for (int u = 0; u < 8; u++) w[u] = f32x4{wcol[(size_t)(16 * u) * H], wcol[(size_t)(16 * u + 1) * H], wcol[(size_t)(16 * u + 2) * H], wcol[(size_t)(16 * u + 3) * H]};
-    };
+    // step s of the GEMM's flat loop over (column tile, k-chunk): tile wave + 4 (s / CPT), chunk s % CPT
+    auto fetch = [&](f32x4 (&w)[8], int s) { seq_fetch_down_rows<H>(w, W, 0, wave + 4 * (s / CPT), s % CPT, r, kg); };
     // a thread's elements of a step's operands (dh_ext, i, f, g, o, tanh(c'), c_prev) and their rows' reset flags: those of step t - 1 are loaded under
     // step t's GEMM
     constexpr int EPT = MR * H / 256;
@@ -254,7 +231,7 @@ __global__ __launch_bounds__(256) void lstm_sequence_backward_kernel(int T, int 
             const int j = wave + 4 * (s / CPT), kc = s % CPT;
             if (kc == 0) acc0 = acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
             const float* arow = gt + r * LDG + kc * 128 + 4 * kg;
-            BG_LSTM_MFMA32(acc0, acc1, arow, cur)
+            BG_RNN_MFMA32(acc0, acc1, arow, cur)
             if (kc == CPT - 1) {
                 const int col = j * 16 + r;
 #pragma unroll
@@ -298,13 +275,8 @@ __global__ __launch_bounds__(256) void lstm_sequence_backward_wide_kernel(int T,
     const int r0 = blockIdx.x * MR, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, kg = lane >> 4;
     for (int k = threadIdx.x; k < MR * LDH; k += blockDim.x) carry[k] = 0.f;
     __syncthreads();
-    // the 32 weights of column tile j, k-chunk kc of pass `pass` for this lane: W_hh[2H pass + 128 kc + 16 u + 4 kg + e][16 j + r], u = 0 .. 7, e = 0 .. 3
-    auto fetch = [&](f32x4 (&w)[8], int pass, int s) {
-        const int j = wave + 4 * (s / CPT), kc = s % CPT;
-        const float* wcol = W + (size_t)(pass * 2 * H + kc * 128 + 4 * kg) * H + j * 16 + r;
-#pragma unroll
-        for (int u = 0; u < 8; u++) w[u] = f32x4{wcol[(size_t)(16 * u) * H], wcol[(size_t)(16 * u + 1) * H], wcol[(size_t)(16 * u + 2) * H], wcol[(size_t)(16 * u + 3) * H]};
-    };
+    // step s of pass `pass` of the GEMM: the rows [2H pass, 2H pass + 2H) of W_hh
+    auto fetch = [&](f32x4 (&w)[8], int pass, int s) { seq_fetch_down_rows<H>(w, W, pass * 2 * H, wave + 4 * (s / CPT), s % CPT, r, kg); };
     float dcc[EPT], dgg[EPT], dout[EPT];
 #pragma unroll
     for (int e = 0; e < EPT; e++) dcc[e] = 0.f;
@@ -382,7 +354,7 @@ __global__ __launch_bounds__(256) void lstm_sequence_backward_wide_kernel(int T,
                     }
                 }
                 const float* arow = gt + r * LDG + kc * 128 + 4 * kg;
-                BG_LSTM_MFMA32(acc0, acc1, arow, cur)
+                BG_RNN_MFMA32(acc0, acc1, arow, cur)
                 if (kc == CPT - 1) {
 #pragma unroll
                     for (int q = 0; q < 4; q++) carry[(kg * 4 + q) * LDH + col] = (pass && rq[q]) ? 0.f : acc0[q] + acc1[q];  // (no other thread reads the tile in this phase)

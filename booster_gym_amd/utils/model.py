@@ -667,54 +667,41 @@ class MLPTrainer:
             torch.sum(self.dw[i], dim=0, out=l.weight.grad)
 
 
-class GRUTrainer:
-    """Forward / backward of a GRU cell in front of an MLPTrainer's network over the T steps of an iteration, for the recurrent student's full-batch
-    update (utils/distill.py; rsl_rl's recurrent `Distillation`: back-propagation through the iteration's steps from the stored state h0).  Rows are
-    [T][N] step-major, B = T N.  Same schedule rules as MLPTrainer: no library GEMM, gradients WRITTEN into the parameters' `.grad`, the weight
-    gradients deferred to the grouped launch (pending_wgrad_problems), the padded copy of W_ih in a WeightCopies under the caller's clock.
-      forward(x)   gi = x W_ih^T + b_ih on all B rows (bg_mlp_layer_forward on the 64-column input), then the recurrence as ONE launch
-                   (bg_gru_sequence_forward) from h0 [N][H] and resets [T][N]; returns h [B][H], the trunk's input;
-      backward()   behind the trunk's backward_hidden: dh_ext = G1 W1, the gradient into the trunk's input that MLPTrainer does not produce (the
-                   same layer kernel on the trunk's transposed first layer), the recurrence backwards as ONE launch (bg_gru_sequence_backward), and
-                   the bias gradients = the column sums of dgi and dgh in a fixed order (bg_elu_backward_colsum without an activation).
-    bias_partial (PPO on a recurrent actor, algorithm.rnn_hidden_size; False: the four launches above, distillation's): the two column sums as ONE
-    launch that leaves a record per 128 rows (bg_gru_bias_partial) and a reduction descriptor for the update's deferred group (backward(finishes=)).
-    The rollout's side of the state lives here too (rollout_begin / rollout_reset / rollout_end): the one statement of which state the recurrence
-    starts from and which env enters which step with a zero state, for Distiller and Runner alike."""
+class CellTrainer:
+    """What GRUTrainer and LSTMTrainer share, written once: the buffers every cell has, the rollout's side of the state, the one check of x / h0 /
+    resets, the x-side GEMM gi = x W_ih^T + b_ih, the GEMM dh_ext = G1 W1 behind the trunk's backward_hidden, the dispatch of the bias gradients'
+    reduction descriptors and the skeleton of the deferred weight gradients.  A cell is described by its number of gates (gi is [rows][gates H]), the
+    width of what the forward recurrence stores for the backward one (`gates` is [rows][stored H]) and the shape of its state h0.  The recurrences
+    themselves, their launches and the bias sums are the subclasses'."""
 
     KIN = 64  # the zero-padded width of the cell's input rows by default (47 observations)
 
-    def __init__(self, cell, trunk, T, N, clock=None, bias_partial=False, kin=None, extra_steps=0):
-        """kin: the zero-padded width of the cell's input rows (pad_input of its real width; default KIN).  extra_steps = E: forward() walks T + E steps,
-        on (T + E) N rows, and backward() differentiates the first T of them (a recurrent critic, algorithm.rnn_critic: the values of the observation
-        after the last step are read, never differentiated)."""
+    def __init__(self, n_gates, stored, state_shape, cell, trunk, T, N, clock, kin, extra_steps=0):
         self.cell, self.trunk, self.T, self.N, self.H = cell, trunk, int(T), int(N), int(cell.hidden_size)
-        self.bias_partial = bool(bias_partial)
+        self._gates, name = int(n_gates), type(self).__name__
         self.kin = int(kin or self.KIN)
         if self.kin not in INPUT_PADS or self.kin < cell.weight_ih.shape[1]:
-            raise ValueError(f"GRUTrainer: an input of {cell.weight_ih.shape[1]} columns padded to {self.kin} (one of {INPUT_PADS}, at least the cell's input)")
+            raise ValueError(f"{name}: an input of {cell.weight_ih.shape[1]} columns padded to {self.kin} (one of {INPUT_PADS}, at least the cell's input)")
         self.TF = self.T + int(extra_steps)  # the steps of the forward pass
-        B, H, dev = self.T * self.N, self.H, cell.weight_ih.device
-        self.B, BF = B, self.TF * self.N
-        self.BF = BF
+        self.B, self.BF = self.T * self.N, self.TF * self.N
+        H, dev = self.H, cell.weight_ih.device
         self.copies = WeightCopies([SimpleNamespace(weight=cell.weight_ih)], clock, self.kin)
-        new = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
-        self.gi, self.h_prev, self.h, self.gates = new(BF, 3 * H), new(BF, H), new(BF, H), new(BF, 4 * H)
-        self.dh_ext, self.dgi, self.dgh = new(B, H), new(B, 3 * H), new(B, 3 * H)
-        self.h0 = new(self.N, H)                                                    # the state entering the iteration (detached)
+        self._new = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+        new = self._new
+        self.gi, self.h_prev, self.h, self.gates = new(self.BF, n_gates * H), new(self.BF, H), new(self.BF, H), new(self.BF, stored * H)
+        self.dh_ext = new(self.B, H)
+        self.h0 = new(*state_shape)                                                 # the state entering the iteration (detached)
         self.resets = torch.zeros(self.TF, self.N, dtype=torch.uint8, device=dev)   # non-zero: the state entering step t of env n is zero
-        self._resets = self.resets                                                  # ... as the last forward() read them (backward() reads the same)
-        self._h0 = self.h0
-        self.next_state = new(self.N, H) if extra_steps else None                   # carry_state()
+        self._resets, self._h0 = self.resets, self.h0                               # ... as the last forward() read them (backward() reads the same)
+        self.next_state = None
         self._zero_bias = new(H)
-        self._cs = new((B + 127) // 128 * (6 if self.bias_partial else 3) * H)  # (bias_partial: one record [6H] per 128 rows)
         self.x = None
         self._pending = False
 
     # ------------------------------------------------------------------ the rollout's side of the state
     def rollout_begin(self, state, last_dones):
-        """At the start of a rollout: the state [N][H] the update's recurrence starts from (detached: the gradient is truncated there) and step 0's
-        reset flags = the done flags of the previous iteration's last step."""
+        """At the start of a rollout: the state (h0's shape) the update's recurrence starts from (detached: the gradient is truncated there) and step
+        0's reset flags = the done flags of the previous iteration's last step."""
         self.h0.copy_(state)
         self.resets[0].copy_(last_dones)
 
@@ -731,6 +718,73 @@ class GRUTrainer:
         if last_dones is not None:
             last_dones.copy_(dones[self.T - 1])
 
+    # ------------------------------------------------------------------ the update's passes
+    def _input_side(self, x, h0, resets):
+        """The check of x / h0 / resets and gi = x W_ih^T + b_ih on all rows of the forward pass; returns the state the recurrence starts from."""
+        lib, st, p, c, name = _lib.load(), _lib.current_stream_ptr(), _lib.ptr, self.cell, type(self).__name__
+        self.x = x
+        h0, self._resets = self.h0 if h0 is None else h0, self.resets if resets is None else resets
+        if h0.shape != self.h0.shape or self._resets.shape != self.resets.shape or self._resets.dtype != torch.uint8 or not (h0.is_contiguous() and self._resets.is_contiguous()):
+            dims = "".join(f"[{d}]" for d in self.h0.shape)
+            raise ValueError(f"{name}.forward: h0 {tuple(h0.shape)} / resets {tuple(self._resets.shape)} are not contiguous {dims} / uint8 [{self.TF}][{self.N}]")
+        if x.shape != (self.BF, self.kin) or not x.is_contiguous():
+            raise ValueError(f"{name}.forward: x {tuple(x.shape)} is not contiguous [{self.BF}][{self.kin}]")
+        self._h0 = h0
+        _lib.check(lib.bg_mlp_layer_forward(self.BF, self.kin, self._gates * self.H, p(x), p(self.copies.get("w0pad", 0)), p(c.bias_ih), p(self.gi), 0, st),
+                   "bg_mlp_layer_forward")
+        return h0
+
+    def _trunk_side(self):
+        """dh_ext = G1 W1 behind the trunk's backward_hidden: the gradient into the trunk's input, which MLPTrainer does not produce."""
+        tr = self.trunk
+        g1, l0 = tr.gin[1], tr.layers[0]  # dL/dz of the trunk's first layer [B][out], behind backward_hidden
+        _lib.check(_lib.load().bg_mlp_layer_forward(self.B, l0.weight.shape[0], self.H, _lib.ptr(g1), _lib.ptr(tr.copies.get("wt", 0)), _lib.ptr(self._zero_bias),
+                                                    _lib.ptr(self.dh_ext), 0, _lib.current_stream_ptr()), "bg_mlp_layer_forward")
+
+    @staticmethod
+    def _dispatch(fins, finishes):
+        """The bias gradients' reduction descriptors: into the caller's deferred group (finishes, a list), or as a bg_reduce_group of their own."""
+        if finishes is not None:
+            finishes.extend(fins)
+        else:
+            from .utils import reduce_group
+            reduce_group(fins)
+
+    def _wgrad_problems(self, dgi, dgh):
+        """(G, A, dW, C_out, C_in (padded), C_in_real) of the cell's two weight gradients, for the grouped launch (GroupedWeightGrad.run): on the B rows
+        the backward pass differentiated, from the gate gradients of the x-side and of the h-side."""
+        if not self._pending:
+            return []
+        self._pending, c, H, B, C = False, self.cell, self.H, self.B, self._gates * self.H
+        return [(dgi, self.x[:B], c.weight_ih.grad, C, self.kin, c.weight_ih.shape[1]), (dgh, self.h_prev[:B], c.weight_hh.grad, C, H, H)]
+
+
+class GRUTrainer(CellTrainer):
+    """Forward / backward of a GRU cell in front of an MLPTrainer's network over the T steps of an iteration, for the recurrent student's full-batch
+    update (utils/distill.py; rsl_rl's recurrent `Distillation`: back-propagation through the iteration's steps from the stored state h0).  Rows are
+    [T][N] step-major, B = T N.  Same schedule rules as MLPTrainer: no library GEMM, gradients WRITTEN into the parameters' `.grad`, the weight
+    gradients deferred to the grouped launch (pending_wgrad_problems), the padded copy of W_ih in a WeightCopies under the caller's clock.
+      forward(x)   gi = x W_ih^T + b_ih on all B rows (bg_mlp_layer_forward on the 64-column input), then the recurrence as ONE launch
+                   (bg_gru_sequence_forward) from h0 [N][H] and resets [T][N]; returns h [B][H], the trunk's input;
+      backward()   behind the trunk's backward_hidden: dh_ext = G1 W1, the gradient into the trunk's input that MLPTrainer does not produce (the
+                   same layer kernel on the trunk's transposed first layer), the recurrence backwards as ONE launch (bg_gru_sequence_backward), and
+                   the bias gradients = the column sums of dgi and dgh in a fixed order (bg_elu_backward_colsum without an activation).
+    bias_partial (PPO on a recurrent actor, algorithm.rnn_hidden_size; False: the four launches above, distillation's): the two column sums as ONE
+    launch that leaves a record per 128 rows (bg_gru_bias_partial) and a reduction descriptor for the update's deferred group (backward(finishes=)).
+    The rollout's side of the state lives here too (rollout_begin / rollout_reset / rollout_end): the one statement of which state the recurrence
+    starts from and which env enters which step with a zero state, for Distiller and Runner alike."""
+
+    def __init__(self, cell, trunk, T, N, clock=None, bias_partial=False, kin=None, extra_steps=0):
+        """kin: the zero-padded width of the cell's input rows (pad_input of its real width; default KIN).  extra_steps = E: forward() walks T + E steps,
+        on (T + E) N rows, and backward() differentiates the first T of them (a recurrent critic, algorithm.rnn_critic: the values of the observation
+        after the last step are read, never differentiated)."""
+        super().__init__(3, 4, (int(N), int(cell.hidden_size)), cell, trunk, T, N, clock, kin, extra_steps)
+        self.bias_partial = bool(bias_partial)
+        B, H, new = self.B, self.H, self._new
+        self.dgi, self.dgh = new(B, 3 * H), new(B, 3 * H)
+        self.next_state = new(self.N, H) if extra_steps else None                   # carry_state()
+        self._cs = new((B + 127) // 128 * (6 if self.bias_partial else 3) * H)  # (bias_partial: one record [6H] per 128 rows)
+
     def carry_state(self):
         """A cell that no rollout launch advances (extra_steps: the critic's): the state the next iteration starts from is this cell's output on step
         T - 1, taken from a forward pass on the parameters the rollout ran on (the update's first, before any optimiser step), on the current stream
@@ -738,24 +792,15 @@ class GRUTrainer:
         then starts the next iteration from it."""
         self.next_state.copy_(self.h[(self.T - 1) * self.N : self.T * self.N])
 
-    # ------------------------------------------------------------------ the update's passes
-    def _input_side(self, x, h0, resets):
-        """gi = x W_ih^T + b_ih on all rows of the forward pass; returns the recurrence's problem (bg_gru_forward_problem) on this trainer's buffers."""
-        lib, st, p, c, H = _lib.load(), _lib.current_stream_ptr(), _lib.ptr, self.cell, self.H
-        self.x = x
-        h0, self._resets = self.h0 if h0 is None else h0, self.resets if resets is None else resets
-        if h0.shape != self.h0.shape or self._resets.shape != self.resets.shape or self._resets.dtype != torch.uint8 or not (h0.is_contiguous() and self._resets.is_contiguous()):
-            raise ValueError(f"GRUTrainer.forward: h0 {tuple(h0.shape)} / resets {tuple(self._resets.shape)} are not contiguous [{self.N}][{H}] / uint8 [{self.TF}][{self.N}]")
-        if x.shape != (self.BF, self.kin) or not x.is_contiguous():
-            raise ValueError(f"GRUTrainer.forward: x {tuple(x.shape)} is not contiguous [{self.BF}][{self.kin}]")
-        self._h0 = h0
-        _lib.check(lib.bg_mlp_layer_forward(self.BF, self.kin, 3 * H, p(x), p(self.copies.get("w0pad", 0)), p(c.bias_ih), p(self.gi), 0, st), "bg_mlp_layer_forward")
+    def _forward_problem(self, x, h0, resets):
+        """The x-side, then the recurrence's problem (bg_gru_forward_problem) on this trainer's buffers."""
+        p, c, h0 = _lib.ptr, self.cell, self._input_side(x, h0, resets)
         return _lib.GruForwardProblem(self.TF, self.N, p(self.gi), p(h0), p(self._resets), p(c.weight_hh), p(c.bias_hh), p(self.h_prev), p(self.h), p(self.gates))
 
     def forward(self, x, h0=None, resets=None):
         """h0 [N][H] / resets [T][N] uint8: the state the recurrence starts from and the reset flags it (and the backward pass behind it) reads, where
         they are not this trainer's own (an env-wise mini-batch: rows of the runner's gathered buffers)."""
-        q = self._input_side(x, h0, resets)
+        q = self._forward_problem(x, h0, resets)
         _lib.check(_lib.load().bg_gru_sequence_forward(q.T, q.N, self.H, q.gi, q.h0, q.reset, q.W_hh, q.b_hh, q.h_prev, q.h, q.gates, _lib.current_stream_ptr()),
                    "bg_gru_sequence_forward")
         return self.h
@@ -764,30 +809,23 @@ class GRUTrainer:
     def forward_group(jobs):
         """jobs = [(trainer, x, h0, resets), ...] (1 to 4 cells of one width): `forward` of every job with the recurrences as ONE launch
         (bg_gru_sequence_forward_group: the single launches' code per cell, bit-identical outputs).  Returns every job's h."""
-        qs = [tr._input_side(x, h0, resets) for tr, x, h0, resets in jobs]
+        qs = [tr._forward_problem(x, h0, resets) for tr, x, h0, resets in jobs]
         arr = (_lib.GruForwardProblem * len(qs))(*qs)
         _lib.check(_lib.load().bg_gru_sequence_forward_group(arr, len(qs), jobs[0][0].H, _lib.current_stream_ptr()), "bg_gru_sequence_forward_group")
         return [tr.h for tr, _, _, _ in jobs]
 
-    def _trunk_side(self):
-        """dh_ext = G1 W1 behind the trunk's backward_hidden; returns the backward recurrence's problem (bg_gru_backward_problem)."""
-        lib, st, p, c, H, tr = _lib.load(), _lib.current_stream_ptr(), _lib.ptr, self.cell, self.H, self.trunk
-        g1, l0 = tr.gin[1], tr.layers[0]  # dL/dz of the trunk's first layer [B][out], behind backward_hidden
-        _lib.check(lib.bg_mlp_layer_forward(self.B, l0.weight.shape[0], H, p(g1), p(tr.copies.get("wt", 0)), p(self._zero_bias), p(self.dh_ext), 0, st),
-                   "bg_mlp_layer_forward")
-        return _lib.GruBackwardProblem(self.T, self.N, p(self.dh_ext), p(self.gates), p(self.h_prev), p(self._resets), p(c.weight_hh), p(self.dgi), p(self.dgh), None)
+    def _backward_problem(self):
+        """dh_ext, then the backward recurrence's problem (bg_gru_backward_problem)."""
+        self._trunk_side()
+        p = _lib.ptr
+        return _lib.GruBackwardProblem(self.T, self.N, p(self.dh_ext), p(self.gates), p(self.h_prev), p(self._resets), p(self.cell.weight_hh), p(self.dgi), p(self.dgh), None)
 
     def _bias_side(self, finishes):
         lib, st, p, c, H = _lib.load(), _lib.current_stream_ptr(), _lib.ptr, self.cell, self.H
         self._pending = True
         if self.bias_partial:
             _lib.check(lib.bg_gru_bias_partial(self.B, H, p(self.dgi), p(self.dgh), p(self._cs), st), "bg_gru_bias_partial")
-            fin = self.bias_finish()
-            if finishes is not None:
-                finishes.append(fin)
-            else:
-                from .utils import reduce_group
-                reduce_group([fin])
+            self._dispatch([self.bias_finish()], finishes)
             return
         for g, b in ((self.dgi, c.bias_ih), (self.dgh, c.bias_hh)):
             _lib.check(lib.bg_elu_backward_colsum(self.B, 3 * H, p(g), None, p(b.grad), p(self._cs), st), "bg_elu_backward_colsum")
@@ -795,7 +833,7 @@ class GRUTrainer:
     def backward(self, finishes=None):
         """finishes (a list; bias_partial only): receives the descriptor of the bias gradients' reduction, for the caller's deferred group; None: it
         runs here, as a bg_reduce_group of its own.  Differentiates the first T steps of the forward pass."""
-        q = self._trunk_side()
+        q = self._backward_problem()
         _lib.check(_lib.load().bg_gru_sequence_backward(q.T, q.N, self.H, q.dh_ext, q.gates, q.h_prev, q.reset, q.W_hh, q.dgi, q.dgh, None, _lib.current_stream_ptr()),
                    "bg_gru_sequence_backward")
         self._bias_side(finishes)
@@ -803,7 +841,7 @@ class GRUTrainer:
     @staticmethod
     def backward_group(trainers, finishes=None):
         """`backward(finishes)` of every trainer (1 to 4 cells of one width) with the recurrences as ONE launch (bg_gru_sequence_backward_group)."""
-        qs = [tr._trunk_side() for tr in trainers]
+        qs = [tr._backward_problem() for tr in trainers]
         arr = (_lib.GruBackwardProblem * len(qs))(*qs)
         _lib.check(_lib.load().bg_gru_sequence_backward_group(arr, len(qs), trainers[0].H, _lib.current_stream_ptr()), "bg_gru_sequence_backward_group")
         for tr in trainers:
@@ -817,15 +855,11 @@ class GRUTrainer:
         return fin
 
     def pending_wgrad_problems(self):
-        """(G, A, dW, C_out, C_in (padded), C_in_real) of the cell's two weight gradients, for the grouped launch (GroupedWeightGrad.run): on the B rows
-        the backward pass differentiated."""
-        if not self._pending:
-            return []
-        self._pending, c, H, B = False, self.cell, self.H, self.B
-        return [(self.dgi, self.x[:B], c.weight_ih.grad, 3 * H, self.kin, c.weight_ih.shape[1]), (self.dgh, self.h_prev[:B], c.weight_hh.grad, 3 * H, H, H)]
+        """The cell's two weight gradients for the grouped launch: (dgi, x) and (dgh, h_prev)."""
+        return self._wgrad_problems(self.dgi, self.dgh)
 
 
-class LSTMTrainer(GRUTrainer):
+class LSTMTrainer(CellTrainer):
     """GRUTrainer's interface around a torch.nn.LSTMCell (PPO on an LSTM actor, algorithm.rnn_cell: "lstm"): the same rollout side, the same passes,
     the same deferred weight and bias gradients, so the Runner's mini-epoch code does not fork.  What differs is the cell:
       the state     ONE tensor [2][N][H], h then c (`h0` here, the model's memory_state): the copies and the zeroing stay one op;
@@ -838,26 +872,11 @@ class LSTMTrainer(GRUTrainer):
     No extra steps (a recurrent critic is a GRU's) and no grouped recurrences."""
 
     def __init__(self, cell, trunk, T, N, clock=None, kin=None):
-        self.cell, self.trunk, self.T, self.N, self.H = cell, trunk, int(T), int(N), int(cell.hidden_size)
+        super().__init__(4, 5, (2, int(N), int(cell.hidden_size)), cell, trunk, T, N, clock, kin)  # (h0: the states entering the iteration, h then c)
         self.bias_partial = True
-        self.kin = int(kin or self.KIN)
-        if self.kin not in INPUT_PADS or self.kin < cell.weight_ih.shape[1]:
-            raise ValueError(f"LSTMTrainer: an input of {cell.weight_ih.shape[1]} columns padded to {self.kin} (one of {INPUT_PADS}, at least the cell's input)")
-        self.TF = self.T
-        B, H, dev = self.T * self.N, self.H, cell.weight_ih.device
-        self.B = self.BF = B
-        self.copies = WeightCopies([SimpleNamespace(weight=cell.weight_ih)], clock, self.kin)
-        new = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
-        self.gi, self.gates, self.dg = new(B, 4 * H), new(B, 5 * H), new(B, 4 * H)
-        self.h_prev, self.c_prev, self.h, self.c, self.dh_ext = new(B, H), new(B, H), new(B, H), new(B, H), new(B, H)
-        self.h0 = new(2, self.N, H)                                                # the states entering the iteration, h then c (detached)
-        self.resets = torch.zeros(self.T, self.N, dtype=torch.uint8, device=dev)   # non-zero: both states entering step t of env n are zero
-        self._resets, self._h0 = self.resets, self.h0
-        self.next_state = None
-        self._zero_bias = new(H)
+        B, H, new = self.B, self.H, self._new
+        self.dg, self.c_prev, self.c = new(B, 4 * H), new(B, H), new(B, H)
         self._cs = new((B + 127) // 128 * 4 * H)  # one record [4H] per 128 rows
-        self.x = None
-        self._pending = False
 
     def carry_state(self):
         raise ValueError("LSTMTrainer: no extra steps, nothing to carry (a recurrent critic's cell is a GRU)")
@@ -865,17 +884,10 @@ class LSTMTrainer(GRUTrainer):
     def forward(self, x, h0=None, resets=None):
         """h0 [2][N][H] / resets [T][N] uint8: the states the recurrence starts from and the reset flags it (and the backward pass behind it) reads,
         where they are not this trainer's own."""
-        lib, st, p, c, H = _lib.load(), _lib.current_stream_ptr(), _lib.ptr, self.cell, self.H
-        self.x = x
-        h0, self._resets = self.h0 if h0 is None else h0, self.resets if resets is None else resets
-        if h0.shape != self.h0.shape or self._resets.shape != self.resets.shape or self._resets.dtype != torch.uint8 or not (h0.is_contiguous() and self._resets.is_contiguous()):
-            raise ValueError(f"LSTMTrainer.forward: h0 {tuple(h0.shape)} / resets {tuple(self._resets.shape)} are not contiguous [2][{self.N}][{H}] / uint8 [{self.T}][{self.N}]")
-        if x.shape != (self.B, self.kin) or not x.is_contiguous():
-            raise ValueError(f"LSTMTrainer.forward: x {tuple(x.shape)} is not contiguous [{self.B}][{self.kin}]")
-        self._h0 = h0
-        _lib.check(lib.bg_mlp_layer_forward(self.B, self.kin, 4 * H, p(x), p(self.copies.get("w0pad", 0)), p(c.bias_ih), p(self.gi), 0, st), "bg_mlp_layer_forward")
-        _lib.check(lib.bg_lstm_sequence_forward(self.T, self.N, H, p(self.gi), p(h0[0]), p(h0[1]), p(self._resets), p(c.weight_hh), p(c.bias_hh), p(self.h_prev),
-                                                p(self.c_prev), p(self.h), p(self.c), p(self.gates), st), "bg_lstm_sequence_forward")
+        p, c, h0 = _lib.ptr, self.cell, self._input_side(x, h0, resets)
+        _lib.check(_lib.load().bg_lstm_sequence_forward(self.T, self.N, self.H, p(self.gi), p(h0[0]), p(h0[1]), p(self._resets), p(c.weight_hh), p(c.bias_hh),
+                                                        p(self.h_prev), p(self.c_prev), p(self.h), p(self.c), p(self.gates), _lib.current_stream_ptr()),
+                   "bg_lstm_sequence_forward")
         return self.h
 
     @staticmethod
@@ -885,20 +897,13 @@ class LSTMTrainer(GRUTrainer):
     def backward(self, finishes=None):
         """finishes (a list): receives the two descriptors of the bias gradients' reductions, for the caller's deferred group; None: they run here, as a
         bg_reduce_group of their own."""
-        lib, st, p, c, H, tr = _lib.load(), _lib.current_stream_ptr(), _lib.ptr, self.cell, self.H, self.trunk
-        g1, l0 = tr.gin[1], tr.layers[0]  # dL/dz of the trunk's first layer [B][out], behind backward_hidden
-        _lib.check(lib.bg_mlp_layer_forward(self.B, l0.weight.shape[0], H, p(g1), p(tr.copies.get("wt", 0)), p(self._zero_bias), p(self.dh_ext), 0, st),
-                   "bg_mlp_layer_forward")
-        _lib.check(lib.bg_lstm_sequence_backward(self.T, self.N, H, p(self.dh_ext), p(self.gates), p(self.c_prev), p(self._resets), p(c.weight_hh), p(self.dg),
-                                                 None, None, st), "bg_lstm_sequence_backward")
+        lib, st, p = _lib.load(), _lib.current_stream_ptr(), _lib.ptr
+        self._trunk_side()
+        _lib.check(lib.bg_lstm_sequence_backward(self.T, self.N, self.H, p(self.dh_ext), p(self.gates), p(self.c_prev), p(self._resets), p(self.cell.weight_hh),
+                                                 p(self.dg), None, None, st), "bg_lstm_sequence_backward")
         self._pending = True
-        _lib.check(lib.bg_lstm_bias_partial(self.B, H, p(self.dg), p(self._cs), st), "bg_lstm_bias_partial")
-        fins = self.bias_finish()
-        if finishes is not None:
-            finishes.extend(fins)
-        else:
-            from .utils import reduce_group
-            reduce_group(fins)
+        _lib.check(lib.bg_lstm_bias_partial(self.B, self.H, p(self.dg), p(self._cs), st), "bg_lstm_bias_partial")
+        self._dispatch(self.bias_finish(), finishes)
 
     @staticmethod
     def backward_group(trainers, finishes=None):
@@ -915,11 +920,8 @@ class LSTMTrainer(GRUTrainer):
         return fins
 
     def pending_wgrad_problems(self):
-        """(G, A, dW, C_out, C_in (padded), C_in_real) of the cell's two weight gradients, for the grouped launch: both on the ONE gate gradient dg."""
-        if not self._pending:
-            return []
-        self._pending, c, H = False, self.cell, self.H
-        return [(self.dg, self.x, c.weight_ih.grad, 4 * H, self.kin, c.weight_ih.shape[1]), (self.dg, self.h_prev, c.weight_hh.grad, 4 * H, H, H)]
+        """The cell's two weight gradients for the grouped launch: both on the ONE gate gradient dg."""
+        return self._wgrad_problems(self.dg, self.dg)
 
 
 class EstimatorActor(torch.nn.Module):
@@ -1195,14 +1197,9 @@ class ActorCritic(torch.nn.Module):
         if key != self._gru_key:
             self._gru_descs, self._gru_key = (self.gru_descriptor(), layer_descriptors(lin)), key
         gd, layers = self._gru_descs
-        if self.memory_cell == "lstm":  # ONE launch as well (bg_actor_sample_lstm), both states of the one tensor [2][N][H] advanced in place
-            name = "bg_actor_sample_lstm" + row
-            _lib.check(getattr(_lib.load(), name)(N, _lib.ptr(obs), obs.shape[-1], gd, len(lin), layers, _lib.ptr(self.logstd), int(seed), int(counter),
-                                                  _lib.ptr(reset), _lib.ptr(h[0]), _lib.ptr(h[0]), _lib.ptr(h[1]), _lib.ptr(h[1]), _lib.ptr(mu_out),
-                                                  _lib.ptr(actions_out), _lib.current_stream_ptr()), name)
-            return actions_out
-        name = "bg_actor_sample_gru" + row
+        # every state advanced in place, (in, out) per state: the GRU's h [N][H]; the LSTM's h and c of the one tensor [2][N][H] (bg_actor_sample_lstm)
+        states = [_lib.ptr(s) for s in ((h[0], h[1]) if self.memory_cell == "lstm" else (h,)) for _ in range(2)]
+        name = f"bg_actor_sample_{self.memory_cell}{row}"
         _lib.check(getattr(_lib.load(), name)(N, _lib.ptr(obs), obs.shape[-1], gd, len(lin), layers, _lib.ptr(self.logstd), int(seed), int(counter),
-                                              _lib.ptr(reset), _lib.ptr(h), _lib.ptr(h), _lib.ptr(mu_out), _lib.ptr(actions_out), _lib.current_stream_ptr()),
-                   name)
+                                              _lib.ptr(reset), *states, _lib.ptr(mu_out), _lib.ptr(actions_out), _lib.current_stream_ptr()), name)
         return actions_out

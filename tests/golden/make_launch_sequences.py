@@ -1,8 +1,10 @@
 """Record the library entry points that two training iterations call, in order, for the supervised paths: a Runner with estimator.enabled and a
-Distiller plain, with student_frame_stack 3, teacher_action_prob 0.5, symmetric_coef 10, student_memory 128 and student_memory 128 with
-teacher_action_prob 0.5; and for the forms of PPO's optimiser step: a Runner under the default plan (bg_update_tail), with _one_launch_tail = False
-(bg_reduce_group, the weight gradients' finish, bg_optimizer_step), with _fused_opt = False (bg_adam_step, bg_adapt_lr) and with
-algorithm.rnn_hidden_size 128 (the GRU trainer in the grouped launch and among the mirrors).  tests/test_gpu_launch_sequences.py holds the tree against the committed record, so a refactor of the host code cannot
+Distiller plain, with student_frame_stack 3, teacher_action_prob 0.5, symmetric_coef 10, student_memory 128, student_memory 128 with
+teacher_action_prob 0.5 and student_memory 128 with student_cell "lstm"; and for the forms of PPO's optimiser step: a Runner under the default plan
+(bg_update_tail), with _one_launch_tail = False (bg_reduce_group, the weight gradients' finish, bg_optimizer_step), with _fused_opt = False
+(bg_adam_step, bg_adapt_lr), with algorithm.rnn_hidden_size 128 (the GRU trainer in the grouped launch and among the mirrors), the same with
+rnn_cell "lstm" (the LSTM trainer), with rnn_cell "lstm" and rnn_input "row" (at one frame and at two), and with rnn_critic (two GRU recurrences).
+tests/test_gpu_launch_sequences.py holds the tree against the committed record, so a refactor of the host code cannot
 drop, add or reorder a launch (a clock tick lost or an order swapped passes the float64 comparisons of the other tests).
 
 The cases run at 128 envs under the `_cfg` helpers of tests/test_gpu_estimator.py and tests/test_gpu_distill.py with the latter's seeded teacher, no BG_*
@@ -31,14 +33,21 @@ RUNNER_CASES = {"runner_estimator": ({}, {}),
                 "ppo_default_plan": (PPO, {}),
                 "ppo_tail_as_three_launches": (PPO, {"_one_launch_tail": False}),
                 "ppo_separate_optimizer_launches": (PPO, {"_fused_opt": False}),
-                "ppo_rnn_hidden_size_128": ({**PPO, "algorithm.rnn_hidden_size": 128}, {})}
+                "ppo_rnn_hidden_size_128": ({**PPO, "algorithm.rnn_hidden_size": 128}, {}),
+                "ppo_rnn_cell_lstm_128": ({**PPO, "algorithm.rnn_hidden_size": 128, "algorithm.rnn_cell": "lstm"}, {}),
+                "ppo_rnn_cell_lstm_128_rnn_input_row": ({**PPO, "algorithm.rnn_hidden_size": 128, "algorithm.rnn_cell": "lstm", "algorithm.rnn_input": "row"}, {}),
+                # (at one frame the row is the 47 observations and "row" takes the launches above: two frames reach bg_actor_sample_lstm_row)
+                "ppo_rnn_cell_lstm_128_rnn_input_row_2_frames": ({**PPO, "algorithm.rnn_hidden_size": 128, "algorithm.rnn_cell": "lstm", "algorithm.rnn_input": "row",
+                                                                  "env.frame_stack": 2, "env.num_observations": 94}, {}),
+                "ppo_rnn_critic_128": ({**PPO, "algorithm.rnn_hidden_size": 128, "algorithm.rnn_critic": True}, {})}
 CASES = {**RUNNER_CASES,  # (every other case: the overrides of a Distiller's config)
          "distill_plain": {},
          "distill_student_frame_stack_3": {"distillation.student_frame_stack": 3},
          "distill_teacher_action_prob": {"distillation.teacher_action_prob": 0.5},
          "distill_symmetric_coef_10": {"distillation.symmetric_coef": 10.0},
          "distill_student_memory_128": {"distillation.student_memory": 128},
-         "distill_student_memory_128_teacher_action_prob": {"distillation.student_memory": 128, "distillation.teacher_action_prob": 0.5}}
+         "distill_student_memory_128_teacher_action_prob": {"distillation.student_memory": 128, "distillation.teacher_action_prob": 0.5},
+         "distill_student_cell_lstm_128": {"distillation.student_memory": 128, "distillation.student_cell": "lstm"}}
 
 
 @contextlib.contextmanager
